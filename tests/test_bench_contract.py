@@ -18,6 +18,13 @@ def test_defaults_without_flags():
     assert (c4.dtype, c4.route, c4.steps, c4.warmup) == ("f32c", "reference", 5, 1)      # BASELINE configs[3]: fp32 contractions
     assert bench.parse_args(["--workload", "c5"]).route == "reference"
     assert bench.PEAK_TFLOPS == {"f64": 78.6, "f32c": 157.3}
+    assert (a.full, a.dump_outputs) == (False, None)
+    # --steps / --warmup given are what runs, also where they equal another workload's defaults
+    c4 = bench.parse_args(["--workload", "c4", "--steps", "60", "--warmup", "10"])
+    assert (c4.steps, c4.warmup) == (60, 10)
+    assert bench.parse_args(["--workload", "c4", "--steps", "7"]).steps == 7
+    f = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert (f.full, f.dump_outputs) == (True, "out")
 
 
 def test_parallelism_text_says_what_the_step_does():
@@ -49,7 +56,7 @@ def _run(args, env=None):
 
 @pytest.mark.gpu
 def test_one_json_line_with_the_agreed_keys():
-    d = _run(["--steps", "4", "--warmup", "1"])
+    d = _run(["--steps", "4", "--warmup", "1", "--full"])
     for k in REQUIRED:
         assert k in d, k
     assert d["metric"].startswith("ELBO iters/sec (T=4096, M=512, x_dim=4, S=32)") and d["unit"] == "iters/sec"
@@ -93,11 +100,54 @@ def test_c1_workload_is_the_actuator_fixture():
     np.testing.assert_array_equal(p2["X"], params["X"])                 # seeded
 
 
+def test_dump_outputs_writes_the_step_result(tmp_path):
+    """--dump-outputs: the 8 sums a step returns and the 7 mean terms finish() makes of them, fp64, under DIR/<name>.npy."""
+    import numpy as np
+    import bench
+    from ffvd_amd._lib import TERM_NAMES
+    from ffvd_amd.distributed import finish
+    sums = np.array([-3.0, 1.5, 2.0, 0.25, -1.0, 4.0, -64.0, 32.0])
+    bench.dump_outputs(str(tmp_path / "out"), sums, finish(sums))
+    got = np.load(tmp_path / "out" / "elbo_sums.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, sums)
+    terms = np.load(tmp_path / "out" / "nll_terms.npy")
+    assert terms.dtype == np.float64 and terms.shape == (len(TERM_NAMES),)
+    np.testing.assert_array_equal(terms, sums[:7] / 32.0)
+
+
+LEAN = ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+        "dtype", "data", "config", "nll"]
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_its_dumped_outputs_repeat(tmp_path):
+    """A plain run times the K steps and nothing else (the extra passes and the CPU baseline are --full's); --dump-outputs
+    holds the last step's result, and a second run with the same arguments computes the same."""
+    import numpy as np
+    runs = []
+    for i in range(2):
+        d = _run(["--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / str(i))])
+        for k in LEAN:
+            assert k in d, k
+        for k in ("roofline", "cpu_baseline", "ms_per_step_without_collective", "train_ms_per_step"):
+            assert k not in d, k
+        assert d["metric"].startswith("ELBO iters/sec (T=4096, M=512, x_dim=4, S=32)") and d["unit"] == "iters/sec"
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["higher_is_better"] is True and d["dtype"] == "f64"
+        assert abs(d["value"] * d["ms_per_step"] / 1e3 - 1.0) < 1e-9
+        sums = np.load(tmp_path / str(i) / "elbo_sums.npy")
+        terms = np.load(tmp_path / str(i) / "nll_terms.npy")
+        assert sums.shape == (8,) and sums[7] == 32.0 and terms.shape == (7,)
+        assert terms[-1] == pytest.approx(d["nll"], rel=1e-15)
+        runs.append((sums, terms))
+    np.testing.assert_allclose(runs[1][0], runs[0][0], rtol=1e-12)
+    np.testing.assert_allclose(runs[1][1], runs[0][1], rtol=1e-12)
+
+
 @pytest.mark.gpu
 def test_c1_line_has_gpu_and_cpu_side_by_side():
     """VERDICT r3 Missing 2: configs[0] -- the one configuration a CPU can run in milliseconds -- with the CPU baseline of ALL chains
     beside it, forward and training step, the whole iteration in one launch."""
-    d = _run(["--workload", "c1", "--steps", "20", "--warmup", "5"])
+    d = _run(["--workload", "c1", "--steps", "20", "--warmup", "5", "--full"])
     for k in REQUIRED:
         assert k in d, k
     assert d["metric"].startswith("ELBO iters/sec (T=512, M=100, x_dim=4, S=10)")

@@ -13,7 +13,7 @@ for i in $(seq $REPS); do
   for v in $A $B; do
     L=$(libpath $v)
     if [ -n "$L" ]; then export FFVD_LIB=$L; else unset FFVD_LIB; fi
-    python bench.py --no-cpu-baseline "$@" 2>/dev/null | python -c "
+    python bench.py --full --no-cpu-baseline "$@" 2>/dev/null | python -c "
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 st = d['roofline']['stage_ms_per_step']
