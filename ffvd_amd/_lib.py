@@ -67,6 +67,11 @@ _SIGNATURES = {
                                           _dp, _dp]),
     "ffvd_op_conditional_precalc": (C.c_int, [C.c_int, _dp, _dp, C.c_int, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp,
                                               _dp, _dp, _dp]),
+    "ffvd_op_conditional_cov": (C.c_int, [C.c_int, _dp, C.c_int, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int,
+                                          C.c_double, _dp, _dp]),
+    "ffvd_op_conditional_precalc_cov": (C.c_int, [C.c_int, _dp, _dp, C.c_int, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp,
+                                                  C.c_int, _dp, _dp]),
+    "ffvd_op_get_rand_full_cov": (C.c_int, [_dp, _dp, _dp, C.c_int, C.c_int, C.c_double, _dp]),
     "ffvd_op_predict_mean": (C.c_int, [_dp, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp]),
     "ffvd_op_logdensity_norm_diag": (C.c_int, [C.c_int, _dp, _dp, _dp, C.c_int, C.c_int, _dp]),
     "ffvd_op_get_rand": (C.c_int, [_dp, _dp, _dp, C.c_int64, _dp]),

@@ -1,4 +1,5 @@
-"""Single-kernel GPflow-style conditional -- counterpart of vfegpssm/conditionals.py (jitter 1e-7, :101).
+"""Single-kernel GPflow-style conditional -- counterpart of vfegpssm/conditionals.py (jitter 1e-7, :101); with full_cov=True
+var is R x N x N.
 
 R independent GPs (columns of f) share ONE kernel; arithmetic identical to conditionals_multi_output."""
 from __future__ import annotations

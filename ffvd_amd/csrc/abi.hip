@@ -2514,24 +2514,49 @@ extern "C" int ffvd_op_kernel_diag(int kind, const double *X, int N, int P, doub
     return FFVD_OK;
 }
 
+// Batched Cholesky of `batch` np x np slabs (identity padded, np % NB == 0) at dA, which the caller uploaded from host_in (left
+// intact); hinfo[b] <- 0 or 1 + first bad pivot.  If the one-launch (dataflow) variant gave up on a bounded wait, the batch is uploaded
+// again from host_in and re-run with the launch-per-column variant, which has no inter-workgroup waits (*recovered = true).
+// Shared by ffvd_op_cholesky and ffvd_op_get_rand_full_cov.
+static int potrf_with_stall_recovery(Scratch &sc, double *dA, const double *host_in, int np, int batch, int32_t *dinfo,
+                                     double *dinv, int32_t *hinfo, bool *recovered, const char *who) {
+    ffvd_handle *h = nullptr;
+    const size_t slab = (size_t)np * np;
+    *recovered = false;
+    for (int attempt = 0;; ++attempt) {
+        {
+            CholOverrideGuard guard;            // reset on the error returns below as well
+            if (attempt == 1) {
+                HIP_TRY(hipMemcpyAsync(dA, host_in, slab * batch * sizeof(double), hipMemcpyHostToDevice, sc.stream));
+                guard.force_left();
+            }
+            HIP_TRY(hipMemsetAsync(dinfo, 0, batch * sizeof(int32_t), sc.stream));
+            launch_potrf_ext(sc.stream, dA, np, 0, 0, batch, slab, dinfo, dinv);
+        }
+        HIP_TRY(hipMemcpyAsync(hinfo, dinfo, batch * sizeof(int32_t), hipMemcpyDeviceToHost, sc.stream));
+        HIP_TRY(hipStreamSynchronize(sc.stream));
+        bool stalled = false;
+        for (int b = 0; b < batch; ++b) stalled = stalled || hinfo[b] < 0;
+        if (!stalled) { *recovered = attempt == 1; return FFVD_OK; }
+        if (attempt == 1)
+            return set_error(nullptr, FFVD_EDEVICE, std::string(who) + ": abandoned, a block row waited more than 1 s for the row above it");
+    }
+}
+
 extern "C" int ffvd_op_cholesky(const double *A, int n, int batch, double *L, int32_t *info) {
     if (!A || !L || n < 1 || batch < 0) return set_error(nullptr, FFVD_EINVAL, "ffvd_op_cholesky: bad argument");
     OP_BEGIN("ffvd_op_cholesky");
     if (batch == 0) return FFVD_OK;
     const int np = round_up(n, NB);
     const size_t slab = (size_t)np * np;
-    std::vector<double> pad(slab * batch);
-    auto fill_pad = [&] {
-        std::fill(pad.begin(), pad.end(), 0.0);
-        for (int b = 0; b < batch; ++b) {
-            double *S = pad.data() + slab * b;
-            for (int i = 0; i < np; ++i) {
-                if (i < n) memcpy(S + (size_t)i * np, A + ((size_t)b * n + i) * n, (size_t)n * sizeof(double));
-                else S[(size_t)i * np + i] = 1.0;
-            }
+    std::vector<double> pad(slab * batch, 0.0);
+    for (int b = 0; b < batch; ++b) {
+        double *S = pad.data() + slab * b;
+        for (int i = 0; i < np; ++i) {
+            if (i < n) memcpy(S + (size_t)i * np, A + ((size_t)b * n + i) * n, (size_t)n * sizeof(double));
+            else S[(size_t)i * np + i] = 1.0;
         }
-    };
-    fill_pad();
+    }
     double *dA = sc.upload(pad.data(), pad.size());
     OP_CHECK(dA, "ffvd_op_cholesky");
     int32_t *dinfo = sc.alloc<int32_t>(batch);
@@ -2540,28 +2565,10 @@ extern "C" int ffvd_op_cholesky(const double *A, int n, int batch, double *L, in
     OP_CHECK(dinv, "ffvd_op_cholesky");
     std::vector<int32_t> hinfo(batch, 0);
     bool recovered = false;
-    for (int attempt = 0;; ++attempt) {
-        // attempt 1 (only after the dataflow launch gave up on a bounded wait): the same batch again with the launch-per-column
-        // Cholesky, which has no inter-workgroup waits (stall recovery, see fetch_with_stall_recovery)
-        {
-            CholOverrideGuard guard;            // reset on the error returns below as well
-            if (attempt == 1) {
-                fill_pad();
-                HIP_TRY(hipMemcpyAsync(dA, pad.data(), pad.size() * sizeof(double), hipMemcpyHostToDevice, sc.stream));
-                guard.force_left();
-            }
-            HIP_TRY(hipMemsetAsync(dinfo, 0, batch * sizeof(int32_t), sc.stream));
-            launch_potrf_ext(sc.stream, dA, np, 0, 0, batch, slab, dinfo, dinv);
-        }
-        HIP_TRY(hipMemcpyAsync(pad.data(), dA, pad.size() * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
-        HIP_TRY(hipMemcpyAsync(hinfo.data(), dinfo, batch * sizeof(int32_t), hipMemcpyDeviceToHost, sc.stream));
-        HIP_TRY(hipStreamSynchronize(sc.stream));
-        bool stalled = false;
-        for (int b = 0; b < batch; ++b) stalled = stalled || hinfo[b] < 0;
-        if (!stalled) { recovered = attempt == 1; break; }
-        if (attempt == 1)
-            return set_error(nullptr, FFVD_EDEVICE, "ffvd_op_cholesky: abandoned, a block row waited more than 1 s for the row above it");
-    }
+    int rc = potrf_with_stall_recovery(sc, dA, pad.data(), np, batch, dinfo, dinv, hinfo.data(), &recovered, "ffvd_op_cholesky");
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(pad.data(), dA, pad.size() * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
+    HIP_TRY(hipStreamSynchronize(sc.stream));
     int bad = -1;
     for (int b = 0; b < batch; ++b) {
         const double *S = pad.data() + slab * b;
@@ -2966,6 +2973,168 @@ extern "C" int ffvd_op_conditional_precalc(int kind, const double *Lm_inverse_se
     HIP_TRY(hipMemcpyAsync(mean, dmean, (size_t)N * D * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
     HIP_TRY(hipMemcpyAsync(var, dvar, (size_t)N * D * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
     HIP_TRY(hipStreamSynchronize(sc.stream));
+    return FFVD_OK;
+}
+
+// Full predictive covariance / q_sqrt inflation of the conditional (ffvd_op_conditional_cov, ffvd_op_conditional_precalc_cov), once
+// the stack W_d = L_d^-T (Mp x Mp, slab stride w_stride) and the hyper-parameters are on the device.  Mean and per-point variance run
+// through the same launches as ffvd_op_conditional / ffvd_op_conditional_precalc (projection with F kept, conditional_finish); then
+//   q_sqrt (M x M slice 0, as given):  E_d = F_d q0 (cov.hip, COV_GEN, q0^T uploaded once for all d);
+//   full_cov:  Sigma_d = K_d(Xnew, Xnew) - F_d F_d^T (+ E_d E_d^T) (cov.hip, COV_SYM), var: D x N x N, its diagonal the per-point
+//              variance (without q_sqrt: that of the full_cov = 0 form bit for bit; with it: the q_sqrt term summed from E's rows);
+//   otherwise: var[:, d] += sum_j E_d[:, j]^2 through qsqrt_inflation (conditionals_multi_output.py:371-380), var: N x D.
+static int conditional_cov_tail(Scratch &sc, const char *who, int kind, const HyperView &hv, const double *W, size_t w_stride,
+                                const double *Xnew, int N, int M, int P, int D, const double *f, const double *q_sqrt, int full_cov,
+                                double *mean, double *var) {
+    ffvd_handle *h = nullptr;
+    const int Mp = round_up(M, NB), Tp = round_up(N, STRIP), ng = (Mp + 511) / 512;
+    double *dX = sc.upload(Xnew, (size_t)N * P), *dU = sc.upload(f, (size_t)M * D);
+    double *rowsq = sc.alloc<double>((size_t)D * ng * Tp), *fmean = sc.alloc<double>((size_t)D * ng * Tp);
+    double *dmean = sc.alloc<double>((size_t)N * D), *dvar = sc.alloc<double>((size_t)N * D);
+    double *F = sc.alloc<double>((size_t)D * Tp * Mp);
+    if (!dX || !dU || !rowsq || !fmean || !dmean || !dvar || !F)
+        return set_error(nullptr, FFVD_ENOMEM, std::string(who) + ": device allocation or upload failed");
+    ProjectArgs pa{};
+    pa.kind = kind; pa.x = dX; pa.x_chain_stride = 0; pa.x_ld = P; pa.x_cols = P; pa.ctrl = nullptr;
+    pa.T = N; pa.Tp = Tp; pa.C = 0; pa.P = P; pa.M = M; pa.Mp = Mp; pa.Dl = D; pa.d_begin = 0; pa.hv = hv;
+    pa.W = W; pa.w_stride = w_stride; pa.U = dU; pa.u_ld = D; pa.b0 = 0; pa.nb = D;
+    pa.F = F; pa.rowsq = rowsq; pa.fmean = fmean; pa.ng = ng;
+    launch_project(sc.stream, pa);                                   // F = A^T = K_fu L^-T (:34 / :349), mean (:48 / :365)
+    if (!full_cov) {
+        double *dQs = q_sqrt ? sc.upload(q_sqrt, (size_t)M * M) : nullptr, *extra = q_sqrt ? sc.alloc<double>((size_t)D * Tp) : nullptr;
+        if (q_sqrt && (!dQs || !extra)) return set_error(nullptr, FFVD_ENOMEM, std::string(who) + ": device allocation or upload failed");
+        if (q_sqrt) launch_qsqrt_inflation(sc.stream, F, (size_t)Tp * Mp, Tp, Mp, M, dQs, extra, N, D);
+        launch_conditional_finish(sc.stream, kind, dX, N, P, hv.variance, rowsq, fmean, ng, Tp, D, dmean, dvar, extra);
+        HIP_TRY(hipMemcpyAsync(mean, dmean, (size_t)N * D * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
+        HIP_TRY(hipMemcpyAsync(var, dvar, (size_t)N * D * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
+        HIP_TRY(hipStreamSynchronize(sc.stream));
+        return FFVD_OK;
+    }
+    double *E = nullptr, *extra = nullptr;
+    if (q_sqrt) {
+        std::vector<double> qt((size_t)Mp * Mp, 0.0);                // q0^T, zero padded: row j = column j of q0
+        for (int k = 0; k < M; ++k)
+            for (int j = 0; j < M; ++j) qt[(size_t)j * Mp + k] = q_sqrt[(size_t)k * M + j];
+        double *dQt = sc.upload(qt.data(), qt.size());
+        E = sc.alloc<double>((size_t)D * Tp * Mp);
+        extra = sc.alloc<double>((size_t)D * Tp);
+        if (!dQt || !E || !extra) return set_error(nullptr, FFVD_ENOMEM, std::string(who) + ": device allocation or upload failed");
+        CovArgs ea{};
+        ea.mode = COV_GEN; ea.A = F; ea.a_stride = (size_t)Tp * Mp; ea.lda = Mp; ea.arows = Tp; ea.K = Mp;
+        ea.B = dQt; ea.b_stride = 0; ea.ldb = Mp; ea.brows = Mp; ea.ncols = Mp;
+        ea.C = E; ea.c_stride = (size_t)Tp * Mp; ea.ldc = Mp; ea.nb = D;
+        launch_cov(sc.stream, ea);                                   // LTA^T = F q0 (:371-376, slice 0 for every dim)
+        launch_row_sumsq(sc.stream, E, (size_t)Tp * Mp, Mp, Mp, N, D, Tp, extra);     // sum_j LTA^2 (:380)
+        HIP_TRY(hipStreamSynchronize(sc.stream));                    // (qt leaves scope: its upload must have completed)
+    }
+    // the per-point variance becomes the diagonal of Sigma_d
+    launch_conditional_finish(sc.stream, kind, dX, N, P, hv.variance, rowsq, fmean, ng, Tp, D, dmean, dvar, extra);
+    double *dS = sc.alloc<double>((size_t)D * N * N);
+    if (!dS) return set_error(nullptr, FFVD_ENOMEM, std::string(who) + ": device allocation failed");
+    CovArgs ca{};
+    ca.mode = COV_SYM; ca.A = F; ca.E = E; ca.a_stride = (size_t)Tp * Mp; ca.lda = Mp; ca.arows = Tp; ca.K = Mp;
+    ca.C = dS; ca.c_stride = (size_t)N * N; ca.ldc = N; ca.N = N; ca.kind = kind; ca.P = P; ca.x = dX;
+    ca.variance = hv.variance; ca.len = hv.len; ca.diag = dvar; ca.nb = D;
+    launch_cov(sc.stream, ca);                                       // K(Xnew) - A^T A (+ LTA^T LTA) (:41-44 full_cov branch)
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(mean, dmean, (size_t)N * D * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
+    if (!sc.download(var, dS, (size_t)D * N * N * sizeof(double)))
+        return set_error(nullptr, FFVD_EDEVICE, std::string(who) + ": device error while copying the covariance out");
+    return FFVD_OK;
+}
+
+static bool cov_args_ok(int kind, const double *Xnew, int N, const double *Z, int M, int P, int D, const double *logvariance,
+                        const double *loglengthscales, const double *f, const double *q_sqrt, int full_cov, const double *mean,
+                        const double *var) {
+    return Xnew && Z && logvariance && f && mean && var && N >= 0 && M >= 1 && P >= 1 && P <= MAXP && D >= 1 &&
+           (kind == FFVD_KERNEL_SE || kind == FFVD_KERNEL_LINEAR) && (kind != FFVD_KERNEL_SE || loglengthscales) &&
+           (full_cov == 0 || full_cov == 1) && (!q_sqrt || M <= 2048) &&
+           (size_t)D * N * N <= ((size_t)1 << 40);
+}
+
+extern "C" int ffvd_op_conditional_cov(int kind, const double *Xnew, int N, const double *Z, int M, int P, int D,
+                                       const double *logvariance, const double *loglengthscales, const double *f,
+                                       const double *q_sqrt, int full_cov, double jitter, double *mean, double *var) {
+    if (!cov_args_ok(kind, Xnew, N, Z, M, P, D, logvariance, loglengthscales, f, q_sqrt, full_cov, mean, var))
+        return set_error(nullptr, FFVD_EINVAL, "ffvd_op_conditional_cov: bad argument");
+    OP_BEGIN("ffvd_op_conditional_cov");
+    if (N == 0) return FFVD_OK;
+    KuuWork w{};
+    int rc = build_kuu(sc, kind, Z, M, P, D, logvariance, loglengthscales, jitter, w, nullptr);
+    if (rc) return set_error(nullptr, rc, "ffvd_op_conditional_cov: device allocation or upload failed");
+    const int Mp = w.Mp;
+    HyperView hv{w.variance, w.len, w.Zs, w.zz};
+    rc = conditional_cov_tail(sc, "ffvd_op_conditional_cov", kind, hv, w.Kuu + (size_t)Mp * Mp, (size_t)2 * Mp * Mp, Xnew, N, M, P,
+                              D, f, q_sqrt, full_cov, mean, var);
+    if (rc) return rc;
+    return check_kuu_info(sc, w, D, "ffvd_op_conditional_cov");
+}
+
+extern "C" int ffvd_op_conditional_precalc_cov(int kind, const double *Lm_inverse_seq, const double *Xnew, int N, const double *Z,
+                                               int M, int P, int D, const double *logvariance, const double *loglengthscales,
+                                               const double *f, const double *q_sqrt, int full_cov, double *mean, double *var) {
+    if (!Lm_inverse_seq || !cov_args_ok(kind, Xnew, N, Z, M, P, D, logvariance, loglengthscales, f, q_sqrt, full_cov, mean, var))
+        return set_error(nullptr, FFVD_EINVAL, "ffvd_op_conditional_precalc_cov: bad argument");
+    OP_BEGIN("ffvd_op_conditional_precalc_cov");
+    if (N == 0) return FFVD_OK;
+    const int Mp = round_up(M, NB);
+    std::vector<double> Wp;
+    double *dW = upload_stack(sc, Lm_inverse_seq, D, M, Mp, Wp);
+    double *dZ = sc.upload(Z, (size_t)M * P), *dlv = sc.upload(logvariance, D), *dll = sc.alloc<double>((size_t)D * P);
+    double *variance = sc.alloc<double>(D), *len = sc.alloc<double>((size_t)D * P);
+    double *Zs = sc.alloc<double>((size_t)D * Mp * P), *zz = sc.alloc<double>((size_t)D * Mp);
+    if (!dW || !dZ || !dlv || !dll || !variance || !len || !Zs || !zz)
+        return set_error(nullptr, FFVD_ENOMEM, "ffvd_op_conditional_precalc_cov: device allocation or upload failed");
+    if (loglengthscales)
+        HIP_TRY(hipMemcpyAsync(dll, loglengthscales, (size_t)D * P * sizeof(double), hipMemcpyHostToDevice, sc.stream));
+    launch_prep_hypers(sc.stream, kind, dZ, M, Mp, P, D, 0, dlv, dll, variance, len, Zs, zz);
+    HyperView hv{variance, len, Zs, zz};
+    return conditional_cov_tail(sc, "ffvd_op_conditional_precalc_cov", kind, hv, dW, (size_t)Mp * Mp, Xnew, N, M, P, D, f, q_sqrt,
+                                full_cov, mean, var);
+}
+
+extern "C" int ffvd_op_get_rand_full_cov(const double *mean, const double *var, const double *eps, int N, int D, double jitter,
+                                         double *out) {
+    if (!mean || !var || !eps || !out || N < 0 || D < 1 || !(jitter >= 0.0) || (size_t)D * N * N > ((size_t)1 << 40))
+        return set_error(nullptr, FFVD_EINVAL, "ffvd_op_get_rand_full_cov: bad argument");
+    OP_BEGIN("ffvd_op_get_rand_full_cov");
+    if (N == 0) return FFVD_OK;
+    const int np = round_up(N, NB);
+    const size_t slab = (size_t)np * np;
+    std::vector<double> pad(slab * D, 0.0);                          // Sigma_d + jitter I, identity padded to np
+    for (int d = 0; d < D; ++d) {
+        double *S = pad.data() + slab * d;
+        for (int i = 0; i < np; ++i) {
+            if (i < N) {
+                memcpy(S + (size_t)i * np, var + ((size_t)d * N + i) * N, (size_t)N * sizeof(double));
+                S[(size_t)i * np + i] += jitter;
+            } else S[(size_t)i * np + i] = 1.0;
+        }
+    }
+    double *dA = sc.upload(pad.data(), pad.size());
+    double *dm = sc.upload(mean, (size_t)N * D), *de = sc.upload(eps, (size_t)N * D), *dO = sc.alloc<double>((size_t)N * D);
+    int32_t *dinfo = sc.alloc<int32_t>(D);
+    double *dinv = sc.alloc<double>(potrf_scratch_doubles(np, D));
+    if (!dA || !dm || !de || !dO || !dinfo || !dinv)
+        return set_error(nullptr, FFVD_ENOMEM, "ffvd_op_get_rand_full_cov: device allocation or upload failed");
+    std::vector<int32_t> hinfo(D, 0);
+    bool recovered = false;
+    int rc = potrf_with_stall_recovery(sc, dA, pad.data(), np, D, dinfo, dinv, hinfo.data(), &recovered, "ffvd_op_get_rand_full_cov");
+    if (rc) return rc;
+    for (int d = 0; d < D; ++d)
+        if (hinfo[d]) {
+            char msg[200];
+            snprintf(msg, sizeof msg, "ffvd_op_get_rand_full_cov: Cholesky of var[%d] + jitter*I failed: latent dim %d, pivot %d is not "
+                     "positive", d, d, hinfo[d] - 1);
+            return set_error(nullptr, FFVD_ENOTPD, msg);
+        }
+    launch_tril_matvec(sc.stream, dA, slab, np, N, D, dm, de, dO);    // mean + L eps (utils.py:4-11, full_cov branch)
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, dO, (size_t)N * D * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
+    HIP_TRY(hipStreamSynchronize(sc.stream));
+    if (recovered)
+        set_error(nullptr, FFVD_OK, "warning: ffvd_op_get_rand_full_cov: the one-launch (dataflow) Cholesky gave up on a bounded wait; "
+                                    "the batch was re-run with the launch-per-column Cholesky and completed");
     return FFVD_OK;
 }
 

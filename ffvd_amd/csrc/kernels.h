@@ -265,6 +265,32 @@ void launch_matvec(hipStream_t stream, const double *W, size_t w_stride, const d
 void launch_qsqrt_inflation(hipStream_t stream, const double *F, size_t f_stride, int Tp, int Mp, int M, const double *Qs,
                             double *extra, int N, int batch);
 
+// Full predictive covariance (cov.hip): one batched fp64 MFMA NT product, 128 x 128 tiles, grid (tiles, nb).
+//   COV_SYM: C[d] (N x N, ld ldc) = K_d(x_i, x_j) - A_d A_d^T + E_d E_d^T (E optional), lower-triangular tiles, each element stored at
+//            (i, j) and (j, i); A, E: [nb] arows x lda (k-contiguous rows, slab stride a_stride, rows >= N zero), depth K.  The seed is
+//            formed from x (N x P), variance [nb], len [nb][P] (prep_hypers) with the arithmetic of launch_kernel_matrix.
+//   COV_GEN: C[d] (arows x ncols, ld ldc) = A_d B_d^T, B_d: brows x ldb rows (b_stride 0: one B for all d), depth K.
+// K is a multiple of 16; lda, ldb even.
+enum { COV_SYM = 0, COV_GEN = 1 };
+struct CovArgs {
+    int mode;
+    const double *A, *E; size_t a_stride; int lda, arows, K;
+    const double *B; size_t b_stride; int ldb, brows, ncols;
+    double *C; size_t c_stride; int ldc;
+    int N, kind, P;
+    const double *x, *variance, *len;
+    const double *diag;     // COV_SYM, optional [N][nb]: C[d][i][i] = diag[i][d] (the per-point variance of the same call)
+    int nb;
+};
+void launch_cov(hipStream_t stream, const CovArgs &a);
+// out[d * out_stride + n] = sum_{j < K} E[d][n][j]^2, n < N (E: slabs of e_stride doubles, row stride ld)
+void launch_row_sumsq(hipStream_t stream, const double *E, size_t e_stride, int ld, int K, int N, int D, size_t out_stride,
+                      double *out);
+// out[i][d] = mean[i][d] + sum_{j <= i} L[d][i][j] eps[j][d]  (N x D, row-major); L: [D] slabs of l_stride doubles, row stride ld,
+// lower triangle only read
+void launch_tril_matvec(hipStream_t stream, const double *L, size_t l_stride, int ld, int N, int D, const double *mean,
+                        const double *eps, double *out);
+
 // operator-API elementwise kernels
 void launch_predict_mean(hipStream_t stream, const double *X, int N, int D, const double *CC, const double *DD, int J,
                          double *out);

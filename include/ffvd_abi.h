@@ -388,6 +388,30 @@ int  ffvd_op_collapse_u_mean(int kind, const double *Lm_inverse_seq, const doubl
 int  ffvd_op_conditional_precalc(int kind, const double *Lm_inverse_seq, const double *Xnew, int N, const double *Z,
                                  int M, int P, int D, const double *logvariance, const double *loglengthscales,
                                  const double *f, const double *q_sqrt, double *mean, double *var);
+/* conditional(Xnew, Z, kern, f, full_cov=..., q_sqrt=..., white=True) (conditionals_multi_output.py:73-120 -> base_conditional
+ * :6-70), per latent dim d with F_d = K_d(Xnew, Z) L_d^-T (N x M) and L_d = chol(K_d(Z, Z) + jitter I):
+ *   mean: N x D, the same values as ffvd_op_conditional.
+ *   full_cov = 0: var N x D, var[:, d] = Kdiag_d(Xnew) - sum_j F_d[:, j]^2 (+ sum_j E_d[:, j]^2 with q_sqrt).
+ *   full_cov = 1: var D x N x N (GPflow's R x N x N layout), var[d] = K_d(Xnew, Xnew) - F_d F_d^T (+ E_d E_d^T with q_sqrt),
+ *                 exactly symmetric.  The reference's final stacking (`[:, :, 0]` and a transpose, :120) is written for N x 1
+ *                 blocks and does not return a covariance for N x N ones: not reproduced.
+ * q_sqrt: NULL, or the M x M slice 0 of the D x M x M stack, used as given (no triangle mask): E_d = F_d q_sqrt for EVERY d -- the
+ * convention of ffvd_op_conditional_precalc (the reference hands the whole stack to every dim and keeps index 0).  A 2-D (M x D)
+ * q_sqrt is the slice diag(q_sqrt[:, 0]) (built by the caller).  M <= 2048 when q_sqrt is given.
+ * Returns FFVD_EINVAL (before any device work) on a null pointer, N < 0, full_cov not 0 / 1, M > 2048 with q_sqrt. */
+int  ffvd_op_conditional_cov(int kind, const double *Xnew, int N, const double *Z, int M, int P, int D,
+                             const double *logvariance, const double *loglengthscales, const double *f, const double *q_sqrt,
+                             int full_cov, double jitter, double *mean, double *var);
+/* conditional_after_kernel_precalculation(..., full_cov=..., q_sqrt=..., white=True) (conditionals_multi_output.py:306-387): as
+ * ffvd_op_conditional_cov with the caller's stack Lm_inverse_seq = L_d^-T (D x M x M) instead of the factorisation. */
+int  ffvd_op_conditional_precalc_cov(int kind, const double *Lm_inverse_seq, const double *Xnew, int N, const double *Z, int M,
+                                     int P, int D, const double *logvariance, const double *loglengthscales, const double *f,
+                                     const double *q_sqrt, int full_cov, double *mean, double *var);
+/* get_rand((mean, var), eps, full_cov=True) (utils.py:4-11): the joint draw out[:, d] = mean[:, d] + L_d eps[:, d],
+ * L_d = chol(var[d] + jitter I).  mean, eps, out: N x D; var: D x N x N (ffvd_op_conditional_cov, full_cov = 1).  The DGP code the
+ * reference derives get_rand from uses jitter 1e-7.  A var[d] + jitter I that is not positive definite returns FFVD_ENOTPD; the
+ * message names the dim and the pivot. */
+int  ffvd_op_get_rand_full_cov(const double *mean, const double *var, const double *eps, int N, int D, double jitter, double *out);
 /* Gaussian.predict_mean(X_end) = X_end @ CC + DD (likelihoods.py:76-79). X_end: N x D, out: N x Ydim. */
 int  ffvd_op_predict_mean(const double *X_end, int N, int D, const double *CC, const double *DD, int Ydim, double *out);
 /* logdensity_norm_diag (nonvec = 0, out: N; likelihoods.py:96-111) / logdensity_norm_diag_nonvec (nonvec = 1,
