@@ -443,15 +443,20 @@ int  ffvd_op_release_cache(void);
  * d = 0 slice or NULL as in ffvd_op_conditional_precalc), then x_next = x + f_mu + eps * sqrt(f_var + Q) (:304-306).
  * x_last: D (= layers[-1].X[-1], :226); ctrl: steps x C, row t = control_inputs[Y_train.shape[0] + t] (:293), NULL when
  * C = 0; f = U_val: M x D; eps: steps x R x D standard-normal draws (injected); outputs R x steps x D:
- * predict_x (:313) and predict_var = f_var + Q (:314). */
+ * predict_x (:313) and predict_var = f_var + Q (:314).
+ * M <= 2048, P = D + C <= 32.  Lm_inverse_seq must be upper triangular, as ffvd_op_kernel_pre_cal returns it: the step products skip
+ * its strict lower triangle without reading it (and that of W q_sqrt when the q_sqrt slice is upper triangular, which is checked).
+ * Which form runs: the resident-operand loop when R <= 32 (R <= 64 with FFVD_STEP_LOOP=2), M <= 512, D <= 8 and P <= 8; otherwise
+ * per-step launches, the skinny step product for R <= 512 and the tiled projection beyond. */
 int  ffvd_op_rollout(int kind, const double *Lm_inverse_seq, const double *Z, int M, int P, int D,
                      const double *logvariance, const double *loglengthscales, const double *f, const double *q_sqrt,
                      const double *x_last, int R, const double *ctrl, int C, int steps, const double *log_Q,
                      const double *eps, double *predict_x, double *predict_var);
 /* How many ffvd_op_rollout calls of this process completed on the per-step launches because the resident-operand loop (the default
- * up to 64 rollouts, M <= 512) gave up on a bounded wait -- its workgroups must all be resident, a co-tenant can prevent that.  The
- * two forms agree to 1e-9 but not bit for bit: a seeded rollout is bit-reproducible only while this counter stands still (or with
- * FFVD_STEP_LOOP=0, which always takes the launches).  The call that fell back also leaves a warning in ffvd_last_error(NULL). */
+ * up to 32 rollouts, up to 64 with FFVD_STEP_LOOP=2; M <= 512) gave up on a bounded wait -- its workgroups must all be resident, a
+ * co-tenant can prevent that.  The two forms agree to 1e-9 but not bit for bit: a seeded rollout is bit-reproducible only while this
+ * counter stands still (or with FFVD_STEP_LOOP=0, which always takes the launches).  The call that fell back also leaves a warning
+ * in ffvd_last_error(NULL). */
 int  ffvd_op_rollout_fallbacks(void);
 
 /* One particle-Gibbs sweep over the latent trajectory: the INTENT of BaseModel.PG_for_X_speedup (base_model.py:78-138;
@@ -465,7 +470,8 @@ int  ffvd_op_rollout_fallbacks(void);
  * X_ref: X_N x D; Y: (X_N-1) x Ydim; ctrl: (X_N-1) x C or NULL; Rchols: Ydim x Ydim lower-triangular (= exp(log_Rchols),
  * likelihood.Rchols), Ydim <= 8; eps: (X_N-1) x n_free x D; unif: (X_N-1) x n_free in [0, 1).
  * Outputs: particles X_N x n_free x D (resampled_X of :133) and idx (X_N-1) x n_free (int32, value n_free = reference).
- * The final choice (:135-137) is the caller's: X <- particles[:, final_index] unless final_index == n_free. */
+ * The final choice (:135-137) is the caller's: X <- particles[:, final_index] unless final_index == n_free.
+ * M <= 2048, P = D + C <= 32, n_free + 1 <= 1024; Lm_inverse_seq upper triangular as for ffvd_op_rollout. */
 int  ffvd_op_pg_sweep(int kind, const double *Lm_inverse_seq, const double *Z, int M, int P, int D,
                       const double *logvariance, const double *loglengthscales, const double *U, const double *X_ref,
                       int X_N, const double *Y, int Ydim, const double *ctrl, int C, const double *CC, const double *DD,
