@@ -130,33 +130,16 @@ VARIANTS = {
     "dfstall": ["-DFFVD_DF_TEST_STALL"],
     # wall-clock stamps inside the dataflow Cholesky (tools/df_trace.py)
     "dftrace": ["-DFFVD_DF_TRACE"],
-    # A/B builds (tools/ab.sh) of the round-3 Gram schedule: without the tail split / without combos and tail split (= round 2)
-    "notail": ["-DGRAM_TAIL_SPLIT=0"],
-    "r2gram": ["-DGRAM_COMBO=0", "-DGRAM_TAIL_SPLIT=0"],
-    # ... and round 3's Gram schedule (three 64 x 32-sub-block combos per four diagonal tiles) against round 4's pair combos
-    "r3gram": ["-DGRAM_COMBO=1"],
-    # the 64-pivot diagonal factor of the dataflow Cholesky by wavefront 0 alone (round 3) against all four wavefronts (round 4)
-    "factor1w": ["-DDF_FACTOR_4W=0"],
-    "factortiles": ["-DDF_FACTOR_ROWS=0"],
-    "dftrace_factortiles": ["-DFFVD_DF_TRACE", "-DDF_FACTOR_ROWS=0"],
-    "offdiagglds": ["-DGRAM_GLDS_OFFDIAG=1"],       # off-diagonal Gram tiles staged by LDS-DMA like the pair combos (measured neutral)
-    "dftrace_notail": ["-DFFVD_DF_TRACE", "-DGRAM_TAIL_SPLIT=0"],
     # tiny.hip (the one-launch iteration): wall-clock stamps of every workgroup's phases (tools/tiny_trace.py); a build whose
     # unit-0 head never publishes W, so that every bounded wait of that launch must give up (tests/test_gpu_tiny.py)
     "tinytrace": ("tiny.hip", ["-DFFVD_TINY_TRACE"]),
     "tinystall": ("tiny.hip", ["-DFFVD_TINY_TEST_STALL"]),
-    # A/B build: the head does not take row blocks of the K_uu side (tools/dbg_cmp.py diffs the scratch block of two builds)
-    "tinynohelp": ("tiny.hip", ["-DFFVD_TINY_NO_HEAD_HELP"]),
-    # A/B build: the blocked Cholesky of the one-launch iteration with tile solves behind every pivot chain (round 4, first form)
-    "tinytiles": ("tiny.hip", ["-DTINY_CHOL_ROWS=0"]),
     # the resident rollout loop with release / acquire fences at its hand-offs (inside the HIP memory model; tests compare both forms)
     "rrfenced": ("loops.hip", ["-DFFVD_RR_FENCED"]),
-    # wall-clock stamps of every workgroup of the skinny product of a rollout / particle-Gibbs step (tools/step_trace.py)
     # wall-clock stamps of every workgroup of the fused backward product (tools/bwd_trace.py)
     "bwdtrace": ("grad.hip", ["-DFFVD_BWD_TRACE"]),
-    "bwdtrace_base": ("grad.hip", ["-DFFVD_BWD_TRACE", "-DBWD_EPI_XWF=0"]),
-    "bwdtrace_vsf": ("grad.hip", ["-DFFVD_BWD_TRACE", "-DBWD_EPI_VSF=1"]),
-    "steptrace": ["-DFFVD_STEP_TRACE"], "steptrace4": ["-DFFVD_STEP_TRACE", "-DFFVD_SKINNY_CHUNK=4"],
+    # wall-clock stamps of every workgroup of the skinny product of a rollout / particle-Gibbs step (tools/step_trace.py)
+    "steptrace": ["-DFFVD_STEP_TRACE"],
 }
 
 

@@ -11,6 +11,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <atomic>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -20,7 +21,7 @@
 using namespace ffvd;
 
 static thread_local std::string g_last_error;
-static int g_rollout_fallbacks = 0;     // ffvd_op_rollout calls of this process that fell back from the resident loop to the per-step launches
+static std::atomic<int> g_rollout_fallbacks{0};     // ffvd_op_rollout calls of this process that fell back from the resident loop to the per-step launches
 
 #define HIP_TRY(expr)                                                                         \
     do {                                                                                      \
@@ -56,24 +57,18 @@ struct ffvd_handle {
     int64_t ws_bytes = 0;
     // diagnostic switches, read from the environment ONCE when the handle is created
     struct Switches {
-        bool fused_project = false, grad_explicit = false, no_defer_trace = false, no_late_join = false;
-        bool no_main_first = false, no_kfu_first = false, atb128 = false, grad_serial = false, kuu_flow = true, kinv_gram = false, chain_rl = false;
-        int small_side_rows = 32;         // FFVD_SMALL_SIDE_ROWS: block rows of the K_uu chain (Dl * 2 * Mp / 64) up to which the side chain is ONE dataflow launch
-        int small_side_wgs = 512;         // FFVD_SMALL_SIDE_WGS: tile-pass workgroups (one round of the chip) up to which an iteration counts as tiny (see small_side)
-        bool no_small_side = false;       // FFVD_NO_SMALL_SIDE=1: tiny iterations keep the launch-per-step K_uu chain (round 2)
-        bool no_side_late = false;        // FFVD_NO_SIDE_LATE=1: few-chain forward iterations keep the K_uu chain beside the tile pass (round 4, first half)
-        bool ref_row_in_gram = false;     // FFVD_REF_ROW_IN_GRAM=1: reference route, delta^T F formed by the Gram kernel's diagonal tiles (rounds 1-2)
-        bool no_ref_side = false;         // FFVD_NO_REF_SIDE=1: reference route / explicit-U branch with the K_uu chain on the main stream in front of the K_fu build
+        bool grad_explicit = false;       // FFVD_GRAD_EXPLICIT=1: the explicit-inverse backward pass
+        bool no_defer_trace = false;      // FFVD_NO_DEFER_TRACE=1: trace partials in the Gram / combine epilogue (the main stream then waits for K^-1)
+        bool no_kfu_first = false;        // FFVD_NO_KFU_FIRST=1: the side chain enqueued before the main stream's K_fu build (unsplit pass with raw tiles)
+        bool grad_serial = false;         // FFVD_GRAD_SERIAL=1: the K_uu side of the backward pass on the main stream
         bool no_linear_lowrank = false;   // FFVD_NO_LINEAR_LOWRANK=1: LinearK explicit-U forward through the M-wide projection (rounds 1-2)
         bool lt_armed = false;            // FFVD_GRAD_LT_ARMED=1: write the L^T rows to memory (launch_set_lt_rows) even where the dataflow kernel could read L itself
         bool whiten_products = false;     // FFVD_GRAD_WHITEN_PRODUCTS=1: training forward forms H = W^T A W with two products (round 1/2) instead of arming L^T rows
         bool debug_sync = false;    // FFVD_DEBUG_SYNC: name every launch group on stderr and wait for it (locates a faulting kernel)
         int side_delay_us = 0;      // FFVD_DEBUG_SIDE_DELAY_US=n: a spin kernel of n us at the head of every side-stream fork (schedule tests: results
         int main_delay_us = 0;      //   must not depend on which stream is late); FFVD_DEBUG_MAIN_DELAY_US=n: the same on the main stream behind a fork
-        bool tiny_xcd = true;       // FFVD_TINY_NO_XCD=1: the one-launch iteration with role-major workgroup ids instead of a unit's workgroups on ONE XCD
         bool no_tiny = false;       // FFVD_NO_TINY=1: the multi-kernel schedule also at the reference's own experiment size (rounds 1-3)
         bool no_tiny_a = false;     // FFVD_NO_TINY_A=1: ... for the explicit-U branch only (rounds 1-4)
-        bool no_early_priors = false;   // FFVD_NO_EARLY_PRIORS=1: the parameter-only sums inside the finalize launch at the iteration's tail (rounds 1-4)
     } sw;
     // resident parameters / data (handle-owned copies)
     double *X = nullptr, *Z = nullptr, *U = nullptr, *logvar = nullptr, *loglen = nullptr, *logQ = nullptr;
@@ -88,14 +83,6 @@ struct ffvd_handle {
     double *stage = nullptr;    // staging buffer of ffvd_allreduce_sum
     int64_t stage_count = 0;
     bool kuu_flow_sched = false;   // schedule of the big unsplit Gram pass, decided in ffvd_create (see there)
-    // pass-pipelined forward iteration (enqueue_elbo_pipe; FFVD_PIPE=<passes>, FFVD_PIPE_MODE=<bits>): streams for the K_fu builds
-    // of later passes and for every other pass's Gram launch, one event per pass and stage, one Cholesky scratch region per pass
-    int pipe_passes = 0, pipe_mode = 0;
-    hipStream_t pipe_build = nullptr, pipe_gram = nullptr, pipe_chol = nullptr;
-    std::vector<hipEvent_t> pipe_evB, pipe_evG;
-    hipEvent_t pipe_evC = nullptr;
-    double *pipe_dinv = nullptr;
-    size_t pipe_dinv_stride = 0;
     // one-launch iteration of the reference's own experiment size (tiny.hip): decided once in ffvd_create
     TinyPlan tiny{};
     double *tiny_scratch = nullptr;
@@ -116,7 +103,7 @@ struct ffvd_handle {
     // per-unit sums of F^2 (fp64)
     float *Kf32 = nullptr, *F32 = nullptr, *Linv32 = nullptr;
     double *sqpart = nullptr, *sqsum = nullptr;
-    int nsq = 0, gram_flush = 0;
+    int nsq = 0;
     double *Kcopy = nullptr, *Linv = nullptr, *Kinv = nullptr, *trpart = nullptr, *kterms = nullptr;   // GRAM route
     int ntiles = 0;
     double *chain_partial = nullptr;
@@ -176,6 +163,11 @@ struct ffvd_handle {
     size_t ev_used = 0;
 };
 
+// fixed sizes of the schedule (plan_schedule, create_impl)
+constexpr int F32C_FLUSH_TILES = 128;       // fp32 summation chains of the Gram product are cut every 4096 rows (128 t-tiles of 32 rows)
+constexpr int SMALL_SIDE_WGS = 512;         // tile-pass workgroups (one round of the chip) up to which an iteration counts as tiny (small_side)
+constexpr int SMALL_SIDE_ROWS = 32;         // block rows of the K_uu chain (Dl * 2 * Mp / 64) up to which that iteration's side chain is ONE dataflow launch
+
 static int set_error(ffvd_handle *h, int code, const std::string &msg) {
     if (h) h->err = msg;
     g_last_error = msg;
@@ -221,11 +213,6 @@ extern "C" int ffvd_destroy(ffvd_handle *h) {
     if (h->ev_go) hipEventDestroy(h->ev_go);
     if (h->ev_hwords) hipEventDestroy(h->ev_hwords);
     if (h->ev_prior) hipEventDestroy(h->ev_prior);
-    for (hipEvent_t e : h->pipe_evB) hipEventDestroy(e);
-    for (hipEvent_t e : h->pipe_evG) hipEventDestroy(e);
-    if (h->pipe_evC) hipEventDestroy(h->pipe_evC);
-    for (hipStream_t ps : {h->pipe_build, h->pipe_gram, h->pipe_chol})
-        if (ps) { hipStreamSynchronize(ps); hipStreamDestroy(ps); }
     if (h->stream) hipStreamDestroy(h->stream);
     delete h;
     return FFVD_OK;
@@ -236,15 +223,12 @@ static int create_impl(const ffvd_config *cfg, ffvd_handle *h) {
     {
         auto on = [](const char *name) { const char *e = getenv(name); return e && *e && strcmp(e, "0") != 0; };
         ffvd_handle::Switches &w = h->sw;
-        w.fused_project = on("FFVD_FUSED_PROJECT");   w.grad_explicit = on("FFVD_GRAD_EXPLICIT");
-        w.no_defer_trace = on("FFVD_NO_DEFER_TRACE"); w.no_late_join = on("FFVD_NO_LATE_JOIN");
-        w.no_main_first = on("FFVD_NO_MAIN_FIRST");   w.no_kfu_first = on("FFVD_NO_KFU_FIRST");
-        w.whiten_products = on("FFVD_GRAD_WHITEN_PRODUCTS");   w.lt_armed = on("FFVD_GRAD_LT_ARMED");   w.no_small_side = on("FFVD_NO_SMALL_SIDE");   w.no_side_late = on("FFVD_NO_SIDE_LATE");   if (const char *e = getenv("FFVD_SMALL_SIDE_WGS")) w.small_side_wgs = atoi(e);   if (const char *e = getenv("FFVD_SMALL_SIDE_ROWS")) w.small_side_rows = atoi(e);   w.ref_row_in_gram = on("FFVD_REF_ROW_IN_GRAM");   w.no_ref_side = on("FFVD_NO_REF_SIDE");   w.no_linear_lowrank = on("FFVD_NO_LINEAR_LOWRANK");
-        w.kuu_flow = !on("FFVD_NO_KUU_FLOW");   w.kinv_gram = on("FFVD_KINV_GRAM");   w.chain_rl = on("FFVD_CHAIN_RL");
-        w.atb128 = on("FFVD_ATB128");                 w.grad_serial = on("FFVD_GRAD_SERIAL");
+        w.grad_explicit = on("FFVD_GRAD_EXPLICIT");   w.no_defer_trace = on("FFVD_NO_DEFER_TRACE");
+        w.no_kfu_first = on("FFVD_NO_KFU_FIRST");     w.grad_serial = on("FFVD_GRAD_SERIAL");
+        w.whiten_products = on("FFVD_GRAD_WHITEN_PRODUCTS");   w.lt_armed = on("FFVD_GRAD_LT_ARMED");
+        w.no_linear_lowrank = on("FFVD_NO_LINEAR_LOWRANK");
         w.debug_sync = on("FFVD_DEBUG_SYNC");
         w.no_tiny = on("FFVD_NO_TINY");               w.no_tiny_a = on("FFVD_NO_TINY_A");
-        w.no_early_priors = on("FFVD_NO_EARLY_PRIORS");               w.tiny_xcd = !on("FFVD_TINY_NO_XCD");
         if (const char *e = getenv("FFVD_DEBUG_SIDE_DELAY_US")) w.side_delay_us = atoi(e);
         if (const char *e = getenv("FFVD_DEBUG_MAIN_DELAY_US")) w.main_delay_us = atoi(e);
     }
@@ -298,14 +282,12 @@ static int create_impl(const ffvd_config *cfg, ffvd_handle *h) {
     HIP_TRY(dev_alloc(h, &h->Zs, Dl * Mp * P));
     HIP_TRY(dev_alloc(h, &h->zz, Dl * Mp));
     HIP_TRY(dev_alloc(h, &h->Kuu, Dl * 2 * Mp * Mp));
-    // reference route of the collapsed branch: K_fu is built once (kfu_build) and projected by a triangular GEMM,
-    // unless FFVD_FUSED_PROJECT asks for the older kernel that generates K_fu inside the projection
+    // reference route of the collapsed branch: K_fu is built once (kfu_build) and projected by a triangular GEMM
     // (explicit-U branch: only from 64 units of the headline size on -- below that the single fused kernel is quicker:
     //  1.10 vs 1.21 ms on config 5's 16 units -- or when the backward pass needs K_fu anyway)
     const bool big_a = (size_t)h->nbatch * Tp * Mp >= (size_t)64 * 4096 * 512 || c.grad;
     const bool grad_ref = c.grad && c.branch == FFVD_BRANCH_B && c.route == FFVD_ROUTE_REFERENCE;    // backward pass in the reference's op order
-    const bool proj_gemm = ((c.branch == FFVD_BRANCH_A && big_a) || (c.branch == FFVD_BRANCH_B && c.route == FFVD_ROUTE_REFERENCE)) &&
-                           (!h->sw.fused_project || grad_ref);
+    const bool proj_gemm = (c.branch == FFVD_BRANCH_A && big_a) || (c.branch == FFVD_BRANCH_B && c.route == FFVD_ROUTE_REFERENCE);
     h->ngr = (proj_gemm && c.dtype != FFVD_F32C) ? (int)((Mp + 127) / 128) : 0;
     HIP_TRY(dev_alloc(h, &h->rowsq, (size_t)h->nbatch * (h->ngr > h->ng ? h->ngr : h->ng) * Tp));
     HIP_TRY(dev_alloc(h, &h->fmean, (size_t)h->nbatch * (h->ngr > h->ng ? h->ngr : h->ng) * Tp));
@@ -318,9 +300,6 @@ static int create_impl(const ffvd_config *cfg, ffvd_handle *h) {
             h->nsq = proj_f32_ntiles((int)Tp, (int)Mp);
             HIP_TRY(dev_alloc(h, &h->sqpart, (size_t)h->nbatch * h->nsq));
             HIP_TRY(dev_alloc(h, &h->sqsum, (size_t)h->nbatch));
-            // fp32 summation chains of the Gram product are cut every 4096 rows (128 t-tiles); FFVD_F32C_FLUSH overrides
-            h->gram_flush = 128;
-            if (const char *e = getenv("FFVD_F32C_FLUSH")) h->gram_flush = atoi(e);
         } else {
             HIP_TRY(dev_alloc(h, &h->F, pass_b * Tp * Mp));
             if (h->ngr) HIP_TRY(dev_alloc(h, &h->Kf2, pass_b * Tp * Mp));
@@ -429,13 +408,12 @@ static int create_impl(const ffvd_config *cfg, ffvd_handle *h) {
     if (c.branch == FFVD_BRANCH_B && c.dtype != FFVD_F32C) {
         const int upass = h->cpp * (int)Dl;
         // the K_fu build forms delta^T K_fu (Gram route) / the projection GEMM forms delta^T F (reference route): the Gram kernel has no row
-        const bool ext_row = (c.route == FFVD_ROUTE_GRAM && c.T_total == 0) || (c.route == FFVD_ROUTE_REFERENCE && h->ngr > 0 && !h->sw.ref_row_in_gram);
+        const bool ext_row = (c.route == FFVD_ROUTE_GRAM && c.T_total == 0) || (c.route == FFVD_ROUTE_REFERENCE && h->ngr > 0);
         // Few chains (one pass, no backward pass): the K_uu side chain goes BEHIND the tile pass as one dataflow launch (beside Cholesky(A)),
         // and the tile pass takes the row ranges that fill the chip's 512 slots exactly -- beside the pass, the chain's two dozen launches
         // only ran where the pass left slots free, which is what held the pass at three ranges (plan_schedule, side_late)
-        const bool late_ok = c.route == FFVD_ROUTE_GRAM && !c.grad && c.T_total == 0 && c.S_local <= h->cpp && !h->sw.no_side_late &&
-                             !h->sw.no_defer_trace && !h->sw.no_late_join && !h->sw.no_main_first && !h->sw.chain_rl &&
-                             (size_t)Dl * 2 * (Mp / NB) <= 64 && (size_t)Dl * 2 * (Mp / NB) > (size_t)h->sw.small_side_rows &&
+        const bool late_ok = c.route == FFVD_ROUTE_GRAM && !c.grad && c.T_total == 0 && c.S_local <= h->cpp && !h->sw.no_defer_trace &&
+                             (size_t)Dl * 2 * (Mp / NB) <= 64 && (size_t)Dl * 2 * (Mp / NB) > (size_t)SMALL_SIDE_ROWS &&
                              potrf_flow_forms_inverse((int)Mp, (int)Dl, CHOL_FLOW);
         h->side_late = late_ok && upass <= 96;
         if (h->side_late) {
@@ -450,7 +428,7 @@ static int create_impl(const ffvd_config *cfg, ffvd_handle *h) {
             HIP_TRY(hipMemsetAsync(h->gtail, 0, gram_tail_doubles(h->gtail_wg) * sizeof(double), h->stream));   // counters start at 0
         }
         if (h->gsplit > 1) HIP_TRY(dev_alloc(h, &h->gpart, gram_part_doubles((int)Mp, upass, h->gsplit)));
-        else if (c.route == FFVD_ROUTE_GRAM && h->sw.kuu_flow && (size_t)upass * Tp * Mp >= (size_t)128 * 4096 * 512)
+        else if (c.route == FFVD_ROUTE_GRAM && (size_t)upass * Tp * Mp >= (size_t)128 * 4096 * 512)
             // a K_fu build of 0.4 ms or more: the K_uu chain as ONE dataflow launch finishes beside it, the main stream
             // joins before the Gram kernel, which then forms the trace partials in its own epilogue
             h->kuu_flow_sched = true;
@@ -459,31 +437,6 @@ static int create_impl(const ffvd_config *cfg, ffvd_handle *h) {
             // (unsplit pass of up to 16 chains: the chain's launches were starved by the pass and ended 0.1 ms behind Cholesky(A) -- behind
             //  the pass as one dataflow launch as well)
             h->side_late = late_ok && upass <= 64;
-        }
-    }
-    // Pass-pipelined forward iteration (enqueue_elbo_pipe): only where the full-batch schedule runs today
-    // (one buffer pass over all chains, unsplit Gram launches, K_uu chain as one dataflow launch with L^-1 and K^-1 out of it)
-    if (h->kuu_flow_sched && !c.grad && c.T_total == 0 && h->cpp >= c.S_local && !h->gpart && !h->graw && h->growpart) {
-        int passes = 0;
-        if (const char *e = getenv("FFVD_PIPE")) passes = atoi(e);
-        if (const char *e = getenv("FFVD_PIPE_MODE")) h->pipe_mode = atoi(e);
-        if (passes > c.S_local) passes = c.S_local;
-        if (passes >= 2 && potrf_flow_forms_inverse((int)Mp, (int)Dl, CHOL_FLOW) && !h->sw.kinv_gram) {
-            h->pipe_passes = passes;
-            int lo = 0, hi = 0;
-            HIP_TRY(hipDeviceGetStreamPriorityRange(&lo, &hi));
-            HIP_TRY(hipStreamCreateWithFlags(&h->pipe_build, hipStreamNonBlocking));
-            HIP_TRY(hipStreamCreateWithFlags(&h->pipe_gram, hipStreamNonBlocking));
-            HIP_TRY(hipStreamCreateWithPriority(&h->pipe_chol, hipStreamNonBlocking, (h->pipe_mode & 4) ? lo : hi));
-            h->pipe_evB.resize(passes); h->pipe_evG.resize(passes);
-            for (int i = 0; i < passes; ++i) {
-                HIP_TRY(hipEventCreateWithFlags(&h->pipe_evB[i], hipEventDisableTiming));
-                HIP_TRY(hipEventCreateWithFlags(&h->pipe_evG[i], hipEventDisableTiming));
-            }
-            HIP_TRY(hipEventCreateWithFlags(&h->pipe_evC, hipEventDisableTiming));
-            const int max_units = ((c.S_local + passes - 1) / passes) * (int)Dl;
-            h->pipe_dinv_stride = (potrf_scratch_doubles((int)Mp, max_units) + 31) / 32 * 32;
-            HIP_TRY(dev_alloc(h, &h->pipe_dinv, h->pipe_dinv_stride * passes));
         }
     }
     if (c.branch == FFVD_BRANCH_A && !c.grad && !h->sw.no_linear_lowrank && linear_lowrank_supported(c.kernel_kind, P))
@@ -699,8 +652,8 @@ struct ElboSchedule {
     bool lt_rows, lt_virtual;       // Gram-route training: L^T in the extension rows of A (read in place by the dataflow kernel)
     int first_units, ns_first;
     bool late_join;                 // split-K first pass: the K_uu chain only has to be back for the combine pass
-    bool defer_trace;               //   ... one pass: the combine pass waits for the K_uu COPY only, trace partials follow on the side stream
-    bool main_first;                //   ... and the main stream's K_fu build + tile pass are enqueued before the chain's launches
+    bool defer_trace;               //   ... one pass: the combine pass waits for the K_uu COPY only, trace partials follow on the side stream, and the
+                                    //   main stream's K_fu build + tile pass are enqueued before the chain's launches
     bool defer_full;                // unsplit first pass beside the chain: raw tiles kept, trace pass on the side stream
     bool side_chain;                // Gram route: the K_uu chain runs on the side stream
     bool kuu_flow;                  //   ... as ONE dataflow launch resident before the K_fu build, joined before the Gram kernel
@@ -721,36 +674,35 @@ static ElboSchedule plan_schedule(const ffvd_handle *h) {
     sc.grad_ref = c.grad && c.branch == FFVD_BRANCH_B && !sc.gram_route;
     sc.first_units = ((c.S_local < h->cpp) ? c.S_local : h->cpp) * Dl;
     sc.ns_first = (h->cpp <= c.S_local) ? h->cpp : c.S_local;
-    sc.late_join = sc.gram_route && h->gpart && sc.first_units == h->cpp * Dl && !h->sw.no_late_join;
+    sc.late_join = sc.gram_route && h->gpart && sc.first_units == h->cpp * Dl;
     sc.lt_rows = c.grad && sc.gram_route && h->gw.whitened && !h->sw.whiten_products;
     sc.lt_virtual = sc.lt_rows && !h->sw.lt_armed && potrf_flow_selected(Mp, h->nbatch, CHOL_FLOW);
     sc.defer_trace = sc.late_join && c.S_local <= h->cpp && !h->sw.no_defer_trace;
-    sc.main_first = sc.defer_trace && !h->sw.no_main_first;
     sc.defer_full = sc.gram_route && !sc.late_join && h->graw;
     sc.zt_rows = h->lrpart != nullptr;
-    sc.ref_side = !sc.gram_route && h->ngr > 0 && c.dtype != FFVD_F32C && h->aux && !h->sw.no_ref_side && !h->sw.chain_rl &&
+    sc.ref_side = !sc.gram_route && h->ngr > 0 && c.dtype != FFVD_F32C && h->aux &&
                   potrf_flow_selected(Mp, Dl, CHOL_FLOW);
     sc.side_chain = sc.gram_route && (sc.late_join || (size_t)sc.first_units * Tp * Mp >= (size_t)64 * 4096 * 512);
     sc.kuu_flow = sc.side_chain && h->kuu_flow_sched && !sc.late_join;
-    sc.kfu_first = sc.side_chain && (sc.main_first || (sc.defer_full && !h->sw.no_kfu_first));
+    sc.kfu_first = sc.side_chain && (sc.defer_trace || (sc.defer_full && !h->sw.no_kfu_first));
     sc.ident_on_side = sc.side_chain && c.grad && (sc.defer_full || sc.defer_trace) && !sc.lt_rows;
     const bool on_side = sc.ref_side || sc.side_chain;          // sk != s
     const bool kuu_on_main = sc.ref_side || sc.kuu_flow;        // K_uu is built (and its chain launched) before the common chain code
     sc.reduce_early = sc.gram_route && on_side;
-    sc.small_side = sc.defer_trace && sc.main_first && !c.grad && !kuu_on_main && on_side && !h->sw.chain_rl && !h->sw.no_small_side &&
-                    (size_t)sc.first_units * h->ntiles * (h->gsplit > 1 ? h->gsplit : 1) <= (size_t)h->sw.small_side_wgs &&
-                    (size_t)Dl * 2 * (Mp / NB) <= (size_t)h->sw.small_side_rows;
+    sc.small_side = sc.defer_trace && !c.grad && !kuu_on_main && on_side &&
+                    (size_t)sc.first_units * h->ntiles * (h->gsplit > 1 ? h->gsplit : 1) <= (size_t)SMALL_SIDE_WGS &&
+                    (size_t)Dl * 2 * (Mp / NB) <= (size_t)SMALL_SIDE_ROWS;
     // (Round 4, measured and not kept: at 8-16 chains the side chain -- a dozen dependent right-looking launches -- is starved of slots by
     //  the tile pass and its tail ends 0.14 ms behind Cholesky(A).  As ONE dataflow launch beside the K_fu build it holds its slots
     //  against the tile pass instead: that pass 1.43 instead of 1.18 ms at 16 chains, the iteration 1.91 either way; a main stream whose
     //  CU mask leaves 8-32 compute units to the side stream runs 1.2 x slower; `small_side` widened to these sizes: 1.19 vs 1.14 ms at 8.)
-    sc.side_late = h->side_late && ((sc.defer_trace && sc.main_first) || (sc.defer_full && sc.kfu_first)) && !kuu_on_main && on_side && !sc.small_side &&
+    sc.side_late = h->side_late && (sc.defer_trace || (sc.defer_full && sc.kfu_first)) && !kuu_on_main && on_side && !sc.small_side &&
                    potrf_flow_forms_inverse(Mp, Dl, CHOL_FLOW);            // (a forced launch-per-column Cholesky: the first-half schedule)
-    sc.chain_flow_here = !kuu_on_main && (!on_side || sc.small_side || sc.side_late) && potrf_flow_selected(Mp, Dl, CHOL_FLOW) && !h->sw.chain_rl;
+    sc.chain_flow_here = !kuu_on_main && (!on_side || sc.small_side || sc.side_late) && potrf_flow_selected(Mp, Dl, CHOL_FLOW);
     // invariants the launch code relies on (a violated one would be a silent wrong answer, not a crash)
     if ((sc.defer_full && sc.late_join) || (sc.defer_trace && !sc.late_join) || (sc.kuu_flow && sc.defer_full) || (sc.small_side && sc.kuu_flow) ||
-        (sc.side_late && (sc.small_side || !(sc.main_first || sc.defer_full) || !sc.chain_flow_here)) ||
-        (sc.ref_side && sc.side_chain) || (sc.main_first && !sc.defer_trace) || (sc.kuu_flow && h->graw))
+        (sc.side_late && (sc.small_side || !(sc.defer_trace || sc.defer_full) || !sc.chain_flow_here)) ||
+        (sc.ref_side && sc.side_chain) || (sc.kuu_flow && h->graw))
         sc.name = nullptr;
     else if (!sc.gram_route) sc.name = sc.ref_side ? "projection route, K_uu chain as one dataflow launch on the side stream beside the K_fu build"
                                                    : "projection route, serial (K_uu chain on the main stream)";
@@ -764,13 +716,10 @@ static ElboSchedule plan_schedule(const ffvd_handle *h) {
     else sc.name = "serial: K_uu chain on the main stream in front of the K_fu build";
     return sc;
 }
-// (the pipelined passes need the dataflow Cholesky: a forced launch-per-column variant -- stall recovery, FFVD_CHOL -- takes the plain schedule)
-static bool pipe_selected(const ffvd_handle *h) { return h->pipe_passes >= 2 && potrf_override_current() == CHOL_FORCE_NONE; }
 extern "C" const char *ffvd_schedule_name(const ffvd_handle *h) {
     if (!h) return "";
     if (h->stall_hold > 0) return "stall back-off: multi-kernel schedule with the launch-per-column Cholesky (no inter-workgroup waits) until the next probe";
     if (h->tiny.ok && potrf_override_current() == CHOL_FORCE_NONE) return "one launch (tiny.hip)";
-    if (pipe_selected(h)) return "pipelined passes: K_fu build of pass p+1 | Gram kernel of pass p | Cholesky(A) of pass p-1 on separate streams";
     const ElboSchedule sc = plan_schedule(h);
     return sc.name ? sc.name : "INVALID";
 }
@@ -809,7 +758,7 @@ static int enqueue_tiny(ffvd_handle *h, double *out_dev, StageTimer *st, bool wi
     tiny_bind_scratch(a, h->tiny, h->tiny_scratch, h->tiny_flags);
     {   // all workgroups of a unit on one XCD when the padded grid (8 x ceil(units / 8) unit slots) still fits the chip
         const int wpu = 1 + h->tiny.nstrips + (a.side ? h->tiny.NT : 0);
-        a.xcd_map = (h->sw.tiny_xcd && 8 * wpu * ((h->tiny.nunits + 7) / 8) <= h->tiny_cus) ? 1 : 0;
+        a.xcd_map = (8 * wpu * ((h->tiny.nunits + 7) / 8) <= h->tiny_cus) ? 1 : 0;
     }
     a.info = h->info; a.chain_nll = h->chain_nll; a.out_terms = out_dev ? out_dev : h->out_terms;
     if (with_grad) {
@@ -892,93 +841,6 @@ static FinalizeArgs elbo_finalize_args(const ffvd_handle *h, double *out_dev, bo
 }
 
 
-// ---- pass-pipelined forward iteration ----------------------------------------------------------------------------
-// The per-(s, d) units of conditionals_multi_output.py:238-255 are independent, and the full-batch iteration is three phases bound by
-// three different things: the K_fu build by HBM writes, the Gram kernel by the matrix pipe, Cholesky(A) by latency.  This schedule cuts
-// the chains into `pipe_passes` passes (each with its own slice of F, H and growpart -- the buffers already hold all chains) and lets
-// the phases of neighbouring passes run side by side:
-//
-//   main   : prep, K_uu build | reductions | build(0) | Gram(0) ........... Gram(2) ...                      | wait C | finalize
-//   aux    :   K_uu chain (one dataflow launch, L^-1, K^-1, log|K|) --ev_join--> (every Gram launch waits for it once per stream)
-//   build  :                     wait B0 | build(1) build(2) ...            (mode bit 0: build(p) waits for Gram(p-2) -- "lazy")
-//   gram   :                                  wait B1 | Gram(1) ........... Gram(3) ...     (mode bit 1: every Gram launch on main)
-//   chol   : clears of all passes' progress words | wait G0 | Chol(0) finish(0) | wait G1 | Chol(1) ...     --evC-->
-//
-// Odd passes' Gram launches go to a second stream so that Gram(p+1) can take the slots Gram(p)'s early finishers free (stream order
-// would hold it until the last workgroup of Gram(p) has left: the ends of a round are spread over 0.3 ms).
-// FFVD_PIPE=<passes> turns it on for handles that would run the "full unsplit" schedule; results are bit-identical to that schedule
-// (same kernels on the same units; only the launch partition differs).
-static int enqueue_elbo_pipe(ffvd_handle *h, double *out_dev, StageTimer *st) {
-    const ffvd_config &c = h->cfg;
-    const int Mp = h->Mp, Tp = h->Tp, Dl = h->Dl, P = h->P, NP = h->pipe_passes;
-    const ffvd_params &p = h->cur;
-    hipStream_t s = h->stream, sk = h->aux, sb = h->pipe_build, sg = (h->pipe_mode & 2) ? h->stream : h->pipe_gram, sc = h->pipe_chol;
-    const size_t msq = (size_t)Mp * Mp, kstride = 2 * msq, fstride = (size_t)Tp * Mp, hstride = elbo_h_stride(h);
-    const bool lazy = (h->pipe_mode & 1) != 0;
-    const int nt = (h->pipe_mode & 8) ? 0 : 1;          // streaming stores for every pass's K_fu unless bit 3 says cacheable
-    if (st) st->mark(-1);
-    launch_prep_hypers(s, c.kernel_kind, p.Z, c.M, Mp, P, Dl, c.d_begin, p.logvariance, p.loglengthscales,
-                       h->variance, h->len, h->Zs, h->zz, h->info, Dl + h->nbatch);
-    HyperView hv{h->variance, h->len, h->Zs, h->zz};
-    launch_kuu_build(s, c.kernel_kind, hv, c.M, Mp, P, Dl, c.jitter, h->Kuu, h->Kcopy);
-    { int rcf = fork_side(h, h->ev_fork, s, sk); if (rcf) return rcf; }
-    // the chain's row workgroups must be on the chip before the first K_fu build floods it (as in the full-batch schedule)
-    potrf_flow_clear(sk, h->dinvK, Dl);
-    HIP_TRY(hipEventRecord(h->ev_go, sk));
-    launch_potrf_ext(sk, h->Kuu, Mp, Mp, Mp, Dl, kstride, h->info, h->dinvK, CHOL_FLOW, h->Linv, msq, true, false, h->Kinv, msq);
-    launch_h_finish(sk, h->Kuu, Mp, kstride, Dl, h->kterms);
-    HIP_TRY(hipEventRecord(h->ev_join, sk));
-    launch_chain_reduce(s, elbo_reduce_args(h, true), h->chain_partial);      // inputs only; fills the wait below
-    HIP_TRY(hipStreamWaitEvent(s, h->ev_go, 0));
-    // progress words of every pass's factorisation: cleared up front on the stream that runs them
-    HIP_TRY(hipStreamWaitEvent(sc, h->ev_fork, 0));
-    for (int q = 0; q < NP; ++q) {
-        const int c0 = (int)((long long)c.S_local * q / NP), c1 = (int)((long long)c.S_local * (q + 1) / NP);
-        potrf_flow_clear(sc, h->pipe_dinv + h->pipe_dinv_stride * q, (c1 - c0) * Dl);
-    }
-    if (st) st->mark(0);
-    for (int q = 0; q < NP; ++q) {
-        const int c0 = (int)((long long)c.S_local * q / NP), c1 = (int)((long long)c.S_local * (q + 1) / NP);
-        const int ns = c1 - c0, u0 = c0 * Dl, nu = ns * Dl;
-        // K_fu of the pass (+ the row b from the partial sums it leaves)
-        hipStream_t bs = q == 0 ? s : sb;
-        if (q == 1) HIP_TRY(hipStreamWaitEvent(sb, h->pipe_evB[0], 0));            // builds one after the other
-        if (lazy && q >= 2) HIP_TRY(hipStreamWaitEvent(sb, h->pipe_evG[q - 2], 0));  // ... and not before Gram(q-2) has left
-        ProjectArgs pa = elbo_project_args(h, hv, c0, ns, true);
-        pa.F = h->F + (size_t)u0 * fstride;
-        pa.gpart = h->growpart + (size_t)u0 * (Tp / 64) * Mp;
-        launch_kfu_build(bs, pa, nt);
-        launch_brow_finish(bs, pa.gpart, Tp / 64, Mp, Dl, c.d_begin, u0, nu, p.log_Q, 1.0, h->H + (size_t)u0 * hstride, hstride, Mp);
-        HIP_TRY(hipEventRecord(h->pipe_evB[q], bs));
-        if (st && q == 0) st->mark(1);
-        // Gram kernel of the pass (trace partials in its epilogue: needs K_uu's copy and K^-1 from the chain)
-        hipStream_t gs = (q % 2 == 0) ? s : sg;
-        if (gs != bs) HIP_TRY(hipStreamWaitEvent(gs, h->pipe_evB[q], 0));
-        if (q < 2) HIP_TRY(hipStreamWaitEvent(gs, h->ev_join, 0));
-        GramArgs ga = elbo_gram_args(h, c0, ns, true);
-        ga.A = h->F + (size_t)u0 * fstride;
-        ga.H = h->H + (size_t)u0 * hstride;
-        ga.tail_wg = 0; ga.tail_part = nullptr;              // (the tail split's blocks are sized for the full batch's launch)
-        launch_gram(gs, ga);
-        HIP_TRY(hipEventRecord(h->pipe_evG[q], gs));
-        // Cholesky(A) of the pass, log|A| and b^T A^-1 b
-        HIP_TRY(hipStreamWaitEvent(sc, h->pipe_evG[q], 0));
-        launch_potrf_ext(sc, ga.H, Mp, NB, 0, nu, hstride, h->info + Dl + u0, h->pipe_dinv + h->pipe_dinv_stride * q, CHOL_FLOW, nullptr, 0,
-                         true, true);
-        launch_h_finish(sc, ga.H, Mp, hstride, nu, h->hterms + (size_t)2 * u0);
-    }
-    if (st) { st->mark(2); }
-    HIP_TRY(hipEventRecord(h->pipe_evC, sc));
-    HIP_TRY(hipStreamWaitEvent(s, h->pipe_evC, 0));
-    if (NP >= 2 && sg != s) HIP_TRY(hipStreamWaitEvent(s, h->pipe_evG[NP % 2 == 0 ? NP - 1 : NP - 2], 0));   // (implied by evC; keeps the graph explicit)
-    if (st) st->mark(3);
-    launch_finalize(s, elbo_finalize_args(h, out_dev, true));
-    if (st) st->mark(4);
-    DBG_SYNC(h, "forward (pipelined passes)");
-    HIP_TRY(hipGetLastError());
-    return FFVD_OK;
-}
-
 // ---- the multi-kernel forward iteration, phase by phase -------------------------------------------------------
 // enqueue_elbo used to be one 425-line function; it is now the sequence below, each phase a function of its own over one context.
 // The SCHEDULE is sc (plan_schedule: every flag decided in one place, named, checked); the context only adds launch PROGRESS -- which
@@ -990,7 +852,7 @@ static int enqueue_elbo_pipe(ffvd_handle *h, double *out_dev, StageTimer *st) {
 //   unsplit + raw tiles       M: prep ->fork | build, brow | kuu-> Gram(raw) ->tiles | Chol(A) | join2-> finalize
 //   (defer_full)              S: fork-> K_uu build ->kuu | chain (launches) | K^-1, log|K| ->join | reductions | tiles-> trace pass ->join2
 //   split-K one pass          M: prep ->fork | build, brow, tile pass ->tiles | kuu-> combine (no trace) | Chol(A) | join2-> finalize
-//   (defer_trace, main_first) S: fork-> K_uu build ->kuu | chain | K^-1, log|K| ->join | reductions | tiles-> trace partials ->join2
+//   (defer_trace)             S: fork-> K_uu build ->kuu | chain | K^-1, log|K| ->join | reductions | tiles-> trace partials ->join2
 //   side late                 as the two above, but the chain is ONE dataflow launch enqueued behind the tile pass (tiles-> chain), the
 //                             reductions in front of it, the trace pass behind it
 //   small side                split-K one pass with the chain as one dataflow launch; reductions and trace partials on M (join-> trace)
@@ -1035,7 +897,7 @@ struct FwdCtx {
 // that stream idles at the start (few-chain schedules); schedules without a slack window keep them in the finalize launch.
 static int fwd_prior_sums(FwdCtx &x, hipStream_t stream) {
     ffvd_handle *h = x.h;
-    if (h->sw.no_early_priors || x.prior_early) return FFVD_OK;
+    if (x.prior_early) return FFVD_OK;
     launch_prior_sums(stream, elbo_finalize_args(h, x.out_dev, x.sc.gram_route), h->prior_sums);
     if (stream != x.s) {
         HIP_TRY(hipEventRecord(h->ev_prior, stream));
@@ -1070,7 +932,7 @@ static int fwd_chain_ref_side(FwdCtx &x) {
 // Gram route: nothing of the K_fu build depends on K_uu, so the latency-bound K_uu chain runs on the side stream.  This is the fork
 // and whatever the schedule wants on either stream BEFORE the chain's own launches (fwd_chain_rest): the full-batch schedule's
 // dataflow chain and the work that fills the main stream's wait for it; the first pass's K_fu build / tile pass when the main
-// stream is the critical one (kfu_first, main_first); the identity rows of a training pass on the side stream.
+// stream is the critical one (kfu_first, defer_trace); the identity rows of a training pass on the side stream.
 static int fwd_chain_fork(FwdCtx &x) {
     ffvd_handle *h = x.h;
     const ffvd_config &c = h->cfg;
@@ -1094,7 +956,7 @@ static int fwd_chain_fork(FwdCtx &x) {
             potrf_flow_clear(sk, h->dinvK, Dl);
             HIP_TRY(hipEventRecord(h->ev_go, sk));
         }
-        x.kinv_done = x.linv_done && !h->sw.kinv_gram && potrf_flow_forms_inverse(Mp, Dl, CHOL_FLOW);
+        x.kinv_done = x.linv_done && potrf_flow_forms_inverse(Mp, Dl, CHOL_FLOW);
         launch_potrf_ext(sk, h->Kuu, Mp, Mp, Mp, Dl, x.kstride, h->info, h->dinvK, CHOL_FLOW, h->Linv, x.msq, x.linv_done, false,
                          x.kinv_done ? h->Kinv : nullptr, x.msq);
         if (x.linv_done) {
@@ -1122,7 +984,7 @@ static int fwd_chain_fork(FwdCtx &x) {
         x.brow_finish(0, sc.ns_first);
         if (x.st) x.st->mark(1);
     }
-    if (sc.main_first) {        // ... and so does the split-K tile pass (it needs neither K_uu nor K^-1)
+    if (sc.defer_trace) {       // ... and so does the split-K tile pass (it needs neither K_uu nor K^-1)
         const GramArgs ga = x.gram_args(0, c.S_local);
         launch_gram(s, ga, 1);
         HIP_TRY(hipEventRecord(h->ev_tiles, s));
@@ -1170,7 +1032,7 @@ static int fwd_chain_rest(FwdCtx &x) {
         gk.d_begin = c.d_begin; gk.b0 = 0; gk.nb = Dl; gk.yn_over_batch = 1.0; gk.H = h->Kinv; gk.h_stride = msq;
         if (x.kinv_done) {
             // (the identity-row workgroups of the chain's launch have formed it: kernels.hip, df_inverse_tiles)
-        } else if (c.grad || (x.kuu_on_main && !h->sw.kinv_gram)) {
+        } else if (c.grad || x.kuu_on_main) {
             // the backward pass reads K^-1 everywhere, the Gram kernel only writes lower tiles; and beside the K_fu build
             // (kuu_on_main: the main stream waits for this product) 256-thread workgroups find a slot where the Gram
             // kernel's 1024-thread ones wait for the build to drain (0.19 against 0.05 ms)
@@ -1268,9 +1130,9 @@ static int fwd_pass_gram(FwdCtx &x, int s0, int ns, GramArgs &ga, bool &trace_pe
         // (armed right in front of the factorisation, when at all: L comes from the K_uu chain)
     } else if (c.grad && !((sc.ident_on_side || x.ident_early) && s0 == 0)) launch_set_identity(s, h->H, ga.h_stride, Mp, Mp, ns * Dl);
     if (s0 == 0 && sc.late_join) {
-        if (!sc.main_first) launch_gram(s, ga, 1);
+        if (!sc.defer_trace) launch_gram(s, ga, 1);
         if (sc.defer_trace) {
-            if (!sc.main_first) HIP_TRY(hipEventRecord(h->ev_tiles, s));
+            if (!sc.defer_trace) HIP_TRY(hipEventRecord(h->ev_tiles, s));
             HIP_TRY(hipStreamWaitEvent(s, h->ev_kuu, 0));
             ga.trace_mode = 1;
             // side late: the trace pass runs long after this one (behind the K_uu chain) -- it reads the summed raw tiles this
@@ -1294,7 +1156,7 @@ static int fwd_pass_gram(FwdCtx &x, int s0, int ns, GramArgs &ga, bool &trace_pe
         gf.F = h->F32; gf.f_stride = (size_t)Tp * Mp; gf.rows = Tp; gf.with_row = 1; gf.brow = c.grad ? 2 * Mp : Mp;
         gf.X = p.X; gf.log_Q = p.log_Q; gf.T = c.T; gf.D = c.D; gf.Mp = Mp; gf.Dl = Dl; gf.d_begin = c.d_begin;
         gf.b0 = s0 * Dl; gf.nb = ns * Dl; gf.yn_over_batch = 1.0; gf.H = h->H; gf.h_stride = ga.h_stride;
-        gf.flush = h->gram_flush;
+        gf.flush = F32C_FLUSH_TILES;
         launch_gram_f32(s, gf);                               // H = F^T F / Q + I, b = delta^T F / Q  (:246-248)
     } else {
         // training: the unsplit Gram kernel stores the symmetric copy of A itself (no copy + symmetrize launches: 0.25 ms)
@@ -1315,18 +1177,17 @@ static int fwd_whiten_products(FwdCtx &x, int ns, const GramArgs &ga) {
     const int Mp = h->Mp, Dl = h->Dl, nbp = ns * Dl;
     const size_t msq = x.msq, kstride = x.kstride;
     hipStream_t s = x.s;
-    const int small = h->sw.atb128 ? 0 : 1;
     if (x.sk != s) HIP_TRY(hipStreamWaitEvent(s, h->ev_join, 0));       // W and L^-1 come from the K_uu chain
     launch_symmetrize(s, g.Acopy, Mp, nbp);                            // (the saved copy holds the lower triangle)
     AtbArgs t1{};
     t1.mode = ATB_PLAIN; t1.A = g.Acopy; t1.a_stride = msq; t1.lda = Mp; t1.nA = Mp;
     t1.B = h->Kuu + msq; t1.b_stride = kstride; t1.ldb = Mp; t1.nB = Mp; t1.b_per_dim = 1; t1.rows = Mp;
-    t1.C = g.T1; t1.c_stride = msq; t1.ldc = Mp; t1.nb = nbp; t1.Dl = Dl; t1.krange = 8; t1.small_tiles = small;      // W upper triangular
+    t1.C = g.T1; t1.c_stride = msq; t1.ldc = Mp; t1.nb = nbp; t1.Dl = Dl; t1.krange = 8; t1.small_tiles = 1;      // W upper triangular
     launch_atb(s, t1);                                                  // T1 = A W
     AtbArgs t2{};
     t2.mode = ATB_PLAIN; t2.A = h->Kuu + msq; t2.a_stride = kstride; t2.lda = Mp; t2.nA = Mp; t2.a_per_dim = 1;
     t2.B = g.T1; t2.b_stride = msq; t2.ldb = Mp; t2.nB = Mp; t2.rows = Mp;
-    t2.C = h->H; t2.c_stride = ga.h_stride; t2.ldc = Mp; t2.nb = nbp; t2.Dl = Dl; t2.krange = 4; t2.sym = 1; t2.small_tiles = small;
+    t2.C = h->H; t2.c_stride = ga.h_stride; t2.ldc = Mp; t2.nb = nbp; t2.Dl = Dl; t2.krange = 4; t2.sym = 1; t2.small_tiles = 1;
     launch_atb(s, t2);                                                  // H = W^T T1 into rows [0, Mp)
     launch_matvec(s, h->Linv, msq, h->H + 2 * msq, ga.h_stride, Mp, g.bw, 1, Mp, Mp, nbp, Dl);   // b = W^T c
     HIP_TRY(hipMemcpy2DAsync(h->H + 2 * msq, ga.h_stride * sizeof(double), g.bw, (size_t)Mp * sizeof(double),
@@ -1420,7 +1281,6 @@ static int enqueue_elbo(ffvd_handle *h, double *out_dev, StageTimer *st) {
     if (tiny_selected(h)) return enqueue_tiny(h, out_dev, st, false, h->cfg.S_local);
     StageTimer live{h};
     if (!st && h->timing_on) st = &live;
-    if (pipe_selected(h)) return enqueue_elbo_pipe(h, out_dev, st);
     const ffvd_config &c = h->cfg;
     const ffvd_params &p = h->cur;
     const int Mp = h->Mp, Dl = h->Dl;
@@ -1857,7 +1717,7 @@ static int enqueue_grad_b(ffvd_handle *h, int S_total) {
         AtbArgs tb{};       // B[i][j] = sum_k L_H^-T[k][i] L^-1[k][j]: the extension rows as they are, no transpose
         tb.mode = ATB_PLAIN; tb.A = h->H + msq; tb.a_stride = hstride; tb.lda = Mp; tb.nA = Mp;
         tb.B = h->Linv; tb.b_stride = msq; tb.ldb = Mp; tb.nB = Mp; tb.b_per_dim = 1; tb.rows = Mp;
-        tb.C = g.T1; tb.c_stride = msq; tb.ldc = Mp; tb.nb = nb; tb.Dl = Dl; tb.krange = 2 | 4; tb.small_tiles = h->sw.atb128 ? 0 : 1;      // k in [tile tj, tile (ti + 1))
+        tb.C = g.T1; tb.c_stride = msq; tb.ldc = Mp; tb.nb = nb; tb.Dl = Dl; tb.krange = 2 | 4; tb.small_tiles = 1;      // k in [tile tj, tile (ti + 1))
         launch_atb(s, tb);
         ag.A = g.T1; ag.B = g.T1;
     } else {
@@ -3235,8 +3095,6 @@ extern "C" int ffvd_op_rollout(int kind, const double *Lm_inverse_seq, const dou
             for (int j = 0; j < i; ++j)
                 if (q_sqrt[(size_t)i * M + j] != 0.0) { q_upper = 0; break; }
     }
-    static const bool no_upper2 = getenv("FFVD_NO_QSQRT_UPPER") != nullptr;       // A/B switch (read once)
-    if (no_upper2) q_upper = 0;
     double *dQs = q_sqrt ? (skinny ? upload_stack(sc, q_sqrt, 1, M, Mp, Qp) /* (F is zero in the padded columns) */ : sc.upload(q_sqrt, (size_t)M * M)) : nullptr;   // slice d = 0 only
     double *extra = q_sqrt ? sc.alloc<double>((size_t)D * (skinny ? ngs : 1) * Tp) : nullptr;
     // skinny path: W q_sqrt once per call (D products of M^3), so that the inflation term is a second right-hand side of the

@@ -576,14 +576,6 @@ __global__ __launch_bounds__(512, 4) void bwd_fused_kernel(BwdFusedArgs a) {
     TileAcc res = gemm_rowmajor_a(As, Bs, rt, Kfb, Tp, Gb, Mp, Mp, 1 << 30);
     d4 (&acc)[4][2] = res.v;
     BWD_STAMP(1);
-#if defined(BWD_DIAG) && BWD_DIAG == 1      // diagnostic build (tools/build_grad_variant.sh): main loop only
-    {
-        double v = 0.0;
-        for (int x = 0; x < 4; ++x) for (int y = 0; y < 2; ++y) for (int q = 0; q < 4; ++q) v += acc[x][y][q];
-        a.rp[(((size_t)tj * a.nb + bz) * a.Tp + ti * 128 + (tid & 127)) * 8 + (tid >> 7)] = v;
-        return;
-    }
-#endif
 
     // ---------------- epilogue ----------------
     const int b = a.b0 + bz, s = b / a.Dl, dl = b % a.Dl, dg = a.d_begin + dl;
@@ -645,28 +637,13 @@ __global__ __launch_bounds__(512, 4) void bwd_fused_kernel(BwdFusedArgs a) {
     // The K_fu values of strip x + 1 are requested before the matrix work of strip x.
     d4 ac[2] = {(d4){0.0, 0.0, 0.0, 0.0}, (d4){0.0, 0.0, 0.0, 0.0}};
     double *Tw = sb + wave * (16 * 17);
-#ifndef BWD_EPI_XWF
-#define BWD_EPI_XWF 1        // A/B switches of the epilogue's fragment prefetches (tools: variants bwdtrace_base / bwdtrace_vsf)
-#endif
-#ifndef BWD_EPI_VSF
-#define BWD_EPI_VSF 0
-#endif
-#if BWD_EPI_VSF
-    double vsf[2][4];                            // the [1, z] fragments of the wavefront's 32 columns: the same for every strip
-#pragma unroll
-    for (int y = 0; y < 2; ++y)
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) vsf[y][ks] = (lr < 8) ? Vs[lr * XW_LD + wc * 32 + 16 * y + 4 * ks + lk] : 0.0;
-#endif
 #pragma unroll
     for (int x = 0; x < 4; ++x) {
         // the strip's four [1; x^T] fragments are requested first: an LDS read takes hundreds of cycles beside the other workgroup's main
         // loop (stamps: 8 MFMAs behind 8 reads took 2.3 us), the e pass below covers them
         double xwf[4];
-#if BWD_EPI_XWF
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) xwf[ks] = (lr < 8) ? XW[lr * XW_LD + wr * 64 + 16 * x + 4 * ks + lk] : 0.0;
-#endif
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int il = wr * 64 + 16 * x + lk + 4 * q;
@@ -688,12 +665,7 @@ __global__ __launch_bounds__(512, 4) void bwd_fused_kernel(BwdFusedArgs a) {
 #pragma unroll
         for (int y = 0; y < 2; ++y)
 #pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-#if !BWD_EPI_XWF
-                xwf[ks] = (lr < 8) ? XW[lr * XW_LD + wr * 64 + 16 * x + 4 * ks + lk] : 0.0;
-#endif
-                ac[y] = mfma_f64(xwf[ks], acc[x][y][ks], ac[y]);
-            }
+            for (int ks = 0; ks < 4; ++ks) ac[y] = mfma_f64(xwf[ks], acc[x][y][ks], ac[y]);
         if (x == 0) BWD_STAMP(8);
         d4 r4 = (d4){0.0, 0.0, 0.0, 0.0};
 #pragma unroll
@@ -704,12 +676,8 @@ __global__ __launch_bounds__(512, 4) void bwd_fused_kernel(BwdFusedArgs a) {
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) {
                 const double af = Tw[lr * 17 + 4 * ks + lk];
-#if BWD_EPI_VSF
-                r4 = mfma_f64(af, vsf[y][ks], r4);
-#else
                 const double bf = (lr < 8) ? Vs[lr * XW_LD + wc * 32 + 16 * y + 4 * ks + lk] : 0.0;
                 r4 = mfma_f64(af, bf, r4);
-#endif
             }
             wave_lds_order();
         }

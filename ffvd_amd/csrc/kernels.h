@@ -133,7 +133,7 @@ size_t linear_lowrank_doubles(int Mp, int Dl, int P);
 void launch_linear_lowrank(hipStream_t stream, const ProjectArgs &a, double *part);
 // a.F[bz][t][m] = K_fu itself (route K_uu + K_uf K_fu / Q); uses x, ctrl, hv, T, Tp, M, Mp, b0, nb of `a`.
 void launch_kfu_build_t(hipStream_t stream, const ProjectArgs &a, int ldt);      // a.F <- KT[nb][Mp][ldt]: a step's K(x, Z), m-major
-void launch_kfu_build(hipStream_t stream, const ProjectArgs &a, int streaming = -1 /* -1: by output size, 0 / 1: cacheable / streaming stores */);
+void launch_kfu_build(hipStream_t stream, const ProjectArgs &a);
 
 // GRAM_KFU_RAW: as GRAM_KFU, but the trace partials are left to a later trace-only pass (phase 3) over the raw tiles
 // this launch also writes into `part` (ksplit = 1 layout) -- K^-1 is not read
@@ -172,9 +172,8 @@ struct GramArgs {
     int raw_summed;     // split-K combine: the pass without the trace (trace_mode 1) leaves the summed raw tile in partial 0, the trace pass (2) reads only that -- the caller orders the two passes
     // Launches without a delta^T A row, Mp a multiple of 256: (1) the diagonal tiles of every two neighbouring column panels are
     // ONE workgroup ("pair combo", gram_pair_role, round 4: row blocks i and 7 - i of a diagonal tile on one wavefront, nine MFMA
-    // tiles, nothing above the diagonal executed; also the diagonal workgroups of split-K launches).  Round 3's form -- three
-    // workgroups of eight 64 x 32 sub-blocks per four diagonal tiles, gram_combo_body -- is kept behind GRAM_COMBO=1 for A/B
-    // builds.  wg_per_unit = workgroups per unit (filled by launch_gram);
+    // tiles, nothing above the diagonal executed; also the diagonal workgroups of split-K launches).
+    // wg_per_unit = workgroups per unit (filled by launch_gram);
     // (2) unsplit launches: the workgroups of the LAST, partial round of the launch are cut into two row halves that run side by side on the
     // CUs that free up first; the half that finishes second adds the other's accumulators (two addends: the sum does not
     // depend on which one that is) and runs the epilogue.  tail_wg = workgroups cut (multiple of 8, 0 = off), tail_part =

@@ -291,11 +291,9 @@ void launch_kfu_build_t(hipStream_t stream, const ProjectArgs &a, int ldt) {
         else hipLaunchKernelGGL((kfu_build_t_kernel<1, 0, MW>), grid, dim3(256), 0, stream, a, ldt);
     }
 }
-void launch_kfu_build(hipStream_t stream, const ProjectArgs &a, int streaming) {
-    static const bool no_nt = getenv("FFVD_KFU_NO_NT") != nullptr;          // A/B switch (read once)
-    // streaming stores for outputs of 1 GB and more (nothing of them survives in a cache until the Gram kernel reads it);
-    // `streaming` 0 / 1 decides for the caller (a pass of a pipelined iteration is part of a larger output)
-    const bool nt = streaming >= 0 ? streaming != 0 : ((size_t)a.nb * a.Tp * a.Mp * sizeof(double) >= ((size_t)1 << 30) && !no_nt);
+void launch_kfu_build(hipStream_t stream, const ProjectArgs &a) {
+    // streaming stores for outputs of 1 GB and more (nothing of them survives in a cache until the Gram kernel reads it)
+    const bool nt = (size_t)a.nb * a.Tp * a.Mp * sizeof(double) >= ((size_t)1 << 30);
     if (nt) launch_kfu_build_nt<true>(stream, a);
     else launch_kfu_build_nt<false>(stream, a);
 }
@@ -360,9 +358,6 @@ void launch_kernel_diag(hipStream_t stream, int kind, const double *X, int N, in
 #ifdef FFVD_DF_TRACE
 __device__ long long df_trace_buf[64 * 64];
 __device__ long long gram_trace_buf[128 * 10 * 4];      // start, end, HW_ID, blockIdx of every Gram tile (<= 128 units of 10 tiles)
-#define DF_STAMP0(slot) do { if (blockIdx.x == 0 && threadIdx.x == 0) df_trace_buf[63 * 64 + (slot)] = wall_clock64(); } while (0)
-#else
-#define DF_STAMP0(slot) do { } while (0)
 #endif
 
 // 64x64 Cholesky by ONE wavefront with no workgroup barriers: lane = row, the whole row in registers
@@ -377,12 +372,6 @@ __device__ long long gram_trace_buf[128 * 10 * 4];      // start, end, HW_ID, bl
 // PIPE = false drops the software pipeline (plain left-looking sums, the newest term by v_readlane): about 100
 // VGPRs fewer, for launches whose many workgroups care about occupancy more than about one tile's latency.
 constexpr int LR_LD = NB + 2;
-#ifndef DF_FACTOR_4W
-#define DF_FACTOR_4W 1            // the 64-pivot diagonal factor by all four wavefronts (chol64_mfma_4w); 0: wavefront 0 alone (A/B builds)
-#endif
-#ifndef DF_FACTOR_ROWS
-#define DF_FACTOR_ROWS 1          // chol64_mfma_4w: the tiles below a diagonal tile go through its pivot chain (0: tile solves on the matrix cores, A/B builds)
-#endif
 constexpr int DV_LD = 17;       // row stride of the 16 x 16 inverse / scratch tiles (doubles)
 template <bool PIPE>
 __device__ __forceinline__ int chol64_1w(double (&a)[NB], double (*Lr)[LR_LD], double *invd, const int lane) {
@@ -440,178 +429,21 @@ __device__ __forceinline__ int chol64_1w(double (&a)[NB], double (*Lr)[LR_LD], d
     return bad;
 }
 
-// 64x64 Cholesky by ONE wavefront, blocked 4 x 4 in 16 x 16 tiles, left-looking at tile level: everything but the
-// pivots runs on the matrix cores.  For tile column s:
-//   S_s = T_ss - sum_{k<s} L_sk L_sk^T                        (s tile products, accumulator layout -> LDS -> lane = row)
-//   16-pivot chain on S_s in registers (right-looking, the multipliers by v_readlane); lanes 16..31 carry the rows of the
-//     identity through the same updates and come out as L_ss^-T, which is at once the operand of the tile solves below and the
-//     inverted diagonal sub-block the panel kernels multiply by (dinv_b, no separate substitution pass)
-//   L_is^T = L_ss^-1 (T_is - sum_{k<s} L_ik L_sk^T)^T  for i > s, kept TRANSPOSED in the accumulator layout (= the B-operand
-//     layout of the next product, as in potrf_panel_kernel), one residual refinement against L_ss.
-// The single-wavefront chain above (chol64_1w) issues 2016 dependent-free but in-order FMA + LDS-broadcast pairs for its
-// left-looking sums and is bound by that issue stream (13 us); here those sums are 64 + 48 MFMAs and the four chains have at
-// most 15 terms per pivot.  No workgroup barrier inside: LDS hand-offs are within the wavefront.
+// 64x64 Cholesky by the FOUR wavefronts of the workgroup, blocked 4 x 4 in 16 x 16 tiles, left-looking at tile level.  For tile
+// column s the wavefronts form T'_is = T_is - sum_{k<s} L_ik L_sk^T of the step's tiles side by side on the matrix cores (i = s +
+// wave), one barrier, then wavefront 0 runs ONE 16-pivot chain in registers with the tiles BELOW the diagonal tile riding through
+// it.  The chain is right-looking -- pivot j scales column j of every row and subtracts its multiple of row j's multipliers from the
+// columns right of it -- so a lane that starts from a row of T'_is comes out holding that row of L_is, exactly as the unblocked
+// factorisation would produce it.  Lanes 0-15: the diagonal tile, 16-31: the rows of the identity (they come out as L_ss^-T, the
+// inverted diagonal sub-block the panel kernels multiply by), 32-47 / 48-63: tiles (s+1, s), (s+2, s); step 0 has a third tile
+// below, which a second wavefront takes through the same chain (it repeats the pivots for itself).  The chain as in tiny.hip's
+// tiny_chol_inv: per-lane base pointers instead of an exec-masked load per element, no scalar test per pivot -- a non-positive or
+// NaN pivot leaves NaN on L's diagonal from there on, looked for once behind the chain.  tools/df_trace.py: about 10.5 us per
+// 64-block, i.e. per block column of every factorisation's latency chain (one wavefront with tile solves behind every chain: 15.5).
 // In: Ts (lower triangle valid).  Out: Lr = L (lower triangle of every tile row, exact zeros above the diagonal inside the
-// diagonal tiles), dinv_b[(16 s + r) * 16 + c] = (L_ss^-1)[r][c] in global memory.  Sc: two 16 x DV_LD scratch tiles.
-// Returns 0 or 1 + first bad pivot.
-__device__ __forceinline__ int chol64_mfma_1w(double (*Ts)[NB + 1], double (*Lr)[LR_LD], double (*Sc)[16][DV_LD],
-                                              double *dinv_b, const int lane) {
-    const int lr = lane & 15, lk = lane >> 4;
-    int bad = 0;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-        const int s0 = 16 * s;
-        DF_STAMP0(4 * s + 0);
-        d4 acc = (d4){0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int k = 0; k < s; ++k)
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const double v = Lr[s0 + lr][16 * k + 4 * t + lk];      // A[m][kk] = B[kk][n]^T: the same tile
-                acc = mfma_f64(v, v, acc);
-            }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) Sc[0][lk + 4 * r][lr] = Ts[s0 + lk + 4 * r][s0 + lr] - acc[r];
-        wave_lds_order();
-        DF_STAMP0(4 * s + 1);
-        double a[16];
-#pragma unroll
-        for (int c = 0; c < 16; ++c) a[c] = (lane < 16) ? Sc[0][lr][c] : ((lane < 32 && lr == c) ? 1.0 : 0.0);
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const double ajj = readlane_f64(a[j], j);
-            if (!(ajj > 0.0) && bad == 0) bad = s0 + j + 1;
-            double piv, y;
-            pivot_sqrt(ajj, piv, y);
-            a[j] *= y;
-#pragma unroll
-            for (int c = j + 1; c < 16; ++c) a[c] = fma(-a[j], readlane_f64(a[j], c), a[c]);
-        }
-        DF_STAMP0(4 * s + 2);
-        if (lane < 16) {
-#pragma unroll
-            for (int c = 0; c < 16; ++c) Lr[s0 + lr][s0 + c] = (c <= lr) ? a[c] : 0.0;
-        } else if (lane < 32) {
-#pragma unroll
-            for (int c = 0; c < 16; ++c) {
-                Sc[1][lr][c] = a[c];                                    // X = L_ss^-T
-                dinv_b[(s0 + c) * 16 + lr] = a[c];                      // (L_ss^-1)[c][lr] = X[lr][c]
-            }
-        }
-        wave_lds_order();
-        DF_STAMP0(4 * s + 3);
-#pragma unroll
-        for (int i = s + 1; i < 4; ++i) {
-            const int i0 = 16 * i;
-            d4 ac2 = (d4){0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-            for (int k = 0; k < s; ++k)
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-                    ac2 = mfma_f64(Lr[s0 + lr][16 * k + 4 * t + lk], Lr[i0 + lr][16 * k + 4 * t + lk], ac2);
-            d4 Rt;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) Rt[r] = Ts[i0 + lr][s0 + lk + 4 * r] - ac2[r];      // (T')^T[m][n] = T'[n][m]
-            d4 x = (d4){0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-            for (int t = 0; t < 4; ++t) x = mfma_f64(Sc[1][lk + 4 * t][lr], Rt[t], x);       // A = L_ss^-1[m][kk] = X[kk][m]
-            d4 res = Rt;
-#pragma unroll
-            for (int t = 0; t < 4; ++t) res = mfma_f64(-Lr[s0 + lr][s0 + 4 * t + lk], x[t], res);
-#pragma unroll
-            for (int t = 0; t < 4; ++t) x = mfma_f64(Sc[1][lk + 4 * t][lr], res[t], x);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) Lr[i0 + lr][s0 + lk + 4 * r] = x[r];                // L_is[n][m]
-        }
-        wave_lds_order();
-    }
-    DF_STAMP0(16);
-    return bad;
-}
-
-// The same factor by the FOUR wavefronts of the workgroup (round 4): wavefront 0 keeps the critical path -- tile (s+1, s), the sums
-// of diagonal tile s + 1 and its 16-pivot chain -- and the tiles (s+2, s), (s+3, s) of column step s, which chol64_mfma_1w solved
-// behind every chain, go to wavefronts 1 and 2 beside it (tiny_chol_inv's schedule on the 4 x 4 tiles of a 64-block): 15.5 -> about
-// 11.5 us per diagonal block, i.e. per block column of every factorisation's latency chain.  Sc: three 16 x DV_LD scratch tiles
-// (S; L_ss^-T of the even and of the odd steps: the helpers of step s read it while wavefront 0 writes the next one).
-// All 256 threads call; returns wavefront 0's verdict on every thread of wavefront 0 (others: 0).
-__device__ __forceinline__ void chol64_tile_solve(double (*Ts)[NB + 1], double (*Lr)[LR_LD], const double (*X)[DV_LD], const int s,
-                                                  const int i, const int lr, const int lk) {
-    const int s0 = 16 * s, i0 = 16 * i;
-    d4 ac2 = (d4){0.0, 0.0, 0.0, 0.0};
-    for (int k = 0; k < s; ++k)
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-            ac2 = mfma_f64(Lr[s0 + lr][16 * k + 4 * t + lk], Lr[i0 + lr][16 * k + 4 * t + lk], ac2);
-    d4 Rt;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) Rt[r] = Ts[i0 + lr][s0 + lk + 4 * r] - ac2[r];      // (T')^T[m][n] = T'[n][m]
-    d4 x = (d4){0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int t = 0; t < 4; ++t) x = mfma_f64(X[lk + 4 * t][lr], Rt[t], x);           // A = L_ss^-1[m][kk] = X[kk][m]
-    d4 res = Rt;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) res = mfma_f64(-Lr[s0 + lr][s0 + 4 * t + lk], x[t], res);
-#pragma unroll
-    for (int t = 0; t < 4; ++t) x = mfma_f64(X[lk + 4 * t][lr], res[t], x);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) Lr[i0 + lr][s0 + lk + 4 * r] = x[r];                // L_is[n][m]
-}
-// sums + 16-pivot chain of diagonal tile s (one wavefront): L_ss into Lr, L_ss^-T into Xo and (transposed) into dinv_b.
-// Id: an identity tile in LDS (the rows lanes 16-31 start from).  The chain as in tiny.hip's tiny_chain16 (tools/probes/lat_probe.hip:
-// 1.92 -> 1.54 us): per-lane base pointers instead of an exec-masked load per element, no scalar test per pivot -- a non-positive or
-// NaN pivot leaves NaN on L's diagonal from there on, looked for once behind the chain.
-__device__ __forceinline__ int chol64_diag_tile(double (*Ts)[NB + 1], double (*Lr)[LR_LD], double (*Sw)[DV_LD], double (*Xo)[DV_LD],
-                                                const double (*Id)[DV_LD], double *dinv_b, const int s, const int lane) {
-    const int lr = lane & 15, lk = lane >> 4, s0 = 16 * s;
-    d4 acc = (d4){0.0, 0.0, 0.0, 0.0}, acc1 = acc;
-    for (int k = 0; k < s; ++k)
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const double v = Lr[s0 + lr][16 * k + 4 * t + lk];
-            if (t & 1) acc1 = mfma_f64(v, v, acc1);
-            else acc = mfma_f64(v, v, acc);
-        }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) Sw[lk + 4 * r][lr] = Ts[s0 + lk + 4 * r][s0 + lr] - (acc[r] + acc1[r]);
-    wave_lds_order();
-    double a[16];
-    const double *src = (lane < 16) ? &Sw[lr][0] : &Id[lr][0];
-#pragma unroll
-    for (int c = 0; c < 16; ++c) a[c] = src[c];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-        const double ajj = readlane_f64(a[j], j);
-        double piv, y;
-        pivot_sqrt(ajj, piv, y);
-        a[j] *= y;
-#pragma unroll
-        for (int c = j + 1; c < 16; ++c) a[c] = fma(-a[j], readlane_f64(a[j], c), a[c]);
-    }
-    double diag = a[0];
-#pragma unroll
-    for (int c = 1; c < 16; ++c) diag = (lr == c) ? a[c] : diag;
-    if (lane < 32) {
-        double *base = (lane < 16) ? &Lr[s0 + lr][s0] : &Xo[lr][0];
-#pragma unroll
-        for (int c = 0; c < 16; ++c) base[c] = (lane >= 16 || c <= lr) ? a[c] : 0.0;
-        if (lane >= 16) {
-#pragma unroll
-            for (int c = 0; c < 16; ++c) dinv_b[(s0 + c) * 16 + lr] = a[c];              // (L_ss^-1)[c][lr] = X[lr][c]
-        }
-    }
-    const unsigned long long m = __ballot((lane < 16) & !(diag > 0.0));
-    return m ? s0 + (int)__builtin_ctzll(m) + 1 : 0;
-}
-#if DF_FACTOR_ROWS
-// Round 4, second form: the tiles BELOW diagonal tile s ride through its 16-pivot chain.  The chain is right-looking -- pivot j scales
-// column j of every row and subtracts its multiple of row j's multipliers from the columns right of it -- so a lane that starts from a
-// row of T'_is = T_is - sum_{k<s} L_ik L_sk^T comes out holding that row of L_is, exactly as the unblocked factorisation would produce
-// it.  Lanes 0-15: the diagonal tile, 16-31: the identity (-> L_ss^-T for the panel solves), 32-47 / 48-63: tiles (s+1, s), (s+2, s);
-// step 0 has a third tile below, which a second wavefront takes through the same chain (it repeats the pivots for itself).  What was
-// a tile solve on the matrix cores behind every chain (three dependent groups of four MFMAs with an LDS round trip, then the sums of
-// the next diagonal tile) is gone from the latency chain: the wavefronts form the left-looking sums of the step's tiles side by
-// side, one barrier, chain.  tools/df_trace.py: the factor of a 64-block 14.5 -> about 10.5 us.
+// diagonal tiles), dinv_b[(16 s + r) * 16 + c] = (L_ss^-1)[r][c] in global memory.  Sc: four 16 x DV_LD scratch tiles (Sc[3]: the
+// identity).  All 256 threads call; ends with the workgroup synchronised; returns 0 or 1 + first bad pivot on every thread of
+// wavefront 0 (others: 0).
 __device__ __forceinline__ int chol64_mfma_4w(double (*Ts)[NB + 1], double (*Lr)[LR_LD], double (*Sc)[16][DV_LD], double *dinv_b) {
     const int lane = threadIdx.x & 63, lr = lane & 15, lk = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -682,42 +514,12 @@ __device__ __forceinline__ int chol64_mfma_4w(double (*Ts)[NB + 1], double (*Lr)
     }
     return bad;
 }
-#else
-__device__ __forceinline__ int chol64_mfma_4w(double (*Ts)[NB + 1], double (*Lr)[LR_LD], double (*Sc)[16][DV_LD], double *dinv_b) {
-    const int lane = threadIdx.x & 63, lr = lane & 15, lk = lane >> 4;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    // Sc[3]: the identity tile of the pivot chains (the four scratch tiles are the panel code's inverse blocks at other times)
-    if (threadIdx.x < 256) Sc[3][threadIdx.x >> 4][threadIdx.x & 15] = ((threadIdx.x >> 4) == (threadIdx.x & 15)) ? 1.0 : 0.0;
-    __syncthreads();
-    int bad = 0;
-    if (wave == 0) {
-        __builtin_amdgcn_s_setprio(3);
-        bad = chol64_diag_tile(Ts, Lr, Sc[0], Sc[1], Sc[3], dinv_b, 0, lane);
-        __builtin_amdgcn_s_setprio(0);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int s = 0; s < 3; ++s) {
-        const double (*X)[DV_LD] = Sc[1 + (s & 1)];
-        if (wave == 0) {
-            __builtin_amdgcn_s_setprio(3);
-            chol64_tile_solve(Ts, Lr, X, s, s + 1, lr, lk);
-            wave_lds_order();
-            const int b2 = chol64_diag_tile(Ts, Lr, Sc[0], Sc[1 + ((s + 1) & 1)], Sc[3], dinv_b, s + 1, lane);
-            if (b2 && !bad) bad = b2;
-            __builtin_amdgcn_s_setprio(0);
-        } else if (s + 1 + wave < 4) chol64_tile_solve(Ts, Lr, X, s, s + 1 + wave, lr, lk);
-        __syncthreads();
-    }
-    return bad;
-}
-#endif
 
 // Factorise the diagonal block held in LDS tile `Ts` (row-major, stride NB+1): wavefront 0 runs chol64_1w, which
 // leaves L in the LDS tile `Lr`; then all 256 threads publish L in place (lower triangle of the global block) and
 // the four wavefronts invert the four 16x16 diagonal sub-blocks of L (lane = column, 16-step forward substitution)
 // into dinv_b[4][16][16] -- what the panel kernel's blocked substitution multiplies by.
-// (Sc != nullptr: the blocked matrix-core factor chol64_mfma_1w, which needs Lr and Ts in DIFFERENT memory and two scratch
+// (Sc != nullptr: the blocked matrix-core factor chol64_mfma_4w, which needs Lr and Ts in DIFFERENT memory and four scratch
 // tiles, and leaves the inverted sub-blocks behind itself.)
 template <bool PIPE>
 __device__ __forceinline__ void diag_block_finish(double (*Ts)[NB + 1], double (*Lr)[LR_LD], double *invd, double *S, int n,
@@ -725,20 +527,8 @@ __device__ __forceinline__ void diag_block_finish(double (*Ts)[NB + 1], double (
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     if (Sc) {
-#if DF_FACTOR_4W
-        {
-            const int bad = chol64_mfma_4w(Ts, Lr, Sc, dinv_b);      // (ends with the workgroup synchronised)
-            if (w == 0 && bad && lane == 0 && *info_b == 0) *info_b = k0 + bad;
-        }
-#else
-        if (w == 0) {
-            __builtin_amdgcn_s_setprio(3);
-            const int bad = chol64_mfma_1w(Ts, Lr, Sc, dinv_b, lane);
-            __builtin_amdgcn_s_setprio(0);
-            if (bad && lane == 0 && *info_b == 0) *info_b = k0 + bad;
-        }
-        __syncthreads();
-#endif
+        const int bad = chol64_mfma_4w(Ts, Lr, Sc, dinv_b);      // (ends with the workgroup synchronised)
+        if (w == 0 && bad && lane == 0 && *info_b == 0) *info_b = k0 + bad;
         for (int r = tid >> 6; r < NB; r += 4)
             if (lane <= r) S[(size_t)(k0 + r) * n + k0 + lane] = Lr[r][lane];         // coalesced rows of L
         return;
@@ -1235,9 +1025,6 @@ void launch_trsm_ext(hipStream_t stream, double *A, int n, int extra_rows, int b
 // waiting workgroup leaves, info[b] = -1 says so).
 // Block order (group, row, matrix-in-group): G a multiple of 8, so all rows of a matrix share blockIdx % 8 = one XCD's L2.
 // ---------------------------------------------------------------------------------------------
-#ifndef DF_MFMA_FACTOR
-#define DF_MFMA_FACTOR 1
-#endif
 constexpr int DF_PS = 64;                         // progress words per matrix (main block rows: n <= 4096)
 static_assert(DF_PS == 64, "launch_kuu_build zeroes 64 progress words per matrix");
 constexpr int DF_DINV = 4 * 16 * 16;              // doubles of inverted diagonal sub-blocks per (matrix, block column)
@@ -1258,7 +1045,6 @@ struct DfArgs {
     size_t kinv_stride;//   the identity-row workgroups once their rows are complete (df_inverse_tiles)
     int defer_ext;     // block order: identity-structured rows of all groups behind the main rows of all groups (potrf_df_kernel)
     int kinv_help;     // (with kinv, every workgroup resident at once) the main-row workgroups form half of the inverse's tiles: df_inverse_tiles
-    int kacc;          // (with kinv) the inverse's tiles are accumulated column by column as the rows of L^-T arrive: df_inverse_column
     int fine;          // small batches (every block row on a CU of its own): a main row also announces every COLUMN it has solved
                        // (word 2 nb + row), and a gather waits term by term -- see df_column
     const double *lt;  // optional: the identity-structured extra rows of slab b start as L_d^T (d = b % lt_dl) instead of what
@@ -1587,84 +1373,6 @@ __device__ __forceinline__ void df_vector_row(const DfArgs &a, double *S, int *p
     }
 }
 
-// Round 5 (lead 2): the inverse's tiles accumulated AS THE COLUMNS ARRIVE.  Tile (e, f) of A^-1 = W W^T, W = L^-T, is
-// sum_{j >= e} W(e,j) W(f,j)^T, and term j exists as soon as block column j of rows e and f is solved -- df_inverse_tiles forms all
-// of it behind the last column (up to 20 tile products: 60-70 us behind the chain of a K_uu matrix).  Here identity-row workgroup e,
-// right behind its column j: announces it (word 3 nb + e = columns done), and for every f <= e waits for row f's column j, carries the
-// tile's accumulator over from the previous column THROUGH MEMORY (the same lanes wrote it), runs the same 16 MFMA steps on it and
-// puts it back; the last column also writes the mirror image.  The same products on the same accumulators in the same order as
-// df_inverse_tiles: the same bits.  What is left behind the last column is one product per tile of the workgroup's row.
-__device__ __forceinline__ bool df_inverse_column(const DfArgs &a, double *S, int *pg, const int b, const int e, const int j,
-                                                  double (*Xs)[LL_LD], double (*Ls)[LL_LD], int *wslot, int &wc) {
-    const int n = a.n, nb = a.nb;
-    const int tid = threadIdx.x, lane = tid & 63, lr = lane & 15, lk = lane >> 4;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int qr = wave >> 1, qc = wave & 1;
-    const int sr = tid >> 5, sc = 2 * (tid & 31);
-    int *pc = pg + 3 * nb;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // this wavefront's stores of W(e,j) (and of the previous column's tiles) have left it
-    __syncthreads();
-    if (tid == 0) df_publish(pc + e, j + 1);
-    double *Kb = a.kinv + (size_t)b * a.kinv_stride;
-    const double *We = S + (size_t)(n + e * NB) * n + (size_t)j * NB;
-    const bool last = j + 1 == nb;
-    for (int f = 0; f <= e; ++f) {
-        if (f < e) {
-            const int seen = df_wait(pc + f, j + 1, a.abort_w, &wslot[wc++ & 1]);
-            if (seen < 0) return false;
-        }
-        const double *Wf = S + (size_t)(n + f * NB) * n + (size_t)j * NB;
-        d2 vx[8], vl[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            vx[i] = *reinterpret_cast<const d2 *>(We + (size_t)(sr + 8 * i) * n + sc);
-            vl[i] = *reinterpret_cast<const d2 *>(Wf + (size_t)(sr + 8 * i) * n + sc);
-        }
-        d4 acc[2][2];
-#pragma unroll
-        for (int x = 0; x < 2; ++x)
-#pragma unroll
-            for (int y = 0; y < 2; ++y)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const size_t i = (size_t)(e * NB + qr * 32 + 16 * x + lk + 4 * q), jj = (size_t)(f * NB + qc * 32 + 16 * y + lr);
-                    acc[x][y][q] = (j > e) ? Kb[i * n + jj] : 0.0;
-                }
-        __syncthreads();                                // everyone is done reading the previous tiles
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            Xs[sr + 8 * i][sc] = vx[i].x; Xs[sr + 8 * i][sc + 1] = vx[i].y;
-            Ls[sr + 8 * i][sc] = vl[i].x; Ls[sr + 8 * i][sc + 1] = vl[i].y;
-        }
-        __syncthreads();
-#pragma unroll 4
-        for (int ks = 0; ks < NB / 4; ++ks) {
-            double ax[2], bl[2];
-#pragma unroll
-            for (int x = 0; x < 2; ++x) {
-                ax[x] = Xs[qr * 32 + 16 * x + lr][4 * ks + lk];
-                bl[x] = Ls[qc * 32 + 16 * x + lr][4 * ks + lk];
-            }
-#pragma unroll
-            for (int x = 0; x < 2; ++x)
-#pragma unroll
-                for (int y = 0; y < 2; ++y) acc[x][y] = mfma_f64(ax[x], bl[y], acc[x][y]);
-        }
-#pragma unroll
-        for (int x = 0; x < 2; ++x)
-#pragma unroll
-            for (int y = 0; y < 2; ++y)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const size_t i = (size_t)(e * NB + qr * 32 + 16 * x + lk + 4 * q), jj = (size_t)(f * NB + qc * 32 + 16 * y + lr);
-                    Kb[i * n + jj] = acc[x][y][q];
-                    if (last && f < e) Kb[jj * n + i] = acc[x][y][q];
-                }
-    }
-    __syncthreads();                                    // (the next column's staging reuses the tiles)
-    return true;
-}
-
 // Identity-row workgroup e, its row W(e, e..) = (L^-T)(e, .) complete: announce it, then form the tiles (e, f), f <= e, of
 // A^-1 = L^-T L^-1 = W W^T:  (e,f) = sum_{j >= e} W(e,j) W(f,j)^T  (rows f < e belong to workgroups dispatched earlier).  The
 // same staging loop as the panel gather; both triangles are written.  A separate product launch after the factorisation
@@ -1819,7 +1527,6 @@ __global__ __launch_bounds__(256, 2) void potrf_df_kernel(DfArgs a) {
                 }
             }
         } else {
-            const bool kacc = a.kacc && !main_row && ri - nb < a.nid;
             for (int j = k0; j < nplain; ++j) {
                 d4 unused_c[2][2], unused_a[2][2];
                 if (!df_column<false>(a, S, pg, dvb, row0, j, k0, Xs, Ls, Dv, wslot, wc, unused_c, unused_a, trow, xt_row, lt_src,
@@ -1827,15 +1534,11 @@ __global__ __launch_bounds__(256, 2) void potrf_df_kernel(DfArgs a) {
                     if (tid == 0 && a.info) a.info[b] = -1;
                     return;
                 }
-                if (kacc && !df_inverse_column(a, S, pg, b, ri - nb, j, Xs, Ls, wslot, wc)) {
-                    if (tid == 0 && a.info) a.info[b] = -1;
-                    return;
-                }
             }
         }
     }
     if (!main_row) {
-        if (a.kinv && !a.kacc && ri - nb < a.nid && !df_inverse_tiles(a, S, pg, b, ri - nb, Xs, Ls, wslot)) {
+        if (a.kinv && ri - nb < a.nid && !df_inverse_tiles(a, S, pg, b, ri - nb, Xs, Ls, wslot)) {
             if (tid == 0 && a.info) a.info[b] = -1;
         }
         return;
@@ -1886,7 +1589,7 @@ __global__ __launch_bounds__(256, 2) void potrf_df_kernel(DfArgs a) {
         df_publish(pg + ri, ri);
         if (a.fine) __hip_atomic_store(pg + 2 * nb + ri, ri, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (behind the release above)
     }
-    diag_block_finish<PIPE>(Ts, Lr, invd, S, n, row0, a.info + b, dvb + (size_t)ri * DF_DINV, DF_MFMA_FACTOR ? Dv : nullptr);
+    diag_block_finish<PIPE>(Ts, Lr, invd, S, n, row0, a.info + b, dvb + (size_t)ri * DF_DINV, Dv);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     DF_STAMP(trow, 49);
@@ -1947,21 +1650,11 @@ static void launch_potrf_flow(hipStream_t stream, double *A, int n, int extra_ro
     a.defer_ext = (a.nid > 0 && groups > 1 && !a.xt && !a.kinv && defer_mode != 0) ? 1 : 0;
     // Few matrices (every block row finds a CU of its own): 16 KB of unused dynamic LDS keep a second workgroup off the CU --
     // a pivot chain that shares its SIMD with another row's MFMA loop takes up to twice as long (tools/df_trace.py)
-    static const int pad_mode = [] { const char *e = getenv("FFVD_DF_PAD"); return e ? atoi(e) : -1; }();
     // (... and up to 640 block rows without identity-structured rows -- 64 matrices of a 16-chain rank: 1.87 vs 1.945 ms per iteration with
     //  one row per compute unit; 288 and 432 rows no difference, 864 none, 1152 rows 2 % slower: profiles/r04_ab_df_pad.txt)
     const bool one_per_cu = (size_t)batch * R <= 256 || (a.nid == 0 && (size_t)batch * R <= 640);
-    static const int kh_mode = [] { const char *e = getenv("FFVD_DF_KINV_HELP"); return e ? atoi(e) : -1; }();
-    // column-wise accumulation of the inverse's tiles (df_inverse_column): opt-in, FFVD_DF_KACC=1 -- built for the few-chain schedules,
-    // where the chain's tail is on the iteration's critical path, bit-identical, and measured SLOWER there (per-rank iteration at
-    // 1 / 2 / 4 / 8 chains 0.458 / 0.540 / 0.718 / 1.026 ms against 0.428 / 0.508 / 0.685 / 1.003, profiles/r05_ab_kacc.txt): a tile
-    // update through memory is a wait, two tile loads, the accumulator's round trip, 64 MFMAs and a store in sequence (4-8 us), row 7
-    // has eight of them behind the last column, nobody helps it (the main rows' help needs finished rows), and the identity rows now
-    // wait for each other at every column.  Needs a fourth set of progress words.
-    const int kacc_mode = [] { const char *e = getenv("FFVD_DF_KACC"); return e ? atoi(e) : -1; }();      // (read per launch: tests switch it)
-    a.kacc = (a.kinv && a.nid == a.nb && 4 * a.nb <= DF_PS && kacc_mode > 0) ? 1 : 0;
-    a.kinv_help = (kinv_help && a.kinv && !a.kacc && a.nid == a.nb && (size_t)batch * R <= 256 && kh_mode != 0) ? 1 : 0;
-    const bool alone = (pad_mode >= 0) ? (pad_mode != 0) : one_per_cu;
+    a.kinv_help = (kinv_help && a.kinv && a.nid == a.nb && (size_t)batch * R <= 256) ? 1 : 0;
+    const bool alone = one_per_cu;
     const int fine_mode = [] { const char *e = getenv("FFVD_DF_FINE"); return e ? atoi(e) : -1; }();      // (read per launch: tests switch it)
     a.fine = ((fine_mode >= 0 ? fine_mode != 0 : (alone && (size_t)batch * R <= 256)) && 3 * a.nb <= DF_PS) ? (fine_mode == 2 ? 2 : 1) : 0;    // (2: A/B, no early sums)
     hipLaunchKernelGGL(potrf_df_kernel<true>, dim3((unsigned)((size_t)groups * R * a.G)), dim3(256), alone ? 16384 : 0, stream, a);
@@ -2394,12 +2087,6 @@ void launch_linear_lowrank(hipStream_t stream, const ProjectArgs &a, double *par
 // (Measured alternatives at M = 512, T = 4096, 128 units: 4 wavefronts of 64x64 3.45 ms; 16 wavefronts of 32x32,
 //  one workgroup per CU 3.36 ms; 128x64 tiles, 8 wavefronts of 32x32 3.27 ms; this layout 2.98 ms.)
 // ---------------------------------------------------------------------------------------------
-#ifndef GRAM_GLDS_OFFDIAG
-#define GRAM_GLDS_OFFDIAG 0         // 1: off-diagonal tiles staged by LDS-DMA too -- measured neutral (2.24 vs 2.25 ms, profiles/r04_ab_gram_offdiag_glds.txt)
-#endif
-#ifndef GRAM_COMBO
-#define GRAM_COMBO 2                // 0: none, 1: three 64 x 32-sub-block workgroups per four diagonal tiles (round 3), 2: pair combos (round 4)
-#endif
 constexpr int GT = 16;              // rows of A per LDS chunk
 constexpr int G_LD = 128 + 16;      // LDS row stride (doubles): lanes l and l+16 land in different bank halves
 
@@ -2412,7 +2099,7 @@ template <int N>
 __device__ __forceinline__ bool gram_tail_exchange(const GramArgs &a, const int tail_id, const int half, const bool active,
                                                    d4 (&acc)[N], double &bs0, double &bs1, int *tail_slot);
 
-template <int MODE, bool DIAG, bool GLDS = false>
+template <int MODE, bool DIAG>
 __device__ __forceinline__ void gram_body(const GramArgs a, const int bz, const int ti, const int tj, const int tile,
                                           const int kpart, const int ksplit, double (*As)[GT][G_LD],
                                           double (*Bs)[GT][G_LD], double (*dls)[GT], double *red, const int tail_id = -1,
@@ -2491,35 +2178,12 @@ __device__ __forceinline__ void gram_body(const GramArgs a, const int bz, const 
     const int per = (nchunk_all + nrange - 1) / nrange;
     const int cbeg = kpart * per;
     const int nchunk = (cbeg + per <= nchunk_all) ? cbeg + per : nchunk_all;      // this range: chunks [cbeg, nchunk)
-    // GLDS (off-diagonal tiles of launches whose panels are whole: Mp a multiple of 128): the panels go global -> LDS by DMA, as in the
-    // pair combos (gram_pair_role has the notes), no staging registers and no ds_write pass
-    const unsigned voffA = (unsigned)((rowl * Mp + ti * 128 + 2 * lane) * (int)sizeof(double));
-    const unsigned voffB = (unsigned)((rowl * Mp + tj * 128 + 2 * lane) * (int)sizeof(double));
-    auto glds = [&](const double *base, const unsigned voff, const void *lds_row) {
-        typedef __attribute__((address_space(3))) void lvoid;
-        const unsigned dst = (unsigned)(uintptr_t)(lvoid *)lds_row;
-        unsigned keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(voff), "s"(dst), "s"(base) : "memory");
-    };
-    auto dma = [&](int c, int buf) {
-        const double *base0 = Ab + (size_t)c * GT * Mp, *base1 = base0 + (size_t)8 * Mp;
-        glds(base0, voffA, &As[buf][wave][0]);
-        glds(base0, voffB, &Bs[buf][wave][0]);
-        glds(base1, voffA, &As[buf][wave + 8][0]);
-        glds(base1, voffB, &Bs[buf][wave + 8][0]);
-    };
-    if (GLDS) {
-        dma(cbeg, cbeg & 1);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    } else {
-        gload(cbeg);
-        lstore(cbeg & 1);
-    }
+    gload(cbeg);
+    lstore(cbeg & 1);
     __syncthreads();
     for (int c = cbeg; c < nchunk; ++c) {
         const int buf = c & 1;
-        if (c + 1 < nchunk) { if (GLDS) dma(c + 1, buf ^ 1); else gload(c + 1); }
+        if (c + 1 < nchunk) gload(c + 1);
         if (active) {
             const double(*Bp)[G_LD] = DIAG ? As[buf] : Bs[buf];
             double af[4], bf[2], afn[4], bfn[2];
@@ -2549,8 +2213,7 @@ __device__ __forceinline__ void gram_body(const GramArgs a, const int bz, const 
 #pragma unroll
             for (int r = 0; r < GT; ++r) bsum += As[buf][r][tid - 384] * dls[buf][r];
         }
-        if (GLDS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the next chunk has landed (the DMAs are invisible to hipcc's counting)
-        else if (c + 1 < nchunk) lstore(buf ^ 1);
+        if (c + 1 < nchunk) lstore(buf ^ 1);
         __syncthreads();
     }
 
@@ -2680,151 +2343,6 @@ __device__ __forceinline__ bool gram_tail_exchange(const GramArgs &a, const int 
     bs1 += Po[(size_t)(4 * N + 1) * 512 + tid];
     return true;
 }
-
-// "Combo" workgroups: the 24 sub-blocks (64 x 32) of the four diagonal tiles of a group of four column panels b .. b + 3, dealt
-// to three workgroups of eight -- every wavefront a full sub-block, every SIMD two matrix wavefronts, as in an off-diagonal tile:
-//   type 0 (panels b, b+1 in LDS):     tile (b,b) complete (6)                + rows 0-63 of tile (b+1,b+1) (2)
-//   type 1 (panels b+1, b+2):          rows 64-127 of tile (b+1,b+1) (4)      + rows 64-127 of tile (b+2,b+2) (4)
-//   type 2 (panels b+2, b+3):          rows 0-63 of tile (b+2,b+2) (2)        + tile (b+3,b+3) complete (6)
-// (gram_body<.., true> gives a diagonal tile's six sub-blocks to six wavefronts: SIMDs 0 and 1 carry two matrix wavefronts, SIMDs
-// 2 and 3 one, the tile lasts as long as an off-diagonal one -- 1085 vs 1091 us, tools/gram_rounds.py -- and what SIMDs 2 and 3
-// have to spare nobody can use.)  Combos form no delta^T A row -- there is no idle wavefront for it, and vector FMAs beside the
-// matrix work cost 0.47 ms at config 2: launch_gram uses them only for launches with with_row = 0 (the Gram route sums
-// delta^T K_fu in the K_fu build, kfu_build_kernel / brow_finish_kernel).
-// entry = buffer (0 = first panel, 1 = second) << 3 | row half << 2 | column quarter
-__device__ __constant__ unsigned char GRAM_COMBO_ROLE[3][8] = {
-    {0 << 3 | 1 << 2 | 0, 0 << 3 | 1 << 2 | 1, 0 << 3 | 1 << 2 | 2, 0 << 3 | 1 << 2 | 3, 0 << 3 | 0 << 2 | 0, 0 << 3 | 0 << 2 | 1, 1 << 3 | 0 << 2 | 0, 1 << 3 | 0 << 2 | 1},
-    {0 << 3 | 1 << 2 | 0, 0 << 3 | 1 << 2 | 1, 0 << 3 | 1 << 2 | 2, 0 << 3 | 1 << 2 | 3, 1 << 3 | 1 << 2 | 0, 1 << 3 | 1 << 2 | 1, 1 << 3 | 1 << 2 | 2, 1 << 3 | 1 << 2 | 3},
-    {0 << 3 | 0 << 2 | 0, 0 << 3 | 0 << 2 | 1, 1 << 3 | 1 << 2 | 0, 1 << 3 | 1 << 2 | 1, 1 << 3 | 1 << 2 | 2, 1 << 3 | 1 << 2 | 3, 1 << 3 | 0 << 2 | 0, 1 << 3 | 0 << 2 | 1}};
-
-template <int MODE>
-__device__ __forceinline__ void gram_combo_body(const GramArgs a, const int bz, const int pbase, const int type, const int tail_id,
-                                                const int half, double (*As)[GT][G_LD], double (*Bs)[GT][G_LD],
-                                                double *red, int *tail_slot) {
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int lr = lane & 15, lk = lane >> 4;
-    const int Mp = a.Mp;
-    const int b = a.b0 + bz, s = b / a.Dl, dl = b % a.Dl, dg = a.d_begin + dl;
-    const int pa = pbase + type, pb = pbase + type + 1;                  // the two panels this workgroup stages
-    const int role = __builtin_amdgcn_readfirstlane((int)GRAM_COMBO_ROLE[type][wave]);
-    const int rbuf = role >> 3, rh = (role >> 2) & 1, rq = role & 3;
-    const int panel = rbuf ? pb : pa;
-    const int I0 = panel * 128 + rh * 64, J0 = panel * 128 + rq * 32;   // Mp % 512 == 0: every sub-block is real
-    const int r0 = rh * 64, c0 = rq * 32;                               // offsets inside the staged panel
-
-    const double *Ab = a.A + (size_t)bz * a.a_stride;
-    const int colA = pa * 128 + 2 * lane, colB = pb * 128 + 2 * lane;
-    const int rowl = tid >> 6;   // 0..7
-    double2 ra0, ra1, rb0, rb1;
-    auto gload = [&](int c) {
-        const double *row0 = Ab + ((size_t)c * GT + rowl) * Mp, *row1 = row0 + (size_t)8 * Mp;
-        ra0 = *reinterpret_cast<const double2 *>(row0 + colA);
-        rb0 = *reinterpret_cast<const double2 *>(row0 + colB);
-        ra1 = *reinterpret_cast<const double2 *>(row1 + colA);
-        rb1 = *reinterpret_cast<const double2 *>(row1 + colB);
-    };
-    auto lstore = [&](int buf) {
-        *reinterpret_cast<double2 *>(&As[buf][rowl][2 * lane]) = ra0;
-        *reinterpret_cast<double2 *>(&Bs[buf][rowl][2 * lane]) = rb0;
-        *reinterpret_cast<double2 *>(&As[buf][rowl + 8][2 * lane]) = ra1;
-        *reinterpret_cast<double2 *>(&Bs[buf][rowl + 8][2 * lane]) = rb1;
-    };
-
-    d4 acc[4][2];
-#pragma unroll
-    for (int x = 0; x < 4; ++x)
-#pragma unroll
-        for (int y = 0; y < 2; ++y) acc[x][y] = (d4){0.0, 0.0, 0.0, 0.0};
-    const int nchunk_all = a.rows / GT;
-    const int nrange = (tail_id >= 0) ? 2 : 1;
-    const int per = (nchunk_all + nrange - 1) / nrange;
-    const int cbeg = half * per;
-    const int nchunk = (cbeg + per <= nchunk_all) ? cbeg + per : nchunk_all;
-    gload(cbeg);
-    lstore(cbeg & 1);
-    __syncthreads();
-    for (int c = cbeg; c < nchunk; ++c) {
-        const int buf = c & 1;
-        if (c + 1 < nchunk) gload(c + 1);
-        {
-            const double(*Sp)[G_LD] = rbuf ? Bs[buf] : As[buf];          // this wavefront's panel holds both of its operands
-            double af[4], bf[2], afn[4], bfn[2];
-#pragma unroll
-            for (int x = 0; x < 4; ++x) af[x] = Sp[lk][r0 + 16 * x + lr];
-#pragma unroll
-            for (int y = 0; y < 2; ++y) bf[y] = Sp[lk][c0 + 16 * y + lr];
-#pragma unroll
-            for (int ks = 0; ks < GT / 4; ++ks) {
-                if (ks + 1 < GT / 4) {       // fragments of the next k-step are requested before this step's MFMAs
-#pragma unroll
-                    for (int x = 0; x < 4; ++x) afn[x] = Sp[4 * (ks + 1) + lk][r0 + 16 * x + lr];
-#pragma unroll
-                    for (int y = 0; y < 2; ++y) bfn[y] = Sp[4 * (ks + 1) + lk][c0 + 16 * y + lr];
-                }
-#pragma unroll
-                for (int x = 0; x < 4; ++x)
-#pragma unroll
-                    for (int y = 0; y < 2; ++y) acc[x][y] = mfma_f64(af[x], bf[y], acc[x][y]);
-#pragma unroll
-                for (int x = 0; x < 4; ++x) af[x] = afn[x];
-#pragma unroll
-                for (int y = 0; y < 2; ++y) bf[y] = bfn[y];
-            }
-        }
-        if (c + 1 < nchunk) lstore(buf ^ 1);
-        __syncthreads();
-    }
-    double bs0 = 0.0, bs1 = 0.0;           // (no delta^T A row here: launch_gram gives combos only to launches without one)
-    if (tail_id >= 0 && !gram_tail_exchange(a, tail_id, half, true, reinterpret_cast<d4(&)[8]>(acc), bs0, bs1, tail_slot)) return;
-
-    const double scale = (MODE == GRAM_PLAIN) ? 1.0 : a.yn_over_batch / exp(a.log_Q[dg]);
-    double *Hb = a.H + (size_t)bz * a.h_stride;
-    const double *Kadd = (MODE == GRAM_KFU || MODE == GRAM_KFU_RAW) ? a.Kadd + (size_t)dl * a.kadd_stride : nullptr;
-    const double *Kinv = (MODE == GRAM_KFU) ? a.Kinv + (size_t)dl * a.kinv_stride : nullptr;
-    double *Rb = (MODE == GRAM_KFU_RAW) ? a.part + (size_t)bz * ((size_t)(Mp + 1) * Mp) : nullptr;
-    double *Cb2 = ((MODE == GRAM_KFU_RAW || MODE == GRAM_KFU) && a.Hcopy) ? a.Hcopy + (size_t)bz * a.hcopy_stride : nullptr;
-    double trp = 0.0;
-#pragma unroll
-    for (int x = 0; x < 4; ++x)
-#pragma unroll
-        for (int y = 0; y < 2; ++y)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int i = I0 + 16 * x + lk + 4 * q, j = J0 + 16 * y + lr;
-                const double g = acc[x][y][q];
-                double v;
-                if (MODE == GRAM_F) v = g * scale + ((i == j) ? 1.0 : 0.0);
-                else if (MODE == GRAM_KFU_RAW) {
-                    v = g * scale + Kadd[(size_t)i * Mp + j];
-                    Rb[(size_t)i * Mp + j] = g;
-                    if (Cb2 && j <= i) {                    // the copy holds the lower triangle (its readers sum over the chains first and mirror the sum: a mirror here was 64 cache lines per store)
-                        Cb2[(size_t)i * Mp + j] = v;
-                    }
-                } else if (MODE == GRAM_KFU) {
-                    v = g * scale + Kadd[(size_t)i * Mp + j];
-                    if (Cb2 && j <= i) {
-                        Cb2[(size_t)i * Mp + j] = v;
-                    }
-                    const double w = (i > j) ? 2.0 : ((i == j) ? 1.0 : 0.0);
-                    trp += w * (Kinv[(size_t)i * Mp + j] * g);
-                } else v = g;
-                Hb[(size_t)i * Mp + j] = v;
-            }
-    if (MODE == GRAM_KFU) {      // deterministic workgroup reduction of the trace partial; slot of the first panel's diagonal tile
-        red[tid] = trp;
-        __syncthreads();
-        for (int st = 256; st > 0; st >>= 1) {
-            if (tid < st) red[tid] += red[tid + st];
-            __syncthreads();
-        }
-        if (tid == 0) {
-            a.trpart[(size_t)b * a.ntiles + pa * (pa + 1) / 2 + pa] = red[0];
-            if (type == 2) a.trpart[(size_t)b * a.ntiles + pb * (pb + 1) / 2 + pb] = 0.0;     // (three workgroups, four slots)
-        }
-    }
-}
-
 
 // "Pair" combos (round 4): 16-granular triangle.  A diagonal 128-tile has 8 x 9 / 2 = 36 MFMA tiles on or below its diagonal; row
 // block i (16 rows) owns i + 1 of them, so the row blocks i and 7 - i together own NINE whatever i -- four wavefronts per diagonal
@@ -3009,7 +2527,7 @@ __global__ __launch_bounds__(512, 4) void gram_kernel(GramArgs a) {
     const int xcd = id & 7;
     int loc = id >> 3;
     const int ksplit = (a.ksplit > 1 && a.part) ? a.ksplit : 1;
-    const int per_unit = a.wg_per_unit;                  // ntiles * ksplit, or (combos) off-diagonal tiles + 3 per group of 4 panels
+    const int per_unit = a.wg_per_unit;                  // ntiles * ksplit, or (combos) off-diagonal tiles + one per pair of panels, * ksplit
     // tail split: the last tail_wg / 8 workgroup slots of every XCD's list appear twice, first all their first row halves, then
     // all their second ones (workgroups that run together then read the same rows of K_fu)
     int tail_id = -1, tail_half = 0;
@@ -3042,15 +2560,11 @@ __global__ __launch_bounds__(512, 4) void gram_kernel(GramArgs a) {
     if (a.combo) {
         const int n128 = a.Mp / 128, noff = n128 * (n128 - 1) / 2, w = wsel / ksplit;      // (split-K: the row ranges of a workgroup are neighbours in the list)
         const int cpart = (tail_id >= 0) ? tail_half : wsel % ksplit;
-        if (w >= noff) {                                 // a combo workgroup: pair combos take two panels, the older ones three per group of four
+        if (w >= noff) {                                 // a pair combo: the diagonal tiles of two neighbouring panels
 #ifdef FFVD_DF_TRACE
             const long long tc0 = wall_clock64();
 #endif
-#if GRAM_COMBO == 2
             gram_pair_body<MODE>(a, bz, 2 * (w - noff), tail_id, cpart, ksplit, As, Bs, red, &tail_slot);
-#else
-            gram_combo_body<MODE>(a, bz, 4 * ((w - noff) / 3), (w - noff) % 3, tail_id, tail_half, As, Bs, red, &tail_slot);
-#endif
 #ifdef FFVD_DF_TRACE
             if (threadIdx.x == 0 && bz < 128 && per_unit <= 10 && MODE == GRAM_KFU) {
                 long long *g = gram_trace_buf + (size_t)(bz * 10 + w) * 4;
@@ -3074,9 +2588,6 @@ __global__ __launch_bounds__(512, 4) void gram_kernel(GramArgs a) {
     const long long tw0 = wall_clock64();     // debug build (tools/gram_trace.py): start and end of the tiles of the first 16 units
 #endif
     if (ti == tj) gram_body<MODE, true>(a, bz, ti, tj, tile, kpart, ksplit, As, Bs, dls, red, tail_id, &tail_slot);
-#if GRAM_GLDS_OFFDIAG
-    else if (a.Mp % 128 == 0) gram_body<MODE, false, true>(a, bz, ti, tj, tile, kpart, ksplit, As, Bs, dls, red, tail_id, &tail_slot);
-#endif
     else gram_body<MODE, false>(a, bz, ti, tj, tile, kpart, ksplit, As, Bs, dls, red, tail_id, &tail_slot);
 #ifdef FFVD_DF_TRACE
     if (threadIdx.x == 0 && bz < 16 && ksplit == 1 && a.ntiles <= 10 && MODE == GRAM_KFU) {
@@ -3174,7 +2685,7 @@ int gram_ntiles(int Mp) {
     return n128 * (n128 + 1) / 2;
 }
 
-static bool gram_uses_combos(int Mp, int ksplit, int with_row);
+static bool gram_uses_combos(int Mp, int with_row);
 static int gram_wg_per_unit(int Mp, int ksplit, int with_row);
 // Few tiles cannot fill the 512 workgroup slots (256 CUs x 2), and 1-2 tiles per slot balance badly (640 tiles take
 // 1.56 x the time of 512).  Measured at M = 512, T = 4096: 160 tiles 0.60 ms unsplit / 0.48 ms in 3 row ranges (one
@@ -3182,7 +2693,7 @@ static int gram_wg_per_unit(int Mp, int ksplit, int with_row);
 int gram_ksplit(int Mp, int nb, int rows, int with_row, bool fill_slots) {
     if (const char *e = getenv("FFVD_GSPLIT")) return atoi(e) > 0 ? atoi(e) : 1;       // tuning override
     const int nchunk = rows / GT;
-    if (fill_slots && gram_uses_combos(Mp, 1, with_row) && GRAM_COMBO == 2) {
+    if (fill_slots && gram_uses_combos(Mp, with_row)) {
         // Nothing beside the launch (the K_uu chain runs behind it): the ranges that give every slot of the chip one workgroup --
         // tools/gsplit_s1.sh: 4 chains 320 us in four ranges against 382 in three, 2 chains 157 against 202, 1 chain 150 in eight
         // Measured per-rank iterations, side chain behind the pass vs beside it in three ranges (tools/sync_step.py, same box,
@@ -3197,7 +2708,7 @@ int gram_ksplit(int Mp, int nb, int rows, int with_row, bool fill_slots) {
         if (n > 0 && n <= 64 && nchunk / 8 >= 8) return 8;
         return 0;                                                                   // (the caller keeps the first-half schedule)
     }
-    if (gram_uses_combos(Mp, 1, with_row) && GRAM_COMBO == 2) {
+    if (gram_uses_combos(Mp, with_row)) {
         // pair combos: 8 workgroups per unit at M = 512.  Measured per-rank iteration times at config 2's shape, 1 .. 24 chains and
         // 1, 2, 3, 4, 6, 8 row ranges (tools/gram_split_sweep.sh, profiles/r04_gram_split.txt): three ranges are the best or within
         // 1 % of it everywhere (few units: 0.55 ms against 0.63 in 2, 4 or 8) -- except when the unsplit launch is exactly whole
@@ -3221,19 +2732,15 @@ size_t gram_part_doubles(int Mp, int nb, int ksplit) {
     return ksplit > 1 ? (size_t)ksplit * nb * (size_t)(Mp + 1) * Mp : 0;
 }
 
-#ifndef GRAM_TAIL_SPLIT
-#define GRAM_TAIL_SPLIT 1
-#endif
-// workgroups per unit of an unsplit launch: with Mp a multiple of 512 the diagonal tiles of every four panels become three combos
-// (and only when the kernel has no delta^T A row to form: the combos have no idle wavefront for it)
-static bool gram_uses_combos(int Mp, int ksplit, int with_row) {
-    if (GRAM_COMBO == 2) return Mp % 256 == 0 && !with_row;          // pair combos: also the diagonal workgroups of a split-K launch
-    return GRAM_COMBO && ksplit <= 1 && Mp % 512 == 0 && !with_row;
+// workgroups per unit of a launch: with Mp a multiple of 256 the diagonal tiles of every two panels become one pair combo, also in
+// a split-K launch (and only when the kernel has no delta^T A row to form: the combos have no idle wavefront for it)
+static bool gram_uses_combos(int Mp, int with_row) {
+    return Mp % 256 == 0 && !with_row;
 }
 static int gram_wg_per_unit(int Mp, int ksplit, int with_row) {
     const int n128 = (Mp / NB + 1) / 2;
-    if (gram_uses_combos(Mp, ksplit, with_row))
-        return (n128 * (n128 - 1) / 2 + (GRAM_COMBO == 2 ? n128 / 2 : 3 * (n128 / 4))) * (ksplit > 1 ? ksplit : 1);
+    if (gram_uses_combos(Mp, with_row))
+        return (n128 * (n128 - 1) / 2 + n128 / 2) * (ksplit > 1 ? ksplit : 1);
     return gram_ntiles(Mp) * (ksplit > 1 ? ksplit : 1);
 }
 // Which workgroups of an unsplit launch are cut in two row halves: those of the last, partial round, when their halves still fit
@@ -3243,7 +2750,7 @@ static int gram_wg_per_unit(int Mp, int ksplit, int with_row) {
 // and a 2-way split of a whole half round (256 tiles -> 512 halves) ended LATER than no split because the last halves start
 // when the last slot frees up; with combos the remainder is 128 workgroups -> 256 halves -> the 256 slots that free up first.
 int gram_tail_wg(int Mp, int nb, int ksplit, int with_row) {
-    if (!GRAM_TAIL_SPLIT || ksplit > 1) return 0;
+    if (ksplit > 1) return 0;
     static const int slots = [] {
         int dev = 0, cus = 256;
         hipDeviceProp_t p;
@@ -3266,7 +2773,7 @@ void launch_gram(hipStream_t stream, GramArgs a, int phase) {
     if (a.brow <= 0) a.brow = a.Mp;
     if (!a.part || a.ksplit < 1) a.ksplit = 1;
     const int groups = (a.nb + 7) / 8;
-    a.combo = gram_uses_combos(a.Mp, a.ksplit, a.with_row) ? 1 : 0;
+    a.combo = gram_uses_combos(a.Mp, a.with_row) ? 1 : 0;
     a.wg_per_unit = gram_wg_per_unit(a.Mp, a.ksplit, a.with_row);
     if (a.ksplit > 1 || !a.tail_part || a.tail_wg != gram_tail_wg(a.Mp, a.nb, a.ksplit, a.with_row)) a.tail_wg = 0;
     if (a.tail_wg > 0) a.tail_cnt = reinterpret_cast<int *>(a.tail_part + (size_t)a.tail_wg * 2 * GRAM_TAIL_DOUBLES);

@@ -209,9 +209,6 @@ struct SkinnyArgs {
     int upper2;                                     // B2[k][n] = 0 for k > n as well (W q_sqrt with an upper-triangular q_sqrt: the reference's L_H^-T)
 };
 
-#ifndef FFVD_SKINNY_CHUNK
-#define FFVD_SKINNY_CHUNK 1       // k blocks whose operands are in flight together: 2 and 4 measured no faster (profiles/r05_step_trace.txt)
-#endif
 __device__ __forceinline__ void skinny_body(const SkinnyArgs &a, const int bx, const int by, const int bzz) {
     __shared__ double red[4][2][4][64];
     const int wg_lin = blockIdx.x + (int)gridDim.x * (blockIdx.y + (int)gridDim.y * blockIdx.z);
@@ -235,25 +232,17 @@ __device__ __forceinline__ void skinny_body(const SkinnyArgs &a, const int bx, c
     if (a.a_trans) {
         const double *atp = Ab + (size_t)(4 * lk) * a.lda + r0 + lr;        // AT[k][row]: 16 lanes = 128 contiguous bytes
         const size_t la = (size_t)a.lda;
-        constexpr int CH = FFVD_SKINNY_CHUNK;
-        // operands of up to CH k blocks in flight (the loads are one line per 16 lanes now: the loop is bound by their latency)
-        for (int kb = kb0; kb < kb1; kb += CH) {
-            double av[CH][8], bv[CH][4];
+        // one k block's operands in flight (the loads are one line per 16 lanes: the loop is bound by their latency; 2 and 4 blocks in
+        // flight together measured no faster, profiles/r05_step_trace.txt)
+        for (int kb = kb0; kb < kb1; ++kb) {
+            double av[8], bv[4];
+            const double *aq = atp + (size_t)(16 * kb) * la, *bq = bp + (size_t)(16 * kb) * ldb;
 #pragma unroll
-            for (int j = 0; j < CH; ++j)
-                if (kb + j < kb1) {
-                    const double *aq = atp + (size_t)(16 * (kb + j)) * la, *bq = bp + (size_t)(16 * (kb + j)) * ldb;
+            for (int e = 0; e < 4; ++e) { av[e] = aq[e * la]; av[4 + e] = aq[e * la + 16]; bv[e] = bq[e * (size_t)ldb]; }
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) { av[j][e] = aq[e * la]; av[j][4 + e] = aq[e * la + 16]; bv[j][e] = bq[e * (size_t)ldb]; }
-                }
-#pragma unroll
-            for (int j = 0; j < CH; ++j)
-                if (kb + j < kb1) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        acc[0] = mfma_f64(av[j][e], bv[j][e], acc[0]); acc[1] = mfma_f64(av[j][4 + e], bv[j][e], acc[1]);
-                    }
-                }
+            for (int e = 0; e < 4; ++e) {
+                acc[0] = mfma_f64(av[e], bv[e], acc[0]); acc[1] = mfma_f64(av[4 + e], bv[e], acc[1]);
+            }
         }
     } else {
     const double *ap0 = Ab + (size_t)(r0 + lr) * a.lda + 4 * lk, *ap1 = ap0 + (size_t)16 * a.lda;

@@ -141,78 +141,26 @@ __device__ __forceinline__ void tiny_sum(double (&v)[N], double *red) {
 }
 
 // ---- blocked Cholesky of an n x n matrix in LDS (n = 16 NT), with L^-T -----------------------------------------------------
-// 16-pivot chain on the tile in Sc (lower triangle valid): lanes 0-15 carry its rows, lanes 16-31 the rows of the identity through
-// the same column operations -- they come out as L_ss^-T (kernels.hip, chol64_mfma_1w).  Writes L_ss (zeros above the diagonal)
-// into the diagonal tile of Am and L_ss^-T into Dv.  Returns 0 or 1 + the first non-positive pivot of the tile.
-// (tools/probes/lat_probe.hip: the bare right-looking chain is 1.06 us; as first written -- the identity rows chosen by a select
-//  per element, i.e. an exec-masked load each; the first bad pivot tracked by a scalar compare per pivot; two exec-masked store
-//  streams -- 1.92 us.  This form: 1.54 us.  Lanes 16-31 read an identity tile that sits in LDS behind Sc; a non-positive or NaN
-//  pivot leaves NaN on the diagonal of L from there on, which is looked for once, behind the chain; one store stream.)
-__device__ __forceinline__ int tiny_chain16(const double (*Sc)[17], double *Am, const int LD, const int s0, double (*Dv)[17], const int lane) {
-    const int lr = lane & 15;
-    double a[16];
-    const double *src = &Sc[(lane < 16) ? lr : 16 + lr][0];             // rows 16-31 of Sc's block: the identity tile
-#pragma unroll
-    for (int c = 0; c < 16; ++c) a[c] = src[c];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-        const double ajj = readlane_f64(a[j], j);
-        double piv, y;
-        pivot_sqrt(ajj, piv, y);
-        a[j] *= y;
-#pragma unroll
-        for (int c = j + 1; c < 16; ++c) a[c] = fma(-a[j], readlane_f64(a[j], c), a[c]);
-    }
-    double diag = a[0];
-#pragma unroll
-    for (int c = 1; c < 16; ++c) diag = (lr == c) ? a[c] : diag;
-    if (lane < 32) {
-        double *base = (lane < 16) ? Am + (size_t)(s0 + lr) * LD + s0 : &Dv[lr][0];
-#pragma unroll
-        for (int c = 0; c < 16; ++c) base[c] = (lane >= 16 || c <= lr) ? a[c] : 0.0;
-    }
-    const unsigned long long m = __ballot((lane < 16) & !(diag > 0.0));
-    return m ? (int)__builtin_ctzll(m) + 1 : 0;
-}
-
-// S = A(s,s) - sum_{kbeg<=k<s} L(s,k) L(s,k)^T into Sc (one wavefront)
-__device__ __forceinline__ void tiny_diag_gather(const double *Am, const int LD, const int s, const int kbeg, double (*Sc)[17], const int lane) {
-    const int lr = lane & 15, lk = lane >> 4, s0 = 16 * s;
-    d4 a0 = (d4){0.0, 0.0, 0.0, 0.0}, a1 = a0;
-    for (int k = kbeg; k < s; ++k) {
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const double v = Am[(size_t)(s0 + lr) * LD + 16 * k + 4 * t + lk];
-            if (t & 1) a1 = mfma_f64(v, v, a1);
-            else a0 = mfma_f64(v, v, a0);
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) Sc[lk + 4 * r][lr] = Am[(size_t)(s0 + lk + 4 * r) * LD + s0 + lr] - (a0[r] + a1[r]);
-}
-
-// One 16 x 16 tile of block column s (one wavefront): X = (T - sum_{k0<=k<s} Xrow(k) L(s,k)^T) L_ss^-T, in place.
-//   main row block rb > s:  T = A(rb,s), k from 0;      extension row block e = rb < s (identity-structured: it becomes
-//   W(e,s) = (L^-T)(e,s)):  T = 0, k from e, and the k = e term reads W(e,e) = Dinv[e].
+// One 16 x 16 tile of block column s of the identity-structured extension row block e < s (one wavefront), in place: it becomes
+//   W(e,s) = (L^-T)(e,s) = -(sum_{e<=k<s} W(e,k) L(s,k)^T) L_ss^-T,   where the k = e term reads W(e,e) = Dinv[e].
 // The products run transposed in the accumulator layout, which is the B-operand layout of the next product (potrf_panel_kernel);
 // one residual refinement step against L_ss restores substitution accuracy.
-__device__ __forceinline__ void tiny_tile_solve(double *Am, const int LD, double (*Dinv)[16][17], const int s, const int rb, const bool ext,
-                                                const int lane, const int kmain = 0 /* main rows: first term still to subtract */) {
-    const int lr = lane & 15, lk = lane >> 4, s0 = 16 * s, r0 = 16 * rb;
+__device__ __forceinline__ void tiny_tile_solve(double *Am, const int LD, double (*Dinv)[16][17], const int s, const int e, const int lane) {
+    const int lr = lane & 15, lk = lane >> 4, s0 = 16 * s, r0 = 16 * e;
     d4 a0 = (d4){0.0, 0.0, 0.0, 0.0}, a1 = a0;
-    for (int k = ext ? rb : kmain; k < s; ++k) {
-        const bool dk = ext && k == rb;
+    for (int k = e; k < s; ++k) {
+        const bool dk = k == e;
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             const double av = Am[(size_t)(s0 + lr) * LD + 16 * k + 4 * t + lk];
-            const double bv = dk ? Dinv[rb][lr][4 * t + lk] : Am[(size_t)(r0 + lr) * LD + 16 * k + 4 * t + lk];
+            const double bv = dk ? Dinv[e][lr][4 * t + lk] : Am[(size_t)(r0 + lr) * LD + 16 * k + 4 * t + lk];
             if (t & 1) a1 = mfma_f64(av, bv, a1);
             else a0 = mfma_f64(av, bv, a0);
         }
     }
     d4 Rt;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) Rt[r] = (ext ? 0.0 : Am[(size_t)(r0 + lr) * LD + s0 + lk + 4 * r]) - (a0[r] + a1[r]);
+    for (int r = 0; r < 4; ++r) Rt[r] = 0.0 - (a0[r] + a1[r]);
     d4 x = (d4){0.0, 0.0, 0.0, 0.0};
 #pragma unroll
     for (int t = 0; t < 4; ++t) x = mfma_f64(Dinv[s][lk + 4 * t][lr], Rt[t], x);
@@ -225,33 +173,6 @@ __device__ __forceinline__ void tiny_tile_solve(double *Am, const int LD, double
     for (int r = 0; r < 4; ++r) Am[(size_t)(r0 + lr) * LD + s0 + lk + 4 * r] = x[r];
 }
 
-// Row block r is factorised by wavefront 0 in column step r - 1.  One step earlier (column r - 2) every term k <= r - 3 of its two
-// tiles on the critical path is final: a helper subtracts them in place then,
-//   A(r, r-1) -= sum_{k<kend} L(r,k) L(r-1,k)^T,   A(r, r) -= sum_{k<kend} L(r,k) L(r,k)^T,   kend = r - 2,
-// and wavefront 0 is left with one term for the tile and two for the diagonal block whatever the column (the gathers were 40 % of
-// its step at column 5: tools/tiny_trace.py).
-__device__ __forceinline__ void tiny_pregather(double *Am, const int LD, const int r, const int kend, const int lane) {
-    const int lr = lane & 15, lk = lane >> 4, r0 = 16 * r, q0 = 16 * (r - 1);
-    d4 g0 = (d4){0.0, 0.0, 0.0, 0.0}, g1 = g0, h0 = g0, h1 = g0;
-    for (int k = 0; k < kend; ++k) {
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const double lq = Am[(size_t)(q0 + lr) * LD + 16 * k + 4 * t + lk], lrw = Am[(size_t)(r0 + lr) * LD + 16 * k + 4 * t + lk];
-            if (t & 1) { g1 = mfma_f64(lq, lrw, g1); h1 = mfma_f64(lrw, lrw, h1); }
-            else { g0 = mfma_f64(lq, lrw, g0); h0 = mfma_f64(lrw, lrw, h0); }
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        Am[(size_t)(r0 + lr) * LD + q0 + lk + 4 * q] -= g0[q] + g1[q];        // (transposed in the accumulator layout, as in tiny_tile_solve)
-        Am[(size_t)(r0 + lk + 4 * q) * LD + r0 + lr] -= h0[q] + h1[q];
-    }
-}
-
-#ifndef TINY_CHOL_ROWS
-#define TINY_CHOL_ROWS 1      // 0: the round-4 first form below (tile solves on the matrix cores behind every chain; A/B build `tinytiles`)
-#endif
-#if TINY_CHOL_ROWS
 // One older term range of a tile of a LATER column, in place (one wavefront):  A(i, c) -= sum_{k<kend} L(i,k) L(c,k)^T
 __device__ __forceinline__ void tiny_tile_sub(double *Am, const int LD, const int i, const int c, const int kbeg, const int kend, const int lane) {
     const int lr = lane & 15, lk = lane >> 4, i0 = 16 * i, c0 = 16 * c;
@@ -279,6 +200,10 @@ __device__ __forceinline__ void tiny_tile_sub(double *Am, const int LD, const in
 //       W(e, s-1), e < s-1, of the inverse (they need W(s-1,s-1), which chain s-1 left) as before on the matrix cores; barrier
 // so that the latency chain of a column is one 4-MFMA product, two barriers and the pivot chain -- the first form had a tile solve
 // (three dependent groups of four MFMAs), the sums of the next diagonal tile and two LDS round trips there: 3.15 -> 2.2 us per column.
+// The chain itself (tools/probes/lat_probe.hip: the bare right-looking chain is 1.06 us; with the identity rows chosen by a select per
+// element, i.e. an exec-masked load each, and the first bad pivot tracked by a scalar compare per pivot, 1.92 us; this form 1.54 us):
+// per-lane base pointers, the identity rows read from a tile that sits in LDS behind Sc; a non-positive or NaN pivot leaves NaN on
+// the diagonal of L from there on, which is looked for once, behind the chain.
 template <int NW>
 __device__ __forceinline__ void tiny_chol_inv(double *Am, const int LD, const int NT, double (*Dinv)[16][17], double (*Sc)[17],
                                               int32_t *info_word) {
@@ -344,68 +269,17 @@ __device__ __forceinline__ void tiny_chol_inv(double *Am, const int LD, const in
                 for (int i = s + 1; i < NT; ++i, ++idx)
                     if (idx % nid == me) tiny_tile_sub(Am, LD, i, s + 1, 0, s, lane);
             for (int e = 0; e + 1 < s; ++e, ++idx)
-                if (idx % nid == me) tiny_tile_solve(Am, LD, Dinv, s - 1, e, true, lane);
+                if (idx % nid == me) tiny_tile_solve(Am, LD, Dinv, s - 1, e, lane);
         }
         __syncthreads();
         TSTAMP(18 + (s < 8 ? s : 7));
     }
     {   // the inverse's tiles of the last column
-        for (int e = wave; e + 1 < NT; e += NW) tiny_tile_solve(Am, LD, Dinv, NT - 1, e, true, lane);
+        for (int e = wave; e + 1 < NT; e += NW) tiny_tile_solve(Am, LD, Dinv, NT - 1, e, lane);
         __syncthreads();
     }
     if (wave == 0 && lane == 0 && bad && *info_word == 0) *info_word = bad;
 }
-#else
-// In: lower triangle of Am.  Out: lower triangle = L (diagonal tiles with zeros above the diagonal), tiles above the diagonal =
-// W = L^-T, Dinv[s] = W(s,s).  Left-looking by tile column; wavefront 0 owns the critical path (tile (s+1,s), then the gather and
-// the 16-pivot chain of diagonal tile s+1), the others solve the remaining tiles of column s beside it; one barrier per column.
-template <int NW>
-__device__ __forceinline__ void tiny_chol_inv(double *Am, const int LD, const int NT, double (*Dinv)[16][17], double (*Sc)[17],
-                                              int32_t *info_word) {
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int bad = 0;
-    if (wave == 0) {
-        tiny_diag_gather(Am, LD, 0, 0, Sc, lane);
-        wave_lds_order();
-        bad = tiny_chain16(Sc, Am, LD, 0, Dinv[0], lane);
-    }
-    __syncthreads();
-    for (int s = 0; s < NT; ++s) {
-        if (wave == 0) {
-            if (s + 1 < NT) {
-                const int kb = s >= 1 ? s - 1 : 0;                            // terms k < s - 1 of row s + 1 were subtracted in step s - 1
-                __builtin_amdgcn_s_setprio(3);
-                tiny_tile_solve(Am, LD, Dinv, s, s + 1, false, lane, kb);
-                wave_lds_order();
-                TSTAMP(27);
-                tiny_diag_gather(Am, LD, s + 1, kb, Sc, lane);
-                wave_lds_order();
-                TSTAMP(28);
-                const int b2 = tiny_chain16(Sc, Am, LD, 16 * (s + 1), Dinv[s + 1], lane);
-                TSTAMP(29);
-                if (b2 && !bad) bad = 16 * (s + 1) + b2;
-                __builtin_amdgcn_s_setprio(0);
-            }
-        } else {
-            int idx = 0;
-            if (s >= 1 && s + 2 < NT) {                                       // row s + 2: its terms k <= s - 1, one step ahead of wavefront 0
-                if (idx % (NW - 1) == wave - 1) tiny_pregather(Am, LD, s + 2, s, lane);
-                ++idx;
-            }
-            // (the helper that pre-gathered row s + 2 must not ALSO solve tile (s + 2, s) before it: that tile's gather reads what the
-            //  pre-gather leaves alone -- columns < s of row s + 2 -- and writes column s; the pre-gather writes columns s + 1, s + 2)
-            for (int i = s + 2; i < NT; ++i, ++idx)
-                if (idx % (NW - 1) == wave - 1) tiny_tile_solve(Am, LD, Dinv, s, i, false, lane);
-            for (int e = 0; e < s; ++e, ++idx)
-                if (idx % (NW - 1) == wave - 1) tiny_tile_solve(Am, LD, Dinv, s, e, true, lane);
-        }
-        __syncthreads();
-        TSTAMP(18 + (s < 8 ? s : 7));
-    }
-    if (wave == 0 && lane == 0 && bad && *info_word == 0) *info_word = bad;
-}
-#endif
 
 // element (i, j) of W = L^-T as tiny_chol_inv leaves it (i <= j by tiles; zero below the block diagonal)
 __device__ __forceinline__ double tiny_w_elem(const double *Am, const int LD, double (*Dinv)[16][17], const int i, const int j) {
@@ -843,10 +717,6 @@ __device__ __forceinline__ void tiny_kuu_split(const int NT, const int nst, int 
     hn = NT - nst;
     if (hn > 3) hn = 3;
     if (hn < 0 || NT < 3) hn = 0;               // (the head's matrix area must hold the three 16-row patches: Mp >= 48)
-#ifdef FFVD_TINY_NO_HEAD_HELP
-    hn = 0;
-#endif
-
     h0 = nst;
 }
 
@@ -941,7 +811,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void tiny_kernel(const Ti
         tab[tau] = ti | (tj << 8);
     }
     if (tid < 8) ilen[tid] = (tid < P) ? exp(a.loglen[(size_t)dg * P + tid]) : 1.0;      // :161
-    if (head)                                                                          // the identity rows of the pivot chains (tiny_chain16)
+    if (head)                                                                          // the identity rows of the pivot chains (tiny_chol_inv)
         for (int e = tid; e < 16 * 17; e += NTHR) lds[L.sc + 16 * 17 + e] = ((e / 17) == (e % 17)) ? 1.0 : 0.0;
 
     if (head) {

@@ -27,7 +27,7 @@ nunits = S * D
 nst = (T + 63) // 64 if int(e.lib.ffvd_single_launch(e._h)) == 4 else (T + 127) // 128
 NT = (M + 15) // 16
 nwg = nunits * (1 + nst + (NT if grad else 0))
-if not os.environ.get("FFVD_TINY_NO_XCD") and 8 * (1 + nst + (NT if grad else 0)) * ((nunits + 7) // 8) <= 256:        # undo the kernel's xcd_map: physical workgroup id -> role-major id
+if 8 * (1 + nst + (NT if grad else 0)) * ((nunits + 7) // 8) <= 256:        # undo the kernel's xcd_map: physical workgroup id -> role-major id
     wpu = 1 + nst + (NT if grad else 0)
     phys = a.copy(); a = np.zeros_like(phys)
     for b in range(8 * wpu * ((nunits + 7) // 8)):
