@@ -7,6 +7,7 @@
 #include "optim.h"
 #include "tiny.h"
 #include "step_bodies.h"
+#include "rollout_group.h"
 
 #include <algorithm>
 #include <chrono>
@@ -3231,6 +3232,93 @@ extern "C" int ffvd_op_rollout(int kind, const double *Lm_inverse_seq, const dou
     HIP_TRY(hipMemcpyAsync(predict_x, dpx, (size_t)R * steps * D * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
     HIP_TRY(hipMemcpyAsync(predict_var, dpv, (size_t)R * steps * D * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
     HIP_TRY(hipStreamSynchronize(sc.stream));
+    return FFVD_OK;
+}
+
+// G posteriors, one launch per step for all of them (rollout_group.hip)
+extern "C" int ffvd_op_rollout_grouped(int kind, int G, const double *const *Lm_inverse_seqs, const double *Zs, int M, int P, int D,
+                                       const double *logvariances, const double *loglengthscales, const double *fs,
+                                       const double *const *q_sqrts, const double *x_lasts, int R, const double *ctrl, int C, int steps,
+                                       const double *log_Qs, const double *eps, double *predict_x, double *predict_var) {
+    const char *bad = "ffvd_op_rollout_grouped: bad argument";
+    if ((kind != FFVD_KERNEL_SE && kind != FFVD_KERNEL_LINEAR) || G < 0 || R < 1 || steps < 0 || M < 1 || M > 2048 || D < 1 || C < 0 ||
+        P != D + C || P > MAXP)
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    const int Mp = round_up(M, RG_SLAB), NS = Mp / RG_SLAB;
+    if ((long long)G * D * Mp * Mp > (1LL << 29) || (long long)G * R > (1LL << 20) || (R + RG_RC - 1) / RG_RC > 65535 ||
+        (long long)G * D * NS >= (1LL << 31))
+        return set_error(nullptr, FFVD_EINVAL, "ffvd_op_rollout_grouped: bad argument (beyond the limits of rollout_group.h)");
+    if (G == 0 || steps == 0) return FFVD_OK;
+    if (!Lm_inverse_seqs || !Zs || !logvariances || !fs || !x_lasts || !log_Qs || !eps || !predict_x || !predict_var ||
+        (C > 0 && !ctrl) || (kind == FFVD_KERNEL_SE && !loglengthscales))
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    const size_t GD = (size_t)G * D, out_n = (size_t)G * R * steps * D;
+    for (size_t b = 0; b < GD; ++b) if (!Lm_inverse_seqs[b]) return set_error(nullptr, FFVD_EINVAL, bad);
+    if (q_sqrts)
+        for (int g = 0; g < G; ++g) if (!q_sqrts[g]) return set_error(nullptr, FFVD_EINVAL, bad);
+    OP_BEGIN("ffvd_op_rollout_grouped");
+    // FFVD_RG_TIMING=1 (tools): where the call spends its wall time (the stream is synchronised at every lap, so the call is slower)
+    const bool timing = getenv("FFVD_RG_TIMING") != nullptr;
+    auto t_last = std::chrono::steady_clock::now();
+    auto lap = [&](const char *what) {
+        if (!timing) return;
+        (void)hipStreamSynchronize(sc.stream);
+        const auto now = std::chrono::steady_clock::now();
+        fprintf(stderr, "ffvd_op_rollout_grouped:   %-28s %.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
+        t_last = now;
+    };
+    // The big operands are NOT packed on the host: every M x M matrix goes from where the caller keeps it straight into its slot of the
+    // padded device stack (a pitched copy when M is not a multiple of 16; the padding is zeroed on the device).
+    auto upload_matrices = [&](const double *const *src, size_t n) -> double * {
+        double *dst = sc.alloc<double>(n * Mp * Mp);
+        if (!dst) return nullptr;
+        if (Mp != M && hipMemsetAsync(dst, 0, n * Mp * Mp * sizeof(double), sc.stream) != hipSuccess) return nullptr;
+        for (size_t b = 0; b < n; ++b) {
+            const hipError_t e = (Mp == M)
+                ? hipMemcpyAsync(dst + b * Mp * Mp, src[b], (size_t)M * M * sizeof(double), hipMemcpyHostToDevice, sc.stream)
+                : hipMemcpy2DAsync(dst + b * Mp * Mp, (size_t)Mp * sizeof(double), src[b], (size_t)M * sizeof(double),
+                                   (size_t)M * sizeof(double), M, hipMemcpyHostToDevice, sc.stream);
+            if (e != hipSuccess) return nullptr;
+        }
+        return dst;
+    };
+    double *dW = upload_matrices(Lm_inverse_seqs, GD);
+    lap("W uploaded");
+    // W q_sqrt is upper triangular when every group's q_sqrt slice is (the reference hands over L_H^-T): the step products then stop at
+    // a slab's last row for both right-hand sides.  Otherwise they walk all rows; for a group whose slice IS upper triangular the extra
+    // terms are exact zeros, so its results do not depend on what the other groups hold.
+    int q_upper = q_sqrts ? 1 : 0;
+    for (int g = 0; q_upper && g < G; ++g)
+        for (int i = 1; i < M && q_upper; ++i)
+            for (int j = 0; j < i; ++j)
+                if (q_sqrts[g][(size_t)i * M + j] != 0.0) { q_upper = 0; break; }
+    lap("q_sqrt scanned");
+    double *dq = q_sqrts ? upload_matrices(q_sqrts, (size_t)G) : nullptr;
+    double *dB = q_sqrts ? sc.alloc<double>(GD * Mp * Mp) : nullptr;
+    double *dZ = sc.upload(Zs, (size_t)G * M * P), *dU = sc.upload(fs, (size_t)G * M * D), *dxl = sc.upload(x_lasts, GD);
+    double *dlv = sc.upload(logvariances, GD), *dll = loglengthscales ? sc.upload(loglengthscales, GD * P) : nullptr;
+    double *dlq = sc.upload(log_Qs, GD), *deps = sc.upload(eps, (size_t)steps * G * R * D);
+    double *dctrl = C ? sc.upload(ctrl, (size_t)steps * C) : nullptr;
+    double *variance = sc.alloc<double>(GD), *len = sc.alloc<double>(GD * P), *Zsc = sc.alloc<double>(GD * Mp * P), *zz = sc.alloc<double>(GD * Mp);
+    double *part = sc.alloc<double>((size_t)2 * GD * NS * R * 4), *xbuf = sc.alloc<double>((size_t)2 * G * R * D);
+    double *dpx = sc.alloc<double>(out_n), *dpv = sc.alloc<double>(out_n);
+    OP_CHECK(dW && dZ && dU && dxl && dlv && dlq && deps && (!C || dctrl) && (!loglengthscales || dll) && variance && len && Zsc && zz &&
+             part && xbuf && dpx && dpv && (!q_sqrts || (dq && dB)), "ffvd_op_rollout_grouped");
+    lap("q_sqrt, small arrays uploaded");
+    launch_rg_prep(sc.stream, kind, G, D, M, Mp, P, dZ, dlv, dll, variance, len, Zsc, zz);
+    if (q_sqrts) launch_rg_wq(sc.stream, G, D, Mp, q_upper, dW, dq, dB);
+    lap("hyper-parameters, W q_sqrt");
+    RolloutGroupArgs a{};
+    a.kind = kind; a.G = G; a.R = R; a.D = D; a.C = C; a.P = P; a.M = M; a.Mp = Mp; a.NS = NS; a.steps = steps;
+    a.has_q = q_sqrts ? 1 : 0; a.q_upper = q_upper;
+    a.W = dW; a.B = dB; a.Zs = Zsc; a.zz = zz; a.variance = variance; a.len = len; a.f = dU; a.x_last = dxl; a.log_Q = dlq;
+    a.ctrl = dctrl; a.eps = deps; a.part = part; a.xbuf = xbuf; a.predict_x = dpx; a.predict_var = dpv;
+    for (int t = 0; t <= steps; ++t) launch_rg_step(sc.stream, a, t);
+    HIP_TRY(hipGetLastError());
+    lap("step launches");
+    if (!sc.download(predict_x, dpx, out_n * sizeof(double)) || !sc.download(predict_var, dpv, out_n * sizeof(double)))
+        return set_error(nullptr, FFVD_EDEVICE, "ffvd_op_rollout_grouped: copying the results back failed");
+    lap("results downloaded");
     return FFVD_OK;
 }
 

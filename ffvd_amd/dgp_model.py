@@ -7,6 +7,8 @@ reference's attribute names (layers[-1].X / .U / .Z, kernels, log_Q, likelihood.
 """
 from __future__ import annotations
 
+import copy
+
 import numpy as np
 
 from .engine import ElboEngine
@@ -34,6 +36,8 @@ class DGPSSM:
 
     Constructor arguments keep the reference's names (dgp_model.py:160-166).  `num_chains` > 1 evaluates
     S latent trajectories X_s in one call (`set_X`), which is what BASELINE.json's metric measures."""
+
+    ROLLOUT_MODES = ("reference", "intent", "intent-batched")      # collect_samples_formal(rollout_mode=...)
 
     def __init__(self, Y, x_dims, n_inducing, kernels, likelihood, minibatch_size=None, window_size=64,
                  output_dim=None, prior_type="uniform", full_cov=False, epsilon=0.01, mdecay=0.05, QQ_chol=None,
@@ -303,16 +307,18 @@ class DGPSSM:
                          session.run at :326-327, after the last sample_op, so every rollout sees the final variable
                          values; the `num` rollouts differ by their noise only;
           "intent"    -- rollout num_i uses the variables as they are after its own sample_ops (K_uu factors and
-                         posterior U recomputed per sample), which is what the loop sets out to do.
+                         posterior U recomputed per sample), which is what the loop sets out to do;
+          "intent-batched" -- the same sampler sequence and the same per-sample posteriors as "intent", with the `num` rollouts
+                         deferred into ONE `rollout_grouped` call (G = num posteriors, R = 1) after the last sample_op.
         `eps` (test_len, num, D) injects the standard-normal draws of :306 (else numpy's default_rng(seed)); the
         SG-HMC noise comes from the model's generator (`seed()`).  Returns a dict and sets the reference's attributes
         (fit_x, predict_y, predict_y_var, fit_y, RMSE_val)."""
         from . import conditionals_multi_output as cmo
-        from .prediction import predict_y_summary, rollout
+        from .prediction import predict_y_summary, rollout, rollout_grouped
         if synthetic_data_function_plot:
             raise NotImplementedError("synthetic_data_function_plot: plotting aid of the kink toy problem, not on the GP-SSM path")
-        if rollout_mode not in ("reference", "intent"):
-            raise ValueError("rollout_mode must be 'reference' or 'intent'")
+        if rollout_mode not in self.ROLLOUT_MODES:
+            raise ValueError("rollout_mode must be 'reference', 'intent' or 'intent-batched'")
         if sghmc_var_len and sghmc_var_len != len(self.vars):
             raise ValueError(f"sghmc_var_len = {sghmc_var_len} but the model samples {len(self.vars)} variables")
         if self._host_stale:
@@ -339,6 +345,7 @@ class DGPSSM:
 
         mc = [[] for _ in self.vars]
         px_parts, pv_parts = [], []
+        groups = []                                                                             # "intent-batched": one posterior per sample
         if sghmc_var_len:
             for num_i in range(num):
                 for _ in range(spacing):                                                        # :225-231
@@ -354,7 +361,18 @@ class DGPSSM:
                                      eps[:, num_i:num_i + 1])
                     px_parts.append(px)
                     pv_parts.append(pv)
-        if px_parts:
+                elif rollout_mode == "intent-batched":
+                    Lm, U_val, U_chol = posterior()
+                    lay = self.layers[-1]
+                    groups.append((Lm, np.array(lay.Z, copy=True), copy.deepcopy(lay.kernel), U_val, U_chol,
+                                   np.array(lay.X[-1], copy=True), np.array(self.Q, copy=True)))
+        if groups:
+            cols = list(zip(*groups))
+            px, pv = rollout_grouped(cols[0], cols[1], cols[2], cols[3], cols[4] if U_collapse else None, cols[5], ci, n_train,
+                                     test_len, cols[6], eps[:, :, None, :])
+            px, pv = px[:, 0], pv[:, 0]
+            U_val = U_val if U_collapse else self.layers[-1].U
+        elif px_parts:
             px, pv = np.concatenate(px_parts, axis=0), np.concatenate(pv_parts, axis=0)
             U_val = U_val if U_collapse else self.layers[-1].U
         else:
@@ -376,4 +394,44 @@ class DGPSSM:
             out["results_file"] = save_results(save_path_file, self, Y_test, Y_train, Y_train_std, case=case, ll_seq=ll_seq,
                                                running_time_seq=running_time_seq, PG_num=PG_num,
                                                mc_posterior_samples=out["mc_posterior_samples"])
+        return out
+
+    def collect_samples_chains(self, num_per_chain, control_inputs, test_len, *, Y_test=None, Y_train_std=1.0, Y_train=None,
+                               eps=None, seed=None):
+        """Rollouts from EVERY chain of a `num_chains = S` model (collect_samples_formal predicts from chain 0 only): the K_uu
+        factors once, the collapsed posterior U | X_s per chain (with explicit U: the shared U, no q_sqrt), `num_per_chain`
+        rollouts of `test_len` steps from each chain's own X_s[-1] -- one `rollout_grouped` call with G = S, R = num_per_chain.
+        `eps` (test_len, S, num_per_chain, D) injects the draws of base_model.py:306 (else numpy's default_rng(seed)).
+        Returns a dict: predict_x, predict_x_var (S, num_per_chain, test_len, D) and the predict_y_summary over all S * R rollouts."""
+        from . import conditionals_multi_output as cmo
+        from .prediction import predict_y_summary, rollout_grouped
+        if self._host_stale:
+            self.pull_parameters()
+        S, D, T, R = self.num_chains, self.output_dim, self.X_N - 1, int(num_per_chain)
+        if R < 1:
+            raise ValueError("num_per_chain must be at least 1")
+        ci = self.control_inputs if control_inputs is None else np.asarray(control_inputs, dtype=np.float64)
+        if eps is None:
+            eps = np.random.default_rng(seed).standard_normal((test_len, S, R, D))
+        eps = np.asarray(eps, dtype=np.float64)
+        if eps.shape != (test_len, S, R, D):
+            raise ValueError(f"eps: expected {(test_len, S, R, D)}, got {eps.shape}")
+        n_train = self.Y.shape[0] if Y_train is None else np.asarray(Y_train).shape[0]
+        lay = self.layers[-1]
+        Lm = cmo.kernel_pre_cal(lay.Z, lay.kernel)
+        U_vals, U_chols = [], []
+        for s_ in range(S):
+            Xs = self._X_chains[s_]
+            if self.U_collapse:
+                xc = np.concatenate((Xs[:T], ci[:T]), axis=1) if ci.shape[1] > 0 else Xs[:-1]
+                U_val, U_chol = cmo.collapse_u_mean_after_kernel_precalculation(Lm, xc, Xs, lay.Z, lay.kernel, self.Q)
+            else:
+                U_val, U_chol = lay.U, None
+            U_vals.append(U_val)
+            U_chols.append(U_chol)
+        px, pv = rollout_grouped([Lm] * S, [lay.Z] * S, [lay.kernel] * S, U_vals, U_chols if self.U_collapse else None,
+                                 [self._X_chains[s_][-1] for s_ in range(S)], ci, n_train, test_len, [self.Q] * S, eps)
+        out = predict_y_summary(px.reshape(S * R, test_len, D), pv.reshape(S * R, test_len, D), self.likelihood.CC,
+                                self.likelihood.DD, self.likelihood.log_Rchols, Y_test, Y_train_std)
+        out.update(predict_x=px, predict_x_var=pv, U_vals=U_vals)
         return out

@@ -55,6 +55,79 @@ def rollout(Lm_inverse_seq, Z, kern, U_val, q_sqrt, x_last, control_inputs, ctrl
     return px, pv
 
 
+def rollout_grouped(Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x_lasts, control_inputs, ctrl_offset, steps, Qs, eps):
+    """G independent posteriors rolled forward by one call (`ffvd_op_rollout_grouped`): one launch per step for all groups.
+
+    Every argument but control_inputs / ctrl_offset / steps / eps is a length-G sequence of the matching argument of `rollout`
+    (one posterior per SG-HMC sample, or per chain); q_sqrts: None or G stacks (D, M, M), slice 0 of each is used (SURVEY a14);
+    eps: (steps, G, R, D).  Kernel kind, M, P and D are common to the groups.  Returns predict_x, predict_x_var (G, R, steps, D);
+    group g's slab is bit-identical to what a G = 1 call on that group alone returns."""
+    G = len(kerns)
+    if G < 1:
+        raise ValueError("rollout_grouped: at least one group is needed")
+    for name, seq in (("Lm_inverse_seqs", Lm_inverse_seqs), ("Zs", Zs), ("U_vals", U_vals), ("x_lasts", x_lasts), ("Qs", Qs)):
+        if len(seq) != G:
+            raise ValueError(f"{name}: expected {G} groups, got {len(seq)}")
+    if q_sqrts is not None and len(q_sqrts) != G:
+        raise ValueError(f"q_sqrts: expected None or {G} groups, got {len(q_sqrts)}")
+    hy = [stack_hypers(k) for k in kerns]
+    kind, D = hy[0][0], len(kerns[0])
+    Z0 = np.asarray(Zs[0])
+    if Z0.ndim != 2:
+        raise ValueError(f"Zs[0]: expected (M, P), got {Z0.shape}")
+    M, P = Z0.shape
+    for g in range(G):
+        if hy[g][0] != kind:
+            raise ValueError(f"kerns[{g}]: every group must use the same kernel type")
+        if len(kerns[g]) != D:
+            raise ValueError(f"kerns[{g}]: expected {D} kernels (one per latent dim), got {len(kerns[g])}")
+    eps = _lib.as_f64(eps)
+    if eps.ndim != 4 or eps.shape[0] != steps or eps.shape[1] != G or eps.shape[2] < 1 or eps.shape[3] != D:
+        raise ValueError(f"eps: expected ({steps}, {G}, R >= 1, {D}), got {eps.shape}")
+    R = eps.shape[2]
+    C = P - D
+    ctrl = None
+    if C > 0:
+        ci = _lib.as_f64(control_inputs)
+        if ci.ndim != 2 or ci.shape[1] != C or ci.shape[0] < ctrl_offset + steps:
+            raise ValueError(f"control_inputs: need at least {ctrl_offset + steps} rows of {C} columns")
+        ctrl = np.ascontiguousarray(ci[ctrl_offset: ctrl_offset + steps])
+    # the small arrays are packed (one upload per kind); the M x M matrices are NOT copied on the host: the library gets a table of
+    # pointers and sends every matrix from where it lies into its slot of the padded device stack
+    Z = np.empty((G, M, P))
+    Wm, qm = [], []                                  # (keeps the matrices alive until the call returns)
+    f = np.empty((G, M, D))
+    xl, log_Q, logvar = np.empty((G, D)), np.empty((G, D)), np.empty((G, D))
+    loglen = None if hy[0][3] is None else np.empty((G, D, P))
+    for g in range(G):
+        Z[g] = _lib.as_f64(Zs[g], (M, P), f"Zs[{g}]")
+        if len(Lm_inverse_seqs[g]) != D:
+            raise ValueError(f"Lm_inverse_seqs[{g}]: expected {D} matrices, got {len(Lm_inverse_seqs[g])}")
+        for d in range(D):
+            Wm.append(_lib.as_f64(Lm_inverse_seqs[g][d], (M, M), f"Lm_inverse_seqs[{g}][{d}]"))
+        f[g] = _lib.as_f64(U_vals[g], (M, D), f"U_vals[{g}]")
+        xl[g] = _lib.as_f64(x_lasts[g], (D,), f"x_lasts[{g}]")
+        log_Q[g] = np.log(_lib.as_f64(Qs[g], (D,), f"Qs[{g}]"))
+        logvar[g] = _lib.as_f64(hy[g][2], (D,), f"kerns[{g}] logvariance")
+        if loglen is not None:
+            loglen[g] = _lib.as_f64(hy[g][3], (D, P), f"kerns[{g}] loglengthscales")
+        if q_sqrts is not None:
+            q = np.asarray(q_sqrts[g], dtype=np.float64)
+            if q.ndim != 3 or q.shape[1:] != (M, M) or q.shape[0] < 1:
+                raise ValueError(f"Bad dimension for q_sqrts[{g}]: expected (D, M, M)")
+            qm.append(np.ascontiguousarray(q[0]))
+    import ctypes
+    Wt = (ctypes.c_void_p * len(Wm))(*[w.ctypes.data for w in Wm])
+    qt = (ctypes.c_void_p * len(qm))(*[q.ctypes.data for q in qm]) if q_sqrts is not None else None
+    px, pv = np.empty((G, R, steps, D)), np.empty((G, R, steps, D))
+    rc = _lib.load().ffvd_op_rollout_grouped(kind, G, Wt, _lib.dptr(Z), M, P, D, _lib.dptr(logvar),
+                                             None if loglen is None else _lib.dptr(loglen), _lib.dptr(f), qt, _lib.dptr(xl), R,
+                                             None if ctrl is None else _lib.dptr(ctrl), C, steps, _lib.dptr(log_Q), _lib.dptr(eps),
+                                             _lib.dptr(px), _lib.dptr(pv))
+    _lib.check(rc, None, "ffvd_op_rollout_grouped")
+    return px, pv
+
+
 def predict_y_summary(predict_x, predict_x_var, CC, DD, log_Rchols, Y_test=None, Y_train_std=1.0):
     """base_model.py:330-348 (host-side: a (num, test_len, D) x (D, Ydim) contraction and three means)."""
     CC, DD = np.asarray(CC, dtype=np.float64), np.asarray(DD, dtype=np.float64)

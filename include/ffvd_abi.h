@@ -459,6 +459,28 @@ int  ffvd_op_rollout(int kind, const double *Lm_inverse_seq, const double *Z, in
  * in ffvd_last_error(NULL). */
 int  ffvd_op_rollout_fallbacks(void);
 
+/* The same prediction loop (base_model.py:223-314) for G INDEPENDENT posteriors in one call: one per SG-HMC sample of cases 2/3/5 (every
+ * sample num_i has its own hyper-parameters, :223-240) or one per chain.  Group g has its own Lm_inverse_seq, Z, hyper-parameters,
+ * f = U_val, q_sqrt slice, x_last and log_Q; kind, M, P, D, C, R, steps and ctrl are common.  Per step, group, rollout and dim the
+ * arithmetic is that of ffvd_op_rollout.  The big operands are handed over as POINTER TABLES, so that nothing is packed on the host:
+ * Lm_inverse_seqs: G * D pointers (entry g * D + d -> the M x M matrix of group g, dim d), q_sqrts: G pointers (entry g -> the M x M
+ * d = 0 slice of group g's stack, it inflates every dim: SURVEY a14) or NULL for all groups; each matrix goes straight into its slot of
+ * the padded device stack.  The other arrays are packed, row-major, group outermost: Zs G x M x P;
+ * logvariances G x D; loglengthscales G x D x P (NULL for LinearK); fs G x M x D; x_lasts G x D; log_Qs G x D; ctrl steps x C (NULL when C = 0);
+ * eps steps x G x R x D; outputs predict_x and predict_var = f_var + Q, each G x R x steps x D.
+ * Every Lm_inverse_seq must be upper triangular, as ffvd_op_kernel_pre_cal returns it: the step products skip its strict lower triangle
+ * without reading it (and that of W q_sqrt when every group's q_sqrt slice is upper triangular, which is checked).
+ * Determinism: a step is one launch over a fixed set of workgroups per group that depends on (M, D, R) only; nothing waits on another
+ * workgroup, no workgroup needs to be resident with another, there is no second form and no fallback.  Group g's outputs are
+ * bit-identical whether it is computed alone (G = 1) or among any other groups, from run to run, and whatever else the GPU is doing.
+ * f_var + Q <= 0 gives NaN from that step of that rollout on, as in ffvd_op_rollout; nothing faults.
+ * Limits: M <= 2048, P = D + C <= 32, G * D * Mp^2 <= 2^29 (Mp = M rounded up to 16: 4 GiB per operand stack), G * R <= 2^20,
+ * R <= 524280; FFVD_EINVAL beyond them, before any device work.  G = 0 or steps = 0: FFVD_OK, nothing is touched. */
+int  ffvd_op_rollout_grouped(int kind, int G, const double *const *Lm_inverse_seqs, const double *Zs, int M, int P, int D,
+                             const double *logvariances, const double *loglengthscales, const double *fs,
+                             const double *const *q_sqrts, const double *x_lasts, int R, const double *ctrl, int C, int steps,
+                             const double *log_Qs, const double *eps, double *predict_x, double *predict_var);
+
 /* One particle-Gibbs sweep over the latent trajectory: the INTENT of BaseModel.PG_for_X_speedup (base_model.py:78-138;
  * as written that op never updates X -- discarded TensorArray.write results (:115), an assign that is never run (:137) --
  * so there is no reference behaviour to match, see oracle/ffvd_pg_oracle.py).  n_free = PG_particles - 1 free particles
