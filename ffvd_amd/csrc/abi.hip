@@ -1,18 +1,15 @@
 // C ABI of libffvd_hip.so (see include/ffvd_abi.h): handle lifetime, resident buffers, the per-iteration
-// launch sequence of the ELBO, and operator-level entry points used by the Python mirror of the reference API.
-#include "../../include/ffvd_abi.h"
+// launch sequence of the ELBO, training steps, T-shards and RCCL.  The stateless ffvd_op_* operators are in ops.hip.
+#include "abi_internal.h"
 #include "kernels.h"
 #include "kernels_f32.h"
 #include "grad.h"
 #include "optim.h"
 #include "tiny.h"
-#include "step_bodies.h"
-#include "rollout_group.h"
 
 #include <algorithm>
 #include <chrono>
 #include <cmath>
-#include <atomic>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -22,18 +19,7 @@
 using namespace ffvd;
 
 static thread_local std::string g_last_error;
-static std::atomic<int> g_rollout_fallbacks{0};     // ffvd_op_rollout calls of this process that fell back from the resident loop to the per-step launches
-
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) {                                                               \
-            char buf_[512];                                                                   \
-            snprintf(buf_, sizeof buf_, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
-                     __FILE__, __LINE__);                                                     \
-            return set_error(h, (e_ == hipErrorOutOfMemory) ? FFVD_ENOMEM : FFVD_EDEVICE, buf_); \
-        }                                                                                     \
-    } while (0)
+std::string &ffvd::last_error() { return g_last_error; }
 
 struct ffvd_handle {
     ffvd_config cfg;
@@ -169,12 +155,8 @@ constexpr int F32C_FLUSH_TILES = 128;       // fp32 summation chains of the Gram
 constexpr int SMALL_SIDE_WGS = 512;         // tile-pass workgroups (one round of the chip) up to which an iteration counts as tiny (small_side)
 constexpr int SMALL_SIDE_ROWS = 32;         // block rows of the K_uu chain (Dl * 2 * Mp / 64) up to which that iteration's side chain is ONE dataflow launch
 
-static int set_error(ffvd_handle *h, int code, const std::string &msg) {
+int ffvd::set_error(ffvd_handle *h, int code, const std::string &msg) {
     if (h) h->err = msg;
-    g_last_error = msg;
-    return code;
-}
-static int set_error(std::nullptr_t, int code, const std::string &msg) {
     g_last_error = msg;
     return code;
 }
@@ -1358,13 +1340,7 @@ static int check_info(ffvd_handle *h) {
 // inter-workgroup waits (every launch re-zeroes what it needs; the dataflow launches of later iterations clear their own words).
 // A second failure is reported as FFVD_EDEVICE.  The first recovery leaves a note for ffvd_last_error.  Collective entry points
 // (ffvd_elbo_allreduce, ffvd_*_step_allreduce, T-shards) do NOT retry: the other ranks have already moved on.
-// The override is thread-local state: it is reset on EVERY exit path of the scope that set it (an error return between
-// set and reset left the launch-per-column variant selected for every later factorisation of the thread).
-struct CholOverrideGuard {
-    bool armed = false;
-    void force_left() { potrf_override_variant(CHOL_FORCE_LEFT); armed = true; }
-    ~CholOverrideGuard() { if (armed) potrf_override_variant(CHOL_FORCE_NONE); }
-};
+// (The override is reset by CholOverrideGuard, abi_internal.h.)
 
 // A stall is remembered.  The one-launch iteration and the dataflow Cholesky need every workgroup resident at once; a
 // co-tenant that keeps compute units busy makes EVERY call wait out its bounded spin (1 s) before the recovery runs -- FFVD_OK each
@@ -2204,1252 +2180,6 @@ extern "C" int ffvd_sghmc_apply(ffvd_handle *h, double epsilon, double mdecay, u
     if ((rc = train_fetch(h, "ffvd_sghmc_apply"))) return rc;
     if ((rc = sghmc_update(h, epsilon, mdecay, sample_mask, burn_in))) return rc;
     train_report(h, out_terms, out_nll);
-    return FFVD_OK;
-}
-
-// ---- operator-level entry points (temporaries per call; not the hot path) -------------------------------------------------------------
-// Round 5: the temporaries come from a per-thread cache instead of hipMalloc / hipFree / hipStreamCreate per call.  A rollout call made
-// ~27 allocations and as many frees around 200 steps of 15 us: 2.7 ms of host work per call (profiles/r04_next_rows.json: 27.6 us per
-// step of a 200-step call against 15.3 marginal).  A block is handed out again when its size fits (smallest block that is large enough
-// and at most 4 x the request); the cache is bounded (256 blocks / 8 GiB: beyond that everything idle is freed) and can be released
-// with ffvd_op_release_cache().  Nothing relies on fresh memory being zero (hipMalloc never promised that).
-namespace {
-struct OpCache {
-    struct Block { void *p; size_t bytes; bool busy; };
-    std::vector<Block> blocks;
-    size_t total = 0;
-    hipStream_t stream = nullptr;
-    int device = -1;
-    void *pinned = nullptr;             // page-locked staging block for large results (a device-to-host copy into fresh pageable memory
-    size_t pinned_bytes = 0;            //  pins its pages on the fly: 13 MB took up to 30 ms; through this block + memcpy: ~3)
-    void release_idle() {
-        std::vector<Block> keep;
-        for (Block &b : blocks) {
-            if (b.busy) keep.push_back(b);
-            else { hipFree(b.p); total -= b.bytes; }
-        }
-        blocks.swap(keep);
-    }
-    void release_all() {
-        release_idle();
-        if (stream && blocks.empty()) { hipStreamDestroy(stream); stream = nullptr; }
-        if (pinned) { hipHostFree(pinned); pinned = nullptr; pinned_bytes = 0; }
-    }
-    ~OpCache() { /* process exit: the runtime may already be gone; leave the memory to it */ }
-};
-thread_local OpCache g_op_cache;
-
-struct Scratch {
-    std::vector<size_t> mine;           // indices into the cache of the blocks this call holds
-    hipStream_t stream = nullptr;
-    bool begin() {
-        OpCache &c = g_op_cache;
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) return false;
-        if (c.device != dev) {           // (another device was made current on this thread: start over)
-            c.release_all();
-            c.device = dev;
-        }
-        if (!c.stream && hipStreamCreate(&c.stream) != hipSuccess) return false;
-        stream = c.stream;
-        return true;
-    }
-    ~Scratch() {
-        if (stream) hipStreamSynchronize(stream);
-        OpCache &c = g_op_cache;
-        for (size_t i : mine) c.blocks[i].busy = false;
-        if (c.blocks.size() > 256 || c.total > ((size_t)8 << 30)) c.release_idle();
-    }
-    template <class T>
-    T *alloc(size_t n) {
-        OpCache &c = g_op_cache;
-        const size_t bytes = ((n ? n : 1) * sizeof(T) + 255) / 256 * 256;
-        size_t best = (size_t)-1;
-        for (size_t i = 0; i < c.blocks.size(); ++i) {
-            const OpCache::Block &b = c.blocks[i];
-            if (!b.busy && b.bytes >= bytes && b.bytes <= 4 * bytes && (best == (size_t)-1 || b.bytes < c.blocks[best].bytes)) best = i;
-        }
-        if (best == (size_t)-1) {
-            void *p = nullptr;
-            if (hipMalloc(&p, bytes) != hipSuccess) {
-                (void)hipGetLastError();
-                c.release_idle();                                   // make room and try once more
-                mine.clear();
-                for (size_t i = 0; i < c.blocks.size(); ++i) if (c.blocks[i].busy) mine.push_back(i);      // (indices moved; every busy block is this call's: one call per thread at a time)
-                if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-            }
-            c.blocks.push_back({p, bytes, false});
-            c.total += bytes;
-            best = c.blocks.size() - 1;
-        }
-        c.blocks[best].busy = true;
-        mine.push_back(best);
-        // FFVD_OP_CACHE_POISON=1 (tests): every block handed out starts as NaN bytes -- nothing may rely on what a block held before
-        static const bool poison = [] { const char *e = getenv("FFVD_OP_CACHE_POISON"); return e && *e && strcmp(e, "0") != 0; }();
-        if (poison && stream) (void)hipMemsetAsync(c.blocks[best].p, 0xFF, c.blocks[best].bytes, stream);
-        return (T *)c.blocks[best].p;
-    }
-    // device -> host for a large result: through the thread's page-locked block when it has (or gets) one of that size, else directly.
-    // Synchronises the stream.
-    bool download(void *dst, const void *src, size_t bytes) {
-        if (void *pin = pinned_block(bytes)) {
-            if (hipMemcpyAsync(pin, src, bytes, hipMemcpyDeviceToHost, stream) != hipSuccess) return false;
-            if (hipStreamSynchronize(stream) != hipSuccess) return false;
-            memcpy(dst, pin, bytes);
-            return true;
-        }
-        return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream) == hipSuccess && hipStreamSynchronize(stream) == hipSuccess;
-    }
-    // the thread's page-locked block, grown to `bytes` (nullptr when it cannot be had or the size is outside 1 MB .. 256 MB)
-    void *pinned_block(size_t bytes) {
-        OpCache &c = g_op_cache;
-        if (bytes < ((size_t)1 << 20) || bytes > ((size_t)256 << 20)) return nullptr;
-        if (c.pinned_bytes < bytes) {
-            if (c.pinned) { hipHostFree(c.pinned); c.pinned = nullptr; c.pinned_bytes = 0; }
-            if (hipHostMalloc(&c.pinned, bytes, hipHostMallocDefault) == hipSuccess) c.pinned_bytes = bytes;
-            else { (void)hipGetLastError(); c.pinned = nullptr; }
-        }
-        return c.pinned;
-    }
-    // host -> device, asynchronous, straight from the caller's memory.  (Measured: large uploads through the page-locked block + a
-    // synchronisation made a 200-step rollout call 0.4 ms slower and changed nothing for the sweep -- the 28 ms some calls spend here in
-    // tools/bench_next.py's process are a wait of the stream behind the 0.2 ms DMA, whichever memory it reads; FFVD_PG_TIMING=1 shows it.)
-    double *upload(const double *src, size_t n) {
-        double *d = alloc<double>(n);
-        if (d && n && hipMemcpyAsync(d, src, n * sizeof(double), hipMemcpyHostToDevice, stream) != hipSuccess) return nullptr;
-        return d;
-    }
-};
-}  // namespace
-
-// Free what the calling thread's operator cache holds (device buffers of finished ffvd_op_* calls, their stream).
-extern "C" int ffvd_op_release_cache(void) {
-    g_op_cache.release_all();
-    return FFVD_OK;
-}
-
-#define OP_BEGIN(name)                                                                       \
-    ffvd_handle *h = nullptr;                                                                \
-    (void)h;                                                                                 \
-    Scratch sc;                                                                              \
-    if (!sc.begin())                                                                         \
-        return set_error(nullptr, FFVD_EDEVICE, name ": no usable HIP device / stream creation failed");
-#define OP_CHECK(ptr, name) \
-    if (!(ptr)) return set_error(nullptr, FFVD_ENOMEM, name ": device allocation or upload failed");
-
-extern "C" int ffvd_op_kernel_matrix(int kind, const double *X, int N, const double *X2, int N2, int P,
-                                     double logvariance, const double *loglengthscales, double jitter, double *out) {
-    if (!X || !out || N < 0 || P < 1 || (X2 && N2 < 0) || (kind == FFVD_KERNEL_SE && !loglengthscales) ||
-        (kind != FFVD_KERNEL_SE && kind != FFVD_KERNEL_LINEAR))
-        return set_error(nullptr, FFVD_EINVAL, "ffvd_op_kernel_matrix: bad argument");
-    OP_BEGIN("ffvd_op_kernel_matrix");
-    const int same = (X2 == nullptr);
-    if (same) N2 = N;
-    if ((size_t)N * N2 == 0) return FFVD_OK;
-    double *dX = sc.upload(X, (size_t)N * P);
-    OP_CHECK(dX, "ffvd_op_kernel_matrix");
-    double *dX2 = same ? dX : sc.upload(X2, (size_t)N2 * P);
-    OP_CHECK(dX2, "ffvd_op_kernel_matrix");
-    double *dl = sc.alloc<double>(P);
-    OP_CHECK(dl, "ffvd_op_kernel_matrix");
-    if (loglengthscales) HIP_TRY(hipMemcpyAsync(dl, loglengthscales, P * sizeof(double), hipMemcpyHostToDevice, sc.stream));
-    double *dO = sc.alloc<double>((size_t)N * N2);
-    OP_CHECK(dO, "ffvd_op_kernel_matrix");
-    launch_kernel_matrix(sc.stream, kind, dX, N, dX2, N2, P, logvariance, dl, jitter, same, dO);
-    HIP_TRY(hipMemcpyAsync(out, dO, (size_t)N * N2 * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
-    HIP_TRY(hipStreamSynchronize(sc.stream));
-    return FFVD_OK;
-}
-
-extern "C" int ffvd_op_kernel_diag(int kind, const double *X, int N, int P, double logvariance, double *out) {
-    if (!X || !out || N < 0 || P < 1) return set_error(nullptr, FFVD_EINVAL, "ffvd_op_kernel_diag: bad argument");
-    OP_BEGIN("ffvd_op_kernel_diag");
-    if (N == 0) return FFVD_OK;
-    double *dX = sc.upload(X, (size_t)N * P);
-    OP_CHECK(dX, "ffvd_op_kernel_diag");
-    double *dO = sc.alloc<double>(N);
-    OP_CHECK(dO, "ffvd_op_kernel_diag");
-    launch_kernel_diag(sc.stream, kind, dX, N, P, logvariance, dO);
-    HIP_TRY(hipMemcpyAsync(out, dO, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
-    HIP_TRY(hipStreamSynchronize(sc.stream));
-    return FFVD_OK;
-}
-
-// Batched Cholesky of `batch` np x np slabs (identity padded, np % NB == 0) at dA, which the caller uploaded from host_in (left
-// intact); hinfo[b] <- 0 or 1 + first bad pivot.  If the one-launch (dataflow) variant gave up on a bounded wait, the batch is uploaded
-// again from host_in and re-run with the launch-per-column variant, which has no inter-workgroup waits (*recovered = true).
-// Shared by ffvd_op_cholesky and ffvd_op_get_rand_full_cov.
-static int potrf_with_stall_recovery(Scratch &sc, double *dA, const double *host_in, int np, int batch, int32_t *dinfo,
-                                     double *dinv, int32_t *hinfo, bool *recovered, const char *who) {
-    ffvd_handle *h = nullptr;
-    const size_t slab = (size_t)np * np;
-    *recovered = false;
-    for (int attempt = 0;; ++attempt) {
-        {
-            CholOverrideGuard guard;            // reset on the error returns below as well
-            if (attempt == 1) {
-                HIP_TRY(hipMemcpyAsync(dA, host_in, slab * batch * sizeof(double), hipMemcpyHostToDevice, sc.stream));
-                guard.force_left();
-            }
-            HIP_TRY(hipMemsetAsync(dinfo, 0, batch * sizeof(int32_t), sc.stream));
-            launch_potrf_ext(sc.stream, dA, np, 0, 0, batch, slab, dinfo, dinv);
-        }
-        HIP_TRY(hipMemcpyAsync(hinfo, dinfo, batch * sizeof(int32_t), hipMemcpyDeviceToHost, sc.stream));
-        HIP_TRY(hipStreamSynchronize(sc.stream));
-        bool stalled = false;
-        for (int b = 0; b < batch; ++b) stalled = stalled || hinfo[b] < 0;
-        if (!stalled) { *recovered = attempt == 1; return FFVD_OK; }
-        if (attempt == 1)
-            return set_error(nullptr, FFVD_EDEVICE, std::string(who) + ": abandoned, a block row waited more than 1 s for the row above it");
-    }
-}
-
-extern "C" int ffvd_op_cholesky(const double *A, int n, int batch, double *L, int32_t *info) {
-    if (!A || !L || n < 1 || batch < 0) return set_error(nullptr, FFVD_EINVAL, "ffvd_op_cholesky: bad argument");
-    OP_BEGIN("ffvd_op_cholesky");
-    if (batch == 0) return FFVD_OK;
-    const int np = round_up(n, NB);
-    const size_t slab = (size_t)np * np;
-    std::vector<double> pad(slab * batch, 0.0);
-    for (int b = 0; b < batch; ++b) {
-        double *S = pad.data() + slab * b;
-        for (int i = 0; i < np; ++i) {
-            if (i < n) memcpy(S + (size_t)i * np, A + ((size_t)b * n + i) * n, (size_t)n * sizeof(double));
-            else S[(size_t)i * np + i] = 1.0;
-        }
-    }
-    double *dA = sc.upload(pad.data(), pad.size());
-    OP_CHECK(dA, "ffvd_op_cholesky");
-    int32_t *dinfo = sc.alloc<int32_t>(batch);
-    OP_CHECK(dinfo, "ffvd_op_cholesky");
-    double *dinv = sc.alloc<double>(potrf_scratch_doubles(np, batch));
-    OP_CHECK(dinv, "ffvd_op_cholesky");
-    std::vector<int32_t> hinfo(batch, 0);
-    bool recovered = false;
-    int rc = potrf_with_stall_recovery(sc, dA, pad.data(), np, batch, dinfo, dinv, hinfo.data(), &recovered, "ffvd_op_cholesky");
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(pad.data(), dA, pad.size() * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
-    HIP_TRY(hipStreamSynchronize(sc.stream));
-    int bad = -1;
-    for (int b = 0; b < batch; ++b) {
-        const double *S = pad.data() + slab * b;
-        for (int i = 0; i < n; ++i)
-            for (int j = 0; j < n; ++j) L[((size_t)b * n + i) * n + j] = (j <= i) ? S[(size_t)i * np + j] : 0.0;
-        if (info) info[b] = hinfo[b];
-        if (hinfo[b] != 0 && bad < 0) bad = b;
-    }
-    if (bad >= 0) {
-        char msg[160];
-        snprintf(msg, sizeof msg, "ffvd_op_cholesky: matrix %d is not positive definite (pivot %d)", bad, hinfo[bad] - 1);
-        return set_error(nullptr, FFVD_ENOTPD, msg);
-    }
-    if (recovered)
-        set_error(nullptr, FFVD_OK, "warning: ffvd_op_cholesky: the one-launch (dataflow) Cholesky gave up on a bounded wait; the batch was "
-                                    "re-run with the launch-per-column Cholesky and completed");
-    return FFVD_OK;
-}
-
-// shared by kernel_pre_cal / conditional: device-side hypers + K_uu + extended Cholesky
-struct KuuWork {
-    double *variance, *len, *Zs, *zz, *Kuu, *logvar, *loglen, *dinv;
-    int32_t *info;
-    int Mp;
-};
-static int build_kuu(Scratch &sc, int kind, const double *Z, int M, int P, int D, const double *logvariance,
-                     const double *loglengthscales, double jitter, KuuWork &w, double **dZ_out) {
-    const int Mp = round_up(M, NB);
-    w.Mp = Mp;
-    double *dZ = sc.upload(Z, (size_t)M * P);
-    w.logvar = sc.upload(logvariance, D);
-    w.loglen = sc.alloc<double>((size_t)D * P);
-    w.variance = sc.alloc<double>(D);
-    w.len = sc.alloc<double>((size_t)D * P);
-    w.Zs = sc.alloc<double>((size_t)D * Mp * P);
-    w.zz = sc.alloc<double>((size_t)D * Mp);
-    w.Kuu = sc.alloc<double>((size_t)D * 2 * Mp * Mp);
-    w.info = sc.alloc<int32_t>(D);
-    w.dinv = sc.alloc<double>(potrf_scratch_doubles(Mp, D));
-    if (!dZ || !w.logvar || !w.loglen || !w.variance || !w.len || !w.Zs || !w.zz || !w.Kuu || !w.info || !w.dinv) return FFVD_ENOMEM;
-    if (loglengthscales &&
-        hipMemcpyAsync(w.loglen, loglengthscales, (size_t)D * P * sizeof(double), hipMemcpyHostToDevice, sc.stream) != hipSuccess)
-        return FFVD_EDEVICE;
-    if (hipMemsetAsync(w.info, 0, D * sizeof(int32_t), sc.stream) != hipSuccess) return FFVD_EDEVICE;
-    launch_prep_hypers(sc.stream, kind, dZ, M, Mp, P, D, 0, w.logvar, w.loglen, w.variance, w.len, w.Zs, w.zz);
-    HyperView hv{w.variance, w.len, w.Zs, w.zz};
-    launch_kuu_build(sc.stream, kind, hv, M, Mp, P, D, jitter, w.Kuu, nullptr);
-    launch_potrf_ext(sc.stream, w.Kuu, Mp, Mp, Mp, D, (size_t)2 * Mp * Mp, w.info, w.dinv);
-    if (dZ_out) *dZ_out = dZ;
-    return FFVD_OK;
-}
-static int check_kuu_info(Scratch &sc, const KuuWork &w, int D, const char *who) {
-    std::vector<int32_t> hinfo(D, 0);
-    if (hipMemcpyAsync(hinfo.data(), w.info, D * sizeof(int32_t), hipMemcpyDeviceToHost, sc.stream) != hipSuccess ||
-        hipStreamSynchronize(sc.stream) != hipSuccess)
-        return set_error(nullptr, FFVD_EDEVICE, std::string(who) + ": device error while reading Cholesky status");
-    for (int d = 0; d < D; ++d)
-        if (hinfo[d]) {
-            char msg[200];
-            snprintf(msg, sizeof msg, "%s: Cholesky of K_uu + jitter*I failed: latent dim %d, pivot %d is not positive", who, d,
-                     hinfo[d] - 1);
-            return set_error(nullptr, FFVD_ENOTPD, msg);
-        }
-    return FFVD_OK;
-}
-
-extern "C" int ffvd_op_trsm(const double *L, int n, const double *B, int m, double *X) {
-    if (!L || !B || !X || n < 1 || m < 0) return set_error(nullptr, FFVD_EINVAL, "ffvd_op_trsm: bad argument");
-    for (int i = 0; i < n; ++i)
-        if (!(L[(size_t)i * n + i] != 0.0)) return set_error(nullptr, FFVD_EINVAL, "ffvd_op_trsm: zero on the diagonal of L");
-    OP_BEGIN("ffvd_op_trsm");
-    if (m == 0) return FFVD_OK;
-    // slab = [ L (np x np, identity padding) ; R = B^T (mp x np, zero padding) ];  X^T = R L^-T
-    const int np = round_up(n, NB), mp = round_up(m, NB);
-    std::vector<double> slab((size_t)(np + mp) * np, 0.0);
-    for (int i = 0; i < np; ++i) {
-        if (i < n) for (int j = 0; j <= i; ++j) slab[(size_t)i * np + j] = L[(size_t)i * n + j];
-        else slab[(size_t)i * np + i] = 1.0;
-    }
-    for (int c = 0; c < m; ++c)
-        for (int i = 0; i < n; ++i) slab[(size_t)(np + c) * np + i] = B[(size_t)i * m + c];
-    double *dA = sc.upload(slab.data(), slab.size());
-    OP_CHECK(dA, "ffvd_op_trsm");
-    double *dinv = sc.alloc<double>(DINV_STRIDE);
-    OP_CHECK(dinv, "ffvd_op_trsm");
-    launch_trsm_ext(sc.stream, dA, np, mp, 1, slab.size(), dinv);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(slab.data(), dA, slab.size() * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
-    HIP_TRY(hipStreamSynchronize(sc.stream));
-    for (int c = 0; c < m; ++c)
-        for (int i = 0; i < n; ++i) X[(size_t)i * m + c] = slab[(size_t)(np + c) * np + i];
-    return FFVD_OK;
-}
-
-extern "C" int ffvd_op_kernel_pre_cal(int kind, const double *Z, int M, int P, int D, const double *logvariance,
-                                      const double *loglengthscales, double jitter, double *Lm_inverse_seq) {
-    if (!Z || !logvariance || !Lm_inverse_seq || M < 1 || P < 1 || P > MAXP || D < 1 ||
-        (kind == FFVD_KERNEL_SE && !loglengthscales))
-        return set_error(nullptr, FFVD_EINVAL, "ffvd_op_kernel_pre_cal: bad argument");
-    OP_BEGIN("ffvd_op_kernel_pre_cal");
-    KuuWork w{};
-    int rc = build_kuu(sc, kind, Z, M, P, D, logvariance, loglengthscales, jitter, w, nullptr);
-    if (rc) return set_error(nullptr, rc, "ffvd_op_kernel_pre_cal: device allocation or upload failed");
-    const size_t Mp = w.Mp;
-    std::vector<double> host((size_t)D * 2 * Mp * Mp);
-    HIP_TRY(hipMemcpyAsync(host.data(), w.Kuu, host.size() * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
-    if ((rc = check_kuu_info(sc, w, D, "ffvd_op_kernel_pre_cal"))) return rc;
-    for (int d = 0; d < D; ++d) {
-        const double *Wd = host.data() + (size_t)d * 2 * Mp * Mp + Mp * Mp;
-        for (int i = 0; i < M; ++i)
-            memcpy(Lm_inverse_seq + ((size_t)d * M + i) * M, Wd + (size_t)i * Mp, (size_t)M * sizeof(double));
-    }
-    return FFVD_OK;
-}
-
-extern "C" int ffvd_op_collapse(int kind, const double *Lm_inverse_seq, const double *X_combine, const double *X,
-                                const double *Z, int T, int M, int P, int D, const double *logvariance,
-                                const double *loglengthscales, const double *Q, double batch_size, double Y_N,
-                                double out3[3]) {
-    if (!Lm_inverse_seq || !X_combine || !X || !Z || !logvariance || !Q || !out3 || T < 1 || M < 1 || P < 1 ||
-        P > MAXP || D < 1 || (kind == FFVD_KERNEL_SE && !loglengthscales) || !(batch_size > 0.0))
-        return set_error(nullptr, FFVD_EINVAL, "ffvd_op_collapse: bad argument");
-    OP_BEGIN("ffvd_op_collapse");
-    const int Mp = round_up(M, NB), Tp = round_up(T, STRIP), ng = (Mp + 511) / 512;
-    // pad the caller's L^{-T} stack to Mp with an identity block
-    std::vector<double> Wp((size_t)D * Mp * Mp, 0.0);
-    for (int d = 0; d < D; ++d)
-        for (int i = 0; i < Mp; ++i) {
-            double *row = Wp.data() + ((size_t)d * Mp + i) * Mp;
-            if (i < M) memcpy(row, Lm_inverse_seq + ((size_t)d * M + i) * M, (size_t)M * sizeof(double));
-            else row[i] = 1.0;
-        }
-    std::vector<double> logQ(D);
-    for (int d = 0; d < D; ++d) logQ[d] = log(Q[d]);
-    double *dW = sc.upload(Wp.data(), Wp.size());
-    double *dXc = sc.upload(X_combine, (size_t)T * P);
-    double *dX = sc.upload(X, (size_t)(T + 1) * D);
-    double *dZ = sc.upload(Z, (size_t)M * P);
-    double *dlv = sc.upload(logvariance, D);
-    double *dll = sc.alloc<double>((size_t)D * P);
-    double *dlq = sc.upload(logQ.data(), D);
-    double *variance = sc.alloc<double>(D), *len = sc.alloc<double>((size_t)D * P);
-    double *Zs = sc.alloc<double>((size_t)D * Mp * P), *zz = sc.alloc<double>((size_t)D * Mp);
-    double *F = sc.alloc<double>((size_t)D * Tp * Mp);
-    const size_t hstride = (size_t)(Mp + NB) * Mp;
-    double *H = sc.alloc<double>((size_t)D * hstride);
-    double *rowsq = sc.alloc<double>((size_t)D * ng * Tp);
-    double *hterms = sc.alloc<double>((size_t)D * 2), *cterms = sc.alloc<double>(8);
-    int32_t *info = sc.alloc<int32_t>(D);
-    double *dinv = sc.alloc<double>(potrf_scratch_doubles(Mp, D));
-    if (!dW || !dXc || !dX || !dZ || !dlv || !dll || !dlq || !variance || !len || !Zs || !zz || !F || !H || !rowsq ||
-        !hterms || !cterms || !info || !dinv)
-        return set_error(nullptr, FFVD_ENOMEM, "ffvd_op_collapse: device allocation or upload failed");
-    if (loglengthscales)
-        HIP_TRY(hipMemcpyAsync(dll, loglengthscales, (size_t)D * P * sizeof(double), hipMemcpyHostToDevice, sc.stream));
-    HIP_TRY(hipMemsetAsync(H, 0, (size_t)D * hstride * sizeof(double), sc.stream));
-    HIP_TRY(hipMemsetAsync(info, 0, D * sizeof(int32_t), sc.stream));
-    launch_prep_hypers(sc.stream, kind, dZ, M, Mp, P, D, 0, dlv, dll, variance, len, Zs, zz);
-    HyperView hv{variance, len, Zs, zz};
-    ProjectArgs pa{};
-    pa.kind = kind; pa.x = dXc; pa.x_chain_stride = 0; pa.x_ld = P; pa.x_cols = P; pa.ctrl = nullptr;
-    pa.T = T; pa.Tp = Tp; pa.C = 0; pa.P = P; pa.M = M; pa.Mp = Mp; pa.Dl = D; pa.d_begin = 0; pa.hv = hv;
-    pa.W = dW; pa.w_stride = (size_t)Mp * Mp; pa.U = nullptr; pa.u_ld = 0; pa.b0 = 0; pa.nb = D; pa.F = F;
-    pa.rowsq = rowsq; pa.fmean = nullptr; pa.ng = ng;
-    launch_project(sc.stream, pa);
-    GramArgs ga{};
-    ga.mode = GRAM_F; ga.A = F; ga.a_stride = (size_t)Tp * Mp; ga.rows = Tp; ga.with_row = 1;
-    ga.X = dX; ga.log_Q = dlq; ga.T = T; ga.D = D; ga.Mp = Mp; ga.Dl = D; ga.d_begin = 0;
-    ga.b0 = 0; ga.nb = D; ga.yn_over_batch = Y_N / batch_size; ga.H = H; ga.h_stride = hstride;
-    launch_gram(sc.stream, ga);
-    launch_potrf_ext(sc.stream, H, Mp, NB, 0, D, hstride, info, dinv);
-    launch_h_finish(sc.stream, H, Mp, hstride, D, hterms);
-    ReduceArgs ra{};
-    ra.kind = kind; ra.branch = FFVD_BRANCH_B; ra.X = dX; ra.ctrl = nullptr; ra.Y = nullptr; ra.log_Q = dlq;
-    ra.CC = nullptr; ra.DD = nullptr; ra.log_Rchols = nullptr; ra.variance = variance; ra.T = T; ra.Tp = Tp; ra.D = D;
-    ra.C = 0; ra.Ydim = 0; ra.Dl = D; ra.d_begin = 0; ra.S = 1; ra.ng = ng; ra.shared_terms = 0;
-    ra.xk = dXc; ra.xk_chain_stride = 0; ra.xk_ld = P; ra.xk_cols = P; ra.rowsq = rowsq; ra.fmean = nullptr;
-    ra.chain_terms = cterms;
-    double *cpart = sc.alloc<double>(128);
-    if (!cpart) return set_error(nullptr, FFVD_ENOMEM, "ffvd_op_collapse: device allocation failed");
-    launch_chain_reduce(sc.stream, ra, cpart);
-    std::vector<double> ht((size_t)D * 2), ct(8);
-    std::vector<int32_t> hinfo(D);
-    HIP_TRY(hipMemcpyAsync(ht.data(), hterms, ht.size() * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
-    HIP_TRY(hipMemcpyAsync(ct.data(), cterms, 8 * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
-    HIP_TRY(hipMemcpyAsync(hinfo.data(), info, D * sizeof(int32_t), hipMemcpyDeviceToHost, sc.stream));
-    HIP_TRY(hipStreamSynchronize(sc.stream));
-    for (int d = 0; d < D; ++d)
-        if (hinfo[d]) {
-            char msg[160];
-            snprintf(msg, sizeof msg, "ffvd_op_collapse: Cholesky of H failed: latent dim %d, pivot %d is not positive", d, hinfo[d] - 1);
-            return set_error(nullptr, FFVD_ENOTPD, msg);
-        }
-    double term1 = 0.0, term2 = 0.0;
-    for (int d = 0; d < D; ++d) { term1 += -0.5 * ht[2 * d]; term2 += 0.5 * ht[2 * d + 1]; }
-    out3[0] = -term1 / Y_N;
-    out3[1] = -term2 / Y_N;
-    out3[2] = -ct[2] / Y_N;      // chain_reduce's trace sum: sum_d sum_t -0.5 (Kdiag - |F_t|^2) / Q_d
-    return FFVD_OK;
-}
-
-extern "C" int ffvd_op_conditional(int kind, const double *Xnew, int N, const double *Z, int M, int P, int D,
-                                   const double *logvariance, const double *loglengthscales, const double *f,
-                                   double jitter, double *mean, double *var) {
-    if (!Xnew || !Z || !logvariance || !f || !mean || !var || N < 0 || M < 1 || P < 1 || P > MAXP || D < 1 ||
-        (kind == FFVD_KERNEL_SE && !loglengthscales))
-        return set_error(nullptr, FFVD_EINVAL, "ffvd_op_conditional: bad argument");
-    OP_BEGIN("ffvd_op_conditional");
-    if (N == 0) return FFVD_OK;
-    KuuWork w{};
-    int rc = build_kuu(sc, kind, Z, M, P, D, logvariance, loglengthscales, jitter, w, nullptr);
-    if (rc) return set_error(nullptr, rc, "ffvd_op_conditional: device allocation or upload failed");
-    const int Mp = w.Mp, Tp = round_up(N, STRIP), ng = (Mp + 511) / 512;
-    double *dX = sc.upload(Xnew, (size_t)N * P);
-    double *dU = sc.upload(f, (size_t)M * D);
-    double *rowsq = sc.alloc<double>((size_t)D * ng * Tp), *fmean = sc.alloc<double>((size_t)D * ng * Tp);
-    double *dmean = sc.alloc<double>((size_t)N * D), *dvar = sc.alloc<double>((size_t)N * D);
-    if (!dX || !dU || !rowsq || !fmean || !dmean || !dvar)
-        return set_error(nullptr, FFVD_ENOMEM, "ffvd_op_conditional: device allocation or upload failed");
-    HyperView hv{w.variance, w.len, w.Zs, w.zz};
-    ProjectArgs pa{};
-    pa.kind = kind; pa.x = dX; pa.x_chain_stride = 0; pa.x_ld = P; pa.x_cols = P; pa.ctrl = nullptr;
-    pa.T = N; pa.Tp = Tp; pa.C = 0; pa.P = P; pa.M = M; pa.Mp = Mp; pa.Dl = D; pa.d_begin = 0; pa.hv = hv;
-    pa.W = w.Kuu + (size_t)Mp * Mp; pa.w_stride = (size_t)2 * Mp * Mp; pa.U = dU; pa.u_ld = D; pa.b0 = 0; pa.nb = D;
-    pa.F = nullptr; pa.rowsq = rowsq; pa.fmean = fmean; pa.ng = ng;
-    launch_project(sc.stream, pa);
-    launch_conditional_finish(sc.stream, kind, dX, N, P, w.variance, rowsq, fmean, ng, Tp, D, dmean, dvar, nullptr);
-    HIP_TRY(hipMemcpyAsync(mean, dmean, (size_t)N * D * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
-    HIP_TRY(hipMemcpyAsync(var, dvar, (size_t)N * D * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
-    return check_kuu_info(sc, w, D, "ffvd_op_conditional");
-}
-
-extern "C" int ffvd_op_predict_mean(const double *X_end, int N, int D, const double *CC, const double *DD, int Ydim,
-                                    double *out) {
-    if (!X_end || !CC || !DD || !out || N < 0 || D < 1 || Ydim < 1)
-        return set_error(nullptr, FFVD_EINVAL, "ffvd_op_predict_mean: bad argument");
-    OP_BEGIN("ffvd_op_predict_mean");
-    if (N == 0) return FFVD_OK;
-    double *dX = sc.upload(X_end, (size_t)N * D), *dC = sc.upload(CC, (size_t)D * Ydim), *dD = sc.upload(DD, Ydim);
-    double *dO = sc.alloc<double>((size_t)N * Ydim);
-    if (!dX || !dC || !dD || !dO) return set_error(nullptr, FFVD_ENOMEM, "ffvd_op_predict_mean: device allocation or upload failed");
-    launch_predict_mean(sc.stream, dX, N, D, dC, dD, Ydim, dO);
-    HIP_TRY(hipMemcpyAsync(out, dO, (size_t)N * Ydim * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
-    HIP_TRY(hipStreamSynchronize(sc.stream));
-    return FFVD_OK;
-}
-
-extern "C" int ffvd_op_logdensity_norm_diag(int nonvec, const double *y, const double *ymean, const double *Rchols, int N,
-                                            int J, double *out) {
-    if (!y || !ymean || !Rchols || !out || N < 0 || J < 1)
-        return set_error(nullptr, FFVD_EINVAL, "ffvd_op_logdensity_norm_diag: bad argument");
-    OP_BEGIN("ffvd_op_logdensity_norm_diag");
-    if (N == 0) return FFVD_OK;
-    const size_t nout = nonvec ? (size_t)N * J : (size_t)N;
-    double *dy = sc.upload(y, (size_t)N * J), *dm = sc.upload(ymean, (size_t)N * J), *dR = sc.upload(Rchols, J);
-    double *dO = sc.alloc<double>(nout);
-    if (!dy || !dm || !dR || !dO) return set_error(nullptr, FFVD_ENOMEM, "ffvd_op_logdensity_norm_diag: device allocation or upload failed");
-    launch_logdensity(sc.stream, nonvec ? 1 : 0, dy, dm, dR, N, J, dO);
-    HIP_TRY(hipMemcpyAsync(out, dO, nout * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
-    HIP_TRY(hipStreamSynchronize(sc.stream));
-    return FFVD_OK;
-}
-
-extern "C" int ffvd_op_get_rand(const double *mean, const double *var, const double *eps, int64_t n, double *out) {
-    if (!mean || !var || !eps || !out || n < 0) return set_error(nullptr, FFVD_EINVAL, "ffvd_op_get_rand: bad argument");
-    OP_BEGIN("ffvd_op_get_rand");
-    if (n == 0) return FFVD_OK;
-    double *dm = sc.upload(mean, (size_t)n), *dv = sc.upload(var, (size_t)n), *de = sc.upload(eps, (size_t)n);
-    double *dO = sc.alloc<double>((size_t)n);
-    if (!dm || !dv || !de || !dO) return set_error(nullptr, FFVD_ENOMEM, "ffvd_op_get_rand: device allocation or upload failed");
-    launch_get_rand(sc.stream, dm, dv, de, (size_t)n, dO);
-    HIP_TRY(hipMemcpyAsync(out, dO, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
-    HIP_TRY(hipStreamSynchronize(sc.stream));
-    return FFVD_OK;
-}
-
-// shared by ffvd_op_collapse_u_mean / ffvd_op_conditional_precalc: pad a caller-supplied stack of D M x M matrices
-// (M a multiple of the block size: nothing to pad -- the callers upload the caller's array itself, pad_needed)
-static bool pad_needed(int M, int Mp) { return M != Mp; }
-static std::vector<double> pad_stack(const double *src, int D, int M, int Mp) {
-    std::vector<double> out((size_t)D * Mp * Mp, 0.0);
-    for (int d = 0; d < D; ++d)
-        for (int i = 0; i < Mp; ++i) {
-            double *row = out.data() + ((size_t)d * Mp + i) * Mp;
-            if (i < M) memcpy(row, src + ((size_t)d * M + i) * M, (size_t)M * sizeof(double));
-            else row[i] = 1.0;
-        }
-    return out;
-}
-
-// upload a stack of D M x M matrices padded to Mp (`keep` owns the padded host copy until the call returns; none when M == Mp)
-static double *upload_stack(Scratch &sc, const double *src, int D, int M, int Mp, std::vector<double> &keep) {
-    if (!pad_needed(M, Mp)) return sc.upload(src, (size_t)D * M * M);
-    keep = pad_stack(src, D, M, Mp);
-    return sc.upload(keep.data(), keep.size());
-}
-
-extern "C" int ffvd_op_collapse_u_mean(int kind, const double *Lm_inverse_seq, const double *X_combine, const double *X,
-                                       const double *Z, int T, int M, int P, int D, const double *logvariance,
-                                       const double *loglengthscales, const double *Q, double *U_mean,
-                                       double *H_inv_sqrt) {
-    if (!Lm_inverse_seq || !X_combine || !X || !Z || !logvariance || !Q || !U_mean || !H_inv_sqrt || T < 1 || M < 1 ||
-        P < 1 || P > MAXP || D < 1 || (kind == FFVD_KERNEL_SE && !loglengthscales))
-        return set_error(nullptr, FFVD_EINVAL, "ffvd_op_collapse_u_mean: bad argument");
-    OP_BEGIN("ffvd_op_collapse_u_mean");
-    const int Mp = round_up(M, NB), Tp = round_up(T, STRIP), ng = (Mp + 511) / 512;
-    std::vector<double> Wp;
-    std::vector<double> logQ(D);
-    for (int d = 0; d < D; ++d) logQ[d] = log(Q[d]);
-    // slab per dim: rows [0,Mp) H, rows [Mp,2Mp) identity -> L_H^-T, row 2Mp carries b -> L_H^-1 b
-    const size_t hstride = (size_t)(2 * Mp + NB) * Mp;
-    std::vector<double> Hinit((size_t)D * hstride, 0.0);
-    for (int d = 0; d < D; ++d)
-        for (int i = 0; i < Mp; ++i) Hinit[(size_t)d * hstride + (size_t)(Mp + i) * Mp + i] = 1.0;
-    double *dW = upload_stack(sc, Lm_inverse_seq, D, M, Mp, Wp);
-    double *dXc = sc.upload(X_combine, (size_t)T * P), *dX = sc.upload(X, (size_t)(T + 1) * D);
-    double *dZ = sc.upload(Z, (size_t)M * P), *dlv = sc.upload(logvariance, D), *dlq = sc.upload(logQ.data(), D);
-    double *dll = sc.alloc<double>((size_t)D * P);
-    double *variance = sc.alloc<double>(D), *len = sc.alloc<double>((size_t)D * P);
-    double *Zs = sc.alloc<double>((size_t)D * Mp * P), *zz = sc.alloc<double>((size_t)D * Mp);
-    double *F = sc.alloc<double>((size_t)D * Tp * Mp), *rowsq = sc.alloc<double>((size_t)D * ng * Tp);
-    double *H = sc.upload(Hinit.data(), Hinit.size());
-    double *dU = sc.alloc<double>((size_t)M * D);
-    int32_t *info = sc.alloc<int32_t>(D);
-    double *dinv = sc.alloc<double>(potrf_scratch_doubles(Mp, D));
-    if (!dW || !dXc || !dX || !dZ || !dlv || !dlq || !dll || !variance || !len || !Zs || !zz || !F || !rowsq || !H || !dU || !info || !dinv)
-        return set_error(nullptr, FFVD_ENOMEM, "ffvd_op_collapse_u_mean: device allocation or upload failed");
-    if (loglengthscales)
-        HIP_TRY(hipMemcpyAsync(dll, loglengthscales, (size_t)D * P * sizeof(double), hipMemcpyHostToDevice, sc.stream));
-    HIP_TRY(hipMemsetAsync(info, 0, D * sizeof(int32_t), sc.stream));
-    launch_prep_hypers(sc.stream, kind, dZ, M, Mp, P, D, 0, dlv, dll, variance, len, Zs, zz);
-    HyperView hv{variance, len, Zs, zz};
-    ProjectArgs pa{};
-    pa.kind = kind; pa.x = dXc; pa.x_chain_stride = 0; pa.x_ld = P; pa.x_cols = P; pa.ctrl = nullptr;
-    pa.T = T; pa.Tp = Tp; pa.C = 0; pa.P = P; pa.M = M; pa.Mp = Mp; pa.Dl = D; pa.d_begin = 0; pa.hv = hv;
-    pa.W = dW; pa.w_stride = (size_t)Mp * Mp; pa.U = nullptr; pa.u_ld = 0; pa.b0 = 0; pa.nb = D; pa.F = F;
-    pa.rowsq = rowsq; pa.fmean = nullptr; pa.ng = ng;
-    launch_project(sc.stream, pa);
-    GramArgs ga{};
-    ga.mode = GRAM_F; ga.A = F; ga.a_stride = (size_t)Tp * Mp; ga.rows = Tp; ga.with_row = 1; ga.brow = 2 * Mp;
-    ga.X = dX; ga.log_Q = dlq; ga.T = T; ga.D = D; ga.Mp = Mp; ga.Dl = D; ga.d_begin = 0;
-    ga.b0 = 0; ga.nb = D; ga.yn_over_batch = 1.0; ga.H = H; ga.h_stride = hstride;     // :215,:217 (no batch rescaling)
-    launch_gram(sc.stream, ga);
-    launch_potrf_ext(sc.stream, H, Mp, Mp + NB, Mp, D, hstride, info, dinv);
-    // U_mean[:, d] = H^-1 b = L_H^-T (L_H^-1 b)   (tf.linalg.solve, :219)
-    launch_matvec(sc.stream, H + (size_t)Mp * Mp, hstride, H + (size_t)2 * Mp * Mp, hstride, Mp, dU, D, 1, M, D);
-    std::vector<double> hH((size_t)D * hstride);
-    std::vector<int32_t> hinfo(D);
-    HIP_TRY(hipMemcpyAsync(hH.data(), H, hH.size() * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
-    HIP_TRY(hipMemcpyAsync(U_mean, dU, (size_t)M * D * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
-    HIP_TRY(hipMemcpyAsync(hinfo.data(), info, D * sizeof(int32_t), hipMemcpyDeviceToHost, sc.stream));
-    HIP_TRY(hipStreamSynchronize(sc.stream));
-    for (int d = 0; d < D; ++d)
-        if (hinfo[d]) {
-            char msg[160];
-            snprintf(msg, sizeof msg, "ffvd_op_collapse_u_mean: Cholesky of H failed: latent dim %d, pivot %d is not positive", d, hinfo[d] - 1);
-            return set_error(nullptr, FFVD_ENOTPD, msg);
-        }
-    for (int d = 0; d < D; ++d)          // Lm_inverse_dd_seq = L_H^-T (:222)
-        for (int i = 0; i < M; ++i)
-            memcpy(H_inv_sqrt + ((size_t)d * M + i) * M, hH.data() + (size_t)d * hstride + (size_t)(Mp + i) * Mp,
-                   (size_t)M * sizeof(double));
-    return FFVD_OK;
-}
-
-extern "C" int ffvd_op_conditional_precalc(int kind, const double *Lm_inverse_seq, const double *Xnew, int N,
-                                           const double *Z, int M, int P, int D, const double *logvariance,
-                                           const double *loglengthscales, const double *f, const double *q_sqrt,
-                                           double *mean, double *var) {
-    if (!Lm_inverse_seq || !Xnew || !Z || !logvariance || !f || !mean || !var || N < 0 || M < 1 || M > 2048 || P < 1 ||
-        P > MAXP || D < 1 || (kind == FFVD_KERNEL_SE && !loglengthscales))
-        return set_error(nullptr, FFVD_EINVAL, "ffvd_op_conditional_precalc: bad argument");
-    OP_BEGIN("ffvd_op_conditional_precalc");
-    if (N == 0) return FFVD_OK;
-    const int Mp = round_up(M, NB), Tp = round_up(N, STRIP), ng = (Mp + 511) / 512;
-    std::vector<double> Wp;
-    double *dW = upload_stack(sc, Lm_inverse_seq, D, M, Mp, Wp);
-    double *dX = sc.upload(Xnew, (size_t)N * P), *dZ = sc.upload(Z, (size_t)M * P), *dU = sc.upload(f, (size_t)M * D);
-    double *dlv = sc.upload(logvariance, D), *dll = sc.alloc<double>((size_t)D * P);
-    double *variance = sc.alloc<double>(D), *len = sc.alloc<double>((size_t)D * P);
-    double *Zs = sc.alloc<double>((size_t)D * Mp * P), *zz = sc.alloc<double>((size_t)D * Mp);
-    double *F = sc.alloc<double>((size_t)D * Tp * Mp);
-    double *rowsq = sc.alloc<double>((size_t)D * ng * Tp), *fmean = sc.alloc<double>((size_t)D * ng * Tp);
-    double *dmean = sc.alloc<double>((size_t)N * D), *dvar = sc.alloc<double>((size_t)N * D);
-    double *dQs = q_sqrt ? sc.upload(q_sqrt, (size_t)M * M) : nullptr;     // slice d = 0 only (the reference quirk)
-    double *extra = q_sqrt ? sc.alloc<double>((size_t)D * Tp) : nullptr;
-    if (!dW || !dX || !dZ || !dU || !dlv || !dll || !variance || !len || !Zs || !zz || !F || !rowsq || !fmean || !dmean ||
-        !dvar || (q_sqrt && (!dQs || !extra)))
-        return set_error(nullptr, FFVD_ENOMEM, "ffvd_op_conditional_precalc: device allocation or upload failed");
-    if (loglengthscales)
-        HIP_TRY(hipMemcpyAsync(dll, loglengthscales, (size_t)D * P * sizeof(double), hipMemcpyHostToDevice, sc.stream));
-    launch_prep_hypers(sc.stream, kind, dZ, M, Mp, P, D, 0, dlv, dll, variance, len, Zs, zz);
-    HyperView hv{variance, len, Zs, zz};
-    ProjectArgs pa{};
-    pa.kind = kind; pa.x = dX; pa.x_chain_stride = 0; pa.x_ld = P; pa.x_cols = P; pa.ctrl = nullptr;
-    pa.T = N; pa.Tp = Tp; pa.C = 0; pa.P = P; pa.M = M; pa.Mp = Mp; pa.Dl = D; pa.d_begin = 0; pa.hv = hv;
-    pa.W = dW; pa.w_stride = (size_t)Mp * Mp; pa.U = dU; pa.u_ld = D; pa.b0 = 0; pa.nb = D;
-    pa.F = q_sqrt ? F : nullptr; pa.rowsq = rowsq; pa.fmean = fmean; pa.ng = ng;
-    launch_project(sc.stream, pa);                                           // A^T = K_fu L^-T (:349), mean (:365), sum A^2 (:356)
-    if (q_sqrt) launch_qsqrt_inflation(sc.stream, F, (size_t)Tp * Mp, Tp, Mp, M, dQs, extra, N, D);
-    launch_conditional_finish(sc.stream, kind, dX, N, P, variance, rowsq, fmean, ng, Tp, D, dmean, dvar, extra);
-    HIP_TRY(hipMemcpyAsync(mean, dmean, (size_t)N * D * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
-    HIP_TRY(hipMemcpyAsync(var, dvar, (size_t)N * D * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
-    HIP_TRY(hipStreamSynchronize(sc.stream));
-    return FFVD_OK;
-}
-
-// Full predictive covariance / q_sqrt inflation of the conditional (ffvd_op_conditional_cov, ffvd_op_conditional_precalc_cov), once
-// the stack W_d = L_d^-T (Mp x Mp, slab stride w_stride) and the hyper-parameters are on the device.  Mean and per-point variance run
-// through the same launches as ffvd_op_conditional / ffvd_op_conditional_precalc (projection with F kept, conditional_finish); then
-//   q_sqrt (M x M slice 0, as given):  E_d = F_d q0 (cov.hip, COV_GEN, q0^T uploaded once for all d);
-//   full_cov:  Sigma_d = K_d(Xnew, Xnew) - F_d F_d^T (+ E_d E_d^T) (cov.hip, COV_SYM), var: D x N x N, its diagonal the per-point
-//              variance (without q_sqrt: that of the full_cov = 0 form bit for bit; with it: the q_sqrt term summed from E's rows);
-//   otherwise: var[:, d] += sum_j E_d[:, j]^2 through qsqrt_inflation (conditionals_multi_output.py:371-380), var: N x D.
-static int conditional_cov_tail(Scratch &sc, const char *who, int kind, const HyperView &hv, const double *W, size_t w_stride,
-                                const double *Xnew, int N, int M, int P, int D, const double *f, const double *q_sqrt, int full_cov,
-                                double *mean, double *var) {
-    ffvd_handle *h = nullptr;
-    const int Mp = round_up(M, NB), Tp = round_up(N, STRIP), ng = (Mp + 511) / 512;
-    double *dX = sc.upload(Xnew, (size_t)N * P), *dU = sc.upload(f, (size_t)M * D);
-    double *rowsq = sc.alloc<double>((size_t)D * ng * Tp), *fmean = sc.alloc<double>((size_t)D * ng * Tp);
-    double *dmean = sc.alloc<double>((size_t)N * D), *dvar = sc.alloc<double>((size_t)N * D);
-    double *F = sc.alloc<double>((size_t)D * Tp * Mp);
-    if (!dX || !dU || !rowsq || !fmean || !dmean || !dvar || !F)
-        return set_error(nullptr, FFVD_ENOMEM, std::string(who) + ": device allocation or upload failed");
-    ProjectArgs pa{};
-    pa.kind = kind; pa.x = dX; pa.x_chain_stride = 0; pa.x_ld = P; pa.x_cols = P; pa.ctrl = nullptr;
-    pa.T = N; pa.Tp = Tp; pa.C = 0; pa.P = P; pa.M = M; pa.Mp = Mp; pa.Dl = D; pa.d_begin = 0; pa.hv = hv;
-    pa.W = W; pa.w_stride = w_stride; pa.U = dU; pa.u_ld = D; pa.b0 = 0; pa.nb = D;
-    pa.F = F; pa.rowsq = rowsq; pa.fmean = fmean; pa.ng = ng;
-    launch_project(sc.stream, pa);                                   // F = A^T = K_fu L^-T (:34 / :349), mean (:48 / :365)
-    if (!full_cov) {
-        double *dQs = q_sqrt ? sc.upload(q_sqrt, (size_t)M * M) : nullptr, *extra = q_sqrt ? sc.alloc<double>((size_t)D * Tp) : nullptr;
-        if (q_sqrt && (!dQs || !extra)) return set_error(nullptr, FFVD_ENOMEM, std::string(who) + ": device allocation or upload failed");
-        if (q_sqrt) launch_qsqrt_inflation(sc.stream, F, (size_t)Tp * Mp, Tp, Mp, M, dQs, extra, N, D);
-        launch_conditional_finish(sc.stream, kind, dX, N, P, hv.variance, rowsq, fmean, ng, Tp, D, dmean, dvar, extra);
-        HIP_TRY(hipMemcpyAsync(mean, dmean, (size_t)N * D * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
-        HIP_TRY(hipMemcpyAsync(var, dvar, (size_t)N * D * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
-        HIP_TRY(hipStreamSynchronize(sc.stream));
-        return FFVD_OK;
-    }
-    double *E = nullptr, *extra = nullptr;
-    if (q_sqrt) {
-        std::vector<double> qt((size_t)Mp * Mp, 0.0);                // q0^T, zero padded: row j = column j of q0
-        for (int k = 0; k < M; ++k)
-            for (int j = 0; j < M; ++j) qt[(size_t)j * Mp + k] = q_sqrt[(size_t)k * M + j];
-        double *dQt = sc.upload(qt.data(), qt.size());
-        E = sc.alloc<double>((size_t)D * Tp * Mp);
-        extra = sc.alloc<double>((size_t)D * Tp);
-        if (!dQt || !E || !extra) return set_error(nullptr, FFVD_ENOMEM, std::string(who) + ": device allocation or upload failed");
-        CovArgs ea{};
-        ea.mode = COV_GEN; ea.A = F; ea.a_stride = (size_t)Tp * Mp; ea.lda = Mp; ea.arows = Tp; ea.K = Mp;
-        ea.B = dQt; ea.b_stride = 0; ea.ldb = Mp; ea.brows = Mp; ea.ncols = Mp;
-        ea.C = E; ea.c_stride = (size_t)Tp * Mp; ea.ldc = Mp; ea.nb = D;
-        launch_cov(sc.stream, ea);                                   // LTA^T = F q0 (:371-376, slice 0 for every dim)
-        launch_row_sumsq(sc.stream, E, (size_t)Tp * Mp, Mp, Mp, N, D, Tp, extra);     // sum_j LTA^2 (:380)
-        HIP_TRY(hipStreamSynchronize(sc.stream));                    // (qt leaves scope: its upload must have completed)
-    }
-    // the per-point variance becomes the diagonal of Sigma_d
-    launch_conditional_finish(sc.stream, kind, dX, N, P, hv.variance, rowsq, fmean, ng, Tp, D, dmean, dvar, extra);
-    double *dS = sc.alloc<double>((size_t)D * N * N);
-    if (!dS) return set_error(nullptr, FFVD_ENOMEM, std::string(who) + ": device allocation failed");
-    CovArgs ca{};
-    ca.mode = COV_SYM; ca.A = F; ca.E = E; ca.a_stride = (size_t)Tp * Mp; ca.lda = Mp; ca.arows = Tp; ca.K = Mp;
-    ca.C = dS; ca.c_stride = (size_t)N * N; ca.ldc = N; ca.N = N; ca.kind = kind; ca.P = P; ca.x = dX;
-    ca.variance = hv.variance; ca.len = hv.len; ca.diag = dvar; ca.nb = D;
-    launch_cov(sc.stream, ca);                                       // K(Xnew) - A^T A (+ LTA^T LTA) (:41-44 full_cov branch)
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(mean, dmean, (size_t)N * D * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
-    if (!sc.download(var, dS, (size_t)D * N * N * sizeof(double)))
-        return set_error(nullptr, FFVD_EDEVICE, std::string(who) + ": device error while copying the covariance out");
-    return FFVD_OK;
-}
-
-static bool cov_args_ok(int kind, const double *Xnew, int N, const double *Z, int M, int P, int D, const double *logvariance,
-                        const double *loglengthscales, const double *f, const double *q_sqrt, int full_cov, const double *mean,
-                        const double *var) {
-    return Xnew && Z && logvariance && f && mean && var && N >= 0 && M >= 1 && P >= 1 && P <= MAXP && D >= 1 &&
-           (kind == FFVD_KERNEL_SE || kind == FFVD_KERNEL_LINEAR) && (kind != FFVD_KERNEL_SE || loglengthscales) &&
-           (full_cov == 0 || full_cov == 1) && (!q_sqrt || M <= 2048) &&
-           (size_t)D * N * N <= ((size_t)1 << 40);
-}
-
-extern "C" int ffvd_op_conditional_cov(int kind, const double *Xnew, int N, const double *Z, int M, int P, int D,
-                                       const double *logvariance, const double *loglengthscales, const double *f,
-                                       const double *q_sqrt, int full_cov, double jitter, double *mean, double *var) {
-    if (!cov_args_ok(kind, Xnew, N, Z, M, P, D, logvariance, loglengthscales, f, q_sqrt, full_cov, mean, var))
-        return set_error(nullptr, FFVD_EINVAL, "ffvd_op_conditional_cov: bad argument");
-    OP_BEGIN("ffvd_op_conditional_cov");
-    if (N == 0) return FFVD_OK;
-    KuuWork w{};
-    int rc = build_kuu(sc, kind, Z, M, P, D, logvariance, loglengthscales, jitter, w, nullptr);
-    if (rc) return set_error(nullptr, rc, "ffvd_op_conditional_cov: device allocation or upload failed");
-    const int Mp = w.Mp;
-    HyperView hv{w.variance, w.len, w.Zs, w.zz};
-    rc = conditional_cov_tail(sc, "ffvd_op_conditional_cov", kind, hv, w.Kuu + (size_t)Mp * Mp, (size_t)2 * Mp * Mp, Xnew, N, M, P,
-                              D, f, q_sqrt, full_cov, mean, var);
-    if (rc) return rc;
-    return check_kuu_info(sc, w, D, "ffvd_op_conditional_cov");
-}
-
-extern "C" int ffvd_op_conditional_precalc_cov(int kind, const double *Lm_inverse_seq, const double *Xnew, int N, const double *Z,
-                                               int M, int P, int D, const double *logvariance, const double *loglengthscales,
-                                               const double *f, const double *q_sqrt, int full_cov, double *mean, double *var) {
-    if (!Lm_inverse_seq || !cov_args_ok(kind, Xnew, N, Z, M, P, D, logvariance, loglengthscales, f, q_sqrt, full_cov, mean, var))
-        return set_error(nullptr, FFVD_EINVAL, "ffvd_op_conditional_precalc_cov: bad argument");
-    OP_BEGIN("ffvd_op_conditional_precalc_cov");
-    if (N == 0) return FFVD_OK;
-    const int Mp = round_up(M, NB);
-    std::vector<double> Wp;
-    double *dW = upload_stack(sc, Lm_inverse_seq, D, M, Mp, Wp);
-    double *dZ = sc.upload(Z, (size_t)M * P), *dlv = sc.upload(logvariance, D), *dll = sc.alloc<double>((size_t)D * P);
-    double *variance = sc.alloc<double>(D), *len = sc.alloc<double>((size_t)D * P);
-    double *Zs = sc.alloc<double>((size_t)D * Mp * P), *zz = sc.alloc<double>((size_t)D * Mp);
-    if (!dW || !dZ || !dlv || !dll || !variance || !len || !Zs || !zz)
-        return set_error(nullptr, FFVD_ENOMEM, "ffvd_op_conditional_precalc_cov: device allocation or upload failed");
-    if (loglengthscales)
-        HIP_TRY(hipMemcpyAsync(dll, loglengthscales, (size_t)D * P * sizeof(double), hipMemcpyHostToDevice, sc.stream));
-    launch_prep_hypers(sc.stream, kind, dZ, M, Mp, P, D, 0, dlv, dll, variance, len, Zs, zz);
-    HyperView hv{variance, len, Zs, zz};
-    return conditional_cov_tail(sc, "ffvd_op_conditional_precalc_cov", kind, hv, dW, (size_t)Mp * Mp, Xnew, N, M, P, D, f, q_sqrt,
-                                full_cov, mean, var);
-}
-
-extern "C" int ffvd_op_get_rand_full_cov(const double *mean, const double *var, const double *eps, int N, int D, double jitter,
-                                         double *out) {
-    if (!mean || !var || !eps || !out || N < 0 || D < 1 || !(jitter >= 0.0) || (size_t)D * N * N > ((size_t)1 << 40))
-        return set_error(nullptr, FFVD_EINVAL, "ffvd_op_get_rand_full_cov: bad argument");
-    OP_BEGIN("ffvd_op_get_rand_full_cov");
-    if (N == 0) return FFVD_OK;
-    const int np = round_up(N, NB);
-    const size_t slab = (size_t)np * np;
-    std::vector<double> pad(slab * D, 0.0);                          // Sigma_d + jitter I, identity padded to np
-    for (int d = 0; d < D; ++d) {
-        double *S = pad.data() + slab * d;
-        for (int i = 0; i < np; ++i) {
-            if (i < N) {
-                memcpy(S + (size_t)i * np, var + ((size_t)d * N + i) * N, (size_t)N * sizeof(double));
-                S[(size_t)i * np + i] += jitter;
-            } else S[(size_t)i * np + i] = 1.0;
-        }
-    }
-    double *dA = sc.upload(pad.data(), pad.size());
-    double *dm = sc.upload(mean, (size_t)N * D), *de = sc.upload(eps, (size_t)N * D), *dO = sc.alloc<double>((size_t)N * D);
-    int32_t *dinfo = sc.alloc<int32_t>(D);
-    double *dinv = sc.alloc<double>(potrf_scratch_doubles(np, D));
-    if (!dA || !dm || !de || !dO || !dinfo || !dinv)
-        return set_error(nullptr, FFVD_ENOMEM, "ffvd_op_get_rand_full_cov: device allocation or upload failed");
-    std::vector<int32_t> hinfo(D, 0);
-    bool recovered = false;
-    int rc = potrf_with_stall_recovery(sc, dA, pad.data(), np, D, dinfo, dinv, hinfo.data(), &recovered, "ffvd_op_get_rand_full_cov");
-    if (rc) return rc;
-    for (int d = 0; d < D; ++d)
-        if (hinfo[d]) {
-            char msg[200];
-            snprintf(msg, sizeof msg, "ffvd_op_get_rand_full_cov: Cholesky of var[%d] + jitter*I failed: latent dim %d, pivot %d is not "
-                     "positive", d, d, hinfo[d] - 1);
-            return set_error(nullptr, FFVD_ENOTPD, msg);
-        }
-    launch_tril_matvec(sc.stream, dA, slab, np, N, D, dm, de, dO);    // mean + L eps (utils.py:4-11, full_cov branch)
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out, dO, (size_t)N * D * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
-    HIP_TRY(hipStreamSynchronize(sc.stream));
-    if (recovered)
-        set_error(nullptr, FFVD_OK, "warning: ffvd_op_get_rand_full_cov: the one-launch (dataflow) Cholesky gave up on a bounded wait; "
-                                    "the batch was re-run with the launch-per-column Cholesky and completed");
-    return FFVD_OK;
-}
-
-extern "C" int ffvd_op_adam_step(double *theta, const double *grad, double *m, double *v, int64_t n, double lr,
-                                 double beta1, double beta2, double eps, int64_t t) {
-    if (!theta || !grad || !m || !v || n < 0 || t < 1 || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0))
-        return set_error(nullptr, FFVD_EINVAL, "ffvd_op_adam_step: bad argument");
-    OP_BEGIN("ffvd_op_adam_step");
-    if (n == 0) return FFVD_OK;
-    double *dth = sc.upload(theta, n), *dm = sc.upload(m, n), *dv = sc.upload(v, n);
-    const double *dg = sc.upload(grad, n);
-    if (!dth || !dm || !dv || !dg) return set_error(nullptr, FFVD_ENOMEM, "ffvd_op_adam_step: device allocation or upload failed");
-    OptTable tab{};
-    tab.count = 1;
-    tab.t[0].theta = dth; tab.t[0].grad = dg; tab.t[0].s0 = dm; tab.t[0].s1 = dv; tab.t[0].n = n;
-    const double lr_t = lr * sqrt(1.0 - pow(beta2, (double)t)) / (1.0 - pow(beta1, (double)t));
-    launch_adam(sc.stream, tab, lr_t, beta1, beta2, eps);
-    HIP_TRY(hipMemcpyAsync(theta, dth, n * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
-    HIP_TRY(hipMemcpyAsync(m, dm, n * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
-    HIP_TRY(hipMemcpyAsync(v, dv, n * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
-    HIP_TRY(hipStreamSynchronize(sc.stream));
-    return FFVD_OK;
-}
-
-extern "C" int ffvd_op_sghmc_step(double *theta, const double *grad, double *xi, double *g, double *g2, double *p,
-                                  const double *noise, int64_t n, double epsilon, double mdecay, double X_N, int burn_in) {
-    if (!theta || !grad || !xi || !g || !g2 || !p || !noise || n < 0 || !(X_N > 0.0))
-        return set_error(nullptr, FFVD_EINVAL, "ffvd_op_sghmc_step: bad argument");
-    OP_BEGIN("ffvd_op_sghmc_step");
-    if (n == 0) return FFVD_OK;
-    double *dth = sc.upload(theta, n), *dxi = sc.upload(xi, n), *dg_ = sc.upload(g, n), *dg2 = sc.upload(g2, n);
-    double *dp = sc.upload(p, n);
-    const double *dgrad = sc.upload(grad, n), *dnoise = sc.upload(noise, n);
-    if (!dth || !dxi || !dg_ || !dg2 || !dp || !dgrad || !dnoise)
-        return set_error(nullptr, FFVD_ENOMEM, "ffvd_op_sghmc_step: device allocation or upload failed");
-    OptTable tab{};
-    tab.count = 1;
-    OptTensor &t = tab.t[0];
-    t.theta = dth; t.grad = dgrad; t.s0 = dxi; t.s1 = dg_; t.s2 = dg2; t.s3 = dp; t.noise = dnoise; t.n = n;
-    launch_sghmc(sc.stream, tab, epsilon, mdecay, X_N, burn_in);
-    HIP_TRY(hipMemcpyAsync(theta, dth, n * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
-    HIP_TRY(hipMemcpyAsync(p, dp, n * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
-    if (burn_in) {
-        HIP_TRY(hipMemcpyAsync(xi, dxi, n * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
-        HIP_TRY(hipMemcpyAsync(g, dg_, n * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
-        HIP_TRY(hipMemcpyAsync(g2, dg2, n * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
-    }
-    HIP_TRY(hipStreamSynchronize(sc.stream));
-    return FFVD_OK;
-}
-
-extern "C" int ffvd_op_rollout_fallbacks(void) { return g_rollout_fallbacks; }
-
-extern "C" int ffvd_op_rollout(int kind, const double *Lm_inverse_seq, const double *Z, int M, int P, int D,
-                               const double *logvariance, const double *loglengthscales, const double *f,
-                               const double *q_sqrt, const double *x_last, int R, const double *ctrl, int C, int steps,
-                               const double *log_Q, const double *eps, double *predict_x, double *predict_var) {
-    if (!Lm_inverse_seq || !Z || !logvariance || !f || !x_last || !log_Q || !eps || !predict_x || !predict_var || R < 1 ||
-        steps < 0 || M < 1 || M > 2048 || D < 1 || C < 0 || P != D + C || P > MAXP || (C > 0 && !ctrl) ||
-        (kind == FFVD_KERNEL_SE && !loglengthscales))
-        return set_error(nullptr, FFVD_EINVAL, "ffvd_op_rollout: bad argument");
-    OP_BEGIN("ffvd_op_rollout");
-    if (steps == 0) return FFVD_OK;
-    // K_fu rows once per step, then the triangular projection GEMM with fvar / fmean in its epilogue (one workgroup
-    // per 128-column tile and dim): 16 workgroups instead of the 4 of the fused projection kernel, whose single
-    // workgroup per dim made a step compute-bound on one CU
-    const int Mp = round_up(M, NB), Tp = round_up(R, STRIP), ng = (Mp + 127) / 128;
-    std::vector<double> Wp;
-    std::vector<double> xc0((size_t)R * P);
-    for (int r = 0; r < R; ++r) {
-        for (int d = 0; d < D; ++d) xc0[(size_t)r * P + d] = x_last[d];              // x_t = X[-1] (:226), every rollout
-        for (int c = 0; c < C; ++c) xc0[(size_t)r * P + D + c] = ctrl[c];            // control row of step 0 (:293)
-    }
-    double *dW = upload_stack(sc, Lm_inverse_seq, D, M, Mp, Wp);
-    double *dxc = sc.upload(xc0.data(), xc0.size()), *dZ = sc.upload(Z, (size_t)M * P), *dU = sc.upload(f, (size_t)M * D);
-    double *dxc2 = sc.alloc<double>(xc0.size());          // the rows of step t + 1 (the step kernel reads one buffer and writes the other)
-    double *dlv = sc.upload(logvariance, D), *dll = sc.alloc<double>((size_t)D * P), *dlq = sc.upload(log_Q, D);
-    double *deps = sc.upload(eps, (size_t)steps * R * D);
-    double *dctrl = C ? sc.upload(ctrl, (size_t)steps * C) : nullptr;
-    double *variance = sc.alloc<double>(D), *len = sc.alloc<double>((size_t)D * P);
-    double *Zs = sc.alloc<double>((size_t)D * Mp * P), *zz = sc.alloc<double>((size_t)D * Mp);
-    double *F = q_sqrt ? sc.alloc<double>((size_t)D * Tp * Mp) : nullptr;
-    double *Kf = sc.alloc<double>((size_t)D * Tp * Mp), *ucol = sc.alloc<double>((size_t)D * Mp);
-    // few rows per step (R rollouts): the skinny product (kernels.hip) with one partial sum per 16-column slab replaces the
-    // 128 x 128-tile projection GEMM (50 -> 7 us per step) and the per-row q_sqrt kernel (37 us)
-    const bool skinny = R <= 512;
-    const int ngs = skinny ? Mp / 16 : ng;
-    double *rowsq = sc.alloc<double>((size_t)D * ngs * Tp), *fmean = sc.alloc<double>((size_t)D * ngs * Tp);
-    double *dmean = sc.alloc<double>((size_t)R * D), *dvar = sc.alloc<double>((size_t)R * D);
-    double *dpx = sc.alloc<double>((size_t)R * steps * D), *dpv = sc.alloc<double>((size_t)R * steps * D);
-    std::vector<double> Qp;
-    // W = L^-T is upper triangular; when q_sqrt (slice 0) is too -- the reference hands over L_H^-T -- so is W q_sqrt, and the second
-    // right-hand side of a step's product stops at a slab's last row like the first (exact zeros are skipped: half of its k range)
-    int q_upper = 0;
-    if (q_sqrt && skinny) {
-        q_upper = 1;
-        for (int i = 1; i < M && q_upper; ++i)
-            for (int j = 0; j < i; ++j)
-                if (q_sqrt[(size_t)i * M + j] != 0.0) { q_upper = 0; break; }
-    }
-    double *dQs = q_sqrt ? (skinny ? upload_stack(sc, q_sqrt, 1, M, Mp, Qp) /* (F is zero in the padded columns) */ : sc.upload(q_sqrt, (size_t)M * M)) : nullptr;   // slice d = 0 only
-    double *extra = q_sqrt ? sc.alloc<double>((size_t)D * (skinny ? ngs : 1) * Tp) : nullptr;
-    // skinny path: W q_sqrt once per call (D products of M^3), so that the inflation term is a second right-hand side of the
-    // step's one product instead of a dependent product on F
-    double *dWQ = (q_sqrt && skinny) ? sc.alloc<double>((size_t)D * Mp * Mp) : nullptr;
-    if (!dW || !dxc || !dxc2 || !dZ || !dU || !dlv || !dll || !dlq || !deps || (C && !dctrl) || !variance || !len || !Zs || !zz ||
-        !rowsq || !fmean || !dmean || !dvar || !dpx || !dpv || !Kf || !ucol || (q_sqrt && (!dQs || !extra || !F)) || (q_sqrt && skinny && !dWQ))
-        return set_error(nullptr, FFVD_ENOMEM, "ffvd_op_rollout: device allocation or upload failed");
-    if (loglengthscales)
-        HIP_TRY(hipMemcpyAsync(dll, loglengthscales, (size_t)D * P * sizeof(double), hipMemcpyHostToDevice, sc.stream));
-    launch_prep_hypers(sc.stream, kind, dZ, M, Mp, P, D, 0, dlv, dll, variance, len, Zs, zz);
-    HyperView hv{variance, len, Zs, zz};
-    ProjectArgs pa{};
-    pa.kind = kind; pa.x = dxc; pa.x_chain_stride = 0; pa.x_ld = P; pa.x_cols = P; pa.ctrl = nullptr;
-    pa.T = R; pa.Tp = Tp; pa.C = 0; pa.P = P; pa.M = M; pa.Mp = Mp; pa.Dl = D; pa.d_begin = 0; pa.hv = hv;
-    pa.W = dW; pa.w_stride = (size_t)Mp * Mp; pa.U = dU; pa.u_ld = D; pa.b0 = 0; pa.nb = D;
-    pa.F = Kf; pa.rowsq = rowsq; pa.fmean = fmean; pa.ng = ng;
-    launch_ucols(sc.stream, dU, M, Mp, D, 0, D, ucol);
-    ProjGemmArgs pg{};
-    pg.Kf = Kf; pg.kf_stride = (size_t)Tp * Mp; pg.W = dW; pg.w_stride = (size_t)Mp * Mp; pg.F = F; pg.f_stride = (size_t)Tp * Mp;
-    pg.rowsq = rowsq; pg.fmean = fmean; pg.u = ucol; pg.u_stride = Mp; pg.Tp = Tp; pg.Mp = Mp; pg.Dl = D; pg.b0 = 0; pg.nb = D;
-    // the whole loop is enqueued at once: steps x (K_fu rows, projection, [q_sqrt inflation], conditional, update)
-    if (dWQ)
-        launch_skinny_gemm(sc.stream, dW, (size_t)Mp * Mp, Mp, dQs, 0, Mp, 0, Mp, Mp, Mp, D, Mp, dWQ, (size_t)Mp * Mp, Mp, nullptr, 0,
-                           nullptr, nullptr);
-    double *xbuf[2] = {dxc, dxc2};                                           // input rows of step t in xbuf[t & 1]
-    auto step_launches = [&]() {                                              // three dependent launches per step
-        for (int t = 0; t < steps; ++t) {
-            pa.x = xbuf[t & 1];
-            if (skinny) {
-                launch_kfu_build_t(sc.stream, pa, Tp);                               // K(x_t, Z) per dim, m-major (coalesced operand loads)
-                // conditional_after_kernel_precalculation (:300) and, in the same launch, sum_j (F q_sqrt)_j^2 = |K (W q_sqrt)|^2 (:371-380)
-                launch_skinny_gemm(sc.stream, Kf, (size_t)Tp * Mp, Tp, dW, (size_t)Mp * Mp, Mp, 1, R, Mp, Mp, D, Tp,
-                                   nullptr, 0, 0, ucol, Mp, rowsq, fmean, q_sqrt ? dWQ : nullptr, (size_t)Mp * Mp, Mp, Mp, extra, 1, q_upper);
-            } else {
-                launch_kfu_build(sc.stream, pa);                                     // K(x_t, Z) per dim
-                launch_proj_gemm(sc.stream, pg);
-                if (q_sqrt) launch_qsqrt_inflation(sc.stream, F, (size_t)Tp * Mp, Tp, Mp, M, dQs, extra, R, D);
-            }
-            // conditional epilogue + x <- x + f_mu + eps sqrt(f_var + Q) in one launch (three dependent launches per step instead of five)
-            launch_rollout_finish_update(sc.stream, kind, variance, rowsq, fmean, skinny ? ngs : ng, Tp, extra, skinny ? ngs : 1, dlq,
-                                         deps + (size_t)t * R * D, (C && t + 1 < steps) ? dctrl + (size_t)(t + 1) * C : nullptr, R, D, C, t,
-                                         steps, xbuf[t & 1], xbuf[(t + 1) & 1], dpx, dpv);
-        }
-    };
-    // Round 4: the whole loop as ONE persistent launch (loops.hip; the same kernel bodies: bit-identical) -- first
-    // with a grid-wide barrier between the phases (64.7 against 32.7 us per step at 32 rollouts: 160-512 workgroups on one counter),
-    // then with one role per workgroup and per-unit counters (40.3 against 36.0; 93 against 57 at 100 rollouts).  MEASURED SLOWER both
-    // times: ~170 agent-scope releases / acquires per step cost more than the three kernel boundaries they replace -- so it is opt-in:
-    // FFVD_STEP_LOOP=1.
-    const char *nsl = getenv("FFVD_STEP_LOOP");
-    const int loop_mode = (nsl && *nsl) ? atoi(nsl) : -1;
-    // Third form (loops.hip, rollout_resident_kernel; FFVD_STEP_LOOP=2): L^-T and W q_sqrt stay in LDS for the whole loop, three hand-offs
-    // per step.  Measured as the slope between 200 and 800 steps at M = 512, D = 4 (tools/rollout_modes.py): 16.6-19.2 us per step at 16
-    // rollouts, 19.3-23.9 at 32, 27-50 at 64 against 19.6-20.8 / 20.1-20.6 / 20.5-25.7 for the launches -- a hand-off among 32 workgroups
-    // costs 4-5 us here (release 2, wait + acquire 2.5-3: FFVD_RR_STAMPS=1), three of them are what three kernel boundaries cost.
-    // (Second measurement, with the hand-offs rebuilt without cache maintenance -- write-through stores and sc1 loads instead of fences, as in
-    //  the Gram kernel's tail exchange: 10.1-11.8 us per step at 16 rollouts, 13.6-17.9 at 32, 20.5-27 at 64.  The default up to 32 rollouts.)
-    // (Third measurement, the products' MFMA section branch-free per chunk: 10.4-12.5 / 12.5-15.4 / 17.9-22.5 us per step.  The default
-    //  wherever it applies: up to 64 rollouts, M <= 512, 8 latent dims.)
-    // (Round 5: with K^T operands, the XCD-mapped grid and long / short slabs paired per CU the per-step launches take 15.4-15.6 us
-    //  (18.4-21.8 with q_sqrt) from 40 to 64 rollouts, the resident loop 16.6-18.6 (20.3-23.4); at 32: 15.0 / 16.6 against 12.7 / 14.9,
-    //  profiles/r05_rollout_modes.txt -- the resident loop is the default up to 32 rollouts, FFVD_STEP_LOOP=2 asks for it up to 64.)
-    const bool resident = skinny && rollout_resident_ok(R, D, P, Mp) && (loop_mode == 2 || (loop_mode < 0 && R <= 32));
-    const bool use_loop = skinny && loop_mode == 1;
-    bool resident_done = false;
-    if (resident) {
-        const int RT = (R + 15) / 16, RP = 16 * RT, NS = Mp / 16;
-        int32_t *words = sc.alloc<int32_t>(rollout_resident_words());
-        double *Kt = sc.alloc<double>((size_t)D * Mp * RP), *part = sc.alloc<double>((size_t)D * NS * RP * 4);
-        double *xb = sc.alloc<double>((size_t)2 * RP * D), *dxl = sc.upload(x_last, D);
-        OP_CHECK(words && Kt && part && xb && dxl, "ffvd_op_rollout");
-        HIP_TRY(hipMemsetAsync(words, 0, (size_t)rollout_resident_words() * sizeof(int32_t), sc.stream));
-        RolloutResidentArgs ra{};
-        ra.kind = kind; ra.R = R; ra.RT = RT; ra.D = D; ra.C = C; ra.P = P; ra.M = M; ra.Mp = Mp; ra.steps = steps; ra.NS = NS;
-        ra.hv = hv; ra.W = dW; ra.w_stride = (size_t)Mp * Mp; ra.WQ = q_sqrt ? dWQ : nullptr; ra.wq_upper = q_sqrt ? q_upper : 0; ra.ucol = ucol;
-        ra.log_Q = dlq; ra.eps = deps; ra.ctrl = dctrl; ra.x_last = dxl; ra.Kt = Kt; ra.part = part; ra.xbuf = xb;
-        ra.predict_x = dpx; ra.predict_var = dpv; ra.words = words; ra.abort_w = words + 1;
-        long long *dst = nullptr;
-        if (getenv("FFVD_RR_STAMPS")) { dst = sc.alloc<long long>(32); if (dst) HIP_TRY(hipMemsetAsync(dst, 0, 32 * sizeof(long long), sc.stream)); }
-        ra.stamps = dst;
-        ra.test_stall = getenv("FFVD_RR_TEST_STALL") ? 1 : 0;
-        const int lrc = launch_rollout_resident(sc.stream, ra);
-        if (lrc == 0) {
-            int32_t hw[4] = {0, 0, 0, 0};
-            HIP_TRY(hipMemcpyAsync(hw, words, sizeof hw, hipMemcpyDeviceToHost, sc.stream));
-            HIP_TRY(hipStreamSynchronize(sc.stream));
-            resident_done = hw[1] == 0;          // (a wait gave up: the per-step launches below, from the initial rows)
-            if (!resident_done) {
-                // the two forms agree to 1e-9, not bit for bit, so a fallback decided by run-time contention must not be
-                // silent -- counted (ffvd_op_rollout_fallbacks) and left as a warning for ffvd_last_error(NULL)
-                ++g_rollout_fallbacks;
-                g_last_error = "warning: ffvd_op_rollout: the resident-operand loop gave up on a bounded wait (its workgroups were not all "
-                               "resident: another tenant on the GPU?); the call was completed by the per-step launches, whose results "
-                               "agree to 1e-9 but are not bit-identical (FFVD_STEP_LOOP=0 selects them always)";
-            }
-            if (dst && steps > 10) {             // tools: where step 10 spent its time (us since its start), slab 0 (the updater) and the last slab of dim 0
-                long long hs[32];
-                HIP_TRY(hipMemcpy(hs, dst, sizeof hs, hipMemcpyDeviceToHost));
-                static const char *nm[12] = {"start", "x_t seen", "inputs staged", "K stored", "K counted", "all K seen", "products", "partials stored",
-                                             "partials counted", "all partials seen", "updated", "x counted"};
-                for (int w = 0; w < 2; ++w) {
-                    fprintf(stderr, "rollout_resident R=%d q=%d slab %s:", R, q_sqrt ? 1 : 0, w ? "last" : "0");
-                    for (int i = 1; i < 12; ++i) if (hs[16 * w + i]) fprintf(stderr, "  %s %.2f", nm[i], (double)(hs[16 * w + i] - hs[16 * w]) / 100.0);
-                    fprintf(stderr, "\n");
-                }
-            }
-        } else (void)hipGetLastError();
-    }
-    if (resident_done) {
-    } else if (use_loop) {
-        const int nwords = loop_words(D);
-        int32_t *words = sc.alloc<int32_t>(nwords);
-        OP_CHECK(words, "ffvd_op_rollout");
-        HIP_TRY(hipMemsetAsync(words, 0, (size_t)nwords * sizeof(int32_t), sc.stream));
-        RolloutLoopArgs la{};
-        la.pa = pa;
-        la.sk = SkinnyArgs{Kf, (size_t)Tp * Mp, Mp, dW, (size_t)Mp * Mp, Mp, 1, R, Mp, Mp, D, Tp, nullptr, 0, 0, ucol, (size_t)Mp, rowsq, fmean,
-                           q_sqrt ? dWQ : nullptr, (size_t)Mp * Mp, Mp, q_sqrt ? Mp : 0, extra, 0, q_sqrt ? q_upper : 0};
-        la.f = FinishIn{kind, D + C, ngs, Tp, D, ngs, variance, rowsq, fmean, extra};
-        la.log_Q = dlq; la.eps = deps; la.ctrl = dctrl; la.R = R; la.C = C; la.steps = steps;
-        la.xbuf0 = xbuf[0]; la.xbuf1 = xbuf[1]; la.predict_x = dpx; la.predict_var = dpv;
-        la.bar = reinterpret_cast<unsigned *>(words); la.abort_w = words + 1;
-        launch_rollout_loop(sc.stream, la);
-        int32_t hw[4] = {0, 0, 0, 0};
-        HIP_TRY(hipMemcpyAsync(hw, words, sizeof hw, hipMemcpyDeviceToHost, sc.stream));
-        HIP_TRY(hipStreamSynchronize(sc.stream));
-        if (hw[1] != 0) {           // a wait gave up (the grid was not resident at once): the per-step launches, from the initial rows
-            HIP_TRY(hipMemcpyAsync(dxc, xc0.data(), xc0.size() * sizeof(double), hipMemcpyHostToDevice, sc.stream));
-            step_launches();
-        }
-    } else step_launches();
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(predict_x, dpx, (size_t)R * steps * D * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
-    HIP_TRY(hipMemcpyAsync(predict_var, dpv, (size_t)R * steps * D * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
-    HIP_TRY(hipStreamSynchronize(sc.stream));
-    return FFVD_OK;
-}
-
-// G posteriors, one launch per step for all of them (rollout_group.hip)
-extern "C" int ffvd_op_rollout_grouped(int kind, int G, const double *const *Lm_inverse_seqs, const double *Zs, int M, int P, int D,
-                                       const double *logvariances, const double *loglengthscales, const double *fs,
-                                       const double *const *q_sqrts, const double *x_lasts, int R, const double *ctrl, int C, int steps,
-                                       const double *log_Qs, const double *eps, double *predict_x, double *predict_var) {
-    const char *bad = "ffvd_op_rollout_grouped: bad argument";
-    if ((kind != FFVD_KERNEL_SE && kind != FFVD_KERNEL_LINEAR) || G < 0 || R < 1 || steps < 0 || M < 1 || M > 2048 || D < 1 || C < 0 ||
-        P != D + C || P > MAXP)
-        return set_error(nullptr, FFVD_EINVAL, bad);
-    const int Mp = round_up(M, RG_SLAB), NS = Mp / RG_SLAB;
-    if ((long long)G * D * Mp * Mp > (1LL << 29) || (long long)G * R > (1LL << 20) || (R + RG_RC - 1) / RG_RC > 65535 ||
-        (long long)G * D * NS >= (1LL << 31))
-        return set_error(nullptr, FFVD_EINVAL, "ffvd_op_rollout_grouped: bad argument (beyond the limits of rollout_group.h)");
-    if (G == 0 || steps == 0) return FFVD_OK;
-    if (!Lm_inverse_seqs || !Zs || !logvariances || !fs || !x_lasts || !log_Qs || !eps || !predict_x || !predict_var ||
-        (C > 0 && !ctrl) || (kind == FFVD_KERNEL_SE && !loglengthscales))
-        return set_error(nullptr, FFVD_EINVAL, bad);
-    const size_t GD = (size_t)G * D, out_n = (size_t)G * R * steps * D;
-    for (size_t b = 0; b < GD; ++b) if (!Lm_inverse_seqs[b]) return set_error(nullptr, FFVD_EINVAL, bad);
-    if (q_sqrts)
-        for (int g = 0; g < G; ++g) if (!q_sqrts[g]) return set_error(nullptr, FFVD_EINVAL, bad);
-    OP_BEGIN("ffvd_op_rollout_grouped");
-    // FFVD_RG_TIMING=1 (tools): where the call spends its wall time (the stream is synchronised at every lap, so the call is slower)
-    const bool timing = getenv("FFVD_RG_TIMING") != nullptr;
-    auto t_last = std::chrono::steady_clock::now();
-    auto lap = [&](const char *what) {
-        if (!timing) return;
-        (void)hipStreamSynchronize(sc.stream);
-        const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "ffvd_op_rollout_grouped:   %-28s %.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
-        t_last = now;
-    };
-    // The big operands are NOT packed on the host: every M x M matrix goes from where the caller keeps it straight into its slot of the
-    // padded device stack (a pitched copy when M is not a multiple of 16; the padding is zeroed on the device).
-    auto upload_matrices = [&](const double *const *src, size_t n) -> double * {
-        double *dst = sc.alloc<double>(n * Mp * Mp);
-        if (!dst) return nullptr;
-        if (Mp != M && hipMemsetAsync(dst, 0, n * Mp * Mp * sizeof(double), sc.stream) != hipSuccess) return nullptr;
-        for (size_t b = 0; b < n; ++b) {
-            const hipError_t e = (Mp == M)
-                ? hipMemcpyAsync(dst + b * Mp * Mp, src[b], (size_t)M * M * sizeof(double), hipMemcpyHostToDevice, sc.stream)
-                : hipMemcpy2DAsync(dst + b * Mp * Mp, (size_t)Mp * sizeof(double), src[b], (size_t)M * sizeof(double),
-                                   (size_t)M * sizeof(double), M, hipMemcpyHostToDevice, sc.stream);
-            if (e != hipSuccess) return nullptr;
-        }
-        return dst;
-    };
-    double *dW = upload_matrices(Lm_inverse_seqs, GD);
-    lap("W uploaded");
-    // W q_sqrt is upper triangular when every group's q_sqrt slice is (the reference hands over L_H^-T): the step products then stop at
-    // a slab's last row for both right-hand sides.  Otherwise they walk all rows; for a group whose slice IS upper triangular the extra
-    // terms are exact zeros, so its results do not depend on what the other groups hold.
-    int q_upper = q_sqrts ? 1 : 0;
-    for (int g = 0; q_upper && g < G; ++g)
-        for (int i = 1; i < M && q_upper; ++i)
-            for (int j = 0; j < i; ++j)
-                if (q_sqrts[g][(size_t)i * M + j] != 0.0) { q_upper = 0; break; }
-    lap("q_sqrt scanned");
-    double *dq = q_sqrts ? upload_matrices(q_sqrts, (size_t)G) : nullptr;
-    double *dB = q_sqrts ? sc.alloc<double>(GD * Mp * Mp) : nullptr;
-    double *dZ = sc.upload(Zs, (size_t)G * M * P), *dU = sc.upload(fs, (size_t)G * M * D), *dxl = sc.upload(x_lasts, GD);
-    double *dlv = sc.upload(logvariances, GD), *dll = loglengthscales ? sc.upload(loglengthscales, GD * P) : nullptr;
-    double *dlq = sc.upload(log_Qs, GD), *deps = sc.upload(eps, (size_t)steps * G * R * D);
-    double *dctrl = C ? sc.upload(ctrl, (size_t)steps * C) : nullptr;
-    double *variance = sc.alloc<double>(GD), *len = sc.alloc<double>(GD * P), *Zsc = sc.alloc<double>(GD * Mp * P), *zz = sc.alloc<double>(GD * Mp);
-    double *part = sc.alloc<double>((size_t)2 * GD * NS * R * 4), *xbuf = sc.alloc<double>((size_t)2 * G * R * D);
-    double *dpx = sc.alloc<double>(out_n), *dpv = sc.alloc<double>(out_n);
-    OP_CHECK(dW && dZ && dU && dxl && dlv && dlq && deps && (!C || dctrl) && (!loglengthscales || dll) && variance && len && Zsc && zz &&
-             part && xbuf && dpx && dpv && (!q_sqrts || (dq && dB)), "ffvd_op_rollout_grouped");
-    lap("q_sqrt, small arrays uploaded");
-    launch_rg_prep(sc.stream, kind, G, D, M, Mp, P, dZ, dlv, dll, variance, len, Zsc, zz);
-    if (q_sqrts) launch_rg_wq(sc.stream, G, D, Mp, q_upper, dW, dq, dB);
-    lap("hyper-parameters, W q_sqrt");
-    RolloutGroupArgs a{};
-    a.kind = kind; a.G = G; a.R = R; a.D = D; a.C = C; a.P = P; a.M = M; a.Mp = Mp; a.NS = NS; a.steps = steps;
-    a.has_q = q_sqrts ? 1 : 0; a.q_upper = q_upper;
-    a.W = dW; a.B = dB; a.Zs = Zsc; a.zz = zz; a.variance = variance; a.len = len; a.f = dU; a.x_last = dxl; a.log_Q = dlq;
-    a.ctrl = dctrl; a.eps = deps; a.part = part; a.xbuf = xbuf; a.predict_x = dpx; a.predict_var = dpv;
-    for (int t = 0; t <= steps; ++t) launch_rg_step(sc.stream, a, t);
-    HIP_TRY(hipGetLastError());
-    lap("step launches");
-    if (!sc.download(predict_x, dpx, out_n * sizeof(double)) || !sc.download(predict_var, dpv, out_n * sizeof(double)))
-        return set_error(nullptr, FFVD_EDEVICE, "ffvd_op_rollout_grouped: copying the results back failed");
-    lap("results downloaded");
-    return FFVD_OK;
-}
-
-extern "C" int ffvd_op_pg_sweep(int kind, const double *Lm_inverse_seq, const double *Z, int M, int P, int D,
-                                const double *logvariance, const double *loglengthscales, const double *U,
-                                const double *X_ref, int X_N, const double *Y, int Ydim, const double *ctrl, int C,
-                                const double *CC, const double *DD, const double *Rchols, const double *log_Q, int n_free,
-                                const double *x0, const double *eps, const double *unif, double *particles, int32_t *idx) {
-    if (!Lm_inverse_seq || !Z || !logvariance || !U || !X_ref || !Y || !CC || !DD || !Rchols || !log_Q || !x0 || !eps ||
-        !unif || !particles || !idx || n_free < 1 || n_free + 1 > 1024 || X_N < 1 || M < 1 || M > 2048 || D < 1 || C < 0 ||
-        P != D + C || P > MAXP || Ydim < 1 || Ydim > 8 || (C > 0 && !ctrl) || (kind == FFVD_KERNEL_SE && !loglengthscales))
-        return set_error(nullptr, FFVD_EINVAL, "ffvd_op_pg_sweep: bad argument");
-    for (int j = 0; j < Ydim; ++j)
-        if (!(Rchols[(size_t)j * Ydim + j] > 0.0)) return set_error(nullptr, FFVD_EINVAL, "ffvd_op_pg_sweep: Rchols diagonal must be positive");
-    OP_BEGIN("ffvd_op_pg_sweep");
-    const auto t_begin = std::chrono::steady_clock::now();
-    const int R = n_free, steps = X_N - 1;
-    memcpy(particles, x0, (size_t)R * D * sizeof(double));                                   // particles[0] (:87)
-    if (steps == 0) return FFVD_OK;
-    const int Mp = round_up(M, NB), Tp = round_up(R, STRIP), ng = (Mp + 127) / 128;
-    std::vector<double> Wp;
-    std::vector<double> xc0((size_t)R * P);
-    for (int r = 0; r < R; ++r) {
-        for (int d = 0; d < D; ++d) xc0[(size_t)r * P + d] = x0[(size_t)r * D + d];
-        for (int c = 0; c < C; ++c) xc0[(size_t)r * P + D + c] = ctrl[c];                     // control row of step 0 (:93)
-    }
-    const bool pg_timing = getenv("FFVD_PG_TIMING") != nullptr;
-    auto lap = [&](const char *what) {
-        if (pg_timing) fprintf(stderr, "ffvd_op_pg_sweep:   %s at %.2f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
-    };
-    lap("begin");
-    double *dW = upload_stack(sc, Lm_inverse_seq, D, M, Mp, Wp);
-    lap("L^-T uploaded");
-    double *dxc = sc.upload(xc0.data(), xc0.size()), *dZ = sc.upload(Z, (size_t)M * P), *dU = sc.upload(U, (size_t)M * D);
-    double *dlv = sc.upload(logvariance, D), *dll = sc.alloc<double>((size_t)D * P), *dlq = sc.upload(log_Q, D);
-    double *deps = sc.upload(eps, (size_t)steps * R * D), *dun = sc.upload(unif, (size_t)steps * R);
-    lap("draws uploaded");
-    double *dctrl = C ? sc.upload(ctrl, (size_t)steps * C) : nullptr;
-    double *dXr = sc.upload(X_ref, (size_t)X_N * D), *dY = sc.upload(Y, (size_t)steps * Ydim);
-    double *dCC = sc.upload(CC, (size_t)D * Ydim), *dDD = sc.upload(DD, Ydim), *dR = sc.upload(Rchols, (size_t)Ydim * Ydim);
-    double *variance = sc.alloc<double>(D), *len = sc.alloc<double>((size_t)D * P);
-    double *Zs = sc.alloc<double>((size_t)D * Mp * P), *zz = sc.alloc<double>((size_t)D * Mp);
-    double *Kf = sc.alloc<double>((size_t)D * Tp * Mp), *ucol = sc.alloc<double>((size_t)D * Mp);
-    const bool skinny = R <= 512;                       // see ffvd_op_rollout
-    const int ngs = skinny ? Mp / 16 : ng;
-    double *rowsq = sc.alloc<double>((size_t)D * ngs * Tp), *fmean = sc.alloc<double>((size_t)D * ngs * Tp);
-    double *dmean = sc.alloc<double>((size_t)R * D), *dvar = sc.alloc<double>((size_t)R * D);
-    double *cand = sc.alloc<double>((size_t)(R + 1) * D);
-    double *dparts = sc.alloc<double>((size_t)steps * R * D);
-    int32_t *didx = sc.alloc<int32_t>((size_t)steps * R);
-    lap("temporaries allocated");
-    if (!dW || !dxc || !dZ || !dU || !dlv || !dll || !dlq || !deps || !dun || (C && !dctrl) || !dXr || !dY || !dCC || !dDD ||
-        !dR || !variance || !len || !Zs || !zz || !Kf || !ucol || !rowsq || !fmean || !dmean || !dvar || !cand || !dparts || !didx)
-        return set_error(nullptr, FFVD_ENOMEM, "ffvd_op_pg_sweep: device allocation or upload failed");
-    if (loglengthscales)
-        HIP_TRY(hipMemcpyAsync(dll, loglengthscales, (size_t)D * P * sizeof(double), hipMemcpyHostToDevice, sc.stream));
-    launch_prep_hypers(sc.stream, kind, dZ, M, Mp, P, D, 0, dlv, dll, variance, len, Zs, zz);
-    HyperView hv{variance, len, Zs, zz};
-    ProjectArgs pa{};
-    pa.kind = kind; pa.x = dxc; pa.x_chain_stride = 0; pa.x_ld = P; pa.x_cols = P; pa.ctrl = nullptr;
-    pa.T = R; pa.Tp = Tp; pa.C = 0; pa.P = P; pa.M = M; pa.Mp = Mp; pa.Dl = D; pa.d_begin = 0; pa.hv = hv;
-    pa.W = dW; pa.w_stride = (size_t)Mp * Mp; pa.U = dU; pa.u_ld = D; pa.b0 = 0; pa.nb = D;
-    pa.F = Kf; pa.rowsq = rowsq; pa.fmean = fmean; pa.ng = ng;
-    launch_ucols(sc.stream, dU, M, Mp, D, 0, D, ucol);
-    ProjGemmArgs pg{};
-    pg.Kf = Kf; pg.kf_stride = (size_t)Tp * Mp; pg.W = dW; pg.w_stride = (size_t)Mp * Mp; pg.F = nullptr; pg.f_stride = 0;
-    pg.rowsq = rowsq; pg.fmean = fmean; pg.u = ucol; pg.u_stride = Mp; pg.Tp = Tp; pg.Mp = Mp; pg.Dl = D; pg.b0 = 0; pg.nb = D;
-    // the whole sweep is enqueued at once: steps x (K_fu rows, projection, conditional, propagate + weight + resample)
-    auto step_launches = [&]() {
-        for (int t = 0; t < steps; ++t) {
-            if (skinny) {                               // K(x_t, Z) m-major: the skinny product's operand loads coalesce
-                launch_kfu_build_t(sc.stream, pa, Tp);
-                launch_skinny_gemm(sc.stream, Kf, (size_t)Tp * Mp, Tp, dW, (size_t)Mp * Mp, Mp, 1, R, Mp, Mp, D, Tp,
-                                   nullptr, 0, 0, ucol, Mp, rowsq, fmean, nullptr, 0, 0, 0, nullptr, 1);
-            } else { launch_kfu_build(sc.stream, pa); launch_proj_gemm(sc.stream, pg); }                                // conditional_after_kernel_precalculation (:95-97)
-            const double *ctrl_next = (C && t + 1 < steps) ? dctrl + (size_t)(t + 1) * C : nullptr;
-            launch_conditional_finish(sc.stream, kind, dxc, R, P, variance, rowsq, fmean, ngs, Tp, D, dmean, dvar, nullptr);
-            launch_pg_step(sc.stream, dmean, dvar, dlq, deps + (size_t)t * R * D, dun + (size_t)t * R, dY + (size_t)t * Ydim,
-                           dXr + (size_t)(t + 1) * D, dCC, dDD, dR, ctrl_next,
-                           R, D, C, Ydim, dxc, cand, dparts + (size_t)t * R * D, didx + (size_t)t * R);
-        }
-    };
-    // Round 4: ONE persistent launch for the sweep (loops.hip), three grid-wide barriers per step instead of four dependent launches:
-    // measured slower (86 against 43 us per step with roles and per-unit counters, 151 with a grid-wide barrier; see ffvd_op_rollout), opt-in with FFVD_STEP_LOOP=1
-    const char *nsl = getenv("FFVD_STEP_LOOP");
-    const bool use_loop = skinny && nsl && *nsl && strcmp(nsl, "0") != 0;
-    if (use_loop) {
-        const int nwords = loop_words(D);
-        int32_t *words = sc.alloc<int32_t>(nwords);
-        OP_CHECK(words, "ffvd_op_pg_sweep");
-        HIP_TRY(hipMemsetAsync(words, 0, (size_t)nwords * sizeof(int32_t), sc.stream));
-        PgLoopArgs la{};
-        la.pa = pa;
-        la.sk = SkinnyArgs{Kf, (size_t)Tp * Mp, Mp, dW, (size_t)Mp * Mp, Mp, 1, R, Mp, Mp, D, Tp, nullptr, 0, 0, ucol, (size_t)Mp, rowsq, fmean,
-                           nullptr, 0, 0, 0, nullptr};
-        la.kind = kind; la.R = R; la.D = D; la.C = C; la.Ydim = Ydim; la.steps = steps; la.ngs = ngs;
-        la.variance = variance; la.rowsq = rowsq; la.fmean = fmean; la.mean = dmean; la.var = dvar; la.cand = cand; la.parts = dparts;
-        la.idx = didx; la.log_Q = dlq; la.eps = deps; la.unif = dun; la.Y = dY; la.X_ref = dXr; la.CC = dCC; la.DD = dDD; la.Rch = dR;
-        la.ctrl = dctrl; la.bar = reinterpret_cast<unsigned *>(words); la.abort_w = words + 1;
-        launch_pg_loop(sc.stream, la);
-        int32_t hw[4] = {0, 0, 0, 0};
-        HIP_TRY(hipMemcpyAsync(hw, words, sizeof hw, hipMemcpyDeviceToHost, sc.stream));
-        HIP_TRY(hipStreamSynchronize(sc.stream));
-        if (hw[1] != 0) {
-            HIP_TRY(hipMemcpyAsync(dxc, xc0.data(), xc0.size() * sizeof(double), hipMemcpyHostToDevice, sc.stream));
-            step_launches();
-        }
-    } else {
-        const bool timing = getenv("FFVD_PG_TIMING") != nullptr;          // debug: how long the host takes to enqueue the sweep
-        if (timing) {
-            hipStreamSynchronize(sc.stream);
-            fprintf(stderr, "ffvd_op_pg_sweep: uploads and set-up %.2f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
-        }
-        const auto t0 = std::chrono::steady_clock::now();
-        step_launches();
-        if (timing) {
-            const auto t1 = std::chrono::steady_clock::now();
-            hipStreamSynchronize(sc.stream);
-            const auto t2 = std::chrono::steady_clock::now();
-            fprintf(stderr, "ffvd_op_pg_sweep: %d steps enqueued in %.2f ms, drained %.2f ms later\n", steps,
-                    std::chrono::duration<double, std::milli>(t1 - t0).count(), std::chrono::duration<double, std::milli>(t2 - t1).count());
-        }
-    }
-    HIP_TRY(hipGetLastError());
-    const auto t_dl = std::chrono::steady_clock::now();
-    if (!sc.download(particles + (size_t)R * D, dparts, (size_t)steps * R * D * sizeof(double)) ||
-        !sc.download(idx, didx, (size_t)steps * R * sizeof(int32_t)))
-        return set_error(nullptr, FFVD_EDEVICE, "ffvd_op_pg_sweep: copying the results to the host failed");
-    if (getenv("FFVD_PG_TIMING"))
-        fprintf(stderr, "ffvd_op_pg_sweep: results to the host %.2f ms (after the sweep had drained)\n",
-                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_dl).count());
     return FFVD_OK;
 }
 

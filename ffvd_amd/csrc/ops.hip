@@ -1,0 +1,1196 @@
+// The stateless operator entry points of the C ABI (ffvd_op_*, include/ffvd_abi.h): what the Python mirror of the reference API
+// calls.  Temporaries per call, not the hot path.  Shares only abi_internal.h with abi.hip.
+#include "abi_internal.h"
+#include "kernels.h"
+#include "grad.h"
+#include "optim.h"
+#include "step_bodies.h"
+#include "rollout_group.h"
+
+#include <atomic>
+#include <chrono>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <deque>
+#include <string>
+#include <vector>
+
+using namespace ffvd;
+
+static std::atomic<int> g_rollout_fallbacks{0};     // ffvd_op_rollout calls of this process that fell back from the resident loop to the per-step launches
+
+// ---- operator-level entry points (temporaries per call; not the hot path) -------------------------------------------------------------
+// Round 5: the temporaries come from a per-thread cache instead of hipMalloc / hipFree / hipStreamCreate per call.  A rollout call made
+// ~27 allocations and as many frees around 200 steps of 15 us: 2.7 ms of host work per call (profiles/r04_next_rows.json: 27.6 us per
+// step of a 200-step call against 15.3 marginal).  A block is handed out again when its size fits (smallest block that is large enough
+// and at most 4 x the request); the cache is bounded (256 blocks / 8 GiB: beyond that everything idle is freed) and can be released
+// with ffvd_op_release_cache().  Nothing relies on fresh memory being zero (hipMalloc never promised that).
+namespace {
+struct OpCache {
+    struct Block { void *p; size_t bytes; bool busy; };
+    std::vector<Block> blocks;
+    size_t total = 0;
+    hipStream_t stream = nullptr;
+    int device = -1;
+    void *pinned = nullptr;             // page-locked staging block for large results (a device-to-host copy into fresh pageable memory
+    size_t pinned_bytes = 0;            //  pins its pages on the fly: 13 MB took up to 30 ms; through this block + memcpy: ~3)
+    void release_idle() {
+        std::vector<Block> keep;
+        for (Block &b : blocks) {
+            if (b.busy) keep.push_back(b);
+            else { hipFree(b.p); total -= b.bytes; }
+        }
+        blocks.swap(keep);
+    }
+    void release_all() {
+        release_idle();
+        if (stream && blocks.empty()) { hipStreamDestroy(stream); stream = nullptr; }
+        if (pinned) { hipHostFree(pinned); pinned = nullptr; pinned_bytes = 0; }
+    }
+    ~OpCache() { /* process exit: the runtime may already be gone; leave the memory to it */ }
+};
+thread_local OpCache g_op_cache;
+
+struct Scratch {
+    std::vector<size_t> mine;           // indices into the cache of the blocks this call holds
+    hipStream_t stream = nullptr;
+    // host staging buffers of this call (host()).  A member, so it outlives the destructor body: an asynchronous upload may read its
+    // source until the stream has been synchronised, on the early error returns as well.
+    std::deque<std::vector<double>> staged;
+    bool begin() {
+        OpCache &c = g_op_cache;
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess) return false;
+        if (c.device != dev) {           // (another device was made current on this thread: start over)
+            c.release_all();
+            c.device = dev;
+        }
+        if (!c.stream && hipStreamCreate(&c.stream) != hipSuccess) return false;
+        stream = c.stream;
+        return true;
+    }
+    ~Scratch() {
+        if (stream) hipStreamSynchronize(stream);
+        OpCache &c = g_op_cache;
+        for (size_t i : mine) c.blocks[i].busy = false;
+        if (c.blocks.size() > 256 || c.total > ((size_t)8 << 30)) c.release_idle();
+    }
+    // n doubles of host memory that live until the call's stream has drained: every source of an asynchronous upload that the
+    // operator builds itself comes from here
+    std::vector<double> &host(size_t n, double fill = 0.0) {
+        staged.emplace_back(n, fill);
+        return staged.back();
+    }
+    template <class T>
+    T *alloc(size_t n) {
+        OpCache &c = g_op_cache;
+        const size_t bytes = ((n ? n : 1) * sizeof(T) + 255) / 256 * 256;
+        size_t best = (size_t)-1;
+        for (size_t i = 0; i < c.blocks.size(); ++i) {
+            const OpCache::Block &b = c.blocks[i];
+            if (!b.busy && b.bytes >= bytes && b.bytes <= 4 * bytes && (best == (size_t)-1 || b.bytes < c.blocks[best].bytes)) best = i;
+        }
+        if (best == (size_t)-1) {
+            void *p = nullptr;
+            if (hipMalloc(&p, bytes) != hipSuccess) {
+                (void)hipGetLastError();
+                c.release_idle();                                   // make room and try once more
+                mine.clear();
+                for (size_t i = 0; i < c.blocks.size(); ++i) if (c.blocks[i].busy) mine.push_back(i);      // (indices moved; every busy block is this call's: one call per thread at a time)
+                if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+            }
+            c.blocks.push_back({p, bytes, false});
+            c.total += bytes;
+            best = c.blocks.size() - 1;
+        }
+        c.blocks[best].busy = true;
+        mine.push_back(best);
+        // FFVD_OP_CACHE_POISON=1 (tests): every block handed out starts as NaN bytes -- nothing may rely on what a block held before
+        static const bool poison = [] { const char *e = getenv("FFVD_OP_CACHE_POISON"); return e && *e && strcmp(e, "0") != 0; }();
+        if (poison && stream) (void)hipMemsetAsync(c.blocks[best].p, 0xFF, c.blocks[best].bytes, stream);
+        return (T *)c.blocks[best].p;
+    }
+    // device -> host for a large result: through the thread's page-locked block when it has (or gets) one of that size, else directly.
+    // Synchronises the stream.
+    bool download(void *dst, const void *src, size_t bytes) {
+        if (void *pin = pinned_block(bytes)) {
+            if (hipMemcpyAsync(pin, src, bytes, hipMemcpyDeviceToHost, stream) != hipSuccess) return false;
+            if (hipStreamSynchronize(stream) != hipSuccess) return false;
+            memcpy(dst, pin, bytes);
+            return true;
+        }
+        return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream) == hipSuccess && hipStreamSynchronize(stream) == hipSuccess;
+    }
+    // the thread's page-locked block, grown to `bytes` (nullptr when it cannot be had or the size is outside 1 MB .. 256 MB)
+    void *pinned_block(size_t bytes) {
+        OpCache &c = g_op_cache;
+        if (bytes < ((size_t)1 << 20) || bytes > ((size_t)256 << 20)) return nullptr;
+        if (c.pinned_bytes < bytes) {
+            if (c.pinned) { hipHostFree(c.pinned); c.pinned = nullptr; c.pinned_bytes = 0; }
+            if (hipHostMalloc(&c.pinned, bytes, hipHostMallocDefault) == hipSuccess) c.pinned_bytes = bytes;
+            else { (void)hipGetLastError(); c.pinned = nullptr; }
+        }
+        return c.pinned;
+    }
+    // host -> device, asynchronous, straight from the caller's memory.  (Measured: large uploads through the page-locked block + a
+    // synchronisation made a 200-step rollout call 0.4 ms slower and changed nothing for the sweep -- the 28 ms some calls spend here in
+    // tools/bench_next.py's process are a wait of the stream behind the 0.2 ms DMA, whichever memory it reads; FFVD_PG_TIMING=1 shows it.)
+    double *upload(const double *src, size_t n) {
+        double *d = alloc<double>(n);
+        if (d && n && hipMemcpyAsync(d, src, n * sizeof(double), hipMemcpyHostToDevice, stream) != hipSuccess) return nullptr;
+        return d;
+    }
+};
+
+// FFVD_PG_TIMING / FFVD_RG_TIMING (tools): where a call spends its wall time, one line per lap on stderr.  A lap waits for the stream
+// first (so a timed call is slower) unless told not to: the time the host needed to enqueue, then the time the GPU needed after that.
+struct LapTimer {
+    const char *who;
+    hipStream_t stream;
+    bool on;
+    std::chrono::steady_clock::time_point last;
+    LapTimer(const char *env, const char *who_, hipStream_t s) : who(who_), stream(s), on(getenv(env) != nullptr), last(std::chrono::steady_clock::now()) {}
+    void lap(const char *what, bool drain = true) {
+        if (!on) return;
+        if (drain) (void)hipStreamSynchronize(stream);
+        const auto now = std::chrono::steady_clock::now();
+        fprintf(stderr, "%s:   %-28s %.3f ms\n", who, what, std::chrono::duration<double, std::milli>(now - last).count());
+        last = now;
+    }
+};
+}  // namespace
+
+// Free what the calling thread's operator cache holds (device buffers of finished ffvd_op_* calls, their stream).
+extern "C" int ffvd_op_release_cache(void) {
+    g_op_cache.release_all();
+    return FFVD_OK;
+}
+
+#define OP_BEGIN(name)                                                                       \
+    Scratch sc;                                                                              \
+    if (!sc.begin())                                                                         \
+        return set_error(nullptr, FFVD_EDEVICE, name ": no usable HIP device / stream creation failed");
+#define OP_CHECK(ptr, name) \
+    if (!(ptr)) return set_error(nullptr, FFVD_ENOMEM, name ": device allocation or upload failed");
+
+// ---- set-up shared by the operators ------------------------------------------------------------------------------------------------
+// Device-side hyper-parameters of D kernels over the inducing inputs Z: uploads Z and logvariance, runs prep_hypers.  (LinearK has no
+// lengthscales: its loglen block is allocated and not written.)
+static int stage_hypers(Scratch &sc, const char *who, int kind, const double *Z, int M, int Mp, int P, int D, const double *logvariance,
+                        const double *loglengthscales, HyperView &hv) {
+    double *dZ = sc.upload(Z, (size_t)M * P), *dlogvar = sc.upload(logvariance, D);
+    double *loglen = sc.alloc<double>((size_t)D * P);
+    double *variance = sc.alloc<double>(D), *len = sc.alloc<double>((size_t)D * P);
+    double *Zs = sc.alloc<double>((size_t)D * Mp * P), *zz = sc.alloc<double>((size_t)D * Mp);
+    if (!dZ || !dlogvar || !loglen || !variance || !len || !Zs || !zz)
+        return set_error(nullptr, FFVD_ENOMEM, std::string(who) + ": device allocation or upload failed");
+    if (loglengthscales)
+        OP_TRY(hipMemcpyAsync(loglen, loglengthscales, (size_t)D * P * sizeof(double), hipMemcpyHostToDevice, sc.stream));
+    launch_prep_hypers(sc.stream, kind, dZ, M, Mp, P, D, 0, dlogvar, loglen, variance, len, Zs, zz);
+    hv = HyperView{variance, len, Zs, zz};
+    return FFVD_OK;
+}
+
+// Projection arguments of an operator: one chain, all D dims, GP inputs x (T rows of P columns, no separate control block).
+static ProjectArgs op_project_args(int kind, const HyperView &hv, const double *x, int T, int Tp, int P, int M, int Mp, int D,
+                                   const double *W, size_t w_stride, const double *U, double *F, double *rowsq, double *fmean, int ng) {
+    ProjectArgs pa{};
+    pa.kind = kind; pa.x = x; pa.x_chain_stride = 0; pa.x_ld = P; pa.x_cols = P; pa.ctrl = nullptr;
+    pa.T = T; pa.Tp = Tp; pa.C = 0; pa.P = P; pa.M = M; pa.Mp = Mp; pa.Dl = D; pa.d_begin = 0; pa.hv = hv;
+    pa.W = W; pa.w_stride = w_stride; pa.U = U; pa.u_ld = U ? D : 0; pa.b0 = 0; pa.nb = D; pa.F = F;
+    pa.rowsq = rowsq; pa.fmean = fmean; pa.ng = ng;
+    return pa;
+}
+
+// Host copy (an upload source: from sc.host) of `batch` n x n matrices, each padded to np x np with an identity block; diag_add is
+// added to the n live diagonal entries.
+static std::vector<double> &pad_identity(Scratch &sc, const double *src, int batch, int n, int np, double diag_add = 0.0) {
+    const size_t slab = (size_t)np * np;
+    std::vector<double> &out = sc.host(slab * batch);
+    for (int b = 0; b < batch; ++b) {
+        double *S = out.data() + slab * b;
+        for (int i = 0; i < np; ++i) {
+            if (i < n) {
+                memcpy(S + (size_t)i * np, src + ((size_t)b * n + i) * n, (size_t)n * sizeof(double));
+                if (diag_add != 0.0) S[(size_t)i * np + i] += diag_add;
+            } else S[(size_t)i * np + i] = 1.0;
+        }
+    }
+    return out;
+}
+
+// upload a caller-supplied stack of D M x M matrices padded to Mp (M a multiple of the block size: nothing to pad -- the caller's
+// array itself is uploaded)
+static double *upload_stack(Scratch &sc, const double *src, int D, int M, int Mp) {
+    if (M == Mp) return sc.upload(src, (size_t)D * M * M);
+    std::vector<double> &pad = pad_identity(sc, src, D, M, Mp);
+    return sc.upload(pad.data(), pad.size());
+}
+
+// FFVD_ENOTPD for matrix d of a batch whose Cholesky flag (1 + first bad pivot) is set
+static int chol_not_pd(const char *who, const std::string &what, int d, int32_t flag) {
+    return set_error(nullptr, FFVD_ENOTPD, std::string(who) + ": Cholesky of " + what + " failed: latent dim " + std::to_string(d) + ", pivot " +
+                                               std::to_string(flag - 1) + " is not positive");
+}
+// read the D Cholesky flags back (synchronises the stream, so every copy enqueued before has landed too)
+static int fetch_chol_info(Scratch &sc, const int32_t *dinfo, int D, const char *who, const char *what) {
+    std::vector<int32_t> hinfo(D, 0);
+    if (hipMemcpyAsync(hinfo.data(), dinfo, D * sizeof(int32_t), hipMemcpyDeviceToHost, sc.stream) != hipSuccess ||
+        hipStreamSynchronize(sc.stream) != hipSuccess)
+        return set_error(nullptr, FFVD_EDEVICE, std::string(who) + ": device error while reading Cholesky status");
+    for (int d = 0; d < D; ++d)
+        if (hinfo[d]) return chol_not_pd(who, what, d, hinfo[d]);
+    return FFVD_OK;
+}
+
+static void launch_skinny_gemm(hipStream_t stream, const SkinnyArgs &a) {
+    ffvd::launch_skinny_gemm(stream, a.A, a.a_stride, a.lda, a.B, a.b_stride, a.ldb, a.upper, a.rows, a.K, a.N, a.nb, a.Tp, a.C, a.c_stride,
+                             a.ldc, a.u, a.u_stride, a.sq, a.dot, a.B2, a.b2_stride, a.ldb2, a.N2, a.sq2, a.a_trans, a.upper2);
+}
+
+extern "C" int ffvd_op_kernel_matrix(int kind, const double *X, int N, const double *X2, int N2, int P,
+                                     double logvariance, const double *loglengthscales, double jitter, double *out) {
+    if (!X || !out || N < 0 || P < 1 || (X2 && N2 < 0) || (kind == FFVD_KERNEL_SE && !loglengthscales) ||
+        (kind != FFVD_KERNEL_SE && kind != FFVD_KERNEL_LINEAR))
+        return set_error(nullptr, FFVD_EINVAL, "ffvd_op_kernel_matrix: bad argument");
+    OP_BEGIN("ffvd_op_kernel_matrix");
+    const int same = (X2 == nullptr);
+    if (same) N2 = N;
+    if ((size_t)N * N2 == 0) return FFVD_OK;
+    double *dX = sc.upload(X, (size_t)N * P);
+    OP_CHECK(dX, "ffvd_op_kernel_matrix");
+    double *dX2 = same ? dX : sc.upload(X2, (size_t)N2 * P);
+    OP_CHECK(dX2, "ffvd_op_kernel_matrix");
+    double *dl = sc.alloc<double>(P);
+    OP_CHECK(dl, "ffvd_op_kernel_matrix");
+    if (loglengthscales) OP_TRY(hipMemcpyAsync(dl, loglengthscales, P * sizeof(double), hipMemcpyHostToDevice, sc.stream));
+    double *dO = sc.alloc<double>((size_t)N * N2);
+    OP_CHECK(dO, "ffvd_op_kernel_matrix");
+    launch_kernel_matrix(sc.stream, kind, dX, N, dX2, N2, P, logvariance, dl, jitter, same, dO);
+    OP_TRY(hipMemcpyAsync(out, dO, (size_t)N * N2 * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
+    OP_TRY(hipStreamSynchronize(sc.stream));
+    return FFVD_OK;
+}
+
+extern "C" int ffvd_op_kernel_diag(int kind, const double *X, int N, int P, double logvariance, double *out) {
+    if (!X || !out || N < 0 || P < 1) return set_error(nullptr, FFVD_EINVAL, "ffvd_op_kernel_diag: bad argument");
+    OP_BEGIN("ffvd_op_kernel_diag");
+    if (N == 0) return FFVD_OK;
+    double *dX = sc.upload(X, (size_t)N * P);
+    OP_CHECK(dX, "ffvd_op_kernel_diag");
+    double *dO = sc.alloc<double>(N);
+    OP_CHECK(dO, "ffvd_op_kernel_diag");
+    launch_kernel_diag(sc.stream, kind, dX, N, P, logvariance, dO);
+    OP_TRY(hipMemcpyAsync(out, dO, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
+    OP_TRY(hipStreamSynchronize(sc.stream));
+    return FFVD_OK;
+}
+
+// Batched Cholesky of `batch` np x np slabs (identity padded, np % NB == 0) at dA, which the caller uploaded from host_in (left
+// intact); hinfo[b] <- 0 or 1 + first bad pivot.  If the one-launch (dataflow) variant gave up on a bounded wait, the batch is uploaded
+// again from host_in and re-run with the launch-per-column variant, which has no inter-workgroup waits; a warning for
+// ffvd_last_error(NULL) says so (an error of the caller's replaces it).
+// Shared by ffvd_op_cholesky and ffvd_op_get_rand_full_cov.
+static int potrf_with_stall_recovery(Scratch &sc, double *dA, const double *host_in, int np, int batch, int32_t *dinfo,
+                                     double *dinv, int32_t *hinfo, const char *who) {
+    const size_t slab = (size_t)np * np;
+    for (int attempt = 0;; ++attempt) {
+        {
+            CholOverrideGuard guard;            // reset on the error returns below as well
+            if (attempt == 1) {
+                OP_TRY(hipMemcpyAsync(dA, host_in, slab * batch * sizeof(double), hipMemcpyHostToDevice, sc.stream));
+                guard.force_left();
+            }
+            OP_TRY(hipMemsetAsync(dinfo, 0, batch * sizeof(int32_t), sc.stream));
+            launch_potrf_ext(sc.stream, dA, np, 0, 0, batch, slab, dinfo, dinv);
+        }
+        OP_TRY(hipMemcpyAsync(hinfo, dinfo, batch * sizeof(int32_t), hipMemcpyDeviceToHost, sc.stream));
+        OP_TRY(hipStreamSynchronize(sc.stream));
+        bool stalled = false;
+        for (int b = 0; b < batch; ++b) stalled = stalled || hinfo[b] < 0;
+        if (!stalled) {
+            if (attempt == 1)
+                set_error(nullptr, FFVD_OK, "warning: " + std::string(who) + ": the one-launch (dataflow) Cholesky gave up on a bounded wait; the batch "
+                                            "was re-run with the launch-per-column Cholesky and completed");
+            return FFVD_OK;
+        }
+        if (attempt == 1)
+            return set_error(nullptr, FFVD_EDEVICE, std::string(who) + ": abandoned, a block row waited more than 1 s for the row above it");
+    }
+}
+
+extern "C" int ffvd_op_cholesky(const double *A, int n, int batch, double *L, int32_t *info) {
+    if (!A || !L || n < 1 || batch < 0) return set_error(nullptr, FFVD_EINVAL, "ffvd_op_cholesky: bad argument");
+    OP_BEGIN("ffvd_op_cholesky");
+    if (batch == 0) return FFVD_OK;
+    const int np = round_up(n, NB);
+    const size_t slab = (size_t)np * np;
+    std::vector<double> &pad = pad_identity(sc, A, batch, n, np);
+    double *dA = sc.upload(pad.data(), pad.size());
+    OP_CHECK(dA, "ffvd_op_cholesky");
+    int32_t *dinfo = sc.alloc<int32_t>(batch);
+    OP_CHECK(dinfo, "ffvd_op_cholesky");
+    double *dinv = sc.alloc<double>(potrf_scratch_doubles(np, batch));
+    OP_CHECK(dinv, "ffvd_op_cholesky");
+    std::vector<int32_t> hinfo(batch, 0);
+    int rc = potrf_with_stall_recovery(sc, dA, pad.data(), np, batch, dinfo, dinv, hinfo.data(), "ffvd_op_cholesky");
+    if (rc) return rc;
+    OP_TRY(hipMemcpyAsync(pad.data(), dA, pad.size() * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
+    OP_TRY(hipStreamSynchronize(sc.stream));
+    int bad = -1;
+    for (int b = 0; b < batch; ++b) {
+        const double *S = pad.data() + slab * b;
+        for (int i = 0; i < n; ++i)
+            for (int j = 0; j < n; ++j) L[((size_t)b * n + i) * n + j] = (j <= i) ? S[(size_t)i * np + j] : 0.0;
+        if (info) info[b] = hinfo[b];
+        if (hinfo[b] != 0 && bad < 0) bad = b;
+    }
+    if (bad >= 0) {
+        char msg[160];
+        snprintf(msg, sizeof msg, "ffvd_op_cholesky: matrix %d is not positive definite (pivot %d)", bad, hinfo[bad] - 1);
+        return set_error(nullptr, FFVD_ENOTPD, msg);
+    }
+    return FFVD_OK;
+}
+
+// shared by kernel_pre_cal / conditional: device-side hypers + K_uu + extended Cholesky
+struct KuuWork {
+    HyperView hv;
+    double *Kuu, *dinv;
+    int32_t *info;
+    int Mp;
+};
+static int build_kuu(Scratch &sc, const char *who, int kind, const double *Z, int M, int P, int D, const double *logvariance,
+                     const double *loglengthscales, double jitter, KuuWork &w) {
+    const int Mp = round_up(M, NB);
+    w.Mp = Mp;
+    if (int rc = stage_hypers(sc, who, kind, Z, M, Mp, P, D, logvariance, loglengthscales, w.hv)) return rc;
+    w.Kuu = sc.alloc<double>((size_t)D * 2 * Mp * Mp);
+    w.info = sc.alloc<int32_t>(D);
+    w.dinv = sc.alloc<double>(potrf_scratch_doubles(Mp, D));
+    if (!w.Kuu || !w.info || !w.dinv) return FFVD_ENOMEM;
+    if (hipMemsetAsync(w.info, 0, D * sizeof(int32_t), sc.stream) != hipSuccess) return FFVD_EDEVICE;
+    launch_kuu_build(sc.stream, kind, w.hv, M, Mp, P, D, jitter, w.Kuu, nullptr);
+    launch_potrf_ext(sc.stream, w.Kuu, Mp, Mp, Mp, D, (size_t)2 * Mp * Mp, w.info, w.dinv);
+    return FFVD_OK;
+}
+
+extern "C" int ffvd_op_trsm(const double *L, int n, const double *B, int m, double *X) {
+    if (!L || !B || !X || n < 1 || m < 0) return set_error(nullptr, FFVD_EINVAL, "ffvd_op_trsm: bad argument");
+    for (int i = 0; i < n; ++i)
+        if (!(L[(size_t)i * n + i] != 0.0)) return set_error(nullptr, FFVD_EINVAL, "ffvd_op_trsm: zero on the diagonal of L");
+    OP_BEGIN("ffvd_op_trsm");
+    if (m == 0) return FFVD_OK;
+    // slab = [ L (np x np, identity padding) ; R = B^T (mp x np, zero padding) ];  X^T = R L^-T
+    const int np = round_up(n, NB), mp = round_up(m, NB);
+    std::vector<double> &slab = sc.host((size_t)(np + mp) * np);
+    for (int i = 0; i < np; ++i) {
+        if (i < n) for (int j = 0; j <= i; ++j) slab[(size_t)i * np + j] = L[(size_t)i * n + j];
+        else slab[(size_t)i * np + i] = 1.0;
+    }
+    for (int c = 0; c < m; ++c)
+        for (int i = 0; i < n; ++i) slab[(size_t)(np + c) * np + i] = B[(size_t)i * m + c];
+    double *dA = sc.upload(slab.data(), slab.size());
+    OP_CHECK(dA, "ffvd_op_trsm");
+    double *dinv = sc.alloc<double>(DINV_STRIDE);
+    OP_CHECK(dinv, "ffvd_op_trsm");
+    launch_trsm_ext(sc.stream, dA, np, mp, 1, slab.size(), dinv);
+    OP_TRY(hipGetLastError());
+    OP_TRY(hipMemcpyAsync(slab.data(), dA, slab.size() * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
+    OP_TRY(hipStreamSynchronize(sc.stream));
+    for (int c = 0; c < m; ++c)
+        for (int i = 0; i < n; ++i) X[(size_t)i * m + c] = slab[(size_t)(np + c) * np + i];
+    return FFVD_OK;
+}
+
+extern "C" int ffvd_op_kernel_pre_cal(int kind, const double *Z, int M, int P, int D, const double *logvariance,
+                                      const double *loglengthscales, double jitter, double *Lm_inverse_seq) {
+    if (!Z || !logvariance || !Lm_inverse_seq || M < 1 || P < 1 || P > MAXP || D < 1 ||
+        (kind == FFVD_KERNEL_SE && !loglengthscales))
+        return set_error(nullptr, FFVD_EINVAL, "ffvd_op_kernel_pre_cal: bad argument");
+    OP_BEGIN("ffvd_op_kernel_pre_cal");
+    KuuWork w{};
+    int rc = build_kuu(sc, "ffvd_op_kernel_pre_cal", kind, Z, M, P, D, logvariance, loglengthscales, jitter, w);
+    if (rc) return set_error(nullptr, rc, "ffvd_op_kernel_pre_cal: device allocation or upload failed");
+    const size_t Mp = w.Mp;
+    std::vector<double> host((size_t)D * 2 * Mp * Mp);
+    OP_TRY(hipMemcpyAsync(host.data(), w.Kuu, host.size() * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
+    if ((rc = fetch_chol_info(sc, w.info, D, "ffvd_op_kernel_pre_cal", "K_uu + jitter*I"))) return rc;
+    for (int d = 0; d < D; ++d) {
+        const double *Wd = host.data() + (size_t)d * 2 * Mp * Mp + Mp * Mp;
+        for (int i = 0; i < M; ++i)
+            memcpy(Lm_inverse_seq + ((size_t)d * M + i) * M, Wd + (size_t)i * Mp, (size_t)M * sizeof(double));
+    }
+    return FFVD_OK;
+}
+
+extern "C" int ffvd_op_collapse(int kind, const double *Lm_inverse_seq, const double *X_combine, const double *X,
+                                const double *Z, int T, int M, int P, int D, const double *logvariance,
+                                const double *loglengthscales, const double *Q, double batch_size, double Y_N,
+                                double out3[3]) {
+    if (!Lm_inverse_seq || !X_combine || !X || !Z || !logvariance || !Q || !out3 || T < 1 || M < 1 || P < 1 ||
+        P > MAXP || D < 1 || (kind == FFVD_KERNEL_SE && !loglengthscales) || !(batch_size > 0.0))
+        return set_error(nullptr, FFVD_EINVAL, "ffvd_op_collapse: bad argument");
+    OP_BEGIN("ffvd_op_collapse");
+    const int Mp = round_up(M, NB), Tp = round_up(T, STRIP), ng = (Mp + 511) / 512;
+    std::vector<double> &logQ = sc.host(D);
+    for (int d = 0; d < D; ++d) logQ[d] = log(Q[d]);
+    HyperView hv{};
+    if (int rc = stage_hypers(sc, "ffvd_op_collapse", kind, Z, M, Mp, P, D, logvariance, loglengthscales, hv)) return rc;
+    double *dW = upload_stack(sc, Lm_inverse_seq, D, M, Mp);      // the caller's L^{-T} stack, padded to Mp with an identity block
+    double *dXc = sc.upload(X_combine, (size_t)T * P);
+    double *dX = sc.upload(X, (size_t)(T + 1) * D);
+    double *dlq = sc.upload(logQ.data(), D);
+    double *F = sc.alloc<double>((size_t)D * Tp * Mp);
+    const size_t hstride = (size_t)(Mp + NB) * Mp;
+    double *H = sc.alloc<double>((size_t)D * hstride);
+    double *rowsq = sc.alloc<double>((size_t)D * ng * Tp);
+    double *hterms = sc.alloc<double>((size_t)D * 2), *cterms = sc.alloc<double>(8);
+    int32_t *info = sc.alloc<int32_t>(D);
+    double *dinv = sc.alloc<double>(potrf_scratch_doubles(Mp, D));
+    if (!dW || !dXc || !dX || !dlq || !F || !H || !rowsq || !hterms || !cterms || !info || !dinv)
+        return set_error(nullptr, FFVD_ENOMEM, "ffvd_op_collapse: device allocation or upload failed");
+    OP_TRY(hipMemsetAsync(H, 0, (size_t)D * hstride * sizeof(double), sc.stream));
+    OP_TRY(hipMemsetAsync(info, 0, D * sizeof(int32_t), sc.stream));
+    launch_project(sc.stream, op_project_args(kind, hv, dXc, T, Tp, P, M, Mp, D, dW, (size_t)Mp * Mp, nullptr, F, rowsq, nullptr, ng));
+    GramArgs ga{};
+    ga.mode = GRAM_F; ga.A = F; ga.a_stride = (size_t)Tp * Mp; ga.rows = Tp; ga.with_row = 1;
+    ga.X = dX; ga.log_Q = dlq; ga.T = T; ga.D = D; ga.Mp = Mp; ga.Dl = D; ga.d_begin = 0;
+    ga.b0 = 0; ga.nb = D; ga.yn_over_batch = Y_N / batch_size; ga.H = H; ga.h_stride = hstride;
+    launch_gram(sc.stream, ga);
+    launch_potrf_ext(sc.stream, H, Mp, NB, 0, D, hstride, info, dinv);
+    launch_h_finish(sc.stream, H, Mp, hstride, D, hterms);
+    ReduceArgs ra{};
+    ra.kind = kind; ra.branch = FFVD_BRANCH_B; ra.X = dX; ra.ctrl = nullptr; ra.Y = nullptr; ra.log_Q = dlq;
+    ra.CC = nullptr; ra.DD = nullptr; ra.log_Rchols = nullptr; ra.variance = hv.variance; ra.T = T; ra.Tp = Tp; ra.D = D;
+    ra.C = 0; ra.Ydim = 0; ra.Dl = D; ra.d_begin = 0; ra.S = 1; ra.ng = ng; ra.shared_terms = 0;
+    ra.xk = dXc; ra.xk_chain_stride = 0; ra.xk_ld = P; ra.xk_cols = P; ra.rowsq = rowsq; ra.fmean = nullptr;
+    ra.chain_terms = cterms;
+    double *cpart = sc.alloc<double>(128);
+    if (!cpart) return set_error(nullptr, FFVD_ENOMEM, "ffvd_op_collapse: device allocation failed");
+    launch_chain_reduce(sc.stream, ra, cpart);
+    std::vector<double> ht((size_t)D * 2), ct(8);
+    OP_TRY(hipMemcpyAsync(ht.data(), hterms, ht.size() * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
+    OP_TRY(hipMemcpyAsync(ct.data(), cterms, 8 * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
+    if (int rc = fetch_chol_info(sc, info, D, "ffvd_op_collapse", "H")) return rc;
+    double term1 = 0.0, term2 = 0.0;
+    for (int d = 0; d < D; ++d) { term1 += -0.5 * ht[2 * d]; term2 += 0.5 * ht[2 * d + 1]; }
+    out3[0] = -term1 / Y_N;
+    out3[1] = -term2 / Y_N;
+    out3[2] = -ct[2] / Y_N;      // chain_reduce's trace sum: sum_d sum_t -0.5 (Kdiag - |F_t|^2) / Q_d
+    return FFVD_OK;
+}
+
+extern "C" int ffvd_op_conditional(int kind, const double *Xnew, int N, const double *Z, int M, int P, int D,
+                                   const double *logvariance, const double *loglengthscales, const double *f,
+                                   double jitter, double *mean, double *var) {
+    if (!Xnew || !Z || !logvariance || !f || !mean || !var || N < 0 || M < 1 || P < 1 || P > MAXP || D < 1 ||
+        (kind == FFVD_KERNEL_SE && !loglengthscales))
+        return set_error(nullptr, FFVD_EINVAL, "ffvd_op_conditional: bad argument");
+    OP_BEGIN("ffvd_op_conditional");
+    if (N == 0) return FFVD_OK;
+    KuuWork w{};
+    int rc = build_kuu(sc, "ffvd_op_conditional", kind, Z, M, P, D, logvariance, loglengthscales, jitter, w);
+    if (rc) return set_error(nullptr, rc, "ffvd_op_conditional: device allocation or upload failed");
+    const int Mp = w.Mp, Tp = round_up(N, STRIP), ng = (Mp + 511) / 512;
+    double *dX = sc.upload(Xnew, (size_t)N * P);
+    double *dU = sc.upload(f, (size_t)M * D);
+    double *rowsq = sc.alloc<double>((size_t)D * ng * Tp), *fmean = sc.alloc<double>((size_t)D * ng * Tp);
+    double *dmean = sc.alloc<double>((size_t)N * D), *dvar = sc.alloc<double>((size_t)N * D);
+    if (!dX || !dU || !rowsq || !fmean || !dmean || !dvar)
+        return set_error(nullptr, FFVD_ENOMEM, "ffvd_op_conditional: device allocation or upload failed");
+    launch_project(sc.stream, op_project_args(kind, w.hv, dX, N, Tp, P, M, Mp, D, w.Kuu + (size_t)Mp * Mp, (size_t)2 * Mp * Mp, dU, nullptr,
+                                              rowsq, fmean, ng));
+    launch_conditional_finish(sc.stream, kind, dX, N, P, w.hv.variance, rowsq, fmean, ng, Tp, D, dmean, dvar, nullptr);
+    OP_TRY(hipMemcpyAsync(mean, dmean, (size_t)N * D * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
+    OP_TRY(hipMemcpyAsync(var, dvar, (size_t)N * D * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
+    return fetch_chol_info(sc, w.info, D, "ffvd_op_conditional", "K_uu + jitter*I");
+}
+
+extern "C" int ffvd_op_predict_mean(const double *X_end, int N, int D, const double *CC, const double *DD, int Ydim,
+                                    double *out) {
+    if (!X_end || !CC || !DD || !out || N < 0 || D < 1 || Ydim < 1)
+        return set_error(nullptr, FFVD_EINVAL, "ffvd_op_predict_mean: bad argument");
+    OP_BEGIN("ffvd_op_predict_mean");
+    if (N == 0) return FFVD_OK;
+    double *dX = sc.upload(X_end, (size_t)N * D), *dC = sc.upload(CC, (size_t)D * Ydim), *dD = sc.upload(DD, Ydim);
+    double *dO = sc.alloc<double>((size_t)N * Ydim);
+    if (!dX || !dC || !dD || !dO) return set_error(nullptr, FFVD_ENOMEM, "ffvd_op_predict_mean: device allocation or upload failed");
+    launch_predict_mean(sc.stream, dX, N, D, dC, dD, Ydim, dO);
+    OP_TRY(hipMemcpyAsync(out, dO, (size_t)N * Ydim * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
+    OP_TRY(hipStreamSynchronize(sc.stream));
+    return FFVD_OK;
+}
+
+extern "C" int ffvd_op_logdensity_norm_diag(int nonvec, const double *y, const double *ymean, const double *Rchols, int N,
+                                            int J, double *out) {
+    if (!y || !ymean || !Rchols || !out || N < 0 || J < 1)
+        return set_error(nullptr, FFVD_EINVAL, "ffvd_op_logdensity_norm_diag: bad argument");
+    OP_BEGIN("ffvd_op_logdensity_norm_diag");
+    if (N == 0) return FFVD_OK;
+    const size_t nout = nonvec ? (size_t)N * J : (size_t)N;
+    double *dy = sc.upload(y, (size_t)N * J), *dm = sc.upload(ymean, (size_t)N * J), *dR = sc.upload(Rchols, J);
+    double *dO = sc.alloc<double>(nout);
+    if (!dy || !dm || !dR || !dO) return set_error(nullptr, FFVD_ENOMEM, "ffvd_op_logdensity_norm_diag: device allocation or upload failed");
+    launch_logdensity(sc.stream, nonvec ? 1 : 0, dy, dm, dR, N, J, dO);
+    OP_TRY(hipMemcpyAsync(out, dO, nout * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
+    OP_TRY(hipStreamSynchronize(sc.stream));
+    return FFVD_OK;
+}
+
+extern "C" int ffvd_op_get_rand(const double *mean, const double *var, const double *eps, int64_t n, double *out) {
+    if (!mean || !var || !eps || !out || n < 0) return set_error(nullptr, FFVD_EINVAL, "ffvd_op_get_rand: bad argument");
+    OP_BEGIN("ffvd_op_get_rand");
+    if (n == 0) return FFVD_OK;
+    double *dm = sc.upload(mean, (size_t)n), *dv = sc.upload(var, (size_t)n), *de = sc.upload(eps, (size_t)n);
+    double *dO = sc.alloc<double>((size_t)n);
+    if (!dm || !dv || !de || !dO) return set_error(nullptr, FFVD_ENOMEM, "ffvd_op_get_rand: device allocation or upload failed");
+    launch_get_rand(sc.stream, dm, dv, de, (size_t)n, dO);
+    OP_TRY(hipMemcpyAsync(out, dO, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
+    OP_TRY(hipStreamSynchronize(sc.stream));
+    return FFVD_OK;
+}
+
+extern "C" int ffvd_op_collapse_u_mean(int kind, const double *Lm_inverse_seq, const double *X_combine, const double *X,
+                                       const double *Z, int T, int M, int P, int D, const double *logvariance,
+                                       const double *loglengthscales, const double *Q, double *U_mean,
+                                       double *H_inv_sqrt) {
+    if (!Lm_inverse_seq || !X_combine || !X || !Z || !logvariance || !Q || !U_mean || !H_inv_sqrt || T < 1 || M < 1 ||
+        P < 1 || P > MAXP || D < 1 || (kind == FFVD_KERNEL_SE && !loglengthscales))
+        return set_error(nullptr, FFVD_EINVAL, "ffvd_op_collapse_u_mean: bad argument");
+    OP_BEGIN("ffvd_op_collapse_u_mean");
+    const int Mp = round_up(M, NB), Tp = round_up(T, STRIP), ng = (Mp + 511) / 512;
+    std::vector<double> &logQ = sc.host(D);
+    for (int d = 0; d < D; ++d) logQ[d] = log(Q[d]);
+    // slab per dim: rows [0,Mp) H, rows [Mp,2Mp) identity -> L_H^-T, row 2Mp carries b -> L_H^-1 b
+    const size_t hstride = (size_t)(2 * Mp + NB) * Mp;
+    std::vector<double> &Hinit = sc.host((size_t)D * hstride);
+    for (int d = 0; d < D; ++d)
+        for (int i = 0; i < Mp; ++i) Hinit[(size_t)d * hstride + (size_t)(Mp + i) * Mp + i] = 1.0;
+    HyperView hv{};
+    if (int rc = stage_hypers(sc, "ffvd_op_collapse_u_mean", kind, Z, M, Mp, P, D, logvariance, loglengthscales, hv)) return rc;
+    double *dW = upload_stack(sc, Lm_inverse_seq, D, M, Mp);
+    double *dXc = sc.upload(X_combine, (size_t)T * P), *dX = sc.upload(X, (size_t)(T + 1) * D);
+    double *dlq = sc.upload(logQ.data(), D);
+    double *F = sc.alloc<double>((size_t)D * Tp * Mp), *rowsq = sc.alloc<double>((size_t)D * ng * Tp);
+    double *H = sc.upload(Hinit.data(), Hinit.size());
+    double *dU = sc.alloc<double>((size_t)M * D);
+    int32_t *info = sc.alloc<int32_t>(D);
+    double *dinv = sc.alloc<double>(potrf_scratch_doubles(Mp, D));
+    if (!dW || !dXc || !dX || !dlq || !F || !rowsq || !H || !dU || !info || !dinv)
+        return set_error(nullptr, FFVD_ENOMEM, "ffvd_op_collapse_u_mean: device allocation or upload failed");
+    OP_TRY(hipMemsetAsync(info, 0, D * sizeof(int32_t), sc.stream));
+    launch_project(sc.stream, op_project_args(kind, hv, dXc, T, Tp, P, M, Mp, D, dW, (size_t)Mp * Mp, nullptr, F, rowsq, nullptr, ng));
+    GramArgs ga{};
+    ga.mode = GRAM_F; ga.A = F; ga.a_stride = (size_t)Tp * Mp; ga.rows = Tp; ga.with_row = 1; ga.brow = 2 * Mp;
+    ga.X = dX; ga.log_Q = dlq; ga.T = T; ga.D = D; ga.Mp = Mp; ga.Dl = D; ga.d_begin = 0;
+    ga.b0 = 0; ga.nb = D; ga.yn_over_batch = 1.0; ga.H = H; ga.h_stride = hstride;     // :215,:217 (no batch rescaling)
+    launch_gram(sc.stream, ga);
+    launch_potrf_ext(sc.stream, H, Mp, Mp + NB, Mp, D, hstride, info, dinv);
+    // U_mean[:, d] = H^-1 b = L_H^-T (L_H^-1 b)   (tf.linalg.solve, :219)
+    launch_matvec(sc.stream, H + (size_t)Mp * Mp, hstride, H + (size_t)2 * Mp * Mp, hstride, Mp, dU, D, 1, M, D);
+    std::vector<double> hH((size_t)D * hstride);
+    OP_TRY(hipMemcpyAsync(hH.data(), H, hH.size() * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
+    OP_TRY(hipMemcpyAsync(U_mean, dU, (size_t)M * D * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
+    if (int rc = fetch_chol_info(sc, info, D, "ffvd_op_collapse_u_mean", "H")) return rc;
+    for (int d = 0; d < D; ++d)          // Lm_inverse_dd_seq = L_H^-T (:222)
+        for (int i = 0; i < M; ++i)
+            memcpy(H_inv_sqrt + ((size_t)d * M + i) * M, hH.data() + (size_t)d * hstride + (size_t)(Mp + i) * Mp,
+                   (size_t)M * sizeof(double));
+    return FFVD_OK;
+}
+
+extern "C" int ffvd_op_conditional_precalc(int kind, const double *Lm_inverse_seq, const double *Xnew, int N,
+                                           const double *Z, int M, int P, int D, const double *logvariance,
+                                           const double *loglengthscales, const double *f, const double *q_sqrt,
+                                           double *mean, double *var) {
+    if (!Lm_inverse_seq || !Xnew || !Z || !logvariance || !f || !mean || !var || N < 0 || M < 1 || M > 2048 || P < 1 ||
+        P > MAXP || D < 1 || (kind == FFVD_KERNEL_SE && !loglengthscales))
+        return set_error(nullptr, FFVD_EINVAL, "ffvd_op_conditional_precalc: bad argument");
+    OP_BEGIN("ffvd_op_conditional_precalc");
+    if (N == 0) return FFVD_OK;
+    const int Mp = round_up(M, NB), Tp = round_up(N, STRIP), ng = (Mp + 511) / 512;
+    HyperView hv{};
+    if (int rc = stage_hypers(sc, "ffvd_op_conditional_precalc", kind, Z, M, Mp, P, D, logvariance, loglengthscales, hv)) return rc;
+    double *dW = upload_stack(sc, Lm_inverse_seq, D, M, Mp);
+    double *dX = sc.upload(Xnew, (size_t)N * P), *dU = sc.upload(f, (size_t)M * D);
+    double *F = sc.alloc<double>((size_t)D * Tp * Mp);
+    double *rowsq = sc.alloc<double>((size_t)D * ng * Tp), *fmean = sc.alloc<double>((size_t)D * ng * Tp);
+    double *dmean = sc.alloc<double>((size_t)N * D), *dvar = sc.alloc<double>((size_t)N * D);
+    double *dQs = q_sqrt ? sc.upload(q_sqrt, (size_t)M * M) : nullptr;     // slice d = 0 only (the reference quirk)
+    double *extra = q_sqrt ? sc.alloc<double>((size_t)D * Tp) : nullptr;
+    if (!dW || !dX || !dU || !F || !rowsq || !fmean || !dmean || !dvar || (q_sqrt && (!dQs || !extra)))
+        return set_error(nullptr, FFVD_ENOMEM, "ffvd_op_conditional_precalc: device allocation or upload failed");
+    // A^T = K_fu L^-T (:349), mean (:365), sum A^2 (:356)
+    launch_project(sc.stream, op_project_args(kind, hv, dX, N, Tp, P, M, Mp, D, dW, (size_t)Mp * Mp, dU, q_sqrt ? F : nullptr, rowsq,
+                                              fmean, ng));
+    if (q_sqrt) launch_qsqrt_inflation(sc.stream, F, (size_t)Tp * Mp, Tp, Mp, M, dQs, extra, N, D);
+    launch_conditional_finish(sc.stream, kind, dX, N, P, hv.variance, rowsq, fmean, ng, Tp, D, dmean, dvar, extra);
+    OP_TRY(hipMemcpyAsync(mean, dmean, (size_t)N * D * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
+    OP_TRY(hipMemcpyAsync(var, dvar, (size_t)N * D * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
+    OP_TRY(hipStreamSynchronize(sc.stream));
+    return FFVD_OK;
+}
+
+// Full predictive covariance / q_sqrt inflation of the conditional (ffvd_op_conditional_cov, ffvd_op_conditional_precalc_cov), once
+// the stack W_d = L_d^-T (Mp x Mp, slab stride w_stride) and the hyper-parameters are on the device.  Mean and per-point variance run
+// through the same launches as ffvd_op_conditional / ffvd_op_conditional_precalc (projection with F kept, conditional_finish); then
+//   q_sqrt (M x M slice 0, as given):  E_d = F_d q0 (cov.hip, COV_GEN, q0^T uploaded once for all d);
+//   full_cov:  Sigma_d = K_d(Xnew, Xnew) - F_d F_d^T (+ E_d E_d^T) (cov.hip, COV_SYM), var: D x N x N, its diagonal the per-point
+//              variance (without q_sqrt: that of the full_cov = 0 form bit for bit; with it: the q_sqrt term summed from E's rows);
+//   otherwise: var[:, d] += sum_j E_d[:, j]^2 through qsqrt_inflation (conditionals_multi_output.py:371-380), var: N x D.
+static int conditional_cov_tail(Scratch &sc, const char *who, int kind, const HyperView &hv, const double *W, size_t w_stride,
+                                const double *Xnew, int N, int M, int P, int D, const double *f, const double *q_sqrt, int full_cov,
+                                double *mean, double *var) {
+    const int Mp = round_up(M, NB), Tp = round_up(N, STRIP), ng = (Mp + 511) / 512;
+    double *dX = sc.upload(Xnew, (size_t)N * P), *dU = sc.upload(f, (size_t)M * D);
+    double *rowsq = sc.alloc<double>((size_t)D * ng * Tp), *fmean = sc.alloc<double>((size_t)D * ng * Tp);
+    double *dmean = sc.alloc<double>((size_t)N * D), *dvar = sc.alloc<double>((size_t)N * D);
+    double *F = sc.alloc<double>((size_t)D * Tp * Mp);
+    if (!dX || !dU || !rowsq || !fmean || !dmean || !dvar || !F)
+        return set_error(nullptr, FFVD_ENOMEM, std::string(who) + ": device allocation or upload failed");
+    // F = A^T = K_fu L^-T (:34 / :349), mean (:48 / :365)
+    launch_project(sc.stream, op_project_args(kind, hv, dX, N, Tp, P, M, Mp, D, W, w_stride, dU, F, rowsq, fmean, ng));
+    if (!full_cov) {
+        double *dQs = q_sqrt ? sc.upload(q_sqrt, (size_t)M * M) : nullptr, *extra = q_sqrt ? sc.alloc<double>((size_t)D * Tp) : nullptr;
+        if (q_sqrt && (!dQs || !extra)) return set_error(nullptr, FFVD_ENOMEM, std::string(who) + ": device allocation or upload failed");
+        if (q_sqrt) launch_qsqrt_inflation(sc.stream, F, (size_t)Tp * Mp, Tp, Mp, M, dQs, extra, N, D);
+        launch_conditional_finish(sc.stream, kind, dX, N, P, hv.variance, rowsq, fmean, ng, Tp, D, dmean, dvar, extra);
+        OP_TRY(hipMemcpyAsync(mean, dmean, (size_t)N * D * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
+        OP_TRY(hipMemcpyAsync(var, dvar, (size_t)N * D * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
+        OP_TRY(hipStreamSynchronize(sc.stream));
+        return FFVD_OK;
+    }
+    double *E = nullptr, *extra = nullptr;
+    if (q_sqrt) {
+        std::vector<double> &qt = sc.host((size_t)Mp * Mp);          // q0^T, zero padded: row j = column j of q0
+        for (int k = 0; k < M; ++k)
+            for (int j = 0; j < M; ++j) qt[(size_t)j * Mp + k] = q_sqrt[(size_t)k * M + j];
+        double *dQt = sc.upload(qt.data(), qt.size());
+        E = sc.alloc<double>((size_t)D * Tp * Mp);
+        extra = sc.alloc<double>((size_t)D * Tp);
+        if (!dQt || !E || !extra) return set_error(nullptr, FFVD_ENOMEM, std::string(who) + ": device allocation or upload failed");
+        CovArgs ea{};
+        ea.mode = COV_GEN; ea.A = F; ea.a_stride = (size_t)Tp * Mp; ea.lda = Mp; ea.arows = Tp; ea.K = Mp;
+        ea.B = dQt; ea.b_stride = 0; ea.ldb = Mp; ea.brows = Mp; ea.ncols = Mp;
+        ea.C = E; ea.c_stride = (size_t)Tp * Mp; ea.ldc = Mp; ea.nb = D;
+        launch_cov(sc.stream, ea);                                   // LTA^T = F q0 (:371-376, slice 0 for every dim)
+        launch_row_sumsq(sc.stream, E, (size_t)Tp * Mp, Mp, Mp, N, D, Tp, extra);     // sum_j LTA^2 (:380)
+    }
+    // the per-point variance becomes the diagonal of Sigma_d
+    launch_conditional_finish(sc.stream, kind, dX, N, P, hv.variance, rowsq, fmean, ng, Tp, D, dmean, dvar, extra);
+    double *dS = sc.alloc<double>((size_t)D * N * N);
+    if (!dS) return set_error(nullptr, FFVD_ENOMEM, std::string(who) + ": device allocation failed");
+    CovArgs ca{};
+    ca.mode = COV_SYM; ca.A = F; ca.E = E; ca.a_stride = (size_t)Tp * Mp; ca.lda = Mp; ca.arows = Tp; ca.K = Mp;
+    ca.C = dS; ca.c_stride = (size_t)N * N; ca.ldc = N; ca.N = N; ca.kind = kind; ca.P = P; ca.x = dX;
+    ca.variance = hv.variance; ca.len = hv.len; ca.diag = dvar; ca.nb = D;
+    launch_cov(sc.stream, ca);                                       // K(Xnew) - A^T A (+ LTA^T LTA) (:41-44 full_cov branch)
+    OP_TRY(hipGetLastError());
+    OP_TRY(hipMemcpyAsync(mean, dmean, (size_t)N * D * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
+    if (!sc.download(var, dS, (size_t)D * N * N * sizeof(double)))
+        return set_error(nullptr, FFVD_EDEVICE, std::string(who) + ": device error while copying the covariance out");
+    return FFVD_OK;
+}
+
+static bool cov_args_ok(int kind, const double *Xnew, int N, const double *Z, int M, int P, int D, const double *logvariance,
+                        const double *loglengthscales, const double *f, const double *q_sqrt, int full_cov, const double *mean,
+                        const double *var) {
+    return Xnew && Z && logvariance && f && mean && var && N >= 0 && M >= 1 && P >= 1 && P <= MAXP && D >= 1 &&
+           (kind == FFVD_KERNEL_SE || kind == FFVD_KERNEL_LINEAR) && (kind != FFVD_KERNEL_SE || loglengthscales) &&
+           (full_cov == 0 || full_cov == 1) && (!q_sqrt || M <= 2048) &&
+           (size_t)D * N * N <= ((size_t)1 << 40);
+}
+
+extern "C" int ffvd_op_conditional_cov(int kind, const double *Xnew, int N, const double *Z, int M, int P, int D,
+                                       const double *logvariance, const double *loglengthscales, const double *f,
+                                       const double *q_sqrt, int full_cov, double jitter, double *mean, double *var) {
+    if (!cov_args_ok(kind, Xnew, N, Z, M, P, D, logvariance, loglengthscales, f, q_sqrt, full_cov, mean, var))
+        return set_error(nullptr, FFVD_EINVAL, "ffvd_op_conditional_cov: bad argument");
+    OP_BEGIN("ffvd_op_conditional_cov");
+    if (N == 0) return FFVD_OK;
+    KuuWork w{};
+    int rc = build_kuu(sc, "ffvd_op_conditional_cov", kind, Z, M, P, D, logvariance, loglengthscales, jitter, w);
+    if (rc) return set_error(nullptr, rc, "ffvd_op_conditional_cov: device allocation or upload failed");
+    const int Mp = w.Mp;
+    rc = conditional_cov_tail(sc, "ffvd_op_conditional_cov", kind, w.hv, w.Kuu + (size_t)Mp * Mp, (size_t)2 * Mp * Mp, Xnew, N, M, P,
+                              D, f, q_sqrt, full_cov, mean, var);
+    if (rc) return rc;
+    return fetch_chol_info(sc, w.info, D, "ffvd_op_conditional_cov", "K_uu + jitter*I");
+}
+
+extern "C" int ffvd_op_conditional_precalc_cov(int kind, const double *Lm_inverse_seq, const double *Xnew, int N, const double *Z,
+                                               int M, int P, int D, const double *logvariance, const double *loglengthscales,
+                                               const double *f, const double *q_sqrt, int full_cov, double *mean, double *var) {
+    if (!Lm_inverse_seq || !cov_args_ok(kind, Xnew, N, Z, M, P, D, logvariance, loglengthscales, f, q_sqrt, full_cov, mean, var))
+        return set_error(nullptr, FFVD_EINVAL, "ffvd_op_conditional_precalc_cov: bad argument");
+    OP_BEGIN("ffvd_op_conditional_precalc_cov");
+    if (N == 0) return FFVD_OK;
+    const int Mp = round_up(M, NB);
+    HyperView hv{};
+    if (int rc = stage_hypers(sc, "ffvd_op_conditional_precalc_cov", kind, Z, M, Mp, P, D, logvariance, loglengthscales, hv)) return rc;
+    double *dW = upload_stack(sc, Lm_inverse_seq, D, M, Mp);
+    OP_CHECK(dW, "ffvd_op_conditional_precalc_cov");
+    return conditional_cov_tail(sc, "ffvd_op_conditional_precalc_cov", kind, hv, dW, (size_t)Mp * Mp, Xnew, N, M, P, D, f, q_sqrt,
+                                full_cov, mean, var);
+}
+
+extern "C" int ffvd_op_get_rand_full_cov(const double *mean, const double *var, const double *eps, int N, int D, double jitter,
+                                         double *out) {
+    if (!mean || !var || !eps || !out || N < 0 || D < 1 || !(jitter >= 0.0) || (size_t)D * N * N > ((size_t)1 << 40))
+        return set_error(nullptr, FFVD_EINVAL, "ffvd_op_get_rand_full_cov: bad argument");
+    OP_BEGIN("ffvd_op_get_rand_full_cov");
+    if (N == 0) return FFVD_OK;
+    const int np = round_up(N, NB);
+    const size_t slab = (size_t)np * np;
+    std::vector<double> &pad = pad_identity(sc, var, D, N, np, jitter);      // Sigma_d + jitter I, identity padded to np
+    double *dA = sc.upload(pad.data(), pad.size());
+    double *dm = sc.upload(mean, (size_t)N * D), *de = sc.upload(eps, (size_t)N * D), *dO = sc.alloc<double>((size_t)N * D);
+    int32_t *dinfo = sc.alloc<int32_t>(D);
+    double *dinv = sc.alloc<double>(potrf_scratch_doubles(np, D));
+    if (!dA || !dm || !de || !dO || !dinfo || !dinv)
+        return set_error(nullptr, FFVD_ENOMEM, "ffvd_op_get_rand_full_cov: device allocation or upload failed");
+    std::vector<int32_t> hinfo(D, 0);
+    int rc = potrf_with_stall_recovery(sc, dA, pad.data(), np, D, dinfo, dinv, hinfo.data(), "ffvd_op_get_rand_full_cov");
+    if (rc) return rc;
+    for (int d = 0; d < D; ++d)
+        if (hinfo[d]) return chol_not_pd("ffvd_op_get_rand_full_cov", "var[" + std::to_string(d) + "] + jitter*I", d, hinfo[d]);
+    launch_tril_matvec(sc.stream, dA, slab, np, N, D, dm, de, dO);    // mean + L eps (utils.py:4-11, full_cov branch)
+    OP_TRY(hipGetLastError());
+    OP_TRY(hipMemcpyAsync(out, dO, (size_t)N * D * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
+    OP_TRY(hipStreamSynchronize(sc.stream));
+    return FFVD_OK;
+}
+
+extern "C" int ffvd_op_adam_step(double *theta, const double *grad, double *m, double *v, int64_t n, double lr,
+                                 double beta1, double beta2, double eps, int64_t t) {
+    if (!theta || !grad || !m || !v || n < 0 || t < 1 || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0))
+        return set_error(nullptr, FFVD_EINVAL, "ffvd_op_adam_step: bad argument");
+    OP_BEGIN("ffvd_op_adam_step");
+    if (n == 0) return FFVD_OK;
+    double *dth = sc.upload(theta, n), *dm = sc.upload(m, n), *dv = sc.upload(v, n);
+    const double *dg = sc.upload(grad, n);
+    if (!dth || !dm || !dv || !dg) return set_error(nullptr, FFVD_ENOMEM, "ffvd_op_adam_step: device allocation or upload failed");
+    OptTable tab{};
+    tab.count = 1;
+    tab.t[0].theta = dth; tab.t[0].grad = dg; tab.t[0].s0 = dm; tab.t[0].s1 = dv; tab.t[0].n = n;
+    const double lr_t = lr * sqrt(1.0 - pow(beta2, (double)t)) / (1.0 - pow(beta1, (double)t));
+    launch_adam(sc.stream, tab, lr_t, beta1, beta2, eps);
+    OP_TRY(hipMemcpyAsync(theta, dth, n * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
+    OP_TRY(hipMemcpyAsync(m, dm, n * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
+    OP_TRY(hipMemcpyAsync(v, dv, n * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
+    OP_TRY(hipStreamSynchronize(sc.stream));
+    return FFVD_OK;
+}
+
+extern "C" int ffvd_op_sghmc_step(double *theta, const double *grad, double *xi, double *g, double *g2, double *p,
+                                  const double *noise, int64_t n, double epsilon, double mdecay, double X_N, int burn_in) {
+    if (!theta || !grad || !xi || !g || !g2 || !p || !noise || n < 0 || !(X_N > 0.0))
+        return set_error(nullptr, FFVD_EINVAL, "ffvd_op_sghmc_step: bad argument");
+    OP_BEGIN("ffvd_op_sghmc_step");
+    if (n == 0) return FFVD_OK;
+    double *dth = sc.upload(theta, n), *dxi = sc.upload(xi, n), *dg_ = sc.upload(g, n), *dg2 = sc.upload(g2, n);
+    double *dp = sc.upload(p, n);
+    const double *dgrad = sc.upload(grad, n), *dnoise = sc.upload(noise, n);
+    if (!dth || !dxi || !dg_ || !dg2 || !dp || !dgrad || !dnoise)
+        return set_error(nullptr, FFVD_ENOMEM, "ffvd_op_sghmc_step: device allocation or upload failed");
+    OptTable tab{};
+    tab.count = 1;
+    OptTensor &t = tab.t[0];
+    t.theta = dth; t.grad = dgrad; t.s0 = dxi; t.s1 = dg_; t.s2 = dg2; t.s3 = dp; t.noise = dnoise; t.n = n;
+    launch_sghmc(sc.stream, tab, epsilon, mdecay, X_N, burn_in);
+    OP_TRY(hipMemcpyAsync(theta, dth, n * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
+    OP_TRY(hipMemcpyAsync(p, dp, n * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
+    if (burn_in) {
+        OP_TRY(hipMemcpyAsync(xi, dxi, n * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
+        OP_TRY(hipMemcpyAsync(g, dg_, n * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
+        OP_TRY(hipMemcpyAsync(g2, dg2, n * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
+    }
+    OP_TRY(hipStreamSynchronize(sc.stream));
+    return FFVD_OK;
+}
+
+// ---- step loops: posterior rollouts and the particle-Gibbs sweep -----------------------------------------------------------------------
+// What a rollout step and a particle-Gibbs step share.  K_fu rows once per step, then the triangular projection GEMM with fvar / fmean
+// in its epilogue (one workgroup per 128-column tile and dim): 16 workgroups instead of the 4 of the fused projection kernel, whose
+// single workgroup per dim made a step compute-bound on one CU.
+// Few rows per step (R rollouts / particles): the skinny product (kernels.hip) with one partial sum per 16-column slab replaces the
+// 128 x 128-tile projection GEMM (50 -> 7 us per step) and the per-row q_sqrt kernel (37 us).
+struct StepSetup {
+    int R, D, Mp, Tp, ng;
+    bool skinny;
+    int ngs;                                    // partial sums per row in rowsq / fmean: 16-column slabs (skinny) or 128-column tiles
+    double *Kf = nullptr, *ucol = nullptr, *rowsq = nullptr, *fmean = nullptr;
+    ProjectArgs pa{};                           // K(x_t, Z) rows (pa.x: the step's input rows)
+    ProjGemmArgs pg{};                          // tiled step: F = K_fu L^-T
+    SkinnyArgs sk{};                            // skinny step: the same product from the k-major rows of launch_kfu_build_t
+    StepSetup(Scratch &sc, int R_, int M, int D_)
+        : R(R_), D(D_), Mp(round_up(M, NB)), Tp(round_up(R_, STRIP)), ng((Mp + 127) / 128), skinny(R_ <= 512), ngs(skinny ? Mp / 16 : ng) {
+        Kf = sc.alloc<double>((size_t)D * Tp * Mp), ucol = sc.alloc<double>((size_t)D * Mp);
+        rowsq = sc.alloc<double>((size_t)D * ngs * Tp), fmean = sc.alloc<double>((size_t)D * ngs * Tp);
+    }
+    bool ok() const { return Kf && ucol && rowsq && fmean; }
+    // x: the R start rows; W = L^-T stack, U: inducing outputs (M x D); F: where the tiled step keeps F, or null; WQ (skinny step,
+    // optional): W q_sqrt as second right-hand side, its slab sums of squares into extra.  Enqueues the columns of U (ucol).
+    void fill(Scratch &sc, int kind, const HyperView &hv, const double *x, int P, int M, const double *W, const double *U, double *F,
+              const double *WQ, double *extra, int q_upper) {
+        const size_t msq = (size_t)Mp * Mp, fst = (size_t)Tp * Mp;
+        pa = op_project_args(kind, hv, x, R, Tp, P, M, Mp, D, W, msq, U, Kf, rowsq, fmean, ng);
+        launch_ucols(sc.stream, U, M, Mp, D, 0, D, ucol);
+        pg.Kf = Kf; pg.kf_stride = fst; pg.W = W; pg.w_stride = msq; pg.F = F; pg.f_stride = F ? fst : 0;
+        pg.rowsq = rowsq; pg.fmean = fmean; pg.u = ucol; pg.u_stride = Mp; pg.Tp = Tp; pg.Mp = Mp; pg.Dl = D; pg.b0 = 0; pg.nb = D;
+        sk = SkinnyArgs{Kf, fst, Tp, W, msq, Mp, 1, R, Mp, Mp, D, Tp, nullptr, 0, 0, ucol, (size_t)Mp, rowsq, fmean,
+                        WQ, WQ ? msq : 0, WQ ? Mp : 0, WQ ? Mp : 0, WQ ? extra : nullptr, 1, WQ ? q_upper : 0};
+    }
+    // the persistent loop kernels (loops.hip) build K(x_t, Z) row-major
+    SkinnyArgs loop_sk() const {
+        SkinnyArgs s = sk;
+        s.lda = Mp; s.a_trans = 0;
+        return s;
+    }
+};
+
+// the R x (D + C) input rows of step 0: a state (x_stride = 0: the same for every row) and the control row of step 0
+static std::vector<double> &start_rows(Scratch &sc, const double *x, int x_stride, const double *ctrl, int R, int D, int C) {
+    const int P = D + C;
+    std::vector<double> &xc0 = sc.host((size_t)R * P);
+    for (int r = 0; r < R; ++r) {
+        for (int d = 0; d < D; ++d) xc0[(size_t)r * P + d] = x[(size_t)r * x_stride + d];
+        for (int c = 0; c < C; ++c) xc0[(size_t)r * P + D + c] = ctrl[c];
+    }
+    return xc0;
+}
+
+// FFVD_STEP_LOOP=1: the whole loop as one persistent launch (launch_loop gets the zeroed counter block).  If a wait gave up (the grid
+// was not resident at once) the start rows are uploaded again and the per-step launches run.
+template <class LaunchLoop, class StepLaunches>
+static int run_step_loop(Scratch &sc, const char *who, int D, double *dxc, const std::vector<double> &xc0, LaunchLoop launch_loop,
+                         StepLaunches step_launches) {
+    const int nwords = loop_words(D);
+    int32_t *words = sc.alloc<int32_t>(nwords);
+    if (!words) return set_error(nullptr, FFVD_ENOMEM, std::string(who) + ": device allocation or upload failed");
+    OP_TRY(hipMemsetAsync(words, 0, (size_t)nwords * sizeof(int32_t), sc.stream));
+    launch_loop(words);
+    int32_t hw[4] = {0, 0, 0, 0};
+    OP_TRY(hipMemcpyAsync(hw, words, sizeof hw, hipMemcpyDeviceToHost, sc.stream));
+    OP_TRY(hipStreamSynchronize(sc.stream));
+    if (hw[1] != 0) {
+        OP_TRY(hipMemcpyAsync(dxc, xc0.data(), xc0.size() * sizeof(double), hipMemcpyHostToDevice, sc.stream));
+        step_launches();
+    }
+    return FFVD_OK;
+}
+
+// W = L^-T is upper triangular; when q_sqrt (one M x M slice) is too -- the reference hands over L_H^-T -- so is W q_sqrt, and the second
+// right-hand side of a step's product stops at a slab's last row like the first (exact zeros are skipped: half of its k range)
+static bool q_sqrt_is_upper(const double *q, int M) {
+    for (int i = 1; i < M; ++i)
+        for (int j = 0; j < i; ++j)
+            if (q[(size_t)i * M + j] != 0.0) return false;
+    return true;
+}
+
+extern "C" int ffvd_op_rollout_fallbacks(void) { return g_rollout_fallbacks; }
+
+extern "C" int ffvd_op_rollout(int kind, const double *Lm_inverse_seq, const double *Z, int M, int P, int D,
+                               const double *logvariance, const double *loglengthscales, const double *f,
+                               const double *q_sqrt, const double *x_last, int R, const double *ctrl, int C, int steps,
+                               const double *log_Q, const double *eps, double *predict_x, double *predict_var) {
+    if (!Lm_inverse_seq || !Z || !logvariance || !f || !x_last || !log_Q || !eps || !predict_x || !predict_var || R < 1 ||
+        steps < 0 || M < 1 || M > 2048 || D < 1 || C < 0 || P != D + C || P > MAXP || (C > 0 && !ctrl) ||
+        (kind == FFVD_KERNEL_SE && !loglengthscales))
+        return set_error(nullptr, FFVD_EINVAL, "ffvd_op_rollout: bad argument");
+    OP_BEGIN("ffvd_op_rollout");
+    if (steps == 0) return FFVD_OK;
+    StepSetup st(sc, R, M, D);
+    const int Mp = st.Mp, Tp = st.Tp, ng = st.ng, ngs = st.ngs;
+    const bool skinny = st.skinny;
+    std::vector<double> &xc0 = start_rows(sc, x_last, 0, ctrl, R, D, C);   // x_t = X[-1] (:226), every rollout; control row of step 0 (:293)
+    HyperView hv{};
+    if (int rc = stage_hypers(sc, "ffvd_op_rollout", kind, Z, M, Mp, P, D, logvariance, loglengthscales, hv)) return rc;
+    double *dW = upload_stack(sc, Lm_inverse_seq, D, M, Mp);
+    double *dxc = sc.upload(xc0.data(), xc0.size()), *dU = sc.upload(f, (size_t)M * D);
+    double *dxc2 = sc.alloc<double>(xc0.size());          // the rows of step t + 1 (the step kernel reads one buffer and writes the other)
+    double *dlq = sc.upload(log_Q, D), *deps = sc.upload(eps, (size_t)steps * R * D);
+    double *dctrl = C ? sc.upload(ctrl, (size_t)steps * C) : nullptr;
+    double *F = q_sqrt ? sc.alloc<double>((size_t)D * Tp * Mp) : nullptr;
+    double *dpx = sc.alloc<double>((size_t)R * steps * D), *dpv = sc.alloc<double>((size_t)R * steps * D);
+    const int q_upper = (q_sqrt && skinny && q_sqrt_is_upper(q_sqrt, M)) ? 1 : 0;
+    double *dQs = q_sqrt ? (skinny ? upload_stack(sc, q_sqrt, 1, M, Mp) /* (F is zero in the padded columns) */ : sc.upload(q_sqrt, (size_t)M * M)) : nullptr;   // slice d = 0 only
+    double *extra = q_sqrt ? sc.alloc<double>((size_t)D * (skinny ? ngs : 1) * Tp) : nullptr;
+    // skinny path: W q_sqrt once per call (D products of M^3), so that the inflation term is a second right-hand side of the
+    // step's one product instead of a dependent product on F
+    double *dWQ = (q_sqrt && skinny) ? sc.alloc<double>((size_t)D * Mp * Mp) : nullptr;
+    if (!dW || !dxc || !dxc2 || !dU || !dlq || !deps || (C && !dctrl) || !st.ok() || !dpx || !dpv || (q_sqrt && (!dQs || !extra || !F)) ||
+        (q_sqrt && skinny && !dWQ))
+        return set_error(nullptr, FFVD_ENOMEM, "ffvd_op_rollout: device allocation or upload failed");
+    st.fill(sc, kind, hv, dxc, P, M, dW, dU, F, dWQ, extra, q_upper);
+    // the whole loop is enqueued at once: steps x (K_fu rows, projection, [q_sqrt inflation], conditional, update)
+    if (dWQ)
+        ffvd::launch_skinny_gemm(sc.stream, dW, (size_t)Mp * Mp, Mp, dQs, 0, Mp, 0, Mp, Mp, Mp, D, Mp, dWQ, (size_t)Mp * Mp, Mp, nullptr, 0,
+                                 nullptr, nullptr);
+    double *xbuf[2] = {dxc, dxc2};                                           // input rows of step t in xbuf[t & 1]
+    auto step_launches = [&]() {                                              // three dependent launches per step
+        for (int t = 0; t < steps; ++t) {
+            st.pa.x = xbuf[t & 1];
+            if (skinny) {
+                launch_kfu_build_t(sc.stream, st.pa, Tp);                            // K(x_t, Z) per dim, m-major (coalesced operand loads)
+                // conditional_after_kernel_precalculation (:300) and, in the same launch, sum_j (F q_sqrt)_j^2 = |K (W q_sqrt)|^2 (:371-380)
+                launch_skinny_gemm(sc.stream, st.sk);
+            } else {
+                launch_kfu_build(sc.stream, st.pa);                                  // K(x_t, Z) per dim
+                launch_proj_gemm(sc.stream, st.pg);
+                if (q_sqrt) launch_qsqrt_inflation(sc.stream, F, (size_t)Tp * Mp, Tp, Mp, M, dQs, extra, R, D);
+            }
+            // conditional epilogue + x <- x + f_mu + eps sqrt(f_var + Q) in one launch (three dependent launches per step instead of five)
+            launch_rollout_finish_update(sc.stream, kind, hv.variance, st.rowsq, st.fmean, skinny ? ngs : ng, Tp, extra, skinny ? ngs : 1, dlq,
+                                         deps + (size_t)t * R * D, (C && t + 1 < steps) ? dctrl + (size_t)(t + 1) * C : nullptr, R, D, C, t,
+                                         steps, xbuf[t & 1], xbuf[(t + 1) & 1], dpx, dpv);
+        }
+    };
+    // Round 4: the whole loop as ONE persistent launch (loops.hip; the same kernel bodies: bit-identical) -- first
+    // with a grid-wide barrier between the phases (64.7 against 32.7 us per step at 32 rollouts: 160-512 workgroups on one counter),
+    // then with one role per workgroup and per-unit counters (40.3 against 36.0; 93 against 57 at 100 rollouts).  MEASURED SLOWER both
+    // times: ~170 agent-scope releases / acquires per step cost more than the three kernel boundaries they replace -- so it is opt-in:
+    // FFVD_STEP_LOOP=1.
+    const char *nsl = getenv("FFVD_STEP_LOOP");
+    const int loop_mode = (nsl && *nsl) ? atoi(nsl) : -1;
+    // Third form (loops.hip, rollout_resident_kernel; FFVD_STEP_LOOP=2): L^-T and W q_sqrt stay in LDS for the whole loop, three hand-offs
+    // per step.  Measured as the slope between 200 and 800 steps at M = 512, D = 4 (tools/rollout_modes.py): 16.6-19.2 us per step at 16
+    // rollouts, 19.3-23.9 at 32, 27-50 at 64 against 19.6-20.8 / 20.1-20.6 / 20.5-25.7 for the launches -- a hand-off among 32 workgroups
+    // costs 4-5 us here (release 2, wait + acquire 2.5-3: FFVD_RR_STAMPS=1), three of them are what three kernel boundaries cost.
+    // (Second measurement, with the hand-offs rebuilt without cache maintenance -- write-through stores and sc1 loads instead of fences, as in
+    //  the Gram kernel's tail exchange: 10.1-11.8 us per step at 16 rollouts, 13.6-17.9 at 32, 20.5-27 at 64.  The default up to 32 rollouts.)
+    // (Third measurement, the products' MFMA section branch-free per chunk: 10.4-12.5 / 12.5-15.4 / 17.9-22.5 us per step.  The default
+    //  wherever it applies: up to 64 rollouts, M <= 512, 8 latent dims.)
+    // (Round 5: with K^T operands, the XCD-mapped grid and long / short slabs paired per CU the per-step launches take 15.4-15.6 us
+    //  (18.4-21.8 with q_sqrt) from 40 to 64 rollouts, the resident loop 16.6-18.6 (20.3-23.4); at 32: 15.0 / 16.6 against 12.7 / 14.9,
+    //  profiles/r05_rollout_modes.txt -- the resident loop is the default up to 32 rollouts, FFVD_STEP_LOOP=2 asks for it up to 64.)
+    const bool resident = skinny && rollout_resident_ok(R, D, P, Mp) && (loop_mode == 2 || (loop_mode < 0 && R <= 32));
+    const bool use_loop = skinny && loop_mode == 1;
+    bool resident_done = false;
+    if (resident) {
+        const int RT = (R + 15) / 16, RP = 16 * RT, NS = Mp / 16;
+        int32_t *words = sc.alloc<int32_t>(rollout_resident_words());
+        double *Kt = sc.alloc<double>((size_t)D * Mp * RP), *part = sc.alloc<double>((size_t)D * NS * RP * 4);
+        double *xb = sc.alloc<double>((size_t)2 * RP * D), *dxl = sc.upload(x_last, D);
+        OP_CHECK(words && Kt && part && xb && dxl, "ffvd_op_rollout");
+        OP_TRY(hipMemsetAsync(words, 0, (size_t)rollout_resident_words() * sizeof(int32_t), sc.stream));
+        RolloutResidentArgs ra{};
+        ra.kind = kind; ra.R = R; ra.RT = RT; ra.D = D; ra.C = C; ra.P = P; ra.M = M; ra.Mp = Mp; ra.steps = steps; ra.NS = NS;
+        ra.hv = hv; ra.W = dW; ra.w_stride = (size_t)Mp * Mp; ra.WQ = q_sqrt ? dWQ : nullptr; ra.wq_upper = q_sqrt ? q_upper : 0; ra.ucol = st.ucol;
+        ra.log_Q = dlq; ra.eps = deps; ra.ctrl = dctrl; ra.x_last = dxl; ra.Kt = Kt; ra.part = part; ra.xbuf = xb;
+        ra.predict_x = dpx; ra.predict_var = dpv; ra.words = words; ra.abort_w = words + 1;
+        long long *dst = nullptr;
+        if (getenv("FFVD_RR_STAMPS")) { dst = sc.alloc<long long>(32); if (dst) OP_TRY(hipMemsetAsync(dst, 0, 32 * sizeof(long long), sc.stream)); }
+        ra.stamps = dst;
+        ra.test_stall = getenv("FFVD_RR_TEST_STALL") ? 1 : 0;
+        const int lrc = launch_rollout_resident(sc.stream, ra);
+        if (lrc == 0) {
+            int32_t hw[4] = {0, 0, 0, 0};
+            OP_TRY(hipMemcpyAsync(hw, words, sizeof hw, hipMemcpyDeviceToHost, sc.stream));
+            OP_TRY(hipStreamSynchronize(sc.stream));
+            resident_done = hw[1] == 0;          // (a wait gave up: the per-step launches below, from the initial rows)
+            if (!resident_done) {
+                // the two forms agree to 1e-9, not bit for bit, so a fallback decided by run-time contention must not be
+                // silent -- counted (ffvd_op_rollout_fallbacks) and left as a warning for ffvd_last_error(NULL)
+                ++g_rollout_fallbacks;
+                set_error(nullptr, FFVD_OK,
+                          "warning: ffvd_op_rollout: the resident-operand loop gave up on a bounded wait (its workgroups were not all "
+                          "resident: another tenant on the GPU?); the call was completed by the per-step launches, whose results "
+                          "agree to 1e-9 but are not bit-identical (FFVD_STEP_LOOP=0 selects them always)");
+            }
+            if (dst && steps > 10) {             // tools: where step 10 spent its time (us since its start), slab 0 (the updater) and the last slab of dim 0
+                long long hs[32];
+                OP_TRY(hipMemcpy(hs, dst, sizeof hs, hipMemcpyDeviceToHost));
+                static const char *nm[12] = {"start", "x_t seen", "inputs staged", "K stored", "K counted", "all K seen", "products", "partials stored",
+                                             "partials counted", "all partials seen", "updated", "x counted"};
+                for (int w = 0; w < 2; ++w) {
+                    fprintf(stderr, "rollout_resident R=%d q=%d slab %s:", R, q_sqrt ? 1 : 0, w ? "last" : "0");
+                    for (int i = 1; i < 12; ++i) if (hs[16 * w + i]) fprintf(stderr, "  %s %.2f", nm[i], (double)(hs[16 * w + i] - hs[16 * w]) / 100.0);
+                    fprintf(stderr, "\n");
+                }
+            }
+        } else (void)hipGetLastError();
+    }
+    if (resident_done) {
+    } else if (use_loop) {
+        RolloutLoopArgs la{};
+        la.pa = st.pa;
+        la.sk = st.loop_sk();
+        la.f = FinishIn{kind, D + C, ngs, Tp, D, ngs, hv.variance, st.rowsq, st.fmean, extra};
+        la.log_Q = dlq; la.eps = deps; la.ctrl = dctrl; la.R = R; la.C = C; la.steps = steps;
+        la.xbuf0 = xbuf[0]; la.xbuf1 = xbuf[1]; la.predict_x = dpx; la.predict_var = dpv;
+        const int rc = run_step_loop(sc, "ffvd_op_rollout", D, dxc, xc0, [&](int32_t *words) {
+            la.bar = reinterpret_cast<unsigned *>(words); la.abort_w = words + 1;
+            launch_rollout_loop(sc.stream, la);
+        }, step_launches);
+        if (rc) return rc;
+    } else step_launches();
+    OP_TRY(hipGetLastError());
+    OP_TRY(hipMemcpyAsync(predict_x, dpx, (size_t)R * steps * D * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
+    OP_TRY(hipMemcpyAsync(predict_var, dpv, (size_t)R * steps * D * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
+    OP_TRY(hipStreamSynchronize(sc.stream));
+    return FFVD_OK;
+}
+
+// G posteriors, one launch per step for all of them (rollout_group.hip)
+extern "C" int ffvd_op_rollout_grouped(int kind, int G, const double *const *Lm_inverse_seqs, const double *Zs, int M, int P, int D,
+                                       const double *logvariances, const double *loglengthscales, const double *fs,
+                                       const double *const *q_sqrts, const double *x_lasts, int R, const double *ctrl, int C, int steps,
+                                       const double *log_Qs, const double *eps, double *predict_x, double *predict_var) {
+    const char *bad = "ffvd_op_rollout_grouped: bad argument";
+    if ((kind != FFVD_KERNEL_SE && kind != FFVD_KERNEL_LINEAR) || G < 0 || R < 1 || steps < 0 || M < 1 || M > 2048 || D < 1 || C < 0 ||
+        P != D + C || P > MAXP)
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    const int Mp = round_up(M, RG_SLAB), NS = Mp / RG_SLAB;
+    if ((long long)G * D * Mp * Mp > (1LL << 29) || (long long)G * R > (1LL << 20) || (R + RG_RC - 1) / RG_RC > 65535 ||
+        (long long)G * D * NS >= (1LL << 31))
+        return set_error(nullptr, FFVD_EINVAL, "ffvd_op_rollout_grouped: bad argument (beyond the limits of rollout_group.h)");
+    if (G == 0 || steps == 0) return FFVD_OK;
+    if (!Lm_inverse_seqs || !Zs || !logvariances || !fs || !x_lasts || !log_Qs || !eps || !predict_x || !predict_var ||
+        (C > 0 && !ctrl) || (kind == FFVD_KERNEL_SE && !loglengthscales))
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    const size_t GD = (size_t)G * D, out_n = (size_t)G * R * steps * D;
+    for (size_t b = 0; b < GD; ++b) if (!Lm_inverse_seqs[b]) return set_error(nullptr, FFVD_EINVAL, bad);
+    if (q_sqrts)
+        for (int g = 0; g < G; ++g) if (!q_sqrts[g]) return set_error(nullptr, FFVD_EINVAL, bad);
+    OP_BEGIN("ffvd_op_rollout_grouped");
+    LapTimer timer("FFVD_RG_TIMING", "ffvd_op_rollout_grouped", sc.stream);
+    // The big operands are NOT packed on the host: every M x M matrix goes from where the caller keeps it straight into its slot of the
+    // padded device stack (a pitched copy when M is not a multiple of 16; the padding is zeroed on the device).
+    auto upload_matrices = [&](const double *const *src, size_t n) -> double * {
+        double *dst = sc.alloc<double>(n * Mp * Mp);
+        if (!dst) return nullptr;
+        if (Mp != M && hipMemsetAsync(dst, 0, n * Mp * Mp * sizeof(double), sc.stream) != hipSuccess) return nullptr;
+        for (size_t b = 0; b < n; ++b) {
+            const hipError_t e = (Mp == M)
+                ? hipMemcpyAsync(dst + b * Mp * Mp, src[b], (size_t)M * M * sizeof(double), hipMemcpyHostToDevice, sc.stream)
+                : hipMemcpy2DAsync(dst + b * Mp * Mp, (size_t)Mp * sizeof(double), src[b], (size_t)M * sizeof(double),
+                                   (size_t)M * sizeof(double), M, hipMemcpyHostToDevice, sc.stream);
+            if (e != hipSuccess) return nullptr;
+        }
+        return dst;
+    };
+    double *dW = upload_matrices(Lm_inverse_seqs, GD);
+    timer.lap("W uploaded");
+    // W q_sqrt is upper triangular when every group's q_sqrt slice is (the reference hands over L_H^-T): the step products then stop at
+    // a slab's last row for both right-hand sides.  Otherwise they walk all rows; for a group whose slice IS upper triangular the extra
+    // terms are exact zeros, so its results do not depend on what the other groups hold.
+    int q_upper = q_sqrts ? 1 : 0;
+    for (int g = 0; q_upper && g < G; ++g) q_upper = q_sqrt_is_upper(q_sqrts[g], M) ? 1 : 0;
+    timer.lap("q_sqrt scanned");
+    double *dq = q_sqrts ? upload_matrices(q_sqrts, (size_t)G) : nullptr;
+    double *dB = q_sqrts ? sc.alloc<double>(GD * Mp * Mp) : nullptr;
+    double *dZ = sc.upload(Zs, (size_t)G * M * P), *dU = sc.upload(fs, (size_t)G * M * D), *dxl = sc.upload(x_lasts, GD);
+    double *dlv = sc.upload(logvariances, GD), *dll = loglengthscales ? sc.upload(loglengthscales, GD * P) : nullptr;
+    double *dlq = sc.upload(log_Qs, GD), *deps = sc.upload(eps, (size_t)steps * G * R * D);
+    double *dctrl = C ? sc.upload(ctrl, (size_t)steps * C) : nullptr;
+    double *variance = sc.alloc<double>(GD), *len = sc.alloc<double>(GD * P), *Zsc = sc.alloc<double>(GD * Mp * P), *zz = sc.alloc<double>(GD * Mp);
+    double *part = sc.alloc<double>((size_t)2 * GD * NS * R * 4), *xbuf = sc.alloc<double>((size_t)2 * G * R * D);
+    double *dpx = sc.alloc<double>(out_n), *dpv = sc.alloc<double>(out_n);
+    OP_CHECK(dW && dZ && dU && dxl && dlv && dlq && deps && (!C || dctrl) && (!loglengthscales || dll) && variance && len && Zsc && zz &&
+             part && xbuf && dpx && dpv && (!q_sqrts || (dq && dB)), "ffvd_op_rollout_grouped");
+    timer.lap("q_sqrt, small arrays uploaded");
+    launch_rg_prep(sc.stream, kind, G, D, M, Mp, P, dZ, dlv, dll, variance, len, Zsc, zz);
+    if (q_sqrts) launch_rg_wq(sc.stream, G, D, Mp, q_upper, dW, dq, dB);
+    timer.lap("hyper-parameters, W q_sqrt");
+    RolloutGroupArgs a{};
+    a.kind = kind; a.G = G; a.R = R; a.D = D; a.C = C; a.P = P; a.M = M; a.Mp = Mp; a.NS = NS; a.steps = steps;
+    a.has_q = q_sqrts ? 1 : 0; a.q_upper = q_upper;
+    a.W = dW; a.B = dB; a.Zs = Zsc; a.zz = zz; a.variance = variance; a.len = len; a.f = dU; a.x_last = dxl; a.log_Q = dlq;
+    a.ctrl = dctrl; a.eps = deps; a.part = part; a.xbuf = xbuf; a.predict_x = dpx; a.predict_var = dpv;
+    for (int t = 0; t <= steps; ++t) launch_rg_step(sc.stream, a, t);
+    OP_TRY(hipGetLastError());
+    timer.lap("step launches");
+    if (!sc.download(predict_x, dpx, out_n * sizeof(double)) || !sc.download(predict_var, dpv, out_n * sizeof(double)))
+        return set_error(nullptr, FFVD_EDEVICE, "ffvd_op_rollout_grouped: copying the results back failed");
+    timer.lap("results downloaded");
+    return FFVD_OK;
+}
+
+extern "C" int ffvd_op_pg_sweep(int kind, const double *Lm_inverse_seq, const double *Z, int M, int P, int D,
+                                const double *logvariance, const double *loglengthscales, const double *U,
+                                const double *X_ref, int X_N, const double *Y, int Ydim, const double *ctrl, int C,
+                                const double *CC, const double *DD, const double *Rchols, const double *log_Q, int n_free,
+                                const double *x0, const double *eps, const double *unif, double *particles, int32_t *idx) {
+    if (!Lm_inverse_seq || !Z || !logvariance || !U || !X_ref || !Y || !CC || !DD || !Rchols || !log_Q || !x0 || !eps ||
+        !unif || !particles || !idx || n_free < 1 || n_free + 1 > 1024 || X_N < 1 || M < 1 || M > 2048 || D < 1 || C < 0 ||
+        P != D + C || P > MAXP || Ydim < 1 || Ydim > 8 || (C > 0 && !ctrl) || (kind == FFVD_KERNEL_SE && !loglengthscales))
+        return set_error(nullptr, FFVD_EINVAL, "ffvd_op_pg_sweep: bad argument");
+    for (int j = 0; j < Ydim; ++j)
+        if (!(Rchols[(size_t)j * Ydim + j] > 0.0)) return set_error(nullptr, FFVD_EINVAL, "ffvd_op_pg_sweep: Rchols diagonal must be positive");
+    OP_BEGIN("ffvd_op_pg_sweep");
+    const int R = n_free, steps = X_N - 1;
+    memcpy(particles, x0, (size_t)R * D * sizeof(double));                                   // particles[0] (:87)
+    if (steps == 0) return FFVD_OK;
+    StepSetup st(sc, R, M, D);
+    const int Mp = st.Mp, Tp = st.Tp, ngs = st.ngs;
+    const bool skinny = st.skinny;
+    std::vector<double> &xc0 = start_rows(sc, x0, D, ctrl, R, D, C);                          // control row of step 0 (:93)
+    LapTimer timer("FFVD_PG_TIMING", "ffvd_op_pg_sweep", sc.stream);
+    double *dW = upload_stack(sc, Lm_inverse_seq, D, M, Mp);
+    timer.lap("L^-T uploaded");
+    HyperView hv{};
+    if (int rc = stage_hypers(sc, "ffvd_op_pg_sweep", kind, Z, M, Mp, P, D, logvariance, loglengthscales, hv)) return rc;
+    double *dxc = sc.upload(xc0.data(), xc0.size()), *dU = sc.upload(U, (size_t)M * D);
+    double *dlq = sc.upload(log_Q, D);
+    double *deps = sc.upload(eps, (size_t)steps * R * D), *dun = sc.upload(unif, (size_t)steps * R);
+    timer.lap("draws uploaded");
+    double *dctrl = C ? sc.upload(ctrl, (size_t)steps * C) : nullptr;
+    double *dXr = sc.upload(X_ref, (size_t)X_N * D), *dY = sc.upload(Y, (size_t)steps * Ydim);
+    double *dCC = sc.upload(CC, (size_t)D * Ydim), *dDD = sc.upload(DD, Ydim), *dR = sc.upload(Rchols, (size_t)Ydim * Ydim);
+    double *dmean = sc.alloc<double>((size_t)R * D), *dvar = sc.alloc<double>((size_t)R * D);
+    double *cand = sc.alloc<double>((size_t)(R + 1) * D);
+    double *dparts = sc.alloc<double>((size_t)steps * R * D);
+    int32_t *didx = sc.alloc<int32_t>((size_t)steps * R);
+    if (!dW || !dxc || !dU || !dlq || !deps || !dun || (C && !dctrl) || !dXr || !dY || !dCC || !dDD || !dR || !st.ok() || !dmean || !dvar ||
+        !cand || !dparts || !didx)
+        return set_error(nullptr, FFVD_ENOMEM, "ffvd_op_pg_sweep: device allocation or upload failed");
+    st.fill(sc, kind, hv, dxc, P, M, dW, dU, nullptr, nullptr, nullptr, 0);
+    // the whole sweep is enqueued at once: steps x (K_fu rows, projection, conditional, propagate + weight + resample)
+    auto step_launches = [&]() {
+        for (int t = 0; t < steps; ++t) {
+            if (skinny) {                               // K(x_t, Z) m-major: the skinny product's operand loads coalesce
+                launch_kfu_build_t(sc.stream, st.pa, Tp);
+                launch_skinny_gemm(sc.stream, st.sk);
+            } else { launch_kfu_build(sc.stream, st.pa); launch_proj_gemm(sc.stream, st.pg); }                          // conditional_after_kernel_precalculation (:95-97)
+            const double *ctrl_next = (C && t + 1 < steps) ? dctrl + (size_t)(t + 1) * C : nullptr;
+            launch_conditional_finish(sc.stream, kind, dxc, R, P, hv.variance, st.rowsq, st.fmean, ngs, Tp, D, dmean, dvar, nullptr);
+            launch_pg_step(sc.stream, dmean, dvar, dlq, deps + (size_t)t * R * D, dun + (size_t)t * R, dY + (size_t)t * Ydim,
+                           dXr + (size_t)(t + 1) * D, dCC, dDD, dR, ctrl_next,
+                           R, D, C, Ydim, dxc, cand, dparts + (size_t)t * R * D, didx + (size_t)t * R);
+        }
+    };
+    // Round 4: ONE persistent launch for the sweep (loops.hip), three grid-wide barriers per step instead of four dependent launches:
+    // measured slower (86 against 43 us per step with roles and per-unit counters, 151 with a grid-wide barrier; see ffvd_op_rollout), opt-in with FFVD_STEP_LOOP=1
+    const char *nsl = getenv("FFVD_STEP_LOOP");
+    const bool use_loop = skinny && nsl && *nsl && strcmp(nsl, "0") != 0;
+    if (use_loop) {
+        PgLoopArgs la{};
+        la.pa = st.pa;
+        la.sk = st.loop_sk();
+        la.kind = kind; la.R = R; la.D = D; la.C = C; la.Ydim = Ydim; la.steps = steps; la.ngs = ngs;
+        la.variance = hv.variance; la.rowsq = st.rowsq; la.fmean = st.fmean; la.mean = dmean; la.var = dvar; la.cand = cand; la.parts = dparts;
+        la.idx = didx; la.log_Q = dlq; la.eps = deps; la.unif = dun; la.Y = dY; la.X_ref = dXr; la.CC = dCC; la.DD = dDD; la.Rch = dR;
+        la.ctrl = dctrl;
+        const int rc = run_step_loop(sc, "ffvd_op_pg_sweep", D, dxc, xc0, [&](int32_t *words) {
+            la.bar = reinterpret_cast<unsigned *>(words); la.abort_w = words + 1;
+            launch_pg_loop(sc.stream, la);
+        }, step_launches);
+        if (rc) return rc;
+    } else {
+        timer.lap("uploads and set-up");
+        step_launches();
+        timer.lap("steps enqueued", false);        // how long the host takes to enqueue the sweep ...
+        timer.lap("steps drained");                // ... and how long the GPU needs after that
+    }
+    OP_TRY(hipGetLastError());
+    if (!sc.download(particles + (size_t)R * D, dparts, (size_t)steps * R * D * sizeof(double)) ||
+        !sc.download(idx, didx, (size_t)steps * R * sizeof(int32_t)))
+        return set_error(nullptr, FFVD_EDEVICE, "ffvd_op_pg_sweep: copying the results to the host failed");
+    timer.lap("results to the host");
+    return FFVD_OK;
+}
