@@ -1,6 +1,7 @@
 // C ABI of libffvd_hip.so (see include/ffvd_abi.h): handle lifetime, resident buffers, the per-iteration
-// launch sequence of the ELBO, training steps, T-shards and RCCL.  The stateless ffvd_op_* operators are in ops.hip.
-#include "abi_internal.h"
+// launch sequence of the ELBO, training steps, T-shards and RCCL.  The multi-kernel backward pass is in backward.hip (the handle
+// both see: handle.h), the stateless ffvd_op_* operators are in ops.hip.
+#include "handle.h"
 #include "kernels.h"
 #include "kernels_f32.h"
 #include "grad.h"
@@ -21,135 +22,6 @@ using namespace ffvd;
 static thread_local std::string g_last_error;
 std::string &ffvd::last_error() { return g_last_error; }
 
-struct ffvd_handle {
-    ffvd_config cfg;
-    int P = 0, Mp = 0, Tp = 0, Dl = 0, nbatch = 0, ng = 0, cpp = 0;
-    hipStream_t stream = nullptr;
-    double *dinvK = nullptr, *dinvH = nullptr;   // Cholesky scratch (kernels.h DINV_STRIDE per matrix)
-    double *gpart = nullptr;                     // split-K partial tiles of the Gram kernel (few units per pass)
-    int gsplit = 1;
-    bool side_late = false;     // few chains, forward: the K_uu side chain as ONE dataflow launch BEHIND the tile pass (plan_schedule); decided with gsplit at create
-    double *graw = nullptr;                      // unsplit first pass: raw Gram tiles for the deferred trace pass
-    double *gtail = nullptr;                     // unsplit passes: blocks + counters of the tail split (kernels.h GramArgs)
-    int gtail_wg = 0;
-    double *lrpart = nullptr;                    // LinearK explicit-U forward: partial sums of G = C C^T and v = C u per column block (kernels.h)
-    double *growpart = nullptr;                  // Gram route: per-64-row-block partial sums of delta^T K_fu from the K_fu build
-    hipStream_t aux = nullptr;          // side stream: the K_uu chain runs beside the K_fu build (Gram route)
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_join2 = nullptr, ev_kuu = nullptr, ev_tiles = nullptr, ev_go = nullptr;
-    hipEvent_t ev_hwords = nullptr;     // recorded right behind a side-stream clear of Cholesky(A)'s progress words: the launch that trusts the clear waits for IT
-    hipEvent_t ev_prior = nullptr;      // recorded behind an early prior-sums launch on the side stream (fwd_prior_sums)
-    double *prior_sums = nullptr;       // [16] the ten parameter-only sums of the nll assembly, formed early in the iteration
-    std::string err;
-    std::vector<void *> allocs;
-    int64_t ws_bytes = 0;
-    // diagnostic switches, read from the environment ONCE when the handle is created
-    struct Switches {
-        bool grad_explicit = false;       // FFVD_GRAD_EXPLICIT=1: the explicit-inverse backward pass
-        bool no_defer_trace = false;      // FFVD_NO_DEFER_TRACE=1: trace partials in the Gram / combine epilogue (the main stream then waits for K^-1)
-        bool no_kfu_first = false;        // FFVD_NO_KFU_FIRST=1: the side chain enqueued before the main stream's K_fu build (unsplit pass with raw tiles)
-        bool grad_serial = false;         // FFVD_GRAD_SERIAL=1: the K_uu side of the backward pass on the main stream
-        bool no_linear_lowrank = false;   // FFVD_NO_LINEAR_LOWRANK=1: LinearK explicit-U forward through the M-wide projection (rounds 1-2)
-        bool lt_armed = false;            // FFVD_GRAD_LT_ARMED=1: write the L^T rows to memory (launch_set_lt_rows) even where the dataflow kernel could read L itself
-        bool whiten_products = false;     // FFVD_GRAD_WHITEN_PRODUCTS=1: training forward forms H = W^T A W with two products (round 1/2) instead of arming L^T rows
-        bool debug_sync = false;    // FFVD_DEBUG_SYNC: name every launch group on stderr and wait for it (locates a faulting kernel)
-        int side_delay_us = 0;      // FFVD_DEBUG_SIDE_DELAY_US=n: a spin kernel of n us at the head of every side-stream fork (schedule tests: results
-        int main_delay_us = 0;      //   must not depend on which stream is late); FFVD_DEBUG_MAIN_DELAY_US=n: the same on the main stream behind a fork
-        bool no_tiny = false;       // FFVD_NO_TINY=1: the multi-kernel schedule also at the reference's own experiment size (rounds 1-3)
-        bool no_tiny_a = false;     // FFVD_NO_TINY_A=1: ... for the explicit-U branch only (rounds 1-4)
-    } sw;
-    // resident parameters / data (handle-owned copies)
-    double *X = nullptr, *Z = nullptr, *U = nullptr, *logvar = nullptr, *loglen = nullptr, *logQ = nullptr;
-    double *CC = nullptr, *DD = nullptr, *logR = nullptr, *Y = nullptr, *ctrl = nullptr;
-    ffvd_params cur{};          // pointers the kernels read (resident copies or caller's device pointers)
-    bool have_params = false, have_data = false;
-    void *comm = nullptr;       // RCCL communicator created by ffvd_comm_init (owned by the handle), else null
-    int comm_world = 1, comm_rank = 0;
-    int tiny_cus = 0;           // compute units of the device (one-launch plan)
-    double *tsbuf = nullptr;    // T-shard exchange buffer: [nbatch][(Mp+1) x Mp] raw Gram tiles + delta^T K_fu rows, then [S][8] chain sums
-    int64_t ts_count = 0;
-    double *stage = nullptr;    // staging buffer of ffvd_allreduce_sum
-    int64_t stage_count = 0;
-    bool kuu_flow_sched = false;   // schedule of the big unsplit Gram pass, decided in ffvd_create (see there)
-    // one-launch iteration of the reference's own experiment size (tiny.hip): decided once in ffvd_create
-    TinyPlan tiny{};
-    double *tiny_scratch = nullptr;
-    int *tiny_flags = nullptr;
-    TinyArgs *tiny_dargs = nullptr;     // [2] device copies of the argument block (forward / forward + backward)
-    TinyArgRing tiny_ring[2];           // per copy: pinned upload slots guarded by events + what the device copy holds (tiny.h)
-    bool tiny_ring_made = false;
-    size_t tiny_private_bytes = 0;      // scratch per lane of the one-launch kernel as the loaded code object reports it
-    bool tiny_dirty = false;       // a launch was abandoned on a bounded wait: its hand-off words are re-zeroed before the next one
-    bool info_pending = false;  // an ffvd_elbo_async was enqueued whose Cholesky info flags nobody has looked at yet
-    // workspace
-    double *variance = nullptr, *len = nullptr, *Zs = nullptr, *zz = nullptr;
-    double *Kuu = nullptr, *F = nullptr, *H = nullptr, *rowsq = nullptr, *fmean = nullptr;
-    double *ucolA = nullptr;        // explicit-U branch: U columns of the local dims, zero padded to Mp
-    double *Kf2 = nullptr;          // reference route, branch B: K_fu (input of the projection GEMM); F keeps K_fu L^-T
-    int ngr = 0;                    // row-sum partials per unit in that path (128-column tiles)
-    // fp32-contraction path (cfg.dtype == FFVD_F32C): K_fu, F = K_fu L^-T, L^-1 as fp32 GEMM operands; per-tile and
-    // per-unit sums of F^2 (fp64)
-    float *Kf32 = nullptr, *F32 = nullptr, *Linv32 = nullptr;
-    double *sqpart = nullptr, *sqsum = nullptr;
-    int nsq = 0;
-    double *Kcopy = nullptr, *Linv = nullptr, *Kinv = nullptr, *trpart = nullptr, *kterms = nullptr;   // GRAM route
-    int ntiles = 0;
-    double *chain_partial = nullptr;
-    // backward-pass workspace (cfg.grad)
-    struct GradWs {
-        double *Acopy = nullptr, *u = nullptr, *LAinv = nullptr, *Gamma = nullptr, *gam_part = nullptr, *uku = nullptr;
-        // whitened backward (collapsed branch): T1 = A W, later B = L_H^-1 L^-1; w = H^-1 b; b = W^T c staging; identity
-        // matrix (w^T w through the u^T K u kernel); two more per-dim products of the K_uu side
-        double *T1 = nullptr, *wv = nullptr, *bw = nullptr, *Ident = nullptr, *P2 = nullptr, *P3 = nullptr;
-        bool whitened = false;
-        double *E = nullptr, *rp = nullptr, *rsum = nullptr, *ez = nullptr, *kfu = nullptr;
-        float *Gam32 = nullptr;         // fp32-contraction backward: Gamma rounded to fp32, the right operand of R = K_fu Gamma
-        double *fsq = nullptr;          // reference route, fp64: sum_t |F_t|^2 per unit (the fp32 path has sqsum)
-        double *cs_part = nullptr, *etx_part = nullptr, *rx2_part = nullptr, *dz_unit = nullptr, *dll_unit = nullptr, *dls_unit = nullptr;
-        double *Asum = nullptr, *GamSum = nullptr, *Gs = nullptr, *gsum = nullptr, *P1 = nullptr, *KGK = nullptr, *Epsi = nullptr;
-        double *rsum2 = nullptr, *ez2 = nullptr, *cs2 = nullptr, *etx2 = nullptr, *rx22 = nullptr, *dz_kuu = nullptr, *dll_kuu = nullptr, *dls_kuu = nullptr;
-        double *shared_part = nullptr, *dX = nullptr, *dZ = nullptr, *dlogvar = nullptr, *dloglen = nullptr, *dlogQ = nullptr;
-        size_t small_count = 0;         // doubles in the block dlogvar | dloglen | dlogQ | dCC | dDD | dlogR (one allocation)
-        double *dCC = nullptr, *dDD = nullptr, *dlogR = nullptr;
-        // explicit-U branch
-        double *Gu = nullptr, *Gsum = nullptr, *r = nullptr, *dalpha = nullptr, *ucol = nullptr, *beta = nullptr, *du = nullptr;
-        double *GammaA = nullptr, *Lclean = nullptr, *dU = nullptr, *xsq = nullptr;
-        int ngam = 0, sp_stride = 0;
-        // Exchange block of a sharded training step (ffvd_adam_step_allreduce): [8 term sums | dZ | dlogvar..dlogR | dU | dX],
-        // every segment starting on a 256-byte boundary.  The gradient arrays above ARE these segments, so the block is
-        // all-reduced in place with no packing pass; dX comes last because chain shards keep it out of the exchange.
-        double *pack = nullptr;
-        size_t pack_shared = 0, pack_total = 0;     // doubles up to (excluding) dX / including dX
-    } gw;
-    double *hterms = nullptr, *chain_terms = nullptr, *chain_nll = nullptr, *out_terms = nullptr;
-    int32_t *info = nullptr;
-    // Adam state for ffvd_adam_step: first/second moments per parameter array (order of FFVD_TRAIN_* bits), step count
-    double *adam_m[9] = {nullptr}, *adam_v[9] = {nullptr};
-    double *hmc[9][5] = {{nullptr}};     // SG-HMC state per array: xi, g, g2, p and the uploaded noise
-    bool hmc_ready = false;
-    int64_t adam_t = 0;
-    bool adam_ready = false;
-    // pinned host staging
-    // result block: [8 term sums][S_local chain nll][Dl + nbatch info flags], contiguous on the device (resblk) and in
-    // pinned host memory (h_res) so that one copy brings everything back; out_terms / chain_nll / info and h_out /
-    // h_chain / h_info point into the two blocks
-    double *resblk = nullptr, *h_res = nullptr;
-    size_t res_bytes = 0;
-    double *h_out = nullptr, *h_chain = nullptr, *h_sums = nullptr;
-    int32_t *h_info = nullptr;
-    int train_S_total = 0;
-    bool stalled = false;       // check_info saw info = -1: the dataflow Cholesky gave up on a bounded wait
-    int stall_recoveries = 0;   // iterations re-run with the launch-per-column Cholesky after such a stall
-    int stall_hold = 0;         // > 0: this many further calls stay on the schedule without inter-workgroup waits (fetch_with_stall_recovery)
-    int stall_hold_next = 16;   // length of the next hold: doubles with every stalled probe (cap 1024), back to 16 after a clean one
-    long long enq_ns = 0, enq_calls = 0;      // host time spent enqueueing iterations (ffvd_debug_enqueue_us: tools)
-    std::string warning;        // one-time note about the first recovery (ffvd_last_error returns it while no error is pending)      // > 0: ffvd_train_local has left a backward pass (scaled 1 / S_total) in gw.pack
-    // optional live stage timing (HIP events on the handle's stream)
-    bool timing_on = false;
-    std::vector<hipEvent_t> ev_pool;
-    std::vector<int> ev_stage;
-    size_t ev_used = 0;
-};
-
 // fixed sizes of the schedule (plan_schedule, create_impl)
 constexpr int F32C_FLUSH_TILES = 128;       // fp32 summation chains of the Gram product are cut every 4096 rows (128 t-tiles of 32 rows)
 constexpr int SMALL_SIDE_WGS = 512;         // tile-pass workgroups (one round of the chip) up to which an iteration counts as tiny (small_side)
@@ -159,17 +31,6 @@ int ffvd::set_error(ffvd_handle *h, int code, const std::string &msg) {
     if (h) h->err = msg;
     g_last_error = msg;
     return code;
-}
-
-template <class T>
-static hipError_t dev_alloc(ffvd_handle *h, T **p, size_t count) {
-    size_t bytes = (count ? count : 1) * sizeof(T);
-    hipError_t e = hipMalloc((void **)p, bytes);
-    if (e == hipSuccess) {
-        h->allocs.push_back((void *)*p);
-        h->ws_bytes += (int64_t)bytes;
-    }
-    return e;
 }
 
 extern "C" const char *ffvd_last_error(const ffvd_handle *h) {
@@ -305,65 +166,7 @@ static int create_impl(const ffvd_config *cfg, ffvd_handle *h) {
         HIP_TRY(dev_alloc(h, &h->trpart, (size_t)h->nbatch * h->ntiles));
         HIP_TRY(dev_alloc(h, &h->kterms, Dl * 2));
     }
-    if (c.grad) {
-        ffvd_handle::GradWs &g = h->gw;
-        const size_t nbt = h->nbatch, msq = Mp * Mp, nblk = Tp / 64, nblk2 = Mp / 64, S = c.S_local, J = c.Ydim;
-        g.ngam = atb_ntiles_sym64(h->Mp);        // the Gamma launch uses the 64 x 64-tile kernel
-        g.sp_stride = c.D * c.Ydim + 2 * c.Ydim + (int)Dl;
-        HIP_TRY(dev_alloc(h, &g.Acopy, nbt * msq));      HIP_TRY(dev_alloc(h, &g.u, nbt * Mp));
-        HIP_TRY(dev_alloc(h, &g.LAinv, nbt * msq));      HIP_TRY(dev_alloc(h, &g.Gamma, nbt * msq));
-        HIP_TRY(dev_alloc(h, &g.gam_part, nbt * g.ngam)); HIP_TRY(dev_alloc(h, &g.uku, nbt));
-        if (c.dtype == FFVD_F32C) HIP_TRY(dev_alloc(h, &g.Gam32, nbt * msq));                          // E formed on the fly from fp32 operands
-        else if (P <= 6) HIP_TRY(dev_alloc(h, &g.rp, bwd_fused_rp_doubles((int)Mp, (int)Tp, (int)nbt)));   // fused E reductions
-        else HIP_TRY(dev_alloc(h, &g.E, nbt * Tp * Mp));
-        if (grad_ref && c.dtype != FFVD_F32C) HIP_TRY(dev_alloc(h, &g.fsq, nbt));
-        HIP_TRY(dev_alloc(h, &g.rsum, nbt * Tp));        HIP_TRY(dev_alloc(h, &g.ez, nbt * Tp * P));
-        HIP_TRY(dev_alloc(h, &g.kfu, nbt * Tp));
-        HIP_TRY(dev_alloc(h, &g.cs_part, nbt * nblk * Mp)); HIP_TRY(dev_alloc(h, &g.etx_part, nbt * nblk * Mp * P));
-        HIP_TRY(dev_alloc(h, &g.rx2_part, nbt * nblk * P));
-        HIP_TRY(dev_alloc(h, &g.dz_unit, nbt * c.M * P)); HIP_TRY(dev_alloc(h, &g.dll_unit, nbt * P));
-        HIP_TRY(dev_alloc(h, &g.dls_unit, nbt));
-        HIP_TRY(dev_alloc(h, &g.Asum, Dl * msq));  HIP_TRY(dev_alloc(h, &g.GamSum, Dl * msq)); HIP_TRY(dev_alloc(h, &g.Gs, Dl * msq));
-        HIP_TRY(dev_alloc(h, &g.gsum, Dl * msq));  HIP_TRY(dev_alloc(h, &g.P1, Dl * msq));     HIP_TRY(dev_alloc(h, &g.KGK, Dl * msq));
-        HIP_TRY(dev_alloc(h, &g.Epsi, Dl * msq));
-        // (the reference route factorises H = I + F^T F / Q itself: its backward pass is the whitened one by construction)
-        g.whitened = c.branch == FFVD_BRANCH_B && (!h->sw.grad_explicit || grad_ref);
-        if (g.whitened) {
-            HIP_TRY(dev_alloc(h, &g.T1, nbt * msq));
-            HIP_TRY(dev_alloc(h, &g.wv, nbt * Mp));    HIP_TRY(dev_alloc(h, &g.bw, nbt * Mp));
-            HIP_TRY(dev_alloc(h, &g.Ident, msq));      HIP_TRY(dev_alloc(h, &g.P2, Dl * msq)); HIP_TRY(dev_alloc(h, &g.P3, Dl * msq));
-            launch_set_identity(h->stream, g.Ident, 0, 0, (int)Mp, 1);
-            HIP_TRY(hipStreamSynchronize(h->stream));
-        }
-        HIP_TRY(dev_alloc(h, &g.rsum2, Dl * Mp));  HIP_TRY(dev_alloc(h, &g.ez2, Dl * Mp * P));
-        HIP_TRY(dev_alloc(h, &g.cs2, Dl * nblk2 * Mp)); HIP_TRY(dev_alloc(h, &g.etx2, Dl * nblk2 * Mp * P));
-        HIP_TRY(dev_alloc(h, &g.rx22, Dl * nblk2 * P));
-        HIP_TRY(dev_alloc(h, &g.dz_kuu, Dl * c.M * P)); HIP_TRY(dev_alloc(h, &g.dll_kuu, Dl * P)); HIP_TRY(dev_alloc(h, &g.dls_kuu, Dl));
-        HIP_TRY(dev_alloc(h, &g.shared_part, S * g.sp_stride));
-        {   // every parameter gradient lives in ONE block (see GradWs::pack); the six small shared-parameter gradients are
-            // contiguous inside it: one fill per backward pass instead of six memsets
-            auto seg = [](size_t n) { return (n + 31) / 32 * 32; };
-            g.small_count = (size_t)c.D + (size_t)c.D * P + (size_t)c.D + (size_t)c.D * J + J + J * J;
-            const size_t nZ = (size_t)c.M * P, nU = grad_a ? (size_t)c.M * c.D : 0, nX = S * (c.T + 1) * c.D;
-            const size_t oZ = seg(8), oS = oZ + seg(nZ), oU = oS + seg(g.small_count), oX = oU + seg(nU);
-            g.pack_shared = oX; g.pack_total = oX + seg(nX);
-            HIP_TRY(dev_alloc(h, &g.pack, g.pack_total));
-            HIP_TRY(hipMemsetAsync(g.pack, 0, g.pack_total * sizeof(double), h->stream));     // the padding stays zero
-            g.dZ = g.pack + oZ; g.dlogvar = g.pack + oS; g.dX = g.pack + oX;
-            if (grad_a) g.dU = g.pack + oU;
-            g.dloglen = g.dlogvar + c.D; g.dlogQ = g.dloglen + (size_t)c.D * P; g.dCC = g.dlogQ + c.D;
-            g.dDD = g.dCC + (size_t)c.D * J; g.dlogR = g.dDD + J;
-        }
-        if (!grad_a && c.kernel_kind != FFVD_KERNEL_SE) HIP_TRY(dev_alloc(h, &g.xsq, nbt));      // LinearK, collapsed branch: sum_t |x_t|^2 per unit
-        if (grad_a) {
-            HIP_TRY(dev_alloc(h, &g.Gu, nbt * (Mp + NB) * Mp));   HIP_TRY(dev_alloc(h, &g.Gsum, Dl * (Mp + NB) * Mp));
-            HIP_TRY(dev_alloc(h, &g.r, nbt * Tp));                HIP_TRY(dev_alloc(h, &g.dalpha, nbt));
-            HIP_TRY(dev_alloc(h, &g.xsq, nbt));
-            HIP_TRY(dev_alloc(h, &g.ucol, Dl * Mp));              HIP_TRY(dev_alloc(h, &g.beta, Dl * Mp));
-            HIP_TRY(dev_alloc(h, &g.du, Dl * Mp));                HIP_TRY(dev_alloc(h, &g.GammaA, Dl * msq));
-            HIP_TRY(dev_alloc(h, &g.Lclean, Dl * msq));           // (g.dU: a segment of g.pack)
-        }
-    }
+    if (c.grad) { int rcg = alloc_grad_workspace(h); if (rcg) return rcg; }
     HIP_TRY(dev_alloc(h, &h->hterms, (size_t)h->nbatch * 2));
     if (c.T_total > 0) {        // the chain sums live at the tail of the exchange buffer: one all-reduce covers both
         const size_t raw = (size_t)h->nbatch * (Mp + 1) * Mp;
@@ -600,17 +403,6 @@ extern "C" int ffvd_set_params(ffvd_handle *h, const ffvd_params *p, int on_devi
 // ---- the per-iteration launch sequence -------------------------------------------------------
 // Stage timing: an event is recorded after each stage's launches; the interval ending at an event is
 // attributed to that stage (stage -1 = origin of an iteration).  Events come from a pool owned by the handle.
-// FFVD_DEBUG_SYNC=1: print the name of the launch group just enqueued and wait for both streams, so that a faulting kernel is the
-// one named last (diagnostic only; read once per handle)
-#define DBG_SYNC(h, name)                                                                              \
-    do {                                                                                               \
-        if ((h)->sw.debug_sync) {                                                                      \
-            fprintf(stderr, "[ffvd debug] %s ...", name); fflush(stderr);                             \
-            hipError_t e1_ = hipStreamSynchronize((h)->stream), e2_ = hipStreamSynchronize((h)->aux);  \
-            fprintf(stderr, " %s\n", (e1_ == hipSuccess && e2_ == hipSuccess) ? "ok" : hipGetErrorString(e1_ != hipSuccess ? e1_ : e2_)); \
-        }                                                                                              \
-    } while (0)
-
 struct StageTimer {
     ffvd_handle *h;
     void mark(int stage_id) {
@@ -709,7 +501,7 @@ extern "C" const char *ffvd_schedule_name(const ffvd_handle *h) {
 
 // Fork the side stream off the main stream.  Diagnostic switches (schedule tests): a spin kernel at the head of the side stream
 // (FFVD_DEBUG_SIDE_DELAY_US) and / or of the main stream behind the fork (FFVD_DEBUG_MAIN_DELAY_US) -- results must not change.
-static int fork_side(ffvd_handle *h, hipEvent_t ev, hipStream_t from, hipStream_t to) {
+int ffvd::fork_side(ffvd_handle *h, hipEvent_t ev, hipStream_t from, hipStream_t to) {
     HIP_TRY(hipEventRecord(ev, from));
     HIP_TRY(hipStreamWaitEvent(to, ev, 0));
     if (h->sw.side_delay_us > 0) launch_spin(to, h->sw.side_delay_us);
@@ -1512,329 +1304,12 @@ extern "C" int ffvd_stage_times(ffvd_handle *h, double out_ms[8], int32_t out_la
     return FFVD_OK;
 }
 
-// ---- backward pass (see grad.hip); runs on the handle's stream right after the forward kernels ----------
-// Backward pass of the explicit-U branch (closed form: oracle/ffvd_grad_oracle.py nll_grad_explicit_u).  The T x M work
-// reuses the collapsed branch's kernels: one Gram pass (G = K_uf K_fu and g_r = K_uf r per unit) and the fused E
-// product with Gamma := alpha K^-1 / 2, delta := r, u := beta = L^-T u; everything else is M x M per latent dim.
-static int enqueue_grad_a(ffvd_handle *h, int S_total) {
-    const ffvd_config &c = h->cfg;
-    ffvd_handle::GradWs &g = h->gw;
-    const int Mp = h->Mp, Tp = h->Tp, Dl = h->Dl, P = h->P, nb = h->nbatch, S = c.S_local;
-    const size_t msq = (size_t)Mp * Mp, kstride = 2 * msq, fstride = (size_t)Tp * Mp, gstride = (size_t)(Mp + NB) * Mp;
-    hipStream_t s = h->stream;
-    const ffvd_params &p = h->cur;
-    const double *W = h->Kuu + msq;                                                     // L^-T rows, per dim stride kstride
-    // beta = W u,  r = delta - mean,  dl/dalpha per unit
-    launch_ucols(s, p.U, c.M, Mp, c.D, c.d_begin, Dl, g.ucol);
-    launch_matvec(s, W, kstride, g.ucol, Mp, Mp, g.beta, 1, Mp, Mp, Dl);
-    const int kind = c.kernel_kind;
-    launch_resid_a(s, kind, p.X, h->ctrl, c.C, h->fmean, h->rowsq, h->variance, p.log_Q, c.T, Tp, c.D, Dl, c.d_begin,
-                   h->ngr ? h->ngr : h->ng, nb, g.r, g.dalpha, g.xsq);
-    // G = K_uf K_fu (lower tiles) and g_r = K_uf r (row Mp) per unit, then summed over the chains
-    GramArgs gg{};
-    gg.mode = GRAM_PLAIN; gg.A = h->F; gg.a_stride = fstride; gg.rows = Tp; gg.with_row = 1; gg.brow = Mp; gg.rvec = g.r;
-    gg.X = p.X; gg.log_Q = p.log_Q; gg.T = c.T; gg.D = c.D; gg.Mp = Mp; gg.Dl = Dl; gg.d_begin = c.d_begin; gg.b0 = 0; gg.nb = nb;
-    gg.yn_over_batch = 1.0; gg.H = g.Gu; gg.h_stride = gstride;
-    launch_gram(s, gg);
-    launch_chain_sum(s, g.Gu, gstride, S, Dl, (size_t)(Mp + 1) * Mp, g.Gsum, gstride);
-    // M x M chain per dim:  dW = alpha (g_r u^T + G W);  P = W dW^T W;  dL = -tril(P);  Phi = sym(tril(L^T dL), diag/2);
-    // dK = W Phi W^T;  E_psi = dK o K_uu.  Temporaries: Asum (G sym), Gs (T1), gsum (dW), P1, KGK, GamSum
-    HIP_TRY(hipMemcpy2DAsync(g.Asum, msq * sizeof(double), g.Gsum, gstride * sizeof(double), msq * sizeof(double), Dl,
-                             hipMemcpyDeviceToDevice, s));
-    launch_symmetrize(s, g.Asum, Mp, Dl);
-    AtbArgs ap{};
-    ap.mode = ATB_PLAIN; ap.lda = Mp; ap.nA = Mp; ap.ldb = Mp; ap.nB = Mp; ap.rows = Mp; ap.ldc = Mp; ap.nb = Dl; ap.Dl = Dl;
-    ap.c_stride = msq;
-    ap.A = g.Asum; ap.a_stride = msq; ap.B = W; ap.b_stride = kstride; ap.C = g.Gs;
-    launch_atb(s, ap);                                                                  // T1 = G W
-    launch_dw_a(s, g.Gs, g.Gsum + msq, gstride, g.ucol, p.log_Q, Mp, Dl, c.d_begin, g.gsum);   // dW
-    ap.A = g.gsum; ap.a_stride = msq; ap.B = W; ap.b_stride = kstride; ap.C = g.P1;
-    launch_atb(s, ap);                                                                  // Q1 = dW^T W
-    ap.A = h->Linv; ap.a_stride = msq; ap.B = g.P1; ap.b_stride = msq; ap.C = g.KGK;
-    launch_atb(s, ap);                                                                  // P = W Q1
-    launch_tril_neg(s, g.KGK, Mp, Dl, g.GamSum);                                        // dL
-    launch_tril_copy(s, h->Kuu, kstride, Mp, Dl, g.Lclean);
-    ap.A = g.Lclean; ap.a_stride = msq; ap.B = g.GamSum; ap.b_stride = msq; ap.C = g.P1;
-    launch_atb(s, ap);                                                                  // S = L^T dL
-    launch_phi(s, g.P1, Mp, Dl, g.KGK);                                                 // Phi
-    ap.A = g.KGK; ap.a_stride = msq; ap.B = h->Linv; ap.b_stride = msq; ap.C = g.P1;
-    launch_atb(s, ap);                                                                  // Q2 = Phi W^T
-    ap.A = h->Linv; ap.a_stride = msq; ap.B = g.P1; ap.b_stride = msq; ap.C = g.KGK;
-    launch_atb(s, ap);                                                                  // dK = W Q2
-    launch_epsi_a(s, kind, g.KGK, h->Kcopy, c.M, Mp, Dl, c.jitter, g.Epsi);
-    EReduceArgs ek{};
-    ek.kind = kind; ek.variance = h->variance;
-    ek.E = g.Epsi; ek.e_stride = msq; ek.Kf = nullptr; ek.u = nullptr; ek.x_is_z = 1; ek.Z = p.Z; ek.len = h->len;
-    ek.T = c.M; ek.Tp = Mp; ek.M = c.M; ek.Mp = Mp; ek.P = P; ek.Dl = Dl; ek.b0 = 0; ek.nb = Dl; ek.nblk = Mp / 64;
-    ek.rsum = g.rsum2; ek.ez = g.ez2; ek.kfu = nullptr; ek.cs_part = g.cs2; ek.etx_part = g.etx2; ek.rx2_part = g.rx22;
-    launch_e_reduce(s, ek);
-    launch_e_finish(s, ek, g.dz_kuu, g.dll_kuu, g.dls_kuu);
-    // du = W^T g_r (per dim) for dU
-    launch_matvec(s, h->Linv, msq, g.Gsum + msq, gstride, Mp, g.du, 1, Mp, Mp, Dl);
-    // K_fu side: E = (alpha K_fu K^-1 + alpha r beta^T) o K_fu, reduced in the fused kernel
-    launch_scale_kinv(s, h->Kinv, p.log_Q, Mp, Dl, c.d_begin, g.GammaA);
-    EReduceArgs er{};
-    er.kind = kind; er.variance = h->variance; er.u_per_dim = 1;
-    er.E = g.E; er.e_stride = fstride; er.Kf = h->F; er.u = g.beta; er.u_stride = Mp; er.x_is_z = 0;
-    er.x = p.X; er.x_chain_stride = (size_t)(c.T + 1) * c.D; er.x_ld = c.D; er.x_cols = c.D; er.ctrl = h->ctrl; er.C = c.C;
-    er.Z = p.Z; er.len = h->len; er.T = c.T; er.Tp = Tp; er.M = c.M; er.Mp = Mp; er.P = P; er.Dl = Dl; er.b0 = 0; er.nb = nb;
-    er.nblk = Tp / 64; er.rsum = g.rsum; er.ez = g.ez; er.kfu = g.kfu; er.cs_part = g.cs_part; er.etx_part = g.etx_part;
-    er.rx2_part = g.rx2_part;
-    BwdFusedArgs bf{};
-    bf.Kf = h->F; bf.kf_stride = fstride; bf.Gamma = g.GammaA; bf.g_stride = msq; bf.u = g.beta; bf.u_stride = Mp;
-    bf.per_dim = 1; bf.rvec = g.r;
-    bf.X = p.X; bf.ctrl = h->ctrl; bf.Z = p.Z; bf.log_Q = p.log_Q; bf.T = c.T; bf.Tp = Tp; bf.D = c.D; bf.C = c.C;
-    bf.M = c.M; bf.Mp = Mp; bf.P = P; bf.Dl = Dl; bf.d_begin = c.d_begin; bf.b0 = 0; bf.nb = nb; bf.rp = g.rp;
-    bf.cs_part = g.cs_part; bf.etx_part = g.etx_part; bf.rsum = g.rsum; bf.ez = g.ez; bf.kfu = g.kfu; bf.rx2_part = g.rx2_part;
-    bf.linear = kind != FFVD_KERNEL_SE;
-    if (g.rp) launch_bwd_fused(s, bf);
-    else {
-        // P > 6 (BASELINE config 5: P = 17): materialise E = alpha (K_fu K^-1 + r beta^T) [o K_fu for the SE kernel] and
-        // reduce it in a second kernel
-        AtbArgs ae{};
-        ae.mode = ATB_BWD_E; ae.A = h->F; ae.a_stride = fstride; ae.lda = Mp; ae.nA = Tp; ae.a_rowmajor = 1;
-        ae.B = g.GammaA; ae.b_stride = msq; ae.ldb = Mp; ae.nB = Mp; ae.b_per_dim = 1; ae.rows = Mp;
-        ae.C = g.E; ae.c_stride = fstride; ae.ldc = Mp; ae.nb = nb; ae.b0 = 0; ae.Dl = Dl; ae.d_begin = c.d_begin;
-        ae.log_Q = p.log_Q; ae.u = g.beta; ae.u_stride = Mp; ae.u_per_dim = 1; ae.X = p.X; ae.T = c.T; ae.D = c.D;
-        ae.Kf = h->F; ae.kf_stride = fstride; ae.ldkf = Mp; ae.rvec = g.r; ae.no_hadamard = kind != FFVD_KERNEL_SE;
-        launch_atb(s, ae);
-        launch_e_reduce(s, er);
-    }
-    launch_e_finish(s, er, g.dz_unit, g.dll_unit, g.dls_unit);
-    DxArgs dx{};
-    dx.kind = kind; dx.variance = h->variance;
-    dx.X = p.X; dx.Y = h->Y; dx.CC = p.CC; dx.DD = p.DD; dx.log_Rchols = p.log_Rchols; dx.log_Q = p.log_Q; dx.len = h->len;
-    dx.rsum = g.rsum; dx.ez = g.ez; dx.kfu = g.kfu; dx.S = S; dx.S_total = S_total; dx.T = c.T; dx.Tp = Tp; dx.D = c.D;
-    dx.P = P; dx.Ydim = c.Ydim; dx.Dl = Dl; dx.d_begin = c.d_begin; dx.shared_terms = c.shared_terms; dx.dX = g.dX;
-    dx.T_norm = c.T_total; dx.skip_x0 = (c.T_total > 0 && c.t_begin > 0) ? 1 : 0;      // T-shards: the job's 1 / T, x_0 on the first shard
-    launch_dx(s, dx);
-    launch_shared_partials(s, dx, g.shared_part, g.sp_stride);
-    GradFinalArgs gf{};
-    gf.T = c.T; gf.D = c.D; gf.P = P; gf.M = c.M; gf.Mp = Mp; gf.Ydim = c.Ydim; gf.Dl = Dl; gf.d_begin = c.d_begin; gf.S = S;
-    gf.S_total = S_total; gf.shared_terms = c.shared_terms; gf.prior_type = c.prior_type;
-    gf.Z = p.Z; gf.logvar = p.logvariance; gf.loglen = p.loglengthscales; gf.log_Q = p.log_Q; gf.CC = p.CC; gf.DD = p.DD;
-    gf.log_Rchols = p.log_Rchols; gf.dz_unit = g.dz_unit; gf.dll_unit = g.dll_unit; gf.dls_unit = g.dls_unit;
-    gf.dz_kuu = g.dz_kuu; gf.dll_kuu = g.dll_kuu; gf.dls_kuu = g.dls_kuu; gf.shared_part = g.shared_part;
-    gf.sp_stride = g.sp_stride; gf.dZ = g.dZ; gf.dlogvar = g.dlogvar; gf.dloglen = g.dloglen; gf.dlogQ = g.dlogQ;
-    gf.dCC = g.dCC; gf.dDD = g.dDD; gf.dlogR = g.dlogR;
-    gf.branch_a = 1; gf.dalpha_unit = g.dalpha; gf.du_dim = g.du; gf.U = p.U; gf.dU = g.dU;
-    gf.kind = kind; gf.xsq_unit = g.xsq;
-    launch_fill(s, g.dlogvar, g.small_count, 0.0);        // dlogvar | dloglen | dlogQ | dCC | dDD | dlogR
-    launch_grad_finalize(s, gf);
-    HIP_TRY(hipGetLastError());
-    return FFVD_OK;
-}
-
-static int enqueue_grad_b(ffvd_handle *h, int S_total) {
-    const ffvd_config &c = h->cfg;
-    ffvd_handle::GradWs &g = h->gw;
-    const int Mp = h->Mp, Tp = h->Tp, Dl = h->Dl, P = h->P, nb = h->nbatch, S = c.S_local;
-    const size_t msq = (size_t)Mp * Mp, hstride = (size_t)(2 * Mp + NB) * Mp, fstride = (size_t)Tp * Mp;
-    hipStream_t s = h->stream;
-    const ffvd_params &p = h->cur;
-    const size_t kstride = (size_t)2 * Mp * Mp;
-    const bool wh = g.whitened;
-    // Reference route (F = K_fu L^-T, H = F^T F / Q + I factorised by the forward pass; fp64 or fp32 contractions): the slab already
-    // holds the factor of the whitened H, so the M x M side below is the whitened one as it stands; what differs is where K_fu
-    // lives (Kf2, or the fp32 copy), that sum_s H_s is read instead of W^T (sum_s A_s) W, and where sum_t |F_t|^2 comes from.
-    const bool ref = c.route == FFVD_ROUTE_REFERENCE;
-    const bool f32c = c.dtype == FFVD_F32C;
-    const double *Kf64 = ref ? h->Kf2 : h->F;
-    // explicit form: u = A^-1 c = L_A^-T (L_A^-1 c), Gamma = alpha/2 (K^-1 - A^-1 - u u^T) with A^-1 from the factor of A.
-    // whitened form (default): the slab holds the factor of H = W^T A W and y = L_H^-1 b.  Then w = H^-1 b, u = W w, and
-    // A^-1 = B^T B with B = L_H^-1 L^-1 (a product of two accurate triangular factors; K^-1 = (L^-1)^T L^-1 is formed
-    // the same way in the forward pass), so the same Gamma launch runs on B instead of on the inverse factor of the
-    // ill-conditioned A -- dZ at M = 512 then agrees with central differences to 7 digits instead of 3.
-    AtbArgs ag{};
-    ag.mode = ATB_GAMMA; ag.a_stride = msq; ag.lda = Mp; ag.nA = Mp;
-    ag.b_stride = msq; ag.ldb = Mp; ag.nB = Mp; ag.b_per_dim = 0; ag.rows = Mp;
-    ag.C = g.Gamma; ag.c_stride = msq; ag.ldc = Mp; ag.nb = nb; ag.b0 = 0; ag.Dl = Dl; ag.d_begin = c.d_begin;
-    ag.log_Q = p.log_Q; ag.u = g.u; ag.u_stride = Mp; ag.Kinv = h->Kinv; ag.Kcopy = h->Kcopy; ag.k_stride = msq; ag.ldk = Mp;
-    ag.part = g.gam_part; ag.k_lower = 1; ag.sym = 1; ag.small_tiles = 1;   // inverse factor lower triangular, its Gram symmetric
-    // K_uu side, first half: K^-1 (sum_s A_s - S K) K^-1 needs the saved A-matrices and the K_uu chain only, not Gamma.  When the E
-    // product is short (tiny problems: the side stream's launches are the critical path of the backward pass) it starts here,
-    // ahead of w / u / B / Gamma; Gamma's sum joins it through ev_go.
-    hipStream_t sk = h->sw.grad_serial ? s : h->aux;
-    const bool tiny = (size_t)nb * Tp * Mp <= (size_t)64 * 1024 * 128 && sk != s;
-    auto kgk_chain = [&]() -> int {
-        launch_chain_sum(sk, g.Acopy, msq, S, Dl, msq, g.Asum, msq);      // (reference route: the saved matrices are the H_s)
-        launch_symmetrize(sk, g.Asum, Mp, Dl);
-        if (!ref) launch_axpby(sk, g.Asum, h->Kcopy, 1.0, -(double)S, p.log_Q, c.d_begin, 0, msq, Dl, g.Gs);
-        AtbArgs ap{};
-        ap.mode = ATB_PLAIN; ap.a_stride = msq; ap.lda = Mp; ap.nA = Mp; ap.b_stride = msq;
-        ap.ldb = Mp; ap.nB = Mp; ap.rows = Mp; ap.c_stride = msq; ap.ldc = Mp; ap.nb = Dl; ap.Dl = Dl;
-        if (wh) {       // K^-1 Gs K^-1 = W (W^T Gs W) W^T, conjugated step by step (Gs and W^T Gs W are symmetric)
-            if (ref) launch_sub_identity(sk, g.Asum, (double)S, Mp, Dl, g.P2);     // W^T Gs W = sum_s (H_s - I): no products needed
-            else {
-                ap.A = g.Gs; ap.B = h->Kuu + msq; ap.b_stride = kstride; ap.C = g.P1; ap.krange = 8;
-                launch_atb(sk, ap);                             // P1 = Gs W
-                ap.A = h->Kuu + msq; ap.a_stride = kstride; ap.B = g.P1; ap.b_stride = msq; ap.C = g.P2; ap.krange = 4;
-                launch_atb(sk, ap);                             // P2 = W^T Gs W
-            }
-            ap.a_stride = msq; ap.b_stride = msq;
-            ap.A = g.P2; ap.a_stride = msq; ap.B = h->Linv; ap.C = g.P3; ap.krange = 2;
-            launch_atb(sk, ap);                             // P3 = P2 W^T
-            ap.A = h->Linv; ap.B = g.P3; ap.C = g.KGK; ap.krange = 1;
-            launch_atb(sk, ap);                             // KGK = W P3
-        } else {
-            ap.A = g.Gs; ap.B = h->Kinv; ap.C = g.P1;
-            launch_atb(sk, ap);                             // P1 = Gs^T K^-1 = Gs K^-1
-            ap.A = g.P1; ap.C = g.KGK;
-            launch_atb(sk, ap);                             // P1^T K^-1 = K^-1 Gs K^-1
-        }
-        return FFVD_OK;
-    };
-    if (tiny) {
-        { int rcf = fork_side(h, h->ev_fork, s, sk); if (rcf) return rcf; }
-        kgk_chain();
-    }
-    if (wh) {
-        launch_matvec(s, h->H + msq, hstride, h->H + 2 * msq, hstride, Mp, g.wv, 1, Mp, Mp, nb);          // w = L_H^-T y
-        launch_matvec(s, h->Kuu + msq, kstride, g.wv, Mp, Mp, g.u, 1, Mp, Mp, nb, Dl);                     // u = W w
-        AtbArgs tb{};       // B[i][j] = sum_k L_H^-T[k][i] L^-1[k][j]: the extension rows as they are, no transpose
-        tb.mode = ATB_PLAIN; tb.A = h->H + msq; tb.a_stride = hstride; tb.lda = Mp; tb.nA = Mp;
-        tb.B = h->Linv; tb.b_stride = msq; tb.ldb = Mp; tb.nB = Mp; tb.b_per_dim = 1; tb.rows = Mp;
-        tb.C = g.T1; tb.c_stride = msq; tb.ldc = Mp; tb.nb = nb; tb.Dl = Dl; tb.krange = 2 | 4; tb.small_tiles = 1;      // k in [tile tj, tile (ti + 1))
-        launch_atb(s, tb);
-        ag.A = g.T1; ag.B = g.T1;
-    } else {
-        launch_matvec(s, h->H + msq, hstride, h->H + 2 * msq, hstride, Mp, g.u, 1, Mp, Mp, nb);
-        launch_transpose(s, h->H + msq, hstride, g.LAinv, msq, Mp, nb);
-        ag.A = g.LAinv; ag.B = g.LAinv;
-    }
-    launch_atb(s, ag);
-    DBG_SYNC(h, "backward: w, u, B, Gamma");
-    // K_uu side: Psi_d = sum_s Gamma_s / alpha_d - 1/2 K^-1 (sum_s A_s - S K) K^-1.  It needs Gamma and the saved
-    // A-matrices only, so its dozen small launches go to the side stream and run beside the E product
-    // (enqueued after it: the main stream must not wait for their launch overhead).
-    if (sk != s) { int rcf = fork_side(h, tiny ? h->ev_go : h->ev_fork, s, sk); if (rcf) return rcf; }          // Gamma is there
-    EReduceArgs er{};
-    er.E = g.E; er.e_stride = fstride; er.Kf = Kf64; er.u = g.u; er.u_stride = Mp; er.x_is_z = 0;
-    er.x = p.X; er.x_chain_stride = (size_t)(c.T + 1) * c.D; er.x_ld = c.D; er.x_cols = c.D; er.ctrl = h->ctrl; er.C = c.C;
-    er.Z = p.Z; er.len = h->len; er.T = c.T; er.Tp = Tp; er.M = c.M; er.Mp = Mp; er.P = P; er.Dl = Dl; er.b0 = 0; er.nb = nb;
-    er.nblk = Tp / 64; er.rsum = g.rsum; er.ez = g.ez; er.kfu = g.kfu; er.cs_part = g.cs_part; er.etx_part = g.etx_part;
-    er.rx2_part = g.rx2_part;
-    // LinearK (kernels.py:270-281) in the collapsed branch: K = (x s2) z^T has no Hadamard factor in its chain rule and its Kdiag_t =
-    // s2 |x_t|^2 depends on the inputs -- the switches the explicit-U branch already uses (enqueue_grad_a), plus sum_t |x_t|^2 per unit
-    const int kind = c.kernel_kind;
-    const bool lin = kind != FFVD_KERNEL_SE;
-    er.kind = kind; er.variance = h->variance;
-    if (lin) launch_xsq_unit(sk, p.X, h->ctrl, c.T, c.D, c.C, S, Dl, g.xsq);
-    if (f32c) {
-        // fp32 contractions (BASELINE configs[3]): Gamma rounded once, R = K_fu Gamma on v_mfma_f32_32x32x2_f32 into the buffer F
-        // occupied in the forward pass, then E_tm = (2 R_tm + alpha delta_t u_m) K_tm formed on the fly inside the reduction
-        // kernel with every sum in fp64 (E itself is never stored)
-        launch_to_f32(s, g.Gamma, g.Gam32, (size_t)nb * msq);
-        ProjF32Args pg{};
-        pg.Kf = h->Kf32; pg.kf_stride = fstride; pg.Bunit = g.Gam32; pg.bunit_stride = msq; pg.F = h->F32; pg.f_stride = fstride;
-        pg.sqpart = nullptr; pg.Tp = Tp; pg.Mp = Mp; pg.Dl = Dl; pg.b0 = 0; pg.nb = nb;
-        launch_proj_gemm_f32(s, pg);
-        er.E = nullptr; er.Kf = nullptr; er.R32 = h->F32; er.Kf32 = h->Kf32; er.Xd = p.X; er.log_Q = p.log_Q; er.D = c.D;
-        er.d_begin = c.d_begin;
-        launch_e_reduce(s, er);
-    } else if (g.rp) {
-        // E = (2 Kf Gamma + alpha delta u^T) o Kf formed and reduced tile by tile: it never reaches HBM
-        BwdFusedArgs bf{};
-        bf.Kf = Kf64; bf.kf_stride = fstride; bf.Gamma = g.Gamma; bf.g_stride = msq; bf.u = g.u; bf.u_stride = Mp;
-        bf.X = p.X; bf.ctrl = h->ctrl; bf.Z = p.Z; bf.log_Q = p.log_Q; bf.T = c.T; bf.Tp = Tp; bf.D = c.D; bf.C = c.C;
-        bf.M = c.M; bf.Mp = Mp; bf.P = P; bf.Dl = Dl; bf.d_begin = c.d_begin; bf.b0 = 0; bf.nb = nb; bf.rp = g.rp;
-        bf.cs_part = g.cs_part; bf.etx_part = g.etx_part; bf.rsum = g.rsum; bf.ez = g.ez; bf.kfu = g.kfu;
-        bf.rx2_part = g.rx2_part;
-        bf.linear = lin ? 1 : 0;
-        launch_bwd_fused(s, bf);
-    } else {
-        // P > 6: materialise E and reduce it in a second kernel
-        AtbArgs ae{};
-        ae.mode = ATB_BWD_E; ae.A = Kf64; ae.a_stride = fstride; ae.lda = Mp; ae.nA = Tp; ae.a_rowmajor = 1;   // K_fu itself
-        ae.B = g.Gamma; ae.b_stride = msq; ae.ldb = Mp; ae.nB = Mp; ae.rows = Mp;
-        ae.C = g.E; ae.c_stride = fstride; ae.ldc = Mp; ae.nb = nb; ae.b0 = 0; ae.Dl = Dl; ae.d_begin = c.d_begin;
-        ae.log_Q = p.log_Q; ae.u = g.u; ae.u_stride = Mp; ae.X = p.X; ae.T = c.T; ae.D = c.D;
-        ae.Kf = Kf64; ae.kf_stride = fstride; ae.ldkf = Mp; ae.no_hadamard = lin ? 1 : 0;
-        launch_atb(s, ae);
-        launch_e_reduce(s, er);
-    }
-    DBG_SYNC(h, "backward: E product + reductions");
-    launch_e_finish(s, er, g.dz_unit, g.dll_unit, g.dls_unit);
-    DBG_SYNC(h, "backward: e_finish");
-    // latent trajectories (after the E product) and the per-chain partials of the shared parameters (inputs only: side)
-    DxArgs dx{};
-    dx.kind = kind; dx.variance = h->variance;
-    dx.X = p.X; dx.Y = h->Y; dx.CC = p.CC; dx.DD = p.DD; dx.log_Rchols = p.log_Rchols; dx.log_Q = p.log_Q; dx.len = h->len;
-    dx.rsum = g.rsum; dx.ez = g.ez; dx.kfu = g.kfu; dx.S = S; dx.S_total = S_total; dx.T = c.T; dx.Tp = Tp; dx.D = c.D;
-    dx.P = P; dx.Ydim = c.Ydim; dx.Dl = Dl; dx.d_begin = c.d_begin; dx.shared_terms = c.shared_terms; dx.dX = g.dX;
-    dx.T_norm = c.T_total; dx.skip_x0 = (c.T_total > 0 && c.t_begin > 0) ? 1 : 0;      // T-shards: the job's 1 / T, x_0 on the first shard
-    // u^T K u and the per-chain partials of the shared parameters feed grad_finalize only.  Beside a long E product they ride on
-    // the side stream; when that product is a few dozen microseconds (the reference's own experiment sizes) the side stream's
-    // dozen launches ARE the backward pass's critical path and these two go to the main stream, which has the slack there
-    hipStream_t su = ((size_t)nb * Tp * Mp <= (size_t)64 * 1024 * 128 && !h->sw.grad_serial) ? s : sk;
-    if (wh) launch_utu(su, g.wv, Mp, Mp, nb, g.uku);                       // u^T K u = w^T w
-    else launch_uku(su, g.u, Mp, h->Kcopy, msq, Mp, Dl, nb, g.uku);   // u^T K u per unit: only grad_finalize reads it
-    launch_shared_partials(su, dx, g.shared_part, g.sp_stride);
-    if (!tiny) kgk_chain();
-    launch_chain_sum(sk, g.Gamma, msq, S, Dl, msq, g.GamSum, msq);
-    launch_axpby(sk, g.GamSum, nullptr, 1.0, 0.0, p.log_Q, c.d_begin, 1, msq, Dl, g.gsum);
-    launch_psi_e(sk, g.gsum, g.KGK, h->Kcopy, c.M, Mp, Dl, c.jitter, g.Epsi, kind);
-    EReduceArgs ek{};
-    ek.E = g.Epsi; ek.e_stride = msq; ek.Kf = nullptr; ek.u = nullptr; ek.x_is_z = 1; ek.Z = p.Z; ek.len = h->len;
-    ek.T = c.M; ek.Tp = Mp; ek.M = c.M; ek.Mp = Mp; ek.P = P; ek.Dl = Dl; ek.b0 = 0; ek.nb = Dl; ek.nblk = Mp / 64;
-    ek.rsum = g.rsum2; ek.ez = g.ez2; ek.kfu = nullptr; ek.cs_part = g.cs2; ek.etx_part = g.etx2; ek.rx2_part = g.rx22;
-    ek.kind = kind; ek.variance = h->variance;
-    launch_e_reduce(sk, ek);
-    launch_e_finish(sk, ek, g.dz_kuu, g.dll_kuu, g.dls_kuu);
-    if (sk != s) HIP_TRY(hipEventRecord(h->ev_join, sk));
-    if (sk != s) HIP_TRY(hipStreamWaitEvent(s, h->ev_join, 0));
-    DBG_SYNC(h, "backward: K_uu side");
-    launch_dx(s, dx);
-    GradFinalArgs gf{};
-    gf.T = c.T; gf.D = c.D; gf.P = P; gf.M = c.M; gf.Mp = Mp; gf.Ydim = c.Ydim; gf.Dl = Dl; gf.d_begin = c.d_begin; gf.S = S;
-    gf.S_total = S_total; gf.shared_terms = c.shared_terms; gf.prior_type = c.prior_type;
-    gf.T_norm = c.T_total; gf.replicated_skip = (c.T_total > 0 && c.t_begin > 0) ? 1 : 0;
-    gf.Z = p.Z; gf.logvar = p.logvariance; gf.loglen = p.loglengthscales; gf.log_Q = p.log_Q; gf.CC = p.CC; gf.DD = p.DD;
-    gf.log_Rchols = p.log_Rchols; gf.dz_unit = g.dz_unit; gf.dll_unit = g.dll_unit; gf.dls_unit = g.dls_unit;
-    gf.dz_kuu = g.dz_kuu; gf.dll_kuu = g.dll_kuu; gf.dls_kuu = g.dls_kuu; gf.gam_part = g.gam_part; gf.ngam = g.ngam;
-    gf.trpart = h->trpart; gf.ntr = h->ntiles; gf.hterms = h->hterms;
-    gf.uku = g.uku; gf.shared_part = g.shared_part;
-    gf.kind = kind; gf.xsq_unit = g.xsq;
-    if (ref) { gf.trpart = f32c ? h->sqsum : g.fsq; gf.ntr = 1; }       // sum_t |F_t|^2 per unit (Gram route: tr(K^-1 K_uf K_fu) by tiles)
-    gf.sp_stride = g.sp_stride; gf.dZ = g.dZ; gf.dlogvar = g.dlogvar; gf.dloglen = g.dloglen; gf.dlogQ = g.dlogQ;
-    gf.dCC = g.dCC; gf.dDD = g.dDD; gf.dlogR = g.dlogR;
-    // entries this handle does not own (other ranks' dims; the shared terms off rank 0) stay zero for the all-reduce
-    launch_fill(s, g.dlogvar, g.small_count, 0.0);        // dlogvar | dloglen | dlogQ | dCC | dDD | dlogR
-    launch_grad_finalize(s, gf);
-    DBG_SYNC(h, "backward: dx + finalize");
-    HIP_TRY(hipGetLastError());
-    return FFVD_OK;
-}
-
-static int enqueue_grad(ffvd_handle *h, int S_total) {
-    return h->cfg.branch == FFVD_BRANCH_A ? enqueue_grad_a(h, S_total) : enqueue_grad_b(h, S_total);
-}
+// ---- backward pass: backward.hip (enqueue_grad, copy_grads_out); it runs on the handle's streams right behind the forward kernels ----------
 // forward + backward pass of one training iteration: ONE launch where the handle has the small-problem plan (tiny.hip)
 static int enqueue_forward_backward(ffvd_handle *h, int S_total) {
     if (h->cfg.grad && tiny_selected(h)) return enqueue_tiny(h, nullptr, nullptr, true, S_total);
     const int r = enqueue_elbo(h, nullptr, nullptr);
     return r ? r : enqueue_grad(h, S_total);
-}
-
-// the gradient arrays of the handle to the caller's host arrays (enqueued on the main stream; the caller synchronises)
-static int copy_grads_out(ffvd_handle *h, const ffvd_grads *gout) {
-    const ffvd_config &c = h->cfg;
-    ffvd_handle::GradWs &g = h->gw;
-    hipStream_t s = h->stream;
-    const size_t P = h->P, J = c.Ydim;
-    if (gout->X) HIP_TRY(hipMemcpyAsync(gout->X, g.dX, (size_t)c.S_local * (c.T + 1) * c.D * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (gout->Z) HIP_TRY(hipMemcpyAsync(gout->Z, g.dZ, (size_t)c.M * P * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (gout->logvariance) HIP_TRY(hipMemcpyAsync(gout->logvariance, g.dlogvar, (size_t)c.D * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (gout->loglengthscales) HIP_TRY(hipMemcpyAsync(gout->loglengthscales, g.dloglen, (size_t)c.D * P * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (gout->log_Q) HIP_TRY(hipMemcpyAsync(gout->log_Q, g.dlogQ, (size_t)c.D * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (gout->CC) HIP_TRY(hipMemcpyAsync(gout->CC, g.dCC, (size_t)c.D * J * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (gout->DD) HIP_TRY(hipMemcpyAsync(gout->DD, g.dDD, J * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (gout->log_Rchols) HIP_TRY(hipMemcpyAsync(gout->log_Rchols, g.dlogR, J * J * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (gout->U) {
-        if (g.dU) HIP_TRY(hipMemcpyAsync(gout->U, g.dU, (size_t)c.M * c.D * sizeof(double), hipMemcpyDeviceToHost, s));
-        else memset(gout->U, 0, (size_t)c.M * c.D * sizeof(double));        // collapsed branch: U is integrated out
-    }
-    return FFVD_OK;
 }
 
 extern "C" int ffvd_elbo_grad(ffvd_handle *h, const ffvd_params *p, uint32_t flags, int S_total, double out_terms[8],

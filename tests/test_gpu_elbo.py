@@ -621,11 +621,16 @@ def test_no_control_inputs(branch):
 
 @pytest.mark.parametrize("ov", [dict(T=170, M=150, S=2, D=3, C=1),      # Mp = 192, Tp = 192: half-empty 128-tiles
                                 dict(T=130, M=40, S=2, D=4, C=2),       # P = 6: last shape of the fused backward epilogue
-                                dict(T=130, M=40, S=2, D=5, C=2)])      # P = 7: materialised-E fallback
-def test_gradient_on_awkward_shapes(ov):
+                                dict(T=130, M=40, S=2, D=5, C=2),       # P = 7: materialised-E fallback
+                                dict(T=130, M=40, S=2, D=5, C=2, no_tiny=True)])     # ... on the multi-kernel schedule (E through ATB_BWD_E)
+def test_gradient_on_awkward_shapes(ov, monkeypatch):
     """Backward pass against the closed-form oracle where tiles are partial and on both sides of the P <= 6 switch
-    between the fused and the two-kernel E reduction."""
+    between the fused and the two-kernel E reduction.  These shapes take the one-launch path where it fits; no_tiny runs the
+    multi-kernel backward pass (FFVD_NO_TINY=1, read when a handle is created) at the shape whose E is materialised."""
     from oracle import ffvd_grad_oracle as gorc
+    ov = dict(ov)
+    if ov.pop("no_tiny", False):
+        monkeypatch.setenv("FFVD_NO_TINY", "1")
     params, Y, c, meta = synthetic.make_named("tiny", **ov)
     S = meta["S"]
     with ElboEngine(meta["T"], meta["D"], meta["C"], meta["M"], S, route="gram", grad=True) as e:
