@@ -1,6 +1,7 @@
 // C ABI of libffvd_hip.so (see include/ffvd_abi.h): handle lifetime, resident buffers, the per-iteration
-// launch sequence of the ELBO, training steps, T-shards and RCCL.  The multi-kernel backward pass is in backward.hip (the handle
-// both see: handle.h), the stateless ffvd_op_* operators are in ops.hip.
+// launch sequence of the ELBO and of a T-shard, parameters in and out.  The multi-kernel backward pass is in backward.hip, optimiser
+// steps and the shard entry points in train.hip, the RCCL binding in comm.hip (the handle all four see: handle.h); the stateless
+// ffvd_op_* operators are in ops.hip.
 #include "handle.h"
 #include "kernels.h"
 #include "kernels_f32.h"
@@ -326,8 +327,6 @@ extern "C" int ffvd_create(const ffvd_config *cfg, ffvd_handle **out) {
     *out = h;
     return FFVD_OK;
 }
-
-static int check_info(ffvd_handle *h);
 
 extern "C" int ffvd_sync(ffvd_handle *h) {
     if (!h) return set_error(nullptr, FFVD_EINVAL, "ffvd_sync: null handle");
@@ -1097,13 +1096,13 @@ static int enqueue_elbo(ffvd_handle *h, double *out_dev, StageTimer *st) {
     return fwd_finalize(x);
 }
 
-static int ready(ffvd_handle *h, const char *who) {
+int ffvd::ready(ffvd_handle *h, const char *who) {
     if (!h->have_data) return set_error(h, FFVD_EINVAL, std::string(who) + ": call ffvd_set_data first");
     if (!h->have_params) return set_error(h, FFVD_EINVAL, std::string(who) + ": no parameters bound (ffvd_set_params or pass params)");
     return FFVD_OK;
 }
 
-static int check_info(ffvd_handle *h) {
+int ffvd::check_info(ffvd_handle *h) {
     const int Dl = h->Dl;
     h->stalled = false;
     for (int i = 0; i < Dl + h->nbatch; ++i) {
@@ -1123,6 +1122,12 @@ static int check_info(ffvd_handle *h) {
             return set_error(h, FFVD_ENOTPD, msg);
         }
     }
+    return FFVD_OK;
+}
+
+int ffvd::check_finite(ffvd_handle *h, const double *sums, int n, const char *who, const char *what) {
+    for (int i = 0; i < n; ++i)
+        if (!std::isfinite(sums[i])) return set_error(h, FFVD_ENOTPD, std::string(who) + ": non-finite " + what);
     return FFVD_OK;
 }
 
@@ -1216,8 +1221,7 @@ extern "C" int ffvd_elbo(ffvd_handle *h, const ffvd_params *p, uint32_t flags, d
     }
     if ((rc = ready(h, "ffvd_elbo"))) return rc;
     if ((rc = fetch_with_stall_recovery(h, [&] { return enqueue_elbo(h, nullptr, nullptr); }))) return rc;
-    if (out_terms) memcpy(out_terms, h->h_out, 8 * sizeof(double));
-    if (out_nll) *out_nll = h->h_out[FFVD_TERM_NLL] / (double)h->cfg.S_local;
+    report_local(h, out_terms, out_nll);
     return FFVD_OK;
 }
 
@@ -1306,10 +1310,13 @@ extern "C" int ffvd_stage_times(ffvd_handle *h, double out_ms[8], int32_t out_la
 
 // ---- backward pass: backward.hip (enqueue_grad, copy_grads_out); it runs on the handle's streams right behind the forward kernels ----------
 // forward + backward pass of one training iteration: ONE launch where the handle has the small-problem plan (tiny.hip)
-static int enqueue_forward_backward(ffvd_handle *h, int S_total) {
+int ffvd::enqueue_forward_backward(ffvd_handle *h, int S_total) {
     if (h->cfg.grad && tiny_selected(h)) return enqueue_tiny(h, nullptr, nullptr, true, S_total);
     const int r = enqueue_elbo(h, nullptr, nullptr);
     return r ? r : enqueue_grad(h, S_total);
+}
+int ffvd::run_forward_backward(ffvd_handle *h, int S_total) {
+    return fetch_with_stall_recovery(h, [&] { return enqueue_forward_backward(h, S_total); });
 }
 
 extern "C" int ffvd_elbo_grad(ffvd_handle *h, const ffvd_params *p, uint32_t flags, int S_total, double out_terms[8],
@@ -1330,344 +1337,43 @@ extern "C" int ffvd_elbo_grad(ffvd_handle *h, const ffvd_params *p, uint32_t fla
         } else if ((rc = ffvd_set_params(h, p, 0))) return rc;
     }
     if ((rc = ready(h, "ffvd_elbo_grad"))) return rc;
-    if ((rc = fetch_with_stall_recovery(h, [&] { return enqueue_forward_backward(h, S_total); })))
-        return rc;
+    if ((rc = run_forward_backward(h, S_total))) return rc;
     if ((rc = copy_grads_out(h, gout))) return rc;
-    const ffvd_config &c = h->cfg;
-    hipStream_t s = h->stream;
-    HIP_TRY(hipStreamSynchronize(s));
-    if (out_terms) memcpy(out_terms, h->h_out, 8 * sizeof(double));
-    if (out_nll) *out_nll = h->h_out[FFVD_TERM_NLL] / (double)c.S_local;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    report_local(h, out_terms, out_nll);
     return FFVD_OK;
 }
 
-// ---- optimiser steps on the resident parameters --------------------------------------
-static constexpr int NPARAM = 9;       // order of the FFVD_TRAIN_* bits: X, Z, logvariance, loglengthscales, log_Q, CC, DD, log_Rchols, U
-static void param_table(ffvd_handle *h, double *theta[NPARAM], const double *grad[NPARAM], size_t n[NPARAM]) {
-    const ffvd_config &c = h->cfg;
-    const size_t P = h->P, J = c.Ydim;
-    const ffvd_handle::GradWs &g = h->gw;
-    const ffvd_params &p = h->cur;
-    double *th[NPARAM] = {const_cast<double *>(p.X), const_cast<double *>(p.Z), const_cast<double *>(p.logvariance),
-                          const_cast<double *>(p.loglengthscales), const_cast<double *>(p.log_Q), const_cast<double *>(p.CC),
-                          const_cast<double *>(p.DD), const_cast<double *>(p.log_Rchols), const_cast<double *>(p.U)};
-    const double *gr[NPARAM] = {g.dX, g.dZ, g.dlogvar, g.dloglen, g.dlogQ, g.dCC, g.dDD, g.dlogR, g.dU};
-    const size_t nn[NPARAM] = {(size_t)c.S_local * (c.T + 1) * c.D, (size_t)c.M * P, (size_t)c.D, (size_t)c.D * P, (size_t)c.D,
-                               (size_t)c.D * J, J, J * J, g.dU ? (size_t)c.M * c.D : 0};      // U only where it has a gradient
-    for (int i = 0; i < NPARAM; ++i) { theta[i] = th[i]; grad[i] = gr[i]; n[i] = nn[i]; }
-}
-
-extern "C" int ffvd_optimizer_reset(ffvd_handle *h) {
-    if (!h) return set_error(nullptr, FFVD_EINVAL, "ffvd_optimizer_reset: null handle");
-    if (!h->cfg.grad) return set_error(h, FFVD_EINVAL, "ffvd_optimizer_reset: the handle was created without grad = 1");
+// ffvd_get_params / ffvd_update_params: the bound arrays to / from the host arrays of `host` (NULL = skip), complete on return
+static int copy_params(ffvd_handle *h, const ffvd_params *host, hipMemcpyKind kind) {
     HIP_TRY(hipSetDevice(h->cfg.device_id));
-    double *theta[NPARAM]; const double *grad[NPARAM]; size_t n[NPARAM];
-    param_table(h, theta, grad, n);
     for (int i = 0; i < NPARAM; ++i) {
-        if (!n[i]) continue;
-        if (!h->adam_m[i]) { HIP_TRY(dev_alloc(h, &h->adam_m[i], n[i])); HIP_TRY(dev_alloc(h, &h->adam_v[i], n[i])); }
-        HIP_TRY(hipMemsetAsync(h->adam_m[i], 0, n[i] * sizeof(double), h->stream));
-        HIP_TRY(hipMemsetAsync(h->adam_v[i], 0, n[i] * sizeof(double), h->stream));
+        double *dev = const_cast<double *>(h->cur.*PARAM_MEMBER[i]), *hp = const_cast<double *>(host->*PARAM_MEMBER[i]);
+        const bool out = kind == hipMemcpyDeviceToHost;
+        if (dev && hp && param_count(h, i))
+            HIP_TRY(hipMemcpyAsync(out ? hp : dev, out ? dev : hp, param_count(h, i) * sizeof(double), kind, h->stream));
     }
-    h->adam_t = 0;
-    h->adam_ready = true;
-    return FFVD_OK;
-}
-
-static int adam_update(ffvd_handle *h, double lr, double beta1, double beta2, double eps, uint32_t train_mask);
-static int sghmc_prepare(ffvd_handle *h, uint32_t sample_mask, const ffvd_params *noise, const char *who);
-static int sghmc_update(ffvd_handle *h, double epsilon, double mdecay, uint32_t sample_mask, int burn_in);
-
-extern "C" int ffvd_adam_step(ffvd_handle *h, double lr, double beta1, double beta2, double eps, uint32_t train_mask,
-                              double out_terms[8], double *out_nll) {
-    if (!h) return set_error(nullptr, FFVD_EINVAL, "ffvd_adam_step: null handle");
-    if (!h->cfg.grad) return set_error(h, FFVD_EINVAL, "ffvd_adam_step: the handle was created without grad = 1");
-    if (h->Dl != h->cfg.D)
-        return set_error(h, FFVD_EINVAL, "ffvd_adam_step: a latent-dim shard holds partial gradients; use ffvd_adam_step_allreduce");
-    if (h->comm_world > 1)
-        return set_error(h, FFVD_EINVAL, "ffvd_adam_step: this handle is one rank of a multi-rank communicator, its gradient is a share of "
-                                         "the job's; use ffvd_adam_step_allreduce");
-    if (!(lr > 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0))
-        return set_error(h, FFVD_EINVAL, "ffvd_adam_step: bad hyper-parameter");
-    HIP_TRY(hipSetDevice(h->cfg.device_id));
-    int rc;
-    if ((rc = ready(h, "ffvd_adam_step"))) return rc;
-    if (!h->adam_ready && (rc = ffvd_optimizer_reset(h))) return rc;
-    // (a failed factorisation leaves the parameters untouched)
-    if ((rc = fetch_with_stall_recovery(h, [&] { return enqueue_forward_backward(h, h->cfg.S_local); })))
-        return rc;
-    if ((rc = adam_update(h, lr, beta1, beta2, eps, train_mask))) return rc;
-    if (out_terms) memcpy(out_terms, h->h_out, 8 * sizeof(double));
-    if (out_nll) *out_nll = h->h_out[FFVD_TERM_NLL] / (double)h->cfg.S_local;
+    HIP_TRY(hipStreamSynchronize(h->stream));
     return FFVD_OK;
 }
 
 extern "C" int ffvd_get_params(ffvd_handle *h, const ffvd_params *out) {
     if (!h || !out) return set_error(h, FFVD_EINVAL, "ffvd_get_params: null argument");
     if (!h->have_params) return set_error(h, FFVD_EINVAL, "ffvd_get_params: no parameters bound");
-    const ffvd_config &c = h->cfg;
-    const size_t P = h->P, J = c.Ydim;
-    HIP_TRY(hipSetDevice(c.device_id));
-    hipStream_t s = h->stream;
-    const ffvd_params &p = h->cur;
-    const void *src[9] = {p.X, p.Z, p.U, p.logvariance, p.loglengthscales, p.log_Q, p.CC, p.DD, p.log_Rchols};
-    const void *dst[9] = {out->X, out->Z, out->U, out->logvariance, out->loglengthscales, out->log_Q, out->CC, out->DD,
-                          out->log_Rchols};
-    const size_t n[9] = {(size_t)c.S_local * (c.T + 1) * c.D, (size_t)c.M * P, (size_t)c.M * c.D, (size_t)c.D, (size_t)c.D * P,
-                         (size_t)c.D, (size_t)c.D * J, J, J * J};
-    for (int i = 0; i < 9; ++i)
-        if (dst[i] && src[i] && n[i])
-            HIP_TRY(hipMemcpyAsync(const_cast<void *>(dst[i]), src[i], n[i] * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return FFVD_OK;
+    return copy_params(h, out, hipMemcpyDeviceToHost);
 }
 
 // ffvd_update_params: overwrite some of the bound parameter arrays from host memory (NULL = keep).
 extern "C" int ffvd_update_params(ffvd_handle *h, const ffvd_params *p) {
     if (!h || !p) return set_error(h, FFVD_EINVAL, "ffvd_update_params: null argument");
     if (!h->have_params) return set_error(h, FFVD_EINVAL, "ffvd_update_params: no parameters bound yet (ffvd_set_params)");
-    const ffvd_config &c = h->cfg;
-    const size_t P = h->P, J = c.Ydim;
-    HIP_TRY(hipSetDevice(c.device_id));
-    const ffvd_params &cur = h->cur;
-    const void *dst[9] = {cur.X, cur.Z, cur.U, cur.logvariance, cur.loglengthscales, cur.log_Q, cur.CC, cur.DD, cur.log_Rchols};
-    const void *src[9] = {p->X, p->Z, p->U, p->logvariance, p->loglengthscales, p->log_Q, p->CC, p->DD, p->log_Rchols};
-    const size_t n[9] = {(size_t)c.S_local * (c.T + 1) * c.D, (size_t)c.M * P, (size_t)c.M * c.D, (size_t)c.D, (size_t)c.D * P,
-                         (size_t)c.D, (size_t)c.D * J, J, J * J};
-    for (int i = 0; i < 9; ++i)
-        if (src[i] && dst[i] && n[i])
-            HIP_TRY(hipMemcpyAsync(const_cast<void *>(dst[i]), src[i], n[i] * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return FFVD_OK;
+    return copy_params(h, p, hipMemcpyHostToDevice);
 }
 
-extern "C" int ffvd_sghmc_step(ffvd_handle *h, double epsilon, double mdecay, uint32_t sample_mask, int burn_in,
-                               const ffvd_params *noise, double out_terms[8], double *out_nll) {
-    if (!h) return set_error(nullptr, FFVD_EINVAL, "ffvd_sghmc_step: null handle");
-    if (!h->cfg.grad) return set_error(h, FFVD_EINVAL, "ffvd_sghmc_step: the handle was created without grad = 1");
-    if (h->Dl != h->cfg.D)
-        return set_error(h, FFVD_EINVAL, "ffvd_sghmc_step: a latent-dim shard holds partial gradients; use ffvd_sghmc_step_allreduce");
-    if (h->comm_world > 1)
-        return set_error(h, FFVD_EINVAL, "ffvd_sghmc_step: this handle is one rank of a multi-rank communicator, its gradient is a share of "
-                                         "the job's; use ffvd_sghmc_step_allreduce");
-    if (!noise || !(epsilon > 0.0) || !(mdecay >= 0.0))
-        return set_error(h, FFVD_EINVAL, "ffvd_sghmc_step: bad argument");
-    if (sample_mask & FFVD_TRAIN_X)
-        return set_error(h, FFVD_EINVAL, "ffvd_sghmc_step: X is never an SG-HMC variable (dgp_model.py:213-244)");
-    HIP_TRY(hipSetDevice(h->cfg.device_id));
-    int rc;
-    if ((rc = ready(h, "ffvd_sghmc_step"))) return rc;
-    if ((rc = sghmc_prepare(h, sample_mask, noise, "ffvd_sghmc_step"))) return rc;
-    if ((rc = fetch_with_stall_recovery(h, [&] { return enqueue_forward_backward(h, h->cfg.S_local); })))
-        return rc;
-    if ((rc = sghmc_update(h, epsilon, mdecay, sample_mask, burn_in))) return rc;
-    if (out_terms) memcpy(out_terms, h->h_out, 8 * sizeof(double));
-    if (out_nll) *out_nll = h->h_out[FFVD_TERM_NLL] / (double)h->cfg.S_local;
-    return FFVD_OK;
-}
-
-// ---- sharded, device-resident training step (multi-GPU counterpart of adam.minimize(nll), dgp_model.py:303-305 /
-// train_hypers, base_model.py:944-950, and of one burn_in_op / sample_op, base_model.py:143-179) ---------------------------
-// Every rank: forward + backward with the whole job's chain count as the divisor, so that its gradient block is its ADDITIVE
-// share; ONE all-reduce(sum) of [8 term sums | shared-parameter gradients (| dX for latent-dim shards)] in place in HBM;
-// then the fused update from the reduced block.  No gradient crosses PCIe; the only host traffic is the result block.
-static int train_local(ffvd_handle *h, int S_total, const char *who) {
-    if (!h->cfg.grad) return set_error(h, FFVD_EINVAL, std::string(who) + ": the handle was created without grad = 1");
-    if (S_total < h->cfg.S_local) return set_error(h, FFVD_EINVAL, std::string(who) + ": S_total < S_local");
-    HIP_TRY(hipSetDevice(h->cfg.device_id));
-    int rc;
-    if ((rc = ready(h, who))) return rc;
-    h->train_S_total = 0;
-    if ((rc = enqueue_forward_backward(h, S_total))) return rc;
-    HIP_TRY(hipMemcpyAsync(h->gw.pack, h->out_terms, 8 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    h->train_S_total = S_total;
-    return FFVD_OK;
-}
-
-// doubles of the block that take part in the exchange: chain shards keep dX (their own chains' rows) out of it
-static size_t train_exchange_count(const ffvd_handle *h) {
-    return (h->Dl != h->cfg.D) ? h->gw.pack_total : h->gw.pack_shared;
-}
-
-// result block + the (reduced) sums to the host, one synchronisation; a failed factorisation anywhere leaves the parameters as they are
-static int train_fetch(ffvd_handle *h, const char *who) {
-    if (h->train_S_total <= 0) return set_error(h, FFVD_EINVAL, std::string(who) + ": no pending backward pass (ffvd_train_local first)");
-    hipStream_t s = h->stream;
-    HIP_TRY(hipMemcpyAsync(h->h_res, h->resblk, h->res_bytes, hipMemcpyDeviceToHost, s));      // this rank's chain nll + info flags
-    HIP_TRY(hipMemcpyAsync(h->h_sums, h->gw.pack, 8 * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    h->train_S_total = 0;
-    int rc;
-    if ((rc = check_info(h))) return rc;
-    for (int i = 0; i < 8; ++i)
-        if (!std::isfinite(h->h_sums[i]))
-            return set_error(h, FFVD_ENOTPD, std::string(who) + ": non-finite sums after the exchange (a factorisation failed or was abandoned on another rank); parameters untouched");
-    return FFVD_OK;
-}
-
-static void train_report(ffvd_handle *h, double out_terms[8], double *out_nll) {
-    if (out_terms) memcpy(out_terms, h->h_sums, 8 * sizeof(double));
-    if (out_nll) *out_nll = h->h_sums[FFVD_TERM_NLL] / h->h_sums[FFVD_TERM_COUNT];
-}
-
-static int adam_update(ffvd_handle *h, double lr, double beta1, double beta2, double eps, uint32_t train_mask) {
-    double *theta[NPARAM]; const double *grad[NPARAM]; size_t n[NPARAM];
-    param_table(h, theta, grad, n);
-    OptTable tab{};
-    for (int i = 0; i < NPARAM; ++i) {
-        if (!(train_mask & (1u << i)) || n[i] == 0) continue;
-        OptTensor &t = tab.t[tab.count++];
-        t.theta = theta[i]; t.grad = grad[i]; t.s0 = h->adam_m[i]; t.s1 = h->adam_v[i]; t.n = (int64_t)n[i];
-    }
-    h->adam_t += 1;
-    const double lr_t = lr * sqrt(1.0 - pow(beta2, (double)h->adam_t)) / (1.0 - pow(beta1, (double)h->adam_t));
-    launch_adam(h->stream, tab, lr_t, beta1, beta2, eps);
-    HIP_TRY(hipGetLastError());
-    return FFVD_OK;
-}
-
-extern "C" int ffvd_train_local(ffvd_handle *h, int S_total) {
-    if (!h) return set_error(nullptr, FFVD_EINVAL, "ffvd_train_local: null handle");
-    return train_local(h, S_total, "ffvd_train_local");
-}
-
-extern "C" int64_t ffvd_train_exchange_count(const ffvd_handle *h) { return (h && h->cfg.grad) ? (int64_t)train_exchange_count(h) : 0; }
-
-extern "C" void *ffvd_train_exchange_ptr(ffvd_handle *h) { return (h && h->cfg.grad) ? (void *)h->gw.pack : nullptr; }
-
-extern "C" int ffvd_train_exchange_get(ffvd_handle *h, double *host_out) {
-    if (!h || !host_out || !h->cfg.grad) return set_error(h, FFVD_EINVAL, "ffvd_train_exchange_get: bad argument");
-    HIP_TRY(hipSetDevice(h->cfg.device_id));
-    HIP_TRY(hipMemcpyAsync(host_out, h->gw.pack, train_exchange_count(h) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return FFVD_OK;
-}
-
-extern "C" int ffvd_train_exchange_set(ffvd_handle *h, const double *host_in) {
-    if (!h || !host_in || !h->cfg.grad) return set_error(h, FFVD_EINVAL, "ffvd_train_exchange_set: bad argument");
-    HIP_TRY(hipSetDevice(h->cfg.device_id));
-    HIP_TRY(hipMemcpyAsync(h->gw.pack, host_in, train_exchange_count(h) * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));          // the host array is the caller's
-    return FFVD_OK;
-}
-
-extern "C" int ffvd_adam_apply(ffvd_handle *h, double lr, double beta1, double beta2, double eps, uint32_t train_mask,
-                               double out_terms[8], double *out_nll) {
-    if (!h) return set_error(nullptr, FFVD_EINVAL, "ffvd_adam_apply: null handle");
-    if (!h->cfg.grad) return set_error(h, FFVD_EINVAL, "ffvd_adam_apply: the handle was created without grad = 1");
-    if (!(lr > 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0))
-        return set_error(h, FFVD_EINVAL, "ffvd_adam_apply: bad hyper-parameter");
-    HIP_TRY(hipSetDevice(h->cfg.device_id));
-    int rc;
-    if (!h->adam_ready && (rc = ffvd_optimizer_reset(h))) return rc;
-    if ((rc = train_fetch(h, "ffvd_adam_apply"))) return rc;
-    if ((rc = adam_update(h, lr, beta1, beta2, eps, train_mask))) return rc;
-    train_report(h, out_terms, out_nll);
-    return FFVD_OK;
-}
-
-extern "C" int ffvd_adam_step_allreduce(ffvd_handle *h, void *rccl_comm, int S_total, double lr, double beta1, double beta2,
-                                        double eps, uint32_t train_mask, double out_terms[8], double *out_nll) {
-    if (!h) return set_error(nullptr, FFVD_EINVAL, "ffvd_adam_step_allreduce: null handle");
-    if (!(lr > 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0))
-        return set_error(h, FFVD_EINVAL, "ffvd_adam_step_allreduce: bad hyper-parameter");
-    if (!rccl_comm && !h->comm)
-        return set_error(h, FFVD_EINVAL, "ffvd_adam_step_allreduce: no communicator (pass one or call ffvd_comm_init)");
-    int rc;
-    if (h->cfg.grad && !h->adam_ready && (rc = ffvd_optimizer_reset(h))) return rc;
-    if ((rc = train_local(h, S_total, "ffvd_adam_step_allreduce"))) return rc;
-    if ((rc = ffvd_allreduce_sum_async(h, rccl_comm, h->gw.pack, (int64_t)train_exchange_count(h)))) { h->train_S_total = 0; return rc; }
-    if ((rc = train_fetch(h, "ffvd_adam_step_allreduce"))) return rc;
-    if ((rc = adam_update(h, lr, beta1, beta2, eps, train_mask))) return rc;
-    train_report(h, out_terms, out_nll);
-    return FFVD_OK;
-}
-
-static int sghmc_prepare(ffvd_handle *h, uint32_t sample_mask, const ffvd_params *noise, const char *who) {
-    double *theta[NPARAM]; const double *grad[NPARAM]; size_t n[NPARAM];
-    param_table(h, theta, grad, n);
-    const double *nz[NPARAM] = {noise->X, noise->Z, noise->logvariance, noise->loglengthscales, noise->log_Q, noise->CC,
-                                noise->DD, noise->log_Rchols, noise->U};
-    for (int i = 1; i < NPARAM; ++i) {
-        if (!(sample_mask & (1u << i)) || n[i] == 0) continue;
-        if (!nz[i]) return set_error(h, FFVD_EINVAL, std::string(who) + ": a sampled array has no noise array");
-        if (!h->hmc[i][0]) {            // xi, g, g2 <- 1, p <- 0 (base_model.py:151-154)
-            std::vector<double> ones(n[i], 1.0);
-            for (int k = 0; k < 5; ++k) HIP_TRY(dev_alloc(h, &h->hmc[i][k], n[i]));
-            for (int k = 0; k < 3; ++k)
-                HIP_TRY(hipMemcpy(h->hmc[i][k], ones.data(), n[i] * sizeof(double), hipMemcpyHostToDevice));
-            HIP_TRY(hipMemset(h->hmc[i][3], 0, n[i] * sizeof(double)));
-        }
-        HIP_TRY(hipMemcpyAsync(h->hmc[i][4], nz[i], n[i] * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    }
-    return FFVD_OK;
-}
-
-static int sghmc_update(ffvd_handle *h, double epsilon, double mdecay, uint32_t sample_mask, int burn_in) {
-    double *theta[NPARAM]; const double *grad[NPARAM]; size_t n[NPARAM];
-    param_table(h, theta, grad, n);
-    OptTable tab{};
-    for (int i = 1; i < NPARAM; ++i) {
-        if (!(sample_mask & (1u << i)) || n[i] == 0) continue;
-        OptTensor &t = tab.t[tab.count++];
-        t.theta = theta[i]; t.grad = grad[i]; t.s0 = h->hmc[i][0]; t.s1 = h->hmc[i][1]; t.s2 = h->hmc[i][2];
-        t.s3 = h->hmc[i][3]; t.noise = h->hmc[i][4]; t.n = (int64_t)n[i];
-    }
-    // X_N = rows of X (dgp_model.py:203) -- of the JOB's trajectory: a T-shard handle holds T_r + 1 of its T_total + 1 rows
-    const double x_n = (double)((h->cfg.T_total > 0 ? h->cfg.T_total : h->cfg.T) + 1);
-    launch_sghmc(h->stream, tab, epsilon, mdecay, x_n, burn_in);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(h->stream));           // the noise arrays are the caller's: done with them on return
-    return FFVD_OK;
-}
-
-extern "C" int ffvd_sghmc_step_allreduce(ffvd_handle *h, void *rccl_comm, int S_total, double epsilon, double mdecay,
-                                         uint32_t sample_mask, int burn_in, const ffvd_params *noise, double out_terms[8],
-                                         double *out_nll) {
-    if (!h) return set_error(nullptr, FFVD_EINVAL, "ffvd_sghmc_step_allreduce: null handle");
-    if (!h->cfg.grad) return set_error(h, FFVD_EINVAL, "ffvd_sghmc_step_allreduce: the handle was created without grad = 1");
-    if (!noise || !(epsilon > 0.0) || !(mdecay >= 0.0)) return set_error(h, FFVD_EINVAL, "ffvd_sghmc_step_allreduce: bad argument");
-    if (sample_mask & FFVD_TRAIN_X)
-        return set_error(h, FFVD_EINVAL, "ffvd_sghmc_step_allreduce: X is never an SG-HMC variable (dgp_model.py:213-244)");
-    if (!rccl_comm && !h->comm)
-        return set_error(h, FFVD_EINVAL, "ffvd_sghmc_step_allreduce: no communicator (pass one or call ffvd_comm_init)");
-    HIP_TRY(hipSetDevice(h->cfg.device_id));
-    int rc;
-    if ((rc = ready(h, "ffvd_sghmc_step_allreduce"))) return rc;
-    if ((rc = sghmc_prepare(h, sample_mask, noise, "ffvd_sghmc_step_allreduce"))) return rc;
-    if ((rc = train_local(h, S_total, "ffvd_sghmc_step_allreduce"))) return rc;
-    if ((rc = ffvd_allreduce_sum_async(h, rccl_comm, h->gw.pack, (int64_t)train_exchange_count(h)))) { h->train_S_total = 0; return rc; }
-    if ((rc = train_fetch(h, "ffvd_sghmc_step_allreduce"))) return rc;
-    if ((rc = sghmc_update(h, epsilon, mdecay, sample_mask, burn_in))) return rc;
-    train_report(h, out_terms, out_nll);
-    return FFVD_OK;
-}
-
-extern "C" int ffvd_sghmc_apply(ffvd_handle *h, double epsilon, double mdecay, uint32_t sample_mask, int burn_in,
-                                const ffvd_params *noise, double out_terms[8], double *out_nll) {
-    if (!h) return set_error(nullptr, FFVD_EINVAL, "ffvd_sghmc_apply: null handle");
-    if (!h->cfg.grad) return set_error(h, FFVD_EINVAL, "ffvd_sghmc_apply: the handle was created without grad = 1");
-    if (!noise || !(epsilon > 0.0) || !(mdecay >= 0.0)) return set_error(h, FFVD_EINVAL, "ffvd_sghmc_apply: bad argument");
-    if (sample_mask & FFVD_TRAIN_X) return set_error(h, FFVD_EINVAL, "ffvd_sghmc_apply: X is never an SG-HMC variable (dgp_model.py:213-244)");
-    HIP_TRY(hipSetDevice(h->cfg.device_id));
-    int rc;
-    if ((rc = sghmc_prepare(h, sample_mask, noise, "ffvd_sghmc_apply"))) return rc;
-    if ((rc = train_fetch(h, "ffvd_sghmc_apply"))) return rc;
-    if ((rc = sghmc_update(h, epsilon, mdecay, sample_mask, burn_in))) return rc;
-    train_report(h, out_terms, out_nll);
-    return FFVD_OK;
-}
-
-// ---- T-shard fallback (include/ffvd_abi.h "T-shard") ------------------------------------------------------
-static int tshard_ready(ffvd_handle *h, const char *who) {
-    if (!h) return set_error(nullptr, FFVD_EINVAL, std::string(who) + ": null handle");
-    if (h->cfg.T_total <= 0) return set_error(h, FFVD_EINVAL, std::string(who) + ": the handle is not a T-shard (cfg.T_total = 0)");
-    return ready(h, who);
-}
-
+// ---- T-shard fallback (include/ffvd_abi.h "T-shard"): the two launch sequences; entry points in train.hip ------------------
 // this shard's rows: raw Gram tiles K_uf K_fu + delta^T K_fu rows into the exchange buffer, likelihood / transition /
 // trace sums into its tail.  The K_uu chain (identical on every rank) runs first on the same stream.
-static int enqueue_tshard_local(ffvd_handle *h) {
+int ffvd::enqueue_tshard_local(ffvd_handle *h) {
     const ffvd_config &c = h->cfg;
     const int Mp = h->Mp, Tp = h->Tp, Dl = h->Dl, P = h->P;
     hipStream_t s = h->stream;
@@ -1684,25 +1390,14 @@ static int enqueue_tshard_local(ffvd_handle *h) {
     gk.d_begin = c.d_begin; gk.b0 = 0; gk.nb = Dl; gk.yn_over_batch = 1.0; gk.H = h->Kinv; gk.h_stride = msq;
     launch_gram(s, gk);                                                     // K^-1 = L^-T L^-1
     launch_h_finish(s, h->Kuu, Mp, kstride, Dl, h->kterms);                 // log|K|
-    ProjectArgs pa{};
-    pa.kind = c.kernel_kind;
-    pa.x = p.X; pa.x_chain_stride = (size_t)(c.T + 1) * c.D; pa.x_ld = c.D; pa.x_cols = c.D;
-    pa.ctrl = h->ctrl; pa.T = c.T; pa.Tp = Tp; pa.C = c.C; pa.P = P; pa.M = c.M; pa.Mp = Mp; pa.Dl = Dl;
-    pa.d_begin = c.d_begin; pa.hv = hv; pa.b0 = 0; pa.nb = h->nbatch; pa.F = h->F; pa.ng = h->ng;
-    launch_kfu_build(s, pa);
+    launch_kfu_build(s, elbo_project_args(h, hv, 0, c.S_local, true));     // (a T-shard has no growpart: the row comes from the Gram launch)
     GramArgs gr{};
     gr.mode = GRAM_PLAIN; gr.A = h->F; gr.a_stride = (size_t)Tp * Mp; gr.rows = Tp; gr.with_row = 1; gr.brow = Mp;
     gr.X = p.X; gr.log_Q = p.log_Q; gr.T = c.T; gr.D = c.D; gr.Mp = Mp; gr.Dl = Dl; gr.d_begin = c.d_begin; gr.b0 = 0;
     gr.nb = h->nbatch; gr.yn_over_batch = 1.0; gr.H = h->tsbuf; gr.h_stride = (size_t)(Mp + 1) * Mp;
     if (h->gpart) { gr.ksplit = h->gsplit; gr.part = h->gpart; }
     launch_gram(s, gr);                                                     // raw sum over this shard's rows
-    ReduceArgs ra{};
-    ra.kind = c.kernel_kind; ra.branch = c.branch; ra.X = p.X; ra.ctrl = h->ctrl; ra.Y = h->Y;
-    ra.log_Q = p.log_Q; ra.CC = p.CC; ra.DD = p.DD; ra.log_Rchols = p.log_Rchols; ra.variance = h->variance;
-    ra.T = c.T; ra.Tp = Tp; ra.D = c.D; ra.C = c.C; ra.Ydim = c.Ydim; ra.Dl = Dl; ra.d_begin = c.d_begin;
-    ra.S = c.S_local; ra.ng = h->ng; ra.shared_terms = c.shared_terms;
-    ra.xk = p.X; ra.xk_chain_stride = (size_t)(c.T + 1) * c.D; ra.xk_ld = c.D; ra.xk_cols = c.D;
-    ra.rowsq = nullptr; ra.fmean = h->fmean; ra.chain_terms = h->chain_terms;
+    ReduceArgs ra = elbo_reduce_args(h, true);
     ra.skip_x0 = c.t_begin > 0;
     ra.info = h->info; ra.ninfo = Dl;       // a failed / abandoned K_uu chain of THIS shard turns its chain sums into NaN: they are part of the exchange
     launch_chain_reduce(s, ra, h->chain_partial);
@@ -1711,9 +1406,9 @@ static int enqueue_tshard_local(ffvd_handle *h) {
 }
 
 // on the all-reduced sums: A = K_uu + K_uf K_fu / Q, the trace partials, Cholesky(A), the solve, the assembly
-static int enqueue_tshard_finish(ffvd_handle *h) {
+int ffvd::enqueue_tshard_finish(ffvd_handle *h) {
     const ffvd_config &c = h->cfg;
-    const int Mp = h->Mp, Dl = h->Dl, P = h->P;
+    const int Mp = h->Mp, Dl = h->Dl;
     hipStream_t s = h->stream;
     const ffvd_params &p = h->cur;
     const size_t msq = (size_t)Mp * Mp;
@@ -1743,381 +1438,9 @@ static int enqueue_tshard_finish(ffvd_handle *h) {
         launch_potrf_ext(s, h->H, Mp, NB, 0, h->nbatch, ga.h_stride, h->info + Dl, h->dinvH, CHOL_FLOW, nullptr, 0, false, true);
         launch_h_finish(s, h->H, Mp, ga.h_stride, h->nbatch, h->hterms);
     }
-    FinalizeArgs fa{};
-    fa.kind = c.kernel_kind; fa.branch = c.branch; fa.prior_type = c.prior_type; fa.shared_terms = c.shared_terms;
+    FinalizeArgs fa = elbo_finalize_args(h, nullptr, true);
     fa.T = c.T_total;                                   // every /T of dgp_model.py:261-297 is the whole job's
-    fa.D = c.D; fa.P = P; fa.M = c.M; fa.Ydim = c.Ydim; fa.Dl = Dl; fa.d_begin = c.d_begin;
-    fa.S = c.S_local; fa.Z = p.Z; fa.U = p.U; fa.logvar = p.logvariance; fa.loglen = p.loglengthscales;
-    fa.log_Q = p.log_Q; fa.CC = p.CC; fa.DD = p.DD; fa.log_Rchols = p.log_Rchols;
-    fa.chain_terms = h->chain_terms; fa.hterms = h->hterms; fa.chain_nll = h->chain_nll;
-    fa.route = 1; fa.kterms = h->kterms; fa.trpart = h->trpart; fa.ntiles = h->ntiles;
-    fa.out_terms = h->out_terms;
-    fa.info = h->info; fa.ninfo = Dl + h->nbatch;
     launch_finalize(s, fa);
     HIP_TRY(hipGetLastError());
-    return FFVD_OK;
-}
-
-extern "C" int64_t ffvd_tshard_count(const ffvd_handle *h) { return h ? h->ts_count : 0; }
-
-extern "C" int ffvd_tshard_local(ffvd_handle *h) {
-    int rc;
-    if ((rc = tshard_ready(h, "ffvd_tshard_local"))) return rc;
-    HIP_TRY(hipSetDevice(h->cfg.device_id));
-    return enqueue_tshard_local(h);
-}
-
-extern "C" int ffvd_tshard_get(ffvd_handle *h, double *host_out) {
-    int rc;
-    if ((rc = tshard_ready(h, "ffvd_tshard_get"))) return rc;
-    if (!host_out) return set_error(h, FFVD_EINVAL, "ffvd_tshard_get: null output");
-    HIP_TRY(hipSetDevice(h->cfg.device_id));
-    HIP_TRY(hipMemcpyAsync(host_out, h->tsbuf, (size_t)h->ts_count * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return FFVD_OK;
-}
-
-extern "C" int ffvd_tshard_set(ffvd_handle *h, const double *host_in) {
-    int rc;
-    if ((rc = tshard_ready(h, "ffvd_tshard_set"))) return rc;
-    if (!host_in) return set_error(h, FFVD_EINVAL, "ffvd_tshard_set: null input");
-    HIP_TRY(hipSetDevice(h->cfg.device_id));
-    HIP_TRY(hipMemcpyAsync(h->tsbuf, host_in, (size_t)h->ts_count * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return FFVD_OK;
-}
-
-// The finish (S_total > 0: and the backward pass behind it) with the recovery of an abandoned dataflow Cholesky(A).
-static int tshard_finish_run(ffvd_handle *h, int S_total, const char *who, double out_terms[8], double *out_nll) {
-    int rc;
-    // The finish is a pure function of the exchanged buffer (read-only here) and of this rank's K_uu chain, and no collective
-    // follows inside the call: a dataflow Cholesky(A) that gave up on a bounded wait is re-run ONCE with the launch-per-column
-    // variant, like the single-rank entry points (fetch_with_stall_recovery).  A failure of the K_uu chain itself (local phase,
-    // BEFORE the exchange) has already turned the exchanged chain sums into NaN on every rank.
-    for (int attempt = 0;; ++attempt) {
-        {
-            CholOverrideGuard guard;
-            if (attempt == 1) {
-                guard.force_left();
-                HIP_TRY(hipMemsetAsync(h->info + h->Dl, 0, (size_t)h->nbatch * sizeof(int32_t), h->stream));
-            }
-            if ((rc = enqueue_tshard_finish(h))) return rc;
-            if (S_total > 0) {
-                // backward pass on the job's factorisation: this shard's ADDITIVE share of every gradient (grad_finalize: the
-                // M x M-side terms and the priors count on the first shard only), dX for the shard's own rows.  The term sums
-                // head the block like in a sharded training step -- the job's on the first shard, zero elsewhere -- so that
-                // ONE all-reduce(sum) of ffvd_train_exchange_count doubles completes both.
-                if ((rc = enqueue_grad_b(h, S_total))) return rc;
-                if (h->cfg.t_begin == 0)
-                    HIP_TRY(hipMemcpyAsync(h->gw.pack, h->out_terms, 8 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-                else HIP_TRY(hipMemsetAsync(h->gw.pack, 0, 8 * sizeof(double), h->stream));
-            }
-        }
-        HIP_TRY(hipMemcpyAsync(h->h_res, h->resblk, h->res_bytes, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        rc = check_info(h);
-        bool kuu_ok = true;
-        for (int i = 0; i < h->Dl; ++i) kuu_ok = kuu_ok && h->h_info[i] == 0;
-        if (rc == FFVD_EDEVICE && h->stalled && kuu_ok && attempt == 0) continue;
-        if (rc == FFVD_OK && attempt == 1) {
-            if (h->stall_recoveries++ == 0)
-                h->warning = "warning: the one-launch (dataflow) Cholesky gave up on a bounded wait; the T-shard finish was re-run with "
-                             "the launch-per-column Cholesky and completed";
-            h->err = h->warning;
-        }
-        break;
-    }
-    if (rc) return rc;
-    for (int i = 0; i < 7; ++i)
-        if (!std::isfinite(h->h_out[i]))
-            return set_error(h, FFVD_ENOTPD, std::string(who) + ": non-finite sums after the exchange (a factorisation failed or was abandoned on another rank)");
-    if (out_terms) memcpy(out_terms, h->h_out, 8 * sizeof(double));
-    if (out_nll) *out_nll = h->h_out[FFVD_TERM_NLL] / (double)h->cfg.S_local;
-    return FFVD_OK;
-}
-
-extern "C" int ffvd_tshard_finish(ffvd_handle *h, double out_terms[8], double *out_nll) {
-    int rc;
-    if ((rc = tshard_ready(h, "ffvd_tshard_finish"))) return rc;
-    HIP_TRY(hipSetDevice(h->cfg.device_id));
-    return tshard_finish_run(h, 0, "ffvd_tshard_finish", out_terms, out_nll);
-}
-
-// ---- gradient of a T-sharded job -------------------------------------------------------------------------
-// After the exchange of the raw tiles every shard holds the job's A, its factor, u and Gamma; the K_fu side of the backward pass
-// (E = (2 K_fu Gamma + alpha delta u^T) o K_fu and its reductions) runs over the shard's own rows and is additive over shards,
-// like the likelihood / transition sums; the M x M side (K_uu chain rule, tr(A^-1 G), u^T G u, priors) is the same on every shard
-// and counted on the first.  dX covers the shard's own T + 1 rows: the row two neighbouring shards share (the last of one, the
-// first of the next) gets a part from each -- the caller adds them.
-static int tshard_grad_ready(ffvd_handle *h, const char *who, int S_total) {
-    int rc;
-    if ((rc = tshard_ready(h, who))) return rc;
-    if (!h->cfg.grad) return set_error(h, FFVD_EINVAL, std::string(who) + ": the handle was created without grad = 1");
-    if (S_total < h->cfg.S_local) return set_error(h, FFVD_EINVAL, std::string(who) + ": S_total < S_local");
-    return FFVD_OK;
-}
-
-extern "C" int ffvd_tshard_finish_grad(ffvd_handle *h, int S_total, double out_terms[8], double *out_nll) {
-    int rc;
-    if ((rc = tshard_grad_ready(h, "ffvd_tshard_finish_grad", S_total))) return rc;
-    HIP_TRY(hipSetDevice(h->cfg.device_id));
-    return tshard_finish_run(h, S_total, "ffvd_tshard_finish_grad", out_terms, out_nll);
-}
-
-extern "C" int ffvd_tshard_grad_fetch(ffvd_handle *h, double out_terms[8], const ffvd_grads *gout) {
-    int rc;
-    if ((rc = tshard_grad_ready(h, "ffvd_tshard_grad_fetch", h ? h->cfg.S_local : 0))) return rc;
-    if (!gout) return set_error(h, FFVD_EINVAL, "ffvd_tshard_grad_fetch: null gradient struct");
-    HIP_TRY(hipSetDevice(h->cfg.device_id));
-    if ((rc = copy_grads_out(h, gout))) return rc;
-    HIP_TRY(hipMemcpyAsync(h->h_sums, h->gw.pack, 8 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    for (int i = 0; i < 8; ++i)
-        if (!std::isfinite(h->h_sums[i]))
-            return set_error(h, FFVD_ENOTPD, "ffvd_tshard_grad_fetch: non-finite sums in the exchanged block (a factorisation failed on another rank)");
-    if (out_terms) memcpy(out_terms, h->h_sums, 8 * sizeof(double));
-    return FFVD_OK;
-}
-
-// Optimiser step of a T-sharded job (dgp_model.py:303-305 trains every variable).  After ffvd_tshard_grad_fetch /
-// ffvd_elbo_tshard_grad the exchanged block in gw.pack holds the WHOLE job's shared-parameter gradients, identical on every shard;
-// dX holds this shard's own T + 1 rows, whose first and last row each lack the part of the neighbouring shard.  The caller adds
-// those parts (one small exchange of boundary rows, ffvd_amd/distributed.py) and hands the rows back here: they replace gw.dX and the
-// fused Adam update runs over every parameter array.  Shared parameters receive the same gradient and carry the same optimiser
-// state on every shard, the two copies of a boundary row likewise: the shards' parameters stay identical without a broadcast.
-extern "C" int ffvd_tshard_adam_apply(ffvd_handle *h, const double *dX_rows, double lr, double beta1, double beta2, double eps,
-                                      uint32_t train_mask, double out_terms[8], double *out_nll) {
-    int rc;
-    if ((rc = tshard_grad_ready(h, "ffvd_tshard_adam_apply", h ? h->cfg.S_local : 0))) return rc;
-    if (!dX_rows) return set_error(h, FFVD_EINVAL, "ffvd_tshard_adam_apply: null dX rows");
-    if (!(lr > 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0))
-        return set_error(h, FFVD_EINVAL, "ffvd_tshard_adam_apply: bad hyper-parameter");
-    HIP_TRY(hipSetDevice(h->cfg.device_id));
-    if (!h->adam_ready && (rc = ffvd_optimizer_reset(h))) return rc;
-    const ffvd_config &c = h->cfg;
-    HIP_TRY(hipMemcpyAsync(h->h_sums, h->gw.pack, 8 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->gw.dX, dX_rows, (size_t)c.S_local * (c.T + 1) * c.D * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));          // the host rows are the caller's
-    for (int i = 0; i < 8; ++i)
-        if (!std::isfinite(h->h_sums[i]))
-            return set_error(h, FFVD_ENOTPD, "ffvd_tshard_adam_apply: non-finite sums in the exchanged block (a factorisation failed on a shard); parameters untouched");
-    if ((rc = adam_update(h, lr, beta1, beta2, eps, train_mask))) return rc;
-    train_report(h, out_terms, out_nll);
-    return FFVD_OK;
-}
-
-// ... and the SG-HMC update (burn_in_op / sample_op, base_model.py:143-179) of a T-sharded job: X is never an SG-HMC variable
-// (dgp_model.py:213-244), so the exchanged block is all it needs -- every shard applies the same update with the same noise.
-extern "C" int ffvd_tshard_sghmc_apply(ffvd_handle *h, double epsilon, double mdecay, uint32_t sample_mask, int burn_in,
-                                       const ffvd_params *noise, double out_terms[8], double *out_nll) {
-    int rc;
-    if ((rc = tshard_grad_ready(h, "ffvd_tshard_sghmc_apply", h ? h->cfg.S_local : 0))) return rc;
-    if (!noise || !(epsilon > 0.0) || !(mdecay >= 0.0)) return set_error(h, FFVD_EINVAL, "ffvd_tshard_sghmc_apply: bad argument");
-    if (sample_mask & FFVD_TRAIN_X) return set_error(h, FFVD_EINVAL, "ffvd_tshard_sghmc_apply: X is never an SG-HMC variable (dgp_model.py:213-244)");
-    HIP_TRY(hipSetDevice(h->cfg.device_id));
-    if ((rc = sghmc_prepare(h, sample_mask, noise, "ffvd_tshard_sghmc_apply"))) return rc;
-    HIP_TRY(hipMemcpyAsync(h->h_sums, h->gw.pack, 8 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    for (int i = 0; i < 8; ++i)
-        if (!std::isfinite(h->h_sums[i]))
-            return set_error(h, FFVD_ENOTPD, "ffvd_tshard_sghmc_apply: non-finite sums in the exchanged block (a factorisation failed on a shard); parameters untouched");
-    if ((rc = sghmc_update(h, epsilon, mdecay, sample_mask, burn_in))) return rc;
-    train_report(h, out_terms, out_nll);
-    return FFVD_OK;
-}
-
-extern "C" int ffvd_allreduce_sum_async(ffvd_handle *h, void *rccl_comm, double *buf_dev, int64_t count);
-extern "C" int ffvd_elbo_tshard(ffvd_handle *h, void *rccl_comm, double out_terms[8], double *out_nll) {
-    int rc;
-    if ((rc = tshard_ready(h, "ffvd_elbo_tshard"))) return rc;
-    HIP_TRY(hipSetDevice(h->cfg.device_id));
-    if ((rc = enqueue_tshard_local(h))) return rc;
-    if ((rc = ffvd_allreduce_sum_async(h, rccl_comm, h->tsbuf, h->ts_count))) return rc;      // the ONE exchange step
-    return ffvd_tshard_finish(h, out_terms, out_nll);
-}
-// nll + gradient of a T-sharded job: two exchange steps (raw tiles + chain sums; then the gradient block), both native RCCL
-extern "C" int ffvd_elbo_tshard_grad(ffvd_handle *h, void *rccl_comm, int S_total, double out_terms[8], double *out_nll,
-                                     const ffvd_grads *gout) {
-    int rc;
-    if ((rc = tshard_grad_ready(h, "ffvd_elbo_tshard_grad", S_total))) return rc;
-    if (!gout) return set_error(h, FFVD_EINVAL, "ffvd_elbo_tshard_grad: null gradient struct");
-    HIP_TRY(hipSetDevice(h->cfg.device_id));
-    if ((rc = enqueue_tshard_local(h))) return rc;
-    if ((rc = ffvd_allreduce_sum_async(h, rccl_comm, h->tsbuf, h->ts_count))) return rc;
-    // a failed finish still takes part in the second exchange (NaN sums at the head of its block): the ranks stay in step
-    const int rc_fin = tshard_finish_run(h, S_total, "ffvd_elbo_tshard_grad", nullptr, nullptr);
-    if (rc_fin) {
-        std::vector<double> nan8(8, std::nan(""));
-        HIP_TRY(hipMemcpy(h->gw.pack, nan8.data(), 8 * sizeof(double), hipMemcpyHostToDevice));
-    }
-    const std::string first_err = rc_fin ? h->err : std::string();
-    if ((rc = ffvd_allreduce_sum_async(h, rccl_comm, h->gw.pack, (int64_t)h->gw.pack_shared))) return rc;
-    if (rc_fin) { HIP_TRY(hipStreamSynchronize(h->stream)); return set_error(h, rc_fin, first_err); }
-    double sums[8];
-    if ((rc = ffvd_tshard_grad_fetch(h, sums, gout))) return rc;
-    if (out_terms) memcpy(out_terms, sums, 8 * sizeof(double));
-    if (out_nll) *out_nll = sums[FFVD_TERM_NLL] / sums[FFVD_TERM_COUNT];
-    return FFVD_OK;
-}
-
-// ---- native RCCL collectives (SURVEY 8b `ffvd_elbo_allreduce(h, rccl_comm)`, 8e) ---------------------------------
-// The only exchange step of the path is an all-reduce(sum) of the 8 partial sums over xGMI.  librccl is bound at run time
-// (dlopen): the library that is already mapped in the process wins (a host that also runs PyTorch has torch's bundled
-// RCCL mapped, and two RCCL copies in one process must be avoided), then $FFVD_RCCL_LIB, then the system library.  A
-// build box or a host without RCCL therefore still loads libffvd_hip.so; the collective entry points then fail loudly.
-#include <dlfcn.h>
-#include <mutex>
-#include <rccl/rccl.h>
-
-namespace {
-struct RcclApi {
-    void *lib = nullptr;
-    ncclResult_t (*GetUniqueId)(ncclUniqueId *) = nullptr;
-    ncclResult_t (*CommInitRank)(ncclComm_t *, int, ncclUniqueId, int) = nullptr;
-    ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
-    ncclResult_t (*AllReduce)(const void *, void *, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t) = nullptr;
-    const char *(*GetErrorString)(ncclResult_t) = nullptr;
-    std::string why;
-};
-void rccl_bind(RcclApi &api);
-RcclApi *rccl_api() {
-    static RcclApi api;
-    static std::once_flag once;             // handles of different threads may ask at the same time
-    std::call_once(once, [] { rccl_bind(api); });
-    return &api;
-}
-void rccl_bind(RcclApi &api) {
-    const char *env = getenv("FFVD_RCCL_LIB");
-    const char *names[] = {"librccl.so.1", "librccl.so"};
-    for (const char *n : names)
-        if (!api.lib) api.lib = dlopen(n, RTLD_NOW | RTLD_NOLOAD);           // whatever the process already runs on
-    if (!api.lib && env && *env) api.lib = dlopen(env, RTLD_NOW | RTLD_GLOBAL);
-    for (const char *n : names)
-        if (!api.lib) api.lib = dlopen(n, RTLD_NOW | RTLD_GLOBAL);
-    if (!api.lib) api.lib = dlopen("/opt/rocm/lib/librccl.so.1", RTLD_NOW | RTLD_GLOBAL);
-    if (!api.lib) {
-        const char *why = dlerror();
-        api.why = std::string("librccl not found: ") + (why ? why : "?");
-        return;
-    }
-    api.GetUniqueId = (decltype(api.GetUniqueId))dlsym(api.lib, "ncclGetUniqueId");
-    api.CommInitRank = (decltype(api.CommInitRank))dlsym(api.lib, "ncclCommInitRank");
-    api.CommDestroy = (decltype(api.CommDestroy))dlsym(api.lib, "ncclCommDestroy");
-    api.AllReduce = (decltype(api.AllReduce))dlsym(api.lib, "ncclAllReduce");
-    api.GetErrorString = (decltype(api.GetErrorString))dlsym(api.lib, "ncclGetErrorString");
-    if (!api.GetUniqueId || !api.CommInitRank || !api.CommDestroy || !api.AllReduce || !api.GetErrorString) {
-        api.why = "librccl lacks an expected symbol";
-        api.lib = nullptr;
-    }
-}
-}  // namespace
-
-#define RCCL_TRY(expr)                                                                             \
-    do {                                                                                           \
-        ncclResult_t r_ = (expr);                                                                  \
-        if (r_ != ncclSuccess) {                                                                   \
-            char buf_[512];                                                                        \
-            snprintf(buf_, sizeof buf_, "%s failed: %s (%s:%d)", #expr, api->GetErrorString(r_), __FILE__, __LINE__); \
-            return set_error(h, FFVD_EDEVICE, buf_);                                               \
-        }                                                                                          \
-    } while (0)
-
-extern "C" int ffvd_comm_unique_id(void *id_out) {
-    ffvd_handle *h = nullptr;
-    if (!id_out) return set_error(nullptr, FFVD_EINVAL, "ffvd_comm_unique_id: null argument");
-    RcclApi *api = rccl_api();
-    if (!api->lib) return set_error(nullptr, FFVD_EDEVICE, "ffvd_comm_unique_id: " + api->why);
-    ncclUniqueId id;
-    RCCL_TRY(api->GetUniqueId(&id));
-    memcpy(id_out, &id, FFVD_COMM_ID_BYTES);
-    return FFVD_OK;
-}
-
-extern "C" int ffvd_comm_init(ffvd_handle *h, int world, int rank, const void *id) {
-    if (!h || !id || world < 1 || rank < 0 || rank >= world)
-        return set_error(h, FFVD_EINVAL, "ffvd_comm_init: bad argument");
-    if (h->comm) return set_error(h, FFVD_EINVAL, "ffvd_comm_init: the handle already owns a communicator");
-    RcclApi *api = rccl_api();
-    if (!api->lib) return set_error(h, FFVD_EDEVICE, "ffvd_comm_init: " + api->why);
-    HIP_TRY(hipSetDevice(h->cfg.device_id));
-    ncclUniqueId uid;
-    static_assert(sizeof(uid) == FFVD_COMM_ID_BYTES, "ncclUniqueId size");
-    memcpy(&uid, id, sizeof uid);
-    ncclComm_t comm = nullptr;
-    RCCL_TRY(api->CommInitRank(&comm, world, uid, rank));
-    h->comm = (void *)comm;
-    h->comm_world = world;
-    h->comm_rank = rank;
-    return FFVD_OK;
-}
-
-extern "C" int ffvd_comm_destroy(ffvd_handle *h) {
-    if (!h) return set_error(nullptr, FFVD_EINVAL, "ffvd_comm_destroy: null handle");
-    if (!h->comm) return FFVD_OK;
-    RcclApi *api = rccl_api();
-    hipSetDevice(h->cfg.device_id);
-    hipStreamSynchronize(h->stream);
-    ncclComm_t comm = (ncclComm_t)h->comm;
-    h->comm = nullptr;
-    if (api->lib) RCCL_TRY(api->CommDestroy(comm));
-    return FFVD_OK;
-}
-
-extern "C" void *ffvd_comm_get(ffvd_handle *h) { return h ? h->comm : nullptr; }
-
-extern "C" int ffvd_allreduce_sum_async(ffvd_handle *h, void *rccl_comm, double *buf_dev, int64_t count) {
-    if (!h || !buf_dev || count < 0) return set_error(h, FFVD_EINVAL, "ffvd_allreduce_sum_async: bad argument");
-    void *comm = rccl_comm ? rccl_comm : h->comm;
-    if (!comm) return set_error(h, FFVD_EINVAL, "ffvd_allreduce_sum_async: no communicator (pass one or call ffvd_comm_init)");
-    RcclApi *api = rccl_api();
-    if (!api->lib) return set_error(h, FFVD_EDEVICE, "ffvd_allreduce_sum_async: " + api->why);
-    HIP_TRY(hipSetDevice(h->cfg.device_id));
-    if (count == 0) return FFVD_OK;
-    RCCL_TRY(api->AllReduce(buf_dev, buf_dev, (size_t)count, ncclDouble, ncclSum, (ncclComm_t)comm, h->stream));
-    return FFVD_OK;
-}
-
-extern "C" int ffvd_allreduce_sum(ffvd_handle *h, void *rccl_comm, double *buf_host, int64_t count) {
-    if (!h || !buf_host || count < 0) return set_error(h, FFVD_EINVAL, "ffvd_allreduce_sum: bad argument");
-    if (count == 0) return FFVD_OK;
-    HIP_TRY(hipSetDevice(h->cfg.device_id));
-    if (h->stage_count < count) {          // device staging buffer, grown on demand and kept by the handle
-        double *d = nullptr;
-        HIP_TRY(dev_alloc(h, &d, (size_t)count));
-        h->stage = d;
-        h->stage_count = count;
-    }
-    HIP_TRY(hipMemcpyAsync(h->stage, buf_host, (size_t)count * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    int rc = ffvd_allreduce_sum_async(h, rccl_comm, h->stage, count);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(buf_host, h->stage, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return FFVD_OK;
-}
-
-extern "C" int ffvd_elbo_allreduce_async(ffvd_handle *h, void *rccl_comm, double *out_terms_dev) {
-    if (!h) return set_error(nullptr, FFVD_EINVAL, "ffvd_elbo_allreduce_async: null handle");
-    int rc;
-    double *dst = out_terms_dev ? out_terms_dev : h->out_terms;
-    if ((rc = ffvd_elbo_async(h, dst))) return rc;
-    return ffvd_allreduce_sum_async(h, rccl_comm, dst, 8);
-}
-
-extern "C" int ffvd_elbo_allreduce(ffvd_handle *h, void *rccl_comm, double out_terms[8], double *out_nll) {
-    if (!h) return set_error(nullptr, FFVD_EINVAL, "ffvd_elbo_allreduce: null handle");
-    int rc;
-    // kernels -> finalize (8 partial sums in HBM) -> ncclAllReduce on the same stream -> one copy back: the only host
-    // synchronisation of the step is the final one
-    if ((rc = ffvd_elbo_allreduce_async(h, rccl_comm, nullptr))) return rc;
-    h->info_pending = false;
-    HIP_TRY(hipMemcpyAsync(h->h_res, h->resblk, h->res_bytes, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if ((rc = check_info(h))) return rc;              // this rank's factorisations
-    bool finite = true;
-    for (int i = 0; i < 8; ++i) finite = finite && std::isfinite(h->h_out[i]);
-    if (!finite)                                      // a failed factorisation on ANOTHER rank poisons the sums with NaN
-        return set_error(h, FFVD_ENOTPD, "ffvd_elbo_allreduce: non-finite partial sums after the all-reduce (a factorisation failed or was abandoned on another rank)");
-    if (out_terms) memcpy(out_terms, h->h_out, 8 * sizeof(double));
-    if (out_nll) *out_nll = h->h_out[FFVD_TERM_NLL] / h->h_out[FFVD_TERM_COUNT];
     return FFVD_OK;
 }

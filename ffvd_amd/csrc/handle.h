@@ -1,9 +1,11 @@
-// The handle behind the C ABI and what the sources that see inside it share: abi.hip (lifetime, the forward iteration, training,
-// shards) and backward.hip (the multi-kernel backward pass).  ops.hip and every other source keep the opaque type.
+// The handle behind the C ABI and what the sources that see inside it share: abi.hip (lifetime, the forward iteration), backward.hip
+// (the multi-kernel backward pass), train.hip (optimiser steps, shards) and comm.hip (RCCL).  ops.hip and every other source keep the
+// opaque type.
 #pragma once
 #include "abi_internal.h"
 #include "tiny.h"
 
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -111,7 +113,6 @@ struct ffvd_handle {
     // Adam state for ffvd_adam_step: first/second moments per parameter array (order of FFVD_TRAIN_* bits), step count
     double *adam_m[9] = {nullptr}, *adam_v[9] = {nullptr};
     double *hmc[9][5] = {{nullptr}};     // SG-HMC state per array: xi, g, g2, p and the uploaded noise
-    bool hmc_ready = false;
     int64_t adam_t = 0;
     bool adam_ready = false;
     // result block and its pinned host staging: [8 term sums][S_local chain nll][Dl + nbatch info flags], contiguous on the device (resblk) and in
@@ -160,8 +161,41 @@ static hipError_t dev_alloc(ffvd_handle *h, T **p, size_t count) {
 
 namespace ffvd {
 
-// Fork the side stream off the main stream (abi.hip)
+// The nine parameter arrays in the order of the FFVD_TRAIN_* bits (bit i = array i): the member of an ffvd_params and the element
+// count.  U counts M x D here (ffvd_get_params, ffvd_update_params); the optimiser table of train.hip gives it 0 where U has no gradient.
+constexpr int NPARAM = 9, PARAM_U = 8;
+constexpr const double *ffvd_params::*PARAM_MEMBER[NPARAM] = {
+    &ffvd_params::X,  &ffvd_params::Z,  &ffvd_params::logvariance, &ffvd_params::loglengthscales, &ffvd_params::log_Q,
+    &ffvd_params::CC, &ffvd_params::DD, &ffvd_params::log_Rchols,  &ffvd_params::U};
+inline size_t param_count(const ffvd_handle *h, int i) {
+    const ffvd_config &c = h->cfg;
+    const size_t P = h->P, J = c.Ydim;
+    const size_t n[NPARAM] = {(size_t)c.S_local * (c.T + 1) * c.D, (size_t)c.M * P, (size_t)c.D, (size_t)c.D * P, (size_t)c.D,
+                              (size_t)c.D * J, J, J * J, (size_t)c.M * c.D};
+    return n[i];
+}
+
+// results to the caller (either pointer may be null): the 8 sums and nll = NLL / chains -- the COUNT among a job's reduced sums
+// (report_sums), S_local for this rank's own result block (report_local)
+inline void report_sums(const double sums[8], double out_terms[8], double *out_nll, double chains = 0.0) {
+    if (out_terms) memcpy(out_terms, sums, 8 * sizeof(double));
+    if (out_nll) *out_nll = sums[FFVD_TERM_NLL] / (chains > 0.0 ? chains : sums[FFVD_TERM_COUNT]);
+}
+inline void report_local(const ffvd_handle *h, double out_terms[8], double *out_nll) {
+    report_sums(h->h_out, out_terms, out_nll, (double)h->cfg.S_local);
+}
+
+// abi.hip: fork the side stream off the main stream; data and parameters bound; the factorisation flags of the fetched result block;
+// FFVD_ENOTPD "<who>: non-finite <what>" unless the n sums are finite; the two launch sequences of a T-shard; forward + backward pass
+// of one training iteration, enqueued / run to its result block with the recovery of a stalled dataflow Cholesky
 int fork_side(ffvd_handle *h, hipEvent_t ev, hipStream_t from, hipStream_t to);
+int ready(ffvd_handle *h, const char *who);
+int check_info(ffvd_handle *h);
+int check_finite(ffvd_handle *h, const double *sums, int n, const char *who, const char *what);
+int enqueue_tshard_local(ffvd_handle *h);
+int enqueue_tshard_finish(ffvd_handle *h);
+int enqueue_forward_backward(ffvd_handle *h, int S_total);
+int run_forward_backward(ffvd_handle *h, int S_total);
 
 // backward.hip: the backward-pass workspace h->gw (create_impl, cfg.grad), the multi-kernel backward pass behind a forward
 // iteration (enqueue_grad_b: its collapsed branch, which a T-shard finish calls directly), gradients to the caller's host arrays

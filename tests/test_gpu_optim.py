@@ -577,6 +577,56 @@ def test_plain_steps_refuse_a_shard():
             e.adam_apply(np.zeros(int(e.lib.ffvd_train_exchange_count(e._h))), 0.01)
 
 
+def test_optimiser_entry_points_name_themselves_in_argument_errors():
+    """Bad hyper-parameters / SG-HMC arguments on real handles, raw library calls (the Python wrappers may validate first): every one
+    of the four Adam and four SG-HMC entry points returns FFVD_EINVAL with its own name in front of the message, before any device
+    work -- the parameters afterwards are bit-equal.  The strings are the literals of the source before these checks were folded."""
+    import ctypes as ct
+    from ffvd_amd import _lib
+    from ffvd_amd.distributed import ShardedElbo
+    params, Y, c, meta = synthetic.make_named("tiny")
+    plain = ElboEngine(meta["T"], meta["D"], meta["C"], meta["M"], meta["S"], route="gram", grad=True)
+    chains = tshard = None
+    try:
+        plain.set_data(Y, c)
+        plain.set_params(params)
+        chains = ShardedElbo(params, Y, c, meta, rank=0, world=1, mode="chains", device=0, always_reduce=True, route="gram", grad=True)
+        tshard = ShardedElbo(params, Y, c, meta, rank=0, world=1, mode="time", device=0, grad=True)
+        engines = {"plain": plain, "chains": chains.engine, "time": tshard.engine}
+        before = {k: e.get_params() for k, e in engines.items()}
+        lib, S = plain.lib, meta["S"]
+        out, nll = np.zeros(8), ct.c_double()
+        res = (_lib.dptr(out), ct.byref(nll))
+        rows = np.zeros((S, meta["T"] + 1, meta["D"]))
+        adam = {"ffvd_adam_step": ("plain", ()), "ffvd_adam_apply": ("plain", ()),        # name -> (engine, arguments in front of lr)
+                "ffvd_adam_step_allreduce": ("chains", (None, S)), "ffvd_tshard_adam_apply": ("time", (_lib.dptr(rows),))}
+        for name, (k, front) in adam.items():
+            for hyper in ((0.0, 0.9, 0.999, 1e-8), (1e-3, 1.0, 0.999, 1e-8)):          # lr = 0; beta1 = 1
+                h = engines[k]._h
+                assert getattr(lib, name)(h, *front, *hyper, _lib.TRAIN_ALL, *res) == _lib.FFVD_EINVAL, (name, hyper)
+                assert lib.ffvd_last_error(h).decode() == name + ": bad hyper-parameter"
+        znoise = np.zeros((meta["M"], meta["P"]))
+        with_z, without = _lib.FfvdParams(Z=znoise.ctypes.data), _lib.FfvdParams()
+        bit = _lib.TRAIN_BITS
+        sghmc = {"ffvd_sghmc_step": ("plain", ()), "ffvd_sghmc_apply": ("plain", ()),
+                 "ffvd_sghmc_step_allreduce": ("chains", (None, S)), "ffvd_tshard_sghmc_apply": ("time", ())}
+        for name, (k, front) in sghmc.items():
+            h = engines[k]._h
+            for mask, noise, text in ((bit["X"] | bit["Z"], with_z, ": X is never an SG-HMC variable (dgp_model.py:213-244)"),
+                                      (bit["Z"], without, ": a sampled array has no noise array")):
+                assert getattr(lib, name)(h, *front, 0.01, 0.05, mask, 1, ct.byref(noise), *res) == _lib.FFVD_EINVAL, (name, text)
+                assert lib.ffvd_last_error(h).decode() == name + text
+        for k, e in engines.items():
+            after = e.get_params()
+            for n in before[k]:
+                np.testing.assert_array_equal(after[n], before[k][n], err_msg=f"{k} {n}")
+    finally:
+        for sh in (chains, tshard):
+            if sh is not None:
+                sh.close()
+        plain.close()
+
+
 TRAIN_WORKER = r"""
 import os, sys
 sys.path.insert(0, os.environ["FFVD_ROOT"])
