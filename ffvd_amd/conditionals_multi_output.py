@@ -175,3 +175,91 @@ def conditional_after_kernel_precalculation(Lm_inverse_seq, Xnew, Z, kern, f, *,
                                          _lib.dptr(var))
     _lib.check(rc, None, "conditional_after_kernel_precalculation")
     return mean, var
+
+
+def pack_posterior_groups(Zs, kerns, Xs, control_inputs, Qs, who):
+    """The packed inputs of the grouped posterior operators (`ffvd_op_posterior_grouped`, `ffvd_op_posterior_rollout_grouped`), with
+    every shape checked before any device call.  `Zs` / `kerns`: one model (an (M, P) array and a list of D kernels: shared by all
+    groups) or a length-G sequence of them; `Xs`: G trajectories (T+1, D); `Qs`: G vectors (D,), or one for all groups;
+    control_inputs: rows [0, T) are used ((>= T, C); None or no columns when P = D)."""
+    G = len(Xs)
+    if G < 1:
+        raise ValueError(f"{who}: at least one group is needed")
+    one_model = len(kerns) > 0 and not isinstance(kerns[0], (list, tuple))
+    if one_model:
+        if np.ndim(Zs) != 2:
+            raise ValueError(f"{who}: Zs: one list of kernels goes with one (M, P) array, got an array of {np.ndim(Zs)} dimensions")
+        Zl, kl = [Zs], [kerns]
+    else:
+        Zl, kl = list(Zs), list(kerns)
+        if len(Zl) != len(kl):
+            raise ValueError(f"{who}: Zs: expected {len(kl)} models (one per kernel list), got {len(Zl)}")
+    n_models = len(kl)
+    if n_models not in (1, G):
+        raise ValueError(f"{who}: n_models: expected 1 or {G} (one per group of Xs), got {n_models}")
+    hy = [stack_hypers(k) for k in kl]
+    kind, D = hy[0][0], len(kl[0])
+    Z0 = np.asarray(Zl[0])
+    if Z0.ndim != 2:
+        raise ValueError(f"{who}: Zs[0]: expected (M, P), got {Z0.shape}")
+    M, P = Z0.shape
+    C = P - D
+    if C < 0:
+        raise ValueError(f"{who}: Zs: {P} input columns for {D} latent dims")
+    Z = np.empty((n_models, M, P))
+    logvar = np.empty((n_models, D))
+    loglen = None if hy[0][3] is None else np.empty((n_models, D, P))
+    for m in range(n_models):
+        if hy[m][0] != kind:
+            raise ValueError(f"{who}: kerns[{m}]: every group must use the same kernel type")
+        if len(kl[m]) != D:
+            raise ValueError(f"{who}: kerns[{m}]: expected {D} kernels (one per latent dim), got {len(kl[m])}")
+        Z[m] = _lib.as_f64(Zl[m], (M, P), f"Zs[{m}]")
+        logvar[m] = _lib.as_f64(hy[m][2], (D,), f"kerns[{m}] logvariance")
+        if loglen is not None:
+            loglen[m] = _lib.as_f64(hy[m][3], (D, P), f"kerns[{m}] loglengthscales")
+    X0 = np.asarray(Xs[0])
+    if X0.ndim != 2 or X0.shape[1] != D or X0.shape[0] < 2:
+        raise ValueError(f"{who}: Xs[0]: expected (T + 1, {D}) with T >= 1, got {X0.shape}")
+    T = X0.shape[0] - 1
+    X = np.empty((G, T + 1, D))
+    for g in range(G):
+        X[g] = _lib.as_f64(Xs[g], (T + 1, D), f"Xs[{g}]")
+    Qa = np.asarray(Qs, dtype=np.float64)
+    if Qa.shape == (D,):
+        Qa = np.broadcast_to(Qa, (G, D))
+    if Qa.shape != (G, D):
+        raise ValueError(f"{who}: Qs: expected {G} groups of ({D},), got {Qa.shape}")
+    log_Q = np.ascontiguousarray(np.log(Qa))
+    ctrl = None
+    if C > 0:
+        ci = _lib.as_f64(control_inputs)
+        if ci.ndim != 2 or ci.shape[1] != C or ci.shape[0] < T:
+            raise ValueError(f"{who}: control_inputs: need at least {T} rows of {C} columns")
+        ctrl = np.ascontiguousarray(ci[:T])
+    return dict(kind=kind, G=G, n_models=n_models, M=M, P=P, D=D, C=C, T=T, Z=Z, logvar=logvar, loglen=loglen, X=X, log_Q=log_Q,
+                ctrl=ctrl)
+
+
+def collapse_u_mean_grouped(Zs, kerns, Xs, control_inputs, Qs, *, jitter=JITTER, groups_per_pass=0, return_factors=True):
+    """kernel_pre_cal + collapse_u_mean_after_kernel_precalculation (conditionals_multi_output.py:124-169, :206-227, as
+    base_model.py:243-256 calls them) for G groups in one call (`ffvd_op_posterior_grouped`): one group per chain (`Zs`, `kerns` one
+    model) or per SG-HMC sample (length-G sequences).  Xs: G trajectories (T+1, D); X_combine of group g is [Xs[g][:T], control_inputs[:T]].
+    Returns (U_means (G, M, D), H_inv_sqrts (G, D, M, M), Lm_inverse (n_models, D, M, M)); with return_factors=False the two stacks
+    are neither packed nor downloaded and come back as None.  groups_per_pass: see include/ffvd_abi.h (0 = automatic)."""
+    who = "collapse_u_mean_grouped"
+    a = pack_posterior_groups(Zs, kerns, Xs, control_inputs, Qs, who)
+    if int(groups_per_pass) < 0:
+        raise ValueError(f"{who}: groups_per_pass must be 0 (automatic) or positive")
+    G, nm, M, D = a["G"], a["n_models"], a["M"], a["D"]
+    U = np.empty((G, M, D))
+    Hinv = np.empty((G, D, M, M)) if return_factors else None
+    Lm = np.empty((nm, D, M, M)) if return_factors else None
+    dp = _lib.dptr
+    rc = _lib.load().ffvd_op_posterior_grouped(a["kind"], G, nm, dp(a["Z"]), M, a["P"], D, dp(a["logvar"]),
+                                               None if a["loglen"] is None else dp(a["loglen"]), dp(a["X"]),
+                                               None if a["ctrl"] is None else dp(a["ctrl"]), a["C"], a["T"], dp(a["log_Q"]),
+                                               float(jitter), int(groups_per_pass), None if Lm is None else dp(Lm), dp(U),
+                                               None if Hinv is None else dp(Hinv))
+    _lib.check(rc, None, who)
+    return U, Hinv, Lm

@@ -6,6 +6,7 @@
 #include "optim.h"
 #include "step_bodies.h"
 #include "rollout_group.h"
+#include "posterior_group.h"
 
 #include <atomic>
 #include <chrono>
@@ -1192,5 +1193,245 @@ extern "C" int ffvd_op_pg_sweep(int kind, const double *Lm_inverse_seq, const do
         !sc.download(idx, didx, (size_t)steps * R * sizeof(int32_t)))
         return set_error(nullptr, FFVD_EDEVICE, "ffvd_op_pg_sweep: copying the results to the host failed");
     timer.lap("results to the host");
+    return FFVD_OK;
+}
+
+// ---- grouped collapsed posteriors (posterior_group.h) ---------------------------------------------------------------------------------
+// U_mean and L_H^-T of collapse_u_mean_after_kernel_precalculation (conditionals_multi_output.py:206-227, called at
+// base_model.py:243-256) for G groups over n_models (1 or G) sets of Z / hyper-parameters, with the K_uu factors of kernel_pre_cal
+// (:124-169) formed in the same call.  Everything between the small uploads and the results stays on the device.
+namespace {
+struct PgIn {
+    const char *who;
+    int kind, G, n_models, M, P, D, C, T, groups_per_pass;
+    const double *Zs, *logvar, *loglen, *Xs, *ctrl_fit, *log_Qs;
+    double jitter;
+};
+struct PgWork {
+    int Mp, nK;                    // M rounded up to 64; K_uu factorisations = n_models * D
+    double *Kuu;                   // [nK] slabs of 2 Mp x Mp: L, then L^-T
+    double *Xs, *log_Qs;           // the uploaded [G][T+1][D], [G][D]
+    double *U;                     // [G][M][D]
+    // optional targets, filled pass by pass
+    double *q0 = nullptr;          // [G][Mp16][Mp16]: L_H^-T of each group's d = 0 (upper triangle, zero padding)
+    int Mp16 = 0;
+    double *Hpack = nullptr;       // [G][D][M][M]: L_H^-T as ffvd_op_collapse_u_mean returns it
+};
+
+// scalar-argument checks shared by the two entry points (before any device call)
+bool pg_scalars_ok(int kind, int G, int n_models, int M, int P, int D, int C, int T, int groups_per_pass, double jitter) {
+    return (kind == FFVD_KERNEL_SE || kind == FFVD_KERNEL_LINEAR) && G >= 0 && M >= 1 && M <= 2048 && D >= 1 && C >= 0 && P == D + C &&
+           P <= MAXP && T >= 1 && groups_per_pass >= 0 && (n_models == 1 || n_models == G) && std::isfinite(jitter) &&
+           (long long)G * D <= (1LL << 24);                 // (units are counted in int)
+}
+
+// Uploads the inputs, enqueues the whole posterior (K_uu chain, projection, Gram, H chain, matvec, the pass's packing kernels) and
+// reads every factorisation flag in ONE download; nothing before that waits for the device.  A dataflow Cholesky launch that gave up
+// on a bounded wait: everything is enqueued once more from the inputs (still on the device) with the launch-per-column variant, as
+// potrf_with_stall_recovery does.  On FFVD_OK the stream is drained and w's arrays are final.
+int pg_posterior(Scratch &sc, const PgIn &in, PgWork &w) {
+    const int G = in.G, D = in.D, M = in.M, P = in.P, C = in.C, T = in.T, nm = in.n_models, kind = in.kind;
+    const int Mp = round_up(M, NB), Tp = round_up(T, STRIP), ng = (Mp + 511) / 512, nK = nm * D, GD = G * D;
+    const size_t kstride = (size_t)2 * Mp * Mp, hstride = (size_t)(2 * Mp + NB) * Mp, fstride = (size_t)Tp * Mp;
+    w.Mp = Mp; w.nK = nK;
+    int gpp = in.groups_per_pass > 0 ? in.groups_per_pass : pg_groups_per_pass(G, D, Tp, Mp);
+    if (gpp > G) gpp = G;
+    if ((long long)gpp * D > 32768) gpp = 32768 / D > 0 ? 32768 / D : 1;
+    const int upp = gpp * D;                                       // units per pass
+    const std::string who = in.who;
+
+    double *dZ = sc.upload(in.Zs, (size_t)nm * M * P), *dlv = sc.upload(in.logvar, nK);
+    double *dll = in.loglen ? sc.upload(in.loglen, (size_t)nK * P) : nullptr;
+    double *dctrl = C ? sc.upload(in.ctrl_fit, (size_t)T * C) : nullptr;
+    w.Xs = sc.upload(in.Xs, (size_t)G * (T + 1) * D);
+    w.log_Qs = sc.upload(in.log_Qs, GD);
+    double *variance = sc.alloc<double>(nK), *len = sc.alloc<double>((size_t)nK * P);
+    double *Zsc = sc.alloc<double>((size_t)nK * Mp * P), *zz = sc.alloc<double>((size_t)nK * Mp);
+    double *Xt = sc.alloc<double>((size_t)(T + 1) * GD);
+    w.Kuu = sc.alloc<double>((size_t)nK * kstride);
+    double *F = sc.alloc<double>((size_t)upp * fstride), *H = sc.alloc<double>((size_t)upp * hstride);
+    double *ubuf = sc.alloc<double>((size_t)upp * M);
+    w.U = sc.alloc<double>((size_t)GD * M);
+    const int kchunk = nK < 32768 ? nK : 32768;
+    double *dinvK = sc.alloc<double>(potrf_scratch_doubles(Mp, kchunk)), *dinvH = sc.alloc<double>(potrf_scratch_doubles(Mp, upp));
+    int32_t *info = sc.alloc<int32_t>((size_t)nK + GD);
+    if (!dZ || !dlv || (in.loglen && !dll) || (C && !dctrl) || !w.Xs || !w.log_Qs || !variance || !len || !Zsc || !zz || !Xt || !w.Kuu ||
+        !F || !H || !ubuf || !w.U || !dinvK || !dinvH || !info)
+        return set_error(nullptr, FFVD_ENOMEM, who + ": device allocation or upload failed");
+
+    std::vector<int32_t> hinfo((size_t)nK + GD, 0);
+    for (int attempt = 0;; ++attempt) {
+        {
+            CholOverrideGuard guard;            // reset on the error returns below as well
+            if (attempt == 1) guard.force_left();
+            OP_TRY(hipMemsetAsync(info, 0, ((size_t)nK + GD) * sizeof(int32_t), sc.stream));
+            // 1. hyper-parameters of every (model, dim): prep_hypers' arithmetic, one launch, in HyperView's layout
+            launch_rg_prep(sc.stream, kind, nm, D, M, Mp, P, dZ, dlv, dll, variance, len, Zsc, zz);
+            // 2. K_uu + jitter I -> L, L^-T (kernel_pre_cal, :124-169)
+            for (int k0 = 0; k0 < nK; k0 += kchunk) {
+                const int n = nK - k0 < kchunk ? nK - k0 : kchunk;
+                const HyperView hv{variance + k0, len + (size_t)k0 * P, Zsc + (size_t)k0 * Mp * P, zz + (size_t)k0 * Mp};
+                launch_kuu_build(sc.stream, kind, hv, M, Mp, P, n, in.jitter, w.Kuu + (size_t)k0 * kstride, nullptr);
+                launch_potrf_ext(sc.stream, w.Kuu + (size_t)k0 * kstride, Mp, Mp, Mp, n, kstride, info + k0, dinvK);
+            }
+            launch_pg_stage_x(sc.stream, w.Xs, G, T, D, Xt);
+            for (int g0 = 0; g0 < G; g0 += gpp) {
+                const int ngp = G - g0 < gpp ? G - g0 : gpp, nb = ngp * D, b0 = g0 * D;
+                // 3. F = K_fu L^-T (:212-213)
+                ProjectArgs pa{};
+                pa.kind = kind; pa.x_ld = D; pa.x_cols = D; pa.ctrl = dctrl; pa.T = T; pa.Tp = Tp; pa.C = C; pa.P = P; pa.M = M; pa.Mp = Mp;
+                pa.Dl = D; pa.d_begin = 0; pa.w_stride = kstride; pa.ng = ng;
+                if (nm == 1) {          // the ELBO's shape: chains s = b / D of one model
+                    pa.x = w.Xs; pa.x_chain_stride = (size_t)(T + 1) * D; pa.hv = HyperView{variance, len, Zsc, zz};
+                    pa.W = w.Kuu + (size_t)Mp * Mp; pa.b0 = b0; pa.nb = nb; pa.F = F;
+                    launch_project(sc.stream, pa);
+                } else {
+                    for (int gl = 0; gl < ngp; ++gl) {
+                        const size_t k0 = (size_t)(g0 + gl) * D;
+                        pa.x = w.Xs + (size_t)(g0 + gl) * (T + 1) * D; pa.x_chain_stride = 0;
+                        pa.hv = HyperView{variance + k0, len + k0 * P, Zsc + k0 * Mp * P, zz + k0 * Mp};
+                        pa.W = w.Kuu + k0 * kstride + (size_t)Mp * Mp; pa.b0 = 0; pa.nb = D; pa.F = F + (size_t)gl * D * fstride;
+                        launch_project(sc.stream, pa);
+                    }
+                }
+                // 4. H = I + F^T F / Q and b = F^T delta / Q (:214-217) into zeroed slabs with a device-set identity, then the chain
+                OP_TRY(hipMemsetAsync(H, 0, (size_t)nb * hstride * sizeof(double), sc.stream));
+                launch_set_identity(sc.stream, H, hstride, Mp, Mp, nb);
+                GramArgs ga{};
+                ga.mode = GRAM_F; ga.A = F; ga.a_stride = fstride; ga.rows = Tp; ga.with_row = 1; ga.brow = 2 * Mp;
+                ga.X = Xt; ga.log_Q = w.log_Qs; ga.T = T; ga.D = GD; ga.Mp = Mp; ga.Dl = GD; ga.d_begin = 0;      // one chain of G * D dims
+                ga.b0 = b0; ga.nb = nb; ga.yn_over_batch = 1.0; ga.H = H; ga.h_stride = hstride;
+                launch_gram(sc.stream, ga);
+                launch_potrf_ext(sc.stream, H, Mp, Mp + NB, Mp, nb, hstride, info + nK + b0, dinvH);
+                // 5. U_mean[:, d] = L_H^-T (L_H^-1 b) (:219)
+                launch_matvec(sc.stream, H + (size_t)Mp * Mp, hstride, H + (size_t)2 * Mp * Mp, hstride, Mp, ubuf, 1, M, M, nb);
+                launch_pg_unpack_u(sc.stream, ubuf, ngp, D, M, w.U + (size_t)g0 * M * D);
+                if (w.q0)               // slice d = 0 of each group
+                    launch_pg_pack(sc.stream, H, hstride, Mp, Mp, ngp, D, M, 1, w.q0 + (size_t)g0 * w.Mp16 * w.Mp16, w.Mp16, w.Mp16, ngp);
+                if (w.Hpack)            // Lm_inverse_dd_seq = L_H^-T (:222)
+                    launch_pg_pack(sc.stream, H, hstride, Mp, Mp, nb, 1, M, 0, w.Hpack + (size_t)b0 * M * M, M, M, nb);
+            }
+        }
+        OP_TRY(hipGetLastError());
+        OP_TRY(hipMemcpyAsync(hinfo.data(), info, hinfo.size() * sizeof(int32_t), hipMemcpyDeviceToHost, sc.stream));
+        if (hipStreamSynchronize(sc.stream) != hipSuccess)
+            return set_error(nullptr, FFVD_EDEVICE, who + ": device error while reading Cholesky status");
+        for (int k = 0; k < nK; ++k)
+            if (hinfo[k] > 0)
+                return set_error(nullptr, FFVD_ENOTPD, who + ": Cholesky of K_uu + jitter*I failed: group " + std::to_string(k / D) +
+                                                       ", latent dim " + std::to_string(k % D) + ", pivot " + std::to_string(hinfo[k] - 1) +
+                                                       " is not positive");
+        bool stalled = false;
+        for (int32_t f : hinfo) stalled = stalled || f < 0;
+        if (stalled) {
+            if (attempt == 1)
+                return set_error(nullptr, FFVD_EDEVICE, who + ": abandoned, a block row waited more than 1 s for the row above it");
+            continue;
+        }
+        for (int b = 0; b < GD; ++b)
+            if (hinfo[nK + b] > 0)
+                return set_error(nullptr, FFVD_ENOTPD, who + ": Cholesky of H failed: group " + std::to_string(b / D) + ", latent dim " +
+                                                       std::to_string(b % D) + ", pivot " + std::to_string(hinfo[nK + b] - 1) +
+                                                       " is not positive");
+        if (attempt == 1)
+            set_error(nullptr, FFVD_OK, "warning: " + who + ": the one-launch (dataflow) Cholesky gave up on a bounded wait; the posteriors "
+                                        "were formed again with the launch-per-column Cholesky and completed");
+        return FFVD_OK;
+    }
+}
+}  // namespace
+
+extern "C" int ffvd_op_posterior_grouped(int kind, int G, int n_models, const double *Zs, int M, int P, int D, const double *logvariances,
+                                         const double *loglengthscales, const double *Xs, const double *ctrl_fit, int C, int T,
+                                         const double *log_Qs, double jitter, int groups_per_pass, double *Lm_inverse, double *U_means,
+                                         double *H_inv_sqrts) {
+    const char *who = "ffvd_op_posterior_grouped", *bad = "ffvd_op_posterior_grouped: bad argument";
+    if (!pg_scalars_ok(kind, G, n_models, M, P, D, C, T, groups_per_pass, jitter)) return set_error(nullptr, FFVD_EINVAL, bad);
+    if (G == 0) return FFVD_OK;
+    if (!Zs || !logvariances || !Xs || !log_Qs || !U_means || (C > 0 && !ctrl_fit) || (kind == FFVD_KERNEL_SE && !loglengthscales))
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    OP_BEGIN("ffvd_op_posterior_grouped");
+    PgIn in{who, kind, G, n_models, M, P, D, C, T, groups_per_pass, Zs, logvariances, loglengthscales, Xs, ctrl_fit, log_Qs, jitter};
+    PgWork w{};
+    const size_t GD = (size_t)G * D, MM = (size_t)M * M, nK = (size_t)n_models * D;
+    if (H_inv_sqrts) { w.Hpack = sc.alloc<double>(GD * MM); OP_CHECK(w.Hpack, "ffvd_op_posterior_grouped"); }
+    double *Lpack = Lm_inverse ? sc.alloc<double>(nK * MM) : nullptr;
+    if (Lm_inverse) OP_CHECK(Lpack, "ffvd_op_posterior_grouped");
+    if (int rc = pg_posterior(sc, in, w)) return rc;
+    if (Lpack) launch_pg_pack(sc.stream, w.Kuu, (size_t)2 * w.Mp * w.Mp, w.Mp, w.Mp, (int)nK, 1, M, 0, Lpack, M, M, (int)nK);
+    OP_TRY(hipGetLastError());
+    if (!sc.download(U_means, w.U, GD * M * sizeof(double)) || (H_inv_sqrts && !sc.download(H_inv_sqrts, w.Hpack, GD * MM * sizeof(double))) ||
+        (Lpack && !sc.download(Lm_inverse, Lpack, nK * MM * sizeof(double))))
+        return set_error(nullptr, FFVD_EDEVICE, "ffvd_op_posterior_grouped: copying the results back failed");
+    return FFVD_OK;
+}
+
+// The posteriors above handed to the grouped rollout loop (base_model.py:243-314 per group) without leaving the device: W, q0, f and
+// x_last of RolloutGroupArgs are written by posterior_group.hip's kernels from the factorisation slabs, then launch_rg_prep /
+// launch_rg_wq / launch_rg_step run as in ffvd_op_rollout_grouped.
+extern "C" int ffvd_op_posterior_rollout_grouped(int kind, int G, int n_models, const double *Zs, int M, int P, int D,
+                                                 const double *logvariances, const double *loglengthscales, const double *Xs,
+                                                 const double *ctrl_fit, int C, int T, const double *log_Qs, double jitter,
+                                                 int groups_per_pass, int R, const double *ctrl_roll, int steps, const double *eps,
+                                                 double *predict_x, double *predict_var, double *U_means) {
+    const char *who = "ffvd_op_posterior_rollout_grouped", *bad = "ffvd_op_posterior_rollout_grouped: bad argument";
+    if (!pg_scalars_ok(kind, G, n_models, M, P, D, C, T, groups_per_pass, jitter) || R < 1 || steps < 0)
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    const int Mp16 = round_up(M, RG_SLAB), NS = Mp16 / RG_SLAB;
+    if ((long long)G * D * Mp16 * Mp16 > (1LL << 29) || (long long)G * R > (1LL << 20) || (R + RG_RC - 1) / RG_RC > 65535 ||
+        (long long)G * D * NS >= (1LL << 31))
+        return set_error(nullptr, FFVD_EINVAL, "ffvd_op_posterior_rollout_grouped: bad argument (beyond the limits of rollout_group.h)");
+    if (G == 0 || steps == 0) return FFVD_OK;
+    if (!Zs || !logvariances || !Xs || !log_Qs || !eps || !predict_x || !predict_var || (C > 0 && (!ctrl_fit || !ctrl_roll)) ||
+        (kind == FFVD_KERNEL_SE && !loglengthscales))
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    OP_BEGIN("ffvd_op_posterior_rollout_grouped");
+    LapTimer timer("FFVD_RG_TIMING", who, sc.stream);
+    PgIn in{who, kind, G, n_models, M, P, D, C, T, groups_per_pass, Zs, logvariances, loglengthscales, Xs, ctrl_fit, log_Qs, jitter};
+    PgWork w{};
+    const size_t GD = (size_t)G * D, mm16 = (size_t)Mp16 * Mp16, out_n = (size_t)G * R * steps * D;
+    w.Mp16 = Mp16;
+    w.q0 = sc.alloc<double>((size_t)G * mm16);
+    double *dW = sc.alloc<double>(GD * mm16), *dB = sc.alloc<double>(GD * mm16);
+    OP_CHECK(w.q0 && dW && dB, "ffvd_op_posterior_rollout_grouped");
+    if (int rc = pg_posterior(sc, in, w)) return rc;
+    timer.lap("posteriors");
+    // the rollout loop's own copy of the small inputs, one row per group (a shared model is repeated: launch_rg_step indexes by group)
+    const double *hZ = Zs, *hlv = logvariances, *hll = loglengthscales;
+    if (n_models == 1 && G > 1) {
+        std::vector<double> &rz = sc.host((size_t)G * M * P), &rv = sc.host(GD), &rl = sc.host(loglengthscales ? GD * P : 0);
+        for (int g = 0; g < G; ++g) {
+            memcpy(rz.data() + (size_t)g * M * P, Zs, (size_t)M * P * sizeof(double));
+            memcpy(rv.data() + (size_t)g * D, logvariances, D * sizeof(double));
+            if (loglengthscales) memcpy(rl.data() + (size_t)g * D * P, loglengthscales, (size_t)D * P * sizeof(double));
+        }
+        hZ = rz.data(); hlv = rv.data(); hll = loglengthscales ? rl.data() : nullptr;
+    }
+    double *dZ = sc.upload(hZ, (size_t)G * M * P), *dlv = sc.upload(hlv, GD), *dll = hll ? sc.upload(hll, GD * P) : nullptr;
+    double *deps = sc.upload(eps, (size_t)steps * G * R * D), *dctrl = C ? sc.upload(ctrl_roll, (size_t)steps * C) : nullptr;
+    double *dxl = sc.alloc<double>(GD);
+    double *variance = sc.alloc<double>(GD), *len = sc.alloc<double>(GD * P), *Zsc = sc.alloc<double>(GD * Mp16 * P), *zz = sc.alloc<double>(GD * Mp16);
+    double *part = sc.alloc<double>((size_t)2 * GD * NS * R * 4), *xbuf = sc.alloc<double>((size_t)2 * G * R * D);
+    double *dpx = sc.alloc<double>(out_n), *dpv = sc.alloc<double>(out_n);
+    OP_CHECK(dZ && dlv && (!hll || dll) && deps && (!C || dctrl) && dxl && variance && len && Zsc && zz && part && xbuf && dpx && dpv,
+             "ffvd_op_posterior_rollout_grouped");
+    // W[g][d] = L^-T of the group's model; with one model every group reads the same slab (the stack is still materialised)
+    launch_pg_pack(sc.stream, w.Kuu, (size_t)2 * w.Mp * w.Mp, w.Mp, w.Mp, w.nK, 1, M, 1, dW, Mp16, Mp16, (int)GD);
+    launch_pg_x_last(sc.stream, w.Xs, G, T, D, dxl);
+    launch_rg_prep(sc.stream, kind, G, D, M, Mp16, P, dZ, dlv, dll, variance, len, Zsc, zz);
+    launch_rg_wq(sc.stream, G, D, Mp16, 1, dW, w.q0, dB);
+    timer.lap("operands packed, W q_sqrt");
+    RolloutGroupArgs a{};
+    a.kind = kind; a.G = G; a.R = R; a.D = D; a.C = C; a.P = P; a.M = M; a.Mp = Mp16; a.NS = NS; a.steps = steps;
+    a.has_q = 1; a.q_upper = 1;          // q0's strict lower triangle was written as exact zeros
+    a.W = dW; a.B = dB; a.Zs = Zsc; a.zz = zz; a.variance = variance; a.len = len; a.f = w.U; a.x_last = dxl; a.log_Q = w.log_Qs;
+    a.ctrl = dctrl; a.eps = deps; a.part = part; a.xbuf = xbuf; a.predict_x = dpx; a.predict_var = dpv;
+    for (int t = 0; t <= steps; ++t) launch_rg_step(sc.stream, a, t);
+    OP_TRY(hipGetLastError());
+    timer.lap("step launches");
+    if (!sc.download(predict_x, dpx, out_n * sizeof(double)) || !sc.download(predict_var, dpv, out_n * sizeof(double)) ||
+        (U_means && !sc.download(U_means, w.U, GD * M * sizeof(double))))
+        return set_error(nullptr, FFVD_EDEVICE, "ffvd_op_posterior_rollout_grouped: copying the results back failed");
+    timer.lap("results downloaded");
     return FFVD_OK;
 }

@@ -37,7 +37,7 @@ class DGPSSM:
     Constructor arguments keep the reference's names (dgp_model.py:160-166).  `num_chains` > 1 evaluates
     S latent trajectories X_s in one call (`set_X`), which is what BASELINE.json's metric measures."""
 
-    ROLLOUT_MODES = ("reference", "intent", "intent-batched")      # collect_samples_formal(rollout_mode=...)
+    ROLLOUT_MODES = ("reference", "intent", "intent-batched", "intent-fused")      # collect_samples_formal(rollout_mode=...)
 
     def __init__(self, Y, x_dims, n_inducing, kernels, likelihood, minibatch_size=None, window_size=64,
                  output_dim=None, prior_type="uniform", full_cov=False, epsilon=0.01, mdecay=0.05, QQ_chol=None,
@@ -309,16 +309,20 @@ class DGPSSM:
           "intent"    -- rollout num_i uses the variables as they are after its own sample_ops (K_uu factors and
                          posterior U recomputed per sample), which is what the loop sets out to do;
           "intent-batched" -- the same sampler sequence and the same per-sample posteriors as "intent", with the `num` rollouts
-                         deferred into ONE `rollout_grouped` call (G = num posteriors, R = 1) after the last sample_op.
+                         deferred into ONE `rollout_grouped` call (G = num posteriors, R = 1) after the last sample_op;
+          "intent-fused" -- the sampler sequence and the recorded variables of "intent-batched"; per sample only Z, the kernels,
+                         chain 0's X and Q are kept, and after the last sample_op ONE `posterior_rollout_grouped` call (G = num,
+                         R = 1, one model per group) forms the `num` posteriors and their rollouts without the posteriors leaving
+                         the device.  Collapsed branch only: with explicit U it is "intent-batched".
         `eps` (test_len, num, D) injects the standard-normal draws of :306 (else numpy's default_rng(seed)); the
         SG-HMC noise comes from the model's generator (`seed()`).  Returns a dict and sets the reference's attributes
         (fit_x, predict_y, predict_y_var, fit_y, RMSE_val)."""
         from . import conditionals_multi_output as cmo
-        from .prediction import predict_y_summary, rollout, rollout_grouped
+        from .prediction import posterior_rollout_grouped, predict_y_summary, rollout, rollout_grouped
         if synthetic_data_function_plot:
             raise NotImplementedError("synthetic_data_function_plot: plotting aid of the kink toy problem, not on the GP-SSM path")
         if rollout_mode not in self.ROLLOUT_MODES:
-            raise ValueError("rollout_mode must be 'reference', 'intent' or 'intent-batched'")
+            raise ValueError("rollout_mode must be 'reference', 'intent', 'intent-batched' or 'intent-fused'")
         if sghmc_var_len and sghmc_var_len != len(self.vars):
             raise ValueError(f"sghmc_var_len = {sghmc_var_len} but the model samples {len(self.vars)} variables")
         if self._host_stale:
@@ -346,6 +350,7 @@ class DGPSSM:
         mc = [[] for _ in self.vars]
         px_parts, pv_parts = [], []
         groups = []                                                                             # "intent-batched": one posterior per sample
+        fused_groups = []                                                                       # "intent-fused": one model per sample
         if sghmc_var_len:
             for num_i in range(num):
                 for _ in range(spacing):                                                        # :225-231
@@ -361,7 +366,11 @@ class DGPSSM:
                                      eps[:, num_i:num_i + 1])
                     px_parts.append(px)
                     pv_parts.append(pv)
-                elif rollout_mode == "intent-batched":
+                elif rollout_mode == "intent-fused" and U_collapse:
+                    lay = self.layers[-1]
+                    fused_groups.append((np.array(lay.Z, copy=True), copy.deepcopy(lay.kernel), np.array(lay.X, copy=True),
+                                         np.array(self.Q, copy=True)))
+                elif rollout_mode in ("intent-batched", "intent-fused"):
                     Lm, U_val, U_chol = posterior()
                     lay = self.layers[-1]
                     groups.append((Lm, np.array(lay.Z, copy=True), copy.deepcopy(lay.kernel), U_val, U_chol,
@@ -372,6 +381,11 @@ class DGPSSM:
                                      test_len, cols[6], eps[:, :, None, :])
             px, pv = px[:, 0], pv[:, 0]
             U_val = U_val if U_collapse else self.layers[-1].U
+        elif fused_groups:
+            cols = list(zip(*fused_groups))
+            px, pv, U_all = posterior_rollout_grouped(cols[0], cols[1], cols[2], cols[3], ci, n_train, test_len, eps[:, :, None, :],
+                                                      return_U=True)
+            px, pv, U_val = px[:, 0], pv[:, 0], U_all[-1]
         elif px_parts:
             px, pv = np.concatenate(px_parts, axis=0), np.concatenate(pv_parts, axis=0)
             U_val = U_val if U_collapse else self.layers[-1].U
@@ -397,14 +411,18 @@ class DGPSSM:
         return out
 
     def collect_samples_chains(self, num_per_chain, control_inputs, test_len, *, Y_test=None, Y_train_std=1.0, Y_train=None,
-                               eps=None, seed=None):
+                               eps=None, seed=None, fused=False):
         """Rollouts from EVERY chain of a `num_chains = S` model (collect_samples_formal predicts from chain 0 only): the K_uu
         factors once, the collapsed posterior U | X_s per chain (with explicit U: the shared U, no q_sqrt), `num_per_chain`
         rollouts of `test_len` steps from each chain's own X_s[-1] -- one `rollout_grouped` call with G = S, R = num_per_chain.
         `eps` (test_len, S, num_per_chain, D) injects the draws of base_model.py:306 (else numpy's default_rng(seed)).
+        fused=True (collapsed U only; ValueError with explicit U: there is no posterior to build): the S posteriors and their rollouts
+        in ONE `posterior_rollout_grouped` call with the model shared by the groups -- the posteriors never leave the device.
         Returns a dict: predict_x, predict_x_var (S, num_per_chain, test_len, D) and the predict_y_summary over all S * R rollouts."""
         from . import conditionals_multi_output as cmo
-        from .prediction import predict_y_summary, rollout_grouped
+        from .prediction import posterior_rollout_grouped, predict_y_summary, rollout_grouped
+        if fused and not self.U_collapse:
+            raise ValueError("collect_samples_chains: fused=True builds the collapsed posterior; with explicit U there is none to build")
         if self._host_stale:
             self.pull_parameters()
         S, D, T, R = self.num_chains, self.output_dim, self.X_N - 1, int(num_per_chain)
@@ -418,6 +436,13 @@ class DGPSSM:
             raise ValueError(f"eps: expected {(test_len, S, R, D)}, got {eps.shape}")
         n_train = self.Y.shape[0] if Y_train is None else np.asarray(Y_train).shape[0]
         lay = self.layers[-1]
+        if fused:
+            px, pv, U_all = posterior_rollout_grouped(lay.Z, lay.kernel, [self._X_chains[s_] for s_ in range(S)], self.Q, ci, n_train,
+                                                      test_len, eps, return_U=True)
+            out = predict_y_summary(px.reshape(S * R, test_len, D), pv.reshape(S * R, test_len, D), self.likelihood.CC,
+                                    self.likelihood.DD, self.likelihood.log_Rchols, Y_test, Y_train_std)
+            out.update(predict_x=px, predict_x_var=pv, U_vals=[U_all[s_] for s_ in range(S)])
+            return out
         Lm = cmo.kernel_pre_cal(lay.Z, lay.kernel)
         U_vals, U_chols = [], []
         for s_ in range(S):

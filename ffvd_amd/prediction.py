@@ -11,6 +11,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _lib
+from .conditionals_multi_output import JITTER, pack_posterior_groups
 from .kernels import stack_hypers
 
 
@@ -126,6 +127,43 @@ def rollout_grouped(Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x_lasts, contro
                                              _lib.dptr(px), _lib.dptr(pv))
     _lib.check(rc, None, "ffvd_op_rollout_grouped")
     return px, pv
+
+
+def posterior_rollout_grouped(Zs, kerns, Xs, Qs, control_inputs, ctrl_offset, steps, eps, *, jitter=JITTER, groups_per_pass=0,
+                              return_U=False):
+    """The collapsed posterior of G groups and their rollouts in ONE call (`ffvd_op_posterior_rollout_grouped`): what
+    `conditionals_multi_output.collapse_u_mean_grouped` followed by `rollout_grouped` computes, without the posteriors leaving the
+    device.  `Zs` / `kerns`: one model (shared by the groups: one per chain) or length-G sequences (one per SG-HMC sample); Xs: G
+    trajectories (T+1, D), the rollouts of group g start at Xs[g][-1]; Qs: G vectors (D,) or one; rows [0, T) of control_inputs feed
+    the posterior, rows [ctrl_offset, ctrl_offset + steps) the rollouts; eps: (steps, G, R, D).
+    Returns predict_x, predict_x_var (G, R, steps, D) and, with return_U, U_means (G, M, D)."""
+    who = "posterior_rollout_grouped"
+    a = pack_posterior_groups(Zs, kerns, Xs, control_inputs, Qs, who)
+    G, nm, M, D, C = a["G"], a["n_models"], a["M"], a["D"], a["C"]
+    steps = int(steps)
+    if steps < 0 or int(ctrl_offset) < 0 or int(groups_per_pass) < 0:
+        raise ValueError(f"{who}: steps, ctrl_offset and groups_per_pass must not be negative")
+    eps = _lib.as_f64(eps)
+    if eps.ndim != 4 or eps.shape[0] != steps or eps.shape[1] != G or eps.shape[2] < 1 or eps.shape[3] != D:
+        raise ValueError(f"eps: expected ({steps}, {G}, R >= 1, {D}), got {eps.shape}")
+    R = eps.shape[2]
+    ctrl = None
+    if C > 0:
+        ci = _lib.as_f64(control_inputs)
+        if ci.shape[0] < ctrl_offset + steps:
+            raise ValueError(f"control_inputs: need at least {ctrl_offset + steps} rows of {C} columns")
+        ctrl = np.ascontiguousarray(ci[ctrl_offset: ctrl_offset + steps])
+    px, pv = np.empty((G, R, steps, D)), np.empty((G, R, steps, D))
+    U = np.empty((G, M, D)) if return_U else None
+    dp = _lib.dptr
+    rc = _lib.load().ffvd_op_posterior_rollout_grouped(a["kind"], G, nm, dp(a["Z"]), M, a["P"], D, dp(a["logvar"]),
+                                                       None if a["loglen"] is None else dp(a["loglen"]), dp(a["X"]),
+                                                       None if a["ctrl"] is None else dp(a["ctrl"]), C, a["T"], dp(a["log_Q"]),
+                                                       float(jitter), int(groups_per_pass), R,
+                                                       None if ctrl is None else dp(ctrl), steps, dp(eps), dp(px), dp(pv),
+                                                       None if U is None else dp(U))
+    _lib.check(rc, None, who)
+    return (px, pv, U) if return_U else (px, pv)
 
 
 def predict_y_summary(predict_x, predict_x_var, CC, DD, log_Rchols, Y_test=None, Y_train_std=1.0):

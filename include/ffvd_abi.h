@@ -481,6 +481,41 @@ int  ffvd_op_rollout_grouped(int kind, int G, const double *const *Lm_inverse_se
                              const double *const *q_sqrts, const double *x_lasts, int R, const double *ctrl, int C, int steps,
                              const double *log_Qs, const double *eps, double *predict_x, double *predict_var);
 
+/* The collapsed posterior of G groups in one call: per group what ffvd_op_kernel_pre_cal (conditionals_multi_output.py:124-169) and
+ * ffvd_op_collapse_u_mean (:206-227) compute one after the other, as base_model.py:243-256 calls them -- one group per chain of a
+ * trained model (n_models = 1: Z and the hyper-parameters are shared, so is W = L^-T) or per SG-HMC sample (n_models = G: every group
+ * has its own).  Units b = g * D + d run through the ELBO's batch launches; the K_uu slabs, the zeroed H slabs with their identity
+ * rows, F and L_H^-T never leave the device, and there is no host synchronisation before the factorisation flags are read (once).
+ * Packed, row-major, group outermost: Zs n_models x M x P; logvariances n_models x D; loglengthscales n_models x D x P (NULL for
+ * LinearK); Xs G x (T+1) x D; ctrl_fit T x C (NULL when C = 0), common to the groups; log_Qs G x D (log Q: :215 divides by exp of it).
+ * Outputs: U_means G x M x D; H_inv_sqrts G x D x M x M (L_H^-T, :222) or NULL; Lm_inverse n_models x D x M x M (L^-T) or NULL.
+ * groups_per_pass: F = K_fu L^-T takes D * Tp * Mp doubles per group (Tp, Mp: T, M rounded up to 64) and is reused between passes of
+ * that many groups; 0 = the largest count whose F is at most 2 GiB (at least 1), a function of the shapes alone.
+ * Determinism: two identical calls give bit-identical outputs (fixed summation orders, no atomics on results).  A group's posterior
+ * is NOT promised to be independent of G or groups_per_pass: the batch launches choose their shape from the number of units.
+ * Errors: a non-positive pivot gives FFVD_ENOTPD and ffvd_last_error names the group, the latent dim and the matrix (K_uu + jitter*I
+ * or H); a one-launch Cholesky that gave up on a bounded wait is re-run with the launch-per-column variant (a warning says so).  No
+ * output is written on failure.
+ * Limits: M <= 2048, P = D + C <= 32, T >= 1, n_models 1 or G; FFVD_EINVAL beyond them, before any device call.  G = 0: FFVD_OK,
+ * nothing is touched. */
+int  ffvd_op_posterior_grouped(int kind, int G, int n_models, const double *Zs, int M, int P, int D, const double *logvariances,
+                               const double *loglengthscales, const double *Xs, const double *ctrl_fit, int C, int T,
+                               const double *log_Qs, double jitter, int groups_per_pass, double *Lm_inverse, double *U_means,
+                               double *H_inv_sqrts);
+
+/* ffvd_op_posterior_grouped followed by ffvd_op_rollout_grouped (base_model.py:243-314 per group: posterior, then R rollouts of
+ * `steps` steps from the last row of the group's X) WITHOUT the posteriors leaving the device: W, the d = 0 slice of L_H^-T (it
+ * inflates every dim), f = U_mean and x_last are written into the rollout loop's operands by device kernels -- padding
+ * and strict lower triangles as exact zeros -- and the loop's own launches follow unchanged.  Only the inputs above, ctrl_roll
+ * steps x C (NULL when C = 0), eps steps x G x R x D and the results predict_x, predict_var = f_var + Q (G x R x steps x D) and,
+ * optionally, U_means (G x M x D) cross the host link.  The flags are read before the first step is enqueued; errors as above.
+ * Limits: those of ffvd_op_posterior_grouped and of ffvd_op_rollout_grouped.  G = 0 or steps = 0: FFVD_OK, nothing is touched. */
+int  ffvd_op_posterior_rollout_grouped(int kind, int G, int n_models, const double *Zs, int M, int P, int D,
+                                       const double *logvariances, const double *loglengthscales, const double *Xs,
+                                       const double *ctrl_fit, int C, int T, const double *log_Qs, double jitter,
+                                       int groups_per_pass, int R, const double *ctrl_roll, int steps, const double *eps,
+                                       double *predict_x, double *predict_var, double *U_means);
+
 /* One particle-Gibbs sweep over the latent trajectory: the INTENT of BaseModel.PG_for_X_speedup (base_model.py:78-138;
  * as written that op never updates X -- discarded TensorArray.write results (:115), an assign that is never run (:137) --
  * so there is no reference behaviour to match, see oracle/ffvd_pg_oracle.py).  n_free = PG_particles - 1 free particles
