@@ -263,3 +263,98 @@ def collapse_u_mean_grouped(Zs, kerns, Xs, control_inputs, Qs, *, jitter=JITTER,
                                                None if Hinv is None else dp(Hinv))
     _lib.check(rc, None, who)
     return U, Hinv, Lm
+
+
+Q_MODES = {"reference": 0, "intent": 1}
+
+
+def check_conditional_query(who, Xnew, P, q_mode, rows_per_pass, per_group, summary):
+    """Xnew as a contiguous (N, P) array and the q_mode code of the grouped conditionals, checked before any device call."""
+    if q_mode not in Q_MODES:
+        raise ValueError(f"{who}: q_mode: expected one of {sorted(Q_MODES)}, got {q_mode!r}")
+    if int(rows_per_pass) < 0:
+        raise ValueError(f"{who}: rows_per_pass must be 0 (automatic) or positive")
+    if not per_group and not summary:
+        raise ValueError(f"{who}: per_group=False and summary=False leave nothing to compute")
+    Xnew = _lib.as_f64(Xnew)
+    if Xnew.ndim != 2 or Xnew.shape[1] != P:
+        raise ValueError(f"{who}: Xnew: expected (N, {P}), got {Xnew.shape}")
+    return Xnew, Q_MODES[q_mode]
+
+
+def conditional_grouped(Lm_inverse_seqs, Zs, kerns, fs, q_sqrts, Xnew, *, q_mode="reference", per_group=True, summary=True,
+                        rows_per_pass=0):
+    """conditional_after_kernel_precalculation (conditionals_multi_output.py:306-387, white=True, full_cov=False) for G posteriors at
+    the same N inputs in one call (`ffvd_op_conditional_grouped`): the transition function f(x, c) of every chain or SG-HMC sample.
+
+    `Zs` / `kerns` / `Lm_inverse_seqs`: one model (an (M, P) array, a list of D kernels, D matrices L^-T: shared by the groups) or
+    length-G sequences of them; fs: G arrays (M, D), the whitened inducing outputs; q_sqrts: None (explicit U: no third variance
+    term) or G stacks (D, M, M); Xnew (N, P).  q_mode "reference": slice 0 of a group's stack inflates every dim (what
+    the reference and the rollouts do); "intent": slice d inflates dim d.
+    Returns (means, vars, mix_mean, mix_var): (G, N, D) per group (None unless per_group) and the equal-weight mixture over the
+    groups, (N, D): mix_mean = mean_g(mean), mix_var = mean_g(var + mean^2) - mix_mean^2 (None unless summary).
+    rows_per_pass: see include/ffvd_abi.h (0 = automatic)."""
+    who = "conditional_grouped"
+    G = len(fs)
+    if G < 1:
+        raise ValueError(f"{who}: at least one group is needed")
+    one_model = len(kerns) > 0 and not isinstance(kerns[0], (list, tuple))
+    if one_model:
+        if np.ndim(Zs) != 2:
+            raise ValueError(f"{who}: Zs: one list of kernels goes with one (M, P) array, got an array of {np.ndim(Zs)} dimensions")
+        Zl, kl, Wl = [Zs], [kerns], [Lm_inverse_seqs]
+    else:
+        Zl, kl, Wl = list(Zs), list(kerns), list(Lm_inverse_seqs)
+        if len(Zl) != len(kl) or len(Wl) != len(kl):
+            raise ValueError(f"{who}: expected {len(kl)} models (one per kernel list), got {len(Zl)} Zs and {len(Wl)} Lm_inverse_seqs")
+    nm = len(kl)
+    if nm not in (1, G):
+        raise ValueError(f"{who}: n_models: expected 1 or {G} (one per group of fs), got {nm}")
+    hy = [stack_hypers(k) for k in kl]
+    kind, D = hy[0][0], len(kl[0])
+    Z0 = np.asarray(Zl[0])
+    if Z0.ndim != 2:
+        raise ValueError(f"{who}: Zs[0]: expected (M, P), got {Z0.shape}")
+    M, P = Z0.shape
+    if P < D:
+        raise ValueError(f"{who}: Zs: {P} input columns for {D} latent dims")
+    Xnew, qm = check_conditional_query(who, Xnew, P, q_mode, rows_per_pass, per_group, summary)
+    N = Xnew.shape[0]
+    Z, logvar = np.empty((nm, M, P)), np.empty((nm, D))
+    loglen = None if hy[0][3] is None else np.empty((nm, D, P))
+    Wm, qmats = [], []                                   # (keeps the matrices alive until the call returns)
+    for m in range(nm):
+        if hy[m][0] != kind:
+            raise ValueError(f"{who}: kerns[{m}]: every group must use the same kernel type")
+        if len(kl[m]) != D:
+            raise ValueError(f"{who}: kerns[{m}]: expected {D} kernels (one per latent dim), got {len(kl[m])}")
+        Z[m] = _lib.as_f64(Zl[m], (M, P), f"Zs[{m}]")
+        logvar[m] = _lib.as_f64(hy[m][2], (D,), f"kerns[{m}] logvariance")
+        if loglen is not None:
+            loglen[m] = _lib.as_f64(hy[m][3], (D, P), f"kerns[{m}] loglengthscales")
+        if len(Wl[m]) != D:
+            raise ValueError(f"{who}: Lm_inverse_seqs[{m}]: expected {D} matrices, got {len(Wl[m])}")
+        for d in range(D):
+            Wm.append(_lib.as_f64(Wl[m][d], (M, M), f"Lm_inverse_seqs[{m}][{d}]"))
+    f = np.empty((G, M, D))
+    for g in range(G):
+        f[g] = _lib.as_f64(fs[g], (M, D), f"fs[{g}]")
+    if q_sqrts is not None:
+        if len(q_sqrts) != G:
+            raise ValueError(f"{who}: q_sqrts: expected None or {G} groups, got {len(q_sqrts)}")
+        for g in range(G):
+            q = np.asarray(q_sqrts[g], dtype=np.float64)
+            if q.shape != (D, M, M):
+                raise ValueError(f"{who}: q_sqrts[{g}]: expected ({D}, {M}, {M}), got {q.shape}")
+            qmats.extend(np.ascontiguousarray(q[d]) for d in (range(D) if qm else (0,)))
+    import ctypes
+    Wt = (ctypes.c_void_p * len(Wm))(*[w.ctypes.data for w in Wm])
+    qt = (ctypes.c_void_p * len(qmats))(*[q.ctypes.data for q in qmats]) if q_sqrts is not None else None
+    means, vars_ = (np.empty((G, N, D)), np.empty((G, N, D))) if per_group else (None, None)
+    mm, mv = (np.empty((N, D)), np.empty((N, D))) if summary else (None, None)
+    dp = _lib.dptr
+    opt = lambda a: None if a is None else dp(a)
+    rc = _lib.load().ffvd_op_conditional_grouped(kind, G, nm, Wt, dp(Z), M, P, D, dp(logvar), opt(loglen), dp(f), qt, qm, dp(Xnew), N,
+                                                 int(rows_per_pass), opt(means), opt(vars_), opt(mm), opt(mv))
+    _lib.check(rc, None, who)
+    return means, vars_, mm, mv

@@ -7,6 +7,7 @@
 #include "step_bodies.h"
 #include "rollout_group.h"
 #include "posterior_group.h"
+#include "conditional_group.h"
 
 #include <atomic>
 #include <chrono>
@@ -228,6 +229,22 @@ static double *upload_stack(Scratch &sc, const double *src, int D, int M, int Mp
     if (M == Mp) return sc.upload(src, (size_t)D * M * M);
     std::vector<double> &pad = pad_identity(sc, src, D, M, Mp);
     return sc.upload(pad.data(), pad.size());
+}
+
+// n M x M matrices given as a table of host pointers -> a device stack of Mp x Mp slots.  The matrices are NOT packed on the host:
+// each goes from where the caller keeps it straight into its slot (a pitched copy when M != Mp; the padding is zeroed on the device).
+static double *upload_matrix_table(Scratch &sc, const double *const *src, size_t n, int M, int Mp) {
+    double *dst = sc.alloc<double>(n * Mp * Mp);
+    if (!dst) return nullptr;
+    if (Mp != M && hipMemsetAsync(dst, 0, n * Mp * Mp * sizeof(double), sc.stream) != hipSuccess) return nullptr;
+    for (size_t b = 0; b < n; ++b) {
+        const hipError_t e = (Mp == M)
+            ? hipMemcpyAsync(dst + b * Mp * Mp, src[b], (size_t)M * M * sizeof(double), hipMemcpyHostToDevice, sc.stream)
+            : hipMemcpy2DAsync(dst + b * Mp * Mp, (size_t)Mp * sizeof(double), src[b], (size_t)M * sizeof(double),
+                               (size_t)M * sizeof(double), M, hipMemcpyHostToDevice, sc.stream);
+        if (e != hipSuccess) return nullptr;
+    }
+    return dst;
 }
 
 // FFVD_ENOTPD for matrix d of a batch whose Cholesky flag (1 + first bad pivot) is set
@@ -1060,22 +1077,7 @@ extern "C" int ffvd_op_rollout_grouped(int kind, int G, const double *const *Lm_
         for (int g = 0; g < G; ++g) if (!q_sqrts[g]) return set_error(nullptr, FFVD_EINVAL, bad);
     OP_BEGIN("ffvd_op_rollout_grouped");
     LapTimer timer("FFVD_RG_TIMING", "ffvd_op_rollout_grouped", sc.stream);
-    // The big operands are NOT packed on the host: every M x M matrix goes from where the caller keeps it straight into its slot of the
-    // padded device stack (a pitched copy when M is not a multiple of 16; the padding is zeroed on the device).
-    auto upload_matrices = [&](const double *const *src, size_t n) -> double * {
-        double *dst = sc.alloc<double>(n * Mp * Mp);
-        if (!dst) return nullptr;
-        if (Mp != M && hipMemsetAsync(dst, 0, n * Mp * Mp * sizeof(double), sc.stream) != hipSuccess) return nullptr;
-        for (size_t b = 0; b < n; ++b) {
-            const hipError_t e = (Mp == M)
-                ? hipMemcpyAsync(dst + b * Mp * Mp, src[b], (size_t)M * M * sizeof(double), hipMemcpyHostToDevice, sc.stream)
-                : hipMemcpy2DAsync(dst + b * Mp * Mp, (size_t)Mp * sizeof(double), src[b], (size_t)M * sizeof(double),
-                                   (size_t)M * sizeof(double), M, hipMemcpyHostToDevice, sc.stream);
-            if (e != hipSuccess) return nullptr;
-        }
-        return dst;
-    };
-    double *dW = upload_matrices(Lm_inverse_seqs, GD);
+    double *dW = upload_matrix_table(sc, Lm_inverse_seqs, GD, M, Mp);
     timer.lap("W uploaded");
     // W q_sqrt is upper triangular when every group's q_sqrt slice is (the reference hands over L_H^-T): the step products then stop at
     // a slab's last row for both right-hand sides.  Otherwise they walk all rows; for a group whose slice IS upper triangular the extra
@@ -1083,7 +1085,7 @@ extern "C" int ffvd_op_rollout_grouped(int kind, int G, const double *const *Lm_
     int q_upper = q_sqrts ? 1 : 0;
     for (int g = 0; q_upper && g < G; ++g) q_upper = q_sqrt_is_upper(q_sqrts[g], M) ? 1 : 0;
     timer.lap("q_sqrt scanned");
-    double *dq = q_sqrts ? upload_matrices(q_sqrts, (size_t)G) : nullptr;
+    double *dq = q_sqrts ? upload_matrix_table(sc, q_sqrts, (size_t)G, M, Mp) : nullptr;
     double *dB = q_sqrts ? sc.alloc<double>(GD * Mp * Mp) : nullptr;
     double *dZ = sc.upload(Zs, (size_t)G * M * P), *dU = sc.upload(fs, (size_t)G * M * D), *dxl = sc.upload(x_lasts, GD);
     double *dlv = sc.upload(logvariances, GD), *dll = loglengthscales ? sc.upload(loglengthscales, GD * P) : nullptr;
@@ -1216,6 +1218,8 @@ struct PgWork {
     double *q0 = nullptr;          // [G][Mp16][Mp16]: L_H^-T of each group's d = 0 (upper triangle, zero padding)
     int Mp16 = 0;
     double *Hpack = nullptr;       // [G][D][M][M]: L_H^-T as ffvd_op_collapse_u_mean returns it
+    double *qall = nullptr;        // [G][D][Mp][Mp]: L_H^-T of every (group, dim) (upper triangle, zero padding)
+    HyperView hv{};                // [nK] device hyper-parameters (launch_rg_prep), left for what follows the posteriors
 };
 
 // scalar-argument checks shared by the two entry points (before any device call)
@@ -1249,6 +1253,7 @@ int pg_posterior(Scratch &sc, const PgIn &in, PgWork &w) {
     double *Zsc = sc.alloc<double>((size_t)nK * Mp * P), *zz = sc.alloc<double>((size_t)nK * Mp);
     double *Xt = sc.alloc<double>((size_t)(T + 1) * GD);
     w.Kuu = sc.alloc<double>((size_t)nK * kstride);
+    w.hv = HyperView{variance, len, Zsc, zz};
     double *F = sc.alloc<double>((size_t)upp * fstride), *H = sc.alloc<double>((size_t)upp * hstride);
     double *ubuf = sc.alloc<double>((size_t)upp * M);
     w.U = sc.alloc<double>((size_t)GD * M);
@@ -1308,6 +1313,8 @@ int pg_posterior(Scratch &sc, const PgIn &in, PgWork &w) {
                 launch_pg_unpack_u(sc.stream, ubuf, ngp, D, M, w.U + (size_t)g0 * M * D);
                 if (w.q0)               // slice d = 0 of each group
                     launch_pg_pack(sc.stream, H, hstride, Mp, Mp, ngp, D, M, 1, w.q0 + (size_t)g0 * w.Mp16 * w.Mp16, w.Mp16, w.Mp16, ngp);
+                if (w.qall)             // every slice (q_mode "intent" of the grouped conditionals)
+                    launch_pg_pack(sc.stream, H, hstride, Mp, Mp, nb, 1, M, 1, w.qall + (size_t)b0 * Mp * Mp, Mp, Mp, nb);
                 if (w.Hpack)            // Lm_inverse_dd_seq = L_H^-T (:222)
                     launch_pg_pack(sc.stream, H, hstride, Mp, Mp, nb, 1, M, 0, w.Hpack + (size_t)b0 * M * M, M, M, nb);
             }
@@ -1433,5 +1440,118 @@ extern "C" int ffvd_op_posterior_rollout_grouped(int kind, int G, int n_models, 
         (U_means && !sc.download(U_means, w.U, GD * M * sizeof(double))))
         return set_error(nullptr, FFVD_EDEVICE, "ffvd_op_posterior_rollout_grouped: copying the results back failed");
     timer.lap("results downloaded");
+    return FFVD_OK;
+}
+
+// ---- grouped GP conditionals (conditional_group.h) ------------------------------------------------------------------------------------
+// conditional_after_kernel_precalculation (conditionals_multi_output.py:306-387, white=True, full_cov=False) for G posteriors at N
+// common inputs: F = K(Xnew, Z) L^-T (:349) once per (model, dim), mean = F U_g (:365), var = Kdiag - sum F^2 (:356) + sum (F q)^2
+// (:369-380), and the equal-weight mixture over the groups.
+namespace {
+struct CgOut { double *means, *vars, *mix_mean, *mix_var; };
+
+// scalar-argument checks shared by the two entry points (before any device call); C = P - D
+bool cg_scalars_ok(int kind, int G, int n_models, int M, int P, int D, int N, int q_mode, int rows_per_pass) {
+    if (!((kind == FFVD_KERNEL_SE || kind == FFVD_KERNEL_LINEAR) && G >= 0 && M >= 1 && M <= 2048 && D >= 1 && P >= D && P <= MAXP &&
+          N >= 0 && (q_mode == 0 || q_mode == 1) && rows_per_pass >= 0 && (n_models == 1 || n_models == G) &&
+          (long long)G * D <= (1LL << 24)))
+        return false;
+    const long long Mp = round_up(M, NB);
+    return (long long)G * D * Mp * Mp <= (1LL << 29) && (long long)G * D * N < (1LL << 31);
+}
+bool cg_outputs_ok(const CgOut &o) { return (o.means || o.vars || o.mix_mean) && (!o.mix_mean == !o.mix_var); }
+
+// The launches of conditional_group.h on operands that are already on the device, then the requested outputs come down.
+int cg_run(Scratch &sc, const std::string &who, int kind, int G, int nm, int M, int P, int D, int N, int rows_per_pass, const HyperView &hv,
+           const double *W, size_t w_stride, const double *dU, const double *dq, int q_per_dim, int q_upper, const double *dX,
+           const CgOut &o) {
+    const int Mp = round_up(M, NB);
+    const size_t out_n = (size_t)G * N * D, ND = (size_t)N * D;
+    CondGroupArgs a{};
+    a.kind = kind; a.G = G; a.n_models = nm; a.M = M; a.Mp = Mp; a.P = P; a.D = D; a.N = N;
+    a.rows_per_pass = rows_per_pass > 0 ? rows_per_pass : cg_rows_per_pass(nm, D, Mp);
+    a.hv = hv; a.W = W; a.w_stride = w_stride; a.U = dU; a.q = dq; a.q_per_dim = q_per_dim; a.q_upper = q_upper; a.x = dX;
+    a.need_var = (o.vars || o.mix_var) ? 1 : 0;
+    const CondGroupScratch need = cg_scratch_doubles(G, nm, D, Mp, N, a.rows_per_pass, a.need_var && dq);
+    a.F = sc.alloc<double>(need.F); a.rowsq = sc.alloc<double>(need.rowsq); a.Ut = sc.alloc<double>(need.Ut); a.mbuf = sc.alloc<double>(need.mbuf);
+    a.part = need.part ? sc.alloc<double>(need.part) : nullptr;
+    a.mean = sc.alloc<double>(out_n);
+    a.var = a.need_var ? sc.alloc<double>(out_n) : nullptr;
+    double *dmm = o.mix_mean ? sc.alloc<double>(ND) : nullptr, *dmv = o.mix_mean ? sc.alloc<double>(ND) : nullptr;
+    if (!a.F || !a.rowsq || !a.Ut || !a.mbuf || (need.part && !a.part) || !a.mean || (a.need_var && !a.var) || (o.mix_mean && (!dmm || !dmv)))
+        return set_error(nullptr, FFVD_ENOMEM, who + ": device allocation or upload failed");
+    launch_conditional_group(sc.stream, a);
+    if (o.mix_mean) launch_cg_mixture(sc.stream, a.mean, a.var, G, ND, dmm, dmv);
+    OP_TRY(hipGetLastError());
+    if ((o.means && !sc.download(o.means, a.mean, out_n * sizeof(double))) || (o.vars && !sc.download(o.vars, a.var, out_n * sizeof(double))) ||
+        (o.mix_mean && (!sc.download(o.mix_mean, dmm, ND * sizeof(double)) || !sc.download(o.mix_var, dmv, ND * sizeof(double)))))
+        return set_error(nullptr, FFVD_EDEVICE, who + ": copying the results back failed");
+    OP_TRY(hipStreamSynchronize(sc.stream));
+    return FFVD_OK;
+}
+}  // namespace
+
+// Posteriors given by the caller (also explicit-U models and SG-HMC samples of U: q_sqrts = NULL)
+extern "C" int ffvd_op_conditional_grouped(int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M, int P,
+                                           int D, const double *logvariances, const double *loglengthscales, const double *fs,
+                                           const double *const *q_sqrts, int q_mode, const double *Xnew, int N, int rows_per_pass,
+                                           double *means, double *vars, double *mix_mean, double *mix_var) {
+    const char *who = "ffvd_op_conditional_grouped", *bad = "ffvd_op_conditional_grouped: bad argument";
+    if (!cg_scalars_ok(kind, G, n_models, M, P, D, N, q_mode, rows_per_pass)) return set_error(nullptr, FFVD_EINVAL, bad);
+    if (G == 0 || N == 0) return FFVD_OK;
+    const CgOut out{means, vars, mix_mean, mix_var};
+    if (!Lm_inverse_seqs || !Zs || !logvariances || !fs || !Xnew || !cg_outputs_ok(out) || (kind == FFVD_KERNEL_SE && !loglengthscales))
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    const size_t nK = (size_t)n_models * D, GD = (size_t)G * D, nq = q_sqrts ? (q_mode ? GD : (size_t)G) : 0;
+    for (size_t b = 0; b < nK; ++b) if (!Lm_inverse_seqs[b]) return set_error(nullptr, FFVD_EINVAL, bad);
+    for (size_t b = 0; b < nq; ++b) if (!q_sqrts[b]) return set_error(nullptr, FFVD_EINVAL, bad);
+    OP_BEGIN("ffvd_op_conditional_grouped");
+    const int Mp = round_up(M, NB);
+    // the triangular k cut needs EVERY slice upper triangular (the reference hands over L_H^-T); a dense slice takes the full range
+    int q_upper = nq ? 1 : 0;
+    for (size_t b = 0; q_upper && b < nq; ++b) q_upper = q_sqrt_is_upper(q_sqrts[b], M) ? 1 : 0;
+    double *dW = upload_matrix_table(sc, Lm_inverse_seqs, nK, M, Mp), *dq = nq ? upload_matrix_table(sc, q_sqrts, nq, M, Mp) : nullptr;
+    double *dZ = sc.upload(Zs, (size_t)n_models * M * P), *dU = sc.upload(fs, GD * M), *dX = sc.upload(Xnew, (size_t)N * P);
+    double *dlv = sc.upload(logvariances, nK), *dll = loglengthscales ? sc.upload(loglengthscales, nK * P) : nullptr;
+    double *variance = sc.alloc<double>(nK), *len = sc.alloc<double>(nK * P), *Zsc = sc.alloc<double>(nK * Mp * P), *zz = sc.alloc<double>(nK * Mp);
+    OP_CHECK(dW && (!nq || dq) && dZ && dU && dX && dlv && (!loglengthscales || dll) && variance && len && Zsc && zz, "ffvd_op_conditional_grouped");
+    launch_rg_prep(sc.stream, kind, n_models, D, M, Mp, P, dZ, dlv, dll, variance, len, Zsc, zz);
+    return cg_run(sc, who, kind, G, n_models, M, P, D, N, rows_per_pass, HyperView{variance, len, Zsc, zz}, dW, (size_t)Mp * Mp, dU, dq,
+                  q_mode, q_upper, dX, out);
+}
+
+// The collapsed posteriors of ffvd_op_posterior_grouped (base_model.py:243-256) evaluated at Xnew without leaving the device: L^-T is
+// read in the K_uu slabs, U_mean where the matvec left it, the q slices are packed by launch_pg_pack (exact zeros in the padding and
+// the strict lower triangle, so the k cut holds by construction).
+extern "C" int ffvd_op_posterior_conditional_grouped(int kind, int G, int n_models, const double *Zs, int M, int P, int D,
+                                                     const double *logvariances, const double *loglengthscales, const double *Xs,
+                                                     const double *ctrl_fit, int C, int T, const double *log_Qs, double jitter,
+                                                     int groups_per_pass, int q_mode, const double *Xnew, int N, int rows_per_pass,
+                                                     double *means, double *vars, double *mix_mean, double *mix_var, double *U_means) {
+    const char *who = "ffvd_op_posterior_conditional_grouped", *bad = "ffvd_op_posterior_conditional_grouped: bad argument";
+    if (!pg_scalars_ok(kind, G, n_models, M, P, D, C, T, groups_per_pass, jitter) ||
+        !cg_scalars_ok(kind, G, n_models, M, P, D, N, q_mode, rows_per_pass))
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    if (G == 0 || N == 0) return FFVD_OK;
+    const CgOut out{means, vars, mix_mean, mix_var};
+    if (!Zs || !logvariances || !Xs || !log_Qs || !Xnew || !cg_outputs_ok(out) || (C > 0 && !ctrl_fit) ||
+        (kind == FFVD_KERNEL_SE && !loglengthscales))
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    OP_BEGIN("ffvd_op_posterior_conditional_grouped");
+    PgIn in{who, kind, G, n_models, M, P, D, C, T, groups_per_pass, Zs, logvariances, loglengthscales, Xs, ctrl_fit, log_Qs, jitter};
+    PgWork w{};
+    const int Mp = round_up(M, NB);
+    const size_t GD = (size_t)G * D, mm = (size_t)Mp * Mp;
+    const bool need_q = vars || mix_var;
+    if (need_q && q_mode) w.qall = sc.alloc<double>(GD * mm);
+    else if (need_q) { w.Mp16 = Mp; w.q0 = sc.alloc<double>((size_t)G * mm); }
+    double *dX = sc.upload(Xnew, (size_t)N * P);
+    OP_CHECK(dX && (!need_q || w.qall || w.q0), "ffvd_op_posterior_conditional_grouped");
+    if (int rc = pg_posterior(sc, in, w)) return rc;
+    if (int rc = cg_run(sc, who, kind, G, n_models, M, P, D, N, rows_per_pass, w.hv, w.Kuu + mm, 2 * mm, w.U, q_mode ? w.qall : w.q0, q_mode, 1,
+                        dX, out))
+        return rc;
+    if (U_means && !sc.download(U_means, w.U, GD * M * sizeof(double)))
+        return set_error(nullptr, FFVD_EDEVICE, "ffvd_op_posterior_conditional_grouped: copying the results back failed");
     return FFVD_OK;
 }

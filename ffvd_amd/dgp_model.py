@@ -460,3 +460,31 @@ class DGPSSM:
                                 self.likelihood.DD, self.likelihood.log_Rchols, Y_test, Y_train_std)
         out.update(predict_x=px, predict_x_var=pv, U_vals=U_vals)
         return out
+
+    def predict_transition(self, Xnew, *, q_mode="reference", per_chain=True):
+        """The learned transition function at inputs of the caller's choice: mean and variance of the posterior GP increment
+        f(x, c) at the rows of Xnew (N, D + C) -- the f_mu and f_var a rollout adds at every step (x_next = x + f_mu +
+        eps sqrt(f_var + Q), base_model.py:304-314).  This is f itself: NOT x_next (add x, and Q to the variance, for that) and
+        NOT y (the emission C x + d with its noise is not applied).
+        Collapsed U: the S = num_chains posteriors U | X_s in one fused `posterior_conditional_grouped` call (G = S, one model);
+        q_mode "reference" inflates every dim with slice 0 of L_H^-T as the reference and the rollouts do, "intent"
+        dim d with slice d.  Explicit U: f does not depend on the chain, so one group is evaluated (no q_sqrt term) and `mean` /
+        `var` have a leading axis of 1.  Parameters newer on the device than on the host are pulled first.
+        Returns a dict: mean, var (S or 1, N, D; None unless per_chain), mix_mean, mix_var (N, D): the equal-weight mixture over
+        the chains."""
+        from . import conditionals_multi_output as cmo
+        from .prediction import posterior_conditional_grouped
+        if q_mode not in cmo.Q_MODES:
+            raise ValueError(f"predict_transition: q_mode: expected one of {sorted(cmo.Q_MODES)}, got {q_mode!r}")
+        if self._host_stale:
+            self.pull_parameters()
+        lay = self.layers[-1]
+        if self.U_collapse:
+            S = self.num_chains
+            mean, var, mm, mv = posterior_conditional_grouped(lay.Z, lay.kernel, [self._X_chains[s_] for s_ in range(S)], self.Q,
+                                                              self.control_inputs, Xnew, q_mode=q_mode, per_group=bool(per_chain))
+        else:
+            Lm = cmo.kernel_pre_cal(lay.Z, lay.kernel)
+            mean, var, mm, mv = cmo.conditional_grouped(Lm, lay.Z, lay.kernel, [lay.U], None, Xnew, q_mode=q_mode,
+                                                        per_group=bool(per_chain))
+        return dict(mean=mean, var=var, mix_mean=mm, mix_var=mv)

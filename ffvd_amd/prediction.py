@@ -11,7 +11,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _lib
-from .conditionals_multi_output import JITTER, pack_posterior_groups
+from .conditionals_multi_output import JITTER, check_conditional_query, pack_posterior_groups
 from .kernels import stack_hypers
 
 
@@ -164,6 +164,33 @@ def posterior_rollout_grouped(Zs, kerns, Xs, Qs, control_inputs, ctrl_offset, st
                                                        None if U is None else dp(U))
     _lib.check(rc, None, who)
     return (px, pv, U) if return_U else (px, pv)
+
+
+def posterior_conditional_grouped(Zs, kerns, Xs, Qs, control_inputs, Xnew, *, q_mode="reference", jitter=JITTER, groups_per_pass=0,
+                                  rows_per_pass=0, per_group=True, summary=True, return_U=False):
+    """The collapsed posterior of G groups and its transition function f(x, c) at Xnew (N, P) in ONE call
+    (`ffvd_op_posterior_conditional_grouped`): what `conditionals_multi_output.collapse_u_mean_grouped` followed by
+    `conditional_grouped` computes, without the posteriors leaving the device.  `Zs` / `kerns` / `Xs` / `Qs` / `control_inputs`: as
+    `posterior_rollout_grouped`; q_mode, per_group, summary, rows_per_pass: as `conditional_grouped`.
+    Returns (means, vars, mix_mean, mix_var) and, with return_U, U_means (G, M, D)."""
+    who = "posterior_conditional_grouped"
+    a = pack_posterior_groups(Zs, kerns, Xs, control_inputs, Qs, who)
+    G, nm, M, D = a["G"], a["n_models"], a["M"], a["D"]
+    if int(groups_per_pass) < 0:
+        raise ValueError(f"{who}: groups_per_pass must be 0 (automatic) or positive")
+    Xnew, qm = check_conditional_query(who, Xnew, a["P"], q_mode, rows_per_pass, per_group, summary)
+    N = Xnew.shape[0]
+    means, vars_ = (np.empty((G, N, D)), np.empty((G, N, D))) if per_group else (None, None)
+    mm, mv = (np.empty((N, D)), np.empty((N, D))) if summary else (None, None)
+    U = np.empty((G, M, D)) if return_U else None
+    dp = _lib.dptr
+    opt = lambda x: None if x is None else dp(x)
+    rc = _lib.load().ffvd_op_posterior_conditional_grouped(a["kind"], G, nm, dp(a["Z"]), M, a["P"], D, dp(a["logvar"]), opt(a["loglen"]),
+                                                           dp(a["X"]), opt(a["ctrl"]), a["C"], a["T"], dp(a["log_Q"]), float(jitter),
+                                                           int(groups_per_pass), qm, dp(Xnew), N, int(rows_per_pass), opt(means),
+                                                           opt(vars_), opt(mm), opt(mv), opt(U))
+    _lib.check(rc, None, who)
+    return (means, vars_, mm, mv, U) if return_U else (means, vars_, mm, mv)
 
 
 def predict_y_summary(predict_x, predict_x_var, CC, DD, log_Rchols, Y_test=None, Y_train_std=1.0):

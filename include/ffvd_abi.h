@@ -516,6 +516,48 @@ int  ffvd_op_posterior_rollout_grouped(int kind, int G, int n_models, const doub
                                        int groups_per_pass, int R, const double *ctrl_roll, int steps, const double *eps,
                                        double *predict_x, double *predict_var, double *U_means);
 
+/* The posterior transition function f(x, c) of G groups at N common inputs: conditional_after_kernel_precalculation
+ * (conditionals_multi_output.py:306-387, white=True, full_cov=False) for every group in one launch sequence.  Group g uses model
+ * m(g) (n_models = 1: Z, the hyper-parameters and W = L^-T are shared; n_models = G: own).  With F_{m,d} = K_d(Xnew, Z_m) W_{m,d}
+ * (:349), projected once per (model, dim):
+ *   means[g][n][d] = sum_j F_{m(g),d}[n][j] U_g[j][d]                                                      (:365)
+ *   vars[g][n][d]  = Kdiag_d(x_n) - sum_j F_{m(g),d}[n][j]^2 + sum_j (F_{m(g),d} q_{g,d'})[n][j]^2         (:356, :369-380)
+ * q_mode 0 ("reference"): d' = 0, slice 0 of the group's L_H^-T stack inflates every dim (the stack is handed to every dim at :317,
+ * `[:, :, 0]` at :322 keeps slice 0) and q_sqrts holds G pointers; q_mode 1 ("intent"): d' = d, G * D pointers, entry
+ * g * D + d.  q_sqrts = NULL: no third term (explicit U, SG-HMC samples of U).  The pooled posterior is the equal-weight mixture,
+ * summed over g in ascending order: mix_mean = (sum_g mean_g) / G, mix_var = (sum_g (var_g + mean_g^2)) / G - mix_mean^2.
+ * Lm_inverse_seqs: n_models * D pointers, entry m * D + d -> M x M, upper triangular; every matrix goes from the caller's memory
+ * into its slot of a padded device stack.  Zs n_models x M x P; logvariances n_models x D; loglengthscales n_models x D x P (NULL
+ * for LinearK); fs G x M x D; Xnew N x P.  Outputs: means, vars G x N x D, either may be NULL; mix_mean, mix_var N x D, both or
+ * neither; at least one output overall.
+ * The third term is a 128 x 128-tiled fp64-MFMA product whose epilogue keeps only row sums of squares.  When every q slice is upper
+ * triangular (checked on the host) the k range of a column tile ends at its last column; a dense slice takes the full range and, where
+ * its strict lower triangle is zero, gives the same bits.
+ * rows_per_pass: F takes n_models * D * rows * Mp doubles (Mp: M rounded up to 64) and is reused between passes over the rows of
+ * Xnew; 0 = the largest multiple of 128 whose F is at most 2 GiB, a function of the shapes alone; a positive value forces the size.
+ * Determinism: two identical calls are bit-identical; a group's means / vars do not depend on G or on the other groups, nor on the
+ * pass size (fixed summation orders, no atomics).
+ * Limits: M <= 2048, D <= P <= 32, n_models 1 or G, N >= 0, q_mode 0 or 1, rows_per_pass >= 0, G * D <= 2^24, G * D * Mp^2 <= 2^29
+ * doubles (the q stack), G * N * D < 2^31; FFVD_EINVAL beyond them, before any device call.  G = 0 or N = 0: FFVD_OK, nothing is
+ * touched. */
+int  ffvd_op_conditional_grouped(int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M, int P,
+                                 int D, const double *logvariances, const double *loglengthscales, const double *fs,
+                                 const double *const *q_sqrts, int q_mode, const double *Xnew, int N, int rows_per_pass,
+                                 double *means, double *vars, double *mix_mean, double *mix_var);
+
+/* ffvd_op_posterior_grouped (kernel_pre_cal :124-169 and collapse_u_mean_after_kernel_precalculation :206-227, as base_model.py:243-256
+ * calls them) followed by ffvd_op_conditional_grouped (:306-387) WITHOUT the posteriors leaving the device: W is read where the K_uu
+ * chain left it, f = U_mean where the matvec left it, and the q slices (q_mode 0: slice 0 of each group, q_mode 1: all D) are packed
+ * by a device kernel with exact zeros in the padding and the strict lower triangle, so the triangular k cut holds by construction.
+ * Up the host link go the inputs; down come the factorisation flags, once, and the requested outputs (U_means G x M x D optional).
+ * Errors, stall recovery, "no output written on failure" and determinism: as ffvd_op_posterior_grouped.
+ * Limits: those of ffvd_op_posterior_grouped and of ffvd_op_conditional_grouped.  G = 0 or N = 0: FFVD_OK, nothing is touched. */
+int  ffvd_op_posterior_conditional_grouped(int kind, int G, int n_models, const double *Zs, int M, int P, int D,
+                                           const double *logvariances, const double *loglengthscales, const double *Xs,
+                                           const double *ctrl_fit, int C, int T, const double *log_Qs, double jitter,
+                                           int groups_per_pass, int q_mode, const double *Xnew, int N, int rows_per_pass,
+                                           double *means, double *vars, double *mix_mean, double *mix_var, double *U_means);
+
 /* One particle-Gibbs sweep over the latent trajectory: the INTENT of BaseModel.PG_for_X_speedup (base_model.py:78-138;
  * as written that op never updates X -- discarded TensorArray.write results (:115), an assign that is never run (:137) --
  * so there is no reference behaviour to match, see oracle/ffvd_pg_oracle.py).  n_free = PG_particles - 1 free particles
