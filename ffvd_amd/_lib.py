@@ -120,6 +120,15 @@ _SIGNATURES = {
     "ffvd_op_posterior_rollout_grouped": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp,
                                                     C.c_int, C.c_int, _dp, C.c_double, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp,
                                                     _dp, _dp]),
+    "ffvd_op_rollout_summary": (C.c_int, [_dp, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_int,
+                                          _dp, _dp, _dp, _dp, _dp]),
+    "ffvd_op_rollout_grouped_summary": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_void_p), _dp, C.c_int, C.c_int, C.c_int, _dp, _dp,
+                                                  _dp, C.POINTER(C.c_void_p), _dp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp,
+                                                  _dp, _dp, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp]),
+    "ffvd_op_posterior_rollout_grouped_summary": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp,
+                                                            _dp, C.c_int, C.c_int, _dp, C.c_double, C.c_int, C.c_int, _dp, C.c_int,
+                                                            _dp, _dp, _dp, _dp,
+                                                            _dp, _dp, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "ffvd_op_conditional_grouped": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), _dp, C.c_int, C.c_int, C.c_int, _dp, _dp,
                                               _dp, C.POINTER(C.c_void_p), C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp]),
     "ffvd_op_posterior_conditional_grouped": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp,

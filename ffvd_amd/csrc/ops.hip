@@ -8,6 +8,7 @@
 #include "rollout_group.h"
 #include "posterior_group.h"
 #include "conditional_group.h"
+#include "predict_summary.h"
 
 #include <atomic>
 #include <chrono>
@@ -174,6 +175,13 @@ extern "C" int ffvd_op_release_cache(void) {
     Scratch sc;                                                                              \
     if (!sc.begin())                                                                         \
         return set_error(nullptr, FFVD_EDEVICE, name ": no usable HIP device / stream creation failed");
+// the same for a body that several entry points share: `who` (a std::string) names the one that was called
+#define OP_BEGIN_AS(who)                                                                     \
+    Scratch sc;                                                                              \
+    if (!sc.begin())                                                                         \
+        return set_error(nullptr, FFVD_EDEVICE, (who) + ": no usable HIP device / stream creation failed");
+#define OP_CHECK_AS(ptr, who) \
+    if (!(ptr)) return set_error(nullptr, FFVD_ENOMEM, (who) + ": device allocation or upload failed");
 #define OP_CHECK(ptr, name) \
     if (!(ptr)) return set_error(nullptr, FFVD_ENOMEM, name ": device allocation or upload failed");
 
@@ -1054,29 +1062,96 @@ extern "C" int ffvd_op_rollout(int kind, const double *Lm_inverse_seq, const dou
     return FFVD_OK;
 }
 
-// G posteriors, one launch per step for all of them (rollout_group.hip)
-extern "C" int ffvd_op_rollout_grouped(int kind, int G, const double *const *Lm_inverse_seqs, const double *Zs, int M, int P, int D,
-                                       const double *logvariances, const double *loglengthscales, const double *fs,
-                                       const double *const *q_sqrts, const double *x_lasts, int R, const double *ctrl, int C, int steps,
-                                       const double *log_Qs, const double *eps, double *predict_x, double *predict_var) {
-    const char *bad = "ffvd_op_rollout_grouped: bad argument";
+// ---- rollout summaries (predict_summary.h) --------------------------------------------------------------------------------------------
+// The held-out predictive summary of base_model.py:330-348 over all rollouts of a call, formed on the device stacks.
+namespace {
+struct SummaryReq {
+    const double *CC, *DD, *noise_std;           // D x J, J, J
+    int J;
+    const double *Y_test;                        // n_test x J or NULL
+    int n_test;
+    double *y_mean, *y_var, *y_var_total;        // steps x J, each may be NULL
+    double *lpd, *lpd_gauss;                     // n_test x J, each may be NULL
+};
+
+// the checks that need no array (before the "nothing to do" return) and those that read the small arrays (after it)
+bool summary_scalars_ok(const SummaryReq &q, long long N, int steps, int D) {
+    if (q.J < 1 || q.J > PS_MAXJ || D < 1 || D > MAXP || N < 0 || steps < 0 || q.n_test < 0 || q.n_test > steps) return false;
+    return N == 0 || steps == 0 || N <= ((1LL << 31) - 1) / steps / D;              // N * steps * D < 2^31 elements per stack
+}
+bool summary_arrays_ok(const SummaryReq &q) {
+    if (!q.CC || !q.DD || !q.noise_std || !(q.y_mean || q.y_var || q.y_var_total || q.lpd || q.lpd_gauss)) return false;
+    if ((q.n_test > 0 || q.lpd || q.lpd_gauss) && !q.Y_test) return false;
+    for (int j = 0; j < q.J; ++j)
+        if (!std::isfinite(q.noise_std[j]) || !(q.noise_std[j] > 0.0)) return false;
+    return true;
+}
+
+// The two launches of predict_summary.h on stacks that are on the device, then the requested outputs come down (one small copy).
+int run_summary(Scratch &sc, const std::string &who, const double *dpx, const double *dpv, int N, int steps, int D, const SummaryReq &q) {
+    const int J = q.J;
+    const size_t SJ = (size_t)steps * J, TJ = (size_t)q.n_test * J;
+    PredictSummaryArgs a{};
+    a.N = N; a.steps = steps; a.D = D; a.J = J; a.n_test = q.n_test; a.x = dpx; a.v = dpv;
+    a.CC = sc.upload(q.CC, (size_t)D * J); a.DD = sc.upload(q.DD, J); a.sd = sc.upload(q.noise_std, J);
+    a.Y = q.n_test ? sc.upload(q.Y_test, TJ) : nullptr;
+    a.part = sc.alloc<double>(ps_part_doubles(N, steps, J));
+    a.out = sc.alloc<double>(ps_out_doubles(steps, J));
+    if (!a.CC || !a.DD || !a.sd || (q.n_test && !a.Y) || !a.part || !a.out)
+        return set_error(nullptr, FFVD_ENOMEM, who + ": device allocation or upload failed");
+    launch_predict_summary(sc.stream, a);
+    OP_TRY(hipGetLastError());
+    std::vector<double> &h = sc.host(ps_out_doubles(steps, J));
+    OP_TRY(hipMemcpyAsync(h.data(), a.out, h.size() * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
+    OP_TRY(hipStreamSynchronize(sc.stream));
+    double *const dst[5] = {q.y_mean, q.y_var, q.y_var_total, q.lpd, q.lpd_gauss};
+    for (int f = 0; f < 5; ++f)
+        if (dst[f]) memcpy(dst[f], h.data() + f * SJ, (f < 3 ? SJ : TJ) * sizeof(double));
+    return FFVD_OK;
+}
+}  // namespace
+
+// base_model.py:330-348 for stacks the caller holds: they are uploaded, summarised by the same launches as in the fused calls
+extern "C" int ffvd_op_rollout_summary(const double *predict_x, const double *predict_var, int N, int steps, int D, const double *CC,
+                                       const double *DD, const double *noise_std, int J, const double *Y_test, int n_test,
+                                       double *y_mean, double *y_var, double *y_var_total, double *lpd, double *lpd_gauss) {
+    const char *bad = "ffvd_op_rollout_summary: bad argument";
+    const SummaryReq q{CC, DD, noise_std, J, Y_test, n_test, y_mean, y_var, y_var_total, lpd, lpd_gauss};
+    if (!summary_scalars_ok(q, N, steps, D)) return set_error(nullptr, FFVD_EINVAL, bad);
+    if (N == 0 || steps == 0) return FFVD_OK;
+    if (!predict_x || !predict_var || !summary_arrays_ok(q)) return set_error(nullptr, FFVD_EINVAL, bad);
+    OP_BEGIN("ffvd_op_rollout_summary");
+    const size_t n = (size_t)N * steps * D;
+    double *dpx = sc.upload(predict_x, n), *dpv = sc.upload(predict_var, n);
+    OP_CHECK(dpx && dpv, "ffvd_op_rollout_summary");
+    return run_summary(sc, "ffvd_op_rollout_summary", dpx, dpv, N, steps, D, q);
+}
+
+// G posteriors, one launch per step for all of them (rollout_group.hip).  sum: the rollouts are also summarised where the step
+// launches wrote them, before any download, and predict_x / predict_var may each be NULL (not downloaded).
+static int rollout_grouped_run(const std::string &who, int kind, int G, const double *const *Lm_inverse_seqs, const double *Zs, int M,
+                               int P, int D, const double *logvariances, const double *loglengthscales, const double *fs,
+                               const double *const *q_sqrts, const double *x_lasts, int R, const double *ctrl, int C, int steps,
+                               const double *log_Qs, const double *eps, double *predict_x, double *predict_var, const SummaryReq *sum) {
+    const std::string bad = who + ": bad argument";
     if ((kind != FFVD_KERNEL_SE && kind != FFVD_KERNEL_LINEAR) || G < 0 || R < 1 || steps < 0 || M < 1 || M > 2048 || D < 1 || C < 0 ||
         P != D + C || P > MAXP)
         return set_error(nullptr, FFVD_EINVAL, bad);
     const int Mp = round_up(M, RG_SLAB), NS = Mp / RG_SLAB;
     if ((long long)G * D * Mp * Mp > (1LL << 29) || (long long)G * R > (1LL << 20) || (R + RG_RC - 1) / RG_RC > 65535 ||
         (long long)G * D * NS >= (1LL << 31))
-        return set_error(nullptr, FFVD_EINVAL, "ffvd_op_rollout_grouped: bad argument (beyond the limits of rollout_group.h)");
+        return set_error(nullptr, FFVD_EINVAL, bad + " (beyond the limits of rollout_group.h)");
+    if (sum && !summary_scalars_ok(*sum, (long long)G * R, steps, D)) return set_error(nullptr, FFVD_EINVAL, bad);
     if (G == 0 || steps == 0) return FFVD_OK;
-    if (!Lm_inverse_seqs || !Zs || !logvariances || !fs || !x_lasts || !log_Qs || !eps || !predict_x || !predict_var ||
-        (C > 0 && !ctrl) || (kind == FFVD_KERNEL_SE && !loglengthscales))
+    if (!Lm_inverse_seqs || !Zs || !logvariances || !fs || !x_lasts || !log_Qs || !eps || (!sum && (!predict_x || !predict_var)) ||
+        (C > 0 && !ctrl) || (kind == FFVD_KERNEL_SE && !loglengthscales) || (sum && !summary_arrays_ok(*sum)))
         return set_error(nullptr, FFVD_EINVAL, bad);
     const size_t GD = (size_t)G * D, out_n = (size_t)G * R * steps * D;
     for (size_t b = 0; b < GD; ++b) if (!Lm_inverse_seqs[b]) return set_error(nullptr, FFVD_EINVAL, bad);
     if (q_sqrts)
         for (int g = 0; g < G; ++g) if (!q_sqrts[g]) return set_error(nullptr, FFVD_EINVAL, bad);
-    OP_BEGIN("ffvd_op_rollout_grouped");
-    LapTimer timer("FFVD_RG_TIMING", "ffvd_op_rollout_grouped", sc.stream);
+    OP_BEGIN_AS(who);
+    LapTimer timer("FFVD_RG_TIMING", who.c_str(), sc.stream);
     double *dW = upload_matrix_table(sc, Lm_inverse_seqs, GD, M, Mp);
     timer.lap("W uploaded");
     // W q_sqrt is upper triangular when every group's q_sqrt slice is (the reference hands over L_H^-T): the step products then stop at
@@ -1094,8 +1169,8 @@ extern "C" int ffvd_op_rollout_grouped(int kind, int G, const double *const *Lm_
     double *variance = sc.alloc<double>(GD), *len = sc.alloc<double>(GD * P), *Zsc = sc.alloc<double>(GD * Mp * P), *zz = sc.alloc<double>(GD * Mp);
     double *part = sc.alloc<double>((size_t)2 * GD * NS * R * 4), *xbuf = sc.alloc<double>((size_t)2 * G * R * D);
     double *dpx = sc.alloc<double>(out_n), *dpv = sc.alloc<double>(out_n);
-    OP_CHECK(dW && dZ && dU && dxl && dlv && dlq && deps && (!C || dctrl) && (!loglengthscales || dll) && variance && len && Zsc && zz &&
-             part && xbuf && dpx && dpv && (!q_sqrts || (dq && dB)), "ffvd_op_rollout_grouped");
+    OP_CHECK_AS(dW && dZ && dU && dxl && dlv && dlq && deps && (!C || dctrl) && (!loglengthscales || dll) && variance && len && Zsc && zz &&
+             part && xbuf && dpx && dpv && (!q_sqrts || (dq && dB)), who);
     timer.lap("q_sqrt, small arrays uploaded");
     launch_rg_prep(sc.stream, kind, G, D, M, Mp, P, dZ, dlv, dll, variance, len, Zsc, zz);
     if (q_sqrts) launch_rg_wq(sc.stream, G, D, Mp, q_upper, dW, dq, dB);
@@ -1108,10 +1183,35 @@ extern "C" int ffvd_op_rollout_grouped(int kind, int G, const double *const *Lm_
     for (int t = 0; t <= steps; ++t) launch_rg_step(sc.stream, a, t);
     OP_TRY(hipGetLastError());
     timer.lap("step launches");
-    if (!sc.download(predict_x, dpx, out_n * sizeof(double)) || !sc.download(predict_var, dpv, out_n * sizeof(double)))
-        return set_error(nullptr, FFVD_EDEVICE, "ffvd_op_rollout_grouped: copying the results back failed");
+    if (sum) {
+        if (int rc = run_summary(sc, who, dpx, dpv, G * R, steps, D, *sum)) return rc;
+        timer.lap("summary");
+    }
+    if ((predict_x && !sc.download(predict_x, dpx, out_n * sizeof(double))) ||
+        (predict_var && !sc.download(predict_var, dpv, out_n * sizeof(double))))
+        return set_error(nullptr, FFVD_EDEVICE, who + ": copying the results back failed");
     timer.lap("results downloaded");
     return FFVD_OK;
+}
+
+extern "C" int ffvd_op_rollout_grouped(int kind, int G, const double *const *Lm_inverse_seqs, const double *Zs, int M, int P, int D,
+                                       const double *logvariances, const double *loglengthscales, const double *fs,
+                                       const double *const *q_sqrts, const double *x_lasts, int R, const double *ctrl, int C, int steps,
+                                       const double *log_Qs, const double *eps, double *predict_x, double *predict_var) {
+    return rollout_grouped_run("ffvd_op_rollout_grouped", kind, G, Lm_inverse_seqs, Zs, M, P, D, logvariances, loglengthscales, fs, q_sqrts,
+                               x_lasts, R, ctrl, C, steps, log_Qs, eps, predict_x, predict_var, nullptr);
+}
+
+extern "C" int ffvd_op_rollout_grouped_summary(int kind, int G, const double *const *Lm_inverse_seqs, const double *Zs, int M, int P,
+                                               int D, const double *logvariances, const double *loglengthscales, const double *fs,
+                                               const double *const *q_sqrts, const double *x_lasts, int R, const double *ctrl, int C,
+                                               int steps, const double *log_Qs, const double *eps, double *predict_x,
+                                               double *predict_var, const double *CC, const double *DD, const double *noise_std, int J,
+                                               const double *Y_test, int n_test, double *y_mean, double *y_var, double *y_var_total,
+                                               double *lpd, double *lpd_gauss) {
+    const SummaryReq q{CC, DD, noise_std, J, Y_test, n_test, y_mean, y_var, y_var_total, lpd, lpd_gauss};
+    return rollout_grouped_run("ffvd_op_rollout_grouped_summary", kind, G, Lm_inverse_seqs, Zs, M, P, D, logvariances, loglengthscales, fs,
+                               q_sqrts, x_lasts, R, ctrl, C, steps, log_Qs, eps, predict_x, predict_var, &q);
 }
 
 extern "C" int ffvd_op_pg_sweep(int kind, const double *Lm_inverse_seq, const double *Z, int M, int P, int D,
@@ -1376,23 +1476,26 @@ extern "C" int ffvd_op_posterior_grouped(int kind, int G, int n_models, const do
 // The posteriors above handed to the grouped rollout loop (base_model.py:243-314 per group) without leaving the device: W, q0, f and
 // x_last of RolloutGroupArgs are written by posterior_group.hip's kernels from the factorisation slabs, then launch_rg_prep /
 // launch_rg_wq / launch_rg_step run as in ffvd_op_rollout_grouped.
-extern "C" int ffvd_op_posterior_rollout_grouped(int kind, int G, int n_models, const double *Zs, int M, int P, int D,
-                                                 const double *logvariances, const double *loglengthscales, const double *Xs,
-                                                 const double *ctrl_fit, int C, int T, const double *log_Qs, double jitter,
-                                                 int groups_per_pass, int R, const double *ctrl_roll, int steps, const double *eps,
-                                                 double *predict_x, double *predict_var, double *U_means) {
-    const char *who = "ffvd_op_posterior_rollout_grouped", *bad = "ffvd_op_posterior_rollout_grouped: bad argument";
+// sum: as in rollout_grouped_run -- the summary launches follow the step launches, predict_x / predict_var may each be NULL.
+static int posterior_rollout_grouped_run(const std::string &whos, int kind, int G, int n_models, const double *Zs, int M, int P, int D,
+                                         const double *logvariances, const double *loglengthscales, const double *Xs,
+                                         const double *ctrl_fit, int C, int T, const double *log_Qs, double jitter, int groups_per_pass,
+                                         int R, const double *ctrl_roll, int steps, const double *eps, double *predict_x,
+                                         double *predict_var, double *U_means, const SummaryReq *sum) {
+    const char *who = whos.c_str();
+    const std::string bad = whos + ": bad argument";
     if (!pg_scalars_ok(kind, G, n_models, M, P, D, C, T, groups_per_pass, jitter) || R < 1 || steps < 0)
         return set_error(nullptr, FFVD_EINVAL, bad);
     const int Mp16 = round_up(M, RG_SLAB), NS = Mp16 / RG_SLAB;
     if ((long long)G * D * Mp16 * Mp16 > (1LL << 29) || (long long)G * R > (1LL << 20) || (R + RG_RC - 1) / RG_RC > 65535 ||
         (long long)G * D * NS >= (1LL << 31))
-        return set_error(nullptr, FFVD_EINVAL, "ffvd_op_posterior_rollout_grouped: bad argument (beyond the limits of rollout_group.h)");
+        return set_error(nullptr, FFVD_EINVAL, bad + " (beyond the limits of rollout_group.h)");
+    if (sum && !summary_scalars_ok(*sum, (long long)G * R, steps, D)) return set_error(nullptr, FFVD_EINVAL, bad);
     if (G == 0 || steps == 0) return FFVD_OK;
-    if (!Zs || !logvariances || !Xs || !log_Qs || !eps || !predict_x || !predict_var || (C > 0 && (!ctrl_fit || !ctrl_roll)) ||
-        (kind == FFVD_KERNEL_SE && !loglengthscales))
+    if (!Zs || !logvariances || !Xs || !log_Qs || !eps || (!sum && (!predict_x || !predict_var)) || (C > 0 && (!ctrl_fit || !ctrl_roll)) ||
+        (kind == FFVD_KERNEL_SE && !loglengthscales) || (sum && !summary_arrays_ok(*sum)))
         return set_error(nullptr, FFVD_EINVAL, bad);
-    OP_BEGIN("ffvd_op_posterior_rollout_grouped");
+    OP_BEGIN_AS(whos);
     LapTimer timer("FFVD_RG_TIMING", who, sc.stream);
     PgIn in{who, kind, G, n_models, M, P, D, C, T, groups_per_pass, Zs, logvariances, loglengthscales, Xs, ctrl_fit, log_Qs, jitter};
     PgWork w{};
@@ -1400,7 +1503,7 @@ extern "C" int ffvd_op_posterior_rollout_grouped(int kind, int G, int n_models, 
     w.Mp16 = Mp16;
     w.q0 = sc.alloc<double>((size_t)G * mm16);
     double *dW = sc.alloc<double>(GD * mm16), *dB = sc.alloc<double>(GD * mm16);
-    OP_CHECK(w.q0 && dW && dB, "ffvd_op_posterior_rollout_grouped");
+    OP_CHECK_AS(w.q0 && dW && dB, whos);
     if (int rc = pg_posterior(sc, in, w)) return rc;
     timer.lap("posteriors");
     // the rollout loop's own copy of the small inputs, one row per group (a shared model is repeated: launch_rg_step indexes by group)
@@ -1420,8 +1523,8 @@ extern "C" int ffvd_op_posterior_rollout_grouped(int kind, int G, int n_models, 
     double *variance = sc.alloc<double>(GD), *len = sc.alloc<double>(GD * P), *Zsc = sc.alloc<double>(GD * Mp16 * P), *zz = sc.alloc<double>(GD * Mp16);
     double *part = sc.alloc<double>((size_t)2 * GD * NS * R * 4), *xbuf = sc.alloc<double>((size_t)2 * G * R * D);
     double *dpx = sc.alloc<double>(out_n), *dpv = sc.alloc<double>(out_n);
-    OP_CHECK(dZ && dlv && (!hll || dll) && deps && (!C || dctrl) && dxl && variance && len && Zsc && zz && part && xbuf && dpx && dpv,
-             "ffvd_op_posterior_rollout_grouped");
+    OP_CHECK_AS(dZ && dlv && (!hll || dll) && deps && (!C || dctrl) && dxl && variance && len && Zsc && zz && part && xbuf && dpx && dpv,
+             whos);
     // W[g][d] = L^-T of the group's model; with one model every group reads the same slab (the stack is still materialised)
     launch_pg_pack(sc.stream, w.Kuu, (size_t)2 * w.Mp * w.Mp, w.Mp, w.Mp, w.nK, 1, M, 1, dW, Mp16, Mp16, (int)GD);
     launch_pg_x_last(sc.stream, w.Xs, G, T, D, dxl);
@@ -1436,11 +1539,40 @@ extern "C" int ffvd_op_posterior_rollout_grouped(int kind, int G, int n_models, 
     for (int t = 0; t <= steps; ++t) launch_rg_step(sc.stream, a, t);
     OP_TRY(hipGetLastError());
     timer.lap("step launches");
-    if (!sc.download(predict_x, dpx, out_n * sizeof(double)) || !sc.download(predict_var, dpv, out_n * sizeof(double)) ||
+    if (sum) {
+        if (int rc = run_summary(sc, whos, dpx, dpv, G * R, steps, D, *sum)) return rc;
+        timer.lap("summary");
+    }
+    if ((predict_x && !sc.download(predict_x, dpx, out_n * sizeof(double))) ||
+        (predict_var && !sc.download(predict_var, dpv, out_n * sizeof(double))) ||
         (U_means && !sc.download(U_means, w.U, GD * M * sizeof(double))))
-        return set_error(nullptr, FFVD_EDEVICE, "ffvd_op_posterior_rollout_grouped: copying the results back failed");
+        return set_error(nullptr, FFVD_EDEVICE, whos + ": copying the results back failed");
     timer.lap("results downloaded");
     return FFVD_OK;
+}
+
+extern "C" int ffvd_op_posterior_rollout_grouped(int kind, int G, int n_models, const double *Zs, int M, int P, int D,
+                                                 const double *logvariances, const double *loglengthscales, const double *Xs,
+                                                 const double *ctrl_fit, int C, int T, const double *log_Qs, double jitter,
+                                                 int groups_per_pass, int R, const double *ctrl_roll, int steps, const double *eps,
+                                                 double *predict_x, double *predict_var, double *U_means) {
+    return posterior_rollout_grouped_run("ffvd_op_posterior_rollout_grouped", kind, G, n_models, Zs, M, P, D, logvariances, loglengthscales,
+                                         Xs, ctrl_fit, C, T, log_Qs, jitter, groups_per_pass, R, ctrl_roll, steps, eps, predict_x,
+                                         predict_var, U_means, nullptr);
+}
+
+extern "C" int ffvd_op_posterior_rollout_grouped_summary(int kind, int G, int n_models, const double *Zs, int M, int P, int D,
+                                                         const double *logvariances, const double *loglengthscales, const double *Xs,
+                                                         const double *ctrl_fit, int C, int T, const double *log_Qs, double jitter,
+                                                         int groups_per_pass, int R, const double *ctrl_roll, int steps,
+                                                         const double *eps, double *predict_x, double *predict_var, double *U_means,
+                                                         const double *CC, const double *DD, const double *noise_std, int J,
+                                                         const double *Y_test, int n_test, double *y_mean, double *y_var,
+                                                         double *y_var_total, double *lpd, double *lpd_gauss) {
+    const SummaryReq q{CC, DD, noise_std, J, Y_test, n_test, y_mean, y_var, y_var_total, lpd, lpd_gauss};
+    return posterior_rollout_grouped_run("ffvd_op_posterior_rollout_grouped_summary", kind, G, n_models, Zs, M, P, D, logvariances,
+                                         loglengthscales, Xs, ctrl_fit, C, T, log_Qs, jitter, groups_per_pass, R, ctrl_roll, steps, eps,
+                                         predict_x, predict_var, U_means, &q);
 }
 
 // ---- grouped GP conditionals (conditional_group.h) ------------------------------------------------------------------------------------

@@ -411,16 +411,22 @@ class DGPSSM:
         return out
 
     def collect_samples_chains(self, num_per_chain, control_inputs, test_len, *, Y_test=None, Y_train_std=1.0, Y_train=None,
-                               eps=None, seed=None, fused=False):
+                               eps=None, seed=None, fused=False, summary="host"):
         """Rollouts from EVERY chain of a `num_chains = S` model (collect_samples_formal predicts from chain 0 only): the K_uu
         factors once, the collapsed posterior U | X_s per chain (with explicit U: the shared U, no q_sqrt), `num_per_chain`
         rollouts of `test_len` steps from each chain's own X_s[-1] -- one `rollout_grouped` call with G = S, R = num_per_chain.
         `eps` (test_len, S, num_per_chain, D) injects the draws of base_model.py:306 (else numpy's default_rng(seed)).
         fused=True (collapsed U only; ValueError with explicit U: there is no posterior to build): the S posteriors and their rollouts
         in ONE `posterior_rollout_grouped` call with the model shared by the groups -- the posteriors never leave the device.
+        summary "host": `predict_y_summary` in NumPy on the downloaded stacks; "device": the same keys from the summary kernels in
+        the same call (`rollout_grouped_summary` / `posterior_rollout_grouped_summary`), plus predict_y_var_total and, with Y_test,
+        lpd, lpd_gauss, ll and ll_original_units (prediction.rollout_summary).
         Returns a dict: predict_x, predict_x_var (S, num_per_chain, test_len, D) and the predict_y_summary over all S * R rollouts."""
         from . import conditionals_multi_output as cmo
-        from .prediction import posterior_rollout_grouped, predict_y_summary, rollout_grouped
+        from .prediction import (posterior_rollout_grouped, posterior_rollout_grouped_summary, predict_y_summary, rollout_grouped,
+                                 rollout_grouped_summary)
+        if summary not in ("host", "device"):
+            raise ValueError("collect_samples_chains: summary must be 'host' or 'device'")
         if fused and not self.U_collapse:
             raise ValueError("collect_samples_chains: fused=True builds the collapsed posterior; with explicit U there is none to build")
         if self._host_stale:
@@ -436,6 +442,14 @@ class DGPSSM:
             raise ValueError(f"eps: expected {(test_len, S, R, D)}, got {eps.shape}")
         n_train = self.Y.shape[0] if Y_train is None else np.asarray(Y_train).shape[0]
         lay = self.layers[-1]
+        lik = self.likelihood
+        if fused and summary == "device":
+            out = posterior_rollout_grouped_summary(lay.Z, lay.kernel, [self._X_chains[s_] for s_ in range(S)], self.Q, ci, n_train,
+                                                    test_len, eps, lik.CC, lik.DD, lik.log_Rchols, Y_test, Y_train_std,
+                                                    return_rollouts=True, return_U=True)
+            U_all = out.pop("U_means")
+            out["U_vals"] = [U_all[s_] for s_ in range(S)]
+            return out
         if fused:
             px, pv, U_all = posterior_rollout_grouped(lay.Z, lay.kernel, [self._X_chains[s_] for s_ in range(S)], self.Q, ci, n_train,
                                                       test_len, eps, return_U=True)
@@ -454,12 +468,54 @@ class DGPSSM:
                 U_val, U_chol = lay.U, None
             U_vals.append(U_val)
             U_chols.append(U_chol)
+        if summary == "device":
+            out = rollout_grouped_summary([Lm] * S, [lay.Z] * S, [lay.kernel] * S, U_vals, U_chols if self.U_collapse else None,
+                                          [self._X_chains[s_][-1] for s_ in range(S)], ci, n_train, test_len, [self.Q] * S, eps,
+                                          lik.CC, lik.DD, lik.log_Rchols, Y_test, Y_train_std, return_rollouts=True)
+            out["U_vals"] = U_vals
+            return out
         px, pv = rollout_grouped([Lm] * S, [lay.Z] * S, [lay.kernel] * S, U_vals, U_chols if self.U_collapse else None,
                                  [self._X_chains[s_][-1] for s_ in range(S)], ci, n_train, test_len, [self.Q] * S, eps)
         out = predict_y_summary(px.reshape(S * R, test_len, D), pv.reshape(S * R, test_len, D), self.likelihood.CC,
                                 self.likelihood.DD, self.likelihood.log_Rchols, Y_test, Y_train_std)
         out.update(predict_x=px, predict_x_var=pv, U_vals=U_vals)
         return out
+
+    def evaluate_heldout(self, Y_test, control_inputs, num_per_chain, *, Y_train_std=1.0, eps=None, seed=None):
+        """Held-out metrics of the model as it stands: `num_per_chain` rollouts of len(Y_test) steps from every chain's X_s[-1],
+        summarised on the device (prediction.rollout_summary has the quantities) -- no trajectory is downloaded.
+        Collapsed U: ONE `posterior_rollout_grouped_summary` call with G = S and the model shared by the groups.  Explicit U:
+        `kernel_pre_cal` once, then `rollout_grouped_summary` with the shared U and no q_sqrt.
+        `eps` (len(Y_test), S, num_per_chain, D) injects the draws of base_model.py:306 (else numpy's default_rng(seed): the model's
+        own generator is not advanced).  Parameters newer on the device than on the host are pulled first.
+        Returns a dict: RMSE (first 30 test points, base_model.py:346-348), ll (mean log predictive density), ll_original_units,
+        and the per-step arrays predict_y, predict_y_var, predict_y_var_total, lpd, lpd_gauss."""
+        from . import conditionals_multi_output as cmo
+        from .prediction import posterior_rollout_grouped_summary, rollout_grouped_summary
+        Y_test = np.asarray(Y_test, dtype=np.float64)
+        if Y_test.ndim == 1:
+            Y_test = Y_test[:, None]
+        if Y_test.ndim != 2 or Y_test.shape[0] < 1 or Y_test.shape[1] != self.Y.shape[1]:
+            raise ValueError(f"evaluate_heldout: Y_test: expected (n_test >= 1, {self.Y.shape[1]}), got {Y_test.shape}")
+        if self._host_stale:
+            self.pull_parameters()
+        S, D, R, steps = self.num_chains, self.output_dim, int(num_per_chain), Y_test.shape[0]
+        if R < 1:
+            raise ValueError("num_per_chain must be at least 1")
+        ci = self.control_inputs if control_inputs is None else np.asarray(control_inputs, dtype=np.float64)
+        if eps is None:
+            eps = np.random.default_rng(seed).standard_normal((steps, S, R, D))
+        eps = np.asarray(eps, dtype=np.float64)
+        if eps.shape != (steps, S, R, D):
+            raise ValueError(f"eps: expected {(steps, S, R, D)}, got {eps.shape}")
+        lay, lik, n_train = self.layers[-1], self.likelihood, self.Y.shape[0]
+        if self.U_collapse:
+            return posterior_rollout_grouped_summary(lay.Z, lay.kernel, [self._X_chains[s_] for s_ in range(S)], self.Q, ci, n_train,
+                                                     steps, eps, lik.CC, lik.DD, lik.log_Rchols, Y_test, Y_train_std)
+        Lm = cmo.kernel_pre_cal(lay.Z, lay.kernel)
+        return rollout_grouped_summary([Lm] * S, [lay.Z] * S, [lay.kernel] * S, [lay.U] * S, None,
+                                       [self._X_chains[s_][-1] for s_ in range(S)], ci, n_train, steps, [self.Q] * S, eps,
+                                       lik.CC, lik.DD, lik.log_Rchols, Y_test, Y_train_std)
 
     def predict_transition(self, Xnew, *, q_mode="reference", per_chain=True):
         """The learned transition function at inputs of the caller's choice: mean and variance of the posterior GP increment

@@ -37,7 +37,17 @@ class Model:
         if prior_type not in ("determinantal", "normal", "strauss", "uniform"):
             raise Exception("Invalid prior type")    # models.py:35-41
 
-    def _fit(self, Y_train, lik, kernel_type, kernel_train_flag, iterations=None, epsilon=0.01, **kwargs):
+    def _fit(self, Y_train, lik, kernel_type, kernel_train_flag, iterations=None, epsilon=0.01, Y_test=None, eval_every=0,
+             eval_rollouts=8, Y_train_std=1.0, **kwargs):
+        """eval_every = k > 0 with Y_test: after every k-th round `DGPSSM.evaluate_heldout` (eval_rollouts rollouts per chain, on
+        the device) appends its RMSE and mean log predictive density to rmse_seq / ll_seq (models.py:89-92 creates them).  Its
+        noise comes from a generator of its own, seeded with the round: the training noise stream is not touched.  The default 0
+        leaves the loop exactly as it is."""
+        eval_every = int(eval_every)
+        if eval_every < 0:
+            raise ValueError("eval_every must not be negative")
+        if eval_every and Y_test is None:
+            raise ValueError("eval_every needs Y_test")
         Y_train = np.asarray(Y_train, dtype=np.float64)
         if Y_train.ndim == 1:
             Y_train = Y_train[:, None]
@@ -89,6 +99,10 @@ class Model:
                 self.model.gp_x_sampling()                                       # models.py:156-158
             t = self.model.train_hypers()                                        # models.py:168
             self.nll_seq.append(t["nll"])
+            if eval_every and self.global_step % eval_every == 0:
+                ev = self.model.evaluate_heldout(Y_test, None, eval_rollouts, Y_train_std=Y_train_std, seed=self.global_step)
+                self.rmse_seq.append(ev["RMSE"])
+                self.ll_seq.append(ev["ll"])
         if n_iter:
             self.model.pull_parameters()
         return self
@@ -100,10 +114,19 @@ class RegressionModel(Model):
 
     def fit(self, Y_train, Y_test=None, tensorboard_savepath="", dataname="", fileid="",
             kernel_type="SquaredExponential", kernel_train_flag=True, likelihood_traning=True, X_train=None,
-            X_test=None, Ystd=None, data_uu=None, epsilon=0.01, iterations=None, **kwargs):
+            X_test=None, Ystd=None, data_uu=None, epsilon=0.01, iterations=None, eval_every=0, eval_rollouts=8, **kwargs):
         """models.py:319-322.  `iterations`: number of (sghmc_step, [gp_x_sampling,] train_hypers) rounds; the default
         None = 2 * ARGS.iterations as models.py:142, so the reference's call (FFVD_Main.py:343) trains; 0 builds the model
-        and evaluates the initial nll only."""
+        and evaluates the initial nll only.  eval_every = k > 0 (with Y_test): held-out RMSE and log predictive density every k
+        rounds into rmse_seq / ll_seq (`_fit`), from eval_rollouts rollouts per chain; Ystd, one standard deviation for all outputs (as
+        base_model.py:348's Y_train_std; ValueError for more than one entry), scales that RMSE.  Without eval_every Ystd is
+        ignored, as before."""
+        Y_train_std = 1.0
+        if eval_every and Ystd is not None:
+            std = np.asarray(Ystd, dtype=np.float64).reshape(-1)
+            if std.size != 1:                  # the RMSE and ll_original_units are scaled by ONE standard deviation (base_model.py:348)
+                raise ValueError(f"fit: eval_every takes one Ystd for all outputs (a scalar), got {std.size} entries")
+            Y_train_std = float(std[0])
         Y_train = np.asarray(Y_train, dtype=np.float64)
         if Y_train.ndim == 1:
             Y_train = Y_train[:, None]
@@ -111,4 +134,6 @@ class RegressionModel(Model):
         lik = Gaussian(Y_train.shape[1], A.x_dims[-1], CC=A.CC, DD=A.DD, RR_chol=A.RR_chol,
                        hyperparameter_sampling=getattr(A, "hyperparameter_sampling", False),
                        likelihood_traning=likelihood_traning)                     # models.py:320
-        return self._fit(Y_train, lik, kernel_type, kernel_train_flag, iterations=iterations, epsilon=epsilon, **kwargs)
+        return self._fit(Y_train, lik, kernel_type, kernel_train_flag, iterations=iterations, epsilon=epsilon,
+                         Y_test=Y_test if eval_every else None, eval_every=eval_every, eval_rollouts=eval_rollouts,
+                         Y_train_std=Y_train_std, **kwargs)

@@ -56,13 +56,9 @@ def rollout(Lm_inverse_seq, Z, kern, U_val, q_sqrt, x_last, control_inputs, ctrl
     return px, pv
 
 
-def rollout_grouped(Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x_lasts, control_inputs, ctrl_offset, steps, Qs, eps):
-    """G independent posteriors rolled forward by one call (`ffvd_op_rollout_grouped`): one launch per step for all groups.
-
-    Every argument but control_inputs / ctrl_offset / steps / eps is a length-G sequence of the matching argument of `rollout`
-    (one posterior per SG-HMC sample, or per chain); q_sqrts: None or G stacks (D, M, M), slice 0 of each is used (SURVEY a14);
-    eps: (steps, G, R, D).  Kernel kind, M, P and D are common to the groups.  Returns predict_x, predict_x_var (G, R, steps, D);
-    group g's slab is bit-identical to what a G = 1 call on that group alone returns."""
+def _pack_rollout_groups(Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x_lasts, control_inputs, ctrl_offset, steps, Qs, eps):
+    """Shape checks and packing of `rollout_grouped`'s arguments (before the library is loaded): the leading arguments of
+    `ffvd_op_rollout_grouped` up to eps, and the shapes."""
     G = len(kerns)
     if G < 1:
         raise ValueError("rollout_grouped: at least one group is needed")
@@ -120,24 +116,29 @@ def rollout_grouped(Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x_lasts, contro
     import ctypes
     Wt = (ctypes.c_void_p * len(Wm))(*[w.ctypes.data for w in Wm])
     qt = (ctypes.c_void_p * len(qm))(*[q.ctypes.data for q in qm]) if q_sqrts is not None else None
+    args = (kind, G, Wt, _lib.dptr(Z), M, P, D, _lib.dptr(logvar), None if loglen is None else _lib.dptr(loglen), _lib.dptr(f), qt,
+            _lib.dptr(xl), R, None if ctrl is None else _lib.dptr(ctrl), C, steps, _lib.dptr(log_Q), _lib.dptr(eps))
+    return dict(args=args, G=G, R=R, D=D, steps=steps, keep=(Wm, qm, Z, logvar, loglen, f, xl, ctrl, log_Q, eps))
+
+
+def rollout_grouped(Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x_lasts, control_inputs, ctrl_offset, steps, Qs, eps):
+    """G independent posteriors rolled forward by one call (`ffvd_op_rollout_grouped`): one launch per step for all groups.
+
+    Every argument but control_inputs / ctrl_offset / steps / eps is a length-G sequence of the matching argument of `rollout`
+    (one posterior per SG-HMC sample, or per chain); q_sqrts: None or G stacks (D, M, M), slice 0 of each is used (SURVEY a14);
+    eps: (steps, G, R, D).  Kernel kind, M, P and D are common to the groups.  Returns predict_x, predict_x_var (G, R, steps, D);
+    group g's slab is bit-identical to what a G = 1 call on that group alone returns."""
+    a = _pack_rollout_groups(Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x_lasts, control_inputs, ctrl_offset, steps, Qs, eps)
+    G, R, D = a["G"], a["R"], a["D"]
     px, pv = np.empty((G, R, steps, D)), np.empty((G, R, steps, D))
-    rc = _lib.load().ffvd_op_rollout_grouped(kind, G, Wt, _lib.dptr(Z), M, P, D, _lib.dptr(logvar),
-                                             None if loglen is None else _lib.dptr(loglen), _lib.dptr(f), qt, _lib.dptr(xl), R,
-                                             None if ctrl is None else _lib.dptr(ctrl), C, steps, _lib.dptr(log_Q), _lib.dptr(eps),
-                                             _lib.dptr(px), _lib.dptr(pv))
+    rc = _lib.load().ffvd_op_rollout_grouped(*a["args"], _lib.dptr(px), _lib.dptr(pv))
     _lib.check(rc, None, "ffvd_op_rollout_grouped")
     return px, pv
 
 
-def posterior_rollout_grouped(Zs, kerns, Xs, Qs, control_inputs, ctrl_offset, steps, eps, *, jitter=JITTER, groups_per_pass=0,
-                              return_U=False):
-    """The collapsed posterior of G groups and their rollouts in ONE call (`ffvd_op_posterior_rollout_grouped`): what
-    `conditionals_multi_output.collapse_u_mean_grouped` followed by `rollout_grouped` computes, without the posteriors leaving the
-    device.  `Zs` / `kerns`: one model (shared by the groups: one per chain) or length-G sequences (one per SG-HMC sample); Xs: G
-    trajectories (T+1, D), the rollouts of group g start at Xs[g][-1]; Qs: G vectors (D,) or one; rows [0, T) of control_inputs feed
-    the posterior, rows [ctrl_offset, ctrl_offset + steps) the rollouts; eps: (steps, G, R, D).
-    Returns predict_x, predict_x_var (G, R, steps, D) and, with return_U, U_means (G, M, D)."""
-    who = "posterior_rollout_grouped"
+def _pack_posterior_rollout(who, Zs, kerns, Xs, Qs, control_inputs, ctrl_offset, steps, eps, jitter, groups_per_pass):
+    """Shape checks and packing of `posterior_rollout_grouped`'s arguments (before the library is loaded): the leading arguments
+    of `ffvd_op_posterior_rollout_grouped` up to eps, and the shapes."""
     a = pack_posterior_groups(Zs, kerns, Xs, control_inputs, Qs, who)
     G, nm, M, D, C = a["G"], a["n_models"], a["M"], a["D"], a["C"]
     steps = int(steps)
@@ -153,15 +154,28 @@ def posterior_rollout_grouped(Zs, kerns, Xs, Qs, control_inputs, ctrl_offset, st
         if ci.shape[0] < ctrl_offset + steps:
             raise ValueError(f"control_inputs: need at least {ctrl_offset + steps} rows of {C} columns")
         ctrl = np.ascontiguousarray(ci[ctrl_offset: ctrl_offset + steps])
+    dp = _lib.dptr
+    args = (a["kind"], G, nm, dp(a["Z"]), M, a["P"], D, dp(a["logvar"]), None if a["loglen"] is None else dp(a["loglen"]), dp(a["X"]),
+            None if a["ctrl"] is None else dp(a["ctrl"]), C, a["T"], dp(a["log_Q"]), float(jitter), int(groups_per_pass), R,
+            None if ctrl is None else dp(ctrl), steps, dp(eps))
+    return dict(args=args, G=G, R=R, M=M, D=D, steps=steps, keep=(a, ctrl, eps))
+
+
+def posterior_rollout_grouped(Zs, kerns, Xs, Qs, control_inputs, ctrl_offset, steps, eps, *, jitter=JITTER, groups_per_pass=0,
+                              return_U=False):
+    """The collapsed posterior of G groups and their rollouts in ONE call (`ffvd_op_posterior_rollout_grouped`): what
+    `conditionals_multi_output.collapse_u_mean_grouped` followed by `rollout_grouped` computes, without the posteriors leaving the
+    device.  `Zs` / `kerns`: one model (shared by the groups: one per chain) or length-G sequences (one per SG-HMC sample); Xs: G
+    trajectories (T+1, D), the rollouts of group g start at Xs[g][-1]; Qs: G vectors (D,) or one; rows [0, T) of control_inputs feed
+    the posterior, rows [ctrl_offset, ctrl_offset + steps) the rollouts; eps: (steps, G, R, D).
+    Returns predict_x, predict_x_var (G, R, steps, D) and, with return_U, U_means (G, M, D)."""
+    who = "posterior_rollout_grouped"
+    a = _pack_posterior_rollout(who, Zs, kerns, Xs, Qs, control_inputs, ctrl_offset, steps, eps, jitter, groups_per_pass)
+    G, R, M, D, steps = a["G"], a["R"], a["M"], a["D"], a["steps"]
     px, pv = np.empty((G, R, steps, D)), np.empty((G, R, steps, D))
     U = np.empty((G, M, D)) if return_U else None
     dp = _lib.dptr
-    rc = _lib.load().ffvd_op_posterior_rollout_grouped(a["kind"], G, nm, dp(a["Z"]), M, a["P"], D, dp(a["logvar"]),
-                                                       None if a["loglen"] is None else dp(a["loglen"]), dp(a["X"]),
-                                                       None if a["ctrl"] is None else dp(a["ctrl"]), C, a["T"], dp(a["log_Q"]),
-                                                       float(jitter), int(groups_per_pass), R,
-                                                       None if ctrl is None else dp(ctrl), steps, dp(eps), dp(px), dp(pv),
-                                                       None if U is None else dp(U))
+    rc = _lib.load().ffvd_op_posterior_rollout_grouped(*a["args"], dp(px), dp(pv), None if U is None else dp(U))
     _lib.check(rc, None, who)
     return (px, pv, U) if return_U else (px, pv)
 
@@ -204,6 +218,130 @@ def predict_y_summary(predict_x, predict_x_var, CC, DD, log_Rchols, Y_test=None,
         y30, p30 = np.asarray(Y_test, dtype=np.float64)[:30].reshape(-1), predict_y[:30]
         out["RMSE"] = float(np.sqrt(np.mean((y30 - p30) ** 2)) * Y_train_std)
     return out
+
+
+SUMMARY_MAX_OUTPUTS = 8       # J <= 8, as the particle-Gibbs step
+
+
+def _pack_summary(who, D, steps, CC, DD, log_Rchols, Y_test):
+    """Shape checks of the emission and the held-out data (before the library is loaded).  The noise standard deviation of output
+    j is exp(log_Rchols[0, j]): row 0, the row the likelihood of the nll uses (dgp_model.py:250); a vector of J entries (or a scalar
+    for J = 1) is taken as that row."""
+    CC = _lib.as_f64(CC)
+    if CC.ndim != 2 or CC.shape[0] != D or not 1 <= CC.shape[1] <= SUMMARY_MAX_OUTPUTS:
+        raise ValueError(f"{who}: CC: expected ({D}, J) with 1 <= J <= {SUMMARY_MAX_OUTPUTS}, got {CC.shape}")
+    J = CC.shape[1]
+    DD = _lib.as_f64(np.asarray(DD, dtype=np.float64).reshape(-1), (J,), "DD")
+    lr = np.asarray(log_Rchols, dtype=np.float64)
+    if lr.ndim == 2 and lr.shape == (J, J):
+        lr = lr[0]
+    elif lr.size == J and lr.ndim <= 1:
+        lr = lr.reshape(J)
+    else:
+        raise ValueError(f"{who}: log_Rchols: expected ({J}, {J}) or ({J},), got {lr.shape}")
+    sd = np.ascontiguousarray(np.exp(lr))
+    if not np.all(np.isfinite(sd)) or not np.all(sd > 0.0):
+        raise ValueError(f"{who}: exp(log_Rchols[0, :]) must be finite and positive")
+    Y = None
+    if Y_test is not None:
+        Y = np.asarray(Y_test, dtype=np.float64)
+        if Y.ndim == 1 and J == 1:
+            Y = Y[:, None]
+        if Y.ndim != 2 or Y.shape[1] != J or Y.shape[0] > steps:
+            raise ValueError(f"{who}: Y_test: expected (n_test <= {steps}, {J}), got {Y.shape}")
+        Y = np.ascontiguousarray(Y)
+    return dict(CC=CC, DD=DD, sd=sd, Y=Y, J=J, n_test=0 if Y is None else Y.shape[0])
+
+
+def _summary_call(m, steps):
+    """Output arrays and the trailing arguments of the three summary entry points."""
+    J, nt, dp = m["J"], m["n_test"], _lib.dptr
+    out = dict(y_mean=np.empty((steps, J)), y_var=np.empty((steps, J)), y_var_total=np.empty((steps, J)))
+    if m["Y"] is not None:
+        out.update(lpd=np.empty((nt, J)), lpd_gauss=np.empty((nt, J)))
+    opt = lambda k: dp(out[k]) if k in out and out[k].size else None            # (no held-out rows: no density is asked for)
+    args = (dp(m["CC"]), dp(m["DD"]), dp(m["sd"]), J, dp(m["Y"]) if nt else None, nt, opt("y_mean"), opt("y_var"),
+            opt("y_var_total"), opt("lpd"), opt("lpd_gauss"))
+    return out, args
+
+
+def _summary_dict(m, out, Y_train_std):
+    """The dict the summary functions return: predict_y / predict_y_var flattened as `predict_y_summary` does, the total variance,
+    and with Y_test the densities, their mean `ll` (and in the data's units: minus log Y_train_std) and the RMSE over the first
+    30 test points (base_model.py:346-348: `predict_y_summary`'s expression on y_mean)."""
+    res = {"predict_y": out["y_mean"].reshape(-1), "predict_y_var": out["y_var"].reshape(-1),
+           "predict_y_var_total": out["y_var_total"].reshape(-1)}
+    if m["Y"] is not None:
+        n30 = min(30, m["n_test"])
+        y30, p30 = m["Y"][:n30].reshape(-1), out["y_mean"][:n30].reshape(-1)
+        res["RMSE"] = float(np.sqrt(np.mean((y30 - p30) ** 2)) * Y_train_std) if n30 else float("nan")
+        ll = float(np.mean(out["lpd"])) if out["lpd"].size else float("nan")
+        res.update(lpd=out["lpd"], lpd_gauss=out["lpd_gauss"], ll=ll, ll_original_units=ll - float(np.log(Y_train_std)))
+    return res
+
+
+def rollout_summary(predict_x, predict_x_var, CC, DD, log_Rchols, Y_test=None, Y_train_std=1.0):
+    """The held-out predictive summary of base_model.py:330-348 on the GPU (`ffvd_op_rollout_summary`): `predict_y_summary`'s
+    predict_y / predict_y_var, and what it lacks -- predict_y_var_total (noise plus the spread of the rollouts: the law of total
+    variance) and, with Y_test (n_test <= steps, J), lpd (n_test, J): the log of the Monte-Carlo predictive density of each held-out
+    point, lpd_gauss: its moment-matched Gaussian counterpart, ll = mean(lpd), ll_original_units and RMSE.
+    predict_x, predict_x_var: (N, steps, D) or (G, R, steps, D); CC (D, J <= 8); DD (J,); log_Rchols (J, J) (row 0 is used) or (J,)."""
+    who = "rollout_summary"
+    px, pv = _lib.as_f64(predict_x), _lib.as_f64(predict_x_var)
+    if px.ndim not in (3, 4) or px.shape != pv.shape:
+        raise ValueError(f"{who}: predict_x and predict_x_var: expected equal shapes (N, steps, D) or (G, R, steps, D), got "
+                         f"{px.shape} and {pv.shape}")
+    steps, D = px.shape[-2:]
+    N = int(np.prod(px.shape[:-2]))
+    if N < 1 or steps < 1 or D < 1:
+        raise ValueError(f"{who}: at least one rollout, one step and one latent dim are needed, got {px.shape}")
+    m = _pack_summary(who, D, steps, CC, DD, log_Rchols, Y_test)
+    out, args = _summary_call(m, steps)
+    rc = _lib.load().ffvd_op_rollout_summary(_lib.dptr(px), _lib.dptr(pv), N, steps, D, *args)
+    _lib.check(rc, None, who)
+    return _summary_dict(m, out, Y_train_std)
+
+
+def rollout_grouped_summary(Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x_lasts, control_inputs, ctrl_offset, steps, Qs, eps, CC, DD,
+                            log_Rchols, Y_test=None, Y_train_std=1.0, *, return_rollouts=False):
+    """`rollout_grouped` and `rollout_summary` over all G * R rollouts in ONE call (`ffvd_op_rollout_grouped_summary`): the summary
+    is formed on the device; the (G, R, steps, D) stacks come down only with return_rollouts (keys predict_x, predict_x_var)."""
+    who = "rollout_grouped_summary"
+    a = _pack_rollout_groups(Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x_lasts, control_inputs, ctrl_offset, steps, Qs, eps)
+    G, R, D = a["G"], a["R"], a["D"]
+    m = _pack_summary(who, D, steps, CC, DD, log_Rchols, Y_test)
+    out, args = _summary_call(m, steps)
+    px, pv = (np.empty((G, R, steps, D)), np.empty((G, R, steps, D))) if return_rollouts else (None, None)
+    opt = lambda x: None if x is None else _lib.dptr(x)
+    rc = _lib.load().ffvd_op_rollout_grouped_summary(*a["args"], opt(px), opt(pv), *args)
+    _lib.check(rc, None, who)
+    res = _summary_dict(m, out, Y_train_std)
+    if return_rollouts:
+        res.update(predict_x=px, predict_x_var=pv)
+    return res
+
+
+def posterior_rollout_grouped_summary(Zs, kerns, Xs, Qs, control_inputs, ctrl_offset, steps, eps, CC, DD, log_Rchols, Y_test=None,
+                                      Y_train_std=1.0, *, jitter=JITTER, groups_per_pass=0, return_rollouts=False, return_U=False):
+    """`posterior_rollout_grouped` and `rollout_summary` over all G * R rollouts in ONE call
+    (`ffvd_op_posterior_rollout_grouped_summary`): posteriors, rollouts and summary stay on the device; the (G, R, steps, D) stacks
+    come down only with return_rollouts (keys predict_x, predict_x_var), U_means (G, M, D) only with return_U."""
+    who = "posterior_rollout_grouped_summary"
+    a = _pack_posterior_rollout(who, Zs, kerns, Xs, Qs, control_inputs, ctrl_offset, steps, eps, jitter, groups_per_pass)
+    G, R, M, D, steps = a["G"], a["R"], a["M"], a["D"], a["steps"]
+    m = _pack_summary(who, D, steps, CC, DD, log_Rchols, Y_test)
+    out, args = _summary_call(m, steps)
+    px, pv = (np.empty((G, R, steps, D)), np.empty((G, R, steps, D))) if return_rollouts else (None, None)
+    U = np.empty((G, M, D)) if return_U else None
+    opt = lambda x: None if x is None else _lib.dptr(x)
+    rc = _lib.load().ffvd_op_posterior_rollout_grouped_summary(*a["args"], opt(px), opt(pv), opt(U), *args)
+    _lib.check(rc, None, who)
+    res = _summary_dict(m, out, Y_train_std)
+    if return_rollouts:
+        res.update(predict_x=px, predict_x_var=pv)
+    if return_U:
+        res["U_means"] = U
+    return res
 
 
 def pg_sweep(Lm_inverse_seq, Z, kern, U_val, X_ref, Y, control_inputs, CC, DD, Rchols, Q, x0, eps, unif):

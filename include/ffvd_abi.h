@@ -516,6 +516,51 @@ int  ffvd_op_posterior_rollout_grouped(int kind, int G, int n_models, const doub
                                        int groups_per_pass, int R, const double *ctrl_roll, int steps, const double *eps,
                                        double *predict_x, double *predict_var, double *U_means);
 
+/* The held-out predictive summary of base_model.py:330-348 over N rollouts, and what it lacks: the total variance and the predictive
+ * log density.  predict_x, predict_var (= f_var + Q, :311): N x steps x D, as the rollout operators return them (G x R x steps x D is
+ * N = G * R); CC D x J, DD J (the emission, :341); noise_std J: s_j > 0, the standard deviation of the emission noise of output j
+ * (the Python layer passes exp(log_Rchols[0, :]), the row the likelihood uses); Y_test n_test x J (NULL when n_test = 0), the
+ * held-out observations of steps t < n_test.  With p[n][t][j] = sum_k predict_x[n][t][k] CC[k][j] (k ascending):
+ *   y_mean[t][j]      = (1/N) sum_n p + DD_j                                          (:341)
+ *   y_var[t][j]       = (1/N) sum_n sum_k predict_var[n][t][k] CC[k][j]^2 + s_j^2     (:342: the mean of the one-step variances)
+ *   y_var_total[t][j] = s_j^2 + (1/N) sum_n (p - pbar)^2     (law of total variance: the noise plus the spread of the rollouts; from
+ *                       centred sums -- Welford per chunk of 32 rollouts, (count, mean, M2) merged pairwise -- never E[p^2] - E[p]^2)
+ *   lpd[t][j]         = log (1/N) sum_n N(Y_test[t][j]; p + DD_j, s_j^2)              (the largest exponent is subtracted before summing)
+ *   lpd_gauss[t][j]   = log N(Y_test[t][j]; y_mean[t][j], y_var_total[t][j])
+ * y_mean, y_var, y_var_total: steps x J; lpd, lpd_gauss: n_test x J; each output may be NULL, at least one must not be.  Per-output
+ * marginals only: no joint density over the J outputs.
+ * Determinism: a wavefront owns 32 rollouts and 64 steps and sums in ascending rollout order, a second launch merges the chunks in
+ * ascending order; no atomics.  The decomposition depends on (N, steps, D, J) only: two calls are bit-identical.
+ * Limits: 1 <= D <= 32, 1 <= J <= 8, 0 <= n_test <= steps, N * steps * D < 2^31, every s_j finite and positive, Y_test given when
+ * n_test > 0 or an lpd output is requested; FFVD_EINVAL otherwise, before any device call.  N = 0 or steps = 0: FFVD_OK, nothing is
+ * touched. */
+int  ffvd_op_rollout_summary(const double *predict_x, const double *predict_var, int N, int steps, int D, const double *CC,
+                             const double *DD, const double *noise_std, int J, const double *Y_test, int n_test, double *y_mean,
+                             double *y_var, double *y_var_total, double *lpd, double *lpd_gauss);
+
+/* ffvd_op_rollout_grouped with the summary of ffvd_op_rollout_summary (base_model.py:330-348) over all N = G * R rollouts, formed on
+ * the device stacks the step launches wrote, before any download.  The arguments of ffvd_op_rollout_grouped, then those of the
+ * summary.  predict_x / predict_var may each be NULL: that stack is then not downloaded, and the summary does not depend on it.
+ * The stacks are bit-identical to ffvd_op_rollout_grouped's, the summary to ffvd_op_rollout_summary's on those stacks.
+ * Limits: those of both.  G = 0 or steps = 0: FFVD_OK, nothing is touched. */
+int  ffvd_op_rollout_grouped_summary(int kind, int G, const double *const *Lm_inverse_seqs, const double *Zs, int M, int P, int D,
+                                     const double *logvariances, const double *loglengthscales, const double *fs,
+                                     const double *const *q_sqrts, const double *x_lasts, int R, const double *ctrl, int C, int steps,
+                                     const double *log_Qs, const double *eps, double *predict_x, double *predict_var,
+                                     const double *CC, const double *DD, const double *noise_std, int J, const double *Y_test,
+                                     int n_test, double *y_mean, double *y_var, double *y_var_total, double *lpd, double *lpd_gauss);
+
+/* ffvd_op_posterior_rollout_grouped with the summary of ffvd_op_rollout_summary (base_model.py:330-348) in the same way: posteriors,
+ * rollouts and summary without anything but the inputs and the steps x J results crossing the host link when predict_x, predict_var
+ * and U_means are NULL. */
+int  ffvd_op_posterior_rollout_grouped_summary(int kind, int G, int n_models, const double *Zs, int M, int P, int D,
+                                               const double *logvariances, const double *loglengthscales, const double *Xs,
+                                               const double *ctrl_fit, int C, int T, const double *log_Qs, double jitter,
+                                               int groups_per_pass, int R, const double *ctrl_roll, int steps, const double *eps,
+                                               double *predict_x, double *predict_var, double *U_means, const double *CC,
+                                               const double *DD, const double *noise_std, int J, const double *Y_test, int n_test,
+                                               double *y_mean, double *y_var, double *y_var_total, double *lpd, double *lpd_gauss);
+
 /* The posterior transition function f(x, c) of G groups at N common inputs: conditional_after_kernel_precalculation
  * (conditionals_multi_output.py:306-387, white=True, full_cov=False) for every group in one launch sequence.  Group g uses model
  * m(g) (n_models = 1: Z, the hyper-parameters and W = L^-T are shared; n_models = G: own).  With F_{m,d} = K_d(Xnew, Z_m) W_{m,d}
