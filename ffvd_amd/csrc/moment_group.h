@@ -1,0 +1,57 @@
+// Moment-matched prediction (moment_group.hip): a Gaussian state x_t ~ N(mu, Sigma) of each of G posteriors is pushed through
+// x_{t+1} = x_t + f(x_t, c_t) + process noise in closed form (SE-ARD kernels only; Girard et al. 2003, the PILCO propagation) and
+// re-approximated as a Gaussian: one launch per step for all groups, no sampling.  DESIGN.md section 9 has the formulas.
+//
+// Limits (the operators return FFVD_EINVAL beyond them): SE kernel, D <= MG_MAXD, D <= P <= 32, M <= 2048, n_models 1 or G,
+//   G * D * Mp * Mp <= 2^29 doubles (the W E and Gamma stacks), Mp = M rounded up to 64;  G * npair * NS < 2^31 (grid x),
+//   npair = D (D + 1) / 2, NS = ceil(M / MG_SLAB);  G * steps * D * D < 2^31.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+
+namespace ffvd {
+
+constexpr int MG_SLAB = 16;          // rows i of the pair tables per workgroup
+constexpr int MG_MAXD = 8;           // latent dims (the D x D elimination runs in one thread)
+
+__host__ __device__ inline int mg_npair(int D) { return D * (D + 1) / 2; }
+__host__ __device__ inline int mg_fields(int D) { return mg_npair(D) + D + D * D; }     // Cov(f) pairs, E[f], Cov(x, f)
+
+struct MomentGroupArgs {
+    int G, n_models, D, C, P, M, Mp, NS, steps;
+    int unit_per_group;      // beta is always per (group, dim); Gamma per (group, dim) (1) or per (model, dim) of a shared model (0)
+    const double *Z;         // [n_models][M][P]
+    const double *variance;  // [n_models][D]
+    const double *len;       // [n_models][D][P]   lengthscales
+    const double *beta;      // [G][D][Mp]         W u
+    const double *gam;       // [units][Mp][Mp]    Gamma = W (I - q q^T) W^T, entries (i, j < M) are read
+    const double *x_last;    // [G][D]
+    const double *S0;        // [G][D][D] or nullptr (zeros)
+    const double *log_Q;     // [G][D]
+    const double *ctrl;      // [steps][C] or nullptr
+    double *part;            // [2][G][fields][NS]: slab sums of a step (step parity)
+    double *state;           // [2][G][D + D * D]: mu, Sigma (step parity)
+    double *m_x;             // [G][steps][D]
+    double *S_x;             // [G][steps][D][D]
+};
+
+// beta[(g * D + d) * Mp + i] = sum_{j < M} W[unit(g, d)][i][j] U[g][j][d], i < M; unit = g * D + d (w_per_group) or d
+void launch_mg_beta(hipStream_t stream, int G, int D, int M, int Mp, int w_per_group, const double *W, const double *U, double *beta);
+// N = I - q and E = (N + N^T) - N N^T (in place over -N N^T) for nq slots of Mp x Mp: I - q q^T without its cancellation
+void launch_mg_nmat(hipStream_t stream, int nq, int M, int Mp, const double *q, double *N);
+void launch_mg_emat(hipStream_t stream, int nq, int M, int Mp, const double *N, double *E);
+// launch t of steps + 1: finishes step t - 1 (t > 0) and forms the slab sums of step t (t < steps)
+void launch_mg_step(hipStream_t stream, const MomentGroupArgs &a, int t);
+
+struct MomentSummaryArgs {
+    int G, steps, D, J, n_test;
+    const double *m, *S;             // [G][steps][D], [G][steps][D][D]
+    const double *CC;                // [D][J]
+    const double *DD, *sd;           // [J]
+    const double *Y;                 // [n_test][J] or nullptr
+    double *out;                     // [5][steps][J]: y_mean, y_var (= y_var_total), y_var_total, lpd, lpd_gauss (rows t < n_test)
+};
+void launch_moment_summary(hipStream_t stream, const MomentSummaryArgs &a);
+
+}  // namespace ffvd

@@ -9,6 +9,7 @@
 #include "posterior_group.h"
 #include "conditional_group.h"
 #include "predict_summary.h"
+#include "moment_group.h"
 
 #include <atomic>
 #include <chrono>
@@ -1686,4 +1687,206 @@ extern "C" int ffvd_op_posterior_conditional_grouped(int kind, int G, int n_mode
     if (U_means && !sc.download(U_means, w.U, GD * M * sizeof(double)))
         return set_error(nullptr, FFVD_EDEVICE, "ffvd_op_posterior_conditional_grouped: copying the results back failed");
     return FFVD_OK;
+}
+
+// ---- moment-matched prediction (moment_group.h) ---------------------------------------------------------------------------------------
+// A Gaussian state of each of G posteriors pushed through x_{t+1} = x_t + f(x_t, c_t) + noise in closed form (SE-ARD only), one launch
+// per step for all groups; optionally summarised as a held-out prediction before anything comes down.
+namespace {
+// scalar-argument checks shared by the two entry points (before any device call)
+bool mg_scalars_ok(int kind, int G, int n_models, int M, int P, int D, int C, int steps, int q_mode) {
+    if (!(kind == FFVD_KERNEL_SE && G >= 0 && steps >= 0 && M >= 1 && M <= 2048 && D >= 1 && D <= MG_MAXD && C >= 0 && P == D + C &&
+          P <= MAXP && (q_mode == 0 || q_mode == 1) && (n_models == 1 || n_models == G) && (long long)G * D <= (1LL << 24)))
+        return false;
+    const long long Mp = round_up(M, NB), NS = (M + MG_SLAB - 1) / MG_SLAB;
+    return (long long)G * D * Mp * Mp <= (1LL << 29) && (long long)G * mg_npair(D) * NS < (1LL << 31) &&
+           (steps == 0 || G <= ((1LL << 31) - 1) / steps / D / D);
+}
+// the trailing summary block of the entry points: asked for when anything in it is given
+bool mg_summary_wanted(const SummaryReq &q) {
+    return q.CC || q.DD || q.noise_std || q.J != 0 || q.Y_test || q.n_test != 0 || q.y_mean || q.y_var || q.y_var_total || q.lpd || q.lpd_gauss;
+}
+
+// the summary launch of moment_group.h on stacks that are on the device, then the requested outputs come down (one small copy)
+int mg_summary(Scratch &sc, const std::string &who, const double *dm, const double *dS, int G, int steps, int D, const SummaryReq &q) {
+    const int J = q.J;
+    const size_t SJ = (size_t)steps * J, TJ = (size_t)q.n_test * J;
+    MomentSummaryArgs a{};
+    a.G = G; a.steps = steps; a.D = D; a.J = J; a.n_test = q.n_test; a.m = dm; a.S = dS;
+    a.CC = sc.upload(q.CC, (size_t)D * J); a.DD = sc.upload(q.DD, J); a.sd = sc.upload(q.noise_std, J);
+    a.Y = q.n_test ? sc.upload(q.Y_test, TJ) : nullptr;
+    a.out = sc.alloc<double>(5 * SJ);
+    if (!a.CC || !a.DD || !a.sd || (q.n_test && !a.Y) || !a.out)
+        return set_error(nullptr, FFVD_ENOMEM, who + ": device allocation or upload failed");
+    launch_moment_summary(sc.stream, a);
+    OP_TRY(hipGetLastError());
+    std::vector<double> &h = sc.host(5 * SJ);
+    OP_TRY(hipMemcpyAsync(h.data(), a.out, h.size() * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
+    OP_TRY(hipStreamSynchronize(sc.stream));
+    double *const dst[5] = {q.y_mean, q.y_var, q.y_var_total, q.lpd, q.lpd_gauss};
+    for (int f = 0; f < 5; ++f)
+        if (dst[f]) memcpy(dst[f], h.data() + f * SJ, (f < 3 ? SJ : TJ) * sizeof(double));
+    return FFVD_OK;
+}
+
+// Operands on the device -> beta, Gamma, the step launches, the summary, the downloads.  dW: [n_models * D] slots of Mp x Mp (upper
+// triangular, zero padded); dq: nullptr, or [G] (q_mode 0) / [G * D] (q_mode 1) slots of Mp x Mp; hv: variance / len per (model, dim).
+int mg_run(Scratch &sc, const std::string &who, int G, int nm, int M, int P, int D, int C, int steps, const HyperView &hv, const double *dZ,
+           const double *dW, const double *dq, int q_mode, const double *dU, const double *dxl, const double *dS0, const double *dlq,
+           const double *dctrl, double *m_x, double *S_x, const SummaryReq *sum) {
+    const int Mp = round_up(M, NB), NS = (M + MG_SLAB - 1) / MG_SLAB, nK = nm * D, GD = G * D;
+    const size_t mm = (size_t)Mp * Mp, nm_x = (size_t)G * steps * D, nS_x = nm_x * D;
+    const int units = dq ? GD : nK, nq = dq ? (q_mode ? GD : G) : 0;
+    double *beta = sc.alloc<double>((size_t)GD * Mp), *gam = sc.alloc<double>((size_t)units * mm);
+    double *dN = dq ? sc.alloc<double>((size_t)nq * mm) : nullptr, *dE = dq ? sc.alloc<double>((size_t)nq * mm) : nullptr;
+    double *dWE = dq ? sc.alloc<double>((size_t)GD * mm) : nullptr;
+    double *unused = sc.alloc<double>((size_t)(nq > units ? nq : units));          // (cov.hip reads a variance per slot for its seed: none here)
+    double *part = sc.alloc<double>((size_t)2 * G * mg_fields(D) * NS), *state = sc.alloc<double>((size_t)2 * G * (D + D * D));
+    double *dm = sc.alloc<double>(nm_x), *dS = sc.alloc<double>(nS_x);
+    OP_CHECK_AS(beta && gam && (!dq || (dN && dE && dWE)) && unused && part && state && dm && dS, who);
+    launch_mg_beta(sc.stream, G, D, M, Mp, nm == G, dW, dU, beta);
+    // Gamma = W (I - q q^T) W^T through cov.hip's product body.  COV_GEN: C = A B^T, all Mp x Mp entries written.
+    CovArgs gen{};
+    gen.mode = COV_GEN; gen.a_stride = mm; gen.lda = Mp; gen.arows = Mp; gen.K = Mp; gen.ldb = Mp; gen.brows = Mp; gen.ncols = Mp;
+    gen.c_stride = mm; gen.ldc = Mp;
+    auto product = [&](const double *A, const double *B, size_t b_stride, double *Cdst, int n) {
+        for (int u0 = 0; u0 < n; u0 += 32768) {                                       // (grid y)
+            gen.A = A + (size_t)u0 * mm; gen.B = B + (size_t)u0 * b_stride; gen.b_stride = b_stride; gen.C = Cdst + (size_t)u0 * mm;
+            gen.nb = n - u0 < 32768 ? n - u0 : 32768;
+            launch_cov(sc.stream, gen);
+        }
+    };
+    if (!dq) product(dW, dW, mm, gam, nK);                                            // W W^T per (model, dim)
+    else {
+        // E = I - q q^T as (N + N^T) - N N^T with N = I - q: no cancellation where q is close to the identity, which is where W is
+        // large.  -N N^T: the symmetric product C = seed - A A^T with an empty seed (a LinearK seed over P = 0 columns is an exact zero).
+        OP_TRY(hipMemsetAsync(dE, 0, (size_t)nq * mm * sizeof(double), sc.stream));
+        CovArgs sym{};
+        sym.mode = COV_SYM; sym.a_stride = mm; sym.lda = Mp; sym.arows = Mp; sym.K = Mp; sym.c_stride = mm; sym.ldc = Mp; sym.N = M;
+        sym.kind = FFVD_KERNEL_LINEAR; sym.P = 0; sym.variance = unused; sym.len = hv.len;
+        for (int u0 = 0; u0 < nq; u0 += 32768) {
+            const int n = nq - u0 < 32768 ? nq - u0 : 32768;
+            launch_mg_nmat(sc.stream, n, M, Mp, dq + (size_t)u0 * mm, dN + (size_t)u0 * mm);
+            sym.A = dN + (size_t)u0 * mm; sym.C = dE + (size_t)u0 * mm; sym.nb = n;
+            launch_cov(sc.stream, sym);
+            launch_mg_emat(sc.stream, n, M, Mp, dN + (size_t)u0 * mm, dE + (size_t)u0 * mm);
+        }
+        // (W E) W^T per (group, dim); E is symmetric, so W E = W E^T.  One launch pair per group: a group's W and E slots are
+        // contiguous whichever of them is shared
+        for (int g = 0; g < G; ++g) {
+            const double *Wg = dW + (nm == G ? (size_t)g * D * mm : 0);
+            double *WEg = dWE + (size_t)g * D * mm;
+            product(Wg, q_mode ? dE + (size_t)g * D * mm : dE + (size_t)g * mm, q_mode ? mm : 0, WEg, D);
+            product(WEg, Wg, mm, gam + (size_t)g * D * mm, D);
+        }
+    }
+    MomentGroupArgs a{};
+    a.G = G; a.n_models = nm; a.D = D; a.C = C; a.P = P; a.M = M; a.Mp = Mp; a.NS = NS; a.steps = steps; a.unit_per_group = dq ? 1 : 0;
+    a.Z = dZ; a.variance = hv.variance; a.len = hv.len; a.beta = beta; a.gam = gam; a.x_last = dxl; a.S0 = dS0; a.log_Q = dlq;
+    a.ctrl = dctrl; a.part = part; a.state = state; a.m_x = dm; a.S_x = dS;
+    for (int t = 0; t <= steps; ++t) launch_mg_step(sc.stream, a, t);
+    OP_TRY(hipGetLastError());
+    if (sum)
+        if (int rc = mg_summary(sc, who, dm, dS, G, steps, D, *sum)) return rc;
+    if ((m_x && !sc.download(m_x, dm, nm_x * sizeof(double))) || (S_x && !sc.download(S_x, dS, nS_x * sizeof(double))))
+        return set_error(nullptr, FFVD_EDEVICE, who + ": copying the results back failed");
+    OP_TRY(hipStreamSynchronize(sc.stream));
+    return FFVD_OK;
+}
+}  // namespace
+
+// Posteriors given by the caller (also explicit-U models and SG-HMC samples of U: q_sqrts = NULL)
+extern "C" int ffvd_op_moment_grouped(int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M, int P,
+                                      int D, const double *logvariances, const double *loglengthscales, const double *fs,
+                                      const double *const *q_sqrts, int q_mode, const double *x_lasts, const double *S0s,
+                                      const double *ctrl, int C, int steps, const double *log_Qs, double *m_x, double *S_x,
+                                      const double *CC, const double *DD, const double *noise_std, int J, const double *Y_test, int n_test,
+                                      double *y_mean, double *y_var, double *y_var_total, double *lpd, double *lpd_gauss) {
+    const std::string who = "ffvd_op_moment_grouped", bad = who + ": bad argument";
+    const SummaryReq q{CC, DD, noise_std, J, Y_test, n_test, y_mean, y_var, y_var_total, lpd, lpd_gauss};
+    const SummaryReq *sum = mg_summary_wanted(q) ? &q : nullptr;
+    if (kind != FFVD_KERNEL_SE) return set_error(nullptr, FFVD_EINVAL, bad + " (moment matching is closed-form for the SE kernel only)");
+    if (!mg_scalars_ok(kind, G, n_models, M, P, D, C, steps, q_mode) || (sum && !summary_scalars_ok(q, G, steps, D)))
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    if (G == 0 || steps == 0) return FFVD_OK;
+    if (!Lm_inverse_seqs || !Zs || !logvariances || !loglengthscales || !fs || !x_lasts || !log_Qs || (C > 0 && !ctrl) ||
+        (!sum && (!m_x || !S_x)) || (sum && !summary_arrays_ok(q)))
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    const size_t nK = (size_t)n_models * D, GD = (size_t)G * D, nq = q_sqrts ? (q_mode ? GD : (size_t)G) : 0;
+    for (size_t b = 0; b < nK; ++b) if (!Lm_inverse_seqs[b]) return set_error(nullptr, FFVD_EINVAL, bad);
+    for (size_t b = 0; b < nq; ++b) if (!q_sqrts[b]) return set_error(nullptr, FFVD_EINVAL, bad);
+    OP_BEGIN_AS(who);
+    const int Mp = round_up(M, NB);
+    double *dW = upload_matrix_table(sc, Lm_inverse_seqs, nK, M, Mp), *dq = nq ? upload_matrix_table(sc, q_sqrts, nq, M, Mp) : nullptr;
+    double *dZ = sc.upload(Zs, (size_t)n_models * M * P), *dU = sc.upload(fs, GD * M), *dxl = sc.upload(x_lasts, GD);
+    double *dS0 = S0s ? sc.upload(S0s, GD * D) : nullptr, *dlq = sc.upload(log_Qs, GD), *dctrl = C ? sc.upload(ctrl, (size_t)steps * C) : nullptr;
+    double *dlv = sc.upload(logvariances, nK), *dll = sc.upload(loglengthscales, nK * P);
+    double *variance = sc.alloc<double>(nK), *len = sc.alloc<double>(nK * P), *Zsc = sc.alloc<double>(nK * Mp * P), *zz = sc.alloc<double>(nK * Mp);
+    OP_CHECK_AS(dW && (!nq || dq) && dZ && dU && dxl && (!S0s || dS0) && dlq && (!C || dctrl) && dlv && dll && variance && len && Zsc && zz, who);
+    launch_rg_prep(sc.stream, kind, n_models, D, M, Mp, P, dZ, dlv, dll, variance, len, Zsc, zz);
+    return mg_run(sc, who, G, n_models, M, P, D, C, steps, HyperView{variance, len, Zsc, zz}, dZ, dW, dq, q_mode, dU, dxl, dS0, dlq,
+                  dctrl, m_x, S_x, sum);
+}
+
+// The collapsed posteriors of ffvd_op_posterior_grouped (base_model.py:243-256) propagated without leaving the device: L^-T is packed
+// from the K_uu slabs, U_mean is read where the matvec left it, the q slices are packed by launch_pg_pack (exact zeros in the padding
+// and the strict lower triangle), the start means are the last rows of Xs.
+extern "C" int ffvd_op_posterior_moment_grouped(int kind, int G, int n_models, const double *Zs, int M, int P, int D,
+                                                const double *logvariances, const double *loglengthscales, const double *Xs,
+                                                const double *ctrl_fit, int C, int T, const double *log_Qs, double jitter,
+                                                int groups_per_pass, int q_mode, const double *S0s, const double *ctrl_roll, int steps,
+                                                double *m_x, double *S_x, double *U_means, const double *CC, const double *DD,
+                                                const double *noise_std, int J, const double *Y_test, int n_test, double *y_mean,
+                                                double *y_var, double *y_var_total, double *lpd, double *lpd_gauss) {
+    const std::string whos = "ffvd_op_posterior_moment_grouped", bad = whos + ": bad argument";
+    const char *who = "ffvd_op_posterior_moment_grouped";
+    const SummaryReq q{CC, DD, noise_std, J, Y_test, n_test, y_mean, y_var, y_var_total, lpd, lpd_gauss};
+    const SummaryReq *sum = mg_summary_wanted(q) ? &q : nullptr;
+    if (kind != FFVD_KERNEL_SE) return set_error(nullptr, FFVD_EINVAL, bad + " (moment matching is closed-form for the SE kernel only)");
+    if (!pg_scalars_ok(kind, G, n_models, M, P, D, C, T, groups_per_pass, jitter) || !mg_scalars_ok(kind, G, n_models, M, P, D, C, steps, q_mode) ||
+        (sum && !summary_scalars_ok(q, G, steps, D)))
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    if (G == 0 || steps == 0) return FFVD_OK;
+    if (!Zs || !logvariances || !loglengthscales || !Xs || !log_Qs || (C > 0 && (!ctrl_fit || !ctrl_roll)) || (!sum && (!m_x || !S_x)) ||
+        (sum && !summary_arrays_ok(q)))
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    OP_BEGIN_AS(whos);
+    PgIn in{who, kind, G, n_models, M, P, D, C, T, groups_per_pass, Zs, logvariances, loglengthscales, Xs, ctrl_fit, log_Qs, jitter};
+    PgWork w{};
+    const int Mp = round_up(M, NB), nK = n_models * D;
+    const size_t GD = (size_t)G * D, mm = (size_t)Mp * Mp;
+    if (q_mode) w.qall = sc.alloc<double>(GD * mm);
+    else { w.Mp16 = Mp; w.q0 = sc.alloc<double>((size_t)G * mm); }
+    double *dW = sc.alloc<double>((size_t)nK * mm), *dxl = sc.alloc<double>(GD);
+    OP_CHECK_AS((w.qall || w.q0) && dW && dxl, whos);
+    if (int rc = pg_posterior(sc, in, w)) return rc;
+    double *dZ = sc.upload(Zs, (size_t)n_models * M * P), *dS0 = S0s ? sc.upload(S0s, GD * D) : nullptr;
+    double *dctrl = C ? sc.upload(ctrl_roll, (size_t)steps * C) : nullptr;
+    OP_CHECK_AS(dZ && (!S0s || dS0) && (!C || dctrl), whos);
+    launch_pg_pack(sc.stream, w.Kuu, 2 * mm, Mp, Mp, nK, 1, M, 1, dW, Mp, Mp, nK);
+    launch_pg_x_last(sc.stream, w.Xs, G, T, D, dxl);
+    if (int rc = mg_run(sc, whos, G, n_models, M, P, D, C, steps, w.hv, dZ, dW, q_mode ? w.qall : w.q0, q_mode, w.U, dxl, dS0, w.log_Qs,
+                        dctrl, m_x, S_x, sum))
+        return rc;
+    if (U_means && !sc.download(U_means, w.U, GD * M * sizeof(double)))
+        return set_error(nullptr, FFVD_EDEVICE, whos + ": copying the results back failed");
+    return FFVD_OK;
+}
+
+// The summary of the moment-matched prediction for stacks the caller holds: they are uploaded, summarised by the same launch as in the
+// two calls above
+extern "C" int ffvd_op_moment_summary(const double *m_x, const double *S_x, int G, int steps, int D, const double *CC, const double *DD,
+                                      const double *noise_std, int J, const double *Y_test, int n_test, double *y_mean, double *y_var,
+                                      double *y_var_total, double *lpd, double *lpd_gauss) {
+    const std::string who = "ffvd_op_moment_summary", bad = who + ": bad argument";
+    const SummaryReq q{CC, DD, noise_std, J, Y_test, n_test, y_mean, y_var, y_var_total, lpd, lpd_gauss};
+    if (!summary_scalars_ok(q, G, steps, D) || D > MG_MAXD || (G > 0 && steps > 0 && G > ((1LL << 31) - 1) / steps / D / D))
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    if (G == 0 || steps == 0) return FFVD_OK;
+    if (!m_x || !S_x || !summary_arrays_ok(q)) return set_error(nullptr, FFVD_EINVAL, bad);
+    OP_BEGIN_AS(who);
+    const size_t n = (size_t)G * steps * D;
+    double *dm = sc.upload(m_x, n), *dS = sc.upload(S_x, n * D);
+    OP_CHECK_AS(dm && dS, who);
+    return mg_summary(sc, who, dm, dS, G, steps, D, q);
 }

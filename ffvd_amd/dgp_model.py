@@ -481,22 +481,29 @@ class DGPSSM:
         out.update(predict_x=px, predict_x_var=pv, U_vals=U_vals)
         return out
 
-    def evaluate_heldout(self, Y_test, control_inputs, num_per_chain, *, Y_train_std=1.0, eps=None, seed=None):
+    def evaluate_heldout(self, Y_test, control_inputs, num_per_chain, *, Y_train_std=1.0, eps=None, seed=None, method="rollouts"):
         """Held-out metrics of the model as it stands: `num_per_chain` rollouts of len(Y_test) steps from every chain's X_s[-1],
         summarised on the device (prediction.rollout_summary has the quantities) -- no trajectory is downloaded.
         Collapsed U: ONE `posterior_rollout_grouped_summary` call with G = S and the model shared by the groups.  Explicit U:
         `kernel_pre_cal` once, then `rollout_grouped_summary` with the shared U and no q_sqrt.
         `eps` (len(Y_test), S, num_per_chain, D) injects the draws of base_model.py:306 (else numpy's default_rng(seed): the model's
         own generator is not advanced).  Parameters newer on the device than on the host are pulled first.
+        method "moment" replaces the rollouts by the moment-matched prediction (`predict_moments`): deterministic, one pass of
+        len(Y_test) launches; num_per_chain, eps and seed are ignored, and predict_y_var equals predict_y_var_total.
         Returns a dict: RMSE (first 30 test points, base_model.py:346-348), ll (mean log predictive density), ll_original_units,
         and the per-step arrays predict_y, predict_y_var, predict_y_var_total, lpd, lpd_gauss."""
         from . import conditionals_multi_output as cmo
         from .prediction import posterior_rollout_grouped_summary, rollout_grouped_summary
+        if method not in ("rollouts", "moment"):
+            raise ValueError(f"evaluate_heldout: method: expected 'rollouts' or 'moment', got {method!r}")
         Y_test = np.asarray(Y_test, dtype=np.float64)
         if Y_test.ndim == 1:
             Y_test = Y_test[:, None]
         if Y_test.ndim != 2 or Y_test.shape[0] < 1 or Y_test.shape[1] != self.Y.shape[1]:
             raise ValueError(f"evaluate_heldout: Y_test: expected (n_test >= 1, {self.Y.shape[1]}), got {Y_test.shape}")
+        if method == "moment":
+            out = self.predict_moments(control_inputs, Y_test.shape[0], Y_test=Y_test, Y_train_std=Y_train_std)
+            return {k: v for k, v in out.items() if k not in ("m_x", "S_x")}          # the keys of the default method
         if self._host_stale:
             self.pull_parameters()
         S, D, R, steps = self.num_chains, self.output_dim, int(num_per_chain), Y_test.shape[0]
@@ -516,6 +523,37 @@ class DGPSSM:
         return rollout_grouped_summary([Lm] * S, [lay.Z] * S, [lay.kernel] * S, [lay.U] * S, None,
                                        [self._X_chains[s_][-1] for s_ in range(S)], ci, n_train, steps, [self.Q] * S, eps,
                                        lik.CC, lik.DD, lik.log_Rchols, Y_test, Y_train_std)
+
+    def predict_moments(self, control_inputs, test_len, *, Y_test=None, Y_train_std=1.0, q_mode="reference"):
+        """Moment-matched held-out prediction: from every chain's X_s[-1] with zero start covariance, the Gaussian state is pushed
+        test_len steps through the learned transition in closed form (prediction.moment_grouped has the method; SquaredExponential
+        kernels only) and summarised on the device (prediction.moment_summary has the quantities) -- deterministic, no rollouts.
+        Collapsed U: ONE `posterior_moment_grouped_summary` call with G = S and the model shared by the groups; q_mode as
+        `predict_transition`.  Explicit U: `kernel_pre_cal` once, then `moment_grouped_summary` with the shared U and no q_sqrt.
+        control_inputs None: the model's own; rows [n_train, n_train + test_len) feed the steps.  Parameters newer on the device
+        than on the host are pulled first.
+        Returns the dict of `evaluate_heldout` (without Y_test: predict_y, predict_y_var, predict_y_var_total only) plus m_x
+        (S, test_len, D) and S_x (S, test_len, D, D), the state moments of every chain."""
+        from . import conditionals_multi_output as cmo
+        from .prediction import moment_grouped_summary, posterior_moment_grouped_summary
+        if q_mode not in cmo.Q_MODES:
+            raise ValueError(f"predict_moments: q_mode: expected one of {sorted(cmo.Q_MODES)}, got {q_mode!r}")
+        steps = int(test_len)
+        if steps < 1:
+            raise ValueError("predict_moments: test_len must be at least 1")
+        if self._host_stale:
+            self.pull_parameters()
+        S = self.num_chains
+        ci = self.control_inputs if control_inputs is None else np.asarray(control_inputs, dtype=np.float64)
+        lay, lik, n_train = self.layers[-1], self.likelihood, self.Y.shape[0]
+        if self.U_collapse:
+            return posterior_moment_grouped_summary(lay.Z, lay.kernel, [self._X_chains[s_] for s_ in range(S)], self.Q, ci, n_train,
+                                                    steps, lik.CC, lik.DD, lik.log_Rchols, Y_test, Y_train_std, q_mode=q_mode,
+                                                    return_moments=True)
+        Lm = cmo.kernel_pre_cal(lay.Z, lay.kernel)
+        return moment_grouped_summary(Lm, lay.Z, lay.kernel, [lay.U] * S, None, [self._X_chains[s_][-1] for s_ in range(S)], ci,
+                                      n_train, steps, self.Q, lik.CC, lik.DD, lik.log_Rchols, Y_test, Y_train_std, q_mode=q_mode,
+                                      return_moments=True)
 
     def predict_transition(self, Xnew, *, q_mode="reference", per_chain=True):
         """The learned transition function at inputs of the caller's choice: mean and variance of the posterior GP increment

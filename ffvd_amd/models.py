@@ -38,12 +38,15 @@ class Model:
             raise Exception("Invalid prior type")    # models.py:35-41
 
     def _fit(self, Y_train, lik, kernel_type, kernel_train_flag, iterations=None, epsilon=0.01, Y_test=None, eval_every=0,
-             eval_rollouts=8, Y_train_std=1.0, **kwargs):
+             eval_rollouts=8, Y_train_std=1.0, eval_method="rollouts", **kwargs):
         """eval_every = k > 0 with Y_test: after every k-th round `DGPSSM.evaluate_heldout` (eval_rollouts rollouts per chain, on
         the device) appends its RMSE and mean log predictive density to rmse_seq / ll_seq (models.py:89-92 creates them).  Its
         noise comes from a generator of its own, seeded with the round: the training noise stream is not touched.  The default 0
-        leaves the loop exactly as it is."""
+        leaves the loop exactly as it is.  eval_method "moment": the moment-matched prediction instead of rollouts (deterministic;
+        eval_rollouts and the seed are then unused)."""
         eval_every = int(eval_every)
+        if eval_method not in ("rollouts", "moment"):
+            raise ValueError(f"eval_method: expected 'rollouts' or 'moment', got {eval_method!r}")
         if eval_every < 0:
             raise ValueError("eval_every must not be negative")
         if eval_every and Y_test is None:
@@ -100,7 +103,8 @@ class Model:
             t = self.model.train_hypers()                                        # models.py:168
             self.nll_seq.append(t["nll"])
             if eval_every and self.global_step % eval_every == 0:
-                ev = self.model.evaluate_heldout(Y_test, None, eval_rollouts, Y_train_std=Y_train_std, seed=self.global_step)
+                ev = self.model.evaluate_heldout(Y_test, None, eval_rollouts, Y_train_std=Y_train_std, seed=self.global_step,
+                                                 method=eval_method)
                 self.rmse_seq.append(ev["RMSE"])
                 self.ll_seq.append(ev["ll"])
         if n_iter:
@@ -114,13 +118,14 @@ class RegressionModel(Model):
 
     def fit(self, Y_train, Y_test=None, tensorboard_savepath="", dataname="", fileid="",
             kernel_type="SquaredExponential", kernel_train_flag=True, likelihood_traning=True, X_train=None,
-            X_test=None, Ystd=None, data_uu=None, epsilon=0.01, iterations=None, eval_every=0, eval_rollouts=8, **kwargs):
+            X_test=None, Ystd=None, data_uu=None, epsilon=0.01, iterations=None, eval_every=0, eval_rollouts=8,
+            eval_method="rollouts", **kwargs):
         """models.py:319-322.  `iterations`: number of (sghmc_step, [gp_x_sampling,] train_hypers) rounds; the default
         None = 2 * ARGS.iterations as models.py:142, so the reference's call (FFVD_Main.py:343) trains; 0 builds the model
         and evaluates the initial nll only.  eval_every = k > 0 (with Y_test): held-out RMSE and log predictive density every k
         rounds into rmse_seq / ll_seq (`_fit`), from eval_rollouts rollouts per chain; Ystd, one standard deviation for all outputs (as
         base_model.py:348's Y_train_std; ValueError for more than one entry), scales that RMSE.  Without eval_every Ystd is
-        ignored, as before."""
+        ignored, as before.  eval_method: "rollouts" (the default) or "moment", passed to `DGPSSM.evaluate_heldout` as `method`."""
         Y_train_std = 1.0
         if eval_every and Ystd is not None:
             std = np.asarray(Ystd, dtype=np.float64).reshape(-1)
@@ -136,4 +141,4 @@ class RegressionModel(Model):
                        likelihood_traning=likelihood_traning)                     # models.py:320
         return self._fit(Y_train, lik, kernel_type, kernel_train_flag, iterations=iterations, epsilon=epsilon,
                          Y_test=Y_test if eval_every else None, eval_every=eval_every, eval_rollouts=eval_rollouts,
-                         Y_train_std=Y_train_std, **kwargs)
+                         Y_train_std=Y_train_std, eval_method=eval_method, **kwargs)

@@ -11,7 +11,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _lib
-from .conditionals_multi_output import JITTER, check_conditional_query, pack_posterior_groups
+from .conditionals_multi_output import JITTER, Q_MODES, check_conditional_query, pack_posterior_groups
 from .kernels import stack_hypers
 
 
@@ -339,6 +339,233 @@ def posterior_rollout_grouped_summary(Zs, kerns, Xs, Qs, control_inputs, ctrl_of
     res = _summary_dict(m, out, Y_train_std)
     if return_rollouts:
         res.update(predict_x=px, predict_x_var=pv)
+    if return_U:
+        res["U_means"] = U
+    return res
+
+
+MOMENT_MAX_D, MOMENT_MAX_P, MOMENT_MAX_M = 8, 32, 2048
+
+
+def _moment_limits(who, kind, M, P, D):
+    """The limits of the moment-matched prediction that depend on the model alone (before the library is loaded)."""
+    if kind != 0:
+        raise ValueError(f"{who}: moment matching is closed-form for the SquaredExponential kernel only (LinearK is rejected)")
+    if not 1 <= D <= MOMENT_MAX_D or not D <= P <= MOMENT_MAX_P or not 1 <= M <= MOMENT_MAX_M:
+        raise ValueError(f"{who}: expected D <= {MOMENT_MAX_D}, D <= P <= {MOMENT_MAX_P}, M <= {MOMENT_MAX_M}, got D = {D}, P = {P}, M = {M}")
+
+
+def _moment_run_args(who, G, D, C, control_inputs, ctrl_offset, steps, S0s, q_mode):
+    """q_mode code, start covariances (G, D, D) or None, and the control rows of the propagation, checked."""
+    if q_mode not in Q_MODES:
+        raise ValueError(f"{who}: q_mode: expected one of {sorted(Q_MODES)}, got {q_mode!r}")
+    steps, ctrl_offset = int(steps), int(ctrl_offset)
+    if steps < 0 or ctrl_offset < 0:
+        raise ValueError(f"{who}: steps and ctrl_offset must not be negative")
+    S0 = None
+    if S0s is not None:
+        S0 = _lib.as_f64(S0s, (G, D, D), "S0s")
+        if not np.all(np.isfinite(S0)) or not np.array_equal(S0, np.swapaxes(S0, 1, 2)):
+            raise ValueError(f"{who}: S0s: every start covariance must be finite and exactly symmetric")
+    ctrl = None
+    if C > 0:
+        ci = _lib.as_f64(control_inputs)
+        if ci.ndim != 2 or ci.shape[1] != C or ci.shape[0] < ctrl_offset + steps:
+            raise ValueError(f"{who}: control_inputs: need at least {ctrl_offset + steps} rows of {C} columns")
+        ctrl = np.ascontiguousarray(ci[ctrl_offset: ctrl_offset + steps])
+    return Q_MODES[q_mode], S0, ctrl, steps
+
+
+def _pack_moment_groups(who, Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x_lasts, control_inputs, ctrl_offset, steps, Qs, S0s, q_mode):
+    """Shape checks and packing of `moment_grouped`'s arguments (before the library is loaded): the arguments of
+    `ffvd_op_moment_grouped` up to log_Qs, and the shapes."""
+    G = len(U_vals)
+    if G < 1:
+        raise ValueError(f"{who}: at least one group is needed")
+    one_model = len(kerns) > 0 and not isinstance(kerns[0], (list, tuple))
+    if one_model:
+        if np.ndim(Zs) != 2:
+            raise ValueError(f"{who}: Zs: one list of kernels goes with one (M, P) array, got an array of {np.ndim(Zs)} dimensions")
+        Zl, kl, Wl = [Zs], [kerns], [Lm_inverse_seqs]
+    else:
+        Zl, kl, Wl = list(Zs), list(kerns), list(Lm_inverse_seqs)
+        if len(Zl) != len(kl) or len(Wl) != len(kl):
+            raise ValueError(f"{who}: expected {len(kl)} models (one per kernel list), got {len(Zl)} Zs and {len(Wl)} Lm_inverse_seqs")
+    nm = len(kl)
+    if nm not in (1, G):
+        raise ValueError(f"{who}: n_models: expected 1 or {G} (one per group of U_vals), got {nm}")
+    hy = [stack_hypers(k) for k in kl]
+    kind, D = hy[0][0], len(kl[0])
+    Z0 = np.asarray(Zl[0])
+    if Z0.ndim != 2:
+        raise ValueError(f"{who}: Zs[0]: expected (M, P), got {Z0.shape}")
+    M, P = Z0.shape
+    if any(h[0] != kind for h in hy):
+        raise ValueError(f"{who}: every group must use the same kernel type")
+    _moment_limits(who, kind, M, P, D)
+    C = P - D
+    qm, S0, ctrl, steps = _moment_run_args(who, G, D, C, control_inputs, ctrl_offset, steps, S0s, q_mode)
+    if len(x_lasts) != G:
+        raise ValueError(f"{who}: x_lasts: expected {G} groups, got {len(x_lasts)}")
+    Z, logvar, loglen = np.empty((nm, M, P)), np.empty((nm, D)), np.empty((nm, D, P))
+    Wm, qmats = [], []                                   # (keeps the matrices alive until the call returns)
+    for m in range(nm):
+        if len(kl[m]) != D:
+            raise ValueError(f"{who}: kerns[{m}]: expected {D} kernels (one per latent dim), got {len(kl[m])}")
+        Z[m] = _lib.as_f64(Zl[m], (M, P), f"Zs[{m}]")
+        logvar[m] = _lib.as_f64(hy[m][2], (D,), f"kerns[{m}] logvariance")
+        loglen[m] = _lib.as_f64(hy[m][3], (D, P), f"kerns[{m}] loglengthscales")
+        if len(Wl[m]) != D:
+            raise ValueError(f"{who}: Lm_inverse_seqs[{m}]: expected {D} matrices, got {len(Wl[m])}")
+        for d in range(D):
+            Wm.append(_lib.as_f64(Wl[m][d], (M, M), f"Lm_inverse_seqs[{m}][{d}]"))
+    f, xl = np.empty((G, M, D)), np.empty((G, D))
+    for g in range(G):
+        f[g] = _lib.as_f64(U_vals[g], (M, D), f"U_vals[{g}]")
+        xl[g] = _lib.as_f64(x_lasts[g], (D,), f"x_lasts[{g}]")
+    Qa = np.asarray(Qs, dtype=np.float64)
+    if Qa.shape == (D,):
+        Qa = np.broadcast_to(Qa, (G, D))
+    if Qa.shape != (G, D):
+        raise ValueError(f"{who}: Qs: expected {G} groups of ({D},), got {Qa.shape}")
+    log_Q = np.ascontiguousarray(np.log(Qa))
+    if q_sqrts is not None:
+        if len(q_sqrts) != G:
+            raise ValueError(f"{who}: q_sqrts: expected None or {G} groups, got {len(q_sqrts)}")
+        for g in range(G):
+            q = np.asarray(q_sqrts[g], dtype=np.float64)
+            if q.shape != (D, M, M):
+                raise ValueError(f"{who}: q_sqrts[{g}]: expected ({D}, {M}, {M}), got {q.shape}")
+            qmats.extend(np.ascontiguousarray(q[d]) for d in (range(D) if qm else (0,)))
+    import ctypes
+    Wt = (ctypes.c_void_p * len(Wm))(*[w.ctypes.data for w in Wm])
+    qt = (ctypes.c_void_p * len(qmats))(*[q.ctypes.data for q in qmats]) if q_sqrts is not None else None
+    dp = _lib.dptr
+    opt = lambda x: None if x is None else dp(x)
+    args = (kind, G, nm, Wt, dp(Z), M, P, D, dp(logvar), dp(loglen), dp(f), qt, qm, dp(xl), opt(S0), opt(ctrl), C, steps, dp(log_Q))
+    return dict(args=args, G=G, M=M, D=D, steps=steps, keep=(Wm, qmats, Z, logvar, loglen, f, xl, S0, ctrl, log_Q))
+
+
+_NO_SUMMARY = (None, None, None, 0, None, 0, None, None, None, None, None)
+
+
+def moment_grouped(Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x_lasts, control_inputs, ctrl_offset, steps, Qs, *, S0s=None,
+                   q_mode="reference"):
+    """Moment-matched prediction of G posteriors in one call (`ffvd_op_moment_grouped`): the Gaussian state N(x_last, S0) of every
+    group is pushed `steps` times through x' = x + f(x, c_t) + N(0, Q) in closed form and re-approximated as a Gaussian (Girard et
+    al. 2003); nothing is sampled, one launch per step serves all groups.  SquaredExponential kernels only.
+
+    `Zs` / `kerns` / `Lm_inverse_seqs`: one model (an (M, P) array, a list of D kernels, D upper-triangular matrices L^-T: shared by
+    the groups) or length-G sequences of them; U_vals: G arrays (M, D), the whitened inducing outputs; q_sqrts: None (explicit U) or
+    G stacks (D, M, M); q_mode "reference": slice 0 of a group's stack enters every dim's variance (what the rollouts
+    do), "intent": slice d enters dim d; x_lasts: G start means (D,); S0s: None (zeros) or (G, D, D) symmetric start covariances;
+    rows [ctrl_offset, ctrl_offset + steps) of control_inputs feed the steps; Qs: G vectors (D,) or one.
+    Returns m_x (G, steps, D) and S_x (G, steps, D, D): mean and covariance of the state after each step, S_x exactly symmetric;
+    group g's slabs are bit-identical to what a G = 1 call on that group alone returns."""
+    who = "moment_grouped"
+    a = _pack_moment_groups(who, Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x_lasts, control_inputs, ctrl_offset, steps, Qs, S0s, q_mode)
+    G, D, steps = a["G"], a["D"], a["steps"]
+    m_x, S_x = np.empty((G, steps, D)), np.empty((G, steps, D, D))
+    rc = _lib.load().ffvd_op_moment_grouped(*a["args"], _lib.dptr(m_x), _lib.dptr(S_x), *_NO_SUMMARY)
+    _lib.check(rc, None, who)
+    return m_x, S_x
+
+
+def _pack_posterior_moment(who, Zs, kerns, Xs, Qs, control_inputs, ctrl_offset, steps, S0s, q_mode, jitter, groups_per_pass):
+    """Shape checks and packing of `posterior_moment_grouped`'s arguments (before the library is loaded): the arguments of
+    `ffvd_op_posterior_moment_grouped` up to steps, and the shapes."""
+    a = pack_posterior_groups(Zs, kerns, Xs, control_inputs, Qs, who)
+    G, nm, M, D, C = a["G"], a["n_models"], a["M"], a["D"], a["C"]
+    _moment_limits(who, a["kind"], M, a["P"], D)
+    if int(groups_per_pass) < 0:
+        raise ValueError(f"{who}: groups_per_pass must be 0 (automatic) or positive")
+    qm, S0, ctrl, steps = _moment_run_args(who, G, D, C, control_inputs, ctrl_offset, steps, S0s, q_mode)
+    dp = _lib.dptr
+    opt = lambda x: None if x is None else dp(x)
+    args = (a["kind"], G, nm, dp(a["Z"]), M, a["P"], D, dp(a["logvar"]), dp(a["loglen"]), dp(a["X"]), opt(a["ctrl"]), C, a["T"],
+            dp(a["log_Q"]), float(jitter), int(groups_per_pass), qm, opt(S0), opt(ctrl), steps)
+    return dict(args=args, G=G, M=M, D=D, steps=steps, keep=(a, S0, ctrl))
+
+
+def posterior_moment_grouped(Zs, kerns, Xs, Qs, control_inputs, ctrl_offset, steps, *, S0s=None, q_mode="reference", jitter=JITTER,
+                             groups_per_pass=0, return_U=False):
+    """The collapsed posterior of G groups and its moment-matched prediction in ONE call (`ffvd_op_posterior_moment_grouped`): what
+    `conditionals_multi_output.collapse_u_mean_grouped` followed by `moment_grouped` computes (q_sqrts = L_H^-T, x_lasts = Xs[g][-1]),
+    without the posteriors leaving the device.  `Zs` / `kerns` / `Xs` / `Qs` / `control_inputs`: as `posterior_rollout_grouped`.
+    Returns m_x (G, steps, D), S_x (G, steps, D, D) and, with return_U, U_means (G, M, D)."""
+    who = "posterior_moment_grouped"
+    a = _pack_posterior_moment(who, Zs, kerns, Xs, Qs, control_inputs, ctrl_offset, steps, S0s, q_mode, jitter, groups_per_pass)
+    G, M, D, steps = a["G"], a["M"], a["D"], a["steps"]
+    m_x, S_x = np.empty((G, steps, D)), np.empty((G, steps, D, D))
+    U = np.empty((G, M, D)) if return_U else None
+    dp = _lib.dptr
+    rc = _lib.load().ffvd_op_posterior_moment_grouped(*a["args"], dp(m_x), dp(S_x), None if U is None else dp(U), *_NO_SUMMARY)
+    _lib.check(rc, None, who)
+    return (m_x, S_x, U) if return_U else (m_x, S_x)
+
+
+def moment_summary(m_x, S_x, CC, DD, log_Rchols, Y_test=None, Y_train_std=1.0):
+    """The held-out predictive summary of a moment-matched prediction on the GPU (`ffvd_op_moment_summary`): the dict of
+    `rollout_summary`, from Gaussian states instead of rollouts.  m_x (G, steps, D), S_x (G, steps, D, D); per output j and group g,
+    m_gj = CC_j^T mu_g + DD_j and s2_gj = CC_j^T Sigma_g CC_j + exp(2 log_Rchols[0, j]); the groups are pooled with equal weights:
+    predict_y = mean_g m, predict_y_var_total = mean_g (s2 + m^2) - predict_y^2, lpd = log mean_g N(y; m_g, s2_g) (a mixture of G
+    Gaussians), lpd_gauss = log N(y; predict_y, predict_y_var_total).  predict_y_var and predict_y_var_total are BOTH the total
+    variance: this method has no separate "reference variance" (the mean of one-step variances of `rollout_summary`)."""
+    who = "moment_summary"
+    m, S = _lib.as_f64(m_x), _lib.as_f64(S_x)
+    if m.ndim != 3 or S.shape != m.shape + (m.shape[2],):
+        raise ValueError(f"{who}: expected m_x (G, steps, D) and S_x (G, steps, D, D), got {m.shape} and {S.shape}")
+    G, steps, D = m.shape
+    if G < 1 or steps < 1 or not 1 <= D <= MOMENT_MAX_D:
+        raise ValueError(f"{who}: at least one group, one step and 1 <= D <= {MOMENT_MAX_D} are needed, got {m.shape}")
+    s = _pack_summary(who, D, steps, CC, DD, log_Rchols, Y_test)
+    out, args = _summary_call(s, steps)
+    rc = _lib.load().ffvd_op_moment_summary(_lib.dptr(m), _lib.dptr(S), G, steps, D, *args)
+    _lib.check(rc, None, who)
+    return _summary_dict(s, out, Y_train_std)
+
+
+def moment_grouped_summary(Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x_lasts, control_inputs, ctrl_offset, steps, Qs, CC, DD,
+                           log_Rchols, Y_test=None, Y_train_std=1.0, *, S0s=None, q_mode="reference", return_moments=False):
+    """`moment_grouped` and `moment_summary` in ONE call: the summary is formed on the device; m_x / S_x come down only with
+    return_moments (keys m_x, S_x)."""
+    who = "moment_grouped_summary"
+    a = _pack_moment_groups(who, Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x_lasts, control_inputs, ctrl_offset, steps, Qs, S0s, q_mode)
+    G, D, steps = a["G"], a["D"], a["steps"]
+    if steps < 1:
+        raise ValueError(f"{who}: at least one step is needed")
+    s = _pack_summary(who, D, steps, CC, DD, log_Rchols, Y_test)
+    out, args = _summary_call(s, steps)
+    m_x, S_x = (np.empty((G, steps, D)), np.empty((G, steps, D, D))) if return_moments else (None, None)
+    opt = lambda x: None if x is None else _lib.dptr(x)
+    rc = _lib.load().ffvd_op_moment_grouped(*a["args"], opt(m_x), opt(S_x), *args)
+    _lib.check(rc, None, who)
+    res = _summary_dict(s, out, Y_train_std)
+    if return_moments:
+        res.update(m_x=m_x, S_x=S_x)
+    return res
+
+
+def posterior_moment_grouped_summary(Zs, kerns, Xs, Qs, control_inputs, ctrl_offset, steps, CC, DD, log_Rchols, Y_test=None,
+                                     Y_train_std=1.0, *, S0s=None, q_mode="reference", jitter=JITTER, groups_per_pass=0,
+                                     return_moments=False, return_U=False):
+    """`posterior_moment_grouped` and `moment_summary` in ONE call: posteriors, propagation and summary stay on the device; m_x / S_x
+    come down only with return_moments (keys m_x, S_x), U_means (G, M, D) only with return_U."""
+    who = "posterior_moment_grouped_summary"
+    a = _pack_posterior_moment(who, Zs, kerns, Xs, Qs, control_inputs, ctrl_offset, steps, S0s, q_mode, jitter, groups_per_pass)
+    G, M, D, steps = a["G"], a["M"], a["D"], a["steps"]
+    if steps < 1:
+        raise ValueError(f"{who}: at least one step is needed")
+    s = _pack_summary(who, D, steps, CC, DD, log_Rchols, Y_test)
+    out, args = _summary_call(s, steps)
+    m_x, S_x = (np.empty((G, steps, D)), np.empty((G, steps, D, D))) if return_moments else (None, None)
+    U = np.empty((G, M, D)) if return_U else None
+    opt = lambda x: None if x is None else _lib.dptr(x)
+    rc = _lib.load().ffvd_op_posterior_moment_grouped(*a["args"], opt(m_x), opt(S_x), opt(U), *args)
+    _lib.check(rc, None, who)
+    res = _summary_dict(s, out, Y_train_std)
+    if return_moments:
+        res.update(m_x=m_x, S_x=S_x)
     if return_U:
         res["U_means"] = U
     return res

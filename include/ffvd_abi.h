@@ -603,6 +603,57 @@ int  ffvd_op_posterior_conditional_grouped(int kind, int G, int n_models, const 
                                            int groups_per_pass, int q_mode, const double *Xnew, int N, int rows_per_pass,
                                            double *means, double *vars, double *mix_mean, double *mix_var, double *U_means);
 
+/* Moment-matched prediction: the Gaussian state x_t ~ N(mu, Sigma) of each of G posteriors is pushed through
+ * x_{t+1} = x_t + f(x_t, ctrl_t) + N(0, Q) in closed form and re-approximated as a Gaussian (Girard et al. 2003; the propagation of
+ * PILCO); one launch per step for all groups, nothing is sampled.  SE-ARD kernels only.  The posterior is that of
+ * ffvd_op_conditional_grouped, with the same arguments: m_a(x) = k_a(x, Z) beta_a, v_a(x) = variance_a - k_a(x, Z) Gamma_a k_a(Z, x),
+ * beta_a = W_a u_a, Gamma_a = W_a (I - q q^T) W_a^T (q_sqrts = NULL: W_a W_a^T); q_mode 0 ("reference"): q is slice 0 of the group's
+ * stack for every dim (G pointers; what the rollouts use), q_mode 1 ("intent"): slice a (G * D pointers, entry g * D + a).
+ * Per step, with nu_i = z_i - [mu ; ctrl_t], lambda_a the first D entries of 1 / lengthscales_a^2 and R_a = Sigma diag(lambda_a) + I:
+ *   E[f_a]        = sum_i beta_ai q^a_i,  q^a_i = variance_a |R_a|^-1/2 exp(-nu_i^xT (Sigma + Lambda_a^xx)^-1 nu_i^x / 2 - (control part) / 2)
+ *   Cov(f_a, f_b) = sum_ij beta_ai beta_bj (Q^ab_ij - q^a_i q^b_j),  a = b: + variance_a - sum_ij Gamma_a,ij Q^aa_ij, where
+ *   Q^ab_ij       = variance_a variance_b |R|^-1/2 exp(-nu_i^T Lambda_a^-1 nu_i / 2 - nu_j^T Lambda_b^-1 nu_j / 2 + (a_i + b_j)^T T (a_i + b_j) / 2),
+ *                   R = Sigma diag(lambda_a + lambda_b) + I, T = R^-1 Sigma, a_i = lambda_a nu_i^x, b_j = lambda_b nu_j^x
+ *   Cov(x, f_a)   = Sigma (Sigma + Lambda_a^xx)^-1 sum_i beta_ai q^a_i nu_i^x  (column a of V)
+ *   mu' = mu + E[f],  Sigma' = Sigma + Cov(f) + V + V^T + diag(Q)  (stored exactly symmetric)
+ * The D x D systems are solved by Gaussian elimination with partial pivoting (Sigma = 0 is allowed); |R| <= 0 or a non-finite state
+ * gives NaN for that group from that step on, nothing faults.
+ * x_lasts G x D (start means); S0s NULL (zeros) or G x D x D (start covariances, symmetric); ctrl steps x C (NULL when C = 0);
+ * log_Qs G x D.  Outputs m_x G x steps x D, S_x G x steps x D x D (the state AFTER step t at index t); either may be NULL when a
+ * summary is requested.  The trailing block is that of ffvd_op_rollout_grouped_summary; it is requested by giving any of its
+ * arguments.  Per output j over the G groups (equal weights, ascending order), m_gj = CC_j^T mu_g + DD_j, s2_gj = CC_j^T Sigma_g CC_j
+ * + s_j^2:  y_mean = mean_g m,  y_var_total = mean_g (s2 + m^2) - y_mean^2,  y_var = y_var_total (this method has no other variance),
+ * lpd = log (1/G) sum_g N(y; m_g, s2_g) (largest exponent subtracted),  lpd_gauss = log N(y; y_mean, y_var_total).
+ * Determinism: the decomposition of a group depends on (M, D) only, sums have fixed orders, no atomics: two calls are bit-identical
+ * and a group's m_x / S_x do not depend on G or the other groups.
+ * Limits: SE kernel, D <= 8, P = D + C <= 32, M <= 2048, J <= 8, n_models 1 or G, q_mode 0 or 1, G * D <= 2^24, G * D * Mp^2 <= 2^29
+ * doubles (Mp: M rounded up to 64), G * steps * D * D < 2^31; FFVD_EINVAL beyond them, before any device call.  G = 0 or steps = 0:
+ * FFVD_OK, nothing is touched. */
+int  ffvd_op_moment_grouped(int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M, int P, int D,
+                            const double *logvariances, const double *loglengthscales, const double *fs,
+                            const double *const *q_sqrts, int q_mode, const double *x_lasts, const double *S0s, const double *ctrl,
+                            int C, int steps, const double *log_Qs, double *m_x, double *S_x, const double *CC, const double *DD,
+                            const double *noise_std, int J, const double *Y_test, int n_test, double *y_mean, double *y_var,
+                            double *y_var_total, double *lpd, double *lpd_gauss);
+
+/* ffvd_op_posterior_grouped followed by ffvd_op_moment_grouped WITHOUT the posteriors leaving the device (as
+ * ffvd_op_posterior_rollout_grouped does for the rollouts): W is packed from the K_uu slabs, f = U_mean is read where the matvec left
+ * it, the q slices are packed with exact zeros in the padding and the strict lower triangle, the start means are Xs[g][T].  ctrl_fit
+ * T x C feeds the posterior, ctrl_roll steps x C the propagation.  U_means G x M x D optional.
+ * Limits: those of ffvd_op_posterior_grouped and of ffvd_op_moment_grouped.  G = 0 or steps = 0: FFVD_OK, nothing is touched. */
+int  ffvd_op_posterior_moment_grouped(int kind, int G, int n_models, const double *Zs, int M, int P, int D, const double *logvariances,
+                                      const double *loglengthscales, const double *Xs, const double *ctrl_fit, int C, int T,
+                                      const double *log_Qs, double jitter, int groups_per_pass, int q_mode, const double *S0s,
+                                      const double *ctrl_roll, int steps, double *m_x, double *S_x, double *U_means, const double *CC,
+                                      const double *DD, const double *noise_std, int J, const double *Y_test, int n_test,
+                                      double *y_mean, double *y_var, double *y_var_total, double *lpd, double *lpd_gauss);
+
+/* The summary of ffvd_op_moment_grouped for stacks the caller holds (m_x G x steps x D, S_x G x steps x D x D): the same launch.
+ * Limits: D <= 8, J <= 8, 0 <= n_test <= steps, G * steps * D * D < 2^31, as ffvd_op_rollout_summary otherwise. */
+int  ffvd_op_moment_summary(const double *m_x, const double *S_x, int G, int steps, int D, const double *CC, const double *DD,
+                            const double *noise_std, int J, const double *Y_test, int n_test, double *y_mean, double *y_var,
+                            double *y_var_total, double *lpd, double *lpd_gauss);
+
 /* One particle-Gibbs sweep over the latent trajectory: the INTENT of BaseModel.PG_for_X_speedup (base_model.py:78-138;
  * as written that op never updates X -- discarded TensorArray.write results (:115), an assign that is never run (:137) --
  * so there is no reference behaviour to match, see oracle/ffvd_pg_oracle.py).  n_free = PG_particles - 1 free particles
