@@ -44,6 +44,34 @@ void launch_mg_emat(hipStream_t stream, int nq, int M, int Mp, const double *N, 
 // launch t of steps + 1: finishes step t - 1 (t > 0) and forms the slab sums of step t (t < steps)
 void launch_mg_step(hipStream_t stream, const MomentGroupArgs &a, int t);
 
+// Filtering ("Filtering and smoothing"): the same launch with a measurement update between "finish step t - 1"
+// and "form the slabs of step t".  The state after step i emits row i of Y (y = CC^T x + DD + noise, diagonal noise sd_j); a NaN entry
+// of Y is unobserved.  The update is a sequence of scalar updates in ascending j, run redundantly by every workgroup of the group (the
+// same instructions in the same order, as the finish of the step); only the writer workgroup stores.  MomentGroupArgs::m_x / S_x are
+// the PREDICTED moments m^-_i, S^-_i in this form; state[] holds the FILTERED state.
+constexpr int MG_MAXJ = 8;           // outputs of the emission
+struct MomentFilterArgs {
+    int J;
+    const double *CC;                // [D][J]
+    const double *DD, *sd;           // [J]
+    const double *Y;                 // [steps][J], NaN = unobserved
+    double *m_filt, *S_filt;         // [G][steps][D], [G][steps][D][D]: after the update with row i
+    double *cross;                   // [G][steps][D][D]: Cov(x_{i-1}, x_i | y_{0:i-1}), row = component of x_{i-1}
+    double *lpd;                     // [G][steps][J]: log N(y_ij; .) under the predicted state, NaN where unobserved
+    double *lpd_joint;               // [G][steps]: joint log density of the observed entries of row i, NaN where there is none
+};
+void launch_mg_filter_step(hipStream_t stream, const MomentGroupArgs &a, const MomentFilterArgs &f, int t);
+
+// RTS pass over the stored stacks, one workgroup per group, i = steps - 2 .. 0:  J_i = X_{i+1} (S^-_{i+1})^-1 (pivoted elimination),
+// m^s_i = m_i + J_i (m^s_{i+1} - m^-_{i+1}),  S^s_i = S_i + J_i (S^s_{i+1} - S^-_{i+1}) J_i^T (exactly symmetric); the last row is the
+// filtered one bit for bit.  Every sum has a fixed order.
+struct MomentSmoothArgs {
+    int G, D, steps;
+    const double *m_pred, *S_pred, *m_filt, *S_filt, *cross;
+    double *m_smooth, *S_smooth;     // [G][steps][D], [G][steps][D][D]
+};
+void launch_mg_smooth(hipStream_t stream, const MomentSmoothArgs &a);
+
 struct MomentSummaryArgs {
     int G, steps, D, J, n_test;
     const double *m, *S;             // [G][steps][D], [G][steps][D][D]

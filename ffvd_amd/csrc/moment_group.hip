@@ -28,9 +28,10 @@
 // among others, and run to run.
 //
 // |R| <= 0 or a non-finite state: NaN for that group from there on; no global address depends on a computed value.
-#include "moment_group.h"
-#include "kernels.h"
-#include "dev_common.h"
+//
+// The step kernel itself is in moment_step.h: this file instantiates it as the propagation (FILTER = false), moment_filter.hip as the
+// filter.  Separate translation units, so that the propagation's code does not change with the filter's.
+#include "moment_step.h"
 
 namespace ffvd {
 
@@ -76,223 +77,6 @@ void launch_mg_emat(hipStream_t stream, int nq, int M, int Mp, const double *N, 
 }
 
 namespace {
-constexpr double LOG_2PI = 1.8378770664093454835606594728112;
-
-// T = R^-1 S with R = S diag(lam) + I: Gaussian elimination with partial pivoting on the rows [R | S] (A: this thread's LDS);
-// returns |R|.  S need not be positive definite (S = 0 at step 0: R = I); a zero pivot gives inf / NaN, which propagate.
-template <int D>
-__device__ __noinline__ double mg_solve(const double (*S)[MG_MAXD], const double *lam, double (*A)[2 * MG_MAXD], double (*T)[MG_MAXD]) {
-    for (int r = 0; r < D; ++r)
-        for (int c = 0; c < D; ++c) {
-            A[r][c] = S[r][c] * lam[c] + (r == c ? 1.0 : 0.0);
-            A[r][D + c] = S[r][c];
-        }
-    double det = 1.0;
-    for (int k = 0; k < D; ++k) {
-        int piv = k;                                             // in [k, D): an LDS row of this thread, whatever the values are
-        double best = fabs(A[k][k]);
-        for (int r = k + 1; r < D; ++r) {
-            const double v = fabs(A[r][k]);
-            if (v > best) { best = v; piv = r; }
-        }
-        if (piv != k) {
-            for (int c = k; c < 2 * D; ++c) { const double x = A[k][c]; A[k][c] = A[piv][c]; A[piv][c] = x; }
-            det = -det;
-        }
-        const double p = A[k][k], ip = 1.0 / p;
-        det *= p;
-        for (int r = k + 1; r < D; ++r) {
-            const double f = A[r][k] * ip;
-            for (int c = k + 1; c < 2 * D; ++c) A[r][c] -= f * A[k][c];
-        }
-    }
-    for (int c = 0; c < D; ++c)
-        for (int r = D - 1; r >= 0; --r) {
-            double s = A[r][D + c];
-            for (int k = r + 1; k < D; ++k) s -= A[r][k] * T[k][c];
-            T[r][c] = s / A[r][r];
-        }
-    return det;
-}
-
-// One inducing row z for one latent dim: av = lambda nu^x, q = E[k(x, z)] (scale = variance |R_d|^-1/2), and
-// de = av^T (T - T_d) av / 2, the row's share of delta.  il: 1 / lengthscales of the dim; Td, Tp: T of the dim and of the pair.
-template <int D>
-__device__ __forceinline__ void mg_row(const double *z, const double *xin, const double *il, int P, const double (*Td)[MG_MAXD],
-                                       const double (*Tp)[MG_MAXD], double scale, double (&av)[D], double &q, double &de) {
-    double c = 0.0;
-#pragma unroll
-    for (int p = 0; p < D; ++p) {
-        const double u = (z[p] - xin[p]) * il[p];
-        c += u * u;
-        av[p] = u * il[p];
-    }
-    for (int p = D; p < P; ++p) {
-        const double u = (z[p] - xin[p]) * il[p];
-        c += u * u;
-    }
-    double qa = 0.0, qt = 0.0;
-#pragma unroll
-    for (int r = 0; r < D; ++r) {
-        double sa = 0.0, st = 0.0;
-#pragma unroll
-        for (int k = 0; k < D; ++k) { sa += Td[r][k] * av[k]; st += Tp[r][k] * av[k]; }
-        qa += av[r] * sa;
-        qt += av[r] * st;
-    }
-    q = scale * exp(0.5 * qa - 0.5 * c);                         // the whole exponent (never positive) before the exp
-    de = 0.5 * qt - 0.5 * qa;
-}
-
-template <int D>
-__global__ __launch_bounds__(256) void mg_step_kernel(MomentGroupArgs a, const int t) {
-    constexpr int NP = D * (D + 1) / 2, NF = NP + D + D * D;
-    __shared__ double mu[MG_MAXD], Sg[MG_MAXD][MG_MAXD], xin[MAXP], fin[NF];
-    __shared__ double ils[2][MAXP], lam[3][MG_MAXD];
-    __shared__ double GA[3][MG_MAXD][2 * MG_MAXD], TT[3][MG_MAXD][MG_MAXD], dets[3];
-    __shared__ double tav[MG_SLAB][MG_MAXD], avs[MG_SLAB][MG_MAXD], dei[MG_SLAB], bqi[MG_SLAB], qi[MG_SLAB], rvec[MG_MAXD];
-    __shared__ double red[4][2];
-    const int tid = threadIdx.x;
-    const int G = a.G, C = a.C, P = a.P, M = a.M, Mp = a.Mp, NS = a.NS, steps = a.steps;
-    const int s = blockIdx.x % NS, gp = blockIdx.x / NS, pr = gp % NP, g = gp / NP;
-    int da = 0, db = pr;                                          // pair pr -> (da <= db), row-major over the upper triangle
-    while (db >= D - da) { db -= D - da; ++da; }
-    db += da;
-    const bool writer = (pr == 0 && s == 0);
-    if (t == steps && !writer) return;
-    const int model = a.n_models == 1 ? 0 : g;
-
-    // 1. the state of this launch: (x_last, S0), or the state of launch t - 1 plus its slab sums
-    if (t == 0) {
-        if (tid < D) mu[tid] = a.x_last[(size_t)g * D + tid];
-        if (tid < D * D) Sg[tid / D][tid % D] = a.S0 ? a.S0[(size_t)g * D * D + tid] : 0.0;
-    } else {
-        const double *pp = a.part + ((size_t)((t - 1) & 1) * G + g) * NF * NS;
-        if (tid < NF) {
-            double sum = 0.0;
-            for (int sl = 0; sl < NS; ++sl) sum += pp[(size_t)tid * NS + sl];          // slab order, the same in every workgroup
-            fin[tid] = sum;
-        }
-        __syncthreads();
-        const double *sp = a.state + ((size_t)((t - 1) & 1) * G + g) * (D + D * D);
-        if (tid < D) mu[tid] = sp[tid] + fin[NP + tid];
-        if (tid < D * D) {                                        // (r, c) and (c, r) run the same expression: exactly symmetric
-            const int r = tid / D, c = tid % D, lo = r < c ? r : c, hi = r < c ? c : r;
-            const int pi = lo * D - lo * (lo - 1) / 2 + (hi - lo);
-            double v = sp[D + lo * D + hi] + fin[pi];
-            v += fin[NP + D + hi * D + lo] + fin[NP + D + lo * D + hi];                   // Cov(x_lo, f_hi) + Cov(x_hi, f_lo)
-            if (lo == hi) v += a.variance[(size_t)model * D + lo] + exp(a.log_Q[(size_t)g * D + lo]);
-            Sg[r][c] = v;
-        }
-    }
-    __syncthreads();
-    if (writer) {
-        double *sc = a.state + ((size_t)(t & 1) * G + g) * (D + D * D);
-        if (tid < D) {
-            sc[tid] = mu[tid];
-            if (t > 0) a.m_x[((size_t)g * steps + (t - 1)) * D + tid] = mu[tid];
-        }
-        if (tid < D * D) {
-            const double v = Sg[tid / D][tid % D];
-            sc[D + tid] = v;
-            if (t > 0) a.S_x[((size_t)g * steps + (t - 1)) * D * D + tid] = v;
-        }
-    }
-    if (t == steps) return;
-
-    // 2. the three eliminations of the pair
-    const double *lena = a.len + ((size_t)model * D + da) * P, *lenb = a.len + ((size_t)model * D + db) * P;
-    if (tid < P) {
-        xin[tid] = tid < D ? mu[tid] : a.ctrl[(size_t)t * C + (tid - D)];
-        const double ia = 1.0 / lena[tid], ib = 1.0 / lenb[tid];
-        ils[0][tid] = ia;
-        ils[1][tid] = ib;
-        if (tid < D) { lam[0][tid] = ia * ia; lam[1][tid] = ib * ib; lam[2][tid] = ia * ia + ib * ib; }
-    }
-    __syncthreads();
-    if (tid < 3) dets[tid] = mg_solve<D>(Sg, lam[tid], GA[tid], TT[tid]);
-    __syncthreads();
-    const double detA = dets[0], detB = dets[1], detP = dets[2];
-    const bool ok = detA > 0.0 && detB > 0.0 && detP > 0.0;
-    const double nan = __builtin_nan("");
-    const double sca = ok ? a.variance[(size_t)model * D + da] / sqrt(detA) : nan;
-    const double scb = ok ? a.variance[(size_t)model * D + db] / sqrt(detB) : nan;
-    const double rho = ok ? sqrt(detA * detB / detP) : nan, rho1 = rho - 1.0;
-
-    // 3. the slab's rows (dim a)
-    const int i0 = MG_SLAB * s, ni = (M - i0 < MG_SLAB) ? M - i0 : MG_SLAB;
-    const double *Zm = a.Z + (size_t)model * M * P;
-    const double *bea = a.beta + ((size_t)g * D + da) * Mp, *beb = a.beta + ((size_t)g * D + db) * Mp;
-    if (tid < MG_SLAB) {
-        double av[D], q = 0.0, de = 0.0, be = 0.0;
-#pragma unroll
-        for (int k = 0; k < D; ++k) av[k] = 0.0;
-        if (tid < ni) {
-            mg_row<D>(Zm + (size_t)(i0 + tid) * P, xin, ils[0], P, TT[0], TT[2], sca, av, q, de);
-            be = bea[i0 + tid];
-        }
-#pragma unroll
-        for (int r = 0; r < D; ++r) {
-            double st = 0.0;
-#pragma unroll
-            for (int k = 0; k < D; ++k) st += TT[2][k][r] * av[k];
-            tav[tid][r] = st;
-            avs[tid][r] = av[r];
-        }
-        dei[tid] = de;
-        qi[tid] = q;
-        bqi[tid] = be * q;
-    }
-    __syncthreads();
-    double *po = a.part + ((size_t)(t & 1) * G + g) * NF * NS;
-    const bool diag = da == db;
-    if (diag && tid < D) {
-        double r = 0.0;
-        for (int i = 0; i < ni; ++i) r += bqi[i] * avs[i][tid];
-        rvec[tid] = r;
-    }
-    if (diag && tid == 64) {
-        double m = 0.0;
-        for (int i = 0; i < ni; ++i) m += bqi[i];
-        po[(size_t)(NP + da) * NS + s] = m;                                               // E[f_a] of the slab
-    }
-    __syncthreads();
-    if (diag && tid < D) {
-        double v = 0.0;
-#pragma unroll
-        for (int k = 0; k < D; ++k) v += TT[0][tid][k] * rvec[k];
-        po[(size_t)(NP + D + da * D + tid) * NS + s] = v;                                 // Cov(x, f_a) of the slab
-    }
-
-    // 4. the slab of the pair table: thread = column j
-    const double *Gg = diag ? a.gam + ((size_t)(a.unit_per_group ? g : model) * D + da) * Mp * Mp + (size_t)i0 * Mp : nullptr;
-    double accc = 0.0, accg = 0.0;
-    for (int j = tid; j < M; j += 256) {
-        double bv[D], qj, dg;
-        mg_row<D>(Zm + (size_t)j * P, xin, ils[1], P, TT[1], TT[2], scb, bv, qj, dg);
-        const double bqj = beb[j] * qj;
-        for (int i = 0; i < ni; ++i) {
-            double del = dei[i] + dg;
-#pragma unroll
-            for (int k = 0; k < D; ++k) del += tav[i][k] * bv[k];
-            // Q_ij <= its bound means del <= -(log q_i + log q_j): an exponent beyond 700 belongs to a product q_i q_j that is zero
-            const double em = expm1(del > 700.0 ? 700.0 : del);
-            accc += bqi[i] * (bqj * (rho * em + rho1));
-            if (diag) accg -= Gg[(size_t)i * Mp + j] * ((qi[i] * qj) * (rho * (em + 1.0)));
-        }
-    }
-    const int lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-    for (int mm = 32; mm > 0; mm >>= 1) { accc += __shfl_xor(accc, mm); accg += __shfl_xor(accg, mm); }
-    if (lane == 0) { red[wave][0] = accc; red[wave][1] = accg; }
-    __syncthreads();
-    if (tid == 0) {
-        const double cs = ((red[0][0] + red[1][0]) + red[2][0]) + red[3][0];
-        const double gs = ((red[0][1] + red[1][1]) + red[2][1]) + red[3][1];
-        po[(size_t)pr * NS + s] = cs + gs;                        // Cov(f_a, f_b) of the slab (a = b: with E[v_a] - variance_a)
-    }
-}
-
 __global__ __launch_bounds__(256) void mg_summary_kernel(MomentSummaryArgs a) {
     const size_t SJ = (size_t)a.steps * a.J, e = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= SJ) return;
@@ -347,7 +131,7 @@ __global__ __launch_bounds__(256) void mg_summary_kernel(MomentSummaryArgs a) {
 void launch_mg_step(hipStream_t stream, const MomentGroupArgs &a, int t) {
     const dim3 grid((unsigned)((size_t)a.G * mg_npair(a.D) * a.NS));
     switch (a.D) {
-#define MG_CASE(d) case d: hipLaunchKernelGGL(mg_step_kernel<d>, grid, dim3(256), 0, stream, a, t); break;
+#define MG_CASE(d) case d: hipLaunchKernelGGL(HIP_KERNEL_NAME(mg_step_kernel<d, false>), grid, dim3(256), 0, stream, a, t); break;
         MG_CASE(1) MG_CASE(2) MG_CASE(3) MG_CASE(4) MG_CASE(5) MG_CASE(6) MG_CASE(7) MG_CASE(8)
 #undef MG_CASE
         default: break;

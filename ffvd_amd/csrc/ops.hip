@@ -1729,11 +1729,34 @@ int mg_summary(Scratch &sc, const std::string &who, const double *dm, const doub
     return FFVD_OK;
 }
 
-// Operands on the device -> beta, Gamma, the step launches, the summary, the downloads.  dW: [n_models * D] slots of Mp x Mp (upper
+// The filter request of mg_run: the emission, the observations (NaN = unobserved) and the outputs, each of which may be NULL
+struct FilterReq {
+    const double *CC, *DD, *noise_std;           // D x J, J, J
+    int J;
+    const double *Y_obs;                         // steps x J
+    double *m_filt, *S_filt, *cross, *lpd, *lpd_joint, *m_smooth, *S_smooth;
+    double *y_mean, *y_var_total, *lpd_mix, *lpd_gauss;      // the pooled one-step summary (steps x J)
+};
+// the checks of a filter request that need no array, and those that read the small arrays (Y_obs: no infinity)
+bool filter_scalars_ok(const FilterReq &f) { return f.J >= 1 && f.J <= MG_MAXJ; }
+bool filter_arrays_ok(const FilterReq &f, int steps, const double *m_pred, const double *S_pred) {
+    if (!f.CC || !f.DD || !f.noise_std || !f.Y_obs) return false;
+    if (!(m_pred || S_pred || f.m_filt || f.S_filt || f.cross || f.lpd || f.lpd_joint || f.m_smooth || f.S_smooth || f.y_mean ||
+          f.y_var_total || f.lpd_mix || f.lpd_gauss))
+        return false;
+    for (int j = 0; j < f.J; ++j)
+        if (!std::isfinite(f.noise_std[j]) || !(f.noise_std[j] > 0.0)) return false;
+    for (size_t e = 0; e < (size_t)steps * f.J; ++e)
+        if (std::isinf(f.Y_obs[e])) return false;
+    return true;
+}
+
+// Operands on the device -> beta, Gamma, the step launches, the summary, the downloads.  flt: the launches are those of the filter
+// (moment_group.h), m_x / S_x are the predicted moments, the summary is the pooled one-step summary of the request.  dW: [n_models * D] slots of Mp x Mp (upper
 // triangular, zero padded); dq: nullptr, or [G] (q_mode 0) / [G * D] (q_mode 1) slots of Mp x Mp; hv: variance / len per (model, dim).
 int mg_run(Scratch &sc, const std::string &who, int G, int nm, int M, int P, int D, int C, int steps, const HyperView &hv, const double *dZ,
            const double *dW, const double *dq, int q_mode, const double *dU, const double *dxl, const double *dS0, const double *dlq,
-           const double *dctrl, double *m_x, double *S_x, const SummaryReq *sum) {
+           const double *dctrl, double *m_x, double *S_x, const SummaryReq *sum, const FilterReq *flt = nullptr) {
     const int Mp = round_up(M, NB), NS = (M + MG_SLAB - 1) / MG_SLAB, nK = nm * D, GD = G * D;
     const size_t mm = (size_t)Mp * Mp, nm_x = (size_t)G * steps * D, nS_x = nm_x * D;
     const int units = dq ? GD : nK, nq = dq ? (q_mode ? GD : G) : 0;
@@ -1744,6 +1767,23 @@ int mg_run(Scratch &sc, const std::string &who, int G, int nm, int M, int P, int
     double *part = sc.alloc<double>((size_t)2 * G * mg_fields(D) * NS), *state = sc.alloc<double>((size_t)2 * G * (D + D * D));
     double *dm = sc.alloc<double>(nm_x), *dS = sc.alloc<double>(nS_x);
     OP_CHECK_AS(beta && gam && (!dq || (dN && dE && dWE)) && unused && part && state && dm && dS, who);
+    MomentFilterArgs fa{};
+    MomentSmoothArgs sa{};
+    const bool smooth = flt && (flt->m_smooth || flt->S_smooth);
+    const size_t nlpd = flt ? (size_t)G * steps * flt->J : 0, nlj = (size_t)G * steps;
+    if (flt) {
+        fa.J = flt->J;
+        fa.CC = sc.upload(flt->CC, (size_t)D * flt->J); fa.DD = sc.upload(flt->DD, flt->J); fa.sd = sc.upload(flt->noise_std, flt->J);
+        fa.Y = sc.upload(flt->Y_obs, (size_t)steps * flt->J);
+        fa.m_filt = sc.alloc<double>(nm_x); fa.S_filt = sc.alloc<double>(nS_x); fa.cross = sc.alloc<double>(nS_x);
+        fa.lpd = sc.alloc<double>(nlpd); fa.lpd_joint = sc.alloc<double>(nlj);
+        OP_CHECK_AS(fa.CC && fa.DD && fa.sd && fa.Y && fa.m_filt && fa.S_filt && fa.cross && fa.lpd && fa.lpd_joint, who);
+        if (smooth) {
+            sa.G = G; sa.D = D; sa.steps = steps; sa.m_pred = dm; sa.S_pred = dS; sa.m_filt = fa.m_filt; sa.S_filt = fa.S_filt;
+            sa.cross = fa.cross; sa.m_smooth = sc.alloc<double>(nm_x); sa.S_smooth = sc.alloc<double>(nS_x);
+            OP_CHECK_AS(sa.m_smooth && sa.S_smooth, who);
+        }
+    }
     launch_mg_beta(sc.stream, G, D, M, Mp, nm == G, dW, dU, beta);
     // Gamma = W (I - q q^T) W^T through cov.hip's product body.  COV_GEN: C = A B^T, all Mp x Mp entries written.
     CovArgs gen{};
@@ -1784,10 +1824,22 @@ int mg_run(Scratch &sc, const std::string &who, int G, int nm, int M, int P, int
     a.G = G; a.n_models = nm; a.D = D; a.C = C; a.P = P; a.M = M; a.Mp = Mp; a.NS = NS; a.steps = steps; a.unit_per_group = dq ? 1 : 0;
     a.Z = dZ; a.variance = hv.variance; a.len = hv.len; a.beta = beta; a.gam = gam; a.x_last = dxl; a.S0 = dS0; a.log_Q = dlq;
     a.ctrl = dctrl; a.part = part; a.state = state; a.m_x = dm; a.S_x = dS;
-    for (int t = 0; t <= steps; ++t) launch_mg_step(sc.stream, a, t);
+    if (!flt)
+        for (int t = 0; t <= steps; ++t) launch_mg_step(sc.stream, a, t);
+    else {
+        for (int t = 0; t <= steps; ++t) launch_mg_filter_step(sc.stream, a, fa, t);
+        if (smooth) launch_mg_smooth(sc.stream, sa);
+    }
     OP_TRY(hipGetLastError());
     if (sum)
         if (int rc = mg_summary(sc, who, dm, dS, G, steps, D, *sum)) return rc;
+    if (flt) {
+        auto down = [&](double *dst, const double *src, size_t n) { return !dst || sc.download(dst, src, n * sizeof(double)); };
+        if (!down(flt->m_filt, fa.m_filt, nm_x) || !down(flt->S_filt, fa.S_filt, nS_x) || !down(flt->cross, fa.cross, nS_x) ||
+            !down(flt->lpd, fa.lpd, nlpd) || !down(flt->lpd_joint, fa.lpd_joint, nlj) || !down(flt->m_smooth, sa.m_smooth, nm_x) ||
+            !down(flt->S_smooth, sa.S_smooth, nS_x))
+            return set_error(nullptr, FFVD_EDEVICE, who + ": copying the results back failed");
+    }
     if ((m_x && !sc.download(m_x, dm, nm_x * sizeof(double))) || (S_x && !sc.download(S_x, dS, nS_x * sizeof(double))))
         return set_error(nullptr, FFVD_EDEVICE, who + ": copying the results back failed");
     OP_TRY(hipStreamSynchronize(sc.stream));
@@ -1867,6 +1919,99 @@ extern "C" int ffvd_op_posterior_moment_grouped(int kind, int G, int n_models, c
     launch_pg_x_last(sc.stream, w.Xs, G, T, D, dxl);
     if (int rc = mg_run(sc, whos, G, n_models, M, P, D, C, steps, w.hv, dZ, dW, q_mode ? w.qall : w.q0, q_mode, w.U, dxl, dS0, w.log_Qs,
                         dctrl, m_x, S_x, sum))
+        return rc;
+    if (U_means && !sc.download(U_means, w.U, GD * M * sizeof(double)))
+        return set_error(nullptr, FFVD_EDEVICE, whos + ": copying the results back failed");
+    return FFVD_OK;
+}
+
+// ---- filtering and smoothing (moment_group.h) -------------------------------------------------------------------------------------
+namespace {
+// the pooled one-step summary of a filter request as a summary request on the predicted stacks (every row carries an observation
+// row: NaN entries give NaN densities), or nothing when none of its outputs is asked for
+bool filter_summary(const FilterReq &f, int steps, SummaryReq &q) {
+    q = SummaryReq{f.CC, f.DD, f.noise_std, f.J, f.Y_obs, steps, f.y_mean, nullptr, f.y_var_total, f.lpd_mix, f.lpd_gauss};
+    return f.y_mean || f.y_var_total || f.lpd_mix || f.lpd_gauss;
+}
+}  // namespace
+
+// ffvd_op_moment_grouped with a measurement update after every step (posteriors given by the caller)
+extern "C" int ffvd_op_filter_grouped(int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M, int P,
+                                      int D, const double *logvariances, const double *loglengthscales, const double *fs,
+                                      const double *const *q_sqrts, int q_mode, const double *x_lasts, const double *S0s,
+                                      const double *ctrl, int C, int steps, const double *log_Qs, const double *CC, const double *DD,
+                                      const double *noise_std, int J, const double *Y_obs, double *m_pred, double *S_pred,
+                                      double *m_filt, double *S_filt, double *cross, double *lpd, double *lpd_joint, double *m_smooth,
+                                      double *S_smooth, double *y_mean, double *y_var_total, double *lpd_mix, double *lpd_gauss) {
+    const std::string who = "ffvd_op_filter_grouped", bad = who + ": bad argument";
+    const FilterReq f{CC, DD, noise_std, J, Y_obs, m_filt, S_filt, cross, lpd, lpd_joint, m_smooth, S_smooth, y_mean, y_var_total, lpd_mix,
+                      lpd_gauss};
+    if (kind != FFVD_KERNEL_SE) return set_error(nullptr, FFVD_EINVAL, bad + " (moment matching is closed-form for the SE kernel only)");
+    if (!mg_scalars_ok(kind, G, n_models, M, P, D, C, steps, q_mode) || !filter_scalars_ok(f)) return set_error(nullptr, FFVD_EINVAL, bad);
+    if (G == 0 || steps == 0) return FFVD_OK;
+    if (!Lm_inverse_seqs || !Zs || !logvariances || !loglengthscales || !fs || !x_lasts || !log_Qs || (C > 0 && !ctrl) ||
+        !filter_arrays_ok(f, steps, m_pred, S_pred))
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    const size_t nK = (size_t)n_models * D, GD = (size_t)G * D, nq = q_sqrts ? (q_mode ? GD : (size_t)G) : 0;
+    for (size_t b = 0; b < nK; ++b) if (!Lm_inverse_seqs[b]) return set_error(nullptr, FFVD_EINVAL, bad);
+    for (size_t b = 0; b < nq; ++b) if (!q_sqrts[b]) return set_error(nullptr, FFVD_EINVAL, bad);
+    SummaryReq q{};
+    const SummaryReq *sum = filter_summary(f, steps, q) ? &q : nullptr;
+    OP_BEGIN_AS(who);
+    const int Mp = round_up(M, NB);
+    double *dW = upload_matrix_table(sc, Lm_inverse_seqs, nK, M, Mp), *dq = nq ? upload_matrix_table(sc, q_sqrts, nq, M, Mp) : nullptr;
+    double *dZ = sc.upload(Zs, (size_t)n_models * M * P), *dU = sc.upload(fs, GD * M), *dxl = sc.upload(x_lasts, GD);
+    double *dS0 = S0s ? sc.upload(S0s, GD * D) : nullptr, *dlq = sc.upload(log_Qs, GD), *dctrl = C ? sc.upload(ctrl, (size_t)steps * C) : nullptr;
+    double *dlv = sc.upload(logvariances, nK), *dll = sc.upload(loglengthscales, nK * P);
+    double *variance = sc.alloc<double>(nK), *len = sc.alloc<double>(nK * P), *Zsc = sc.alloc<double>(nK * Mp * P), *zz = sc.alloc<double>(nK * Mp);
+    OP_CHECK_AS(dW && (!nq || dq) && dZ && dU && dxl && (!S0s || dS0) && dlq && (!C || dctrl) && dlv && dll && variance && len && Zsc && zz, who);
+    launch_rg_prep(sc.stream, kind, n_models, D, M, Mp, P, dZ, dlv, dll, variance, len, Zsc, zz);
+    return mg_run(sc, who, G, n_models, M, P, D, C, steps, HyperView{variance, len, Zsc, zz}, dZ, dW, dq, q_mode, dU, dxl, dS0, dlq,
+                  dctrl, m_pred, S_pred, sum, &f);
+}
+
+// The collapsed posteriors of ffvd_op_posterior_grouped filtered without leaving the device (as ffvd_op_posterior_moment_grouped);
+// x0s NULL: the start means are the last rows of Xs
+extern "C" int ffvd_op_posterior_filter_grouped(int kind, int G, int n_models, const double *Zs, int M, int P, int D,
+                                                const double *logvariances, const double *loglengthscales, const double *Xs,
+                                                const double *ctrl_fit, int C, int T, const double *log_Qs, double jitter,
+                                                int groups_per_pass, int q_mode, const double *x0s, const double *S0s,
+                                                const double *ctrl_roll, int steps, const double *CC, const double *DD,
+                                                const double *noise_std, int J, const double *Y_obs, double *m_pred, double *S_pred,
+                                                double *m_filt, double *S_filt, double *cross, double *lpd, double *lpd_joint,
+                                                double *m_smooth, double *S_smooth, double *y_mean, double *y_var_total, double *lpd_mix,
+                                                double *lpd_gauss, double *U_means) {
+    const std::string whos = "ffvd_op_posterior_filter_grouped", bad = whos + ": bad argument";
+    const char *who = "ffvd_op_posterior_filter_grouped";
+    const FilterReq f{CC, DD, noise_std, J, Y_obs, m_filt, S_filt, cross, lpd, lpd_joint, m_smooth, S_smooth, y_mean, y_var_total, lpd_mix,
+                      lpd_gauss};
+    if (kind != FFVD_KERNEL_SE) return set_error(nullptr, FFVD_EINVAL, bad + " (moment matching is closed-form for the SE kernel only)");
+    if (!pg_scalars_ok(kind, G, n_models, M, P, D, C, T, groups_per_pass, jitter) || !mg_scalars_ok(kind, G, n_models, M, P, D, C, steps, q_mode) ||
+        !filter_scalars_ok(f))
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    if (G == 0 || steps == 0) return FFVD_OK;
+    if (!Zs || !logvariances || !loglengthscales || !Xs || !log_Qs || (C > 0 && (!ctrl_fit || !ctrl_roll)) ||
+        !filter_arrays_ok(f, steps, m_pred, S_pred))
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    SummaryReq q{};
+    const SummaryReq *sum = filter_summary(f, steps, q) ? &q : nullptr;
+    OP_BEGIN_AS(whos);
+    PgIn in{who, kind, G, n_models, M, P, D, C, T, groups_per_pass, Zs, logvariances, loglengthscales, Xs, ctrl_fit, log_Qs, jitter};
+    PgWork w{};
+    const int Mp = round_up(M, NB), nK = n_models * D;
+    const size_t GD = (size_t)G * D, mm = (size_t)Mp * Mp;
+    if (q_mode) w.qall = sc.alloc<double>(GD * mm);
+    else { w.Mp16 = Mp; w.q0 = sc.alloc<double>((size_t)G * mm); }
+    double *dW = sc.alloc<double>((size_t)nK * mm), *dxl = x0s ? sc.upload(x0s, GD) : sc.alloc<double>(GD);
+    OP_CHECK_AS((w.qall || w.q0) && dW && dxl, whos);
+    if (int rc = pg_posterior(sc, in, w)) return rc;
+    double *dZ = sc.upload(Zs, (size_t)n_models * M * P), *dS0 = S0s ? sc.upload(S0s, GD * D) : nullptr;
+    double *dctrl = C ? sc.upload(ctrl_roll, (size_t)steps * C) : nullptr;
+    OP_CHECK_AS(dZ && (!S0s || dS0) && (!C || dctrl), whos);
+    launch_pg_pack(sc.stream, w.Kuu, 2 * mm, Mp, Mp, nK, 1, M, 1, dW, Mp, Mp, nK);
+    if (!x0s) launch_pg_x_last(sc.stream, w.Xs, G, T, D, dxl);
+    if (int rc = mg_run(sc, whos, G, n_models, M, P, D, C, steps, w.hv, dZ, dW, q_mode ? w.qall : w.q0, q_mode, w.U, dxl, dS0, w.log_Qs,
+                        dctrl, m_pred, S_pred, sum, &f))
         return rc;
     if (U_means && !sc.download(U_means, w.U, GD * M * sizeof(double)))
         return set_error(nullptr, FFVD_EDEVICE, whos + ": copying the results back failed");

@@ -555,6 +555,41 @@ class DGPSSM:
                                       n_train, steps, self.Q, lik.CC, lik.DD, lik.log_Rchols, Y_test, Y_train_std, q_mode=q_mode,
                                       return_moments=True)
 
+    def filter_heldout(self, Y_test, control_inputs=None, *, x0=None, S0=None, smooth=False, q_mode="reference", Y_train_std=1.0):
+        """One-step-ahead (prequential) evaluation, filtered and (with `smooth`) smoothed latent states of a held-out record: every
+        chain's Gaussian state is pushed through the learned transition and updated with each row of Y_test (len, Ydim; a NaN entry
+        is unobserved, trailing all-NaN rows forecast) -- prediction.filter_grouped has the method and the dict that is returned
+        (SquaredExponential kernels only; deterministic).  x0 None: every chain starts at its X_s[-1] (the record continues the
+        training sequence) with S0 None: zero covariance; else x0 (D,) or (S, D) and S0 (D, D) or (S, D, D) for a fresh record.
+        Collapsed U: ONE `posterior_filter_grouped` call with G = S and the model shared by the groups.  Explicit U:
+        `kernel_pre_cal` once, then `filter_grouped` with the shared U and no q_sqrt.  control_inputs None: the model's own; rows
+        [n_train, n_train + len(Y_test)) feed the steps, as in `predict_moments`.  Parameters newer on the device than on the host
+        are pulled first."""
+        from . import conditionals_multi_output as cmo
+        from .prediction import filter_grouped, posterior_filter_grouped
+        if q_mode not in cmo.Q_MODES:
+            raise ValueError(f"filter_heldout: q_mode: expected one of {sorted(cmo.Q_MODES)}, got {q_mode!r}")
+        Y_test = np.asarray(Y_test, dtype=np.float64)
+        if Y_test.ndim == 1:
+            Y_test = Y_test[:, None]
+        if Y_test.ndim != 2 or Y_test.shape[1] != self.Y.shape[1]:
+            raise ValueError(f"filter_heldout: Y_test: expected (n_test, {self.Y.shape[1]}), got {Y_test.shape}")
+        if self._host_stale:
+            self.pull_parameters()
+        S, D = self.num_chains, self.output_dim
+        x0s = None if x0 is None else np.broadcast_to(np.asarray(x0, dtype=np.float64), (S, D))
+        S0s = None if S0 is None else np.broadcast_to(np.asarray(S0, dtype=np.float64), (S, D, D))
+        ci = self.control_inputs if control_inputs is None else np.asarray(control_inputs, dtype=np.float64)
+        lay, lik, n_train = self.layers[-1], self.likelihood, self.Y.shape[0]
+        if self.U_collapse:
+            return posterior_filter_grouped(lay.Z, lay.kernel, [self._X_chains[s_] for s_ in range(S)], self.Q, ci, n_train, Y_test,
+                                            lik.CC, lik.DD, lik.log_Rchols, x0s=x0s, S0s=S0s, q_mode=q_mode, smooth=smooth,
+                                            Y_train_std=Y_train_std)
+        Lm = cmo.kernel_pre_cal(lay.Z, lay.kernel)
+        starts = [self._X_chains[s_][-1] for s_ in range(S)] if x0s is None else list(x0s)
+        return filter_grouped(Lm, lay.Z, lay.kernel, [lay.U] * S, None, starts, ci, n_train, Y_test, self.Q, lik.CC, lik.DD,
+                              lik.log_Rchols, S0s=S0s, q_mode=q_mode, smooth=smooth, Y_train_std=Y_train_std)
+
     def predict_transition(self, Xnew, *, q_mode="reference", per_chain=True):
         """The learned transition function at inputs of the caller's choice: mean and variance of the posterior GP increment
         f(x, c) at the rows of Xnew (N, D + C) -- the f_mu and f_var a rollout adds at every step (x_next = x + f_mu +

@@ -571,6 +571,102 @@ def posterior_moment_grouped_summary(Zs, kerns, Xs, Qs, control_inputs, ctrl_off
     return res
 
 
+def _filter_steps(who, Y_obs):
+    """steps = len(Y_obs)"""
+    shape = np.shape(Y_obs)
+    if len(shape) not in (1, 2):
+        raise ValueError(f"{who}: Y_obs: expected (steps, J), got {shape}")
+    return shape[0]
+
+
+def _pack_filter(who, D, Y_obs, CC, DD, log_Rchols):
+    """Shape checks of the observations and the emission of the filter (before the library is loaded): `_pack_summary` with
+    steps = len(Y_obs); NaN marks an unobserved entry, an infinity is rejected."""
+    m = _pack_summary(who, D, _filter_steps(who, Y_obs), CC, DD, log_Rchols, Y_obs)
+    if np.any(np.isinf(m["Y"])):
+        raise ValueError(f"{who}: Y_obs: an infinite observation (NaN marks an unobserved entry)")
+    return m
+
+
+def _filter_call(m, G, D, steps, smooth):
+    """Output arrays and the trailing arguments (CC .. lpd_gauss) of the two filter entry points."""
+    J, dp = m["J"], _lib.dptr
+    out = dict(m_pred=np.empty((G, steps, D)), S_pred=np.empty((G, steps, D, D)), m_filt=np.empty((G, steps, D)),
+               S_filt=np.empty((G, steps, D, D)), cross=np.empty((G, steps, D, D)), lpd=np.empty((G, steps, J)),
+               lpd_joint=np.empty((G, steps)))
+    if smooth:
+        out.update(m_smooth=np.empty((G, steps, D)), S_smooth=np.empty((G, steps, D, D)))
+    out.update(predict_y=np.empty((steps, J)), predict_y_var_total=np.empty((steps, J)), lpd_mix=np.empty((steps, J)),
+               lpd_gauss=np.empty((steps, J)))
+    names = ("m_pred", "S_pred", "m_filt", "S_filt", "cross", "lpd", "lpd_joint", "m_smooth", "S_smooth", "predict_y",
+             "predict_y_var_total", "lpd_mix", "lpd_gauss")
+    args = (dp(m["CC"]), dp(m["DD"]), dp(m["sd"]), J, dp(m["Y"])) + tuple(dp(out[k]) if k in out else None for k in names)
+    return out, args
+
+
+def _filter_dict(m, out, Y_train_std):
+    """The dict the filter functions return: the arrays of `_filter_call` and the scalars ll (mean of lpd_mix over the observed
+    entries), ll_joint (mean over the rows with an observed entry of log mean_g exp(lpd_joint[g, i]), largest exponent subtracted),
+    ll_original_units (ll - log Y_train_std) and RMSE (one-step-ahead, observed entries of the first 30 rows, times Y_train_std)."""
+    Y, nan = m["Y"], float("nan")
+    seen = ~np.isnan(Y)
+    ll = float(np.mean(out["lpd_mix"][seen])) if np.any(seen) else nan
+    rows = np.any(seen, axis=1)
+    ll_joint = nan
+    if np.any(rows):
+        lj = out["lpd_joint"][:, rows]
+        mx = np.max(lj, axis=0)
+        ll_joint = float(np.mean(mx + np.log(np.mean(np.exp(lj - mx[None, :]), axis=0))))
+    s30 = seen[:30]
+    rmse = float(np.sqrt(np.mean((Y[:30][s30] - out["predict_y"][:30][s30]) ** 2)) * Y_train_std) if np.any(s30) else nan
+    res = dict(out)
+    res.update(ll=ll, ll_joint=ll_joint, ll_original_units=ll - float(np.log(Y_train_std)), RMSE=rmse)
+    return res
+
+
+def filter_grouped(Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_inputs, ctrl_offset, Y_obs, Qs, CC, DD, log_Rchols, *,
+                   S0s=None, q_mode="reference", smooth=False, Y_train_std=1.0):
+    """Gaussian filtering (and, with `smooth`, RTS smoothing) of an observed sequence through G posteriors in one call
+    (`ffvd_op_filter_grouped`): `moment_grouped`'s step with a measurement update after every step -- assumed-density filtering by
+    moment matching (Deisenroth et al. 2012).  The state after step i emits row i of Y_obs (steps, J): y = CC^T x + DD + noise of
+    standard deviation exp(log_Rchols[0, :]); a NaN entry is unobserved (an all-NaN row is a prediction step; trailing all-NaN rows
+    forecast from the filtered state).  Every group starts from N(x0s[g], S0s[g]) (S0s None: zeros); the other arguments are
+    `moment_grouped`'s, rows [ctrl_offset, ctrl_offset + steps) of control_inputs feed the steps.
+    Returns a dict.  Per group: m_pred (G, steps, D), S_pred (G, steps, D, D): the state before row i is seen; m_filt, S_filt:
+    after; cross (G, steps, D, D): Cov(x_{i-1}, x_i | y_{0:i-1}), row = component of x_{i-1}; lpd (G, steps, J):
+    log p(y_ij | y_{0:i-1}) per entry (marginal), lpd_joint (G, steps): of the observed entries of row i jointly (NaN where
+    unobserved); with smooth: m_smooth, S_smooth (the start state is not smoothed).  Pooled over the groups with EQUAL weights (the
+    chains are not re-weighted by their likelihoods), one step ahead, (steps, J): predict_y, predict_y_var_total, lpd_mix,
+    lpd_gauss.  Scalars: ll, ll_joint, ll_original_units, RMSE (`_filter_dict`).  Every covariance is exactly symmetric; group g's
+    arrays are bit-identical to a G = 1 call on that group."""
+    who = "filter_grouped"
+    steps = _filter_steps(who, Y_obs)
+    a = _pack_moment_groups(who, Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_inputs, ctrl_offset, steps, Qs, S0s, q_mode)
+    m = _pack_filter(who, a["D"], Y_obs, CC, DD, log_Rchols)
+    out, args = _filter_call(m, a["G"], a["D"], steps, smooth)
+    rc = _lib.load().ffvd_op_filter_grouped(*a["args"], *args)
+    _lib.check(rc, None, who)
+    return _filter_dict(m, out, Y_train_std)
+
+
+def posterior_filter_grouped(Zs, kerns, Xs, Qs, control_inputs, ctrl_offset, Y_obs, CC, DD, log_Rchols, *, x0s=None, S0s=None,
+                             q_mode="reference", smooth=False, Y_train_std=1.0, jitter=JITTER, groups_per_pass=0):
+    """The collapsed posterior of G groups and the filter of `filter_grouped` in ONE call (`ffvd_op_posterior_filter_grouped`): what
+    `conditionals_multi_output.collapse_u_mean_grouped` followed by `filter_grouped` computes, without the posteriors leaving the
+    device.  x0s None: the start means are Xs[g][-1] (the record continues the training sequence), else (G, D).  `Zs` / `kerns` /
+    `Xs` / `Qs` / `control_inputs`: as `posterior_moment_grouped`.  Returns the dict of `filter_grouped`."""
+    who = "posterior_filter_grouped"
+    steps = _filter_steps(who, Y_obs)
+    a = _pack_posterior_moment(who, Zs, kerns, Xs, Qs, control_inputs, ctrl_offset, steps, S0s, q_mode, jitter, groups_per_pass)
+    m = _pack_filter(who, a["D"], Y_obs, CC, DD, log_Rchols)
+    x0 = None if x0s is None else _lib.as_f64(x0s, (a["G"], a["D"]), "x0s")
+    out, args = _filter_call(m, a["G"], a["D"], steps, smooth)
+    pre = a["args"][:17] + (None if x0 is None else _lib.dptr(x0),) + a["args"][17:]
+    rc = _lib.load().ffvd_op_posterior_filter_grouped(*pre, *args, None)
+    _lib.check(rc, None, who)
+    return _filter_dict(m, out, Y_train_std)
+
+
 def pg_sweep(Lm_inverse_seq, Z, kern, U_val, X_ref, Y, control_inputs, CC, DD, Rchols, Q, x0, eps, unif):
     """One particle-Gibbs sweep over the latent trajectory: the INTENT of BaseModel.PG_for_X_speedup
     (base_model.py:78-138; the op as written never updates X, see include/ffvd_abi.h `ffvd_op_pg_sweep`).

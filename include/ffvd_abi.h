@@ -648,6 +648,49 @@ int  ffvd_op_posterior_moment_grouped(int kind, int G, int n_models, const doubl
                                       const double *DD, const double *noise_std, int J, const double *Y_test, int n_test,
                                       double *y_mean, double *y_var, double *y_var_total, double *lpd, double *lpd_gauss);
 
+/* Gaussian filtering and RTS smoothing of an observed sequence through the GP by moment matching (assumed-density filtering;
+ * Deisenroth et al. 2012): ffvd_op_moment_grouped -- same arguments up to log_Qs, same posterior, same step -- with a measurement
+ * update after every step.  The state after step i emits row i of Y_obs (steps x J): y = CC^T x + DD + N(0, diag(noise_std^2));
+ * a NaN entry of Y_obs is unobserved (an all-NaN row is a pure prediction step: trailing all-NaN rows forecast); an infinity is
+ * rejected.  Per group, from N(x_lasts[g], S0s[g]), for i = 0 .. steps - 1:
+ *   predict:  m^-_i = mu + E[f],  S^-_i = Sigma + Cov(f) + V + V^T + diag(Q)  (the step of ffvd_op_moment_grouped from the filtered
+ *             state of index i - 1),  X_i = Sigma + V = Cov(x_{i-1}, x_i | y_{0:i-1})  (row: component of x_{i-1});
+ *   density:  lpd[g][i][j] = log N(y_ij; CC_j^T m^-_i + DD_j, CC_j^T S^-_i CC_j + s_j^2)  (marginal, before any update),
+ *             lpd_joint[g][i] = joint log density of the observed entries of row i;  NaN where the entry / the whole row is unobserved;
+ *   update:   exact, as scalar updates in ascending j over the observed entries: with h = CC_j, s = h^T Sigma h + s_j^2,
+ *             e = y_ij - h^T mu - DD_j:  mu += Sigma h e / s,  Sigma -= (Sigma h)(Sigma h)^T / s  (no J x J factorisation; the terms
+ *             -(log 2 pi + log s) / 2 - e^2 / (2 s) add up to lpd_joint).  A row without an observed entry leaves m_filt = m_pred and
+ *             S_filt = S_pred bit for bit.
+ * Smoothing (only when m_smooth or S_smooth is given; the start state is not smoothed): the last row is the filtered one bit for bit,
+ * then for i = steps - 2 .. 0:  J_i = X_{i+1} (S^-_{i+1})^-1 (Gaussian elimination with partial pivoting),
+ *   m^s_i = m_i + J_i (m^s_{i+1} - m^-_{i+1}),  S^s_i = S_i + J_i (S^s_{i+1} - S^-_{i+1}) J_i^T.
+ * Outputs, each may be NULL: m_pred, m_filt, m_smooth G x steps x D;  S_pred, S_filt, cross, S_smooth G x steps x D x D (every
+ * covariance exactly symmetric);  lpd G x steps x J;  lpd_joint G x steps;  and the pooled ONE-STEP summary y_mean, y_var_total, lpd_mix,
+ * lpd_gauss, each steps x J: the summary of ffvd_op_moment_grouped applied to the predicted stacks with Y_obs (NaN densities where
+ * an entry is unobserved).  It pools the groups with EQUAL weights, as everywhere in this library: the chains are NOT re-weighted by
+ * their likelihoods.  Determinism as ffvd_op_moment_grouped: two calls are bit-identical, a group does not depend on the others.
+ * Limits: those of ffvd_op_moment_grouped, 1 <= J <= 8, steps >= 0, at least one output; FFVD_EINVAL beyond them, before any device
+ * call.  G = 0 or steps = 0: FFVD_OK, nothing is touched. */
+int  ffvd_op_filter_grouped(int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M, int P, int D,
+                            const double *logvariances, const double *loglengthscales, const double *fs,
+                            const double *const *q_sqrts, int q_mode, const double *x_lasts, const double *S0s, const double *ctrl,
+                            int C, int steps, const double *log_Qs, const double *CC, const double *DD, const double *noise_std, int J,
+                            const double *Y_obs, double *m_pred, double *S_pred, double *m_filt, double *S_filt, double *cross,
+                            double *lpd, double *lpd_joint, double *m_smooth, double *S_smooth, double *y_mean, double *y_var_total,
+                            double *lpd_mix, double *lpd_gauss);
+
+/* ffvd_op_posterior_grouped followed by ffvd_op_filter_grouped WITHOUT the posteriors leaving the device (as
+ * ffvd_op_posterior_moment_grouped).  x0s G x D: the start means, NULL: Xs[g][T] (the record continues the training sequence).
+ * Limits: those of ffvd_op_posterior_grouped and of ffvd_op_filter_grouped. */
+int  ffvd_op_posterior_filter_grouped(int kind, int G, int n_models, const double *Zs, int M, int P, int D, const double *logvariances,
+                                      const double *loglengthscales, const double *Xs, const double *ctrl_fit, int C, int T,
+                                      const double *log_Qs, double jitter, int groups_per_pass, int q_mode, const double *x0s,
+                                      const double *S0s, const double *ctrl_roll, int steps, const double *CC, const double *DD,
+                                      const double *noise_std, int J, const double *Y_obs, double *m_pred, double *S_pred,
+                                      double *m_filt, double *S_filt, double *cross, double *lpd, double *lpd_joint, double *m_smooth,
+                                      double *S_smooth, double *y_mean, double *y_var_total, double *lpd_mix, double *lpd_gauss,
+                                      double *U_means);
+
 /* The summary of ffvd_op_moment_grouped for stacks the caller holds (m_x G x steps x D, S_x G x steps x D x D): the same launch.
  * Limits: D <= 8, J <= 8, 0 <= n_test <= steps, G * steps * D * D < 2^31, as ffvd_op_rollout_summary otherwise. */
 int  ffvd_op_moment_summary(const double *m_x, const double *S_x, int G, int steps, int D, const double *CC, const double *DD,
