@@ -1,7 +1,7 @@
 // C ABI of libffvd_hip.so (see include/ffvd_abi.h): handle lifetime, resident buffers, the per-iteration
 // launch sequence of the ELBO and of a T-shard, parameters in and out.  The multi-kernel backward pass is in backward.hip, optimiser
 // steps and the shard entry points in train.hip, the RCCL binding in comm.hip (the handle all four see: handle.h); the stateless
-// ffvd_op_* operators are in ops.hip.
+// ffvd_op_* operators are in ops.hip, ops_loops.hip and ops_grouped.hip.
 #include "handle.h"
 #include "kernels.h"
 #include "kernels_f32.h"

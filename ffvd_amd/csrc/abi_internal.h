@@ -1,5 +1,5 @@
 // What the two halves of the C ABI share: abi.hip with backward.hip, train.hip and comm.hip (handles, the ELBO iteration and its
-// backward pass, training, shards, RCCL) and ops.hip (the stateless ffvd_op_* operators).  Error reporting and the guard around a
+// backward pass, training, shards, RCCL) and ops.hip, ops_loops.hip, ops_grouped.hip (the stateless ffvd_op_* operators).  Error reporting and the guard around a
 // forced Cholesky variant; nothing else crosses between them.
 #pragma once
 #include "../../include/ffvd_abi.h"
@@ -14,7 +14,7 @@ namespace ffvd {
 // the calling thread's error / warning string (what ffvd_last_error(NULL) returns); defined once, in abi.hip
 std::string &last_error();
 // records msg (in the handle as well when there is one) and returns code
-int set_error(ffvd_handle *h, int code, const std::string &msg);      // abi.hip; the handle is defined in handle.h, which ops.hip does not include
+int set_error(ffvd_handle *h, int code, const std::string &msg);      // abi.hip; the handle is defined in handle.h, which the operator sources do not include
 inline int set_error(std::nullptr_t, int code, const std::string &msg) {
     last_error() = msg;
     return code;

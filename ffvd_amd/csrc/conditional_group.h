@@ -1,6 +1,6 @@
 // Grouped GP conditionals (conditional_group.hip): mean and variance of the transition function f(x, c) of G posteriors at N common
 // inputs, conditional_after_kernel_precalculation (conditionals_multi_output.py:306-387, white=True, full_cov=False) for every group
-// in one launch sequence.  The operators ffvd_op_conditional_grouped / ffvd_op_posterior_conditional_grouped (ops.hip) stage the
+// in one launch sequence.  The operators ffvd_op_conditional_grouped / ffvd_op_posterior_conditional_grouped (ops_grouped.hip) stage the
 // operands and call launch_conditional_group.
 //
 // Layouts (Mp = M rounded up to 64, Tp = the rows of a pass rounded up to 64):

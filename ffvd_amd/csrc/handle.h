@@ -1,5 +1,5 @@
 // The handle behind the C ABI and what the sources that see inside it share: abi.hip (lifetime, the forward iteration), backward.hip
-// (the multi-kernel backward pass), train.hip (optimiser steps, shards) and comm.hip (RCCL).  ops.hip and every other source keep the
+// (the multi-kernel backward pass), train.hip (optimiser steps, shards) and comm.hip (RCCL).  The operator sources (ops*.hip) and every other source keep the
 // opaque type.
 #pragma once
 #include "abi_internal.h"

@@ -1,7 +1,7 @@
 // Moment-matched prediction for G posteriors with SE-ARD kernels: x_t ~ N(mu, Sigma) -> mean and covariance of
 // x_{t+1} = x_t + f(x_t, c_t) + process noise in closed form, re-approximated as a Gaussian.
 //
-// From the posterior, once per call (ops.hip puts the launches together): beta_a = W_a u_a (mg_beta_kernel) and
+// From the posterior, once per call (ops_grouped.hip puts the launches together): beta_a = W_a u_a (mg_beta_kernel) and
 // Gamma_a = W_a (I - q q^T) W_a^T, so that m_a(x) = k_a(x, Z) beta_a, v_a(x) = variance_a - k_a(x, Z) Gamma_a k_a(Z, x).
 // Gamma is NOT formed as W W^T - (W q)(W q)^T: where K_uu is ill-conditioned both products have entries near 1e5 and their
 // difference entries near 1 (five digits lost in fp64).  With N = I - q (exact in fp64 for the entries that matter),

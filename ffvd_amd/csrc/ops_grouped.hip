@@ -1,0 +1,901 @@
+// The grouped operators of the C ABI: rollout summaries, grouped rollouts, grouped collapsed posteriors, grouped conditionals, and
+// moment-matched prediction with filtering.  Each staging block (hyper-parameters, a caller's posterior, a posterior formed in the
+// call, the emission of a summary) is written once and shared by the entry points.
+#include "op_scratch.h"
+#include "rollout_group.h"
+#include "posterior_group.h"
+#include "conditional_group.h"
+#include "predict_summary.h"
+#include "moment_group.h"
+
+#include <cmath>
+
+using namespace ffvd;
+
+// ---- rollout summaries (predict_summary.h) --------------------------------------------------------------------------------------------
+// The held-out predictive summary of base_model.py:330-348 over all rollouts of a call, formed on the device stacks.
+namespace {
+struct SummaryReq {
+    const double *CC, *DD, *noise_std;           // D x J, J, J
+    int J;
+    const double *Y_test;                        // n_test x J or NULL
+    int n_test;
+    double *y_mean, *y_var, *y_var_total;        // steps x J, each may be NULL
+    double *lpd, *lpd_gauss;                     // n_test x J, each may be NULL
+};
+
+// the checks that need no array (before the "nothing to do" return) and those that read the small arrays (after it)
+bool summary_scalars_ok(const SummaryReq &q, long long N, int steps, int D) {
+    if (q.J < 1 || q.J > PS_MAXJ || D < 1 || D > MAXP || N < 0 || steps < 0 || q.n_test < 0 || q.n_test > steps) return false;
+    return N == 0 || steps == 0 || N <= ((1LL << 31) - 1) / steps / D;              // N * steps * D < 2^31 elements per stack
+}
+bool summary_arrays_ok(const SummaryReq &q) {
+    if (!q.CC || !q.DD || !q.noise_std || !(q.y_mean || q.y_var || q.y_var_total || q.lpd || q.lpd_gauss)) return false;
+    if ((q.n_test > 0 || q.lpd || q.lpd_gauss) && !q.Y_test) return false;
+    for (int j = 0; j < q.J; ++j)
+        if (!std::isfinite(q.noise_std[j]) || !(q.noise_std[j] > 0.0)) return false;
+    return true;
+}
+
+// The emission of a summary or a filter on the device, from the caller's arrays: CC (D x J), DD, noise_std (J), `rows` rows of Y (0: none)
+struct Emission { const double *CC, *DD, *sd, *Y; bool ok; };
+Emission stage_emission(Scratch &sc, int D, int J, const double *CC, const double *DD, const double *noise_std, const double *Y, size_t rows) {
+    Emission e{sc.upload(CC, (size_t)D * J), sc.upload(DD, J), sc.upload(noise_std, J), rows ? sc.upload(Y, rows * J) : nullptr, false};
+    e.ok = e.CC && e.DD && e.sd && (!rows || e.Y);
+    return e;
+}
+
+// The tail of a summary: its five fields (steps x J each, at dout; n_out doubles in all) come down in one small copy and go to the
+// outputs that were asked for (n_test rows of the last two)
+int fetch_summary(Scratch &sc, const double *dout, size_t n_out, int steps, const SummaryReq &q) {
+    const size_t SJ = (size_t)steps * q.J, TJ = (size_t)q.n_test * q.J;
+    OP_TRY(hipGetLastError());
+    std::vector<double> &h = sc.host(n_out);
+    OP_TRY(hipMemcpyAsync(h.data(), dout, h.size() * sizeof(double), hipMemcpyDeviceToHost, sc.stream));
+    OP_TRY(hipStreamSynchronize(sc.stream));
+    double *const dst[5] = {q.y_mean, q.y_var, q.y_var_total, q.lpd, q.lpd_gauss};
+    for (int f = 0; f < 5; ++f)
+        if (dst[f]) memcpy(dst[f], h.data() + f * SJ, (f < 3 ? SJ : TJ) * sizeof(double));
+    return FFVD_OK;
+}
+
+// The two launches of predict_summary.h on stacks that are on the device, then the requested outputs come down.
+int run_summary(Scratch &sc, const std::string &who, const double *dpx, const double *dpv, int N, int steps, int D, const SummaryReq &q) {
+    const Emission e = stage_emission(sc, D, q.J, q.CC, q.DD, q.noise_std, q.Y_test, q.n_test);
+    PredictSummaryArgs a{};
+    a.N = N; a.steps = steps; a.D = D; a.J = q.J; a.n_test = q.n_test; a.x = dpx; a.v = dpv;
+    a.CC = e.CC; a.DD = e.DD; a.sd = e.sd; a.Y = e.Y;
+    a.part = sc.alloc<double>(ps_part_doubles(N, steps, q.J));
+    a.out = sc.alloc<double>(ps_out_doubles(steps, q.J));
+    OP_CHECK(e.ok && a.part && a.out, who);
+    launch_predict_summary(sc.stream, a);
+    return fetch_summary(sc, a.out, ps_out_doubles(steps, q.J), steps, q);
+}
+
+// the summary launch of moment_group.h on stacks that are on the device, then the requested outputs come down
+int mg_summary(Scratch &sc, const std::string &who, const double *dm, const double *dS, int G, int steps, int D, const SummaryReq &q) {
+    const Emission e = stage_emission(sc, D, q.J, q.CC, q.DD, q.noise_std, q.Y_test, q.n_test);
+    MomentSummaryArgs a{};
+    a.G = G; a.steps = steps; a.D = D; a.J = q.J; a.n_test = q.n_test; a.m = dm; a.S = dS;
+    a.CC = e.CC; a.DD = e.DD; a.sd = e.sd; a.Y = e.Y;
+    a.out = sc.alloc<double>((size_t)5 * steps * q.J);
+    OP_CHECK(e.ok && a.out, who);
+    launch_moment_summary(sc.stream, a);
+    return fetch_summary(sc, a.out, (size_t)5 * steps * q.J, steps, q);
+}
+
+// ---- staging shared by the grouped operators -----------------------------------------------------------------------------------------
+// Device hyper-parameters of n models (n * D kernels over n sets of inducing inputs), in three steps that a caller places among its
+// own requests, because which cached block a buffer is handed depends on the order of a call's requests and every call keeps the
+// order it always had: stage_group_hypers uploads Z; logs() uploads logvar and loglen (nullptr: no lengthscales); blocks() allocates
+// what launch_rg_prep fills and says whether all three steps succeeded.  prep(): that launch, the caller's to place.
+struct GroupHypers {
+    int kind, n, D, M, Mp, P;
+    const double *logvar, *loglen;               // the host arrays, until logs()
+    double *dZ, *dlv, *dll;                      // uploaded: [n][M][P], [n][D], [n][D][P]
+    double *variance, *len, *Zsc, *zz;           // HyperView's layout
+    bool uploaded;
+    bool logs(Scratch &sc) {
+        dlv = sc.upload(logvar, (size_t)n * D); dll = loglen ? sc.upload(loglen, (size_t)n * D * P) : nullptr;
+        return uploaded = dZ && dlv && (!loglen || dll);
+    }
+    bool blocks(Scratch &sc) {
+        const size_t nK = (size_t)n * D;
+        variance = sc.alloc<double>(nK); len = sc.alloc<double>(nK * P); Zsc = sc.alloc<double>(nK * Mp * P); zz = sc.alloc<double>(nK * Mp);
+        return uploaded && variance && len && Zsc && zz;
+    }
+    HyperView hv() const { return HyperView{variance, len, Zsc, zz}; }
+    void prep(hipStream_t stream) const { launch_rg_prep(stream, kind, n, D, M, Mp, P, dZ, dlv, dll, variance, len, Zsc, zz); }
+};
+GroupHypers stage_group_hypers(Scratch &sc, int kind, int n, int D, int M, int Mp, int P, const double *Zs, const double *logvar,
+                               const double *loglen) {
+    GroupHypers h{kind, n, D, M, Mp, P, logvar, loglen};
+    h.dZ = sc.upload(Zs, (size_t)n * M * P);
+    return h;
+}
+
+// A posterior given by the caller: nW matrices W = L^-T and nq slices of q_sqrt (none without q_sqrts) as tables of host pointers,
+// each uploaded by upload_matrix_table.  given_nq / given_tables_ok read host memory only: the entry points call them before OP_BEGIN.
+size_t given_nq(const double *const *q_sqrts, int q_mode, int G, int D) { return q_sqrts ? (q_mode ? (size_t)G * D : (size_t)G) : 0; }
+bool given_tables_ok(const double *const *Lm_inverse_seqs, size_t nW, const double *const *q_sqrts, size_t nq) {
+    for (size_t b = 0; b < nW; ++b) if (!Lm_inverse_seqs[b]) return false;
+    for (size_t b = 0; b < nq; ++b) if (!q_sqrts[b]) return false;
+    return true;
+}
+// W q_sqrt is upper triangular when EVERY slice of q_sqrt is (the reference hands over L_H^-T): the products then stop at a slab's last
+// row for both right-hand sides.  Otherwise they walk all rows; for a group whose slice IS upper triangular the extra terms are exact
+// zeros, so its results do not depend on what the other groups hold.  Reads every strict lower triangle: only the rollouts and the
+// conditionals, whose kernels take the cut, ask -- between the two uploads, while W is on its way.
+int given_q_upper(const double *const *q_sqrts, size_t nq, int M) {
+    for (size_t b = 0; b < nq; ++b) if (!q_sqrt_is_upper(q_sqrts[b], M)) return 0;
+    return nq ? 1 : 0;
+}
+
+// ---- grouped rollouts (rollout_group.h): the limits and the shared runner ----------------------------------------------------------------
+bool rg_limits_ok(int G, int D, int R, int Mp) {
+    return (long long)G * D * Mp * Mp <= (1LL << 29) && (long long)G * R <= (1LL << 20) && (R + RG_RC - 1) / RG_RC <= 65535 &&
+           (long long)G * D * (Mp / RG_SLAB) < (1LL << 31);
+}
+
+// The grouped rollout on operands that are on the device: gh, the uploaded hyper-parameters of G models at Mp = M rounded up to
+// RG_SLAB; dW, [G * D] slots of Mp x Mp; dq, nullptr or [G] slots of q_sqrt, with dB, [G * D] slots for W q_sqrt; dU, dxl, dlq per
+// group; deps, dctrl.  Then hyper-parameters and W q_sqrt (the timer's ready_lap), one launch per step for all groups, the summary where
+// the step launches wrote (sum: predict_x / predict_var may each be NULL, not downloaded), the downloads (U_means from dU).
+int rg_run(Scratch &sc, const std::string &who, LapTimer &timer, const char *ready_lap, GroupHypers &gh, int R, int C, int steps,
+           const double *dW, const double *dq, double *dB, int q_upper, const double *dU, const double *dxl, const double *dlq,
+           const double *dctrl, const double *deps, double *predict_x, double *predict_var, double *U_means, const SummaryReq *sum) {
+    const int G = gh.n, D = gh.D, M = gh.M, Mp = gh.Mp, NS = Mp / RG_SLAB;
+    const size_t GD = (size_t)G * D, out_n = (size_t)G * R * steps * D;
+    const bool hypers = gh.blocks(sc);
+    double *part = sc.alloc<double>((size_t)2 * GD * NS * R * 4), *xbuf = sc.alloc<double>((size_t)2 * G * R * D);
+    double *dpx = sc.alloc<double>(out_n), *dpv = sc.alloc<double>(out_n);
+    OP_CHECK(hypers && part && xbuf && dpx && dpv, who);
+    gh.prep(sc.stream);
+    if (dq) launch_rg_wq(sc.stream, G, D, Mp, q_upper, dW, dq, dB);
+    timer.lap(ready_lap);
+    RolloutGroupArgs a{};
+    a.kind = gh.kind; a.G = G; a.R = R; a.D = D; a.C = C; a.P = gh.P; a.M = M; a.Mp = Mp; a.NS = NS; a.steps = steps;
+    a.has_q = dq ? 1 : 0; a.q_upper = q_upper;
+    a.W = dW; a.B = dB; a.Zs = gh.Zsc; a.zz = gh.zz; a.variance = gh.variance; a.len = gh.len; a.f = dU; a.x_last = dxl; a.log_Q = dlq;
+    a.ctrl = dctrl; a.eps = deps; a.part = part; a.xbuf = xbuf; a.predict_x = dpx; a.predict_var = dpv;
+    for (int t = 0; t <= steps; ++t) launch_rg_step(sc.stream, a, t);
+    OP_TRY(hipGetLastError());
+    timer.lap("step launches");
+    if (sum) {
+        if (int rc = run_summary(sc, who, dpx, dpv, G * R, steps, D, *sum)) return rc;
+        timer.lap("summary");
+    }
+    if ((predict_x && !sc.download(predict_x, dpx, out_n * sizeof(double))) ||
+        (predict_var && !sc.download(predict_var, dpv, out_n * sizeof(double))) ||
+        (U_means && !sc.download(U_means, dU, GD * M * sizeof(double))))
+        return set_error(nullptr, FFVD_EDEVICE, who + ": copying the results back failed");
+    timer.lap("results downloaded");
+    return FFVD_OK;
+}
+}  // namespace
+
+// base_model.py:330-348 for stacks the caller holds: they are uploaded, summarised by the same launches as in the fused calls
+extern "C" int ffvd_op_rollout_summary(const double *predict_x, const double *predict_var, int N, int steps, int D, const double *CC,
+                                       const double *DD, const double *noise_std, int J, const double *Y_test, int n_test,
+                                       double *y_mean, double *y_var, double *y_var_total, double *lpd, double *lpd_gauss) {
+    const std::string who = "ffvd_op_rollout_summary", bad = who + ": bad argument";
+    const SummaryReq q{CC, DD, noise_std, J, Y_test, n_test, y_mean, y_var, y_var_total, lpd, lpd_gauss};
+    if (!summary_scalars_ok(q, N, steps, D)) return set_error(nullptr, FFVD_EINVAL, bad);
+    if (N == 0 || steps == 0) return FFVD_OK;
+    if (!predict_x || !predict_var || !summary_arrays_ok(q)) return set_error(nullptr, FFVD_EINVAL, bad);
+    OP_BEGIN(who);
+    const size_t n = (size_t)N * steps * D;
+    double *dpx = sc.upload(predict_x, n), *dpv = sc.upload(predict_var, n);
+    OP_CHECK(dpx && dpv, who);
+    return run_summary(sc, who, dpx, dpv, N, steps, D, q);
+}
+
+// G posteriors given by the caller, one launch per step for all of them (rollout_group.hip)
+static int rollout_grouped_run(const std::string &who, int kind, int G, const double *const *Lm_inverse_seqs, const double *Zs, int M,
+                               int P, int D, const double *logvariances, const double *loglengthscales, const double *fs,
+                               const double *const *q_sqrts, const double *x_lasts, int R, const double *ctrl, int C, int steps,
+                               const double *log_Qs, const double *eps, double *predict_x, double *predict_var, const SummaryReq *sum) {
+    const std::string bad = who + ": bad argument";
+    if ((kind != FFVD_KERNEL_SE && kind != FFVD_KERNEL_LINEAR) || G < 0 || R < 1 || steps < 0 || M < 1 || M > 2048 || D < 1 || C < 0 ||
+        P != D + C || P > MAXP)
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    const int Mp = round_up(M, RG_SLAB);
+    if (!rg_limits_ok(G, D, R, Mp)) return set_error(nullptr, FFVD_EINVAL, bad + " (beyond the limits of rollout_group.h)");
+    if (sum && !summary_scalars_ok(*sum, (long long)G * R, steps, D)) return set_error(nullptr, FFVD_EINVAL, bad);
+    if (G == 0 || steps == 0) return FFVD_OK;
+    if (!Lm_inverse_seqs || !Zs || !logvariances || !fs || !x_lasts || !log_Qs || !eps || (!sum && (!predict_x || !predict_var)) ||
+        (C > 0 && !ctrl) || (kind == FFVD_KERNEL_SE && !loglengthscales) || (sum && !summary_arrays_ok(*sum)))
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    const size_t GD = (size_t)G * D, nq = given_nq(q_sqrts, 0, G, D);
+    if (!given_tables_ok(Lm_inverse_seqs, GD, q_sqrts, nq)) return set_error(nullptr, FFVD_EINVAL, bad);
+    OP_BEGIN(who);
+    LapTimer timer("FFVD_RG_TIMING", who.c_str(), sc.stream);
+    double *dW = upload_matrix_table(sc, Lm_inverse_seqs, GD, M, Mp);
+    timer.lap("W uploaded");
+    const int q_upper = given_q_upper(q_sqrts, nq, M);
+    timer.lap("q_sqrt scanned");
+    double *dq = nq ? upload_matrix_table(sc, q_sqrts, nq, M, Mp) : nullptr, *dB = nq ? sc.alloc<double>(GD * Mp * Mp) : nullptr;
+    GroupHypers gh = stage_group_hypers(sc, kind, G, D, M, Mp, P, Zs, logvariances, loglengthscales);
+    double *dU = sc.upload(fs, GD * M), *dxl = sc.upload(x_lasts, GD);
+    const bool hypers = gh.logs(sc);
+    double *dlq = sc.upload(log_Qs, GD), *deps = sc.upload(eps, (size_t)steps * G * R * D), *dctrl = C ? sc.upload(ctrl, (size_t)steps * C) : nullptr;
+    OP_CHECK(dW && (!nq || (dq && dB)) && hypers && dU && dxl && dlq && deps && (!C || dctrl), who);
+    timer.lap("q_sqrt, small arrays uploaded");
+    return rg_run(sc, who, timer, "hyper-parameters, W q_sqrt", gh, R, C, steps, dW, dq, dB, q_upper, dU, dxl, dlq, dctrl, deps, predict_x,
+                  predict_var, nullptr, sum);
+}
+
+extern "C" int ffvd_op_rollout_grouped(int kind, int G, const double *const *Lm_inverse_seqs, const double *Zs, int M, int P, int D,
+                                       const double *logvariances, const double *loglengthscales, const double *fs,
+                                       const double *const *q_sqrts, const double *x_lasts, int R, const double *ctrl, int C, int steps,
+                                       const double *log_Qs, const double *eps, double *predict_x, double *predict_var) {
+    return rollout_grouped_run("ffvd_op_rollout_grouped", kind, G, Lm_inverse_seqs, Zs, M, P, D, logvariances, loglengthscales, fs, q_sqrts,
+                               x_lasts, R, ctrl, C, steps, log_Qs, eps, predict_x, predict_var, nullptr);
+}
+
+extern "C" int ffvd_op_rollout_grouped_summary(int kind, int G, const double *const *Lm_inverse_seqs, const double *Zs, int M, int P,
+                                               int D, const double *logvariances, const double *loglengthscales, const double *fs,
+                                               const double *const *q_sqrts, const double *x_lasts, int R, const double *ctrl, int C,
+                                               int steps, const double *log_Qs, const double *eps, double *predict_x,
+                                               double *predict_var, const double *CC, const double *DD, const double *noise_std, int J,
+                                               const double *Y_test, int n_test, double *y_mean, double *y_var, double *y_var_total,
+                                               double *lpd, double *lpd_gauss) {
+    const SummaryReq q{CC, DD, noise_std, J, Y_test, n_test, y_mean, y_var, y_var_total, lpd, lpd_gauss};
+    return rollout_grouped_run("ffvd_op_rollout_grouped_summary", kind, G, Lm_inverse_seqs, Zs, M, P, D, logvariances, loglengthscales, fs,
+                               q_sqrts, x_lasts, R, ctrl, C, steps, log_Qs, eps, predict_x, predict_var, &q);
+}
+
+// ---- grouped collapsed posteriors (posterior_group.h) ---------------------------------------------------------------------------------
+// U_mean and L_H^-T of collapse_u_mean_after_kernel_precalculation (conditionals_multi_output.py:206-227, called at
+// base_model.py:243-256) for G groups over n_models (1 or G) sets of Z / hyper-parameters, with the K_uu factors of kernel_pre_cal
+// (:124-169) formed in the same call.  Everything between the small uploads and the results stays on the device.
+namespace {
+struct PgIn {
+    std::string who;
+    int kind, G, n_models, M, P, D, C, T, groups_per_pass;
+    const double *Zs, *logvar, *loglen, *Xs, *ctrl_fit, *log_Qs;
+    double jitter;
+};
+struct PgWork {
+    int Mp, nK;                    // M rounded up to 64; K_uu factorisations = n_models * D
+    double *Kuu;                   // [nK] slabs of 2 Mp x Mp: L, then L^-T
+    double *Xs, *log_Qs;           // the uploaded [G][T+1][D], [G][D]
+    double *U;                     // [G][M][D]
+    // optional targets, filled pass by pass
+    double *q0 = nullptr;          // [G][Mp16][Mp16]: L_H^-T of each group's d = 0 (upper triangle, zero padding)
+    int Mp16 = 0;
+    double *Hpack = nullptr;       // [G][D][M][M]: L_H^-T as ffvd_op_collapse_u_mean returns it
+    double *qall = nullptr;        // [G][D][Mp][Mp]: L_H^-T of every (group, dim) (upper triangle, zero padding)
+    HyperView hv{};                // [nK] device hyper-parameters (launch_rg_prep), left for what follows the posteriors
+};
+
+// scalar-argument checks shared by the two entry points (before any device call)
+bool pg_scalars_ok(int kind, int G, int n_models, int M, int P, int D, int C, int T, int groups_per_pass, double jitter) {
+    return (kind == FFVD_KERNEL_SE || kind == FFVD_KERNEL_LINEAR) && G >= 0 && M >= 1 && M <= 2048 && D >= 1 && C >= 0 && P == D + C &&
+           P <= MAXP && T >= 1 && groups_per_pass >= 0 && (n_models == 1 || n_models == G) && std::isfinite(jitter) &&
+           (long long)G * D <= (1LL << 24);                 // (units are counted in int)
+}
+
+// The q_sqrt slices that a posterior hands on in slots of the block size of its factorisations, asked for before pg_posterior:
+// every (group, dim) slice for q_mode 1, slice d = 0 of each group otherwise.  pg_q: what was packed.
+bool pg_want_q(Scratch &sc, PgWork &w, int q_mode, int G, int D, int M) {
+    const int Mp = round_up(M, NB);
+    if (q_mode) w.qall = sc.alloc<double>((size_t)G * D * Mp * Mp);
+    else { w.Mp16 = Mp; w.q0 = sc.alloc<double>((size_t)G * Mp * Mp); }
+    return w.qall || w.q0;
+}
+const double *pg_q(const PgWork &w, int q_mode) { return q_mode ? w.qall : w.q0; }
+
+// Uploads the inputs, enqueues the whole posterior (K_uu chain, projection, Gram, H chain, matvec, the pass's packing kernels) and
+// reads every factorisation flag in ONE download; nothing before that waits for the device.  A dataflow Cholesky launch that gave up
+// on a bounded wait: everything is enqueued once more from the inputs (still on the device) with the launch-per-column variant, as
+// potrf_with_stall_recovery does.  On FFVD_OK the stream is drained and w's arrays are final.
+int pg_posterior(Scratch &sc, const PgIn &in, PgWork &w) {
+    const int G = in.G, D = in.D, M = in.M, P = in.P, C = in.C, T = in.T, nm = in.n_models, kind = in.kind;
+    const int Mp = round_up(M, NB), Tp = round_up(T, STRIP), ng = (Mp + 511) / 512, nK = nm * D, GD = G * D;
+    const size_t kstride = (size_t)2 * Mp * Mp, hstride = (size_t)(2 * Mp + NB) * Mp, fstride = (size_t)Tp * Mp;
+    w.Mp = Mp; w.nK = nK;
+    int gpp = in.groups_per_pass > 0 ? in.groups_per_pass : pg_groups_per_pass(G, D, Tp, Mp);
+    if (gpp > G) gpp = G;
+    if ((long long)gpp * D > 32768) gpp = 32768 / D > 0 ? 32768 / D : 1;
+    const int upp = gpp * D;                                       // units per pass
+    const std::string &who = in.who;
+
+    GroupHypers gh = stage_group_hypers(sc, kind, nm, D, M, Mp, P, in.Zs, in.logvar, in.loglen);      // (prep: in the loop below)
+    gh.logs(sc);
+    double *dctrl = C ? sc.upload(in.ctrl_fit, (size_t)T * C) : nullptr;
+    w.Xs = sc.upload(in.Xs, (size_t)G * (T + 1) * D);
+    w.log_Qs = sc.upload(in.log_Qs, GD);
+    const bool hypers = gh.blocks(sc);
+    double *const variance = gh.variance, *const len = gh.len, *const Zsc = gh.Zsc, *const zz = gh.zz;
+    double *Xt = sc.alloc<double>((size_t)(T + 1) * GD);
+    w.Kuu = sc.alloc<double>((size_t)nK * kstride);
+    w.hv = gh.hv();
+    double *F = sc.alloc<double>((size_t)upp * fstride), *H = sc.alloc<double>((size_t)upp * hstride);
+    double *ubuf = sc.alloc<double>((size_t)upp * M);
+    w.U = sc.alloc<double>((size_t)GD * M);
+    const int kchunk = nK < 32768 ? nK : 32768;
+    double *dinvK = sc.alloc<double>(potrf_scratch_doubles(Mp, kchunk)), *dinvH = sc.alloc<double>(potrf_scratch_doubles(Mp, upp));
+    int32_t *info = sc.alloc<int32_t>((size_t)nK + GD);
+    OP_CHECK(hypers && (!C || dctrl) && w.Xs && w.log_Qs && Xt && w.Kuu && F && H && ubuf && w.U && dinvK && dinvH && info, who);
+
+    std::vector<int32_t> hinfo((size_t)nK + GD, 0);
+    for (int attempt = 0;; ++attempt) {
+        {
+            CholOverrideGuard guard;            // reset on the error returns below as well
+            if (attempt == 1) guard.force_left();
+            OP_TRY(hipMemsetAsync(info, 0, ((size_t)nK + GD) * sizeof(int32_t), sc.stream));
+            // 1. hyper-parameters of every (model, dim): prep_hypers' arithmetic, one launch, in HyperView's layout
+            gh.prep(sc.stream);
+            // 2. K_uu + jitter I -> L, L^-T (kernel_pre_cal, :124-169)
+            for (int k0 = 0; k0 < nK; k0 += kchunk) {
+                const int n = nK - k0 < kchunk ? nK - k0 : kchunk;
+                const HyperView hv{variance + k0, len + (size_t)k0 * P, Zsc + (size_t)k0 * Mp * P, zz + (size_t)k0 * Mp};
+                launch_kuu_build(sc.stream, kind, hv, M, Mp, P, n, in.jitter, w.Kuu + (size_t)k0 * kstride, nullptr);
+                launch_potrf_ext(sc.stream, w.Kuu + (size_t)k0 * kstride, Mp, Mp, Mp, n, kstride, info + k0, dinvK);
+            }
+            launch_pg_stage_x(sc.stream, w.Xs, G, T, D, Xt);
+            for (int g0 = 0; g0 < G; g0 += gpp) {
+                const int ngp = G - g0 < gpp ? G - g0 : gpp, nb = ngp * D, b0 = g0 * D;
+                // 3. F = K_fu L^-T (:212-213)
+                ProjectArgs pa{};
+                pa.kind = kind; pa.x_ld = D; pa.x_cols = D; pa.ctrl = dctrl; pa.T = T; pa.Tp = Tp; pa.C = C; pa.P = P; pa.M = M; pa.Mp = Mp;
+                pa.Dl = D; pa.d_begin = 0; pa.w_stride = kstride; pa.ng = ng;
+                if (nm == 1) {          // the ELBO's shape: chains s = b / D of one model
+                    pa.x = w.Xs; pa.x_chain_stride = (size_t)(T + 1) * D; pa.hv = HyperView{variance, len, Zsc, zz};
+                    pa.W = w.Kuu + (size_t)Mp * Mp; pa.b0 = b0; pa.nb = nb; pa.F = F;
+                    launch_project(sc.stream, pa);
+                } else {
+                    for (int gl = 0; gl < ngp; ++gl) {
+                        const size_t k0 = (size_t)(g0 + gl) * D;
+                        pa.x = w.Xs + (size_t)(g0 + gl) * (T + 1) * D; pa.x_chain_stride = 0;
+                        pa.hv = HyperView{variance + k0, len + k0 * P, Zsc + k0 * Mp * P, zz + k0 * Mp};
+                        pa.W = w.Kuu + k0 * kstride + (size_t)Mp * Mp; pa.b0 = 0; pa.nb = D; pa.F = F + (size_t)gl * D * fstride;
+                        launch_project(sc.stream, pa);
+                    }
+                }
+                // 4. H = I + F^T F / Q and b = F^T delta / Q (:214-217) into zeroed slabs with a device-set identity, then the chain
+                OP_TRY(hipMemsetAsync(H, 0, (size_t)nb * hstride * sizeof(double), sc.stream));
+                launch_set_identity(sc.stream, H, hstride, Mp, Mp, nb);
+                GramArgs ga{};
+                ga.mode = GRAM_F; ga.A = F; ga.a_stride = fstride; ga.rows = Tp; ga.with_row = 1; ga.brow = 2 * Mp;
+                ga.X = Xt; ga.log_Q = w.log_Qs; ga.T = T; ga.D = GD; ga.Mp = Mp; ga.Dl = GD; ga.d_begin = 0;      // one chain of G * D dims
+                ga.b0 = b0; ga.nb = nb; ga.yn_over_batch = 1.0; ga.H = H; ga.h_stride = hstride;
+                launch_gram(sc.stream, ga);
+                launch_potrf_ext(sc.stream, H, Mp, Mp + NB, Mp, nb, hstride, info + nK + b0, dinvH);
+                // 5. U_mean[:, d] = L_H^-T (L_H^-1 b) (:219)
+                launch_matvec(sc.stream, H + (size_t)Mp * Mp, hstride, H + (size_t)2 * Mp * Mp, hstride, Mp, ubuf, 1, M, M, nb);
+                launch_pg_unpack_u(sc.stream, ubuf, ngp, D, M, w.U + (size_t)g0 * M * D);
+                if (w.q0)               // slice d = 0 of each group
+                    launch_pg_pack(sc.stream, H, hstride, Mp, Mp, ngp, D, M, 1, w.q0 + (size_t)g0 * w.Mp16 * w.Mp16, w.Mp16, w.Mp16, ngp);
+                if (w.qall)             // every slice (q_mode "intent" of the grouped conditionals)
+                    launch_pg_pack(sc.stream, H, hstride, Mp, Mp, nb, 1, M, 1, w.qall + (size_t)b0 * Mp * Mp, Mp, Mp, nb);
+                if (w.Hpack)            // Lm_inverse_dd_seq = L_H^-T (:222)
+                    launch_pg_pack(sc.stream, H, hstride, Mp, Mp, nb, 1, M, 0, w.Hpack + (size_t)b0 * M * M, M, M, nb);
+            }
+        }
+        OP_TRY(hipGetLastError());
+        OP_TRY(hipMemcpyAsync(hinfo.data(), info, hinfo.size() * sizeof(int32_t), hipMemcpyDeviceToHost, sc.stream));
+        if (hipStreamSynchronize(sc.stream) != hipSuccess)
+            return set_error(nullptr, FFVD_EDEVICE, who + ": device error while reading Cholesky status");
+        for (int k = 0; k < nK; ++k)
+            if (hinfo[k] > 0)
+                return set_error(nullptr, FFVD_ENOTPD, who + ": Cholesky of K_uu + jitter*I failed: group " + std::to_string(k / D) +
+                                                       ", latent dim " + std::to_string(k % D) + ", pivot " + std::to_string(hinfo[k] - 1) +
+                                                       " is not positive");
+        bool stalled = false;
+        for (int32_t f : hinfo) stalled = stalled || f < 0;
+        if (stalled) {
+            if (attempt == 1)
+                return set_error(nullptr, FFVD_EDEVICE, who + ": abandoned, a block row waited more than 1 s for the row above it");
+            continue;
+        }
+        for (int b = 0; b < GD; ++b)
+            if (hinfo[nK + b] > 0)
+                return set_error(nullptr, FFVD_ENOTPD, who + ": Cholesky of H failed: group " + std::to_string(b / D) + ", latent dim " +
+                                                       std::to_string(b % D) + ", pivot " + std::to_string(hinfo[nK + b] - 1) +
+                                                       " is not positive");
+        if (attempt == 1)
+            set_error(nullptr, FFVD_OK, "warning: " + who + ": the one-launch (dataflow) Cholesky gave up on a bounded wait; the posteriors "
+                                        "were formed again with the launch-per-column Cholesky and completed");
+        return FFVD_OK;
+    }
+}
+}  // namespace
+
+extern "C" int ffvd_op_posterior_grouped(int kind, int G, int n_models, const double *Zs, int M, int P, int D, const double *logvariances,
+                                         const double *loglengthscales, const double *Xs, const double *ctrl_fit, int C, int T,
+                                         const double *log_Qs, double jitter, int groups_per_pass, double *Lm_inverse, double *U_means,
+                                         double *H_inv_sqrts) {
+    const std::string who = "ffvd_op_posterior_grouped", bad = who + ": bad argument";
+    if (!pg_scalars_ok(kind, G, n_models, M, P, D, C, T, groups_per_pass, jitter)) return set_error(nullptr, FFVD_EINVAL, bad);
+    if (G == 0) return FFVD_OK;
+    if (!Zs || !logvariances || !Xs || !log_Qs || !U_means || (C > 0 && !ctrl_fit) || (kind == FFVD_KERNEL_SE && !loglengthscales))
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    OP_BEGIN(who);
+    PgIn in{who, kind, G, n_models, M, P, D, C, T, groups_per_pass, Zs, logvariances, loglengthscales, Xs, ctrl_fit, log_Qs, jitter};
+    PgWork w{};
+    const size_t GD = (size_t)G * D, MM = (size_t)M * M, nK = (size_t)n_models * D;
+    if (H_inv_sqrts) w.Hpack = sc.alloc<double>(GD * MM);
+    double *Lpack = Lm_inverse ? sc.alloc<double>(nK * MM) : nullptr;
+    OP_CHECK((!H_inv_sqrts || w.Hpack) && (!Lm_inverse || Lpack), who);
+    if (int rc = pg_posterior(sc, in, w)) return rc;
+    if (Lpack) launch_pg_pack(sc.stream, w.Kuu, (size_t)2 * w.Mp * w.Mp, w.Mp, w.Mp, (int)nK, 1, M, 0, Lpack, M, M, (int)nK);
+    OP_TRY(hipGetLastError());
+    if (!sc.download(U_means, w.U, GD * M * sizeof(double)) || (H_inv_sqrts && !sc.download(H_inv_sqrts, w.Hpack, GD * MM * sizeof(double))) ||
+        (Lpack && !sc.download(Lm_inverse, Lpack, nK * MM * sizeof(double))))
+        return set_error(nullptr, FFVD_EDEVICE, who + ": copying the results back failed");
+    return FFVD_OK;
+}
+
+// The posteriors above handed to the grouped rollout loop (base_model.py:243-314 per group) without leaving the device: W, q0, f and
+// x_last of RolloutGroupArgs are written by posterior_group.hip's kernels from the factorisation slabs, then rg_run.
+static int posterior_rollout_grouped_run(const std::string &who, int kind, int G, int n_models, const double *Zs, int M, int P, int D,
+                                         const double *logvariances, const double *loglengthscales, const double *Xs,
+                                         const double *ctrl_fit, int C, int T, const double *log_Qs, double jitter, int groups_per_pass,
+                                         int R, const double *ctrl_roll, int steps, const double *eps, double *predict_x,
+                                         double *predict_var, double *U_means, const SummaryReq *sum) {
+    const std::string bad = who + ": bad argument";
+    if (!pg_scalars_ok(kind, G, n_models, M, P, D, C, T, groups_per_pass, jitter) || R < 1 || steps < 0)
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    const int Mp16 = round_up(M, RG_SLAB);
+    if (!rg_limits_ok(G, D, R, Mp16)) return set_error(nullptr, FFVD_EINVAL, bad + " (beyond the limits of rollout_group.h)");
+    if (sum && !summary_scalars_ok(*sum, (long long)G * R, steps, D)) return set_error(nullptr, FFVD_EINVAL, bad);
+    if (G == 0 || steps == 0) return FFVD_OK;
+    if (!Zs || !logvariances || !Xs || !log_Qs || !eps || (!sum && (!predict_x || !predict_var)) || (C > 0 && (!ctrl_fit || !ctrl_roll)) ||
+        (kind == FFVD_KERNEL_SE && !loglengthscales) || (sum && !summary_arrays_ok(*sum)))
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    OP_BEGIN(who);
+    LapTimer timer("FFVD_RG_TIMING", who.c_str(), sc.stream);
+    PgIn in{who, kind, G, n_models, M, P, D, C, T, groups_per_pass, Zs, logvariances, loglengthscales, Xs, ctrl_fit, log_Qs, jitter};
+    PgWork w{};
+    const size_t GD = (size_t)G * D, mm16 = (size_t)Mp16 * Mp16;
+    w.Mp16 = Mp16; w.q0 = sc.alloc<double>((size_t)G * mm16);
+    double *dW = sc.alloc<double>(GD * mm16), *dB = sc.alloc<double>(GD * mm16);
+    OP_CHECK(w.q0 && dW && dB, who);
+    if (int rc = pg_posterior(sc, in, w)) return rc;
+    timer.lap("posteriors");
+    // the rollout loop's own copy of the small inputs, one row per group (a shared model is repeated: launch_rg_step indexes by group)
+    const double *hZ = Zs, *hlv = logvariances, *hll = loglengthscales;
+    if (n_models == 1 && G > 1) {
+        std::vector<double> &rz = sc.host((size_t)G * M * P), &rv = sc.host(GD), &rl = sc.host(loglengthscales ? GD * P : 0);
+        for (int g = 0; g < G; ++g) {
+            memcpy(rz.data() + (size_t)g * M * P, Zs, (size_t)M * P * sizeof(double));
+            memcpy(rv.data() + (size_t)g * D, logvariances, D * sizeof(double));
+            if (loglengthscales) memcpy(rl.data() + (size_t)g * D * P, loglengthscales, (size_t)D * P * sizeof(double));
+        }
+        hZ = rz.data(); hlv = rv.data(); hll = loglengthscales ? rl.data() : nullptr;
+    }
+    GroupHypers gh = stage_group_hypers(sc, kind, G, D, M, Mp16, P, hZ, hlv, hll);
+    gh.logs(sc);
+    double *deps = sc.upload(eps, (size_t)steps * G * R * D), *dctrl = C ? sc.upload(ctrl_roll, (size_t)steps * C) : nullptr, *dxl = sc.alloc<double>(GD);
+    OP_CHECK(gh.uploaded && deps && (!C || dctrl) && dxl, who);
+    // W[g][d] = L^-T of the group's model; with one model every group reads the same slab (the stack is still materialised)
+    launch_pg_pack(sc.stream, w.Kuu, (size_t)2 * w.Mp * w.Mp, w.Mp, w.Mp, w.nK, 1, M, 1, dW, Mp16, Mp16, (int)GD);
+    launch_pg_x_last(sc.stream, w.Xs, G, T, D, dxl);
+    // (q_upper: q0's strict lower triangle was written as exact zeros)
+    return rg_run(sc, who, timer, "operands packed, W q_sqrt", gh, R, C, steps, dW, w.q0, dB, 1, w.U, dxl, w.log_Qs, dctrl, deps, predict_x,
+                  predict_var, U_means, sum);
+}
+
+extern "C" int ffvd_op_posterior_rollout_grouped(int kind, int G, int n_models, const double *Zs, int M, int P, int D,
+                                                 const double *logvariances, const double *loglengthscales, const double *Xs,
+                                                 const double *ctrl_fit, int C, int T, const double *log_Qs, double jitter,
+                                                 int groups_per_pass, int R, const double *ctrl_roll, int steps, const double *eps,
+                                                 double *predict_x, double *predict_var, double *U_means) {
+    return posterior_rollout_grouped_run("ffvd_op_posterior_rollout_grouped", kind, G, n_models, Zs, M, P, D, logvariances, loglengthscales,
+                                         Xs, ctrl_fit, C, T, log_Qs, jitter, groups_per_pass, R, ctrl_roll, steps, eps, predict_x,
+                                         predict_var, U_means, nullptr);
+}
+
+extern "C" int ffvd_op_posterior_rollout_grouped_summary(int kind, int G, int n_models, const double *Zs, int M, int P, int D,
+                                                         const double *logvariances, const double *loglengthscales, const double *Xs,
+                                                         const double *ctrl_fit, int C, int T, const double *log_Qs, double jitter,
+                                                         int groups_per_pass, int R, const double *ctrl_roll, int steps,
+                                                         const double *eps, double *predict_x, double *predict_var, double *U_means,
+                                                         const double *CC, const double *DD, const double *noise_std, int J,
+                                                         const double *Y_test, int n_test, double *y_mean, double *y_var,
+                                                         double *y_var_total, double *lpd, double *lpd_gauss) {
+    const SummaryReq q{CC, DD, noise_std, J, Y_test, n_test, y_mean, y_var, y_var_total, lpd, lpd_gauss};
+    return posterior_rollout_grouped_run("ffvd_op_posterior_rollout_grouped_summary", kind, G, n_models, Zs, M, P, D, logvariances,
+                                         loglengthscales, Xs, ctrl_fit, C, T, log_Qs, jitter, groups_per_pass, R, ctrl_roll, steps, eps,
+                                         predict_x, predict_var, U_means, &q);
+}
+
+// ---- grouped GP conditionals (conditional_group.h) ------------------------------------------------------------------------------------
+// conditional_after_kernel_precalculation (conditionals_multi_output.py:306-387, white=True, full_cov=False) for G posteriors at N
+// common inputs: F = K(Xnew, Z) L^-T (:349) once per (model, dim), mean = F U_g (:365), var = Kdiag - sum F^2 (:356) + sum (F q)^2
+// (:369-380), and the equal-weight mixture over the groups.
+namespace {
+struct CgOut { double *means, *vars, *mix_mean, *mix_var; };
+
+// scalar-argument checks shared by the two entry points (before any device call); C = P - D
+bool cg_scalars_ok(int kind, int G, int n_models, int M, int P, int D, int N, int q_mode, int rows_per_pass) {
+    if (!((kind == FFVD_KERNEL_SE || kind == FFVD_KERNEL_LINEAR) && G >= 0 && M >= 1 && M <= 2048 && D >= 1 && P >= D && P <= MAXP &&
+          N >= 0 && (q_mode == 0 || q_mode == 1) && rows_per_pass >= 0 && (n_models == 1 || n_models == G) &&
+          (long long)G * D <= (1LL << 24)))
+        return false;
+    const long long Mp = round_up(M, NB);
+    return (long long)G * D * Mp * Mp <= (1LL << 29) && (long long)G * D * N < (1LL << 31);
+}
+bool cg_outputs_ok(const CgOut &o) { return (o.means || o.vars || o.mix_mean) && (!o.mix_mean == !o.mix_var); }
+
+// The launches of conditional_group.h on operands that are already on the device, then the requested outputs come down.
+int cg_run(Scratch &sc, const std::string &who, int kind, int G, int nm, int M, int P, int D, int N, int rows_per_pass, const HyperView &hv,
+           const double *W, size_t w_stride, const double *dU, const double *dq, int q_per_dim, int q_upper, const double *dX,
+           const CgOut &o) {
+    const int Mp = round_up(M, NB);
+    const size_t out_n = (size_t)G * N * D, ND = (size_t)N * D;
+    CondGroupArgs a{};
+    a.kind = kind; a.G = G; a.n_models = nm; a.M = M; a.Mp = Mp; a.P = P; a.D = D; a.N = N;
+    a.rows_per_pass = rows_per_pass > 0 ? rows_per_pass : cg_rows_per_pass(nm, D, Mp);
+    a.hv = hv; a.W = W; a.w_stride = w_stride; a.U = dU; a.q = dq; a.q_per_dim = q_per_dim; a.q_upper = q_upper; a.x = dX;
+    a.need_var = (o.vars || o.mix_var) ? 1 : 0;
+    const CondGroupScratch need = cg_scratch_doubles(G, nm, D, Mp, N, a.rows_per_pass, a.need_var && dq);
+    a.F = sc.alloc<double>(need.F); a.rowsq = sc.alloc<double>(need.rowsq); a.Ut = sc.alloc<double>(need.Ut); a.mbuf = sc.alloc<double>(need.mbuf);
+    a.part = need.part ? sc.alloc<double>(need.part) : nullptr;
+    a.mean = sc.alloc<double>(out_n);
+    a.var = a.need_var ? sc.alloc<double>(out_n) : nullptr;
+    double *dmm = o.mix_mean ? sc.alloc<double>(ND) : nullptr, *dmv = o.mix_mean ? sc.alloc<double>(ND) : nullptr;
+    OP_CHECK(a.F && a.rowsq && a.Ut && a.mbuf && (!need.part || a.part) && a.mean && (!a.need_var || a.var) && (!o.mix_mean || (dmm && dmv)), who);
+    launch_conditional_group(sc.stream, a);
+    if (o.mix_mean) launch_cg_mixture(sc.stream, a.mean, a.var, G, ND, dmm, dmv);
+    OP_TRY(hipGetLastError());
+    if ((o.means && !sc.download(o.means, a.mean, out_n * sizeof(double))) || (o.vars && !sc.download(o.vars, a.var, out_n * sizeof(double))) ||
+        (o.mix_mean && (!sc.download(o.mix_mean, dmm, ND * sizeof(double)) || !sc.download(o.mix_var, dmv, ND * sizeof(double)))))
+        return set_error(nullptr, FFVD_EDEVICE, who + ": copying the results back failed");
+    OP_TRY(hipStreamSynchronize(sc.stream));
+    return FFVD_OK;
+}
+}  // namespace
+
+// Posteriors given by the caller (also explicit-U models and SG-HMC samples of U: q_sqrts = NULL)
+extern "C" int ffvd_op_conditional_grouped(int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M, int P,
+                                           int D, const double *logvariances, const double *loglengthscales, const double *fs,
+                                           const double *const *q_sqrts, int q_mode, const double *Xnew, int N, int rows_per_pass,
+                                           double *means, double *vars, double *mix_mean, double *mix_var) {
+    const std::string who = "ffvd_op_conditional_grouped", bad = who + ": bad argument";
+    if (!cg_scalars_ok(kind, G, n_models, M, P, D, N, q_mode, rows_per_pass)) return set_error(nullptr, FFVD_EINVAL, bad);
+    if (G == 0 || N == 0) return FFVD_OK;
+    const CgOut out{means, vars, mix_mean, mix_var};
+    if (!Lm_inverse_seqs || !Zs || !logvariances || !fs || !Xnew || !cg_outputs_ok(out) || (kind == FFVD_KERNEL_SE && !loglengthscales))
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    const size_t nK = (size_t)n_models * D, nq = given_nq(q_sqrts, q_mode, G, D);
+    if (!given_tables_ok(Lm_inverse_seqs, nK, q_sqrts, nq)) return set_error(nullptr, FFVD_EINVAL, bad);
+    OP_BEGIN(who);
+    const int Mp = round_up(M, NB);
+    double *dW = upload_matrix_table(sc, Lm_inverse_seqs, nK, M, Mp);
+    const int q_upper = given_q_upper(q_sqrts, nq, M);
+    double *dq = nq ? upload_matrix_table(sc, q_sqrts, nq, M, Mp) : nullptr;
+    GroupHypers gh = stage_group_hypers(sc, kind, n_models, D, M, Mp, P, Zs, logvariances, loglengthscales);
+    double *dU = sc.upload(fs, (size_t)G * D * M), *dX = sc.upload(Xnew, (size_t)N * P);
+    OP_CHECK(dW && (!nq || dq) && dU && dX && gh.logs(sc) && gh.blocks(sc), who);
+    gh.prep(sc.stream);
+    return cg_run(sc, who, kind, G, n_models, M, P, D, N, rows_per_pass, gh.hv(), dW, (size_t)Mp * Mp, dU, dq, q_mode, q_upper, dX, out);
+}
+
+// The collapsed posteriors of ffvd_op_posterior_grouped (base_model.py:243-256) evaluated at Xnew without leaving the device: L^-T is
+// read in the K_uu slabs, U_mean where the matvec left it, the q slices are packed by launch_pg_pack (exact zeros in the padding and
+// the strict lower triangle, so the k cut holds by construction).
+extern "C" int ffvd_op_posterior_conditional_grouped(int kind, int G, int n_models, const double *Zs, int M, int P, int D,
+                                                     const double *logvariances, const double *loglengthscales, const double *Xs,
+                                                     const double *ctrl_fit, int C, int T, const double *log_Qs, double jitter,
+                                                     int groups_per_pass, int q_mode, const double *Xnew, int N, int rows_per_pass,
+                                                     double *means, double *vars, double *mix_mean, double *mix_var, double *U_means) {
+    const std::string who = "ffvd_op_posterior_conditional_grouped", bad = who + ": bad argument";
+    if (!pg_scalars_ok(kind, G, n_models, M, P, D, C, T, groups_per_pass, jitter) ||
+        !cg_scalars_ok(kind, G, n_models, M, P, D, N, q_mode, rows_per_pass))
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    if (G == 0 || N == 0) return FFVD_OK;
+    const CgOut out{means, vars, mix_mean, mix_var};
+    if (!Zs || !logvariances || !Xs || !log_Qs || !Xnew || !cg_outputs_ok(out) || (C > 0 && !ctrl_fit) ||
+        (kind == FFVD_KERNEL_SE && !loglengthscales))
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    OP_BEGIN(who);
+    PgIn in{who, kind, G, n_models, M, P, D, C, T, groups_per_pass, Zs, logvariances, loglengthscales, Xs, ctrl_fit, log_Qs, jitter};
+    PgWork w{};
+    const size_t mm = (size_t)round_up(M, NB) * round_up(M, NB);
+    const bool need_q = vars || mix_var, have_q = need_q && pg_want_q(sc, w, q_mode, G, D, M);
+    double *dX = sc.upload(Xnew, (size_t)N * P);
+    OP_CHECK(dX && (!need_q || have_q), who);
+    if (int rc = pg_posterior(sc, in, w)) return rc;
+    if (int rc = cg_run(sc, who, kind, G, n_models, M, P, D, N, rows_per_pass, w.hv, w.Kuu + mm, 2 * mm, w.U, pg_q(w, q_mode), q_mode, 1, dX, out))
+        return rc;
+    if (U_means && !sc.download(U_means, w.U, (size_t)G * D * M * sizeof(double)))
+        return set_error(nullptr, FFVD_EDEVICE, who + ": copying the results back failed");
+    return FFVD_OK;
+}
+
+// ---- moment-matched prediction (moment_group.h) ---------------------------------------------------------------------------------------
+// A Gaussian state of each of G posteriors pushed through x_{t+1} = x_t + f(x_t, c_t) + noise in closed form (SE-ARD only), one launch
+// per step for all groups; optionally summarised as a held-out prediction before anything comes down.
+namespace {
+// scalar-argument checks shared by the two entry points (before any device call)
+bool mg_scalars_ok(int kind, int G, int n_models, int M, int P, int D, int C, int steps, int q_mode) {
+    if (!(kind == FFVD_KERNEL_SE && G >= 0 && steps >= 0 && M >= 1 && M <= 2048 && D >= 1 && D <= MG_MAXD && C >= 0 && P == D + C &&
+          P <= MAXP && (q_mode == 0 || q_mode == 1) && (n_models == 1 || n_models == G) && (long long)G * D <= (1LL << 24)))
+        return false;
+    const long long Mp = round_up(M, NB), NS = (M + MG_SLAB - 1) / MG_SLAB;
+    return (long long)G * D * Mp * Mp <= (1LL << 29) && (long long)G * mg_npair(D) * NS < (1LL << 31) &&
+           (steps == 0 || G <= ((1LL << 31) - 1) / steps / D / D);
+}
+// the trailing summary block of the entry points: asked for when anything in it is given
+bool mg_summary_wanted(const SummaryReq &q) {
+    return q.CC || q.DD || q.noise_std || q.J != 0 || q.Y_test || q.n_test != 0 || q.y_mean || q.y_var || q.y_var_total || q.lpd || q.lpd_gauss;
+}
+
+// The filter request of mg_run: the emission, the observations (NaN = unobserved) and the outputs, each of which may be NULL
+struct FilterReq {
+    const double *CC, *DD, *noise_std;           // D x J, J, J
+    int J;
+    const double *Y_obs;                         // steps x J
+    double *m_filt, *S_filt, *cross, *lpd, *lpd_joint, *m_smooth, *S_smooth;
+    double *y_mean, *y_var_total, *lpd_mix, *lpd_gauss;      // the pooled one-step summary (steps x J)
+    // ... as a summary request on the predicted stacks: every row carries an observation row (NaN entries give NaN densities)
+    SummaryReq pooled(int steps) const { return SummaryReq{CC, DD, noise_std, J, Y_obs, steps, y_mean, nullptr, y_var_total, lpd_mix, lpd_gauss}; }
+};
+// the checks of a filter request that need no array, and those that read the small arrays (Y_obs: no infinity)
+bool filter_scalars_ok(const FilterReq &f) { return f.J >= 1 && f.J <= MG_MAXJ; }
+bool filter_arrays_ok(const FilterReq &f, int steps, const double *m_pred, const double *S_pred) {
+    if (!f.CC || !f.DD || !f.noise_std || !f.Y_obs) return false;
+    if (!(m_pred || S_pred || f.m_filt || f.S_filt || f.cross || f.lpd || f.lpd_joint || f.m_smooth || f.S_smooth || f.y_mean ||
+          f.y_var_total || f.lpd_mix || f.lpd_gauss))
+        return false;
+    for (int j = 0; j < f.J; ++j)
+        if (!std::isfinite(f.noise_std[j]) || !(f.noise_std[j] > 0.0)) return false;
+    for (size_t e = 0; e < (size_t)steps * f.J; ++e)
+        if (std::isinf(f.Y_obs[e])) return false;
+    return true;
+}
+
+// Operands on the device -> beta, Gamma, the step launches, the summary, the downloads.  flt: the launches are those of the filter
+// (moment_group.h), m_x / S_x are the predicted moments, and `sum` is REPLACED by the pooled one-step summary of the request when that
+// asks for one (the filter callers pass nullptr).  dW: [n_models * D] slots of Mp x Mp (upper triangular, zero padded); dq: nullptr,
+// or [G] (q_mode 0) / [G * D] (q_mode 1) slots of Mp x Mp; hv: variance / len per (model, dim).
+int mg_run(Scratch &sc, const std::string &who, int G, int nm, int M, int P, int D, int C, int steps, const HyperView &hv, const double *dZ,
+           const double *dW, const double *dq, int q_mode, const double *dU, const double *dxl, const double *dS0, const double *dlq,
+           const double *dctrl, double *m_x, double *S_x, const SummaryReq *sum, const FilterReq *flt) {
+    const int Mp = round_up(M, NB), NS = (M + MG_SLAB - 1) / MG_SLAB, nK = nm * D, GD = G * D;
+    const size_t mm = (size_t)Mp * Mp, nm_x = (size_t)G * steps * D, nS_x = nm_x * D;
+    const SummaryReq fsum = flt ? flt->pooled(steps) : SummaryReq{};
+    if (fsum.y_mean || fsum.y_var_total || fsum.lpd || fsum.lpd_gauss) sum = &fsum;
+    const int units = dq ? GD : nK, nq = dq ? (q_mode ? GD : G) : 0;
+    double *beta = sc.alloc<double>((size_t)GD * Mp), *gam = sc.alloc<double>((size_t)units * mm);
+    double *dN = dq ? sc.alloc<double>((size_t)nq * mm) : nullptr, *dE = dq ? sc.alloc<double>((size_t)nq * mm) : nullptr;
+    double *dWE = dq ? sc.alloc<double>((size_t)GD * mm) : nullptr;
+    double *unused = sc.alloc<double>((size_t)(nq > units ? nq : units));          // (cov.hip reads a variance per slot for its seed: none here)
+    double *part = sc.alloc<double>((size_t)2 * G * mg_fields(D) * NS), *state = sc.alloc<double>((size_t)2 * G * (D + D * D));
+    double *dm = sc.alloc<double>(nm_x), *dS = sc.alloc<double>(nS_x);
+    OP_CHECK(beta && gam && (!dq || (dN && dE && dWE)) && unused && part && state && dm && dS, who);
+    MomentFilterArgs fa{};
+    MomentSmoothArgs sa{};
+    const bool smooth = flt && (flt->m_smooth || flt->S_smooth);
+    const size_t nlpd = flt ? (size_t)G * steps * flt->J : 0, nlj = (size_t)G * steps;
+    if (flt) {
+        const Emission e = stage_emission(sc, D, flt->J, flt->CC, flt->DD, flt->noise_std, flt->Y_obs, steps);
+        fa.J = flt->J; fa.CC = e.CC; fa.DD = e.DD; fa.sd = e.sd; fa.Y = e.Y;
+        fa.m_filt = sc.alloc<double>(nm_x); fa.S_filt = sc.alloc<double>(nS_x); fa.cross = sc.alloc<double>(nS_x);
+        fa.lpd = sc.alloc<double>(nlpd); fa.lpd_joint = sc.alloc<double>(nlj);
+        OP_CHECK(e.ok && fa.m_filt && fa.S_filt && fa.cross && fa.lpd && fa.lpd_joint, who);
+        if (smooth) {
+            sa.G = G; sa.D = D; sa.steps = steps; sa.m_pred = dm; sa.S_pred = dS; sa.m_filt = fa.m_filt; sa.S_filt = fa.S_filt;
+            sa.cross = fa.cross; sa.m_smooth = sc.alloc<double>(nm_x); sa.S_smooth = sc.alloc<double>(nS_x);
+            OP_CHECK(sa.m_smooth && sa.S_smooth, who);
+        }
+    }
+    launch_mg_beta(sc.stream, G, D, M, Mp, nm == G, dW, dU, beta);
+    // Gamma = W (I - q q^T) W^T through cov.hip's product body.  COV_GEN: C = A B^T, all Mp x Mp entries written.
+    CovArgs gen{};
+    gen.mode = COV_GEN; gen.a_stride = mm; gen.lda = Mp; gen.arows = Mp; gen.K = Mp; gen.ldb = Mp; gen.brows = Mp; gen.ncols = Mp;
+    gen.c_stride = mm; gen.ldc = Mp;
+    auto product = [&](const double *A, const double *B, size_t b_stride, double *Cdst, int n) {
+        for (int u0 = 0; u0 < n; u0 += 32768) {                                       // (grid y)
+            gen.A = A + (size_t)u0 * mm; gen.B = B + (size_t)u0 * b_stride; gen.b_stride = b_stride; gen.C = Cdst + (size_t)u0 * mm;
+            gen.nb = n - u0 < 32768 ? n - u0 : 32768;
+            launch_cov(sc.stream, gen);
+        }
+    };
+    if (!dq) product(dW, dW, mm, gam, nK);                                            // W W^T per (model, dim)
+    else {
+        // E = I - q q^T as (N + N^T) - N N^T with N = I - q: no cancellation where q is close to the identity, which is where W is
+        // large.  -N N^T: the symmetric product C = seed - A A^T with an empty seed (a LinearK seed over P = 0 columns is an exact zero).
+        OP_TRY(hipMemsetAsync(dE, 0, (size_t)nq * mm * sizeof(double), sc.stream));
+        CovArgs sym{};
+        sym.mode = COV_SYM; sym.a_stride = mm; sym.lda = Mp; sym.arows = Mp; sym.K = Mp; sym.c_stride = mm; sym.ldc = Mp; sym.N = M;
+        sym.kind = FFVD_KERNEL_LINEAR; sym.P = 0; sym.variance = unused; sym.len = hv.len;
+        for (int u0 = 0; u0 < nq; u0 += 32768) {
+            const int n = nq - u0 < 32768 ? nq - u0 : 32768;
+            launch_mg_nmat(sc.stream, n, M, Mp, dq + (size_t)u0 * mm, dN + (size_t)u0 * mm);
+            sym.A = dN + (size_t)u0 * mm; sym.C = dE + (size_t)u0 * mm; sym.nb = n;
+            launch_cov(sc.stream, sym);
+            launch_mg_emat(sc.stream, n, M, Mp, dN + (size_t)u0 * mm, dE + (size_t)u0 * mm);
+        }
+        // (W E) W^T per (group, dim); E is symmetric, so W E = W E^T.  One launch pair per group: a group's W and E slots are
+        // contiguous whichever of them is shared
+        for (int g = 0; g < G; ++g) {
+            const double *Wg = dW + (nm == G ? (size_t)g * D * mm : 0);
+            double *WEg = dWE + (size_t)g * D * mm;
+            product(Wg, q_mode ? dE + (size_t)g * D * mm : dE + (size_t)g * mm, q_mode ? mm : 0, WEg, D);
+            product(WEg, Wg, mm, gam + (size_t)g * D * mm, D);
+        }
+    }
+    MomentGroupArgs a{};
+    a.G = G; a.n_models = nm; a.D = D; a.C = C; a.P = P; a.M = M; a.Mp = Mp; a.NS = NS; a.steps = steps; a.unit_per_group = dq ? 1 : 0;
+    a.Z = dZ; a.variance = hv.variance; a.len = hv.len; a.beta = beta; a.gam = gam; a.x_last = dxl; a.S0 = dS0; a.log_Q = dlq;
+    a.ctrl = dctrl; a.part = part; a.state = state; a.m_x = dm; a.S_x = dS;
+    if (!flt)
+        for (int t = 0; t <= steps; ++t) launch_mg_step(sc.stream, a, t);
+    else {
+        for (int t = 0; t <= steps; ++t) launch_mg_filter_step(sc.stream, a, fa, t);
+        if (smooth) launch_mg_smooth(sc.stream, sa);
+    }
+    OP_TRY(hipGetLastError());
+    if (sum)
+        if (int rc = mg_summary(sc, who, dm, dS, G, steps, D, *sum)) return rc;
+    if (flt) {
+        auto down = [&](double *dst, const double *src, size_t n) { return !dst || sc.download(dst, src, n * sizeof(double)); };
+        if (!down(flt->m_filt, fa.m_filt, nm_x) || !down(flt->S_filt, fa.S_filt, nS_x) || !down(flt->cross, fa.cross, nS_x) ||
+            !down(flt->lpd, fa.lpd, nlpd) || !down(flt->lpd_joint, fa.lpd_joint, nlj) || !down(flt->m_smooth, sa.m_smooth, nm_x) ||
+            !down(flt->S_smooth, sa.S_smooth, nS_x))
+            return set_error(nullptr, FFVD_EDEVICE, who + ": copying the results back failed");
+    }
+    if ((m_x && !sc.download(m_x, dm, nm_x * sizeof(double))) || (S_x && !sc.download(S_x, dS, nS_x * sizeof(double))))
+        return set_error(nullptr, FFVD_EDEVICE, who + ": copying the results back failed");
+    OP_TRY(hipStreamSynchronize(sc.stream));
+    return FFVD_OK;
+}
+const char *const mg_se_only = " (moment matching is closed-form for the SE kernel only)";
+
+// Posteriors given by the caller (also explicit-U models, SG-HMC samples of U: q_sqrts = NULL) through mg_run, scalars and pointers checked
+int mg_given_run(const std::string &who, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M, int P, int D,
+                 const double *logvariances, const double *loglengthscales, const double *fs, const double *const *q_sqrts, int q_mode,
+                 const double *x_lasts, const double *S0s, const double *ctrl, int C, int steps, const double *log_Qs, double *m_x,
+                 double *S_x, const SummaryReq *sum, const FilterReq *flt) {
+    const size_t nK = (size_t)n_models * D, GD = (size_t)G * D, nq = given_nq(q_sqrts, q_mode, G, D);
+    if (!given_tables_ok(Lm_inverse_seqs, nK, q_sqrts, nq)) return set_error(nullptr, FFVD_EINVAL, who + ": bad argument");
+    OP_BEGIN(who);
+    const int Mp = round_up(M, NB);
+    double *dW = upload_matrix_table(sc, Lm_inverse_seqs, nK, M, Mp), *dq = nq ? upload_matrix_table(sc, q_sqrts, nq, M, Mp) : nullptr;
+    GroupHypers gh = stage_group_hypers(sc, FFVD_KERNEL_SE, n_models, D, M, Mp, P, Zs, logvariances, loglengthscales);
+    double *dU = sc.upload(fs, GD * M), *dxl = sc.upload(x_lasts, GD), *dS0 = S0s ? sc.upload(S0s, GD * D) : nullptr, *dlq = sc.upload(log_Qs, GD);
+    double *dctrl = C ? sc.upload(ctrl, (size_t)steps * C) : nullptr;
+    OP_CHECK(dW && (!nq || dq) && dU && dxl && (!S0s || dS0) && dlq && (!C || dctrl) && gh.logs(sc) && gh.blocks(sc), who);
+    gh.prep(sc.stream);
+    return mg_run(sc, who, G, n_models, M, P, D, C, steps, gh.hv(), gh.dZ, dW, dq, q_mode, dU, dxl, dS0, dlq, dctrl, m_x, S_x, sum, flt);
+}
+
+// The collapsed posteriors of ffvd_op_posterior_grouped (base_model.py:243-256) through mg_run without leaving the device: L^-T is
+// packed from the K_uu slabs, U_mean read where the matvec left it, the q slices packed by launch_pg_pack (exact zeros in the padding
+// and the strict lower triangle); the start means are x0s or, without them, the last rows of Xs.
+int mg_posterior_run(const PgIn &in, int q_mode, const double *x0s, const double *S0s, const double *ctrl_roll, int steps, double *m_x,
+                     double *S_x, double *U_means, const SummaryReq *sum, const FilterReq *flt) {
+    const std::string &who = in.who;
+    OP_BEGIN(who);
+    PgWork w{};
+    const int G = in.G, D = in.D, M = in.M, C = in.C, nm = in.n_models, Mp = round_up(M, NB), nK = nm * D;
+    const size_t GD = (size_t)G * D, mm = (size_t)Mp * Mp;
+    const bool have_q = pg_want_q(sc, w, q_mode, G, D, M);
+    double *dW = sc.alloc<double>((size_t)nK * mm), *dxl = x0s ? sc.upload(x0s, GD) : sc.alloc<double>(GD);
+    OP_CHECK(have_q && dW && dxl, who);
+    if (int rc = pg_posterior(sc, in, w)) return rc;
+    double *dZ = sc.upload(in.Zs, (size_t)nm * M * in.P), *dS0 = S0s ? sc.upload(S0s, GD * D) : nullptr;
+    double *dctrl = C ? sc.upload(ctrl_roll, (size_t)steps * C) : nullptr;
+    OP_CHECK(dZ && (!S0s || dS0) && (!C || dctrl), who);
+    launch_pg_pack(sc.stream, w.Kuu, 2 * mm, Mp, Mp, nK, 1, M, 1, dW, Mp, Mp, nK);
+    if (!x0s) launch_pg_x_last(sc.stream, w.Xs, G, in.T, D, dxl);
+    if (int rc = mg_run(sc, who, G, nm, M, in.P, D, C, steps, w.hv, dZ, dW, pg_q(w, q_mode), q_mode, w.U, dxl, dS0, w.log_Qs, dctrl, m_x, S_x,
+                        sum, flt))
+        return rc;
+    if (U_means && !sc.download(U_means, w.U, GD * M * sizeof(double)))
+        return set_error(nullptr, FFVD_EDEVICE, who + ": copying the results back failed");
+    return FFVD_OK;
+}
+}  // namespace
+
+extern "C" int ffvd_op_moment_grouped(int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M, int P,
+                                      int D, const double *logvariances, const double *loglengthscales, const double *fs,
+                                      const double *const *q_sqrts, int q_mode, const double *x_lasts, const double *S0s,
+                                      const double *ctrl, int C, int steps, const double *log_Qs, double *m_x, double *S_x,
+                                      const double *CC, const double *DD, const double *noise_std, int J, const double *Y_test, int n_test,
+                                      double *y_mean, double *y_var, double *y_var_total, double *lpd, double *lpd_gauss) {
+    const std::string who = "ffvd_op_moment_grouped", bad = who + ": bad argument";
+    const SummaryReq q{CC, DD, noise_std, J, Y_test, n_test, y_mean, y_var, y_var_total, lpd, lpd_gauss};
+    const SummaryReq *sum = mg_summary_wanted(q) ? &q : nullptr;
+    if (kind != FFVD_KERNEL_SE) return set_error(nullptr, FFVD_EINVAL, bad + mg_se_only);
+    if (!mg_scalars_ok(kind, G, n_models, M, P, D, C, steps, q_mode) || (sum && !summary_scalars_ok(q, G, steps, D)))
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    if (G == 0 || steps == 0) return FFVD_OK;
+    if (!Lm_inverse_seqs || !Zs || !logvariances || !loglengthscales || !fs || !x_lasts || !log_Qs || (C > 0 && !ctrl) ||
+        (!sum && (!m_x || !S_x)) || (sum && !summary_arrays_ok(q)))
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    return mg_given_run(who, G, n_models, Lm_inverse_seqs, Zs, M, P, D, logvariances, loglengthscales, fs, q_sqrts, q_mode, x_lasts, S0s, ctrl,
+                        C, steps, log_Qs, m_x, S_x, sum, nullptr);
+}
+
+extern "C" int ffvd_op_posterior_moment_grouped(int kind, int G, int n_models, const double *Zs, int M, int P, int D,
+                                                const double *logvariances, const double *loglengthscales, const double *Xs,
+                                                const double *ctrl_fit, int C, int T, const double *log_Qs, double jitter,
+                                                int groups_per_pass, int q_mode, const double *S0s, const double *ctrl_roll, int steps,
+                                                double *m_x, double *S_x, double *U_means, const double *CC, const double *DD,
+                                                const double *noise_std, int J, const double *Y_test, int n_test, double *y_mean,
+                                                double *y_var, double *y_var_total, double *lpd, double *lpd_gauss) {
+    const std::string who = "ffvd_op_posterior_moment_grouped", bad = who + ": bad argument";
+    const SummaryReq q{CC, DD, noise_std, J, Y_test, n_test, y_mean, y_var, y_var_total, lpd, lpd_gauss};
+    const SummaryReq *sum = mg_summary_wanted(q) ? &q : nullptr;
+    if (kind != FFVD_KERNEL_SE) return set_error(nullptr, FFVD_EINVAL, bad + mg_se_only);
+    if (!pg_scalars_ok(kind, G, n_models, M, P, D, C, T, groups_per_pass, jitter) || !mg_scalars_ok(kind, G, n_models, M, P, D, C, steps, q_mode) ||
+        (sum && !summary_scalars_ok(q, G, steps, D)))
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    if (G == 0 || steps == 0) return FFVD_OK;
+    if (!Zs || !logvariances || !loglengthscales || !Xs || !log_Qs || (C > 0 && (!ctrl_fit || !ctrl_roll)) || (!sum && (!m_x || !S_x)) ||
+        (sum && !summary_arrays_ok(q)))
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    const PgIn in{who, kind, G, n_models, M, P, D, C, T, groups_per_pass, Zs, logvariances, loglengthscales, Xs, ctrl_fit, log_Qs, jitter};
+    return mg_posterior_run(in, q_mode, nullptr, S0s, ctrl_roll, steps, m_x, S_x, U_means, sum, nullptr);
+}
+
+// ---- filtering and smoothing (moment_group.h) -------------------------------------------------------------------------------------
+// ffvd_op_moment_grouped with a measurement update after every step (posteriors given by the caller)
+extern "C" int ffvd_op_filter_grouped(int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M, int P,
+                                      int D, const double *logvariances, const double *loglengthscales, const double *fs,
+                                      const double *const *q_sqrts, int q_mode, const double *x_lasts, const double *S0s,
+                                      const double *ctrl, int C, int steps, const double *log_Qs, const double *CC, const double *DD,
+                                      const double *noise_std, int J, const double *Y_obs, double *m_pred, double *S_pred,
+                                      double *m_filt, double *S_filt, double *cross, double *lpd, double *lpd_joint, double *m_smooth,
+                                      double *S_smooth, double *y_mean, double *y_var_total, double *lpd_mix, double *lpd_gauss) {
+    const std::string who = "ffvd_op_filter_grouped", bad = who + ": bad argument";
+    const FilterReq f{CC, DD, noise_std, J, Y_obs, m_filt, S_filt, cross, lpd, lpd_joint, m_smooth, S_smooth, y_mean, y_var_total, lpd_mix,
+                      lpd_gauss};
+    if (kind != FFVD_KERNEL_SE) return set_error(nullptr, FFVD_EINVAL, bad + mg_se_only);
+    if (!mg_scalars_ok(kind, G, n_models, M, P, D, C, steps, q_mode) || !filter_scalars_ok(f)) return set_error(nullptr, FFVD_EINVAL, bad);
+    if (G == 0 || steps == 0) return FFVD_OK;
+    if (!Lm_inverse_seqs || !Zs || !logvariances || !loglengthscales || !fs || !x_lasts || !log_Qs || (C > 0 && !ctrl) ||
+        !filter_arrays_ok(f, steps, m_pred, S_pred))
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    return mg_given_run(who, G, n_models, Lm_inverse_seqs, Zs, M, P, D, logvariances, loglengthscales, fs, q_sqrts, q_mode, x_lasts, S0s, ctrl,
+                        C, steps, log_Qs, m_pred, S_pred, nullptr, &f);
+}
+
+// The collapsed posteriors of ffvd_op_posterior_grouped filtered without leaving the device (as ffvd_op_posterior_moment_grouped);
+// x0s NULL: the start means are the last rows of Xs
+extern "C" int ffvd_op_posterior_filter_grouped(int kind, int G, int n_models, const double *Zs, int M, int P, int D,
+                                                const double *logvariances, const double *loglengthscales, const double *Xs,
+                                                const double *ctrl_fit, int C, int T, const double *log_Qs, double jitter,
+                                                int groups_per_pass, int q_mode, const double *x0s, const double *S0s,
+                                                const double *ctrl_roll, int steps, const double *CC, const double *DD,
+                                                const double *noise_std, int J, const double *Y_obs, double *m_pred, double *S_pred,
+                                                double *m_filt, double *S_filt, double *cross, double *lpd, double *lpd_joint,
+                                                double *m_smooth, double *S_smooth, double *y_mean, double *y_var_total, double *lpd_mix,
+                                                double *lpd_gauss, double *U_means) {
+    const std::string who = "ffvd_op_posterior_filter_grouped", bad = who + ": bad argument";
+    const FilterReq f{CC, DD, noise_std, J, Y_obs, m_filt, S_filt, cross, lpd, lpd_joint, m_smooth, S_smooth, y_mean, y_var_total, lpd_mix,
+                      lpd_gauss};
+    if (kind != FFVD_KERNEL_SE) return set_error(nullptr, FFVD_EINVAL, bad + mg_se_only);
+    if (!pg_scalars_ok(kind, G, n_models, M, P, D, C, T, groups_per_pass, jitter) || !mg_scalars_ok(kind, G, n_models, M, P, D, C, steps, q_mode) ||
+        !filter_scalars_ok(f))
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    if (G == 0 || steps == 0) return FFVD_OK;
+    if (!Zs || !logvariances || !loglengthscales || !Xs || !log_Qs || (C > 0 && (!ctrl_fit || !ctrl_roll)) ||
+        !filter_arrays_ok(f, steps, m_pred, S_pred))
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    const PgIn in{who, kind, G, n_models, M, P, D, C, T, groups_per_pass, Zs, logvariances, loglengthscales, Xs, ctrl_fit, log_Qs, jitter};
+    return mg_posterior_run(in, q_mode, x0s, S0s, ctrl_roll, steps, m_pred, S_pred, U_means, nullptr, &f);
+}
+
+// The summary of the moment-matched prediction for stacks the caller holds: they are uploaded, summarised by the same launch as in the
+// calls above
+extern "C" int ffvd_op_moment_summary(const double *m_x, const double *S_x, int G, int steps, int D, const double *CC, const double *DD,
+                                      const double *noise_std, int J, const double *Y_test, int n_test, double *y_mean, double *y_var,
+                                      double *y_var_total, double *lpd, double *lpd_gauss) {
+    const std::string who = "ffvd_op_moment_summary", bad = who + ": bad argument";
+    const SummaryReq q{CC, DD, noise_std, J, Y_test, n_test, y_mean, y_var, y_var_total, lpd, lpd_gauss};
+    if (!summary_scalars_ok(q, G, steps, D) || D > MG_MAXD || (G > 0 && steps > 0 && G > ((1LL << 31) - 1) / steps / D / D))
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    if (G == 0 || steps == 0) return FFVD_OK;
+    if (!m_x || !S_x || !summary_arrays_ok(q)) return set_error(nullptr, FFVD_EINVAL, bad);
+    OP_BEGIN(who);
+    const size_t n = (size_t)G * steps * D;
+    double *dm = sc.upload(m_x, n), *dS = sc.upload(S_x, n * D);
+    OP_CHECK(dm && dS, who);
+    return mg_summary(sc, who, dm, dS, G, steps, D, q);
+}

@@ -1,7 +1,7 @@
 // Grouped collapsed posteriors (posterior_group.hip): the kernels that hand G posteriors from the factorisation slabs to the grouped
 // rollout loop (rollout_group.hip) or to packed result arrays without a trip through the host.  The factorisations themselves are
 // the ELBO's batch machinery (kernels.h: launch_kuu_build, launch_project, launch_gram, launch_potrf_ext, launch_matvec); the
-// operators ffvd_op_posterior_grouped / ffvd_op_posterior_rollout_grouped (ops.hip) put the launches together.
+// operators ffvd_op_posterior_grouped / ffvd_op_posterior_rollout_grouped (ops_grouped.hip) put the launches together.
 //
 // Slab layouts read here (Mp = M rounded up to 64, ld Mp):
 //   K_uu slab of (model, dim): 2 Mp rows, rows [Mp, 2 Mp) = L^-T after launch_potrf_ext (upper triangular, identity padding);

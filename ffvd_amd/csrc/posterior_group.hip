@@ -1,6 +1,6 @@
 // Grouped collapsed posteriors: U_mean and L_H^-T of collapse_u_mean_after_kernel_precalculation (conditionals_multi_output.py:206-227,
 // called at base_model.py:243-256) for G groups -- one per chain or per SG-HMC sample -- without the host in between.  The
-// factorisations are the ELBO's batch launches over units b = g * D + d (ops.hip puts them together); the kernels here move their
+// factorisations are the ELBO's batch launches over units b = g * D + d (ops_grouped.hip puts them together); the kernels here move their
 // results from the factorisation slabs (Mp = M rounded up to 64) into the operands of the grouped rollout loop (rollout_group.h:
 // Mp16 = M rounded up to 16, exact zeros in the padding and below the diagonal) or into packed result arrays.
 // Pure data movement: every output element is written by exactly one thread from at most one input element, so the results are
