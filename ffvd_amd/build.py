@@ -17,8 +17,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libffvd_hip.so")
 HASH = LIB + ".hash"
 OBJDIR = os.path.join(HERE, "build")
-SOURCES = ["kernels.hip", "kernels_f32.hip", "grad.hip", "optim.hip", "tiny.hip", "loops.hip", "rollout_group.hip", "posterior_group.hip", "conditional_group.hip", "predict_summary.hip", "moment_group.hip", "moment_filter.hip", "cov.hip", "abi.hip", "backward.hip", "ops.hip", "ops_loops.hip", "ops_grouped.hip", "train.hip", "comm.hip"]
-HEADERS = ["kernels.h", "dev_common.h", "step_bodies.h", "tiny.h", "kernels_f32.h", "grad.h", "optim.h", "rollout_group.h", "posterior_group.h", "conditional_group.h", "predict_summary.h", "moment_group.h", "moment_step.h", "gemm_rowmajor.h", "abi_internal.h", "op_scratch.h", "handle.h", os.path.join("..", "..", "include", "ffvd_abi.h")]
+SOURCES = ["kernels.hip", "gram.hip", "potrf.hip", "potrf_flow.hip", "project.hip", "kernels_f32.hip", "grad.hip", "optim.hip", "tiny.hip", "loops.hip", "rollout_group.hip", "posterior_group.hip", "conditional_group.hip", "predict_summary.hip", "moment_group.hip", "moment_filter.hip", "cov.hip", "abi.hip", "backward.hip", "ops.hip", "ops_loops.hip", "ops_grouped.hip", "train.hip", "comm.hip"]
+HEADERS = ["kernels.h", "dev_common.h", "potrf_blocks.h", "step_bodies.h", "tiny.h", "kernels_f32.h", "grad.h", "optim.h", "rollout_group.h", "posterior_group.h", "conditional_group.h", "predict_summary.h", "moment_group.h", "moment_step.h", "gemm_rowmajor.h", "abi_internal.h", "op_scratch.h", "handle.h", os.path.join("..", "..", "include", "ffvd_abi.h")]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-Wno-unused-value"]
 LINK = ["-shared", "-fPIC", "--offload-arch=gfx950", "-ldl"]
 
@@ -124,12 +124,13 @@ def variant_path(name):
     return os.path.join(HERE, f"libffvd_hip_{name}.so")
 
 
+# name -> (the source, or the sources, recompiled with the defines; the defines)
 VARIANTS = {
     # the dataflow Cholesky with matrix 0 never announcing its first diagonal block: every other block row of that matrix
     # must give up after the bounded wait instead of hanging (tests/test_gpu_ops.py)
-    "dfstall": ["-DFFVD_DF_TEST_STALL"],
-    # wall-clock stamps inside the dataflow Cholesky (tools/df_trace.py)
-    "dftrace": ["-DFFVD_DF_TRACE"],
+    "dfstall": ("potrf_flow.hip", ["-DFFVD_DF_TEST_STALL"]),
+    # wall-clock stamps inside the dataflow Cholesky (tools/df_trace.py) and of the Gram kernel's workgroups (tools/gram_rounds.py)
+    "dftrace": (["potrf_flow.hip", "gram.hip"], ["-DFFVD_DF_TRACE"]),
     # tiny.hip (the one-launch iteration): wall-clock stamps of every workgroup's phases (tools/tiny_trace.py); a build whose
     # unit-0 head never publishes W, so that every bounded wait of that launch must give up (tests/test_gpu_tiny.py)
     "tinytrace": ("tiny.hip", ["-DFFVD_TINY_TRACE"]),
@@ -139,30 +140,40 @@ VARIANTS = {
     # wall-clock stamps of every workgroup of the fused backward product (tools/bwd_trace.py)
     "bwdtrace": ("grad.hip", ["-DFFVD_BWD_TRACE"]),
     # wall-clock stamps of every workgroup of the skinny product of a rollout / particle-Gibbs step (tools/step_trace.py)
-    "steptrace": ["-DFFVD_STEP_TRACE"],
+    "steptrace": ("kernels.hip", ["-DFFVD_STEP_TRACE"]),
 }
 
 
+def variant_sources(name):
+    sources = VARIANTS[name][0]
+    return [sources] if isinstance(sources, str) else list(sources)
+
+
 def build_variant(name, verbose=False):
-    """Test / diagnostic build: kernels.hip recompiled with the variant's defines, every other object shared with the
+    """Test / diagnostic build: the variant's own sources recompiled with its defines, every other object shared with the
     product library (which is built first).  Load it with FFVD_LIB=<path>."""
     build(force=False, verbose=verbose)
     out = variant_path(name)
     stamp = out + ".hash"
-    spec = VARIANTS[name]
-    source, defines = spec if isinstance(spec, tuple) else ("kernels.hip", spec)
-    want = source_hash() + " " + source + " " + " ".join(defines)
+    sources, defines = variant_sources(name), VARIANTS[name][1]
+    want = source_hash() + " " + " ".join(sources) + " " + " ".join(defines)
     if os.path.exists(out) and os.path.exists(stamp) and open(stamp).read().strip() == want:
         return out
     cc = hipcc_path()
-    obj = os.path.join(OBJDIR, f"{source}.{name}.o")
-    cmd = [cc] + FLAGS + defines + ["-c", os.path.join(CSRC, source), "-o", obj]
-    if verbose:
-        print(" ".join(cmd), flush=True)
-    proc = subprocess.run(cmd, capture_output=True, text=True)
-    if proc.returncode != 0:
-        raise RuntimeError(f"hipcc failed on {source} ({name}):\n" + proc.stdout + proc.stderr)
-    objs = [obj] + [os.path.join(OBJDIR, src + ".o") for src in SOURCES if src != source]
+
+    def compile_one(source):
+        obj = os.path.join(OBJDIR, f"{source}.{name}.o")
+        cmd = [cc] + FLAGS + defines + ["-c", os.path.join(CSRC, source), "-o", obj]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        proc = subprocess.run(cmd, capture_output=True, text=True)
+        if proc.returncode != 0:
+            raise RuntimeError(f"hipcc failed on {source} ({name}):\n" + proc.stdout + proc.stderr)
+        return obj
+
+    with ThreadPoolExecutor(max_workers=len(sources)) as pool:
+        objs = list(pool.map(compile_one, sources))
+    objs += [os.path.join(OBJDIR, src + ".o") for src in SOURCES if src not in sources]
     proc = subprocess.run([cc] + objs + LINK + ["-o", out], capture_output=True, text=True)
     if proc.returncode != 0:
         raise RuntimeError(f"hipcc link failed ({name}):\n" + proc.stdout + proc.stderr)

@@ -805,7 +805,7 @@ static int fwd_chain_rest(FwdCtx &x) {
         gk.mode = GRAM_PLAIN; gk.A = h->Linv; gk.a_stride = msq; gk.rows = Mp; gk.with_row = 0; gk.Mp = Mp; gk.Dl = Dl;
         gk.d_begin = c.d_begin; gk.b0 = 0; gk.nb = Dl; gk.yn_over_batch = 1.0; gk.H = h->Kinv; gk.h_stride = msq;
         if (x.kinv_done) {
-            // (the identity-row workgroups of the chain's launch have formed it: kernels.hip, df_inverse_tiles)
+            // (the identity-row workgroups of the chain's launch have formed it: potrf_flow.hip, df_inverse_tiles)
         } else if (c.grad || x.kuu_on_main) {
             // the backward pass reads K^-1 everywhere, the Gram kernel only writes lower tiles; and beside the K_fu build
             // (kuu_on_main: the main stream waits for this product) 256-thread workgroups find a slot where the Gram
@@ -1106,7 +1106,7 @@ int ffvd::check_info(ffvd_handle *h) {
     const int Dl = h->Dl;
     h->stalled = false;
     for (int i = 0; i < Dl + h->nbatch; ++i) {
-        if (h->h_info[i] < 0) {        // the dataflow Cholesky bounds every wait (kernels.hip, potrf_df_kernel); so does tiny.hip
+        if (h->h_info[i] < 0) {        // the dataflow Cholesky bounds every wait (potrf_flow.hip, potrf_df_kernel); so does tiny.hip
             h->stalled = true;
             h->tiny_dirty = true;
             return set_error(h, FFVD_EDEVICE, "blocked Cholesky abandoned: a block row waited more than 1 s for the row above it");

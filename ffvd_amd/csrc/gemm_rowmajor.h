@@ -89,7 +89,7 @@ __device__ __forceinline__ TileAcc gemm_rowmajor_a(double (*As)[AT][A_LDT], doub
         }
     };
     // LDS-DMA of one 1 KiB row (lane l -> bytes 16 l): uniform 64-bit base + ONE per-lane byte offset, LDS address through M0; written as
-    // asm, so hipcc does not count it (see the Gram kernel's staging, kernels.hip): waited for by hand below.
+    // asm, so hipcc does not count it (see the Gram kernel's staging, gram.hip): waited for by hand below.
     typedef __attribute__((address_space(3))) void lvoid;
     const unsigned voff = (unsigned)(2 * lane * (int)sizeof(double));
     auto glds = [&](const double *base, const void *lds_row) {

@@ -88,6 +88,10 @@ bool potrf_flow_forms_inverse(int n, int batch, int hint);
 // clears them itself (one memset in front of the kernel) unless the caller has done so earlier with potrf_flow_clear on a
 // stream whose order reaches the launch, and says so (words_zeroed).
 void potrf_flow_clear(hipStream_t stream, double *dinv, int batch);
+constexpr int DF_PS = 64;     // progress words per matrix (main block rows: n <= 4096)
+// the `int` words at the start of `dinv` that a launch for `batch` matrices polls and potrf_flow_clear zeroes: the progress
+// words, then the abort word, padded to 16 bytes
+static inline size_t potrf_flow_words(int batch) { return ((size_t)batch * DF_PS + 4 + 3) / 4 * 4; }
 void launch_set_identity(hipStream_t stream, double *A, size_t slab_stride, int row0, int n, int batch);
 // rows [row0, row0 + n) of slab b <- L_d^T, d = b % Dl (upper triangular; L_d = lower-triangular n x n factor, ld n, n % 64 == 0)
 void launch_set_lt_rows(hipStream_t stream, const double *L, size_t l_stride, int Dl, double *A, size_t slab_stride, int row0,
@@ -125,7 +129,7 @@ void launch_brow_finish(hipStream_t stream, const double *gpart, int nblk, int M
                         const double *log_Q, double yn_over_batch, double *H, size_t h_stride, int brow);
 // F = K_fu * L^{-T} with K_fu generated on the fly (never stored).
 void launch_project(hipStream_t stream, const ProjectArgs &a);
-// LinearK, explicit-U branch, forward only (kernels.hip, "the projection through the kernel's rank"): fills a.rowsq / a.fmean with ONE
+// LinearK, explicit-U branch, forward only (project.hip, "the projection through the kernel's rank"): fills a.rowsq / a.fmean with ONE
 // column group per unit ([nbatch][Tp]) from x, ctrl, hv, U and a.W = the C rows the K_uu chain left behind (launch_kuu_build zt_rows;
 // slab stride a.w_stride) -- no F, no K_fu.  `part`: linear_lowrank_doubles(Mp, Dl, P) doubles.
 bool linear_lowrank_supported(int kind, int P);

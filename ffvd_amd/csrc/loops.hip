@@ -173,7 +173,7 @@ __global__ __launch_bounds__(256) void pg_loop_kernel(PgLoopArgs a, const int GA
 // 32 workgroups of a dim).  Every word another workgroup reads is written with an agent-scope (sc1, write-through) store and read with an
 // agent-scope load, i.e. past the caches that are not coherent across compute units / XCDs; the producer waits for its stores
 // (s_waitcnt vmcnt(0)) in front of the workgroup barrier behind which one lane counts, the consumer's loads are issued behind the
-// barrier that follows its poll.  No fence on either side -- the Gram kernel's tail exchange (kernels.hip) is the same construction.
+// barrier that follows its poll.  No fence on either side -- the Gram kernel's tail exchange (gram.hip) is the same construction.
 __device__ __forceinline__ void rr_store(double *p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ double rr_load(const double *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 constexpr long long RR_SPIN_TICKS = 10000000LL;         // 0.1 s of the 100 MHz wall clock: a step is 10-25 us; a wait this long means that the

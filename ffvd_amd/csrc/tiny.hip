@@ -10,7 +10,7 @@
 // Backward pass: the closed form of oracle/ffvd_grad_oracle.py (whitened variables), arranged as in tools/tiny_proto.py.
 //
 // Roles (one workgroup each, ALL resident at once -- tiny_plan checks that they fit; hand-offs through agent-scope flags exactly as
-// in the dataflow Cholesky of kernels.hip: plain stores -> every wavefront's s_waitcnt vmcnt(0) -> barrier -> one lane's release +
+// in the dataflow Cholesky of potrf_flow.hip: plain stores -> every wavefront's s_waitcnt vmcnt(0) -> barrier -> one lane's release +
 // flag store; one lane polls -> acquire -> barrier -> plain loads; every wait is bounded by the wall clock):
 //   head(u), one per (chain, latent dim) unit, blockIdx < nunits (dispatched first; a head never waits before it has published W):
 //     K_uu in LDS -> blocked Cholesky (16 x 16 tiles: the 16-pivot chains on ONE wavefront, everything else on the matrix cores
@@ -190,7 +190,7 @@ __device__ __forceinline__ void tiny_tile_sub(double *Am, const int LD, const in
 }
 // In: lower triangle of Am.  Out: lower triangle = L (diagonal tiles with zeros above the diagonal), tiles above the diagonal =
 // W = L^-T, Dinv[s] = W(s,s).
-// Every tile BELOW diagonal tile s rides through that tile's 16-pivot chain (kernels.hip, chol64_mfma_4w has the argument: the chain is
+// Every tile BELOW diagonal tile s rides through that tile's 16-pivot chain (potrf_blocks.h, chol64_mfma_4w has the argument: the chain is
 // the unblocked right-looking elimination, a lane that starts from a row of T'(i,s) = A(i,s) - sum_{k<s} L(i,k) L(s,k)^T leaves it as
 // that row of L(i,s)).  A chain wavefront carries the diagonal tile's rows in lanes 0-15 and three riders in lanes 16-63: wavefront
 // 0 the identity (-> L_ss^-T = W(s,s)) and tiles (s+1,s), (s+2,s), wavefronts 1, 2 the tiles further down -- they repeat the pivots for

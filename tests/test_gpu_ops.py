@@ -146,7 +146,7 @@ def test_dataflow_cholesky_gives_up_instead_of_hanging(tmp_path):
     import time
     from ffvd_amd import build as fb
     # never skipped: the variant library is git-ignored, so a fresh checkout builds it here (one hipcc run of
-    # kernels.hip; a no-op when its recorded source hash is current) and a box without hipcc FAILS the test
+    # potrf_flow.hip; a no-op when its recorded source hash is current) and a box without hipcc FAILS the test
     lib_path = fb.build_variant("dfstall")
     assert os.path.exists(lib_path)
     env = dict(os.environ, FFVD_LIB=lib_path, PYTHONPATH=os.path.dirname(os.path.dirname(os.path.abspath(__file__))),

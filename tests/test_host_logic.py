@@ -592,3 +592,24 @@ def test_tshard_boundary_rows_fake_collective():
             assert np.array_equal(out[:, 0], parts[r][:, 0])
         if r < world - 1:
             assert np.allclose(out[:, -1], parts[r][:, -1] + parts[r + 1][:, 0])
+
+
+def test_build_lists_cover_the_source_tree():
+    """ffvd_amd/build.py against ffvd_amd/csrc: every *.hip is compiled (SOURCES), every quoted #include resolves to a header
+    whose bytes enter the source hash (HEADERS), and a variant recompiles only files the product build compiles too."""
+    import re
+    from ffvd_amd import build as fb
+    on_disk = sorted(f for f in os.listdir(fb.CSRC) if f.endswith(".hip"))
+    assert sorted(fb.SOURCES) == on_disk
+    assert len(set(fb.SOURCES)) == len(fb.SOURCES)
+    headers = {os.path.normpath(os.path.join(fb.CSRC, h)) for h in fb.HEADERS}
+    assert all(os.path.isfile(h) for h in headers)
+    for name in os.listdir(fb.CSRC):
+        if not name.endswith((".hip", ".h")):
+            continue
+        with open(os.path.join(fb.CSRC, name)) as f:
+            for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', f.read(), flags=re.M):
+                assert os.path.normpath(os.path.join(fb.CSRC, inc)) in headers, f"{name} includes {inc}, which HEADERS does not list"
+    for variant in fb.VARIANTS:
+        sources = fb.variant_sources(variant)
+        assert sources and set(sources) <= set(fb.SOURCES), variant

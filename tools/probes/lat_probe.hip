@@ -54,7 +54,7 @@ __global__ void probe(double *out, long long *t, int n, double seed) {
     if (threadIdx.x == 0) { t[0] = t1 - t0; t[1] = t2 - t1; t[2] = t3 - t2; t[3] = t4 - t3; }
 }
 
-// the product's 16-pivot chain as tiny.hip / kernels.hip have it (tile from LDS, identity rows in lanes 16-31, first bad pivot tracked,
+// the product's 16-pivot chain as tiny.hip / potrf_blocks.h (chol64_mfma_4w) have it (tile from LDS, identity rows in lanes 16-31, first bad pivot tracked,
 // L_ss and L_ss^-T back to LDS)
 template <bool BAD, bool LOAD, bool STORE>
 __device__ __forceinline__ int chain16_product(const double (*Sc)[17], double *Am, const int LD, const int s0, double (*Dv)[17], const int lane) {
