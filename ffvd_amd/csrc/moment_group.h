@@ -72,6 +72,24 @@ struct MomentSmoothArgs {
 };
 void launch_mg_smooth(hipStream_t stream, const MomentSmoothArgs &a);
 
+// Rolling-origin forecasts (moment_fan.hip; DESIGN.md section 9, "Rolling-origin forecasts"): the propagation's launch with a TRACK as
+// its unit of work.  Track v = g * Bp + b of a pass is (group g, origin b0 + b of the origin table): it reads beta, Gamma, the
+// hyper-parameters and log_Q of its group, starts from row origin[b0 + b] of the filter's stacks (launch 0, no gather pass), reads
+// control row origin[b0 + b] + 1 + t at launch t, and launch t + 1 writes row t of its forecast.  In this form MomentGroupArgs::G is
+// the number of tracks of the pass (part and state are per track), steps the horizon h, ctrl the rows the filter read, and m_x / S_x
+// the forecast stacks [G][B][h][D], [G][B][h][D][D]; x_last and S0 are not read.
+// Limits: a pass holds at most Bp tracks per group with G * Bp * npair * NS < 2^31 (grid x) and 2 * G * Bp * fields * NS <=
+//   MG_FAN_PART_DOUBLES (the slab sums of its tracks: 128 MiB);  G * B * h * D * D < 2^31.
+constexpr long long MG_FAN_PART_DOUBLES = 1LL << 24;
+struct MomentFanArgs {
+    int B, Bp, b0, n;                // origins of the call; tracks per group of this pass; its first origin; rows of the filter's stacks
+    const int *origin;               // [B], ascending, every origin + h < n (checked on the host)
+    const double *m_filt, *S_filt;   // [groups][n][D], [groups][n][D][D]
+};
+// the largest number of tracks per group of a pass (at least 1) for G groups and B origins
+int mg_fan_tracks_per_pass(int G, int D, int NS, int B);
+void launch_mg_fan_step(hipStream_t stream, const MomentGroupArgs &a, const MomentFanArgs &f, int t);
+
 struct MomentSummaryArgs {
     int G, steps, D, J, n_test;
     const double *m, *S;             // [G][steps][D], [G][steps][D][D]

@@ -1,6 +1,7 @@
 // The step kernel of the moment-matched prediction and of the filter: one template, instantiated with
-// FILTER = false by moment_group.hip (the propagation) and with FILTER = true by moment_filter.hip (the measurement update added).
-// The two instantiations live in separate translation units so that the code of the propagation does not depend on the filter's.
+// FILTER = false by moment_group.hip (the propagation), with FILTER = true by moment_filter.hip (the measurement update added) and
+// with FILTER = false and one MomentFanArgs by moment_fan.hip (the propagation with a track as its unit: rolling-origin forecasts).
+// The instantiations live in separate translation units so that the code of the propagation does not depend on the others'.
 #pragma once
 #include "moment_group.h"
 #include "kernels.h"
@@ -152,9 +153,14 @@ __device__ __forceinline__ void mg_update(const MomentGroupArgs &a, const Moment
 }
 
 __device__ __forceinline__ const MomentFilterArgs &mg_filter_args(const MomentFilterArgs &f) { return f; }
+__device__ __forceinline__ const MomentFanArgs &mg_fan_args(const MomentFanArgs &f) { return f; }
 
-// One launch of the propagation (FILTER = false, no further argument: the kernel as it was before the filter existed) or of the
-// filter (FILTER = true, one MomentFilterArgs: the measurement update and the stores of the filter are added).
+// One launch of the propagation (FILTER = false, no further argument: the kernel as it was before the filter existed), of the
+// filter (FILTER = true, one MomentFilterArgs: the measurement update and the stores of the filter are added) or of the fan
+// (FILTER = false, one MomentFanArgs: the unit g of the decomposition is a track, see moment_group.h).  The fan changes WHERE a unit
+// reads and writes, never an expression on the values: gq is the group whose posterior, hyper-parameters and log_Q the unit uses,
+// orow the first row of its output stacks, crow its first control row; without a MomentFanArgs they are g, g * steps and 0 (and
+// the existing instantiations keep the expressions they had, so that their code does not change).
 template <int D, bool FILTER, class... F>
 __global__ __launch_bounds__(256) void mg_step_kernel(MomentGroupArgs a, const int t, F... f) {
     constexpr int NP = D * (D + 1) / 2, NF = NP + D + D * D;
@@ -171,12 +177,28 @@ __global__ __launch_bounds__(256) void mg_step_kernel(MomentGroupArgs a, const i
     db += da;
     const bool writer = (pr == 0 && s == 0);
     if (t == steps && !writer) return;
-    const int model = a.n_models == 1 ? 0 : g;
+    constexpr bool FAN = !FILTER && sizeof...(F) == 1;
+    int gq = g, crow = 0;
+    size_t orow = 0, srow = 0;
+    if constexpr (FAN) {
+        const MomentFanArgs &fn = mg_fan_args(f...);
+        const int b = fn.b0 + g % fn.Bp, org = fn.origin[b];        // (the table was checked on the host: 0 <= org, org + steps < n)
+        gq = g / fn.Bp;
+        crow = org + 1;
+        orow = ((size_t)gq * fn.B + b) * steps;
+        srow = (size_t)gq * fn.n + org;
+    }
+    const int model = a.n_models == 1 ? 0 : gq;
 
     // 1. the state of this launch: (x_last, S0), or the state of launch t - 1 plus its slab sums
     if (t == 0) {
-        if (tid < D) mu[tid] = a.x_last[(size_t)g * D + tid];
-        if (tid < D * D) Sg[tid / D][tid % D] = a.S0 ? a.S0[(size_t)g * D * D + tid] : 0.0;
+        if constexpr (FAN) {                                      // the filtered state at the track's origin, where the filter left it
+            if (tid < D) mu[tid] = mg_fan_args(f...).m_filt[srow * D + tid];
+            if (tid < D * D) Sg[tid / D][tid % D] = mg_fan_args(f...).S_filt[srow * D * D + tid];
+        } else {
+            if (tid < D) mu[tid] = a.x_last[(size_t)g * D + tid];
+            if (tid < D * D) Sg[tid / D][tid % D] = a.S0 ? a.S0[(size_t)g * D * D + tid] : 0.0;
+        }
     } else {
         const double *pp = a.part + ((size_t)((t - 1) & 1) * G + g) * NF * NS;
         if (tid < NF) {
@@ -192,7 +214,7 @@ __global__ __launch_bounds__(256) void mg_step_kernel(MomentGroupArgs a, const i
             const int pi = lo * D - lo * (lo - 1) / 2 + (hi - lo);
             double v = sp[D + lo * D + hi] + fin[pi];
             v += fin[NP + D + hi * D + lo] + fin[NP + D + lo * D + hi];                   // Cov(x_lo, f_hi) + Cov(x_hi, f_lo)
-            if (lo == hi) v += a.variance[(size_t)model * D + lo] + exp(a.log_Q[(size_t)g * D + lo]);
+            if (lo == hi) v += a.variance[(size_t)model * D + lo] + exp(a.log_Q[(size_t)gq * D + lo]);
             Sg[r][c] = v;
             if constexpr (FILTER)                                 // X = Sigma + V: Cov(x_{t-2}, x_{t-1}), Sigma the filtered one
                 if (writer) mg_filter_args(f...).cross[((size_t)g * steps + (t - 1)) * D * D + tid] = sp[D + tid] + fin[NP + D + c * D + r];
@@ -203,12 +225,20 @@ __global__ __launch_bounds__(256) void mg_step_kernel(MomentGroupArgs a, const i
         double *sc = a.state + ((size_t)(t & 1) * G + g) * (D + D * D);
         if (tid < D) {
             if constexpr (!FILTER) sc[tid] = mu[tid];
-            if (t > 0) a.m_x[((size_t)g * steps + (t - 1)) * D + tid] = mu[tid];
+            if constexpr (FAN) {
+                if (t > 0) a.m_x[(orow + (t - 1)) * D + tid] = mu[tid];
+            } else {
+                if (t > 0) a.m_x[((size_t)g * steps + (t - 1)) * D + tid] = mu[tid];
+            }
         }
         if (tid < D * D) {
             const double v = Sg[tid / D][tid % D];
             if constexpr (!FILTER) sc[D + tid] = v;
-            if (t > 0) a.S_x[((size_t)g * steps + (t - 1)) * D * D + tid] = v;
+            if constexpr (FAN) {
+                if (t > 0) a.S_x[(orow + (t - 1)) * D * D + tid] = v;
+            } else {
+                if (t > 0) a.S_x[((size_t)g * steps + (t - 1)) * D * D + tid] = v;
+            }
         }
     }
     if constexpr (FILTER) mg_update<D>(a, mg_filter_args(f...), t, g, writer, mu, Sg);
@@ -217,7 +247,7 @@ __global__ __launch_bounds__(256) void mg_step_kernel(MomentGroupArgs a, const i
     // 2. the three eliminations of the pair
     const double *lena = a.len + ((size_t)model * D + da) * P, *lenb = a.len + ((size_t)model * D + db) * P;
     if (tid < P) {
-        xin[tid] = tid < D ? mu[tid] : a.ctrl[(size_t)t * C + (tid - D)];
+        xin[tid] = tid < D ? mu[tid] : a.ctrl[(size_t)(crow + t) * C + (tid - D)];
         const double ia = 1.0 / lena[tid], ib = 1.0 / lenb[tid];
         ils[0][tid] = ia;
         ils[1][tid] = ib;
@@ -236,7 +266,7 @@ __global__ __launch_bounds__(256) void mg_step_kernel(MomentGroupArgs a, const i
     // 3. the slab's rows (dim a)
     const int i0 = MG_SLAB * s, ni = (M - i0 < MG_SLAB) ? M - i0 : MG_SLAB;
     const double *Zm = a.Z + (size_t)model * M * P;
-    const double *bea = a.beta + ((size_t)g * D + da) * Mp, *beb = a.beta + ((size_t)g * D + db) * Mp;
+    const double *bea = a.beta + ((size_t)gq * D + da) * Mp, *beb = a.beta + ((size_t)gq * D + db) * Mp;
     if (tid < MG_SLAB) {
         double av[D], q = 0.0, de = 0.0, be = 0.0;
 #pragma unroll
@@ -279,7 +309,7 @@ __global__ __launch_bounds__(256) void mg_step_kernel(MomentGroupArgs a, const i
     }
 
     // 4. the slab of the pair table: thread = column j
-    const double *Gg = diag ? a.gam + ((size_t)(a.unit_per_group ? g : model) * D + da) * Mp * Mp + (size_t)i0 * Mp : nullptr;
+    const double *Gg = diag ? a.gam + ((size_t)(a.unit_per_group ? gq : model) * D + da) * Mp * Mp + (size_t)i0 * Mp : nullptr;
     double accc = 0.0, accg = 0.0;
     for (int j = tid; j < M; j += 256) {
         double bv[D], qj, dg;

@@ -1,6 +1,6 @@
 // The grouped operators of the C ABI: rollout summaries, grouped rollouts, grouped collapsed posteriors, grouped conditionals, and
-// moment-matched prediction with filtering.  Each staging block (hyper-parameters, a caller's posterior, a posterior formed in the
-// call, the emission of a summary) is written once and shared by the entry points.
+// moment-matched prediction with filtering and rolling-origin forecasts.  Each staging block (hyper-parameters, a caller's posterior,
+// a posterior formed in the call, the emission of a summary) is written once and shared by the entry points.
 #include "op_scratch.h"
 #include "rollout_group.h"
 #include "posterior_group.h"
@@ -636,9 +636,9 @@ struct FilterReq {
 };
 // the checks of a filter request that need no array, and those that read the small arrays (Y_obs: no infinity)
 bool filter_scalars_ok(const FilterReq &f) { return f.J >= 1 && f.J <= MG_MAXJ; }
-bool filter_arrays_ok(const FilterReq &f, int steps, const double *m_pred, const double *S_pred) {
+bool filter_arrays_ok(const FilterReq &f, int steps, const double *m_pred, const double *S_pred, bool other_output = false) {
     if (!f.CC || !f.DD || !f.noise_std || !f.Y_obs) return false;
-    if (!(m_pred || S_pred || f.m_filt || f.S_filt || f.cross || f.lpd || f.lpd_joint || f.m_smooth || f.S_smooth || f.y_mean ||
+    if (!(other_output || m_pred || S_pred || f.m_filt || f.S_filt || f.cross || f.lpd || f.lpd_joint || f.m_smooth || f.S_smooth || f.y_mean ||
           f.y_var_total || f.lpd_mix || f.lpd_gauss))
         return false;
     for (int j = 0; j < f.J; ++j)
@@ -648,13 +648,35 @@ bool filter_arrays_ok(const FilterReq &f, int steps, const double *m_pred, const
     return true;
 }
 
+// The forecast request of mg_run (with a filter request): from every origin (a row of the record, ascending) `horizon` steps of the
+// propagation started at the filtered state of that row, as tracks of moment_group.h's fan launch; the outputs, each of which may be NULL
+struct ForecastReq {
+    int horizon, n_origins, tracks_per_pass;
+    const int *origins;
+    double *m_fc, *S_fc;                                     // [G][B][h][D], [G][B][h][D][D]
+    double *y_mean, *y_var_total, *lpd_mix, *lpd_gauss;      // pooled over the groups, [B * h][J]: row b * h + k against Y_obs[origins[b] + 1 + k]
+    bool any_output() const { return m_fc || S_fc || y_mean || y_var_total || lpd_mix || lpd_gauss; }
+};
+// the checks of a forecast request that need no array (G * B * h * D * D < 2^31), and the origin table: strictly ascending, every
+// track inside the record so that its control rows exist
+bool forecast_scalars_ok(const ForecastReq &q, int G, int steps, int D) {
+    if (q.horizon < 1 || q.n_origins < 1 || q.tracks_per_pass < 0) return false;
+    return G == 0 || steps == 0 || (long long)G * q.n_origins <= ((1LL << 31) - 1) / q.horizon / D / D;
+}
+bool forecast_origins_ok(const ForecastReq &q, int steps) {
+    if (!q.origins) return false;
+    for (int b = 0; b < q.n_origins; ++b)
+        if (q.origins[b] < 0 || q.origins[b] > steps - 1 - q.horizon || (b > 0 && q.origins[b] <= q.origins[b - 1])) return false;
+    return true;
+}
+
 // Operands on the device -> beta, Gamma, the step launches, the summary, the downloads.  flt: the launches are those of the filter
 // (moment_group.h), m_x / S_x are the predicted moments, and `sum` is REPLACED by the pooled one-step summary of the request when that
 // asks for one (the filter callers pass nullptr).  dW: [n_models * D] slots of Mp x Mp (upper triangular, zero padded); dq: nullptr,
 // or [G] (q_mode 0) / [G * D] (q_mode 1) slots of Mp x Mp; hv: variance / len per (model, dim).
 int mg_run(Scratch &sc, const std::string &who, int G, int nm, int M, int P, int D, int C, int steps, const HyperView &hv, const double *dZ,
            const double *dW, const double *dq, int q_mode, const double *dU, const double *dxl, const double *dS0, const double *dlq,
-           const double *dctrl, double *m_x, double *S_x, const SummaryReq *sum, const FilterReq *flt) {
+           const double *dctrl, double *m_x, double *S_x, const SummaryReq *sum, const FilterReq *flt, const ForecastReq *fc = nullptr) {
     const int Mp = round_up(M, NB), NS = (M + MG_SLAB - 1) / MG_SLAB, nK = nm * D, GD = G * D;
     const size_t mm = (size_t)Mp * Mp, nm_x = (size_t)G * steps * D, nS_x = nm_x * D;
     const SummaryReq fsum = flt ? flt->pooled(steps) : SummaryReq{};
@@ -682,6 +704,19 @@ int mg_run(Scratch &sc, const std::string &who, int G, int nm, int M, int P, int
             sa.cross = fa.cross; sa.m_smooth = sc.alloc<double>(nm_x); sa.S_smooth = sc.alloc<double>(nS_x);
             OP_CHECK(sa.m_smooth && sa.S_smooth, who);
         }
+    }
+    // the forecast: stacks, the origin table and the slab sums / states of one pass of tracks (after every request the filter makes)
+    const int B = fc ? fc->n_origins : 0, h = fc ? fc->horizon : 0;
+    int Bp = fc ? mg_fan_tracks_per_pass(G, D, NS, B) : 0;
+    if (fc && fc->tracks_per_pass > 0 && fc->tracks_per_pass < Bp) Bp = fc->tracks_per_pass;
+    const size_t nm_fc = (size_t)G * B * h * D, nS_fc = nm_fc * D;
+    double *dmfc = nullptr, *dSfc = nullptr, *fpart = nullptr, *fstate = nullptr;
+    int *dorg = nullptr;
+    if (fc) {
+        dmfc = sc.alloc<double>(nm_fc); dSfc = sc.alloc<double>(nS_fc); dorg = sc.alloc<int>(B);
+        fpart = sc.alloc<double>((size_t)2 * G * Bp * mg_fields(D) * NS); fstate = sc.alloc<double>((size_t)2 * G * Bp * (D + D * D));
+        OP_CHECK(dmfc && dSfc && dorg && fpart && fstate, who);
+        OP_TRY(hipMemcpyAsync(dorg, fc->origins, (size_t)B * sizeof(int), hipMemcpyHostToDevice, sc.stream));
     }
     launch_mg_beta(sc.stream, G, D, M, Mp, nm == G, dW, dU, beta);
     // Gamma = W (I - q q^T) W^T through cov.hip's product body.  COV_GEN: C = A B^T, all Mp x Mp entries written.
@@ -729,9 +764,32 @@ int mg_run(Scratch &sc, const std::string &who, int G, int nm, int M, int P, int
         for (int t = 0; t <= steps; ++t) launch_mg_filter_step(sc.stream, a, fa, t);
         if (smooth) launch_mg_smooth(sc.stream, sa);
     }
+    if (fc) {
+        // passes of at most Bp origins, h + 1 launches each; a track's values do not depend on the pass it is in
+        MomentGroupArgs ta = a;
+        ta.steps = h; ta.x_last = nullptr; ta.S0 = nullptr; ta.part = fpart; ta.state = fstate; ta.m_x = dmfc; ta.S_x = dSfc;
+        MomentFanArgs fn{};
+        fn.B = B; fn.n = steps; fn.origin = dorg; fn.m_filt = fa.m_filt; fn.S_filt = fa.S_filt;
+        for (int b0 = 0; b0 < B; b0 += Bp) {
+            fn.b0 = b0; fn.Bp = B - b0 < Bp ? B - b0 : Bp;
+            ta.G = G * fn.Bp;
+            for (int t = 0; t <= h; ++t) launch_mg_fan_step(sc.stream, ta, fn, t);
+        }
+    }
     OP_TRY(hipGetLastError());
     if (sum)
         if (int rc = mg_summary(sc, who, dm, dS, G, steps, D, *sum)) return rc;
+    if (fc && (fc->y_mean || fc->y_var_total || fc->lpd_mix || fc->lpd_gauss)) {
+        // the forecast stacks as [G][B * h][D] against the targets Y_fc[b * h + k] = Y_obs[origins[b] + 1 + k]
+        const int J = flt->J;
+        std::vector<double> &yfc = sc.host((size_t)B * h * J);
+        for (int b = 0; b < B; ++b)
+            memcpy(yfc.data() + (size_t)b * h * J, flt->Y_obs + (size_t)(fc->origins[b] + 1) * J, (size_t)h * J * sizeof(double));
+        const SummaryReq fq{flt->CC, flt->DD, flt->noise_std, J, yfc.data(), B * h, fc->y_mean, nullptr, fc->y_var_total, fc->lpd_mix, fc->lpd_gauss};
+        if (int rc = mg_summary(sc, who, dmfc, dSfc, G, B * h, D, fq)) return rc;
+    }
+    if (fc && ((fc->m_fc && !sc.download(fc->m_fc, dmfc, nm_fc * sizeof(double))) || (fc->S_fc && !sc.download(fc->S_fc, dSfc, nS_fc * sizeof(double)))))
+        return set_error(nullptr, FFVD_EDEVICE, who + ": copying the results back failed");
     if (flt) {
         auto down = [&](double *dst, const double *src, size_t n) { return !dst || sc.download(dst, src, n * sizeof(double)); };
         if (!down(flt->m_filt, fa.m_filt, nm_x) || !down(flt->S_filt, fa.S_filt, nS_x) || !down(flt->cross, fa.cross, nS_x) ||
@@ -750,7 +808,7 @@ const char *const mg_se_only = " (moment matching is closed-form for the SE kern
 int mg_given_run(const std::string &who, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M, int P, int D,
                  const double *logvariances, const double *loglengthscales, const double *fs, const double *const *q_sqrts, int q_mode,
                  const double *x_lasts, const double *S0s, const double *ctrl, int C, int steps, const double *log_Qs, double *m_x,
-                 double *S_x, const SummaryReq *sum, const FilterReq *flt) {
+                 double *S_x, const SummaryReq *sum, const FilterReq *flt, const ForecastReq *fc = nullptr) {
     const size_t nK = (size_t)n_models * D, GD = (size_t)G * D, nq = given_nq(q_sqrts, q_mode, G, D);
     if (!given_tables_ok(Lm_inverse_seqs, nK, q_sqrts, nq)) return set_error(nullptr, FFVD_EINVAL, who + ": bad argument");
     OP_BEGIN(who);
@@ -761,14 +819,14 @@ int mg_given_run(const std::string &who, int G, int n_models, const double *cons
     double *dctrl = C ? sc.upload(ctrl, (size_t)steps * C) : nullptr;
     OP_CHECK(dW && (!nq || dq) && dU && dxl && (!S0s || dS0) && dlq && (!C || dctrl) && gh.logs(sc) && gh.blocks(sc), who);
     gh.prep(sc.stream);
-    return mg_run(sc, who, G, n_models, M, P, D, C, steps, gh.hv(), gh.dZ, dW, dq, q_mode, dU, dxl, dS0, dlq, dctrl, m_x, S_x, sum, flt);
+    return mg_run(sc, who, G, n_models, M, P, D, C, steps, gh.hv(), gh.dZ, dW, dq, q_mode, dU, dxl, dS0, dlq, dctrl, m_x, S_x, sum, flt, fc);
 }
 
 // The collapsed posteriors of ffvd_op_posterior_grouped (base_model.py:243-256) through mg_run without leaving the device: L^-T is
 // packed from the K_uu slabs, U_mean read where the matvec left it, the q slices packed by launch_pg_pack (exact zeros in the padding
 // and the strict lower triangle); the start means are x0s or, without them, the last rows of Xs.
 int mg_posterior_run(const PgIn &in, int q_mode, const double *x0s, const double *S0s, const double *ctrl_roll, int steps, double *m_x,
-                     double *S_x, double *U_means, const SummaryReq *sum, const FilterReq *flt) {
+                     double *S_x, double *U_means, const SummaryReq *sum, const FilterReq *flt, const ForecastReq *fc = nullptr) {
     const std::string &who = in.who;
     OP_BEGIN(who);
     PgWork w{};
@@ -784,7 +842,7 @@ int mg_posterior_run(const PgIn &in, int q_mode, const double *x0s, const double
     launch_pg_pack(sc.stream, w.Kuu, 2 * mm, Mp, Mp, nK, 1, M, 1, dW, Mp, Mp, nK);
     if (!x0s) launch_pg_x_last(sc.stream, w.Xs, G, in.T, D, dxl);
     if (int rc = mg_run(sc, who, G, nm, M, in.P, D, C, steps, w.hv, dZ, dW, pg_q(w, q_mode), q_mode, w.U, dxl, dS0, w.log_Qs, dctrl, m_x, S_x,
-                        sum, flt))
+                        sum, flt, fc))
         return rc;
     if (U_means && !sc.download(U_means, w.U, GD * M * sizeof(double)))
         return set_error(nullptr, FFVD_EDEVICE, who + ": copying the results back failed");
@@ -880,6 +938,61 @@ extern "C" int ffvd_op_posterior_filter_grouped(int kind, int G, int n_models, c
         return set_error(nullptr, FFVD_EINVAL, bad);
     const PgIn in{who, kind, G, n_models, M, P, D, C, T, groups_per_pass, Zs, logvariances, loglengthscales, Xs, ctrl_fit, log_Qs, jitter};
     return mg_posterior_run(in, q_mode, x0s, S0s, ctrl_roll, steps, m_pred, S_pred, U_means, nullptr, &f);
+}
+
+// ---- rolling-origin forecasts (moment_group.h, MomentFanArgs) -----------------------------------------------------------------------
+// ffvd_op_filter_grouped, then from every origin `horizon` steps of the propagation started at the filtered state of that row: one
+// launch per forecast step for all (group, origin) tracks of a pass, and the pooled summary of every (origin, horizon)
+extern "C" int ffvd_op_forecast_grouped(int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M, int P,
+                                        int D, const double *logvariances, const double *loglengthscales, const double *fs,
+                                        const double *const *q_sqrts, int q_mode, const double *x_lasts, const double *S0s,
+                                        const double *ctrl, int C, int steps, const double *log_Qs, const double *CC, const double *DD,
+                                        const double *noise_std, int J, const double *Y_obs, double *m_pred, double *S_pred,
+                                        double *m_filt, double *S_filt, double *cross, double *lpd, double *lpd_joint, double *m_smooth,
+                                        double *S_smooth, double *y_mean, double *y_var_total, double *lpd_mix, double *lpd_gauss,
+                                        int horizon, const int *origins, int n_origins, int tracks_per_pass, double *m_fc, double *S_fc,
+                                        double *fc_y_mean, double *fc_y_var_total, double *fc_lpd_mix, double *fc_lpd_gauss) {
+    const std::string who = "ffvd_op_forecast_grouped", bad = who + ": bad argument";
+    const FilterReq f{CC, DD, noise_std, J, Y_obs, m_filt, S_filt, cross, lpd, lpd_joint, m_smooth, S_smooth, y_mean, y_var_total, lpd_mix,
+                      lpd_gauss};
+    const ForecastReq q{horizon, n_origins, tracks_per_pass, origins, m_fc, S_fc, fc_y_mean, fc_y_var_total, fc_lpd_mix, fc_lpd_gauss};
+    if (kind != FFVD_KERNEL_SE) return set_error(nullptr, FFVD_EINVAL, bad + mg_se_only);
+    if (!mg_scalars_ok(kind, G, n_models, M, P, D, C, steps, q_mode) || !filter_scalars_ok(f) || !forecast_scalars_ok(q, G, steps, D))
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    if (G == 0 || steps == 0) return FFVD_OK;
+    if (!Lm_inverse_seqs || !Zs || !logvariances || !loglengthscales || !fs || !x_lasts || !log_Qs || (C > 0 && !ctrl) ||
+        !filter_arrays_ok(f, steps, m_pred, S_pred, q.any_output()) || !forecast_origins_ok(q, steps))
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    return mg_given_run(who, G, n_models, Lm_inverse_seqs, Zs, M, P, D, logvariances, loglengthscales, fs, q_sqrts, q_mode, x_lasts, S0s, ctrl,
+                        C, steps, log_Qs, m_pred, S_pred, nullptr, &f, &q);
+}
+
+// The same on the collapsed posteriors of ffvd_op_posterior_grouped (as ffvd_op_posterior_filter_grouped): they never leave the device
+extern "C" int ffvd_op_posterior_forecast_grouped(int kind, int G, int n_models, const double *Zs, int M, int P, int D,
+                                                  const double *logvariances, const double *loglengthscales, const double *Xs,
+                                                  const double *ctrl_fit, int C, int T, const double *log_Qs, double jitter,
+                                                  int groups_per_pass, int q_mode, const double *x0s, const double *S0s,
+                                                  const double *ctrl_roll, int steps, const double *CC, const double *DD,
+                                                  const double *noise_std, int J, const double *Y_obs, double *m_pred, double *S_pred,
+                                                  double *m_filt, double *S_filt, double *cross, double *lpd, double *lpd_joint,
+                                                  double *m_smooth, double *S_smooth, double *y_mean, double *y_var_total, double *lpd_mix,
+                                                  double *lpd_gauss, double *U_means, int horizon, const int *origins, int n_origins,
+                                                  int tracks_per_pass, double *m_fc, double *S_fc, double *fc_y_mean,
+                                                  double *fc_y_var_total, double *fc_lpd_mix, double *fc_lpd_gauss) {
+    const std::string who = "ffvd_op_posterior_forecast_grouped", bad = who + ": bad argument";
+    const FilterReq f{CC, DD, noise_std, J, Y_obs, m_filt, S_filt, cross, lpd, lpd_joint, m_smooth, S_smooth, y_mean, y_var_total, lpd_mix,
+                      lpd_gauss};
+    const ForecastReq q{horizon, n_origins, tracks_per_pass, origins, m_fc, S_fc, fc_y_mean, fc_y_var_total, fc_lpd_mix, fc_lpd_gauss};
+    if (kind != FFVD_KERNEL_SE) return set_error(nullptr, FFVD_EINVAL, bad + mg_se_only);
+    if (!pg_scalars_ok(kind, G, n_models, M, P, D, C, T, groups_per_pass, jitter) || !mg_scalars_ok(kind, G, n_models, M, P, D, C, steps, q_mode) ||
+        !filter_scalars_ok(f) || !forecast_scalars_ok(q, G, steps, D))
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    if (G == 0 || steps == 0) return FFVD_OK;
+    if (!Zs || !logvariances || !loglengthscales || !Xs || !log_Qs || (C > 0 && (!ctrl_fit || !ctrl_roll)) ||
+        !filter_arrays_ok(f, steps, m_pred, S_pred, q.any_output()) || !forecast_origins_ok(q, steps))
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    const PgIn in{who, kind, G, n_models, M, P, D, C, T, groups_per_pass, Zs, logvariances, loglengthscales, Xs, ctrl_fit, log_Qs, jitter};
+    return mg_posterior_run(in, q_mode, x0s, S0s, ctrl_roll, steps, m_pred, S_pred, U_means, nullptr, &f, &q);
 }
 
 // The summary of the moment-matched prediction for stacks the caller holds: they are uploaded, summarised by the same launch as in the

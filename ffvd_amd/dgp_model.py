@@ -555,6 +555,26 @@ class DGPSSM:
                                       n_train, steps, self.Q, lik.CC, lik.DD, lik.log_Rchols, Y_test, Y_train_std, q_mode=q_mode,
                                       return_moments=True)
 
+    def _heldout_record(self, who, Y_test, control_inputs, x0, S0, q_mode):
+        """What `filter_heldout` and `forecast_heldout` do before their call: q_mode and Y_test (len, Ydim) checked, parameters newer
+        on the device pulled, the start broadcast to the chains (None stays None), the control inputs chosen.  (Called through the
+        class: the argument tests hand the two methods a stand-in for the model.)"""
+        from . import conditionals_multi_output as cmo
+        if q_mode not in cmo.Q_MODES:
+            raise ValueError(f"{who}: q_mode: expected one of {sorted(cmo.Q_MODES)}, got {q_mode!r}")
+        Y_test = np.asarray(Y_test, dtype=np.float64)
+        if Y_test.ndim == 1:
+            Y_test = Y_test[:, None]
+        if Y_test.ndim != 2 or Y_test.shape[1] != self.Y.shape[1]:
+            raise ValueError(f"{who}: Y_test: expected (n_test, {self.Y.shape[1]}), got {Y_test.shape}")
+        if self._host_stale:
+            self.pull_parameters()
+        S, D = self.num_chains, self.output_dim
+        x0s = None if x0 is None else np.broadcast_to(np.asarray(x0, dtype=np.float64), (S, D))
+        S0s = None if S0 is None else np.broadcast_to(np.asarray(S0, dtype=np.float64), (S, D, D))
+        ci = self.control_inputs if control_inputs is None else np.asarray(control_inputs, dtype=np.float64)
+        return Y_test, x0s, S0s, ci
+
     def filter_heldout(self, Y_test, control_inputs=None, *, x0=None, S0=None, smooth=False, q_mode="reference", Y_train_std=1.0):
         """One-step-ahead (prequential) evaluation, filtered and (with `smooth`) smoothed latent states of a held-out record: every
         chain's Gaussian state is pushed through the learned transition and updated with each row of Y_test (len, Ydim; a NaN entry
@@ -567,20 +587,8 @@ class DGPSSM:
         are pulled first."""
         from . import conditionals_multi_output as cmo
         from .prediction import filter_grouped, posterior_filter_grouped
-        if q_mode not in cmo.Q_MODES:
-            raise ValueError(f"filter_heldout: q_mode: expected one of {sorted(cmo.Q_MODES)}, got {q_mode!r}")
-        Y_test = np.asarray(Y_test, dtype=np.float64)
-        if Y_test.ndim == 1:
-            Y_test = Y_test[:, None]
-        if Y_test.ndim != 2 or Y_test.shape[1] != self.Y.shape[1]:
-            raise ValueError(f"filter_heldout: Y_test: expected (n_test, {self.Y.shape[1]}), got {Y_test.shape}")
-        if self._host_stale:
-            self.pull_parameters()
-        S, D = self.num_chains, self.output_dim
-        x0s = None if x0 is None else np.broadcast_to(np.asarray(x0, dtype=np.float64), (S, D))
-        S0s = None if S0 is None else np.broadcast_to(np.asarray(S0, dtype=np.float64), (S, D, D))
-        ci = self.control_inputs if control_inputs is None else np.asarray(control_inputs, dtype=np.float64)
-        lay, lik, n_train = self.layers[-1], self.likelihood, self.Y.shape[0]
+        Y_test, x0s, S0s, ci = DGPSSM._heldout_record(self, "filter_heldout", Y_test, control_inputs, x0, S0, q_mode)
+        S, lay, lik, n_train = self.num_chains, self.layers[-1], self.likelihood, self.Y.shape[0]
         if self.U_collapse:
             return posterior_filter_grouped(lay.Z, lay.kernel, [self._X_chains[s_] for s_ in range(S)], self.Q, ci, n_train, Y_test,
                                             lik.CC, lik.DD, lik.log_Rchols, x0s=x0s, S0s=S0s, q_mode=q_mode, smooth=smooth,
@@ -589,6 +597,27 @@ class DGPSSM:
         starts = [self._X_chains[s_][-1] for s_ in range(S)] if x0s is None else list(x0s)
         return filter_grouped(Lm, lay.Z, lay.kernel, [lay.U] * S, None, starts, ci, n_train, Y_test, self.Q, lik.CC, lik.DD,
                               lik.log_Rchols, S0s=S0s, q_mode=q_mode, smooth=smooth, Y_train_std=Y_train_std)
+
+    def forecast_heldout(self, Y_test, control_inputs=None, horizon=10, *, stride=1, origins=None, x0=None, S0=None, q_mode="reference",
+                         Y_train_std=1.0, return_tracks=False):
+        """k-step-ahead evaluation of a held-out record for k = 1 .. horizon, with every row of the record as the forecast origin
+        (every `stride`-th, or the rows `origins`): the filter of `filter_heldout`, then from each origin `horizon` steps of the
+        moment-matched prediction started at the filtered state -- prediction.forecast_grouped has the method and the dict that is
+        returned (the horizon curves rmse_h, ll_h, ll_gauss_h, n_h of shape (horizon, Ydim) among it; SquaredExponential kernels
+        only; deterministic).  The start, the control rows and the two forms (collapsed U: ONE `posterior_forecast_grouped` call;
+        explicit U: `kernel_pre_cal` once, then `forecast_grouped`) are those of `filter_heldout`."""
+        from . import conditionals_multi_output as cmo
+        from .prediction import forecast_grouped, posterior_forecast_grouped
+        Y_test, x0s, S0s, ci = DGPSSM._heldout_record(self, "forecast_heldout", Y_test, control_inputs, x0, S0, q_mode)
+        S, lay, lik, n_train = self.num_chains, self.layers[-1], self.likelihood, self.Y.shape[0]
+        kw = dict(origins=origins, stride=stride, S0s=S0s, q_mode=q_mode, Y_train_std=Y_train_std, return_tracks=return_tracks)
+        if self.U_collapse:
+            return posterior_forecast_grouped(lay.Z, lay.kernel, [self._X_chains[s_] for s_ in range(S)], self.Q, ci, n_train, Y_test,
+                                              lik.CC, lik.DD, lik.log_Rchols, horizon, x0s=x0s, **kw)
+        Lm = cmo.kernel_pre_cal(lay.Z, lay.kernel)
+        starts = [self._X_chains[s_][-1] for s_ in range(S)] if x0s is None else list(x0s)
+        return forecast_grouped(Lm, lay.Z, lay.kernel, [lay.U] * S, None, starts, ci, n_train, Y_test, self.Q, lik.CC, lik.DD,
+                                lik.log_Rchols, horizon, **kw)
 
     def predict_transition(self, Xnew, *, q_mode="reference", per_chain=True):
         """The learned transition function at inputs of the caller's choice: mean and variance of the posterior GP increment

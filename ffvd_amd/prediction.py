@@ -667,6 +667,131 @@ def posterior_filter_grouped(Zs, kerns, Xs, Qs, control_inputs, ctrl_offset, Y_o
     return _filter_dict(m, out, Y_train_std)
 
 
+def _pack_forecast(who, n, horizon, origins=None, stride=1, model=None):
+    """Horizon and forecast origins of a record of n rows, checked (before the library is loaded): 1 <= horizon <= n - 1; origins
+    None: range(0, n - horizon, stride) with stride >= 1, else strictly ascending integers in [0, n - 1 - horizon], so that every
+    track lies inside the record and its control rows exist.  model: (kind, M, P, D) for `_moment_limits` (LinearK is rejected).
+    Returns horizon and the origins as a contiguous int32 array (B,)."""
+    if model is not None:
+        _moment_limits(who, *model)
+    if isinstance(horizon, bool) or int(horizon) != horizon:
+        raise ValueError(f"{who}: horizon: expected an integer, got {horizon!r}")
+    h, n = int(horizon), int(n)
+    if h < 1:
+        raise ValueError(f"{who}: horizon: at least one step ahead is needed, got {h}")
+    if n - h < 1:
+        raise ValueError(f"{who}: horizon {h} does not fit a record of {n} rows (an origin and {h} rows after it are needed)")
+    if origins is None:
+        if isinstance(stride, bool) or int(stride) != stride or int(stride) < 1:
+            raise ValueError(f"{who}: stride: expected a positive integer, got {stride!r}")
+        org = np.arange(0, n - h, int(stride), dtype=np.int32)
+    else:
+        o = np.asarray(origins)
+        if o.ndim != 1 or o.size < 1 or not (np.issubdtype(o.dtype, np.integer) or np.array_equal(o, np.floor(o))):
+            raise ValueError(f"{who}: origins: expected a non-empty sequence of integers")
+        o = o.astype(np.int64)
+        if o[0] < 0 or o[-1] > n - 1 - h or np.any(np.diff(o) <= 0) or np.any(o < 0) or np.any(o > n - 1 - h):
+            raise ValueError(f"{who}: origins: expected strictly ascending rows in [0, {n - 1 - h}] (horizon {h}, {n} rows)")
+        org = np.ascontiguousarray(o, dtype=np.int32)
+    return h, org
+
+
+_NO_FILTER_OUTPUTS = (None,) * 13
+FORECAST_POOLED = ("predict_y", "predict_y_var_total", "lpd_mix", "lpd_gauss")
+
+
+def _forecast_call(m, G, D, steps, h, org, return_tracks, return_filter, tracks_per_pass):
+    """Output arrays (the filter's, the forecast's) and the arguments CC .. lpd_gauss and horizon .. fc_lpd_gauss of the two forecast
+    entry points (U_means of the fused one goes between them)."""
+    if isinstance(tracks_per_pass, bool) or int(tracks_per_pass) != tracks_per_pass or int(tracks_per_pass) < 0:
+        raise ValueError(f"tracks_per_pass must be 0 (automatic) or a positive integer, got {tracks_per_pass!r}")
+    import ctypes
+    J, B, dp = m["J"], len(org), _lib.dptr
+    if return_filter:
+        fout, fargs = _filter_call(m, G, D, steps, False)
+    else:
+        fout, fargs = None, (dp(m["CC"]), dp(m["DD"]), dp(m["sd"]), J, dp(m["Y"])) + _NO_FILTER_OUTPUTS
+    out = {k: np.empty((B, h, J)) for k in FORECAST_POOLED}
+    if return_tracks:
+        out.update(m_fc=np.empty((G, B, h, D)), S_fc=np.empty((G, B, h, D, D)))
+    opt = lambda k: dp(out[k]) if k in out else None
+    args = (h, org.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), B, int(tracks_per_pass), opt("m_fc"), opt("S_fc")) + \
+        tuple(dp(out[k]) for k in FORECAST_POOLED)
+    return fout, fargs, out, args
+
+
+def _forecast_dict(m, org, h, fout, out, Y_train_std):
+    """The dict the forecast functions return: origins, the arrays of `_forecast_call`, and the per-horizon curves over the observed
+    targets Y[origins[b] + k] (formed here as `_filter_dict` forms ll): n_h, rmse_h, ll_h, ll_gauss_h, ll_h_original_units, each
+    (h, J); a horizon or output without an observed target gives NaN and n_h = 0.  With the filter's outputs: the keys of
+    `filter_grouped`, its four pooled one-step arrays as filter_predict_y, filter_predict_y_var_total, filter_lpd_mix,
+    filter_lpd_gauss (the plain names are the forecast's here)."""
+    Y = m["Y"]
+    Yt = Y[org.astype(np.int64)[:, None] + 1 + np.arange(h)[None, :]]                     # (B, h, J)
+    seen = ~np.isnan(Yt)
+    n_h = np.sum(seen, axis=0).astype(np.int64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        over = lambda x: np.where(n_h > 0, np.sum(np.where(seen, x, 0.0), axis=0) / n_h, np.nan)
+        rmse_h = np.sqrt(over((Yt - out["predict_y"]) ** 2)) * Y_train_std
+        ll_h, ll_gauss_h = over(out["lpd_mix"]), over(out["lpd_gauss"])
+    res = {}
+    if fout is not None:
+        f = _filter_dict(m, fout, Y_train_std)
+        res.update({("filter_" + k if k in FORECAST_POOLED else k): v for k, v in f.items()})
+    res.update(out)
+    res.update(origins=org.astype(np.int64), n_h=n_h, rmse_h=rmse_h, ll_h=ll_h, ll_gauss_h=ll_gauss_h,
+               ll_h_original_units=ll_h - float(np.log(Y_train_std)))
+    return res
+
+
+def forecast_grouped(Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_inputs, ctrl_offset, Y_obs, Qs, CC, DD, log_Rchols,
+                     horizon, *, origins=None, stride=1, S0s=None, q_mode="reference", Y_train_std=1.0, return_tracks=False,
+                     return_filter=False, tracks_per_pass=0):
+    """Rolling-origin multi-step forecasts of an observed record through G posteriors in ONE call (`ffvd_op_forecast_grouped`): the
+    filter of `filter_grouped` (same arguments up to log_Rchols), then from every origin -- a row of the record -- `horizon` steps of
+    `moment_grouped` started at the filtered state of that row.  All (group, origin) tracks advance in one launch per forecast
+    step; the posteriors are prepared once and the filtered states never leave the device.  origins: strictly ascending rows in
+    [0, n - 1 - horizon]; None: range(0, n - horizon, stride).
+    Returns a dict.  origins (B,);  predict_y, predict_y_var_total, lpd_mix, lpd_gauss (B, horizon, J): entry [b, k - 1] is the
+    equal-weight pool over the groups (the chains are not re-weighted by their likelihoods) of the k-step-ahead prediction of row
+    origins[b] + k given rows 0 .. origins[b]; NaN densities where that target is unobserved.  Per-horizon curves over the observed
+    targets, (horizon, J): n_h (count), rmse_h (times Y_train_std), ll_h, ll_gauss_h, ll_h_original_units (ll_h - log Y_train_std);
+    NaN where n_h = 0.  With return_tracks: m_fc (G, B, horizon, D), S_fc (G, B, horizon, D, D), exactly symmetric.  With
+    return_filter: the keys of `filter_grouped` without the smoothed ones, its pooled one-step arrays under filter_predict_y,
+    filter_predict_y_var_total, filter_lpd_mix, filter_lpd_gauss.  A track is bit-identical to `moment_grouped` from
+    x_lasts = m_filt[:, o], S0s = S_filt[:, o], ctrl_offset + o + 1, and does not depend on the other tracks, the other groups or
+    tracks_per_pass (0: automatic; the number of origins that advance together)."""
+    who = "forecast_grouped"
+    steps = _filter_steps(who, Y_obs)
+    a = _pack_moment_groups(who, Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_inputs, ctrl_offset, steps, Qs, S0s, q_mode)
+    h, org = _pack_forecast(who, steps, horizon, origins, stride, (a["args"][0], a["M"], a["args"][6], a["D"]))
+    m = _pack_filter(who, a["D"], Y_obs, CC, DD, log_Rchols)
+    fout, fargs, out, args = _forecast_call(m, a["G"], a["D"], steps, h, org, return_tracks, return_filter, tracks_per_pass)
+    rc = _lib.load().ffvd_op_forecast_grouped(*a["args"], *fargs, *args)
+    _lib.check(rc, None, who)
+    return _forecast_dict(m, org, h, fout, out, Y_train_std)
+
+
+def posterior_forecast_grouped(Zs, kerns, Xs, Qs, control_inputs, ctrl_offset, Y_obs, CC, DD, log_Rchols, horizon, *, x0s=None,
+                               origins=None, stride=1, S0s=None, q_mode="reference", Y_train_std=1.0, return_tracks=False,
+                               return_filter=False, tracks_per_pass=0, jitter=JITTER, groups_per_pass=0):
+    """The collapsed posterior of G groups and the forecasts of `forecast_grouped` in ONE call
+    (`ffvd_op_posterior_forecast_grouped`): what `conditionals_multi_output.collapse_u_mean_grouped` followed by `forecast_grouped`
+    computes, without the posteriors leaving the device.  The arguments up to log_Rchols, x0s, jitter and groups_per_pass are
+    `posterior_filter_grouped`'s.  Returns the dict of `forecast_grouped`."""
+    who = "posterior_forecast_grouped"
+    steps = _filter_steps(who, Y_obs)
+    a = _pack_posterior_moment(who, Zs, kerns, Xs, Qs, control_inputs, ctrl_offset, steps, S0s, q_mode, jitter, groups_per_pass)
+    h, org = _pack_forecast(who, steps, horizon, origins, stride, (a["args"][0], a["M"], a["args"][5], a["D"]))
+    m = _pack_filter(who, a["D"], Y_obs, CC, DD, log_Rchols)
+    x0 = None if x0s is None else _lib.as_f64(x0s, (a["G"], a["D"]), "x0s")
+    fout, fargs, out, args = _forecast_call(m, a["G"], a["D"], steps, h, org, return_tracks, return_filter, tracks_per_pass)
+    pre = a["args"][:17] + (None if x0 is None else _lib.dptr(x0),) + a["args"][17:]
+    rc = _lib.load().ffvd_op_posterior_forecast_grouped(*pre, *fargs, None, *args)
+    _lib.check(rc, None, who)
+    return _forecast_dict(m, org, h, fout, out, Y_train_std)
+
+
 def pg_sweep(Lm_inverse_seq, Z, kern, U_val, X_ref, Y, control_inputs, CC, DD, Rchols, Q, x0, eps, unif):
     """One particle-Gibbs sweep over the latent trajectory: the INTENT of BaseModel.PG_for_X_speedup
     (base_model.py:78-138; the op as written never updates X, see include/ffvd_abi.h `ffvd_op_pg_sweep`).

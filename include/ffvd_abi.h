@@ -691,6 +691,43 @@ int  ffvd_op_posterior_filter_grouped(int kind, int G, int n_models, const doubl
                                       double *S_smooth, double *y_mean, double *y_var_total, double *lpd_mix, double *lpd_gauss,
                                       double *U_means);
 
+/* Rolling-origin multi-step forecasts in one call: ffvd_op_filter_grouped (same arguments, same outputs, each of which may be NULL),
+ * then from every origin o = origins[b] (n_origins rows of the record, strictly ascending, 0 <= o <= steps - 1 - horizon) `horizon`
+ * steps of ffvd_op_moment_grouped started at the FILTERED state of row o, N(m_filt[g][o], S_filt[g][o]), with the control rows
+ * o + 1 .. o + horizon of `ctrl`: entry k - 1 of a track predicts row o + k of the record given rows 0 .. o.  All (group, origin)
+ * tracks of a pass advance in one launch per forecast step; the filtered states are read where the filter left them.  A track is
+ * bit-identical to ffvd_op_moment_grouped called with x_lasts = m_filt[:, o], S0s = S_filt[:, o] and those control rows, and does
+ * not depend on the other tracks, on the other groups or on tracks_per_pass (0: automatic; otherwise at most that many origins per
+ * pass of horizon + 1 launches).
+ * Outputs, each may be NULL (at least one output of the call is needed): m_fc G x n_origins x horizon x D, S_fc G x n_origins x
+ * horizon x D x D (exactly symmetric), and the pooled summary of ffvd_op_moment_grouped over the groups (equal weights), each
+ * (n_origins * horizon) x J, row b * horizon + k - 1 against Y_obs[origins[b] + k]: fc_y_mean, fc_y_var_total, fc_lpd_mix,
+ * fc_lpd_gauss (NaN densities where the target is unobserved; means and variances are finite there).
+ * Limits: those of ffvd_op_filter_grouped, horizon >= 1, n_origins >= 1, tracks_per_pass >= 0, G * n_origins * horizon * D * D < 2^31;
+ * FFVD_EINVAL beyond them, before any device call.  G = 0 or steps = 0: FFVD_OK, nothing is touched. */
+int  ffvd_op_forecast_grouped(int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M, int P, int D,
+                              const double *logvariances, const double *loglengthscales, const double *fs,
+                              const double *const *q_sqrts, int q_mode, const double *x_lasts, const double *S0s, const double *ctrl,
+                              int C, int steps, const double *log_Qs, const double *CC, const double *DD, const double *noise_std, int J,
+                              const double *Y_obs, double *m_pred, double *S_pred, double *m_filt, double *S_filt, double *cross,
+                              double *lpd, double *lpd_joint, double *m_smooth, double *S_smooth, double *y_mean, double *y_var_total,
+                              double *lpd_mix, double *lpd_gauss, int horizon, const int *origins, int n_origins, int tracks_per_pass,
+                              double *m_fc, double *S_fc, double *fc_y_mean, double *fc_y_var_total, double *fc_lpd_mix,
+                              double *fc_lpd_gauss);
+
+/* The same on the arguments of ffvd_op_posterior_filter_grouped: the collapsed posteriors never leave the device.
+ * Limits: those of ffvd_op_posterior_filter_grouped and of ffvd_op_forecast_grouped. */
+int  ffvd_op_posterior_forecast_grouped(int kind, int G, int n_models, const double *Zs, int M, int P, int D, const double *logvariances,
+                                        const double *loglengthscales, const double *Xs, const double *ctrl_fit, int C, int T,
+                                        const double *log_Qs, double jitter, int groups_per_pass, int q_mode, const double *x0s,
+                                        const double *S0s, const double *ctrl_roll, int steps, const double *CC, const double *DD,
+                                        const double *noise_std, int J, const double *Y_obs, double *m_pred, double *S_pred,
+                                        double *m_filt, double *S_filt, double *cross, double *lpd, double *lpd_joint, double *m_smooth,
+                                        double *S_smooth, double *y_mean, double *y_var_total, double *lpd_mix, double *lpd_gauss,
+                                        double *U_means, int horizon, const int *origins, int n_origins, int tracks_per_pass,
+                                        double *m_fc, double *S_fc, double *fc_y_mean, double *fc_y_var_total, double *fc_lpd_mix,
+                                        double *fc_lpd_gauss);
+
 /* The summary of ffvd_op_moment_grouped for stacks the caller holds (m_x G x steps x D, S_x G x steps x D x D): the same launch.
  * Limits: D <= 8, J <= 8, 0 <= n_test <= steps, G * steps * D * D < 2^31, as ffvd_op_rollout_summary otherwise. */
 int  ffvd_op_moment_summary(const double *m_x, const double *S_x, int G, int steps, int D, const double *CC, const double *DD,
