@@ -134,6 +134,11 @@ _SIGNATURES = {
     "ffvd_op_posterior_conditional_grouped": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp,
                                                         C.c_int, C.c_int, _dp, C.c_double, C.c_int, C.c_int, _dp, C.c_int, C.c_int,
                                                         _dp, _dp, _dp, _dp, _dp]),
+    "ffvd_op_conditional_grad_grouped": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), _dp, C.c_int, C.c_int, C.c_int, _dp,
+                                                   _dp, _dp, C.POINTER(C.c_void_p), C.c_int, _dp, C.c_int, C.c_int] + [_dp] * 8),
+    "ffvd_op_posterior_conditional_grad_grouped": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp,
+                                                             _dp, C.c_int, C.c_int, _dp, C.c_double, C.c_int, C.c_int, _dp, C.c_int,
+                                                             C.c_int] + [_dp] * 9),
     "ffvd_op_moment_grouped": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp,
                                          C.POINTER(C.c_void_p), C.c_int, _dp, _dp, _dp, C.c_int, C.c_int, _dp, _dp, _dp,
                                          _dp, _dp, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp]),

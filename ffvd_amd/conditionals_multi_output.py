@@ -282,19 +282,9 @@ def check_conditional_query(who, Xnew, P, q_mode, rows_per_pass, per_group, summ
     return Xnew, Q_MODES[q_mode]
 
 
-def conditional_grouped(Lm_inverse_seqs, Zs, kerns, fs, q_sqrts, Xnew, *, q_mode="reference", per_group=True, summary=True,
-                        rows_per_pass=0):
-    """conditional_after_kernel_precalculation (conditionals_multi_output.py:306-387, white=True, full_cov=False) for G posteriors at
-    the same N inputs in one call (`ffvd_op_conditional_grouped`): the transition function f(x, c) of every chain or SG-HMC sample.
-
-    `Zs` / `kerns` / `Lm_inverse_seqs`: one model (an (M, P) array, a list of D kernels, D matrices L^-T: shared by the groups) or
-    length-G sequences of them; fs: G arrays (M, D), the whitened inducing outputs; q_sqrts: None (explicit U: no third variance
-    term) or G stacks (D, M, M); Xnew (N, P).  q_mode "reference": slice 0 of a group's stack inflates every dim (SURVEY a14, what
-    the reference and the rollouts do); "intent": slice d inflates dim d.
-    Returns (means, vars, mix_mean, mix_var): (G, N, D) per group (None unless per_group) and the equal-weight mixture over the
-    groups, (N, D): mix_mean = mean_g(mean), mix_var = mean_g(var + mean^2) - mix_mean^2 (None unless summary).
-    rows_per_pass: see include/ffvd_abi.h (0 = automatic)."""
-    who = "conditional_grouped"
+def pack_conditional_groups(who, Lm_inverse_seqs, Zs, kerns, fs, q_sqrts, Xnew, q_mode, rows_per_pass, per_group, summary):
+    """The packed inputs of the grouped conditional operators (`ffvd_op_conditional_grouped`, `ffvd_op_conditional_grad_grouped`), with
+    every shape checked before any device call.  The pointer tables `Wt` / `qt` refer to the arrays kept under `keep`."""
     G = len(fs)
     if G < 1:
         raise ValueError(f"{who}: at least one group is needed")
@@ -319,7 +309,6 @@ def conditional_grouped(Lm_inverse_seqs, Zs, kerns, fs, q_sqrts, Xnew, *, q_mode
     if P < D:
         raise ValueError(f"{who}: Zs: {P} input columns for {D} latent dims")
     Xnew, qm = check_conditional_query(who, Xnew, P, q_mode, rows_per_pass, per_group, summary)
-    N = Xnew.shape[0]
     Z, logvar = np.empty((nm, M, P)), np.empty((nm, D))
     loglen = None if hy[0][3] is None else np.empty((nm, D, P))
     Wm, qmats = [], []                                   # (keeps the matrices alive until the call returns)
@@ -350,11 +339,79 @@ def conditional_grouped(Lm_inverse_seqs, Zs, kerns, fs, q_sqrts, Xnew, *, q_mode
     import ctypes
     Wt = (ctypes.c_void_p * len(Wm))(*[w.ctypes.data for w in Wm])
     qt = (ctypes.c_void_p * len(qmats))(*[q.ctypes.data for q in qmats]) if q_sqrts is not None else None
+    return dict(kind=kind, G=G, n_models=nm, M=M, P=P, D=D, N=Xnew.shape[0], Z=Z, logvar=logvar, loglen=loglen, f=f, Xnew=Xnew, q_mode=qm,
+                Wt=Wt, qt=qt, keep=(Wm, qmats))
+
+
+def conditional_grouped(Lm_inverse_seqs, Zs, kerns, fs, q_sqrts, Xnew, *, q_mode="reference", per_group=True, summary=True,
+                        rows_per_pass=0):
+    """conditional_after_kernel_precalculation (conditionals_multi_output.py:306-387, white=True, full_cov=False) for G posteriors at
+    the same N inputs in one call (`ffvd_op_conditional_grouped`): the transition function f(x, c) of every chain or SG-HMC sample.
+
+    `Zs` / `kerns` / `Lm_inverse_seqs`: one model (an (M, P) array, a list of D kernels, D matrices L^-T: shared by the groups) or
+    length-G sequences of them; fs: G arrays (M, D), the whitened inducing outputs; q_sqrts: None (explicit U: no third variance
+    term) or G stacks (D, M, M); Xnew (N, P).  q_mode "reference": slice 0 of a group's stack inflates every dim (SURVEY a14, what
+    the reference and the rollouts do); "intent": slice d inflates dim d.
+    Returns (means, vars, mix_mean, mix_var): (G, N, D) per group (None unless per_group) and the equal-weight mixture over the
+    groups, (N, D): mix_mean = mean_g(mean), mix_var = mean_g(var + mean^2) - mix_mean^2 (None unless summary).
+    rows_per_pass: see include/ffvd_abi.h (0 = automatic)."""
+    who = "conditional_grouped"
+    a = pack_conditional_groups(who, Lm_inverse_seqs, Zs, kerns, fs, q_sqrts, Xnew, q_mode, rows_per_pass, per_group, summary)
+    G, N, D = a["G"], a["N"], a["D"]
     means, vars_ = (np.empty((G, N, D)), np.empty((G, N, D))) if per_group else (None, None)
     mm, mv = (np.empty((N, D)), np.empty((N, D))) if summary else (None, None)
     dp = _lib.dptr
-    opt = lambda a: None if a is None else dp(a)
-    rc = _lib.load().ffvd_op_conditional_grouped(kind, G, nm, Wt, dp(Z), M, P, D, dp(logvar), opt(loglen), dp(f), qt, qm, dp(Xnew), N,
-                                                 int(rows_per_pass), opt(means), opt(vars_), opt(mm), opt(mv))
+    opt = lambda x: None if x is None else dp(x)
+    rc = _lib.load().ffvd_op_conditional_grouped(a["kind"], G, a["n_models"], a["Wt"], dp(a["Z"]), a["M"], a["P"], D, dp(a["logvar"]),
+                                                 opt(a["loglen"]), dp(a["f"]), a["qt"], a["q_mode"], dp(a["Xnew"]), N, int(rows_per_pass),
+                                                 opt(means), opt(vars_), opt(mm), opt(mv))
     _lib.check(rc, None, who)
     return means, vars_, mm, mv
+
+
+GRAD_KEYS = ("mean", "var", "dmean", "dvar", "mix_mean", "mix_var", "mix_dmean", "mix_dvar")
+
+
+def grad_outputs(G, N, D, P, per_group, summary, variance):
+    """The output arrays of the linearisation operators as a dict over GRAD_KEYS (None where not asked for): per group (G, N, D) and
+    (G, N, D, P), the mixture (N, D) and (N, D, P); the mixture values come as a pair, so summary=True forms the variance side."""
+    out = dict.fromkeys(GRAD_KEYS)
+    if per_group:
+        out["mean"], out["dmean"] = np.empty((G, N, D)), np.empty((G, N, D, P))
+        if variance:
+            out["var"], out["dvar"] = np.empty((G, N, D)), np.empty((G, N, D, P))
+    if summary:
+        out["mix_mean"], out["mix_var"], out["mix_dmean"] = np.empty((N, D)), np.empty((N, D)), np.empty((N, D, P))
+        if variance:
+            out["mix_dvar"] = np.empty((N, D, P))
+    return out
+
+
+def check_se_only(who, kind):
+    if kind != 0:
+        raise ValueError(f"{who}: the input gradients are closed-form for the SE kernel only (a linear kernel's Jacobian is constant)")
+
+
+def conditional_grad_grouped(Lm_inverse_seqs, Zs, kerns, fs, q_sqrts, Xnew, *, q_mode="reference", per_group=True, summary=True,
+                             variance=True, rows_per_pass=0):
+    """`conditional_grouped` with the gradients of mean and variance with respect to the rows of Xnew, in one call
+    (`ffvd_op_conditional_grad_grouped`): the linearisation of the transition function f(x, c) of every chain or SG-HMC sample.
+    SE-ARD kernels only.  Arguments as `conditional_grouped`.
+
+    Returns a dict: mean, var (G, N, D), dmean, dvar (G, N, D, P) with dmean[g, n, d, p] = d mean[g, n, d] / d Xnew[n, p] (the first D
+    columns are d/dx, the last C are d/dc) (None unless per_group); mix_mean, mix_var (N, D), mix_dmean, mix_dvar (N, D, P): the
+    equal-weight mixture over the groups and its gradients (None unless summary).  variance=False: var, dvar and mix_dvar are None and,
+    with summary=False, the variance side is not computed at all.  The local linear model of x' = x + f(x, c) is
+    A = I + dmean[..., :D], B = dmean[..., D:].  rows_per_pass: see include/ffvd_abi.h (0 = automatic)."""
+    who = "conditional_grad_grouped"
+    a = pack_conditional_groups(who, Lm_inverse_seqs, Zs, kerns, fs, q_sqrts, Xnew, q_mode, rows_per_pass, per_group, summary)
+    check_se_only(who, a["kind"])
+    G, N, D, P = a["G"], a["N"], a["D"], a["P"]
+    out = grad_outputs(G, N, D, P, per_group, summary, variance)
+    dp = _lib.dptr
+    opt = lambda x: None if x is None else dp(x)
+    rc = _lib.load().ffvd_op_conditional_grad_grouped(a["kind"], G, a["n_models"], a["Wt"], dp(a["Z"]), a["M"], P, D, dp(a["logvar"]),
+                                                      opt(a["loglen"]), dp(a["f"]), a["qt"], a["q_mode"], dp(a["Xnew"]), N,
+                                                      int(rows_per_pass), *[opt(out[k]) for k in GRAD_KEYS])
+    _lib.check(rc, None, who)
+    return out

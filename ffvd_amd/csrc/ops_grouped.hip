@@ -7,6 +7,7 @@
 #include "conditional_group.h"
 #include "predict_summary.h"
 #include "moment_group.h"
+#include "transition_grad.h"
 
 #include <cmath>
 
@@ -670,6 +671,72 @@ bool forecast_origins_ok(const ForecastReq &q, int steps) {
     return true;
 }
 
+// The posterior terms of the moment family and of the linearisation, on operands that are on the device: beta = W u per (group, dim)
+// and Gamma = W (I - q q^T) W^T per unit -- (group, dim) with q slices, (model, dim) without (W W^T: one model shared by the groups
+// is formed once).  alloc() makes the requests (a caller places them among its own), launch() enqueues the products.  want_gam =
+// false: beta alone (a caller that asks for no variance).
+// dW: [nm * D] slots of Mp x Mp (upper triangular, zero padded); dq: nullptr, or [G] (q_mode 0) / [G * D] (q_mode 1) slots.
+struct BetaGamma {
+    int units, nq;
+    double *beta, *gam;                          // [G * D][Mp], [units][Mp][Mp]
+    double *dN, *dE, *dWE, *unused;
+    bool alloc(Scratch &sc, int G, int nm, int D, int Mp, const double *dq, int q_mode, bool want_gam = true) {
+        const int GD = G * D;
+        const size_t mm = (size_t)Mp * Mp;
+        units = dq ? GD : nm * D; nq = dq ? (q_mode ? GD : G) : 0;
+        beta = sc.alloc<double>((size_t)GD * Mp);
+        if (!want_gam) return beta != nullptr;
+        gam = sc.alloc<double>((size_t)units * mm);
+        dN = dq ? sc.alloc<double>((size_t)nq * mm) : nullptr; dE = dq ? sc.alloc<double>((size_t)nq * mm) : nullptr;
+        dWE = dq ? sc.alloc<double>((size_t)GD * mm) : nullptr;
+        unused = sc.alloc<double>((size_t)(nq > units ? nq : units));          // (cov.hip reads a variance per slot for its seed: none here)
+        return beta && gam && (!dq || (dN && dE && dWE)) && unused;
+    }
+    int launch(Scratch &sc, int G, int nm, int M, int D, int Mp, const double *len, const double *dW, const double *dq, int q_mode,
+               const double *dU) const {
+        const int nK = nm * D;
+        const size_t mm = (size_t)Mp * Mp;
+        launch_mg_beta(sc.stream, G, D, M, Mp, nm == G, dW, dU, beta);
+        if (!gam) return FFVD_OK;
+        // Gamma = W (I - q q^T) W^T through cov.hip's product body.  COV_GEN: C = A B^T, all Mp x Mp entries written.
+        CovArgs gen{};
+        gen.mode = COV_GEN; gen.a_stride = mm; gen.lda = Mp; gen.arows = Mp; gen.K = Mp; gen.ldb = Mp; gen.brows = Mp; gen.ncols = Mp;
+        gen.c_stride = mm; gen.ldc = Mp;
+        auto product = [&](const double *A, const double *B, size_t b_stride, double *Cdst, int n) {
+            for (int u0 = 0; u0 < n; u0 += 32768) {                                       // (grid y)
+                gen.A = A + (size_t)u0 * mm; gen.B = B + (size_t)u0 * b_stride; gen.b_stride = b_stride; gen.C = Cdst + (size_t)u0 * mm;
+                gen.nb = n - u0 < 32768 ? n - u0 : 32768;
+                launch_cov(sc.stream, gen);
+            }
+        };
+        if (!dq) product(dW, dW, mm, gam, nK);                                            // W W^T per (model, dim)
+        else {
+            // E = I - q q^T as (N + N^T) - N N^T with N = I - q: no cancellation where q is close to the identity, which is where W is
+            // large.  -N N^T: the symmetric product C = seed - A A^T with an empty seed (a LinearK seed over P = 0 columns is an exact zero).
+            OP_TRY(hipMemsetAsync(dE, 0, (size_t)nq * mm * sizeof(double), sc.stream));
+            CovArgs sym{};
+            sym.mode = COV_SYM; sym.a_stride = mm; sym.lda = Mp; sym.arows = Mp; sym.K = Mp; sym.c_stride = mm; sym.ldc = Mp; sym.N = M;
+            sym.kind = FFVD_KERNEL_LINEAR; sym.P = 0; sym.variance = unused; sym.len = len;
+            for (int u0 = 0; u0 < nq; u0 += 32768) {
+                const int n = nq - u0 < 32768 ? nq - u0 : 32768;
+                launch_mg_nmat(sc.stream, n, M, Mp, dq + (size_t)u0 * mm, dN + (size_t)u0 * mm);
+                sym.A = dN + (size_t)u0 * mm; sym.C = dE + (size_t)u0 * mm; sym.nb = n;
+                launch_cov(sc.stream, sym);
+                launch_mg_emat(sc.stream, n, M, Mp, dN + (size_t)u0 * mm, dE + (size_t)u0 * mm);
+            }
+            // (W E) W^T per (group, dim); E is symmetric, so W E = W E^T.  One launch pair per group: a group's W and E slots are
+            // contiguous whichever of them is shared
+            for (int g = 0; g < G; ++g) {
+                const double *Wg = dW + (nm == G ? (size_t)g * D * mm : 0);
+                double *WEg = dWE + (size_t)g * D * mm;
+                product(Wg, q_mode ? dE + (size_t)g * D * mm : dE + (size_t)g * mm, q_mode ? mm : 0, WEg, D);
+                product(WEg, Wg, mm, gam + (size_t)g * D * mm, D);
+            }
+        }
+        return FFVD_OK;
+    }
+};
+
 // Operands on the device -> beta, Gamma, the step launches, the summary, the downloads.  flt: the launches are those of the filter
 // (moment_group.h), m_x / S_x are the predicted moments, and `sum` is REPLACED by the pooled one-step summary of the request when that
 // asks for one (the filter callers pass nullptr).  dW: [n_models * D] slots of Mp x Mp (upper triangular, zero padded); dq: nullptr,
@@ -677,18 +744,15 @@ bool forecast_origins_ok(const ForecastReq &q, int steps) {
 int mg_run(Scratch &sc, const std::string &who, int G, int nm, int M, int P, int D, int C, int steps, const HyperView &hv, const double *dZ,
            const double *dW, const double *dq, int q_mode, const double *dU, const double *dxl, const double *dS0, const double *dlq,
            const double *dctrl, double *m_x, double *S_x, const SummaryReq *sum, const FilterReq *flt, const ForecastReq *fc = nullptr) {
-    const int Mp = round_up(M, NB), NS = (M + MG_SLAB - 1) / MG_SLAB, nK = nm * D, GD = G * D;
-    const size_t mm = (size_t)Mp * Mp, nm_x = (size_t)G * steps * D, nS_x = nm_x * D;
+    const int Mp = round_up(M, NB), NS = (M + MG_SLAB - 1) / MG_SLAB;
+    const size_t nm_x = (size_t)G * steps * D, nS_x = nm_x * D;
     const SummaryReq fsum = flt ? flt->pooled(steps) : SummaryReq{};
     if (fsum.y_mean || fsum.y_var_total || fsum.lpd || fsum.lpd_gauss) sum = &fsum;
-    const int units = dq ? GD : nK, nq = dq ? (q_mode ? GD : G) : 0;
-    double *beta = sc.alloc<double>((size_t)GD * Mp), *gam = sc.alloc<double>((size_t)units * mm);
-    double *dN = dq ? sc.alloc<double>((size_t)nq * mm) : nullptr, *dE = dq ? sc.alloc<double>((size_t)nq * mm) : nullptr;
-    double *dWE = dq ? sc.alloc<double>((size_t)GD * mm) : nullptr;
-    double *unused = sc.alloc<double>((size_t)(nq > units ? nq : units));          // (cov.hip reads a variance per slot for its seed: none here)
+    BetaGamma bg{};
+    const bool terms = bg.alloc(sc, G, nm, D, Mp, dq, q_mode);
     double *part = sc.alloc<double>((size_t)2 * G * mg_fields(D) * NS), *state = sc.alloc<double>((size_t)2 * G * (D + D * D));
     double *dm = sc.alloc<double>(nm_x), *dS = sc.alloc<double>(nS_x);
-    OP_CHECK(beta && gam && (!dq || (dN && dE && dWE)) && unused && part && state && dm && dS, who);
+    OP_CHECK(terms && part && state && dm && dS, who);
     MomentFilterArgs fa{};
     MomentSmoothArgs sa{};
     const bool smooth = flt && (flt->m_smooth || flt->S_smooth);
@@ -718,45 +782,10 @@ int mg_run(Scratch &sc, const std::string &who, int G, int nm, int M, int P, int
         OP_CHECK(dmfc && dSfc && dorg && fpart && fstate, who);
         OP_TRY(hipMemcpyAsync(dorg, fc->origins, (size_t)B * sizeof(int), hipMemcpyHostToDevice, sc.stream));
     }
-    launch_mg_beta(sc.stream, G, D, M, Mp, nm == G, dW, dU, beta);
-    // Gamma = W (I - q q^T) W^T through cov.hip's product body.  COV_GEN: C = A B^T, all Mp x Mp entries written.
-    CovArgs gen{};
-    gen.mode = COV_GEN; gen.a_stride = mm; gen.lda = Mp; gen.arows = Mp; gen.K = Mp; gen.ldb = Mp; gen.brows = Mp; gen.ncols = Mp;
-    gen.c_stride = mm; gen.ldc = Mp;
-    auto product = [&](const double *A, const double *B, size_t b_stride, double *Cdst, int n) {
-        for (int u0 = 0; u0 < n; u0 += 32768) {                                       // (grid y)
-            gen.A = A + (size_t)u0 * mm; gen.B = B + (size_t)u0 * b_stride; gen.b_stride = b_stride; gen.C = Cdst + (size_t)u0 * mm;
-            gen.nb = n - u0 < 32768 ? n - u0 : 32768;
-            launch_cov(sc.stream, gen);
-        }
-    };
-    if (!dq) product(dW, dW, mm, gam, nK);                                            // W W^T per (model, dim)
-    else {
-        // E = I - q q^T as (N + N^T) - N N^T with N = I - q: no cancellation where q is close to the identity, which is where W is
-        // large.  -N N^T: the symmetric product C = seed - A A^T with an empty seed (a LinearK seed over P = 0 columns is an exact zero).
-        OP_TRY(hipMemsetAsync(dE, 0, (size_t)nq * mm * sizeof(double), sc.stream));
-        CovArgs sym{};
-        sym.mode = COV_SYM; sym.a_stride = mm; sym.lda = Mp; sym.arows = Mp; sym.K = Mp; sym.c_stride = mm; sym.ldc = Mp; sym.N = M;
-        sym.kind = FFVD_KERNEL_LINEAR; sym.P = 0; sym.variance = unused; sym.len = hv.len;
-        for (int u0 = 0; u0 < nq; u0 += 32768) {
-            const int n = nq - u0 < 32768 ? nq - u0 : 32768;
-            launch_mg_nmat(sc.stream, n, M, Mp, dq + (size_t)u0 * mm, dN + (size_t)u0 * mm);
-            sym.A = dN + (size_t)u0 * mm; sym.C = dE + (size_t)u0 * mm; sym.nb = n;
-            launch_cov(sc.stream, sym);
-            launch_mg_emat(sc.stream, n, M, Mp, dN + (size_t)u0 * mm, dE + (size_t)u0 * mm);
-        }
-        // (W E) W^T per (group, dim); E is symmetric, so W E = W E^T.  One launch pair per group: a group's W and E slots are
-        // contiguous whichever of them is shared
-        for (int g = 0; g < G; ++g) {
-            const double *Wg = dW + (nm == G ? (size_t)g * D * mm : 0);
-            double *WEg = dWE + (size_t)g * D * mm;
-            product(Wg, q_mode ? dE + (size_t)g * D * mm : dE + (size_t)g * mm, q_mode ? mm : 0, WEg, D);
-            product(WEg, Wg, mm, gam + (size_t)g * D * mm, D);
-        }
-    }
+    if (int rc = bg.launch(sc, G, nm, M, D, Mp, hv.len, dW, dq, q_mode, dU)) return rc;
     MomentGroupArgs a{};
     a.G = G; a.n_models = nm; a.D = D; a.C = C; a.P = P; a.M = M; a.Mp = Mp; a.NS = NS; a.steps = steps; a.unit_per_group = dq ? 1 : 0;
-    a.Z = dZ; a.variance = hv.variance; a.len = hv.len; a.beta = beta; a.gam = gam; a.x_last = dxl; a.S0 = dS0; a.log_Q = dlq;
+    a.Z = dZ; a.variance = hv.variance; a.len = hv.len; a.beta = bg.beta; a.gam = bg.gam; a.x_last = dxl; a.S0 = dS0; a.log_Q = dlq;
     a.ctrl = dctrl; a.part = part; a.state = state; a.m_x = dm; a.S_x = dS;
     if (!flt)
         for (int t = 0; t <= steps; ++t) launch_mg_step(sc.stream, a, t);
@@ -1011,4 +1040,120 @@ extern "C" int ffvd_op_moment_summary(const double *m_x, const double *S_x, int 
     double *dm = sc.upload(m_x, n), *dS = sc.upload(S_x, n * D);
     OP_CHECK(dm && dS, who);
     return mg_summary(sc, who, dm, dS, G, steps, D, q);
+}
+
+// ---- linearisation of the transition (transition_grad.h) ------------------------------------------------------------------------------
+// conditional_after_kernel_precalculation (conditionals_multi_output.py:306-387, white=True, full_cov=False) and its gradient with
+// respect to the rows of Xnew, SE-ARD only: values and gradients from K(Xnew, Z), beta and Gamma (the moment family's staging).
+namespace {
+struct TgOut {
+    double *means, *vars, *dmeans, *dvars, *mix_mean, *mix_var, *mix_dmean, *mix_dvar;
+    bool var_side() const { return vars || dvars || mix_var || mix_dvar; }
+};
+// at least one output; the mixture values both or neither; mixture gradients only together with the mixture values
+bool tg_outputs_ok(const TgOut &o) {
+    return (o.means || o.vars || o.dmeans || o.dvars || o.mix_mean || o.mix_var || o.mix_dmean || o.mix_dvar) && (!o.mix_mean == !o.mix_var) &&
+           (!(o.mix_dmean || o.mix_dvar) || o.mix_mean);
+}
+// scalar-argument checks shared by the two entry points (before any device call): cg_scalars_ok and G * D * N * P < 2^31
+bool tg_scalars_ok(int kind, int G, int n_models, int M, int P, int D, int N, int q_mode, int rows_per_pass) {
+    return cg_scalars_ok(kind, G, n_models, M, P, D, N, q_mode, rows_per_pass) && (long long)G * D * N * P < (1LL << 31);
+}
+const char *const tg_se_only = " (the input gradients are closed-form for the SE kernel only)";
+
+// Operands on the device -> beta, Gamma, the launches of transition_grad.h, the mixtures, the downloads.  dW: [nm * D] slots of
+// Mp x Mp (zero padded); dq: nullptr or the q slots of BetaGamma; dZ: [nm][M][P]; hv per (model, dim).
+int tg_run(Scratch &sc, const std::string &who, int G, int nm, int M, int P, int D, int N, int rows_per_pass, const HyperView &hv,
+           const double *dZ, const double *dW, const double *dq, int q_mode, const double *dU, const double *dX, const TgOut &o) {
+    const int Mp = round_up(M, NB);
+    const size_t out_n = (size_t)G * N * D, ND = (size_t)N * D;
+    TransitionGradArgs a{};
+    a.G = G; a.n_models = nm; a.M = M; a.Mp = Mp; a.P = P; a.D = D; a.N = N;
+    a.rows_per_pass = rows_per_pass > 0 ? rows_per_pass : cg_rows_per_pass(nm, D, Mp);
+    a.unit_per_group = dq ? 1 : 0; a.need_var = o.var_side() ? 1 : 0;
+    BetaGamma bg{};
+    const bool terms = bg.alloc(sc, G, nm, D, Mp, dq, q_mode, a.need_var);
+    const TransitionGradScratch need = tg_scratch_doubles(G, nm, D, P, Mp, N, a.rows_per_pass, bg.units, a.need_var);
+    a.hv = hv; a.Z = dZ; a.beta = bg.beta; a.gam = bg.gam; a.x = dX;
+    a.K = sc.alloc<double>(need.K); a.msum = sc.alloc<double>(need.msum); a.vpart = need.vpart ? sc.alloc<double>(need.vpart) : nullptr;
+    a.mean = sc.alloc<double>(out_n); a.dmean = sc.alloc<double>(out_n * P);
+    a.var = a.need_var ? sc.alloc<double>(out_n) : nullptr; a.dvar = a.need_var ? sc.alloc<double>(out_n * P) : nullptr;
+    double *dmm = o.mix_mean ? sc.alloc<double>(ND) : nullptr, *dmv = o.mix_mean ? sc.alloc<double>(ND) : nullptr;
+    double *dmdm = o.mix_dmean || o.mix_dvar ? sc.alloc<double>(ND * P) : nullptr, *dmdv = o.mix_dvar ? sc.alloc<double>(ND * P) : nullptr;
+    OP_CHECK(terms && a.K && a.msum && (!need.vpart || a.vpart) && a.mean && a.dmean && (!a.need_var || (a.var && a.dvar)) &&
+             (!o.mix_mean || (dmm && dmv)) && (!(o.mix_dmean || o.mix_dvar) || dmdm) && (!o.mix_dvar || dmdv), who);
+    if (int rc = bg.launch(sc, G, nm, M, D, Mp, hv.len, dW, dq, q_mode, dU)) return rc;
+    launch_transition_grad(sc.stream, a);
+    if (o.mix_mean) launch_cg_mixture(sc.stream, a.mean, a.var, G, ND, dmm, dmv);
+    if (dmdm) launch_tg_mixture(sc.stream, a.mean, a.dmean, a.dvar, dmm, G, ND, P, dmdm, dmdv);
+    OP_TRY(hipGetLastError());
+    auto down = [&](double *dst, const double *src, size_t n) { return !dst || sc.download(dst, src, n * sizeof(double)); };
+    if (!down(o.means, a.mean, out_n) || !down(o.vars, a.var, out_n) || !down(o.dmeans, a.dmean, out_n * P) || !down(o.dvars, a.dvar, out_n * P) ||
+        !down(o.mix_mean, dmm, ND) || !down(o.mix_var, dmv, ND) || !down(o.mix_dmean, dmdm, ND * P) || !down(o.mix_dvar, dmdv, ND * P))
+        return set_error(nullptr, FFVD_EDEVICE, who + ": copying the results back failed");
+    OP_TRY(hipStreamSynchronize(sc.stream));
+    return FFVD_OK;
+}
+}  // namespace
+
+// Posteriors given by the caller (also explicit-U models and SG-HMC samples of U: q_sqrts = NULL)
+extern "C" int ffvd_op_conditional_grad_grouped(int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M,
+                                                int P, int D, const double *logvariances, const double *loglengthscales, const double *fs,
+                                                const double *const *q_sqrts, int q_mode, const double *Xnew, int N, int rows_per_pass,
+                                                double *means, double *vars, double *dmeans, double *dvars, double *mix_mean,
+                                                double *mix_var, double *mix_dmean, double *mix_dvar) {
+    const std::string who = "ffvd_op_conditional_grad_grouped", bad = who + ": bad argument";
+    if (kind != FFVD_KERNEL_SE) return set_error(nullptr, FFVD_EINVAL, bad + tg_se_only);
+    if (!tg_scalars_ok(kind, G, n_models, M, P, D, N, q_mode, rows_per_pass)) return set_error(nullptr, FFVD_EINVAL, bad);
+    if (G == 0 || N == 0) return FFVD_OK;
+    const TgOut out{means, vars, dmeans, dvars, mix_mean, mix_var, mix_dmean, mix_dvar};
+    if (!Lm_inverse_seqs || !Zs || !logvariances || !loglengthscales || !fs || !Xnew || !tg_outputs_ok(out))
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    const size_t nK = (size_t)n_models * D, nq = given_nq(q_sqrts, q_mode, G, D);
+    if (!given_tables_ok(Lm_inverse_seqs, nK, q_sqrts, nq)) return set_error(nullptr, FFVD_EINVAL, bad);
+    OP_BEGIN(who);
+    const int Mp = round_up(M, NB);
+    const bool with_q = nq && out.var_side();                    // (the q slices enter the variance alone)
+    double *dW = upload_matrix_table(sc, Lm_inverse_seqs, nK, M, Mp), *dq = with_q ? upload_matrix_table(sc, q_sqrts, nq, M, Mp) : nullptr;
+    GroupHypers gh = stage_group_hypers(sc, kind, n_models, D, M, Mp, P, Zs, logvariances, loglengthscales);
+    double *dU = sc.upload(fs, (size_t)G * D * M), *dX = sc.upload(Xnew, (size_t)N * P);
+    OP_CHECK(dW && (!with_q || dq) && dU && dX && gh.logs(sc) && gh.blocks(sc), who);
+    gh.prep(sc.stream);
+    return tg_run(sc, who, G, n_models, M, P, D, N, rows_per_pass, gh.hv(), gh.dZ, dW, dq, q_mode, dU, dX, out);
+}
+
+// The collapsed posteriors of ffvd_op_posterior_grouped (base_model.py:243-256) linearised at Xnew without leaving the device: L^-T is
+// packed from the K_uu slabs, U_mean read where the matvec left it, the q slices packed by launch_pg_pack (as the moment family)
+extern "C" int ffvd_op_posterior_conditional_grad_grouped(int kind, int G, int n_models, const double *Zs, int M, int P, int D,
+                                                          const double *logvariances, const double *loglengthscales, const double *Xs,
+                                                          const double *ctrl_fit, int C, int T, const double *log_Qs, double jitter,
+                                                          int groups_per_pass, int q_mode, const double *Xnew, int N, int rows_per_pass,
+                                                          double *means, double *vars, double *dmeans, double *dvars, double *mix_mean,
+                                                          double *mix_var, double *mix_dmean, double *mix_dvar, double *U_means) {
+    const std::string who = "ffvd_op_posterior_conditional_grad_grouped", bad = who + ": bad argument";
+    if (kind != FFVD_KERNEL_SE) return set_error(nullptr, FFVD_EINVAL, bad + tg_se_only);
+    if (!pg_scalars_ok(kind, G, n_models, M, P, D, C, T, groups_per_pass, jitter) ||
+        !tg_scalars_ok(kind, G, n_models, M, P, D, N, q_mode, rows_per_pass))
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    if (G == 0 || N == 0) return FFVD_OK;
+    const TgOut out{means, vars, dmeans, dvars, mix_mean, mix_var, mix_dmean, mix_dvar};
+    if (!Zs || !logvariances || !loglengthscales || !Xs || !log_Qs || !Xnew || !tg_outputs_ok(out) || (C > 0 && !ctrl_fit))
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    OP_BEGIN(who);
+    const PgIn in{who, kind, G, n_models, M, P, D, C, T, groups_per_pass, Zs, logvariances, loglengthscales, Xs, ctrl_fit, log_Qs, jitter};
+    PgWork w{};
+    const int Mp = round_up(M, NB), nK = n_models * D;
+    const size_t mm = (size_t)Mp * Mp;
+    const bool need_q = out.var_side(), have_q = need_q && pg_want_q(sc, w, q_mode, G, D, M);
+    double *dW = sc.alloc<double>((size_t)nK * mm), *dX = sc.upload(Xnew, (size_t)N * P);
+    OP_CHECK(dW && dX && (!need_q || have_q), who);
+    if (int rc = pg_posterior(sc, in, w)) return rc;
+    double *dZ = sc.upload(Zs, (size_t)n_models * M * P);
+    OP_CHECK(dZ, who);
+    launch_pg_pack(sc.stream, w.Kuu, 2 * mm, Mp, Mp, nK, 1, M, 1, dW, Mp, Mp, nK);
+    if (int rc = tg_run(sc, who, G, n_models, M, P, D, N, rows_per_pass, w.hv, dZ, dW, need_q ? pg_q(w, q_mode) : nullptr, q_mode, w.U, dX, out))
+        return rc;
+    if (U_means && !sc.download(U_means, w.U, (size_t)G * D * M * sizeof(double)))
+        return set_error(nullptr, FFVD_EDEVICE, who + ": copying the results back failed");
+    return FFVD_OK;
 }

@@ -646,3 +646,36 @@ class DGPSSM:
             mean, var, mm, mv = cmo.conditional_grouped(Lm, lay.Z, lay.kernel, [lay.U], None, Xnew, q_mode=q_mode,
                                                         per_group=bool(per_chain))
         return dict(mean=mean, var=var, mix_mean=mm, mix_var=mv)
+
+    def linearize(self, Xnew, *, q_mode="reference", per_chain=True):
+        """The local linear model of the learned transition at the rows of Xnew (N, D + C): `predict_transition` together with the
+        gradients of mean and variance of f(x, c) with respect to x and c, in closed form (SE-ARD kernels only).
+        A = I + d mean / dx and B = d mean / dc: A is the Jacobian of x + f(x, c), i.e. of the TRANSITION MEAN x_next = x + f_mu, not
+        of f (subtract I for that); B is the same for both.  x_next ~= x_next(x0, c0) + A (x - x0) + B (c - c0) is what an EKF,
+        iLQR / MPC or a stability analysis takes; dvar is the gradient of the predictive variance of f (the process noise Q does not
+        depend on the input).
+        Collapsed U: the S = num_chains posteriors in one fused `posterior_conditional_grad_grouped` call; explicit U: one group
+        (leading axis 1), no q_sqrt term -- the split and q_mode of `predict_transition`.
+        Returns a dict: mean, var (S or 1, N, D), dmean, dvar (S or 1, N, D, D + C), A (S or 1, N, D, D), B (S or 1, N, D, C) (None
+        unless per_chain); mix_mean, mix_var (N, D), mix_dmean, mix_dvar (N, D, D + C), mix_A (N, D, D), mix_B (N, D, C): the
+        equal-weight mixture over the chains, mix_A = I + mix_dmean[..., :D]."""
+        from . import conditionals_multi_output as cmo
+        from .prediction import posterior_conditional_grad_grouped
+        if q_mode not in cmo.Q_MODES:
+            raise ValueError(f"linearize: q_mode: expected one of {sorted(cmo.Q_MODES)}, got {q_mode!r}")
+        if self._host_stale:
+            self.pull_parameters()
+        lay = self.layers[-1]
+        if self.U_collapse:
+            S = self.num_chains
+            out = posterior_conditional_grad_grouped(lay.Z, lay.kernel, [self._X_chains[s_] for s_ in range(S)], self.Q,
+                                                     self.control_inputs, Xnew, q_mode=q_mode, per_group=bool(per_chain))
+        else:
+            Lm = cmo.kernel_pre_cal(lay.Z, lay.kernel)
+            out = cmo.conditional_grad_grouped(Lm, lay.Z, lay.kernel, [lay.U], None, Xnew, q_mode=q_mode, per_group=bool(per_chain))
+        for key, a_key, b_key in (("dmean", "A", "B"), ("mix_dmean", "mix_A", "mix_B")):
+            dm = out[key]
+            D = None if dm is None else dm.shape[-2]
+            out[a_key] = None if dm is None else np.eye(D) + dm[..., :D]
+            out[b_key] = None if dm is None else np.ascontiguousarray(dm[..., D:])
+        return out

@@ -207,6 +207,36 @@ def posterior_conditional_grouped(Zs, kerns, Xs, Qs, control_inputs, Xnew, *, q_
     return (means, vars_, mm, mv, U) if return_U else (means, vars_, mm, mv)
 
 
+def posterior_conditional_grad_grouped(Zs, kerns, Xs, Qs, control_inputs, Xnew, *, q_mode="reference", jitter=JITTER, groups_per_pass=0,
+                                       rows_per_pass=0, per_group=True, summary=True, variance=True, return_U=False):
+    """The collapsed posterior of G groups and the linearisation of its transition function f(x, c) at Xnew (N, P) in ONE call
+    (`ffvd_op_posterior_conditional_grad_grouped`): what `conditionals_multi_output.collapse_u_mean_grouped` followed by
+    `conditional_grad_grouped` computes, without the posteriors leaving the device.  SE-ARD kernels only.  `Zs` / `kerns` / `Xs` / `Qs` /
+    `control_inputs`: as `posterior_rollout_grouped`; the other arguments and the returned dict: as `conditional_grad_grouped`, plus
+    `U_means` (G, M, D) with return_U."""
+    from .conditionals_multi_output import GRAD_KEYS, check_se_only, grad_outputs
+    who = "posterior_conditional_grad_grouped"
+    a = pack_posterior_groups(Zs, kerns, Xs, control_inputs, Qs, who)
+    check_se_only(who, a["kind"])
+    G, nm, M, D, P = a["G"], a["n_models"], a["M"], a["D"], a["P"]
+    if int(groups_per_pass) < 0:
+        raise ValueError(f"{who}: groups_per_pass must be 0 (automatic) or positive")
+    Xnew, qm = check_conditional_query(who, Xnew, P, q_mode, rows_per_pass, per_group, summary)
+    N = Xnew.shape[0]
+    out = grad_outputs(G, N, D, P, per_group, summary, variance)
+    U = np.empty((G, M, D)) if return_U else None
+    dp = _lib.dptr
+    opt = lambda x: None if x is None else dp(x)
+    rc = _lib.load().ffvd_op_posterior_conditional_grad_grouped(a["kind"], G, nm, dp(a["Z"]), M, P, D, dp(a["logvar"]), opt(a["loglen"]),
+                                                                dp(a["X"]), opt(a["ctrl"]), a["C"], a["T"], dp(a["log_Q"]), float(jitter),
+                                                                int(groups_per_pass), qm, dp(Xnew), N, int(rows_per_pass),
+                                                                *[opt(out[k]) for k in GRAD_KEYS], opt(U))
+    _lib.check(rc, None, who)
+    if return_U:
+        out["U_means"] = U
+    return out
+
+
 def predict_y_summary(predict_x, predict_x_var, CC, DD, log_Rchols, Y_test=None, Y_train_std=1.0):
     """base_model.py:330-348 (host-side: a (num, test_len, D) x (D, Ydim) contraction and three means)."""
     CC, DD = np.asarray(CC, dtype=np.float64), np.asarray(DD, dtype=np.float64)

@@ -603,6 +603,48 @@ int  ffvd_op_posterior_conditional_grouped(int kind, int G, int n_models, const 
                                            int groups_per_pass, int q_mode, const double *Xnew, int N, int rows_per_pass,
                                            double *means, double *vars, double *mix_mean, double *mix_var, double *U_means);
 
+/* Linearisation of the transition function: ffvd_op_conditional_grouped's mean and variance TOGETHER WITH their gradients with respect
+ * to the rows of Xnew, all P = D + C columns (the first D give d/dx, the last C give d/dc).  SE-ARD kernels only (FFVD_EINVAL for
+ * LinearK: its Jacobian is constant).  conditional_after_kernel_precalculation (conditionals_multi_output.py:306-387, white=True,
+ * full_cov=False) written with the posterior terms of ffvd_op_moment_grouped, beta = W_d u_{g,d} and Gamma = W_d (I - q q^T) W_d^T
+ * (q: slice 0 of the group's stack for q_mode 0, slice d for q_mode 1; q_sqrts = NULL: W_d W_d^T), and differentiated: with
+ * k_j = variance_d exp(-sum_p (x_p - z_jp)^2 / (2 l_dp^2)) (:349's K(Xnew, Z)), nu_jp = z_jp - x_p and t = Gamma k,
+ *   means[g][n][d]     = sum_j k_j beta_j                              (:365)
+ *   vars[g][n][d]      = variance_d - sum_j k_j t_j                    (:356, :369-380)
+ *   dmeans[g][n][d][p] =  (1 / l_dp^2) sum_j k_j beta_j nu_jp
+ *   dvars[g][n][d][p]  = -(2 / l_dp^2) sum_j k_j t_j nu_jp
+ * The mixture keeps ffvd_op_conditional_grouped's mix_mean / mix_var; its gradients in centred form, g ascending:
+ *   mix_dmean = (sum_g dmean_g) / G,   mix_dvar = (sum_g (dvar_g + 2 (mean_g - mix_mean) dmean_g)) / G.
+ * The local linear model of x' = x + f(x, c) at row n is A = I + dmeans[g][n][:, :D], B = dmeans[g][n][:, D:].
+ * Arguments as ffvd_op_conditional_grouped.  Outputs: means, vars G x N x D; dmeans, dvars G x N x D x P; mix_mean, mix_var N x D;
+ * mix_dmean, mix_dvar N x D x P.  Any may be NULL, at least one must be given; mix_mean and mix_var both or neither; mixture gradients
+ * only together with the mixture values.  The variance side (Gamma and the product below) is skipped when none of vars, dvars,
+ * mix_var, mix_dvar is asked for.
+ * K(Xnew, Z) is built once per (model, dim) and pass.  The variance side is a 128 x 128-tiled fp64-MFMA product T = K Gamma per unit --
+ * (group, dim) with q_sqrts, (model, dim) without -- whose epilogue keeps P + 1 weighted row sums per column tile; T never reaches memory.
+ * rows_per_pass: as ffvd_op_conditional_grouped (K takes n_models * D * rows * Mp doubles).
+ * Determinism: two identical calls are bit-identical; a group's outputs do not depend on G or on the other groups, a row's outputs
+ * not on N, on the other rows or on the pass size (fixed summation orders, no atomics).
+ * Limits: those of ffvd_op_conditional_grouped and G * D * N * P < 2^31; FFVD_EINVAL beyond them, before any device call.  G = 0 or
+ * N = 0: FFVD_OK, nothing is touched. */
+int  ffvd_op_conditional_grad_grouped(int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M, int P,
+                                      int D, const double *logvariances, const double *loglengthscales, const double *fs,
+                                      const double *const *q_sqrts, int q_mode, const double *Xnew, int N, int rows_per_pass,
+                                      double *means, double *vars, double *dmeans, double *dvars, double *mix_mean, double *mix_var,
+                                      double *mix_dmean, double *mix_dvar);
+
+/* ffvd_op_posterior_grouped (kernel_pre_cal :124-169 and collapse_u_mean_after_kernel_precalculation :206-227, as base_model.py:243-256
+ * calls them) followed by ffvd_op_conditional_grad_grouped WITHOUT the posteriors leaving the device, as
+ * ffvd_op_posterior_conditional_grouped: W is packed from the K_uu slabs, f = U_mean where the matvec left it, the q slices are packed
+ * by a device kernel.  Errors, stall recovery, "no output written on failure" and determinism: as ffvd_op_posterior_grouped.
+ * Limits: those of ffvd_op_posterior_grouped and of ffvd_op_conditional_grad_grouped.  G = 0 or N = 0: FFVD_OK, nothing is touched. */
+int  ffvd_op_posterior_conditional_grad_grouped(int kind, int G, int n_models, const double *Zs, int M, int P, int D,
+                                                const double *logvariances, const double *loglengthscales, const double *Xs,
+                                                const double *ctrl_fit, int C, int T, const double *log_Qs, double jitter,
+                                                int groups_per_pass, int q_mode, const double *Xnew, int N, int rows_per_pass,
+                                                double *means, double *vars, double *dmeans, double *dvars, double *mix_mean,
+                                                double *mix_var, double *mix_dmean, double *mix_dvar, double *U_means);
+
 /* Moment-matched prediction: the Gaussian state x_t ~ N(mu, Sigma) of each of G posteriors is pushed through
  * x_{t+1} = x_t + f(x_t, ctrl_t) + N(0, Q) in closed form and re-approximated as a Gaussian (Girard et al. 2003; the propagation of
  * PILCO); one launch per step for all groups, nothing is sampled.  SE-ARD kernels only.  The posterior is that of
