@@ -62,6 +62,15 @@ struct MomentFilterArgs {
 };
 void launch_mg_filter_step(hipStream_t stream, const MomentGroupArgs &a, const MomentFilterArgs &f, int t);
 
+// Linearised filtering (moment_linear.hip; DESIGN.md section 9, "Linearised filtering"): the filter's launch sequence, arguments,
+// update and stores with the extended Kalman rule in place of moment matching.  With A = I + J, J the Jacobian of the posterior mean
+// of f at [mu, c_t] (state columns) and v its variance there: m^- = mu + m, S^- = A S A^T + diag(v + Q), cross = S A^T.
+// Workgroup (group, dim, slab of MG_SLAB rows of Gamma_dim): grid x = G * D * NS (below the moment step's G * npair * NS).
+// part is [2][G][D][D + 2][NS]: per dim the slab sums of k_i beta_i, of k_i beta_i nu_ip (p < D) and of k_i (Gamma k)_i.
+constexpr int MG_LINEAR_MAXM = 2048; // the kernel row of a dim lives in LDS (the family's limit on M)
+__host__ __device__ inline int mg_linear_fields(int D) { return D * (D + 2); }
+void launch_mg_linear_step(hipStream_t stream, const MomentGroupArgs &a, const MomentFilterArgs &f, int t);
+
 // RTS pass over the stored stacks, one workgroup per group, i = steps - 2 .. 0:  J_i = X_{i+1} (S^-_{i+1})^-1 (pivoted elimination),
 // m^s_i = m_i + J_i (m^s_{i+1} - m^-_{i+1}),  S^s_i = S_i + J_i (S^s_{i+1} - S^-_{i+1}) J_i^T (exactly symmetric); the last row is the
 // filtered one bit for bit.  Every sum has a fixed order.

@@ -620,6 +620,8 @@ bool mg_scalars_ok(int kind, int G, int n_models, int M, int P, int D, int C, in
     return (long long)G * D * Mp * Mp <= (1LL << 29) && (long long)G * mg_npair(D) * NS < (1LL << 31) &&
            (steps == 0 || G <= ((1LL << 31) - 1) / steps / D / D);
 }
+// the propagation rule of the filter's launches (mg_run)
+enum { MG_METHOD_MOMENT = 0, MG_METHOD_LINEAR = 1 };
 // the trailing summary block of the entry points: asked for when anything in it is given
 bool mg_summary_wanted(const SummaryReq &q) {
     return q.CC || q.DD || q.noise_std || q.J != 0 || q.Y_test || q.n_test != 0 || q.y_mean || q.y_var || q.y_var_total || q.lpd || q.lpd_gauss;
@@ -739,18 +741,24 @@ struct BetaGamma {
 
 // Operands on the device -> beta, Gamma, the step launches, the summary, the downloads.  flt: the launches are those of the filter
 // (moment_group.h), m_x / S_x are the predicted moments, and `sum` is REPLACED by the pooled one-step summary of the request when that
-// asks for one (the filter callers pass nullptr).  dW: [n_models * D] slots of Mp x Mp (upper triangular, zero padded); dq: nullptr,
-// or [G] (q_mode 0) / [G * D] (q_mode 1) slots of Mp x Mp; hv: variance / len per (model, dim).
+// asks for one (the filter callers pass nullptr).  method: the propagation rule of the filter's launches, MG_METHOD_MOMENT (moment
+// matching) or MG_METHOD_LINEAR (the linearisation at the filtered mean, moment_linear.hip; a filter request without a forecast).
+// dW: [n_models * D] slots of Mp x Mp (upper triangular, zero padded); dq: nullptr, or [G] (q_mode 0) / [G * D] (q_mode 1) slots of
+// Mp x Mp; hv: variance / len per (model, dim).
 int mg_run(Scratch &sc, const std::string &who, int G, int nm, int M, int P, int D, int C, int steps, const HyperView &hv, const double *dZ,
            const double *dW, const double *dq, int q_mode, const double *dU, const double *dxl, const double *dS0, const double *dlq,
-           const double *dctrl, double *m_x, double *S_x, const SummaryReq *sum, const FilterReq *flt, const ForecastReq *fc = nullptr) {
+           const double *dctrl, double *m_x, double *S_x, const SummaryReq *sum, const FilterReq *flt, const ForecastReq *fc = nullptr,
+           int method = MG_METHOD_MOMENT) {
     const int Mp = round_up(M, NB), NS = (M + MG_SLAB - 1) / MG_SLAB;
+    const bool linear = method == MG_METHOD_LINEAR;
+    if (linear && (!flt || fc))
+        return set_error(nullptr, FFVD_EINVAL, who + ": bad argument (the linearised rule is built for the filter only, not for forecasts)");
     const size_t nm_x = (size_t)G * steps * D, nS_x = nm_x * D;
     const SummaryReq fsum = flt ? flt->pooled(steps) : SummaryReq{};
     if (fsum.y_mean || fsum.y_var_total || fsum.lpd || fsum.lpd_gauss) sum = &fsum;
     BetaGamma bg{};
     const bool terms = bg.alloc(sc, G, nm, D, Mp, dq, q_mode);
-    double *part = sc.alloc<double>((size_t)2 * G * mg_fields(D) * NS), *state = sc.alloc<double>((size_t)2 * G * (D + D * D));
+    double *part = sc.alloc<double>((size_t)2 * G * (linear ? mg_linear_fields(D) : mg_fields(D)) * NS), *state = sc.alloc<double>((size_t)2 * G * (D + D * D));
     double *dm = sc.alloc<double>(nm_x), *dS = sc.alloc<double>(nS_x);
     OP_CHECK(terms && part && state && dm && dS, who);
     MomentFilterArgs fa{};
@@ -790,7 +798,10 @@ int mg_run(Scratch &sc, const std::string &who, int G, int nm, int M, int P, int
     if (!flt)
         for (int t = 0; t <= steps; ++t) launch_mg_step(sc.stream, a, t);
     else {
-        for (int t = 0; t <= steps; ++t) launch_mg_filter_step(sc.stream, a, fa, t);
+        if (linear)
+            for (int t = 0; t <= steps; ++t) launch_mg_linear_step(sc.stream, a, fa, t);
+        else
+            for (int t = 0; t <= steps; ++t) launch_mg_filter_step(sc.stream, a, fa, t);
         if (smooth) launch_mg_smooth(sc.stream, sa);
     }
     if (fc) {
@@ -832,12 +843,13 @@ int mg_run(Scratch &sc, const std::string &who, int G, int nm, int M, int P, int
     return FFVD_OK;
 }
 const char *const mg_se_only = " (moment matching is closed-form for the SE kernel only)";
+const char *const mg_linear_se_only = " (the linearised filter is built for the SE kernel only: its kernel row and Jacobian are SE-ARD's)";
 
 // Posteriors given by the caller (also explicit-U models, SG-HMC samples of U: q_sqrts = NULL) through mg_run, scalars and pointers checked
 int mg_given_run(const std::string &who, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M, int P, int D,
                  const double *logvariances, const double *loglengthscales, const double *fs, const double *const *q_sqrts, int q_mode,
                  const double *x_lasts, const double *S0s, const double *ctrl, int C, int steps, const double *log_Qs, double *m_x,
-                 double *S_x, const SummaryReq *sum, const FilterReq *flt, const ForecastReq *fc = nullptr) {
+                 double *S_x, const SummaryReq *sum, const FilterReq *flt, const ForecastReq *fc = nullptr, int method = MG_METHOD_MOMENT) {
     const size_t nK = (size_t)n_models * D, GD = (size_t)G * D, nq = given_nq(q_sqrts, q_mode, G, D);
     if (!given_tables_ok(Lm_inverse_seqs, nK, q_sqrts, nq)) return set_error(nullptr, FFVD_EINVAL, who + ": bad argument");
     OP_BEGIN(who);
@@ -848,14 +860,16 @@ int mg_given_run(const std::string &who, int G, int n_models, const double *cons
     double *dctrl = C ? sc.upload(ctrl, (size_t)steps * C) : nullptr;
     OP_CHECK(dW && (!nq || dq) && dU && dxl && (!S0s || dS0) && dlq && (!C || dctrl) && gh.logs(sc) && gh.blocks(sc), who);
     gh.prep(sc.stream);
-    return mg_run(sc, who, G, n_models, M, P, D, C, steps, gh.hv(), gh.dZ, dW, dq, q_mode, dU, dxl, dS0, dlq, dctrl, m_x, S_x, sum, flt, fc);
+    return mg_run(sc, who, G, n_models, M, P, D, C, steps, gh.hv(), gh.dZ, dW, dq, q_mode, dU, dxl, dS0, dlq, dctrl, m_x, S_x, sum, flt, fc,
+                  method);
 }
 
 // The collapsed posteriors of ffvd_op_posterior_grouped (base_model.py:243-256) through mg_run without leaving the device: L^-T is
 // packed from the K_uu slabs, U_mean read where the matvec left it, the q slices packed by launch_pg_pack (exact zeros in the padding
 // and the strict lower triangle); the start means are x0s or, without them, the last rows of Xs.
 int mg_posterior_run(const PgIn &in, int q_mode, const double *x0s, const double *S0s, const double *ctrl_roll, int steps, double *m_x,
-                     double *S_x, double *U_means, const SummaryReq *sum, const FilterReq *flt, const ForecastReq *fc = nullptr) {
+                     double *S_x, double *U_means, const SummaryReq *sum, const FilterReq *flt, const ForecastReq *fc = nullptr,
+                     int method = MG_METHOD_MOMENT) {
     const std::string &who = in.who;
     OP_BEGIN(who);
     PgWork w{};
@@ -871,7 +885,7 @@ int mg_posterior_run(const PgIn &in, int q_mode, const double *x0s, const double
     launch_pg_pack(sc.stream, w.Kuu, 2 * mm, Mp, Mp, nK, 1, M, 1, dW, Mp, Mp, nK);
     if (!x0s) launch_pg_x_last(sc.stream, w.Xs, G, in.T, D, dxl);
     if (int rc = mg_run(sc, who, G, nm, M, in.P, D, C, steps, w.hv, dZ, dW, pg_q(w, q_mode), q_mode, w.U, dxl, dS0, w.log_Qs, dctrl, m_x, S_x,
-                        sum, flt, fc))
+                        sum, flt, fc, method))
         return rc;
     if (U_means && !sc.download(U_means, w.U, GD * M * sizeof(double)))
         return set_error(nullptr, FFVD_EDEVICE, who + ": copying the results back failed");
@@ -922,7 +936,24 @@ extern "C" int ffvd_op_posterior_moment_grouped(int kind, int G, int n_models, c
 }
 
 // ---- filtering and smoothing (moment_group.h) -------------------------------------------------------------------------------------
-// ffvd_op_moment_grouped with a measurement update after every step (posteriors given by the caller)
+// ffvd_op_moment_grouped with a measurement update after every step (posteriors given by the caller); `method`: the propagation rule
+namespace {
+int filter_given(const std::string &who, int method, int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs,
+                 int M, int P, int D, const double *logvariances, const double *loglengthscales, const double *fs,
+                 const double *const *q_sqrts, int q_mode, const double *x_lasts, const double *S0s, const double *ctrl, int C, int steps,
+                 const double *log_Qs, double *m_pred, double *S_pred, const FilterReq &f) {
+    const std::string bad = who + ": bad argument";
+    if (kind != FFVD_KERNEL_SE) return set_error(nullptr, FFVD_EINVAL, bad + (method == MG_METHOD_LINEAR ? mg_linear_se_only : mg_se_only));
+    if (!mg_scalars_ok(kind, G, n_models, M, P, D, C, steps, q_mode) || !filter_scalars_ok(f)) return set_error(nullptr, FFVD_EINVAL, bad);
+    if (G == 0 || steps == 0) return FFVD_OK;
+    if (!Lm_inverse_seqs || !Zs || !logvariances || !loglengthscales || !fs || !x_lasts || !log_Qs || (C > 0 && !ctrl) ||
+        !filter_arrays_ok(f, steps, m_pred, S_pred))
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    return mg_given_run(who, G, n_models, Lm_inverse_seqs, Zs, M, P, D, logvariances, loglengthscales, fs, q_sqrts, q_mode, x_lasts, S0s, ctrl,
+                        C, steps, log_Qs, m_pred, S_pred, nullptr, &f, nullptr, method);
+}
+}  // namespace
+
 extern "C" int ffvd_op_filter_grouped(int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M, int P,
                                       int D, const double *logvariances, const double *loglengthscales, const double *fs,
                                       const double *const *q_sqrts, int q_mode, const double *x_lasts, const double *S0s,
@@ -930,21 +961,48 @@ extern "C" int ffvd_op_filter_grouped(int kind, int G, int n_models, const doubl
                                       const double *noise_std, int J, const double *Y_obs, double *m_pred, double *S_pred,
                                       double *m_filt, double *S_filt, double *cross, double *lpd, double *lpd_joint, double *m_smooth,
                                       double *S_smooth, double *y_mean, double *y_var_total, double *lpd_mix, double *lpd_gauss) {
-    const std::string who = "ffvd_op_filter_grouped", bad = who + ": bad argument";
     const FilterReq f{CC, DD, noise_std, J, Y_obs, m_filt, S_filt, cross, lpd, lpd_joint, m_smooth, S_smooth, y_mean, y_var_total, lpd_mix,
                       lpd_gauss};
-    if (kind != FFVD_KERNEL_SE) return set_error(nullptr, FFVD_EINVAL, bad + mg_se_only);
-    if (!mg_scalars_ok(kind, G, n_models, M, P, D, C, steps, q_mode) || !filter_scalars_ok(f)) return set_error(nullptr, FFVD_EINVAL, bad);
-    if (G == 0 || steps == 0) return FFVD_OK;
-    if (!Lm_inverse_seqs || !Zs || !logvariances || !loglengthscales || !fs || !x_lasts || !log_Qs || (C > 0 && !ctrl) ||
-        !filter_arrays_ok(f, steps, m_pred, S_pred))
-        return set_error(nullptr, FFVD_EINVAL, bad);
-    return mg_given_run(who, G, n_models, Lm_inverse_seqs, Zs, M, P, D, logvariances, loglengthscales, fs, q_sqrts, q_mode, x_lasts, S0s, ctrl,
-                        C, steps, log_Qs, m_pred, S_pred, nullptr, &f);
+    return filter_given("ffvd_op_filter_grouped", MG_METHOD_MOMENT, kind, G, n_models, Lm_inverse_seqs, Zs, M, P, D, logvariances,
+                        loglengthscales, fs, q_sqrts, q_mode, x_lasts, S0s, ctrl, C, steps, log_Qs, m_pred, S_pred, f);
+}
+
+// The same with the linearised (extended Kalman) rule in place of moment matching (moment_linear.hip)
+extern "C" int ffvd_op_filter_linear_grouped(int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M,
+                                             int P, int D, const double *logvariances, const double *loglengthscales, const double *fs,
+                                             const double *const *q_sqrts, int q_mode, const double *x_lasts, const double *S0s,
+                                             const double *ctrl, int C, int steps, const double *log_Qs, const double *CC,
+                                             const double *DD, const double *noise_std, int J, const double *Y_obs, double *m_pred,
+                                             double *S_pred, double *m_filt, double *S_filt, double *cross, double *lpd, double *lpd_joint,
+                                             double *m_smooth, double *S_smooth, double *y_mean, double *y_var_total, double *lpd_mix,
+                                             double *lpd_gauss) {
+    const FilterReq f{CC, DD, noise_std, J, Y_obs, m_filt, S_filt, cross, lpd, lpd_joint, m_smooth, S_smooth, y_mean, y_var_total, lpd_mix,
+                      lpd_gauss};
+    return filter_given("ffvd_op_filter_linear_grouped", MG_METHOD_LINEAR, kind, G, n_models, Lm_inverse_seqs, Zs, M, P, D, logvariances,
+                        loglengthscales, fs, q_sqrts, q_mode, x_lasts, S0s, ctrl, C, steps, log_Qs, m_pred, S_pred, f);
 }
 
 // The collapsed posteriors of ffvd_op_posterior_grouped filtered without leaving the device (as ffvd_op_posterior_moment_grouped);
 // x0s NULL: the start means are the last rows of Xs
+namespace {
+int filter_posterior(const std::string &who, int method, int kind, int G, int n_models, const double *Zs, int M, int P, int D,
+                     const double *logvariances, const double *loglengthscales, const double *Xs, const double *ctrl_fit, int C, int T,
+                     const double *log_Qs, double jitter, int groups_per_pass, int q_mode, const double *x0s, const double *S0s,
+                     const double *ctrl_roll, int steps, double *m_pred, double *S_pred, double *U_means, const FilterReq &f) {
+    const std::string bad = who + ": bad argument";
+    if (kind != FFVD_KERNEL_SE) return set_error(nullptr, FFVD_EINVAL, bad + (method == MG_METHOD_LINEAR ? mg_linear_se_only : mg_se_only));
+    if (!pg_scalars_ok(kind, G, n_models, M, P, D, C, T, groups_per_pass, jitter) || !mg_scalars_ok(kind, G, n_models, M, P, D, C, steps, q_mode) ||
+        !filter_scalars_ok(f))
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    if (G == 0 || steps == 0) return FFVD_OK;
+    if (!Zs || !logvariances || !loglengthscales || !Xs || !log_Qs || (C > 0 && (!ctrl_fit || !ctrl_roll)) ||
+        !filter_arrays_ok(f, steps, m_pred, S_pred))
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    const PgIn in{who, kind, G, n_models, M, P, D, C, T, groups_per_pass, Zs, logvariances, loglengthscales, Xs, ctrl_fit, log_Qs, jitter};
+    return mg_posterior_run(in, q_mode, x0s, S0s, ctrl_roll, steps, m_pred, S_pred, U_means, nullptr, &f, nullptr, method);
+}
+}  // namespace
+
 extern "C" int ffvd_op_posterior_filter_grouped(int kind, int G, int n_models, const double *Zs, int M, int P, int D,
                                                 const double *logvariances, const double *loglengthscales, const double *Xs,
                                                 const double *ctrl_fit, int C, int T, const double *log_Qs, double jitter,
@@ -954,19 +1012,28 @@ extern "C" int ffvd_op_posterior_filter_grouped(int kind, int G, int n_models, c
                                                 double *m_filt, double *S_filt, double *cross, double *lpd, double *lpd_joint,
                                                 double *m_smooth, double *S_smooth, double *y_mean, double *y_var_total, double *lpd_mix,
                                                 double *lpd_gauss, double *U_means) {
-    const std::string who = "ffvd_op_posterior_filter_grouped", bad = who + ": bad argument";
     const FilterReq f{CC, DD, noise_std, J, Y_obs, m_filt, S_filt, cross, lpd, lpd_joint, m_smooth, S_smooth, y_mean, y_var_total, lpd_mix,
                       lpd_gauss};
-    if (kind != FFVD_KERNEL_SE) return set_error(nullptr, FFVD_EINVAL, bad + mg_se_only);
-    if (!pg_scalars_ok(kind, G, n_models, M, P, D, C, T, groups_per_pass, jitter) || !mg_scalars_ok(kind, G, n_models, M, P, D, C, steps, q_mode) ||
-        !filter_scalars_ok(f))
-        return set_error(nullptr, FFVD_EINVAL, bad);
-    if (G == 0 || steps == 0) return FFVD_OK;
-    if (!Zs || !logvariances || !loglengthscales || !Xs || !log_Qs || (C > 0 && (!ctrl_fit || !ctrl_roll)) ||
-        !filter_arrays_ok(f, steps, m_pred, S_pred))
-        return set_error(nullptr, FFVD_EINVAL, bad);
-    const PgIn in{who, kind, G, n_models, M, P, D, C, T, groups_per_pass, Zs, logvariances, loglengthscales, Xs, ctrl_fit, log_Qs, jitter};
-    return mg_posterior_run(in, q_mode, x0s, S0s, ctrl_roll, steps, m_pred, S_pred, U_means, nullptr, &f);
+    return filter_posterior("ffvd_op_posterior_filter_grouped", MG_METHOD_MOMENT, kind, G, n_models, Zs, M, P, D, logvariances,
+                            loglengthscales, Xs, ctrl_fit, C, T, log_Qs, jitter, groups_per_pass, q_mode, x0s, S0s, ctrl_roll, steps, m_pred,
+                            S_pred, U_means, f);
+}
+
+// The same with the linearised (extended Kalman) rule in place of moment matching (moment_linear.hip)
+extern "C" int ffvd_op_posterior_filter_linear_grouped(int kind, int G, int n_models, const double *Zs, int M, int P, int D,
+                                                       const double *logvariances, const double *loglengthscales, const double *Xs,
+                                                       const double *ctrl_fit, int C, int T, const double *log_Qs, double jitter,
+                                                       int groups_per_pass, int q_mode, const double *x0s, const double *S0s,
+                                                       const double *ctrl_roll, int steps, const double *CC, const double *DD,
+                                                       const double *noise_std, int J, const double *Y_obs, double *m_pred,
+                                                       double *S_pred, double *m_filt, double *S_filt, double *cross, double *lpd,
+                                                       double *lpd_joint, double *m_smooth, double *S_smooth, double *y_mean,
+                                                       double *y_var_total, double *lpd_mix, double *lpd_gauss, double *U_means) {
+    const FilterReq f{CC, DD, noise_std, J, Y_obs, m_filt, S_filt, cross, lpd, lpd_joint, m_smooth, S_smooth, y_mean, y_var_total, lpd_mix,
+                      lpd_gauss};
+    return filter_posterior("ffvd_op_posterior_filter_linear_grouped", MG_METHOD_LINEAR, kind, G, n_models, Zs, M, P, D, logvariances,
+                            loglengthscales, Xs, ctrl_fit, C, T, log_Qs, jitter, groups_per_pass, q_mode, x0s, S0s, ctrl_roll, steps, m_pred,
+                            S_pred, U_means, f);
 }
 
 // ---- rolling-origin forecasts (moment_group.h, MomentFanArgs) -----------------------------------------------------------------------

@@ -585,18 +585,33 @@ class DGPSSM:
         `kernel_pre_cal` once, then `filter_grouped` with the shared U and no q_sqrt.  control_inputs None: the model's own; rows
         [n_train, n_train + len(Y_test)) feed the steps, as in `predict_moments`.  Parameters newer on the device than on the host
         are pulled first."""
+        return DGPSSM._filter_heldout(self, "filter_heldout", "moment", Y_test, control_inputs, x0, S0, smooth, q_mode, Y_train_std)
+
+    def filter_heldout_linearised(self, Y_test, control_inputs=None, *, x0=None, S0=None, smooth=False, q_mode="reference",
+                                  Y_train_std=1.0):
+        """`filter_heldout` with the linearised (extended Kalman) rule in place of moment matching: the same arguments, the same
+        dict, the same two forms, with method="linearised" of prediction.filter_grouped / posterior_filter_grouped -- every chain's
+        transition is linearised at its filtered mean.  Much cheaper per row of the record; first order in the state covariance where
+        moment matching is exact for the Gaussian ("Linearised filtering", has both the speed and the fit).  A
+        method of its own: the parameter list of `filter_heldout` is pinned."""
+        return DGPSSM._filter_heldout(self, "filter_heldout_linearised", "linearised", Y_test, control_inputs, x0, S0, smooth, q_mode,
+                                      Y_train_std)
+
+    def _filter_heldout(self, who, method, Y_test, control_inputs, x0, S0, smooth, q_mode, Y_train_std):
+        """The body of `filter_heldout` and `filter_heldout_linearised` (called through the class, as `_heldout_record`)."""
         from . import conditionals_multi_output as cmo
-        from .prediction import filter_grouped, posterior_filter_grouped
-        Y_test, x0s, S0s, ci = DGPSSM._heldout_record(self, "filter_heldout", Y_test, control_inputs, x0, S0, q_mode)
+        from .prediction import _filter_method, filter_grouped, posterior_filter_grouped
+        _filter_method(who, method)
+        Y_test, x0s, S0s, ci = DGPSSM._heldout_record(self, who, Y_test, control_inputs, x0, S0, q_mode)
         S, lay, lik, n_train = self.num_chains, self.layers[-1], self.likelihood, self.Y.shape[0]
         if self.U_collapse:
             return posterior_filter_grouped(lay.Z, lay.kernel, [self._X_chains[s_] for s_ in range(S)], self.Q, ci, n_train, Y_test,
                                             lik.CC, lik.DD, lik.log_Rchols, x0s=x0s, S0s=S0s, q_mode=q_mode, smooth=smooth,
-                                            Y_train_std=Y_train_std)
+                                            Y_train_std=Y_train_std, method=method)
         Lm = cmo.kernel_pre_cal(lay.Z, lay.kernel)
         starts = [self._X_chains[s_][-1] for s_ in range(S)] if x0s is None else list(x0s)
         return filter_grouped(Lm, lay.Z, lay.kernel, [lay.U] * S, None, starts, ci, n_train, Y_test, self.Q, lik.CC, lik.DD,
-                              lik.log_Rchols, S0s=S0s, q_mode=q_mode, smooth=smooth, Y_train_std=Y_train_std)
+                              lik.log_Rchols, S0s=S0s, q_mode=q_mode, smooth=smooth, Y_train_std=Y_train_std, method=method)
 
     def forecast_heldout(self, Y_test, control_inputs=None, horizon=10, *, stride=1, origins=None, x0=None, S0=None, q_mode="reference",
                          Y_train_std=1.0, return_tracks=False):

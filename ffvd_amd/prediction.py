@@ -618,6 +618,20 @@ def _pack_filter(who, D, Y_obs, CC, DD, log_Rchols):
     return m
 
 
+FILTER_METHODS = ("moment", "linearised")
+
+
+def _filter_method(who, method, forecast=False):
+    """The propagation rule of the filter family, checked in the packing stage (before the library is loaded): "moment" (moment
+    matching, the default) or "linearised" (the extended Kalman rule, `filter_grouped`).  The forecast fan has no linearised rule."""
+    if not isinstance(method, str) or method not in FILTER_METHODS:
+        raise ValueError(f"{who}: method: expected one of {list(FILTER_METHODS)}, got {method!r}")
+    if forecast and method != "moment":
+        raise ValueError(f"{who}: method: the forecast fan is built for \"moment\" only (accepted by the filters: "
+                         f"{list(FILTER_METHODS)}), got {method!r}")
+    return method
+
+
 def _filter_call(m, G, D, steps, smooth):
     """Output arrays and the trailing arguments (CC .. lpd_gauss) of the two filter entry points."""
     J, dp = m["J"], _lib.dptr
@@ -655,7 +669,7 @@ def _filter_dict(m, out, Y_train_std):
 
 
 def filter_grouped(Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_inputs, ctrl_offset, Y_obs, Qs, CC, DD, log_Rchols, *,
-                   S0s=None, q_mode="reference", smooth=False, Y_train_std=1.0):
+                   S0s=None, q_mode="reference", smooth=False, Y_train_std=1.0, method="moment"):
     """Gaussian filtering (and, with `smooth`, RTS smoothing) of an observed sequence through G posteriors in one call
     (`ffvd_op_filter_grouped`): `moment_grouped`'s step with a measurement update after every step -- assumed-density filtering by
     moment matching (Deisenroth et al. 2012).  The state after step i emits row i of Y_obs (steps, J): y = CC^T x + DD + noise of
@@ -668,31 +682,41 @@ def filter_grouped(Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_inp
     unobserved); with smooth: m_smooth, S_smooth (the start state is not smoothed).  Pooled over the groups with EQUAL weights (the
     chains are not re-weighted by their likelihoods), one step ahead, (steps, J): predict_y, predict_y_var_total, lpd_mix,
     lpd_gauss.  Scalars: ll, ll_joint, ll_original_units, RMSE (`_filter_dict`).  Every covariance is exactly symmetric; group g's
-    arrays are bit-identical to a G = 1 call on that group."""
+    arrays are bit-identical to a G = 1 call on that group.
+    method "linearised" (`ffvd_op_filter_linear_grouped`): the extended Kalman rule in place of moment matching -- the transition
+    is linearised at the filtered mean mu: with m, v the mean and variance of the GP conditional at [mu, c_i] and J the Jacobian of
+    m with respect to the state, A = I + J: m_pred = mu + m, S_pred = A S A^T + diag(v + Q), cross = S A^T.  Same update, densities,
+    smoother, pooled arrays and guarantees; much cheaper per step, and first order in S where moment matching is exact for the
+    Gaussian ("Linearised filtering")."""
     who = "filter_grouped"
+    method = _filter_method(who, method)
     steps = _filter_steps(who, Y_obs)
     a = _pack_moment_groups(who, Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_inputs, ctrl_offset, steps, Qs, S0s, q_mode)
     m = _pack_filter(who, a["D"], Y_obs, CC, DD, log_Rchols)
     out, args = _filter_call(m, a["G"], a["D"], steps, smooth)
-    rc = _lib.load().ffvd_op_filter_grouped(*a["args"], *args)
+    lib = _lib.load()
+    rc = (lib.ffvd_op_filter_linear_grouped if method == "linearised" else lib.ffvd_op_filter_grouped)(*a["args"], *args)
     _lib.check(rc, None, who)
     return _filter_dict(m, out, Y_train_std)
 
 
 def posterior_filter_grouped(Zs, kerns, Xs, Qs, control_inputs, ctrl_offset, Y_obs, CC, DD, log_Rchols, *, x0s=None, S0s=None,
-                             q_mode="reference", smooth=False, Y_train_std=1.0, jitter=JITTER, groups_per_pass=0):
+                             q_mode="reference", smooth=False, Y_train_std=1.0, jitter=JITTER, groups_per_pass=0, method="moment"):
     """The collapsed posterior of G groups and the filter of `filter_grouped` in ONE call (`ffvd_op_posterior_filter_grouped`): what
     `conditionals_multi_output.collapse_u_mean_grouped` followed by `filter_grouped` computes, without the posteriors leaving the
     device.  x0s None: the start means are Xs[g][-1] (the record continues the training sequence), else (G, D).  `Zs` / `kerns` /
-    `Xs` / `Qs` / `control_inputs`: as `posterior_moment_grouped`.  Returns the dict of `filter_grouped`."""
+    `Xs` / `Qs` / `control_inputs`: as `posterior_moment_grouped`.  method: as `filter_grouped` ("linearised":
+    `ffvd_op_posterior_filter_linear_grouped`).  Returns the dict of `filter_grouped`."""
     who = "posterior_filter_grouped"
+    method = _filter_method(who, method)
     steps = _filter_steps(who, Y_obs)
     a = _pack_posterior_moment(who, Zs, kerns, Xs, Qs, control_inputs, ctrl_offset, steps, S0s, q_mode, jitter, groups_per_pass)
     m = _pack_filter(who, a["D"], Y_obs, CC, DD, log_Rchols)
     x0 = None if x0s is None else _lib.as_f64(x0s, (a["G"], a["D"]), "x0s")
     out, args = _filter_call(m, a["G"], a["D"], steps, smooth)
     pre = a["args"][:17] + (None if x0 is None else _lib.dptr(x0),) + a["args"][17:]
-    rc = _lib.load().ffvd_op_posterior_filter_grouped(*pre, *args, None)
+    lib = _lib.load()
+    rc = (lib.ffvd_op_posterior_filter_linear_grouped if method == "linearised" else lib.ffvd_op_posterior_filter_grouped)(*pre, *args, None)
     _lib.check(rc, None, who)
     return _filter_dict(m, out, Y_train_std)
 
@@ -776,7 +800,7 @@ def _forecast_dict(m, org, h, fout, out, Y_train_std):
 
 def forecast_grouped(Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_inputs, ctrl_offset, Y_obs, Qs, CC, DD, log_Rchols,
                      horizon, *, origins=None, stride=1, S0s=None, q_mode="reference", Y_train_std=1.0, return_tracks=False,
-                     return_filter=False, tracks_per_pass=0):
+                     return_filter=False, tracks_per_pass=0, method="moment"):
     """Rolling-origin multi-step forecasts of an observed record through G posteriors in ONE call (`ffvd_op_forecast_grouped`): the
     filter of `filter_grouped` (same arguments up to log_Rchols), then from every origin -- a row of the record -- `horizon` steps of
     `moment_grouped` started at the filtered state of that row.  All (group, origin) tracks advance in one launch per forecast
@@ -790,8 +814,10 @@ def forecast_grouped(Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_i
     return_filter: the keys of `filter_grouped` without the smoothed ones, its pooled one-step arrays under filter_predict_y,
     filter_predict_y_var_total, filter_lpd_mix, filter_lpd_gauss.  A track is bit-identical to `moment_grouped` from
     x_lasts = m_filt[:, o], S0s = S_filt[:, o], ctrl_offset + o + 1, and does not depend on the other tracks, the other groups or
-    tracks_per_pass (0: automatic; the number of origins that advance together)."""
+    tracks_per_pass (0: automatic; the number of origins that advance together).  method: "moment" only -- the forecast fan has
+    no linearised rule, `filter_grouped`'s "linearised" raises ValueError here."""
     who = "forecast_grouped"
+    _filter_method(who, method, forecast=True)
     steps = _filter_steps(who, Y_obs)
     a = _pack_moment_groups(who, Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_inputs, ctrl_offset, steps, Qs, S0s, q_mode)
     h, org = _pack_forecast(who, steps, horizon, origins, stride, (a["args"][0], a["M"], a["args"][6], a["D"]))
@@ -804,12 +830,13 @@ def forecast_grouped(Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_i
 
 def posterior_forecast_grouped(Zs, kerns, Xs, Qs, control_inputs, ctrl_offset, Y_obs, CC, DD, log_Rchols, horizon, *, x0s=None,
                                origins=None, stride=1, S0s=None, q_mode="reference", Y_train_std=1.0, return_tracks=False,
-                               return_filter=False, tracks_per_pass=0, jitter=JITTER, groups_per_pass=0):
+                               return_filter=False, tracks_per_pass=0, jitter=JITTER, groups_per_pass=0, method="moment"):
     """The collapsed posterior of G groups and the forecasts of `forecast_grouped` in ONE call
     (`ffvd_op_posterior_forecast_grouped`): what `conditionals_multi_output.collapse_u_mean_grouped` followed by `forecast_grouped`
     computes, without the posteriors leaving the device.  The arguments up to log_Rchols, x0s, jitter and groups_per_pass are
-    `posterior_filter_grouped`'s.  Returns the dict of `forecast_grouped`."""
+    `posterior_filter_grouped`'s; method: as `forecast_grouped`.  Returns the dict of `forecast_grouped`."""
     who = "posterior_forecast_grouped"
+    _filter_method(who, method, forecast=True)
     steps = _filter_steps(who, Y_obs)
     a = _pack_posterior_moment(who, Zs, kerns, Xs, Qs, control_inputs, ctrl_offset, steps, S0s, q_mode, jitter, groups_per_pass)
     h, org = _pack_forecast(who, steps, horizon, origins, stride, (a["args"][0], a["M"], a["args"][5], a["D"]))

@@ -733,6 +733,41 @@ int  ffvd_op_posterior_filter_grouped(int kind, int G, int n_models, const doubl
                                       double *S_smooth, double *y_mean, double *y_var_total, double *lpd_mix, double *lpd_gauss,
                                       double *U_means);
 
+/* Linearised (extended Kalman) filtering and RTS smoothing through the GP: ffvd_op_filter_grouped -- same arguments, same outputs,
+ * same timing convention, same measurement update, densities, smoother and pooled summary -- with the transition linearised at the
+ * filtered mean instead of moment-matched (GP-EKF; Deisenroth et al. 2012 compare the two).  With (mu, S) the filtered state before
+ * step t, x = [mu, c_t], beta_d = W_d u_d and Gamma_d = W_d (I - q q^T) W_d^T of the group, per latent dim d:
+ *   k_j = variance_d exp(-1/2 sum_p (x_p - z_jp)^2 / l_dp^2),   nu_jp = z_jp - x_p,
+ *   m_d = sum_j k_j beta_dj,
+ *   J_dp = (1 / l_dp^2) sum_j k_j beta_dj nu_jp   for the D state columns p < D only,
+ *   v_d = variance_d - sum_i k_i (sum_j Gamma_d,ij k_j),
+ * and with A = I + J:
+ *   predict:  m^-_t = mu + m,  S^-_t = A S A^T + diag(v + Q)  (one expression for (lo, hi), mirrored: exactly symmetric),
+ *             cross_t = S A^T = Cov(x_{t-1}, x_t | y_{0:t-1})  (row: component of x_{t-1}).
+ * From S = 0 the first predicted state is the GP conditional at [x_lasts, c_0]: m^- - x_lasts its mean, diag(S^-) - Q its variance,
+ * off-diagonal entries exact zeros.  Cheaper than moment matching (one exp per inducing point and one quadratic form per (group,
+ * dim) against a D (D + 1) / 2-pair table), and first-order where that is exact for the Gaussian: the mean ignores the curvature
+ * of f under S.  Determinism and limits as ffvd_op_filter_grouped; SE kernel only (FFVD_EINVAL with a message that says so). */
+int  ffvd_op_filter_linear_grouped(int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M, int P,
+                                   int D, const double *logvariances, const double *loglengthscales, const double *fs,
+                                   const double *const *q_sqrts, int q_mode, const double *x_lasts, const double *S0s,
+                                   const double *ctrl, int C, int steps, const double *log_Qs, const double *CC, const double *DD,
+                                   const double *noise_std, int J, const double *Y_obs, double *m_pred, double *S_pred, double *m_filt,
+                                   double *S_filt, double *cross, double *lpd, double *lpd_joint, double *m_smooth, double *S_smooth,
+                                   double *y_mean, double *y_var_total, double *lpd_mix, double *lpd_gauss);
+
+/* ffvd_op_posterior_grouped followed by ffvd_op_filter_linear_grouped WITHOUT the posteriors leaving the device: the arguments of
+ * ffvd_op_posterior_filter_grouped, the rule of ffvd_op_filter_linear_grouped. */
+int  ffvd_op_posterior_filter_linear_grouped(int kind, int G, int n_models, const double *Zs, int M, int P, int D,
+                                             const double *logvariances, const double *loglengthscales, const double *Xs,
+                                             const double *ctrl_fit, int C, int T, const double *log_Qs, double jitter,
+                                             int groups_per_pass, int q_mode, const double *x0s, const double *S0s,
+                                             const double *ctrl_roll, int steps, const double *CC, const double *DD,
+                                             const double *noise_std, int J, const double *Y_obs, double *m_pred, double *S_pred,
+                                             double *m_filt, double *S_filt, double *cross, double *lpd, double *lpd_joint,
+                                             double *m_smooth, double *S_smooth, double *y_mean, double *y_var_total, double *lpd_mix,
+                                             double *lpd_gauss, double *U_means);
+
 /* Rolling-origin multi-step forecasts in one call: ffvd_op_filter_grouped (same arguments, same outputs, each of which may be NULL),
  * then from every origin o = origins[b] (n_origins rows of the record, strictly ascending, 0 <= o <= steps - 1 - horizon) `horizon`
  * steps of ffvd_op_moment_grouped started at the FILTERED state of row o, N(m_filt[g][o], S_filt[g][o]), with the control rows
