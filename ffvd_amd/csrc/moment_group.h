@@ -99,6 +99,28 @@ struct MomentFanArgs {
 int mg_fan_tracks_per_pass(int G, int D, int NS, int B);
 void launch_mg_fan_step(hipStream_t stream, const MomentGroupArgs &a, const MomentFanArgs &f, int t);
 
+// Linearised forecasts (moment_linear_fan.hip; DESIGN.md section 9, "Linearised forecasts"): the fan's tracks and indexing with the
+// extended Kalman rule of moment_linear.hip and no measurement update.  Two launches per step for all tracks of a pass: the state
+// kernel (workgroup (track, dim): finishes step t - 1, writes the kernel row of its dim into K and the D + 1 sums of the mean side)
+// and the product kernel (one 128 x 128 tile of T = K Gamma of a unit on the fp64 MFMA; only sum_j k_nj t_nj per column tile is kept).
+// A unit is (group, dim) with rows = the group's tracks of the pass, or -- one model shared by the groups and no q slices, where
+// Gamma is per dim -- (dim) with rows = all tracks of the pass (`shared`); Gamma of unit u is slot u of MomentGroupArgs::gam either way.
+// MomentGroupArgs as for the moment fan; `part` is not read, `state` is [2][tracks][D + D * D].
+// Limits: a pass holds at most Bp tracks per group with G * Bp * D < 2^31 (grid x) and K plus the partials within
+//   MG_LFAN_SCRATCH_DOUBLES (512 MiB; one track per group is always tried).
+constexpr long long MG_LFAN_SCRATCH_DOUBLES = 1LL << 26;
+struct MomentLinearFanArgs {
+    int shared, units, Tp, nr, ntj;  // nr: live rows per unit of this pass; Tp: rows of a K block (a multiple of 128); ntj = ceil(Mp / 128)
+    double *K;                       // [units][Tp][Mp]: kernel rows, zero beyond M
+    double *vpart;                   // [units][ntj][Tp]: column-tile partials of k^T Gamma k
+    double *msum;                    // [2][tracks][D][D + 1]: sum_j k_j beta_j, sum_j k_j beta_j nu_jp (step parity)
+};
+// the layout (without buffers) of a pass of Bp tracks per group
+MomentLinearFanArgs mg_lfan_layout(int G, int n_models, int D, int Mp, int unit_per_group, int Bp);
+int mg_lfan_tracks_per_pass(int G, int n_models, int D, int Mp, int unit_per_group, int B);
+// launch t of h + 1: the state kernel, then (t < h) the product kernel
+void launch_mg_lfan_step(hipStream_t stream, const MomentGroupArgs &a, const MomentFanArgs &f, const MomentLinearFanArgs &l, int t);
+
 struct MomentSummaryArgs {
     int G, steps, D, J, n_test;
     const double *m, *S;             // [G][steps][D], [G][steps][D][D]

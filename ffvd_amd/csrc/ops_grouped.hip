@@ -1,5 +1,6 @@
 // The grouped operators of the C ABI: rollout summaries, grouped rollouts, grouped collapsed posteriors, grouped conditionals, and
-// moment-matched prediction with filtering and rolling-origin forecasts.  Each staging block (hyper-parameters, a caller's posterior,
+// moment-matched prediction with filtering and rolling-origin forecasts (both under either propagation rule: moment matching or the
+// linearisation at the filtered mean).  Each staging block (hyper-parameters, a caller's posterior,
 // a posterior formed in the call, the emission of a summary) is written once and shared by the entry points.
 #include "op_scratch.h"
 #include "rollout_group.h"
@@ -742,7 +743,8 @@ struct BetaGamma {
 // Operands on the device -> beta, Gamma, the step launches, the summary, the downloads.  flt: the launches are those of the filter
 // (moment_group.h), m_x / S_x are the predicted moments, and `sum` is REPLACED by the pooled one-step summary of the request when that
 // asks for one (the filter callers pass nullptr).  method: the propagation rule of the filter's launches, MG_METHOD_MOMENT (moment
-// matching) or MG_METHOD_LINEAR (the linearisation at the filtered mean, moment_linear.hip; a filter request without a forecast).
+// matching) or MG_METHOD_LINEAR (the linearisation at the filtered mean, moment_linear.hip; with a forecast request the tracks take
+// the same rule: moment_linear_fan.hip, two launches per step and pass).
 // dW: [n_models * D] slots of Mp x Mp (upper triangular, zero padded); dq: nullptr, or [G] (q_mode 0) / [G * D] (q_mode 1) slots of
 // Mp x Mp; hv: variance / len per (model, dim).
 int mg_run(Scratch &sc, const std::string &who, int G, int nm, int M, int P, int D, int C, int steps, const HyperView &hv, const double *dZ,
@@ -751,8 +753,8 @@ int mg_run(Scratch &sc, const std::string &who, int G, int nm, int M, int P, int
            int method = MG_METHOD_MOMENT) {
     const int Mp = round_up(M, NB), NS = (M + MG_SLAB - 1) / MG_SLAB;
     const bool linear = method == MG_METHOD_LINEAR;
-    if (linear && (!flt || fc))
-        return set_error(nullptr, FFVD_EINVAL, who + ": bad argument (the linearised rule is built for the filter only, not for forecasts)");
+    if (linear && !flt)
+        return set_error(nullptr, FFVD_EINVAL, who + ": bad argument (the linearised rule is built for the filter and its forecasts only)");
     const size_t nm_x = (size_t)G * steps * D, nS_x = nm_x * D;
     const SummaryReq fsum = flt ? flt->pooled(steps) : SummaryReq{};
     if (fsum.y_mean || fsum.y_var_total || fsum.lpd || fsum.lpd_gauss) sum = &fsum;
@@ -779,20 +781,32 @@ int mg_run(Scratch &sc, const std::string &who, int G, int nm, int M, int P, int
     }
     // the forecast: stacks, the origin table and the slab sums / states of one pass of tracks (after every request the filter makes)
     const int B = fc ? fc->n_origins : 0, h = fc ? fc->horizon : 0;
-    int Bp = fc ? mg_fan_tracks_per_pass(G, D, NS, B) : 0;
+    const int upg = dq ? 1 : 0;
+    int Bp = !fc ? 0 : linear ? mg_lfan_tracks_per_pass(G, nm, D, Mp, upg, B) : mg_fan_tracks_per_pass(G, D, NS, B);
     if (fc && fc->tracks_per_pass > 0 && fc->tracks_per_pass < Bp) Bp = fc->tracks_per_pass;
     const size_t nm_fc = (size_t)G * B * h * D, nS_fc = nm_fc * D;
     double *dmfc = nullptr, *dSfc = nullptr, *fpart = nullptr, *fstate = nullptr;
     int *dorg = nullptr;
+    MomentLinearFanArgs lf{};                                // (linearised tracks: K, the column-tile partials and the mean sums of a pass)
     if (fc) {
         dmfc = sc.alloc<double>(nm_fc); dSfc = sc.alloc<double>(nS_fc); dorg = sc.alloc<int>(B);
-        fpart = sc.alloc<double>((size_t)2 * G * Bp * mg_fields(D) * NS); fstate = sc.alloc<double>((size_t)2 * G * Bp * (D + D * D));
-        OP_CHECK(dmfc && dSfc && dorg && fpart && fstate, who);
+        fstate = sc.alloc<double>((size_t)2 * G * Bp * (D + D * D));
+        if (linear) {
+            lf = mg_lfan_layout(G, nm, D, Mp, upg, Bp);
+            lf.K = sc.alloc<double>((size_t)lf.units * lf.Tp * Mp); lf.vpart = sc.alloc<double>((size_t)lf.units * lf.ntj * lf.Tp);
+            lf.msum = sc.alloc<double>((size_t)2 * G * Bp * D * (D + 1));
+            OP_CHECK(lf.K && lf.vpart && lf.msum, who);
+            OP_TRY(hipMemsetAsync(lf.K, 0, (size_t)lf.units * lf.Tp * Mp * sizeof(double), sc.stream));      // rows no pass fills stay zeros
+        } else {
+            fpart = sc.alloc<double>((size_t)2 * G * Bp * mg_fields(D) * NS);
+            OP_CHECK(fpart, who);
+        }
+        OP_CHECK(dmfc && dSfc && dorg && fstate, who);
         OP_TRY(hipMemcpyAsync(dorg, fc->origins, (size_t)B * sizeof(int), hipMemcpyHostToDevice, sc.stream));
     }
     if (int rc = bg.launch(sc, G, nm, M, D, Mp, hv.len, dW, dq, q_mode, dU)) return rc;
     MomentGroupArgs a{};
-    a.G = G; a.n_models = nm; a.D = D; a.C = C; a.P = P; a.M = M; a.Mp = Mp; a.NS = NS; a.steps = steps; a.unit_per_group = dq ? 1 : 0;
+    a.G = G; a.n_models = nm; a.D = D; a.C = C; a.P = P; a.M = M; a.Mp = Mp; a.NS = NS; a.steps = steps; a.unit_per_group = upg;
     a.Z = dZ; a.variance = hv.variance; a.len = hv.len; a.beta = bg.beta; a.gam = bg.gam; a.x_last = dxl; a.S0 = dS0; a.log_Q = dlq;
     a.ctrl = dctrl; a.part = part; a.state = state; a.m_x = dm; a.S_x = dS;
     if (!flt)
@@ -813,7 +827,11 @@ int mg_run(Scratch &sc, const std::string &who, int G, int nm, int M, int P, int
         for (int b0 = 0; b0 < B; b0 += Bp) {
             fn.b0 = b0; fn.Bp = B - b0 < Bp ? B - b0 : Bp;
             ta.G = G * fn.Bp;
-            for (int t = 0; t <= h; ++t) launch_mg_fan_step(sc.stream, ta, fn, t);
+            if (linear) {
+                lf.nr = lf.shared ? G * fn.Bp : fn.Bp;
+                for (int t = 0; t <= h; ++t) launch_mg_lfan_step(sc.stream, ta, fn, lf, t);
+            } else
+                for (int t = 0; t <= h; ++t) launch_mg_fan_step(sc.stream, ta, fn, t);
         }
     }
     OP_TRY(hipGetLastError());
@@ -844,6 +862,8 @@ int mg_run(Scratch &sc, const std::string &who, int G, int nm, int M, int P, int
 }
 const char *const mg_se_only = " (moment matching is closed-form for the SE kernel only)";
 const char *const mg_linear_se_only = " (the linearised filter is built for the SE kernel only: its kernel row and Jacobian are SE-ARD's)";
+const char *const mg_linear_fc_se_only =
+    " (the linearised forecasts are built for the SE kernel only: their kernel rows and Jacobians are SE-ARD's)";
 
 // Posteriors given by the caller (also explicit-U models, SG-HMC samples of U: q_sqrts = NULL) through mg_run, scalars and pointers checked
 int mg_given_run(const std::string &who, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M, int P, int D,
@@ -1038,7 +1058,61 @@ extern "C" int ffvd_op_posterior_filter_linear_grouped(int kind, int G, int n_mo
 
 // ---- rolling-origin forecasts (moment_group.h, MomentFanArgs) -----------------------------------------------------------------------
 // ffvd_op_filter_grouped, then from every origin `horizon` steps of the propagation started at the filtered state of that row: one
-// launch per forecast step for all (group, origin) tracks of a pass, and the pooled summary of every (origin, horizon)
+// launch per forecast step for all (group, origin) tracks of a pass, and the pooled summary of every (origin, horizon).  `method`: the
+// rule of the filter AND of the tracks (MG_METHOD_LINEAR: moment_linear.hip, then moment_linear_fan.hip, two launches per step)
+namespace {
+int forecast_given(const std::string &who, int method, int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M, int P,
+                                        int D, const double *logvariances, const double *loglengthscales, const double *fs,
+                                        const double *const *q_sqrts, int q_mode, const double *x_lasts, const double *S0s,
+                                        const double *ctrl, int C, int steps, const double *log_Qs, const double *CC, const double *DD,
+                                        const double *noise_std, int J, const double *Y_obs, double *m_pred, double *S_pred,
+                                        double *m_filt, double *S_filt, double *cross, double *lpd, double *lpd_joint, double *m_smooth,
+                                        double *S_smooth, double *y_mean, double *y_var_total, double *lpd_mix, double *lpd_gauss,
+                                        int horizon, const int *origins, int n_origins, int tracks_per_pass, double *m_fc, double *S_fc,
+                                        double *fc_y_mean, double *fc_y_var_total, double *fc_lpd_mix, double *fc_lpd_gauss) {
+    const std::string bad = who + ": bad argument";
+    const FilterReq f{CC, DD, noise_std, J, Y_obs, m_filt, S_filt, cross, lpd, lpd_joint, m_smooth, S_smooth, y_mean, y_var_total, lpd_mix,
+                      lpd_gauss};
+    const ForecastReq q{horizon, n_origins, tracks_per_pass, origins, m_fc, S_fc, fc_y_mean, fc_y_var_total, fc_lpd_mix, fc_lpd_gauss};
+    if (kind != FFVD_KERNEL_SE) return set_error(nullptr, FFVD_EINVAL, bad + (method == MG_METHOD_LINEAR ? mg_linear_fc_se_only : mg_se_only));
+    if (!mg_scalars_ok(kind, G, n_models, M, P, D, C, steps, q_mode) || !filter_scalars_ok(f) || !forecast_scalars_ok(q, G, steps, D))
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    if (G == 0 || steps == 0) return FFVD_OK;
+    if (!Lm_inverse_seqs || !Zs || !logvariances || !loglengthscales || !fs || !x_lasts || !log_Qs || (C > 0 && !ctrl) ||
+        !filter_arrays_ok(f, steps, m_pred, S_pred, q.any_output()) || !forecast_origins_ok(q, steps))
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    return mg_given_run(who, G, n_models, Lm_inverse_seqs, Zs, M, P, D, logvariances, loglengthscales, fs, q_sqrts, q_mode, x_lasts, S0s, ctrl,
+                        C, steps, log_Qs, m_pred, S_pred, nullptr, &f, &q, method);
+}
+
+int forecast_posterior(const std::string &who, int method, int kind, int G, int n_models, const double *Zs, int M, int P, int D,
+                                                  const double *logvariances, const double *loglengthscales, const double *Xs,
+                                                  const double *ctrl_fit, int C, int T, const double *log_Qs, double jitter,
+                                                  int groups_per_pass, int q_mode, const double *x0s, const double *S0s,
+                                                  const double *ctrl_roll, int steps, const double *CC, const double *DD,
+                                                  const double *noise_std, int J, const double *Y_obs, double *m_pred, double *S_pred,
+                                                  double *m_filt, double *S_filt, double *cross, double *lpd, double *lpd_joint,
+                                                  double *m_smooth, double *S_smooth, double *y_mean, double *y_var_total, double *lpd_mix,
+                                                  double *lpd_gauss, double *U_means, int horizon, const int *origins, int n_origins,
+                                                  int tracks_per_pass, double *m_fc, double *S_fc, double *fc_y_mean,
+                                                  double *fc_y_var_total, double *fc_lpd_mix, double *fc_lpd_gauss) {
+    const std::string bad = who + ": bad argument";
+    const FilterReq f{CC, DD, noise_std, J, Y_obs, m_filt, S_filt, cross, lpd, lpd_joint, m_smooth, S_smooth, y_mean, y_var_total, lpd_mix,
+                      lpd_gauss};
+    const ForecastReq q{horizon, n_origins, tracks_per_pass, origins, m_fc, S_fc, fc_y_mean, fc_y_var_total, fc_lpd_mix, fc_lpd_gauss};
+    if (kind != FFVD_KERNEL_SE) return set_error(nullptr, FFVD_EINVAL, bad + (method == MG_METHOD_LINEAR ? mg_linear_fc_se_only : mg_se_only));
+    if (!pg_scalars_ok(kind, G, n_models, M, P, D, C, T, groups_per_pass, jitter) || !mg_scalars_ok(kind, G, n_models, M, P, D, C, steps, q_mode) ||
+        !filter_scalars_ok(f) || !forecast_scalars_ok(q, G, steps, D))
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    if (G == 0 || steps == 0) return FFVD_OK;
+    if (!Zs || !logvariances || !loglengthscales || !Xs || !log_Qs || (C > 0 && (!ctrl_fit || !ctrl_roll)) ||
+        !filter_arrays_ok(f, steps, m_pred, S_pred, q.any_output()) || !forecast_origins_ok(q, steps))
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    const PgIn in{who, kind, G, n_models, M, P, D, C, T, groups_per_pass, Zs, logvariances, loglengthscales, Xs, ctrl_fit, log_Qs, jitter};
+    return mg_posterior_run(in, q_mode, x0s, S0s, ctrl_roll, steps, m_pred, S_pred, U_means, nullptr, &f, &q, method);
+}
+}  // namespace
+
 extern "C" int ffvd_op_forecast_grouped(int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M, int P,
                                         int D, const double *logvariances, const double *loglengthscales, const double *fs,
                                         const double *const *q_sqrts, int q_mode, const double *x_lasts, const double *S0s,
@@ -1048,19 +1122,10 @@ extern "C" int ffvd_op_forecast_grouped(int kind, int G, int n_models, const dou
                                         double *S_smooth, double *y_mean, double *y_var_total, double *lpd_mix, double *lpd_gauss,
                                         int horizon, const int *origins, int n_origins, int tracks_per_pass, double *m_fc, double *S_fc,
                                         double *fc_y_mean, double *fc_y_var_total, double *fc_lpd_mix, double *fc_lpd_gauss) {
-    const std::string who = "ffvd_op_forecast_grouped", bad = who + ": bad argument";
-    const FilterReq f{CC, DD, noise_std, J, Y_obs, m_filt, S_filt, cross, lpd, lpd_joint, m_smooth, S_smooth, y_mean, y_var_total, lpd_mix,
-                      lpd_gauss};
-    const ForecastReq q{horizon, n_origins, tracks_per_pass, origins, m_fc, S_fc, fc_y_mean, fc_y_var_total, fc_lpd_mix, fc_lpd_gauss};
-    if (kind != FFVD_KERNEL_SE) return set_error(nullptr, FFVD_EINVAL, bad + mg_se_only);
-    if (!mg_scalars_ok(kind, G, n_models, M, P, D, C, steps, q_mode) || !filter_scalars_ok(f) || !forecast_scalars_ok(q, G, steps, D))
-        return set_error(nullptr, FFVD_EINVAL, bad);
-    if (G == 0 || steps == 0) return FFVD_OK;
-    if (!Lm_inverse_seqs || !Zs || !logvariances || !loglengthscales || !fs || !x_lasts || !log_Qs || (C > 0 && !ctrl) ||
-        !filter_arrays_ok(f, steps, m_pred, S_pred, q.any_output()) || !forecast_origins_ok(q, steps))
-        return set_error(nullptr, FFVD_EINVAL, bad);
-    return mg_given_run(who, G, n_models, Lm_inverse_seqs, Zs, M, P, D, logvariances, loglengthscales, fs, q_sqrts, q_mode, x_lasts, S0s, ctrl,
-                        C, steps, log_Qs, m_pred, S_pred, nullptr, &f, &q);
+    return forecast_given("ffvd_op_forecast_grouped", MG_METHOD_MOMENT, kind, G, n_models, Lm_inverse_seqs, Zs, M, P, D, logvariances,
+                          loglengthscales, fs, q_sqrts, q_mode, x_lasts, S0s, ctrl, C, steps, log_Qs, CC, DD, noise_std, J, Y_obs, m_pred,
+                          S_pred, m_filt, S_filt, cross, lpd, lpd_joint, m_smooth, S_smooth, y_mean, y_var_total, lpd_mix, lpd_gauss,
+                          horizon, origins, n_origins, tracks_per_pass, m_fc, S_fc, fc_y_mean, fc_y_var_total, fc_lpd_mix, fc_lpd_gauss);
 }
 
 // The same on the collapsed posteriors of ffvd_op_posterior_grouped (as ffvd_op_posterior_filter_grouped): they never leave the device
@@ -1075,20 +1140,46 @@ extern "C" int ffvd_op_posterior_forecast_grouped(int kind, int G, int n_models,
                                                   double *lpd_gauss, double *U_means, int horizon, const int *origins, int n_origins,
                                                   int tracks_per_pass, double *m_fc, double *S_fc, double *fc_y_mean,
                                                   double *fc_y_var_total, double *fc_lpd_mix, double *fc_lpd_gauss) {
-    const std::string who = "ffvd_op_posterior_forecast_grouped", bad = who + ": bad argument";
-    const FilterReq f{CC, DD, noise_std, J, Y_obs, m_filt, S_filt, cross, lpd, lpd_joint, m_smooth, S_smooth, y_mean, y_var_total, lpd_mix,
-                      lpd_gauss};
-    const ForecastReq q{horizon, n_origins, tracks_per_pass, origins, m_fc, S_fc, fc_y_mean, fc_y_var_total, fc_lpd_mix, fc_lpd_gauss};
-    if (kind != FFVD_KERNEL_SE) return set_error(nullptr, FFVD_EINVAL, bad + mg_se_only);
-    if (!pg_scalars_ok(kind, G, n_models, M, P, D, C, T, groups_per_pass, jitter) || !mg_scalars_ok(kind, G, n_models, M, P, D, C, steps, q_mode) ||
-        !filter_scalars_ok(f) || !forecast_scalars_ok(q, G, steps, D))
-        return set_error(nullptr, FFVD_EINVAL, bad);
-    if (G == 0 || steps == 0) return FFVD_OK;
-    if (!Zs || !logvariances || !loglengthscales || !Xs || !log_Qs || (C > 0 && (!ctrl_fit || !ctrl_roll)) ||
-        !filter_arrays_ok(f, steps, m_pred, S_pred, q.any_output()) || !forecast_origins_ok(q, steps))
-        return set_error(nullptr, FFVD_EINVAL, bad);
-    const PgIn in{who, kind, G, n_models, M, P, D, C, T, groups_per_pass, Zs, logvariances, loglengthscales, Xs, ctrl_fit, log_Qs, jitter};
-    return mg_posterior_run(in, q_mode, x0s, S0s, ctrl_roll, steps, m_pred, S_pred, U_means, nullptr, &f, &q);
+    return forecast_posterior("ffvd_op_posterior_forecast_grouped", MG_METHOD_MOMENT, kind, G, n_models, Zs, M, P, D, logvariances,
+                              loglengthscales, Xs, ctrl_fit, C, T, log_Qs, jitter, groups_per_pass, q_mode, x0s, S0s, ctrl_roll, steps, CC,
+                              DD, noise_std, J, Y_obs, m_pred, S_pred, m_filt, S_filt, cross, lpd, lpd_joint, m_smooth, S_smooth, y_mean,
+                              y_var_total, lpd_mix, lpd_gauss, U_means, horizon, origins, n_origins, tracks_per_pass, m_fc, S_fc, fc_y_mean,
+                              fc_y_var_total, fc_lpd_mix, fc_lpd_gauss);
+}
+
+// The two calls above with the linearised (extended Kalman) rule for the filter and for the tracks (moment_linear_fan.hip)
+extern "C" int ffvd_op_forecast_linear_grouped(int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M, int P,
+                                        int D, const double *logvariances, const double *loglengthscales, const double *fs,
+                                        const double *const *q_sqrts, int q_mode, const double *x_lasts, const double *S0s,
+                                        const double *ctrl, int C, int steps, const double *log_Qs, const double *CC, const double *DD,
+                                        const double *noise_std, int J, const double *Y_obs, double *m_pred, double *S_pred,
+                                        double *m_filt, double *S_filt, double *cross, double *lpd, double *lpd_joint, double *m_smooth,
+                                        double *S_smooth, double *y_mean, double *y_var_total, double *lpd_mix, double *lpd_gauss,
+                                        int horizon, const int *origins, int n_origins, int tracks_per_pass, double *m_fc, double *S_fc,
+                                        double *fc_y_mean, double *fc_y_var_total, double *fc_lpd_mix, double *fc_lpd_gauss) {
+    return forecast_given("ffvd_op_forecast_linear_grouped", MG_METHOD_LINEAR, kind, G, n_models, Lm_inverse_seqs, Zs, M, P, D,
+                          logvariances, loglengthscales, fs, q_sqrts, q_mode, x_lasts, S0s, ctrl, C, steps, log_Qs, CC, DD, noise_std, J,
+                          Y_obs, m_pred, S_pred, m_filt, S_filt, cross, lpd, lpd_joint, m_smooth, S_smooth, y_mean, y_var_total, lpd_mix,
+                          lpd_gauss, horizon, origins, n_origins, tracks_per_pass, m_fc, S_fc, fc_y_mean, fc_y_var_total, fc_lpd_mix,
+                          fc_lpd_gauss);
+}
+
+extern "C" int ffvd_op_posterior_forecast_linear_grouped(int kind, int G, int n_models, const double *Zs, int M, int P, int D,
+                                                  const double *logvariances, const double *loglengthscales, const double *Xs,
+                                                  const double *ctrl_fit, int C, int T, const double *log_Qs, double jitter,
+                                                  int groups_per_pass, int q_mode, const double *x0s, const double *S0s,
+                                                  const double *ctrl_roll, int steps, const double *CC, const double *DD,
+                                                  const double *noise_std, int J, const double *Y_obs, double *m_pred, double *S_pred,
+                                                  double *m_filt, double *S_filt, double *cross, double *lpd, double *lpd_joint,
+                                                  double *m_smooth, double *S_smooth, double *y_mean, double *y_var_total, double *lpd_mix,
+                                                  double *lpd_gauss, double *U_means, int horizon, const int *origins, int n_origins,
+                                                  int tracks_per_pass, double *m_fc, double *S_fc, double *fc_y_mean,
+                                                  double *fc_y_var_total, double *fc_lpd_mix, double *fc_lpd_gauss) {
+    return forecast_posterior("ffvd_op_posterior_forecast_linear_grouped", MG_METHOD_LINEAR, kind, G, n_models, Zs, M, P, D, logvariances,
+                              loglengthscales, Xs, ctrl_fit, C, T, log_Qs, jitter, groups_per_pass, q_mode, x0s, S0s, ctrl_roll, steps, CC,
+                              DD, noise_std, J, Y_obs, m_pred, S_pred, m_filt, S_filt, cross, lpd, lpd_joint, m_smooth, S_smooth, y_mean,
+                              y_var_total, lpd_mix, lpd_gauss, U_means, horizon, origins, n_origins, tracks_per_pass, m_fc, S_fc, fc_y_mean,
+                              fc_y_var_total, fc_lpd_mix, fc_lpd_gauss);
 }
 
 // The summary of the moment-matched prediction for stacks the caller holds: they are uploaded, summarised by the same launch as in the

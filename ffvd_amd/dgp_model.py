@@ -621,18 +621,38 @@ class DGPSSM:
         returned (the horizon curves rmse_h, ll_h, ll_gauss_h, n_h of shape (horizon, Ydim) among it; SquaredExponential kernels
         only; deterministic).  The start, the control rows and the two forms (collapsed U: ONE `posterior_forecast_grouped` call;
         explicit U: `kernel_pre_cal` once, then `forecast_grouped`) are those of `filter_heldout`."""
+        return DGPSSM._forecast_heldout(self, "forecast_heldout", "moment", Y_test, control_inputs, horizon, stride, origins, x0, S0, q_mode,
+                                        Y_train_std, return_tracks)
+
+    def forecast_heldout_linearised(self, Y_test, control_inputs=None, horizon=10, *, stride=1, origins=None, x0=None, S0=None,
+                                    q_mode="reference", Y_train_std=1.0, return_tracks=False):
+        """`forecast_heldout` with the linearised (extended Kalman) rule for the filter and for the tracks: the same arguments, the
+        same dict, the same two forms, through prediction.posterior_forecast_linear_grouped / forecast_linear_grouped -- the filter
+        of `filter_heldout_linearised`, then from each origin `horizon` steps of the same linearisation without a measurement update
+        ("Linearised forecasts", has both the speed and the fit).  A method of its own: the parameter list of
+        `forecast_heldout` is pinned."""
+        return DGPSSM._forecast_heldout(self, "forecast_heldout_linearised", "linearised", Y_test, control_inputs, horizon, stride, origins,
+                                        x0, S0, q_mode, Y_train_std, return_tracks)
+
+    def _forecast_heldout(self, who, method, Y_test, control_inputs, horizon, stride, origins, x0, S0, q_mode, Y_train_std, return_tracks):
+        """The body of `forecast_heldout` and `forecast_heldout_linearised` (called through the class, as `_heldout_record`)."""
         from . import conditionals_multi_output as cmo
-        from .prediction import forecast_grouped, posterior_forecast_grouped
-        Y_test, x0s, S0s, ci = DGPSSM._heldout_record(self, "forecast_heldout", Y_test, control_inputs, x0, S0, q_mode)
+        from . import prediction as pr
+        if method not in pr.FILTER_METHODS:
+            raise ValueError(f"{who}: method: expected one of {list(pr.FILTER_METHODS)}, got {method!r}")
+        linear = method == "linearised"
+        Y_test, x0s, S0s, ci = DGPSSM._heldout_record(self, who, Y_test, control_inputs, x0, S0, q_mode)
         S, lay, lik, n_train = self.num_chains, self.layers[-1], self.likelihood, self.Y.shape[0]
         kw = dict(origins=origins, stride=stride, S0s=S0s, q_mode=q_mode, Y_train_std=Y_train_std, return_tracks=return_tracks)
         if self.U_collapse:
-            return posterior_forecast_grouped(lay.Z, lay.kernel, [self._X_chains[s_] for s_ in range(S)], self.Q, ci, n_train, Y_test,
-                                              lik.CC, lik.DD, lik.log_Rchols, horizon, x0s=x0s, **kw)
+            fused = pr.posterior_forecast_linear_grouped if linear else pr.posterior_forecast_grouped
+            return fused(lay.Z, lay.kernel, [self._X_chains[s_] for s_ in range(S)], self.Q, ci, n_train, Y_test, lik.CC, lik.DD,
+                         lik.log_Rchols, horizon, x0s=x0s, **kw)
         Lm = cmo.kernel_pre_cal(lay.Z, lay.kernel)
         starts = [self._X_chains[s_][-1] for s_ in range(S)] if x0s is None else list(x0s)
-        return forecast_grouped(Lm, lay.Z, lay.kernel, [lay.U] * S, None, starts, ci, n_train, Y_test, self.Q, lik.CC, lik.DD,
-                                lik.log_Rchols, horizon, **kw)
+        explicit = pr.forecast_linear_grouped if linear else pr.forecast_grouped
+        return explicit(Lm, lay.Z, lay.kernel, [lay.U] * S, None, starts, ci, n_train, Y_test, self.Q, lik.CC, lik.DD, lik.log_Rchols,
+                        horizon, **kw)
 
     def predict_transition(self, Xnew, *, q_mode="reference", per_chain=True):
         """The learned transition function at inputs of the caller's choice: mean and variance of the posterior GP increment

@@ -623,7 +623,8 @@ FILTER_METHODS = ("moment", "linearised")
 
 def _filter_method(who, method, forecast=False):
     """The propagation rule of the filter family, checked in the packing stage (before the library is loaded): "moment" (moment
-    matching, the default) or "linearised" (the extended Kalman rule, `filter_grouped`).  The forecast fan has no linearised rule."""
+    matching, the default) or "linearised" (the extended Kalman rule, `filter_grouped`).  The forecast functions that take `method` accept "moment" only; the
+    linearised forecasts are `forecast_linear_grouped` / `posterior_forecast_linear_grouped`."""
     if not isinstance(method, str) or method not in FILTER_METHODS:
         raise ValueError(f"{who}: method: expected one of {list(FILTER_METHODS)}, got {method!r}")
     if forecast and method != "moment":
@@ -798,6 +799,34 @@ def _forecast_dict(m, org, h, fout, out, Y_train_std):
     return res
 
 
+def _forecast_given(who, symbol, Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_inputs, ctrl_offset, Y_obs, Qs, CC, DD,
+                    log_Rchols, horizon, origins, stride, S0s, q_mode, Y_train_std, return_tracks, return_filter, tracks_per_pass):
+    """The body of `forecast_grouped` and `forecast_linear_grouped`: `symbol` is the entry point (the propagation rule)."""
+    steps = _filter_steps(who, Y_obs)
+    a = _pack_moment_groups(who, Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_inputs, ctrl_offset, steps, Qs, S0s, q_mode)
+    h, org = _pack_forecast(who, steps, horizon, origins, stride, (a["args"][0], a["M"], a["args"][6], a["D"]))
+    m = _pack_filter(who, a["D"], Y_obs, CC, DD, log_Rchols)
+    fout, fargs, out, args = _forecast_call(m, a["G"], a["D"], steps, h, org, return_tracks, return_filter, tracks_per_pass)
+    rc = getattr(_lib.load(), symbol)(*a["args"], *fargs, *args)
+    _lib.check(rc, None, who)
+    return _forecast_dict(m, org, h, fout, out, Y_train_std)
+
+
+def _forecast_posterior(who, symbol, Zs, kerns, Xs, Qs, control_inputs, ctrl_offset, Y_obs, CC, DD, log_Rchols, horizon, x0s, origins,
+                        stride, S0s, q_mode, Y_train_std, return_tracks, return_filter, tracks_per_pass, jitter, groups_per_pass):
+    """The body of `posterior_forecast_grouped` and `posterior_forecast_linear_grouped`"""
+    steps = _filter_steps(who, Y_obs)
+    a = _pack_posterior_moment(who, Zs, kerns, Xs, Qs, control_inputs, ctrl_offset, steps, S0s, q_mode, jitter, groups_per_pass)
+    h, org = _pack_forecast(who, steps, horizon, origins, stride, (a["args"][0], a["M"], a["args"][5], a["D"]))
+    m = _pack_filter(who, a["D"], Y_obs, CC, DD, log_Rchols)
+    x0 = None if x0s is None else _lib.as_f64(x0s, (a["G"], a["D"]), "x0s")
+    fout, fargs, out, args = _forecast_call(m, a["G"], a["D"], steps, h, org, return_tracks, return_filter, tracks_per_pass)
+    pre = a["args"][:17] + (None if x0 is None else _lib.dptr(x0),) + a["args"][17:]
+    rc = getattr(_lib.load(), symbol)(*pre, *fargs, None, *args)
+    _lib.check(rc, None, who)
+    return _forecast_dict(m, org, h, fout, out, Y_train_std)
+
+
 def forecast_grouped(Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_inputs, ctrl_offset, Y_obs, Qs, CC, DD, log_Rchols,
                      horizon, *, origins=None, stride=1, S0s=None, q_mode="reference", Y_train_std=1.0, return_tracks=False,
                      return_filter=False, tracks_per_pass=0, method="moment"):
@@ -814,18 +843,14 @@ def forecast_grouped(Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_i
     return_filter: the keys of `filter_grouped` without the smoothed ones, its pooled one-step arrays under filter_predict_y,
     filter_predict_y_var_total, filter_lpd_mix, filter_lpd_gauss.  A track is bit-identical to `moment_grouped` from
     x_lasts = m_filt[:, o], S0s = S_filt[:, o], ctrl_offset + o + 1, and does not depend on the other tracks, the other groups or
-    tracks_per_pass (0: automatic; the number of origins that advance together).  method: "moment" only -- the forecast fan has
-    no linearised rule, `filter_grouped`'s "linearised" raises ValueError here."""
+    tracks_per_pass (0: automatic; the number of origins that advance together).  method: "moment" only -- `filter_grouped`'s
+    "linearised" raises ValueError here: the linearised rule has functions of its own, `forecast_linear_grouped` and
+    `posterior_forecast_linear_grouped`."""
     who = "forecast_grouped"
     _filter_method(who, method, forecast=True)
-    steps = _filter_steps(who, Y_obs)
-    a = _pack_moment_groups(who, Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_inputs, ctrl_offset, steps, Qs, S0s, q_mode)
-    h, org = _pack_forecast(who, steps, horizon, origins, stride, (a["args"][0], a["M"], a["args"][6], a["D"]))
-    m = _pack_filter(who, a["D"], Y_obs, CC, DD, log_Rchols)
-    fout, fargs, out, args = _forecast_call(m, a["G"], a["D"], steps, h, org, return_tracks, return_filter, tracks_per_pass)
-    rc = _lib.load().ffvd_op_forecast_grouped(*a["args"], *fargs, *args)
-    _lib.check(rc, None, who)
-    return _forecast_dict(m, org, h, fout, out, Y_train_std)
+    return _forecast_given(who, "ffvd_op_forecast_grouped", Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_inputs, ctrl_offset,
+                           Y_obs, Qs, CC, DD, log_Rchols, horizon, origins, stride, S0s, q_mode, Y_train_std, return_tracks, return_filter,
+                           tracks_per_pass)
 
 
 def posterior_forecast_grouped(Zs, kerns, Xs, Qs, control_inputs, ctrl_offset, Y_obs, CC, DD, log_Rchols, horizon, *, x0s=None,
@@ -837,16 +862,38 @@ def posterior_forecast_grouped(Zs, kerns, Xs, Qs, control_inputs, ctrl_offset, Y
     `posterior_filter_grouped`'s; method: as `forecast_grouped`.  Returns the dict of `forecast_grouped`."""
     who = "posterior_forecast_grouped"
     _filter_method(who, method, forecast=True)
-    steps = _filter_steps(who, Y_obs)
-    a = _pack_posterior_moment(who, Zs, kerns, Xs, Qs, control_inputs, ctrl_offset, steps, S0s, q_mode, jitter, groups_per_pass)
-    h, org = _pack_forecast(who, steps, horizon, origins, stride, (a["args"][0], a["M"], a["args"][5], a["D"]))
-    m = _pack_filter(who, a["D"], Y_obs, CC, DD, log_Rchols)
-    x0 = None if x0s is None else _lib.as_f64(x0s, (a["G"], a["D"]), "x0s")
-    fout, fargs, out, args = _forecast_call(m, a["G"], a["D"], steps, h, org, return_tracks, return_filter, tracks_per_pass)
-    pre = a["args"][:17] + (None if x0 is None else _lib.dptr(x0),) + a["args"][17:]
-    rc = _lib.load().ffvd_op_posterior_forecast_grouped(*pre, *fargs, None, *args)
-    _lib.check(rc, None, who)
-    return _forecast_dict(m, org, h, fout, out, Y_train_std)
+    return _forecast_posterior(who, "ffvd_op_posterior_forecast_grouped", Zs, kerns, Xs, Qs, control_inputs, ctrl_offset, Y_obs, CC, DD,
+                               log_Rchols, horizon, x0s, origins, stride, S0s, q_mode, Y_train_std, return_tracks, return_filter,
+                               tracks_per_pass, jitter, groups_per_pass)
+
+
+def forecast_linear_grouped(Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_inputs, ctrl_offset, Y_obs, Qs, CC, DD, log_Rchols,
+                            horizon, *, origins=None, stride=1, S0s=None, q_mode="reference", Y_train_std=1.0, return_tracks=False,
+                            return_filter=False, tracks_per_pass=0):
+    """`forecast_grouped` under the linearised (extended Kalman) rule, in ONE call (`ffvd_op_forecast_linear_grouped`): the filter of
+    `filter_grouped(method="linearised")`, then from every origin `horizon` steps of the same linearisation without a measurement
+    update, started at the filtered state (mu, S) of that row: with m, v the mean and variance of the GP conditional at
+    [mu, c_row] and J the Jacobian of m with respect to the state, A = I + J: mu' = mu + m, S' = A S A^T + diag(v + Q).  The
+    parameters (without `method`) and the returned dict are `forecast_grouped`'s; the pooled arrays give the groups EQUAL weights (the
+    chains are not re-weighted by their likelihoods).  The call's filter outputs are `filter_grouped(method="linearised")`'s bit for
+    bit.  A track is what that filter computes over the record cut after its origin and continued by `horizon` all-NaN rows, to
+    rounding and not bit for bit: the quadratic forms k^T Gamma k of all tracks that share a Gamma are one dense product on the fp64
+    matrix cores here and are summed in another order.  A track does not depend on the other tracks, the other groups or
+    tracks_per_pass; every S_fc is exactly symmetric ("Linearised forecasts")."""
+    return _forecast_given("forecast_linear_grouped", "ffvd_op_forecast_linear_grouped", Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s,
+                           control_inputs, ctrl_offset, Y_obs, Qs, CC, DD, log_Rchols, horizon, origins, stride, S0s, q_mode, Y_train_std,
+                           return_tracks, return_filter, tracks_per_pass)
+
+
+def posterior_forecast_linear_grouped(Zs, kerns, Xs, Qs, control_inputs, ctrl_offset, Y_obs, CC, DD, log_Rchols, horizon, *, x0s=None,
+                                      origins=None, stride=1, S0s=None, q_mode="reference", Y_train_std=1.0, return_tracks=False,
+                                      return_filter=False, tracks_per_pass=0, jitter=JITTER, groups_per_pass=0):
+    """The collapsed posterior of G groups and the forecasts of `forecast_linear_grouped` in ONE call
+    (`ffvd_op_posterior_forecast_linear_grouped`): the parameters of `posterior_forecast_grouped` without `method`, the dict of
+    `forecast_grouped`."""
+    return _forecast_posterior("posterior_forecast_linear_grouped", "ffvd_op_posterior_forecast_linear_grouped", Zs, kerns, Xs, Qs,
+                               control_inputs, ctrl_offset, Y_obs, CC, DD, log_Rchols, horizon, x0s, origins, stride, S0s, q_mode, Y_train_std,
+                               return_tracks, return_filter, tracks_per_pass, jitter, groups_per_pass)
 
 
 def pg_sweep(Lm_inverse_seq, Z, kern, U_val, X_ref, Y, control_inputs, CC, DD, Rchols, Q, x0, eps, unif):
