@@ -121,6 +121,27 @@ int mg_lfan_tracks_per_pass(int G, int n_models, int D, int Mp, int unit_per_gro
 // launch t of h + 1: the state kernel, then (t < h) the product kernel
 void launch_mg_lfan_step(hipStream_t stream, const MomentGroupArgs &a, const MomentFanArgs &f, const MomentLinearFanArgs &l, int t);
 
+// the product kernel's launches alone: per unit u < units the column-tile partials of diag(K_u Gamma_u K_u^T), rows < nr
+void launch_mg_lfan_var(hipStream_t stream, const double *K, const double *gam, double *vpart, int Tp, int Mp, int nr, int units);
+
+// Linearised filtering of many records (moment_linear_records.hip; DESIGN.md section 9, "Filtering many records"): R observed records
+// through G posteriors, a TRACK (group g, record r) = one independent linearised filter of moment_linear.hip.  The launch pair, the
+// unit layout, K, the partials and the mean sums are those of the linearised forecasts (MomentLinearFanArgs, the product kernel
+// unchanged); the state kernel adds the filter's stores and mg_update with row t - 1 of the track's own record.  Track v = g * Rp + b
+// of a pass is record r = r0 + b; its rows in every stack are those of the global track g * R + r.
+// In this form MomentGroupArgs::G is the number of tracks of the pass (state and msum are per track of the pass), steps the rows of a
+// record, x_last [G][R][D], S0 [G][R][D][D] or nullptr, ctrl [R][steps][C], m_x / S_x the predicted stacks [G][R][steps]...; `part`
+// is not read.  MomentFilterArgs: Y [R][steps][J], every stack [G][R][steps]...
+// Limits: those of the linearised forecasts with records for origins (mg_lfan_tracks_per_pass);  G * R * steps * D * D < 2^31.
+struct MomentRecordArgs {
+    int R, Rp, r0;                   // records of the call; records per group of this pass; its first record
+};
+// launch t of steps + 1: the state kernel, then (t < steps) the product kernel
+void launch_mg_lrec_step(hipStream_t stream, const MomentGroupArgs &a, const MomentFilterArgs &f, const MomentRecordArgs &rc,
+                         const MomentLinearFanArgs &l, int t);
+// dst[g][r][:] = src[g][:] (n doubles per group): the start of every record of a group where the caller gave one per group
+void launch_mg_lrec_spread(hipStream_t stream, int G, int R, int n, const double *src, double *dst);
+
 struct MomentSummaryArgs {
     int G, steps, D, J, n_test;
     const double *m, *S;             // [G][steps][D], [G][steps][D][D]

@@ -234,10 +234,14 @@ void launch_mg_lfan_step(hipStream_t stream, const MomentGroupArgs &a, const Mom
         default: break;
     }
     if (t >= a.steps) return;
-    const int nti = (l.nr + 127) / 128;
-    for (int u0 = 0; u0 < l.units; u0 += 32768) {
-        const LfanVarArgs va{l.K, a.gam, l.vpart, l.Tp, a.Mp, l.nr, u0};
-        hipLaunchKernelGGL(mg_lfan_var_kernel, dim3((unsigned)(nti * l.ntj), (unsigned)(l.units - u0 < 32768 ? l.units - u0 : 32768)),
+    launch_mg_lfan_var(stream, l.K, a.gam, l.vpart, l.Tp, a.Mp, l.nr, l.units);
+}
+
+void launch_mg_lfan_var(hipStream_t stream, const double *K, const double *gam, double *vpart, int Tp, int Mp, int nr, int units) {
+    const int nti = (nr + 127) / 128, ntj = (Mp + 127) / 128;
+    for (int u0 = 0; u0 < units; u0 += 32768) {
+        const LfanVarArgs va{K, gam, vpart, Tp, Mp, nr, u0};
+        hipLaunchKernelGGL(mg_lfan_var_kernel, dim3((unsigned)(nti * ntj), (unsigned)(units - u0 < 32768 ? units - u0 : 32768)),
                            dim3(512), 0, stream, va);
     }
 }

@@ -1,6 +1,6 @@
 // The grouped operators of the C ABI: rollout summaries, grouped rollouts, grouped collapsed posteriors, grouped conditionals, and
 // moment-matched prediction with filtering and rolling-origin forecasts (both under either propagation rule: moment matching or the
-// linearisation at the filtered mean).  Each staging block (hyper-parameters, a caller's posterior,
+// linearisation at the filtered mean), and the linearised filter over many records in one call.  Each staging block (hyper-parameters, a caller's posterior,
 // a posterior formed in the call, the emission of a summary) is written once and shared by the entry points.
 #include "op_scratch.h"
 #include "rollout_group.h"
@@ -1054,6 +1054,182 @@ extern "C" int ffvd_op_posterior_filter_linear_grouped(int kind, int G, int n_mo
     return filter_posterior("ffvd_op_posterior_filter_linear_grouped", MG_METHOD_LINEAR, kind, G, n_models, Zs, M, P, D, logvariances,
                             loglengthscales, Xs, ctrl_fit, C, T, log_Qs, jitter, groups_per_pass, q_mode, x0s, S0s, ctrl_roll, steps, m_pred,
                             S_pred, U_means, f);
+}
+
+// ---- linearised filtering of many records (moment_group.h, MomentRecordArgs) ---------------------------------------------------------
+// ffvd_op_filter_linear_grouped over R observed records in one call: a track (group, record) is an independent linearised filter on
+// the posterior of its group with the observations, control rows and start state of its record.  beta and Gamma are staged once per
+// call; the tracks of a pass advance in one launch pair per step (moment_linear_records.hip, the product kernel of the linearised
+// forecasts), so Gamma is read once per 128 tracks of a unit and not once per record.
+namespace {
+// The records request beside a FilterReq whose Y_obs is [R][steps][J], whose per-track outputs are [G][R][steps]... and whose pooled
+// four are [R][steps][J]
+struct RecordsReq {
+    int R, records_per_pass;
+};
+// the checks of a records request that need no array: G * R * steps * D * D < 2^31, G * R * D within the state kernel's grid x
+bool records_scalars_ok(const RecordsReq &q, int G, int steps, int D) {
+    if (q.R < 0 || q.records_per_pass < 0) return false;
+    if (G == 0 || q.R == 0 || steps == 0) return true;
+    return (long long)G * q.R <= ((1LL << 31) - 1) / steps / D / D && (long long)G * q.R * D < (1LL << 31);
+}
+const char *const mg_records_se_only =
+    " (the linearised filter of many records is built for the SE kernel only: its kernel rows and Jacobians are SE-ARD's)";
+
+// Operands on the device -> beta, Gamma (BetaGamma, once per call), the passes over the records (steps + 1 launch pairs each), the
+// smoother over all G * R tracks, the pooled summary per record and row, the downloads.  A sibling of mg_run's linear branch.
+// dxl: [G][R][D]; dS0: nullptr or [G][R][D][D]; dctrl: nullptr or [R][steps][C]; the other operands as mg_run's.
+int mg_records_run(Scratch &sc, const std::string &who, int G, int nm, int M, int P, int D, int C, int steps, const HyperView &hv,
+                   const double *dZ, const double *dW, const double *dq, int q_mode, const double *dU, const double *dxl, const double *dS0,
+                   const double *dlq, const double *dctrl, double *m_x, double *S_x, const FilterReq &flt, const RecordsReq &rq) {
+    const int Mp = round_up(M, NB), R = rq.R, J = flt.J, upg = dq ? 1 : 0;
+    const int V = G * R;                                                               // tracks of the call (V * steps * D * D < 2^31)
+    const size_t nm_x = (size_t)V * steps * D, nS_x = nm_x * D, nlpd = (size_t)V * steps * J, nlj = (size_t)V * steps;
+    int Rp = mg_lfan_tracks_per_pass(G, nm, D, Mp, upg, R);
+    if (rq.records_per_pass > 0 && rq.records_per_pass < Rp) Rp = rq.records_per_pass;
+    BetaGamma bg{};
+    const bool terms = bg.alloc(sc, G, nm, D, Mp, dq, q_mode);
+    double *state = sc.alloc<double>((size_t)2 * G * Rp * (D + D * D));
+    double *dm = sc.alloc<double>(nm_x), *dS = sc.alloc<double>(nS_x);
+    OP_CHECK(terms && state && dm && dS, who);
+    const Emission e = stage_emission(sc, D, J, flt.CC, flt.DD, flt.noise_std, flt.Y_obs, (size_t)R * steps);
+    MomentFilterArgs fa{};
+    fa.J = J; fa.CC = e.CC; fa.DD = e.DD; fa.sd = e.sd; fa.Y = e.Y;
+    fa.m_filt = sc.alloc<double>(nm_x); fa.S_filt = sc.alloc<double>(nS_x); fa.cross = sc.alloc<double>(nS_x);
+    fa.lpd = sc.alloc<double>(nlpd); fa.lpd_joint = sc.alloc<double>(nlj);
+    OP_CHECK(e.ok && fa.m_filt && fa.S_filt && fa.cross && fa.lpd && fa.lpd_joint, who);
+    MomentSmoothArgs sa{};
+    const bool smooth = flt.m_smooth || flt.S_smooth;
+    if (smooth) {                                                                      // the stacks are [G][R][steps]...: its [G'][steps]...
+        sa.G = V; sa.D = D; sa.steps = steps; sa.m_pred = dm; sa.S_pred = dS; sa.m_filt = fa.m_filt; sa.S_filt = fa.S_filt;
+        sa.cross = fa.cross; sa.m_smooth = sc.alloc<double>(nm_x); sa.S_smooth = sc.alloc<double>(nS_x);
+        OP_CHECK(sa.m_smooth && sa.S_smooth, who);
+    }
+    MomentLinearFanArgs lf = mg_lfan_layout(G, nm, D, Mp, upg, Rp);
+    lf.K = sc.alloc<double>((size_t)lf.units * lf.Tp * Mp); lf.vpart = sc.alloc<double>((size_t)lf.units * lf.ntj * lf.Tp);
+    lf.msum = sc.alloc<double>((size_t)2 * G * Rp * D * (D + 1));
+    OP_CHECK(lf.K && lf.vpart && lf.msum, who);
+    OP_TRY(hipMemsetAsync(lf.K, 0, (size_t)lf.units * lf.Tp * Mp * sizeof(double), sc.stream));          // rows no pass fills stay zeros
+    if (int rc = bg.launch(sc, G, nm, M, D, Mp, hv.len, dW, dq, q_mode, dU)) return rc;
+    MomentGroupArgs a{};
+    a.n_models = nm; a.D = D; a.C = C; a.P = P; a.M = M; a.Mp = Mp; a.NS = 0; a.steps = steps; a.unit_per_group = upg;
+    a.Z = dZ; a.variance = hv.variance; a.len = hv.len; a.beta = bg.beta; a.gam = bg.gam; a.x_last = dxl; a.S0 = dS0; a.log_Q = dlq;
+    a.ctrl = dctrl; a.part = nullptr; a.state = state; a.m_x = dm; a.S_x = dS;
+    // passes of at most Rp records, steps + 1 launch pairs each; a track's values do not depend on the pass it is in
+    MomentRecordArgs ra{};
+    ra.R = R;
+    for (int r0 = 0; r0 < R; r0 += Rp) {
+        ra.r0 = r0; ra.Rp = R - r0 < Rp ? R - r0 : Rp;
+        a.G = G * ra.Rp;
+        lf.nr = lf.shared ? G * ra.Rp : ra.Rp;
+        for (int t = 0; t <= steps; ++t) launch_mg_lrec_step(sc.stream, a, fa, ra, lf, t);
+    }
+    if (smooth) launch_mg_smooth(sc.stream, sa);
+    OP_TRY(hipGetLastError());
+    // the pooled one-step summary per record and row: the predicted stacks as [G][R * steps] against Y as [R * steps][J]
+    const SummaryReq fsum = flt.pooled(R * steps);
+    if (fsum.y_mean || fsum.y_var_total || fsum.lpd || fsum.lpd_gauss)
+        if (int rc = mg_summary(sc, who, dm, dS, G, R * steps, D, fsum)) return rc;
+    auto down = [&](double *dst, const double *src, size_t n) { return !dst || sc.download(dst, src, n * sizeof(double)); };
+    if (!down(flt.m_filt, fa.m_filt, nm_x) || !down(flt.S_filt, fa.S_filt, nS_x) || !down(flt.cross, fa.cross, nS_x) ||
+        !down(flt.lpd, fa.lpd, nlpd) || !down(flt.lpd_joint, fa.lpd_joint, nlj) || !down(flt.m_smooth, sa.m_smooth, nm_x) ||
+        !down(flt.S_smooth, sa.S_smooth, nS_x) || !down(m_x, dm, nm_x) || !down(S_x, dS, nS_x))
+        return set_error(nullptr, FFVD_EDEVICE, who + ": copying the results back failed");
+    OP_TRY(hipStreamSynchronize(sc.stream));
+    return FFVD_OK;
+}
+
+// the scalar-argument checks the two entry points share (before any device call); nothing: FFVD_OK without touching anything
+int records_checks(const std::string &who, int kind, int G, int n_models, int M, int P, int D, int C, int steps, int q_mode, const FilterReq &f,
+                   const RecordsReq &rq, bool &nothing) {
+    const std::string bad = who + ": bad argument";
+    nothing = false;
+    if (kind != FFVD_KERNEL_SE) return set_error(nullptr, FFVD_EINVAL, bad + mg_records_se_only);
+    if (!mg_scalars_ok(kind, G, n_models, M, P, D, C, steps, q_mode) || !filter_scalars_ok(f)) return set_error(nullptr, FFVD_EINVAL, bad);
+    if (!records_scalars_ok(rq, G, steps, D))
+        return set_error(nullptr, FFVD_EINVAL, bad + " (R >= 0, records_per_pass >= 0, G * R * steps * D * D < 2^31 and G * R * D < 2^31 are needed)");
+    nothing = G == 0 || rq.R == 0 || steps == 0;
+    return FFVD_OK;
+}
+}  // namespace
+
+extern "C" int ffvd_op_filter_records_grouped(int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M,
+                                              int P, int D, const double *logvariances, const double *loglengthscales, const double *fs,
+                                              const double *const *q_sqrts, int q_mode, int R, const double *x_lasts, const double *S0s,
+                                              const double *ctrl, int C, int steps, const double *log_Qs, const double *CC,
+                                              const double *DD, const double *noise_std, int J, const double *Y_obs,
+                                              int records_per_pass, double *m_pred, double *S_pred, double *m_filt, double *S_filt,
+                                              double *cross, double *lpd, double *lpd_joint, double *m_smooth, double *S_smooth,
+                                              double *y_mean, double *y_var_total, double *lpd_mix, double *lpd_gauss) {
+    const std::string who = "ffvd_op_filter_records_grouped", bad = who + ": bad argument";
+    const FilterReq f{CC, DD, noise_std, J, Y_obs, m_filt, S_filt, cross, lpd, lpd_joint, m_smooth, S_smooth, y_mean, y_var_total, lpd_mix,
+                      lpd_gauss};
+    const RecordsReq rq{R, records_per_pass};
+    bool nothing;
+    if (int rc = records_checks(who, kind, G, n_models, M, P, D, C, steps, q_mode, f, rq, nothing)) return rc;
+    if (nothing) return FFVD_OK;
+    if (!Lm_inverse_seqs || !Zs || !logvariances || !loglengthscales || !fs || !x_lasts || !log_Qs || (C > 0 && !ctrl) ||
+        !filter_arrays_ok(f, R * steps, m_pred, S_pred))
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    const size_t nK = (size_t)n_models * D, GD = (size_t)G * D, VD = GD * R, nq = given_nq(q_sqrts, q_mode, G, D);
+    if (!given_tables_ok(Lm_inverse_seqs, nK, q_sqrts, nq)) return set_error(nullptr, FFVD_EINVAL, bad);
+    OP_BEGIN(who);
+    const int Mp = round_up(M, NB);
+    double *dW = upload_matrix_table(sc, Lm_inverse_seqs, nK, M, Mp), *dq = nq ? upload_matrix_table(sc, q_sqrts, nq, M, Mp) : nullptr;
+    GroupHypers gh = stage_group_hypers(sc, FFVD_KERNEL_SE, n_models, D, M, Mp, P, Zs, logvariances, loglengthscales);
+    double *dU = sc.upload(fs, GD * M), *dxl = sc.upload(x_lasts, VD), *dS0 = S0s ? sc.upload(S0s, VD * D) : nullptr, *dlq = sc.upload(log_Qs, GD);
+    double *dctrl = C ? sc.upload(ctrl, (size_t)R * steps * C) : nullptr;
+    OP_CHECK(dW && (!nq || dq) && dU && dxl && (!S0s || dS0) && dlq && (!C || dctrl) && gh.logs(sc) && gh.blocks(sc), who);
+    gh.prep(sc.stream);
+    return mg_records_run(sc, who, G, n_models, M, P, D, C, steps, gh.hv(), gh.dZ, dW, dq, q_mode, dU, dxl, dS0, dlq, dctrl, m_pred, S_pred, f, rq);
+}
+
+// The collapsed posteriors of ffvd_op_posterior_grouped filtered over the records without leaving the device (as
+// ffvd_op_posterior_filter_linear_grouped); x0s NULL: every record of group g starts at the last row of Xs[g]
+extern "C" int ffvd_op_posterior_filter_records_grouped(int kind, int G, int n_models, const double *Zs, int M, int P, int D,
+                                                        const double *logvariances, const double *loglengthscales, const double *Xs,
+                                                        const double *ctrl_fit, int C, int T, const double *log_Qs, double jitter,
+                                                        int groups_per_pass, int q_mode, int R, const double *x0s, const double *S0s,
+                                                        const double *ctrl_roll, int steps, const double *CC, const double *DD,
+                                                        const double *noise_std, int J, const double *Y_obs, int records_per_pass,
+                                                        double *m_pred, double *S_pred, double *m_filt, double *S_filt, double *cross,
+                                                        double *lpd, double *lpd_joint, double *m_smooth, double *S_smooth, double *y_mean,
+                                                        double *y_var_total, double *lpd_mix, double *lpd_gauss, double *U_means) {
+    const std::string who = "ffvd_op_posterior_filter_records_grouped", bad = who + ": bad argument";
+    const FilterReq f{CC, DD, noise_std, J, Y_obs, m_filt, S_filt, cross, lpd, lpd_joint, m_smooth, S_smooth, y_mean, y_var_total, lpd_mix,
+                      lpd_gauss};
+    const RecordsReq rq{R, records_per_pass};
+    bool nothing;
+    if (int rc = records_checks(who, kind, G, n_models, M, P, D, C, steps, q_mode, f, rq, nothing)) return rc;
+    if (!pg_scalars_ok(kind, G, n_models, M, P, D, C, T, groups_per_pass, jitter)) return set_error(nullptr, FFVD_EINVAL, bad);
+    if (nothing) return FFVD_OK;
+    if (!Zs || !logvariances || !loglengthscales || !Xs || !log_Qs || (C > 0 && (!ctrl_fit || !ctrl_roll)) ||
+        !filter_arrays_ok(f, R * steps, m_pred, S_pred))
+        return set_error(nullptr, FFVD_EINVAL, bad);
+    const PgIn in{who, kind, G, n_models, M, P, D, C, T, groups_per_pass, Zs, logvariances, loglengthscales, Xs, ctrl_fit, log_Qs, jitter};
+    OP_BEGIN(who);
+    PgWork w{};
+    const int nm = n_models, Mp = round_up(M, NB), nK = nm * D;
+    const size_t GD = (size_t)G * D, VD = GD * R, mm = (size_t)Mp * Mp;
+    const bool have_q = pg_want_q(sc, w, q_mode, G, D, M);
+    double *dW = sc.alloc<double>((size_t)nK * mm), *dxl = x0s ? sc.upload(x0s, VD) : sc.alloc<double>(VD);
+    double *dx1 = x0s ? nullptr : sc.alloc<double>(GD);
+    OP_CHECK(have_q && dW && dxl && (x0s || dx1), who);
+    if (int rc = pg_posterior(sc, in, w)) return rc;
+    double *dZ = sc.upload(Zs, (size_t)nm * M * P), *dS0 = S0s ? sc.upload(S0s, VD * D) : nullptr;
+    double *dctrl = C ? sc.upload(ctrl_roll, (size_t)R * steps * C) : nullptr;
+    OP_CHECK(dZ && (!S0s || dS0) && (!C || dctrl), who);
+    launch_pg_pack(sc.stream, w.Kuu, 2 * mm, Mp, Mp, nK, 1, M, 1, dW, Mp, Mp, nK);
+    if (!x0s) {
+        launch_pg_x_last(sc.stream, w.Xs, G, T, D, dx1);
+        launch_mg_lrec_spread(sc.stream, G, R, D, dx1, dxl);
+    }
+    if (int rc = mg_records_run(sc, who, G, nm, M, P, D, C, steps, w.hv, dZ, dW, pg_q(w, q_mode), q_mode, w.U, dxl, dS0, w.log_Qs, dctrl, m_pred,
+                                S_pred, f, rq))
+        return rc;
+    if (U_means && !sc.download(U_means, w.U, GD * M * sizeof(double)))
+        return set_error(nullptr, FFVD_EDEVICE, who + ": copying the results back failed");
+    return FFVD_OK;
 }
 
 // ---- rolling-origin forecasts (moment_group.h, MomentFanArgs) -----------------------------------------------------------------------

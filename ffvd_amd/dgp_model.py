@@ -613,6 +613,53 @@ class DGPSSM:
         return filter_grouped(Lm, lay.Z, lay.kernel, [lay.U] * S, None, starts, ci, n_train, Y_test, self.Q, lik.CC, lik.DD,
                               lik.log_Rchols, S0s=S0s, q_mode=q_mode, smooth=smooth, Y_train_std=Y_train_std, method=method)
 
+    def filter_records(self, Y_records, control_records=None, *, lengths=None, x0=None, S0=None, smooth=False, q_mode="reference",
+                       Y_train_std=1.0, records_per_pass=0):
+        """`filter_heldout_linearised` over R held-out records -- trials, segments, cross-validation folds -- in ONE call: every
+        (chain, record) pair is an independent linearised filter with the observations Y_records[r] (Y_records (R, steps, Ydim), NaN =
+        unobserved), the control rows control_records[r] ((R, steps, C); a model with controls needs them: a fresh trial has no
+        natural default) and its own start -- prediction.filter_records_grouped has the method, `lengths` for records of different
+        length, and the dict that is returned (per-record scalars as arrays (R,), ll_all over all records).  x0 None: every record
+        starts at its chain's X_s[-1] with S0 None: zero covariance; else x0 (D,), (R, D) or (S, R, D) and S0 (D, D), (R, D, D) or
+        (S, R, D, D).  Collapsed U: ONE `posterior_filter_records_grouped` call with G = S and the model shared by the groups.
+        Explicit U: `kernel_pre_cal` once, then `filter_records_grouped` with the shared U and no q_sqrt.  Parameters newer on the
+        device than on the host are pulled first.  SquaredExponential kernels only; deterministic."""
+        from . import conditionals_multi_output as cmo
+        from . import prediction as pr
+        who = "filter_records"
+        if q_mode not in cmo.Q_MODES:
+            raise ValueError(f"{who}: q_mode: expected one of {sorted(cmo.Q_MODES)}, got {q_mode!r}")
+        Y = np.asarray(Y_records, dtype=np.float64)
+        if Y.ndim != 3 or Y.shape[0] < 1 or Y.shape[2] != self.Y.shape[1]:
+            raise ValueError(f"{who}: Y_records: expected (R, steps, {self.Y.shape[1]}), got {Y.shape}")
+        if self._host_stale:
+            self.pull_parameters()
+        S, D, R = self.num_chains, self.output_dim, Y.shape[0]
+        lay, lik = self.layers[-1], self.likelihood
+        C = np.shape(lay.Z)[1] - D
+        if C > 0 and control_records is None:
+            raise ValueError(f"{who}: control_records: the model has {C} control columns and a fresh record has no default, expected "
+                             f"({R}, {Y.shape[1]}, {C})")
+
+        def spread(v, tail, name):                                # tail, (R,) + tail or (S, R) + tail -> (S, R) + tail
+            if v is None:
+                return None
+            v = np.asarray(v, dtype=np.float64)
+            if v.shape not in (tail, (R,) + tail, (S, R) + tail):
+                raise ValueError(f"{who}: {name}: expected {tail}, {(R,) + tail} or {(S, R) + tail}, got {v.shape}")
+            return np.broadcast_to(v, (S, R) + tail)
+        x0s, S0s = spread(x0, (D,), "x0"), spread(S0, (D, D), "S0")
+        kw = dict(lengths=lengths, S0s=S0s, q_mode=q_mode, smooth=smooth, Y_train_std=Y_train_std, records_per_pass=records_per_pass)
+        if self.U_collapse:
+            return pr.posterior_filter_records_grouped(lay.Z, lay.kernel, [self._X_chains[s_] for s_ in range(S)], self.Q,
+                                                       self.control_inputs, control_records, Y, lik.CC, lik.DD, lik.log_Rchols,
+                                                       x0s=x0s, **kw)
+        Lm = cmo.kernel_pre_cal(lay.Z, lay.kernel)
+        if x0s is None:
+            x0s = np.broadcast_to(np.stack([self._X_chains[s_][-1] for s_ in range(S)])[:, None, :], (S, R, D))
+        return pr.filter_records_grouped(Lm, lay.Z, lay.kernel, [lay.U] * S, None, x0s, control_records, Y, self.Q, lik.CC, lik.DD,
+                                         lik.log_Rchols, **kw)
+
     def forecast_heldout(self, Y_test, control_inputs=None, horizon=10, *, stride=1, origins=None, x0=None, S0=None, q_mode="reference",
                          Y_train_std=1.0, return_tracks=False):
         """k-step-ahead evaluation of a held-out record for k = 1 .. horizon, with every row of the record as the forecast origin

@@ -653,20 +653,25 @@ def _filter_dict(m, out, Y_train_std):
     """The dict the filter functions return: the arrays of `_filter_call` and the scalars ll (mean of lpd_mix over the observed
     entries), ll_joint (mean over the rows with an observed entry of log mean_g exp(lpd_joint[g, i]), largest exponent subtracted),
     ll_original_units (ll - log Y_train_std) and RMSE (one-step-ahead, observed entries of the first 30 rows, times Y_train_std)."""
-    Y, nan = m["Y"], float("nan")
+    res = dict(out)
+    res.update(_filter_scalars(m["Y"], out["lpd_mix"], out["lpd_joint"], out["predict_y"], Y_train_std))
+    return res
+
+
+def _filter_scalars(Y, lpd_mix, lpd_joint, predict_y, Y_train_std):
+    """The scalars of `_filter_dict` for one record: Y, lpd_mix, predict_y (steps, J), lpd_joint (G, steps)."""
+    nan = float("nan")
     seen = ~np.isnan(Y)
-    ll = float(np.mean(out["lpd_mix"][seen])) if np.any(seen) else nan
+    ll = float(np.mean(lpd_mix[seen])) if np.any(seen) else nan
     rows = np.any(seen, axis=1)
     ll_joint = nan
     if np.any(rows):
-        lj = out["lpd_joint"][:, rows]
+        lj = lpd_joint[:, rows]
         mx = np.max(lj, axis=0)
         ll_joint = float(np.mean(mx + np.log(np.mean(np.exp(lj - mx[None, :]), axis=0))))
     s30 = seen[:30]
-    rmse = float(np.sqrt(np.mean((Y[:30][s30] - out["predict_y"][:30][s30]) ** 2)) * Y_train_std) if np.any(s30) else nan
-    res = dict(out)
-    res.update(ll=ll, ll_joint=ll_joint, ll_original_units=ll - float(np.log(Y_train_std)), RMSE=rmse)
-    return res
+    rmse = float(np.sqrt(np.mean((Y[:30][s30] - predict_y[:30][s30]) ** 2)) * Y_train_std) if np.any(s30) else nan
+    return dict(ll=ll, ll_joint=ll_joint, ll_original_units=ll - float(np.log(Y_train_std)), RMSE=rmse)
 
 
 def filter_grouped(Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_inputs, ctrl_offset, Y_obs, Qs, CC, DD, log_Rchols, *,
@@ -720,6 +725,163 @@ def posterior_filter_grouped(Zs, kerns, Xs, Qs, control_inputs, ctrl_offset, Y_o
     rc = (lib.ffvd_op_posterior_filter_linear_grouped if method == "linearised" else lib.ffvd_op_posterior_filter_grouped)(*pre, *args, None)
     _lib.check(rc, None, who)
     return _filter_dict(m, out, Y_train_std)
+
+
+def _pack_records(who, G, D, C, x0s, control_records, Y_records, lengths, S0s, records_per_pass):
+    """Shape checks and packing of the record arguments of `filter_records_grouped` (before the library is loaded).  Returns a dict:
+    R, steps, J, Y (R, steps, J), ctrl (R, steps, C) or None, x0 (G, R, D) or None (x0s None), S0 (G, R, D, D) or None, lengths (R,),
+    live (R, steps) bool (row < lengths[r]), rpp.  The control rows beyond a record's length are zeros in ctrl."""
+    Y = np.asarray(Y_records, dtype=np.float64)
+    if Y.ndim != 3 or Y.shape[0] < 1 or Y.shape[1] < 1:
+        raise ValueError(f"{who}: Y_records: expected (R, steps, J) with at least one record and one row, got {Y.shape}")
+    R, steps, J = Y.shape
+    Y = np.ascontiguousarray(Y)
+    if np.any(np.isinf(Y)):
+        raise ValueError(f"{who}: Y_records: an infinite observation (NaN marks an unobserved entry)")
+    if isinstance(records_per_pass, bool) or int(records_per_pass) != records_per_pass or int(records_per_pass) < 0:
+        raise ValueError(f"{who}: records_per_pass must be 0 (automatic) or a positive integer, got {records_per_pass!r}")
+    if lengths is None:
+        ln = np.full(R, steps, dtype=np.int64)
+    else:
+        la = np.asarray(lengths)
+        if la.shape != (R,) or not (np.issubdtype(la.dtype, np.integer) or np.array_equal(la, np.floor(la))):
+            raise ValueError(f"{who}: lengths: expected {R} integers (one per record), got {lengths!r}")
+        ln = la.astype(np.int64)
+        if np.any(ln < 1) or np.any(ln > steps):
+            raise ValueError(f"{who}: lengths: every record needs between 1 and {steps} rows, got {ln.tolist()}")
+    live = np.arange(steps)[None, :] < ln[:, None]
+    if not np.all(np.isnan(Y[~live])):
+        raise ValueError(f"{who}: Y_records: the rows of a record at and beyond its length must be all NaN")
+    ctrl = None
+    if C > 0:
+        if control_records is None:
+            raise ValueError(f"{who}: control_records: the model has {C} control columns, expected ({R}, {steps}, {C})")
+        ctrl = np.array(_lib.as_f64(control_records, (R, steps, C), "control_records"))
+        ctrl[~live] = 0.0
+        if not np.all(np.isfinite(ctrl)):
+            raise ValueError(f"{who}: control_records: every control row inside a record's length must be finite")
+    elif control_records is not None and np.size(control_records) != 0:
+        raise ValueError(f"{who}: control_records: the model has no control columns, expected None")
+    x0 = None
+    if x0s is not None:
+        x = np.asarray(x0s, dtype=np.float64)
+        if x.shape == (R, D):
+            x = np.broadcast_to(x, (G, R, D))
+        if x.shape != (G, R, D):
+            raise ValueError(f"{who}: x0s: expected ({R}, {D}) or ({G}, {R}, {D}), got {x.shape}")
+        x0 = np.ascontiguousarray(x)
+    S0 = None
+    if S0s is not None:
+        s = np.asarray(S0s, dtype=np.float64)
+        if s.shape == (R, D, D):
+            s = np.broadcast_to(s, (G, R, D, D))
+        if s.shape != (G, R, D, D):
+            raise ValueError(f"{who}: S0s: expected None, ({R}, {D}, {D}) or ({G}, {R}, {D}, {D}), got {s.shape}")
+        if not np.all(np.isfinite(s)) or not np.array_equal(s, np.swapaxes(s, -1, -2)):
+            raise ValueError(f"{who}: S0s: every start covariance must be finite and exactly symmetric")
+        S0 = np.ascontiguousarray(s)
+    return dict(R=R, steps=steps, J=J, Y=Y, ctrl=ctrl, x0=x0, S0=S0, lengths=ln, live=live, rpp=int(records_per_pass))
+
+
+def _records_placeholders(G, Zs, kerns, steps):
+    """Start means (G, D) and control rows (steps, C) of zeros for `_pack_moment_groups`, whose x_lasts / control_inputs slots the
+    records replace.  A malformed model gives empty ones: `_pack_moment_groups`' own checks raise."""
+    try:
+        one = not isinstance(kerns[0], (list, tuple))
+        D = len(kerns) if one else len(kerns[0])
+        P = np.shape(Zs if one else Zs[0])[1]
+    except (IndexError, TypeError):
+        D, P = 0, 0
+    return np.zeros((G, D)), np.zeros((steps, max(P - D, 0)))
+
+
+def _records_dict(r, G, out, Y_train_std):
+    """The dict `filter_records_grouped` returns, from the arrays of `_filter_call` over R * steps rows: per track (G, R, steps, ...),
+    pooled (R, steps, J), NaN in the rows at and beyond a record's length; per record, as arrays (R,): the scalars of `_filter_dict`;
+    ll_all: the mean of lpd_mix over every observed entry of every record."""
+    R, steps, J, live = r["R"], r["steps"], r["J"], r["live"]
+    res, dead = {}, ~live
+    for k, v in out.items():
+        if k in FORECAST_POOLED:
+            res[k] = v.reshape(R, steps, J)
+            res[k][dead] = np.nan
+        else:
+            res[k] = v.reshape((G, R, steps) + v.shape[2:])
+            res[k][:, dead] = np.nan
+    Y = r["Y"]
+    per = [_filter_scalars(Y[i], res["lpd_mix"][i], res["lpd_joint"][:, i], res["predict_y"][i], Y_train_std) for i in range(R)]
+    for k in ("ll", "ll_joint", "ll_original_units", "RMSE"):
+        res[k] = np.array([p[k] for p in per])
+    seen = ~np.isnan(Y)
+    res["ll_all"] = float(np.mean(res["lpd_mix"][seen])) if np.any(seen) else float("nan")
+    return res
+
+
+def filter_records_grouped(Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_records, Y_records, Qs, CC, DD, log_Rchols, *,
+                           lengths=None, S0s=None, q_mode="reference", smooth=False, Y_train_std=1.0, records_per_pass=0):
+    """Linearised (extended Kalman) filtering and, with `smooth`, RTS smoothing of R observed records -- trials, held-out segments,
+    cross-validation folds -- through G posteriors in ONE call (`ffvd_op_filter_records_grouped`).  A track (group g, record r) is an
+    independent filter of `filter_grouped(method="linearised")`: it runs on the posterior of group g and reads the observations
+    Y_records[r] (Y_records (R, steps, J), NaN = unobserved), the control rows control_records[r] (control_records (R, steps, C),
+    None when the model has no controls) and starts from N(x0s[g, r], S0s[g, r]).  x0s: (R, D), shared by the groups, or (G, R, D);
+    S0s: None (zeros), (R, D, D) or (G, R, D, D).  lengths: None, or (R,) integers in [1, steps] for records of different length:
+    rows >= lengths[r] of record r must be all NaN in Y_records; their control rows are not read (zeros are sent), every returned
+    array is NaN there and they take no part in any scalar.  The other arguments are `filter_grouped`'s; the posteriors are prepared
+    once, the tracks of a pass advance in one launch pair per step (records_per_pass 0: automatic, otherwise at most that many
+    records together), and the quadratic forms of all tracks that share a Gamma are one product on the fp64 matrix cores.
+    Returns a dict.  Per track, (G, R, steps, ...): m_pred, S_pred, m_filt, S_filt, cross, lpd, lpd_joint, with smooth m_smooth,
+    S_smooth (as `filter_grouped`, the leading (G, steps) replaced by (G, R, steps)).  Pooled over the groups with EQUAL weights,
+    (R, steps, J): predict_y, predict_y_var_total, lpd_mix, lpd_gauss.  Per record, arrays (R,): ll, ll_joint, ll_original_units,
+    RMSE (`_filter_dict`'s definitions on that record); ll_all: the mean of lpd_mix over the observed entries of all records.
+    A track's arrays are bit-identical whatever the other groups, the other records, their order and records_per_pass are; every
+    covariance is exactly symmetric; against `filter_grouped(method="linearised")` on the same record the arrays agree to rounding,
+    not bit for bit ("Filtering many records").  SquaredExponential kernels only; moment matching over records
+    is not built."""
+    who = "filter_records_grouped"
+    shape = np.shape(Y_records)
+    if len(shape) != 3 or shape[0] < 1 or shape[1] < 1:
+        raise ValueError(f"{who}: Y_records: expected (R, steps, J) with at least one record and one row, got {shape}")
+    G = len(U_vals)
+    if x0s is None:
+        raise ValueError(f"{who}: x0s: the start means are needed, ({shape[0]}, D) or ({G}, {shape[0]}, D)")
+    # the model arguments through `_pack_moment_groups`, with placeholders in the three slots the records replace (x_lasts, S0s, ctrl)
+    xl, ci = _records_placeholders(G, Zs, kerns, shape[1])
+    a = _pack_moment_groups(who, Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, xl, ci, 0, shape[1], Qs, None, q_mode)
+    D, args = a["D"], a["args"]
+    r = _pack_records(who, G, D, args[16], x0s, control_records, Y_records, lengths, S0s, records_per_pass)
+    R, steps = r["R"], r["steps"]
+    m = _pack_summary(who, D, R * steps, CC, DD, log_Rchols, r["Y"].reshape(R * steps, r["J"]))
+    out, fargs = _filter_call(m, G, D, R * steps, smooth)
+    dp = _lib.dptr
+    opt = lambda x: None if x is None else dp(x)
+    rc = _lib.load().ffvd_op_filter_records_grouped(*args[:13], R, dp(r["x0"]), opt(r["S0"]), opt(r["ctrl"]), *args[16:], *fargs[:5],
+                                                    r["rpp"], *fargs[5:])
+    _lib.check(rc, None, who)
+    return _records_dict(r, G, out, Y_train_std)
+
+
+def posterior_filter_records_grouped(Zs, kerns, Xs, Qs, control_inputs, control_records, Y_records, CC, DD, log_Rchols, *, lengths=None,
+                                     x0s=None, S0s=None, q_mode="reference", smooth=False, Y_train_std=1.0, jitter=JITTER,
+                                     groups_per_pass=0, records_per_pass=0):
+    """The collapsed posterior of G groups and the filter of `filter_records_grouped` in ONE call
+    (`ffvd_op_posterior_filter_records_grouped`): what `conditionals_multi_output.collapse_u_mean_grouped` followed by
+    `filter_records_grouped` computes, without the posteriors leaving the device.  `Zs` / `kerns` / `Xs` / `Qs` / `control_inputs`
+    (the training controls the posteriors are formed with) / jitter / groups_per_pass: as `posterior_filter_grouped`; control_records,
+    Y_records, lengths, S0s, records_per_pass: as `filter_records_grouped`; x0s None: every record of group g starts at Xs[g][-1],
+    else (R, D) or (G, R, D).  Returns the dict of `filter_records_grouped`."""
+    who = "posterior_filter_records_grouped"
+    a = _pack_posterior_moment(who, Zs, kerns, Xs, Qs, control_inputs, 0, 0, None, q_mode, jitter, groups_per_pass)
+    G, D, args = a["G"], a["D"], a["args"]
+    r = _pack_records(who, G, D, args[11], x0s, control_records, Y_records, lengths, S0s, records_per_pass)
+    R, steps = r["R"], r["steps"]
+    m = _pack_summary(who, D, R * steps, CC, DD, log_Rchols, r["Y"].reshape(R * steps, r["J"]))
+    out, fargs = _filter_call(m, G, D, R * steps, smooth)
+    dp = _lib.dptr
+    opt = lambda x: None if x is None else dp(x)
+    rc = _lib.load().ffvd_op_posterior_filter_records_grouped(*args[:17], R, opt(r["x0"]), opt(r["S0"]), opt(r["ctrl"]), steps, *fargs[:5],
+                                                              r["rpp"], *fargs[5:], None)
+    _lib.check(rc, None, who)
+    return _records_dict(r, G, out, Y_train_std)
 
 
 def _pack_forecast(who, n, horizon, origins=None, stride=1, model=None):

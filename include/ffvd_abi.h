@@ -768,6 +768,46 @@ int  ffvd_op_posterior_filter_linear_grouped(int kind, int G, int n_models, cons
                                              double *m_smooth, double *S_smooth, double *y_mean, double *y_var_total, double *lpd_mix,
                                              double *lpd_gauss, double *U_means);
 
+/* Linearised filtering (and RTS smoothing) of R observed records in one call: ffvd_op_filter_linear_grouped -- its rule, measurement
+ * update, densities and smoother -- with a TRACK (group g, record r) as the unit.  Every track is an independent filter: it runs on
+ * the posterior of group g, reads the observations Y_obs[r] (steps x J, NaN = unobserved; a shorter record is padded with all-NaN
+ * rows, which are prediction steps), the control rows ctrl[r] (steps x C) and starts from N(x_lasts[g][r], S0s[g][r]).  The
+ * argument list of ffvd_op_filter_linear_grouped with: R records; x_lasts G x R x D; S0s G x R x D x D or NULL (zeros); ctrl
+ * R x steps x C; Y_obs R x steps x J; records_per_pass (0: automatic; otherwise at most that many records advance together).
+ * beta and Gamma are prepared once per call; the tracks of a pass advance in one launch pair per step, and the quadratic forms of
+ * all tracks that share a Gamma are one dense product on the fp64 matrix cores (the product of ffvd_op_forecast_linear_grouped), so
+ * Gamma is read once per 128 tracks.  A track does not depend on the other groups, the other records, their order or
+ * records_per_pass (bit for bit); against ffvd_op_filter_linear_grouped on the same record it agrees to rounding, not bit for bit
+ * (the quadratic form and the mean sums are added in another order).
+ * Outputs, each may be NULL (at least one is needed): m_pred .. S_smooth as ffvd_op_filter_linear_grouped with G x R x steps in
+ * place of G x steps; the pooled one-step summary over the groups (equal weights) per record and row, each R x steps x J: y_mean,
+ * y_var_total, lpd_mix, lpd_gauss.
+ * Limits: those of ffvd_op_filter_linear_grouped, R >= 0, records_per_pass >= 0, G * R * steps * D * D < 2^31, G * R * D < 2^31;
+ * FFVD_EINVAL beyond them, before any device call; SE kernel only (FFVD_EINVAL with a message that says so).  G = 0, R = 0 or
+ * steps = 0: FFVD_OK, nothing is touched. */
+int  ffvd_op_filter_records_grouped(int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M, int P,
+                                    int D, const double *logvariances, const double *loglengthscales, const double *fs,
+                                    const double *const *q_sqrts, int q_mode, int R, const double *x_lasts, const double *S0s,
+                                    const double *ctrl, int C, int steps, const double *log_Qs, const double *CC, const double *DD,
+                                    const double *noise_std, int J, const double *Y_obs, int records_per_pass, double *m_pred,
+                                    double *S_pred, double *m_filt, double *S_filt, double *cross, double *lpd, double *lpd_joint,
+                                    double *m_smooth, double *S_smooth, double *y_mean, double *y_var_total, double *lpd_mix,
+                                    double *lpd_gauss);
+
+/* ffvd_op_posterior_grouped followed by ffvd_op_filter_records_grouped WITHOUT the posteriors leaving the device: the arguments of
+ * ffvd_op_posterior_filter_linear_grouped with R, x0s G x R x D (NULL: every record of group g starts at Xs[g][T]), S0s
+ * G x R x D x D or NULL, ctrl_roll R x steps x C, Y_obs R x steps x J and records_per_pass; the outputs of
+ * ffvd_op_filter_records_grouped and U_means. */
+int  ffvd_op_posterior_filter_records_grouped(int kind, int G, int n_models, const double *Zs, int M, int P, int D,
+                                              const double *logvariances, const double *loglengthscales, const double *Xs,
+                                              const double *ctrl_fit, int C, int T, const double *log_Qs, double jitter,
+                                              int groups_per_pass, int q_mode, int R, const double *x0s, const double *S0s,
+                                              const double *ctrl_roll, int steps, const double *CC, const double *DD,
+                                              const double *noise_std, int J, const double *Y_obs, int records_per_pass, double *m_pred,
+                                              double *S_pred, double *m_filt, double *S_filt, double *cross, double *lpd,
+                                              double *lpd_joint, double *m_smooth, double *S_smooth, double *y_mean,
+                                              double *y_var_total, double *lpd_mix, double *lpd_gauss, double *U_means);
+
 /* Rolling-origin multi-step forecasts in one call: ffvd_op_filter_grouped (same arguments, same outputs, each of which may be NULL),
  * then from every origin o = origins[b] (n_origins rows of the record, strictly ascending, 0 <= o <= steps - 1 - horizon) `horizon`
  * steps of ffvd_op_moment_grouped started at the FILTERED state of row o, N(m_filt[g][o], S_filt[g][o]), with the control rows
