@@ -163,6 +163,12 @@ _SIGNATURES = {
     "ffvd_op_posterior_filter_records_grouped": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp,
                                                            C.c_int, C.c_int, _dp, C.c_double, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp,
                                                            C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_int] + [_dp] * 14),
+    "ffvd_op_filter_cubature_records_grouped": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), _dp, C.c_int, C.c_int, C.c_int, _dp,
+                                                          _dp, _dp, C.POINTER(C.c_void_p), C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, C.c_int,
+                                                          _dp, _dp, _dp, _dp, C.c_int, _dp, C.c_int] + [_dp] * 13),
+    "ffvd_op_posterior_filter_cubature_records_grouped": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp,
+                                                                    _dp, C.c_int, C.c_int, _dp, C.c_double, C.c_int, C.c_int, C.c_int, _dp,
+                                                                    _dp, _dp, C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_int] + [_dp] * 14),
     "ffvd_op_forecast_grouped": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp,
                                            C.POINTER(C.c_void_p), C.c_int, _dp, _dp, _dp, C.c_int, C.c_int, _dp,
                                            _dp, _dp, _dp, C.c_int, _dp] + [_dp] * 13 +

@@ -142,6 +142,19 @@ void launch_mg_lrec_step(hipStream_t stream, const MomentGroupArgs &a, const Mom
 // dst[g][r][:] = src[g][:] (n doubles per group): the start of every record of a group where the caller gave one per group
 void launch_mg_lrec_spread(hipStream_t stream, int G, int R, int n, const double *src, double *dst);
 
+// Cubature filtering of many records (moment_cubature_records.hip; DESIGN.md section 9, "Cubature filtering"): the tracks, passes,
+// stacks and update of the linearised records filter with the third-degree spherical cubature rule as the propagation.  A track brings
+// 2D points per step, mu +- sqrt(D) (column i of the Cholesky factor of S) with the control columns not spread, hence 2D kernel rows per
+// (track, dim): rows 2D * (track row) + i of the unit's K block.  MomentLinearFanArgs is mg_lfan_layout with Bp = 2D * (records per
+// group of the pass); msum is [2][tracks][D][2D] (the mean at every point) and `off` [2][tracks][D][D] (the offsets of a step, kept
+// for the finish of that step; step parity).  The product kernel runs unchanged.
+// Limits: those of the linearised records with 2D rows per track (mg_crec_records_per_pass).
+constexpr int mg_crec_rows(int D) { return 2 * D; }
+int mg_crec_records_per_pass(int G, int n_models, int D, int Mp, int unit_per_group, int R);
+// launch t of steps + 1: the state kernel, then (t < steps) the product kernel
+void launch_mg_crec_step(hipStream_t stream, const MomentGroupArgs &a, const MomentFilterArgs &f, const MomentRecordArgs &rc,
+                         const MomentLinearFanArgs &l, double *off, int t);
+
 struct MomentSummaryArgs {
     int G, steps, D, J, n_test;
     const double *m, *S;             // [G][steps][D], [G][steps][D][D]

@@ -622,7 +622,7 @@ bool mg_scalars_ok(int kind, int G, int n_models, int M, int P, int D, int C, in
            (steps == 0 || G <= ((1LL << 31) - 1) / steps / D / D);
 }
 // the propagation rule of the filter's launches (mg_run)
-enum { MG_METHOD_MOMENT = 0, MG_METHOD_LINEAR = 1 };
+enum { MG_METHOD_MOMENT = 0, MG_METHOD_LINEAR = 1, MG_METHOD_CUBATURE = 2 };    // (cubature: the records calls only)
 // the trailing summary block of the entry points: asked for when anything in it is given
 bool mg_summary_wanted(const SummaryReq &q) {
     return q.CC || q.DD || q.noise_std || q.J != 0 || q.Y_test || q.n_test != 0 || q.y_mean || q.y_var || q.y_var_total || q.lpd || q.lpd_gauss;
@@ -1075,17 +1075,23 @@ bool records_scalars_ok(const RecordsReq &q, int G, int steps, int D) {
 }
 const char *const mg_records_se_only =
     " (the linearised filter of many records is built for the SE kernel only: its kernel rows and Jacobians are SE-ARD's)";
+const char *const mg_crecords_se_only =
+    " (the cubature filter of many records is built for the SE kernel only: its kernel rows are SE-ARD's)";
 
 // Operands on the device -> beta, Gamma (BetaGamma, once per call), the passes over the records (steps + 1 launch pairs each), the
 // smoother over all G * R tracks, the pooled summary per record and row, the downloads.  A sibling of mg_run's linear branch.
 // dxl: [G][R][D]; dS0: nullptr or [G][R][D][D]; dctrl: nullptr or [R][steps][C]; the other operands as mg_run's.
-int mg_records_run(Scratch &sc, const std::string &who, int G, int nm, int M, int P, int D, int C, int steps, const HyperView &hv,
+// method: MG_METHOD_LINEAR (moment_linear_records.hip) or MG_METHOD_CUBATURE (moment_cubature_records.hip: 2D rows of K per track,
+// 2D mean sums per (track, dim) and the offsets of a step beside the state; everything else is shared).
+int mg_records_run(Scratch &sc, const std::string &who, int method, int G, int nm, int M, int P, int D, int C, int steps, const HyperView &hv,
                    const double *dZ, const double *dW, const double *dq, int q_mode, const double *dU, const double *dxl, const double *dS0,
                    const double *dlq, const double *dctrl, double *m_x, double *S_x, const FilterReq &flt, const RecordsReq &rq) {
     const int Mp = round_up(M, NB), R = rq.R, J = flt.J, upg = dq ? 1 : 0;
     const int V = G * R;                                                               // tracks of the call (V * steps * D * D < 2^31)
     const size_t nm_x = (size_t)V * steps * D, nS_x = nm_x * D, nlpd = (size_t)V * steps * J, nlj = (size_t)V * steps;
-    int Rp = mg_lfan_tracks_per_pass(G, nm, D, Mp, upg, R);
+    const bool cub = method == MG_METHOD_CUBATURE;
+    const int nrow = cub ? mg_crec_rows(D) : 1;                                        // rows of K per track
+    int Rp = cub ? mg_crec_records_per_pass(G, nm, D, Mp, upg, R) : mg_lfan_tracks_per_pass(G, nm, D, Mp, upg, R);
     if (rq.records_per_pass > 0 && rq.records_per_pass < Rp) Rp = rq.records_per_pass;
     BetaGamma bg{};
     const bool terms = bg.alloc(sc, G, nm, D, Mp, dq, q_mode);
@@ -1105,10 +1111,11 @@ int mg_records_run(Scratch &sc, const std::string &who, int G, int nm, int M, in
         sa.cross = fa.cross; sa.m_smooth = sc.alloc<double>(nm_x); sa.S_smooth = sc.alloc<double>(nS_x);
         OP_CHECK(sa.m_smooth && sa.S_smooth, who);
     }
-    MomentLinearFanArgs lf = mg_lfan_layout(G, nm, D, Mp, upg, Rp);
+    MomentLinearFanArgs lf = mg_lfan_layout(G, nm, D, Mp, upg, Rp * nrow);
     lf.K = sc.alloc<double>((size_t)lf.units * lf.Tp * Mp); lf.vpart = sc.alloc<double>((size_t)lf.units * lf.ntj * lf.Tp);
-    lf.msum = sc.alloc<double>((size_t)2 * G * Rp * D * (D + 1));
-    OP_CHECK(lf.K && lf.vpart && lf.msum, who);
+    lf.msum = sc.alloc<double>((size_t)2 * G * Rp * D * (cub ? nrow : D + 1));
+    double *coff = cub ? sc.alloc<double>((size_t)2 * G * Rp * D * D) : nullptr;
+    OP_CHECK(lf.K && lf.vpart && lf.msum && (!cub || coff), who);
     OP_TRY(hipMemsetAsync(lf.K, 0, (size_t)lf.units * lf.Tp * Mp * sizeof(double), sc.stream));          // rows no pass fills stay zeros
     if (int rc = bg.launch(sc, G, nm, M, D, Mp, hv.len, dW, dq, q_mode, dU)) return rc;
     MomentGroupArgs a{};
@@ -1121,8 +1128,11 @@ int mg_records_run(Scratch &sc, const std::string &who, int G, int nm, int M, in
     for (int r0 = 0; r0 < R; r0 += Rp) {
         ra.r0 = r0; ra.Rp = R - r0 < Rp ? R - r0 : Rp;
         a.G = G * ra.Rp;
-        lf.nr = lf.shared ? G * ra.Rp : ra.Rp;
-        for (int t = 0; t <= steps; ++t) launch_mg_lrec_step(sc.stream, a, fa, ra, lf, t);
+        lf.nr = (lf.shared ? G * ra.Rp : ra.Rp) * nrow;
+        for (int t = 0; t <= steps; ++t) {
+            if (cub) launch_mg_crec_step(sc.stream, a, fa, ra, lf, coff, t);
+            else launch_mg_lrec_step(sc.stream, a, fa, ra, lf, t);
+        }
     }
     if (smooth) launch_mg_smooth(sc.stream, sa);
     OP_TRY(hipGetLastError());
@@ -1140,33 +1150,34 @@ int mg_records_run(Scratch &sc, const std::string &who, int G, int nm, int M, in
 }
 
 // the scalar-argument checks the two entry points share (before any device call); nothing: FFVD_OK without touching anything
-int records_checks(const std::string &who, int kind, int G, int n_models, int M, int P, int D, int C, int steps, int q_mode, const FilterReq &f,
+int records_checks(const std::string &who, int method, int kind, int G, int n_models, int M, int P, int D, int C, int steps, int q_mode, const FilterReq &f,
                    const RecordsReq &rq, bool &nothing) {
     const std::string bad = who + ": bad argument";
     nothing = false;
-    if (kind != FFVD_KERNEL_SE) return set_error(nullptr, FFVD_EINVAL, bad + mg_records_se_only);
+    if (kind != FFVD_KERNEL_SE)
+        return set_error(nullptr, FFVD_EINVAL, bad + (method == MG_METHOD_CUBATURE ? mg_crecords_se_only : mg_records_se_only));
     if (!mg_scalars_ok(kind, G, n_models, M, P, D, C, steps, q_mode) || !filter_scalars_ok(f)) return set_error(nullptr, FFVD_EINVAL, bad);
     if (!records_scalars_ok(rq, G, steps, D))
         return set_error(nullptr, FFVD_EINVAL, bad + " (R >= 0, records_per_pass >= 0, G * R * steps * D * D < 2^31 and G * R * D < 2^31 are needed)");
     nothing = G == 0 || rq.R == 0 || steps == 0;
     return FFVD_OK;
 }
-}  // namespace
 
-extern "C" int ffvd_op_filter_records_grouped(int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M,
-                                              int P, int D, const double *logvariances, const double *loglengthscales, const double *fs,
-                                              const double *const *q_sqrts, int q_mode, int R, const double *x_lasts, const double *S0s,
-                                              const double *ctrl, int C, int steps, const double *log_Qs, const double *CC,
-                                              const double *DD, const double *noise_std, int J, const double *Y_obs,
-                                              int records_per_pass, double *m_pred, double *S_pred, double *m_filt, double *S_filt,
-                                              double *cross, double *lpd, double *lpd_joint, double *m_smooth, double *S_smooth,
-                                              double *y_mean, double *y_var_total, double *lpd_mix, double *lpd_gauss) {
-    const std::string who = "ffvd_op_filter_records_grouped", bad = who + ": bad argument";
+// the body of ffvd_op_filter_records_grouped (MG_METHOD_LINEAR) and ffvd_op_filter_cubature_records_grouped (MG_METHOD_CUBATURE)
+int records_given(const std::string &who, int method, int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M,
+                  int P, int D, const double *logvariances, const double *loglengthscales, const double *fs,
+                  const double *const *q_sqrts, int q_mode, int R, const double *x_lasts, const double *S0s,
+                  const double *ctrl, int C, int steps, const double *log_Qs, const double *CC,
+                  const double *DD, const double *noise_std, int J, const double *Y_obs,
+                  int records_per_pass, double *m_pred, double *S_pred, double *m_filt, double *S_filt,
+                  double *cross, double *lpd, double *lpd_joint, double *m_smooth, double *S_smooth,
+                  double *y_mean, double *y_var_total, double *lpd_mix, double *lpd_gauss) {
+    const std::string bad = who + ": bad argument";
     const FilterReq f{CC, DD, noise_std, J, Y_obs, m_filt, S_filt, cross, lpd, lpd_joint, m_smooth, S_smooth, y_mean, y_var_total, lpd_mix,
                       lpd_gauss};
     const RecordsReq rq{R, records_per_pass};
     bool nothing;
-    if (int rc = records_checks(who, kind, G, n_models, M, P, D, C, steps, q_mode, f, rq, nothing)) return rc;
+    if (int rc = records_checks(who, method, kind, G, n_models, M, P, D, C, steps, q_mode, f, rq, nothing)) return rc;
     if (nothing) return FFVD_OK;
     if (!Lm_inverse_seqs || !Zs || !logvariances || !loglengthscales || !fs || !x_lasts || !log_Qs || (C > 0 && !ctrl) ||
         !filter_arrays_ok(f, R * steps, m_pred, S_pred))
@@ -1181,26 +1192,26 @@ extern "C" int ffvd_op_filter_records_grouped(int kind, int G, int n_models, con
     double *dctrl = C ? sc.upload(ctrl, (size_t)R * steps * C) : nullptr;
     OP_CHECK(dW && (!nq || dq) && dU && dxl && (!S0s || dS0) && dlq && (!C || dctrl) && gh.logs(sc) && gh.blocks(sc), who);
     gh.prep(sc.stream);
-    return mg_records_run(sc, who, G, n_models, M, P, D, C, steps, gh.hv(), gh.dZ, dW, dq, q_mode, dU, dxl, dS0, dlq, dctrl, m_pred, S_pred, f, rq);
+    return mg_records_run(sc, who, method, G, n_models, M, P, D, C, steps, gh.hv(), gh.dZ, dW, dq, q_mode, dU, dxl, dS0, dlq, dctrl, m_pred, S_pred, f,
+                          rq);
 }
 
-// The collapsed posteriors of ffvd_op_posterior_grouped filtered over the records without leaving the device (as
-// ffvd_op_posterior_filter_linear_grouped); x0s NULL: every record of group g starts at the last row of Xs[g]
-extern "C" int ffvd_op_posterior_filter_records_grouped(int kind, int G, int n_models, const double *Zs, int M, int P, int D,
-                                                        const double *logvariances, const double *loglengthscales, const double *Xs,
-                                                        const double *ctrl_fit, int C, int T, const double *log_Qs, double jitter,
-                                                        int groups_per_pass, int q_mode, int R, const double *x0s, const double *S0s,
-                                                        const double *ctrl_roll, int steps, const double *CC, const double *DD,
-                                                        const double *noise_std, int J, const double *Y_obs, int records_per_pass,
-                                                        double *m_pred, double *S_pred, double *m_filt, double *S_filt, double *cross,
-                                                        double *lpd, double *lpd_joint, double *m_smooth, double *S_smooth, double *y_mean,
-                                                        double *y_var_total, double *lpd_mix, double *lpd_gauss, double *U_means) {
-    const std::string who = "ffvd_op_posterior_filter_records_grouped", bad = who + ": bad argument";
+// the body of ffvd_op_posterior_filter_records_grouped and ffvd_op_posterior_filter_cubature_records_grouped
+int records_posterior(const std::string &who, int method, int kind, int G, int n_models, const double *Zs, int M, int P, int D,
+                      const double *logvariances, const double *loglengthscales, const double *Xs,
+                      const double *ctrl_fit, int C, int T, const double *log_Qs, double jitter,
+                      int groups_per_pass, int q_mode, int R, const double *x0s, const double *S0s,
+                      const double *ctrl_roll, int steps, const double *CC, const double *DD,
+                      const double *noise_std, int J, const double *Y_obs, int records_per_pass,
+                      double *m_pred, double *S_pred, double *m_filt, double *S_filt, double *cross,
+                      double *lpd, double *lpd_joint, double *m_smooth, double *S_smooth, double *y_mean,
+                      double *y_var_total, double *lpd_mix, double *lpd_gauss, double *U_means) {
+    const std::string bad = who + ": bad argument";
     const FilterReq f{CC, DD, noise_std, J, Y_obs, m_filt, S_filt, cross, lpd, lpd_joint, m_smooth, S_smooth, y_mean, y_var_total, lpd_mix,
                       lpd_gauss};
     const RecordsReq rq{R, records_per_pass};
     bool nothing;
-    if (int rc = records_checks(who, kind, G, n_models, M, P, D, C, steps, q_mode, f, rq, nothing)) return rc;
+    if (int rc = records_checks(who, method, kind, G, n_models, M, P, D, C, steps, q_mode, f, rq, nothing)) return rc;
     if (!pg_scalars_ok(kind, G, n_models, M, P, D, C, T, groups_per_pass, jitter)) return set_error(nullptr, FFVD_EINVAL, bad);
     if (nothing) return FFVD_OK;
     if (!Zs || !logvariances || !loglengthscales || !Xs || !log_Qs || (C > 0 && (!ctrl_fit || !ctrl_roll)) ||
@@ -1224,13 +1235,60 @@ extern "C" int ffvd_op_posterior_filter_records_grouped(int kind, int G, int n_m
         launch_pg_x_last(sc.stream, w.Xs, G, T, D, dx1);
         launch_mg_lrec_spread(sc.stream, G, R, D, dx1, dxl);
     }
-    if (int rc = mg_records_run(sc, who, G, nm, M, P, D, C, steps, w.hv, dZ, dW, pg_q(w, q_mode), q_mode, w.U, dxl, dS0, w.log_Qs, dctrl, m_pred,
-                                S_pred, f, rq))
+    if (int rc = mg_records_run(sc, who, method, G, nm, M, P, D, C, steps, w.hv, dZ, dW, pg_q(w, q_mode), q_mode, w.U, dxl, dS0, w.log_Qs, dctrl,
+                                m_pred, S_pred, f, rq))
         return rc;
     if (U_means && !sc.download(U_means, w.U, GD * M * sizeof(double)))
         return set_error(nullptr, FFVD_EDEVICE, who + ": copying the results back failed");
     return FFVD_OK;
 }
+}  // namespace
+
+#define FFVD_RECORDS_GIVEN_PARAMS                                                                                                            \
+    int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M, int P, int D, const double *logvariances, \
+        const double *loglengthscales, const double *fs, const double *const *q_sqrts, int q_mode, int R, const double *x_lasts,            \
+        const double *S0s, const double *ctrl, int C, int steps, const double *log_Qs, const double *CC, const double *DD,                  \
+        const double *noise_std, int J, const double *Y_obs, int records_per_pass, double *m_pred, double *S_pred, double *m_filt,          \
+        double *S_filt, double *cross, double *lpd, double *lpd_joint, double *m_smooth, double *S_smooth, double *y_mean,                  \
+        double *y_var_total, double *lpd_mix, double *lpd_gauss
+#define FFVD_RECORDS_GIVEN_ARGS                                                                                                              \
+    kind, G, n_models, Lm_inverse_seqs, Zs, M, P, D, logvariances, loglengthscales, fs, q_sqrts, q_mode, R, x_lasts, S0s, ctrl, C, steps,   \
+        log_Qs, CC, DD, noise_std, J, Y_obs, records_per_pass, m_pred, S_pred, m_filt, S_filt, cross, lpd, lpd_joint, m_smooth, S_smooth,   \
+        y_mean, y_var_total, lpd_mix, lpd_gauss
+#define FFVD_RECORDS_POSTERIOR_PARAMS                                                                                                        \
+    int kind, int G, int n_models, const double *Zs, int M, int P, int D, const double *logvariances, const double *loglengthscales,        \
+        const double *Xs, const double *ctrl_fit, int C, int T, const double *log_Qs, double jitter, int groups_per_pass, int q_mode,       \
+        int R, const double *x0s, const double *S0s, const double *ctrl_roll, int steps, const double *CC, const double *DD,                \
+        const double *noise_std, int J, const double *Y_obs, int records_per_pass, double *m_pred, double *S_pred, double *m_filt,          \
+        double *S_filt, double *cross, double *lpd, double *lpd_joint, double *m_smooth, double *S_smooth, double *y_mean,                  \
+        double *y_var_total, double *lpd_mix, double *lpd_gauss, double *U_means
+#define FFVD_RECORDS_POSTERIOR_ARGS                                                                                                          \
+    kind, G, n_models, Zs, M, P, D, logvariances, loglengthscales, Xs, ctrl_fit, C, T, log_Qs, jitter, groups_per_pass, q_mode, R, x0s,     \
+        S0s, ctrl_roll, steps, CC, DD, noise_std, J, Y_obs, records_per_pass, m_pred, S_pred, m_filt, S_filt, cross, lpd, lpd_joint,        \
+        m_smooth, S_smooth, y_mean, y_var_total, lpd_mix, lpd_gauss, U_means
+
+extern "C" int ffvd_op_filter_records_grouped(FFVD_RECORDS_GIVEN_PARAMS) {
+    return records_given("ffvd_op_filter_records_grouped", MG_METHOD_LINEAR, FFVD_RECORDS_GIVEN_ARGS);
+}
+
+// The collapsed posteriors of ffvd_op_posterior_grouped filtered over the records without leaving the device (as
+// ffvd_op_posterior_filter_linear_grouped); x0s NULL: every record of group g starts at the last row of Xs[g]
+extern "C" int ffvd_op_posterior_filter_records_grouped(FFVD_RECORDS_POSTERIOR_PARAMS) {
+    return records_posterior("ffvd_op_posterior_filter_records_grouped", MG_METHOD_LINEAR, FFVD_RECORDS_POSTERIOR_ARGS);
+}
+
+// The same two calls with the third-degree spherical cubature rule as the propagation (moment_cubature_records.hip)
+extern "C" int ffvd_op_filter_cubature_records_grouped(FFVD_RECORDS_GIVEN_PARAMS) {
+    return records_given("ffvd_op_filter_cubature_records_grouped", MG_METHOD_CUBATURE, FFVD_RECORDS_GIVEN_ARGS);
+}
+
+extern "C" int ffvd_op_posterior_filter_cubature_records_grouped(FFVD_RECORDS_POSTERIOR_PARAMS) {
+    return records_posterior("ffvd_op_posterior_filter_cubature_records_grouped", MG_METHOD_CUBATURE, FFVD_RECORDS_POSTERIOR_ARGS);
+}
+#undef FFVD_RECORDS_GIVEN_PARAMS
+#undef FFVD_RECORDS_GIVEN_ARGS
+#undef FFVD_RECORDS_POSTERIOR_PARAMS
+#undef FFVD_RECORDS_POSTERIOR_ARGS
 
 // ---- rolling-origin forecasts (moment_group.h, MomentFanArgs) -----------------------------------------------------------------------
 // ffvd_op_filter_grouped, then from every origin `horizon` steps of the propagation started at the filtered state of that row: one

@@ -624,9 +624,25 @@ class DGPSSM:
         (S, R, D, D).  Collapsed U: ONE `posterior_filter_records_grouped` call with G = S and the model shared by the groups.
         Explicit U: `kernel_pre_cal` once, then `filter_records_grouped` with the shared U and no q_sqrt.  Parameters newer on the
         device than on the host are pulled first.  SquaredExponential kernels only; deterministic."""
+        return DGPSSM._filter_records(self, "filter_records", "filter_records_grouped", Y_records, control_records, lengths, x0, S0, smooth,
+                                      q_mode, Y_train_std, records_per_pass)
+
+    def filter_records_cubature(self, Y_records, control_records=None, *, lengths=None, x0=None, S0=None, smooth=False, q_mode="reference",
+                                Y_train_std=1.0, records_per_pass=0):
+        """`filter_records` with the third-degree spherical cubature rule in place of the linearisation: 2D sigma points per step, a
+        one-step difference from moment matching that is second order in the state covariance where the linearised rule's is first
+        order -- the call for a caller who needs the latent states themselves (smoothing, control) over many records, or over one:
+        R = 1 is a valid single-record call.  prediction.filter_cubature_records_grouped has the method.  Parameters, checks, the two
+        forms (collapsed U: ONE `posterior_filter_cubature_records_grouped` call; explicit U: `kernel_pre_cal` once, then
+        `filter_cubature_records_grouped`) and the dict that is returned are those of `filter_records`."""
+        return DGPSSM._filter_records(self, "filter_records_cubature", "filter_cubature_records_grouped", Y_records, control_records, lengths,
+                                      x0, S0, smooth, q_mode, Y_train_std, records_per_pass)
+
+    def _filter_records(self, who, fn, Y_records, control_records, lengths, x0, S0, smooth, q_mode, Y_train_std, records_per_pass):
+        """The body of `filter_records` and `filter_records_cubature` (called through the class, as `_filter_heldout`): `fn` names the
+        prediction-level function of the explicit form, "posterior_" + fn the fused one."""
         from . import conditionals_multi_output as cmo
         from . import prediction as pr
-        who = "filter_records"
         if q_mode not in cmo.Q_MODES:
             raise ValueError(f"{who}: q_mode: expected one of {sorted(cmo.Q_MODES)}, got {q_mode!r}")
         Y = np.asarray(Y_records, dtype=np.float64)
@@ -651,14 +667,12 @@ class DGPSSM:
         x0s, S0s = spread(x0, (D,), "x0"), spread(S0, (D, D), "S0")
         kw = dict(lengths=lengths, S0s=S0s, q_mode=q_mode, smooth=smooth, Y_train_std=Y_train_std, records_per_pass=records_per_pass)
         if self.U_collapse:
-            return pr.posterior_filter_records_grouped(lay.Z, lay.kernel, [self._X_chains[s_] for s_ in range(S)], self.Q,
-                                                       self.control_inputs, control_records, Y, lik.CC, lik.DD, lik.log_Rchols,
-                                                       x0s=x0s, **kw)
+            return getattr(pr, "posterior_" + fn)(lay.Z, lay.kernel, [self._X_chains[s_] for s_ in range(S)], self.Q, self.control_inputs,
+                                                  control_records, Y, lik.CC, lik.DD, lik.log_Rchols, x0s=x0s, **kw)
         Lm = cmo.kernel_pre_cal(lay.Z, lay.kernel)
         if x0s is None:
             x0s = np.broadcast_to(np.stack([self._X_chains[s_][-1] for s_ in range(S)])[:, None, :], (S, R, D))
-        return pr.filter_records_grouped(Lm, lay.Z, lay.kernel, [lay.U] * S, None, x0s, control_records, Y, self.Q, lik.CC, lik.DD,
-                                         lik.log_Rchols, **kw)
+        return getattr(pr, fn)(Lm, lay.Z, lay.kernel, [lay.U] * S, None, x0s, control_records, Y, self.Q, lik.CC, lik.DD, lik.log_Rchols, **kw)
 
     def forecast_heldout(self, Y_test, control_inputs=None, horizon=10, *, stride=1, origins=None, x0=None, S0=None, q_mode="reference",
                          Y_train_std=1.0, return_tracks=False):

@@ -837,7 +837,13 @@ def filter_records_grouped(Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, con
     covariance is exactly symmetric; against `filter_grouped(method="linearised")` on the same record the arrays agree to rounding,
     not bit for bit ("Filtering many records").  SquaredExponential kernels only; moment matching over records
     is not built."""
-    who = "filter_records_grouped"
+    return _filter_records_given("filter_records_grouped", "ffvd_op_filter_records_grouped", Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s,
+                                 control_records, Y_records, Qs, CC, DD, log_Rchols, lengths, S0s, q_mode, smooth, Y_train_std, records_per_pass)
+
+
+def _filter_records_given(who, entry, Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_records, Y_records, Qs, CC, DD, log_Rchols,
+                          lengths, S0s, q_mode, smooth, Y_train_std, records_per_pass):
+    """The body of `filter_records_grouped` and `filter_cubature_records_grouped`: `entry` is the symbol of the library."""
     shape = np.shape(Y_records)
     if len(shape) != 3 or shape[0] < 1 or shape[1] < 1:
         raise ValueError(f"{who}: Y_records: expected (R, steps, J) with at least one record and one row, got {shape}")
@@ -854,8 +860,7 @@ def filter_records_grouped(Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, con
     out, fargs = _filter_call(m, G, D, R * steps, smooth)
     dp = _lib.dptr
     opt = lambda x: None if x is None else dp(x)
-    rc = _lib.load().ffvd_op_filter_records_grouped(*args[:13], R, dp(r["x0"]), opt(r["S0"]), opt(r["ctrl"]), *args[16:], *fargs[:5],
-                                                    r["rpp"], *fargs[5:])
+    rc = getattr(_lib.load(), entry)(*args[:13], R, dp(r["x0"]), opt(r["S0"]), opt(r["ctrl"]), *args[16:], *fargs[:5], r["rpp"], *fargs[5:])
     _lib.check(rc, None, who)
     return _records_dict(r, G, out, Y_train_std)
 
@@ -869,7 +874,14 @@ def posterior_filter_records_grouped(Zs, kerns, Xs, Qs, control_inputs, control_
     (the training controls the posteriors are formed with) / jitter / groups_per_pass: as `posterior_filter_grouped`; control_records,
     Y_records, lengths, S0s, records_per_pass: as `filter_records_grouped`; x0s None: every record of group g starts at Xs[g][-1],
     else (R, D) or (G, R, D).  Returns the dict of `filter_records_grouped`."""
-    who = "posterior_filter_records_grouped"
+    return _filter_records_posterior("posterior_filter_records_grouped", "ffvd_op_posterior_filter_records_grouped", Zs, kerns, Xs, Qs,
+                                     control_inputs, control_records, Y_records, CC, DD, log_Rchols, lengths, x0s, S0s, q_mode, smooth, Y_train_std,
+                                     jitter, groups_per_pass, records_per_pass)
+
+
+def _filter_records_posterior(who, entry, Zs, kerns, Xs, Qs, control_inputs, control_records, Y_records, CC, DD, log_Rchols, lengths, x0s, S0s,
+                              q_mode, smooth, Y_train_std, jitter, groups_per_pass, records_per_pass):
+    """The body of `posterior_filter_records_grouped` and `posterior_filter_cubature_records_grouped`: `entry` is the symbol of the library."""
     a = _pack_posterior_moment(who, Zs, kerns, Xs, Qs, control_inputs, 0, 0, None, q_mode, jitter, groups_per_pass)
     G, D, args = a["G"], a["D"], a["args"]
     r = _pack_records(who, G, D, args[11], x0s, control_records, Y_records, lengths, S0s, records_per_pass)
@@ -878,10 +890,42 @@ def posterior_filter_records_grouped(Zs, kerns, Xs, Qs, control_inputs, control_
     out, fargs = _filter_call(m, G, D, R * steps, smooth)
     dp = _lib.dptr
     opt = lambda x: None if x is None else dp(x)
-    rc = _lib.load().ffvd_op_posterior_filter_records_grouped(*args[:17], R, opt(r["x0"]), opt(r["S0"]), opt(r["ctrl"]), steps, *fargs[:5],
-                                                              r["rpp"], *fargs[5:], None)
+    rc = getattr(_lib.load(), entry)(*args[:17], R, opt(r["x0"]), opt(r["S0"]), opt(r["ctrl"]), steps, *fargs[:5], r["rpp"], *fargs[5:], None)
     _lib.check(rc, None, who)
     return _records_dict(r, G, out, Y_train_std)
+
+
+def filter_cubature_records_grouped(Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_records, Y_records, Qs, CC, DD, log_Rchols, *,
+                                    lengths=None, S0s=None, q_mode="reference", smooth=False, Y_train_std=1.0, records_per_pass=0):
+    """Cubature (sigma-point) filtering and, with `smooth`, RTS smoothing of R observed records through G posteriors in ONE call
+    (`ffvd_op_filter_cubature_records_grouped`): `filter_records_grouped` -- its tracks, timing, emission, measurement update,
+    densities, smoother, pooled arrays, per-record scalars, parameters, checks, defaults and returned dict -- with the third-degree
+    spherical cubature rule (Arasaratnam & Haykin 2009) as the propagation.  Per step, with (mu, S) the filtered state, c the
+    record's control row and w = 1 / (2D): L is the lower Cholesky factor of S without pivoting (a pivot <= 0 gives a zero column, so
+    S = 0 and a rank-deficient S are allowed); the 2D points are x_i = [mu + dx_i, c] with dx_i = +sqrt(D) (column i of L) and
+    dx_{i+D} = -dx_i (the control columns are not spread); with m(x_i), v(x_i) the mean and variance of the GP conditional there,
+    mbar = w sum_i m(x_i), Cov(f) = w sum_i (m(x_i) - mbar)(m(x_i) - mbar)^T + diag(w sum_i v(x_i)), V = w sum_i dx_i (m(x_i) - mbar)^T:
+    m_pred = mu + mbar, S_pred = S + Cov(f) + V + V^T + diag(Q), cross = S + V.  Its one-step difference from moment matching is
+    second order in S where the linearised rule's is first order, so its latent states follow moment matching's far more closely,
+    at 2D kernel rows per (track, dim) in the same product on the fp64 matrix cores ("Cubature filtering").
+    The guarantees of `filter_records_grouped` hold: pooled with EQUAL weights; a track's arrays are bit-identical whatever the other
+    groups, the other records, their order and records_per_pass are; every covariance is exactly symmetric.  From S = 0 a step is the
+    conditional at [mu, c] and its `cross` is exact zeros.  SquaredExponential kernels only; R = 1 is a valid single-record call."""
+    return _filter_records_given("filter_cubature_records_grouped", "ffvd_op_filter_cubature_records_grouped", Lm_inverse_seqs, Zs, kerns, U_vals,
+                                 q_sqrts, x0s, control_records, Y_records, Qs, CC, DD, log_Rchols, lengths, S0s, q_mode, smooth, Y_train_std,
+                                 records_per_pass)
+
+
+def posterior_filter_cubature_records_grouped(Zs, kerns, Xs, Qs, control_inputs, control_records, Y_records, CC, DD, log_Rchols, *, lengths=None,
+                                              x0s=None, S0s=None, q_mode="reference", smooth=False, Y_train_std=1.0, jitter=JITTER,
+                                              groups_per_pass=0, records_per_pass=0):
+    """The collapsed posterior of G groups and the filter of `filter_cubature_records_grouped` in ONE call
+    (`ffvd_op_posterior_filter_cubature_records_grouped`): what `conditionals_multi_output.collapse_u_mean_grouped` followed by
+    `filter_cubature_records_grouped` computes, without the posteriors leaving the device.  The arguments are
+    `posterior_filter_records_grouped`'s; returns the dict of `filter_records_grouped`."""
+    return _filter_records_posterior("posterior_filter_cubature_records_grouped", "ffvd_op_posterior_filter_cubature_records_grouped", Zs, kerns,
+                                     Xs, Qs, control_inputs, control_records, Y_records, CC, DD, log_Rchols, lengths, x0s, S0s, q_mode, smooth,
+                                     Y_train_std, jitter, groups_per_pass, records_per_pass)
 
 
 def _pack_forecast(who, n, horizon, origins=None, stride=1, model=None):

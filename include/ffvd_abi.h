@@ -808,6 +808,42 @@ int  ffvd_op_posterior_filter_records_grouped(int kind, int G, int n_models, con
                                               double *lpd_joint, double *m_smooth, double *S_smooth, double *y_mean,
                                               double *y_var_total, double *lpd_mix, double *lpd_gauss, double *U_means);
 
+/* Cubature (sigma-point) filtering of R observed records in one call: ffvd_op_filter_records_grouped -- its tracks, timing, emission,
+ * measurement update, densities, smoother, pooled summary, passes and argument list -- with the third-degree spherical cubature rule
+ * (Arasaratnam & Haykin 2009) as the propagation in place of the extended Kalman rule.  Per step, with (mu, S) the filtered state,
+ * c the record's control row and w = 1 / (2D): L the lower Cholesky factor of S without pivoting (a pivot <= 0 gives a zero column:
+ * S = 0 and a rank-deficient S are allowed); offsets dx_i = +sqrt(D) (column i of L), dx_{i+D} = -dx_i; points x_i = [mu + dx_i, c]
+ * (the control columns are not spread); m(x_i), v(x_i) the mean and variance of the GP conditional there;
+ *   mbar = w sum_i m(x_i),  Cov(f) = w sum_i (m(x_i) - mbar)(m(x_i) - mbar)^T + diag(w sum_i v(x_i)),  V = w sum_i dx_i (m(x_i) - mbar)^T,
+ *   m_pred = mu + mbar,  S_pred = S + Cov(f) + V + V^T + diag(Q),  cross = S + V.
+ * Its difference from moment matching is second order in S where the extended Kalman rule's is first order.  The 2D kernel rows of
+ * every (track, dim) are rows of the same dense product on the fp64 matrix cores, so Gamma is still read once per 128 rows.  Every
+ * covariance is exactly symmetric; from S = 0 the step is the conditional at [mu, c] and cross is exact zeros; a track does not depend
+ * on the other groups, the other records, their order or records_per_pass (bit for bit).
+ * Arguments, outputs and limits: those of ffvd_op_filter_records_grouped (x_lasts G x R x D, G * R * steps * D * D < 2^31); SE kernel
+ * only (FFVD_EINVAL with a message that says so).  G = 0, R = 0 or steps = 0: FFVD_OK, nothing is touched. */
+int  ffvd_op_filter_cubature_records_grouped(int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M,
+                                             int P, int D, const double *logvariances, const double *loglengthscales, const double *fs,
+                                             const double *const *q_sqrts, int q_mode, int R, const double *x_lasts, const double *S0s,
+                                             const double *ctrl, int C, int steps, const double *log_Qs, const double *CC,
+                                             const double *DD, const double *noise_std, int J, const double *Y_obs,
+                                             int records_per_pass, double *m_pred, double *S_pred, double *m_filt, double *S_filt,
+                                             double *cross, double *lpd, double *lpd_joint, double *m_smooth, double *S_smooth,
+                                             double *y_mean, double *y_var_total, double *lpd_mix, double *lpd_gauss);
+
+/* ffvd_op_posterior_grouped followed by ffvd_op_filter_cubature_records_grouped WITHOUT the posteriors leaving the device: the
+ * arguments and outputs of ffvd_op_posterior_filter_records_grouped. */
+int  ffvd_op_posterior_filter_cubature_records_grouped(int kind, int G, int n_models, const double *Zs, int M, int P, int D,
+                                                       const double *logvariances, const double *loglengthscales, const double *Xs,
+                                                       const double *ctrl_fit, int C, int T, const double *log_Qs, double jitter,
+                                                       int groups_per_pass, int q_mode, int R, const double *x0s, const double *S0s,
+                                                       const double *ctrl_roll, int steps, const double *CC, const double *DD,
+                                                       const double *noise_std, int J, const double *Y_obs, int records_per_pass,
+                                                       double *m_pred, double *S_pred, double *m_filt, double *S_filt, double *cross,
+                                                       double *lpd, double *lpd_joint, double *m_smooth, double *S_smooth,
+                                                       double *y_mean, double *y_var_total, double *lpd_mix, double *lpd_gauss,
+                                                       double *U_means);
+
 /* Rolling-origin multi-step forecasts in one call: ffvd_op_filter_grouped (same arguments, same outputs, each of which may be NULL),
  * then from every origin o = origins[b] (n_origins rows of the record, strictly ascending, 0 <= o <= steps - 1 - horizon) `horizon`
  * steps of ffvd_op_moment_grouped started at the FILTERED state of row o, N(m_filt[g][o], S_filt[g][o]), with the control rows
