@@ -185,6 +185,14 @@ _SIGNATURES = {
                                                             C.c_int, C.c_int, _dp, C.c_double, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int,
                                                             _dp, _dp, _dp, C.c_int, _dp] + [_dp] * 14 +
                                                            [C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int] + [_dp] * 6),
+    "ffvd_op_forecast_cubature_grouped": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), _dp, C.c_int, C.c_int, C.c_int, _dp, _dp,
+                                                    _dp, C.POINTER(C.c_void_p), C.c_int, _dp, _dp, _dp, C.c_int, C.c_int, _dp,
+                                                    _dp, _dp, _dp, C.c_int, _dp] + [_dp] * 13 +
+                                                   [C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int] + [_dp] * 6),
+    "ffvd_op_posterior_forecast_cubature_grouped": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp,
+                                                              C.c_int, C.c_int, _dp, C.c_double, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int,
+                                                              _dp, _dp, _dp, C.c_int, _dp] + [_dp] * 14 +
+                                                             [C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int] + [_dp] * 6),
     "ffvd_op_moment_summary": (C.c_int, [_dp, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_int,
                                          _dp, _dp, _dp, _dp, _dp]),
     "ffvd_op_pg_sweep": (C.c_int, [C.c_int, _dp, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, _dp, C.c_int,

@@ -155,6 +155,15 @@ int mg_crec_records_per_pass(int G, int n_models, int D, int Mp, int unit_per_gr
 void launch_mg_crec_step(hipStream_t stream, const MomentGroupArgs &a, const MomentFilterArgs &f, const MomentRecordArgs &rc,
                          const MomentLinearFanArgs &l, double *off, int t);
 
+// Cubature forecasts (moment_cubature_fan.hip; DESIGN.md section 9, "Cubature forecasts"): the fan's tracks and indexing (MomentFanArgs)
+// with the cubature rule above and no measurement update.  MomentGroupArgs as for the linearised forecasts; MomentLinearFanArgs is
+// mg_lfan_layout with Bp = 2D * (tracks per group of the pass), msum [2][tracks][D][2D], `off` [2][tracks][D][D].  The product kernel
+// runs unchanged.
+// Limits: those of the cubature records with origins for records (mg_crec_records_per_pass);  G * B * h * D * D < 2^31.
+// launch t of h + 1: the state kernel, then (t < h) the product kernel
+void launch_mg_cfan_step(hipStream_t stream, const MomentGroupArgs &a, const MomentFanArgs &f, const MomentLinearFanArgs &l, double *off,
+                         int t);
+
 struct MomentSummaryArgs {
     int G, steps, D, J, n_test;
     const double *m, *S;             // [G][steps][D], [G][steps][D][D]

@@ -622,7 +622,7 @@ bool mg_scalars_ok(int kind, int G, int n_models, int M, int P, int D, int C, in
            (steps == 0 || G <= ((1LL << 31) - 1) / steps / D / D);
 }
 // the propagation rule of the filter's launches (mg_run)
-enum { MG_METHOD_MOMENT = 0, MG_METHOD_LINEAR = 1, MG_METHOD_CUBATURE = 2 };    // (cubature: the records calls only)
+enum { MG_METHOD_MOMENT = 0, MG_METHOD_LINEAR = 1, MG_METHOD_CUBATURE = 2 };    // (cubature: the records calls and the forecasts)
 // the trailing summary block of the entry points: asked for when anything in it is given
 bool mg_summary_wanted(const SummaryReq &q) {
     return q.CC || q.DD || q.noise_std || q.J != 0 || q.Y_test || q.n_test != 0 || q.y_mean || q.y_var || q.y_var_total || q.lpd || q.lpd_gauss;
@@ -744,7 +744,9 @@ struct BetaGamma {
 // (moment_group.h), m_x / S_x are the predicted moments, and `sum` is REPLACED by the pooled one-step summary of the request when that
 // asks for one (the filter callers pass nullptr).  method: the propagation rule of the filter's launches, MG_METHOD_MOMENT (moment
 // matching) or MG_METHOD_LINEAR (the linearisation at the filtered mean, moment_linear.hip; with a forecast request the tracks take
-// the same rule: moment_linear_fan.hip, two launches per step and pass).
+// the same rule: moment_linear_fan.hip, two launches per step and pass) or, with a forecast request only, MG_METHOD_CUBATURE (the
+// filter is the cubature records launch with one record, moment_cubature_records.hip: [G][1][steps] stacks are [G][steps] stacks;
+// the tracks are moment_cubature_fan.hip's; K, the partials, the mean sums and the offsets are sized for the larger stage, the tracks').
 // dW: [n_models * D] slots of Mp x Mp (upper triangular, zero padded); dq: nullptr, or [G] (q_mode 0) / [G * D] (q_mode 1) slots of
 // Mp x Mp; hv: variance / len per (model, dim).
 int mg_run(Scratch &sc, const std::string &who, int G, int nm, int M, int P, int D, int C, int steps, const HyperView &hv, const double *dZ,
@@ -752,15 +754,18 @@ int mg_run(Scratch &sc, const std::string &who, int G, int nm, int M, int P, int
            const double *dctrl, double *m_x, double *S_x, const SummaryReq *sum, const FilterReq *flt, const ForecastReq *fc = nullptr,
            int method = MG_METHOD_MOMENT) {
     const int Mp = round_up(M, NB), NS = (M + MG_SLAB - 1) / MG_SLAB;
-    const bool linear = method == MG_METHOD_LINEAR;
+    const bool linear = method == MG_METHOD_LINEAR, cub = method == MG_METHOD_CUBATURE;
     if (linear && !flt)
         return set_error(nullptr, FFVD_EINVAL, who + ": bad argument (the linearised rule is built for the filter and its forecasts only)");
+    if (cub && !(flt && fc))
+        return set_error(nullptr, FFVD_EINVAL, who + ": bad argument (the cubature rule is built for the records filter and the forecasts only)");
+    const int nrow = cub ? mg_crec_rows(D) : 1;                // rows of K per track
     const size_t nm_x = (size_t)G * steps * D, nS_x = nm_x * D;
     const SummaryReq fsum = flt ? flt->pooled(steps) : SummaryReq{};
     if (fsum.y_mean || fsum.y_var_total || fsum.lpd || fsum.lpd_gauss) sum = &fsum;
     BetaGamma bg{};
     const bool terms = bg.alloc(sc, G, nm, D, Mp, dq, q_mode);
-    double *part = sc.alloc<double>((size_t)2 * G * (linear ? mg_linear_fields(D) : mg_fields(D)) * NS), *state = sc.alloc<double>((size_t)2 * G * (D + D * D));
+    double *part = sc.alloc<double>(cub ? 1 : (size_t)2 * G * (linear ? mg_linear_fields(D) : mg_fields(D)) * NS), *state = sc.alloc<double>((size_t)2 * G * (D + D * D));
     double *dm = sc.alloc<double>(nm_x), *dS = sc.alloc<double>(nS_x);
     OP_CHECK(terms && part && state && dm && dS, who);
     MomentFilterArgs fa{};
@@ -782,20 +787,23 @@ int mg_run(Scratch &sc, const std::string &who, int G, int nm, int M, int P, int
     // the forecast: stacks, the origin table and the slab sums / states of one pass of tracks (after every request the filter makes)
     const int B = fc ? fc->n_origins : 0, h = fc ? fc->horizon : 0;
     const int upg = dq ? 1 : 0;
-    int Bp = !fc ? 0 : linear ? mg_lfan_tracks_per_pass(G, nm, D, Mp, upg, B) : mg_fan_tracks_per_pass(G, D, NS, B);
+    int Bp = !fc ? 0 : linear ? mg_lfan_tracks_per_pass(G, nm, D, Mp, upg, B) : cub ? mg_crec_records_per_pass(G, nm, D, Mp, upg, B)
+                                                                                    : mg_fan_tracks_per_pass(G, D, NS, B);
     if (fc && fc->tracks_per_pass > 0 && fc->tracks_per_pass < Bp) Bp = fc->tracks_per_pass;
     const size_t nm_fc = (size_t)G * B * h * D, nS_fc = nm_fc * D;
     double *dmfc = nullptr, *dSfc = nullptr, *fpart = nullptr, *fstate = nullptr;
     int *dorg = nullptr;
-    MomentLinearFanArgs lf{};                                // (linearised tracks: K, the column-tile partials and the mean sums of a pass)
+    MomentLinearFanArgs lf{};                                // (linearised and cubature tracks: K, the column-tile partials and the mean sums of a pass)
+    double *coff = nullptr;                                  // (cubature: the offsets of a step)
     if (fc) {
         dmfc = sc.alloc<double>(nm_fc); dSfc = sc.alloc<double>(nS_fc); dorg = sc.alloc<int>(B);
         fstate = sc.alloc<double>((size_t)2 * G * Bp * (D + D * D));
-        if (linear) {
-            lf = mg_lfan_layout(G, nm, D, Mp, upg, Bp);
+        if (linear || cub) {
+            lf = mg_lfan_layout(G, nm, D, Mp, upg, Bp * nrow);
             lf.K = sc.alloc<double>((size_t)lf.units * lf.Tp * Mp); lf.vpart = sc.alloc<double>((size_t)lf.units * lf.ntj * lf.Tp);
-            lf.msum = sc.alloc<double>((size_t)2 * G * Bp * D * (D + 1));
-            OP_CHECK(lf.K && lf.vpart && lf.msum, who);
+            lf.msum = sc.alloc<double>((size_t)2 * G * Bp * D * (cub ? nrow : D + 1));
+            if (cub) coff = sc.alloc<double>((size_t)2 * G * Bp * D * D);
+            OP_CHECK(lf.K && lf.vpart && lf.msum && (!cub || coff), who);
             OP_TRY(hipMemsetAsync(lf.K, 0, (size_t)lf.units * lf.Tp * Mp * sizeof(double), sc.stream));      // rows no pass fills stay zeros
         } else {
             fpart = sc.alloc<double>((size_t)2 * G * Bp * mg_fields(D) * NS);
@@ -814,7 +822,15 @@ int mg_run(Scratch &sc, const std::string &who, int G, int nm, int M, int P, int
     else {
         if (linear)
             for (int t = 0; t <= steps; ++t) launch_mg_linear_step(sc.stream, a, fa, t);
-        else
+        else if (cub) {
+            // one record per group through the records launch, in the buffers of the tracks with the layout of one record per group
+            // (Bp >= 1: never larger than theirs); the K rows it filled are zeros again before the first pass of tracks
+            const MomentRecordArgs ra{1, 1, 0};
+            MomentLinearFanArgs l1 = mg_lfan_layout(G, nm, D, Mp, upg, nrow);
+            l1.K = lf.K; l1.vpart = lf.vpart; l1.msum = lf.msum;
+            for (int t = 0; t <= steps; ++t) launch_mg_crec_step(sc.stream, a, fa, ra, l1, coff, t);
+            OP_TRY(hipMemsetAsync(lf.K, 0, (size_t)l1.units * l1.Tp * Mp * sizeof(double), sc.stream));
+        } else
             for (int t = 0; t <= steps; ++t) launch_mg_filter_step(sc.stream, a, fa, t);
         if (smooth) launch_mg_smooth(sc.stream, sa);
     }
@@ -830,6 +846,9 @@ int mg_run(Scratch &sc, const std::string &who, int G, int nm, int M, int P, int
             if (linear) {
                 lf.nr = lf.shared ? G * fn.Bp : fn.Bp;
                 for (int t = 0; t <= h; ++t) launch_mg_lfan_step(sc.stream, ta, fn, lf, t);
+            } else if (cub) {
+                lf.nr = (lf.shared ? G * fn.Bp : fn.Bp) * nrow;
+                for (int t = 0; t <= h; ++t) launch_mg_cfan_step(sc.stream, ta, fn, lf, coff, t);
             } else
                 for (int t = 0; t <= h; ++t) launch_mg_fan_step(sc.stream, ta, fn, t);
         }
@@ -864,6 +883,10 @@ const char *const mg_se_only = " (moment matching is closed-form for the SE kern
 const char *const mg_linear_se_only = " (the linearised filter is built for the SE kernel only: its kernel row and Jacobian are SE-ARD's)";
 const char *const mg_linear_fc_se_only =
     " (the linearised forecasts are built for the SE kernel only: their kernel rows and Jacobians are SE-ARD's)";
+const char *const mg_cubature_fc_se_only = " (the cubature forecasts are built for the SE kernel only: their kernel rows are SE-ARD's)";
+const char *mg_fc_se_only(int method) {
+    return method == MG_METHOD_LINEAR ? mg_linear_fc_se_only : method == MG_METHOD_CUBATURE ? mg_cubature_fc_se_only : mg_se_only;
+}
 
 // Posteriors given by the caller (also explicit-U models, SG-HMC samples of U: q_sqrts = NULL) through mg_run, scalars and pointers checked
 int mg_given_run(const std::string &who, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M, int P, int D,
@@ -1293,7 +1316,8 @@ extern "C" int ffvd_op_posterior_filter_cubature_records_grouped(FFVD_RECORDS_PO
 // ---- rolling-origin forecasts (moment_group.h, MomentFanArgs) -----------------------------------------------------------------------
 // ffvd_op_filter_grouped, then from every origin `horizon` steps of the propagation started at the filtered state of that row: one
 // launch per forecast step for all (group, origin) tracks of a pass, and the pooled summary of every (origin, horizon).  `method`: the
-// rule of the filter AND of the tracks (MG_METHOD_LINEAR: moment_linear.hip, then moment_linear_fan.hip, two launches per step)
+// rule of the filter AND of the tracks (MG_METHOD_LINEAR: moment_linear.hip, then moment_linear_fan.hip, two launches per step;
+// MG_METHOD_CUBATURE: moment_cubature_records.hip with one record, then moment_cubature_fan.hip, two launches per step)
 namespace {
 int forecast_given(const std::string &who, int method, int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M, int P,
                                         int D, const double *logvariances, const double *loglengthscales, const double *fs,
@@ -1308,7 +1332,7 @@ int forecast_given(const std::string &who, int method, int kind, int G, int n_mo
     const FilterReq f{CC, DD, noise_std, J, Y_obs, m_filt, S_filt, cross, lpd, lpd_joint, m_smooth, S_smooth, y_mean, y_var_total, lpd_mix,
                       lpd_gauss};
     const ForecastReq q{horizon, n_origins, tracks_per_pass, origins, m_fc, S_fc, fc_y_mean, fc_y_var_total, fc_lpd_mix, fc_lpd_gauss};
-    if (kind != FFVD_KERNEL_SE) return set_error(nullptr, FFVD_EINVAL, bad + (method == MG_METHOD_LINEAR ? mg_linear_fc_se_only : mg_se_only));
+    if (kind != FFVD_KERNEL_SE) return set_error(nullptr, FFVD_EINVAL, bad + mg_fc_se_only(method));
     if (!mg_scalars_ok(kind, G, n_models, M, P, D, C, steps, q_mode) || !filter_scalars_ok(f) || !forecast_scalars_ok(q, G, steps, D))
         return set_error(nullptr, FFVD_EINVAL, bad);
     if (G == 0 || steps == 0) return FFVD_OK;
@@ -1334,7 +1358,7 @@ int forecast_posterior(const std::string &who, int method, int kind, int G, int 
     const FilterReq f{CC, DD, noise_std, J, Y_obs, m_filt, S_filt, cross, lpd, lpd_joint, m_smooth, S_smooth, y_mean, y_var_total, lpd_mix,
                       lpd_gauss};
     const ForecastReq q{horizon, n_origins, tracks_per_pass, origins, m_fc, S_fc, fc_y_mean, fc_y_var_total, fc_lpd_mix, fc_lpd_gauss};
-    if (kind != FFVD_KERNEL_SE) return set_error(nullptr, FFVD_EINVAL, bad + (method == MG_METHOD_LINEAR ? mg_linear_fc_se_only : mg_se_only));
+    if (kind != FFVD_KERNEL_SE) return set_error(nullptr, FFVD_EINVAL, bad + mg_fc_se_only(method));
     if (!pg_scalars_ok(kind, G, n_models, M, P, D, C, T, groups_per_pass, jitter) || !mg_scalars_ok(kind, G, n_models, M, P, D, C, steps, q_mode) ||
         !filter_scalars_ok(f) || !forecast_scalars_ok(q, G, steps, D))
         return set_error(nullptr, FFVD_EINVAL, bad);
@@ -1410,6 +1434,42 @@ extern "C" int ffvd_op_posterior_forecast_linear_grouped(int kind, int G, int n_
                                                   int tracks_per_pass, double *m_fc, double *S_fc, double *fc_y_mean,
                                                   double *fc_y_var_total, double *fc_lpd_mix, double *fc_lpd_gauss) {
     return forecast_posterior("ffvd_op_posterior_forecast_linear_grouped", MG_METHOD_LINEAR, kind, G, n_models, Zs, M, P, D, logvariances,
+                              loglengthscales, Xs, ctrl_fit, C, T, log_Qs, jitter, groups_per_pass, q_mode, x0s, S0s, ctrl_roll, steps, CC,
+                              DD, noise_std, J, Y_obs, m_pred, S_pred, m_filt, S_filt, cross, lpd, lpd_joint, m_smooth, S_smooth, y_mean,
+                              y_var_total, lpd_mix, lpd_gauss, U_means, horizon, origins, n_origins, tracks_per_pass, m_fc, S_fc, fc_y_mean,
+                              fc_y_var_total, fc_lpd_mix, fc_lpd_gauss);
+}
+
+// The same two calls with the third-degree spherical cubature rule for the filter (the cubature records launch with one record) and
+// for the tracks (moment_cubature_fan.hip)
+extern "C" int ffvd_op_forecast_cubature_grouped(int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M, int P,
+                                        int D, const double *logvariances, const double *loglengthscales, const double *fs,
+                                        const double *const *q_sqrts, int q_mode, const double *x_lasts, const double *S0s,
+                                        const double *ctrl, int C, int steps, const double *log_Qs, const double *CC, const double *DD,
+                                        const double *noise_std, int J, const double *Y_obs, double *m_pred, double *S_pred,
+                                        double *m_filt, double *S_filt, double *cross, double *lpd, double *lpd_joint, double *m_smooth,
+                                        double *S_smooth, double *y_mean, double *y_var_total, double *lpd_mix, double *lpd_gauss,
+                                        int horizon, const int *origins, int n_origins, int tracks_per_pass, double *m_fc, double *S_fc,
+                                        double *fc_y_mean, double *fc_y_var_total, double *fc_lpd_mix, double *fc_lpd_gauss) {
+    return forecast_given("ffvd_op_forecast_cubature_grouped", MG_METHOD_CUBATURE, kind, G, n_models, Lm_inverse_seqs, Zs, M, P, D,
+                          logvariances, loglengthscales, fs, q_sqrts, q_mode, x_lasts, S0s, ctrl, C, steps, log_Qs, CC, DD, noise_std, J,
+                          Y_obs, m_pred, S_pred, m_filt, S_filt, cross, lpd, lpd_joint, m_smooth, S_smooth, y_mean, y_var_total, lpd_mix,
+                          lpd_gauss, horizon, origins, n_origins, tracks_per_pass, m_fc, S_fc, fc_y_mean, fc_y_var_total, fc_lpd_mix,
+                          fc_lpd_gauss);
+}
+
+extern "C" int ffvd_op_posterior_forecast_cubature_grouped(int kind, int G, int n_models, const double *Zs, int M, int P, int D,
+                                                  const double *logvariances, const double *loglengthscales, const double *Xs,
+                                                  const double *ctrl_fit, int C, int T, const double *log_Qs, double jitter,
+                                                  int groups_per_pass, int q_mode, const double *x0s, const double *S0s,
+                                                  const double *ctrl_roll, int steps, const double *CC, const double *DD,
+                                                  const double *noise_std, int J, const double *Y_obs, double *m_pred, double *S_pred,
+                                                  double *m_filt, double *S_filt, double *cross, double *lpd, double *lpd_joint,
+                                                  double *m_smooth, double *S_smooth, double *y_mean, double *y_var_total, double *lpd_mix,
+                                                  double *lpd_gauss, double *U_means, int horizon, const int *origins, int n_origins,
+                                                  int tracks_per_pass, double *m_fc, double *S_fc, double *fc_y_mean,
+                                                  double *fc_y_var_total, double *fc_lpd_mix, double *fc_lpd_gauss) {
+    return forecast_posterior("ffvd_op_posterior_forecast_cubature_grouped", MG_METHOD_CUBATURE, kind, G, n_models, Zs, M, P, D, logvariances,
                               loglengthscales, Xs, ctrl_fit, C, T, log_Qs, jitter, groups_per_pass, q_mode, x0s, S0s, ctrl_roll, steps, CC,
                               DD, noise_std, J, Y_obs, m_pred, S_pred, m_filt, S_filt, cross, lpd, lpd_joint, m_smooth, S_smooth, y_mean,
                               y_var_total, lpd_mix, lpd_gauss, U_means, horizon, origins, n_origins, tracks_per_pass, m_fc, S_fc, fc_y_mean,

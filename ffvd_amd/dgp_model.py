@@ -695,23 +695,34 @@ class DGPSSM:
         return DGPSSM._forecast_heldout(self, "forecast_heldout_linearised", "linearised", Y_test, control_inputs, horizon, stride, origins,
                                         x0, S0, q_mode, Y_train_std, return_tracks)
 
+    def forecast_heldout_cubature(self, Y_test, control_inputs=None, horizon=10, *, stride=1, origins=None, x0=None, S0=None,
+                                  q_mode="reference", Y_train_std=1.0, return_tracks=False):
+        """`forecast_heldout` with the third-degree spherical cubature rule for the filter and for the tracks: the same arguments, the
+        same dict, the same two forms, through prediction.posterior_forecast_cubature_grouped / forecast_cubature_grouped -- the filter
+        of `filter_records_cubature` over the one record, then from each origin `horizon` steps of the same 2D-point propagation
+        without a measurement update ("Cubature forecasts", has both the speed and the fit)."""
+        return DGPSSM._forecast_heldout(self, "forecast_heldout_cubature", "cubature", Y_test, control_inputs, horizon, stride, origins,
+                                        x0, S0, q_mode, Y_train_std, return_tracks)
+
     def _forecast_heldout(self, who, method, Y_test, control_inputs, horizon, stride, origins, x0, S0, q_mode, Y_train_std, return_tracks):
-        """The body of `forecast_heldout` and `forecast_heldout_linearised` (called through the class, as `_heldout_record`)."""
+        """The body of `forecast_heldout`, `forecast_heldout_linearised` and `forecast_heldout_cubature` (called through the class, as
+        `_heldout_record`)."""
         from . import conditionals_multi_output as cmo
         from . import prediction as pr
-        if method not in pr.FILTER_METHODS:
-            raise ValueError(f"{who}: method: expected one of {list(pr.FILTER_METHODS)}, got {method!r}")
-        linear = method == "linearised"
+        rules = {"moment": (pr.posterior_forecast_grouped, pr.forecast_grouped),
+                 "linearised": (pr.posterior_forecast_linear_grouped, pr.forecast_linear_grouped),
+                 "cubature": (pr.posterior_forecast_cubature_grouped, pr.forecast_cubature_grouped)}
+        if method not in rules:
+            raise ValueError(f"{who}: method: expected one of {list(rules)}, got {method!r}")
+        fused, explicit = rules[method]
         Y_test, x0s, S0s, ci = DGPSSM._heldout_record(self, who, Y_test, control_inputs, x0, S0, q_mode)
         S, lay, lik, n_train = self.num_chains, self.layers[-1], self.likelihood, self.Y.shape[0]
         kw = dict(origins=origins, stride=stride, S0s=S0s, q_mode=q_mode, Y_train_std=Y_train_std, return_tracks=return_tracks)
         if self.U_collapse:
-            fused = pr.posterior_forecast_linear_grouped if linear else pr.posterior_forecast_grouped
             return fused(lay.Z, lay.kernel, [self._X_chains[s_] for s_ in range(S)], self.Q, ci, n_train, Y_test, lik.CC, lik.DD,
                          lik.log_Rchols, horizon, x0s=x0s, **kw)
         Lm = cmo.kernel_pre_cal(lay.Z, lay.kernel)
         starts = [self._X_chains[s_][-1] for s_ in range(S)] if x0s is None else list(x0s)
-        explicit = pr.forecast_linear_grouped if linear else pr.forecast_grouped
         return explicit(Lm, lay.Z, lay.kernel, [lay.U] * S, None, starts, ci, n_train, Y_test, self.Q, lik.CC, lik.DD, lik.log_Rchols,
                         horizon, **kw)
 

@@ -1007,7 +1007,8 @@ def _forecast_dict(m, org, h, fout, out, Y_train_std):
 
 def _forecast_given(who, symbol, Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_inputs, ctrl_offset, Y_obs, Qs, CC, DD,
                     log_Rchols, horizon, origins, stride, S0s, q_mode, Y_train_std, return_tracks, return_filter, tracks_per_pass):
-    """The body of `forecast_grouped` and `forecast_linear_grouped`: `symbol` is the entry point (the propagation rule)."""
+    """The body of `forecast_grouped`, `forecast_linear_grouped` and `forecast_cubature_grouped`: `symbol` is the entry point (the
+    propagation rule)."""
     steps = _filter_steps(who, Y_obs)
     a = _pack_moment_groups(who, Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_inputs, ctrl_offset, steps, Qs, S0s, q_mode)
     h, org = _pack_forecast(who, steps, horizon, origins, stride, (a["args"][0], a["M"], a["args"][6], a["D"]))
@@ -1020,7 +1021,7 @@ def _forecast_given(who, symbol, Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0
 
 def _forecast_posterior(who, symbol, Zs, kerns, Xs, Qs, control_inputs, ctrl_offset, Y_obs, CC, DD, log_Rchols, horizon, x0s, origins,
                         stride, S0s, q_mode, Y_train_std, return_tracks, return_filter, tracks_per_pass, jitter, groups_per_pass):
-    """The body of `posterior_forecast_grouped` and `posterior_forecast_linear_grouped`"""
+    """The body of `posterior_forecast_grouped`, `posterior_forecast_linear_grouped` and `posterior_forecast_cubature_grouped`"""
     steps = _filter_steps(who, Y_obs)
     a = _pack_posterior_moment(who, Zs, kerns, Xs, Qs, control_inputs, ctrl_offset, steps, S0s, q_mode, jitter, groups_per_pass)
     h, org = _pack_forecast(who, steps, horizon, origins, stride, (a["args"][0], a["M"], a["args"][5], a["D"]))
@@ -1098,6 +1099,33 @@ def posterior_forecast_linear_grouped(Zs, kerns, Xs, Qs, control_inputs, ctrl_of
     (`ffvd_op_posterior_forecast_linear_grouped`): the parameters of `posterior_forecast_grouped` without `method`, the dict of
     `forecast_grouped`."""
     return _forecast_posterior("posterior_forecast_linear_grouped", "ffvd_op_posterior_forecast_linear_grouped", Zs, kerns, Xs, Qs,
+                               control_inputs, ctrl_offset, Y_obs, CC, DD, log_Rchols, horizon, x0s, origins, stride, S0s, q_mode, Y_train_std,
+                               return_tracks, return_filter, tracks_per_pass, jitter, groups_per_pass)
+
+
+def forecast_cubature_grouped(Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_inputs, ctrl_offset, Y_obs, Qs, CC, DD, log_Rchols,
+                              horizon, *, origins=None, stride=1, S0s=None, q_mode="reference", Y_train_std=1.0, return_tracks=False,
+                              return_filter=False, tracks_per_pass=0):
+    """`forecast_grouped` under the third-degree spherical cubature rule, in ONE call (`ffvd_op_forecast_cubature_grouped`): the filter
+    of `filter_cubature_records_grouped` over the one record, then from every origin `horizon` steps of the same propagation without
+    a measurement update, started at the filtered state (mu, S) of that row: S = L L^T, the 2D points [mu +- sqrt(D) L[:, i], c_row]
+    with equal weights, mu' and S' as in `filter_cubature_records_grouped`'s m^- and S^-.  The parameters and the returned dict are
+    `forecast_linear_grouped`'s; the pooled arrays give the groups EQUAL weights.  The call's filter outputs are
+    `filter_cubature_records_grouped`'s with R = 1 bit for bit (record axis dropped).  A track is what that filter computes over the
+    record cut after its origin and continued by `horizon` all-NaN rows.  A track does not depend on the other tracks, the other
+    groups or tracks_per_pass; every S_fc is exactly symmetric ("Cubature forecasts")."""
+    return _forecast_given("forecast_cubature_grouped", "ffvd_op_forecast_cubature_grouped", Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts,
+                           x0s, control_inputs, ctrl_offset, Y_obs, Qs, CC, DD, log_Rchols, horizon, origins, stride, S0s, q_mode,
+                           Y_train_std, return_tracks, return_filter, tracks_per_pass)
+
+
+def posterior_forecast_cubature_grouped(Zs, kerns, Xs, Qs, control_inputs, ctrl_offset, Y_obs, CC, DD, log_Rchols, horizon, *, x0s=None,
+                                        origins=None, stride=1, S0s=None, q_mode="reference", Y_train_std=1.0, return_tracks=False,
+                                        return_filter=False, tracks_per_pass=0, jitter=JITTER, groups_per_pass=0):
+    """The collapsed posterior of G groups and the forecasts of `forecast_cubature_grouped` in ONE call
+    (`ffvd_op_posterior_forecast_cubature_grouped`): the parameters of `posterior_forecast_linear_grouped`, the dict of
+    `forecast_grouped`."""
+    return _forecast_posterior("posterior_forecast_cubature_grouped", "ffvd_op_posterior_forecast_cubature_grouped", Zs, kerns, Xs, Qs,
                                control_inputs, ctrl_offset, Y_obs, CC, DD, log_Rchols, horizon, x0s, origins, stride, S0s, q_mode, Y_train_std,
                                return_tracks, return_filter, tracks_per_pass, jitter, groups_per_pass)
 

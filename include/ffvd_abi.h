@@ -912,6 +912,40 @@ int  ffvd_op_posterior_forecast_linear_grouped(int kind, int G, int n_models, co
                                         double *m_fc, double *S_fc, double *fc_y_mean, double *fc_y_var_total, double *fc_lpd_mix,
                                         double *fc_lpd_gauss);
 
+/* ffvd_op_forecast_grouped with the third-degree spherical cubature rule of ffvd_op_filter_cubature_records_grouped for the filter AND
+ * for the tracks: the arguments, checks, outputs and FFVD_EINVAL cases of ffvd_op_forecast_grouped.  The filter is that call with one
+ * record (R = 1): its outputs are that call's bit for bit, record axis dropped.  A track advances from the filtered state (mu, S) of
+ * its origin without a measurement update: with S = L L^T (no pivoting, a pivot <= 0 gives a zero column), the 2D points
+ * x_i = [mu +- sqrt(D) L[:, i], c_row] and m, v the mean and variance of the GP conditional at a point, w = 1 / (2D),
+ *   mbar = w sum_i m(x_i),   mu' = mu + mbar,
+ *   S' = S + w sum_i (m(x_i) - mbar)(m(x_i) - mbar)^T + diag(w sum_i v(x_i)) + V + V^T + diag(Q),   V = w sum_{i<D} dx_i (m(x_i) - m(x_{i+D}))^T
+ * (one expression for (lo, hi), mirrored: exactly symmetric), control row origin + 1 + t at step t.  The quadratic forms k^T Gamma k
+ * of all points of all tracks that share a Gamma are one dense product K Gamma on the fp64 matrix cores (2D rows of K per track and
+ * dim; the product of ffvd_op_forecast_linear_grouped).  Horizon 1 agrees with the filter's m_pred / S_pred of the next row to
+ * rounding.  A track does not depend on the other tracks, on the other groups or on tracks_per_pass.  SE kernel only (FFVD_EINVAL
+ * with a message that says so). */
+int  ffvd_op_forecast_cubature_grouped(int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M, int P, int D,
+                              const double *logvariances, const double *loglengthscales, const double *fs,
+                              const double *const *q_sqrts, int q_mode, const double *x_lasts, const double *S0s, const double *ctrl,
+                              int C, int steps, const double *log_Qs, const double *CC, const double *DD, const double *noise_std, int J,
+                              const double *Y_obs, double *m_pred, double *S_pred, double *m_filt, double *S_filt, double *cross,
+                              double *lpd, double *lpd_joint, double *m_smooth, double *S_smooth, double *y_mean, double *y_var_total,
+                              double *lpd_mix, double *lpd_gauss, int horizon, const int *origins, int n_origins, int tracks_per_pass,
+                              double *m_fc, double *S_fc, double *fc_y_mean, double *fc_y_var_total, double *fc_lpd_mix,
+                              double *fc_lpd_gauss);
+
+/* The same on the arguments of ffvd_op_posterior_forecast_grouped: the collapsed posteriors never leave the device. */
+int  ffvd_op_posterior_forecast_cubature_grouped(int kind, int G, int n_models, const double *Zs, int M, int P, int D, const double *logvariances,
+                                        const double *loglengthscales, const double *Xs, const double *ctrl_fit, int C, int T,
+                                        const double *log_Qs, double jitter, int groups_per_pass, int q_mode, const double *x0s,
+                                        const double *S0s, const double *ctrl_roll, int steps, const double *CC, const double *DD,
+                                        const double *noise_std, int J, const double *Y_obs, double *m_pred, double *S_pred,
+                                        double *m_filt, double *S_filt, double *cross, double *lpd, double *lpd_joint, double *m_smooth,
+                                        double *S_smooth, double *y_mean, double *y_var_total, double *lpd_mix, double *lpd_gauss,
+                                        double *U_means, int horizon, const int *origins, int n_origins, int tracks_per_pass,
+                                        double *m_fc, double *S_fc, double *fc_y_mean, double *fc_y_var_total, double *fc_lpd_mix,
+                                        double *fc_lpd_gauss);
+
 /* The summary of ffvd_op_moment_grouped for stacks the caller holds (m_x G x steps x D, S_x G x steps x D x D): the same launch.
  * Limits: D <= 8, J <= 8, 0 <= n_test <= steps, G * steps * D * D < 2^31, as ffvd_op_rollout_summary otherwise. */
 int  ffvd_op_moment_summary(const double *m_x, const double *S_x, int G, int steps, int D, const double *CC, const double *DD,
