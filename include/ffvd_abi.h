@@ -357,7 +357,9 @@ int  ffvd_op_kernel_matrix(int kind, const double *X, int N, const double *X2, i
 /* kernel.Kdiag(X): kernels_multi_output.py:199-200, kernels.py:278-281. out: N. */
 int  ffvd_op_kernel_diag(int kind, const double *X, int N, int P, double logvariance, double *out);
 /* batched lower Cholesky of `batch` n x n SPD matrices (tf.linalg.cholesky, conditionals_multi_output.py:28,162).
- * A and L may alias. info[b] = 0 or 1 + index of the first non-positive pivot. Returns FFVD_ENOTPD if any info != 0. */
+ * Only the lower triangle of A is read (entries above the diagonal are ignored, NaN included); L comes back with an exactly zero
+ * strict upper triangle. A and L may alias. info (may be NULL) [b] = 0 or 1 + index of the first pivot that is not positive (NaN
+ * included). Returns FFVD_ENOTPD if any info != 0; the message names the first such matrix. */
 int  ffvd_op_cholesky(const double *A, int n, int batch, double *L, int32_t *info);
 /* The whitened triangular solve of base_conditional: A = Lm^-1 Kmn = tf.linalg.triangular_solve(Lm, Kmn, lower=True)
  * (conditionals_multi_output.py:34, conditionals.py:30).  L: n x n lower triangular (entries above the diagonal are ignored),
