@@ -40,6 +40,8 @@ class FfvdGrads(C.Structure):
 
 
 _dp = C.POINTER(C.c_double)
+# N, then eps, unif and xi0 each with its group and record stride (the particle filter's draws)
+_PARTICLE_DRAWS = [C.c_int] + [_dp, C.c_longlong, C.c_longlong] * 3
 _SIGNATURES = {
     "ffvd_create": (C.c_int, [C.POINTER(FfvdConfig), C.POINTER(C.c_void_p)]),
     "ffvd_destroy": (C.c_int, [C.c_void_p]),
@@ -169,6 +171,14 @@ _SIGNATURES = {
     "ffvd_op_posterior_filter_cubature_records_grouped": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp,
                                                                     _dp, C.c_int, C.c_int, _dp, C.c_double, C.c_int, C.c_int, C.c_int, _dp,
                                                                     _dp, _dp, C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_int] + [_dp] * 14),
+    "ffvd_op_filter_particle_records_grouped": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), _dp, C.c_int, C.c_int, C.c_int, _dp,
+                                                          _dp, _dp, C.POINTER(C.c_void_p), C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, C.c_int,
+                                                          _dp, _dp, _dp, _dp, C.c_int, _dp, C.c_int] + _PARTICLE_DRAWS + [_dp] * 13 +
+                                                         [C.POINTER(C.c_int)]),
+    "ffvd_op_posterior_filter_particle_records_grouped": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp,
+                                                                    _dp, C.c_int, C.c_int, _dp, C.c_double, C.c_int, C.c_int, C.c_int, _dp,
+                                                                    _dp, _dp, C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_int] +
+                                                                   _PARTICLE_DRAWS + [_dp] * 13 + [C.POINTER(C.c_int), _dp]),
     "ffvd_op_forecast_grouped": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp,
                                            C.POINTER(C.c_void_p), C.c_int, _dp, _dp, _dp, C.c_int, C.c_int, _dp,
                                            _dp, _dp, _dp, C.c_int, _dp] + [_dp] * 13 +

@@ -155,6 +155,35 @@ int mg_crec_records_per_pass(int G, int n_models, int D, int Mp, int unit_per_gr
 void launch_mg_crec_step(hipStream_t stream, const MomentGroupArgs &a, const MomentFilterArgs &f, const MomentRecordArgs &rc,
                          const MomentLinearFanArgs &l, double *off, int t);
 
+// Particle filtering of many records (moment_particle_records.hip; DESIGN.md section 9, "Particle filtering"): the tracks, passes and
+// stacks of the linearised records filter with a bootstrap particle filter of N particles per track as the propagation and the update
+// (no Gaussian projection, no `cross`, no smoother).  A track brings N kernel rows per (track, dim): rows N * (track row) + i of the
+// unit's K block.  MomentLinearFanArgs is mg_lfan_layout with Bp = N * (records per group of the pass); msum is not read.  The draws
+// are the caller's: eps [..][steps][N][D], unif [..][steps] and xi0 [..][N][D] (read only with S0) are indexed through a group and a
+// record stride in doubles, each of which may be 0 (common random numbers).  The product kernel runs unchanged.
+// Limits: MG_PREC_MINN <= N <= MG_PREC_MAXN; N <= mg_prec_max_particles (one track per group fits K); G * Rp * D * ceil(N / slab) < 2^31.
+constexpr int MG_PREC_MINN = 2, MG_PREC_MAXN = 2048;
+constexpr int MG_PREC_SLAB = 8;      // particles per workgroup of the rows kernel
+struct MomentParticleArgs {
+    int N;
+    const double *eps;
+    long long eps_g, eps_r;
+    const double *unif;
+    long long unif_g, unif_r;
+    const double *xi0;               // nullptr without S0
+    long long xi0_g, xi0_r;
+    double *xstate;                  // [2][tracks][N][D]: the particles (step parity)
+    double *pmean;                   // [tracks][D][N]: the conditional mean at every particle
+    double *ess;                     // [G][R][steps]
+    double *particles;               // [G][R][steps][N][D] (the X^-) or nullptr
+    int *ancestors;                  // [G][R][steps][N] or nullptr
+};
+long long mg_prec_max_particles(int G, int n_models, int D, int Mp, int unit_per_group);
+int mg_prec_records_per_pass(int G, int n_models, int D, int Mp, int unit_per_group, int R, int N);
+// launch t of steps + 1: the weight kernel, then (t < steps) the rows kernel and the product kernel
+void launch_mg_prec_step(hipStream_t stream, const MomentGroupArgs &a, const MomentFilterArgs &f, const MomentRecordArgs &rc,
+                         const MomentLinearFanArgs &l, const MomentParticleArgs &p, int t);
+
 // Cubature forecasts (moment_cubature_fan.hip; DESIGN.md section 9, "Cubature forecasts"): the fan's tracks and indexing (MomentFanArgs)
 // with the cubature rule above and no measurement update.  MomentGroupArgs as for the linearised forecasts; MomentLinearFanArgs is
 // mg_lfan_layout with Bp = 2D * (tracks per group of the pass), msum [2][tracks][D][2D], `off` [2][tracks][D][D].  The product kernel

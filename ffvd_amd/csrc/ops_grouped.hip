@@ -622,7 +622,7 @@ bool mg_scalars_ok(int kind, int G, int n_models, int M, int P, int D, int C, in
            (steps == 0 || G <= ((1LL << 31) - 1) / steps / D / D);
 }
 // the propagation rule of the filter's launches (mg_run)
-enum { MG_METHOD_MOMENT = 0, MG_METHOD_LINEAR = 1, MG_METHOD_CUBATURE = 2 };    // (cubature: the records calls and the forecasts)
+enum { MG_METHOD_MOMENT = 0, MG_METHOD_LINEAR = 1, MG_METHOD_CUBATURE = 2, MG_METHOD_PARTICLE = 3 };    // (cubature: the records calls and the forecasts; particle: the records calls)
 // the trailing summary block of the entry points: asked for when anything in it is given
 bool mg_summary_wanted(const SummaryReq &q) {
     return q.CC || q.DD || q.noise_std || q.J != 0 || q.Y_test || q.n_test != 0 || q.y_mean || q.y_var || q.y_var_total || q.lpd || q.lpd_gauss;
@@ -1100,6 +1100,91 @@ const char *const mg_records_se_only =
     " (the linearised filter of many records is built for the SE kernel only: its kernel rows and Jacobians are SE-ARD's)";
 const char *const mg_crecords_se_only =
     " (the cubature filter of many records is built for the SE kernel only: its kernel rows are SE-ARD's)";
+const char *const mg_precords_se_only =
+    " (the particle filter of many records is built for the SE kernel only: its kernel rows are SE-ARD's)";
+// The particle request beside a RecordsReq (MG_METHOD_PARTICLE): N particles per track, the caller's draws with their (group, record)
+// strides in doubles -- each 0 or the stride of a contiguous array -- and the outputs the Gaussian rules do not have
+struct ParticleReq {
+    int N;
+    const double *eps;                           // [G or 1][R or 1][steps][N][D]
+    long long eps_g, eps_r;
+    const double *unif;                          // [G or 1][R or 1][steps]
+    long long unif_g, unif_r;
+    const double *xi0;                           // [G or 1][R or 1][N][D]; needed exactly when S0s is given
+    long long xi0_g, xi0_r;
+    double *ess, *log_evidence;                  // [G][R][steps], [G][R]
+    double *particles;                           // [G][R][steps][N][D] or NULL
+    int *ancestors;                              // [G][R][steps][N] or NULL
+};
+// a pair of strides over arrays of `inner` doubles per (group, record): record 0 or inner, group 0 or inner * (R or 1)
+bool particle_strides_ok(long long sg, long long sr, long long inner, int R) {
+    return (sr == 0 || sr == inner) && (sg == 0 || sg == inner * (sr ? R : 1));
+}
+size_t particle_extent(long long sg, long long sr, long long inner, int G, int R) {
+    return (size_t)inner * (sr ? R : 1) * (sg ? G : 1);
+}
+// the checks of a particle request that need no device: N, the strides, the arrays (finite draws, unif in [0, 1))
+bool particle_ok(const ParticleReq &q, int G, int R, int steps, int D, bool with_S0, bool nothing) {
+    if (q.N < MG_PREC_MINN || q.N > MG_PREC_MAXN) return false;
+    const long long ne = (long long)steps * q.N * D, nx = (long long)q.N * D;
+    if (!particle_strides_ok(q.eps_g, q.eps_r, ne, R) || !particle_strides_ok(q.unif_g, q.unif_r, steps, R) ||
+        !particle_strides_ok(q.xi0_g, q.xi0_r, nx, R))
+        return false;
+    if (nothing) return true;
+    if ((long long)G * R > ((1LL << 31) - 1) / steps / q.N / D) return false;          // G * R * steps * N * D < 2^31
+    if (!q.eps || !q.unif || (with_S0 && !q.xi0)) return false;
+    const size_t n_eps = particle_extent(q.eps_g, q.eps_r, ne, G, R), n_u = particle_extent(q.unif_g, q.unif_r, steps, G, R);
+    for (size_t e = 0; e < n_eps; ++e)
+        if (!std::isfinite(q.eps[e])) return false;
+    for (size_t e = 0; e < n_u; ++e)
+        if (!(q.unif[e] >= 0.0 && q.unif[e] < 1.0)) return false;
+    if (with_S0) {
+        const size_t n_x = particle_extent(q.xi0_g, q.xi0_r, nx, G, R);
+        for (size_t e = 0; e < n_x; ++e)
+            if (!std::isfinite(q.xi0[e])) return false;
+    }
+    return true;
+}
+
+// The tail of a particle call: the pooled summary of the predicted stacks on the device (y_mean, y_var_total, lpd_gauss), the downloads,
+// and on the host, from the stacks that came down: lpd_mix = log mean_g exp(lpd[g]) (the mixture of all G * N particles' emissions; in
+// ascending g, the largest exponent subtracted; NaN where the entry is unobserved) and log_evidence = the sum of lpd_joint over the
+// rows that have an observation, in ascending order
+int mg_particle_finish(Scratch &sc, const std::string &who, int G, int R, int steps, int D, const double *dm, const double *dS, double *m_x,
+                       double *S_x, const MomentFilterArgs &fa, const MomentParticleArgs &pa, const FilterReq &flt, const ParticleReq &pq) {
+    const int J = flt.J;
+    const size_t V = (size_t)G * R, nm_x = V * steps * D, nS_x = nm_x * D, nlpd = V * steps * J, nlj = V * steps, RS = (size_t)R * steps;
+    SummaryReq fsum = flt.pooled(R * steps);
+    fsum.lpd = nullptr;
+    if (fsum.y_mean || fsum.y_var_total || fsum.lpd_gauss)
+        if (int rc = mg_summary(sc, who, dm, dS, G, R * steps, D, fsum)) return rc;
+    std::vector<double> hl, hj;                                                        // (host copies where the caller asks for a derived array only)
+    double *lpd = flt.lpd, *lj = flt.lpd_joint;
+    if (!lpd && flt.lpd_mix) { hl.resize(nlpd); lpd = hl.data(); }
+    if (!lj && pq.log_evidence) { hj.resize(nlj); lj = hj.data(); }
+    auto down = [&](void *dst, const void *src, size_t bytes) { return !dst || sc.download(dst, src, bytes); };
+    if (!down(flt.m_filt, fa.m_filt, nm_x * sizeof(double)) || !down(flt.S_filt, fa.S_filt, nS_x * sizeof(double)) ||
+        !down(lpd, fa.lpd, nlpd * sizeof(double)) || !down(lj, fa.lpd_joint, nlj * sizeof(double)) || !down(m_x, dm, nm_x * sizeof(double)) ||
+        !down(S_x, dS, nS_x * sizeof(double)) || !down(pq.ess, pa.ess, nlj * sizeof(double)) ||
+        !down(pq.particles, pa.particles, nm_x * pq.N * sizeof(double)) || !down(pq.ancestors, pa.ancestors, nlj * pq.N * sizeof(int)))
+        return set_error(nullptr, FFVD_EDEVICE, who + ": copying the results back failed");
+    OP_TRY(hipStreamSynchronize(sc.stream));
+    if (flt.lpd_mix)
+        for (size_t e = 0; e < RS * J; ++e) {
+            double mx = -INFINITY, sum = 0.0;
+            for (int g = 0; g < G; ++g) mx = std::fmax(mx, lpd[(size_t)g * RS * J + e]);
+            for (int g = 0; g < G; ++g) sum += std::exp(lpd[(size_t)g * RS * J + e] - mx);
+            flt.lpd_mix[e] = std::isnan(lpd[e]) ? NAN : mx + std::log(sum / G);
+        }
+    if (pq.log_evidence)
+        for (size_t v = 0; v < V; ++v) {
+            double sum = 0.0;
+            for (int i = 0; i < steps; ++i)
+                if (!std::isnan(lj[v * steps + i])) sum += lj[v * steps + i];
+            pq.log_evidence[v] = sum;
+        }
+    return FFVD_OK;
+}
 
 // Operands on the device -> beta, Gamma (BetaGamma, once per call), the passes over the records (steps + 1 launch pairs each), the
 // smoother over all G * R tracks, the pooled summary per record and row, the downloads.  A sibling of mg_run's linear branch.
@@ -1108,13 +1193,21 @@ const char *const mg_crecords_se_only =
 // 2D mean sums per (track, dim) and the offsets of a step beside the state; everything else is shared).
 int mg_records_run(Scratch &sc, const std::string &who, int method, int G, int nm, int M, int P, int D, int C, int steps, const HyperView &hv,
                    const double *dZ, const double *dW, const double *dq, int q_mode, const double *dU, const double *dxl, const double *dS0,
-                   const double *dlq, const double *dctrl, double *m_x, double *S_x, const FilterReq &flt, const RecordsReq &rq) {
+                   const double *dlq, const double *dctrl, double *m_x, double *S_x, const FilterReq &flt, const RecordsReq &rq,
+                   const ParticleReq *pq = nullptr) {
     const int Mp = round_up(M, NB), R = rq.R, J = flt.J, upg = dq ? 1 : 0;
     const int V = G * R;                                                               // tracks of the call (V * steps * D * D < 2^31)
     const size_t nm_x = (size_t)V * steps * D, nS_x = nm_x * D, nlpd = (size_t)V * steps * J, nlj = (size_t)V * steps;
-    const bool cub = method == MG_METHOD_CUBATURE;
-    const int nrow = cub ? mg_crec_rows(D) : 1;                                        // rows of K per track
-    int Rp = cub ? mg_crec_records_per_pass(G, nm, D, Mp, upg, R) : mg_lfan_tracks_per_pass(G, nm, D, Mp, upg, R);
+    const bool cub = method == MG_METHOD_CUBATURE, par = method == MG_METHOD_PARTICLE;
+    const int nrow = cub ? mg_crec_rows(D) : par ? pq->N : 1;                          // rows of K per track
+    if (par) {
+        const long long fit = mg_prec_max_particles(G, nm, D, Mp, upg);
+        if (pq->N > fit)
+            return set_error(nullptr, FFVD_EINVAL, who + ": bad argument (the kernel rows of one record per group do not fit the scratch of a pass: "
+                             "the largest N that fits is " + std::to_string(fit / 128 * 128 > MG_PREC_MAXN ? MG_PREC_MAXN : fit) + ")");
+    }
+    int Rp = cub ? mg_crec_records_per_pass(G, nm, D, Mp, upg, R) : par ? mg_prec_records_per_pass(G, nm, D, Mp, upg, R, pq->N)
+                                                                        : mg_lfan_tracks_per_pass(G, nm, D, Mp, upg, R);
     if (rq.records_per_pass > 0 && rq.records_per_pass < Rp) Rp = rq.records_per_pass;
     BetaGamma bg{};
     const bool terms = bg.alloc(sc, G, nm, D, Mp, dq, q_mode);
@@ -1124,9 +1217,9 @@ int mg_records_run(Scratch &sc, const std::string &who, int method, int G, int n
     const Emission e = stage_emission(sc, D, J, flt.CC, flt.DD, flt.noise_std, flt.Y_obs, (size_t)R * steps);
     MomentFilterArgs fa{};
     fa.J = J; fa.CC = e.CC; fa.DD = e.DD; fa.sd = e.sd; fa.Y = e.Y;
-    fa.m_filt = sc.alloc<double>(nm_x); fa.S_filt = sc.alloc<double>(nS_x); fa.cross = sc.alloc<double>(nS_x);
+    fa.m_filt = sc.alloc<double>(nm_x); fa.S_filt = sc.alloc<double>(nS_x); fa.cross = par ? nullptr : sc.alloc<double>(nS_x);
     fa.lpd = sc.alloc<double>(nlpd); fa.lpd_joint = sc.alloc<double>(nlj);
-    OP_CHECK(e.ok && fa.m_filt && fa.S_filt && fa.cross && fa.lpd && fa.lpd_joint, who);
+    OP_CHECK(e.ok && fa.m_filt && fa.S_filt && (par || fa.cross) && fa.lpd && fa.lpd_joint, who);
     MomentSmoothArgs sa{};
     const bool smooth = flt.m_smooth || flt.S_smooth;
     if (smooth) {                                                                      // the stacks are [G][R][steps]...: its [G'][steps]...
@@ -1136,9 +1229,25 @@ int mg_records_run(Scratch &sc, const std::string &who, int method, int G, int n
     }
     MomentLinearFanArgs lf = mg_lfan_layout(G, nm, D, Mp, upg, Rp * nrow);
     lf.K = sc.alloc<double>((size_t)lf.units * lf.Tp * Mp); lf.vpart = sc.alloc<double>((size_t)lf.units * lf.ntj * lf.Tp);
-    lf.msum = sc.alloc<double>((size_t)2 * G * Rp * D * (cub ? nrow : D + 1));
+    lf.msum = par ? nullptr : sc.alloc<double>((size_t)2 * G * Rp * D * (cub ? nrow : D + 1));
     double *coff = cub ? sc.alloc<double>((size_t)2 * G * Rp * D * D) : nullptr;
-    OP_CHECK(lf.K && lf.vpart && lf.msum && (!cub || coff), who);
+    OP_CHECK(lf.K && lf.vpart && (par || lf.msum) && (!cub || coff), who);
+    MomentParticleArgs pa{};
+    if (par) {                                                                         // the draws, uploaded once; the particles of a pass
+        const ParticleReq &q = *pq;
+        const long long ne = (long long)steps * q.N * D, nx = (long long)q.N * D;
+        pa.N = q.N; pa.eps_g = q.eps_g; pa.eps_r = q.eps_r; pa.unif_g = q.unif_g; pa.unif_r = q.unif_r; pa.xi0_g = q.xi0_g; pa.xi0_r = q.xi0_r;
+        pa.eps = sc.upload(q.eps, particle_extent(q.eps_g, q.eps_r, ne, G, R));
+        pa.unif = sc.upload(q.unif, particle_extent(q.unif_g, q.unif_r, steps, G, R));
+        pa.xi0 = dS0 ? sc.upload(q.xi0, particle_extent(q.xi0_g, q.xi0_r, nx, G, R)) : nullptr;
+        pa.xstate = sc.alloc<double>((size_t)2 * G * Rp * q.N * D);
+        pa.pmean = sc.alloc<double>((size_t)G * Rp * D * q.N);
+        pa.ess = sc.alloc<double>(nlj);
+        pa.particles = q.particles ? sc.alloc<double>(nm_x * q.N) : nullptr;
+        pa.ancestors = q.ancestors ? sc.alloc<int>(nlj * q.N) : nullptr;
+        OP_CHECK(pa.eps && pa.unif && (!dS0 || pa.xi0) && pa.xstate && pa.pmean && pa.ess && (!q.particles || pa.particles) &&
+                 (!q.ancestors || pa.ancestors), who);
+    }
     OP_TRY(hipMemsetAsync(lf.K, 0, (size_t)lf.units * lf.Tp * Mp * sizeof(double), sc.stream));          // rows no pass fills stay zeros
     if (int rc = bg.launch(sc, G, nm, M, D, Mp, hv.len, dW, dq, q_mode, dU)) return rc;
     MomentGroupArgs a{};
@@ -1154,11 +1263,13 @@ int mg_records_run(Scratch &sc, const std::string &who, int method, int G, int n
         lf.nr = (lf.shared ? G * ra.Rp : ra.Rp) * nrow;
         for (int t = 0; t <= steps; ++t) {
             if (cub) launch_mg_crec_step(sc.stream, a, fa, ra, lf, coff, t);
+            else if (par) launch_mg_prec_step(sc.stream, a, fa, ra, lf, pa, t);
             else launch_mg_lrec_step(sc.stream, a, fa, ra, lf, t);
         }
     }
     if (smooth) launch_mg_smooth(sc.stream, sa);
     OP_TRY(hipGetLastError());
+    if (par) return mg_particle_finish(sc, who, G, R, steps, D, dm, dS, m_x, S_x, fa, pa, flt, *pq);
     // the pooled one-step summary per record and row: the predicted stacks as [G][R * steps] against Y as [R * steps][J]
     const SummaryReq fsum = flt.pooled(R * steps);
     if (fsum.y_mean || fsum.y_var_total || fsum.lpd || fsum.lpd_gauss)
@@ -1174,15 +1285,19 @@ int mg_records_run(Scratch &sc, const std::string &who, int method, int G, int n
 
 // the scalar-argument checks the two entry points share (before any device call); nothing: FFVD_OK without touching anything
 int records_checks(const std::string &who, int method, int kind, int G, int n_models, int M, int P, int D, int C, int steps, int q_mode, const FilterReq &f,
-                   const RecordsReq &rq, bool &nothing) {
+                   const RecordsReq &rq, bool &nothing, const ParticleReq *pq = nullptr, bool with_S0 = false) {
     const std::string bad = who + ": bad argument";
     nothing = false;
     if (kind != FFVD_KERNEL_SE)
-        return set_error(nullptr, FFVD_EINVAL, bad + (method == MG_METHOD_CUBATURE ? mg_crecords_se_only : mg_records_se_only));
+        return set_error(nullptr, FFVD_EINVAL, bad + (method == MG_METHOD_CUBATURE ? mg_crecords_se_only : method == MG_METHOD_PARTICLE
+                                                                                                       ? mg_precords_se_only : mg_records_se_only));
     if (!mg_scalars_ok(kind, G, n_models, M, P, D, C, steps, q_mode) || !filter_scalars_ok(f)) return set_error(nullptr, FFVD_EINVAL, bad);
     if (!records_scalars_ok(rq, G, steps, D))
         return set_error(nullptr, FFVD_EINVAL, bad + " (R >= 0, records_per_pass >= 0, G * R * steps * D * D < 2^31 and G * R * D < 2^31 are needed)");
     nothing = G == 0 || rq.R == 0 || steps == 0;
+    if (method == MG_METHOD_PARTICLE && (!pq || !particle_ok(*pq, G, rq.R, steps, D, with_S0, nothing)))
+        return set_error(nullptr, FFVD_EINVAL, bad + " (2 <= N <= 2048, finite draws, unif in [0, 1), xi0 with S0s, strides 0 or contiguous and "
+                                               "G * R * steps * N * D < 2^31 are needed)");
     return FFVD_OK;
 }
 
@@ -1194,16 +1309,16 @@ int records_given(const std::string &who, int method, int kind, int G, int n_mod
                   const double *DD, const double *noise_std, int J, const double *Y_obs,
                   int records_per_pass, double *m_pred, double *S_pred, double *m_filt, double *S_filt,
                   double *cross, double *lpd, double *lpd_joint, double *m_smooth, double *S_smooth,
-                  double *y_mean, double *y_var_total, double *lpd_mix, double *lpd_gauss) {
+                  double *y_mean, double *y_var_total, double *lpd_mix, double *lpd_gauss, const ParticleReq *pq = nullptr) {
     const std::string bad = who + ": bad argument";
     const FilterReq f{CC, DD, noise_std, J, Y_obs, m_filt, S_filt, cross, lpd, lpd_joint, m_smooth, S_smooth, y_mean, y_var_total, lpd_mix,
                       lpd_gauss};
     const RecordsReq rq{R, records_per_pass};
     bool nothing;
-    if (int rc = records_checks(who, method, kind, G, n_models, M, P, D, C, steps, q_mode, f, rq, nothing)) return rc;
+    if (int rc = records_checks(who, method, kind, G, n_models, M, P, D, C, steps, q_mode, f, rq, nothing, pq, S0s != nullptr)) return rc;
     if (nothing) return FFVD_OK;
     if (!Lm_inverse_seqs || !Zs || !logvariances || !loglengthscales || !fs || !x_lasts || !log_Qs || (C > 0 && !ctrl) ||
-        !filter_arrays_ok(f, R * steps, m_pred, S_pred))
+        !filter_arrays_ok(f, R * steps, m_pred, S_pred, pq && (pq->ess || pq->log_evidence || pq->particles || pq->ancestors)))
         return set_error(nullptr, FFVD_EINVAL, bad);
     const size_t nK = (size_t)n_models * D, GD = (size_t)G * D, VD = GD * R, nq = given_nq(q_sqrts, q_mode, G, D);
     if (!given_tables_ok(Lm_inverse_seqs, nK, q_sqrts, nq)) return set_error(nullptr, FFVD_EINVAL, bad);
@@ -1216,7 +1331,7 @@ int records_given(const std::string &who, int method, int kind, int G, int n_mod
     OP_CHECK(dW && (!nq || dq) && dU && dxl && (!S0s || dS0) && dlq && (!C || dctrl) && gh.logs(sc) && gh.blocks(sc), who);
     gh.prep(sc.stream);
     return mg_records_run(sc, who, method, G, n_models, M, P, D, C, steps, gh.hv(), gh.dZ, dW, dq, q_mode, dU, dxl, dS0, dlq, dctrl, m_pred, S_pred, f,
-                          rq);
+                          rq, pq);
 }
 
 // the body of ffvd_op_posterior_filter_records_grouped and ffvd_op_posterior_filter_cubature_records_grouped
@@ -1228,17 +1343,17 @@ int records_posterior(const std::string &who, int method, int kind, int G, int n
                       const double *noise_std, int J, const double *Y_obs, int records_per_pass,
                       double *m_pred, double *S_pred, double *m_filt, double *S_filt, double *cross,
                       double *lpd, double *lpd_joint, double *m_smooth, double *S_smooth, double *y_mean,
-                      double *y_var_total, double *lpd_mix, double *lpd_gauss, double *U_means) {
+                      double *y_var_total, double *lpd_mix, double *lpd_gauss, double *U_means, const ParticleReq *pq = nullptr) {
     const std::string bad = who + ": bad argument";
     const FilterReq f{CC, DD, noise_std, J, Y_obs, m_filt, S_filt, cross, lpd, lpd_joint, m_smooth, S_smooth, y_mean, y_var_total, lpd_mix,
                       lpd_gauss};
     const RecordsReq rq{R, records_per_pass};
     bool nothing;
-    if (int rc = records_checks(who, method, kind, G, n_models, M, P, D, C, steps, q_mode, f, rq, nothing)) return rc;
+    if (int rc = records_checks(who, method, kind, G, n_models, M, P, D, C, steps, q_mode, f, rq, nothing, pq, S0s != nullptr)) return rc;
     if (!pg_scalars_ok(kind, G, n_models, M, P, D, C, T, groups_per_pass, jitter)) return set_error(nullptr, FFVD_EINVAL, bad);
     if (nothing) return FFVD_OK;
     if (!Zs || !logvariances || !loglengthscales || !Xs || !log_Qs || (C > 0 && (!ctrl_fit || !ctrl_roll)) ||
-        !filter_arrays_ok(f, R * steps, m_pred, S_pred))
+        !filter_arrays_ok(f, R * steps, m_pred, S_pred, pq && (pq->ess || pq->log_evidence || pq->particles || pq->ancestors)))
         return set_error(nullptr, FFVD_EINVAL, bad);
     const PgIn in{who, kind, G, n_models, M, P, D, C, T, groups_per_pass, Zs, logvariances, loglengthscales, Xs, ctrl_fit, log_Qs, jitter};
     OP_BEGIN(who);
@@ -1259,7 +1374,7 @@ int records_posterior(const std::string &who, int method, int kind, int G, int n
         launch_mg_lrec_spread(sc.stream, G, R, D, dx1, dxl);
     }
     if (int rc = mg_records_run(sc, who, method, G, nm, M, P, D, C, steps, w.hv, dZ, dW, pg_q(w, q_mode), q_mode, w.U, dxl, dS0, w.log_Qs, dctrl,
-                                m_pred, S_pred, f, rq))
+                                m_pred, S_pred, f, rq, pq))
         return rc;
     if (U_means && !sc.download(U_means, w.U, GD * M * sizeof(double)))
         return set_error(nullptr, FFVD_EDEVICE, who + ": copying the results back failed");
@@ -1308,6 +1423,51 @@ extern "C" int ffvd_op_filter_cubature_records_grouped(FFVD_RECORDS_GIVEN_PARAMS
 extern "C" int ffvd_op_posterior_filter_cubature_records_grouped(FFVD_RECORDS_POSTERIOR_PARAMS) {
     return records_posterior("ffvd_op_posterior_filter_cubature_records_grouped", MG_METHOD_CUBATURE, FFVD_RECORDS_POSTERIOR_ARGS);
 }
+
+// The same two calls with a bootstrap particle filter of N particles per track as the propagation and the update
+// (moment_particle_records.hip): no smoother and no `cross`; the draws are the caller's
+#define FFVD_PARTICLE_PARAMS                                                                                                                 \
+    int N, const double *eps, long long eps_stride_g, long long eps_stride_r, const double *unif, long long unif_stride_g,                  \
+        long long unif_stride_r, const double *xi0, long long xi0_stride_g, long long xi0_stride_r
+#define FFVD_PARTICLE_REQ                                                                                                                    \
+    const ParticleReq pq {                                                                                                                   \
+        N, eps, eps_stride_g, eps_stride_r, unif, unif_stride_g, unif_stride_r, xi0, xi0_stride_g, xi0_stride_r, ess, log_evidence,          \
+            particles, ancestors                                                                                                             \
+    }
+extern "C" int ffvd_op_filter_particle_records_grouped(int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M,
+                                                       int P, int D, const double *logvariances, const double *loglengthscales, const double *fs,
+                                                       const double *const *q_sqrts, int q_mode, int R, const double *x_lasts, const double *S0s,
+                                                       const double *ctrl, int C, int steps, const double *log_Qs, const double *CC,
+                                                       const double *DD, const double *noise_std, int J, const double *Y_obs,
+                                                       int records_per_pass, FFVD_PARTICLE_PARAMS, double *m_pred, double *S_pred,
+                                                       double *m_filt, double *S_filt, double *lpd, double *lpd_joint, double *y_mean,
+                                                       double *y_var_total, double *lpd_mix, double *lpd_gauss, double *ess,
+                                                       double *log_evidence, double *particles, int *ancestors) {
+    FFVD_PARTICLE_REQ;
+    return records_given("ffvd_op_filter_particle_records_grouped", MG_METHOD_PARTICLE, kind, G, n_models, Lm_inverse_seqs, Zs, M, P, D,
+                         logvariances, loglengthscales, fs, q_sqrts, q_mode, R, x_lasts, S0s, ctrl, C, steps, log_Qs, CC, DD, noise_std, J, Y_obs,
+                         records_per_pass, m_pred, S_pred, m_filt, S_filt, nullptr, lpd, lpd_joint, nullptr, nullptr, y_mean, y_var_total, lpd_mix,
+                         lpd_gauss, &pq);
+}
+
+extern "C" int ffvd_op_posterior_filter_particle_records_grouped(int kind, int G, int n_models, const double *Zs, int M, int P, int D,
+                                                                 const double *logvariances, const double *loglengthscales, const double *Xs,
+                                                                 const double *ctrl_fit, int C, int T, const double *log_Qs, double jitter,
+                                                                 int groups_per_pass, int q_mode, int R, const double *x0s, const double *S0s,
+                                                                 const double *ctrl_roll, int steps, const double *CC, const double *DD,
+                                                                 const double *noise_std, int J, const double *Y_obs, int records_per_pass,
+                                                                 FFVD_PARTICLE_PARAMS, double *m_pred, double *S_pred, double *m_filt,
+                                                                 double *S_filt, double *lpd, double *lpd_joint, double *y_mean,
+                                                                 double *y_var_total, double *lpd_mix, double *lpd_gauss, double *ess,
+                                                                 double *log_evidence, double *particles, int *ancestors, double *U_means) {
+    FFVD_PARTICLE_REQ;
+    return records_posterior("ffvd_op_posterior_filter_particle_records_grouped", MG_METHOD_PARTICLE, kind, G, n_models, Zs, M, P, D, logvariances,
+                             loglengthscales, Xs, ctrl_fit, C, T, log_Qs, jitter, groups_per_pass, q_mode, R, x0s, S0s, ctrl_roll, steps, CC, DD,
+                             noise_std, J, Y_obs, records_per_pass, m_pred, S_pred, m_filt, S_filt, nullptr, lpd, lpd_joint, nullptr, nullptr,
+                             y_mean, y_var_total, lpd_mix, lpd_gauss, U_means, &pq);
+}
+#undef FFVD_PARTICLE_PARAMS
+#undef FFVD_PARTICLE_REQ
 #undef FFVD_RECORDS_GIVEN_PARAMS
 #undef FFVD_RECORDS_GIVEN_ARGS
 #undef FFVD_RECORDS_POSTERIOR_PARAMS

@@ -638,9 +638,42 @@ class DGPSSM:
         return DGPSSM._filter_records(self, "filter_records_cubature", "filter_cubature_records_grouped", Y_records, control_records, lengths,
                                       x0, S0, smooth, q_mode, Y_train_std, records_per_pass)
 
-    def _filter_records(self, who, fn, Y_records, control_records, lengths, x0, S0, smooth, q_mode, Y_train_std, records_per_pass):
-        """The body of `filter_records` and `filter_records_cubature` (called through the class, as `_filter_heldout`): `fn` names the
-        prediction-level function of the explicit form, "posterior_" + fn the fused one."""
+    def filter_records_particle(self, Y_records, control_records=None, *, num_particles=256, lengths=None, x0=None, S0=None,
+                                q_mode="reference", Y_train_std=1.0, records_per_pass=0, seed=None, noise="shared", return_particles=False):
+        """`filter_records` with a bootstrap particle filter of `num_particles` particles per (chain, record) in place of a Gaussian
+        rule: the arbiter of the three Gaussian filters -- exact as the particle count grows, with the unbiased SMC estimate
+        `log_evidence` (S, R) of the held-out evidence and the effective sample size `ess` per row.
+        prediction.filter_particle_records_grouped has the method and the dict that is returned (no smoothing: particle smoothing is
+        not built).  The draws come from np.random.default_rng(seed), or from the model's own generator when seed is None.  noise:
+        "shared" -- one set of draws (steps, N, D) for every chain and record (common random numbers; each track's estimator stays
+        unbiased); "per_record" -- one set per record, shared by the chains; "independent" -- one per (chain, record), refused with
+        the byte count when the draws would exceed 1 GiB.  The checks, the start (x0, S0) and the two forms (collapsed U: ONE
+        `posterior_filter_particle_records_grouped` call; explicit U: `kernel_pre_cal` once, then `filter_particle_records_grouped`)
+        are `filter_records`'; R = 1 is a valid single-record call."""
+        who = "filter_records_particle"
+        if noise not in ("shared", "per_record", "independent"):
+            raise ValueError(f"{who}: noise: expected \"shared\", \"per_record\" or \"independent\", got {noise!r}")
+        N = num_particles
+        if isinstance(N, bool) or not isinstance(N, (int, np.integer)) or not 2 <= N <= 2048:
+            raise ValueError(f"{who}: num_particles: expected an integer in [2, 2048], got {num_particles!r}")
+        shape = np.shape(Y_records)
+        if len(shape) != 3 or shape[0] < 1 or shape[1] < 1:
+            raise ValueError(f"{who}: Y_records: expected (R, steps, {self.Y.shape[1]}), got {shape}")
+        S, D, (R, steps) = self.num_chains, self.output_dim, shape[:2]
+        lead = {"shared": (), "per_record": (R,), "independent": (S, R)}[noise]
+        nbytes = 8 * int(np.prod(lead, dtype=np.int64)) * (steps * N * D + steps + (N * D if S0 is not None else 0))
+        if noise == "independent" and nbytes > 2 ** 30:
+            raise ValueError(f"{who}: noise=\"independent\" needs {nbytes} bytes of draws, more than 1 GiB: use \"per_record\" or \"shared\"")
+        rng = np.random.default_rng(seed) if seed is not None else self._rng
+        draws = dict(eps=rng.standard_normal(lead + (steps, N, D)), unif=rng.random(lead + (steps,)),
+                     xi0=None if S0 is None else rng.standard_normal(lead + (N, D)), return_particles=return_particles)
+        return DGPSSM._filter_records(self, who, "filter_particle_records_grouped", Y_records, control_records, lengths, x0, S0, None, q_mode,
+                                      Y_train_std, records_per_pass, draws)
+
+    def _filter_records(self, who, fn, Y_records, control_records, lengths, x0, S0, smooth, q_mode, Y_train_std, records_per_pass, draws=None):
+        """The body of `filter_records`, `filter_records_cubature` and `filter_records_particle` (called through the class, as
+        `_filter_heldout`): `fn` names the prediction-level function of the explicit form, "posterior_" + fn the fused one; draws: the
+        particle filter's eps, unif, xi0 and return_particles (it has no `smooth`)."""
         from . import conditionals_multi_output as cmo
         from . import prediction as pr
         if q_mode not in cmo.Q_MODES:
@@ -666,13 +699,19 @@ class DGPSSM:
             return np.broadcast_to(v, (S, R) + tail)
         x0s, S0s = spread(x0, (D,), "x0"), spread(S0, (D, D), "S0")
         kw = dict(lengths=lengths, S0s=S0s, q_mode=q_mode, smooth=smooth, Y_train_std=Y_train_std, records_per_pass=records_per_pass)
+        tail = ()
+        if draws is not None:                                     # the particle filter: eps and unif follow log_Rchols, no `smooth`
+            del kw["smooth"]
+            tail = (draws["eps"], draws["unif"])
+            kw.update(xi0=draws["xi0"], return_particles=draws["return_particles"])
         if self.U_collapse:
             return getattr(pr, "posterior_" + fn)(lay.Z, lay.kernel, [self._X_chains[s_] for s_ in range(S)], self.Q, self.control_inputs,
-                                                  control_records, Y, lik.CC, lik.DD, lik.log_Rchols, x0s=x0s, **kw)
+                                                  control_records, Y, lik.CC, lik.DD, lik.log_Rchols, *tail, x0s=x0s, **kw)
         Lm = cmo.kernel_pre_cal(lay.Z, lay.kernel)
         if x0s is None:
             x0s = np.broadcast_to(np.stack([self._X_chains[s_][-1] for s_ in range(S)])[:, None, :], (S, R, D))
-        return getattr(pr, fn)(Lm, lay.Z, lay.kernel, [lay.U] * S, None, x0s, control_records, Y, self.Q, lik.CC, lik.DD, lik.log_Rchols, **kw)
+        return getattr(pr, fn)(Lm, lay.Z, lay.kernel, [lay.U] * S, None, x0s, control_records, Y, self.Q, lik.CC, lik.DD, lik.log_Rchols, *tail,
+                               **kw)
 
     def forecast_heldout(self, Y_test, control_inputs=None, horizon=10, *, stride=1, origins=None, x0=None, S0=None, q_mode="reference",
                          Y_train_std=1.0, return_tracks=False):

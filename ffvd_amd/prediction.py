@@ -928,6 +928,157 @@ def posterior_filter_cubature_records_grouped(Zs, kerns, Xs, Qs, control_inputs,
                                      Y_train_std, jitter, groups_per_pass, records_per_pass)
 
 
+PARTICLE_MIN_N, PARTICLE_MAX_N = 2, 2048
+PARTICLE_KEYS = ("m_pred", "S_pred", "m_filt", "S_filt", "lpd", "lpd_joint", "predict_y", "predict_y_var_total", "lpd_mix", "lpd_gauss", "ess")
+
+
+def _particle_layout(who, name, x, tail, G, R):
+    """One of the three layouts of a draw array: tail (shared by groups and records), (R,) + tail (shared by the groups) or
+    (G, R) + tail.  Returns the contiguous array and its (group, record) strides in doubles (0 = shared)."""
+    a = np.asarray(x, dtype=np.float64)
+    inner = int(np.prod(tail, dtype=np.int64))
+    if a.shape == tuple(tail):
+        sg, sr = 0, 0
+    elif a.shape == (R,) + tuple(tail):
+        sg, sr = 0, inner
+    elif a.shape == (G, R) + tuple(tail):
+        sg, sr = R * inner, inner
+    else:
+        raise ValueError(f"{who}: {name}: expected {tuple(tail)}, {(R,) + tuple(tail)} or {(G, R) + tuple(tail)}, got {a.shape}")
+    if not np.all(np.isfinite(a)):
+        raise ValueError(f"{who}: {name}: every draw must be finite")
+    return np.ascontiguousarray(a), sg, sr
+
+
+def _pack_particles(who, G, R, steps, D, eps, unif, xi0, with_S0, return_particles):
+    """Shape and value checks of the draws of `filter_particle_records_grouped` (before the library is loaded): N from eps, the three
+    layouts of eps / unif / xi0, unif in [0, 1), xi0 exactly when S0s is given.  Returns N and the arguments N .. xi0_stride_r."""
+    e = np.asarray(eps, dtype=np.float64)
+    if e.ndim not in (3, 4, 5) or e.shape[-1] != D:
+        raise ValueError(f"{who}: eps: expected ({steps}, N, {D}), ({R}, {steps}, N, {D}) or ({G}, {R}, {steps}, N, {D}), got {e.shape}")
+    N = e.shape[-2]
+    if not PARTICLE_MIN_N <= N <= PARTICLE_MAX_N:
+        raise ValueError(f"{who}: eps: the number of particles N must lie in [{PARTICLE_MIN_N}, {PARTICLE_MAX_N}], got {N}")
+    e, eg, er = _particle_layout(who, "eps", e, (steps, N, D), G, R)
+    u, ug, ur = _particle_layout(who, "unif", unif, (steps,), G, R)
+    if np.any(u < 0.0) or np.any(u >= 1.0):
+        raise ValueError(f"{who}: unif: every uniform must lie in [0, 1)")
+    if with_S0 != (xi0 is not None):
+        raise ValueError(f"{who}: xi0: the start draws ({N}, {D}) are needed exactly when S0s is given (S0s "
+                         f"{'given' if with_S0 else 'None'}, xi0 {'None' if xi0 is None else 'given'})")
+    x, xg, xr = (None, 0, 0) if xi0 is None else _particle_layout(who, "xi0", xi0, (N, D), G, R)
+    if not isinstance(return_particles, (bool, np.bool_)):
+        raise ValueError(f"{who}: return_particles: expected a bool, got {return_particles!r}")
+    if G * R * steps * N * D >= 2 ** 31:
+        raise ValueError(f"{who}: G * R * steps * N * D = {G * R * steps * N * D} must stay below 2^31")
+    dp = _lib.dptr
+    return N, (N, dp(e), eg, er, dp(u), ug, ur, None if x is None else dp(x), xg, xr), (e, u, x)
+
+
+def _particle_call(m, G, R, steps, D, N, return_particles):
+    """Output arrays and the trailing arguments (m_pred .. ancestors) of the two particle entry points."""
+    J, V, dp = m["J"], G * R * steps, _lib.dptr
+    out = dict(m_pred=np.empty((G, R * steps, D)), S_pred=np.empty((G, R * steps, D, D)), m_filt=np.empty((G, R * steps, D)),
+               S_filt=np.empty((G, R * steps, D, D)), lpd=np.empty((G, R * steps, J)), lpd_joint=np.empty((G, R * steps)),
+               predict_y=np.empty((R * steps, J)), predict_y_var_total=np.empty((R * steps, J)), lpd_mix=np.empty((R * steps, J)),
+               lpd_gauss=np.empty((R * steps, J)), ess=np.empty((G, R * steps)))
+    extra = dict(log_evidence=np.empty((G, R)))
+    if return_particles:
+        extra.update(particles=np.empty((G, R, steps, N, D)), ancestors=np.empty((G, R, steps, N), dtype=np.int32))
+    import ctypes
+    anc = extra["ancestors"].ctypes.data_as(ctypes.POINTER(ctypes.c_int)) if return_particles else None
+    args = tuple(dp(out[k]) for k in PARTICLE_KEYS) + (dp(extra["log_evidence"]), dp(extra["particles"]) if return_particles else None, anc)
+    return out, extra, args
+
+
+def _particle_dict(r, G, out, extra, Y_train_std):
+    """`_records_dict` plus log_evidence (G, R) and, when asked for, particles / ancestors: NaN (ancestors -1) at and beyond a
+    record's length."""
+    res = _records_dict(r, G, out, Y_train_std)
+    res["log_evidence"] = extra["log_evidence"]
+    dead = ~r["live"]
+    if "particles" in extra:
+        extra["particles"][:, dead] = np.nan
+        extra["ancestors"][:, dead] = -1
+        res.update(particles=extra["particles"], ancestors=extra["ancestors"])
+    return res
+
+
+def filter_particle_records_grouped(Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_records, Y_records, Qs, CC, DD, log_Rchols,
+                                    eps, unif, *, xi0=None, lengths=None, S0s=None, q_mode="reference", Y_train_std=1.0, records_per_pass=0,
+                                    return_particles=False):
+    """Bootstrap particle filtering of R observed records through G posteriors in ONE call (`ffvd_op_filter_particle_records_grouped`):
+    the fourth records filter, and the only one that does not project the predictive state onto a Gaussian -- it is exact as N grows,
+    keeps a non-Gaussian (multi-modal) filtered state and gives the unbiased SMC estimate of the held-out evidence per chain and
+    record.  Tracks (group g, record r), passes, `lengths`, NaN = unobserved, timing (the state after step i emits row i), emission,
+    staging and q_mode are `filter_records_grouped`'s.  Every random draw is the caller's: eps (steps, N, D), (R, steps, N, D) or
+    (G, R, steps, N, D) standard normal (the first two are common random numbers across groups, or across groups and records: each
+    track's estimator stays unbiased), unif (steps,), (R, steps) or (G, R, steps) in [0, 1), xi0 (N, D), (R, N, D) or (G, R, N, D)
+    standard normal, needed exactly when S0s is given.  N = eps.shape[-2], 2 <= N <= 2048.
+    Per track: X_0i = x0 + L0 xi0_i (L0 the unpivoted lower Cholesky factor of S0, a pivot <= 0 gives a zero column; S0s None: all at
+    x0).  Step t: with (m_i, v_i) the GP conditional of the group at [X_ti, c_t], X^-_i = X_ti + m_i + eps[t, i] sqrt(v_i + Q);
+    m_pred, S_pred: mean and centred covariance of the X^-; l_ij = log N(y_tj; CC[:, j] . X^-_i + DD_j, sd_j^2), lpd[t, j] =
+    log mean_i exp l_ij (NaN where unobserved), L_i the sum of l_ij over the observed j, lpd_joint[t] = log mean_i exp L_i (NaN for a
+    row with nothing observed); W_i = exp(L_i - max L), m_filt / S_filt the W-weighted mean and centred covariance, ess =
+    (sum W)^2 / sum W^2; systematic resampling with unif[t], a_i = min(#{k: cdf_k <= (unif[t] + i) / N cdf_{N-1}}, N - 1), only for
+    a row with an observed entry (otherwise the particles are kept, m_filt = m_pred and S_filt = S_pred bit for bit, ess = N).  No
+    adaptive resampling.  There is no smoothing (no `smooth` parameter, no `cross`): particle smoothing is not built.
+    Returns the dict of `filter_records_grouped` without cross, m_smooth and S_smooth, plus ess (G, R, steps) and log_evidence (G, R),
+    the sum of lpd_joint over the rows with an observation: the SMC estimate of log p(y) of that record under that chain.  Pooled
+    with EQUAL weights, (R, steps, J): predict_y, predict_y_var_total and lpd_gauss from (m_pred, S_pred) as the siblings; lpd_mix =
+    log mean_g exp(lpd[g]), the density of the mixture of all G N particles' emissions.  With return_particles also particles
+    (G, R, steps, N, D), the X^-, and ancestors (G, R, steps, N) int32.  Every array is NaN (ancestors -1) at and beyond a record's
+    length.  A track's arrays are bit-identical whatever the other groups, the other records, their order and records_per_pass are
+    (draws permuted with them); every covariance is exactly symmetric ("Particle filtering").  SquaredExponential
+    kernels only; R = 1 is a valid single-record call."""
+    who = "filter_particle_records_grouped"
+    shape = np.shape(Y_records)
+    if len(shape) != 3 or shape[0] < 1 or shape[1] < 1:
+        raise ValueError(f"{who}: Y_records: expected (R, steps, J) with at least one record and one row, got {shape}")
+    G = len(U_vals)
+    if x0s is None:
+        raise ValueError(f"{who}: x0s: the start means are needed, ({shape[0]}, D) or ({G}, {shape[0]}, D)")
+    xl, ci = _records_placeholders(G, Zs, kerns, shape[1])
+    a = _pack_moment_groups(who, Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, xl, ci, 0, shape[1], Qs, None, q_mode)
+    D, args = a["D"], a["args"]
+    r = _pack_records(who, G, D, args[16], x0s, control_records, Y_records, lengths, S0s, records_per_pass)
+    R, steps = r["R"], r["steps"]
+    N, pargs, keep = _pack_particles(who, G, R, steps, D, eps, unif, xi0, r["S0"] is not None, return_particles)
+    m = _pack_summary(who, D, R * steps, CC, DD, log_Rchols, r["Y"].reshape(R * steps, r["J"]))
+    out, extra, oargs = _particle_call(m, G, R, steps, D, N, bool(return_particles))
+    dp = _lib.dptr
+    opt = lambda x: None if x is None else dp(x)
+    rc = _lib.load().ffvd_op_filter_particle_records_grouped(*args[:13], R, dp(r["x0"]), opt(r["S0"]), opt(r["ctrl"]), *args[16:], dp(m["CC"]),
+                                                             dp(m["DD"]), dp(m["sd"]), m["J"], dp(m["Y"]), r["rpp"], *pargs, *oargs)
+    _lib.check(rc, None, who)
+    return _particle_dict(r, G, out, extra, Y_train_std)
+
+
+def posterior_filter_particle_records_grouped(Zs, kerns, Xs, Qs, control_inputs, control_records, Y_records, CC, DD, log_Rchols, eps, unif, *,
+                                              xi0=None, lengths=None, x0s=None, S0s=None, q_mode="reference", Y_train_std=1.0, jitter=JITTER,
+                                              groups_per_pass=0, records_per_pass=0, return_particles=False):
+    """The collapsed posterior of G groups and the filter of `filter_particle_records_grouped` in ONE call
+    (`ffvd_op_posterior_filter_particle_records_grouped`): what `conditionals_multi_output.collapse_u_mean_grouped` followed by
+    `filter_particle_records_grouped` computes, without the posteriors leaving the device.  The model and start arguments are
+    `posterior_filter_records_grouped`'s (x0s None: every record of group g starts at Xs[g][-1]); eps, unif, xi0, return_particles and
+    the returned dict are `filter_particle_records_grouped`'s."""
+    who = "posterior_filter_particle_records_grouped"
+    a = _pack_posterior_moment(who, Zs, kerns, Xs, Qs, control_inputs, 0, 0, None, q_mode, jitter, groups_per_pass)
+    G, D, args = a["G"], a["D"], a["args"]
+    r = _pack_records(who, G, D, args[11], x0s, control_records, Y_records, lengths, S0s, records_per_pass)
+    R, steps = r["R"], r["steps"]
+    N, pargs, keep = _pack_particles(who, G, R, steps, D, eps, unif, xi0, r["S0"] is not None, return_particles)
+    m = _pack_summary(who, D, R * steps, CC, DD, log_Rchols, r["Y"].reshape(R * steps, r["J"]))
+    out, extra, oargs = _particle_call(m, G, R, steps, D, N, bool(return_particles))
+    dp = _lib.dptr
+    opt = lambda x: None if x is None else dp(x)
+    rc = _lib.load().ffvd_op_posterior_filter_particle_records_grouped(*args[:17], R, opt(r["x0"]), opt(r["S0"]), opt(r["ctrl"]), steps,
+                                                                       dp(m["CC"]), dp(m["DD"]), dp(m["sd"]), m["J"], dp(m["Y"]), r["rpp"],
+                                                                       *pargs, *oargs, None)
+    _lib.check(rc, None, who)
+    return _particle_dict(r, G, out, extra, Y_train_std)
+
+
 def _pack_forecast(who, n, horizon, origins=None, stride=1, model=None):
     """Horizon and forecast origins of a record of n rows, checked (before the library is loaded): 1 <= horizon <= n - 1; origins
     None: range(0, n - horizon, stride) with stride >= 1, else strictly ascending integers in [0, n - 1 - horizon], so that every

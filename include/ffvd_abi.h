@@ -846,6 +846,65 @@ int  ffvd_op_posterior_filter_cubature_records_grouped(int kind, int G, int n_mo
                                                        double *y_mean, double *y_var_total, double *lpd_mix, double *lpd_gauss,
                                                        double *U_means);
 
+/* Bootstrap particle filtering of R observed records in one call: the tracks, passes, timing (the state after step i emits row i of
+ * Y_obs), emission, NaN = unobserved convention, staging and q_mode of ffvd_op_filter_records_grouped with N particles per track in
+ * place of one Gaussian.  Every random draw is the caller's (no device RNG): eps (standard normal, steps x N x D per track), unif
+ * (in [0, 1), steps per track) and xi0 (standard normal, N x D per track; needed exactly when S0s is given) are read through a group
+ * and a record stride in doubles, each 0 (shared: common random numbers) or the stride of a contiguous [G or 1][R or 1][...] array.
+ * Per track:
+ *   start      X_0i = x_last + L0 xi0_i, L0 the lower Cholesky factor of S0 without pivoting (a pivot <= 0 gives a zero column);
+ *              S0s NULL: every particle starts at x_last
+ *   propagate  with (m_i, v_i) the mean and variance of the GP conditional of the group at [X_ti, c_t]:
+ *              X^-_i = X_ti + m_i + eps[t, i] sqrt(v_i + Q) per dim
+ *   moments    m_pred[t] = sum_i X^-_i / N,  S_pred[t] = sum_i (X^-_i - m_pred)(X^-_i - m_pred)^T / N (centred, exactly symmetric)
+ *   densities  l_ij = log N(y_tj; CC[:, j] . X^-_i + DD_j, noise_std_j^2);  lpd[t, j] = log(sum_i exp l_ij / N), NaN where y_tj is NaN;
+ *              L_i = sum over the observed j of l_ij;  lpd_joint[t] = log(sum_i exp L_i / N), NaN for a row with nothing observed
+ *   filtered   W_i = exp(L_i - max L);  m_filt[t], S_filt[t]: the W-weighted mean and centred covariance;  ess[t] = (sum W)^2 / sum W^2;
+ *              a row with nothing observed: W = 1, m_filt = m_pred and S_filt = S_pred bit for bit, ess = N
+ *   resample   systematic, one uniform per track and step, only for a row with an observed entry: cdf_k = W_0 + .. + W_k,
+ *              a_i = min(#{k: cdf_k <= (unif[t] + i) / N cdf_{N-1}}, N - 1), X_{t+1,i} = X^-_{a_i}; otherwise a_i = i.  The index is
+ *              clamped into [0, N) before it addresses anything, whatever the weights are.  No adaptive resampling.
+ * log_evidence (G x R) is the sum of lpd_joint over the rows that have an observation: the SMC estimate of log p(y) of that record
+ * under that group.  Pooled over the groups with equal weights (R x steps x J): y_mean, y_var_total and lpd_gauss as
+ * ffvd_op_filter_records_grouped on (m_pred, S_pred); lpd_mix = log mean_g exp(lpd[g]), the density of the mixture of all G * N
+ * particles' emissions.  There is no smoother and no cross-covariance (particle smoothing is not built).
+ * Outputs, each of which may be NULL: m_pred, m_filt (G x R x steps x D), S_pred, S_filt (.. x D x D), lpd (.. x J), lpd_joint, ess
+ * (G x R x steps), the pooled four, log_evidence, particles (G x R x steps x N x D: the X^-) and ancestors (G x R x steps x N).
+ * The kernel rows of all particles of all tracks that share a Gamma are one dense product on the fp64 matrix cores (the product of
+ * ffvd_op_forecast_linear_grouped, N rows of K per track and dim).  A track does not depend on the other groups, the other records,
+ * their order or records_per_pass (bit for bit).
+ * Limits: those of ffvd_op_filter_records_grouped; 2 <= N <= 2048; G * R * steps * N * D < 2^31; the N kernel rows of one record per
+ * group must fit the scratch of a pass (FFVD_EINVAL with a message that names the largest N that fits); SE kernel only.
+ * G = 0, R = 0 or steps = 0: FFVD_OK, nothing is touched. */
+int  ffvd_op_filter_particle_records_grouped(int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M,
+                                             int P, int D, const double *logvariances, const double *loglengthscales, const double *fs,
+                                             const double *const *q_sqrts, int q_mode, int R, const double *x_lasts, const double *S0s,
+                                             const double *ctrl, int C, int steps, const double *log_Qs, const double *CC,
+                                             const double *DD, const double *noise_std, int J, const double *Y_obs,
+                                             int records_per_pass, int N, const double *eps, long long eps_stride_g,
+                                             long long eps_stride_r, const double *unif, long long unif_stride_g,
+                                             long long unif_stride_r, const double *xi0, long long xi0_stride_g, long long xi0_stride_r,
+                                             double *m_pred, double *S_pred, double *m_filt, double *S_filt, double *lpd,
+                                             double *lpd_joint, double *y_mean, double *y_var_total, double *lpd_mix, double *lpd_gauss,
+                                             double *ess, double *log_evidence, double *particles, int *ancestors);
+
+/* ffvd_op_posterior_grouped followed by ffvd_op_filter_particle_records_grouped WITHOUT the posteriors leaving the device: the model
+ * and start arguments of ffvd_op_posterior_filter_records_grouped (x0s NULL: every record of group g starts at the last row of
+ * Xs[g]), the particle arguments and outputs of the call above. */
+int  ffvd_op_posterior_filter_particle_records_grouped(int kind, int G, int n_models, const double *Zs, int M, int P, int D,
+                                                       const double *logvariances, const double *loglengthscales, const double *Xs,
+                                                       const double *ctrl_fit, int C, int T, const double *log_Qs, double jitter,
+                                                       int groups_per_pass, int q_mode, int R, const double *x0s, const double *S0s,
+                                                       const double *ctrl_roll, int steps, const double *CC, const double *DD,
+                                                       const double *noise_std, int J, const double *Y_obs, int records_per_pass,
+                                                       int N, const double *eps, long long eps_stride_g, long long eps_stride_r,
+                                                       const double *unif, long long unif_stride_g, long long unif_stride_r,
+                                                       const double *xi0, long long xi0_stride_g, long long xi0_stride_r,
+                                                       double *m_pred, double *S_pred, double *m_filt, double *S_filt, double *lpd,
+                                                       double *lpd_joint, double *y_mean, double *y_var_total, double *lpd_mix,
+                                                       double *lpd_gauss, double *ess, double *log_evidence, double *particles,
+                                                       int *ancestors, double *U_means);
+
 /* Rolling-origin multi-step forecasts in one call: ffvd_op_filter_grouped (same arguments, same outputs, each of which may be NULL),
  * then from every origin o = origins[b] (n_origins rows of the record, strictly ascending, 0 <= o <= steps - 1 - horizon) `horizon`
  * steps of ffvd_op_moment_grouped started at the FILTERED state of row o, N(m_filt[g][o], S_filt[g][o]), with the control rows
