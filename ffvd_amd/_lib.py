@@ -42,6 +42,8 @@ class FfvdGrads(C.Structure):
 _dp = C.POINTER(C.c_double)
 # N, then eps, unif and xi0 each with its group and record stride (the particle filter's draws)
 _PARTICLE_DRAWS = [C.c_int] + [_dp, C.c_longlong, C.c_longlong] * 3
+# N, then eps, unif and xi0 each with its group stride, then eps_fc with its group and origin stride (the particle forecasts' draws)
+_PARTICLE_FC_DRAWS = [C.c_int] + [_dp, C.c_longlong] * 3 + [_dp, C.c_longlong, C.c_longlong]
 _SIGNATURES = {
     "ffvd_create": (C.c_int, [C.POINTER(FfvdConfig), C.POINTER(C.c_void_p)]),
     "ffvd_destroy": (C.c_int, [C.c_void_p]),
@@ -203,6 +205,15 @@ _SIGNATURES = {
                                                               C.c_int, C.c_int, _dp, C.c_double, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int,
                                                               _dp, _dp, _dp, C.c_int, _dp] + [_dp] * 14 +
                                                              [C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int] + [_dp] * 6),
+    "ffvd_op_forecast_particle_grouped": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), _dp, C.c_int, C.c_int, C.c_int, _dp, _dp,
+                                                    _dp, C.POINTER(C.c_void_p), C.c_int, _dp, _dp, _dp, C.c_int, C.c_int, _dp,
+                                                    _dp, _dp, _dp, C.c_int, _dp] + [_dp] * 13 +
+                                                   [C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int] + _PARTICLE_FC_DRAWS + [_dp] * 10),
+    "ffvd_op_posterior_forecast_particle_grouped": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp,
+                                                              C.c_int, C.c_int, _dp, C.c_double, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int,
+                                                              _dp, _dp, _dp, C.c_int, _dp] + [_dp] * 14 +
+                                                             [C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int] + _PARTICLE_FC_DRAWS +
+                                                             [_dp] * 10),
     "ffvd_op_moment_summary": (C.c_int, [_dp, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_int,
                                          _dp, _dp, _dp, _dp, _dp]),
     "ffvd_op_pg_sweep": (C.c_int, [C.c_int, _dp, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, _dp, C.c_int,

@@ -193,6 +193,29 @@ void launch_mg_prec_step(hipStream_t stream, const MomentGroupArgs &a, const Mom
 void launch_mg_cfan_step(hipStream_t stream, const MomentGroupArgs &a, const MomentFanArgs &f, const MomentLinearFanArgs &l, double *off,
                          int t);
 
+// Particle forecasts (moment_particle_fan.hip; DESIGN.md section 9, "Particle forecasts"): the fan's tracks and indexing (MomentFanArgs)
+// with the particle propagation above and no weighting or resampling.  A track starts from the particles the filter carries after
+// the row of its origin: `particles` and `ancestors` are the filter's device stacks of the one record, [groups][n][N][D] and
+// [groups][n][N].  MomentGroupArgs as for the linearised forecasts (`state` is not read); MomentFilterArgs gives the emission and the
+// record's Y [n][J] (its output stacks are not touched); MomentLinearFanArgs is mg_lfan_layout with Bp = N * (tracks per group of the
+// pass), msum is not read.  The forecast draws eps_fc [..][h][N][D] are indexed through a group and an origin stride in doubles, each
+// of which may be 0 (common random numbers).  The product kernel runs unchanged.
+// Limits: those of the particle records with origins for records (mg_prec_records_per_pass);  G * B * h * N * D < 2^31.
+struct MomentParticleFanArgs {
+    int N;
+    const double *eps_fc;
+    long long eps_g, eps_b;
+    const double *particles;         // [groups][n][N][D]: the X^- of the filter
+    const int *ancestors;            // [groups][n][N]
+    double *xstate;                  // [2][tracks][N][D]: the particles (step parity)
+    double *pmean;                   // [tracks][D][N]: the conditional mean at every particle
+    double *lpd_fc;                  // [G][B][h][J]: log mean_i N(y; .) per output, NaN where the target is unobserved
+    double *fc_particles;            // [G][B][h][N][D] or nullptr
+};
+// launch t of h + 1: the state kernel, then (t < h) the rows kernel and the product kernel
+void launch_mg_pfan_step(hipStream_t stream, const MomentGroupArgs &a, const MomentFilterArgs &f, const MomentFanArgs &fn,
+                         const MomentLinearFanArgs &l, const MomentParticleFanArgs &p, int t);
+
 struct MomentSummaryArgs {
     int G, steps, D, J, n_test;
     const double *m, *S;             // [G][steps][D], [G][steps][D][D]

@@ -622,7 +622,7 @@ bool mg_scalars_ok(int kind, int G, int n_models, int M, int P, int D, int C, in
            (steps == 0 || G <= ((1LL << 31) - 1) / steps / D / D);
 }
 // the propagation rule of the filter's launches (mg_run)
-enum { MG_METHOD_MOMENT = 0, MG_METHOD_LINEAR = 1, MG_METHOD_CUBATURE = 2, MG_METHOD_PARTICLE = 3 };    // (cubature: the records calls and the forecasts; particle: the records calls)
+enum { MG_METHOD_MOMENT = 0, MG_METHOD_LINEAR = 1, MG_METHOD_CUBATURE = 2, MG_METHOD_PARTICLE = 3 };    // (cubature and particle: the records calls and the forecasts)
 // the trailing summary block of the entry points: asked for when anything in it is given
 bool mg_summary_wanted(const SummaryReq &q) {
     return q.CC || q.DD || q.noise_std || q.J != 0 || q.Y_test || q.n_test != 0 || q.y_mean || q.y_var || q.y_var_total || q.lpd || q.lpd_gauss;
@@ -747,12 +747,24 @@ struct BetaGamma {
 // the same rule: moment_linear_fan.hip, two launches per step and pass) or, with a forecast request only, MG_METHOD_CUBATURE (the
 // filter is the cubature records launch with one record, moment_cubature_records.hip: [G][1][steps] stacks are [G][steps] stacks;
 // the tracks are moment_cubature_fan.hip's; K, the partials, the mean sums and the offsets are sized for the larger stage, the tracks').
+// MG_METHOD_PARTICLE, with a forecast request and a particle forecast request only: the body is mg_particle_fc_run, beside the particle
+// records' driver.
 // dW: [n_models * D] slots of Mp x Mp (upper triangular, zero padded); dq: nullptr, or [G] (q_mode 0) / [G * D] (q_mode 1) slots of
 // Mp x Mp; hv: variance / len per (model, dim).
+struct ParticleFcReq;
+int mg_particle_fc_run(Scratch &sc, const std::string &who, int G, int nm, int M, int P, int D, int C, int steps, const HyperView &hv,
+                       const double *dZ, const double *dW, const double *dq, int q_mode, const double *dU, const double *dxl, const double *dS0,
+                       const double *dlq, const double *dctrl, double *m_x, double *S_x, const FilterReq &flt, const ForecastReq &fc,
+                       const ParticleFcReq &pf);
 int mg_run(Scratch &sc, const std::string &who, int G, int nm, int M, int P, int D, int C, int steps, const HyperView &hv, const double *dZ,
            const double *dW, const double *dq, int q_mode, const double *dU, const double *dxl, const double *dS0, const double *dlq,
            const double *dctrl, double *m_x, double *S_x, const SummaryReq *sum, const FilterReq *flt, const ForecastReq *fc = nullptr,
-           int method = MG_METHOD_MOMENT) {
+           int method = MG_METHOD_MOMENT, const ParticleFcReq *pf = nullptr) {
+    if (method == MG_METHOD_PARTICLE) {
+        if (!(flt && fc && pf))
+            return set_error(nullptr, FFVD_EINVAL, who + ": bad argument (the particle rule is built for the records filter and the forecasts only)");
+        return mg_particle_fc_run(sc, who, G, nm, M, P, D, C, steps, hv, dZ, dW, dq, q_mode, dU, dxl, dS0, dlq, dctrl, m_x, S_x, *flt, *fc, *pf);
+    }
     const int Mp = round_up(M, NB), NS = (M + MG_SLAB - 1) / MG_SLAB;
     const bool linear = method == MG_METHOD_LINEAR, cub = method == MG_METHOD_CUBATURE;
     if (linear && !flt)
@@ -884,15 +896,18 @@ const char *const mg_linear_se_only = " (the linearised filter is built for the 
 const char *const mg_linear_fc_se_only =
     " (the linearised forecasts are built for the SE kernel only: their kernel rows and Jacobians are SE-ARD's)";
 const char *const mg_cubature_fc_se_only = " (the cubature forecasts are built for the SE kernel only: their kernel rows are SE-ARD's)";
+const char *const mg_particle_fc_se_only = " (the particle forecasts are built for the SE kernel only: their kernel rows are SE-ARD's)";
 const char *mg_fc_se_only(int method) {
-    return method == MG_METHOD_LINEAR ? mg_linear_fc_se_only : method == MG_METHOD_CUBATURE ? mg_cubature_fc_se_only : mg_se_only;
+    return method == MG_METHOD_LINEAR ? mg_linear_fc_se_only : method == MG_METHOD_CUBATURE ? mg_cubature_fc_se_only
+         : method == MG_METHOD_PARTICLE ? mg_particle_fc_se_only : mg_se_only;
 }
 
 // Posteriors given by the caller (also explicit-U models, SG-HMC samples of U: q_sqrts = NULL) through mg_run, scalars and pointers checked
 int mg_given_run(const std::string &who, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M, int P, int D,
                  const double *logvariances, const double *loglengthscales, const double *fs, const double *const *q_sqrts, int q_mode,
                  const double *x_lasts, const double *S0s, const double *ctrl, int C, int steps, const double *log_Qs, double *m_x,
-                 double *S_x, const SummaryReq *sum, const FilterReq *flt, const ForecastReq *fc = nullptr, int method = MG_METHOD_MOMENT) {
+                 double *S_x, const SummaryReq *sum, const FilterReq *flt, const ForecastReq *fc = nullptr, int method = MG_METHOD_MOMENT,
+                 const ParticleFcReq *pf = nullptr) {
     const size_t nK = (size_t)n_models * D, GD = (size_t)G * D, nq = given_nq(q_sqrts, q_mode, G, D);
     if (!given_tables_ok(Lm_inverse_seqs, nK, q_sqrts, nq)) return set_error(nullptr, FFVD_EINVAL, who + ": bad argument");
     OP_BEGIN(who);
@@ -904,7 +919,7 @@ int mg_given_run(const std::string &who, int G, int n_models, const double *cons
     OP_CHECK(dW && (!nq || dq) && dU && dxl && (!S0s || dS0) && dlq && (!C || dctrl) && gh.logs(sc) && gh.blocks(sc), who);
     gh.prep(sc.stream);
     return mg_run(sc, who, G, n_models, M, P, D, C, steps, gh.hv(), gh.dZ, dW, dq, q_mode, dU, dxl, dS0, dlq, dctrl, m_x, S_x, sum, flt, fc,
-                  method);
+                  method, pf);
 }
 
 // The collapsed posteriors of ffvd_op_posterior_grouped (base_model.py:243-256) through mg_run without leaving the device: L^-T is
@@ -912,7 +927,7 @@ int mg_given_run(const std::string &who, int G, int n_models, const double *cons
 // and the strict lower triangle); the start means are x0s or, without them, the last rows of Xs.
 int mg_posterior_run(const PgIn &in, int q_mode, const double *x0s, const double *S0s, const double *ctrl_roll, int steps, double *m_x,
                      double *S_x, double *U_means, const SummaryReq *sum, const FilterReq *flt, const ForecastReq *fc = nullptr,
-                     int method = MG_METHOD_MOMENT) {
+                     int method = MG_METHOD_MOMENT, const ParticleFcReq *pf = nullptr) {
     const std::string &who = in.who;
     OP_BEGIN(who);
     PgWork w{};
@@ -928,7 +943,7 @@ int mg_posterior_run(const PgIn &in, int q_mode, const double *x0s, const double
     launch_pg_pack(sc.stream, w.Kuu, 2 * mm, Mp, Mp, nK, 1, M, 1, dW, Mp, Mp, nK);
     if (!x0s) launch_pg_x_last(sc.stream, w.Xs, G, in.T, D, dxl);
     if (int rc = mg_run(sc, who, G, nm, M, in.P, D, C, steps, w.hv, dZ, dW, pg_q(w, q_mode), q_mode, w.U, dxl, dS0, w.log_Qs, dctrl, m_x, S_x,
-                        sum, flt, fc, method))
+                        sum, flt, fc, method, pf))
         return rc;
     if (U_means && !sc.download(U_means, w.U, GD * M * sizeof(double)))
         return set_error(nullptr, FFVD_EDEVICE, who + ": copying the results back failed");
@@ -1186,6 +1201,14 @@ int mg_particle_finish(Scratch &sc, const std::string &who, int G, int R, int st
     return FFVD_OK;
 }
 
+// a call whose single track per group does not fit K is refused with the largest N that fits
+int particle_fits(const std::string &who, int G, int nm, int D, int Mp, int upg, int N) {
+    const long long fit = mg_prec_max_particles(G, nm, D, Mp, upg);
+    if (N <= fit) return FFVD_OK;
+    return set_error(nullptr, FFVD_EINVAL, who + ": bad argument (the kernel rows of one record per group do not fit the scratch of a pass: "
+                     "the largest N that fits is " + std::to_string(fit / 128 * 128 > MG_PREC_MAXN ? MG_PREC_MAXN : fit) + ")");
+}
+
 // Operands on the device -> beta, Gamma (BetaGamma, once per call), the passes over the records (steps + 1 launch pairs each), the
 // smoother over all G * R tracks, the pooled summary per record and row, the downloads.  A sibling of mg_run's linear branch.
 // dxl: [G][R][D]; dS0: nullptr or [G][R][D][D]; dctrl: nullptr or [R][steps][C]; the other operands as mg_run's.
@@ -1200,12 +1223,8 @@ int mg_records_run(Scratch &sc, const std::string &who, int method, int G, int n
     const size_t nm_x = (size_t)V * steps * D, nS_x = nm_x * D, nlpd = (size_t)V * steps * J, nlj = (size_t)V * steps;
     const bool cub = method == MG_METHOD_CUBATURE, par = method == MG_METHOD_PARTICLE;
     const int nrow = cub ? mg_crec_rows(D) : par ? pq->N : 1;                          // rows of K per track
-    if (par) {
-        const long long fit = mg_prec_max_particles(G, nm, D, Mp, upg);
-        if (pq->N > fit)
-            return set_error(nullptr, FFVD_EINVAL, who + ": bad argument (the kernel rows of one record per group do not fit the scratch of a pass: "
-                             "the largest N that fits is " + std::to_string(fit / 128 * 128 > MG_PREC_MAXN ? MG_PREC_MAXN : fit) + ")");
-    }
+    if (par)
+        if (int rc = particle_fits(who, G, nm, D, Mp, upg, pq->N)) return rc;
     int Rp = cub ? mg_crec_records_per_pass(G, nm, D, Mp, upg, R) : par ? mg_prec_records_per_pass(G, nm, D, Mp, upg, R, pq->N)
                                                                         : mg_lfan_tracks_per_pass(G, nm, D, Mp, upg, R);
     if (rq.records_per_pass > 0 && rq.records_per_pass < Rp) Rp = rq.records_per_pass;
@@ -1281,6 +1300,134 @@ int mg_records_run(Scratch &sc, const std::string &who, int method, int G, int n
         return set_error(nullptr, FFVD_EDEVICE, who + ": copying the results back failed");
     OP_TRY(hipStreamSynchronize(sc.stream));
     return FFVD_OK;
+}
+
+// The particle request beside a ForecastReq (mg_run, MG_METHOD_PARTICLE): the filter's request with one record (its record strides
+// are 0), the forecast draws with their (group, origin) strides in doubles -- each 0 or the stride of a contiguous array -- and the
+// outputs the Gaussian fans do not have
+struct ParticleFcReq {
+    ParticleReq filter;
+    const double *eps_fc;                        // [G or 1][B or 1][h][N][D]
+    long long eps_fc_g, eps_fc_b;
+    double *fc_lpd;                              // [G][B][h][J] or NULL
+    double *fc_particles;                        // [G][B][h][N][D] or NULL
+    bool any_output() const { return filter.ess || filter.log_evidence || fc_lpd || fc_particles; }
+};
+// the checks of a particle forecast request that need no device: the filter's with R = 1, the strides and values of eps_fc,
+// G * B * h * N * D < 2^31
+bool particle_fc_ok(const ParticleFcReq &q, int G, int B, int h, int steps, int D, bool with_S0) {
+    if (q.filter.eps_r || q.filter.unif_r || q.filter.xi0_r || q.filter.particles || q.filter.ancestors) return false;
+    if (q.filter.N < MG_PREC_MINN || q.filter.N > MG_PREC_MAXN) return false;
+    const long long ne = (long long)h * q.filter.N * D;
+    if (!particle_strides_ok(q.eps_fc_g, q.eps_fc_b, ne, B) || !q.eps_fc) return false;
+    if ((long long)G * B > ((1LL << 31) - 1) / h / q.filter.N / D) return false;          // (before any array is read)
+    if (!particle_ok(q.filter, G, 1, steps, D, with_S0, false)) return false;
+    const size_t n = particle_extent(q.eps_fc_g, q.eps_fc_b, ne, G, B);
+    for (size_t e = 0; e < n; ++e)
+        if (!std::isfinite(q.eps_fc[e])) return false;
+    return true;
+}
+
+// mg_run with MG_METHOD_PARTICLE: the particle filter over the one record (the records launch with R = 1, in the buffers of the
+// tracks; its device `particles` and `ancestors` stacks are always kept: the tracks start from them), then the passes over the origins
+// (moment_particle_fan.hip: h + 1 launch triples each), the pooled summary of the forecast stacks on the device, the downloads, and on
+// the host fc_lpd_mix = log mean_g exp(fc_lpd[g]) in ascending g, as mg_particle_finish forms the filter's.
+int mg_particle_fc_run(Scratch &sc, const std::string &who, int G, int nm, int M, int P, int D, int C, int steps, const HyperView &hv,
+                       const double *dZ, const double *dW, const double *dq, int q_mode, const double *dU, const double *dxl, const double *dS0,
+                       const double *dlq, const double *dctrl, double *m_x, double *S_x, const FilterReq &flt, const ForecastReq &fc,
+                       const ParticleFcReq &pf) {
+    const int Mp = round_up(M, NB), J = flt.J, upg = dq ? 1 : 0, N = pf.filter.N, B = fc.n_origins, h = fc.horizon;
+    const size_t nm_x = (size_t)G * steps * D, nS_x = nm_x * D, nlpd = (size_t)G * steps * J, nlj = (size_t)G * steps;
+    const size_t nm_fc = (size_t)G * B * h * D, nS_fc = nm_fc * D, nl_fc = (size_t)G * B * h * J, BH = (size_t)B * h;
+    if (int rc = particle_fits(who, G, nm, D, Mp, upg, N)) return rc;
+    int Bp = mg_prec_records_per_pass(G, nm, D, Mp, upg, B, N);
+    if (fc.tracks_per_pass > 0 && fc.tracks_per_pass < Bp) Bp = fc.tracks_per_pass;
+    BetaGamma bg{};
+    const bool terms = bg.alloc(sc, G, nm, D, Mp, dq, q_mode);
+    double *dm = sc.alloc<double>(nm_x), *dS = sc.alloc<double>(nS_x);
+    OP_CHECK(terms && dm && dS, who);
+    const Emission e = stage_emission(sc, D, J, flt.CC, flt.DD, flt.noise_std, flt.Y_obs, steps);
+    MomentFilterArgs fa{};
+    fa.J = J; fa.CC = e.CC; fa.DD = e.DD; fa.sd = e.sd; fa.Y = e.Y;
+    fa.m_filt = sc.alloc<double>(nm_x); fa.S_filt = sc.alloc<double>(nS_x); fa.lpd = sc.alloc<double>(nlpd); fa.lpd_joint = sc.alloc<double>(nlj);
+    OP_CHECK(e.ok && fa.m_filt && fa.S_filt && fa.lpd && fa.lpd_joint, who);
+    double *dmfc = sc.alloc<double>(nm_fc), *dSfc = sc.alloc<double>(nS_fc);
+    int *dorg = sc.alloc<int>(B);
+    MomentLinearFanArgs lf = mg_lfan_layout(G, nm, D, Mp, upg, Bp * N);
+    lf.K = sc.alloc<double>((size_t)lf.units * lf.Tp * Mp); lf.vpart = sc.alloc<double>((size_t)lf.units * lf.ntj * lf.Tp);
+    OP_CHECK(dmfc && dSfc && dorg && lf.K && lf.vpart, who);
+    // the draws, uploaded once; the particles of a pass (the filter's one track per group lives in the same buffers)
+    const ParticleReq &q = pf.filter;
+    const long long ne = (long long)steps * N * D, nx = (long long)N * D, nf = (long long)h * N * D;
+    MomentParticleArgs pa{};
+    pa.N = N; pa.eps_g = q.eps_g; pa.unif_g = q.unif_g; pa.xi0_g = q.xi0_g;
+    pa.eps = sc.upload(q.eps, particle_extent(q.eps_g, 0, ne, G, 1));
+    pa.unif = sc.upload(q.unif, particle_extent(q.unif_g, 0, steps, G, 1));
+    pa.xi0 = dS0 ? sc.upload(q.xi0, particle_extent(q.xi0_g, 0, nx, G, 1)) : nullptr;
+    pa.xstate = sc.alloc<double>((size_t)2 * G * Bp * N * D);
+    pa.pmean = sc.alloc<double>((size_t)G * Bp * D * N);
+    pa.ess = sc.alloc<double>(nlj);
+    pa.particles = sc.alloc<double>(nm_x * N);
+    pa.ancestors = sc.alloc<int>(nlj * N);
+    MomentParticleFanArgs ta{};
+    ta.N = N; ta.eps_g = pf.eps_fc_g; ta.eps_b = pf.eps_fc_b;
+    ta.eps_fc = sc.upload(pf.eps_fc, particle_extent(pf.eps_fc_g, pf.eps_fc_b, nf, G, B));
+    ta.particles = pa.particles; ta.ancestors = pa.ancestors; ta.xstate = pa.xstate; ta.pmean = pa.pmean;
+    ta.lpd_fc = sc.alloc<double>(nl_fc);
+    ta.fc_particles = pf.fc_particles ? sc.alloc<double>(nm_fc * N) : nullptr;
+    OP_CHECK(pa.eps && pa.unif && (!dS0 || pa.xi0) && pa.xstate && pa.pmean && pa.ess && pa.particles && pa.ancestors && ta.eps_fc &&
+             ta.lpd_fc && (!pf.fc_particles || ta.fc_particles), who);
+    OP_TRY(hipMemsetAsync(lf.K, 0, (size_t)lf.units * lf.Tp * Mp * sizeof(double), sc.stream));          // rows no pass fills stay zeros
+    OP_TRY(hipMemcpyAsync(dorg, fc.origins, (size_t)B * sizeof(int), hipMemcpyHostToDevice, sc.stream));
+    if (int rc = bg.launch(sc, G, nm, M, D, Mp, hv.len, dW, dq, q_mode, dU)) return rc;
+    MomentGroupArgs a{};
+    a.G = G; a.n_models = nm; a.D = D; a.C = C; a.P = P; a.M = M; a.Mp = Mp; a.NS = 0; a.steps = steps; a.unit_per_group = upg;
+    a.Z = dZ; a.variance = hv.variance; a.len = hv.len; a.beta = bg.beta; a.gam = bg.gam; a.x_last = dxl; a.S0 = dS0; a.log_Q = dlq;
+    a.ctrl = dctrl; a.part = nullptr; a.state = nullptr; a.m_x = dm; a.S_x = dS;
+    {
+        // one record per group through the records launch, in the buffers of the tracks with the layout of one record per group
+        // (Bp >= 1: never larger than theirs); the K rows it filled are zeros again before the first pass of tracks
+        const MomentRecordArgs ra{1, 1, 0};
+        MomentLinearFanArgs l1 = mg_lfan_layout(G, nm, D, Mp, upg, N);
+        l1.K = lf.K; l1.vpart = lf.vpart;
+        for (int t = 0; t <= steps; ++t) launch_mg_prec_step(sc.stream, a, fa, ra, l1, pa, t);
+        OP_TRY(hipMemsetAsync(lf.K, 0, (size_t)l1.units * l1.Tp * Mp * sizeof(double), sc.stream));
+    }
+    // passes of at most Bp origins, h + 1 launch triples each; a track's values do not depend on the pass it is in
+    MomentGroupArgs tg = a;
+    tg.steps = h; tg.x_last = nullptr; tg.S0 = nullptr; tg.m_x = dmfc; tg.S_x = dSfc;
+    MomentFanArgs fn{};
+    fn.B = B; fn.n = steps; fn.origin = dorg;
+    for (int b0 = 0; b0 < B; b0 += Bp) {
+        fn.b0 = b0; fn.Bp = B - b0 < Bp ? B - b0 : Bp;
+        tg.G = G * fn.Bp;
+        lf.nr = (lf.shared ? G * fn.Bp : fn.Bp) * N;
+        for (int t = 0; t <= h; ++t) launch_mg_pfan_step(sc.stream, tg, fa, fn, lf, ta, t);
+    }
+    OP_TRY(hipGetLastError());
+    std::vector<double> hl;
+    if (fc.y_mean || fc.y_var_total || fc.lpd_gauss) {
+        // the forecast stacks as [G][B * h][D] against the targets Y_fc[b * h + k] = Y_obs[origins[b] + 1 + k]
+        std::vector<double> &yfc = sc.host(BH * J);
+        for (int b = 0; b < B; ++b)
+            memcpy(yfc.data() + (size_t)b * h * J, flt.Y_obs + (size_t)(fc.origins[b] + 1) * J, (size_t)h * J * sizeof(double));
+        const SummaryReq fq{flt.CC, flt.DD, flt.noise_std, J, yfc.data(), B * h, fc.y_mean, nullptr, fc.y_var_total, nullptr, fc.lpd_gauss};
+        if (int rc = mg_summary(sc, who, dmfc, dSfc, G, B * h, D, fq)) return rc;
+    }
+    double *lfc = pf.fc_lpd;
+    if (!lfc && fc.lpd_mix) { hl.resize(nl_fc); lfc = hl.data(); }
+    auto down = [&](void *dst, const void *src, size_t bytes) { return !dst || sc.download(dst, src, bytes); };
+    if (!down(fc.m_fc, dmfc, nm_fc * sizeof(double)) || !down(fc.S_fc, dSfc, nS_fc * sizeof(double)) || !down(lfc, ta.lpd_fc, nl_fc * sizeof(double)) ||
+        !down(pf.fc_particles, ta.fc_particles, nm_fc * N * sizeof(double)))
+        return set_error(nullptr, FFVD_EDEVICE, who + ": copying the results back failed");
+    if (fc.lpd_mix)
+        for (size_t k = 0; k < BH * J; ++k) {
+            double mx = -INFINITY, sum = 0.0;
+            for (int g = 0; g < G; ++g) mx = std::fmax(mx, lfc[(size_t)g * BH * J + k]);
+            for (int g = 0; g < G; ++g) sum += std::exp(lfc[(size_t)g * BH * J + k] - mx);
+            fc.lpd_mix[k] = std::isnan(lfc[k]) ? NAN : mx + std::log(sum / G);
+        }
+    return mg_particle_finish(sc, who, G, 1, steps, D, dm, dS, m_x, S_x, fa, pa, flt, q);
 }
 
 // the scalar-argument checks the two entry points share (before any device call); nothing: FFVD_OK without touching anything
@@ -1479,6 +1626,18 @@ extern "C" int ffvd_op_posterior_filter_particle_records_grouped(int kind, int G
 // rule of the filter AND of the tracks (MG_METHOD_LINEAR: moment_linear.hip, then moment_linear_fan.hip, two launches per step;
 // MG_METHOD_CUBATURE: moment_cubature_records.hip with one record, then moment_cubature_fan.hip, two launches per step)
 namespace {
+// the particle request of a forecast call (MG_METHOD_PARTICLE; the other rules take none): no `cross` and no smoother, the draws
+int particle_fc_checks(const std::string &who, int method, const FilterReq &f, const ForecastReq &q, const ParticleFcReq *pf, int G, int steps,
+                       int D, bool with_S0) {
+    if (method != MG_METHOD_PARTICLE) return pf ? set_error(nullptr, FFVD_EINVAL, who + ": bad argument") : FFVD_OK;
+    if (f.cross || f.m_smooth || f.S_smooth)
+        return set_error(nullptr, FFVD_EINVAL, who + ": bad argument (the particle filter has no cross covariance and no smoother: pass NULL)");
+    if (!pf || !particle_fc_ok(*pf, G, q.n_origins, q.horizon, steps, D, with_S0))
+        return set_error(nullptr, FFVD_EINVAL, who + ": bad argument (2 <= N <= 2048, finite draws, unif in [0, 1), xi0 with S0s, strides 0 or "
+                                               "contiguous, G * steps * N * D < 2^31 and G * B * h * N * D < 2^31 are needed)");
+    return FFVD_OK;
+}
+
 int forecast_given(const std::string &who, int method, int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M, int P,
                                         int D, const double *logvariances, const double *loglengthscales, const double *fs,
                                         const double *const *q_sqrts, int q_mode, const double *x_lasts, const double *S0s,
@@ -1487,7 +1646,8 @@ int forecast_given(const std::string &who, int method, int kind, int G, int n_mo
                                         double *m_filt, double *S_filt, double *cross, double *lpd, double *lpd_joint, double *m_smooth,
                                         double *S_smooth, double *y_mean, double *y_var_total, double *lpd_mix, double *lpd_gauss,
                                         int horizon, const int *origins, int n_origins, int tracks_per_pass, double *m_fc, double *S_fc,
-                                        double *fc_y_mean, double *fc_y_var_total, double *fc_lpd_mix, double *fc_lpd_gauss) {
+                                        double *fc_y_mean, double *fc_y_var_total, double *fc_lpd_mix, double *fc_lpd_gauss,
+                                        const ParticleFcReq *pf = nullptr) {
     const std::string bad = who + ": bad argument";
     const FilterReq f{CC, DD, noise_std, J, Y_obs, m_filt, S_filt, cross, lpd, lpd_joint, m_smooth, S_smooth, y_mean, y_var_total, lpd_mix,
                       lpd_gauss};
@@ -1496,11 +1656,12 @@ int forecast_given(const std::string &who, int method, int kind, int G, int n_mo
     if (!mg_scalars_ok(kind, G, n_models, M, P, D, C, steps, q_mode) || !filter_scalars_ok(f) || !forecast_scalars_ok(q, G, steps, D))
         return set_error(nullptr, FFVD_EINVAL, bad);
     if (G == 0 || steps == 0) return FFVD_OK;
+    if (int rc = particle_fc_checks(who, method, f, q, pf, G, steps, D, S0s != nullptr)) return rc;
     if (!Lm_inverse_seqs || !Zs || !logvariances || !loglengthscales || !fs || !x_lasts || !log_Qs || (C > 0 && !ctrl) ||
-        !filter_arrays_ok(f, steps, m_pred, S_pred, q.any_output()) || !forecast_origins_ok(q, steps))
+        !filter_arrays_ok(f, steps, m_pred, S_pred, q.any_output() || (pf && pf->any_output())) || !forecast_origins_ok(q, steps))
         return set_error(nullptr, FFVD_EINVAL, bad);
     return mg_given_run(who, G, n_models, Lm_inverse_seqs, Zs, M, P, D, logvariances, loglengthscales, fs, q_sqrts, q_mode, x_lasts, S0s, ctrl,
-                        C, steps, log_Qs, m_pred, S_pred, nullptr, &f, &q, method);
+                        C, steps, log_Qs, m_pred, S_pred, nullptr, &f, &q, method, pf);
 }
 
 int forecast_posterior(const std::string &who, int method, int kind, int G, int n_models, const double *Zs, int M, int P, int D,
@@ -1513,7 +1674,8 @@ int forecast_posterior(const std::string &who, int method, int kind, int G, int 
                                                   double *m_smooth, double *S_smooth, double *y_mean, double *y_var_total, double *lpd_mix,
                                                   double *lpd_gauss, double *U_means, int horizon, const int *origins, int n_origins,
                                                   int tracks_per_pass, double *m_fc, double *S_fc, double *fc_y_mean,
-                                                  double *fc_y_var_total, double *fc_lpd_mix, double *fc_lpd_gauss) {
+                                                  double *fc_y_var_total, double *fc_lpd_mix, double *fc_lpd_gauss,
+                                                  const ParticleFcReq *pf = nullptr) {
     const std::string bad = who + ": bad argument";
     const FilterReq f{CC, DD, noise_std, J, Y_obs, m_filt, S_filt, cross, lpd, lpd_joint, m_smooth, S_smooth, y_mean, y_var_total, lpd_mix,
                       lpd_gauss};
@@ -1523,11 +1685,12 @@ int forecast_posterior(const std::string &who, int method, int kind, int G, int 
         !filter_scalars_ok(f) || !forecast_scalars_ok(q, G, steps, D))
         return set_error(nullptr, FFVD_EINVAL, bad);
     if (G == 0 || steps == 0) return FFVD_OK;
+    if (int rc = particle_fc_checks(who, method, f, q, pf, G, steps, D, S0s != nullptr)) return rc;
     if (!Zs || !logvariances || !loglengthscales || !Xs || !log_Qs || (C > 0 && (!ctrl_fit || !ctrl_roll)) ||
-        !filter_arrays_ok(f, steps, m_pred, S_pred, q.any_output()) || !forecast_origins_ok(q, steps))
+        !filter_arrays_ok(f, steps, m_pred, S_pred, q.any_output() || (pf && pf->any_output())) || !forecast_origins_ok(q, steps))
         return set_error(nullptr, FFVD_EINVAL, bad);
     const PgIn in{who, kind, G, n_models, M, P, D, C, T, groups_per_pass, Zs, logvariances, loglengthscales, Xs, ctrl_fit, log_Qs, jitter};
-    return mg_posterior_run(in, q_mode, x0s, S0s, ctrl_roll, steps, m_pred, S_pred, U_means, nullptr, &f, &q, method);
+    return mg_posterior_run(in, q_mode, x0s, S0s, ctrl_roll, steps, m_pred, S_pred, U_means, nullptr, &f, &q, method, pf);
 }
 }  // namespace
 
@@ -1635,6 +1798,59 @@ extern "C" int ffvd_op_posterior_forecast_cubature_grouped(int kind, int G, int 
                               y_var_total, lpd_mix, lpd_gauss, U_means, horizon, origins, n_origins, tracks_per_pass, m_fc, S_fc, fc_y_mean,
                               fc_y_var_total, fc_lpd_mix, fc_lpd_gauss);
 }
+
+// The same two calls with the bootstrap particle filter over the record (the particle records launch with one record) and N equally
+// weighted particles per track, propagated without weighting or resampling (moment_particle_fan.hip).  The draws are the caller's:
+// the filter's eps [G or 1][steps][N][D], unif [G or 1][steps], xi0 [G or 1][N][D] (with S0s) with a group stride each, the forecast's
+// eps_fc [G or 1][B or 1][horizon][N][D] with a group and an origin stride (in doubles; 0 = shared).  cross, m_smooth and S_smooth
+// must be NULL.
+#define FFVD_PARTICLE_FC_PARAMS                                                                                                              \
+    int N, const double *eps, long long eps_stride_g, const double *unif, long long unif_stride_g, const double *xi0,                       \
+        long long xi0_stride_g, const double *eps_fc, long long eps_fc_stride_g, long long eps_fc_stride_b
+#define FFVD_PARTICLE_FC_REQ                                                                                                                 \
+    const ParticleFcReq pf {                                                                                                                 \
+        ParticleReq{N, eps, eps_stride_g, 0, unif, unif_stride_g, 0, xi0, xi0_stride_g, 0, ess, log_evidence, nullptr, nullptr}, eps_fc,     \
+            eps_fc_stride_g, eps_fc_stride_b, fc_lpd, fc_particles                                                                           \
+    }
+extern "C" int ffvd_op_forecast_particle_grouped(int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M, int P,
+                                        int D, const double *logvariances, const double *loglengthscales, const double *fs,
+                                        const double *const *q_sqrts, int q_mode, const double *x_lasts, const double *S0s,
+                                        const double *ctrl, int C, int steps, const double *log_Qs, const double *CC, const double *DD,
+                                        const double *noise_std, int J, const double *Y_obs, double *m_pred, double *S_pred,
+                                        double *m_filt, double *S_filt, double *cross, double *lpd, double *lpd_joint, double *m_smooth,
+                                        double *S_smooth, double *y_mean, double *y_var_total, double *lpd_mix, double *lpd_gauss,
+                                        int horizon, const int *origins, int n_origins, int tracks_per_pass, FFVD_PARTICLE_FC_PARAMS,
+                                        double *m_fc, double *S_fc, double *fc_y_mean, double *fc_y_var_total, double *fc_lpd_mix,
+                                        double *fc_lpd_gauss, double *ess, double *log_evidence, double *fc_lpd, double *fc_particles) {
+    FFVD_PARTICLE_FC_REQ;
+    return forecast_given("ffvd_op_forecast_particle_grouped", MG_METHOD_PARTICLE, kind, G, n_models, Lm_inverse_seqs, Zs, M, P, D,
+                          logvariances, loglengthscales, fs, q_sqrts, q_mode, x_lasts, S0s, ctrl, C, steps, log_Qs, CC, DD, noise_std, J,
+                          Y_obs, m_pred, S_pred, m_filt, S_filt, cross, lpd, lpd_joint, m_smooth, S_smooth, y_mean, y_var_total, lpd_mix,
+                          lpd_gauss, horizon, origins, n_origins, tracks_per_pass, m_fc, S_fc, fc_y_mean, fc_y_var_total, fc_lpd_mix,
+                          fc_lpd_gauss, &pf);
+}
+
+extern "C" int ffvd_op_posterior_forecast_particle_grouped(int kind, int G, int n_models, const double *Zs, int M, int P, int D,
+                                                  const double *logvariances, const double *loglengthscales, const double *Xs,
+                                                  const double *ctrl_fit, int C, int T, const double *log_Qs, double jitter,
+                                                  int groups_per_pass, int q_mode, const double *x0s, const double *S0s,
+                                                  const double *ctrl_roll, int steps, const double *CC, const double *DD,
+                                                  const double *noise_std, int J, const double *Y_obs, double *m_pred, double *S_pred,
+                                                  double *m_filt, double *S_filt, double *cross, double *lpd, double *lpd_joint,
+                                                  double *m_smooth, double *S_smooth, double *y_mean, double *y_var_total, double *lpd_mix,
+                                                  double *lpd_gauss, double *U_means, int horizon, const int *origins, int n_origins,
+                                                  int tracks_per_pass, FFVD_PARTICLE_FC_PARAMS, double *m_fc, double *S_fc,
+                                                  double *fc_y_mean, double *fc_y_var_total, double *fc_lpd_mix, double *fc_lpd_gauss,
+                                                  double *ess, double *log_evidence, double *fc_lpd, double *fc_particles) {
+    FFVD_PARTICLE_FC_REQ;
+    return forecast_posterior("ffvd_op_posterior_forecast_particle_grouped", MG_METHOD_PARTICLE, kind, G, n_models, Zs, M, P, D, logvariances,
+                              loglengthscales, Xs, ctrl_fit, C, T, log_Qs, jitter, groups_per_pass, q_mode, x0s, S0s, ctrl_roll, steps, CC,
+                              DD, noise_std, J, Y_obs, m_pred, S_pred, m_filt, S_filt, cross, lpd, lpd_joint, m_smooth, S_smooth, y_mean,
+                              y_var_total, lpd_mix, lpd_gauss, U_means, horizon, origins, n_origins, tracks_per_pass, m_fc, S_fc, fc_y_mean,
+                              fc_y_var_total, fc_lpd_mix, fc_lpd_gauss, &pf);
+}
+#undef FFVD_PARTICLE_FC_PARAMS
+#undef FFVD_PARTICLE_FC_REQ
 
 // The summary of the moment-matched prediction for stacks the caller holds: they are uploaded, summarised by the same launch as in the
 // calls above

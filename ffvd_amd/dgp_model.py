@@ -743,6 +743,50 @@ class DGPSSM:
         return DGPSSM._forecast_heldout(self, "forecast_heldout_cubature", "cubature", Y_test, control_inputs, horizon, stride, origins,
                                         x0, S0, q_mode, Y_train_std, return_tracks)
 
+    def forecast_heldout_particle(self, Y_test, control_inputs=None, horizon=10, *, num_particles=256, seed=None, noise="shared", stride=1,
+                                  origins=None, x0=None, S0=None, q_mode="reference", Y_train_std=1.0, return_tracks=False):
+        """`forecast_heldout` by particles: the bootstrap particle filter of `filter_records_particle` over the one record, then from
+        each origin `horizon` steps of `num_particles` equally weighted particles per (chain, origin), started from the set the filter
+        carries after that row and advanced without weighting or resampling -- the arbiter of the three Gaussian fans at every
+        horizon: ll_h is the density of the mixture of all S N particles' emissions and is directly comparable with theirs.
+        prediction.forecast_particle_grouped has the method and the dict that is returned (lpd_fc (S, B, horizon, Ydim) among it).
+        The draws come from np.random.default_rng(seed), or from the model's own generator when seed is None, as
+        `filter_records_particle` generates them.  noise: "shared" -- one set of filter draws for every chain and one set of forecast
+        draws (horizon, N, D) for every chain and origin (common random numbers); "independent" -- one set per chain, and per
+        (chain, origin) for the forecast draws, refused with the byte count when the draws would exceed 1 GiB.  The other parameters,
+        the start, the control rows and the two forms (collapsed U: ONE `posterior_forecast_particle_grouped` call; explicit U:
+        `kernel_pre_cal` once, then `forecast_particle_grouped`) are those of `forecast_heldout`."""
+        from . import conditionals_multi_output as cmo
+        from . import prediction as pr
+        who = "forecast_heldout_particle"
+        if noise not in ("shared", "independent"):
+            raise ValueError(f"{who}: noise: expected \"shared\" or \"independent\", got {noise!r}")
+        N = num_particles
+        if isinstance(N, bool) or not isinstance(N, (int, np.integer)) or not 2 <= N <= 2048:
+            raise ValueError(f"{who}: num_particles: expected an integer in [2, 2048], got {num_particles!r}")
+        Y_test, x0s, S0s, ci = DGPSSM._heldout_record(self, who, Y_test, control_inputs, x0, S0, q_mode)
+        S, D, steps = self.num_chains, self.output_dim, Y_test.shape[0]
+        h, org = pr._pack_forecast(who, steps, horizon, origins, stride)
+        B = len(org)
+        lead, lead_fc = ((), ()) if noise == "shared" else ((S,), (S, B))
+        nbytes = 8 * (int(np.prod(lead, dtype=np.int64)) * (steps * N * D + steps + (N * D if S0 is not None else 0)) +
+                      int(np.prod(lead_fc, dtype=np.int64)) * h * N * D)
+        if noise == "independent" and nbytes > 2 ** 30:
+            raise ValueError(f"{who}: noise=\"independent\" needs {nbytes} bytes of draws, more than 1 GiB: use \"shared\"")
+        rng = np.random.default_rng(seed) if seed is not None else self._rng
+        eps, unif = rng.standard_normal(lead + (steps, N, D)), rng.random(lead + (steps,))
+        xi0 = None if S0 is None else rng.standard_normal(lead + (N, D))
+        eps_fc = rng.standard_normal(lead_fc + (h, N, D))
+        lay, lik, n_train = self.layers[-1], self.likelihood, self.Y.shape[0]
+        kw = dict(xi0=xi0, origins=org, S0s=S0s, q_mode=q_mode, Y_train_std=Y_train_std, return_tracks=return_tracks)
+        if self.U_collapse:
+            return pr.posterior_forecast_particle_grouped(lay.Z, lay.kernel, [self._X_chains[s_] for s_ in range(S)], self.Q, ci, n_train,
+                                                          Y_test, lik.CC, lik.DD, lik.log_Rchols, h, eps, unif, eps_fc, x0s=x0s, **kw)
+        Lm = cmo.kernel_pre_cal(lay.Z, lay.kernel)
+        starts = [self._X_chains[s_][-1] for s_ in range(S)] if x0s is None else list(x0s)
+        return pr.forecast_particle_grouped(Lm, lay.Z, lay.kernel, [lay.U] * S, None, starts, ci, n_train, Y_test, self.Q, lik.CC, lik.DD,
+                                            lik.log_Rchols, h, eps, unif, eps_fc, **kw)
+
     def _forecast_heldout(self, who, method, Y_test, control_inputs, horizon, stride, origins, x0, S0, q_mode, Y_train_std, return_tracks):
         """The body of `forecast_heldout`, `forecast_heldout_linearised` and `forecast_heldout_cubature` (called through the class, as
         `_heldout_record`)."""

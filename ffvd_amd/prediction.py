@@ -1281,6 +1281,152 @@ def posterior_forecast_cubature_grouped(Zs, kerns, Xs, Qs, control_inputs, ctrl_
                                return_tracks, return_filter, tracks_per_pass, jitter, groups_per_pass)
 
 
+def _fc_draw_layout(who, name, x, tail, lead):
+    """One of the layouts of a draw array of the particle forecasts: `tail` (shared), or `tail` behind the last one, two, ... of the
+    leading axes `lead`.  Returns the contiguous array and one stride in doubles per leading axis (0 = shared)."""
+    a = np.asarray(x, dtype=np.float64)
+    tail, lead = tuple(tail), tuple(lead)
+    shapes = [lead[len(lead) - k:] + tail for k in range(len(lead) + 1)]
+    if a.shape not in shapes:
+        raise ValueError(f"{who}: {name}: expected " + " or ".join(str(s) for s in shapes) + f", got {a.shape}")
+    if not np.all(np.isfinite(a)):
+        raise ValueError(f"{who}: {name}: every draw must be finite")
+    have = a.ndim - len(tail)
+    strides, inner = [], int(np.prod(tail, dtype=np.int64))
+    for k in range(len(lead)):                          # from the innermost leading axis outwards
+        strides.append(inner if k < have else 0)
+        inner *= lead[len(lead) - 1 - k] if k < have else 1
+    return np.ascontiguousarray(a), tuple(reversed(strides))
+
+
+def _pack_particle_forecast(who, G, B, steps, h, D, eps, unif, xi0, eps_fc, with_S0, return_particles):
+    """Shape and value checks of the draws of `forecast_particle_grouped` (before the library is loaded): N from eps, the layouts of
+    eps / unif / xi0 (shared or per group) and of eps_fc (shared, per origin, or per group and origin), unif in [0, 1), xi0 exactly
+    when S0s is given, the 2^31 limits.  Returns N and the arguments N .. eps_fc_stride_b."""
+    e = np.asarray(eps, dtype=np.float64)
+    if e.ndim not in (3, 4) or e.shape[-1] != D:
+        raise ValueError(f"{who}: eps: expected ({steps}, N, {D}) or ({G}, {steps}, N, {D}), got {e.shape}")
+    N = e.shape[-2]
+    if not PARTICLE_MIN_N <= N <= PARTICLE_MAX_N:
+        raise ValueError(f"{who}: eps: the number of particles N must lie in [{PARTICLE_MIN_N}, {PARTICLE_MAX_N}], got {N}")
+    e, (eg,) = _fc_draw_layout(who, "eps", e, (steps, N, D), (G,))
+    u, (ug,) = _fc_draw_layout(who, "unif", unif, (steps,), (G,))
+    if np.any(u < 0.0) or np.any(u >= 1.0):
+        raise ValueError(f"{who}: unif: every uniform must lie in [0, 1)")
+    if with_S0 != (xi0 is not None):
+        raise ValueError(f"{who}: xi0: the start draws ({N}, {D}) are needed exactly when S0s is given (S0s "
+                         f"{'given' if with_S0 else 'None'}, xi0 {'None' if xi0 is None else 'given'})")
+    x, (xg,) = (None, (0,)) if xi0 is None else _fc_draw_layout(who, "xi0", xi0, (N, D), (G,))
+    f, (fg, fb) = _fc_draw_layout(who, "eps_fc", eps_fc, (h, N, D), (G, B))
+    if not isinstance(return_particles, (bool, np.bool_)):
+        raise ValueError(f"{who}: return_particles: expected a bool, got {return_particles!r}")
+    if G * steps * N * D >= 2 ** 31:
+        raise ValueError(f"{who}: G * steps * N * D = {G * steps * N * D} must stay below 2^31")
+    if G * B * h * N * D >= 2 ** 31:
+        raise ValueError(f"{who}: G * B * horizon * N * D = {G * B * h * N * D} must stay below 2^31")
+    dp = _lib.dptr
+    return N, (N, dp(e), eg, dp(u), ug, None if x is None else dp(x), xg, dp(f), fg, fb), (e, u, x, f)
+
+
+def _particle_forecast_call(m, G, D, steps, h, org, N, return_tracks, return_filter, return_particles, tracks_per_pass):
+    """Output arrays and the arguments CC .. lpd_gauss, horizon .. tracks_per_pass and m_fc .. fc_particles of the two particle
+    forecast entry points (U_means of the fused one goes behind the first block, the draws between the other two)."""
+    if isinstance(tracks_per_pass, bool) or int(tracks_per_pass) != tracks_per_pass or int(tracks_per_pass) < 0:
+        raise ValueError(f"tracks_per_pass must be 0 (automatic) or a positive integer, got {tracks_per_pass!r}")
+    import ctypes
+    J, B, dp = m["J"], len(org), _lib.dptr
+    fout = None
+    if return_filter:
+        fout = dict(m_pred=np.empty((G, steps, D)), S_pred=np.empty((G, steps, D, D)), m_filt=np.empty((G, steps, D)),
+                    S_filt=np.empty((G, steps, D, D)), lpd=np.empty((G, steps, J)), lpd_joint=np.empty((G, steps)),
+                    predict_y=np.empty((steps, J)), predict_y_var_total=np.empty((steps, J)), lpd_mix=np.empty((steps, J)),
+                    lpd_gauss=np.empty((steps, J)), ess=np.empty((G, steps)), log_evidence=np.empty((G,)))
+    fo = lambda k: dp(fout[k]) if fout is not None and k in fout else None
+    names = ("m_pred", "S_pred", "m_filt", "S_filt", "cross", "lpd", "lpd_joint", "m_smooth", "S_smooth", "predict_y",
+             "predict_y_var_total", "lpd_mix", "lpd_gauss")
+    fargs = (dp(m["CC"]), dp(m["DD"]), dp(m["sd"]), J, dp(m["Y"])) + tuple(fo(k) for k in names)
+    out = {k: np.empty((B, h, J)) for k in FORECAST_POOLED}
+    out["lpd_fc"] = np.empty((G, B, h, J))
+    if return_tracks:
+        out.update(m_fc=np.empty((G, B, h, D)), S_fc=np.empty((G, B, h, D, D)))
+    if return_particles:
+        out["fc_particles"] = np.empty((G, B, h, N, D))
+    opt = lambda k: dp(out[k]) if k in out else None
+    hargs = (h, org.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), B, int(tracks_per_pass))
+    oargs = (opt("m_fc"), opt("S_fc")) + tuple(dp(out[k]) for k in FORECAST_POOLED) + \
+        (fo("ess"), fo("log_evidence"), dp(out["lpd_fc"]), opt("fc_particles"))
+    return fout, fargs, out, hargs, oargs
+
+
+def _particle_forecast_dict(m, org, h, fout, out, Y_train_std):
+    """`_forecast_dict`; with the filter's outputs also ll_all (= ll: one record)."""
+    res = _forecast_dict(m, org, h, fout, out, Y_train_std)
+    if fout is not None:
+        res["ll_all"] = res["ll"]
+    return res
+
+
+def forecast_particle_grouped(Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_inputs, ctrl_offset, Y_obs, Qs, CC, DD, log_Rchols,
+                              horizon, eps, unif, eps_fc, *, xi0=None, origins=None, stride=1, S0s=None, q_mode="reference", Y_train_std=1.0,
+                              return_tracks=False, return_filter=False, return_particles=False, tracks_per_pass=0):
+    """`forecast_grouped` by particles, in ONE call (`ffvd_op_forecast_particle_grouped`): the bootstrap particle filter of
+    `filter_particle_records_grouped` over the one record, then from every origin o a track of N equally weighted particles started
+    from the set the filter carries AFTER row o (the X^- of row o gathered through that row's ancestors; the identity for a row
+    with nothing observed) and advanced `horizon` steps with the caller's forecast draws, without weighting or resampling: with
+    (m_i, v_i) the GP conditional of the group at [X_i, c_row], X_i <- X_i + m_i + eps_fc[k - 1, i] sqrt(v_i + Q) for k = 1 .. h,
+    control row ctrl_offset + o + k (the row the Gaussian fans use).  The positional model, record and emission arguments are
+    `forecast_cubature_grouped`'s.  Every random draw is the caller's: eps (steps, N, D) or (G, steps, N, D), unif (steps,) or
+    (G, steps) in [0, 1), xi0 (N, D) or (G, N, D), given exactly when S0s is; eps_fc (h, N, D), (B, h, N, D) or (G, B, h, N, D):
+    the shared layouts are common random numbers across groups, or across groups and origins.  N = eps.shape[-2], 2 <= N <= 2048.
+    Returns the dict of `forecast_grouped`: predict_y, predict_y_var_total and lpd_gauss pool the moments (m_fc, S_fc) of the
+    particle sets over the groups with EQUAL weights as the Gaussian rules do; lpd_mix = log mean_g exp(lpd_fc[g]) is the density of
+    the mixture of all G N particles' emissions, so ll_h is directly comparable with the three Gaussian fans'.  Always lpd_fc
+    (G, B, h, J) = log mean_i N(Y[o + k, j]; CC[:, j] . X_i + DD_j, sd_j^2), NaN where that target is NaN; with return_tracks m_fc
+    (G, B, h, D) and S_fc (G, B, h, D, D), the mean and centred covariance of the N particles, exactly symmetric; with
+    return_particles fc_particles (G, B, h, N, D); with return_filter the keys of `filter_particle_records_grouped` with the record
+    axis dropped, its pooled one-step arrays under filter_predict_y, filter_predict_y_var_total, filter_lpd_mix, filter_lpd_gauss.
+    A track is bit for bit what `filter_particle_records_grouped` computes (m_pred, S_pred, particles at rows o + 1 .. o + h) over
+    the record cut after its origin and continued by `horizon` all-NaN rows with the draws concatenated, and does not depend on the
+    other tracks, the other groups or tracks_per_pass ("Particle forecasts").  SquaredExponential kernels
+    only."""
+    who = "forecast_particle_grouped"
+    steps = _filter_steps(who, Y_obs)
+    a = _pack_moment_groups(who, Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_inputs, ctrl_offset, steps, Qs, S0s, q_mode)
+    G, D = a["G"], a["D"]
+    h, org = _pack_forecast(who, steps, horizon, origins, stride, (a["args"][0], a["M"], a["args"][6], D))
+    m = _pack_filter(who, D, Y_obs, CC, DD, log_Rchols)
+    N, pargs, keep = _pack_particle_forecast(who, G, len(org), steps, h, D, eps, unif, xi0, eps_fc, S0s is not None, return_particles)
+    fout, fargs, out, hargs, oargs = _particle_forecast_call(m, G, D, steps, h, org, N, return_tracks, return_filter,
+                                                             bool(return_particles), tracks_per_pass)
+    rc = _lib.load().ffvd_op_forecast_particle_grouped(*a["args"], *fargs, *hargs, *pargs, *oargs)
+    _lib.check(rc, None, who)
+    return _particle_forecast_dict(m, org, h, fout, out, Y_train_std)
+
+
+def posterior_forecast_particle_grouped(Zs, kerns, Xs, Qs, control_inputs, ctrl_offset, Y_obs, CC, DD, log_Rchols, horizon, eps, unif, eps_fc,
+                                        *, xi0=None, x0s=None, origins=None, stride=1, S0s=None, q_mode="reference", Y_train_std=1.0,
+                                        return_tracks=False, return_filter=False, return_particles=False, tracks_per_pass=0, jitter=JITTER,
+                                        groups_per_pass=0):
+    """The collapsed posterior of G groups and the forecasts of `forecast_particle_grouped` in ONE call
+    (`ffvd_op_posterior_forecast_particle_grouped`): what `conditionals_multi_output.collapse_u_mean_grouped` followed by
+    `forecast_particle_grouped` computes, without the posteriors leaving the device.  The model and start arguments are
+    `posterior_forecast_cubature_grouped`'s; the draws, the return_* flags and the returned dict are `forecast_particle_grouped`'s."""
+    who = "posterior_forecast_particle_grouped"
+    steps = _filter_steps(who, Y_obs)
+    a = _pack_posterior_moment(who, Zs, kerns, Xs, Qs, control_inputs, ctrl_offset, steps, S0s, q_mode, jitter, groups_per_pass)
+    G, D = a["G"], a["D"]
+    h, org = _pack_forecast(who, steps, horizon, origins, stride, (a["args"][0], a["M"], a["args"][5], D))
+    m = _pack_filter(who, D, Y_obs, CC, DD, log_Rchols)
+    x0 = None if x0s is None else _lib.as_f64(x0s, (G, D), "x0s")
+    N, pargs, keep = _pack_particle_forecast(who, G, len(org), steps, h, D, eps, unif, xi0, eps_fc, S0s is not None, return_particles)
+    fout, fargs, out, hargs, oargs = _particle_forecast_call(m, G, D, steps, h, org, N, return_tracks, return_filter,
+                                                             bool(return_particles), tracks_per_pass)
+    pre = a["args"][:17] + (None if x0 is None else _lib.dptr(x0),) + a["args"][17:]
+    rc = _lib.load().ffvd_op_posterior_forecast_particle_grouped(*pre, *fargs, None, *hargs, *pargs, *oargs)
+    _lib.check(rc, None, who)
+    return _particle_forecast_dict(m, org, h, fout, out, Y_train_std)
+
+
 def pg_sweep(Lm_inverse_seq, Z, kern, U_val, X_ref, Y, control_inputs, CC, DD, Rchols, Q, x0, eps, unif):
     """One particle-Gibbs sweep over the latent trajectory: the INTENT of BaseModel.PG_for_X_speedup
     (base_model.py:78-138; the op as written never updates X, see include/ffvd_abi.h `ffvd_op_pg_sweep`).

@@ -1007,6 +1007,54 @@ int  ffvd_op_posterior_forecast_cubature_grouped(int kind, int G, int n_models, 
                                         double *m_fc, double *S_fc, double *fc_y_mean, double *fc_y_var_total, double *fc_lpd_mix,
                                         double *fc_lpd_gauss);
 
+/* ffvd_op_forecast_grouped by particles: the bootstrap particle filter of ffvd_op_filter_particle_records_grouped over the one record
+ * (R = 1: its outputs are that call's bit for bit, record axis dropped; cross, m_smooth and S_smooth must be NULL), then from every
+ * origin o a track of N equally weighted particles started from the set the filter carries AFTER row o -- the X^- of row o gathered
+ * through that row's ancestors, the identity for a row with nothing observed -- and advanced `horizon` steps without weighting or
+ * resampling: with (m_i, v_i) the GP conditional of the group at [X_i, c_row], control row origin + 1 + t at step t,
+ *   X_i <- X_i + m_i + eps_fc[t, i] sqrt(v_i + Q),
+ *   m_fc = mean_i X_i,   S_fc = mean_i (X_i - m_fc)(X_i - m_fc)^T   (upper triangle, mirrored: exactly symmetric),
+ *   fc_lpd[g, b, t, j] = log mean_i N(Y_obs[origin + 1 + t, j]; CC[:, j] . X_i + DD_j, noise_std_j^2)   (NaN where that entry is NaN).
+ * A track is bit for bit what ffvd_op_filter_particle_records_grouped computes (m_pred, S_pred, particles) over the record cut after
+ * its origin and continued by `horizon` all-NaN rows with the draws concatenated; it does not depend on the other tracks, on the
+ * other groups or on tracks_per_pass.  The draws are the caller's: N particles, 2 <= N <= 2048; eps [G or 1][steps][N][D],
+ * unif [G or 1][steps] in [0, 1), xi0 [G or 1][N][D] (given exactly when S0s is) with a group stride each, eps_fc
+ * [G or 1][B or 1][horizon][N][D] with a group and an origin stride; strides in doubles, 0 (shared: common random numbers) or
+ * that of the contiguous array; every draw finite.
+ * Outputs beside those of ffvd_op_forecast_grouped, each of which may be NULL: ess G x steps and log_evidence G (the filter's),
+ * fc_lpd G x B x horizon x J, fc_particles G x B x horizon x N x D.  fc_y_mean, fc_y_var_total and fc_lpd_gauss pool (m_fc, S_fc)
+ * over the groups as the Gaussian rules do; fc_lpd_mix = log mean_g exp(fc_lpd[g]), the density of the mixture of all G N particles.
+ * Limits: those of ffvd_op_filter_particle_records_grouped with R = 1 and of ffvd_op_forecast_grouped; G * B * horizon * N * D < 2^31;
+ * the N kernel rows of one track per group must fit the scratch of a pass (FFVD_EINVAL names the largest N that does).  SE kernel only
+ * (FFVD_EINVAL with a message that says so). */
+int  ffvd_op_forecast_particle_grouped(int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M, int P, int D,
+                              const double *logvariances, const double *loglengthscales, const double *fs,
+                              const double *const *q_sqrts, int q_mode, const double *x_lasts, const double *S0s, const double *ctrl,
+                              int C, int steps, const double *log_Qs, const double *CC, const double *DD, const double *noise_std, int J,
+                              const double *Y_obs, double *m_pred, double *S_pred, double *m_filt, double *S_filt, double *cross,
+                              double *lpd, double *lpd_joint, double *m_smooth, double *S_smooth, double *y_mean, double *y_var_total,
+                              double *lpd_mix, double *lpd_gauss, int horizon, const int *origins, int n_origins, int tracks_per_pass,
+                              int N, const double *eps, long long eps_stride_g, const double *unif, long long unif_stride_g,
+                              const double *xi0, long long xi0_stride_g, const double *eps_fc, long long eps_fc_stride_g,
+                              long long eps_fc_stride_b, double *m_fc, double *S_fc, double *fc_y_mean, double *fc_y_var_total,
+                              double *fc_lpd_mix, double *fc_lpd_gauss, double *ess, double *log_evidence, double *fc_lpd,
+                              double *fc_particles);
+
+/* The same on the arguments of ffvd_op_posterior_forecast_grouped: the collapsed posteriors never leave the device. */
+int  ffvd_op_posterior_forecast_particle_grouped(int kind, int G, int n_models, const double *Zs, int M, int P, int D, const double *logvariances,
+                                        const double *loglengthscales, const double *Xs, const double *ctrl_fit, int C, int T,
+                                        const double *log_Qs, double jitter, int groups_per_pass, int q_mode, const double *x0s,
+                                        const double *S0s, const double *ctrl_roll, int steps, const double *CC, const double *DD,
+                                        const double *noise_std, int J, const double *Y_obs, double *m_pred, double *S_pred,
+                                        double *m_filt, double *S_filt, double *cross, double *lpd, double *lpd_joint, double *m_smooth,
+                                        double *S_smooth, double *y_mean, double *y_var_total, double *lpd_mix, double *lpd_gauss,
+                                        double *U_means, int horizon, const int *origins, int n_origins, int tracks_per_pass,
+                                        int N, const double *eps, long long eps_stride_g, const double *unif, long long unif_stride_g,
+                                        const double *xi0, long long xi0_stride_g, const double *eps_fc, long long eps_fc_stride_g,
+                                        long long eps_fc_stride_b, double *m_fc, double *S_fc, double *fc_y_mean,
+                                        double *fc_y_var_total, double *fc_lpd_mix, double *fc_lpd_gauss, double *ess,
+                                        double *log_evidence, double *fc_lpd, double *fc_particles);
+
 /* The summary of ffvd_op_moment_grouped for stacks the caller holds (m_x G x steps x D, S_x G x steps x D x D): the same launch.
  * Limits: D <= 8, J <= 8, 0 <= n_test <= steps, G * steps * D * D < 2^31, as ffvd_op_rollout_summary otherwise. */
 int  ffvd_op_moment_summary(const double *m_x, const double *S_x, int G, int steps, int D, const double *CC, const double *DD,
