@@ -74,6 +74,7 @@ static int create_impl(const ffvd_config *cfg, ffvd_handle *h) {
         w.no_linear_lowrank = on("FFVD_NO_LINEAR_LOWRANK");
         w.debug_sync = on("FFVD_DEBUG_SYNC");
         w.no_tiny = on("FFVD_NO_TINY");               w.no_tiny_a = on("FFVD_NO_TINY_A");
+        w.ws_poison = on("FFVD_WS_POISON");
         if (const char *e = getenv("FFVD_DEBUG_SIDE_DELAY_US")) w.side_delay_us = atoi(e);
         if (const char *e = getenv("FFVD_DEBUG_MAIN_DELAY_US")) w.main_delay_us = atoi(e);
     }

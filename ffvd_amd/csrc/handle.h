@@ -44,6 +44,8 @@ struct ffvd_handle {
         int main_delay_us = 0;      //   must not depend on which stream is late); FFVD_DEBUG_MAIN_DELAY_US=n: the same on the main stream behind a fork
         bool no_tiny = false;       // FFVD_NO_TINY=1: the multi-kernel schedule also at the reference's own experiment size (rounds 1-3)
         bool no_tiny_a = false;     // FFVD_NO_TINY_A=1: ... for the explicit-U branch only (rounds 1-4)
+        bool ws_poison = false;     // FFVD_WS_POISON=1: every handle allocation starts as 0xFF bytes (NaN) instead of whatever hipMalloc returns
+                                    //   (history tests: no result may depend on what a workspace held before the call)
     } sw;
     // resident parameters / data (handle-owned copies)
     double *X = nullptr, *Z = nullptr, *U = nullptr, *logvar = nullptr, *loglen = nullptr, *logQ = nullptr;
@@ -136,7 +138,9 @@ struct ffvd_handle {
     size_t ev_used = 0;
 };
 
-// a device allocation owned by the handle: freed by ffvd_destroy, counted in ffvd_workspace_bytes
+// a device allocation owned by the handle: freed by ffvd_destroy, counted in ffvd_workspace_bytes.  With FFVD_WS_POISON the block is
+// filled with NaN bytes on the handle's stream (which exists before the first allocation): the clears that create_impl and the
+// workspace builders enqueue behind an allocation follow on the same stream and still win.
 template <class T>
 static hipError_t dev_alloc(ffvd_handle *h, T **p, size_t count) {
     size_t bytes = (count ? count : 1) * sizeof(T);
@@ -144,6 +148,7 @@ static hipError_t dev_alloc(ffvd_handle *h, T **p, size_t count) {
     if (e == hipSuccess) {
         h->allocs.push_back((void *)*p);
         h->ws_bytes += (int64_t)bytes;
+        if (h->sw.ws_poison) e = hipMemsetAsync((void *)*p, 0xFF, bytes, h->stream);
     }
     return e;
 }

@@ -111,8 +111,15 @@ static int sghmc_prepare(ffvd_handle *h, uint32_t sample_mask, const ffvd_params
         if (!h->hmc[i][0]) {            // xi, g, g2 <- 1, p <- 0 (base_model.py:151-154)
             std::vector<double> ones(n, 1.0);
             for (int k = 0; k < 5; ++k) HIP_TRY(dev_alloc(h, &h->hmc[i][k], n));
-            for (int k = 0; k < 3; ++k) HIP_TRY(hipMemcpy(h->hmc[i][k], ones.data(), n * sizeof(double), hipMemcpyHostToDevice));
-            HIP_TRY(hipMemsetAsync(h->hmc[i][3], 0, n * sizeof(double), h->stream));      // the stream the update reads it on
+            // on the handle's stream, behind whatever dev_alloc enqueued there for these blocks (FFVD_WS_POISON).  `ones` is the source of
+            // asynchronous copies: the stream is waited for on every path before it goes out of scope
+            hipError_t e = hipSuccess;
+            for (int k = 0; k < 3 && e == hipSuccess; ++k)
+                e = hipMemcpyAsync(h->hmc[i][k], ones.data(), n * sizeof(double), hipMemcpyHostToDevice, h->stream);
+            if (e == hipSuccess) e = hipMemsetAsync(h->hmc[i][3], 0, n * sizeof(double), h->stream);      // the stream the update reads it on
+            const hipError_t es = hipStreamSynchronize(h->stream);
+            HIP_TRY(e);
+            HIP_TRY(es);
         }
         HIP_TRY(hipMemcpyAsync(h->hmc[i][4], nz, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
     }

@@ -397,7 +397,11 @@ def test_not_positive_definite_is_reported():
         with pytest.raises(np.linalg.LinAlgError, match="K_uu"):
             e.nll_terms(p)
         good = e.nll_terms(params)                       # the handle stays usable after a numerical error
-        assert np.isfinite(good["nll"])
+    with ElboEngine(meta["T"], meta["D"], meta["C"], meta["M"], meta["S"], jitter=0.0) as e:
+        e.set_data(Y, c)
+        fresh = e.nll_terms(params)
+    assert np.isfinite(good["nll"]) and good["nll"] == fresh["nll"]      # ... and the failed call left nothing behind
+    np.testing.assert_array_equal(good["nll_per_chain"], fresh["nll_per_chain"])
 
 
 def test_usage_errors():
@@ -668,7 +672,11 @@ def test_non_finite_inputs_are_reported_not_propagated(route):
         with pytest.raises(np.linalg.LinAlgError, match="chain 1"):
             e.nll_terms(bad)
         ok = e.nll_terms(params)
-        assert np.isfinite(ok["nll"])
+    with ElboEngine(meta["T"], meta["D"], meta["C"], meta["M"], meta["S"], route=route) as e:
+        e.set_data(Y, c)
+        fresh = e.nll_terms(params)
+    assert np.isfinite(ok["nll"]) and ok["nll"] == fresh["nll"]          # the same call on a fresh handle: equal bits
+    np.testing.assert_array_equal(ok["nll_per_chain"], fresh["nll_per_chain"])
 
 
 @pytest.mark.parametrize("name,ov,nshard", [("small", dict(S=1, D=2), 3), ("ragged", dict(S=2, D=1), 4),
