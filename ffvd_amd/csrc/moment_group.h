@@ -184,6 +184,31 @@ int mg_prec_records_per_pass(int G, int n_models, int D, int Mp, int unit_per_gr
 void launch_mg_prec_step(hipStream_t stream, const MomentGroupArgs &a, const MomentFilterArgs &f, const MomentRecordArgs &rc,
                          const MomentLinearFanArgs &l, const MomentParticleArgs &p, int t);
 
+// Particle smoothing of many records (moment_particle_smooth.hip; DESIGN.md section 9, "Particle smoothing"): the marginal
+// forward-filter / backward-smoother on the sets the particle filter above carries.  The driver keeps the filter's device stacks
+// `particles` and `ancestors`, launches the keep kernel after the product launch of every step (trans_mean, trans_var: the two
+// parenthesised sub-expressions of the weight kernel's X^-) and, after the last pass, the smoother over all V = G * R tracks of the
+// call: the weights, the normalisers c of all rows in one launch, the rows n_max - 2 .. 0 (omega, then its fold through the
+// ancestors), the moments.  No GP evaluation, no draws.
+// Limits: the particle filter's.  The stacks take (3 D + 3) N doubles and N ints per track row, omega N doubles per track.
+struct MomentParticleSmoothArgs {
+    int V, R, steps, N, D;           // V = G * R tracks, track v is record v % R
+    const int *lens;                 // [R]: rows of every record, or nullptr (every record has `steps` rows)
+    const double *particles;         // [V][steps][N][D]: the filter's X^-
+    const int *ancestors;            // [V][steps][N]
+    double *trans_mean, *trans_var;  // [V][steps][N][D]
+    double *weights, *w_smooth;      // [V][steps][N]: W_t; the smoothing weights on the X^-_t; NaN at and beyond a record's length
+    double *cnorm;                   // [V][steps][N]: c of the columns of row u at [u], u >= 1
+    double *omega;                   // [V][N]: the backward sums of the row in flight
+    double *m_smooth, *S_smooth;     // [V][steps][D], [V][steps][D][D]
+    double *ess_smooth;              // [V][steps]
+};
+// after launch_mg_prec_step(.., s), s < steps, and before launch_mg_prec_step(.., s + 1)
+void launch_mg_psm_keep(hipStream_t stream, const MomentGroupArgs &a, const MomentRecordArgs &rc, const MomentLinearFanArgs &l,
+                        const MomentParticleArgs &p, const MomentParticleSmoothArgs &q, int s);
+// after the last pass; n_max: the longest record of the call
+void launch_mg_psm_smooth(hipStream_t stream, const MomentFilterArgs &f, const MomentParticleSmoothArgs &q, int n_max);
+
 // Cubature forecasts (moment_cubature_fan.hip; DESIGN.md section 9, "Cubature forecasts"): the fan's tracks and indexing (MomentFanArgs)
 // with the cubature rule above and no measurement update.  MomentGroupArgs as for the linearised forecasts; MomentLinearFanArgs is
 // mg_lfan_layout with Bp = 2D * (tracks per group of the pass), msum [2][tracks][D][2D], `off` [2][tracks][D][D].  The product kernel

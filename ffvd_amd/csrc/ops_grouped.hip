@@ -1131,6 +1131,21 @@ struct ParticleReq {
     double *particles;                           // [G][R][steps][N][D] or NULL
     int *ancestors;                              // [G][R][steps][N] or NULL
 };
+// The smoothing request beside a ParticleReq (moment_particle_smooth.hip): the rows of every record and the outputs, each of which
+// may be NULL
+struct ParticleSmoothReq {
+    const int *lengths;                          // [R], each in [1, steps], or NULL (every record has `steps` rows)
+    double *m_smooth, *S_smooth, *ess_smooth;    // [G][R][steps][D], [..][D][D], [G][R][steps]
+    double *w_smooth, *weights;                  // [G][R][steps][N]
+    double *trans_mean, *trans_var;              // [G][R][steps][N][D]
+    bool any_output() const { return m_smooth || S_smooth || ess_smooth || w_smooth || weights || trans_mean || trans_var; }
+};
+bool particle_smooth_ok(const ParticleSmoothReq &q, int R, int steps) {
+    if (q.lengths)
+        for (int r = 0; r < R; ++r)
+            if (q.lengths[r] < 1 || q.lengths[r] > steps) return false;
+    return true;
+}
 // a pair of strides over arrays of `inner` doubles per (group, record): record 0 or inner, group 0 or inner * (R or 1)
 bool particle_strides_ok(long long sg, long long sr, long long inner, int R) {
     return (sr == 0 || sr == inner) && (sg == 0 || sg == inner * (sr ? R : 1));
@@ -1217,7 +1232,7 @@ int particle_fits(const std::string &who, int G, int nm, int D, int Mp, int upg,
 int mg_records_run(Scratch &sc, const std::string &who, int method, int G, int nm, int M, int P, int D, int C, int steps, const HyperView &hv,
                    const double *dZ, const double *dW, const double *dq, int q_mode, const double *dU, const double *dxl, const double *dS0,
                    const double *dlq, const double *dctrl, double *m_x, double *S_x, const FilterReq &flt, const RecordsReq &rq,
-                   const ParticleReq *pq = nullptr) {
+                   const ParticleReq *pq = nullptr, const ParticleSmoothReq *sq = nullptr) {
     const int Mp = round_up(M, NB), R = rq.R, J = flt.J, upg = dq ? 1 : 0;
     const int V = G * R;                                                               // tracks of the call (V * steps * D * D < 2^31)
     const size_t nm_x = (size_t)V * steps * D, nS_x = nm_x * D, nlpd = (size_t)V * steps * J, nlj = (size_t)V * steps;
@@ -1262,10 +1277,29 @@ int mg_records_run(Scratch &sc, const std::string &who, int method, int G, int n
         pa.xstate = sc.alloc<double>((size_t)2 * G * Rp * q.N * D);
         pa.pmean = sc.alloc<double>((size_t)G * Rp * D * q.N);
         pa.ess = sc.alloc<double>(nlj);
-        pa.particles = q.particles ? sc.alloc<double>(nm_x * q.N) : nullptr;
-        pa.ancestors = q.ancestors ? sc.alloc<int>(nlj * q.N) : nullptr;
-        OP_CHECK(pa.eps && pa.unif && (!dS0 || pa.xi0) && pa.xstate && pa.pmean && pa.ess && (!q.particles || pa.particles) &&
-                 (!q.ancestors || pa.ancestors), who);
+        pa.particles = q.particles || sq ? sc.alloc<double>(nm_x * q.N) : nullptr;
+        pa.ancestors = q.ancestors || sq ? sc.alloc<int>(nlj * q.N) : nullptr;
+        OP_CHECK(pa.eps && pa.unif && (!dS0 || pa.xi0) && pa.xstate && pa.pmean && pa.ess && (!(q.particles || sq) || pa.particles) &&
+                 (!(q.ancestors || sq) || pa.ancestors), who);
+    }
+    MomentParticleSmoothArgs ps{};
+    int n_max = steps;
+    if (par && sq) {                                                                   // the smoother's stacks: (3 D + 3) N doubles per track row
+        int *lens = nullptr;
+        if (sq->lengths) {
+            lens = sc.alloc<int>(R);
+            OP_CHECK(lens, who);
+            OP_TRY(hipMemcpyAsync(lens, sq->lengths, (size_t)R * sizeof(int), hipMemcpyHostToDevice, sc.stream));
+            n_max = 1;
+            for (int r = 0; r < R; ++r) n_max = sq->lengths[r] > n_max ? sq->lengths[r] : n_max;
+        }
+        ps.V = V; ps.R = R; ps.steps = steps; ps.N = pq->N; ps.D = D; ps.lens = lens; ps.particles = pa.particles; ps.ancestors = pa.ancestors;
+        ps.trans_mean = sc.alloc<double>(nm_x * pq->N); ps.trans_var = sc.alloc<double>(nm_x * pq->N);
+        ps.weights = sc.alloc<double>(nlj * pq->N); ps.w_smooth = sc.alloc<double>(nlj * pq->N); ps.cnorm = sc.alloc<double>(nlj * pq->N);
+        ps.omega = sc.alloc<double>((size_t)V * pq->N);
+        ps.m_smooth = sc.alloc<double>(nm_x); ps.S_smooth = sc.alloc<double>(nS_x); ps.ess_smooth = sc.alloc<double>(nlj);
+        OP_CHECK(ps.trans_mean && ps.trans_var && ps.weights && ps.w_smooth && ps.cnorm && ps.omega && ps.m_smooth && ps.S_smooth &&
+                 ps.ess_smooth, who);
     }
     OP_TRY(hipMemsetAsync(lf.K, 0, (size_t)lf.units * lf.Tp * Mp * sizeof(double), sc.stream));          // rows no pass fills stay zeros
     if (int rc = bg.launch(sc, G, nm, M, D, Mp, hv.len, dW, dq, q_mode, dU)) return rc;
@@ -1282,12 +1316,23 @@ int mg_records_run(Scratch &sc, const std::string &who, int method, int G, int n
         lf.nr = (lf.shared ? G * ra.Rp : ra.Rp) * nrow;
         for (int t = 0; t <= steps; ++t) {
             if (cub) launch_mg_crec_step(sc.stream, a, fa, ra, lf, coff, t);
-            else if (par) launch_mg_prec_step(sc.stream, a, fa, ra, lf, pa, t);
-            else launch_mg_lrec_step(sc.stream, a, fa, ra, lf, t);
+            else if (par) {
+                launch_mg_prec_step(sc.stream, a, fa, ra, lf, pa, t);
+                if (sq && t < steps) launch_mg_psm_keep(sc.stream, a, ra, lf, pa, ps, t);   // (mu, s) of step t, before the next weight launch
+            } else launch_mg_lrec_step(sc.stream, a, fa, ra, lf, t);
         }
     }
     if (smooth) launch_mg_smooth(sc.stream, sa);
+    if (par && sq) launch_mg_psm_smooth(sc.stream, fa, ps, n_max);
     OP_TRY(hipGetLastError());
+    if (par && sq) {
+        const size_t N = (size_t)pq->N;
+        auto down = [&](double *dst, const double *src, size_t n) { return !dst || sc.download(dst, src, n * sizeof(double)); };
+        if (!down(sq->m_smooth, ps.m_smooth, nm_x) || !down(sq->S_smooth, ps.S_smooth, nS_x) || !down(sq->ess_smooth, ps.ess_smooth, nlj) ||
+            !down(sq->w_smooth, ps.w_smooth, nlj * N) || !down(sq->weights, ps.weights, nlj * N) ||
+            !down(sq->trans_mean, ps.trans_mean, nm_x * N) || !down(sq->trans_var, ps.trans_var, nm_x * N))
+            return set_error(nullptr, FFVD_EDEVICE, who + ": copying the results back failed");
+    }
     if (par) return mg_particle_finish(sc, who, G, R, steps, D, dm, dS, m_x, S_x, fa, pa, flt, *pq);
     // the pooled one-step summary per record and row: the predicted stacks as [G][R * steps] against Y as [R * steps][J]
     const SummaryReq fsum = flt.pooled(R * steps);
@@ -1456,16 +1501,19 @@ int records_given(const std::string &who, int method, int kind, int G, int n_mod
                   const double *DD, const double *noise_std, int J, const double *Y_obs,
                   int records_per_pass, double *m_pred, double *S_pred, double *m_filt, double *S_filt,
                   double *cross, double *lpd, double *lpd_joint, double *m_smooth, double *S_smooth,
-                  double *y_mean, double *y_var_total, double *lpd_mix, double *lpd_gauss, const ParticleReq *pq = nullptr) {
+                  double *y_mean, double *y_var_total, double *lpd_mix, double *lpd_gauss, const ParticleReq *pq = nullptr,
+                  const ParticleSmoothReq *sq = nullptr) {
     const std::string bad = who + ": bad argument";
     const FilterReq f{CC, DD, noise_std, J, Y_obs, m_filt, S_filt, cross, lpd, lpd_joint, m_smooth, S_smooth, y_mean, y_var_total, lpd_mix,
                       lpd_gauss};
     const RecordsReq rq{R, records_per_pass};
     bool nothing;
     if (int rc = records_checks(who, method, kind, G, n_models, M, P, D, C, steps, q_mode, f, rq, nothing, pq, S0s != nullptr)) return rc;
+    if (sq && !nothing && !particle_smooth_ok(*sq, R, steps))
+        return set_error(nullptr, FFVD_EINVAL, bad + " (every entry of lengths must lie in [1, steps])");
     if (nothing) return FFVD_OK;
     if (!Lm_inverse_seqs || !Zs || !logvariances || !loglengthscales || !fs || !x_lasts || !log_Qs || (C > 0 && !ctrl) ||
-        !filter_arrays_ok(f, R * steps, m_pred, S_pred, pq && (pq->ess || pq->log_evidence || pq->particles || pq->ancestors)))
+        !filter_arrays_ok(f, R * steps, m_pred, S_pred, pq && (pq->ess || pq->log_evidence || pq->particles || pq->ancestors || (sq && sq->any_output()))))
         return set_error(nullptr, FFVD_EINVAL, bad);
     const size_t nK = (size_t)n_models * D, GD = (size_t)G * D, VD = GD * R, nq = given_nq(q_sqrts, q_mode, G, D);
     if (!given_tables_ok(Lm_inverse_seqs, nK, q_sqrts, nq)) return set_error(nullptr, FFVD_EINVAL, bad);
@@ -1478,7 +1526,7 @@ int records_given(const std::string &who, int method, int kind, int G, int n_mod
     OP_CHECK(dW && (!nq || dq) && dU && dxl && (!S0s || dS0) && dlq && (!C || dctrl) && gh.logs(sc) && gh.blocks(sc), who);
     gh.prep(sc.stream);
     return mg_records_run(sc, who, method, G, n_models, M, P, D, C, steps, gh.hv(), gh.dZ, dW, dq, q_mode, dU, dxl, dS0, dlq, dctrl, m_pred, S_pred, f,
-                          rq, pq);
+                          rq, pq, sq);
 }
 
 // the body of ffvd_op_posterior_filter_records_grouped and ffvd_op_posterior_filter_cubature_records_grouped
@@ -1490,17 +1538,20 @@ int records_posterior(const std::string &who, int method, int kind, int G, int n
                       const double *noise_std, int J, const double *Y_obs, int records_per_pass,
                       double *m_pred, double *S_pred, double *m_filt, double *S_filt, double *cross,
                       double *lpd, double *lpd_joint, double *m_smooth, double *S_smooth, double *y_mean,
-                      double *y_var_total, double *lpd_mix, double *lpd_gauss, double *U_means, const ParticleReq *pq = nullptr) {
+                      double *y_var_total, double *lpd_mix, double *lpd_gauss, double *U_means, const ParticleReq *pq = nullptr,
+                      const ParticleSmoothReq *sq = nullptr) {
     const std::string bad = who + ": bad argument";
     const FilterReq f{CC, DD, noise_std, J, Y_obs, m_filt, S_filt, cross, lpd, lpd_joint, m_smooth, S_smooth, y_mean, y_var_total, lpd_mix,
                       lpd_gauss};
     const RecordsReq rq{R, records_per_pass};
     bool nothing;
     if (int rc = records_checks(who, method, kind, G, n_models, M, P, D, C, steps, q_mode, f, rq, nothing, pq, S0s != nullptr)) return rc;
+    if (sq && !nothing && !particle_smooth_ok(*sq, R, steps))
+        return set_error(nullptr, FFVD_EINVAL, bad + " (every entry of lengths must lie in [1, steps])");
     if (!pg_scalars_ok(kind, G, n_models, M, P, D, C, T, groups_per_pass, jitter)) return set_error(nullptr, FFVD_EINVAL, bad);
     if (nothing) return FFVD_OK;
     if (!Zs || !logvariances || !loglengthscales || !Xs || !log_Qs || (C > 0 && (!ctrl_fit || !ctrl_roll)) ||
-        !filter_arrays_ok(f, R * steps, m_pred, S_pred, pq && (pq->ess || pq->log_evidence || pq->particles || pq->ancestors)))
+        !filter_arrays_ok(f, R * steps, m_pred, S_pred, pq && (pq->ess || pq->log_evidence || pq->particles || pq->ancestors || (sq && sq->any_output()))))
         return set_error(nullptr, FFVD_EINVAL, bad);
     const PgIn in{who, kind, G, n_models, M, P, D, C, T, groups_per_pass, Zs, logvariances, loglengthscales, Xs, ctrl_fit, log_Qs, jitter};
     OP_BEGIN(who);
@@ -1521,7 +1572,7 @@ int records_posterior(const std::string &who, int method, int kind, int G, int n
         launch_mg_lrec_spread(sc.stream, G, R, D, dx1, dxl);
     }
     if (int rc = mg_records_run(sc, who, method, G, nm, M, P, D, C, steps, w.hv, dZ, dW, pg_q(w, q_mode), q_mode, w.U, dxl, dS0, w.log_Qs, dctrl,
-                                m_pred, S_pred, f, rq, pq))
+                                m_pred, S_pred, f, rq, pq, sq))
         return rc;
     if (U_means && !sc.download(U_means, w.U, GD * M * sizeof(double)))
         return set_error(nullptr, FFVD_EDEVICE, who + ": copying the results back failed");
@@ -1613,6 +1664,51 @@ extern "C" int ffvd_op_posterior_filter_particle_records_grouped(int kind, int G
                              noise_std, J, Y_obs, records_per_pass, m_pred, S_pred, m_filt, S_filt, nullptr, lpd, lpd_joint, nullptr, nullptr,
                              y_mean, y_var_total, lpd_mix, lpd_gauss, U_means, &pq);
 }
+
+// The same two calls followed by the marginal particle smoother on the carried sets (moment_particle_smooth.hip): the filter's
+// launches with one more per step that keeps (mu, s), then the smoother over all tracks of the call.  The filter outputs are those of
+// the two calls above bit for bit.  (Not ffvd_op_*: see DESIGN.md section 9, "Particle smoothing".)
+#define FFVD_PARTICLE_SMOOTH_PARAMS                                                                                                          \
+    const int *lengths, double *m_smooth, double *S_smooth, double *ess_smooth, double *w_smooth, double *weights, double *trans_mean,      \
+        double *trans_var
+#define FFVD_PARTICLE_SMOOTH_REQ const ParticleSmoothReq sq{lengths, m_smooth, S_smooth, ess_smooth, w_smooth, weights, trans_mean, trans_var}
+extern "C" int ffvd_particle_smooth_records_grouped(int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M,
+                                                    int P, int D, const double *logvariances, const double *loglengthscales, const double *fs,
+                                                    const double *const *q_sqrts, int q_mode, int R, const double *x_lasts, const double *S0s,
+                                                    const double *ctrl, int C, int steps, const double *log_Qs, const double *CC,
+                                                    const double *DD, const double *noise_std, int J, const double *Y_obs,
+                                                    int records_per_pass, FFVD_PARTICLE_PARAMS, double *m_pred, double *S_pred,
+                                                    double *m_filt, double *S_filt, double *lpd, double *lpd_joint, double *y_mean,
+                                                    double *y_var_total, double *lpd_mix, double *lpd_gauss, double *ess,
+                                                    double *log_evidence, double *particles, int *ancestors, FFVD_PARTICLE_SMOOTH_PARAMS) {
+    FFVD_PARTICLE_REQ;
+    FFVD_PARTICLE_SMOOTH_REQ;
+    return records_given("ffvd_particle_smooth_records_grouped", MG_METHOD_PARTICLE, kind, G, n_models, Lm_inverse_seqs, Zs, M, P, D,
+                         logvariances, loglengthscales, fs, q_sqrts, q_mode, R, x_lasts, S0s, ctrl, C, steps, log_Qs, CC, DD, noise_std, J, Y_obs,
+                         records_per_pass, m_pred, S_pred, m_filt, S_filt, nullptr, lpd, lpd_joint, nullptr, nullptr, y_mean, y_var_total, lpd_mix,
+                         lpd_gauss, &pq, &sq);
+}
+
+extern "C" int ffvd_posterior_particle_smooth_records_grouped(int kind, int G, int n_models, const double *Zs, int M, int P, int D,
+                                                              const double *logvariances, const double *loglengthscales, const double *Xs,
+                                                              const double *ctrl_fit, int C, int T, const double *log_Qs, double jitter,
+                                                              int groups_per_pass, int q_mode, int R, const double *x0s, const double *S0s,
+                                                              const double *ctrl_roll, int steps, const double *CC, const double *DD,
+                                                              const double *noise_std, int J, const double *Y_obs, int records_per_pass,
+                                                              FFVD_PARTICLE_PARAMS, double *m_pred, double *S_pred, double *m_filt,
+                                                              double *S_filt, double *lpd, double *lpd_joint, double *y_mean,
+                                                              double *y_var_total, double *lpd_mix, double *lpd_gauss, double *ess,
+                                                              double *log_evidence, double *particles, int *ancestors,
+                                                              FFVD_PARTICLE_SMOOTH_PARAMS, double *U_means) {
+    FFVD_PARTICLE_REQ;
+    FFVD_PARTICLE_SMOOTH_REQ;
+    return records_posterior("ffvd_posterior_particle_smooth_records_grouped", MG_METHOD_PARTICLE, kind, G, n_models, Zs, M, P, D, logvariances,
+                             loglengthscales, Xs, ctrl_fit, C, T, log_Qs, jitter, groups_per_pass, q_mode, R, x0s, S0s, ctrl_roll, steps, CC, DD,
+                             noise_std, J, Y_obs, records_per_pass, m_pred, S_pred, m_filt, S_filt, nullptr, lpd, lpd_joint, nullptr, nullptr,
+                             y_mean, y_var_total, lpd_mix, lpd_gauss, U_means, &pq, &sq);
+}
+#undef FFVD_PARTICLE_SMOOTH_PARAMS
+#undef FFVD_PARTICLE_SMOOTH_REQ
 #undef FFVD_PARTICLE_PARAMS
 #undef FFVD_PARTICLE_REQ
 #undef FFVD_RECORDS_GIVEN_PARAMS

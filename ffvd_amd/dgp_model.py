@@ -644,13 +644,29 @@ class DGPSSM:
         rule: the arbiter of the three Gaussian filters -- exact as the particle count grows, with the unbiased SMC estimate
         `log_evidence` (S, R) of the held-out evidence and the effective sample size `ess` per row.
         prediction.filter_particle_records_grouped has the method and the dict that is returned (no smoothing: particle smoothing is
-        not built).  The draws come from np.random.default_rng(seed), or from the model's own generator when seed is None.  noise:
+        not built into this call, `smooth_records_particle` has it).  The draws come from np.random.default_rng(seed), or from the model's own generator when seed is None.  noise:
         "shared" -- one set of draws (steps, N, D) for every chain and record (common random numbers; each track's estimator stays
         unbiased); "per_record" -- one set per record, shared by the chains; "independent" -- one per (chain, record), refused with
         the byte count when the draws would exceed 1 GiB.  The checks, the start (x0, S0) and the two forms (collapsed U: ONE
         `posterior_filter_particle_records_grouped` call; explicit U: `kernel_pre_cal` once, then `filter_particle_records_grouped`)
         are `filter_records`'; R = 1 is a valid single-record call."""
-        who = "filter_records_particle"
+        return DGPSSM._records_particle(self, "filter_records_particle", "filter_particle_records_grouped", Y_records, control_records,
+                                        num_particles, lengths, x0, S0, q_mode, Y_train_std, records_per_pass, seed, noise, return_particles)
+
+    def smooth_records_particle(self, Y_records, control_records=None, *, num_particles=256, lengths=None, x0=None, S0=None,
+                                q_mode="reference", Y_train_std=1.0, records_per_pass=0, seed=None, noise="shared", return_particles=False):
+        """`filter_records_particle` followed by the marginal particle smoother of every (chain, record) track in the same call: the
+        arbiter of the three Gaussian smoothers.  The parameters, the checks, the draw generation (the same seed gives the same
+        filter, bit for bit) and the two forms (collapsed U: ONE `posterior_smooth_particle_records_grouped` call; explicit U:
+        `kernel_pre_cal` once, then `smooth_particle_records_grouped`) are `filter_records_particle`'s;
+        prediction.smooth_particle_records_grouped has the method and the dict that is returned: the filter's, plus m_smooth, S_smooth
+        and ess_smooth (S, R, steps, ...), with return_particles also weights, w_smooth, trans_mean and trans_var."""
+        return DGPSSM._records_particle(self, "smooth_records_particle", "smooth_particle_records_grouped", Y_records, control_records,
+                                        num_particles, lengths, x0, S0, q_mode, Y_train_std, records_per_pass, seed, noise, return_particles)
+
+    def _records_particle(self, who, fn, Y_records, control_records, num_particles, lengths, x0, S0, q_mode, Y_train_std, records_per_pass,
+                          seed, noise, return_particles):
+        """The body of `filter_records_particle` and `smooth_records_particle`: the checks and the draws, then `_filter_records`."""
         if noise not in ("shared", "per_record", "independent"):
             raise ValueError(f"{who}: noise: expected \"shared\", \"per_record\" or \"independent\", got {noise!r}")
         N = num_particles
@@ -667,7 +683,7 @@ class DGPSSM:
         rng = np.random.default_rng(seed) if seed is not None else self._rng
         draws = dict(eps=rng.standard_normal(lead + (steps, N, D)), unif=rng.random(lead + (steps,)),
                      xi0=None if S0 is None else rng.standard_normal(lead + (N, D)), return_particles=return_particles)
-        return DGPSSM._filter_records(self, who, "filter_particle_records_grouped", Y_records, control_records, lengths, x0, S0, None, q_mode,
+        return DGPSSM._filter_records(self, who, fn, Y_records, control_records, lengths, x0, S0, None, q_mode,
                                       Y_train_std, records_per_pass, draws)
 
     def _filter_records(self, who, fn, Y_records, control_records, lengths, x0, S0, smooth, q_mode, Y_train_std, records_per_pass, draws=None):

@@ -1022,7 +1022,8 @@ def filter_particle_records_grouped(Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts,
     row with nothing observed); W_i = exp(L_i - max L), m_filt / S_filt the W-weighted mean and centred covariance, ess =
     (sum W)^2 / sum W^2; systematic resampling with unif[t], a_i = min(#{k: cdf_k <= (unif[t] + i) / N cdf_{N-1}}, N - 1), only for
     a row with an observed entry (otherwise the particles are kept, m_filt = m_pred and S_filt = S_pred bit for bit, ess = N).  No
-    adaptive resampling.  There is no smoothing (no `smooth` parameter, no `cross`): particle smoothing is not built.
+    adaptive resampling.  There is no smoothing (no `smooth` parameter, no `cross`): particle smoothing is not built into
+    this call, `smooth_particle_records_grouped` has it.
     Returns the dict of `filter_records_grouped` without cross, m_smooth and S_smooth, plus ess (G, R, steps) and log_evidence (G, R),
     the sum of lpd_joint over the rows with an observation: the SMC estimate of log p(y) of that record under that chain.  Pooled
     with EQUAL weights, (R, steps, J): predict_y, predict_y_var_total and lpd_gauss from (m_pred, S_pred) as the siblings; lpd_mix =
@@ -1031,7 +1032,14 @@ def filter_particle_records_grouped(Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts,
     length.  A track's arrays are bit-identical whatever the other groups, the other records, their order and records_per_pass are
     (draws permuted with them); every covariance is exactly symmetric ("Particle filtering").  SquaredExponential
     kernels only; R = 1 is a valid single-record call."""
-    who = "filter_particle_records_grouped"
+    return _particle_records_given("filter_particle_records_grouped", False, Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_records,
+                                   Y_records, Qs, CC, DD, log_Rchols, eps, unif, xi0, lengths, S0s, q_mode, Y_train_std, records_per_pass,
+                                   return_particles)
+
+
+def _particle_records_given(who, smooth, Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_records, Y_records, Qs, CC, DD, log_Rchols,
+                            eps, unif, xi0, lengths, S0s, q_mode, Y_train_std, records_per_pass, return_particles):
+    """The body of `filter_particle_records_grouped` and, with `smooth`, of `smooth_particle_records_grouped`."""
     shape = np.shape(Y_records)
     if len(shape) != 3 or shape[0] < 1 or shape[1] < 1:
         raise ValueError(f"{who}: Y_records: expected (R, steps, J) with at least one record and one row, got {shape}")
@@ -1046,12 +1054,14 @@ def filter_particle_records_grouped(Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts,
     N, pargs, keep = _pack_particles(who, G, R, steps, D, eps, unif, xi0, r["S0"] is not None, return_particles)
     m = _pack_summary(who, D, R * steps, CC, DD, log_Rchols, r["Y"].reshape(R * steps, r["J"]))
     out, extra, oargs = _particle_call(m, G, R, steps, D, N, bool(return_particles))
+    sm, sargs = _smooth_call(r, G, D, N, bool(return_particles)) if smooth else ({}, ())
     dp = _lib.dptr
     opt = lambda x: None if x is None else dp(x)
-    rc = _lib.load().ffvd_op_filter_particle_records_grouped(*args[:13], R, dp(r["x0"]), opt(r["S0"]), opt(r["ctrl"]), *args[16:], dp(m["CC"]),
-                                                             dp(m["DD"]), dp(m["sd"]), m["J"], dp(m["Y"]), r["rpp"], *pargs, *oargs)
+    entry = "ffvd_particle_smooth_records_grouped" if smooth else "ffvd_op_filter_particle_records_grouped"
+    rc = getattr(_lib.load(), entry)(*args[:13], R, dp(r["x0"]), opt(r["S0"]), opt(r["ctrl"]), *args[16:], dp(m["CC"]), dp(m["DD"]), dp(m["sd"]),
+                                     m["J"], dp(m["Y"]), r["rpp"], *pargs, *oargs, *sargs)
     _lib.check(rc, None, who)
-    return _particle_dict(r, G, out, extra, Y_train_std)
+    return _smooth_dict(_particle_dict(r, G, out, extra, Y_train_std), r, sm)
 
 
 def posterior_filter_particle_records_grouped(Zs, kerns, Xs, Qs, control_inputs, control_records, Y_records, CC, DD, log_Rchols, eps, unif, *,
@@ -1062,7 +1072,14 @@ def posterior_filter_particle_records_grouped(Zs, kerns, Xs, Qs, control_inputs,
     `filter_particle_records_grouped` computes, without the posteriors leaving the device.  The model and start arguments are
     `posterior_filter_records_grouped`'s (x0s None: every record of group g starts at Xs[g][-1]); eps, unif, xi0, return_particles and
     the returned dict are `filter_particle_records_grouped`'s."""
-    who = "posterior_filter_particle_records_grouped"
+    return _particle_records_posterior("posterior_filter_particle_records_grouped", False, Zs, kerns, Xs, Qs, control_inputs, control_records,
+                                       Y_records, CC, DD, log_Rchols, eps, unif, xi0, lengths, x0s, S0s, q_mode, Y_train_std, jitter,
+                                       groups_per_pass, records_per_pass, return_particles)
+
+
+def _particle_records_posterior(who, smooth, Zs, kerns, Xs, Qs, control_inputs, control_records, Y_records, CC, DD, log_Rchols, eps, unif, xi0,
+                                lengths, x0s, S0s, q_mode, Y_train_std, jitter, groups_per_pass, records_per_pass, return_particles):
+    """The body of `posterior_filter_particle_records_grouped` and, with `smooth`, of `posterior_smooth_particle_records_grouped`."""
     a = _pack_posterior_moment(who, Zs, kerns, Xs, Qs, control_inputs, 0, 0, None, q_mode, jitter, groups_per_pass)
     G, D, args = a["G"], a["D"], a["args"]
     r = _pack_records(who, G, D, args[11], x0s, control_records, Y_records, lengths, S0s, records_per_pass)
@@ -1070,13 +1087,79 @@ def posterior_filter_particle_records_grouped(Zs, kerns, Xs, Qs, control_inputs,
     N, pargs, keep = _pack_particles(who, G, R, steps, D, eps, unif, xi0, r["S0"] is not None, return_particles)
     m = _pack_summary(who, D, R * steps, CC, DD, log_Rchols, r["Y"].reshape(R * steps, r["J"]))
     out, extra, oargs = _particle_call(m, G, R, steps, D, N, bool(return_particles))
+    sm, sargs = _smooth_call(r, G, D, N, bool(return_particles)) if smooth else ({}, ())
     dp = _lib.dptr
     opt = lambda x: None if x is None else dp(x)
-    rc = _lib.load().ffvd_op_posterior_filter_particle_records_grouped(*args[:17], R, opt(r["x0"]), opt(r["S0"]), opt(r["ctrl"]), steps,
-                                                                       dp(m["CC"]), dp(m["DD"]), dp(m["sd"]), m["J"], dp(m["Y"]), r["rpp"],
-                                                                       *pargs, *oargs, None)
+    entry = "ffvd_posterior_particle_smooth_records_grouped" if smooth else "ffvd_op_posterior_filter_particle_records_grouped"
+    rc = getattr(_lib.load(), entry)(*args[:17], R, opt(r["x0"]), opt(r["S0"]), opt(r["ctrl"]), steps, dp(m["CC"]), dp(m["DD"]), dp(m["sd"]),
+                                     m["J"], dp(m["Y"]), r["rpp"], *pargs, *oargs, *sargs, None)
     _lib.check(rc, None, who)
-    return _particle_dict(r, G, out, extra, Y_train_std)
+    return _smooth_dict(_particle_dict(r, G, out, extra, Y_train_std), r, sm)
+
+
+SMOOTH_PARTICLE_KEYS = ("m_smooth", "S_smooth", "ess_smooth")
+SMOOTH_PARTICLE_STACKS = ("w_smooth", "weights", "trans_mean", "trans_var")
+
+
+def _smooth_call(r, G, D, N, return_particles):
+    """Output arrays and the trailing arguments (lengths, m_smooth .. trans_var) of the two particle smoothing entry points."""
+    import ctypes
+    R, steps, dp = r["R"], r["steps"], _lib.dptr
+    sm = dict(m_smooth=np.empty((G, R, steps, D)), S_smooth=np.empty((G, R, steps, D, D)), ess_smooth=np.empty((G, R, steps)))
+    if return_particles:
+        sm.update(w_smooth=np.empty((G, R, steps, N)), weights=np.empty((G, R, steps, N)), trans_mean=np.empty((G, R, steps, N, D)),
+                  trans_var=np.empty((G, R, steps, N, D)))
+    sm["_lengths"] = np.ascontiguousarray(r["lengths"], dtype=np.int32)                 # (kept alive with the outputs)
+    args = (sm["_lengths"].ctypes.data_as(ctypes.POINTER(ctypes.c_int)),) + tuple(dp(sm[k]) for k in SMOOTH_PARTICLE_KEYS) + \
+        tuple(dp(sm[k]) if return_particles else None for k in SMOOTH_PARTICLE_STACKS)
+    return sm, args
+
+
+def _smooth_dict(res, r, sm):
+    """`res` plus the smoother's arrays, NaN at and beyond a record's length."""
+    dead = ~r["live"]
+    for k, v in sm.items():
+        if not k.startswith("_"):
+            v[:, dead] = np.nan
+            res[k] = v
+    return res
+
+
+def smooth_particle_records_grouped(Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_records, Y_records, Qs, CC, DD, log_Rchols,
+                                    eps, unif, *, xi0=None, lengths=None, S0s=None, q_mode="reference", Y_train_std=1.0, records_per_pass=0,
+                                    return_particles=False):
+    """`filter_particle_records_grouped` followed by the marginal particle smoother of every track in ONE call
+    (`ffvd_particle_smooth_records_grouped`): the forward filter / backward smoother of Doucet, Godsill & Andrieu (2000) on the
+    equally weighted sets the filter carries.  The parameters, their checks and every key of the returned dict are
+    `filter_particle_records_grouped`'s (the filter's arrays bit for bit); no GP is evaluated beyond the filter's and no draw is
+    added, so the result is a deterministic function of the filter's run.  Per track of n = lengths[r] rows, with X_t the set carried
+    into row t, mu_t = X_t + m(X_t, c_t) the transition mean and s_t = v(X_t, c_t) + Q the transition variance (X^-_t = mu_t +
+    eps[t] sqrt(s_t)), W_t the filter's weights and a_t its ancestors: w_smooth[n-1] = W_{n-1} / sum W_{n-1}; for t = n-2 .. 0, with
+    x_j = X^-_{t+1,j}: log f_ij = -1/2 sum_d ((x_jd - mu_{t+1,id})^2 / s_{t+1,id} + log s_{t+1,id}), c_j = log sum_i exp log f_ij,
+    omega_i = sum_j w_smooth[t+1, j] exp(log f_ij - c_j), w_smooth[t, k] = the sum of omega_i over the i with a_t[i] = k (exactly 0
+    for a particle without offspring); nothing is renormalised inside the recursion.
+    Adds to the dict, per track: m_smooth (G, R, steps, D) and S_smooth (G, R, steps, D, D), the w_smooth-weighted mean and centred
+    covariance of the X^-_t (exactly symmetric), and ess_smooth (G, R, steps) = (sum w)^2 / sum w^2.  With return_particles also
+    weights (W_t), w_smooth (G, R, steps, N), trans_mean and trans_var (G, R, steps, N, D) beside particles and ancestors.  NaN at and
+    beyond a record's length; a record of one row returns its filtered row.  A track's arrays are bit-identical whatever the other
+    groups, the other records, their order and records_per_pass are ("Particle smoothing").  The estimate
+    converges at the usual 1 / sqrt(N) rate and does not collapse onto one path as the genealogy of `ancestors` does; joint
+    trajectory draws (backward simulation) are not built."""
+    return _particle_records_given("smooth_particle_records_grouped", True, Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_records,
+                                   Y_records, Qs, CC, DD, log_Rchols, eps, unif, xi0, lengths, S0s, q_mode, Y_train_std, records_per_pass,
+                                   return_particles)
+
+
+def posterior_smooth_particle_records_grouped(Zs, kerns, Xs, Qs, control_inputs, control_records, Y_records, CC, DD, log_Rchols, eps, unif, *,
+                                              xi0=None, lengths=None, x0s=None, S0s=None, q_mode="reference", Y_train_std=1.0, jitter=JITTER,
+                                              groups_per_pass=0, records_per_pass=0, return_particles=False):
+    """The collapsed posterior of G groups and `smooth_particle_records_grouped` in ONE call
+    (`ffvd_posterior_particle_smooth_records_grouped`): what `conditionals_multi_output.collapse_u_mean_grouped` followed by
+    `smooth_particle_records_grouped` computes, without the posteriors leaving the device.  The parameters are
+    `posterior_filter_particle_records_grouped`'s, the returned dict is `smooth_particle_records_grouped`'s."""
+    return _particle_records_posterior("posterior_smooth_particle_records_grouped", True, Zs, kerns, Xs, Qs, control_inputs, control_records,
+                                       Y_records, CC, DD, log_Rchols, eps, unif, xi0, lengths, x0s, S0s, q_mode, Y_train_std, jitter,
+                                       groups_per_pass, records_per_pass, return_particles)
 
 
 def _pack_forecast(who, n, horizon, origins=None, stride=1, model=None):

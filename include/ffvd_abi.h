@@ -867,7 +867,8 @@ int  ffvd_op_posterior_filter_cubature_records_grouped(int kind, int G, int n_mo
  * log_evidence (G x R) is the sum of lpd_joint over the rows that have an observation: the SMC estimate of log p(y) of that record
  * under that group.  Pooled over the groups with equal weights (R x steps x J): y_mean, y_var_total and lpd_gauss as
  * ffvd_op_filter_records_grouped on (m_pred, S_pred); lpd_mix = log mean_g exp(lpd[g]), the density of the mixture of all G * N
- * particles' emissions.  There is no smoother and no cross-covariance (particle smoothing is not built).
+ * particles' emissions.  There is no smoother and no cross-covariance in this call (the particle smoother is
+ * ffvd_particle_smooth_records_grouped).
  * Outputs, each of which may be NULL: m_pred, m_filt (G x R x steps x D), S_pred, S_filt (.. x D x D), lpd (.. x J), lpd_joint, ess
  * (G x R x steps), the pooled four, log_evidence, particles (G x R x steps x N x D: the X^-) and ancestors (G x R x steps x N).
  * The kernel rows of all particles of all tracks that share a Gamma are one dense product on the fp64 matrix cores (the product of
@@ -904,6 +905,63 @@ int  ffvd_op_posterior_filter_particle_records_grouped(int kind, int G, int n_mo
                                                        double *lpd_joint, double *y_mean, double *y_var_total, double *lpd_mix,
                                                        double *lpd_gauss, double *ess, double *log_evidence, double *particles,
                                                        int *ancestors, double *U_means);
+
+/* ffvd_op_filter_particle_records_grouped followed by the marginal particle smoother (forward filter / backward smoother of Doucet,
+ * Godsill & Andrieu 2000) of every (group, record) track, on the equally weighted sets the filter carries.  The arguments and the
+ * filter outputs are those of ffvd_op_filter_particle_records_grouped, bit for bit; no GP is evaluated beyond the filter's and no
+ * draw is added: the result is a deterministic function of the filter's run.  lengths (R ints, each in [1, steps]; NULL: every record
+ * has `steps` rows) gives the rows n of every record: the recursion of a track starts at its row n - 1, and the new outputs are NaN at
+ * and beyond it.  Per track, with X_t the set carried into row t (X_0 the start set), c_t the control row and (m, v) the GP conditional:
+ *   kept       trans_mean[t] = X_t + m(X_t, c_t),  trans_var[t] = v(X_t, c_t) + Q: the two terms of the filter's
+ *              X^-_t = trans_mean[t] + eps[t] sqrt(trans_var[t]), bit for bit (computed through every row of the call)
+ *   weights    weights[t] = W_t of the filter: exp(L_i - max L), L_i the sum of l_ij over the observed j in ascending j; 1 for a row
+ *              with nothing observed
+ *   last row   w_smooth[n-1] = W_{n-1} / sum W_{n-1}
+ *   backward   for t = n-2 .. 0, with x_j = X^-_{t+1,j}, mu_i = trans_mean[t+1, i], s_i = trans_var[t+1, i]:
+ *              log f_ij = -1/2 sum_d ((x_jd - mu_id)^2 / s_id + log s_id)
+ *              c_j = max_i log f_ij + log sum_i exp(log f_ij - max)                       (i ascending)
+ *              omega_i = sum_j w_smooth[t+1, j] exp(log f_ij - c_j)                       (j ascending, every exponent <= 0)
+ *              w_smooth[t, k] = sum of omega_i over the i with ancestors[t, i] = k        (i ascending; no offspring: exactly 0)
+ *              nothing is renormalised inside the recursion
+ *   moments    m_smooth[t] = sum_k w_k X^-_tk / sum_k w_k;  S_smooth[t]: the w-weighted centred covariance, exactly symmetric;
+ *              ess_smooth[t] = (sum w)^2 / sum w^2
+ * New outputs, each of which may be NULL: m_smooth (G x R x steps x D), S_smooth (.. x D x D), ess_smooth (G x R x steps), w_smooth and
+ * weights (G x R x steps x N), trans_mean and trans_var (G x R x steps x N x D).  A record of one row returns its filtered row.  Every
+ * sum has an order fixed by N alone: a track does not depend on the other groups, the other records, their order or records_per_pass
+ * (bit for bit).  The device holds (3 D + 3) N doubles and N ints per track row beside the filter's buffers (FFVD_ENOMEM if they cannot
+ * be had).  Limits: those of ffvd_op_filter_particle_records_grouped.  G = 0, R = 0 or steps = 0: FFVD_OK, nothing is touched. */
+int  ffvd_particle_smooth_records_grouped(int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M,
+                                          int P, int D, const double *logvariances, const double *loglengthscales, const double *fs,
+                                          const double *const *q_sqrts, int q_mode, int R, const double *x_lasts, const double *S0s,
+                                          const double *ctrl, int C, int steps, const double *log_Qs, const double *CC,
+                                          const double *DD, const double *noise_std, int J, const double *Y_obs,
+                                          int records_per_pass, int N, const double *eps, long long eps_stride_g,
+                                          long long eps_stride_r, const double *unif, long long unif_stride_g,
+                                          long long unif_stride_r, const double *xi0, long long xi0_stride_g, long long xi0_stride_r,
+                                          double *m_pred, double *S_pred, double *m_filt, double *S_filt, double *lpd,
+                                          double *lpd_joint, double *y_mean, double *y_var_total, double *lpd_mix, double *lpd_gauss,
+                                          double *ess, double *log_evidence, double *particles, int *ancestors, const int *lengths,
+                                          double *m_smooth, double *S_smooth, double *ess_smooth, double *w_smooth, double *weights,
+                                          double *trans_mean, double *trans_var);
+
+/* ffvd_op_posterior_grouped followed by ffvd_particle_smooth_records_grouped WITHOUT the posteriors leaving the device: the
+ * arguments of ffvd_op_posterior_filter_particle_records_grouped, then lengths and the new outputs of the call above; U_means stays
+ * last. */
+int  ffvd_posterior_particle_smooth_records_grouped(int kind, int G, int n_models, const double *Zs, int M, int P, int D,
+                                                    const double *logvariances, const double *loglengthscales, const double *Xs,
+                                                    const double *ctrl_fit, int C, int T, const double *log_Qs, double jitter,
+                                                    int groups_per_pass, int q_mode, int R, const double *x0s, const double *S0s,
+                                                    const double *ctrl_roll, int steps, const double *CC, const double *DD,
+                                                    const double *noise_std, int J, const double *Y_obs, int records_per_pass,
+                                                    int N, const double *eps, long long eps_stride_g, long long eps_stride_r,
+                                                    const double *unif, long long unif_stride_g, long long unif_stride_r,
+                                                    const double *xi0, long long xi0_stride_g, long long xi0_stride_r,
+                                                    double *m_pred, double *S_pred, double *m_filt, double *S_filt, double *lpd,
+                                                    double *lpd_joint, double *y_mean, double *y_var_total, double *lpd_mix,
+                                                    double *lpd_gauss, double *ess, double *log_evidence, double *particles,
+                                                    int *ancestors, const int *lengths, double *m_smooth, double *S_smooth,
+                                                    double *ess_smooth, double *w_smooth, double *weights, double *trans_mean,
+                                                    double *trans_var, double *U_means);
 
 /* Rolling-origin multi-step forecasts in one call: ffvd_op_filter_grouped (same arguments, same outputs, each of which may be NULL),
  * then from every origin o = origins[b] (n_origins rows of the record, strictly ascending, 0 <= o <= steps - 1 - horizon) `horizon`
