@@ -191,6 +191,18 @@ _SIGNATURES = {
                                                                  _dp, _dp, C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_int] +
                                                                 _PARTICLE_DRAWS + [_dp] * 13 + [C.POINTER(C.c_int), C.POINTER(C.c_int)] +
                                                                 [_dp] * 7 + [_dp]),
+    # the two particle filter calls, then lengths, B, unif_bs and its strides, trajectories, traj_index, m_traj .. trans_var
+    "ffvd_particle_backsim_records_grouped": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), _dp, C.c_int, C.c_int, C.c_int, _dp,
+                                                        _dp, _dp, C.POINTER(C.c_void_p), C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, C.c_int,
+                                                        _dp, _dp, _dp, _dp, C.c_int, _dp, C.c_int] + _PARTICLE_DRAWS + [_dp] * 13 +
+                                                       [C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, _dp, C.c_longlong, C.c_longlong, _dp,
+                                                        C.POINTER(C.c_int)] + [_dp] * 6),
+    "ffvd_posterior_particle_backsim_records_grouped": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp,
+                                                                  _dp, C.c_int, C.c_int, _dp, C.c_double, C.c_int, C.c_int, C.c_int, _dp,
+                                                                  _dp, _dp, C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_int] +
+                                                                 _PARTICLE_DRAWS + [_dp] * 13 +
+                                                                 [C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, _dp, C.c_longlong,
+                                                                  C.c_longlong, _dp, C.POINTER(C.c_int)] + [_dp] * 6 + [_dp]),
     "ffvd_op_forecast_grouped": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp,
                                            C.POINTER(C.c_void_p), C.c_int, _dp, _dp, _dp, C.c_int, C.c_int, _dp,
                                            _dp, _dp, _dp, C.c_int, _dp] + [_dp] * 13 +

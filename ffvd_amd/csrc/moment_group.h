@@ -208,6 +208,34 @@ void launch_mg_psm_keep(hipStream_t stream, const MomentGroupArgs &a, const Mome
                         const MomentParticleArgs &p, const MomentParticleSmoothArgs &q, int s);
 // after the last pass; n_max: the longest record of the call
 void launch_mg_psm_smooth(hipStream_t stream, const MomentFilterArgs &f, const MomentParticleSmoothArgs &q, int n_max);
+// the weights kernel of the smoother alone: q.weights, the last row of q.w_smooth (NaN at and beyond a record's length in both)
+void launch_mg_psm_weights(hipStream_t stream, const MomentFilterArgs &f, const MomentParticleSmoothArgs &q);
+
+// Particle backward simulation (moment_particle_backsim.hip; DESIGN.md section 9, "Particle backward simulation"): B joint trajectories
+// per track by forward filtering / backward simulation (Godsill, Doucet & West 2004) on the stacks the smoother's keep launch and its
+// weights kernel store.  One launch walks t = n - 1 .. 0 for every (track, trajectory), one more forms the moments over the
+// trajectories.  No GP evaluation; the uniforms are the caller's, [..][steps][B] through a group and a record stride in doubles, each
+// of which may be 0.
+// Limits: the particle filter's; 1 <= B <= MG_PBS_MAXB; V * B < 2^31 (grid x).  The stacks are the smoother's without cnorm and
+// omega, plus (D + 1) N doubles per track row for 1 / s and sum log s; trajectories take B * D doubles and B ints per track row.
+constexpr int MG_PBS_MAXB = 4096;
+struct MomentParticleBacksimArgs {
+    int V, R, steps, N, D, B;        // V = G * R tracks, track v is record v % R of group v / R
+    const int *lens;                 // [R] or nullptr
+    const double *particles;         // [V][steps][N][D]
+    const int *ancestors;            // [V][steps][N]
+    const double *trans_mean, *trans_var;  // [V][steps][N][D]
+    const double *weights;           // [V][steps][N]
+    double *inv_var, *log_var;       // [V][steps][N][D], [V][steps][N]: 1 / s and sum_d log s_d of the rows 1 .. n - 1
+    const double *unif;              // the uniforms of (g, r) at unif + g * unif_g + r * unif_r, [steps][B]
+    long long unif_g, unif_r;
+    int *traj_index;                 // [V][steps][B]: k_t, -1 at and beyond a record's length
+    double *trajectories;            // [V][B][steps][D]: X^-_{t, k_t}, NaN at and beyond a record's length
+    double *m_traj, *S_traj;         // [V][steps][D], [V][steps][D][D]
+    double *lag_cov;                 // [V][steps][D][D]: row index = component of x_t; NaN at row n - 1
+};
+// after launch_mg_psm_weights
+void launch_mg_pbs(hipStream_t stream, const MomentParticleBacksimArgs &b);
 
 // Cubature forecasts (moment_cubature_fan.hip; DESIGN.md section 9, "Cubature forecasts"): the fan's tracks and indexing (MomentFanArgs)
 // with the cubature rule above and no measurement update.  MomentGroupArgs as for the linearised forecasts; MomentLinearFanArgs is

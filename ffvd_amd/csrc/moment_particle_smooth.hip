@@ -29,54 +29,12 @@
 // No atomics, nothing waits on another workgroup, every sum has an order fixed by N alone.  The addresses that depend on computed
 // values are the fold's: every ancestor is clamped into [0, N) before it is compared, and the run's bounds lie in [0, N] by
 // construction of the search.  A track whose length is <= t + 1 does nothing at row t.
-#include "moment_step.h"
+#include "moment_particle_smooth.h"
 
 namespace ffvd {
 namespace {
 
-constexpr int PSM_RED = MG_MAXD * (MG_MAXD + 1) / 2;      // the widest reduction: the upper triangle of a covariance
 constexpr int PSM_CHUNK = 256;                            // rows of a staged chunk: (2 D + 1) * 2 KiB of LDS, 34 KiB at D = 8
-
-// v[k] <- the sum over the workgroup, the same in every thread: wavefront butterflies, then the four wavefronts in ascending order
-// (the shape of the weight kernel's sums)
-template <int K>
-__device__ __forceinline__ void psm_sum(double (&v)[K], double (*red)[PSM_RED]) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        double s = v[k];
-#pragma unroll
-        for (int mm = 32; mm > 0; mm >>= 1) s += __shfl_xor(s, mm);
-        if (lane == 0) red[wave][k] = s;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) v[k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
-}
-
-__device__ __forceinline__ double psm_max(double v, double (*red)[PSM_RED]) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-#pragma unroll
-    for (int mm = 32; mm > 0; mm >>= 1) v = fmax(v, __shfl_xor(v, mm));
-    if (lane == 0) red[wave][0] = v;
-    __syncthreads();
-    return fmax(fmax(red[0][0], red[1][0]), fmax(red[2][0], red[3][0]));
-}
-
-// log f without its constant.  Every rounding is spelled out (one subtraction, one product and one fused multiply-add per dim), so
-// that the normaliser and the backward kernel form the same bits for the same pair and every exponent of the latter is <= 0.
-template <int D, class TX, class TM, class TI>
-__device__ __forceinline__ double psm_logf(const TX &x, const TM &mu, const TI &is, const double ls) {
-    double q = 0.0;
-#pragma unroll
-    for (int d = 0; d < D; ++d) {
-        const double u = x[d] - mu[d];
-        q = __builtin_fma(u * u, is[d], q);
-    }
-    return -0.5 * (q + ls);
-}
 
 __device__ __forceinline__ int psm_len(const MomentParticleSmoothArgs &q, int v) {
     const int n = q.lens ? q.lens[v % q.R] : q.steps;
@@ -377,6 +335,18 @@ void launch_mg_psm_smooth(hipStream_t stream, const MomentFilterArgs &f, const M
             hipLaunchKernelGGL(mg_psm_fold_kernel, slabs, dim3(256), 0, stream, q, t);                                              \
         }                                                                                                                           \
         hipLaunchKernelGGL(HIP_KERNEL_NAME(mg_psm_moments_kernel<d>), rows, dim3(256), 0, stream, q);                                \
+        break;
+    MG_SWITCH_D(q.D, MG_CASE)
+#undef MG_CASE
+}
+
+// The weights kernel alone (the particle backward simulation of moment_particle_backsim.hip draws its last row from W_{n-1}); it also
+// writes the last row of q.w_smooth and NaN beyond every length.
+void launch_mg_psm_weights(hipStream_t stream, const MomentFilterArgs &f, const MomentParticleSmoothArgs &q) {
+    const dim3 rows((unsigned)((size_t)q.V * q.steps));
+#define MG_CASE(d)                                                                                                                  \
+    case d:                                                                                                                         \
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(mg_psm_weights_kernel<d>), rows, dim3(256), 0, stream, f, q);                             \
         break;
     MG_SWITCH_D(q.D, MG_CASE)
 #undef MG_CASE

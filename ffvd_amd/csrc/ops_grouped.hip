@@ -1131,6 +1131,17 @@ struct ParticleReq {
     double *particles;                           // [G][R][steps][N][D] or NULL
     int *ancestors;                              // [G][R][steps][N] or NULL
 };
+// The backward-simulation request beside a ParticleSmoothReq (moment_particle_backsim.hip): B trajectories per track from the
+// caller's uniforms; with it the smoother's recursion is not run (its m_smooth .. w_smooth stay NULL)
+struct ParticleBacksimReq {
+    int B;
+    const double *unif_bs;                       // [G or 1][R or 1][steps][B]
+    long long unif_g, unif_r;
+    double *trajectories;                        // [G][R][B][steps][D]
+    int *traj_index;                             // [G][R][steps][B]
+    double *m_traj, *S_traj, *lag_cov;           // [G][R][steps][D], [..][D][D], [..][D][D]
+    bool any_output() const { return trajectories || traj_index || m_traj || S_traj || lag_cov; }
+};
 // The smoothing request beside a ParticleReq (moment_particle_smooth.hip): the rows of every record and the outputs, each of which
 // may be NULL
 struct ParticleSmoothReq {
@@ -1138,7 +1149,10 @@ struct ParticleSmoothReq {
     double *m_smooth, *S_smooth, *ess_smooth;    // [G][R][steps][D], [..][D][D], [G][R][steps]
     double *w_smooth, *weights;                  // [G][R][steps][N]
     double *trans_mean, *trans_var;              // [G][R][steps][N][D]
-    bool any_output() const { return m_smooth || S_smooth || ess_smooth || w_smooth || weights || trans_mean || trans_var; }
+    const ParticleBacksimReq *bs = nullptr;
+    bool any_output() const {
+        return m_smooth || S_smooth || ess_smooth || w_smooth || weights || trans_mean || trans_var || (bs && bs->any_output());
+    }
 };
 bool particle_smooth_ok(const ParticleSmoothReq &q, int R, int steps) {
     if (q.lengths)
@@ -1152,6 +1166,18 @@ bool particle_strides_ok(long long sg, long long sr, long long inner, int R) {
 }
 size_t particle_extent(long long sg, long long sr, long long inner, int G, int R) {
     return (size_t)inner * (sr ? R : 1) * (sg ? G : 1);
+}
+// the checks of a backward-simulation request that need no device: B, the strides, G * R * B within the grid, unif_bs in [0, 1)
+bool particle_backsim_ok(const ParticleBacksimReq &q, int G, int R, int steps, bool nothing) {
+    if (q.B < 1 || q.B > MG_PBS_MAXB) return false;
+    const long long nu = (long long)steps * q.B;
+    if (!particle_strides_ok(q.unif_g, q.unif_r, nu, R)) return false;
+    if (nothing) return true;
+    if ((long long)G * R > ((1LL << 31) - 1) / q.B || !q.unif_bs) return false;
+    const size_t n_u = particle_extent(q.unif_g, q.unif_r, nu, G, R);
+    for (size_t e = 0; e < n_u; ++e)
+        if (!(q.unif_bs[e] >= 0.0 && q.unif_bs[e] < 1.0)) return false;
+    return true;
 }
 // the checks of a particle request that need no device: N, the strides, the arrays (finite draws, unif in [0, 1))
 bool particle_ok(const ParticleReq &q, int G, int R, int steps, int D, bool with_S0, bool nothing) {
@@ -1283,6 +1309,8 @@ int mg_records_run(Scratch &sc, const std::string &who, int method, int G, int n
                  (!(q.ancestors || sq) || pa.ancestors), who);
     }
     MomentParticleSmoothArgs ps{};
+    MomentParticleBacksimArgs pb{};
+    const ParticleBacksimReq *bq = par && sq ? sq->bs : nullptr;
     int n_max = steps;
     if (par && sq) {                                                                   // the smoother's stacks: (3 D + 3) N doubles per track row
         int *lens = nullptr;
@@ -1295,11 +1323,23 @@ int mg_records_run(Scratch &sc, const std::string &who, int method, int G, int n
         }
         ps.V = V; ps.R = R; ps.steps = steps; ps.N = pq->N; ps.D = D; ps.lens = lens; ps.particles = pa.particles; ps.ancestors = pa.ancestors;
         ps.trans_mean = sc.alloc<double>(nm_x * pq->N); ps.trans_var = sc.alloc<double>(nm_x * pq->N);
-        ps.weights = sc.alloc<double>(nlj * pq->N); ps.w_smooth = sc.alloc<double>(nlj * pq->N); ps.cnorm = sc.alloc<double>(nlj * pq->N);
-        ps.omega = sc.alloc<double>((size_t)V * pq->N);
-        ps.m_smooth = sc.alloc<double>(nm_x); ps.S_smooth = sc.alloc<double>(nS_x); ps.ess_smooth = sc.alloc<double>(nlj);
-        OP_CHECK(ps.trans_mean && ps.trans_var && ps.weights && ps.w_smooth && ps.cnorm && ps.omega && ps.m_smooth && ps.S_smooth &&
-                 ps.ess_smooth, who);
+        ps.weights = sc.alloc<double>(nlj * pq->N); ps.w_smooth = sc.alloc<double>(nlj * pq->N);
+        OP_CHECK(ps.trans_mean && ps.trans_var && ps.weights && ps.w_smooth, who);
+        if (!bq) {
+            ps.cnorm = sc.alloc<double>(nlj * pq->N); ps.omega = sc.alloc<double>((size_t)V * pq->N);
+            ps.m_smooth = sc.alloc<double>(nm_x); ps.S_smooth = sc.alloc<double>(nS_x); ps.ess_smooth = sc.alloc<double>(nlj);
+            OP_CHECK(ps.cnorm && ps.omega && ps.m_smooth && ps.S_smooth && ps.ess_smooth, who);
+        } else {                                                                       // the trajectories: B * D doubles and B ints per track row
+            const long long nu = (long long)steps * bq->B;
+            pb.V = V; pb.R = R; pb.steps = steps; pb.N = pq->N; pb.D = D; pb.B = bq->B; pb.lens = lens; pb.particles = pa.particles;
+            pb.ancestors = pa.ancestors; pb.trans_mean = ps.trans_mean; pb.trans_var = ps.trans_var; pb.weights = ps.weights;
+            pb.unif_g = bq->unif_g; pb.unif_r = bq->unif_r;
+            pb.unif = sc.upload(bq->unif_bs, particle_extent(bq->unif_g, bq->unif_r, nu, G, R));
+            pb.inv_var = sc.alloc<double>(nm_x * pq->N); pb.log_var = sc.alloc<double>(nlj * pq->N);
+            pb.traj_index = sc.alloc<int>(nlj * bq->B); pb.trajectories = sc.alloc<double>(nm_x * bq->B);
+            pb.m_traj = sc.alloc<double>(nm_x); pb.S_traj = sc.alloc<double>(nS_x); pb.lag_cov = sc.alloc<double>(nS_x);
+            OP_CHECK(pb.unif && pb.inv_var && pb.log_var && pb.traj_index && pb.trajectories && pb.m_traj && pb.S_traj && pb.lag_cov, who);
+        }
     }
     OP_TRY(hipMemsetAsync(lf.K, 0, (size_t)lf.units * lf.Tp * Mp * sizeof(double), sc.stream));          // rows no pass fills stay zeros
     if (int rc = bg.launch(sc, G, nm, M, D, Mp, hv.len, dW, dq, q_mode, dU)) return rc;
@@ -1323,8 +1363,19 @@ int mg_records_run(Scratch &sc, const std::string &who, int method, int G, int n
         }
     }
     if (smooth) launch_mg_smooth(sc.stream, sa);
-    if (par && sq) launch_mg_psm_smooth(sc.stream, fa, ps, n_max);
+    if (bq) {
+        launch_mg_psm_weights(sc.stream, fa, ps);
+        launch_mg_pbs(sc.stream, pb);
+    } else if (par && sq) launch_mg_psm_smooth(sc.stream, fa, ps, n_max);
     OP_TRY(hipGetLastError());
+    if (bq) {
+        const size_t Bn = (size_t)bq->B;
+        auto down = [&](void *dst, const void *src, size_t bytes) { return !dst || sc.download(dst, src, bytes); };
+        if (!down(bq->trajectories, pb.trajectories, nm_x * Bn * sizeof(double)) || !down(bq->traj_index, pb.traj_index, nlj * Bn * sizeof(int)) ||
+            !down(bq->m_traj, pb.m_traj, nm_x * sizeof(double)) || !down(bq->S_traj, pb.S_traj, nS_x * sizeof(double)) ||
+            !down(bq->lag_cov, pb.lag_cov, nS_x * sizeof(double)))
+            return set_error(nullptr, FFVD_EDEVICE, who + ": copying the results back failed");
+    }
     if (par && sq) {
         const size_t N = (size_t)pq->N;
         auto down = [&](double *dst, const double *src, size_t n) { return !dst || sc.download(dst, src, n * sizeof(double)); };
@@ -1511,6 +1562,8 @@ int records_given(const std::string &who, int method, int kind, int G, int n_mod
     if (int rc = records_checks(who, method, kind, G, n_models, M, P, D, C, steps, q_mode, f, rq, nothing, pq, S0s != nullptr)) return rc;
     if (sq && !nothing && !particle_smooth_ok(*sq, R, steps))
         return set_error(nullptr, FFVD_EINVAL, bad + " (every entry of lengths must lie in [1, steps])");
+    if (sq && sq->bs && !particle_backsim_ok(*sq->bs, G, R, steps, nothing))
+        return set_error(nullptr, FFVD_EINVAL, bad + " (1 <= B <= 4096, unif_bs in [0, 1), strides 0 or contiguous and G * R * B < 2^31 are needed)");
     if (nothing) return FFVD_OK;
     if (!Lm_inverse_seqs || !Zs || !logvariances || !loglengthscales || !fs || !x_lasts || !log_Qs || (C > 0 && !ctrl) ||
         !filter_arrays_ok(f, R * steps, m_pred, S_pred, pq && (pq->ess || pq->log_evidence || pq->particles || pq->ancestors || (sq && sq->any_output()))))
@@ -1548,6 +1601,8 @@ int records_posterior(const std::string &who, int method, int kind, int G, int n
     if (int rc = records_checks(who, method, kind, G, n_models, M, P, D, C, steps, q_mode, f, rq, nothing, pq, S0s != nullptr)) return rc;
     if (sq && !nothing && !particle_smooth_ok(*sq, R, steps))
         return set_error(nullptr, FFVD_EINVAL, bad + " (every entry of lengths must lie in [1, steps])");
+    if (sq && sq->bs && !particle_backsim_ok(*sq->bs, G, R, steps, nothing))
+        return set_error(nullptr, FFVD_EINVAL, bad + " (1 <= B <= 4096, unif_bs in [0, 1), strides 0 or contiguous and G * R * B < 2^31 are needed)");
     if (!pg_scalars_ok(kind, G, n_models, M, P, D, C, T, groups_per_pass, jitter)) return set_error(nullptr, FFVD_EINVAL, bad);
     if (nothing) return FFVD_OK;
     if (!Zs || !logvariances || !loglengthscales || !Xs || !log_Qs || (C > 0 && (!ctrl_fit || !ctrl_roll)) ||
@@ -1709,6 +1764,54 @@ extern "C" int ffvd_posterior_particle_smooth_records_grouped(int kind, int G, i
 }
 #undef FFVD_PARTICLE_SMOOTH_PARAMS
 #undef FFVD_PARTICLE_SMOOTH_REQ
+
+// The same two filter calls followed by the backward simulation of B joint trajectories per track (moment_particle_backsim.hip): the
+// smoothing calls' launches up to the weights kernel, then one launch for all (track, trajectory) recursions and one for the moments.
+// The filter outputs, weights, trans_mean and trans_var are those of the smoothing calls bit for bit.
+#define FFVD_PARTICLE_BACKSIM_PARAMS                                                                                                         \
+    const int *lengths, int B, const double *unif_bs, long long unif_bs_stride_g, long long unif_bs_stride_r, double *trajectories,         \
+        int *traj_index, double *m_traj, double *S_traj, double *lag_cov, double *weights, double *trans_mean, double *trans_var
+#define FFVD_PARTICLE_BACKSIM_REQ                                                                                                            \
+    const ParticleBacksimReq bq{B, unif_bs, unif_bs_stride_g, unif_bs_stride_r, trajectories, traj_index, m_traj, S_traj, lag_cov};          \
+    ParticleSmoothReq sq{lengths, nullptr, nullptr, nullptr, nullptr, weights, trans_mean, trans_var};                                       \
+    sq.bs = &bq
+extern "C" int ffvd_particle_backsim_records_grouped(int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M,
+                                                     int P, int D, const double *logvariances, const double *loglengthscales, const double *fs,
+                                                     const double *const *q_sqrts, int q_mode, int R, const double *x_lasts, const double *S0s,
+                                                     const double *ctrl, int C, int steps, const double *log_Qs, const double *CC,
+                                                     const double *DD, const double *noise_std, int J, const double *Y_obs,
+                                                     int records_per_pass, FFVD_PARTICLE_PARAMS, double *m_pred, double *S_pred,
+                                                     double *m_filt, double *S_filt, double *lpd, double *lpd_joint, double *y_mean,
+                                                     double *y_var_total, double *lpd_mix, double *lpd_gauss, double *ess,
+                                                     double *log_evidence, double *particles, int *ancestors, FFVD_PARTICLE_BACKSIM_PARAMS) {
+    FFVD_PARTICLE_REQ;
+    FFVD_PARTICLE_BACKSIM_REQ;
+    return records_given("ffvd_particle_backsim_records_grouped", MG_METHOD_PARTICLE, kind, G, n_models, Lm_inverse_seqs, Zs, M, P, D,
+                         logvariances, loglengthscales, fs, q_sqrts, q_mode, R, x_lasts, S0s, ctrl, C, steps, log_Qs, CC, DD, noise_std, J, Y_obs,
+                         records_per_pass, m_pred, S_pred, m_filt, S_filt, nullptr, lpd, lpd_joint, nullptr, nullptr, y_mean, y_var_total, lpd_mix,
+                         lpd_gauss, &pq, &sq);
+}
+
+extern "C" int ffvd_posterior_particle_backsim_records_grouped(int kind, int G, int n_models, const double *Zs, int M, int P, int D,
+                                                               const double *logvariances, const double *loglengthscales, const double *Xs,
+                                                               const double *ctrl_fit, int C, int T, const double *log_Qs, double jitter,
+                                                               int groups_per_pass, int q_mode, int R, const double *x0s, const double *S0s,
+                                                               const double *ctrl_roll, int steps, const double *CC, const double *DD,
+                                                               const double *noise_std, int J, const double *Y_obs, int records_per_pass,
+                                                               FFVD_PARTICLE_PARAMS, double *m_pred, double *S_pred, double *m_filt,
+                                                               double *S_filt, double *lpd, double *lpd_joint, double *y_mean,
+                                                               double *y_var_total, double *lpd_mix, double *lpd_gauss, double *ess,
+                                                               double *log_evidence, double *particles, int *ancestors,
+                                                               FFVD_PARTICLE_BACKSIM_PARAMS, double *U_means) {
+    FFVD_PARTICLE_REQ;
+    FFVD_PARTICLE_BACKSIM_REQ;
+    return records_posterior("ffvd_posterior_particle_backsim_records_grouped", MG_METHOD_PARTICLE, kind, G, n_models, Zs, M, P, D, logvariances,
+                             loglengthscales, Xs, ctrl_fit, C, T, log_Qs, jitter, groups_per_pass, q_mode, R, x0s, S0s, ctrl_roll, steps, CC, DD,
+                             noise_std, J, Y_obs, records_per_pass, m_pred, S_pred, m_filt, S_filt, nullptr, lpd, lpd_joint, nullptr, nullptr,
+                             y_mean, y_var_total, lpd_mix, lpd_gauss, U_means, &pq, &sq);
+}
+#undef FFVD_PARTICLE_BACKSIM_PARAMS
+#undef FFVD_PARTICLE_BACKSIM_REQ
 #undef FFVD_PARTICLE_PARAMS
 #undef FFVD_PARTICLE_REQ
 #undef FFVD_RECORDS_GIVEN_PARAMS

@@ -664,9 +664,30 @@ class DGPSSM:
         return DGPSSM._records_particle(self, "smooth_records_particle", "smooth_particle_records_grouped", Y_records, control_records,
                                         num_particles, lengths, x0, S0, q_mode, Y_train_std, records_per_pass, seed, noise, return_particles)
 
+    def sample_records_particle(self, Y_records, control_records=None, *, num_particles=256, num_trajectories=64, lengths=None, x0=None,
+                                S0=None, q_mode="reference", Y_train_std=1.0, records_per_pass=0, seed=None, noise="shared",
+                                return_particles=False):
+        """`filter_records_particle` followed by the backward simulation of `num_trajectories` joint smoothed trajectories of every
+        (chain, record) track in the same call: draws of whole paths given the whole record, for statistics that the marginal
+        smoother of `smooth_records_particle` cannot give (excursions, first-passage times, sums over a window, the lag-one
+        covariance).  The parameters, the checks and the two forms (collapsed U: ONE `posterior_backsim_particle_records_grouped`
+        call; explicit U: `kernel_pre_cal` once, then `backsim_particle_records_grouped`) are `filter_records_particle`'s.  The
+        filter's draws are drawn first and in `filter_records_particle`'s order, so the same seed gives the same filter, bit for bit;
+        the uniforms of the backward simulation (steps, num_trajectories), with the leading dimensions of `noise`, are drawn after
+        them.  prediction.backsim_particle_records_grouped has the method and the dict that is returned: the filter's, plus
+        trajectories (S, R, B, steps, D), traj_index (S, R, steps, B), m_traj, S_traj and lag_cov, with return_particles also weights,
+        trans_mean and trans_var."""
+        B = num_trajectories
+        if isinstance(B, bool) or not isinstance(B, (int, np.integer)) or not 1 <= B <= 4096:
+            raise ValueError(f"sample_records_particle: num_trajectories: expected an integer in [1, 4096], got {num_trajectories!r}")
+        return DGPSSM._records_particle(self, "sample_records_particle", "backsim_particle_records_grouped", Y_records, control_records,
+                                        num_particles, lengths, x0, S0, q_mode, Y_train_std, records_per_pass, seed, noise, return_particles,
+                                        int(B))
+
     def _records_particle(self, who, fn, Y_records, control_records, num_particles, lengths, x0, S0, q_mode, Y_train_std, records_per_pass,
-                          seed, noise, return_particles):
-        """The body of `filter_records_particle` and `smooth_records_particle`: the checks and the draws, then `_filter_records`."""
+                          seed, noise, return_particles, num_trajectories=None):
+        """The body of `filter_records_particle`, `smooth_records_particle` and `sample_records_particle`: the checks and the draws,
+        then `_filter_records`.  num_trajectories: the uniforms of the backward simulation are drawn after the filter's draws."""
         if noise not in ("shared", "per_record", "independent"):
             raise ValueError(f"{who}: noise: expected \"shared\", \"per_record\" or \"independent\", got {noise!r}")
         N = num_particles
@@ -683,6 +704,8 @@ class DGPSSM:
         rng = np.random.default_rng(seed) if seed is not None else self._rng
         draws = dict(eps=rng.standard_normal(lead + (steps, N, D)), unif=rng.random(lead + (steps,)),
                      xi0=None if S0 is None else rng.standard_normal(lead + (N, D)), return_particles=return_particles)
+        if num_trajectories is not None:
+            draws["unif_bs"] = rng.random(lead + (steps, num_trajectories))
         return DGPSSM._filter_records(self, who, fn, Y_records, control_records, lengths, x0, S0, None, q_mode,
                                       Y_train_std, records_per_pass, draws)
 
@@ -718,7 +741,7 @@ class DGPSSM:
         tail = ()
         if draws is not None:                                     # the particle filter: eps and unif follow log_Rchols, no `smooth`
             del kw["smooth"]
-            tail = (draws["eps"], draws["unif"])
+            tail = (draws["eps"], draws["unif"]) + ((draws["unif_bs"],) if "unif_bs" in draws else ())
             kw.update(xi0=draws["xi0"], return_particles=draws["return_particles"])
         if self.U_collapse:
             return getattr(pr, "posterior_" + fn)(lay.Z, lay.kernel, [self._X_chains[s_] for s_ in range(S)], self.Q, self.control_inputs,

@@ -1038,8 +1038,9 @@ def filter_particle_records_grouped(Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts,
 
 
 def _particle_records_given(who, smooth, Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_records, Y_records, Qs, CC, DD, log_Rchols,
-                            eps, unif, xi0, lengths, S0s, q_mode, Y_train_std, records_per_pass, return_particles):
-    """The body of `filter_particle_records_grouped` and, with `smooth`, of `smooth_particle_records_grouped`."""
+                            eps, unif, xi0, lengths, S0s, q_mode, Y_train_std, records_per_pass, return_particles, unif_bs=None):
+    """The body of `filter_particle_records_grouped`, with `smooth` of `smooth_particle_records_grouped`, and with `smooth` and
+    `unif_bs` of `backsim_particle_records_grouped`."""
     shape = np.shape(Y_records)
     if len(shape) != 3 or shape[0] < 1 or shape[1] < 1:
         raise ValueError(f"{who}: Y_records: expected (R, steps, J) with at least one record and one row, got {shape}")
@@ -1054,10 +1055,11 @@ def _particle_records_given(who, smooth, Lm_inverse_seqs, Zs, kerns, U_vals, q_s
     N, pargs, keep = _pack_particles(who, G, R, steps, D, eps, unif, xi0, r["S0"] is not None, return_particles)
     m = _pack_summary(who, D, R * steps, CC, DD, log_Rchols, r["Y"].reshape(R * steps, r["J"]))
     out, extra, oargs = _particle_call(m, G, R, steps, D, N, bool(return_particles))
-    sm, sargs = _smooth_call(r, G, D, N, bool(return_particles)) if smooth else ({}, ())
+    sm, sargs = _smooth_or_backsim_call(who, r, G, D, N, bool(return_particles), smooth, unif_bs)
     dp = _lib.dptr
     opt = lambda x: None if x is None else dp(x)
-    entry = "ffvd_particle_smooth_records_grouped" if smooth else "ffvd_op_filter_particle_records_grouped"
+    entry = ("ffvd_particle_backsim_records_grouped" if unif_bs is not None else "ffvd_particle_smooth_records_grouped") if smooth else \
+        "ffvd_op_filter_particle_records_grouped"
     rc = getattr(_lib.load(), entry)(*args[:13], R, dp(r["x0"]), opt(r["S0"]), opt(r["ctrl"]), *args[16:], dp(m["CC"]), dp(m["DD"]), dp(m["sd"]),
                                      m["J"], dp(m["Y"]), r["rpp"], *pargs, *oargs, *sargs)
     _lib.check(rc, None, who)
@@ -1078,8 +1080,10 @@ def posterior_filter_particle_records_grouped(Zs, kerns, Xs, Qs, control_inputs,
 
 
 def _particle_records_posterior(who, smooth, Zs, kerns, Xs, Qs, control_inputs, control_records, Y_records, CC, DD, log_Rchols, eps, unif, xi0,
-                                lengths, x0s, S0s, q_mode, Y_train_std, jitter, groups_per_pass, records_per_pass, return_particles):
-    """The body of `posterior_filter_particle_records_grouped` and, with `smooth`, of `posterior_smooth_particle_records_grouped`."""
+                                lengths, x0s, S0s, q_mode, Y_train_std, jitter, groups_per_pass, records_per_pass, return_particles,
+                                unif_bs=None):
+    """The body of `posterior_filter_particle_records_grouped`, with `smooth` of `posterior_smooth_particle_records_grouped`, and with
+    `smooth` and `unif_bs` of `posterior_backsim_particle_records_grouped`."""
     a = _pack_posterior_moment(who, Zs, kerns, Xs, Qs, control_inputs, 0, 0, None, q_mode, jitter, groups_per_pass)
     G, D, args = a["G"], a["D"], a["args"]
     r = _pack_records(who, G, D, args[11], x0s, control_records, Y_records, lengths, S0s, records_per_pass)
@@ -1087,10 +1091,11 @@ def _particle_records_posterior(who, smooth, Zs, kerns, Xs, Qs, control_inputs, 
     N, pargs, keep = _pack_particles(who, G, R, steps, D, eps, unif, xi0, r["S0"] is not None, return_particles)
     m = _pack_summary(who, D, R * steps, CC, DD, log_Rchols, r["Y"].reshape(R * steps, r["J"]))
     out, extra, oargs = _particle_call(m, G, R, steps, D, N, bool(return_particles))
-    sm, sargs = _smooth_call(r, G, D, N, bool(return_particles)) if smooth else ({}, ())
+    sm, sargs = _smooth_or_backsim_call(who, r, G, D, N, bool(return_particles), smooth, unif_bs)
     dp = _lib.dptr
     opt = lambda x: None if x is None else dp(x)
-    entry = "ffvd_posterior_particle_smooth_records_grouped" if smooth else "ffvd_op_posterior_filter_particle_records_grouped"
+    entry = ("ffvd_posterior_particle_backsim_records_grouped" if unif_bs is not None else "ffvd_posterior_particle_smooth_records_grouped") \
+        if smooth else "ffvd_op_posterior_filter_particle_records_grouped"
     rc = getattr(_lib.load(), entry)(*args[:17], R, opt(r["x0"]), opt(r["S0"]), opt(r["ctrl"]), steps, dp(m["CC"]), dp(m["DD"]), dp(m["sd"]),
                                      m["J"], dp(m["Y"]), r["rpp"], *pargs, *oargs, *sargs, None)
     _lib.check(rc, None, who)
@@ -1116,11 +1121,12 @@ def _smooth_call(r, G, D, N, return_particles):
 
 
 def _smooth_dict(res, r, sm):
-    """`res` plus the smoother's arrays, NaN at and beyond a record's length."""
+    """`res` plus the arrays of the smoother or of the backward simulation, NaN (traj_index -1) at and beyond a record's length."""
     dead = ~r["live"]
     for k, v in sm.items():
         if not k.startswith("_"):
-            v[:, dead] = np.nan
+            rows = np.swapaxes(v, 2, 3) if k == "trajectories" else v          # (G, R, B, steps, D): a view with the rows third
+            rows[:, dead] = -1 if k == "traj_index" else np.nan
             res[k] = v
     return res
 
@@ -1144,7 +1150,7 @@ def smooth_particle_records_grouped(Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts,
     beyond a record's length; a record of one row returns its filtered row.  A track's arrays are bit-identical whatever the other
     groups, the other records, their order and records_per_pass are ("Particle smoothing").  The estimate
     converges at the usual 1 / sqrt(N) rate and does not collapse onto one path as the genealogy of `ancestors` does; joint
-    trajectory draws (backward simulation) are not built."""
+    trajectory draws (backward simulation) are `backsim_particle_records_grouped`'s."""
     return _particle_records_given("smooth_particle_records_grouped", True, Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_records,
                                    Y_records, Qs, CC, DD, log_Rchols, eps, unif, xi0, lengths, S0s, q_mode, Y_train_std, records_per_pass,
                                    return_particles)
@@ -1160,6 +1166,93 @@ def posterior_smooth_particle_records_grouped(Zs, kerns, Xs, Qs, control_inputs,
     return _particle_records_posterior("posterior_smooth_particle_records_grouped", True, Zs, kerns, Xs, Qs, control_inputs, control_records,
                                        Y_records, CC, DD, log_Rchols, eps, unif, xi0, lengths, x0s, S0s, q_mode, Y_train_std, jitter,
                                        groups_per_pass, records_per_pass, return_particles)
+
+
+BACKSIM_MAX_B = 4096
+BACKSIM_KEYS = ("trajectories", "traj_index", "m_traj", "S_traj", "lag_cov")
+BACKSIM_STACKS = ("weights", "trans_mean", "trans_var")
+
+
+def _smooth_or_backsim_call(who, r, G, D, N, return_particles, smooth, unif_bs):
+    """`_smooth_call`, `_backsim_call` or nothing, by the form of the particle call"""
+    if not smooth:
+        return {}, ()
+    return _smooth_call(r, G, D, N, return_particles) if unif_bs is None else _backsim_call(who, r, G, D, N, return_particles, unif_bs)
+
+
+def _backsim_call(who, r, G, D, N, return_particles, unif_bs):
+    """Checks of `unif_bs` (before the library is loaded), output arrays and the trailing arguments (lengths, B, unif_bs and its
+    strides, trajectories .. trans_var) of the two backward-simulation entry points."""
+    import ctypes
+    R, steps, dp = r["R"], r["steps"], _lib.dptr
+    u = np.asarray(unif_bs, dtype=np.float64)
+    if u.ndim not in (2, 3, 4) or u.shape[-1] < 1:
+        raise ValueError(f"{who}: unif_bs: expected ({steps}, B), ({R}, {steps}, B) or ({G}, {R}, {steps}, B), got {u.shape}")
+    B = u.shape[-1]
+    if B > BACKSIM_MAX_B:
+        raise ValueError(f"{who}: unif_bs: the number of trajectories B must lie in [1, {BACKSIM_MAX_B}], got {B}")
+    u, ug, ur = _particle_layout(who, "unif_bs", u, (steps, B), G, R)
+    if np.any(u < 0.0) or np.any(u >= 1.0):
+        raise ValueError(f"{who}: unif_bs: every uniform must lie in [0, 1)")
+    if G * R * B >= 2 ** 31:
+        raise ValueError(f"{who}: G * R * B = {G * R * B} must stay below 2^31")
+    sm = dict(trajectories=np.empty((G, R, B, steps, D)), traj_index=np.empty((G, R, steps, B), dtype=np.int32), m_traj=np.empty((G, R, steps, D)),
+              S_traj=np.empty((G, R, steps, D, D)), lag_cov=np.empty((G, R, steps, D, D)))
+    if return_particles:
+        sm.update(weights=np.empty((G, R, steps, N)), trans_mean=np.empty((G, R, steps, N, D)), trans_var=np.empty((G, R, steps, N, D)))
+    sm["_lengths"], sm["_unif_bs"] = np.ascontiguousarray(r["lengths"], dtype=np.int32), u     # (kept alive with the outputs)
+    ip = ctypes.POINTER(ctypes.c_int)
+    args = (sm["_lengths"].ctypes.data_as(ip), B, dp(u), ug, ur, dp(sm["trajectories"]), sm["traj_index"].ctypes.data_as(ip)) + \
+        tuple(dp(sm[k]) for k in BACKSIM_KEYS[2:]) + tuple(dp(sm[k]) if return_particles else None for k in BACKSIM_STACKS)
+    return sm, args
+
+
+def backsim_particle_records_grouped(Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_records, Y_records, Qs, CC, DD, log_Rchols,
+                                     eps, unif, unif_bs, *, xi0=None, lengths=None, S0s=None, q_mode="reference", Y_train_std=1.0,
+                                     records_per_pass=0, return_particles=False):
+    """`filter_particle_records_grouped` followed by the backward simulation of B joint smoothed trajectories of every track in ONE
+    call (`ffvd_particle_backsim_records_grouped`): forward filtering / backward simulation (Godsill, Doucet & West 2004) on the
+    equally weighted sets the filter carries.  Where `smooth_particle_records_grouped` weights the particles of one row, this call
+    draws whole paths, so a statistic of a path (an excursion, a first-passage time, a sum over a window, the increment x_{t+1} -
+    x_t) has a sample, at B N density evaluations per row where the marginal smoother needs N^2.  The parameters, their checks and
+    every key of the filter's dict are `filter_particle_records_grouped`'s (the filter's arrays bit for bit); no GP is evaluated
+    beyond the filter's.  unif_bs: the caller's uniforms in [0, 1), (steps, B) shared by all tracks, (R, steps, B) shared by the
+    groups, or (G, R, steps, B); B = unif_bs.shape[-1], 1 <= B <= 4096.
+    Per track of n = lengths[r] rows and trajectory b, with u = unif_bs[t, b] and the notation of `smooth_particle_records_grouped`:
+    row n-1: cdf = the running sum of W_{n-1} in index order, tot = cdf[N-1], k_{n-1} = min(#{k: cdf_k <= u tot}, N - 1); for
+    t = n-2 .. 0, with x = X^-_{t+1, k_{t+1}}: log f_i = -1/2 sum_d ((x_d - mu_{t+1,id})^2 / s_{t+1,id} + log s_{t+1,id}), p_i =
+    exp(log f_i - max_i log f_i) (so tot >= 1: nothing divides by a sum that can vanish), cdf the running sum of p, i* =
+    min(#{i: cdf_i <= u tot}, N - 1) and k_t = ancestors[t, i*].  Conditional on the filter's run P(k_t = k) = w_smooth[t, k].
+    Adds to the dict, per track: traj_index (G, R, steps, B) int32, k_t (-1 at and beyond a record's length); trajectories
+    (G, R, B, steps, D) = particles[t, k_t], a gather, bit for bit; m_traj (G, R, steps, D), the mean over b; S_traj
+    (G, R, steps, D, D), the centred covariance with divisor B (exactly symmetric); lag_cov (G, R, steps, D, D), lag_cov[t] =
+    mean_b (x_t^b - m_traj[t]) (x_{t+1}^b - m_traj[t+1])^T, row index the component of x_t, not symmetric, NaN at the record's last
+    row.  With return_particles also weights (W_t), trans_mean and trans_var beside particles and ancestors.  NaN at and beyond a
+    record's length; a record of one row draws from its filtered weights.  Trajectory b depends on column b of unif_bs alone; a
+    track's arrays are bit-identical whatever the other groups, the other records, their order and records_per_pass are (DESIGN.md
+    section 9, "Particle backward simulation")."""
+    return _particle_records_given("backsim_particle_records_grouped", True, Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_records,
+                                   Y_records, Qs, CC, DD, log_Rchols, eps, unif, xi0, lengths, S0s, q_mode, Y_train_std, records_per_pass,
+                                   return_particles, _need(unif_bs, "backsim_particle_records_grouped"))
+
+
+def posterior_backsim_particle_records_grouped(Zs, kerns, Xs, Qs, control_inputs, control_records, Y_records, CC, DD, log_Rchols, eps, unif,
+                                               unif_bs, *, xi0=None, lengths=None, x0s=None, S0s=None, q_mode="reference", Y_train_std=1.0,
+                                               jitter=JITTER, groups_per_pass=0, records_per_pass=0, return_particles=False):
+    """The collapsed posterior of G groups and `backsim_particle_records_grouped` in ONE call
+    (`ffvd_posterior_particle_backsim_records_grouped`): what `conditionals_multi_output.collapse_u_mean_grouped` followed by
+    `backsim_particle_records_grouped` computes, without the posteriors leaving the device.  The parameters are
+    `posterior_filter_particle_records_grouped`'s plus unif_bs, the returned dict is `backsim_particle_records_grouped`'s."""
+    return _particle_records_posterior("posterior_backsim_particle_records_grouped", True, Zs, kerns, Xs, Qs, control_inputs, control_records,
+                                       Y_records, CC, DD, log_Rchols, eps, unif, xi0, lengths, x0s, S0s, q_mode, Y_train_std, jitter,
+                                       groups_per_pass, records_per_pass, return_particles,
+                                       _need(unif_bs, "posterior_backsim_particle_records_grouped"))
+
+
+def _need(unif_bs, who):
+    if unif_bs is None:
+        raise ValueError(f"{who}: unif_bs: the uniforms of the backward simulation are needed, (steps, B), (R, steps, B) or (G, R, steps, B)")
+    return unif_bs
 
 
 def _pack_forecast(who, n, horizon, origins=None, stride=1, model=None):

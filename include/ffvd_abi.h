@@ -963,6 +963,64 @@ int  ffvd_posterior_particle_smooth_records_grouped(int kind, int G, int n_model
                                                     double *ess_smooth, double *w_smooth, double *weights, double *trans_mean,
                                                     double *trans_var, double *U_means);
 
+/* ffvd_op_filter_particle_records_grouped followed by the backward simulation of B joint smoothed trajectories per (group, record)
+ * track (forward filtering / backward simulation, Godsill, Doucet & West 2004) on the equally weighted sets the filter carries.  The
+ * arguments up to and including `lengths` and the filter outputs are those of ffvd_particle_smooth_records_grouped, bit for bit; no
+ * GP is evaluated beyond the filter's.  The uniforms are the caller's: unif_bs, a block of steps x B per track, each in [0, 1),
+ * indexed through a group and a record stride in doubles (0 = shared, otherwise the stride of a contiguous array).  Per track of n
+ * rows and trajectory b, with u = unif_bs[t, b] and the notation of the smoothing call:
+ *   row n-1    cdf = the running sum of W_{n-1} in index order, tot = cdf[N-1];  k_{n-1} = min(#{k: cdf_k <= u tot}, N - 1)
+ *   backward   for t = n-2 .. 0, with x = X^-_{t+1, k_{t+1}}, mu_i = trans_mean[t+1, i], s_i = trans_var[t+1, i]:
+ *              log f_i = -1/2 sum_d ((x_d - mu_id)^2 / s_id + log s_id),  p_i = exp(log f_i - max_i log f_i)    (tot >= 1 always)
+ *              cdf = the running sum of p in index order;  i* = min(#{i: cdf_i <= u tot}, N - 1);  k_t = ancestors[t, i*]
+ *              every index is clamped into [0, N) before it addresses anything
+ *   outputs    traj_index[t, b] = k_t (-1 at and beyond n);  trajectories[b, t, :] = X^-_{t, k_t}, a gather, bit for bit;
+ *              m_traj[t]: the mean over b;  S_traj[t]: the centred covariance with divisor B, exactly symmetric;
+ *              lag_cov[t] = (1 / B) sum_b (x_t^b - m_traj[t]) (x_{t+1}^b - m_traj[t+1])^T, row index = component of x_t, not
+ *              symmetric, NaN at t = n - 1
+ * Conditional on the filter's run P(k_t = k) = w_smooth[t, k] of ffvd_particle_smooth_records_grouped.  Outputs, each of which may be
+ * NULL: trajectories (G x R x B x steps x D), traj_index (G x R x steps x B), m_traj (G x R x steps x D), S_traj and lag_cov
+ * (.. x D x D), then weights, trans_mean and trans_var of the smoothing call (the stacks the recursion reads); all NaN at and beyond
+ * a record's length; a record of one row draws from its filtered weights.  Trajectory b depends on column b of unif_bs alone, a
+ * track does not depend on the other groups, the other records, their order or records_per_pass (bit for bit).  The device holds
+ * (4 D + 3) N doubles and N ints per track row beside the filter's buffers, and B D doubles and B ints per track row for the
+ * trajectories (FFVD_ENOMEM if they cannot be had).  Limits: those of ffvd_op_filter_particle_records_grouped; 1 <= B <= 4096;
+ * G * R * B < 2^31.  G = 0, R = 0 or steps = 0: FFVD_OK, nothing is touched. */
+int  ffvd_particle_backsim_records_grouped(int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M,
+                                           int P, int D, const double *logvariances, const double *loglengthscales, const double *fs,
+                                           const double *const *q_sqrts, int q_mode, int R, const double *x_lasts, const double *S0s,
+                                           const double *ctrl, int C, int steps, const double *log_Qs, const double *CC,
+                                           const double *DD, const double *noise_std, int J, const double *Y_obs,
+                                           int records_per_pass, int N, const double *eps, long long eps_stride_g,
+                                           long long eps_stride_r, const double *unif, long long unif_stride_g,
+                                           long long unif_stride_r, const double *xi0, long long xi0_stride_g, long long xi0_stride_r,
+                                           double *m_pred, double *S_pred, double *m_filt, double *S_filt, double *lpd,
+                                           double *lpd_joint, double *y_mean, double *y_var_total, double *lpd_mix, double *lpd_gauss,
+                                           double *ess, double *log_evidence, double *particles, int *ancestors, const int *lengths,
+                                           int B, const double *unif_bs, long long unif_bs_stride_g, long long unif_bs_stride_r,
+                                           double *trajectories, int *traj_index, double *m_traj, double *S_traj, double *lag_cov,
+                                           double *weights, double *trans_mean, double *trans_var);
+
+/* ffvd_op_posterior_grouped followed by ffvd_particle_backsim_records_grouped WITHOUT the posteriors leaving the device: the
+ * arguments of ffvd_op_posterior_filter_particle_records_grouped, then lengths, B, unif_bs with its strides and the new outputs of
+ * the call above; U_means stays last. */
+int  ffvd_posterior_particle_backsim_records_grouped(int kind, int G, int n_models, const double *Zs, int M, int P, int D,
+                                                     const double *logvariances, const double *loglengthscales, const double *Xs,
+                                                     const double *ctrl_fit, int C, int T, const double *log_Qs, double jitter,
+                                                     int groups_per_pass, int q_mode, int R, const double *x0s, const double *S0s,
+                                                     const double *ctrl_roll, int steps, const double *CC, const double *DD,
+                                                     const double *noise_std, int J, const double *Y_obs, int records_per_pass,
+                                                     int N, const double *eps, long long eps_stride_g, long long eps_stride_r,
+                                                     const double *unif, long long unif_stride_g, long long unif_stride_r,
+                                                     const double *xi0, long long xi0_stride_g, long long xi0_stride_r,
+                                                     double *m_pred, double *S_pred, double *m_filt, double *S_filt, double *lpd,
+                                                     double *lpd_joint, double *y_mean, double *y_var_total, double *lpd_mix,
+                                                     double *lpd_gauss, double *ess, double *log_evidence, double *particles,
+                                                     int *ancestors, const int *lengths, int B, const double *unif_bs,
+                                                     long long unif_bs_stride_g, long long unif_bs_stride_r, double *trajectories,
+                                                     int *traj_index, double *m_traj, double *S_traj, double *lag_cov, double *weights,
+                                                     double *trans_mean, double *trans_var, double *U_means);
+
 /* Rolling-origin multi-step forecasts in one call: ffvd_op_filter_grouped (same arguments, same outputs, each of which may be NULL),
  * then from every origin o = origins[b] (n_origins rows of the record, strictly ascending, 0 <= o <= steps - 1 - horizon) `horizon`
  * steps of ffvd_op_moment_grouped started at the FILTERED state of row o, N(m_filt[g][o], S_filt[g][o]), with the control rows
