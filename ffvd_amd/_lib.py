@@ -181,6 +181,15 @@ _SIGNATURES = {
                                                                     _dp, C.c_int, C.c_int, _dp, C.c_double, C.c_int, C.c_int, C.c_int, _dp,
                                                                     _dp, _dp, C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_int] +
                                                                    _PARTICLE_DRAWS + [_dp] * 13 + [C.POINTER(C.c_int), _dp]),
+    # the argument lists of the two particle filter calls: the fully adapted filter (the optimal proposal)
+    "ffvd_particle_adapted_records_grouped": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), _dp, C.c_int, C.c_int, C.c_int, _dp,
+                                                        _dp, _dp, C.POINTER(C.c_void_p), C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, C.c_int,
+                                                        _dp, _dp, _dp, _dp, C.c_int, _dp, C.c_int] + _PARTICLE_DRAWS + [_dp] * 13 +
+                                                       [C.POINTER(C.c_int)]),
+    "ffvd_posterior_particle_adapted_records_grouped": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp,
+                                                                  _dp, C.c_int, C.c_int, _dp, C.c_double, C.c_int, C.c_int, C.c_int, _dp,
+                                                                  _dp, _dp, C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_int] +
+                                                                 _PARTICLE_DRAWS + [_dp] * 13 + [C.POINTER(C.c_int), _dp]),
     # the two particle filter calls, then lengths and m_smooth .. trans_var (U_means stays last)
     "ffvd_particle_smooth_records_grouped": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), _dp, C.c_int, C.c_int, C.c_int, _dp,
                                                        _dp, _dp, C.POINTER(C.c_void_p), C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, C.c_int,

@@ -183,6 +183,22 @@ int mg_prec_records_per_pass(int G, int n_models, int D, int Mp, int unit_per_gr
 // launch t of steps + 1: the weight kernel, then (t < steps) the rows kernel and the product kernel
 void launch_mg_prec_step(hipStream_t stream, const MomentGroupArgs &a, const MomentFilterArgs &f, const MomentRecordArgs &rc,
                          const MomentLinearFanArgs &l, const MomentParticleArgs &p, int t);
+// the rows kernel's launch of step t < steps alone (host code only: for the units that bring a weight kernel of their own)
+void launch_mg_prec_rows(hipStream_t stream, const MomentGroupArgs &a, const MomentRecordArgs &rc, const MomentLinearFanArgs &l,
+                         const MomentParticleArgs &p, int t);
+
+// Fully adapted particle filtering of many records (moment_particle_adapted.hip; DESIGN.md section 9, "Adapted particle filtering"):
+// the tracks, passes, stacks, draws and limits of the particle filter above with the optimal proposal: the parents are weighted by
+// p(y_t | parent) before anything is drawn, resampled, and the children are drawn from p(x_t | parent, y_t).  Its weight kernel
+// replaces the bootstrap one; the rows kernel and the product kernel run unchanged.  In this form MomentParticleArgs::particles is
+// the equally weighted FILTERED set after the row (X_{t+1}, not X^-) and ancestors[t, i] indexes the set carried INTO row t.
+// Between the weighting and the draw only the parents' transition mean and variance are kept.
+struct MomentParticleAdaptedArgs {
+    double *mu, *sv;                 // [tracks][N][D]: X_t + mean and v + Q of the row in flight (trans_mean, trans_var of the smoother)
+};
+// launch t of steps + 1: the adapted weight kernel, then (t < steps) the rows kernel and the product kernel
+void launch_mg_parec_step(hipStream_t stream, const MomentGroupArgs &a, const MomentFilterArgs &f, const MomentRecordArgs &rc,
+                          const MomentLinearFanArgs &l, const MomentParticleArgs &p, const MomentParticleAdaptedArgs &q, int t);
 
 // Particle smoothing of many records (moment_particle_smooth.hip; DESIGN.md section 9, "Particle smoothing"): the marginal
 // forward-filter / backward-smoother on the sets the particle filter above carries.  The driver keeps the filter's device stacks

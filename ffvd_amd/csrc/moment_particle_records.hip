@@ -435,4 +435,18 @@ void launch_mg_prec_step(hipStream_t stream, const MomentGroupArgs &a, const Mom
     launch_mg_lfan_var(stream, l.K, a.gam, l.vpart, l.Tp, a.Mp, l.nr, l.units);
 }
 
+// the rows kernel of step t < steps alone, for a unit with a weight kernel of its own (moment_particle_adapted.hip)
+void launch_mg_prec_rows(hipStream_t stream, const MomentGroupArgs &a, const MomentRecordArgs &rc, const MomentLinearFanArgs &l,
+                         const MomentParticleArgs &p, int t) {
+    const int nsl = (p.N + MG_PREC_SLAB - 1) / MG_PREC_SLAB;
+    const dim3 rows((unsigned)((size_t)a.G * a.D * nsl));
+    switch (a.D) {
+#define MG_CASE(d)                                                                                                                  \
+    case d: hipLaunchKernelGGL(HIP_KERNEL_NAME(mg_prec_rows_kernel<d>), rows, dim3(256), 0, stream, a, t, rc, l, p); break;
+        MG_CASE(1) MG_CASE(2) MG_CASE(3) MG_CASE(4) MG_CASE(5) MG_CASE(6) MG_CASE(7) MG_CASE(8)
+#undef MG_CASE
+        default: break;
+    }
+}
+
 }  // namespace ffvd

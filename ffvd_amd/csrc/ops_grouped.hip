@@ -622,7 +622,7 @@ bool mg_scalars_ok(int kind, int G, int n_models, int M, int P, int D, int C, in
            (steps == 0 || G <= ((1LL << 31) - 1) / steps / D / D);
 }
 // the propagation rule of the filter's launches (mg_run)
-enum { MG_METHOD_MOMENT = 0, MG_METHOD_LINEAR = 1, MG_METHOD_CUBATURE = 2, MG_METHOD_PARTICLE = 3 };    // (cubature and particle: the records calls and the forecasts)
+enum { MG_METHOD_MOMENT = 0, MG_METHOD_LINEAR = 1, MG_METHOD_CUBATURE = 2, MG_METHOD_PARTICLE = 3, MG_METHOD_ADAPTED = 4 };    // (cubature and particle: the records calls and the forecasts; adapted: the records calls)
 // the trailing summary block of the entry points: asked for when anything in it is given
 bool mg_summary_wanted(const SummaryReq &q) {
     return q.CC || q.DD || q.noise_std || q.J != 0 || q.Y_test || q.n_test != 0 || q.y_mean || q.y_var || q.y_var_total || q.lpd || q.lpd_gauss;
@@ -1117,6 +1117,12 @@ const char *const mg_crecords_se_only =
     " (the cubature filter of many records is built for the SE kernel only: its kernel rows are SE-ARD's)";
 const char *const mg_precords_se_only =
     " (the particle filter of many records is built for the SE kernel only: its kernel rows are SE-ARD's)";
+const char *const mg_arecords_se_only =
+    " (the adapted particle filter of many records is built for the SE kernel only: its kernel rows are SE-ARD's)";
+// the two rules that take a ParticleReq: the bootstrap filter and the fully adapted one (moment_particle_adapted.hip)
+bool mg_particle_rule(int method) { return method == MG_METHOD_PARTICLE || method == MG_METHOD_ADAPTED; }
+const char *const mg_adapted_no_smoother =
+    " (the adapted particle filter has no smoother and no backward simulation: they stand on the bootstrap filter's sets)";
 // The particle request beside a RecordsReq (MG_METHOD_PARTICLE): N particles per track, the caller's draws with their (group, record)
 // strides in doubles -- each 0 or the stride of a contiguous array -- and the outputs the Gaussian rules do not have
 struct ParticleReq {
@@ -1262,7 +1268,7 @@ int mg_records_run(Scratch &sc, const std::string &who, int method, int G, int n
     const int Mp = round_up(M, NB), R = rq.R, J = flt.J, upg = dq ? 1 : 0;
     const int V = G * R;                                                               // tracks of the call (V * steps * D * D < 2^31)
     const size_t nm_x = (size_t)V * steps * D, nS_x = nm_x * D, nlpd = (size_t)V * steps * J, nlj = (size_t)V * steps;
-    const bool cub = method == MG_METHOD_CUBATURE, par = method == MG_METHOD_PARTICLE;
+    const bool cub = method == MG_METHOD_CUBATURE, par = mg_particle_rule(method), ada = method == MG_METHOD_ADAPTED;
     const int nrow = cub ? mg_crec_rows(D) : par ? pq->N : 1;                          // rows of K per track
     if (par)
         if (int rc = particle_fits(who, G, nm, D, Mp, upg, pq->N)) return rc;
@@ -1307,6 +1313,11 @@ int mg_records_run(Scratch &sc, const std::string &who, int method, int G, int n
         pa.ancestors = q.ancestors || sq ? sc.alloc<int>(nlj * q.N) : nullptr;
         OP_CHECK(pa.eps && pa.unif && (!dS0 || pa.xi0) && pa.xstate && pa.pmean && pa.ess && (!(q.particles || sq) || pa.particles) &&
                  (!(q.ancestors || sq) || pa.ancestors), who);
+    }
+    MomentParticleAdaptedArgs pd{};
+    if (ada) {                                                                         // (mu, s) of the parents of the row in flight
+        pd.mu = sc.alloc<double>((size_t)G * Rp * pq->N * D); pd.sv = sc.alloc<double>((size_t)G * Rp * pq->N * D);
+        OP_CHECK(pd.mu && pd.sv, who);
     }
     MomentParticleSmoothArgs ps{};
     MomentParticleBacksimArgs pb{};
@@ -1356,6 +1367,7 @@ int mg_records_run(Scratch &sc, const std::string &who, int method, int G, int n
         lf.nr = (lf.shared ? G * ra.Rp : ra.Rp) * nrow;
         for (int t = 0; t <= steps; ++t) {
             if (cub) launch_mg_crec_step(sc.stream, a, fa, ra, lf, coff, t);
+            else if (ada) launch_mg_parec_step(sc.stream, a, fa, ra, lf, pa, pd, t);
             else if (par) {
                 launch_mg_prec_step(sc.stream, a, fa, ra, lf, pa, t);
                 if (sq && t < steps) launch_mg_psm_keep(sc.stream, a, ra, lf, pa, ps, t);   // (mu, s) of step t, before the next weight launch
@@ -1533,12 +1545,12 @@ int records_checks(const std::string &who, int method, int kind, int G, int n_mo
     nothing = false;
     if (kind != FFVD_KERNEL_SE)
         return set_error(nullptr, FFVD_EINVAL, bad + (method == MG_METHOD_CUBATURE ? mg_crecords_se_only : method == MG_METHOD_PARTICLE
-                                                                                                       ? mg_precords_se_only : mg_records_se_only));
+                                                      ? mg_precords_se_only : method == MG_METHOD_ADAPTED ? mg_arecords_se_only : mg_records_se_only));
     if (!mg_scalars_ok(kind, G, n_models, M, P, D, C, steps, q_mode) || !filter_scalars_ok(f)) return set_error(nullptr, FFVD_EINVAL, bad);
     if (!records_scalars_ok(rq, G, steps, D))
         return set_error(nullptr, FFVD_EINVAL, bad + " (R >= 0, records_per_pass >= 0, G * R * steps * D * D < 2^31 and G * R * D < 2^31 are needed)");
     nothing = G == 0 || rq.R == 0 || steps == 0;
-    if (method == MG_METHOD_PARTICLE && (!pq || !particle_ok(*pq, G, rq.R, steps, D, with_S0, nothing)))
+    if (mg_particle_rule(method) && (!pq || !particle_ok(*pq, G, rq.R, steps, D, with_S0, nothing)))
         return set_error(nullptr, FFVD_EINVAL, bad + " (2 <= N <= 2048, finite draws, unif in [0, 1), xi0 with S0s, strides 0 or contiguous and "
                                                "G * R * steps * N * D < 2^31 are needed)");
     return FFVD_OK;
@@ -1559,6 +1571,7 @@ int records_given(const std::string &who, int method, int kind, int G, int n_mod
                       lpd_gauss};
     const RecordsReq rq{R, records_per_pass};
     bool nothing;
+    if (method == MG_METHOD_ADAPTED && sq) return set_error(nullptr, FFVD_EINVAL, bad + mg_adapted_no_smoother);
     if (int rc = records_checks(who, method, kind, G, n_models, M, P, D, C, steps, q_mode, f, rq, nothing, pq, S0s != nullptr)) return rc;
     if (sq && !nothing && !particle_smooth_ok(*sq, R, steps))
         return set_error(nullptr, FFVD_EINVAL, bad + " (every entry of lengths must lie in [1, steps])");
@@ -1598,6 +1611,7 @@ int records_posterior(const std::string &who, int method, int kind, int G, int n
                       lpd_gauss};
     const RecordsReq rq{R, records_per_pass};
     bool nothing;
+    if (method == MG_METHOD_ADAPTED && sq) return set_error(nullptr, FFVD_EINVAL, bad + mg_adapted_no_smoother);
     if (int rc = records_checks(who, method, kind, G, n_models, M, P, D, C, steps, q_mode, f, rq, nothing, pq, S0s != nullptr)) return rc;
     if (sq && !nothing && !particle_smooth_ok(*sq, R, steps))
         return set_error(nullptr, FFVD_EINVAL, bad + " (every entry of lengths must lie in [1, steps])");
@@ -1715,6 +1729,42 @@ extern "C" int ffvd_op_posterior_filter_particle_records_grouped(int kind, int G
                                                                  double *log_evidence, double *particles, int *ancestors, double *U_means) {
     FFVD_PARTICLE_REQ;
     return records_posterior("ffvd_op_posterior_filter_particle_records_grouped", MG_METHOD_PARTICLE, kind, G, n_models, Zs, M, P, D, logvariances,
+                             loglengthscales, Xs, ctrl_fit, C, T, log_Qs, jitter, groups_per_pass, q_mode, R, x0s, S0s, ctrl_roll, steps, CC, DD,
+                             noise_std, J, Y_obs, records_per_pass, m_pred, S_pred, m_filt, S_filt, nullptr, lpd, lpd_joint, nullptr, nullptr,
+                             y_mean, y_var_total, lpd_mix, lpd_gauss, U_means, &pq);
+}
+
+// The same two calls with the optimal proposal in place of the bootstrap one (moment_particle_adapted.hip): the fully adapted
+// auxiliary particle filter.  The argument lists are those of the two calls above; `particles` is the equally weighted filtered set
+// after every row and `ancestors` indexes the set carried into the row.  (Not ffvd_op_*: see DESIGN.md section 9, "Particle smoothing".)
+extern "C" int ffvd_particle_adapted_records_grouped(int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M,
+                                                     int P, int D, const double *logvariances, const double *loglengthscales, const double *fs,
+                                                     const double *const *q_sqrts, int q_mode, int R, const double *x_lasts, const double *S0s,
+                                                     const double *ctrl, int C, int steps, const double *log_Qs, const double *CC,
+                                                     const double *DD, const double *noise_std, int J, const double *Y_obs,
+                                                     int records_per_pass, FFVD_PARTICLE_PARAMS, double *m_pred, double *S_pred,
+                                                     double *m_filt, double *S_filt, double *lpd, double *lpd_joint, double *y_mean,
+                                                     double *y_var_total, double *lpd_mix, double *lpd_gauss, double *ess,
+                                                     double *log_evidence, double *particles, int *ancestors) {
+    FFVD_PARTICLE_REQ;
+    return records_given("ffvd_particle_adapted_records_grouped", MG_METHOD_ADAPTED, kind, G, n_models, Lm_inverse_seqs, Zs, M, P, D,
+                         logvariances, loglengthscales, fs, q_sqrts, q_mode, R, x_lasts, S0s, ctrl, C, steps, log_Qs, CC, DD, noise_std, J, Y_obs,
+                         records_per_pass, m_pred, S_pred, m_filt, S_filt, nullptr, lpd, lpd_joint, nullptr, nullptr, y_mean, y_var_total, lpd_mix,
+                         lpd_gauss, &pq);
+}
+
+extern "C" int ffvd_posterior_particle_adapted_records_grouped(int kind, int G, int n_models, const double *Zs, int M, int P, int D,
+                                                               const double *logvariances, const double *loglengthscales, const double *Xs,
+                                                               const double *ctrl_fit, int C, int T, const double *log_Qs, double jitter,
+                                                               int groups_per_pass, int q_mode, int R, const double *x0s, const double *S0s,
+                                                               const double *ctrl_roll, int steps, const double *CC, const double *DD,
+                                                               const double *noise_std, int J, const double *Y_obs, int records_per_pass,
+                                                               FFVD_PARTICLE_PARAMS, double *m_pred, double *S_pred, double *m_filt,
+                                                               double *S_filt, double *lpd, double *lpd_joint, double *y_mean,
+                                                               double *y_var_total, double *lpd_mix, double *lpd_gauss, double *ess,
+                                                               double *log_evidence, double *particles, int *ancestors, double *U_means) {
+    FFVD_PARTICLE_REQ;
+    return records_posterior("ffvd_posterior_particle_adapted_records_grouped", MG_METHOD_ADAPTED, kind, G, n_models, Zs, M, P, D, logvariances,
                              loglengthscales, Xs, ctrl_fit, C, T, log_Qs, jitter, groups_per_pass, q_mode, R, x0s, S0s, ctrl_roll, steps, CC, DD,
                              noise_std, J, Y_obs, records_per_pass, m_pred, S_pred, m_filt, S_filt, nullptr, lpd, lpd_joint, nullptr, nullptr,
                              y_mean, y_var_total, lpd_mix, lpd_gauss, U_means, &pq);

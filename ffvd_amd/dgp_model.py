@@ -653,6 +653,18 @@ class DGPSSM:
         return DGPSSM._records_particle(self, "filter_records_particle", "filter_particle_records_grouped", Y_records, control_records,
                                         num_particles, lengths, x0, S0, q_mode, Y_train_std, records_per_pass, seed, noise, return_particles)
 
+    def filter_records_adapted(self, Y_records, control_records=None, *, num_particles=256, lengths=None, x0=None, S0=None,
+                               q_mode="reference", Y_train_std=1.0, records_per_pass=0, seed=None, noise="shared", return_particles=False):
+        """`filter_records_particle` with the optimal proposal in place of the bootstrap one (the fully adapted auxiliary particle
+        filter): the parents are weighted by how well they predict the row before anything is drawn, so the filter does not collapse
+        where the observations are informative.  The parameters, the checks, the draws (the same seed gives the same draws in the same
+        order) and the two forms (collapsed U: ONE `posterior_filter_adapted_records_grouped` call; explicit U: `kernel_pre_cal` once,
+        then `filter_adapted_records_grouped`) are `filter_records_particle`'s; prediction.filter_adapted_records_grouped has the
+        method and the dict that is returned: particles[t] is the equally weighted filtered set after row t (not X^-) and
+        ancestors[t, i] indexes the set carried into row t.  No smoothing and no forecasts on the adapted sets."""
+        return DGPSSM._records_particle(self, "filter_records_adapted", "filter_adapted_records_grouped", Y_records, control_records,
+                                        num_particles, lengths, x0, S0, q_mode, Y_train_std, records_per_pass, seed, noise, return_particles)
+
     def smooth_records_particle(self, Y_records, control_records=None, *, num_particles=256, lengths=None, x0=None, S0=None,
                                 q_mode="reference", Y_train_std=1.0, records_per_pass=0, seed=None, noise="shared", return_particles=False):
         """`filter_records_particle` followed by the marginal particle smoother of every (chain, record) track in the same call: the

@@ -1038,9 +1038,10 @@ def filter_particle_records_grouped(Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts,
 
 
 def _particle_records_given(who, smooth, Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_records, Y_records, Qs, CC, DD, log_Rchols,
-                            eps, unif, xi0, lengths, S0s, q_mode, Y_train_std, records_per_pass, return_particles, unif_bs=None):
-    """The body of `filter_particle_records_grouped`, with `smooth` of `smooth_particle_records_grouped`, and with `smooth` and
-    `unif_bs` of `backsim_particle_records_grouped`."""
+                            eps, unif, xi0, lengths, S0s, q_mode, Y_train_std, records_per_pass, return_particles, unif_bs=None,
+                            adapted=False):
+    """The body of `filter_particle_records_grouped`, with `smooth` of `smooth_particle_records_grouped`, with `smooth` and
+    `unif_bs` of `backsim_particle_records_grouped`, and with `adapted` of `filter_adapted_records_grouped`."""
     shape = np.shape(Y_records)
     if len(shape) != 3 or shape[0] < 1 or shape[1] < 1:
         raise ValueError(f"{who}: Y_records: expected (R, steps, J) with at least one record and one row, got {shape}")
@@ -1059,7 +1060,7 @@ def _particle_records_given(who, smooth, Lm_inverse_seqs, Zs, kerns, U_vals, q_s
     dp = _lib.dptr
     opt = lambda x: None if x is None else dp(x)
     entry = ("ffvd_particle_backsim_records_grouped" if unif_bs is not None else "ffvd_particle_smooth_records_grouped") if smooth else \
-        "ffvd_op_filter_particle_records_grouped"
+        "ffvd_particle_adapted_records_grouped" if adapted else "ffvd_op_filter_particle_records_grouped"
     rc = getattr(_lib.load(), entry)(*args[:13], R, dp(r["x0"]), opt(r["S0"]), opt(r["ctrl"]), *args[16:], dp(m["CC"]), dp(m["DD"]), dp(m["sd"]),
                                      m["J"], dp(m["Y"]), r["rpp"], *pargs, *oargs, *sargs)
     _lib.check(rc, None, who)
@@ -1081,9 +1082,10 @@ def posterior_filter_particle_records_grouped(Zs, kerns, Xs, Qs, control_inputs,
 
 def _particle_records_posterior(who, smooth, Zs, kerns, Xs, Qs, control_inputs, control_records, Y_records, CC, DD, log_Rchols, eps, unif, xi0,
                                 lengths, x0s, S0s, q_mode, Y_train_std, jitter, groups_per_pass, records_per_pass, return_particles,
-                                unif_bs=None):
-    """The body of `posterior_filter_particle_records_grouped`, with `smooth` of `posterior_smooth_particle_records_grouped`, and with
-    `smooth` and `unif_bs` of `posterior_backsim_particle_records_grouped`."""
+                                unif_bs=None, adapted=False):
+    """The body of `posterior_filter_particle_records_grouped`, with `smooth` of `posterior_smooth_particle_records_grouped`, with
+    `smooth` and `unif_bs` of `posterior_backsim_particle_records_grouped`, and with `adapted` of
+    `posterior_filter_adapted_records_grouped`."""
     a = _pack_posterior_moment(who, Zs, kerns, Xs, Qs, control_inputs, 0, 0, None, q_mode, jitter, groups_per_pass)
     G, D, args = a["G"], a["D"], a["args"]
     r = _pack_records(who, G, D, args[11], x0s, control_records, Y_records, lengths, S0s, records_per_pass)
@@ -1095,11 +1097,54 @@ def _particle_records_posterior(who, smooth, Zs, kerns, Xs, Qs, control_inputs, 
     dp = _lib.dptr
     opt = lambda x: None if x is None else dp(x)
     entry = ("ffvd_posterior_particle_backsim_records_grouped" if unif_bs is not None else "ffvd_posterior_particle_smooth_records_grouped") \
-        if smooth else "ffvd_op_posterior_filter_particle_records_grouped"
+        if smooth else "ffvd_posterior_particle_adapted_records_grouped" if adapted else "ffvd_op_posterior_filter_particle_records_grouped"
     rc = getattr(_lib.load(), entry)(*args[:17], R, opt(r["x0"]), opt(r["S0"]), opt(r["ctrl"]), steps, dp(m["CC"]), dp(m["DD"]), dp(m["sd"]),
                                      m["J"], dp(m["Y"]), r["rpp"], *pargs, *oargs, *sargs, None)
     _lib.check(rc, None, who)
     return _smooth_dict(_particle_dict(r, G, out, extra, Y_train_std), r, sm)
+
+
+def filter_adapted_records_grouped(Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_records, Y_records, Qs, CC, DD, log_Rchols,
+                                   eps, unif, *, xi0=None, lengths=None, S0s=None, q_mode="reference", Y_train_std=1.0, records_per_pass=0,
+                                   return_particles=False):
+    """Fully adapted particle filtering of R observed records through G posteriors in ONE call
+    (`ffvd_particle_adapted_records_grouped`): `filter_particle_records_grouped` with the optimal proposal in place of the bootstrap
+    one (the fully adapted auxiliary particle filter of Pitt & Shephard 1999).  Given the parent particle the transition is Gaussian
+    with a diagonal covariance and the emission is linear-Gaussian, so p(y_t | parent) and p(x_t | parent, y_t) are closed forms: the
+    parents are weighted by how well they predict y_t BEFORE anything is drawn, resampled, and the children are drawn from the
+    optimal proposal; the new set is equally weighted.  Where the observations are informative the bootstrap filter collapses onto a
+    few particles and this one does not.  The parameters, the checks, the draws (the same arrays in the same layouts) and the dict
+    are `filter_particle_records_grouped`'s.
+    Per track, with X_t the equally weighted set carried into row t (X_0: the bootstrap call's start, bit for bit) and (mean_i, v_i)
+    the GP conditional at [X_ti, c_t]: mu_i = X_ti + mean_i, s_i = v_i + Q; m_pred = mean of the mu_i, S_pred = their centred
+    covariance (divisor N) + diag(mean of the s_i) -- the moments of the mixture (1/N) sum_i N(mu_i, diag s_i), no draw enters;
+    lpd[t, j] = log mean_i N(y_tj; CC[:, j] . mu_i + DD_j, sum_d CC[d, j]^2 s_id + sd_j^2); per particle, from (mu_i, diag s_i), exact
+    scalar Kalman updates over the observed j in ascending order give (mt_i, P_i) and L_i = log p(y_t | parent i); lpd_joint[t] =
+    log mean_i exp L_i; W_i = exp(L_i - max L), ess = (sum W)^2 / sum W^2; m_filt, S_filt: the moments of the mixture
+    sum W_i N(mt_i, P_i) / sum W; systematic resampling of the parents with unif[t] (the bootstrap call's rule) gives a_i;
+    X_{t+1,i} = mt_{a_i} + chol(P_{a_i}) eps[t, i] (unpivoted lower factor, a pivot <= 0 gives a zero column).  A row with nothing
+    observed takes the bootstrap call's propagation X_ti + mean_i + eps[t, i] sqrt(v_i + Q) with a_i = i, ess = N and m_filt / S_filt
+    = m_pred / S_pred bit for bit: a record that is all NaN returns `filter_particle_records_grouped`'s particles bit for bit.
+    log_evidence stays the unbiased SMC estimate.
+    Two of the returned arrays differ in meaning from the bootstrap call's: particles[t] (G, R, steps, N, D) is X_{t+1}, the equally
+    weighted FILTERED set after row t (not X^-), and ancestors[t, i] indexes the set carried INTO row t.  There is no smoothing, no
+    backward simulation and no forecast on the adapted sets ("Adapted particle filtering")."""
+    return _particle_records_given("filter_adapted_records_grouped", False, Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_records,
+                                   Y_records, Qs, CC, DD, log_Rchols, eps, unif, xi0, lengths, S0s, q_mode, Y_train_std, records_per_pass,
+                                   return_particles, adapted=True)
+
+
+def posterior_filter_adapted_records_grouped(Zs, kerns, Xs, Qs, control_inputs, control_records, Y_records, CC, DD, log_Rchols, eps, unif, *,
+                                             xi0=None, lengths=None, x0s=None, S0s=None, q_mode="reference", Y_train_std=1.0, jitter=JITTER,
+                                             groups_per_pass=0, records_per_pass=0, return_particles=False):
+    """The collapsed posterior of G groups and the filter of `filter_adapted_records_grouped` in ONE call
+    (`ffvd_posterior_particle_adapted_records_grouped`): what `conditionals_multi_output.collapse_u_mean_grouped` followed by
+    `filter_adapted_records_grouped` computes, without the posteriors leaving the device.  The parameters are
+    `posterior_filter_particle_records_grouped`'s, the returned dict is `filter_adapted_records_grouped`'s (particles[t] is the
+    filtered set X_{t+1}; ancestors[t, i] indexes the set carried into row t)."""
+    return _particle_records_posterior("posterior_filter_adapted_records_grouped", False, Zs, kerns, Xs, Qs, control_inputs, control_records,
+                                       Y_records, CC, DD, log_Rchols, eps, unif, xi0, lengths, x0s, S0s, q_mode, Y_train_std, jitter,
+                                       groups_per_pass, records_per_pass, return_particles, adapted=True)
 
 
 SMOOTH_PARTICLE_KEYS = ("m_smooth", "S_smooth", "ess_smooth")

@@ -906,6 +906,64 @@ int  ffvd_op_posterior_filter_particle_records_grouped(int kind, int G, int n_mo
                                                        double *lpd_gauss, double *ess, double *log_evidence, double *particles,
                                                        int *ancestors, double *U_means);
 
+/* Fully adapted particle filtering of R observed records in one call: ffvd_op_filter_particle_records_grouped with the optimal
+ * proposal in place of the bootstrap one (the fully adapted auxiliary particle filter of Pitt & Shephard 1999).  Given the parent
+ * the transition is Gaussian with a diagonal covariance and the emission is linear-Gaussian, so p(y_t | parent) and
+ * p(x_t | parent, y_t) are closed forms: the parents are weighted by how well they predict y_t before anything is drawn, resampled,
+ * and the children are drawn from the optimal proposal; the new set is equally weighted.  The argument list, the tracks, passes,
+ * timing, NaN convention, staging, q_mode, the caller's draws with their strides and the limits are those of
+ * ffvd_op_filter_particle_records_grouped.  Per track, with X_t the equally weighted set carried into row t (X_0: that call's
+ * start, bit for bit) and (mean_i, v_i) the GP conditional of the group at [X_ti, c_t]:
+ *   parents    mu_i = X_ti + mean_i,  s_i = v_i + Q  (per dim: trans_mean and trans_var of ffvd_particle_smooth_records_grouped)
+ *   moments    m_pred[t] = sum_i mu_i / N,  S_pred[t] = sum_i (mu_i - m_pred)(mu_i - m_pred)^T / N + diag(sum_i s_i / N): the moments
+ *              of the mixture (1/N) sum_i N(mu_i, diag s_i); no draw enters (exactly symmetric)
+ *   densities  lpd[t, j] = log mean_i N(y_tj; CC[:, j] . mu_i + DD_j, sum_d CC[d, j]^2 s_id + noise_std_j^2), NaN where y_tj is NaN
+ *   update     per particle from (m, P) = (mu_i, diag s_i) and L_i = 0, exact scalar updates over the observed j in ascending order:
+ *              h = P c_j, sig2 = c_j . h + noise_std_j^2, r = y_tj - (c_j . m + DD_j), L_i += -1/2 (log 2 pi + log sig2 + r^2 / sig2),
+ *              m += h (r / sig2), P_ab -= h_a h_b / sig2  ->  mt_i, P_i;  lpd_joint[t] = log mean_i exp L_i, NaN for a row with nothing
+ *              observed
+ *   filtered   W_i = exp(L_i - max L);  ess[t] = (sum W)^2 / sum W^2;  m_filt[t] = sum W mt / sum W,
+ *              S_filt[t] = sum W (P_i + (mt_i - m_filt)(mt_i - m_filt)^T) / sum W (exactly symmetric)
+ *   resample   the PARENTS, by ffvd_op_filter_particle_records_grouped's systematic rule with unif[t] (index clamped into [0, N)): a_i
+ *   draw       X_{t+1,i} = mt_{a_i} + L_{a_i} eps[t, i], L the lower Cholesky factor of P without pivoting (a pivot <= 0 gives a zero
+ *              column)
+ *   a row with nothing observed: X_{t+1,i} = X_ti + mean_i + eps[t, i] sqrt(v_i + Q) (that call's expression), a_i = i, W = 1,
+ *              ess = N, m_filt = m_pred and S_filt = S_pred bit for bit; a record that is all NaN returns that call's particles bit
+ *              for bit
+ * The outputs have that call's names and shapes with two differences: particles[t] is X_{t+1}, the equally weighted FILTERED set
+ * after row t (not X^-), and ancestors[t, i] indexes the set carried INTO row t.  log_evidence stays the unbiased SMC estimate; the
+ * pooled arrays are formed as in that call (y_mean, y_var_total, lpd_gauss from (m_pred, S_pred); lpd_mix from lpd).  Three launches
+ * per step as that call: only the per-track weight kernel differs.  There is no smoother, no backward simulation and no forecast
+ * on the adapted sets.  Limits: those of ffvd_op_filter_particle_records_grouped.  G = 0, R = 0 or steps = 0: FFVD_OK, nothing is
+ * touched. */
+int  ffvd_particle_adapted_records_grouped(int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M,
+                                           int P, int D, const double *logvariances, const double *loglengthscales, const double *fs,
+                                           const double *const *q_sqrts, int q_mode, int R, const double *x_lasts, const double *S0s,
+                                           const double *ctrl, int C, int steps, const double *log_Qs, const double *CC,
+                                           const double *DD, const double *noise_std, int J, const double *Y_obs,
+                                           int records_per_pass, int N, const double *eps, long long eps_stride_g,
+                                           long long eps_stride_r, const double *unif, long long unif_stride_g,
+                                           long long unif_stride_r, const double *xi0, long long xi0_stride_g, long long xi0_stride_r,
+                                           double *m_pred, double *S_pred, double *m_filt, double *S_filt, double *lpd,
+                                           double *lpd_joint, double *y_mean, double *y_var_total, double *lpd_mix, double *lpd_gauss,
+                                           double *ess, double *log_evidence, double *particles, int *ancestors);
+
+/* ffvd_op_posterior_grouped followed by ffvd_particle_adapted_records_grouped WITHOUT the posteriors leaving the device: the
+ * argument list of ffvd_op_posterior_filter_particle_records_grouped, the method and outputs of the call above. */
+int  ffvd_posterior_particle_adapted_records_grouped(int kind, int G, int n_models, const double *Zs, int M, int P, int D,
+                                                     const double *logvariances, const double *loglengthscales, const double *Xs,
+                                                     const double *ctrl_fit, int C, int T, const double *log_Qs, double jitter,
+                                                     int groups_per_pass, int q_mode, int R, const double *x0s, const double *S0s,
+                                                     const double *ctrl_roll, int steps, const double *CC, const double *DD,
+                                                     const double *noise_std, int J, const double *Y_obs, int records_per_pass,
+                                                     int N, const double *eps, long long eps_stride_g, long long eps_stride_r,
+                                                     const double *unif, long long unif_stride_g, long long unif_stride_r,
+                                                     const double *xi0, long long xi0_stride_g, long long xi0_stride_r,
+                                                     double *m_pred, double *S_pred, double *m_filt, double *S_filt, double *lpd,
+                                                     double *lpd_joint, double *y_mean, double *y_var_total, double *lpd_mix,
+                                                     double *lpd_gauss, double *ess, double *log_evidence, double *particles,
+                                                     int *ancestors, double *U_means);
+
 /* ffvd_op_filter_particle_records_grouped followed by the marginal particle smoother (forward filter / backward smoother of Doucet,
  * Godsill & Andrieu 2000) of every (group, record) track, on the equally weighted sets the filter carries.  The arguments and the
  * filter outputs are those of ffvd_op_filter_particle_records_grouped, bit for bit; no GP is evaluated beyond the filter's and no
