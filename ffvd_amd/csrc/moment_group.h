@@ -15,6 +15,23 @@ namespace ffvd {
 constexpr int MG_SLAB = 16;          // rows i of the pair tables per workgroup
 constexpr int MG_MAXD = 8;           // latent dims (the D x D elimination runs in one thread)
 
+// The launchers' dispatch on D: the statement with `d` a constant expression equal to D, for D = 1 .. MG_MAXD (nothing beyond: the
+// operators have returned FFVD_EINVAL).  MG_DISPATCH_D(a.D, hipLaunchKernelGGL(HIP_KERNEL_NAME(kernel<d>), ...))
+#define MG_DISPATCH_D_CASE(n, ...)                                                                                                  \
+    case n: {                                                                                                                       \
+        constexpr int d = n;                                                                                                        \
+        __VA_ARGS__;                                                                                                                \
+        break;                                                                                                                      \
+    }
+#define MG_DISPATCH_D(D, ...)                                                                                                       \
+    switch (D) {                                                                                                                    \
+        MG_DISPATCH_D_CASE(1, __VA_ARGS__) MG_DISPATCH_D_CASE(2, __VA_ARGS__) MG_DISPATCH_D_CASE(3, __VA_ARGS__)                    \
+        MG_DISPATCH_D_CASE(4, __VA_ARGS__) MG_DISPATCH_D_CASE(5, __VA_ARGS__) MG_DISPATCH_D_CASE(6, __VA_ARGS__)                    \
+        MG_DISPATCH_D_CASE(7, __VA_ARGS__) MG_DISPATCH_D_CASE(8, __VA_ARGS__)                                                       \
+        default: break;                                                                                                             \
+    }
+static_assert(MG_MAXD == 8, "MG_DISPATCH_D lists the cases 1 .. MG_MAXD");
+
 __host__ __device__ inline int mg_npair(int D) { return D * (D + 1) / 2; }
 __host__ __device__ inline int mg_fields(int D) { return mg_npair(D) + D + D * D; }     // Cov(f) pairs, E[f], Cov(x, f)
 

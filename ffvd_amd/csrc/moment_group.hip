@@ -130,12 +130,7 @@ __global__ __launch_bounds__(256) void mg_summary_kernel(MomentSummaryArgs a) {
 
 void launch_mg_step(hipStream_t stream, const MomentGroupArgs &a, int t) {
     const dim3 grid((unsigned)((size_t)a.G * mg_npair(a.D) * a.NS));
-    switch (a.D) {
-#define MG_CASE(d) case d: hipLaunchKernelGGL(HIP_KERNEL_NAME(mg_step_kernel<d, false>), grid, dim3(256), 0, stream, a, t); break;
-        MG_CASE(1) MG_CASE(2) MG_CASE(3) MG_CASE(4) MG_CASE(5) MG_CASE(6) MG_CASE(7) MG_CASE(8)
-#undef MG_CASE
-        default: break;
-    }
+    MG_DISPATCH_D(a.D, hipLaunchKernelGGL(HIP_KERNEL_NAME(mg_step_kernel<d, false>), grid, dim3(256), 0, stream, a, t))
 }
 
 void launch_moment_summary(hipStream_t stream, const MomentSummaryArgs &a) {

@@ -135,13 +135,7 @@ __global__ __launch_bounds__(256) void mg_linear_kernel(MomentGroupArgs a, const
 
 void launch_mg_linear_step(hipStream_t stream, const MomentGroupArgs &a, const MomentFilterArgs &f, int t) {
     const dim3 grid((unsigned)((size_t)a.G * a.D * a.NS));
-    switch (a.D) {
-#define MG_CASE(d) \
-    case d: hipLaunchKernelGGL(HIP_KERNEL_NAME(mg_linear_kernel<d>), grid, dim3(256), 0, stream, a, t, f); break;
-        MG_CASE(1) MG_CASE(2) MG_CASE(3) MG_CASE(4) MG_CASE(5) MG_CASE(6) MG_CASE(7) MG_CASE(8)
-#undef MG_CASE
-        default: break;
-    }
+    MG_DISPATCH_D(a.D, hipLaunchKernelGGL(HIP_KERNEL_NAME(mg_linear_kernel<d>), grid, dim3(256), 0, stream, a, t, f))
 }
 
 }  // namespace ffvd

@@ -226,13 +226,7 @@ int mg_lfan_tracks_per_pass(int G, int n_models, int D, int Mp, int unit_per_gro
 // a.G: the tracks of the pass (groups * f.Bp); l: mg_lfan_layout of the pass with its buffers
 void launch_mg_lfan_step(hipStream_t stream, const MomentGroupArgs &a, const MomentFanArgs &f, const MomentLinearFanArgs &l, int t) {
     const dim3 grid((unsigned)((size_t)a.G * a.D));
-    switch (a.D) {
-#define MG_CASE(d) \
-    case d: hipLaunchKernelGGL(HIP_KERNEL_NAME(mg_lfan_state_kernel<d>), grid, dim3(256), 0, stream, a, t, f, l); break;
-        MG_CASE(1) MG_CASE(2) MG_CASE(3) MG_CASE(4) MG_CASE(5) MG_CASE(6) MG_CASE(7) MG_CASE(8)
-#undef MG_CASE
-        default: break;
-    }
+    MG_DISPATCH_D(a.D, hipLaunchKernelGGL(HIP_KERNEL_NAME(mg_lfan_state_kernel<d>), grid, dim3(256), 0, stream, a, t, f, l))
     if (t >= a.steps) return;
     launch_mg_lfan_var(stream, l.K, a.gam, l.vpart, l.Tp, a.Mp, l.nr, l.units);
 }

@@ -155,13 +155,7 @@ __global__ __launch_bounds__(256) void mg_lrec_spread_kernel(int R, int n, size_
 void launch_mg_lrec_step(hipStream_t stream, const MomentGroupArgs &a, const MomentFilterArgs &f, const MomentRecordArgs &rc,
                          const MomentLinearFanArgs &l, int t) {
     const dim3 grid((unsigned)((size_t)a.G * a.D));
-    switch (a.D) {
-#define MG_CASE(d) \
-    case d: hipLaunchKernelGGL(HIP_KERNEL_NAME(mg_lrec_state_kernel<d>), grid, dim3(256), 0, stream, a, t, f, rc, l); break;
-        MG_CASE(1) MG_CASE(2) MG_CASE(3) MG_CASE(4) MG_CASE(5) MG_CASE(6) MG_CASE(7) MG_CASE(8)
-#undef MG_CASE
-        default: break;
-    }
+    MG_DISPATCH_D(a.D, hipLaunchKernelGGL(HIP_KERNEL_NAME(mg_lrec_state_kernel<d>), grid, dim3(256), 0, stream, a, t, f, rc, l))
     if (t >= a.steps) return;
     launch_mg_lfan_var(stream, l.K, a.gam, l.vpart, l.Tp, a.Mp, l.nr, l.units);
 }

@@ -27,49 +27,14 @@
 //     Between the weighting and the draw only (mu, s) of every parent are kept (2 D N doubles per track, MomentParticleAdaptedArgs);
 //     the scalar updates are run again where (mt, P) are needed -- for the weighted mean, for the weighted covariance and, after
 //     the gather, for the parent a_i -- instead of keeping (D + D (D + 1) / 2) N doubles per track.
-// No atomics, vector stores only, nothing waits on another workgroup; every reduction and the scan run in the bootstrap kernel's
-// fixed orders (a thread's particles ascending, a 64-lane butterfly, the four wavefronts ascending).  The one address that depends on
-// computed values is the parent's: the ancestor index is clamped into [0, N) before it is used, whatever the weights are.
-#include "moment_step.h"
+// No atomics, vector stores only, nothing waits on another workgroup.  The start, the transition, the scan, the search and the
+// reductions are the blocks of moment_particle.h that the bootstrap kernel calls (a thread's particles ascending, a 64-lane butterfly,
+// the four wavefronts ascending); the sums end in LDS (wg_sum_lds), not in registers.  The one address that depends on computed values
+// is the parent's: the ancestor index is clamped into [0, N) before it is used, whatever the weights are.
+#include "moment_particle.h"
 
 namespace ffvd {
 namespace {
-
-constexpr int PAREC_RED = MG_MAXD * (MG_MAXD + 1) / 2;    // the widest reduction: the upper triangle of a covariance
-
-// out[k] <- (the sum of v[k] over the workgroup) / div, in LDS: wavefront butterflies, then the four wavefronts in ascending order.
-// The results stay in LDS, not in registers: they are uniform, and the passes between which they live are register-bound at D = 8.
-template <int K>
-__device__ __forceinline__ void parec_sum(const double (&v)[K], double (*red)[PAREC_RED], double *out, const double div) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        double s = v[k];
-#pragma unroll
-        for (int mm = 32; mm > 0; mm >>= 1) s += __shfl_xor(s, mm);
-        if (lane == 0) red[wave][k] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < K) out[threadIdx.x] = (((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x]) / div;
-    __syncthreads();
-}
-
-template <int K>
-__device__ __forceinline__ void parec_max(const double (&v)[K], double (*red)[PAREC_RED], double *out) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        double s = v[k];
-#pragma unroll
-        for (int mm = 32; mm > 0; mm >>= 1) s = fmax(s, __shfl_xor(s, mm));
-        if (lane == 0) red[wave][k] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < K) out[threadIdx.x] = fmax(fmax(red[0][threadIdx.x], red[1][threadIdx.x]), fmax(red[2][threadIdx.x], red[3][threadIdx.x]));
-    __syncthreads();
-}
 
 // entry (lo <= hi) of an upper triangle stored row by row
 __device__ __forceinline__ constexpr int parec_tri(int D, int lo, int hi) { return lo * D - lo * (lo - 1) / 2 + (hi - lo); }
@@ -129,9 +94,9 @@ __global__ __launch_bounds__(256) void mg_parec_weight_kernel(MomentGroupArgs a,
                                                               MomentLinearFanArgs l, MomentParticleArgs p, MomentParticleAdaptedArgs q) {
     constexpr int NP = D * (D + 1) / 2;
     __shared__ double Wl[MG_PREC_MAXN], cdf[MG_PREC_MAXN];
-    __shared__ double red[4][PAREC_RED], Lm[MG_MAXD][MG_MAXD], Sg[MG_MAXD][MG_MAXD];
+    __shared__ double red[4][PARTICLE_RED], Lm[MG_MAXD][MG_MAXD], Sg[MG_MAXD][MG_MAXD];
     __shared__ double hs[MG_MAXJ][MG_MAXD], dds[MG_MAXJ], s2s[MG_MAXJ], ys[MG_MAXJ], vard[MG_MAXD], Qd[MG_MAXD], wtot[4];
-    __shared__ double mps[MG_MAXD], sbs[MG_MAXD], mfs[MG_MAXD], mxs[MG_MAXJ + 1], ses[MG_MAXJ], sws[2], sps[PAREC_RED], sfs[PAREC_RED];
+    __shared__ double mps[MG_MAXD], sbs[MG_MAXD], mfs[MG_MAXD], mxs[MG_MAXJ + 1], ses[MG_MAXJ], sws[2], sps[PARTICLE_RED], sfs[PARTICLE_RED];
     const int tid = threadIdx.x;
     const int G = a.G, steps = a.steps, N = p.N, J = f.J;
     const int v = blockIdx.x;
@@ -141,36 +106,8 @@ __global__ __launch_bounds__(256) void mg_parec_weight_kernel(MomentGroupArgs a,
     const size_t vg = (size_t)gq * rc.R + r, orow = vg * steps;                   // the track of the call; its first row in the stacks
     double *Xn = p.xstate + ((size_t)(t & 1) * G + v) * N * D;
 
-    if (t == 0) {                                                 // the start: the bootstrap kernel's, by the same expressions
-        if (tid < D * D) Sg[tid / D][tid % D] = a.S0 ? a.S0[vg * D * D + tid] : 0.0;
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < D; ++j) {
-            if (tid < D) {
-                double pv = Sg[j][j], s = Sg[tid][j];
-                for (int k = 0; k < j; ++k) { pv -= Lm[j][k] * Lm[j][k]; s -= Lm[tid][k] * Lm[j][k]; }
-                double e = 0.0;
-                if (pv > 0.0 && tid >= j) {
-                    const double qq = sqrt(pv);
-                    e = tid == j ? qq : s / qq;
-                }
-                Lm[tid][j] = e;
-            }
-            __syncthreads();
-        }
-        const double *xi = a.S0 ? p.xi0 + (size_t)gq * p.xi0_g + (size_t)r * p.xi0_r : nullptr;
-        for (int i = tid; i < N; i += 256) {
-            double z[D];
-#pragma unroll
-            for (int c = 0; c < D; ++c) z[c] = xi ? xi[(size_t)i * D + c] : 0.0;
-#pragma unroll
-            for (int k = 0; k < D; ++k) {
-                double s = 0.0;
-#pragma unroll
-                for (int c = 0; c <= k; ++c) s += Lm[k][c] * z[c];
-                Xn[(size_t)i * D + k] = a.x_last[vg * D + k] + s;
-            }
-        }
+    if (t == 0) {
+        particle_start<D>(a, p, gq, r, vg, Xn, Sg, Lm);
         return;
     }
 
@@ -183,13 +120,9 @@ __global__ __launch_bounds__(256) void mg_parec_weight_kernel(MomentGroupArgs a,
         s2s[tid] = f.sd[tid] * f.sd[tid];
         ys[tid] = f.Y[((size_t)r * steps + s) * J + tid];
     }
-    if (tid < D) {
-        vard[tid] = a.variance[(size_t)model * D + tid];
-        Qd[tid] = exp(a.log_Q[(size_t)gq * D + tid]);
-    }
+    particle_stage_noise<D>(a, model, gq, vard, Qd);
     __syncthreads();
-    bool any = false;
-    for (int j = 0; j < J; ++j) any = any || ys[j] == ys[j];
+    const bool any = particle_any_observed(ys, J);
 
     // pass A: (mu, s) of every parent, their sums, the predictive log-densities and their largest exponents; a row with nothing
     // observed draws here (a_i = i: no other particle is read)
@@ -205,17 +138,13 @@ __global__ __launch_bounds__(256) void mg_parec_weight_kernel(MomentGroupArgs a,
         double mu[D], sv[D];
 #pragma unroll
         for (int d = 0; d < D; ++d) {
-            const double *vp = l.vpart + (size_t)(l.shared ? d : gq * D + d) * l.ntj * l.Tp + row + i;
-            double qf = 0.0;
-            for (int tj = 0; tj < l.ntj; ++tj) qf += vp[(size_t)tj * l.Tp];        // column tiles in ascending order
-            mu[d] = Xp[(size_t)i * D + d] + pm[(size_t)d * N + i];
-            sv[d] = (vard[d] - qf) + Qd[d];
+            particle_transition<D>(l, gq, d, row, i, N, Xp, pm, vard[d], Qd[d], mu[d], sv[d]);
             Mu[(size_t)i * D + d] = mu[d];
             Sv[(size_t)i * D + d] = sv[d];
             sm[d] += mu[d];
             ss[d] += sv[d];
-            if (!any) {                                           // the bootstrap kernel's X^-, by the same expression
-                const double x = (Xp[(size_t)i * D + d] + pm[(size_t)d * N + i]) + ep[(size_t)i * D + d] * sqrt((vard[d] - qf) + Qd[d]);
+            if (!any) {                                           // the bootstrap kernel's X^-, from the same two values
+                const double x = mu[d] + ep[(size_t)i * D + d] * sqrt(sv[d]);
                 Xn[(size_t)i * D + d] = x;
                 if (po) po[(size_t)i * D + d] = x;
             }
@@ -241,9 +170,9 @@ __global__ __launch_bounds__(256) void mg_parec_weight_kernel(MomentGroupArgs a,
         mx[MG_MAXJ] = fmax(mx[MG_MAXJ], L);
         Wl[i] = L;
     }
-    parec_sum<D>(sm, red, mps, (double)N);                        // m_pred
-    parec_sum<D>(ss, red, sbs, (double)N);                        // sum_i s_i / N
-    parec_max<MG_MAXJ + 1>(mx, red, mxs);
+    wg_sum_lds<D>(sm, red, mps, (double)N);                        // m_pred
+    wg_sum_lds<D>(ss, red, sbs, (double)N);                        // sum_i s_i / N
+    wg_max_lds<MG_MAXJ + 1>(mx, red, mxs);
 
     // pass B: the centred sums of S_pred and the densities
     {
@@ -280,8 +209,8 @@ __global__ __launch_bounds__(256) void mg_parec_weight_kernel(MomentGroupArgs a,
                     se[j] += exp(-0.5 * (LOG_2PI + log(s2) + e * e / s2) - mxs[j]);
                 }
         }
-        parec_sum<NP>(sp, red, sps, (double)N);
-        parec_sum<MG_MAXJ>(se, red, ses, 1.0);
+        wg_sum_lds<NP>(sp, red, sps, (double)N);
+        wg_sum_lds<MG_MAXJ>(se, red, ses, 1.0);
     }
 
     // pass C: the weights and the weighted sums of the conditioned means
@@ -309,8 +238,8 @@ __global__ __launch_bounds__(256) void mg_parec_weight_kernel(MomentGroupArgs a,
             sw[0] += w;
             sw[1] += w * w;
         }
-        parec_sum<2>(sw, red, sws, 1.0);
-        if (any) parec_sum<D>(wm, red, mfs, sws[0]);              // m_filt
+        wg_sum_lds<2>(sw, red, sws, 1.0);
+        if (any) wg_sum_lds<D>(wm, red, mfs, sws[0]);              // m_filt
     }
 
     // pass D: the weighted sums of S_filt (a row with nothing observed: the predicted moments, bit for bit)
@@ -340,10 +269,10 @@ __global__ __launch_bounds__(256) void mg_parec_weight_kernel(MomentGroupArgs a,
                     ++k;
                 }
         }
-        parec_sum<NP>(sf, red, sfs, sws[0]);
+        wg_sum_lds<NP>(sf, red, sfs, sws[0]);
     }
 
-    // the row's outputs, from the sums in LDS: thread k stores entry k; (lo, hi) and (hi, lo) store one value
+    // the row's outputs, from the sums in LDS: thread k stores entry k
     const double nan = __builtin_nan("");
     {
         const size_t o = orow + s;
@@ -375,47 +304,14 @@ __global__ __launch_bounds__(256) void mg_parec_weight_kernel(MomentGroupArgs a,
         }
     }
 
-    // the scan: thread c sums its chunk of PT consecutive weights, the chunk totals are scanned by wavefront, then across the four
-    const int PT = (N + 255) / 256, c0 = tid * PT;
-    __syncthreads();
-    double run = 0.0;
-    for (int k = 0; k < PT; ++k)
-        if (c0 + k < N) {
-            run += Wl[c0 + k];
-            cdf[c0 + k] = run;
-        }
-    const int lane = tid & 63, wave = tid >> 6;
-    double inc = run;
-#pragma unroll
-    for (int mm = 1; mm < 64; mm <<= 1) {
-        const double up = __shfl_up(inc, mm);
-        if (lane >= mm) inc += up;
-    }
-    if (lane == 63) wtot[wave] = inc;
-    __syncthreads();
-    double base = inc - run;                                      // the chunks before this one in its wavefront
-    for (int w = 0; w < wave; ++w) base += wtot[w];
-    for (int k = 0; k < PT; ++k)
-        if (c0 + k < N) cdf[c0 + k] += base;
-    __syncthreads();                                              // (also: every (mu, s) of pass A is visible to the gather)
+    particle_scan(Wl, cdf, N, wtot);                              // (also: every (mu, s) of pass A is visible to the gather)
 
     // the ancestors, the gather of the parents' (mu, s) and the draw from the optimal proposal
     const double tot = cdf[N - 1];
     const double u0 = p.unif[(size_t)gq * p.unif_g + (size_t)r * p.unif_r + s];
     int *ao = p.ancestors ? p.ancestors + (orow + s) * N : nullptr;
     for (int i = tid; i < N; i += 256) {
-        int an = i;
-        if (any) {
-            const double u = (u0 + i) / N * tot;
-            int lo = 0, hi = N;
-            while (lo < hi) {                                     // #{k: cdf_k <= u}: at most 12 rounds, whatever the values are
-                const int mid = (lo + hi) >> 1;
-                if (cdf[mid] <= u) lo = mid + 1;
-                else hi = mid;
-            }
-            an = lo;
-        }
-        an = an < 0 ? 0 : an > N - 1 ? N - 1 : an;                // in [0, N) before any address is formed
+        const int an = any ? particle_search(cdf, N, (u0 + i) / N * tot) : i;
         if (ao) ao[i] = an;
         if (!any) continue;                                       // (drawn in pass A)
         double mu[D], sv[D], m[D], P[NP], z[D];
@@ -461,15 +357,7 @@ __global__ __launch_bounds__(256) void mg_parec_weight_kernel(MomentGroupArgs a,
 void launch_mg_parec_step(hipStream_t stream, const MomentGroupArgs &a, const MomentFilterArgs &f, const MomentRecordArgs &rc,
                           const MomentLinearFanArgs &l, const MomentParticleArgs &p, const MomentParticleAdaptedArgs &q, int t) {
     const dim3 grid((unsigned)a.G);
-    switch (a.D) {
-#define MG_CASE(d)                                                                                                                  \
-    case d:                                                                                                                         \
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(mg_parec_weight_kernel<d>), grid, dim3(256), 0, stream, a, t, f, rc, l, p, q);           \
-        break;
-        MG_CASE(1) MG_CASE(2) MG_CASE(3) MG_CASE(4) MG_CASE(5) MG_CASE(6) MG_CASE(7) MG_CASE(8)
-#undef MG_CASE
-        default: break;
-    }
+    MG_DISPATCH_D(a.D, hipLaunchKernelGGL(HIP_KERNEL_NAME(mg_parec_weight_kernel<d>), grid, dim3(256), 0, stream, a, t, f, rc, l, p, q))
     if (t >= a.steps) return;
     launch_mg_prec_rows(stream, a, rc, l, p, t);
     launch_mg_lfan_var(stream, l.K, a.gam, l.vpart, l.Tp, a.Mp, l.nr, l.units);

@@ -15,15 +15,13 @@
 //                          smoother's kernels, once, so that the B trajectories of a track do not each take D logarithms and D
 //                          divisions per particle and row (the bits are the same);
 //   mg_pbs_kernel          ONE launch, workgroup = (track, trajectory), walking t = n - 1 .. 0: log f of every carried particle into LDS
-//                          (thread = particle, stride 256), the maximum in the shape of psm_max, p in place, the weight kernel's scan
-//                          (thread c sums its PT = ceil(N / 256) consecutive entries, __shfl_up within a wavefront, the four wavefronts
-//                          in ascending order), one binary search of at most 12 rounds over integer bounds, run by every thread on
-//                          the same LDS words; the index is clamped into [0, N) before the ancestor is read and the ancestor again
-//                          before the gather;
+//                          (thread = particle, stride 256), the workgroup maximum, p in place, the filter's scan in place and its
+//                          search (particle_scan, particle_search of moment_particle.h), run by every thread on the same LDS words;
+//                          the index is clamped into [0, N) before the ancestor is read and the ancestor again before the gather;
 //   mg_pbs_moments_kernel  one launch, workgroup = (track, row), striding over the trajectories: their mean, centred covariance
 //                          (divisor B, mirrored) and the lag-one covariance with row t + 1, centred on the two rows' own means.
 // No atomics, nothing waits on another workgroup, every sum has an order fixed by N (by B in the moments) alone.
-#include "moment_particle_smooth.h"
+#include "moment_particle.h"
 
 namespace ffvd {
 namespace {
@@ -54,8 +52,8 @@ __global__ __launch_bounds__(256) void mg_pbs_prep_kernel(MomentParticleBacksimA
 // Workgroup = (track, trajectory)
 template <int D>
 __global__ __launch_bounds__(256) void mg_pbs_kernel(MomentParticleBacksimArgs q) {
-    __shared__ double pl[MG_PREC_MAXN], red[4][PSM_RED], wtot[4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, N = q.N, steps = q.steps, B = q.B;
+    __shared__ double pl[MG_PREC_MAXN], red[4][PARTICLE_RED], wtot[4];
+    const int tid = threadIdx.x, N = q.N, steps = q.steps, B = q.B;
     const int b = blockIdx.x % B, v = blockIdx.x / B, n = pbs_len(q, v);
     const size_t vrow = (size_t)v * steps;
     const double *U = q.unif + (size_t)(v / q.R) * q.unif_g + (size_t)(v % q.R) * q.unif_r;
@@ -63,7 +61,6 @@ __global__ __launch_bounds__(256) void mg_pbs_kernel(MomentParticleBacksimArgs q
     const double nan = __builtin_nan("");
     for (int e = n * D + tid; e < steps * D; e += 256) out[e] = nan;
     for (int t = n + tid; t < steps; t += 256) q.traj_index[(vrow + t) * B + b] = -1;
-    const int PT = (N + 255) / 256, c0 = tid * PT;
     double x[D];
 #pragma unroll
     for (int d = 0; d < D; ++d) x[d] = 0.0;
@@ -86,43 +83,13 @@ __global__ __launch_bounds__(256) void mg_pbs_kernel(MomentParticleBacksimArgs q
                 mx = fmax(mx, lf);
                 pl[i] = lf;
             }
-            mx = psm_max(mx, red);
+            mx = wg_max(mx, red);
             for (int i = tid; i < N; i += 256) pl[i] = exp(pl[i] - mx);          // (this thread's own entries)
         }
-        __syncthreads();
-        // the scan of the filter's weight kernel, in place
-        double run = 0.0;
-        for (int k = 0; k < PT; ++k)
-            if (c0 + k < N) {
-                run += pl[c0 + k];
-                pl[c0 + k] = run;
-            }
-        double inc = run;
-#pragma unroll
-        for (int mm = 1; mm < 64; mm <<= 1) {
-            const double up = __shfl_up(inc, mm);
-            if (lane >= mm) inc += up;
-        }
-        if (lane == 63) wtot[wave] = inc;
-        __syncthreads();
-        double base = inc - run;                                  // the chunks before this one in its wavefront
-        for (int w = 0; w < wave; ++w) base += wtot[w];
-        for (int k = 0; k < PT; ++k)
-            if (c0 + k < N) pl[c0 + k] += base;
-        __syncthreads();
+        particle_scan(pl, pl, N, wtot);
         // every thread runs the same search on the same words
-        const double u = U[(size_t)t * B + b] * pl[N - 1];
-        int lo = 0, hi = N;
-        while (lo < hi) {                                         // #{i: cdf_i <= u}: at most 12 rounds, whatever the values are
-            const int mid = (lo + hi) >> 1;
-            if (pl[mid] <= u) lo = mid + 1;
-            else hi = mid;
-        }
-        int k = lo < 0 ? 0 : lo > N - 1 ? N - 1 : lo;             // in [0, N) before any address is formed
-        if (t < n - 1) {
-            k = q.ancestors[(vrow + t) * N + k];
-            k = k < 0 ? 0 : k > N - 1 ? N - 1 : k;                // in [0, N) whatever the stack holds
-        }
+        int k = particle_search(pl, N, U[(size_t)t * B + b] * pl[N - 1]);
+        if (t < n - 1) k = particle_clamp(q.ancestors[(vrow + t) * N + k], N);   // in [0, N) whatever the stack holds
         const double *X = q.particles + ((vrow + t) * N + k) * D;
 #pragma unroll
         for (int d = 0; d < D; ++d) x[d] = X[d];
@@ -137,7 +104,7 @@ __global__ __launch_bounds__(256) void mg_pbs_kernel(MomentParticleBacksimArgs q
 template <int D>
 __global__ __launch_bounds__(256) void mg_pbs_moments_kernel(MomentParticleBacksimArgs q) {
     constexpr int NP = D * (D + 1) / 2;
-    __shared__ double red[4][PSM_RED];
+    __shared__ double red[4][PARTICLE_RED];
     const int tid = threadIdx.x, steps = q.steps, B = q.B;
     const int t = blockIdx.x % steps, v = blockIdx.x / steps, n = pbs_len(q, v);
     const size_t row = blockIdx.x;
@@ -160,8 +127,8 @@ __global__ __launch_bounds__(256) void mg_pbs_moments_kernel(MomentParticleBacks
             m0[d] += X[b * stride + d];
             m1[d] += Xn[b * stride + d];
         }
-    psm_sum<D>(m0, red);
-    psm_sum<D>(m1, red);
+    wg_sum<D>(m0, red);
+    wg_sum<D>(m1, red);
 #pragma unroll
     for (int d = 0; d < D; ++d) {
         m0[d] /= B;
@@ -180,8 +147,8 @@ __global__ __launch_bounds__(256) void mg_pbs_moments_kernel(MomentParticleBacks
 #pragma unroll
             for (int hi = lo; hi < D; ++hi) sf[k++] += dx[lo] * dx[hi];
     }
-    psm_sum<NP>(sf, red);
-    // every thread holds every sum, thread k stores entry k; (lo, hi) and (hi, lo) store one value
+    wg_sum<NP>(sf, red);
+    // every thread holds every sum, thread k stores entry k
 #pragma unroll
     for (int d = 0; d < D; ++d)
         if (tid == d) q.m_traj[row * D + d] = m0[d];
@@ -190,11 +157,7 @@ __global__ __launch_bounds__(256) void mg_pbs_moments_kernel(MomentParticleBacks
     for (int lo = 0; lo < D; ++lo)
 #pragma unroll
         for (int hi = lo; hi < D; ++hi) {
-            if (tid == 64 + k) {
-                const double s = sf[k] / B;
-                q.S_traj[row * D * D + lo * D + hi] = s;
-                q.S_traj[row * D * D + hi * D + lo] = s;
-            }
+            if (tid == 64 + k) particle_store_sym<D>(q.S_traj, row, lo, hi, sf[k] / B);
             ++k;
         }
     // the lag-one covariance, one row of it (component d of x_t) at a time
@@ -208,7 +171,7 @@ __global__ __launch_bounds__(256) void mg_pbs_moments_kernel(MomentParticleBacks
 #pragma unroll
             for (int e = 0; e < D; ++e) lg[e] += dx * (Xn[b * stride + e] - m1[e]);
         }
-        psm_sum<D>(lg, red);
+        wg_sum<D>(lg, red);
 #pragma unroll
         for (int e = 0; e < D; ++e)
             if (tid == 128 + e) q.lag_cov[row * D * D + d * D + e] = lag ? lg[e] / B : nan;
@@ -223,17 +186,11 @@ void launch_mg_pbs(hipStream_t stream, const MomentParticleBacksimArgs &b) {
     const dim3 trajs((unsigned)((size_t)b.V * b.B)), rows((unsigned)((size_t)b.V * b.steps));
     // V * steps * ceil(N / 256) <= V * steps * N, which the filter's own limit G * R * steps * N * D < 2^31 keeps inside grid x
     const dim3 slabs((unsigned)((size_t)b.V * b.steps * ((b.N + 255) / 256)));
-    switch (b.D) {
-#define MG_CASE(d)                                                                                                                  \
-    case d:                                                                                                                         \
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(mg_pbs_prep_kernel<d>), slabs, dim3(256), 0, stream, b);                                  \
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(mg_pbs_kernel<d>), trajs, dim3(256), 0, stream, b);                                       \
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(mg_pbs_moments_kernel<d>), rows, dim3(256), 0, stream, b);                                \
-        break;
-        MG_CASE(1) MG_CASE(2) MG_CASE(3) MG_CASE(4) MG_CASE(5) MG_CASE(6) MG_CASE(7) MG_CASE(8)
-#undef MG_CASE
-        default: break;
-    }
+    MG_DISPATCH_D(b.D, {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(mg_pbs_prep_kernel<d>), slabs, dim3(256), 0, stream, b);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(mg_pbs_kernel<d>), trajs, dim3(256), 0, stream, b);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(mg_pbs_moments_kernel<d>), rows, dim3(256), 0, stream, b);
+    })
 }
 
 }  // namespace ffvd

@@ -14,52 +14,16 @@
 //     double-buffered state; launch t > 0 finishes step t - 1 from what the previous launches left (the means of pmean, the
 //     column-tile partials in ascending tile order) and stores row t - 1 of the forecast.  No scan, no search, no weights;
 //   mg_pfan_rows_kernel (VALU, 256 threads, workgroup = (track, dim, slab of MG_PREC_SLAB particles)): the zero-padded kernel rows
-//     of the slab's particles into K and their means (the column loop of mg_prec_rows_kernel);
+//     of the slab's particles into K and their means;
 //   mg_lfan_var_kernel (moment_linear_fan.hip).
-// No atomics, nothing waits on another workgroup, every sum has an order fixed by N alone: the reductions and the expression of X^-
-// are the weight kernel's, so a track is bit for bit what the records filter computes over the record cut after the origin and
-// continued by h all-NaN rows.  The one address that depends on computed values is the start gather's: the ancestor index is clamped
-// into [0, N) before it is used.  A ninth translation unit of the family: the code of the others does not change with it.
-#include "moment_step.h"
+// No atomics, nothing waits on another workgroup, every sum has an order fixed by N alone.  The reductions, the transition, the
+// emission and the rows body are the blocks of moment_particle.h that the records filter calls, so a track is bit for bit what that
+// filter computes over the record cut after the origin and continued by h all-NaN rows.  The one address that depends on computed
+// values is the start gather's: the ancestor index is clamped into [0, N) before it is used.
+#include "moment_particle.h"
 
 namespace ffvd {
 namespace {
-
-constexpr int PFAN_RED = MG_MAXD * (MG_MAXD + 1) / 2;     // the widest reduction: the upper triangle of a covariance
-
-// v[k] <- the sum over the workgroup, the same in every thread: wavefront butterflies, then the four wavefronts in ascending order
-// (the weight kernel's reduction, instruction for instruction)
-template <int K>
-__device__ __forceinline__ void pfan_sum(double (&v)[K], double (*red)[PFAN_RED]) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        double s = v[k];
-#pragma unroll
-        for (int mm = 32; mm > 0; mm >>= 1) s += __shfl_xor(s, mm);
-        if (lane == 0) red[wave][k] = s;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) v[k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
-}
-
-template <int K>
-__device__ __forceinline__ void pfan_max(double (&v)[K], double (*red)[PFAN_RED]) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        double s = v[k];
-#pragma unroll
-        for (int mm = 32; mm > 0; mm >>= 1) s = fmax(s, __shfl_xor(s, mm));
-        if (lane == 0) red[wave][k] = s;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) v[k] = fmax(fmax(red[0][k], red[1][k]), fmax(red[2][k], red[3][k]));
-}
 
 // Launch t of h + 1.  a.G: the tracks of the pass (groups * fn.Bp), a.steps: the horizon, a.m_x / a.S_x: the forecast stacks;
 // f: the emission and the record's Y [n][J]; l: mg_lfan_layout with N rows per track; p.xstate: [2][tracks][N][D] (step parity),
@@ -68,7 +32,7 @@ template <int D>
 __global__ __launch_bounds__(256) void mg_pfan_state_kernel(MomentGroupArgs a, const int t, MomentFilterArgs f, MomentFanArgs fn,
                                                             MomentLinearFanArgs l, MomentParticleFanArgs p) {
     constexpr int NP = D * (D + 1) / 2;
-    __shared__ double red[4][PFAN_RED];
+    __shared__ double red[4][PARTICLE_RED];
     __shared__ double hs[MG_MAXJ][MG_MAXD], dds[MG_MAXJ], s2s[MG_MAXJ], ys[MG_MAXJ], lcs[MG_MAXJ], vard[MG_MAXD], Qd[MG_MAXD];
     const int tid = threadIdx.x;
     const int G = a.G, steps = a.steps, N = p.N, J = f.J;
@@ -83,8 +47,7 @@ __global__ __launch_bounds__(256) void mg_pfan_state_kernel(MomentGroupArgs a, c
         const double *xs = p.particles + srow * N * D;
         const int *as = p.ancestors + srow * N;
         for (int i = tid; i < N; i += 256) {
-            int an = as[i];
-            an = an < 0 ? 0 : an > N - 1 ? N - 1 : an;            // in [0, N) before any address is formed
+            const int an = particle_clamp(as[i], N);
 #pragma unroll
             for (int d = 0; d < D; ++d) Xn[(size_t)i * D + d] = xs[(size_t)an * D + d];
         }
@@ -93,18 +56,8 @@ __global__ __launch_bounds__(256) void mg_pfan_state_kernel(MomentGroupArgs a, c
 
     const int s = t - 1;                                          // the step this launch finishes: row org + 1 + s of Y is its target
     const double *Xp = p.xstate + ((size_t)(s & 1) * G + v) * N * D;
-    if (tid < J * D) hs[tid / D][tid % D] = f.CC[(size_t)(tid % D) * J + tid / D];
-    if (tid < J) {
-        const double s2 = f.sd[tid] * f.sd[tid];
-        dds[tid] = f.DD[tid];
-        s2s[tid] = s2;
-        lcs[tid] = -0.5 * (LOG_2PI + log(s2));
-        ys[tid] = f.Y[(size_t)(org + 1 + s) * J + tid];
-    }
-    if (tid < D) {
-        vard[tid] = a.variance[(size_t)model * D + tid];
-        Qd[tid] = exp(a.log_Q[(size_t)gq * D + tid]);
-    }
+    particle_stage_emission<D>(f, f.Y + (size_t)(org + 1 + s) * J, hs, dds, s2s, ys, lcs);
+    particle_stage_noise<D>(a, model, gq, vard, Qd);
     __syncthreads();
 
     // pass A: X^- (kept as the state of launch t: nothing is resampled), the sums of the mean and the largest exponents
@@ -120,26 +73,19 @@ __global__ __launch_bounds__(256) void mg_pfan_state_kernel(MomentGroupArgs a, c
         double x[D];
 #pragma unroll
         for (int d = 0; d < D; ++d) {
-            const double *vp = l.vpart + (size_t)(l.shared ? d : gq * D + d) * l.ntj * l.Tp + row + i;
-            double qf = 0.0;
-            for (int tj = 0; tj < l.ntj; ++tj) qf += vp[(size_t)tj * l.Tp];        // column tiles in ascending order
-            x[d] = (Xp[(size_t)i * D + d] + pm[(size_t)d * N + i]) + ep[(size_t)i * D + d] * sqrt((vard[d] - qf) + Qd[d]);
+            double tm, tv;
+            particle_transition<D>(l, gq, d, row, i, N, Xp, pm, vard[d], Qd[d], tm, tv);
+            x[d] = tm + ep[(size_t)i * D + d] * sqrt(tv);
             Xn[(size_t)i * D + d] = x[d];
             if (po) po[(size_t)i * D + d] = x[d];
             sm[d] += x[d];
         }
 #pragma unroll
         for (int j = 0; j < MG_MAXJ; ++j)
-            if (j < J && ys[j] == ys[j]) {
-                double hm = 0.0;
-#pragma unroll
-                for (int d = 0; d < D; ++d) hm += hs[j][d] * x[d];
-                const double e = (ys[j] - hm) - dds[j], lj = lcs[j] - 0.5 * e * e / s2s[j];
-                mx[j] = fmax(mx[j], lj);
-            }
+            if (j < J && ys[j] == ys[j]) mx[j] = fmax(mx[j], particle_emit_logpdf<D>(j, x, hs, dds, s2s, ys, lcs));
     }
-    pfan_sum<D>(sm, red);
-    pfan_max<MG_MAXJ>(mx, red);
+    wg_sum<D>(sm, red);
+    wg_max<MG_MAXJ>(mx, red);
     double mp[D];
 #pragma unroll
     for (int d = 0; d < D; ++d) mp[d] = sm[d] / N;
@@ -161,22 +107,16 @@ __global__ __launch_bounds__(256) void mg_pfan_state_kernel(MomentGroupArgs a, c
             for (int hi = lo; hi < D; ++hi) sp[k++] += (x[lo] - mp[lo]) * (x[hi] - mp[hi]);
 #pragma unroll
         for (int j = 0; j < MG_MAXJ; ++j)
-            if (j < J && ys[j] == ys[j]) {
-                double hm = 0.0;
-#pragma unroll
-                for (int d = 0; d < D; ++d) hm += hs[j][d] * x[d];
-                const double e = (ys[j] - hm) - dds[j];
-                se[j] += exp((lcs[j] - 0.5 * e * e / s2s[j]) - mx[j]);
-            }
+            if (j < J && ys[j] == ys[j]) se[j] += exp(particle_emit_logpdf<D>(j, x, hs, dds, s2s, ys, lcs) - mx[j]);
     }
-    pfan_sum<NP>(sp, red);
+    wg_sum<NP>(sp, red);
     double my_sp = 0.0;                                           // thread 64 + k keeps entry k of the upper triangle
 #pragma unroll
     for (int k = 0; k < NP; ++k)
         if (tid == 64 + k) my_sp = sp[k] / N;
-    pfan_sum<MG_MAXJ>(se, red);
+    wg_sum<MG_MAXJ>(se, red);
 
-    // the row's outputs: every thread holds every sum, thread k stores entry k; (lo, hi) and (hi, lo) store one value
+    // the row's outputs: every thread holds every sum, thread k stores entry k
     const size_t o = orow + s;
 #pragma unroll
     for (int d = 0; d < D; ++d)
@@ -186,10 +126,7 @@ __global__ __launch_bounds__(256) void mg_pfan_state_kernel(MomentGroupArgs a, c
     for (int lo = 0; lo < D; ++lo)
 #pragma unroll
         for (int hi = lo; hi < D; ++hi) {
-            if (tid == 64 + k) {
-                a.S_x[o * D * D + lo * D + hi] = my_sp;
-                a.S_x[o * D * D + hi * D + lo] = my_sp;
-            }
+            if (tid == 64 + k) particle_store_sym<D>(a.S_x, o, lo, hi, my_sp);
             ++k;
         }
 #pragma unroll
@@ -197,78 +134,16 @@ __global__ __launch_bounds__(256) void mg_pfan_state_kernel(MomentGroupArgs a, c
         if (j < J && tid == 128 + j) p.lpd_fc[o * J + j] = ys[j] == ys[j] ? mx[j] + log(se[j] / N) : __builtin_nan("");
 }
 
-// Launch t < h.  Workgroup (track of the pass, dim, slab of MG_PREC_SLAB particles): thread = column j, one row of Z against the
-// particles of the slab; the kernel rows go to rows N * (track row) + i of the unit's K block, their means to pmean.
+// Launch t < h.  Workgroup (track of the pass, dim, slab of MG_PREC_SLAB particles): the rows body for control row org + 1 + t of
+// the record.
 template <int D>
 __global__ __launch_bounds__(256) void mg_pfan_rows_kernel(MomentGroupArgs a, const int t, MomentFanArgs fn, MomentLinearFanArgs l,
                                                            MomentParticleFanArgs p) {
-    constexpr int NQ = MG_PREC_SLAB;
-    __shared__ double xp[NQ][MG_MAXD], xc[MAXP], il[MAXP], red[4][NQ];
-    const int tid = threadIdx.x;
-    const int G = a.G, C = a.C, P = a.P, M = a.M, Mp = a.Mp, N = p.N;
-    const int NSL = (N + NQ - 1) / NQ;
+    const int N = p.N, NSL = (N + MG_PREC_SLAB - 1) / MG_PREC_SLAB;
     const int sl = blockIdx.x % NSL, vd = blockIdx.x / NSL, d = vd % D, v = vd / D;
     const int bl = v % fn.Bp, gq = v / fn.Bp, org = fn.origin[fn.b0 + bl];
-    const int model = a.n_models == 1 ? 0 : gq;
-    const int i0 = sl * NQ, ni = N - i0 < NQ ? N - i0 : NQ;
-    const int row = N * (l.shared ? v : bl) + i0;
-    const double *X = p.xstate + ((size_t)(t & 1) * G + v) * N * D;
-    const double *lend = a.len + ((size_t)model * D + d) * P;
-    if (tid < NQ * D) {
-        const int i = tid / D, q = tid % D;
-        xp[i][q] = i < ni ? X[(size_t)(i0 + i) * D + q] : 0.0;
-    }
-    if (tid >= 128 && tid < 128 + P) {
-        const int q = tid - 128;
-        xc[q] = q < D ? 0.0 : a.ctrl[(size_t)(org + 1 + t) * C + (q - D)];
-        il[q] = 1.0 / lend[q];
-    }
-    __syncthreads();
-
-    const double *Zm = a.Z + (size_t)model * M * P;
-    const double *bed = a.beta + ((size_t)gq * D + d) * Mp;
-    const double var = a.variance[(size_t)model * D + d];
-    double *Kr = l.K + ((size_t)(l.shared ? d : gq * D + d) * l.Tp + row) * Mp;
-    double acc[NQ];
-#pragma unroll
-    for (int i = 0; i < NQ; ++i) acc[i] = 0.0;
-    for (int j = tid; j < Mp; j += 256) {
-        const bool live = j < M;
-        const double *z = Zm + (size_t)(live ? j : 0) * P;        // (a padding column reads row 0 and writes zeros)
-        double zs[D], cc = 0.0;
-#pragma unroll
-        for (int q = 0; q < D; ++q) zs[q] = z[q];
-        for (int q = D; q < P; ++q) {
-            const double u = (z[q] - xc[q]) * il[q];
-            cc += u * u;
-        }
-        const double be = live ? bed[j] : 0.0, vk = live ? var : 0.0;
-#pragma unroll
-        for (int i = 0; i < NQ; ++i) {
-            if (i < ni) {
-                double c = 0.0;
-#pragma unroll
-                for (int q = 0; q < D; ++q) {
-                    const double u = (zs[q] - xp[i][q]) * il[q];
-                    c += u * u;
-                }
-                const double k = vk * exp(-0.5 * (c + cc));
-                acc[i] += k * be;
-                Kr[(size_t)i * Mp + j] = k;
-            }
-            __builtin_amdgcn_sched_barrier(0);                    // one particle at a time: interleaved exps cost registers
-        }
-    }
-    const int lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-    for (int i = 0; i < NQ; ++i) {
-        double s = acc[i];
-#pragma unroll
-        for (int mm = 32; mm > 0; mm >>= 1) s += __shfl_xor(s, mm);
-        if (lane == 0) red[wave][i] = s;
-    }
-    __syncthreads();
-    if (tid < ni) p.pmean[((size_t)v * D + d) * N + i0 + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+    particle_rows_body<D>(a, l, N, sl, d, gq, a.ctrl + (size_t)(org + 1 + t) * a.C, p.xstate + ((size_t)(t & 1) * a.G + v) * N * D,
+                          p.pmean + ((size_t)v * D + d) * N, N * (l.shared ? v : bl));
 }
 
 }  // namespace
@@ -279,16 +154,10 @@ void launch_mg_pfan_step(hipStream_t stream, const MomentGroupArgs &a, const Mom
     const dim3 grid((unsigned)a.G);
     const int nsl = (p.N + MG_PREC_SLAB - 1) / MG_PREC_SLAB;
     const dim3 rows((unsigned)((size_t)a.G * a.D * nsl));
-    switch (a.D) {
-#define MG_CASE(d)                                                                                                                  \
-    case d:                                                                                                                         \
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(mg_pfan_state_kernel<d>), grid, dim3(256), 0, stream, a, t, f, fn, l, p);                \
-        if (t < a.steps) hipLaunchKernelGGL(HIP_KERNEL_NAME(mg_pfan_rows_kernel<d>), rows, dim3(256), 0, stream, a, t, fn, l, p);   \
-        break;
-        MG_CASE(1) MG_CASE(2) MG_CASE(3) MG_CASE(4) MG_CASE(5) MG_CASE(6) MG_CASE(7) MG_CASE(8)
-#undef MG_CASE
-        default: break;
-    }
+    MG_DISPATCH_D(a.D, {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(mg_pfan_state_kernel<d>), grid, dim3(256), 0, stream, a, t, f, fn, l, p);
+        if (t < a.steps) hipLaunchKernelGGL(HIP_KERNEL_NAME(mg_pfan_rows_kernel<d>), rows, dim3(256), 0, stream, a, t, fn, l, p);
+    })
     if (t >= a.steps) return;
     launch_mg_lfan_var(stream, l.K, a.gam, l.vpart, l.Tp, a.Mp, l.nr, l.units);
 }

@@ -28,8 +28,9 @@
 //   mg_psm_moments_kernel  one launch, workgroup = (track, row): the reduction shape of the weight kernel.
 // No atomics, nothing waits on another workgroup, every sum has an order fixed by N alone.  The addresses that depend on computed
 // values are the fold's: every ancestor is clamped into [0, N) before it is compared, and the run's bounds lie in [0, N] by
-// construction of the search.  A track whose length is <= t + 1 does nothing at row t.
-#include "moment_particle_smooth.h"
+// construction of the search.  A track whose length is <= t + 1 does nothing at row t.  The transition, the emission, the reductions
+// and psm_logf are the blocks of moment_particle.h that the filter and the backward simulation call.
+#include "moment_particle.h"
 
 namespace ffvd {
 namespace {
@@ -56,19 +57,15 @@ __global__ __launch_bounds__(256) void mg_psm_keep_kernel(MomentGroupArgs a, con
     const double *Xp = p.xstate + ((size_t)(s & 1) * G + v) * N * D;
     const double *pm = p.pmean + (size_t)v * D * N;
 #pragma unroll
-    for (int d = 0; d < D; ++d) {
-        const double *vp = l.vpart + (size_t)(l.shared ? d : gq * D + d) * l.ntj * l.Tp + row + i;
-        double qf = 0.0;
-        for (int tj = 0; tj < l.ntj; ++tj) qf += vp[(size_t)tj * l.Tp];            // column tiles in ascending order
-        tm[o + d] = Xp[(size_t)i * D + d] + pm[(size_t)d * N + i];
-        tv[o + d] = (a.variance[(size_t)model * D + d] - qf) + exp(a.log_Q[(size_t)gq * D + d]);
-    }
+    for (int d = 0; d < D; ++d)
+        particle_transition<D>(l, gq, d, row, i, N, Xp, pm, a.variance[(size_t)model * D + d], exp(a.log_Q[(size_t)gq * D + d]), tm[o + d],
+                               tv[o + d]);
 }
 
 // Workgroup = (track, row) of the call
 template <int D>
 __global__ __launch_bounds__(256) void mg_psm_weights_kernel(MomentFilterArgs f, MomentParticleSmoothArgs q) {
-    __shared__ double Wl[MG_PREC_MAXN], red[4][PSM_RED];
+    __shared__ double Wl[MG_PREC_MAXN], red[4][PARTICLE_RED];
     __shared__ double hs[MG_MAXJ][MG_MAXD], dds[MG_MAXJ], s2s[MG_MAXJ], ys[MG_MAXJ], lcs[MG_MAXJ];
     const int tid = threadIdx.x, N = q.N, steps = q.steps, J = f.J;
     const int t = blockIdx.x % steps, v = blockIdx.x / steps, r = v % q.R, n = psm_len(q, v);
@@ -81,17 +78,9 @@ __global__ __launch_bounds__(256) void mg_psm_weights_kernel(MomentFilterArgs f,
         }
         return;
     }
-    if (tid < J * D) hs[tid / D][tid % D] = f.CC[(size_t)(tid % D) * J + tid / D];
-    if (tid < J) {
-        const double s2 = f.sd[tid] * f.sd[tid];
-        dds[tid] = f.DD[tid];
-        s2s[tid] = s2;
-        lcs[tid] = -0.5 * (LOG_2PI + log(s2));
-        ys[tid] = f.Y[((size_t)r * steps + t) * J + tid];
-    }
+    particle_stage_emission<D>(f, f.Y + ((size_t)r * steps + t) * J, hs, dds, s2s, ys, lcs);
     __syncthreads();
-    bool any = false;
-    for (int j = 0; j < J; ++j) any = any || ys[j] == ys[j];
+    const bool any = particle_any_observed(ys, J);
     const double *X = q.particles + o * D;
     double mx = -__builtin_inf();
     for (int i = tid; i < N; i += 256) {
@@ -101,17 +90,11 @@ __global__ __launch_bounds__(256) void mg_psm_weights_kernel(MomentFilterArgs f,
         double L = 0.0;
 #pragma unroll
         for (int j = 0; j < MG_MAXJ; ++j)
-            if (j < J && ys[j] == ys[j]) {
-                double hm = 0.0;
-#pragma unroll
-                for (int d = 0; d < D; ++d) hm += hs[j][d] * x[d];
-                const double e = (ys[j] - hm) - dds[j], lj = lcs[j] - 0.5 * e * e / s2s[j];
-                L += lj;
-            }
+            if (j < J && ys[j] == ys[j]) L += particle_emit_logpdf<D>(j, x, hs, dds, s2s, ys, lcs);
         mx = fmax(mx, L);
         Wl[i] = L;
     }
-    mx = psm_max(mx, red);
+    mx = wg_max(mx, red);
     double sw[1] = {0.0};
     for (int i = tid; i < N; i += 256) {
         const double w = any ? exp(Wl[i] - mx) : 1.0;
@@ -120,7 +103,7 @@ __global__ __launch_bounds__(256) void mg_psm_weights_kernel(MomentFilterArgs f,
         sw[0] += w;
     }
     if (t != n - 1) return;
-    psm_sum<1>(sw, red);
+    wg_sum<1>(sw, red);
     for (int i = tid; i < N; i += 256) q.w_smooth[o + i] = Wl[i] / sw[0];
 }
 
@@ -207,10 +190,7 @@ __global__ __launch_bounds__(256) void mg_psm_fold_kernel(MomentParticleSmoothAr
     const int slab = blockIdx.x % nsl, v = blockIdx.x / nsl;
     if (psm_len(q, v) <= t + 1) return;
     const size_t o = ((size_t)v * steps + t) * N;
-    for (int i = tid; i < N; i += 256) {
-        const int an = q.ancestors[o + i];
-        as[i] = an < 0 ? 0 : an > N - 1 ? N - 1 : an;             // in [0, N) whatever the stack holds
-    }
+    for (int i = tid; i < N; i += 256) as[i] = particle_clamp(q.ancestors[o + i], N);
     __syncthreads();
     const int k = slab * 256 + tid;
     if (k >= N) return;
@@ -237,7 +217,7 @@ __global__ __launch_bounds__(256) void mg_psm_fold_kernel(MomentParticleSmoothAr
 template <int D>
 __global__ __launch_bounds__(256) void mg_psm_moments_kernel(MomentParticleSmoothArgs q) {
     constexpr int NP = D * (D + 1) / 2;
-    __shared__ double red[4][PSM_RED];
+    __shared__ double red[4][PARTICLE_RED];
     const int tid = threadIdx.x, N = q.N, steps = q.steps;
     const int t = blockIdx.x % steps, v = blockIdx.x / steps;
     const size_t row = blockIdx.x, o = row * N;
@@ -260,8 +240,8 @@ __global__ __launch_bounds__(256) void mg_psm_moments_kernel(MomentParticleSmoot
 #pragma unroll
         for (int d = 0; d < D; ++d) wm[d] += w * X[(size_t)i * D + d];
     }
-    psm_sum<2>(sw, red);
-    psm_sum<D>(wm, red);
+    wg_sum<2>(sw, red);
+    wg_sum<D>(wm, red);
     double ms[D];
 #pragma unroll
     for (int d = 0; d < D; ++d) ms[d] = wm[d] / sw[0];
@@ -279,8 +259,8 @@ __global__ __launch_bounds__(256) void mg_psm_moments_kernel(MomentParticleSmoot
 #pragma unroll
             for (int hi = lo; hi < D; ++hi) sf[k++] += w * (x[lo] * x[hi]);
     }
-    psm_sum<NP>(sf, red);
-    // every thread holds every sum, thread k stores entry k; (lo, hi) and (hi, lo) store one value
+    wg_sum<NP>(sf, red);
+    // every thread holds every sum, thread k stores entry k
 #pragma unroll
     for (int d = 0; d < D; ++d)
         if (tid == d) q.m_smooth[row * D + d] = ms[d];
@@ -289,11 +269,7 @@ __global__ __launch_bounds__(256) void mg_psm_moments_kernel(MomentParticleSmoot
     for (int lo = 0; lo < D; ++lo)
 #pragma unroll
         for (int hi = lo; hi < D; ++hi) {
-            if (tid == 64 + k) {
-                const double s = sf[k] / sw[0];
-                q.S_smooth[row * D * D + lo * D + hi] = s;
-                q.S_smooth[row * D * D + hi * D + lo] = s;
-            }
+            if (tid == 64 + k) particle_store_sym<D>(q.S_smooth, row, lo, hi, sf[k] / sw[0]);
             ++k;
         }
     if (tid == 192) q.ess_smooth[row] = sw[0] * sw[0] / sw[1];
@@ -301,23 +277,12 @@ __global__ __launch_bounds__(256) void mg_psm_moments_kernel(MomentParticleSmoot
 
 }  // namespace
 
-#define MG_SWITCH_D(D, BODY)                                                                                                        \
-    switch (D) {                                                                                                                    \
-        BODY(1) BODY(2) BODY(3) BODY(4) BODY(5) BODY(6) BODY(7) BODY(8)                                                             \
-        default: break;                                                                                                             \
-    }
-
 // a.G: the tracks of the pass (groups * rc.Rp); s < steps: the step whose product launch has been enqueued
 void launch_mg_psm_keep(hipStream_t stream, const MomentGroupArgs &a, const MomentRecordArgs &rc, const MomentLinearFanArgs &l,
                         const MomentParticleArgs &p, const MomentParticleSmoothArgs &q, int s) {
     const dim3 grid((unsigned)((size_t)a.G * ((p.N + 255) / 256)));
-#define MG_CASE(d)                                                                                                                  \
-    case d:                                                                                                                         \
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(mg_psm_keep_kernel<d>), grid, dim3(256), 0, stream, a, s, rc, l, p, q.trans_mean,         \
-                           q.trans_var);                                                                                            \
-        break;
-    MG_SWITCH_D(a.D, MG_CASE)
-#undef MG_CASE
+    MG_DISPATCH_D(a.D, hipLaunchKernelGGL(HIP_KERNEL_NAME(mg_psm_keep_kernel<d>), grid, dim3(256), 0, stream, a, s, rc, l, p, q.trans_mean,
+                                          q.trans_var))
 }
 
 // After the filter's last pass: the weights, the normalisers of all rows, the rows n_max - 2 .. 0 (two launches each), the moments.
@@ -326,31 +291,23 @@ void launch_mg_psm_smooth(hipStream_t stream, const MomentFilterArgs &f, const M
     const int nsl = (q.N + 255) / 256;
     const dim3 rows((unsigned)((size_t)q.V * q.steps)), slabs((unsigned)((size_t)q.V * nsl));
     const dim3 pairs((unsigned)((size_t)q.V * (q.steps - 1) * nsl));
-#define MG_CASE(d)                                                                                                                  \
-    case d:                                                                                                                         \
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(mg_psm_weights_kernel<d>), rows, dim3(256), 0, stream, f, q);                             \
-        if (n_max > 1) hipLaunchKernelGGL(HIP_KERNEL_NAME(mg_psm_norm_kernel<d>), pairs, dim3(256), 0, stream, q);                   \
-        for (int t = n_max - 2; t >= 0; --t) {                                                                                      \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(mg_psm_back_kernel<d>), slabs, dim3(256), 0, stream, q, t);                           \
-            hipLaunchKernelGGL(mg_psm_fold_kernel, slabs, dim3(256), 0, stream, q, t);                                              \
-        }                                                                                                                           \
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(mg_psm_moments_kernel<d>), rows, dim3(256), 0, stream, q);                                \
-        break;
-    MG_SWITCH_D(q.D, MG_CASE)
-#undef MG_CASE
+    MG_DISPATCH_D(q.D, {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(mg_psm_weights_kernel<d>), rows, dim3(256), 0, stream, f, q);
+        if (n_max > 1) hipLaunchKernelGGL(HIP_KERNEL_NAME(mg_psm_norm_kernel<d>), pairs, dim3(256), 0, stream, q);
+        for (int t = n_max - 2; t >= 0; --t) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(mg_psm_back_kernel<d>), slabs, dim3(256), 0, stream, q, t);
+            hipLaunchKernelGGL(mg_psm_fold_kernel, slabs, dim3(256), 0, stream, q, t);
+        }
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(mg_psm_moments_kernel<d>), rows, dim3(256), 0, stream, q);
+    })
 }
 
 // The weights kernel alone (the particle backward simulation of moment_particle_backsim.hip draws its last row from W_{n-1}); it also
 // writes the last row of q.w_smooth and NaN beyond every length.
 void launch_mg_psm_weights(hipStream_t stream, const MomentFilterArgs &f, const MomentParticleSmoothArgs &q) {
     const dim3 rows((unsigned)((size_t)q.V * q.steps));
-#define MG_CASE(d)                                                                                                                  \
-    case d:                                                                                                                         \
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(mg_psm_weights_kernel<d>), rows, dim3(256), 0, stream, f, q);                             \
-        break;
-    MG_SWITCH_D(q.D, MG_CASE)
-#undef MG_CASE
+    MG_DISPATCH_D(q.D, hipLaunchKernelGGL(HIP_KERNEL_NAME(mg_psm_weights_kernel<d>), rows, dim3(256), 0, stream, f, q))
 }
-#undef MG_SWITCH_D
 
 }  // namespace ffvd
+

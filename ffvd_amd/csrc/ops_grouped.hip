@@ -1208,9 +1208,19 @@ bool particle_ok(const ParticleReq &q, int G, int R, int steps, int D, bool with
     return true;
 }
 
+// out[e] = log mean_g exp(lpd[g][e]), e < n, on the host: the mixture of all G * N particles' emissions, in ascending g, the largest
+// exponent subtracted; NaN where the entry is unobserved (lpd [G][n], NaN in every group alike)
+void lpd_mix_over_groups(const double *lpd, int G, size_t n, double *out) {
+    for (size_t e = 0; e < n; ++e) {
+        double mx = -INFINITY, sum = 0.0;
+        for (int g = 0; g < G; ++g) mx = std::fmax(mx, lpd[(size_t)g * n + e]);
+        for (int g = 0; g < G; ++g) sum += std::exp(lpd[(size_t)g * n + e] - mx);
+        out[e] = std::isnan(lpd[e]) ? NAN : mx + std::log(sum / G);
+    }
+}
+
 // The tail of a particle call: the pooled summary of the predicted stacks on the device (y_mean, y_var_total, lpd_gauss), the downloads,
-// and on the host, from the stacks that came down: lpd_mix = log mean_g exp(lpd[g]) (the mixture of all G * N particles' emissions; in
-// ascending g, the largest exponent subtracted; NaN where the entry is unobserved) and log_evidence = the sum of lpd_joint over the
+// and on the host, from the stacks that came down: lpd_mix (lpd_mix_over_groups) and log_evidence = the sum of lpd_joint over the
 // rows that have an observation, in ascending order
 int mg_particle_finish(Scratch &sc, const std::string &who, int G, int R, int steps, int D, const double *dm, const double *dS, double *m_x,
                        double *S_x, const MomentFilterArgs &fa, const MomentParticleArgs &pa, const FilterReq &flt, const ParticleReq &pq) {
@@ -1231,13 +1241,7 @@ int mg_particle_finish(Scratch &sc, const std::string &who, int G, int R, int st
         !down(pq.particles, pa.particles, nm_x * pq.N * sizeof(double)) || !down(pq.ancestors, pa.ancestors, nlj * pq.N * sizeof(int)))
         return set_error(nullptr, FFVD_EDEVICE, who + ": copying the results back failed");
     OP_TRY(hipStreamSynchronize(sc.stream));
-    if (flt.lpd_mix)
-        for (size_t e = 0; e < RS * J; ++e) {
-            double mx = -INFINITY, sum = 0.0;
-            for (int g = 0; g < G; ++g) mx = std::fmax(mx, lpd[(size_t)g * RS * J + e]);
-            for (int g = 0; g < G; ++g) sum += std::exp(lpd[(size_t)g * RS * J + e] - mx);
-            flt.lpd_mix[e] = std::isnan(lpd[e]) ? NAN : mx + std::log(sum / G);
-        }
+    if (flt.lpd_mix) lpd_mix_over_groups(lpd, G, RS * J, flt.lpd_mix);
     if (pq.log_evidence)
         for (size_t v = 0; v < V; ++v) {
             double sum = 0.0;
@@ -1528,13 +1532,7 @@ int mg_particle_fc_run(Scratch &sc, const std::string &who, int G, int nm, int M
     if (!down(fc.m_fc, dmfc, nm_fc * sizeof(double)) || !down(fc.S_fc, dSfc, nS_fc * sizeof(double)) || !down(lfc, ta.lpd_fc, nl_fc * sizeof(double)) ||
         !down(pf.fc_particles, ta.fc_particles, nm_fc * N * sizeof(double)))
         return set_error(nullptr, FFVD_EDEVICE, who + ": copying the results back failed");
-    if (fc.lpd_mix)
-        for (size_t k = 0; k < BH * J; ++k) {
-            double mx = -INFINITY, sum = 0.0;
-            for (int g = 0; g < G; ++g) mx = std::fmax(mx, lfc[(size_t)g * BH * J + k]);
-            for (int g = 0; g < G; ++g) sum += std::exp(lfc[(size_t)g * BH * J + k] - mx);
-            fc.lpd_mix[k] = std::isnan(lfc[k]) ? NAN : mx + std::log(sum / G);
-        }
+    if (fc.lpd_mix) lpd_mix_over_groups(lfc, G, BH * J, fc.lpd_mix);
     return mg_particle_finish(sc, who, G, 1, steps, D, dm, dS, m_x, S_x, fa, pa, flt, q);
 }
 
