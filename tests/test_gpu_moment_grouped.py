@@ -9,7 +9,8 @@ floors of tests/test_gpu_conditional_grouped.py (1e-11 + 1e-9 max|ref| on means,
 Where np.longdouble is no wider than 1e-18 the floor alone is used (printed).  Every measured error is printed.
 
 Shapes: tiny (M = 24, D = 2, C = 1), ragged (M = 77, D = 3, C = 2), small (M = 96, D = 4, C = 1), M = 130 past one 128 tile with D = 1
-and no control input, and D = 8 at M = 40: padding, slab edges (M not a multiple of 16), pair indexing and the D x D elimination."""
+and no control input, and D = 8 at M = 40: padding, slab edges (M not a multiple of 16), pair indexing and the D x D elimination.
+These have D = 2, 3, 4, 1 and 8, P <= 9 and J <= 3; D = 5, 6 and 7, J = 8 and P up to 32 run in tests/test_gpu_widths.py."""
 import functools
 
 import numpy as np
