@@ -212,6 +212,27 @@ _SIGNATURES = {
                                                                  _PARTICLE_DRAWS + [_dp] * 13 +
                                                                  [C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, _dp, C.c_longlong,
                                                                   C.c_longlong, _dp, C.POINTER(C.c_int)] + [_dp] * 6 + [_dp]),
+    # the four calls above on the adapted filter's sets: the same lists without `weights`
+    "ffvd_particle_adapted_smooth_records_grouped": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), _dp, C.c_int, C.c_int, C.c_int,
+                                                               _dp, _dp, _dp, C.POINTER(C.c_void_p), C.c_int, C.c_int, _dp, _dp, _dp, C.c_int,
+                                                               C.c_int, _dp, _dp, _dp, _dp, C.c_int, _dp, C.c_int] + _PARTICLE_DRAWS +
+                                                              [_dp] * 13 + [C.POINTER(C.c_int), C.POINTER(C.c_int)] + [_dp] * 6),
+    "ffvd_posterior_particle_adapted_smooth_records_grouped": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp,
+                                                                         _dp, _dp, C.c_int, C.c_int, _dp, C.c_double, C.c_int, C.c_int,
+                                                                         C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp, C.c_int, _dp,
+                                                                         C.c_int] + _PARTICLE_DRAWS + [_dp] * 13 +
+                                                                        [C.POINTER(C.c_int), C.POINTER(C.c_int)] + [_dp] * 6 + [_dp]),
+    "ffvd_particle_adapted_backsim_records_grouped": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), _dp, C.c_int, C.c_int, C.c_int,
+                                                                _dp, _dp, _dp, C.POINTER(C.c_void_p), C.c_int, C.c_int, _dp, _dp, _dp, C.c_int,
+                                                                C.c_int, _dp, _dp, _dp, _dp, C.c_int, _dp, C.c_int] + _PARTICLE_DRAWS +
+                                                               [_dp] * 13 + [C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, _dp,
+                                                                             C.c_longlong, C.c_longlong, _dp, C.POINTER(C.c_int)] + [_dp] * 5),
+    "ffvd_posterior_particle_adapted_backsim_records_grouped": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp,
+                                                                          _dp, _dp, C.c_int, C.c_int, _dp, C.c_double, C.c_int, C.c_int,
+                                                                          C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp, C.c_int, _dp,
+                                                                          C.c_int] + _PARTICLE_DRAWS + [_dp] * 13 +
+                                                                         [C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, _dp, C.c_longlong,
+                                                                          C.c_longlong, _dp, C.POINTER(C.c_int)] + [_dp] * 5 + [_dp]),
     "ffvd_op_forecast_grouped": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp,
                                            C.POINTER(C.c_void_p), C.c_int, _dp, _dp, _dp, C.c_int, C.c_int, _dp,
                                            _dp, _dp, _dp, C.c_int, _dp] + [_dp] * 13 +

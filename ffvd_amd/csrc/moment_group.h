@@ -270,6 +270,21 @@ struct MomentParticleBacksimArgs {
 // after launch_mg_psm_weights
 void launch_mg_pbs(hipStream_t stream, const MomentParticleBacksimArgs &b);
 
+// Particle smoothing and backward simulation on the ADAPTED filter's sets (moment_particle_adapted_smooth.hip; DESIGN.md section 9,
+// "Adapted particle smoothing").  particles[t] is the equally weighted filtered set after row t and (trans_mean, trans_var)[t + 1],
+// kept by launch_mg_psm_keep after the product launch of step t + 1, are the transition moments of exactly those particles: no fold
+// through the ancestors, no emission weights, a uniform last row.  The structs are the bootstrap units' with `ancestors`, `weights`
+// and `omega` not read (nullptr).  The normalisers, the moments, 1 / s and sum log s and the trajectory moments are the bootstrap
+// units' kernels through the launchers below; the backward kernel (one launch per row) and the recursion kernel are the unit's own.
+// Limits: the bootstrap smoother's and backward simulation's.
+void launch_mg_psm_norm(hipStream_t stream, const MomentParticleSmoothArgs &q, int n_max);       // mg_psm_norm_kernel alone (n_max > 1)
+void launch_mg_psm_moments(hipStream_t stream, const MomentParticleSmoothArgs &q);               // mg_psm_moments_kernel alone
+void launch_mg_pbs_prep(hipStream_t stream, const MomentParticleBacksimArgs &b);                 // mg_pbs_prep_kernel alone
+void launch_mg_pbs_moments(hipStream_t stream, const MomentParticleBacksimArgs &b);              // mg_pbs_moments_kernel alone
+// after the adapted filter's last pass; n_max: the longest record of the call
+void launch_mg_pasm_smooth(hipStream_t stream, const MomentParticleSmoothArgs &q, int n_max);
+void launch_mg_pabs(hipStream_t stream, const MomentParticleBacksimArgs &b);
+
 // Cubature forecasts (moment_cubature_fan.hip; DESIGN.md section 9, "Cubature forecasts"): the fan's tracks and indexing (MomentFanArgs)
 // with the cubature rule above and no measurement update.  MomentGroupArgs as for the linearised forecasts; MomentLinearFanArgs is
 // mg_lfan_layout with Bp = 2D * (tracks per group of the pass), msum [2][tracks][D][2D], `off` [2][tracks][D][D].  The product kernel

@@ -193,4 +193,15 @@ void launch_mg_pbs(hipStream_t stream, const MomentParticleBacksimArgs &b) {
     })
 }
 
+// The first and the last of the three launches alone (host code only: the adapted backward simulation of
+// moment_particle_adapted_smooth.hip brings a recursion kernel of its own between them)
+void launch_mg_pbs_prep(hipStream_t stream, const MomentParticleBacksimArgs &b) {
+    const dim3 slabs((unsigned)((size_t)b.V * b.steps * ((b.N + 255) / 256)));
+    MG_DISPATCH_D(b.D, hipLaunchKernelGGL(HIP_KERNEL_NAME(mg_pbs_prep_kernel<d>), slabs, dim3(256), 0, stream, b))
+}
+void launch_mg_pbs_moments(hipStream_t stream, const MomentParticleBacksimArgs &b) {
+    const dim3 rows((unsigned)((size_t)b.V * b.steps));
+    MG_DISPATCH_D(b.D, hipLaunchKernelGGL(HIP_KERNEL_NAME(mg_pbs_moments_kernel<d>), rows, dim3(256), 0, stream, b))
+}
+
 }  // namespace ffvd

@@ -309,5 +309,17 @@ void launch_mg_psm_weights(hipStream_t stream, const MomentFilterArgs &f, const 
     MG_DISPATCH_D(q.D, hipLaunchKernelGGL(HIP_KERNEL_NAME(mg_psm_weights_kernel<d>), rows, dim3(256), 0, stream, f, q))
 }
 
+// The normalisers of all rows and the moments alone (host code only: the adapted smoother of moment_particle_adapted_smooth.hip brings
+// a backward kernel of its own between them)
+void launch_mg_psm_norm(hipStream_t stream, const MomentParticleSmoothArgs &q, int n_max) {
+    if (n_max <= 1) return;
+    const dim3 pairs((unsigned)((size_t)q.V * (q.steps - 1) * ((q.N + 255) / 256)));
+    MG_DISPATCH_D(q.D, hipLaunchKernelGGL(HIP_KERNEL_NAME(mg_psm_norm_kernel<d>), pairs, dim3(256), 0, stream, q))
+}
+void launch_mg_psm_moments(hipStream_t stream, const MomentParticleSmoothArgs &q) {
+    const dim3 rows((unsigned)((size_t)q.V * q.steps));
+    MG_DISPATCH_D(q.D, hipLaunchKernelGGL(HIP_KERNEL_NAME(mg_psm_moments_kernel<d>), rows, dim3(256), 0, stream, q))
+}
+
 }  // namespace ffvd
 

@@ -1121,8 +1121,6 @@ const char *const mg_arecords_se_only =
     " (the adapted particle filter of many records is built for the SE kernel only: its kernel rows are SE-ARD's)";
 // the two rules that take a ParticleReq: the bootstrap filter and the fully adapted one (moment_particle_adapted.hip)
 bool mg_particle_rule(int method) { return method == MG_METHOD_PARTICLE || method == MG_METHOD_ADAPTED; }
-const char *const mg_adapted_no_smoother =
-    " (the adapted particle filter has no smoother and no backward simulation: they stand on the bootstrap filter's sets)";
 // The particle request beside a RecordsReq (MG_METHOD_PARTICLE): N particles per track, the caller's draws with their (group, record)
 // strides in doubles -- each 0 or the stride of a contiguous array -- and the outputs the Gaussian rules do not have
 struct ParticleReq {
@@ -1338,12 +1336,14 @@ int mg_records_run(Scratch &sc, const std::string &who, int method, int G, int n
         }
         ps.V = V; ps.R = R; ps.steps = steps; ps.N = pq->N; ps.D = D; ps.lens = lens; ps.particles = pa.particles; ps.ancestors = pa.ancestors;
         ps.trans_mean = sc.alloc<double>(nm_x * pq->N); ps.trans_var = sc.alloc<double>(nm_x * pq->N);
-        ps.weights = sc.alloc<double>(nlj * pq->N); ps.w_smooth = sc.alloc<double>(nlj * pq->N);
-        OP_CHECK(ps.trans_mean && ps.trans_var && ps.weights && ps.w_smooth, who);
+        // (the adapted rule: the filtered sets are equally weighted and particle i of a row is carried particle i of the next, so
+        // there is no `weights` stack and no omega; its backward simulation does not form w_smooth either)
+        ps.weights = ada ? nullptr : sc.alloc<double>(nlj * pq->N); ps.w_smooth = ada && bq ? nullptr : sc.alloc<double>(nlj * pq->N);
+        OP_CHECK(ps.trans_mean && ps.trans_var && (ada || ps.weights) && ((ada && bq) || ps.w_smooth), who);
         if (!bq) {
-            ps.cnorm = sc.alloc<double>(nlj * pq->N); ps.omega = sc.alloc<double>((size_t)V * pq->N);
+            ps.cnorm = sc.alloc<double>(nlj * pq->N); ps.omega = ada ? nullptr : sc.alloc<double>((size_t)V * pq->N);
             ps.m_smooth = sc.alloc<double>(nm_x); ps.S_smooth = sc.alloc<double>(nS_x); ps.ess_smooth = sc.alloc<double>(nlj);
-            OP_CHECK(ps.cnorm && ps.omega && ps.m_smooth && ps.S_smooth && ps.ess_smooth, who);
+            OP_CHECK(ps.cnorm && (ada || ps.omega) && ps.m_smooth && ps.S_smooth && ps.ess_smooth, who);
         } else {                                                                       // the trajectories: B * D doubles and B ints per track row
             const long long nu = (long long)steps * bq->B;
             pb.V = V; pb.R = R; pb.steps = steps; pb.N = pq->N; pb.D = D; pb.B = bq->B; pb.lens = lens; pb.particles = pa.particles;
@@ -1371,18 +1371,22 @@ int mg_records_run(Scratch &sc, const std::string &who, int method, int G, int n
         lf.nr = (lf.shared ? G * ra.Rp : ra.Rp) * nrow;
         for (int t = 0; t <= steps; ++t) {
             if (cub) launch_mg_crec_step(sc.stream, a, fa, ra, lf, coff, t);
-            else if (ada) launch_mg_parec_step(sc.stream, a, fa, ra, lf, pa, pd, t);
-            else if (par) {
+            else if (ada) {
+                launch_mg_parec_step(sc.stream, a, fa, ra, lf, pa, pd, t);
+                if (sq && t < steps) launch_mg_psm_keep(sc.stream, a, ra, lf, pa, ps, t);   // the same launch: (mu, s) of the set carried into row t
+            } else if (par) {
                 launch_mg_prec_step(sc.stream, a, fa, ra, lf, pa, t);
                 if (sq && t < steps) launch_mg_psm_keep(sc.stream, a, ra, lf, pa, ps, t);   // (mu, s) of step t, before the next weight launch
             } else launch_mg_lrec_step(sc.stream, a, fa, ra, lf, t);
         }
     }
     if (smooth) launch_mg_smooth(sc.stream, sa);
-    if (bq) {
+    if (bq && ada) launch_mg_pabs(sc.stream, pb);
+    else if (bq) {
         launch_mg_psm_weights(sc.stream, fa, ps);
         launch_mg_pbs(sc.stream, pb);
-    } else if (par && sq) launch_mg_psm_smooth(sc.stream, fa, ps, n_max);
+    } else if (ada && sq) launch_mg_pasm_smooth(sc.stream, ps, n_max);
+    else if (par && sq) launch_mg_psm_smooth(sc.stream, fa, ps, n_max);
     OP_TRY(hipGetLastError());
     if (bq) {
         const size_t Bn = (size_t)bq->B;
@@ -1569,7 +1573,6 @@ int records_given(const std::string &who, int method, int kind, int G, int n_mod
                       lpd_gauss};
     const RecordsReq rq{R, records_per_pass};
     bool nothing;
-    if (method == MG_METHOD_ADAPTED && sq) return set_error(nullptr, FFVD_EINVAL, bad + mg_adapted_no_smoother);
     if (int rc = records_checks(who, method, kind, G, n_models, M, P, D, C, steps, q_mode, f, rq, nothing, pq, S0s != nullptr)) return rc;
     if (sq && !nothing && !particle_smooth_ok(*sq, R, steps))
         return set_error(nullptr, FFVD_EINVAL, bad + " (every entry of lengths must lie in [1, steps])");
@@ -1609,7 +1612,6 @@ int records_posterior(const std::string &who, int method, int kind, int G, int n
                       lpd_gauss};
     const RecordsReq rq{R, records_per_pass};
     bool nothing;
-    if (method == MG_METHOD_ADAPTED && sq) return set_error(nullptr, FFVD_EINVAL, bad + mg_adapted_no_smoother);
     if (int rc = records_checks(who, method, kind, G, n_models, M, P, D, C, steps, q_mode, f, rq, nothing, pq, S0s != nullptr)) return rc;
     if (sq && !nothing && !particle_smooth_ok(*sq, R, steps))
         return set_error(nullptr, FFVD_EINVAL, bad + " (every entry of lengths must lie in [1, steps])");
@@ -1860,6 +1862,74 @@ extern "C" int ffvd_posterior_particle_backsim_records_grouped(int kind, int G, 
 }
 #undef FFVD_PARTICLE_BACKSIM_PARAMS
 #undef FFVD_PARTICLE_BACKSIM_REQ
+
+// The adapted filter's two calls followed by the marginal smoother, or by the backward simulation, on the ADAPTED sets
+// (moment_particle_adapted_smooth.hip): the argument lists of the four calls above without `weights` -- the filtered sets are equally
+// weighted.  The filter outputs are those of the adapted calls bit for bit; trans_mean[t] and trans_var[t] are the moments of the set
+// carried into row t.  (Not ffvd_op_*: see DESIGN.md section 9, "Particle smoothing".)
+#define FFVD_ADAPTED_SMOOTH_PARAMS                                                                                                           \
+    const int *lengths, double *m_smooth, double *S_smooth, double *ess_smooth, double *w_smooth, double *trans_mean, double *trans_var
+#define FFVD_ADAPTED_SMOOTH_REQ const ParticleSmoothReq sq{lengths, m_smooth, S_smooth, ess_smooth, w_smooth, nullptr, trans_mean, trans_var}
+#define FFVD_ADAPTED_BACKSIM_PARAMS                                                                                                          \
+    const int *lengths, int B, const double *unif_bs, long long unif_bs_stride_g, long long unif_bs_stride_r, double *trajectories,         \
+        int *traj_index, double *m_traj, double *S_traj, double *lag_cov, double *trans_mean, double *trans_var
+#define FFVD_ADAPTED_BACKSIM_REQ                                                                                                             \
+    const ParticleBacksimReq bq{B, unif_bs, unif_bs_stride_g, unif_bs_stride_r, trajectories, traj_index, m_traj, S_traj, lag_cov};          \
+    ParticleSmoothReq sq{lengths, nullptr, nullptr, nullptr, nullptr, nullptr, trans_mean, trans_var};                                       \
+    sq.bs = &bq
+#define FFVD_ADAPTED_GIVEN_HEAD                                                                                                              \
+    int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M, int P, int D, const double *logvariances, \
+        const double *loglengthscales, const double *fs, const double *const *q_sqrts, int q_mode, int R, const double *x_lasts,            \
+        const double *S0s, const double *ctrl, int C, int steps, const double *log_Qs, const double *CC, const double *DD,                  \
+        const double *noise_std, int J, const double *Y_obs, int records_per_pass, FFVD_PARTICLE_PARAMS, double *m_pred, double *S_pred,    \
+        double *m_filt, double *S_filt, double *lpd, double *lpd_joint, double *y_mean, double *y_var_total, double *lpd_mix,               \
+        double *lpd_gauss, double *ess, double *log_evidence, double *particles, int *ancestors
+#define FFVD_ADAPTED_GIVEN_CALL(who)                                                                                                         \
+    records_given(who, MG_METHOD_ADAPTED, kind, G, n_models, Lm_inverse_seqs, Zs, M, P, D, logvariances, loglengthscales, fs, q_sqrts, q_mode, \
+                  R, x_lasts, S0s, ctrl, C, steps, log_Qs, CC, DD, noise_std, J, Y_obs, records_per_pass, m_pred, S_pred, m_filt, S_filt,   \
+                  nullptr, lpd, lpd_joint, nullptr, nullptr, y_mean, y_var_total, lpd_mix, lpd_gauss, &pq, &sq)
+#define FFVD_ADAPTED_POSTERIOR_HEAD                                                                                                          \
+    int kind, int G, int n_models, const double *Zs, int M, int P, int D, const double *logvariances, const double *loglengthscales,        \
+        const double *Xs, const double *ctrl_fit, int C, int T, const double *log_Qs, double jitter, int groups_per_pass, int q_mode,       \
+        int R, const double *x0s, const double *S0s, const double *ctrl_roll, int steps, const double *CC, const double *DD,                \
+        const double *noise_std, int J, const double *Y_obs, int records_per_pass, FFVD_PARTICLE_PARAMS, double *m_pred, double *S_pred,    \
+        double *m_filt, double *S_filt, double *lpd, double *lpd_joint, double *y_mean, double *y_var_total, double *lpd_mix,               \
+        double *lpd_gauss, double *ess, double *log_evidence, double *particles, int *ancestors
+#define FFVD_ADAPTED_POSTERIOR_CALL(who)                                                                                                     \
+    records_posterior(who, MG_METHOD_ADAPTED, kind, G, n_models, Zs, M, P, D, logvariances, loglengthscales, Xs, ctrl_fit, C, T, log_Qs,    \
+                      jitter, groups_per_pass, q_mode, R, x0s, S0s, ctrl_roll, steps, CC, DD, noise_std, J, Y_obs, records_per_pass, m_pred, \
+                      S_pred, m_filt, S_filt, nullptr, lpd, lpd_joint, nullptr, nullptr, y_mean, y_var_total, lpd_mix, lpd_gauss, U_means,  \
+                      &pq, &sq)
+extern "C" int ffvd_particle_adapted_smooth_records_grouped(FFVD_ADAPTED_GIVEN_HEAD, FFVD_ADAPTED_SMOOTH_PARAMS) {
+    FFVD_PARTICLE_REQ;
+    FFVD_ADAPTED_SMOOTH_REQ;
+    return FFVD_ADAPTED_GIVEN_CALL("ffvd_particle_adapted_smooth_records_grouped");
+}
+extern "C" int ffvd_posterior_particle_adapted_smooth_records_grouped(FFVD_ADAPTED_POSTERIOR_HEAD, FFVD_ADAPTED_SMOOTH_PARAMS,
+                                                                      double *U_means) {
+    FFVD_PARTICLE_REQ;
+    FFVD_ADAPTED_SMOOTH_REQ;
+    return FFVD_ADAPTED_POSTERIOR_CALL("ffvd_posterior_particle_adapted_smooth_records_grouped");
+}
+extern "C" int ffvd_particle_adapted_backsim_records_grouped(FFVD_ADAPTED_GIVEN_HEAD, FFVD_ADAPTED_BACKSIM_PARAMS) {
+    FFVD_PARTICLE_REQ;
+    FFVD_ADAPTED_BACKSIM_REQ;
+    return FFVD_ADAPTED_GIVEN_CALL("ffvd_particle_adapted_backsim_records_grouped");
+}
+extern "C" int ffvd_posterior_particle_adapted_backsim_records_grouped(FFVD_ADAPTED_POSTERIOR_HEAD, FFVD_ADAPTED_BACKSIM_PARAMS,
+                                                                       double *U_means) {
+    FFVD_PARTICLE_REQ;
+    FFVD_ADAPTED_BACKSIM_REQ;
+    return FFVD_ADAPTED_POSTERIOR_CALL("ffvd_posterior_particle_adapted_backsim_records_grouped");
+}
+#undef FFVD_ADAPTED_SMOOTH_PARAMS
+#undef FFVD_ADAPTED_SMOOTH_REQ
+#undef FFVD_ADAPTED_BACKSIM_PARAMS
+#undef FFVD_ADAPTED_BACKSIM_REQ
+#undef FFVD_ADAPTED_GIVEN_HEAD
+#undef FFVD_ADAPTED_GIVEN_CALL
+#undef FFVD_ADAPTED_POSTERIOR_HEAD
+#undef FFVD_ADAPTED_POSTERIOR_CALL
 #undef FFVD_PARTICLE_PARAMS
 #undef FFVD_PARTICLE_REQ
 #undef FFVD_RECORDS_GIVEN_PARAMS

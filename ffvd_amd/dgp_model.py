@@ -661,7 +661,8 @@ class DGPSSM:
         order) and the two forms (collapsed U: ONE `posterior_filter_adapted_records_grouped` call; explicit U: `kernel_pre_cal` once,
         then `filter_adapted_records_grouped`) are `filter_records_particle`'s; prediction.filter_adapted_records_grouped has the
         method and the dict that is returned: particles[t] is the equally weighted filtered set after row t (not X^-) and
-        ancestors[t, i] indexes the set carried into row t.  No smoothing and no forecasts on the adapted sets."""
+        ancestors[t, i] indexes the set carried into row t.  Smoothing and joint trajectories on the adapted sets are
+        `smooth_records_adapted` and `sample_records_adapted`; there are no forecasts on them."""
         return DGPSSM._records_particle(self, "filter_records_adapted", "filter_adapted_records_grouped", Y_records, control_records,
                                         num_particles, lengths, x0, S0, q_mode, Y_train_std, records_per_pass, seed, noise, return_particles)
 
@@ -693,6 +694,38 @@ class DGPSSM:
         if isinstance(B, bool) or not isinstance(B, (int, np.integer)) or not 1 <= B <= 4096:
             raise ValueError(f"sample_records_particle: num_trajectories: expected an integer in [1, 4096], got {num_trajectories!r}")
         return DGPSSM._records_particle(self, "sample_records_particle", "backsim_particle_records_grouped", Y_records, control_records,
+                                        num_particles, lengths, x0, S0, q_mode, Y_train_std, records_per_pass, seed, noise, return_particles,
+                                        int(B))
+
+    def smooth_records_adapted(self, Y_records, control_records=None, *, num_particles=256, lengths=None, x0=None, S0=None,
+                               q_mode="reference", Y_train_std=1.0, records_per_pass=0, seed=None, noise="shared", return_particles=False):
+        """`filter_records_adapted` followed by the marginal particle smoother of every (chain, record) track on the adapted sets in
+        the same call: the smoother to use where the observations are informative and `smooth_records_particle` inherits the
+        bootstrap filter's collapsed sets.  The parameters, the checks, the draw generation (the same seed gives
+        `filter_records_adapted`'s draws, hence its filter bit for bit) and the two forms (collapsed U: ONE
+        `posterior_smooth_adapted_records_grouped` call; explicit U: `kernel_pre_cal` once, then `smooth_adapted_records_grouped`)
+        are `filter_records_particle`'s; prediction.smooth_adapted_records_grouped has the method and the dict that is returned: the
+        adapted filter's, plus m_smooth, S_smooth and ess_smooth (S, R, steps, ...), with return_particles also w_smooth, trans_mean
+        and trans_var (no weights: the filtered sets are equally weighted)."""
+        return DGPSSM._records_particle(self, "smooth_records_adapted", "smooth_adapted_records_grouped", Y_records, control_records,
+                                        num_particles, lengths, x0, S0, q_mode, Y_train_std, records_per_pass, seed, noise, return_particles)
+
+    def sample_records_adapted(self, Y_records, control_records=None, *, num_particles=256, num_trajectories=64, lengths=None, x0=None,
+                               S0=None, q_mode="reference", Y_train_std=1.0, records_per_pass=0, seed=None, noise="shared",
+                               return_particles=False):
+        """`filter_records_adapted` followed by the backward simulation of `num_trajectories` joint smoothed trajectories of every
+        (chain, record) track on the adapted sets in the same call: `sample_records_particle` on the filter that does not collapse.
+        The parameters, the checks and the two forms (collapsed U: ONE `posterior_backsim_adapted_records_grouped` call; explicit U:
+        `kernel_pre_cal` once, then `backsim_adapted_records_grouped`) are `sample_records_particle`'s.  The filter's draws are drawn
+        first and in `filter_records_adapted`'s order, so the same seed gives the same filter, bit for bit; the uniforms of the
+        backward simulation (steps, num_trajectories), with the leading dimensions of `noise`, are drawn after them.
+        prediction.backsim_adapted_records_grouped has the method and the dict that is returned: the adapted filter's, plus
+        trajectories (S, R, B, steps, D), traj_index (S, R, steps, B), m_traj, S_traj and lag_cov, with return_particles also
+        trans_mean and trans_var."""
+        B = num_trajectories
+        if isinstance(B, bool) or not isinstance(B, (int, np.integer)) or not 1 <= B <= 4096:
+            raise ValueError(f"sample_records_adapted: num_trajectories: expected an integer in [1, 4096], got {num_trajectories!r}")
+        return DGPSSM._records_particle(self, "sample_records_adapted", "backsim_adapted_records_grouped", Y_records, control_records,
                                         num_particles, lengths, x0, S0, q_mode, Y_train_std, records_per_pass, seed, noise, return_particles,
                                         int(B))
 

@@ -1056,10 +1056,11 @@ def _particle_records_given(who, smooth, Lm_inverse_seqs, Zs, kerns, U_vals, q_s
     N, pargs, keep = _pack_particles(who, G, R, steps, D, eps, unif, xi0, r["S0"] is not None, return_particles)
     m = _pack_summary(who, D, R * steps, CC, DD, log_Rchols, r["Y"].reshape(R * steps, r["J"]))
     out, extra, oargs = _particle_call(m, G, R, steps, D, N, bool(return_particles))
-    sm, sargs = _smooth_or_backsim_call(who, r, G, D, N, bool(return_particles), smooth, unif_bs)
+    sm, sargs = _smooth_or_backsim_call(who, r, G, D, N, bool(return_particles), smooth, unif_bs, adapted)
     dp = _lib.dptr
     opt = lambda x: None if x is None else dp(x)
-    entry = ("ffvd_particle_backsim_records_grouped" if unif_bs is not None else "ffvd_particle_smooth_records_grouped") if smooth else \
+    rule = "particle_adapted" if adapted else "particle"
+    entry = f"ffvd_{rule}_{'smooth' if unif_bs is None else 'backsim'}_records_grouped" if smooth else \
         "ffvd_particle_adapted_records_grouped" if adapted else "ffvd_op_filter_particle_records_grouped"
     rc = getattr(_lib.load(), entry)(*args[:13], R, dp(r["x0"]), opt(r["S0"]), opt(r["ctrl"]), *args[16:], dp(m["CC"]), dp(m["DD"]), dp(m["sd"]),
                                      m["J"], dp(m["Y"]), r["rpp"], *pargs, *oargs, *sargs)
@@ -1093,10 +1094,11 @@ def _particle_records_posterior(who, smooth, Zs, kerns, Xs, Qs, control_inputs, 
     N, pargs, keep = _pack_particles(who, G, R, steps, D, eps, unif, xi0, r["S0"] is not None, return_particles)
     m = _pack_summary(who, D, R * steps, CC, DD, log_Rchols, r["Y"].reshape(R * steps, r["J"]))
     out, extra, oargs = _particle_call(m, G, R, steps, D, N, bool(return_particles))
-    sm, sargs = _smooth_or_backsim_call(who, r, G, D, N, bool(return_particles), smooth, unif_bs)
+    sm, sargs = _smooth_or_backsim_call(who, r, G, D, N, bool(return_particles), smooth, unif_bs, adapted)
     dp = _lib.dptr
     opt = lambda x: None if x is None else dp(x)
-    entry = ("ffvd_posterior_particle_backsim_records_grouped" if unif_bs is not None else "ffvd_posterior_particle_smooth_records_grouped") \
+    rule = "particle_adapted" if adapted else "particle"
+    entry = f"ffvd_posterior_{rule}_{'smooth' if unif_bs is None else 'backsim'}_records_grouped" \
         if smooth else "ffvd_posterior_particle_adapted_records_grouped" if adapted else "ffvd_op_posterior_filter_particle_records_grouped"
     rc = getattr(_lib.load(), entry)(*args[:17], R, opt(r["x0"]), opt(r["S0"]), opt(r["ctrl"]), steps, dp(m["CC"]), dp(m["DD"]), dp(m["sd"]),
                                      m["J"], dp(m["Y"]), r["rpp"], *pargs, *oargs, *sargs, None)
@@ -1127,8 +1129,9 @@ def filter_adapted_records_grouped(Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, 
     = m_pred / S_pred bit for bit: a record that is all NaN returns `filter_particle_records_grouped`'s particles bit for bit.
     log_evidence stays the unbiased SMC estimate.
     Two of the returned arrays differ in meaning from the bootstrap call's: particles[t] (G, R, steps, N, D) is X_{t+1}, the equally
-    weighted FILTERED set after row t (not X^-), and ancestors[t, i] indexes the set carried INTO row t.  There is no smoothing, no
-    backward simulation and no forecast on the adapted sets ("Adapted particle filtering")."""
+    weighted FILTERED set after row t (not X^-), and ancestors[t, i] indexes the set carried INTO row t.  Smoothing and backward
+    simulation on the adapted sets are `smooth_adapted_records_grouped` and `backsim_adapted_records_grouped`; there is no forecast on
+    them ("Adapted particle filtering")."""
     return _particle_records_given("filter_adapted_records_grouped", False, Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_records,
                                    Y_records, Qs, CC, DD, log_Rchols, eps, unif, xi0, lengths, S0s, q_mode, Y_train_std, records_per_pass,
                                    return_particles, adapted=True)
@@ -1151,17 +1154,18 @@ SMOOTH_PARTICLE_KEYS = ("m_smooth", "S_smooth", "ess_smooth")
 SMOOTH_PARTICLE_STACKS = ("w_smooth", "weights", "trans_mean", "trans_var")
 
 
-def _smooth_call(r, G, D, N, return_particles):
-    """Output arrays and the trailing arguments (lengths, m_smooth .. trans_var) of the two particle smoothing entry points."""
+def _smooth_call(r, G, D, N, return_particles, adapted=False):
+    """Output arrays and the trailing arguments (lengths, m_smooth .. trans_var) of the two particle smoothing entry points; with
+    `adapted` of the two on the adapted sets, which have no `weights`."""
     import ctypes
     R, steps, dp = r["R"], r["steps"], _lib.dptr
     sm = dict(m_smooth=np.empty((G, R, steps, D)), S_smooth=np.empty((G, R, steps, D, D)), ess_smooth=np.empty((G, R, steps)))
+    stacks = tuple(k for k in SMOOTH_PARTICLE_STACKS if not (adapted and k == "weights"))
     if return_particles:
-        sm.update(w_smooth=np.empty((G, R, steps, N)), weights=np.empty((G, R, steps, N)), trans_mean=np.empty((G, R, steps, N, D)),
-                  trans_var=np.empty((G, R, steps, N, D)))
+        sm.update({k: np.empty((G, R, steps, N) + ((D,) if k.startswith("trans_") else ())) for k in stacks})
     sm["_lengths"] = np.ascontiguousarray(r["lengths"], dtype=np.int32)                 # (kept alive with the outputs)
     args = (sm["_lengths"].ctypes.data_as(ctypes.POINTER(ctypes.c_int)),) + tuple(dp(sm[k]) for k in SMOOTH_PARTICLE_KEYS) + \
-        tuple(dp(sm[k]) if return_particles else None for k in SMOOTH_PARTICLE_STACKS)
+        tuple(dp(sm[k]) if return_particles else None for k in stacks)
     return sm, args
 
 
@@ -1218,16 +1222,18 @@ BACKSIM_KEYS = ("trajectories", "traj_index", "m_traj", "S_traj", "lag_cov")
 BACKSIM_STACKS = ("weights", "trans_mean", "trans_var")
 
 
-def _smooth_or_backsim_call(who, r, G, D, N, return_particles, smooth, unif_bs):
+def _smooth_or_backsim_call(who, r, G, D, N, return_particles, smooth, unif_bs, adapted=False):
     """`_smooth_call`, `_backsim_call` or nothing, by the form of the particle call"""
     if not smooth:
         return {}, ()
-    return _smooth_call(r, G, D, N, return_particles) if unif_bs is None else _backsim_call(who, r, G, D, N, return_particles, unif_bs)
+    return _smooth_call(r, G, D, N, return_particles, adapted) if unif_bs is None else \
+        _backsim_call(who, r, G, D, N, return_particles, unif_bs, adapted)
 
 
-def _backsim_call(who, r, G, D, N, return_particles, unif_bs):
+def _backsim_call(who, r, G, D, N, return_particles, unif_bs, adapted=False):
     """Checks of `unif_bs` (before the library is loaded), output arrays and the trailing arguments (lengths, B, unif_bs and its
-    strides, trajectories .. trans_var) of the two backward-simulation entry points."""
+    strides, trajectories .. trans_var) of the two backward-simulation entry points; with `adapted` of the two on the adapted sets,
+    which have no `weights`."""
     import ctypes
     R, steps, dp = r["R"], r["steps"], _lib.dptr
     u = np.asarray(unif_bs, dtype=np.float64)
@@ -1243,12 +1249,13 @@ def _backsim_call(who, r, G, D, N, return_particles, unif_bs):
         raise ValueError(f"{who}: G * R * B = {G * R * B} must stay below 2^31")
     sm = dict(trajectories=np.empty((G, R, B, steps, D)), traj_index=np.empty((G, R, steps, B), dtype=np.int32), m_traj=np.empty((G, R, steps, D)),
               S_traj=np.empty((G, R, steps, D, D)), lag_cov=np.empty((G, R, steps, D, D)))
+    stacks = tuple(k for k in BACKSIM_STACKS if not (adapted and k == "weights"))
     if return_particles:
-        sm.update(weights=np.empty((G, R, steps, N)), trans_mean=np.empty((G, R, steps, N, D)), trans_var=np.empty((G, R, steps, N, D)))
+        sm.update({k: np.empty((G, R, steps, N) + ((D,) if k.startswith("trans_") else ())) for k in stacks})
     sm["_lengths"], sm["_unif_bs"] = np.ascontiguousarray(r["lengths"], dtype=np.int32), u     # (kept alive with the outputs)
     ip = ctypes.POINTER(ctypes.c_int)
     args = (sm["_lengths"].ctypes.data_as(ip), B, dp(u), ug, ur, dp(sm["trajectories"]), sm["traj_index"].ctypes.data_as(ip)) + \
-        tuple(dp(sm[k]) for k in BACKSIM_KEYS[2:]) + tuple(dp(sm[k]) if return_particles else None for k in BACKSIM_STACKS)
+        tuple(dp(sm[k]) for k in BACKSIM_KEYS[2:]) + tuple(dp(sm[k]) if return_particles else None for k in stacks)
     return sm, args
 
 
@@ -1292,6 +1299,76 @@ def posterior_backsim_particle_records_grouped(Zs, kerns, Xs, Qs, control_inputs
                                        Y_records, CC, DD, log_Rchols, eps, unif, xi0, lengths, x0s, S0s, q_mode, Y_train_std, jitter,
                                        groups_per_pass, records_per_pass, return_particles,
                                        _need(unif_bs, "posterior_backsim_particle_records_grouped"))
+
+
+def smooth_adapted_records_grouped(Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_records, Y_records, Qs, CC, DD, log_Rchols,
+                                   eps, unif, *, xi0=None, lengths=None, S0s=None, q_mode="reference", Y_train_std=1.0, records_per_pass=0,
+                                   return_particles=False):
+    """`filter_adapted_records_grouped` followed by the marginal particle smoother of every track on the ADAPTED sets in ONE call
+    (`ffvd_particle_adapted_smooth_records_grouped`).  The parameters and their checks are `smooth_particle_records_grouped`'s; every
+    key of `filter_adapted_records_grouped`'s dict is returned bit for bit (the same draws); no GP is evaluated beyond the filter's
+    and no draw is added.  Where the bootstrap filter collapses, `smooth_particle_records_grouped` inherits its collapsed sets and
+    this call does not.
+    Per track of n = lengths[r] rows, with P_t = particles[t] the equally weighted filtered set after row t and mu_t = trans_mean[t],
+    s_t = trans_var[t] the filter's (mu, s) of the set carried into row t -- for t >= 1 the transition moments of P_{t-1}, particle by
+    particle; row 0 belongs to the start set and is not read: w_smooth[n-1, i] = 1 / N; for t = n-2 .. 0, with x_j = P_{t+1,j}:
+    log f_ij = -1/2 sum_d ((x_jd - mu_{t+1,id})^2 / s_{t+1,id} + log s_{t+1,id}), c_j = log sum_i exp log f_ij, w_smooth[t, i] =
+    sum_j w_smooth[t+1, j] exp(log f_ij - c_j).  There is no fold through the ancestors and no emission weight (particle i of row t
+    IS carried particle i of row t + 1, and the sets are equally weighted); nothing is renormalised.
+    Adds to the dict, per track: m_smooth (G, R, steps, D) and S_smooth (G, R, steps, D, D), the w_smooth-weighted mean and centred
+    covariance of P_t (exactly symmetric), and ess_smooth (G, R, steps) = (sum w)^2 / sum w^2.  With return_particles also w_smooth
+    (G, R, steps, N), trans_mean and trans_var (G, R, steps, N, D) beside particles and ancestors; there is no `weights`.  NaN at and
+    beyond a record's length.  A record of one row returns the plain mean and covariance of P_0: the unweighted particle estimate,
+    not the Rao-Blackwellised m_filt / S_filt.  A record that is all NaN returns `smooth_particle_records_grouped`'s arrays bit for
+    bit.  A track's arrays are bit-identical whatever the other groups, the other records, their order and records_per_pass are
+    ("Adapted particle smoothing")."""
+    return _particle_records_given("smooth_adapted_records_grouped", True, Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_records,
+                                   Y_records, Qs, CC, DD, log_Rchols, eps, unif, xi0, lengths, S0s, q_mode, Y_train_std, records_per_pass,
+                                   return_particles, adapted=True)
+
+
+def posterior_smooth_adapted_records_grouped(Zs, kerns, Xs, Qs, control_inputs, control_records, Y_records, CC, DD, log_Rchols, eps, unif, *,
+                                             xi0=None, lengths=None, x0s=None, S0s=None, q_mode="reference", Y_train_std=1.0, jitter=JITTER,
+                                             groups_per_pass=0, records_per_pass=0, return_particles=False):
+    """The collapsed posterior of G groups and `smooth_adapted_records_grouped` in ONE call
+    (`ffvd_posterior_particle_adapted_smooth_records_grouped`): what `conditionals_multi_output.collapse_u_mean_grouped` followed by
+    `smooth_adapted_records_grouped` computes, without the posteriors leaving the device.  The parameters are
+    `posterior_filter_particle_records_grouped`'s, the returned dict is `smooth_adapted_records_grouped`'s."""
+    return _particle_records_posterior("posterior_smooth_adapted_records_grouped", True, Zs, kerns, Xs, Qs, control_inputs, control_records,
+                                       Y_records, CC, DD, log_Rchols, eps, unif, xi0, lengths, x0s, S0s, q_mode, Y_train_std, jitter,
+                                       groups_per_pass, records_per_pass, return_particles, adapted=True)
+
+
+def backsim_adapted_records_grouped(Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_records, Y_records, Qs, CC, DD, log_Rchols,
+                                    eps, unif, unif_bs, *, xi0=None, lengths=None, S0s=None, q_mode="reference", Y_train_std=1.0,
+                                    records_per_pass=0, return_particles=False):
+    """`filter_adapted_records_grouped` followed by the backward simulation of B joint smoothed trajectories of every track on the
+    ADAPTED sets in ONE call (`ffvd_particle_adapted_backsim_records_grouped`).  The parameters and their checks are
+    `backsim_particle_records_grouped`'s; every key of `filter_adapted_records_grouped`'s dict is returned bit for bit.
+    Per track of n = lengths[r] rows and trajectory b, with u = unif_bs[t, b] and the notation of `smooth_adapted_records_grouped`:
+    k_{n-1} = min(#{k: k + 1 <= u N}, N - 1) (the filter's scan and search on unit weights); for t = n-2 .. 0, with
+    x = P_{t+1, k_{t+1}}: p_i = exp(log f_i - max_i log f_i), cdf the running sum of p, k_t = min(#{i: cdf_i <= u tot}, N - 1): the
+    searched index itself, without an ancestor indirection.  Conditional on the filter's run P(k_t = k) = w_smooth[t, k].
+    Adds to the dict traj_index, trajectories (= particles[t, k_t], a gather, bit for bit), m_traj, S_traj and lag_cov with
+    `backsim_particle_records_grouped`'s shapes and conventions.  With return_particles also trans_mean and trans_var beside
+    particles and ancestors; there is no `weights`.  A record that is all NaN returns `backsim_particle_records_grouped`'s traj_index
+    and trajectories for the same unif_bs bit for bit ("Adapted particle smoothing")."""
+    return _particle_records_given("backsim_adapted_records_grouped", True, Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_records,
+                                   Y_records, Qs, CC, DD, log_Rchols, eps, unif, xi0, lengths, S0s, q_mode, Y_train_std, records_per_pass,
+                                   return_particles, _need(unif_bs, "backsim_adapted_records_grouped"), adapted=True)
+
+
+def posterior_backsim_adapted_records_grouped(Zs, kerns, Xs, Qs, control_inputs, control_records, Y_records, CC, DD, log_Rchols, eps, unif,
+                                              unif_bs, *, xi0=None, lengths=None, x0s=None, S0s=None, q_mode="reference", Y_train_std=1.0,
+                                              jitter=JITTER, groups_per_pass=0, records_per_pass=0, return_particles=False):
+    """The collapsed posterior of G groups and `backsim_adapted_records_grouped` in ONE call
+    (`ffvd_posterior_particle_adapted_backsim_records_grouped`): what `conditionals_multi_output.collapse_u_mean_grouped` followed by
+    `backsim_adapted_records_grouped` computes, without the posteriors leaving the device.  The parameters are
+    `posterior_filter_particle_records_grouped`'s plus unif_bs, the returned dict is `backsim_adapted_records_grouped`'s."""
+    return _particle_records_posterior("posterior_backsim_adapted_records_grouped", True, Zs, kerns, Xs, Qs, control_inputs, control_records,
+                                       Y_records, CC, DD, log_Rchols, eps, unif, xi0, lengths, x0s, S0s, q_mode, Y_train_std, jitter,
+                                       groups_per_pass, records_per_pass, return_particles,
+                                       _need(unif_bs, "posterior_backsim_adapted_records_grouped"), adapted=True)
 
 
 def _need(unif_bs, who):

@@ -933,8 +933,9 @@ int  ffvd_op_posterior_filter_particle_records_grouped(int kind, int G, int n_mo
  * The outputs have that call's names and shapes with two differences: particles[t] is X_{t+1}, the equally weighted FILTERED set
  * after row t (not X^-), and ancestors[t, i] indexes the set carried INTO row t.  log_evidence stays the unbiased SMC estimate; the
  * pooled arrays are formed as in that call (y_mean, y_var_total, lpd_gauss from (m_pred, S_pred); lpd_mix from lpd).  Three launches
- * per step as that call: only the per-track weight kernel differs.  There is no smoother, no backward simulation and no forecast
- * on the adapted sets.  Limits: those of ffvd_op_filter_particle_records_grouped.  G = 0, R = 0 or steps = 0: FFVD_OK, nothing is
+ * per step as that call: only the per-track weight kernel differs.  Smoothing and backward simulation on the adapted sets are
+ * ffvd_particle_adapted_smooth_records_grouped and ffvd_particle_adapted_backsim_records_grouped; there is no forecast on them.
+ * Limits: those of ffvd_op_filter_particle_records_grouped.  G = 0, R = 0 or steps = 0: FFVD_OK, nothing is
  * touched. */
 int  ffvd_particle_adapted_records_grouped(int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M,
                                            int P, int D, const double *logvariances, const double *loglengthscales, const double *fs,
@@ -1078,6 +1079,109 @@ int  ffvd_posterior_particle_backsim_records_grouped(int kind, int G, int n_mode
                                                      long long unif_bs_stride_g, long long unif_bs_stride_r, double *trajectories,
                                                      int *traj_index, double *m_traj, double *S_traj, double *lag_cov, double *weights,
                                                      double *trans_mean, double *trans_var, double *U_means);
+
+/* ffvd_particle_adapted_records_grouped followed by the marginal particle smoother of every (group, record) track on the ADAPTED
+ * sets.  The arguments are those of ffvd_particle_smooth_records_grouped without `weights` (the filtered sets are equally weighted);
+ * the filter outputs are those of ffvd_particle_adapted_records_grouped, bit for bit (the same draws); no GP is evaluated beyond the
+ * filter's and no draw is added.  Per track of n = lengths[r] rows, with P_t = particles[t] the equally weighted filtered set after
+ * row t:
+ *   kept       trans_mean[t], trans_var[t] = (mu, s) of that call for the set carried into row t: for t >= 1 the transition moments
+ *              of P_{t-1}, particle by particle (row 0 belongs to the start set and is not read by the recursion)
+ *   last row   w_smooth[n-1, i] = 1 / N
+ *   backward   for t = n-2 .. 0, with x_j = P_{t+1,j}, mu_i = trans_mean[t+1, i], s_i = trans_var[t+1, i]:
+ *              log f_ij, c_j as in ffvd_particle_smooth_records_grouped
+ *              w_smooth[t, i] = sum_j w_smooth[t+1, j] exp(log f_ij - c_j)                (j ascending, every exponent <= 0)
+ *              no fold through the ancestors, no emission weight, nothing is renormalised
+ *   moments    m_smooth[t], S_smooth[t] (exactly symmetric), ess_smooth[t] from (w_smooth[t], P_t) as in that call
+ * A record of one row returns the plain mean and covariance of P_0: the unweighted particle estimate, not the Rao-Blackwellised
+ * m_filt / S_filt.  An all-NaN record returns ffvd_particle_smooth_records_grouped's new outputs bit for bit.  Outputs, each of which
+ * may be NULL, NaN at and beyond a record's length: m_smooth, S_smooth, ess_smooth, w_smooth, trans_mean, trans_var with that call's
+ * shapes.  A track does not depend on the other groups, the other records, their order or records_per_pass (bit for bit).  The
+ * device holds (3 D + 2) N doubles and N ints per track row beside the filter's buffers (FFVD_ENOMEM if they cannot be had).
+ * Limits: those of ffvd_op_filter_particle_records_grouped.  G = 0, R = 0 or steps = 0: FFVD_OK, nothing is touched. */
+int  ffvd_particle_adapted_smooth_records_grouped(int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs,
+                                                  int M, int P, int D, const double *logvariances, const double *loglengthscales,
+                                                  const double *fs, const double *const *q_sqrts, int q_mode, int R,
+                                                  const double *x_lasts, const double *S0s, const double *ctrl, int C, int steps,
+                                                  const double *log_Qs, const double *CC, const double *DD, const double *noise_std,
+                                                  int J, const double *Y_obs, int records_per_pass, int N, const double *eps,
+                                                  long long eps_stride_g, long long eps_stride_r, const double *unif,
+                                                  long long unif_stride_g, long long unif_stride_r, const double *xi0,
+                                                  long long xi0_stride_g, long long xi0_stride_r, double *m_pred, double *S_pred,
+                                                  double *m_filt, double *S_filt, double *lpd, double *lpd_joint, double *y_mean,
+                                                  double *y_var_total, double *lpd_mix, double *lpd_gauss, double *ess,
+                                                  double *log_evidence, double *particles, int *ancestors, const int *lengths,
+                                                  double *m_smooth, double *S_smooth, double *ess_smooth, double *w_smooth,
+                                                  double *trans_mean, double *trans_var);
+
+/* ffvd_op_posterior_grouped followed by ffvd_particle_adapted_smooth_records_grouped WITHOUT the posteriors leaving the device: the
+ * arguments of ffvd_posterior_particle_smooth_records_grouped without `weights`; U_means stays last. */
+int  ffvd_posterior_particle_adapted_smooth_records_grouped(int kind, int G, int n_models, const double *Zs, int M, int P, int D,
+                                                            const double *logvariances, const double *loglengthscales,
+                                                            const double *Xs, const double *ctrl_fit, int C, int T,
+                                                            const double *log_Qs, double jitter, int groups_per_pass, int q_mode,
+                                                            int R, const double *x0s, const double *S0s, const double *ctrl_roll,
+                                                            int steps, const double *CC, const double *DD, const double *noise_std,
+                                                            int J, const double *Y_obs, int records_per_pass, int N, const double *eps,
+                                                            long long eps_stride_g, long long eps_stride_r, const double *unif,
+                                                            long long unif_stride_g, long long unif_stride_r, const double *xi0,
+                                                            long long xi0_stride_g, long long xi0_stride_r, double *m_pred,
+                                                            double *S_pred, double *m_filt, double *S_filt, double *lpd,
+                                                            double *lpd_joint, double *y_mean, double *y_var_total, double *lpd_mix,
+                                                            double *lpd_gauss, double *ess, double *log_evidence, double *particles,
+                                                            int *ancestors, const int *lengths, double *m_smooth, double *S_smooth,
+                                                            double *ess_smooth, double *w_smooth, double *trans_mean,
+                                                            double *trans_var, double *U_means);
+
+/* ffvd_particle_adapted_records_grouped followed by the backward simulation of B joint smoothed trajectories per (group, record)
+ * track on the ADAPTED sets.  The arguments are those of ffvd_particle_backsim_records_grouped without `weights`; the filter outputs
+ * are those of ffvd_particle_adapted_records_grouped, bit for bit.  Per track of n rows and trajectory b, with u = unif_bs[t, b] and
+ * the notation of ffvd_particle_adapted_smooth_records_grouped:
+ *   row n-1    k_{n-1} = min(#{k: k + 1 <= u N}, N - 1): the filter's scan and search on unit weights
+ *   backward   for t = n-2 .. 0, with x = P_{t+1, k_{t+1}}:  p_i = exp(log f_i - max_i log f_i), cdf = the running sum of p in index
+ *              order, k_t = min(#{i: cdf_i <= u tot}, N - 1): the searched index itself, no ancestor indirection; clamped into
+ *              [0, N) before it addresses anything
+ *   outputs    traj_index, trajectories[b, t, :] = P_{t, k_t} (a gather, bit for bit), m_traj, S_traj, lag_cov as in
+ *              ffvd_particle_backsim_records_grouped; then trans_mean and trans_var
+ * Conditional on the filter's run P(k_t = k) = w_smooth[t, k] of ffvd_particle_adapted_smooth_records_grouped.  An all-NaN record
+ * returns ffvd_particle_backsim_records_grouped's traj_index and trajectories for the same unif_bs, bit for bit.  Limits: those of
+ * ffvd_particle_backsim_records_grouped.  G = 0, R = 0 or steps = 0: FFVD_OK, nothing is touched. */
+int  ffvd_particle_adapted_backsim_records_grouped(int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs,
+                                                   int M, int P, int D, const double *logvariances, const double *loglengthscales,
+                                                   const double *fs, const double *const *q_sqrts, int q_mode, int R,
+                                                   const double *x_lasts, const double *S0s, const double *ctrl, int C, int steps,
+                                                   const double *log_Qs, const double *CC, const double *DD, const double *noise_std,
+                                                   int J, const double *Y_obs, int records_per_pass, int N, const double *eps,
+                                                   long long eps_stride_g, long long eps_stride_r, const double *unif,
+                                                   long long unif_stride_g, long long unif_stride_r, const double *xi0,
+                                                   long long xi0_stride_g, long long xi0_stride_r, double *m_pred, double *S_pred,
+                                                   double *m_filt, double *S_filt, double *lpd, double *lpd_joint, double *y_mean,
+                                                   double *y_var_total, double *lpd_mix, double *lpd_gauss, double *ess,
+                                                   double *log_evidence, double *particles, int *ancestors, const int *lengths, int B,
+                                                   const double *unif_bs, long long unif_bs_stride_g, long long unif_bs_stride_r,
+                                                   double *trajectories, int *traj_index, double *m_traj, double *S_traj,
+                                                   double *lag_cov, double *trans_mean, double *trans_var);
+
+/* ffvd_op_posterior_grouped followed by ffvd_particle_adapted_backsim_records_grouped WITHOUT the posteriors leaving the device: the
+ * arguments of ffvd_posterior_particle_backsim_records_grouped without `weights`; U_means stays last. */
+int  ffvd_posterior_particle_adapted_backsim_records_grouped(int kind, int G, int n_models, const double *Zs, int M, int P, int D,
+                                                             const double *logvariances, const double *loglengthscales,
+                                                             const double *Xs, const double *ctrl_fit, int C, int T,
+                                                             const double *log_Qs, double jitter, int groups_per_pass, int q_mode,
+                                                             int R, const double *x0s, const double *S0s, const double *ctrl_roll,
+                                                             int steps, const double *CC, const double *DD, const double *noise_std,
+                                                             int J, const double *Y_obs, int records_per_pass, int N,
+                                                             const double *eps, long long eps_stride_g, long long eps_stride_r,
+                                                             const double *unif, long long unif_stride_g, long long unif_stride_r,
+                                                             const double *xi0, long long xi0_stride_g, long long xi0_stride_r,
+                                                             double *m_pred, double *S_pred, double *m_filt, double *S_filt,
+                                                             double *lpd, double *lpd_joint, double *y_mean, double *y_var_total,
+                                                             double *lpd_mix, double *lpd_gauss, double *ess, double *log_evidence,
+                                                             double *particles, int *ancestors, const int *lengths, int B,
+                                                             const double *unif_bs, long long unif_bs_stride_g,
+                                                             long long unif_bs_stride_r, double *trajectories, int *traj_index,
+                                                             double *m_traj, double *S_traj, double *lag_cov, double *trans_mean,
+                                                             double *trans_var, double *U_means);
 
 /* Rolling-origin multi-step forecasts in one call: ffvd_op_filter_grouped (same arguments, same outputs, each of which may be NULL),
  * then from every origin o = origins[b] (n_origins rows of the record, strictly ascending, 0 <= o <= steps - 1 - horizon) `horizon`
