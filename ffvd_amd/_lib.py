@@ -44,6 +44,8 @@ _dp = C.POINTER(C.c_double)
 _PARTICLE_DRAWS = [C.c_int] + [_dp, C.c_longlong, C.c_longlong] * 3
 # N, then eps, unif and xi0 each with its group stride, then eps_fc with its group and origin stride (the particle forecasts' draws)
 _PARTICLE_FC_DRAWS = [C.c_int] + [_dp, C.c_longlong] * 3 + [_dp, C.c_longlong, C.c_longlong]
+# N, then the seed and the noise mode that stand in for the draws of a seeded call
+_PARTICLE_SEED = [C.c_int, C.c_ulonglong, C.c_int]
 _SIGNATURES = {
     "ffvd_create": (C.c_int, [C.POINTER(FfvdConfig), C.POINTER(C.c_void_p)]),
     "ffvd_destroy": (C.c_int, [C.c_void_p]),
@@ -233,6 +235,19 @@ _SIGNATURES = {
                                                                           C.c_int] + _PARTICLE_DRAWS + [_dp] * 13 +
                                                                          [C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, _dp, C.c_longlong,
                                                                           C.c_longlong, _dp, C.POINTER(C.c_int)] + [_dp] * 5 + [_dp]),
+    # seeded draws generated on the device: rule, stage, the heads of the particle calls, then N, seed, noise, the filter's outputs,
+    # lengths, B, trajectories, traj_index, m_traj .. trans_var, m_smooth .. w_smooth (U_means stays last)
+    "ffvd_particle_seeded_records_grouped": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), _dp, C.c_int, C.c_int,
+                                                       C.c_int, _dp, _dp, _dp, C.POINTER(C.c_void_p), C.c_int, C.c_int, _dp, _dp, _dp, C.c_int,
+                                                       C.c_int, _dp, _dp, _dp, _dp, C.c_int, _dp, C.c_int] + _PARTICLE_SEED + [_dp] * 13 +
+                                                      [C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, _dp, C.POINTER(C.c_int)] + [_dp] * 10),
+    "ffvd_posterior_particle_seeded_records_grouped": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_int, C.c_int, _dp,
+                                                                 _dp, _dp, _dp, C.c_int, C.c_int, _dp, C.c_double, C.c_int, C.c_int, C.c_int,
+                                                                 _dp, _dp, _dp, C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_int] +
+                                                                _PARTICLE_SEED + [_dp] * 13 +
+                                                                [C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, _dp, C.POINTER(C.c_int)] +
+                                                                [_dp] * 10 + [_dp]),
+    "ffvd_particle_draws": (C.c_int, [C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp]),
     "ffvd_op_forecast_grouped": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp,
                                            C.POINTER(C.c_void_p), C.c_int, _dp, _dp, _dp, C.c_int, C.c_int, _dp,
                                            _dp, _dp, _dp, C.c_int, _dp] + [_dp] * 13 +

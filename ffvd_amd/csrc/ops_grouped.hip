@@ -8,6 +8,7 @@
 #include "conditional_group.h"
 #include "predict_summary.h"
 #include "moment_group.h"
+#include "moment_particle_draws.h"
 #include "transition_grad.h"
 
 #include <cmath>
@@ -1134,6 +1135,10 @@ struct ParticleReq {
     double *ess, *log_evidence;                  // [G][R][steps], [G][R]
     double *particles;                           // [G][R][steps][N][D] or NULL
     int *ancestors;                              // [G][R][steps][N] or NULL
+    // seeded: eps, unif, xi0 (and unif_bs of a ParticleBacksimReq beside it) are NULL and the driver fills their device buffers from
+    // `seed` through the same strides (moment_particle_draws.hip); there is nothing on the host to check or to upload
+    bool seeded = false;
+    unsigned long long seed = 0;
 };
 // The backward-simulation request beside a ParticleSmoothReq (moment_particle_backsim.hip): B trajectories per track from the
 // caller's uniforms; with it the smoother's recursion is not run (its m_smooth .. w_smooth stay NULL)
@@ -1172,12 +1177,15 @@ size_t particle_extent(long long sg, long long sr, long long inner, int G, int R
     return (size_t)inner * (sr ? R : 1) * (sg ? G : 1);
 }
 // the checks of a backward-simulation request that need no device: B, the strides, G * R * B within the grid, unif_bs in [0, 1)
-bool particle_backsim_ok(const ParticleBacksimReq &q, int G, int R, int steps, bool nothing) {
+bool particle_backsim_ok(const ParticleBacksimReq &q, int G, int R, int steps, bool nothing, bool seeded) {
     if (q.B < 1 || q.B > MG_PBS_MAXB) return false;
     const long long nu = (long long)steps * q.B;
     if (!particle_strides_ok(q.unif_g, q.unif_r, nu, R)) return false;
     if (nothing) return true;
-    if ((long long)G * R > ((1LL << 31) - 1) / q.B || !q.unif_bs) return false;
+    if ((long long)G * R > ((1LL << 31) - 1) / q.B) return false;
+    if (seeded)                                                                        // (the fill launch: a block below 2^31 doubles, its grid x)
+        return nu < (1LL << 31) && (((nu + 1) / 2 + 255) / 256) * G * R < (1LL << 31);
+    if (!q.unif_bs) return false;
     const size_t n_u = particle_extent(q.unif_g, q.unif_r, nu, G, R);
     for (size_t e = 0; e < n_u; ++e)
         if (!(q.unif_bs[e] >= 0.0 && q.unif_bs[e] < 1.0)) return false;
@@ -1192,6 +1200,7 @@ bool particle_ok(const ParticleReq &q, int G, int R, int steps, int D, bool with
         return false;
     if (nothing) return true;
     if ((long long)G * R > ((1LL << 31) - 1) / steps / q.N / D) return false;          // G * R * steps * N * D < 2^31
+    if (q.seeded) return true;                                                         // (generated values: finite, unif in [0, 1))
     if (!q.eps || !q.unif || (with_S0 && !q.xi0)) return false;
     const size_t n_eps = particle_extent(q.eps_g, q.eps_r, ne, G, R), n_u = particle_extent(q.unif_g, q.unif_r, steps, G, R);
     for (size_t e = 0; e < n_eps; ++e)
@@ -1301,20 +1310,37 @@ int mg_records_run(Scratch &sc, const std::string &who, int method, int G, int n
     double *coff = cub ? sc.alloc<double>((size_t)2 * G * Rp * D * D) : nullptr;
     OP_CHECK(lf.K && lf.vpart && (par || lf.msum) && (!cub || coff), who);
     MomentParticleArgs pa{};
-    if (par) {                                                                         // the draws, uploaded once; the particles of a pass
+    // the draws of one stream on the device: the caller's, uploaded, or (seeded) a buffer of the same extent that one fill launch
+    // writes through the same strides, every double of it
+    bool fill_refused = false;
+    auto draws = [&](const double *src, int stream_id, bool normal, long long len, long long sg, long long sr) -> const double * {
+        const size_t n = particle_extent(sg, sr, len, G, R);
+        if (!pq->seeded) return sc.upload(src, n);
+        double *d = sc.alloc<double>(n);
+        const MomentParticleDrawsArgs da{(unsigned)(pq->seed & 0xFFFFFFFFull), (unsigned)(pq->seed >> 32), stream_id, normal ? 1 : 0,
+                                         sg ? G : 1, sr ? R : 1, (int)len, sg, sr, d};
+        if (d && !launch_mg_pdraw_fill(sc.stream, da)) fill_refused = true;               // (its grid does not fit: not an allocation failure)
+        return d;
+    };
+    const auto fill_error = [&] {
+        return set_error(nullptr, FFVD_EINVAL, who + ": bad argument (the fill launch of the seeded draws needs ceil(block / 512) * blocks < 2^31)");
+    };
+    if (par) {                                                                         // the draws, staged once; the particles of a pass
         const ParticleReq &q = *pq;
         const long long ne = (long long)steps * q.N * D, nx = (long long)q.N * D;
         pa.N = q.N; pa.eps_g = q.eps_g; pa.eps_r = q.eps_r; pa.unif_g = q.unif_g; pa.unif_r = q.unif_r; pa.xi0_g = q.xi0_g; pa.xi0_r = q.xi0_r;
-        pa.eps = sc.upload(q.eps, particle_extent(q.eps_g, q.eps_r, ne, G, R));
-        pa.unif = sc.upload(q.unif, particle_extent(q.unif_g, q.unif_r, steps, G, R));
-        pa.xi0 = dS0 ? sc.upload(q.xi0, particle_extent(q.xi0_g, q.xi0_r, nx, G, R)) : nullptr;
+        pa.eps = draws(q.eps, MG_PDRAW_EPS, true, ne, q.eps_g, q.eps_r);
+        pa.unif = draws(q.unif, MG_PDRAW_UNIF, false, steps, q.unif_g, q.unif_r);
+        pa.xi0 = dS0 ? draws(q.xi0, MG_PDRAW_XI0, true, nx, q.xi0_g, q.xi0_r) : nullptr;
         pa.xstate = sc.alloc<double>((size_t)2 * G * Rp * q.N * D);
         pa.pmean = sc.alloc<double>((size_t)G * Rp * D * q.N);
         pa.ess = sc.alloc<double>(nlj);
         pa.particles = q.particles || sq ? sc.alloc<double>(nm_x * q.N) : nullptr;
         pa.ancestors = q.ancestors || sq ? sc.alloc<int>(nlj * q.N) : nullptr;
+        if (fill_refused) return fill_error();
         OP_CHECK(pa.eps && pa.unif && (!dS0 || pa.xi0) && pa.xstate && pa.pmean && pa.ess && (!(q.particles || sq) || pa.particles) &&
                  (!(q.ancestors || sq) || pa.ancestors), who);
+        if (q.seeded) OP_TRY(hipGetLastError());
     }
     MomentParticleAdaptedArgs pd{};
     if (ada) {                                                                         // (mu, s) of the parents of the row in flight
@@ -1349,11 +1375,13 @@ int mg_records_run(Scratch &sc, const std::string &who, int method, int G, int n
             pb.V = V; pb.R = R; pb.steps = steps; pb.N = pq->N; pb.D = D; pb.B = bq->B; pb.lens = lens; pb.particles = pa.particles;
             pb.ancestors = pa.ancestors; pb.trans_mean = ps.trans_mean; pb.trans_var = ps.trans_var; pb.weights = ps.weights;
             pb.unif_g = bq->unif_g; pb.unif_r = bq->unif_r;
-            pb.unif = sc.upload(bq->unif_bs, particle_extent(bq->unif_g, bq->unif_r, nu, G, R));
+            pb.unif = draws(bq->unif_bs, MG_PDRAW_UNIF_BS, false, nu, bq->unif_g, bq->unif_r);
             pb.inv_var = sc.alloc<double>(nm_x * pq->N); pb.log_var = sc.alloc<double>(nlj * pq->N);
             pb.traj_index = sc.alloc<int>(nlj * bq->B); pb.trajectories = sc.alloc<double>(nm_x * bq->B);
             pb.m_traj = sc.alloc<double>(nm_x); pb.S_traj = sc.alloc<double>(nS_x); pb.lag_cov = sc.alloc<double>(nS_x);
+            if (fill_refused) return fill_error();
             OP_CHECK(pb.unif && pb.inv_var && pb.log_var && pb.traj_index && pb.trajectories && pb.m_traj && pb.S_traj && pb.lag_cov, who);
+            if (pq->seeded) OP_TRY(hipGetLastError());
         }
     }
     OP_TRY(hipMemsetAsync(lf.K, 0, (size_t)lf.units * lf.Tp * Mp * sizeof(double), sc.stream));          // rows no pass fills stay zeros
@@ -1576,7 +1604,7 @@ int records_given(const std::string &who, int method, int kind, int G, int n_mod
     if (int rc = records_checks(who, method, kind, G, n_models, M, P, D, C, steps, q_mode, f, rq, nothing, pq, S0s != nullptr)) return rc;
     if (sq && !nothing && !particle_smooth_ok(*sq, R, steps))
         return set_error(nullptr, FFVD_EINVAL, bad + " (every entry of lengths must lie in [1, steps])");
-    if (sq && sq->bs && !particle_backsim_ok(*sq->bs, G, R, steps, nothing))
+    if (sq && sq->bs && !particle_backsim_ok(*sq->bs, G, R, steps, nothing, pq && pq->seeded))
         return set_error(nullptr, FFVD_EINVAL, bad + " (1 <= B <= 4096, unif_bs in [0, 1), strides 0 or contiguous and G * R * B < 2^31 are needed)");
     if (nothing) return FFVD_OK;
     if (!Lm_inverse_seqs || !Zs || !logvariances || !loglengthscales || !fs || !x_lasts || !log_Qs || (C > 0 && !ctrl) ||
@@ -1615,7 +1643,7 @@ int records_posterior(const std::string &who, int method, int kind, int G, int n
     if (int rc = records_checks(who, method, kind, G, n_models, M, P, D, C, steps, q_mode, f, rq, nothing, pq, S0s != nullptr)) return rc;
     if (sq && !nothing && !particle_smooth_ok(*sq, R, steps))
         return set_error(nullptr, FFVD_EINVAL, bad + " (every entry of lengths must lie in [1, steps])");
-    if (sq && sq->bs && !particle_backsim_ok(*sq->bs, G, R, steps, nothing))
+    if (sq && sq->bs && !particle_backsim_ok(*sq->bs, G, R, steps, nothing, pq && pq->seeded))
         return set_error(nullptr, FFVD_EINVAL, bad + " (1 <= B <= 4096, unif_bs in [0, 1), strides 0 or contiguous and G * R * B < 2^31 are needed)");
     if (!pg_scalars_ok(kind, G, n_models, M, P, D, C, T, groups_per_pass, jitter)) return set_error(nullptr, FFVD_EINVAL, bad);
     if (nothing) return FFVD_OK;
@@ -1932,6 +1960,151 @@ extern "C" int ffvd_posterior_particle_adapted_backsim_records_grouped(FFVD_ADAP
 #undef FFVD_ADAPTED_POSTERIOR_CALL
 #undef FFVD_PARTICLE_PARAMS
 #undef FFVD_PARTICLE_REQ
+
+// The twelve particle calls above with seeded draws generated on the device (moment_particle_draws.hip; DESIGN.md section 9, "Device
+// draws"): rule 0 bootstrap / 1 adapted, stage 0 filter / 1 marginal smoother / 2 backward simulation select the entry point whose
+// launches run, `seed` and `noise` (0 shared, 1 per record, 2 independent) stand in for its draw arrays and their strides.  The driver
+// is mg_records_run with a seeded ParticleReq: one fill launch per stream writes the buffers the caller's arrays are uploaded into
+// otherwise, so every output is that entry point's, bit for bit, on the arrays of ffvd_particle_draws(seed, noise, ..).
+// (Not ffvd_op_*: see DESIGN.md section 9, "Particle smoothing".)
+namespace {
+constexpr int SEEDED_FILTER = 0, SEEDED_SMOOTH = 1, SEEDED_BACKSIM = 2;
+// the strides of a noise mode over blocks of `inner` doubles: (group, record)
+void seeded_strides(int noise, int R, long long inner, long long &sg, long long &sr) {
+    sr = noise == MG_PDRAW_SHARED ? 0 : inner;
+    sg = noise == MG_PDRAW_INDEPENDENT ? inner * R : 0;
+}
+// The three requests of a seeded call; sq_or_null() is what records_given / records_posterior take beside &pq
+struct SeededReq {
+    int method;
+    ParticleReq pq;
+    ParticleBacksimReq bq;
+    ParticleSmoothReq sq;
+    bool with_sq;
+    const ParticleSmoothReq *sq_or_null() const { return with_sq ? &sq : nullptr; }
+};
+struct SeededOut {                                       // the outputs beyond the filter's, and `lengths`
+    const int *lengths;
+    int B;
+    double *trajectories;
+    int *traj_index;
+    double *m_traj, *S_traj, *lag_cov, *weights, *trans_mean, *trans_var, *m_smooth, *S_smooth, *ess_smooth, *w_smooth;
+};
+// rule, stage, noise; the outputs (and `lengths`) that the (rule, stage) does not have must be NULL.  q is filled in place: q.sq.bs
+// points into it.
+int seeded_request(const std::string &who, int rule, int stage, unsigned long long seed, int noise, int R, int steps, int N, int D,
+                   const SeededOut &o, double *ess, double *log_evidence, double *particles, int *ancestors, SeededReq &q) {
+    const std::string bad = who + ": bad argument";
+    if ((rule != 0 && rule != 1) || stage < SEEDED_FILTER || stage > SEEDED_BACKSIM || noise < MG_PDRAW_SHARED || noise > MG_PDRAW_INDEPENDENT)
+        return set_error(nullptr, FFVD_EINVAL, bad + " (rule 0 or 1, stage 0, 1 or 2 and noise 0, 1 or 2 are needed)");
+    std::string extra;
+    auto must_be_null = [&](const void *p, const char *name) {
+        if (p) extra += (extra.empty() ? "" : ", ") + std::string(name);
+    };
+    if (stage == SEEDED_FILTER) must_be_null(o.lengths, "lengths");
+    if (stage != SEEDED_BACKSIM) {
+        must_be_null(o.trajectories, "trajectories"); must_be_null(o.traj_index, "traj_index"); must_be_null(o.m_traj, "m_traj");
+        must_be_null(o.S_traj, "S_traj"); must_be_null(o.lag_cov, "lag_cov");
+    }
+    if (stage == SEEDED_FILTER || rule == 1) must_be_null(o.weights, "weights");
+    if (stage == SEEDED_FILTER) { must_be_null(o.trans_mean, "trans_mean"); must_be_null(o.trans_var, "trans_var"); }
+    if (stage != SEEDED_SMOOTH) {
+        must_be_null(o.m_smooth, "m_smooth"); must_be_null(o.S_smooth, "S_smooth"); must_be_null(o.ess_smooth, "ess_smooth");
+        must_be_null(o.w_smooth, "w_smooth");
+    }
+    if (!extra.empty())
+        return set_error(nullptr, FFVD_EINVAL, bad + " (rule " + std::to_string(rule) + ", stage " + std::to_string(stage) +
+                                               " does not produce " + extra + ": NULL is needed there)");
+    q.method = rule ? MG_METHOD_ADAPTED : MG_METHOD_PARTICLE;
+    q.pq = ParticleReq{N, nullptr, 0, 0, nullptr, 0, 0, nullptr, 0, 0, ess, log_evidence, particles, ancestors};
+    q.pq.seeded = true;
+    q.pq.seed = seed;
+    seeded_strides(noise, R, (long long)steps * N * D, q.pq.eps_g, q.pq.eps_r);
+    seeded_strides(noise, R, steps, q.pq.unif_g, q.pq.unif_r);
+    seeded_strides(noise, R, (long long)N * D, q.pq.xi0_g, q.pq.xi0_r);
+    q.bq = ParticleBacksimReq{o.B, nullptr, 0, 0, o.trajectories, o.traj_index, o.m_traj, o.S_traj, o.lag_cov};
+    seeded_strides(noise, R, (long long)steps * o.B, q.bq.unif_g, q.bq.unif_r);
+    q.sq = ParticleSmoothReq{o.lengths, o.m_smooth, o.S_smooth, o.ess_smooth, o.w_smooth, o.weights, o.trans_mean, o.trans_var};
+    q.sq.bs = stage == SEEDED_BACKSIM ? &q.bq : nullptr;
+    q.with_sq = stage != SEEDED_FILTER;
+    return FFVD_OK;
+}
+}  // namespace
+
+#define FFVD_SEEDED_TAIL_PARAMS                                                                                                              \
+    int N, unsigned long long seed, int noise, double *m_pred, double *S_pred, double *m_filt, double *S_filt, double *lpd,                 \
+        double *lpd_joint, double *y_mean, double *y_var_total, double *lpd_mix, double *lpd_gauss, double *ess, double *log_evidence,      \
+        double *particles, int *ancestors, const int *lengths, int B, double *trajectories, int *traj_index, double *m_traj,                \
+        double *S_traj, double *lag_cov, double *weights, double *trans_mean, double *trans_var, double *m_smooth, double *S_smooth,        \
+        double *ess_smooth, double *w_smooth
+#define FFVD_SEEDED_REQ(who)                                                                                                                 \
+    const SeededOut so{lengths, B, trajectories, traj_index, m_traj, S_traj, lag_cov, weights, trans_mean, trans_var, m_smooth, S_smooth,   \
+                       ess_smooth, w_smooth};                                                                                               \
+    SeededReq q;                                                                                                                             \
+    if (int rc = seeded_request(who, rule, stage, seed, noise, R, steps, N, D, so, ess, log_evidence, particles, ancestors, q)) return rc
+extern "C" int ffvd_particle_seeded_records_grouped(int rule, int stage, int kind, int G, int n_models, const double *const *Lm_inverse_seqs,
+                                                    const double *Zs, int M, int P, int D, const double *logvariances,
+                                                    const double *loglengthscales, const double *fs, const double *const *q_sqrts, int q_mode,
+                                                    int R, const double *x_lasts, const double *S0s, const double *ctrl, int C, int steps,
+                                                    const double *log_Qs, const double *CC, const double *DD, const double *noise_std, int J,
+                                                    const double *Y_obs, int records_per_pass, FFVD_SEEDED_TAIL_PARAMS) {
+    const char *who = "ffvd_particle_seeded_records_grouped";
+    FFVD_SEEDED_REQ(who);
+    return records_given(who, q.method, kind, G, n_models, Lm_inverse_seqs, Zs, M, P, D, logvariances, loglengthscales, fs, q_sqrts, q_mode, R,
+                         x_lasts, S0s, ctrl, C, steps, log_Qs, CC, DD, noise_std, J, Y_obs, records_per_pass, m_pred, S_pred, m_filt, S_filt,
+                         nullptr, lpd, lpd_joint, nullptr, nullptr, y_mean, y_var_total, lpd_mix, lpd_gauss, &q.pq, q.sq_or_null());
+}
+
+extern "C" int ffvd_posterior_particle_seeded_records_grouped(int rule, int stage, int kind, int G, int n_models, const double *Zs, int M, int P,
+                                                              int D, const double *logvariances, const double *loglengthscales,
+                                                              const double *Xs, const double *ctrl_fit, int C, int T, const double *log_Qs,
+                                                              double jitter, int groups_per_pass, int q_mode, int R, const double *x0s,
+                                                              const double *S0s, const double *ctrl_roll, int steps, const double *CC,
+                                                              const double *DD, const double *noise_std, int J, const double *Y_obs,
+                                                              int records_per_pass, FFVD_SEEDED_TAIL_PARAMS, double *U_means) {
+    const char *who = "ffvd_posterior_particle_seeded_records_grouped";
+    FFVD_SEEDED_REQ(who);
+    return records_posterior(who, q.method, kind, G, n_models, Zs, M, P, D, logvariances, loglengthscales, Xs, ctrl_fit, C, T, log_Qs, jitter,
+                             groups_per_pass, q_mode, R, x0s, S0s, ctrl_roll, steps, CC, DD, noise_std, J, Y_obs, records_per_pass, m_pred,
+                             S_pred, m_filt, S_filt, nullptr, lpd, lpd_joint, nullptr, nullptr, y_mean, y_var_total, lpd_mix, lpd_gauss,
+                             U_means, &q.pq, q.sq_or_null());
+}
+#undef FFVD_SEEDED_TAIL_PARAMS
+#undef FFVD_SEEDED_REQ
+
+// The draws a seeded call uses, generated on the device and downloaded: eps lead + [steps][N][D], unif lead + [steps], xi0 lead + [N][D],
+// unif_bs lead + [steps][B], lead = (), (R,) or (G, R) for noise 0, 1 or 2.  Each output may be NULL; B may be 0 when unif_bs is.
+extern "C" int ffvd_particle_draws(unsigned long long seed, int noise, int G, int R, int steps, int N, int D, int B, double *eps, double *unif,
+                                   double *xi0, double *unif_bs) {
+    const std::string who = "ffvd_particle_draws", bad = who + ": bad argument";
+    if (noise < MG_PDRAW_SHARED || noise > MG_PDRAW_INDEPENDENT || G < 0 || R < 0 || steps < 0 || N < MG_PREC_MINN || N > MG_PREC_MAXN ||
+        D < 1 || D > MG_MAXD || B < 0 || B > MG_PBS_MAXB || (unif_bs && B < 1))
+        return set_error(nullptr, FFVD_EINVAL, bad + " (noise 0, 1 or 2, G, R, steps >= 0, 2 <= N <= 2048, 1 <= D <= 8 and 0 <= B <= 4096, "
+                                               "B >= 1 with unif_bs, are needed)");
+    if (G == 0 || R == 0 || steps == 0) return FFVD_OK;
+    if ((long long)G * R > ((1LL << 31) - 1) / steps / N / D || (B && (long long)G * R > ((1LL << 31) - 1) / B) ||
+        (long long)steps * B >= (1LL << 31))
+        return set_error(nullptr, FFVD_EINVAL, bad + " (G * R * steps * N * D < 2^31, G * R * B < 2^31 and steps * B < 2^31 are needed)");
+    OP_BEGIN(who);
+    struct One { double *dst; int stream_id; bool normal; long long len; };
+    const One all[4] = {{eps, MG_PDRAW_EPS, true, (long long)steps * N * D}, {unif, MG_PDRAW_UNIF, false, steps},
+                        {xi0, MG_PDRAW_XI0, true, (long long)N * D}, {unif_bs, MG_PDRAW_UNIF_BS, false, (long long)steps * B}};
+    for (const One &s : all) {
+        if (!s.dst) continue;
+        long long sg, sr;
+        seeded_strides(noise, R, s.len, sg, sr);
+        const size_t n = particle_extent(sg, sr, s.len, G, R);
+        double *d = sc.alloc<double>(n);
+        OP_CHECK(d, who);
+        const MomentParticleDrawsArgs da{(unsigned)(seed & 0xFFFFFFFFull), (unsigned)(seed >> 32), s.stream_id, s.normal ? 1 : 0,
+                                         sg ? G : 1, sr ? R : 1, (int)s.len, sg, sr, d};
+        if (!launch_mg_pdraw_fill(sc.stream, da)) return set_error(nullptr, FFVD_EINVAL, bad + " (the fill launch's grid does not fit)");
+        OP_TRY(hipGetLastError());
+        if (!sc.download(s.dst, d, n * sizeof(double)))
+            return set_error(nullptr, FFVD_EDEVICE, who + ": copying the results back failed");
+    }
+    return FFVD_OK;
+}
 #undef FFVD_RECORDS_GIVEN_PARAMS
 #undef FFVD_RECORDS_GIVEN_ARGS
 #undef FFVD_RECORDS_POSTERIOR_PARAMS

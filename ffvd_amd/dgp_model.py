@@ -754,10 +754,40 @@ class DGPSSM:
         return DGPSSM._filter_records(self, who, fn, Y_records, control_records, lengths, x0, S0, None, q_mode,
                                       Y_train_std, records_per_pass, draws)
 
-    def _filter_records(self, who, fn, Y_records, control_records, lengths, x0, S0, smooth, q_mode, Y_train_std, records_per_pass, draws=None):
+    def particle_records_seeded(self, Y_records, control_records=None, *, rule="bootstrap", stage="filter", num_particles=256,
+                                num_trajectories=0, lengths=None, x0=None, S0=None, q_mode="reference", Y_train_std=1.0, records_per_pass=0,
+                                seed=None, noise="shared", return_particles=False):
+        """The six particle methods above with the draws generated on the DEVICE from a seed instead of by NumPy on the host:
+        rule "bootstrap" / "adapted" and stage "filter" / "smooth" / "backsim" select `filter_records_particle`,
+        `smooth_records_particle`, `sample_records_particle` (num_trajectories, with stage="backsim" only) or their adapted
+        siblings, whose other parameters, checks, two forms (collapsed U: ONE `posterior_particle_records_seeded` call; explicit U:
+        `kernel_pre_cal` once, then `particle_records_seeded`) and returned dict these are.  Nothing is generated, scanned or
+        uploaded by the host, so the 1 GiB refusal of noise="independent" does not apply: the library's own index limit
+        (S * R * steps * N * D < 2^31) does, with its message.  seed: an integer in [0, 2^64); None takes one 64-bit integer from the
+        model's generator.  The streams are Philox4x32-10, not NumPy's: the same seed does NOT reproduce `filter_records_particle`'s
+        draws, it reproduces this method's, whatever the number of chains and records and records_per_pass are
+        (prediction.particle_draws returns them; DESIGN.md section 9, "Device draws").  A method of its own: the parameter lists of
+        the six methods above are pinned."""
+        from . import prediction as pr
+        who = "particle_records_seeded"
+        if seed is None:
+            seed = int(self._rng.integers(0, 2 ** 64, dtype=np.uint64))
+        shape = np.shape(Y_records)
+        if len(shape) != 3 or shape[0] < 1 or shape[1] < 1:
+            raise ValueError(f"{who}: Y_records: expected (R, steps, {self.Y.shape[1]}), got {shape}")
+        pr._pack_seeded(who, self.num_chains, shape[0], shape[1], self.output_dim, num_particles, rule, stage, seed, noise, num_trajectories,
+                        return_particles)
+        seeded = dict(rule=rule, stage=stage, num_particles=num_particles, num_trajectories=num_trajectories, seed=seed, noise=noise,
+                      return_particles=return_particles)
+        return DGPSSM._filter_records(self, who, who, Y_records, control_records, lengths, x0, S0, None, q_mode, Y_train_std,
+                                      records_per_pass, seeded=seeded)
+
+    def _filter_records(self, who, fn, Y_records, control_records, lengths, x0, S0, smooth, q_mode, Y_train_std, records_per_pass, draws=None,
+                        seeded=None):
         """The body of `filter_records`, `filter_records_cubature` and `filter_records_particle` (called through the class, as
         `_filter_heldout`): `fn` names the prediction-level function of the explicit form, "posterior_" + fn the fused one; draws: the
-        particle filter's eps, unif, xi0 and return_particles (it has no `smooth`)."""
+        particle filter's eps, unif, xi0 and return_particles (it has no `smooth`); seeded: the keywords of `particle_records_seeded`
+        in their place."""
         from . import conditionals_multi_output as cmo
         from . import prediction as pr
         if q_mode not in cmo.Q_MODES:
@@ -788,6 +818,9 @@ class DGPSSM:
             del kw["smooth"]
             tail = (draws["eps"], draws["unif"]) + ((draws["unif_bs"],) if "unif_bs" in draws else ())
             kw.update(xi0=draws["xi0"], return_particles=draws["return_particles"])
+        if seeded is not None:                                    # the draws are the device's: nothing follows log_Rchols, no `smooth`
+            del kw["smooth"]
+            kw.update(seeded)
         if self.U_collapse:
             return getattr(pr, "posterior_" + fn)(lay.Z, lay.kernel, [self._X_chains[s_] for s_ in range(S)], self.Q, self.control_inputs,
                                                   control_records, Y, lik.CC, lik.DD, lik.log_Rchols, *tail, x0s=x0s, **kw)

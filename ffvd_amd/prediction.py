@@ -1377,6 +1377,175 @@ def _need(unif_bs, who):
     return unif_bs
 
 
+PARTICLE_RULES = ("bootstrap", "adapted")
+PARTICLE_STAGES = ("filter", "smooth", "backsim")
+PARTICLE_NOISE = ("shared", "per_record", "independent")
+
+
+def _is_int(x):
+    return isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_))
+
+
+def _seed_and_noise(who, seed, noise):
+    """The checks of a seed (an integer in [0, 2^64)) and a noise mode; returns (seed, index of the mode)."""
+    if not _is_int(seed) or not 0 <= int(seed) < 2 ** 64:
+        raise ValueError(f"{who}: seed: expected an integer in [0, 2^64), got {seed!r}")
+    if not isinstance(noise, str) or noise not in PARTICLE_NOISE:
+        raise ValueError(f"{who}: noise: expected \"shared\", \"per_record\" or \"independent\", got {noise!r}")
+    return int(seed), PARTICLE_NOISE.index(noise)
+
+
+def particle_draws(seed, noise, G, R, steps, N, D, *, with_xi0=False, B=0):
+    """The draws a seeded particle call uses (`ffvd_particle_draws`): generated on the device by Philox4x32-10 and downloaded, for
+    inspection, for a reference, or to feed the calls that take the caller's arrays -- `particle_records_seeded(.., seed, noise)`
+    equals its sibling on these arrays bit for bit.  An element is a pure function of (seed, stream, group, record, index in the
+    block): the arrays of a call with fewer groups, records or steps are slices of a larger call's.  noise: "shared" (no leading
+    dimensions), "per_record" (R,) or "independent" (G, R).  Returns a dict: eps lead + (steps, N, D) standard normal, unif
+    lead + (steps,) in [0, 1), with_xi0 also xi0 lead + (N, D) standard normal, B >= 1 also unif_bs lead + (steps, B) in [0, 1)
+    ("Device draws")."""
+    who = "particle_draws"
+    seed, mode = _seed_and_noise(who, seed, noise)
+    for name, v, lo, hi in (("G", G, 1, None), ("R", R, 1, None), ("steps", steps, 1, None), ("N", N, PARTICLE_MIN_N, PARTICLE_MAX_N),
+                            ("D", D, 1, 8), ("B", B, 0, BACKSIM_MAX_B)):
+        if not _is_int(v) or v < lo or (hi is not None and v > hi):
+            raise ValueError(f"{who}: {name}: expected an integer " + (f"in [{lo}, {hi}]" if hi is not None else f">= {lo}") + f", got {v!r}")
+    if not isinstance(with_xi0, (bool, np.bool_)):
+        raise ValueError(f"{who}: with_xi0: expected a bool, got {with_xi0!r}")
+    G, R, steps, N, D, B = (int(v) for v in (G, R, steps, N, D, B))
+    if G * R * steps * N * D >= 2 ** 31:
+        raise ValueError(f"{who}: G * R * steps * N * D = {G * R * steps * N * D} must stay below 2^31")
+    if G * R * B >= 2 ** 31 or steps * B >= 2 ** 31:
+        raise ValueError(f"{who}: G * R * B = {G * R * B} and steps * B = {steps * B} must stay below 2^31")
+    lead = ((), (R,), (G, R))[mode]
+    out = dict(eps=np.empty(lead + (steps, N, D)), unif=np.empty(lead + (steps,)))
+    if with_xi0:
+        out["xi0"] = np.empty(lead + (N, D))
+    if B:
+        out["unif_bs"] = np.empty(lead + (steps, B))
+    dp = _lib.dptr
+    rc = _lib.load().ffvd_particle_draws(seed, mode, G, R, steps, N, D, B, *(dp(out[k]) if k in out else None
+                                                                            for k in ("eps", "unif", "xi0", "unif_bs")))
+    _lib.check(rc, None, who)
+    return out
+
+
+def _pack_seeded(who, G, R, steps, D, num_particles, rule, stage, seed, noise, num_trajectories, return_particles):
+    """The checks of the scalars of a seeded call (before the library is loaded).  Returns N, B and the leading arguments rule, stage
+    and the middle ones N, seed, noise of the entry points."""
+    if not isinstance(rule, str) or rule not in PARTICLE_RULES:
+        raise ValueError(f"{who}: rule: expected \"bootstrap\" or \"adapted\", got {rule!r}")
+    if not isinstance(stage, str) or stage not in PARTICLE_STAGES:
+        raise ValueError(f"{who}: stage: expected \"filter\", \"smooth\" or \"backsim\", got {stage!r}")
+    seed, mode = _seed_and_noise(who, seed, noise)
+    N, B = num_particles, num_trajectories
+    if not _is_int(N) or not PARTICLE_MIN_N <= N <= PARTICLE_MAX_N:
+        raise ValueError(f"{who}: num_particles: expected an integer in [{PARTICLE_MIN_N}, {PARTICLE_MAX_N}], got {N!r}")
+    if stage == "backsim":
+        if not _is_int(B) or not 1 <= B <= BACKSIM_MAX_B:
+            raise ValueError(f"{who}: num_trajectories: expected an integer in [1, {BACKSIM_MAX_B}] with stage=\"backsim\", got {B!r}")
+    elif not _is_int(B) or B != 0:
+        raise ValueError(f"{who}: num_trajectories: only stage=\"backsim\" draws trajectories, expected 0 with stage={stage!r}, got {B!r}")
+    if not isinstance(return_particles, (bool, np.bool_)):
+        raise ValueError(f"{who}: return_particles: expected a bool, got {return_particles!r}")
+    N, B = int(N), int(B)
+    if G * R * steps * N * D >= 2 ** 31:
+        raise ValueError(f"{who}: G * R * steps * N * D = {G * R * steps * N * D} must stay below 2^31")
+    if G * R * B >= 2 ** 31:
+        raise ValueError(f"{who}: G * R * B = {G * R * B} must stay below 2^31")
+    return N, B, (PARTICLE_RULES.index(rule), PARTICLE_STAGES.index(stage)), (N, seed, mode)
+
+
+def _seeded_call(r, G, D, N, B, return_particles, stage, adapted):
+    """Output arrays and the trailing arguments (lengths, B, trajectories .. trans_var, m_smooth .. w_smooth) of the two seeded entry
+    points: the arrays of `_smooth_call` or `_backsim_call` by the stage, NULL for what the (rule, stage) does not produce."""
+    import ctypes
+    R, steps, dp, ip = r["R"], r["steps"], _lib.dptr, ctypes.POINTER(ctypes.c_int)
+    sm, stacks = {}, ()
+    if stage == "smooth":
+        sm = dict(m_smooth=np.empty((G, R, steps, D)), S_smooth=np.empty((G, R, steps, D, D)), ess_smooth=np.empty((G, R, steps)))
+        stacks = SMOOTH_PARTICLE_STACKS
+    elif stage == "backsim":
+        sm = dict(trajectories=np.empty((G, R, B, steps, D)), traj_index=np.empty((G, R, steps, B), dtype=np.int32),
+                  m_traj=np.empty((G, R, steps, D)), S_traj=np.empty((G, R, steps, D, D)), lag_cov=np.empty((G, R, steps, D, D)))
+        stacks = BACKSIM_STACKS
+    if return_particles:
+        sm.update({k: np.empty((G, R, steps, N) + ((D,) if k.startswith("trans_") else ())) for k in stacks if not (adapted and k == "weights")})
+    lengths = None
+    if stage != "filter":
+        sm["_lengths"] = np.ascontiguousarray(r["lengths"], dtype=np.int32)                 # (kept alive with the outputs)
+        lengths = sm["_lengths"].ctypes.data_as(ip)
+    g = lambda k: dp(sm[k]) if k in sm else None
+    args = (lengths, B, g("trajectories"), sm["traj_index"].ctypes.data_as(ip) if "traj_index" in sm else None) + \
+        tuple(g(k) for k in ("m_traj", "S_traj", "lag_cov", "weights", "trans_mean", "trans_var", "m_smooth", "S_smooth", "ess_smooth", "w_smooth"))
+    return sm, args
+
+
+def particle_records_seeded(Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_records, Y_records, Qs, CC, DD, log_Rchols, *, seed,
+                            num_particles=256, rule="bootstrap", stage="filter", noise="shared", num_trajectories=0, lengths=None,
+                            S0s=None, q_mode="reference", Y_train_std=1.0, records_per_pass=0, return_particles=False):
+    """The six particle calls of many records with SEEDED draws generated on the device (`ffvd_particle_seeded_records_grouped`): no
+    draw is generated, checked or uploaded by the host, so the cost of a call is what runs on the device and noise="independent" is
+    bounded by the library's index limit (G * R * steps * N * D < 2^31) alone.  rule "bootstrap" / "adapted" and stage "filter" /
+    "smooth" / "backsim" select the sibling -- `filter_particle_records_grouped`, `smooth_particle_records_grouped`,
+    `backsim_particle_records_grouped`, `filter_adapted_records_grouped`, `smooth_adapted_records_grouped`,
+    `backsim_adapted_records_grouped` -- whose positional operands (without eps, unif and unif_bs), other keywords, checks and
+    returned dict these are.  seed: an integer in [0, 2^64); noise: "shared" (one set of draws for every track: common random
+    numbers), "per_record" (one per record, shared by the groups) or "independent" (one per (group, record)); num_particles: N;
+    num_trajectories: B, with stage="backsim" only; the start draws xi0 are generated exactly when S0s is given.
+    The draws are Philox4x32-10 blocks addressed by (seed, stream, group, record, element) (`particle_draws` returns them): the call
+    equals its sibling on `particle_draws(seed, noise, G, R, steps, N, D, ..)` bit for bit in every key, and a track's arrays do not
+    depend on the other groups, the other records or records_per_pass ("Device draws")."""
+    who = "particle_records_seeded"
+    shape = np.shape(Y_records)
+    if len(shape) != 3 or shape[0] < 1 or shape[1] < 1:
+        raise ValueError(f"{who}: Y_records: expected (R, steps, J) with at least one record and one row, got {shape}")
+    G = len(U_vals)
+    if x0s is None:
+        raise ValueError(f"{who}: x0s: the start means are needed, ({shape[0]}, D) or ({G}, {shape[0]}, D)")
+    xl, ci = _records_placeholders(G, Zs, kerns, shape[1])
+    a = _pack_moment_groups(who, Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, xl, ci, 0, shape[1], Qs, None, q_mode)
+    D, args = a["D"], a["args"]
+    r = _pack_records(who, G, D, args[16], x0s, control_records, Y_records, lengths, S0s, records_per_pass)
+    R, steps = r["R"], r["steps"]
+    N, B, head, pargs = _pack_seeded(who, G, R, steps, D, num_particles, rule, stage, seed, noise, num_trajectories, return_particles)
+    m = _pack_summary(who, D, R * steps, CC, DD, log_Rchols, r["Y"].reshape(R * steps, r["J"]))
+    out, extra, oargs = _particle_call(m, G, R, steps, D, N, bool(return_particles))
+    sm, sargs = _seeded_call(r, G, D, N, B, bool(return_particles), stage, rule == "adapted")
+    dp = _lib.dptr
+    opt = lambda x: None if x is None else dp(x)
+    rc = _lib.load().ffvd_particle_seeded_records_grouped(*head, *args[:13], R, dp(r["x0"]), opt(r["S0"]), opt(r["ctrl"]), *args[16:], dp(m["CC"]),
+                                                          dp(m["DD"]), dp(m["sd"]), m["J"], dp(m["Y"]), r["rpp"], *pargs, *oargs, *sargs)
+    _lib.check(rc, None, who)
+    return _smooth_dict(_particle_dict(r, G, out, extra, Y_train_std), r, sm)
+
+
+def posterior_particle_records_seeded(Zs, kerns, Xs, Qs, control_inputs, control_records, Y_records, CC, DD, log_Rchols, *, seed,
+                                      num_particles=256, rule="bootstrap", stage="filter", noise="shared", num_trajectories=0,
+                                      lengths=None, x0s=None, S0s=None, q_mode="reference", Y_train_std=1.0, jitter=JITTER,
+                                      groups_per_pass=0, records_per_pass=0, return_particles=False):
+    """The collapsed posterior of G groups and `particle_records_seeded` in ONE call
+    (`ffvd_posterior_particle_seeded_records_grouped`): neither the posteriors nor the draws ever exist on the host.  The model and
+    start arguments are `posterior_filter_particle_records_grouped`'s (x0s None: every record of group g starts at Xs[g][-1]); seed,
+    num_particles, rule, stage, noise, num_trajectories and the returned dict are `particle_records_seeded`'s; the call equals the
+    posterior sibling of its (rule, stage) on `particle_draws(..)` bit for bit."""
+    who = "posterior_particle_records_seeded"
+    a = _pack_posterior_moment(who, Zs, kerns, Xs, Qs, control_inputs, 0, 0, None, q_mode, jitter, groups_per_pass)
+    G, D, args = a["G"], a["D"], a["args"]
+    r = _pack_records(who, G, D, args[11], x0s, control_records, Y_records, lengths, S0s, records_per_pass)
+    R, steps = r["R"], r["steps"]
+    N, B, head, pargs = _pack_seeded(who, G, R, steps, D, num_particles, rule, stage, seed, noise, num_trajectories, return_particles)
+    m = _pack_summary(who, D, R * steps, CC, DD, log_Rchols, r["Y"].reshape(R * steps, r["J"]))
+    out, extra, oargs = _particle_call(m, G, R, steps, D, N, bool(return_particles))
+    sm, sargs = _seeded_call(r, G, D, N, B, bool(return_particles), stage, rule == "adapted")
+    dp = _lib.dptr
+    opt = lambda x: None if x is None else dp(x)
+    rc = _lib.load().ffvd_posterior_particle_seeded_records_grouped(*head, *args[:17], R, opt(r["x0"]), opt(r["S0"]), opt(r["ctrl"]), steps,
+                                                                    dp(m["CC"]), dp(m["DD"]), dp(m["sd"]), m["J"], dp(m["Y"]), r["rpp"], *pargs,
+                                                                    *oargs, *sargs, None)
+    _lib.check(rc, None, who)
+    return _smooth_dict(_particle_dict(r, G, out, extra, Y_train_std), r, sm)
+
+
 def _pack_forecast(who, n, horizon, origins=None, stride=1, model=None):
     """Horizon and forecast origins of a record of n rows, checked (before the library is loaded): 1 <= horizon <= n - 1; origins
     None: range(0, n - horizon, stride) with stride >= 1, else strictly ascending integers in [0, n - 1 - horizon], so that every

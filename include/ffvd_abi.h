@@ -848,8 +848,8 @@ int  ffvd_op_posterior_filter_cubature_records_grouped(int kind, int G, int n_mo
 
 /* Bootstrap particle filtering of R observed records in one call: the tracks, passes, timing (the state after step i emits row i of
  * Y_obs), emission, NaN = unobserved convention, staging and q_mode of ffvd_op_filter_records_grouped with N particles per track in
- * place of one Gaussian.  Every random draw is the caller's (no device RNG): eps (standard normal, steps x N x D per track), unif
- * (in [0, 1), steps per track) and xi0 (standard normal, N x D per track; needed exactly when S0s is given) are read through a group
+ * place of one Gaussian.  Every random draw is the caller's (ffvd_particle_seeded_records_grouped generates them on the device from
+ * a seed instead): eps (standard normal, steps x N x D per track), unif (in [0, 1), steps per track) and xi0 (standard normal, N x D per track; needed exactly when S0s is given) are read through a group
  * and a record stride in doubles, each 0 (shared: common random numbers) or the stride of a contiguous [G or 1][R or 1][...] array.
  * Per track:
  *   start      X_0i = x_last + L0 xi0_i, L0 the lower Cholesky factor of S0 without pivoting (a pivot <= 0 gives a zero column);
@@ -1182,6 +1182,63 @@ int  ffvd_posterior_particle_adapted_backsim_records_grouped(int kind, int G, in
                                                              long long unif_bs_stride_r, double *trajectories, int *traj_index,
                                                              double *m_traj, double *S_traj, double *lag_cov, double *trans_mean,
                                                              double *trans_var, double *U_means);
+
+/* Seeded draws generated on the device (Philox4x32-10, Salmon et al. 2011): the draws of every particle call above as a pure function
+ * of (seed, stream, group, record, element).  noise: 0 shared (one block for every track), 1 per record (one per record, shared by
+ * the groups), 2 independent (one per (group, record)).  A block of a stream is laid out as the calls above read it -- eps
+ * [steps][N][D], unif [steps], xi0 [N][D], unif_bs [steps][B] -- and is generated in pairs of consecutive elements: pair p of the
+ * block of (g, r) is the Philox block of counter (p, g, r, stream) under the key (seed & 0xffffffff, seed >> 32), with g and r 0
+ * where the mode shares the axis and stream 0 eps, 1 unif, 2 xi0, 3 unif_bs.  From its words w0..w3, k1 = (w0 >> 5) 2^26 + (w1 >> 6)
+ * and k2 = (w2 >> 5) 2^26 + (w3 >> 6); the uniform streams hold k1 2^-53 and k2 2^-53 (exact, in [0, 1)); the normal streams hold
+ * rho cos(2 pi u2) and rho sin(2 pi u2) with u1 = (k1 + 1) 2^-53, u2 = k2 2^-53, rho = sqrt(-2 ln u1) (finite, |z| < 8.58); the second
+ * element of the last pair of an odd block is dropped.  So a block does not depend on G, R or steps (a shorter call's draws are a
+ * prefix of a longer one's), nor on records_per_pass.
+ *
+ * ffvd_particle_draws returns the arrays a seeded call uses, generated on the device and downloaded; each output may be NULL.  Shapes:
+ * lead x block with lead = (), (R) or (G x R) for noise 0, 1, 2.  B may be 0 when unif_bs is NULL.  Limits: those of
+ * ffvd_op_filter_particle_records_grouped (2 <= N <= 2048, 1 <= D <= 8, G * R * steps * N * D < 2^31), 0 <= B <= 4096,
+ * G * R * B < 2^31.  G = 0, R = 0 or steps = 0: FFVD_OK, nothing is touched. */
+int  ffvd_particle_draws(unsigned long long seed, int noise, int G, int R, int steps, int N, int D, int B, double *eps, double *unif,
+                         double *xi0, double *unif_bs);
+
+/* The six particle calls of many records with seeded draws: rule 0 bootstrap / 1 fully adapted, stage 0 filter / 1 marginal smoother /
+ * 2 backward simulation, then the arguments of ffvd_particle_backsim_records_grouped with `seed, noise` in place of the nine draw
+ * arguments eps .. xi0_stride_r, without unif_bs and its strides, and with the smoother's m_smooth, S_smooth, ess_smooth, w_smooth
+ * added at the end.  The draws never exist on the host: one launch per stream fills the device buffers the calls above upload into,
+ * and nothing is scanned.  CONTRACT: every output is, bit for bit, that of the existing entry point of the (rule, stage) called with
+ * the arrays of ffvd_particle_draws(seed, noise, ..) and the strides of the mode ((0, 0), (0, block) or (R block, block)).  Outputs
+ * the (rule, stage) does not produce must be NULL -- at stage 0 lengths, trajectories .. w_smooth; at stage 1 trajectories .. lag_cov;
+ * at stage 2 m_smooth .. w_smooth; under rule 1 weights -- else FFVD_EINVAL with a message that names them; B is read at stage 2
+ * only.  A bad rule, stage or noise is FFVD_EINVAL.  Limits and the zero sizes: those of the entry point selected. */
+int  ffvd_particle_seeded_records_grouped(int rule, int stage, int kind, int G, int n_models, const double *const *Lm_inverse_seqs,
+                                          const double *Zs, int M, int P, int D, const double *logvariances,
+                                          const double *loglengthscales, const double *fs, const double *const *q_sqrts, int q_mode,
+                                          int R, const double *x_lasts, const double *S0s, const double *ctrl, int C, int steps,
+                                          const double *log_Qs, const double *CC, const double *DD, const double *noise_std, int J,
+                                          const double *Y_obs, int records_per_pass, int N, unsigned long long seed, int noise,
+                                          double *m_pred, double *S_pred, double *m_filt, double *S_filt, double *lpd,
+                                          double *lpd_joint, double *y_mean, double *y_var_total, double *lpd_mix, double *lpd_gauss,
+                                          double *ess, double *log_evidence, double *particles, int *ancestors, const int *lengths,
+                                          int B, double *trajectories, int *traj_index, double *m_traj, double *S_traj,
+                                          double *lag_cov, double *weights, double *trans_mean, double *trans_var, double *m_smooth,
+                                          double *S_smooth, double *ess_smooth, double *w_smooth);
+
+/* ffvd_op_posterior_grouped followed by ffvd_particle_seeded_records_grouped WITHOUT the posteriors leaving the device: rule, stage,
+ * the arguments of ffvd_posterior_particle_backsim_records_grouped changed as above; U_means stays last. */
+int  ffvd_posterior_particle_seeded_records_grouped(int rule, int stage, int kind, int G, int n_models, const double *Zs, int M, int P,
+                                                    int D, const double *logvariances, const double *loglengthscales,
+                                                    const double *Xs, const double *ctrl_fit, int C, int T, const double *log_Qs,
+                                                    double jitter, int groups_per_pass, int q_mode, int R, const double *x0s,
+                                                    const double *S0s, const double *ctrl_roll, int steps, const double *CC,
+                                                    const double *DD, const double *noise_std, int J, const double *Y_obs,
+                                                    int records_per_pass, int N, unsigned long long seed, int noise, double *m_pred,
+                                                    double *S_pred, double *m_filt, double *S_filt, double *lpd, double *lpd_joint,
+                                                    double *y_mean, double *y_var_total, double *lpd_mix, double *lpd_gauss,
+                                                    double *ess, double *log_evidence, double *particles, int *ancestors,
+                                                    const int *lengths, int B, double *trajectories, int *traj_index, double *m_traj,
+                                                    double *S_traj, double *lag_cov, double *weights, double *trans_mean,
+                                                    double *trans_var, double *m_smooth, double *S_smooth, double *ess_smooth,
+                                                    double *w_smooth, double *U_means);
 
 /* Rolling-origin multi-step forecasts in one call: ffvd_op_filter_grouped (same arguments, same outputs, each of which may be NULL),
  * then from every origin o = origins[b] (n_origins rows of the record, strictly ascending, 0 <= o <= steps - 1 - horizon) `horizon`
