@@ -247,6 +247,26 @@ _SIGNATURES = {
                                                                 _PARTICLE_SEED + [_dp] * 13 +
                                                                 [C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, _dp, C.POINTER(C.c_int)] +
                                                                 [_dp] * 10 + [_dp]),
+    # the two particle filter calls with adaptive resampling: ess_threshold behind the draws, weights and resampled behind ancestors
+    # (U_means stays last); the seeded two with N, seed, noise in place of the draws
+    "ffvd_particle_adaptive_records_grouped": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), _dp, C.c_int, C.c_int, C.c_int, _dp,
+                                                         _dp, _dp, C.POINTER(C.c_void_p), C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, C.c_int,
+                                                         _dp, _dp, _dp, _dp, C.c_int, _dp, C.c_int] + _PARTICLE_DRAWS + [C.c_double] +
+                                                        [_dp] * 13 + [C.POINTER(C.c_int), _dp, C.POINTER(C.c_int)]),
+    "ffvd_posterior_particle_adaptive_records_grouped": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp,
+                                                                   _dp, C.c_int, C.c_int, _dp, C.c_double, C.c_int, C.c_int, C.c_int, _dp,
+                                                                   _dp, _dp, C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_int] +
+                                                                  _PARTICLE_DRAWS + [C.c_double] + [_dp] * 13 +
+                                                                  [C.POINTER(C.c_int), _dp, C.POINTER(C.c_int), _dp]),
+    "ffvd_particle_adaptive_seeded_records_grouped": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), _dp, C.c_int, C.c_int,
+                                                                C.c_int, _dp, _dp, _dp, C.POINTER(C.c_void_p), C.c_int, C.c_int, _dp, _dp, _dp,
+                                                                C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, _dp, C.c_int] + _PARTICLE_SEED +
+                                                               [C.c_double] + [_dp] * 13 + [C.POINTER(C.c_int), _dp, C.POINTER(C.c_int)]),
+    "ffvd_posterior_particle_adaptive_seeded_records_grouped": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp,
+                                                                          _dp, _dp, C.c_int, C.c_int, _dp, C.c_double, C.c_int, C.c_int,
+                                                                          C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp, C.c_int, _dp,
+                                                                          C.c_int] + _PARTICLE_SEED + [C.c_double] + [_dp] * 13 +
+                                                                         [C.POINTER(C.c_int), _dp, C.POINTER(C.c_int), _dp]),
     "ffvd_particle_draws": (C.c_int, [C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp]),
     "ffvd_op_forecast_grouped": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp,
                                            C.POINTER(C.c_void_p), C.c_int, _dp, _dp, _dp, C.c_int, C.c_int, _dp,

@@ -217,6 +217,21 @@ struct MomentParticleAdaptedArgs {
 void launch_mg_parec_step(hipStream_t stream, const MomentGroupArgs &a, const MomentFilterArgs &f, const MomentRecordArgs &rc,
                           const MomentLinearFanArgs &l, const MomentParticleArgs &p, const MomentParticleAdaptedArgs &q, int t);
 
+// Particle filtering of many records with adaptive resampling (moment_particle_adaptive.hip; DESIGN.md section 9, "Adaptive
+// resampling"): the tracks, passes, stacks, draws and limits of the bootstrap particle filter above carrying a weighted set, which is
+// resampled only on the rows whose effective sample size falls below ess_threshold * N (unif of the other rows is not read).  Its
+// weight kernel replaces the bootstrap one; the rows kernel and the product kernel run unchanged.  MomentParticleArgs::particles is
+// the X^- and (particles[t], weights[t]) the filtering approximation after row t.
+struct MomentParticleEssArgs {
+    double *logw;                    // [tracks][N]: the carried log-weights, largest entry 0 (written by the launch at t = 0)
+    double ess_threshold;            // finite, >= 0
+    double *weights;                 // [G][R][steps][N]: the normalised weights after the row, or nullptr
+    int *resampled;                  // [G][R][steps]: 1 where the row resampled
+};
+// launch t of steps + 1: the adaptive weight kernel, then (t < steps) the rows kernel and the product kernel
+void launch_mg_pess_step(hipStream_t stream, const MomentGroupArgs &a, const MomentFilterArgs &f, const MomentRecordArgs &rc,
+                         const MomentLinearFanArgs &l, const MomentParticleArgs &p, const MomentParticleEssArgs &q, int t);
+
 // Particle smoothing of many records (moment_particle_smooth.hip; DESIGN.md section 9, "Particle smoothing"): the marginal
 // forward-filter / backward-smoother on the sets the particle filter above carries.  The driver keeps the filter's device stacks
 // `particles` and `ancestors`, launches the keep kernel after the product launch of every step (trans_mean, trans_var: the two

@@ -623,7 +623,7 @@ bool mg_scalars_ok(int kind, int G, int n_models, int M, int P, int D, int C, in
            (steps == 0 || G <= ((1LL << 31) - 1) / steps / D / D);
 }
 // the propagation rule of the filter's launches (mg_run)
-enum { MG_METHOD_MOMENT = 0, MG_METHOD_LINEAR = 1, MG_METHOD_CUBATURE = 2, MG_METHOD_PARTICLE = 3, MG_METHOD_ADAPTED = 4 };    // (cubature and particle: the records calls and the forecasts; adapted: the records calls)
+enum { MG_METHOD_MOMENT = 0, MG_METHOD_LINEAR = 1, MG_METHOD_CUBATURE = 2, MG_METHOD_PARTICLE = 3, MG_METHOD_ADAPTED = 4, MG_METHOD_ADAPTIVE = 5 };    // (cubature and particle: the records calls and the forecasts; adapted, adaptive: the records calls)
 // the trailing summary block of the entry points: asked for when anything in it is given
 bool mg_summary_wanted(const SummaryReq &q) {
     return q.CC || q.DD || q.noise_std || q.J != 0 || q.Y_test || q.n_test != 0 || q.y_mean || q.y_var || q.y_var_total || q.lpd || q.lpd_gauss;
@@ -1120,8 +1120,11 @@ const char *const mg_precords_se_only =
     " (the particle filter of many records is built for the SE kernel only: its kernel rows are SE-ARD's)";
 const char *const mg_arecords_se_only =
     " (the adapted particle filter of many records is built for the SE kernel only: its kernel rows are SE-ARD's)";
-// the two rules that take a ParticleReq: the bootstrap filter and the fully adapted one (moment_particle_adapted.hip)
-bool mg_particle_rule(int method) { return method == MG_METHOD_PARTICLE || method == MG_METHOD_ADAPTED; }
+const char *const mg_erecords_se_only =
+    " (the adaptive particle filter of many records is built for the SE kernel only: its kernel rows are SE-ARD's)";
+// the three rules that take a ParticleReq: the bootstrap filter, the fully adapted one (moment_particle_adapted.hip) and the bootstrap
+// filter with adaptive resampling (moment_particle_adaptive.hip)
+bool mg_particle_rule(int method) { return method == MG_METHOD_PARTICLE || method == MG_METHOD_ADAPTED || method == MG_METHOD_ADAPTIVE; }
 // The particle request beside a RecordsReq (MG_METHOD_PARTICLE): N particles per track, the caller's draws with their (group, record)
 // strides in doubles -- each 0 or the stride of a contiguous array -- and the outputs the Gaussian rules do not have
 struct ParticleReq {
@@ -1139,6 +1142,10 @@ struct ParticleReq {
     // `seed` through the same strides (moment_particle_draws.hip); there is nothing on the host to check or to upload
     bool seeded = false;
     unsigned long long seed = 0;
+    // MG_METHOD_ADAPTIVE: the rows whose ess falls below ess_threshold * N resample (finite, >= 0); the two outputs it adds
+    double ess_threshold = 0.0;
+    double *weights = nullptr;                   // [G][R][steps][N] or NULL
+    int *resampled = nullptr;                    // [G][R][steps] or NULL
 };
 // The backward-simulation request beside a ParticleSmoothReq (moment_particle_backsim.hip): B trajectories per track from the
 // caller's uniforms; with it the smoother's recursion is not run (its m_smooth .. w_smooth stay NULL)
@@ -1226,11 +1233,13 @@ void lpd_mix_over_groups(const double *lpd, int G, size_t n, double *out) {
     }
 }
 
-// The tail of a particle call: the pooled summary of the predicted stacks on the device (y_mean, y_var_total, lpd_gauss), the downloads,
+// The tail of a particle call: the pooled summary of the predicted stacks on the device (y_mean, y_var_total, lpd_gauss), the downloads
+// (ea: the adaptive rule's stacks, whose `weights` and `resampled` come down with them),
 // and on the host, from the stacks that came down: lpd_mix (lpd_mix_over_groups) and log_evidence = the sum of lpd_joint over the
 // rows that have an observation, in ascending order
 int mg_particle_finish(Scratch &sc, const std::string &who, int G, int R, int steps, int D, const double *dm, const double *dS, double *m_x,
-                       double *S_x, const MomentFilterArgs &fa, const MomentParticleArgs &pa, const FilterReq &flt, const ParticleReq &pq) {
+                       double *S_x, const MomentFilterArgs &fa, const MomentParticleArgs &pa, const FilterReq &flt, const ParticleReq &pq,
+                       const MomentParticleEssArgs *ea = nullptr) {
     const int J = flt.J;
     const size_t V = (size_t)G * R, nm_x = V * steps * D, nS_x = nm_x * D, nlpd = V * steps * J, nlj = V * steps, RS = (size_t)R * steps;
     SummaryReq fsum = flt.pooled(R * steps);
@@ -1245,7 +1254,8 @@ int mg_particle_finish(Scratch &sc, const std::string &who, int G, int R, int st
     if (!down(flt.m_filt, fa.m_filt, nm_x * sizeof(double)) || !down(flt.S_filt, fa.S_filt, nS_x * sizeof(double)) ||
         !down(lpd, fa.lpd, nlpd * sizeof(double)) || !down(lj, fa.lpd_joint, nlj * sizeof(double)) || !down(m_x, dm, nm_x * sizeof(double)) ||
         !down(S_x, dS, nS_x * sizeof(double)) || !down(pq.ess, pa.ess, nlj * sizeof(double)) ||
-        !down(pq.particles, pa.particles, nm_x * pq.N * sizeof(double)) || !down(pq.ancestors, pa.ancestors, nlj * pq.N * sizeof(int)))
+        !down(pq.particles, pa.particles, nm_x * pq.N * sizeof(double)) || !down(pq.ancestors, pa.ancestors, nlj * pq.N * sizeof(int)) ||
+        (ea && (!down(pq.weights, ea->weights, nlj * pq.N * sizeof(double)) || !down(pq.resampled, ea->resampled, nlj * sizeof(int)))))
         return set_error(nullptr, FFVD_EDEVICE, who + ": copying the results back failed");
     OP_TRY(hipStreamSynchronize(sc.stream));
     if (flt.lpd_mix) lpd_mix_over_groups(lpd, G, RS * J, flt.lpd_mix);
@@ -1280,6 +1290,9 @@ int mg_records_run(Scratch &sc, const std::string &who, int method, int G, int n
     const int V = G * R;                                                               // tracks of the call (V * steps * D * D < 2^31)
     const size_t nm_x = (size_t)V * steps * D, nS_x = nm_x * D, nlpd = (size_t)V * steps * J, nlj = (size_t)V * steps;
     const bool cub = method == MG_METHOD_CUBATURE, par = mg_particle_rule(method), ada = method == MG_METHOD_ADAPTED;
+    const bool esr = method == MG_METHOD_ADAPTIVE;
+    if (esr && sq)                                                                     // (the smoothers assume equally weighted carried sets)
+        return set_error(nullptr, FFVD_EINVAL, who + ": bad argument (smoothing and backward simulation are not built on the adaptive rule's weighted sets)");
     const int nrow = cub ? mg_crec_rows(D) : par ? pq->N : 1;                          // rows of K per track
     if (par)
         if (int rc = particle_fits(who, G, nm, D, Mp, upg, pq->N)) return rc;
@@ -1347,6 +1360,14 @@ int mg_records_run(Scratch &sc, const std::string &who, int method, int G, int n
         pd.mu = sc.alloc<double>((size_t)G * Rp * pq->N * D); pd.sv = sc.alloc<double>((size_t)G * Rp * pq->N * D);
         OP_CHECK(pd.mu && pd.sv, who);
     }
+    MomentParticleEssArgs pe{};
+    if (esr) {                                                                         // the carried log-weights of a pass; the two stacks
+        pe.ess_threshold = pq->ess_threshold;
+        pe.logw = sc.alloc<double>((size_t)G * Rp * pq->N);
+        pe.weights = pq->weights ? sc.alloc<double>(nlj * pq->N) : nullptr;
+        pe.resampled = sc.alloc<int>(nlj);
+        OP_CHECK(pe.logw && (!pq->weights || pe.weights) && pe.resampled, who);
+    }
     MomentParticleSmoothArgs ps{};
     MomentParticleBacksimArgs pb{};
     const ParticleBacksimReq *bq = par && sq ? sq->bs : nullptr;
@@ -1402,7 +1423,8 @@ int mg_records_run(Scratch &sc, const std::string &who, int method, int G, int n
             else if (ada) {
                 launch_mg_parec_step(sc.stream, a, fa, ra, lf, pa, pd, t);
                 if (sq && t < steps) launch_mg_psm_keep(sc.stream, a, ra, lf, pa, ps, t);   // the same launch: (mu, s) of the set carried into row t
-            } else if (par) {
+            } else if (esr) launch_mg_pess_step(sc.stream, a, fa, ra, lf, pa, pe, t);
+            else if (par) {
                 launch_mg_prec_step(sc.stream, a, fa, ra, lf, pa, t);
                 if (sq && t < steps) launch_mg_psm_keep(sc.stream, a, ra, lf, pa, ps, t);   // (mu, s) of step t, before the next weight launch
             } else launch_mg_lrec_step(sc.stream, a, fa, ra, lf, t);
@@ -1432,7 +1454,7 @@ int mg_records_run(Scratch &sc, const std::string &who, int method, int G, int n
             !down(sq->trans_mean, ps.trans_mean, nm_x * N) || !down(sq->trans_var, ps.trans_var, nm_x * N))
             return set_error(nullptr, FFVD_EDEVICE, who + ": copying the results back failed");
     }
-    if (par) return mg_particle_finish(sc, who, G, R, steps, D, dm, dS, m_x, S_x, fa, pa, flt, *pq);
+    if (par) return mg_particle_finish(sc, who, G, R, steps, D, dm, dS, m_x, S_x, fa, pa, flt, *pq, esr ? &pe : nullptr);
     // the pooled one-step summary per record and row: the predicted stacks as [G][R * steps] against Y as [R * steps][J]
     const SummaryReq fsum = flt.pooled(R * steps);
     if (fsum.y_mean || fsum.y_var_total || fsum.lpd || fsum.lpd_gauss)
@@ -1575,7 +1597,8 @@ int records_checks(const std::string &who, int method, int kind, int G, int n_mo
     nothing = false;
     if (kind != FFVD_KERNEL_SE)
         return set_error(nullptr, FFVD_EINVAL, bad + (method == MG_METHOD_CUBATURE ? mg_crecords_se_only : method == MG_METHOD_PARTICLE
-                                                      ? mg_precords_se_only : method == MG_METHOD_ADAPTED ? mg_arecords_se_only : mg_records_se_only));
+                                                      ? mg_precords_se_only : method == MG_METHOD_ADAPTED ? mg_arecords_se_only
+                                                      : method == MG_METHOD_ADAPTIVE ? mg_erecords_se_only : mg_records_se_only));
     if (!mg_scalars_ok(kind, G, n_models, M, P, D, C, steps, q_mode) || !filter_scalars_ok(f)) return set_error(nullptr, FFVD_EINVAL, bad);
     if (!records_scalars_ok(rq, G, steps, D))
         return set_error(nullptr, FFVD_EINVAL, bad + " (R >= 0, records_per_pass >= 0, G * R * steps * D * D < 2^31 and G * R * D < 2^31 are needed)");
@@ -1583,6 +1606,8 @@ int records_checks(const std::string &who, int method, int kind, int G, int n_mo
     if (mg_particle_rule(method) && (!pq || !particle_ok(*pq, G, rq.R, steps, D, with_S0, nothing)))
         return set_error(nullptr, FFVD_EINVAL, bad + " (2 <= N <= 2048, finite draws, unif in [0, 1), xi0 with S0s, strides 0 or contiguous and "
                                                "G * R * steps * N * D < 2^31 are needed)");
+    if (method == MG_METHOD_ADAPTIVE && !(std::isfinite(pq->ess_threshold) && pq->ess_threshold >= 0.0))
+        return set_error(nullptr, FFVD_EINVAL, bad + " (ess_threshold must be finite and >= 0)");
     return FFVD_OK;
 }
 
@@ -1608,7 +1633,7 @@ int records_given(const std::string &who, int method, int kind, int G, int n_mod
         return set_error(nullptr, FFVD_EINVAL, bad + " (1 <= B <= 4096, unif_bs in [0, 1), strides 0 or contiguous and G * R * B < 2^31 are needed)");
     if (nothing) return FFVD_OK;
     if (!Lm_inverse_seqs || !Zs || !logvariances || !loglengthscales || !fs || !x_lasts || !log_Qs || (C > 0 && !ctrl) ||
-        !filter_arrays_ok(f, R * steps, m_pred, S_pred, pq && (pq->ess || pq->log_evidence || pq->particles || pq->ancestors || (sq && sq->any_output()))))
+        !filter_arrays_ok(f, R * steps, m_pred, S_pred, pq && (pq->ess || pq->log_evidence || pq->particles || pq->ancestors || pq->weights || pq->resampled || (sq && sq->any_output()))))
         return set_error(nullptr, FFVD_EINVAL, bad);
     const size_t nK = (size_t)n_models * D, GD = (size_t)G * D, VD = GD * R, nq = given_nq(q_sqrts, q_mode, G, D);
     if (!given_tables_ok(Lm_inverse_seqs, nK, q_sqrts, nq)) return set_error(nullptr, FFVD_EINVAL, bad);
@@ -1648,7 +1673,7 @@ int records_posterior(const std::string &who, int method, int kind, int G, int n
     if (!pg_scalars_ok(kind, G, n_models, M, P, D, C, T, groups_per_pass, jitter)) return set_error(nullptr, FFVD_EINVAL, bad);
     if (nothing) return FFVD_OK;
     if (!Zs || !logvariances || !loglengthscales || !Xs || !log_Qs || (C > 0 && (!ctrl_fit || !ctrl_roll)) ||
-        !filter_arrays_ok(f, R * steps, m_pred, S_pred, pq && (pq->ess || pq->log_evidence || pq->particles || pq->ancestors || (sq && sq->any_output()))))
+        !filter_arrays_ok(f, R * steps, m_pred, S_pred, pq && (pq->ess || pq->log_evidence || pq->particles || pq->ancestors || pq->weights || pq->resampled || (sq && sq->any_output()))))
         return set_error(nullptr, FFVD_EINVAL, bad);
     const PgIn in{who, kind, G, n_models, M, P, D, C, T, groups_per_pass, Zs, logvariances, loglengthscales, Xs, ctrl_fit, log_Qs, jitter};
     OP_BEGIN(who);
@@ -2071,6 +2096,81 @@ extern "C" int ffvd_posterior_particle_seeded_records_grouped(int rule, int stag
 }
 #undef FFVD_SEEDED_TAIL_PARAMS
 #undef FFVD_SEEDED_REQ
+
+// The two bootstrap particle filter calls with ADAPTIVE resampling (moment_particle_adaptive.hip; DESIGN.md section 9, "Adaptive
+// resampling"): the track carries a weighted set and resamples only on the rows whose ess falls below ess_threshold * N (finite,
+// >= 0: 0 never resamples, any value > 1 always does and returns the bootstrap calls' arrays bit for bit).  The argument lists are
+// the bootstrap calls' with ess_threshold behind the draws and with weights [G][R][steps][N] (or NULL) and resampled [G][R][steps]
+// (or NULL) behind ancestors; the seeded two take N, seed and noise where the others have N and the nine draw arguments.
+// (Not ffvd_op_*: see DESIGN.md section 9, "Particle smoothing".)
+#define FFVD_ADAPTIVE_GIVEN_HEAD                                                                                                             \
+    int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M, int P, int D, const double *logvariances, \
+        const double *loglengthscales, const double *fs, const double *const *q_sqrts, int q_mode, int R, const double *x_lasts,            \
+        const double *S0s, const double *ctrl, int C, int steps, const double *log_Qs, const double *CC, const double *DD,                  \
+        const double *noise_std, int J, const double *Y_obs, int records_per_pass
+#define FFVD_ADAPTIVE_POSTERIOR_HEAD                                                                                                         \
+    int kind, int G, int n_models, const double *Zs, int M, int P, int D, const double *logvariances, const double *loglengthscales,        \
+        const double *Xs, const double *ctrl_fit, int C, int T, const double *log_Qs, double jitter, int groups_per_pass, int q_mode,       \
+        int R, const double *x0s, const double *S0s, const double *ctrl_roll, int steps, const double *CC, const double *DD,                \
+        const double *noise_std, int J, const double *Y_obs, int records_per_pass
+#define FFVD_ADAPTIVE_DRAWS                                                                                                                  \
+    int N, const double *eps, long long eps_stride_g, long long eps_stride_r, const double *unif, long long unif_stride_g,                  \
+        long long unif_stride_r, const double *xi0, long long xi0_stride_g, long long xi0_stride_r
+#define FFVD_ADAPTIVE_TAIL                                                                                                                   \
+    double ess_threshold, double *m_pred, double *S_pred, double *m_filt, double *S_filt, double *lpd, double *lpd_joint, double *y_mean,   \
+        double *y_var_total, double *lpd_mix, double *lpd_gauss, double *ess, double *log_evidence, double *particles, int *ancestors,      \
+        double *weights, int *resampled
+#define FFVD_ADAPTIVE_REQ                                                                                                                    \
+    ParticleReq pq{N,   eps,          eps_stride_g, eps_stride_r, unif, unif_stride_g, unif_stride_r, xi0, xi0_stride_g, xi0_stride_r,      \
+                   ess, log_evidence, particles,    ancestors};                                                                              \
+    pq.ess_threshold = ess_threshold; pq.weights = weights; pq.resampled = resampled
+#define FFVD_ADAPTIVE_SEEDED_REQ                                                                                                             \
+    if (noise < MG_PDRAW_SHARED || noise > MG_PDRAW_INDEPENDENT)                                                                             \
+        return set_error(nullptr, FFVD_EINVAL, std::string(who) + ": bad argument (noise 0, 1 or 2 is needed)");                            \
+    ParticleReq pq{N, nullptr, 0, 0, nullptr, 0, 0, nullptr, 0, 0, ess, log_evidence, particles, ancestors};                                 \
+    pq.seeded = true; pq.seed = seed;                                                                                                        \
+    seeded_strides(noise, R, (long long)steps * N * D, pq.eps_g, pq.eps_r);                                                                  \
+    seeded_strides(noise, R, steps, pq.unif_g, pq.unif_r);                                                                                   \
+    seeded_strides(noise, R, (long long)N * D, pq.xi0_g, pq.xi0_r);                                                                          \
+    pq.ess_threshold = ess_threshold; pq.weights = weights; pq.resampled = resampled
+#define FFVD_ADAPTIVE_GIVEN_CALL(who)                                                                                                        \
+    records_given(who, MG_METHOD_ADAPTIVE, kind, G, n_models, Lm_inverse_seqs, Zs, M, P, D, logvariances, loglengthscales, fs, q_sqrts,     \
+                  q_mode, R, x_lasts, S0s, ctrl, C, steps, log_Qs, CC, DD, noise_std, J, Y_obs, records_per_pass, m_pred, S_pred, m_filt,   \
+                  S_filt, nullptr, lpd, lpd_joint, nullptr, nullptr, y_mean, y_var_total, lpd_mix, lpd_gauss, &pq)
+#define FFVD_ADAPTIVE_POSTERIOR_CALL(who)                                                                                                    \
+    records_posterior(who, MG_METHOD_ADAPTIVE, kind, G, n_models, Zs, M, P, D, logvariances, loglengthscales, Xs, ctrl_fit, C, T, log_Qs,   \
+                      jitter, groups_per_pass, q_mode, R, x0s, S0s, ctrl_roll, steps, CC, DD, noise_std, J, Y_obs, records_per_pass, m_pred, \
+                      S_pred, m_filt, S_filt, nullptr, lpd, lpd_joint, nullptr, nullptr, y_mean, y_var_total, lpd_mix, lpd_gauss, U_means,  \
+                      &pq)
+extern "C" int ffvd_particle_adaptive_records_grouped(FFVD_ADAPTIVE_GIVEN_HEAD, FFVD_ADAPTIVE_DRAWS, FFVD_ADAPTIVE_TAIL) {
+    FFVD_ADAPTIVE_REQ;
+    return FFVD_ADAPTIVE_GIVEN_CALL("ffvd_particle_adaptive_records_grouped");
+}
+extern "C" int ffvd_posterior_particle_adaptive_records_grouped(FFVD_ADAPTIVE_POSTERIOR_HEAD, FFVD_ADAPTIVE_DRAWS, FFVD_ADAPTIVE_TAIL,
+                                                                double *U_means) {
+    FFVD_ADAPTIVE_REQ;
+    return FFVD_ADAPTIVE_POSTERIOR_CALL("ffvd_posterior_particle_adaptive_records_grouped");
+}
+extern "C" int ffvd_particle_adaptive_seeded_records_grouped(FFVD_ADAPTIVE_GIVEN_HEAD, int N, unsigned long long seed, int noise,
+                                                             FFVD_ADAPTIVE_TAIL) {
+    const char *who = "ffvd_particle_adaptive_seeded_records_grouped";
+    FFVD_ADAPTIVE_SEEDED_REQ;
+    return FFVD_ADAPTIVE_GIVEN_CALL(who);
+}
+extern "C" int ffvd_posterior_particle_adaptive_seeded_records_grouped(FFVD_ADAPTIVE_POSTERIOR_HEAD, int N, unsigned long long seed, int noise,
+                                                                       FFVD_ADAPTIVE_TAIL, double *U_means) {
+    const char *who = "ffvd_posterior_particle_adaptive_seeded_records_grouped";
+    FFVD_ADAPTIVE_SEEDED_REQ;
+    return FFVD_ADAPTIVE_POSTERIOR_CALL(who);
+}
+#undef FFVD_ADAPTIVE_GIVEN_HEAD
+#undef FFVD_ADAPTIVE_POSTERIOR_HEAD
+#undef FFVD_ADAPTIVE_DRAWS
+#undef FFVD_ADAPTIVE_TAIL
+#undef FFVD_ADAPTIVE_REQ
+#undef FFVD_ADAPTIVE_SEEDED_REQ
+#undef FFVD_ADAPTIVE_GIVEN_CALL
+#undef FFVD_ADAPTIVE_POSTERIOR_CALL
 
 // The draws a seeded call uses, generated on the device and downloaded: eps lead + [steps][N][D], unif lead + [steps], xi0 lead + [N][D],
 // unif_bs lead + [steps][B], lead = (), (R,) or (G, R) for noise 0, 1 or 2.  Each output may be NULL; B may be 0 when unif_bs is.

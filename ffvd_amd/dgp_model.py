@@ -729,10 +729,44 @@ class DGPSSM:
                                         num_particles, lengths, x0, S0, q_mode, Y_train_std, records_per_pass, seed, noise, return_particles,
                                         int(B))
 
+    def filter_records_adaptive(self, Y_records, control_records=None, *, num_particles=256, ess_threshold=0.5, lengths=None, x0=None,
+                                S0=None, q_mode="reference", Y_train_std=1.0, records_per_pass=0, seed=None, noise="shared", draws="numpy",
+                                return_particles=False):
+        """`filter_records_particle` with ADAPTIVE resampling: every (chain, record) track carries a weighted set and resamples only
+        on the rows whose effective sample size falls below ess_threshold * num_particles -- the textbook form, for records whose rows
+        have few or uninformative outputs, where resampling at every row only adds variance.  ess_threshold: a finite number >= 0
+        (0 never resamples; above 1 always, which is `filter_records_particle` bit for bit).  draws="numpy": the draws of
+        `filter_records_particle` for the same seed (np.random.default_rng(seed), or the model's generator), with its `noise` modes and
+        its 1 GiB refusal; draws="device": generated on the device as in `particle_records_seeded`, which needs an integer seed in
+        [0, 2^64).  The checks, the start and the two forms (collapsed U: ONE `posterior_filter_adaptive_records_grouped` /
+        `posterior_adaptive_records_seeded` call; explicit U: `kernel_pre_cal` once, then `filter_adaptive_records_grouped` /
+        `adaptive_records_seeded`) are `filter_records`'; prediction.filter_adaptive_records_grouped has the method and the dict that
+        is returned: the bootstrap call's plus resampled (S, R, steps) and, with return_particles, weights (S, R, steps, N)."""
+        from . import prediction as pr
+        who = "filter_records_adaptive"
+        if not isinstance(draws, str) or draws not in ("numpy", "device"):
+            raise ValueError(f"{who}: draws: expected \"numpy\" or \"device\", got {draws!r}")
+        thr = pr._ess_threshold(who, ess_threshold)
+        if draws == "numpy":
+            return DGPSSM._records_particle(self, who, "filter_adaptive_records_grouped", Y_records, control_records, num_particles, lengths,
+                                            x0, S0, q_mode, Y_train_std, records_per_pass, seed, noise, return_particles,
+                                            extra=dict(ess_threshold=thr))
+        if not pr._is_int(seed):
+            raise ValueError(f"{who}: seed: draws=\"device\" needs an integer seed in [0, 2^64), got {seed!r}")
+        shape = np.shape(Y_records)
+        if len(shape) != 3 or shape[0] < 1 or shape[1] < 1:
+            raise ValueError(f"{who}: Y_records: expected (R, steps, {self.Y.shape[1]}), got {shape}")
+        pr._pack_seeded(who, self.num_chains, shape[0], shape[1], self.output_dim, num_particles, "bootstrap", "filter", seed, noise, 0,
+                        return_particles)
+        seeded = dict(num_particles=num_particles, ess_threshold=thr, seed=seed, noise=noise, return_particles=return_particles)
+        return DGPSSM._filter_records(self, who, "adaptive_records_seeded", Y_records, control_records, lengths, x0, S0, None, q_mode,
+                                      Y_train_std, records_per_pass, seeded=seeded)
+
     def _records_particle(self, who, fn, Y_records, control_records, num_particles, lengths, x0, S0, q_mode, Y_train_std, records_per_pass,
-                          seed, noise, return_particles, num_trajectories=None):
+                          seed, noise, return_particles, num_trajectories=None, extra=None):
         """The body of `filter_records_particle`, `smooth_records_particle` and `sample_records_particle`: the checks and the draws,
-        then `_filter_records`.  num_trajectories: the uniforms of the backward simulation are drawn after the filter's draws."""
+        then `_filter_records`.  num_trajectories: the uniforms of the backward simulation are drawn after the filter's draws.
+        extra: further keywords of the prediction-level function (`filter_records_adaptive`'s ess_threshold)."""
         if noise not in ("shared", "per_record", "independent"):
             raise ValueError(f"{who}: noise: expected \"shared\", \"per_record\" or \"independent\", got {noise!r}")
         N = num_particles
@@ -751,6 +785,8 @@ class DGPSSM:
                      xi0=None if S0 is None else rng.standard_normal(lead + (N, D)), return_particles=return_particles)
         if num_trajectories is not None:
             draws["unif_bs"] = rng.random(lead + (steps, num_trajectories))
+        if extra:
+            draws["extra"] = extra
         return DGPSSM._filter_records(self, who, fn, Y_records, control_records, lengths, x0, S0, None, q_mode,
                                       Y_train_std, records_per_pass, draws)
 
@@ -817,7 +853,7 @@ class DGPSSM:
         if draws is not None:                                     # the particle filter: eps and unif follow log_Rchols, no `smooth`
             del kw["smooth"]
             tail = (draws["eps"], draws["unif"]) + ((draws["unif_bs"],) if "unif_bs" in draws else ())
-            kw.update(xi0=draws["xi0"], return_particles=draws["return_particles"])
+            kw.update(xi0=draws["xi0"], return_particles=draws["return_particles"], **draws.get("extra", {}))
         if seeded is not None:                                    # the draws are the device's: nothing follows log_Rchols, no `smooth`
             del kw["smooth"]
             kw.update(seeded)

@@ -1022,7 +1022,8 @@ def filter_particle_records_grouped(Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts,
     row with nothing observed); W_i = exp(L_i - max L), m_filt / S_filt the W-weighted mean and centred covariance, ess =
     (sum W)^2 / sum W^2; systematic resampling with unif[t], a_i = min(#{k: cdf_k <= (unif[t] + i) / N cdf_{N-1}}, N - 1), only for
     a row with an observed entry (otherwise the particles are kept, m_filt = m_pred and S_filt = S_pred bit for bit, ess = N).  No
-    adaptive resampling.  There is no smoothing (no `smooth` parameter, no `cross`): particle smoothing is not built into
+    adaptive resampling in this call: `filter_adaptive_records_grouped` resamples only where the ESS falls below a threshold and
+    equals this call bit for bit with a threshold above 1.  There is no smoothing (no `smooth` parameter, no `cross`): particle smoothing is not built into
     this call, `smooth_particle_records_grouped` has it.
     Returns the dict of `filter_records_grouped` without cross, m_smooth and S_smooth, plus ess (G, R, steps) and log_evidence (G, R),
     the sum of lpd_joint over the rows with an observation: the SMC estimate of log p(y) of that record under that chain.  Pooled
@@ -1148,6 +1149,158 @@ def posterior_filter_adapted_records_grouped(Zs, kerns, Xs, Qs, control_inputs, 
     return _particle_records_posterior("posterior_filter_adapted_records_grouped", False, Zs, kerns, Xs, Qs, control_inputs, control_records,
                                        Y_records, CC, DD, log_Rchols, eps, unif, xi0, lengths, x0s, S0s, q_mode, Y_train_std, jitter,
                                        groups_per_pass, records_per_pass, return_particles, adapted=True)
+
+
+def _ess_threshold(who, ess_threshold):
+    """The check of an ESS threshold: a finite real number >= 0 (not a bool)."""
+    t = ess_threshold
+    if isinstance(t, (bool, np.bool_)) or not isinstance(t, (int, float, np.integer, np.floating)) or not np.isfinite(t) or t < 0:
+        raise ValueError(f"{who}: ess_threshold: expected a finite number >= 0 (0 never resamples, above 1 always), got {t!r}")
+    return float(t)
+
+
+def _adaptive_call(G, R, steps, N, return_particles):
+    """Output arrays and the trailing arguments (weights, resampled) of the four adaptive entry points."""
+    import ctypes
+    ad = dict(resampled=np.empty((G, R, steps), dtype=np.int32))
+    if return_particles:
+        ad["weights"] = np.empty((G, R, steps, N))
+    return ad, (_lib.dptr(ad["weights"]) if return_particles else None, ad["resampled"].ctypes.data_as(ctypes.POINTER(ctypes.c_int)))
+
+
+def _adaptive_dict(res, r, ad):
+    """`_particle_dict` plus resampled (-1 at and beyond a record's length) and, when asked for, weights (NaN there)."""
+    dead = ~r["live"]
+    ad["resampled"][:, dead] = -1
+    if "weights" in ad:
+        ad["weights"][:, dead] = np.nan
+    res.update(ad)
+    return res
+
+
+def _adaptive_draws(who, G, R, steps, D, eps, unif, xi0, with_S0, return_particles, seeded):
+    """N, the draw arguments and what must stay alive: `_pack_particles` on the caller's arrays, or (seeded = (seed, noise,
+    num_particles)) `_pack_seeded`'s N, seed, noise."""
+    if seeded is None:
+        return _pack_particles(who, G, R, steps, D, eps, unif, xi0, with_S0, return_particles)
+    seed, noise, num_particles = seeded
+    N, _, _, pargs = _pack_seeded(who, G, R, steps, D, num_particles, "bootstrap", "filter", seed, noise, 0, return_particles)
+    return N, pargs, None
+
+
+def _adaptive_records_given(who, Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_records, Y_records, Qs, CC, DD, log_Rchols, eps,
+                            unif, xi0, ess_threshold, lengths, S0s, q_mode, Y_train_std, records_per_pass, return_particles, seeded=None):
+    """The body of `filter_adaptive_records_grouped` and, with seeded = (seed, noise, num_particles), of `adaptive_records_seeded`."""
+    shape = np.shape(Y_records)
+    if len(shape) != 3 or shape[0] < 1 or shape[1] < 1:
+        raise ValueError(f"{who}: Y_records: expected (R, steps, J) with at least one record and one row, got {shape}")
+    G = len(U_vals)
+    if x0s is None:
+        raise ValueError(f"{who}: x0s: the start means are needed, ({shape[0]}, D) or ({G}, {shape[0]}, D)")
+    thr = _ess_threshold(who, ess_threshold)
+    xl, ci = _records_placeholders(G, Zs, kerns, shape[1])
+    a = _pack_moment_groups(who, Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, xl, ci, 0, shape[1], Qs, None, q_mode)
+    D, args = a["D"], a["args"]
+    r = _pack_records(who, G, D, args[16], x0s, control_records, Y_records, lengths, S0s, records_per_pass)
+    R, steps = r["R"], r["steps"]
+    N, pargs, keep = _adaptive_draws(who, G, R, steps, D, eps, unif, xi0, r["S0"] is not None, return_particles, seeded)
+    m = _pack_summary(who, D, R * steps, CC, DD, log_Rchols, r["Y"].reshape(R * steps, r["J"]))
+    out, extra, oargs = _particle_call(m, G, R, steps, D, N, bool(return_particles))
+    ad, aargs = _adaptive_call(G, R, steps, N, bool(return_particles))
+    dp = _lib.dptr
+    opt = lambda x: None if x is None else dp(x)
+    entry = "ffvd_particle_adaptive_records_grouped" if seeded is None else "ffvd_particle_adaptive_seeded_records_grouped"
+    rc = getattr(_lib.load(), entry)(*args[:13], R, dp(r["x0"]), opt(r["S0"]), opt(r["ctrl"]), *args[16:], dp(m["CC"]), dp(m["DD"]), dp(m["sd"]),
+                                     m["J"], dp(m["Y"]), r["rpp"], *pargs, thr, *oargs, *aargs)
+    _lib.check(rc, None, who)
+    return _adaptive_dict(_particle_dict(r, G, out, extra, Y_train_std), r, ad)
+
+
+def _adaptive_records_posterior(who, Zs, kerns, Xs, Qs, control_inputs, control_records, Y_records, CC, DD, log_Rchols, eps, unif, xi0,
+                                ess_threshold, lengths, x0s, S0s, q_mode, Y_train_std, jitter, groups_per_pass, records_per_pass,
+                                return_particles, seeded=None):
+    """The body of `posterior_filter_adaptive_records_grouped` and, with seeded = (seed, noise, num_particles), of
+    `posterior_adaptive_records_seeded`."""
+    thr = _ess_threshold(who, ess_threshold)
+    a = _pack_posterior_moment(who, Zs, kerns, Xs, Qs, control_inputs, 0, 0, None, q_mode, jitter, groups_per_pass)
+    G, D, args = a["G"], a["D"], a["args"]
+    r = _pack_records(who, G, D, args[11], x0s, control_records, Y_records, lengths, S0s, records_per_pass)
+    R, steps = r["R"], r["steps"]
+    N, pargs, keep = _adaptive_draws(who, G, R, steps, D, eps, unif, xi0, r["S0"] is not None, return_particles, seeded)
+    m = _pack_summary(who, D, R * steps, CC, DD, log_Rchols, r["Y"].reshape(R * steps, r["J"]))
+    out, extra, oargs = _particle_call(m, G, R, steps, D, N, bool(return_particles))
+    ad, aargs = _adaptive_call(G, R, steps, N, bool(return_particles))
+    dp = _lib.dptr
+    opt = lambda x: None if x is None else dp(x)
+    entry = "ffvd_posterior_particle_adaptive_records_grouped" if seeded is None else "ffvd_posterior_particle_adaptive_seeded_records_grouped"
+    rc = getattr(_lib.load(), entry)(*args[:17], R, opt(r["x0"]), opt(r["S0"]), opt(r["ctrl"]), steps, dp(m["CC"]), dp(m["DD"]), dp(m["sd"]),
+                                     m["J"], dp(m["Y"]), r["rpp"], *pargs, thr, *oargs, *aargs, None)
+    _lib.check(rc, None, who)
+    return _adaptive_dict(_particle_dict(r, G, out, extra, Y_train_std), r, ad)
+
+
+def filter_adaptive_records_grouped(Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_records, Y_records, Qs, CC, DD, log_Rchols,
+                                    eps, unif, *, ess_threshold=0.5, xi0=None, lengths=None, S0s=None, q_mode="reference", Y_train_std=1.0,
+                                    records_per_pass=0, return_particles=False):
+    """Particle filtering of R observed records through G posteriors with ADAPTIVE resampling in ONE call
+    (`ffvd_particle_adaptive_records_grouped`): `filter_particle_records_grouped` carrying a WEIGHTED set that is resampled only on
+    the rows whose effective sample size falls below ess_threshold * N (Liu & Chen 1998), the textbook form.  Where rows have few or
+    uninformative outputs the ESS stays high, and every resampling step saved there takes variance out of log_evidence and of the
+    filtered moments and keeps the ancestry from thinning.  The parameters, the checks, the draws (the same arrays in the same
+    layouts; unif[t] is not read on a row that does not resample) and the dict are `filter_particle_records_grouped`'s.
+    Per track, with X the particles and a the log-weights carried into row t (largest entry exactly 0; a = 0 at the start),
+    e_i = exp(a_i) and A = sum e: X^-_i as in the bootstrap call; m_pred, S_pred: the e-weighted mean and centred covariance of the
+    X^-; lpd[t, j] = max_i(a_i + l_ij) + log(sum_i exp(a_i + l_ij - max) / A); b_i = a_i + L_i, lpd_joint[t] = max b +
+    log(sum_i exp(b_i - max b) / A); W_i = exp(b_i - max b), m_filt / S_filt the W-weighted moments, ess = (sum W)^2 / sum W^2,
+    weights[t, i] = W_i / sum W.  If ess < ess_threshold * N: the bootstrap call's systematic resampling with unif[t], then a = 0 and
+    resampled[t] = 1; otherwise ancestors[t, i] = i, the X^- are carried, a_i = b_i - max b and resampled[t] = 0.  A row with nothing
+    observed only propagates: m_filt = m_pred and S_filt = S_pred bit for bit, ess = A^2 / sum e^2, weights = e / A, a kept.
+    log_evidence, the sum of lpd_joint over the observed rows, is the unbiased SMC estimate whether or not a row resamples.
+    ess_threshold: a finite number >= 0; 0 never resamples (sequential importance sampling), any value above 1 always resamples and
+    returns `filter_particle_records_grouped`'s arrays bit for bit in every key the two share.
+    Returns that call's dict plus resampled (G, R, steps) int32 (-1 at and beyond a record's length) and, with return_particles,
+    weights (G, R, steps, N) (NaN there): (particles[t], weights[t]) is the filtering approximation after every row, resampled or
+    not; particles[t] is X^-.  A track's arrays are bit-identical whatever the other groups, the other records, their order and
+    records_per_pass are.  Smoothing, backward simulation and forecasts on the weighted sets are not built (DESIGN.md section 9,
+    "Adaptive resampling")."""
+    return _adaptive_records_given("filter_adaptive_records_grouped", Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_records,
+                                   Y_records, Qs, CC, DD, log_Rchols, eps, unif, xi0, ess_threshold, lengths, S0s, q_mode, Y_train_std,
+                                   records_per_pass, return_particles)
+
+
+def posterior_filter_adaptive_records_grouped(Zs, kerns, Xs, Qs, control_inputs, control_records, Y_records, CC, DD, log_Rchols, eps, unif, *,
+                                              ess_threshold=0.5, xi0=None, lengths=None, x0s=None, S0s=None, q_mode="reference",
+                                              Y_train_std=1.0, jitter=JITTER, groups_per_pass=0, records_per_pass=0, return_particles=False):
+    """The collapsed posterior of G groups and the filter of `filter_adaptive_records_grouped` in ONE call
+    (`ffvd_posterior_particle_adaptive_records_grouped`): what `conditionals_multi_output.collapse_u_mean_grouped` followed by
+    `filter_adaptive_records_grouped` computes, without the posteriors leaving the device.  The parameters are
+    `posterior_filter_particle_records_grouped`'s plus ess_threshold; the returned dict is `filter_adaptive_records_grouped`'s."""
+    return _adaptive_records_posterior("posterior_filter_adaptive_records_grouped", Zs, kerns, Xs, Qs, control_inputs, control_records,
+                                       Y_records, CC, DD, log_Rchols, eps, unif, xi0, ess_threshold, lengths, x0s, S0s, q_mode, Y_train_std,
+                                       jitter, groups_per_pass, records_per_pass, return_particles)
+
+
+def adaptive_records_seeded(Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_records, Y_records, Qs, CC, DD, log_Rchols, *, seed,
+                            num_particles=256, ess_threshold=0.5, noise="shared", lengths=None, S0s=None, q_mode="reference",
+                            Y_train_std=1.0, records_per_pass=0, return_particles=False):
+    """`filter_adaptive_records_grouped` with SEEDED draws generated on the device (`ffvd_particle_adaptive_seeded_records_grouped`):
+    seed, noise and num_particles are `particle_records_seeded`'s, and the call equals `filter_adaptive_records_grouped` on
+    `particle_draws(seed, noise, G, R, steps, N, D, with_xi0=S0s is not None)` bit for bit in every key."""
+    return _adaptive_records_given("adaptive_records_seeded", Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_records, Y_records,
+                                   Qs, CC, DD, log_Rchols, None, None, None, ess_threshold, lengths, S0s, q_mode, Y_train_std,
+                                   records_per_pass, return_particles, seeded=(seed, noise, num_particles))
+
+
+def posterior_adaptive_records_seeded(Zs, kerns, Xs, Qs, control_inputs, control_records, Y_records, CC, DD, log_Rchols, *, seed,
+                                      num_particles=256, ess_threshold=0.5, noise="shared", lengths=None, x0s=None, S0s=None,
+                                      q_mode="reference", Y_train_std=1.0, jitter=JITTER, groups_per_pass=0, records_per_pass=0,
+                                      return_particles=False):
+    """The collapsed posterior of G groups and `adaptive_records_seeded` in ONE call
+    (`ffvd_posterior_particle_adaptive_seeded_records_grouped`): neither the posteriors nor the draws ever exist on the host.  The
+    model and start arguments are `posterior_filter_particle_records_grouped`'s; the rest and the dict are `adaptive_records_seeded`'s."""
+    return _adaptive_records_posterior("posterior_adaptive_records_seeded", Zs, kerns, Xs, Qs, control_inputs, control_records, Y_records,
+                                       CC, DD, log_Rchols, None, None, None, ess_threshold, lengths, x0s, S0s, q_mode, Y_train_std, jitter,
+                                       groups_per_pass, records_per_pass, return_particles, seeded=(seed, noise, num_particles))
 
 
 SMOOTH_PARTICLE_KEYS = ("m_smooth", "S_smooth", "ess_smooth")

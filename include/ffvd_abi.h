@@ -864,6 +864,7 @@ int  ffvd_op_posterior_filter_cubature_records_grouped(int kind, int G, int n_mo
  *   resample   systematic, one uniform per track and step, only for a row with an observed entry: cdf_k = W_0 + .. + W_k,
  *              a_i = min(#{k: cdf_k <= (unif[t] + i) / N cdf_{N-1}}, N - 1), X_{t+1,i} = X^-_{a_i}; otherwise a_i = i.  The index is
  *              clamped into [0, N) before it addresses anything, whatever the weights are.  No adaptive resampling.
+ *              (ffvd_particle_adaptive_records_grouped resamples only below an ESS threshold.)
  * log_evidence (G x R) is the sum of lpd_joint over the rows that have an observation: the SMC estimate of log p(y) of that record
  * under that group.  Pooled over the groups with equal weights (R x steps x J): y_mean, y_var_total and lpd_gauss as
  * ffvd_op_filter_records_grouped on (m_pred, S_pred); lpd_mix = log mean_g exp(lpd[g]), the density of the mixture of all G * N
@@ -1239,6 +1240,87 @@ int  ffvd_posterior_particle_seeded_records_grouped(int rule, int stage, int kin
                                                     double *S_traj, double *lag_cov, double *weights, double *trans_mean,
                                                     double *trans_var, double *m_smooth, double *S_smooth, double *ess_smooth,
                                                     double *w_smooth, double *U_means);
+
+/* ffvd_op_filter_particle_records_grouped with ADAPTIVE (ESS-triggered) resampling: the track carries a WEIGHTED set and resamples only
+ * on the rows whose effective sample size falls below ess_threshold * N.  The arguments are that call's with `ess_threshold` behind
+ * xi0_stride_r and with `weights` and `resampled` behind `ancestors`; the draws, their layouts and their indexing are that call's
+ * (unif[t] is not read on a row that does not resample).  Per track, with X the particles and a the log-weights carried into row t
+ * (largest entry exactly 0; a = 0 at the start), e_i = exp(a_i) and A = sum_i e_i:
+ *   propagate  X^-_i = X_i + m_i + eps[t, i] sqrt(v_i + Q)  (that call's expression)
+ *   moments    m_pred[t] = sum_i e_i X^-_i / A,  S_pred[t] = sum_i e_i (X^-_i - m_pred)(X^-_i - m_pred)^T / A (exactly symmetric)
+ *   densities  l_ij that call's emission log-density;  lpd[t, j] = max_i (a_i + l_ij) + log(sum_i exp(a_i + l_ij - max) / A), NaN where
+ *              y_tj is NaN;  b_i = a_i + sum_{j observed} l_ij;  lpd_joint[t] = max b + log(sum_i exp(b_i - max b) / A)
+ *   filtered   W_i = exp(b_i - max b);  m_filt[t], S_filt[t]: the W-weighted mean and centred covariance;  ess[t] = (sum W)^2 / sum W^2;
+ *              weights[t, i] = W_i / sum W
+ *   decide     ess[t] < ess_threshold N: that call's systematic resampling with unif[t] (ancestors[t], index clamped into [0, N)),
+ *              then a = 0 and resampled[t] = 1;  otherwise ancestors[t, i] = i, the X^- are carried, a_i = b_i - max b, resampled[t] = 0
+ *   a row with nothing observed: the propagation alone; m_filt = m_pred and S_filt = S_pred bit for bit, lpd and lpd_joint NaN,
+ *              ess[t] = A^2 / sum_i e_i^2, weights[t, i] = e_i / A, ancestors[t, i] = i, a kept, resampled[t] = 0
+ * particles[t] is X^- as in that call, so (particles[t], weights[t]) is the filtering approximation after every row.  log_evidence,
+ * the sum of lpd_joint over the observed rows, is the unbiased SMC estimate whether or not a row resamples.  ess_threshold must be
+ * finite and >= 0 (FFVD_EINVAL otherwise): 0 never resamples (sequential importance sampling), any value > 1 resamples every observed
+ * row.  CONTRACT: with ess_threshold > 1 every output the two calls share is ffvd_op_filter_particle_records_grouped's, bit for bit.
+ * New outputs, each may be NULL: weights G x R x steps x N, resampled G x R x steps (int).  Three launches per step as that call: only
+ * the per-track weight kernel differs.  Smoothing, backward simulation and forecasts on the weighted sets are not built.
+ * Limits: those of ffvd_op_filter_particle_records_grouped.  G = 0, R = 0 or steps = 0: FFVD_OK, nothing is touched. */
+int  ffvd_particle_adaptive_records_grouped(int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M,
+                                            int P, int D, const double *logvariances, const double *loglengthscales, const double *fs,
+                                            const double *const *q_sqrts, int q_mode, int R, const double *x_lasts, const double *S0s,
+                                            const double *ctrl, int C, int steps, const double *log_Qs, const double *CC,
+                                            const double *DD, const double *noise_std, int J, const double *Y_obs,
+                                            int records_per_pass, int N, const double *eps, long long eps_stride_g,
+                                            long long eps_stride_r, const double *unif, long long unif_stride_g,
+                                            long long unif_stride_r, const double *xi0, long long xi0_stride_g, long long xi0_stride_r,
+                                            double ess_threshold, double *m_pred, double *S_pred, double *m_filt, double *S_filt,
+                                            double *lpd, double *lpd_joint, double *y_mean, double *y_var_total, double *lpd_mix,
+                                            double *lpd_gauss, double *ess, double *log_evidence, double *particles, int *ancestors,
+                                            double *weights, int *resampled);
+
+/* ffvd_op_posterior_grouped followed by ffvd_particle_adaptive_records_grouped WITHOUT the posteriors leaving the device: the
+ * argument list of ffvd_op_posterior_filter_particle_records_grouped changed as above (U_means stays last), the method and outputs of
+ * the call above. */
+int  ffvd_posterior_particle_adaptive_records_grouped(int kind, int G, int n_models, const double *Zs, int M, int P, int D,
+                                                      const double *logvariances, const double *loglengthscales, const double *Xs,
+                                                      const double *ctrl_fit, int C, int T, const double *log_Qs, double jitter,
+                                                      int groups_per_pass, int q_mode, int R, const double *x0s, const double *S0s,
+                                                      const double *ctrl_roll, int steps, const double *CC, const double *DD,
+                                                      const double *noise_std, int J, const double *Y_obs, int records_per_pass,
+                                                      int N, const double *eps, long long eps_stride_g, long long eps_stride_r,
+                                                      const double *unif, long long unif_stride_g, long long unif_stride_r,
+                                                      const double *xi0, long long xi0_stride_g, long long xi0_stride_r,
+                                                      double ess_threshold, double *m_pred, double *S_pred, double *m_filt,
+                                                      double *S_filt, double *lpd, double *lpd_joint, double *y_mean,
+                                                      double *y_var_total, double *lpd_mix, double *lpd_gauss, double *ess,
+                                                      double *log_evidence, double *particles, int *ancestors, double *weights,
+                                                      int *resampled, double *U_means);
+
+/* The two calls above with seeded draws generated on the device: `N, seed, noise` (noise 0 shared, 1 per record, 2 independent) in
+ * place of N and the nine draw arguments eps .. xi0_stride_r, as ffvd_particle_seeded_records_grouped, whose fill launches these are.
+ * CONTRACT: every output is, bit for bit, that of the call above on the arrays of ffvd_particle_draws(seed, noise, ..) and the strides
+ * of the mode.  A bad noise is FFVD_EINVAL.  (ffvd_particle_seeded_records_grouped itself keeps its two rules.) */
+int  ffvd_particle_adaptive_seeded_records_grouped(int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs,
+                                                   int M, int P, int D, const double *logvariances, const double *loglengthscales,
+                                                   const double *fs, const double *const *q_sqrts, int q_mode, int R,
+                                                   const double *x_lasts, const double *S0s, const double *ctrl, int C, int steps,
+                                                   const double *log_Qs, const double *CC, const double *DD, const double *noise_std,
+                                                   int J, const double *Y_obs, int records_per_pass, int N, unsigned long long seed,
+                                                   int noise, double ess_threshold, double *m_pred, double *S_pred, double *m_filt,
+                                                   double *S_filt, double *lpd, double *lpd_joint, double *y_mean, double *y_var_total,
+                                                   double *lpd_mix, double *lpd_gauss, double *ess, double *log_evidence,
+                                                   double *particles, int *ancestors, double *weights, int *resampled);
+
+int  ffvd_posterior_particle_adaptive_seeded_records_grouped(int kind, int G, int n_models, const double *Zs, int M, int P, int D,
+                                                             const double *logvariances, const double *loglengthscales,
+                                                             const double *Xs, const double *ctrl_fit, int C, int T,
+                                                             const double *log_Qs, double jitter, int groups_per_pass, int q_mode,
+                                                             int R, const double *x0s, const double *S0s, const double *ctrl_roll,
+                                                             int steps, const double *CC, const double *DD, const double *noise_std,
+                                                             int J, const double *Y_obs, int records_per_pass, int N,
+                                                             unsigned long long seed, int noise, double ess_threshold, double *m_pred,
+                                                             double *S_pred, double *m_filt, double *S_filt, double *lpd,
+                                                             double *lpd_joint, double *y_mean, double *y_var_total, double *lpd_mix,
+                                                             double *lpd_gauss, double *ess, double *log_evidence, double *particles,
+                                                             int *ancestors, double *weights, int *resampled, double *U_means);
 
 /* Rolling-origin multi-step forecasts in one call: ffvd_op_filter_grouped (same arguments, same outputs, each of which may be NULL),
  * then from every origin o = origins[b] (n_origins rows of the record, strictly ascending, 0 <= o <= steps - 1 - horizon) `horizon`
