@@ -301,6 +301,16 @@ _SIGNATURES = {
                                                               _dp, _dp, _dp, C.c_int, _dp] + [_dp] * 14 +
                                                              [C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int] + _PARTICLE_FC_DRAWS +
                                                              [_dp] * 10),
+    # the two calls above on the adapted filter's sets: their argument lists
+    "ffvd_particle_adapted_forecast_grouped": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), _dp, C.c_int, C.c_int, C.c_int, _dp,
+                                                         _dp, _dp, C.POINTER(C.c_void_p), C.c_int, _dp, _dp, _dp, C.c_int, C.c_int, _dp,
+                                                         _dp, _dp, _dp, C.c_int, _dp] + [_dp] * 13 +
+                                                        [C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int] + _PARTICLE_FC_DRAWS + [_dp] * 10),
+    "ffvd_posterior_particle_adapted_forecast_grouped": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp,
+                                                                   _dp, C.c_int, C.c_int, _dp, C.c_double, C.c_int, C.c_int, _dp, _dp, _dp,
+                                                                   C.c_int, _dp, _dp, _dp, C.c_int, _dp] + [_dp] * 14 +
+                                                                  [C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int] + _PARTICLE_FC_DRAWS +
+                                                                  [_dp] * 10),
     "ffvd_op_moment_summary": (C.c_int, [_dp, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_int,
                                          _dp, _dp, _dp, _dp, _dp]),
     "ffvd_op_pg_sweep": (C.c_int, [C.c_int, _dp, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, _dp, C.c_int,

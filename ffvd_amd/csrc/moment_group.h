@@ -332,6 +332,15 @@ struct MomentParticleFanArgs {
 void launch_mg_pfan_step(hipStream_t stream, const MomentGroupArgs &a, const MomentFilterArgs &f, const MomentFanArgs &fn,
                          const MomentLinearFanArgs &l, const MomentParticleFanArgs &p, int t);
 
+// Adapted particle forecasts (moment_particle_adapted_fan.hip; DESIGN.md section 9, "Adapted particle forecasts"): the tracks, passes,
+// buffers, draws and limits of the particle forecasts above on the sets of the ADAPTED filter.  `particles` is that filter's device
+// stack, the equally weighted filtered set after every row, and a track starts from a straight copy of it (`ancestors` is not read).
+// The rows of the forecast are the adapted filter's Rao-Blackwellised m_pred / S_pred / lpd expressions; the set is advanced as that
+// filter advances it over a row with nothing observed.  The product kernel runs unchanged.
+// launch t of h + 1: the state kernel, then (t < h) the rows kernel and the product kernel
+void launch_mg_pafan_step(hipStream_t stream, const MomentGroupArgs &a, const MomentFilterArgs &f, const MomentFanArgs &fn,
+                          const MomentLinearFanArgs &l, const MomentParticleFanArgs &p, int t);
+
 struct MomentSummaryArgs {
     int G, steps, D, J, n_test;
     const double *m, *S;             // [G][steps][D], [G][steps][D][D]

@@ -1477,6 +1477,9 @@ struct ParticleFcReq {
     long long eps_fc_g, eps_fc_b;
     double *fc_lpd;                              // [G][B][h][J] or NULL
     double *fc_particles;                        // [G][B][h][N][D] or NULL
+    // the adapted rule (moment_particle_adapted.hip over the record, moment_particle_adapted_fan.hip for the tracks): the same
+    // request, the same checks
+    bool adapted = false;
     bool any_output() const { return filter.ess || filter.log_evidence || fc_lpd || fc_particles; }
 };
 // the checks of a particle forecast request that need no device: the filter's with R = 1, the strides and values of eps_fc,
@@ -1498,6 +1501,8 @@ bool particle_fc_ok(const ParticleFcReq &q, int G, int B, int h, int steps, int 
 // tracks; its device `particles` and `ancestors` stacks are always kept: the tracks start from them), then the passes over the origins
 // (moment_particle_fan.hip: h + 1 launch triples each), the pooled summary of the forecast stacks on the device, the downloads, and on
 // the host fc_lpd_mix = log mean_g exp(fc_lpd[g]) in ascending g, as mg_particle_finish forms the filter's.
+// pf.adapted: the adapted filter over the record (launch_mg_parec_step, with the (mu, s) buffers of one record per group) and the
+// adapted tracks (moment_particle_adapted_fan.hip), which start from its `particles` stack alone; everything else is shared.
 int mg_particle_fc_run(Scratch &sc, const std::string &who, int G, int nm, int M, int P, int D, int C, int steps, const HyperView &hv,
                        const double *dZ, const double *dW, const double *dq, int q_mode, const double *dU, const double *dxl, const double *dS0,
                        const double *dlq, const double *dctrl, double *m_x, double *S_x, const FilterReq &flt, const ForecastReq &fc,
@@ -1543,6 +1548,11 @@ int mg_particle_fc_run(Scratch &sc, const std::string &who, int G, int nm, int M
     ta.fc_particles = pf.fc_particles ? sc.alloc<double>(nm_fc * N) : nullptr;
     OP_CHECK(pa.eps && pa.unif && (!dS0 || pa.xi0) && pa.xstate && pa.pmean && pa.ess && pa.particles && pa.ancestors && ta.eps_fc &&
              ta.lpd_fc && (!pf.fc_particles || ta.fc_particles), who);
+    MomentParticleAdaptedArgs pd{};
+    if (pf.adapted) {                                                                  // (mu, s) of the parents of the filter's row in flight
+        pd.mu = sc.alloc<double>((size_t)G * N * D); pd.sv = sc.alloc<double>((size_t)G * N * D);
+        OP_CHECK(pd.mu && pd.sv, who);
+    }
     OP_TRY(hipMemsetAsync(lf.K, 0, (size_t)lf.units * lf.Tp * Mp * sizeof(double), sc.stream));          // rows no pass fills stay zeros
     OP_TRY(hipMemcpyAsync(dorg, fc.origins, (size_t)B * sizeof(int), hipMemcpyHostToDevice, sc.stream));
     if (int rc = bg.launch(sc, G, nm, M, D, Mp, hv.len, dW, dq, q_mode, dU)) return rc;
@@ -1556,7 +1566,10 @@ int mg_particle_fc_run(Scratch &sc, const std::string &who, int G, int nm, int M
         const MomentRecordArgs ra{1, 1, 0};
         MomentLinearFanArgs l1 = mg_lfan_layout(G, nm, D, Mp, upg, N);
         l1.K = lf.K; l1.vpart = lf.vpart;
-        for (int t = 0; t <= steps; ++t) launch_mg_prec_step(sc.stream, a, fa, ra, l1, pa, t);
+        for (int t = 0; t <= steps; ++t) {
+            if (pf.adapted) launch_mg_parec_step(sc.stream, a, fa, ra, l1, pa, pd, t);
+            else launch_mg_prec_step(sc.stream, a, fa, ra, l1, pa, t);
+        }
         OP_TRY(hipMemsetAsync(lf.K, 0, (size_t)l1.units * l1.Tp * Mp * sizeof(double), sc.stream));
     }
     // passes of at most Bp origins, h + 1 launch triples each; a track's values do not depend on the pass it is in
@@ -1568,7 +1581,10 @@ int mg_particle_fc_run(Scratch &sc, const std::string &who, int G, int nm, int M
         fn.b0 = b0; fn.Bp = B - b0 < Bp ? B - b0 : Bp;
         tg.G = G * fn.Bp;
         lf.nr = (lf.shared ? G * fn.Bp : fn.Bp) * N;
-        for (int t = 0; t <= h; ++t) launch_mg_pfan_step(sc.stream, tg, fa, fn, lf, ta, t);
+        for (int t = 0; t <= h; ++t) {
+            if (pf.adapted) launch_mg_pafan_step(sc.stream, tg, fa, fn, lf, ta, t);
+            else launch_mg_pfan_step(sc.stream, tg, fa, fn, lf, ta, t);
+        }
     }
     OP_TRY(hipGetLastError());
     std::vector<double> hl;
@@ -2439,6 +2455,61 @@ extern "C" int ffvd_op_posterior_forecast_particle_grouped(int kind, int G, int 
                               y_var_total, lpd_mix, lpd_gauss, U_means, horizon, origins, n_origins, tracks_per_pass, m_fc, S_fc, fc_y_mean,
                               fc_y_var_total, fc_lpd_mix, fc_lpd_gauss, &pf);
 }
+
+// The same two calls with the fully adapted particle filter over the record and the adapted tracks (moment_particle_adapted_fan.hip):
+// the argument lists, the draws and the checks of the two calls above.  A track starts from the filter's equally weighted filtered
+// set after its origin; m_fc / S_fc / fc_lpd are the filter's Rao-Blackwellised prediction expressions at every horizon.
+namespace {
+const char *const mg_afc_se_only =
+    " (the adapted particle forecasts are built for the SE kernel only: their kernel rows are SE-ARD's)";
+}
+#define FFVD_PARTICLE_AFC_REQ                                                                                                                \
+    ParticleFcReq pf {                                                                                                                       \
+        ParticleReq{N, eps, eps_stride_g, 0, unif, unif_stride_g, 0, xi0, xi0_stride_g, 0, ess, log_evidence, nullptr, nullptr}, eps_fc,     \
+            eps_fc_stride_g, eps_fc_stride_b, fc_lpd, fc_particles                                                                           \
+    };                                                                                                                                       \
+    pf.adapted = true;                                                                                                                       \
+    if (kind != FFVD_KERNEL_SE) return set_error(nullptr, FFVD_EINVAL, std::string(who) + ": bad argument" + mg_afc_se_only)
+extern "C" int ffvd_particle_adapted_forecast_grouped(int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M, int P,
+                                        int D, const double *logvariances, const double *loglengthscales, const double *fs,
+                                        const double *const *q_sqrts, int q_mode, const double *x_lasts, const double *S0s,
+                                        const double *ctrl, int C, int steps, const double *log_Qs, const double *CC, const double *DD,
+                                        const double *noise_std, int J, const double *Y_obs, double *m_pred, double *S_pred,
+                                        double *m_filt, double *S_filt, double *cross, double *lpd, double *lpd_joint, double *m_smooth,
+                                        double *S_smooth, double *y_mean, double *y_var_total, double *lpd_mix, double *lpd_gauss,
+                                        int horizon, const int *origins, int n_origins, int tracks_per_pass, FFVD_PARTICLE_FC_PARAMS,
+                                        double *m_fc, double *S_fc, double *fc_y_mean, double *fc_y_var_total, double *fc_lpd_mix,
+                                        double *fc_lpd_gauss, double *ess, double *log_evidence, double *fc_lpd, double *fc_particles) {
+    const char *who = "ffvd_particle_adapted_forecast_grouped";
+    FFVD_PARTICLE_AFC_REQ;
+    return forecast_given(who, MG_METHOD_PARTICLE, kind, G, n_models, Lm_inverse_seqs, Zs, M, P, D,
+                          logvariances, loglengthscales, fs, q_sqrts, q_mode, x_lasts, S0s, ctrl, C, steps, log_Qs, CC, DD, noise_std, J,
+                          Y_obs, m_pred, S_pred, m_filt, S_filt, cross, lpd, lpd_joint, m_smooth, S_smooth, y_mean, y_var_total, lpd_mix,
+                          lpd_gauss, horizon, origins, n_origins, tracks_per_pass, m_fc, S_fc, fc_y_mean, fc_y_var_total, fc_lpd_mix,
+                          fc_lpd_gauss, &pf);
+}
+
+extern "C" int ffvd_posterior_particle_adapted_forecast_grouped(int kind, int G, int n_models, const double *Zs, int M, int P, int D,
+                                                  const double *logvariances, const double *loglengthscales, const double *Xs,
+                                                  const double *ctrl_fit, int C, int T, const double *log_Qs, double jitter,
+                                                  int groups_per_pass, int q_mode, const double *x0s, const double *S0s,
+                                                  const double *ctrl_roll, int steps, const double *CC, const double *DD,
+                                                  const double *noise_std, int J, const double *Y_obs, double *m_pred, double *S_pred,
+                                                  double *m_filt, double *S_filt, double *cross, double *lpd, double *lpd_joint,
+                                                  double *m_smooth, double *S_smooth, double *y_mean, double *y_var_total, double *lpd_mix,
+                                                  double *lpd_gauss, double *U_means, int horizon, const int *origins, int n_origins,
+                                                  int tracks_per_pass, FFVD_PARTICLE_FC_PARAMS, double *m_fc, double *S_fc,
+                                                  double *fc_y_mean, double *fc_y_var_total, double *fc_lpd_mix, double *fc_lpd_gauss,
+                                                  double *ess, double *log_evidence, double *fc_lpd, double *fc_particles) {
+    const char *who = "ffvd_posterior_particle_adapted_forecast_grouped";
+    FFVD_PARTICLE_AFC_REQ;
+    return forecast_posterior(who, MG_METHOD_PARTICLE, kind, G, n_models, Zs, M, P, D, logvariances,
+                              loglengthscales, Xs, ctrl_fit, C, T, log_Qs, jitter, groups_per_pass, q_mode, x0s, S0s, ctrl_roll, steps, CC,
+                              DD, noise_std, J, Y_obs, m_pred, S_pred, m_filt, S_filt, cross, lpd, lpd_joint, m_smooth, S_smooth, y_mean,
+                              y_var_total, lpd_mix, lpd_gauss, U_means, horizon, origins, n_origins, tracks_per_pass, m_fc, S_fc, fc_y_mean,
+                              fc_y_var_total, fc_lpd_mix, fc_lpd_gauss, &pf);
+}
+#undef FFVD_PARTICLE_AFC_REQ
 #undef FFVD_PARTICLE_FC_PARAMS
 #undef FFVD_PARTICLE_FC_REQ
 

@@ -909,9 +909,28 @@ class DGPSSM:
         (chain, origin) for the forecast draws, refused with the byte count when the draws would exceed 1 GiB.  The other parameters,
         the start, the control rows and the two forms (collapsed U: ONE `posterior_forecast_particle_grouped` call; explicit U:
         `kernel_pre_cal` once, then `forecast_particle_grouped`) are those of `forecast_heldout`."""
+        return DGPSSM._forecast_heldout_particles(self, "forecast_heldout_particle", False, Y_test, control_inputs, horizon, num_particles,
+                                                  seed, noise, stride, origins, x0, S0, q_mode, Y_train_std, return_tracks)
+
+    def forecast_heldout_adapted(self, Y_test, control_inputs=None, horizon=10, *, num_particles=256, seed=None, noise="shared", stride=1,
+                                 origins=None, x0=None, S0=None, q_mode="reference", Y_train_std=1.0, return_tracks=False):
+        """`forecast_heldout_particle` on the sets of the fully adapted particle filter (`filter_records_adapted`'s rule over the one
+        record): each track starts from the equally weighted filtered set after its origin, and every forecast row is the adapted
+        filter's Rao-Blackwellised prediction (the last step's process noise in closed form), so the row k = 1 from origin o is the
+        filter's own one-step prediction of row o + 1.  prediction.forecast_adapted_grouped has the method.  The parameters, the
+        draws (the same `seed` gives the same draws as `forecast_heldout_particle`), the two forms (collapsed U: ONE
+        `posterior_forecast_adapted_grouped` call; explicit U: `kernel_pre_cal` once, then `forecast_adapted_grouped`) and the keys of
+        the returned dict are that method's."""
+        return DGPSSM._forecast_heldout_particles(self, "forecast_heldout_adapted", True, Y_test, control_inputs, horizon, num_particles,
+                                                  seed, noise, stride, origins, x0, S0, q_mode, Y_train_std, return_tracks)
+
+    def _forecast_heldout_particles(self, who, adapted, Y_test, control_inputs, horizon, num_particles, seed, noise, stride, origins, x0, S0,
+                                    q_mode, Y_train_std, return_tracks):
+        """The body of `forecast_heldout_particle` and `forecast_heldout_adapted` (called through the class, as `_heldout_record`)."""
         from . import conditionals_multi_output as cmo
         from . import prediction as pr
-        who = "forecast_heldout_particle"
+        fused, explicit = ((pr.posterior_forecast_adapted_grouped, pr.forecast_adapted_grouped) if adapted else
+                           (pr.posterior_forecast_particle_grouped, pr.forecast_particle_grouped))
         if noise not in ("shared", "independent"):
             raise ValueError(f"{who}: noise: expected \"shared\" or \"independent\", got {noise!r}")
         N = num_particles
@@ -933,12 +952,12 @@ class DGPSSM:
         lay, lik, n_train = self.layers[-1], self.likelihood, self.Y.shape[0]
         kw = dict(xi0=xi0, origins=org, S0s=S0s, q_mode=q_mode, Y_train_std=Y_train_std, return_tracks=return_tracks)
         if self.U_collapse:
-            return pr.posterior_forecast_particle_grouped(lay.Z, lay.kernel, [self._X_chains[s_] for s_ in range(S)], self.Q, ci, n_train,
-                                                          Y_test, lik.CC, lik.DD, lik.log_Rchols, h, eps, unif, eps_fc, x0s=x0s, **kw)
+            return fused(lay.Z, lay.kernel, [self._X_chains[s_] for s_ in range(S)], self.Q, ci, n_train, Y_test, lik.CC, lik.DD,
+                         lik.log_Rchols, h, eps, unif, eps_fc, x0s=x0s, **kw)
         Lm = cmo.kernel_pre_cal(lay.Z, lay.kernel)
         starts = [self._X_chains[s_][-1] for s_ in range(S)] if x0s is None else list(x0s)
-        return pr.forecast_particle_grouped(Lm, lay.Z, lay.kernel, [lay.U] * S, None, starts, ci, n_train, Y_test, self.Q, lik.CC, lik.DD,
-                                            lik.log_Rchols, h, eps, unif, eps_fc, **kw)
+        return explicit(Lm, lay.Z, lay.kernel, [lay.U] * S, None, starts, ci, n_train, Y_test, self.Q, lik.CC, lik.DD, lik.log_Rchols, h,
+                        eps, unif, eps_fc, **kw)
 
     def _forecast_heldout(self, who, method, Y_test, control_inputs, horizon, stride, origins, x0, S0, q_mode, Y_train_std, return_tracks):
         """The body of `forecast_heldout`, `forecast_heldout_linearised` and `forecast_heldout_cubature` (called through the class, as

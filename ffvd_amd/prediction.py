@@ -2047,6 +2047,62 @@ def posterior_forecast_particle_grouped(Zs, kerns, Xs, Qs, control_inputs, ctrl_
     return _particle_forecast_dict(m, org, h, fout, out, Y_train_std)
 
 
+def forecast_adapted_grouped(Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_inputs, ctrl_offset, Y_obs, Qs, CC, DD, log_Rchols,
+                             horizon, eps, unif, eps_fc, *, xi0=None, origins=None, stride=1, S0s=None, q_mode="reference", Y_train_std=1.0,
+                             return_tracks=False, return_filter=False, return_particles=False, tracks_per_pass=0):
+    """`forecast_particle_grouped` on the sets of the fully adapted particle filter, in ONE call
+    (`ffvd_particle_adapted_forecast_grouped`): the filter of `filter_adapted_records_grouped` over the one record, then from every
+    origin o a track of N particles started from a straight copy of particles[o], the equally weighted FILTERED set that filter stores
+    after row o (no ancestor is read).  For k = 1 .. h, with (mean_i, v_i) the GP conditional of the group at [X_i, c_row], control
+    row ctrl_offset + o + k, mu_i = X_i + mean_i and s_i = v_i + Q:
+      m_fc = mean_i mu_i,  S_fc = mean_i (mu_i - m_fc)(mu_i - m_fc)^T + diag(mean_i s_i)          (no draw enters)
+      lpd_fc_j = log mean_i N(Y[o + k, j]; CC[:, j] . mu_i + DD_j, sum_d CC[d, j]^2 s_id + sd_j^2), NaN where that target is NaN
+      X_i <- mu_i + eps_fc[k - 1, i] sqrt(s_i);  fc_particles[k - 1] is this advanced set.
+    These are the adapted filter's Rao-Blackwellised m_pred / S_pred / lpd expressions: the last step's process noise is integrated
+    in closed form at every horizon, the row k = 1 from origin o equals the filter's own prediction of row o + 1 bit for bit, and a
+    track is bit for bit what `filter_adapted_records_grouped` computes (m_pred, S_pred, particles at rows o + 1 .. o + h) over the
+    record cut after its origin and continued by `horizon` all-NaN rows with the draws concatenated.  A track does not depend on
+    the other tracks, the other groups or tracks_per_pass ("Adapted particle forecasts").  The parameters, the
+    draws and their layouts, the return_* flags and the keys of the returned dict are `forecast_particle_grouped`'s; with
+    return_filter the filter keys are those of `filter_adapted_records_grouped` with the record axis dropped.  SquaredExponential
+    kernels only."""
+    who = "forecast_adapted_grouped"
+    steps = _filter_steps(who, Y_obs)
+    a = _pack_moment_groups(who, Lm_inverse_seqs, Zs, kerns, U_vals, q_sqrts, x0s, control_inputs, ctrl_offset, steps, Qs, S0s, q_mode)
+    G, D = a["G"], a["D"]
+    h, org = _pack_forecast(who, steps, horizon, origins, stride, (a["args"][0], a["M"], a["args"][6], D))
+    m = _pack_filter(who, D, Y_obs, CC, DD, log_Rchols)
+    N, pargs, keep = _pack_particle_forecast(who, G, len(org), steps, h, D, eps, unif, xi0, eps_fc, S0s is not None, return_particles)
+    fout, fargs, out, hargs, oargs = _particle_forecast_call(m, G, D, steps, h, org, N, return_tracks, return_filter,
+                                                             bool(return_particles), tracks_per_pass)
+    rc = _lib.load().ffvd_particle_adapted_forecast_grouped(*a["args"], *fargs, *hargs, *pargs, *oargs)
+    _lib.check(rc, None, who)
+    return _particle_forecast_dict(m, org, h, fout, out, Y_train_std)
+
+
+def posterior_forecast_adapted_grouped(Zs, kerns, Xs, Qs, control_inputs, ctrl_offset, Y_obs, CC, DD, log_Rchols, horizon, eps, unif, eps_fc,
+                                       *, xi0=None, x0s=None, origins=None, stride=1, S0s=None, q_mode="reference", Y_train_std=1.0,
+                                       return_tracks=False, return_filter=False, return_particles=False, tracks_per_pass=0, jitter=JITTER,
+                                       groups_per_pass=0):
+    """The collapsed posterior of G groups and the forecasts of `forecast_adapted_grouped` in ONE call
+    (`ffvd_posterior_particle_adapted_forecast_grouped`), without the posteriors leaving the device.  The parameters are
+    `posterior_forecast_particle_grouped`'s; the returned dict is `forecast_adapted_grouped`'s."""
+    who = "posterior_forecast_adapted_grouped"
+    steps = _filter_steps(who, Y_obs)
+    a = _pack_posterior_moment(who, Zs, kerns, Xs, Qs, control_inputs, ctrl_offset, steps, S0s, q_mode, jitter, groups_per_pass)
+    G, D = a["G"], a["D"]
+    h, org = _pack_forecast(who, steps, horizon, origins, stride, (a["args"][0], a["M"], a["args"][5], D))
+    m = _pack_filter(who, D, Y_obs, CC, DD, log_Rchols)
+    x0 = None if x0s is None else _lib.as_f64(x0s, (G, D), "x0s")
+    N, pargs, keep = _pack_particle_forecast(who, G, len(org), steps, h, D, eps, unif, xi0, eps_fc, S0s is not None, return_particles)
+    fout, fargs, out, hargs, oargs = _particle_forecast_call(m, G, D, steps, h, org, N, return_tracks, return_filter,
+                                                             bool(return_particles), tracks_per_pass)
+    pre = a["args"][:17] + (None if x0 is None else _lib.dptr(x0),) + a["args"][17:]
+    rc = _lib.load().ffvd_posterior_particle_adapted_forecast_grouped(*pre, *fargs, None, *hargs, *pargs, *oargs)
+    _lib.check(rc, None, who)
+    return _particle_forecast_dict(m, org, h, fout, out, Y_train_std)
+
+
 def pg_sweep(Lm_inverse_seq, Z, kern, U_val, X_ref, Y, control_inputs, CC, DD, Rchols, Q, x0, eps, unif):
     """One particle-Gibbs sweep over the latent trajectory: the INTENT of BaseModel.PG_for_X_speedup
     (base_model.py:78-138; the op as written never updates X, see include/ffvd_abi.h `ffvd_op_pg_sweep`).

@@ -1472,6 +1472,48 @@ int  ffvd_op_posterior_forecast_particle_grouped(int kind, int G, int n_models, 
                                         double *fc_y_var_total, double *fc_lpd_mix, double *fc_lpd_gauss, double *ess,
                                         double *log_evidence, double *fc_lpd, double *fc_particles);
 
+/* ffvd_op_forecast_particle_grouped on the sets of the fully adapted particle filter: the filter of
+ * ffvd_particle_adapted_records_grouped over the one record (R = 1: its outputs are that call's bit for bit, record axis dropped),
+ * then from every origin o a track of N particles started from a straight copy of the equally weighted FILTERED set that filter
+ * stores after row o (no ancestor is read).  With (mean_i, v_i) the GP conditional of the group at [X_i, c_row], control row
+ * origin + 1 + t at step t, mu_i = X_i + mean_i and s_i = v_i + Q:
+ *   m_fc = mean_i mu_i,   S_fc = mean_i (mu_i - m_fc)(mu_i - m_fc)^T + diag(mean_i s_i)   (exactly symmetric; no draw enters),
+ *   fc_lpd[g, b, t, j] = log mean_i N(Y_obs[origin + 1 + t, j]; CC[:, j] . mu_i + DD_j, sum_d CC[d, j]^2 s_id + noise_std_j^2)
+ *                        (NaN where that entry is NaN),
+ *   X_i <- mu_i + eps_fc[t, i] sqrt(s_i);   fc_particles[g, b, t] is this advanced set.
+ * These are the adapted filter's m_pred / S_pred / lpd expressions, so the row t = 0 of a track equals that filter's prediction of
+ * row origin + 1 bit for bit, and a track is bit for bit what ffvd_particle_adapted_records_grouped computes (m_pred, S_pred,
+ * particles) over the record cut after its origin and continued by `horizon` all-NaN rows with the draws concatenated; it does not
+ * depend on the other tracks, on the other groups or on tracks_per_pass.  The arguments, the draws, the outputs, the pooled arrays
+ * and the limits are ffvd_op_forecast_particle_grouped's.  SE kernel only (FFVD_EINVAL with a message that says so). */
+int  ffvd_particle_adapted_forecast_grouped(int kind, int G, int n_models, const double *const *Lm_inverse_seqs, const double *Zs, int M, int P, int D,
+                              const double *logvariances, const double *loglengthscales, const double *fs,
+                              const double *const *q_sqrts, int q_mode, const double *x_lasts, const double *S0s, const double *ctrl,
+                              int C, int steps, const double *log_Qs, const double *CC, const double *DD, const double *noise_std, int J,
+                              const double *Y_obs, double *m_pred, double *S_pred, double *m_filt, double *S_filt, double *cross,
+                              double *lpd, double *lpd_joint, double *m_smooth, double *S_smooth, double *y_mean, double *y_var_total,
+                              double *lpd_mix, double *lpd_gauss, int horizon, const int *origins, int n_origins, int tracks_per_pass,
+                              int N, const double *eps, long long eps_stride_g, const double *unif, long long unif_stride_g,
+                              const double *xi0, long long xi0_stride_g, const double *eps_fc, long long eps_fc_stride_g,
+                              long long eps_fc_stride_b, double *m_fc, double *S_fc, double *fc_y_mean, double *fc_y_var_total,
+                              double *fc_lpd_mix, double *fc_lpd_gauss, double *ess, double *log_evidence, double *fc_lpd,
+                              double *fc_particles);
+
+/* The same on the arguments of ffvd_op_posterior_forecast_particle_grouped: the collapsed posteriors never leave the device. */
+int  ffvd_posterior_particle_adapted_forecast_grouped(int kind, int G, int n_models, const double *Zs, int M, int P, int D, const double *logvariances,
+                                        const double *loglengthscales, const double *Xs, const double *ctrl_fit, int C, int T,
+                                        const double *log_Qs, double jitter, int groups_per_pass, int q_mode, const double *x0s,
+                                        const double *S0s, const double *ctrl_roll, int steps, const double *CC, const double *DD,
+                                        const double *noise_std, int J, const double *Y_obs, double *m_pred, double *S_pred,
+                                        double *m_filt, double *S_filt, double *cross, double *lpd, double *lpd_joint, double *m_smooth,
+                                        double *S_smooth, double *y_mean, double *y_var_total, double *lpd_mix, double *lpd_gauss,
+                                        double *U_means, int horizon, const int *origins, int n_origins, int tracks_per_pass,
+                                        int N, const double *eps, long long eps_stride_g, const double *unif, long long unif_stride_g,
+                                        const double *xi0, long long xi0_stride_g, const double *eps_fc, long long eps_fc_stride_g,
+                                        long long eps_fc_stride_b, double *m_fc, double *S_fc, double *fc_y_mean,
+                                        double *fc_y_var_total, double *fc_lpd_mix, double *fc_lpd_gauss, double *ess,
+                                        double *log_evidence, double *fc_lpd, double *fc_particles);
+
 /* The summary of ffvd_op_moment_grouped for stacks the caller holds (m_x G x steps x D, S_x G x steps x D x D): the same launch.
  * Limits: D <= 8, J <= 8, 0 <= n_test <= steps, G * steps * D * D < 2^31, as ffvd_op_rollout_summary otherwise. */
 int  ffvd_op_moment_summary(const double *m_x, const double *S_x, int G, int steps, int D, const double *CC, const double *DD,
