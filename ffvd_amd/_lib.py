@@ -313,6 +313,10 @@ _SIGNATURES = {
                                                                   [_dp] * 10),
     "ffvd_op_moment_summary": (C.c_int, [_dp, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_int,
                                          _dp, _dp, _dp, _dp, _dp]),
+    "ffvd_score_points": (C.c_int, [_dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_longlong, C.c_longlong, _dp, _dp, _dp,
+                                    C.c_int, _dp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp]),
+    "ffvd_score_moments": (C.c_int, [_dp, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_int, _dp, C.c_int, C.c_int,
+                                     _dp, _dp, _dp]),
     "ffvd_op_pg_sweep": (C.c_int, [C.c_int, _dp, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, _dp, C.c_int,
                                    _dp, C.c_int, _dp, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, C.c_void_p]),
     "ffvd_comm_unique_id": (C.c_int, [C.c_void_p]),

@@ -17,8 +17,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libffvd_hip.so")
 HASH = LIB + ".hash"
 OBJDIR = os.path.join(HERE, "build")
-SOURCES = ["kernels.hip", "gram.hip", "potrf.hip", "potrf_flow.hip", "project.hip", "kernels_f32.hip", "grad.hip", "optim.hip", "tiny.hip", "loops.hip", "rollout_group.hip", "posterior_group.hip", "conditional_group.hip", "transition_grad.hip", "predict_summary.hip", "moment_group.hip", "moment_filter.hip", "moment_fan.hip", "moment_linear.hip", "moment_linear_fan.hip", "moment_linear_records.hip", "moment_cubature_records.hip", "moment_cubature_fan.hip", "moment_particle_records.hip", "moment_particle_fan.hip", "moment_particle_smooth.hip", "moment_particle_backsim.hip", "moment_particle_adapted.hip", "moment_particle_adapted_smooth.hip", "moment_particle_adapted_fan.hip","moment_particle_draws.hip", "moment_particle_adaptive.hip", "cov.hip", "abi.hip", "backward.hip", "ops.hip", "ops_loops.hip", "ops_grouped.hip", "train.hip", "comm.hip"]
-HEADERS = ["kernels.h", "dev_common.h", "potrf_blocks.h", "step_bodies.h", "tiny.h", "kernels_f32.h", "grad.h", "optim.h", "rollout_group.h", "posterior_group.h", "conditional_group.h", "transition_grad.h", "predict_summary.h", "moment_group.h", "moment_step.h", "moment_particle.h", "moment_particle_draws.h", "gemm_rowmajor.h", "abi_internal.h", "op_scratch.h", "handle.h", os.path.join("..", "..", "include", "ffvd_abi.h")]
+SOURCES = ["kernels.hip", "gram.hip", "potrf.hip", "potrf_flow.hip", "project.hip", "kernels_f32.hip", "grad.hip", "optim.hip", "tiny.hip", "loops.hip", "rollout_group.hip", "posterior_group.hip", "conditional_group.hip", "transition_grad.hip", "predict_summary.hip", "predict_score.hip", "moment_group.hip", "moment_filter.hip", "moment_fan.hip", "moment_linear.hip", "moment_linear_fan.hip", "moment_linear_records.hip", "moment_cubature_records.hip", "moment_cubature_fan.hip", "moment_particle_records.hip", "moment_particle_fan.hip", "moment_particle_smooth.hip", "moment_particle_backsim.hip", "moment_particle_adapted.hip", "moment_particle_adapted_smooth.hip", "moment_particle_adapted_fan.hip","moment_particle_draws.hip", "moment_particle_adaptive.hip", "cov.hip", "abi.hip", "backward.hip", "ops.hip", "ops_loops.hip", "ops_grouped.hip", "ops_score.hip", "train.hip", "comm.hip"]
+HEADERS = ["kernels.h", "dev_common.h", "potrf_blocks.h", "step_bodies.h", "tiny.h", "kernels_f32.h", "grad.h", "optim.h", "rollout_group.h", "posterior_group.h", "conditional_group.h", "transition_grad.h", "predict_summary.h", "predict_score.h", "moment_group.h", "moment_step.h", "moment_particle.h", "moment_particle_draws.h", "gemm_rowmajor.h", "abi_internal.h", "op_scratch.h", "handle.h", os.path.join("..", "..", "include", "ffvd_abi.h")]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-Wno-unused-value"]
 LINK = ["-shared", "-fPIC", "--offload-arch=gfx950", "-ldl"]
 

@@ -925,8 +925,9 @@ class DGPSSM:
                                                   seed, noise, stride, origins, x0, S0, q_mode, Y_train_std, return_tracks)
 
     def _forecast_heldout_particles(self, who, adapted, Y_test, control_inputs, horizon, num_particles, seed, noise, stride, origins, x0, S0,
-                                    q_mode, Y_train_std, return_tracks):
-        """The body of `forecast_heldout_particle` and `forecast_heldout_adapted` (called through the class, as `_heldout_record`)."""
+                                    q_mode, Y_train_std, return_tracks, return_particles=False):
+        """The body of `forecast_heldout_particle` and `forecast_heldout_adapted` (called through the class, as `_heldout_record`);
+        return_particles: `forecast_scores` asks for fc_particles as well."""
         from . import conditionals_multi_output as cmo
         from . import prediction as pr
         fused, explicit = ((pr.posterior_forecast_adapted_grouped, pr.forecast_adapted_grouped) if adapted else
@@ -951,6 +952,8 @@ class DGPSSM:
         eps_fc = rng.standard_normal(lead_fc + (h, N, D))
         lay, lik, n_train = self.layers[-1], self.likelihood, self.Y.shape[0]
         kw = dict(xi0=xi0, origins=org, S0s=S0s, q_mode=q_mode, Y_train_std=Y_train_std, return_tracks=return_tracks)
+        if return_particles:
+            kw["return_particles"] = True
         if self.U_collapse:
             return fused(lay.Z, lay.kernel, [self._X_chains[s_] for s_ in range(S)], self.Q, ci, n_train, Y_test, lik.CC, lik.DD,
                          lik.log_Rchols, h, eps, unif, eps_fc, x0s=x0s, **kw)
@@ -980,6 +983,49 @@ class DGPSSM:
         starts = [self._X_chains[s_][-1] for s_ in range(S)] if x0s is None else list(x0s)
         return explicit(Lm, lay.Z, lay.kernel, [lay.U] * S, None, starts, ci, n_train, Y_test, self.Q, lik.CC, lik.DD, lik.log_Rchols,
                         horizon, **kw)
+
+    FORECAST_SCORE_METHODS = ("moment", "linearised", "cubature", "particle", "adapted")
+
+    def forecast_scores(self, Y_test, control_inputs=None, horizon=10, *, method="moment", levels=(0.05, 0.5, 0.95), use="auto", **kwargs):
+        """CRPS, PIT, coverage and predictive quantiles of the k-step-ahead forecasts of a held-out record, k = 1 .. horizon: the
+        prediction-level call of `forecast_heldout` (method "moment"), `forecast_heldout_linearised`, `forecast_heldout_cubature`,
+        `forecast_heldout_particle` or `forecast_heldout_adapted` with its tracks (and, for the two particle rules, its particles)
+        returned, then prediction.forecast_score on that fan.  kwargs: the keywords of that method's `forecast_heldout_*` except
+        return_tracks (stride, origins, x0, S0, q_mode, Y_train_std; num_particles, seed, noise for the particle rules).  The three
+        Gaussian rules are scored as the mixture of the chains' Gaussians; the particle rules by `use`: "auto" / "particles" the
+        mixture of all S N particles' emissions, "moments" the per-chain Gaussians (m_fc, S_fc).  For "adapted" fc_particles is the
+        set after the draw: its point mixture is the sampled form of the Rao-Blackwellised predictive that rule's ll_h reports.
+        Returns the dict of prediction.forecast_score (crps, pit (B, horizon, Ydim), quantiles (B, horizon, Ydim, Q), crps_h,
+        coverage_h, n_h, ...) plus the forecast's own dict under "fan"."""
+        from . import prediction as pr
+        who = "forecast_scores"
+        if method not in DGPSSM.FORECAST_SCORE_METHODS:
+            raise ValueError(f"{who}: method: expected one of {list(DGPSSM.FORECAST_SCORE_METHODS)}, got {method!r}")
+        if use not in pr.SCORE_USES:
+            raise ValueError(f"{who}: use: expected one of {list(pr.SCORE_USES)}, got {use!r}")
+        particles = method in ("particle", "adapted")
+        if use == "particles" and not particles:
+            raise ValueError(f"{who}: use=\"particles\" needs a particle rule (method \"particle\" or \"adapted\"), got {method!r}")
+        allowed = dict(stride=1, origins=None, x0=None, S0=None, q_mode="reference", Y_train_std=1.0)
+        if particles:
+            allowed.update(num_particles=256, seed=None, noise="shared")
+        unknown = sorted(set(kwargs) - set(allowed))
+        if unknown:
+            raise TypeError(f"{who}: method {method!r} takes the keywords {sorted(allowed)}, got {unknown}")
+        k = dict(allowed, **kwargs)
+        pr._pack_levels(who, levels)                                # before any device work
+        if particles:
+            fan = DGPSSM._forecast_heldout_particles(self, who, method == "adapted", Y_test, control_inputs, horizon, k["num_particles"],
+                                                     k["seed"], k["noise"], k["stride"], k["origins"], k["x0"], k["S0"], k["q_mode"],
+                                                     k["Y_train_std"], True, return_particles=use != "moments")
+        else:
+            fan = DGPSSM._forecast_heldout(self, who, method, Y_test, control_inputs, horizon, k["stride"], k["origins"], k["x0"], k["S0"],
+                                           k["q_mode"], k["Y_train_std"], True)
+        lik = self.likelihood
+        Y = np.asarray(Y_test, dtype=np.float64)
+        res = pr.forecast_score(fan, Y, lik.CC, lik.DD, lik.log_Rchols, levels=levels, use=use, Y_train_std=k["Y_train_std"])
+        res["fan"] = fan
+        return res
 
     def predict_transition(self, Xnew, *, q_mode="reference", per_chain=True):
         """The learned transition function at inputs of the caller's choice: mean and variance of the posterior GP increment

@@ -2103,6 +2103,238 @@ def posterior_forecast_adapted_grouped(Zs, kerns, Xs, Qs, control_inputs, ctrl_o
     return _particle_forecast_dict(m, org, h, fout, out, Y_train_std)
 
 
+# ---- proper scores and quantiles of the pooled predictive mixtures (csrc/predict_score.h) -----------------------------------------------
+SCORE_TILE = 256              # components per tile of the pair kernel (PSC_TILE)
+SCORE_MAX_K = 65536
+SCORE_MAX_Q = 16
+SCORE_MAX_D_POINTS = 32
+SCORE_LEVEL_MIN = 1e-9
+SCORE_LEVELS = (0.05, 0.5, 0.95)
+SCORE_USES = ("auto", "moments", "particles")
+
+
+def _pack_levels(who, levels):
+    """The quantile levels as a contiguous vector: at most 16, each in [1e-9, 1 - 1e-9] (NaN is refused)."""
+    try:
+        lv = np.asarray(levels, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: levels: expected a sequence of numbers, got {levels!r}") from None
+    if lv.ndim != 1 or lv.size > SCORE_MAX_Q:
+        raise ValueError(f"{who}: levels: expected at most {SCORE_MAX_Q} levels in one dimension, got shape {lv.shape}")
+    if lv.size and not np.all((lv >= SCORE_LEVEL_MIN) & (lv <= 1.0 - SCORE_LEVEL_MIN)):
+        raise ValueError(f"{who}: levels: every level must lie in [{SCORE_LEVEL_MIN}, 1 - {SCORE_LEVEL_MIN}], got {lv.tolist()}")
+    return np.ascontiguousarray(lv)
+
+
+def _pack_score(who, K, D, steps, CC, DD, log_Rchols, Y_test, levels, targets_per_pass):
+    """Checks shared by the score functions (before the library is loaded): the emission and Y_test as `_pack_summary`, the levels,
+    targets_per_pass, 1 <= K <= 65536 and the 2^31 limits."""
+    if not 1 <= K <= SCORE_MAX_K:
+        raise ValueError(f"{who}: the number of mixture components K must lie in [1, {SCORE_MAX_K}], got {K}")
+    m = _pack_summary(who, D, steps, CC, DD, log_Rchols, Y_test)
+    lv = _pack_levels(who, levels)
+    if m["Y"] is None and lv.size == 0:
+        raise ValueError(f"{who}: nothing to compute: Y_test is None and levels is empty")
+    if isinstance(targets_per_pass, bool) or int(targets_per_pass) != targets_per_pass or int(targets_per_pass) < 0:
+        raise ValueError(f"{who}: targets_per_pass must be 0 (automatic) or a positive integer, got {targets_per_pass!r}")
+    if steps * m["J"] * K >= 2 ** 31:
+        raise ValueError(f"{who}: steps * J * K = {steps * m['J'] * K} must stay below 2^31")
+    m.update(levels=np.ascontiguousarray(lv), Q=lv.size, tpp=int(targets_per_pass))
+    return m
+
+
+def _score_call(m, steps):
+    """Output arrays and the arguments CC .. quantiles of the two score entry points."""
+    J, nt, Q, dp = m["J"], m["n_test"], m["Q"], _lib.dptr
+    out = dict(quantiles=np.empty((steps, J, Q)))
+    if m["Y"] is not None:
+        out.update(crps=np.empty((nt, J)), pit=np.empty((nt, J)))
+    opt = lambda k: dp(out[k]) if k in out and out[k].size else None
+    args = (dp(m["CC"]), dp(m["DD"]), dp(m["sd"]), J, dp(m["Y"]) if nt else None, nt, dp(m["levels"]) if Q else None, Q, m["tpp"],
+            opt("crps"), opt("pit"), opt("quantiles"))
+    return out, args, any(a is not None for a in args[-3:])
+
+
+def _coverage_pairs(levels):
+    """(index of p, index of 1 - p) for every level p < 1/2 whose mirror image is a level too"""
+    lv = np.asarray(levels, dtype=np.float64)
+    pairs = []
+    for i, p in enumerate(lv):
+        if p < 0.5:
+            hit = np.nonzero(np.abs(lv - (1.0 - p)) <= 1e-12)[0]
+            if hit.size:
+                pairs.append((i, int(hit[0])))
+    return pairs
+
+
+def _coverage(pit, seen, levels, axis=None):
+    """Share of the observed targets (`seen`) with p <= pit <= 1 - p, per symmetric pair of levels (last axis), over all targets or
+    along `axis`; NaN where nothing is observed.  Returns the shares and the lower levels p."""
+    pairs = _coverage_pairs(levels)
+    n = np.sum(seen, axis=axis)
+    cov = []
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for i, k in pairs:
+            inside = seen & (pit >= levels[i]) & (pit <= levels[k])
+            cov.append(np.where(n > 0, np.sum(inside, axis=axis) / n, np.nan))
+    shape = np.shape(n) + (len(pairs),)
+    return (np.stack(cov, axis=-1) if pairs else np.empty(shape)), np.array([levels[i] for i, _ in pairs], dtype=np.float64)
+
+
+def _score_dict(m, out, Y_train_std):
+    """The dict the score functions return: quantiles (steps, J, Q) and levels (Q,); with Y_test crps and pit (n_test, J), NaN where
+    the target is NaN, crps_mean over the observed targets (NaN without any), crps_mean_original_units (times Y_train_std),
+    coverage (one share per symmetric pair of levels p, 1 - p: the observed targets with p <= pit <= 1 - p) and coverage_levels
+    (the p of each pair); without Y_test those are None."""
+    res = dict(crps=None, pit=None, quantiles=out["quantiles"], levels=m["levels"], crps_mean=None, crps_mean_original_units=None,
+               coverage=None, coverage_levels=None)
+    if m["Y"] is not None:
+        crps, pit = out["crps"], out["pit"]
+        seen = ~np.isnan(m["Y"])
+        mean = float(np.sum(crps[seen]) / np.sum(seen)) if np.any(seen) else float("nan")
+        cov, low = _coverage(pit, seen, m["levels"])
+        res.update(crps=crps, pit=pit, crps_mean=mean, crps_mean_original_units=mean * float(Y_train_std), coverage=cov,
+                   coverage_levels=low)
+    return res
+
+
+def _score_points(who, x, K1, K2, steps, D, strides, CC, DD, log_Rchols, Y_test, levels, Y_train_std, targets_per_pass):
+    """The body of `rollout_score` and `particle_score`: x contiguous, component k = k1 * K2 + k2 at the strides given."""
+    if not 1 <= D <= SCORE_MAX_D_POINTS:
+        raise ValueError(f"{who}: 1 <= D <= {SCORE_MAX_D_POINTS} is needed, got {D}")
+    if x.size >= 2 ** 31:
+        raise ValueError(f"{who}: the stack holds {x.size} numbers: it must stay below 2^31")
+    m = _pack_score(who, K1 * K2, D, steps, CC, DD, log_Rchols, Y_test, levels, targets_per_pass)
+    out, args, work = _score_call(m, steps)
+    if work:
+        rc = _lib.load().ffvd_score_points(_lib.dptr(x), K1, K2, steps, D, *strides, *args)
+        _lib.check(rc, None, who)
+    return _score_dict(m, out, Y_train_std)
+
+
+def rollout_score(predict_x, CC, DD, log_Rchols, Y_test=None, *, levels=SCORE_LEVELS, Y_train_std=1.0, targets_per_pass=0):
+    """CRPS, PIT and predictive quantiles of the held-out predictive distribution of rollouts on the GPU (`ffvd_score_points`): the
+    sibling of `rollout_summary` on the stack the caller holds.  For row t and output j the distribution is the equal-weight mixture
+    of the K = N (or G R) Gaussians N(CC[:, j] . predict_x[k, t] + DD_j, sd_j^2), the mixture whose log density `rollout_summary`
+    returns as lpd.  With A(d, v) = E|N(d, v)|: crps = mean_k A(y - mu_k, v_k) - (1 / (2 K^2)) sum_kl A(mu_k - mu_l, v_k + v_l),
+    pit = F(y) with F the mixture's distribution function, quantiles[t, j, q] = the x with F(x) = levels[q] (for every row: they
+    need no target).  predict_x (N, steps, D) or (G, R, steps, D), D <= 32, K <= 65536; CC, DD, log_Rchols and Y_test
+    (n_test <= steps, J; NaN = unobserved) as `rollout_summary`; levels: at most 16 numbers in [1e-9, 1 - 1e-9]; targets_per_pass:
+    0 (automatic) or the number of targets whose pair sums share a pass of the scratch -- no result depends on it.  Returns the
+    dict of `_score_dict`: crps, pit, quantiles, levels, crps_mean, crps_mean_original_units, coverage, coverage_levels.  The stack
+    is not scanned for non-finite values: such a component makes the outputs of its row NaN and nothing else."""
+    who = "rollout_score"
+    px = _lib.as_f64(predict_x)
+    if px.ndim not in (3, 4):
+        raise ValueError(f"{who}: predict_x: expected (N, steps, D) or (G, R, steps, D), got {px.shape}")
+    steps, D = px.shape[-2:]
+    K = int(np.prod(px.shape[:-2]))
+    if K < 1 or steps < 1 or D < 1:
+        raise ValueError(f"{who}: at least one rollout, one step and one latent dim are needed, got {px.shape}")
+    return _score_points(who, px, K, 1, steps, D, (steps * D, 0, D), CC, DD, log_Rchols, Y_test, levels, Y_train_std, targets_per_pass)
+
+
+def particle_score(particles, CC, DD, log_Rchols, Y_test=None, *, levels=SCORE_LEVELS, Y_train_std=1.0, targets_per_pass=0):
+    """`rollout_score` on particle sets: particles (G, T, N, D), the layout of `fc_particles` of the particle forecasts with its
+    (origin, horizon) axes flattened and of the filters' `particles` with the record and row axes flattened.  Row t is scored by
+    the mixture of the K = G N particles' emissions, component k = g N + i; read through strides, no copy is made.  The other
+    parameters and the returned dict are `rollout_score`'s; the same components in the same order give the same bits in either
+    layout."""
+    who = "particle_score"
+    p = _lib.as_f64(particles)
+    if p.ndim != 4:
+        raise ValueError(f"{who}: particles: expected (G, T, N, D), got {p.shape}")
+    G, T, N, D = p.shape
+    if G < 1 or T < 1 or N < 1 or D < 1:
+        raise ValueError(f"{who}: at least one group, one row, one particle and one latent dim are needed, got {p.shape}")
+    return _score_points(who, p, G, N, T, D, (T * N * D, D, N * D), CC, DD, log_Rchols, Y_test, levels, Y_train_std, targets_per_pass)
+
+
+def moment_score(m_x, S_x, CC, DD, log_Rchols, Y_test=None, *, levels=SCORE_LEVELS, Y_train_std=1.0, targets_per_pass=0):
+    """`rollout_score` for Gaussian states (`ffvd_score_moments`): the sibling of `moment_summary`.  m_x (G, steps, D), S_x
+    (G, steps, D, D), D <= 8; row t and output j are scored by the mixture of the G Gaussians N(CC_j^T m_g + DD_j,
+    CC_j^T S_g CC_j + sd_j^2), the components of `moment_summary`'s lpd.  The other parameters and the returned dict are
+    `rollout_score`'s."""
+    who = "moment_score"
+    m, S = _lib.as_f64(m_x), _lib.as_f64(S_x)
+    if m.ndim != 3 or S.shape != m.shape + (m.shape[2],):
+        raise ValueError(f"{who}: expected m_x (G, steps, D) and S_x (G, steps, D, D), got {m.shape} and {S.shape}")
+    G, steps, D = m.shape
+    if G < 1 or steps < 1 or not 1 <= D <= MOMENT_MAX_D:
+        raise ValueError(f"{who}: at least one group, one step and 1 <= D <= {MOMENT_MAX_D} are needed, got {m.shape}")
+    if S.size >= 2 ** 31:
+        raise ValueError(f"{who}: G * steps * D * D = {S.size} must stay below 2^31")
+    s = _pack_score(who, G, D, steps, CC, DD, log_Rchols, Y_test, levels, targets_per_pass)
+    out, args, work = _score_call(s, steps)
+    if work:
+        rc = _lib.load().ffvd_score_moments(_lib.dptr(m), _lib.dptr(S), G, steps, D, *args)
+        _lib.check(rc, None, who)
+    return _score_dict(s, out, Y_train_std)
+
+
+def forecast_score(fan, Y_obs, CC, DD, log_Rchols, *, levels=SCORE_LEVELS, use="auto", Y_train_std=1.0):
+    """CRPS, PIT and predictive quantiles of a forecast fan: `fan` is the dict one of the six forecast functions returned with
+    return_tracks=True (m_fc, S_fc) or return_particles=True (fc_particles); Y_obs (n, J) is the record that was forecast.  The
+    targets are Y_obs[origins[b] + k], k = 1 .. h, as in that dict's curves.  use: "particles" scores the mixture of the G N
+    particles' emissions (`particle_score`), "moments" the mixture of the G per-group Gaussians (`moment_score`), "auto" the
+    particles when the fan has them, else the moments.  For the adapted rule fc_particles is the set AFTER the draw: its point
+    mixture is the sampled form of the Rao-Blackwellised predictive whose density that fan reports, and use="moments" scores the
+    per-chain Gaussians instead.  Returns a dict: crps, pit (B, h, J), NaN where the target is unobserved; quantiles (B, h, J, Q);
+    levels; crps_mean, crps_mean_original_units, coverage, coverage_levels over all observed targets; the curves over the origins
+    n_h (h, J), crps_h (h, J) and coverage_h (h, J, pairs), NaN where n_h = 0; origins; used ("moments" or "particles")."""
+    who = "forecast_score"
+    if use not in SCORE_USES:
+        raise ValueError(f"{who}: use: expected one of {list(SCORE_USES)}, got {use!r}")
+    if not isinstance(fan, dict) or "origins" not in fan:
+        raise ValueError(f"{who}: fan: expected the dict a forecast function returned (with origins)")
+    has_p, has_m = fan.get("fc_particles") is not None, fan.get("m_fc") is not None and fan.get("S_fc") is not None
+    if use == "particles" and not has_p:
+        raise ValueError(f"{who}: use=\"particles\" needs fc_particles: call the forecast with return_particles=True")
+    if use == "moments" and not has_m:
+        raise ValueError(f"{who}: use=\"moments\" needs m_fc and S_fc: call the forecast with return_tracks=True")
+    if not (has_p or has_m):
+        raise ValueError(f"{who}: fan holds neither fc_particles nor m_fc / S_fc: call the forecast with return_particles=True or "
+                         "return_tracks=True")
+    used = "particles" if (use == "particles" or (use == "auto" and has_p)) else "moments"
+    org = np.asarray(fan["origins"])
+    if org.ndim != 1 or org.size < 1 or not np.issubdtype(org.dtype, np.integer):
+        raise ValueError(f"{who}: fan[\"origins\"]: expected a non-empty vector of integers")
+    org, B = org.astype(np.int64), org.size
+    if used == "particles":
+        stack = _lib.as_f64(fan["fc_particles"])
+        if stack.ndim != 5 or stack.shape[1] != B:
+            raise ValueError(f"{who}: fc_particles: expected (G, {B}, h, N, D), got {stack.shape}")
+        G, _, h, N, D = stack.shape
+    else:
+        stack, S = _lib.as_f64(fan["m_fc"]), _lib.as_f64(fan["S_fc"])
+        if stack.ndim != 4 or stack.shape[1] != B or S.shape != stack.shape + (stack.shape[3],):
+            raise ValueError(f"{who}: expected m_fc (G, {B}, h, D) and S_fc (G, {B}, h, D, D), got {stack.shape} and {S.shape}")
+        G, _, h, D = stack.shape
+    Y = np.asarray(Y_obs, dtype=np.float64)
+    if Y.ndim == 1:
+        Y = Y[:, None]
+    if Y.ndim != 2:
+        raise ValueError(f"{who}: Y_obs: expected (n, J), got {Y.shape}")
+    if h < 1 or org[0] < 0 or np.any(np.diff(org) <= 0) or org[-1] + h > Y.shape[0] - 1:
+        raise ValueError(f"{who}: origins and horizon {h} do not fit a record of {Y.shape[0]} rows")
+    J = Y.shape[1]
+    Yt = Y[org[:, None] + 1 + np.arange(h)[None, :]]                                         # (B, h, J), as `_forecast_dict`
+    kw = dict(levels=levels, Y_train_std=Y_train_std)
+    if used == "particles":
+        r = particle_score(stack.reshape(G, B * h, N, D), CC, DD, log_Rchols, Yt.reshape(B * h, J), **kw)
+    else:
+        r = moment_score(stack.reshape(G, B * h, D), S.reshape(G, B * h, D, D), CC, DD, log_Rchols, Yt.reshape(B * h, J), **kw)
+    crps, pit = r["crps"].reshape(B, h, J), r["pit"].reshape(B, h, J)
+    seen = ~np.isnan(Yt)
+    n_h = np.sum(seen, axis=0).astype(np.int64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        crps_h = np.where(n_h > 0, np.sum(np.where(seen, crps, 0.0), axis=0) / n_h, np.nan)
+    coverage_h, _ = _coverage(pit, seen, r["levels"], axis=0)
+    r.update(crps=crps, pit=pit, quantiles=r["quantiles"].reshape(B, h, J, -1), n_h=n_h, crps_h=crps_h, coverage_h=coverage_h,
+             origins=org, used=used)
+    return r
+
+
 def pg_sweep(Lm_inverse_seq, Z, kern, U_val, X_ref, Y, control_inputs, CC, DD, Rchols, Q, x0, eps, unif):
     """One particle-Gibbs sweep over the latent trajectory: the INTENT of BaseModel.PG_for_X_speedup
     (base_model.py:78-138; the op as written never updates X, see include/ffvd_abi.h `ffvd_op_pg_sweep`).

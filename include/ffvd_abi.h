@@ -1539,6 +1539,33 @@ int  ffvd_op_pg_sweep(int kind, const double *Lm_inverse_seq, const double *Z, i
                       const double *Rchols, const double *log_Q, int n_free, const double *x0, const double *eps,
                       const double *unif, double *particles, int32_t *idx);
 
+/* CRPS, PIT and predictive quantiles of equal-weight Gaussian mixtures, for stacks the caller holds.  A target is (row t, output j);
+ * its predictive distribution is the mixture of K Gaussians N(mu_k, v_k), the components whose log density the summaries return as
+ * lpd.  With A(d, v) = d erf(d / sqrt(2 v)) + sqrt(2 v / pi) exp(-d^2 / (2 v)) and Phi the standard normal distribution function:
+ *   crps[t][j]         = (1/K) sum_k A(y - mu_k, v_k) - (1/(2 K^2)) sum_k sum_l A(mu_k - mu_l, v_k + v_l)
+ *   pit[t][j]          = F(y),  F(x) = (1/K) sum_k Phi((x - mu_k) / sqrt v_k)
+ *   quantiles[t][j][q] = the x with F(x) = levels[q]        (bisection to neighbouring doubles)
+ * crps, pit: n_test x J, NaN where Y_test is NaN; quantiles: steps x J x Q, for every row.  Each output may be NULL, at least one
+ * must not be; levels may be NULL with Q = 0 when quantiles is NULL.  The stacks are NOT scanned on the host: a component that is
+ * not finite makes the outputs of its targets NaN and nothing else.  K = 0 or steps = 0 returns FFVD_OK and touches nothing.
+ * Limits (FFVD_EINVAL, the message names the limit): 1 <= K <= 65536, 1 <= J <= 8, 0 <= Q <= 16, 1e-9 <= level <= 1 - 1e-9,
+ * 0 <= n_test <= steps, noise_std finite and positive, every index product below 2^31.  targets_per_pass: 0 (automatic) or the
+ * number of targets whose pair sums share one pass of the scratch; no result depends on it.
+ *
+ * ffvd_score_points: the components are points (rollouts, particle sets), mu_k = sum_d x[k][t][d] CC[d][j] + DD_j, v_k =
+ * noise_std[j]^2.  Component k = k1 * K2 + k2 (K = K1 * K2), row t, lies at x + k1 * stride_k1 + k2 * stride_k2 + t * stride_t
+ * (strides in doubles, D contiguous): [K][steps][D] is K1 = K, K2 = 1, stride_k1 = steps * D, stride_t = D; [G][T][N][D] is
+ * K1 = G, K2 = N, stride_k1 = T * N * D, stride_k2 = D, stride_t = N * D.  D <= 32. */
+int  ffvd_score_points(const double *x, int K1, int K2, int steps, int D, long long stride_k1, long long stride_k2, long long stride_t,
+                       const double *CC, const double *DD, const double *noise_std, int J, const double *Y_test, int n_test,
+                       const double *levels, int Q, int targets_per_pass, double *crps, double *pit, double *quantiles);
+
+/* The same for Gaussian states (m_x G x steps x D, S_x G x steps x D x D): mu_g = CC_j^T m[g][t] + DD_j, v_g = CC_j^T S[g][t] CC_j +
+ * noise_std[j]^2, as ffvd_op_moment_summary; K = G.  D <= 8. */
+int  ffvd_score_moments(const double *m_x, const double *S_x, int G, int steps, int D, const double *CC, const double *DD,
+                        const double *noise_std, int J, const double *Y_test, int n_test, const double *levels, int Q,
+                        int targets_per_pass, double *crps, double *pit, double *quantiles);
+
 #ifdef __cplusplus
 }
 #endif
